@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — DiT denoising steps/sec of the MI355X engine on BASELINE.json's metric/config.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one process per GPU under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment, the reference's launch
 contract: README.md:269-276, kandinsky/utils.py:40-55).  Called WITHOUT that environment, `python bench.py --gpus N` launches itself:
@@ -311,7 +311,12 @@ def main():
                          "data-derived softmax bound past the fixed-offset window")
     ap.add_argument("--nabla-p", type=float, default=0.9, help="NABLA cumulative-mass threshold P (config: 0.9); with random weights the "
                     "block softmax is near uniform, so kept density ~ P: 0.0 = STA window only, 0.15 ~ 20 %% density")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what they returned (the fp32 latent) as DIR/latent.npy, so that two builds can be compared "
+                         "output for output (the inputs depend only on the arguments)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if args.oversubscribe:
         os.environ["K5_OVERSUBSCRIBE"] = "1"
@@ -348,6 +353,8 @@ def main():
     wl = WORKLOADS[args.workload]
     T, H, W = wl["latent"]
     N, L = T * (H // 2) * (W // 2), wl["L"]
+    # the configs' 50-step schedule; a run of more warm-up + timed steps stretches it, so that every one of --steps is a real Euler step
+    nfe_steps = max(50, args.warmup + args.steps)
     cfgd = dict(LITE, num_visual_blocks=args.blocks)
     with torch.device("meta"):
         dit = DiffusionTransformer3D(**cfgd)
@@ -361,7 +368,7 @@ def main():
         if cname is None:
             raise SystemExit("--magcache needs a 50-step workload (5s_nocfg, 5s_sft, 10s_nabla)")
         dit.engine(dev)
-        set_magcache_params(dit, default_configs()[cname]["magcache"]["mag_ratios"], 50, abs(wl["w"] - 1.0) <= 1e-6)
+        set_magcache_params(dit, default_configs()[cname]["magcache"]["mag_ratios"], nfe_steps, abs(wl["w"] - 1.0) <= 1e-6)
     if args.fp8:
         dit.set_fp8(int(args.fp8))
     sp_world = world
@@ -398,7 +405,6 @@ def main():
     vpos = [torch.arange(T), torch.arange(H // 2), torch.arange(W // 2)]
     tpos, ntpos = torch.arange(L), torch.arange(wl["Lnull"])
     from kandinsky.generation_utils import sigma_schedule
-    nfe_steps = 50
     sig = sigma_schedule(nfe_steps, 5.0).tolist()
 
     sparse = None
@@ -421,7 +427,7 @@ def main():
     parity = None
     if (args.workload == "5s_nocfg" and args.blocks == 32 and args.qk_gain == 1.0 and not args.fp8 and args.emulate_shard <= 1
             and not args.magcache and not args.no_parity_check):
-        parity = parity_check(dit, noise, dev, sig, te, ne, vpos, tpos, ntpos, wl, sparse)
+        parity = parity_check(dit, noise, dev, sigma_schedule(50, 5.0).tolist(), te, ne, vpos, tpos, ntpos, wl, sparse)   # the golden's NFE 50
     if args.warmup > 0:
         run(0, args.warmup)
     barrier()
@@ -437,6 +443,10 @@ def main():
     # (workload, warm-up + steps) — 512 samples of (latent - noise) + its sum of squares, produced by this engine on an MI355X and tied to
     # the reference through parity_check (same model, same noise, first two steps) and tests/test_gpu_fulldepth.py
     pin = latent_pin(latent, noise, args, world)
+    if args.dump_outputs and rank == 0:   # every rank holds the same latent (rank_check); fp32, 60 MB at most (the 10s_hd latent)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latent.npy"), latent.cpu().numpy())
     if world > 1:
         tt = torch.tensor([dt], device="cpu" if host_group else dev, dtype=torch.float64)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_command_line_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs"):
         assert flag in out.stdout
 
 
@@ -95,6 +95,24 @@ def test_bench_json_line_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "steps/s" and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
     assert d["value"] / c["value"] > 10.0          # sanity only: the ratio says nothing about kernel quality
+
+
+@pytest.mark.gpu
+def test_bench_times_every_step_asked_for_and_dumps_its_outputs(tmp_path):
+    """--steps is the number of timed Euler steps even where warm-up + steps run past the configs' 50-step schedule, and --dump-outputs
+    writes the latent those steps returned as fp32 .npy."""
+    import numpy as np
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a real MI355X (torch.cuda.is_available() is False)")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "48", "--blocks", "2",
+                          "--no-vae", "--no-breakdown", "--no-cpu-baseline", "--no-parity-check", "--no-live-traffic",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    r = d.get("roofline_attention") or d["roofline"]
+    assert d["steps"] == 4 and r["blocks_run"] == 4 * 2, (d["steps"], r["blocks_run"])
+    lat = np.load(tmp_path / "latent.npy")
+    assert lat.dtype == np.float32 and lat.shape == (31, 64, 96, 16) and np.isfinite(lat).all()
 
 
 @pytest.mark.gpu
