@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("K5_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libk5.so"))
 
 K5_OK = 0
-ABI_VERSION = 8          # include/k5.h K5_ABI_VERSION
+ABI_VERSION = 9          # include/k5.h K5_ABI_VERSION
 K5_F32, K5_BF16, K5_F16 = 0, 1, 2
 EPI_BIAS, EPI_BIAS_M, EPI_GELU, EPI_GATE = 0, 1, 2, 3
 
@@ -249,7 +249,9 @@ def _need_cuda(*ts):
 
 def gemm(a, w, bias=None, epilogue=EPI_BIAS, resid=None, gate=None, out=None, kernel=0, token_tile=0):
     """out[M,N] = a[M,K] @ w[N,K]^T (+bias) with fused epilogue. a, w bf16; bias/gate fp32.
-    kernel / token_tile != 0: the named kernel / tile height (k5_gemm_bf16_variant; tests and A/B tools)."""
+    kernel / token_tile != 0: the named kernel / tile height (k5_gemm_bf16_variant; tests and A/B tools): kernel 2 = 128 x 128 tiles,
+    4 = the four-wave persistent kernel, 8 = the eight-wave kernel; any other kernel id raises.  token_tile 128 / 192 / 256 = rows of the
+    four-wave kernel's workgroup tile."""
     _need_cuda(a, w, bias, resid, gate)
     M, K = a.shape
     N = w.shape[0]

@@ -275,7 +275,7 @@ def test_hot_kernels_keep_their_register_budget():
 
 def test_gemm_accumulators_stay_invisible_to_the_compiler():
     """Round 6: the four-wave GEMM keeps its accumulators in PHYSICAL AGPRs that only its own asm statements name (a[4 q : 4 q + 3] in the MFMA text,
-    v_accvgpr_read in the epilogue, global_store from the AGPR file in the split-K tail's helper path) — the register allocator never sees them, which is
+    v_accvgpr_read in the epilogue) — the register allocator never sees them, which is
     what lets a second consumer of the accumulators exist at all (rounds 2-5: 150-500 spilled registers).  That only works while the COMPILER never
     touches an AGPR of its own accord (a VGPR spilled into the AGPR file would land on an accumulator).  This compiles the kernel to ISA and demands:
     no AGPR mentioned outside an inline-asm block, every MFMA of a kernel on its own quads with C = 0 or C = D, all 8 MT quads read back by the epilogue."""
