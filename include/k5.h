@@ -31,7 +31,7 @@ typedef enum { K5_EPI_BIAS = 0, K5_EPI_BIAS_M = 1, K5_EPI_GELU = 2, K5_EPI_GATE 
 
 /* bumped whenever an entry point is added or changes meaning; the host binding checks it BEFORE binding symbols, so that a stale
  * libk5.so fails with a clear message instead of a missing-symbol lookup (round 3: 4) */
-#define K5_ABI_VERSION 9
+#define K5_ABI_VERSION 10
 int k5_abi_version(void);
 const char* k5_last_error(void);
 
@@ -382,6 +382,17 @@ int k5_dit_get_option(k5_dit* dit, const char* name, int* value);
  * bytes and GB/s ("{}" before the first tuning run); returns the text length, copies at most len - 1 characters + NUL (buf may be null).
  * k5_sp_pick_schedule: the selection rule alone (host arithmetic, no GPU): times[rank * ncand + cand] in ms, <= 0 / non-finite = did not
  * run on that rank; valid (nullable) masks candidates; returns the chosen candidate or -1, max-over-ranks per candidate in cost_out. */
+/* Two-level sequence parallelism (ABI 10; "sp_mode" 2, or K5_SP_MODE=2 in the environment of the ranks at communicator init — an explicit
+ * k5_dit_set_option still wins): G = gcd(heads, ranks) head groups x ranks / G query splits, for rank counts that do not divide the heads
+ * (28 heads at 6 or 8 ranks).  Rank r attends head group r % G for the queries of the G consecutive token shards of ranks (r / G) G ..
+ * (r / G) G + G - 1 against all keys, in one pass; k' and V^T reach every rank by one exchange over the whole world, q and the attention
+ * output change hands inside the split.  G = ranks runs Ulysses ("sp_mode" 1), G = 1 and NABLA the all-gather; "sp_mode_used" (read-only)
+ * says which schedule the last sharded forward ran (0 gather, 1 Ulysses, 2 two-level; -1 none yet).  The q | k | V^T projections stay bf16.
+ * k5_sp_plan_2d: the exchange plan every rank derives from (heads, ranks, rows_pad, dim), host arithmetic only.  which: 0 k', 1 V^T, 2 q,
+ * 3 attention output; table (nullable) gets ranks x ranks entries of three int64, table[(src * ranks + dst) * 3 + {0, 1, 2}] = offset in
+ * src's send buffer, offset in dst's receive buffer, bytes (0 = nothing between the two).  Returns the schedule "sp_mode" 2 runs at
+ * (heads, ranks) — 2 two-level, 1 Ulysses, 0 gather — with G in *groups (nullable), or -K5_ERR_ARG. */
+int k5_sp_plan_2d(int heads, int ranks, int rows_pad, int dim, int which, int* groups, long long* table);
 int k5_dit_sp_schedule(k5_dit* dit, char* buf, int len);
 int k5_sp_pick_schedule(const float* times, int ncand, int world, const int* valid, float* cost_out);
 /* (block, head) self-attention launches that took the fixed-offset / the online-max softmax since the last reset. */

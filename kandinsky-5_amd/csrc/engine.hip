@@ -273,7 +273,70 @@ struct Comm {
     if (r != ncclSuccess) { k5_set_error("ncclSend/ncclRecv group: %s", GetErrorString(r)); return K5_ERR_HIP; }
     return K5_OK;
   }
+  // planned exchange (two-level schedule, sp_plan_2d): tab[src * world + dst] = (offset in src's `send`, offset in dst's `recv`, bytes) — the
+  // same table on every rank; 0 bytes = the pair has nothing to trade (peers outside a sub-group).  Every rank of the world issues every call.
+  // The rank's own entry is a device-to-device copy; RCCL: grouped send / recv to the listed peers only; loopback / IPC: pull copies.
+  int exchange(const void* send, void* recv, const k5ipc::Xfer* tab, hipStream_t s) {
+    const char* sb = (const char*)send; char* rb = (char*)recv;
+    const k5ipc::Xfer& me = tab[(size_t)rank * world + rank];
+    if (me.bytes > 0) HIPCHK(hipMemcpyAsync(rb + me.recv_off, sb + me.send_off, (size_t)me.bytes, hipMemcpyDeviceToDevice, s));
+    if (world == 1) return K5_OK;
+    if (ipc) return ipc_status(ipc->exchange(send, recv, tab, s));
+    if (loop) {
+      loop->ptr[rank] = const_cast<void*>(send);
+      HIPCHK(hipEventRecord(loop->ready[rank], s));
+      pthread_barrier_wait(&loop->bar);
+      for (int p = 0; p < world; ++p) {
+        const k5ipc::Xfer& e = tab[(size_t)p * world + rank];
+        if (p == rank || e.bytes <= 0) continue;
+        HIPCHK(hipStreamWaitEvent(s, loop->ready[p], 0));
+        HIPCHK(hipMemcpyAsync(rb + e.recv_off, (const char*)loop->ptr[p] + e.send_off, (size_t)e.bytes, hipMemcpyDeviceToDevice, s));
+      }
+      HIPCHK(hipEventRecord(loop->pulled[rank], s));
+      pthread_barrier_wait(&loop->bar);
+      for (int p = 0; p < world; ++p)
+        if (p != rank) HIPCHK(hipStreamWaitEvent(s, loop->pulled[p], 0));
+      return K5_OK;
+    }
+    if (!can_exchange()) { k5_set_error("RCCL library lacks ncclSend / ncclRecv / ncclGroup*"); return K5_ERR_STATE; }
+    ncclResult_t r = GroupStart();
+    for (int p = 0; p < world && r == ncclSuccess; ++p) {
+      if (p == rank) continue;
+      const k5ipc::Xfer& out = tab[(size_t)rank * world + p];
+      const k5ipc::Xfer& in = tab[(size_t)p * world + rank];
+      if (out.bytes > 0) r = Send(sb + out.send_off, (size_t)out.bytes, ncclUint8, p, comm, s);
+      if (r == ncclSuccess && in.bytes > 0) r = Recv(rb + in.recv_off, (size_t)in.bytes, ncclUint8, p, comm, s);
+    }
+    const ncclResult_t e = GroupEnd();
+    if (r == ncclSuccess) r = e;
+    if (r != ncclSuccess) { k5_set_error("ncclSend/ncclRecv group (planned exchange): %s", GetErrorString(r)); return K5_ERR_HIP; }
+    return K5_OK;
+  }
 };
+
+// ---- the two-level schedule's exchange plan ("sp_mode" = 2; run_self_attention_2d) ----
+// G = gcd(heads, P) head groups of Hp = heads / G heads (Dp = D / G columns); S = P / G query splits.  Rank r serves head group r % G for the
+// queries of split r / G = the token shards of ranks sG .. sG + G - 1 (one contiguous token range).  Every block below is rows_pad x Dp bf16.
+//   SP_K   k' of the rank's rows, send [G][rows_pad][Dp] (block = head group) -> every peer p gets block g(p); recv [P][rows_pad][Dp] = token order
+//   SP_VT  V^T, send [D][rows_pad] as the GEMM writes it (rows g Dp .. = block g) -> every peer p gets block g(p); recv [P][Dp][rows_pad]
+//   SP_Q   q, send [G][rows_pad][Dp] -> only the ranks of the split: block g(p) to p; recv [G][rows_pad][Dp] = the split's rows of my heads
+//   SP_O   attention output, send [G][rows_pad][Dp] (block j = rows of rank sG + j) -> back inside the split; recv [G][rows_pad][Dp] (block = head group)
+enum { SP_K = 0, SP_VT = 1, SP_Q = 2, SP_O = 3 };
+int sp_gcd(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
+// fills tab[src * P + dst]; returns G (0 on bad arguments)
+int sp_plan_2d(int H, int P, int rows_pad, int D, int which, k5ipc::Xfer* tab) {
+  if (H <= 0 || P <= 0 || rows_pad <= 0 || D <= 0 || D % H || which < SP_K || which > SP_O) return 0;
+  const int G = sp_gcd(H, P), Dp = D / G;
+  const long long B = (long long)rows_pad * Dp * 2;
+  for (int src = 0; src < P; ++src)
+    for (int dst = 0; dst < P; ++dst) {
+      k5ipc::Xfer& e = tab[(size_t)src * P + dst];
+      if (which == SP_K || which == SP_VT) e = k5ipc::Xfer{(dst % G) * B, src * B, B};
+      else if (src / G == dst / G) e = k5ipc::Xfer{(dst % G) * B, (src % G) * B, B};
+      else e = k5ipc::Xfer{0, 0, 0};
+    }
+  return G;
+}
 
 }  // namespace
 
@@ -372,6 +435,12 @@ struct k5_dit {
   int sp_mode = 0;                                 // "sp_mode": 0 = K / V^T all-gather (any rank count), 1 = Ulysses all-to-all (heads % ranks == 0, dense attention)
   DevBuf ws_u_send, ws_u_recv, ws_u_vsend, ws_u_vrecv, ws_u_o, ws_u_orecv, ws_u_stats;   // Ulysses exchange buffers
   hipEvent_t ev_u_o = nullptr, ev_u_back = nullptr;
+  // two-level schedule ("sp_mode" = 2, run_self_attention_2d): the split's queries of the rank's head group, and the exchange plans of the
+  // current shape (sp_plan_2d: SP_K, SP_VT, SP_Q, SP_O) — the other buffers are the Ulysses ones, grown to this schedule's sizes
+  DevBuf ws_u_qrecv;
+  std::vector<k5ipc::Xfer> sp_plan[4];
+  int sp_plan_key[2] = {0, 0};                     // (world, rows_pad) the plans were made for
+  int sp_mode_used = -1;                           // "sp_mode_used" (read-only): schedule of the last sharded forward (0 gather, 1 Ulysses, 2 two-level; -1 none yet)
   hipEvent_t ev_slice[4] = {};                     // slice s of every peer has landed
   bool emulated = false;                           // "emulate_world": timing-only layout, results are garbage
   bool last_nabla = false;                         // attention type of the last forward ("fp8_effective": Ulysses, which keeps q | k | V^T in bf16, is a dense-attention schedule)
@@ -1135,6 +1204,124 @@ int run_self_attention_ulysses(k5_dit* d, hipStream_t s, const AttnW& a, const v
   return K5_OK;
 }
 
+// Two-level sequence parallelism ("sp_mode" = 2): Ulysses needs heads % P == 0, which 28 heads at P = 8 (or 6) miss.  With G = gcd(heads, P)
+// head groups and S = P / G query splits, rank r attends head group g = r % G for the queries of split s = r / G (the G consecutive token
+// shards of ranks sG .. sG + G - 1) against all N keys in ONE pass — the one-GPU attention, no fp32 state between passes, as in Ulysses:
+//   1. q | k projection and norm + RoPE of the rank's rows as in Ulysses (|q|^2 / |k'|^2 maxima gathered over the world: the S ranks of a head
+//      group take the same softmax form, decided from all N rows); one pass packs q and k' into per-head-group send planes (sp2d_pack_qk)
+//   2. k' and V^T by one exchange over the whole world, fan-out: every peer gets the block of ITS head group (no copy per destination);
+//      received in token order, [P][rows_pad][Dp] / [P][Dp][rows_pad] — the chunked layout the Ulysses attention launch reads
+//   3. q by an exchange inside the split: [G][rows_pad][Dp] = the split's rows of my heads
+//   4. attention: Hp heads, the split's rows x all N keys (anchored offsets sampled around each row's own block, as in Ulysses)
+//   5. o back inside the split, unpacked as in Ulysses with G head groups, gated out-projection.
+// Per rank and block (P = 8, G = 4, config 2) 107 MB arrive instead of the gather's 299 MB.  Callers: G = 1 -> gather,
+// G = P -> Ulysses (sp_schedule); the same routine does both ends correctly, they are simply not this schedule's business.
+int run_self_attention_2d(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, int rows, int rows_pad, int N, void* o,
+                          const float* cosT, const float* sinT, void* resid, const float* gate, int pref_slot = 0) {
+  const int D = d->D, H = d->Hh, P = d->sp_world, r = d->sp_rank;
+  const int G = sp_gcd(H, P), Hp = H / G, Dp = D / G, g = r % G, sp = r / G;
+  const int q0 = sp * G * rows_pad, Ms = std::min(N, q0 + G * rows_pad) - q0;   // the split's token rows [q0, q0 + Ms)
+  if (Ms <= 0) { k5_set_error("internal: two-level split without rows"); return K5_ERR_STATE; }
+  if (d->sp_plan_key[0] != P || d->sp_plan_key[1] != rows_pad) {
+    for (int w = SP_K; w <= SP_O; ++w) { d->sp_plan[w].resize((size_t)P * P); sp_plan_2d(H, P, rows_pad, D, w, d->sp_plan[w].data()); }
+    d->sp_plan_key[0] = P; d->sp_plan_key[1] = rows_pad;
+  }
+  const size_t blk = (size_t)rows_pad * Dp * 2;   // bytes of one exchange block
+  const bool by_data = d->attn_mode == K5_ATTN_AUTO;
+  K5CHK(d->ws_qk.ensure((size_t)rows * 2 * D * 2));
+  K5CHK(d->ws_u_send.ensure(2 * G * blk));                       // q plane [G][rows_pad][Dp] | k' plane [G][rows_pad][Dp]
+  K5CHK(d->ws_u_recv.ensure(P * blk));                           // k' of all N rows, my heads
+  K5CHK(d->ws_u_vsend.ensure((size_t)D * rows_pad * 2)); K5CHK(d->ws_u_vrecv.ensure(P * blk));
+  K5CHK(d->ws_u_qrecv.ensure(G * blk));
+  K5CHK(d->ws_u_o.ensure(G * blk)); K5CHK(d->ws_u_orecv.ensure(G * blk));
+  K5CHK(ensure_zeroed(d->ws_u_stats, (size_t)P * 2 * H * 4, s));
+  if (!d->ev_u_o) { HIPCHK(hipEventCreateWithFlags(&d->ev_u_o, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&d->ev_u_back, hipEventDisableTiming)); }
+  if (by_data) K5CHK(ensure_attn_flags(d, s));
+  float* ustats = d->ws_u_stats.as<float>();         // [P][2 H], as in Ulysses
+  if (by_data) HIPCHK(hipMemsetAsync(ustats + (size_t)r * 2 * H, 0, (size_t)2 * H * 4, s));
+  bf16_t* qk = d->ws_qk.as<bf16_t>();
+  bf16_t* qsend = d->ws_u_send.as<bf16_t>();
+  bf16_t* ksend = qsend + (size_t)G * rows_pad * Dp;
+  {
+    Scope sc(d, s, "gemm");
+    K5CHK(k5_launch_gemm_bf16(h, a.wqk.p, a.bqk.as<float>(), qk, rows, 2 * D, D, D, D, 2 * D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+  }
+  {
+    Scope sc(d, s, "elementwise");
+    const int32_t hc[2] = {H, 2 * H};
+    K5CHK(k5_launch_rmsnorm_rope(qk, a.norm.as<float>(), cosT, sinT, rows, 2 * H, 2 * D, hc, s, K5_SOFTMAX_C, H, nullptr, 0,
+                                 by_data ? ustats + (size_t)r * 2 * H : nullptr, d->ws_attn_part.as<float>()));
+    K5CHK(k5_launch_sp2d_pack_qk(qk, qsend, ksend, rows, rows_pad, D, G, s));
+  }
+  HIPCHK(hipEventRecord(d->ev_k, s));
+  hipStream_t cs = d->comm_stream;
+  HIPCHK(hipStreamWaitEvent(cs, d->ev_k, 0));
+  {
+    Scope sc(d, cs, "comm");   // the same collectives in the same order on every rank: stats, k', q, V^T, o
+    if (by_data) { K5CHK(d->comm.all_gather_inplace(ustats, (size_t)2 * H, 4, cs)); HIPCHK(hipEventRecord(d->ev_stats, cs)); }
+    K5CHK(d->comm.exchange(ksend, d->ws_u_recv.p, d->sp_plan[SP_K].data(), cs));
+    K5CHK(d->comm.exchange(qsend, d->ws_u_qrecv.p, d->sp_plan[SP_Q].data(), cs));
+  }
+  {
+    Scope sc(d, s, "gemm");   // V^T of the rank's rows while k' / q travel
+    K5CHK(k5_launch_gemm_bf16(a.wv.p, h, a.bv.as<float>(), d->ws_u_vsend.p, D, rows, D, D, D, rows_pad, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
+  }
+  HIPCHK(hipEventRecord(d->ev_v, s));
+  HIPCHK(hipStreamWaitEvent(cs, d->ev_v, 0));
+  {
+    Scope sc(d, cs, "comm");
+    K5CHK(d->comm.exchange(d->ws_u_vsend.p, d->ws_u_vrecv.p, d->sp_plan[SP_VT].data(), cs));
+  }
+  HIPCHK(hipEventRecord(d->ev_gathered, cs));
+  const int* hflags = nullptr;
+  const float* kmax = nullptr;
+  int* pref = nullptr;
+  if (by_data) {   // flags of MY head group from every rank's maxima (all N rows)
+    HIPCHK(hipStreamWaitEvent(s, d->ev_stats, 0));
+    hflags = d->ws_attn_flags.as<int>();
+    float* kmax_w = d->row_offsets ? d->ws_attn_flags.as<float>() + H : nullptr;
+    kmax = kmax_w;
+    if (kmax_w) { K5CHK(ensure_zeroed(a.pref, (size_t)2 * H * 4, s)); pref = a.pref.as<int>() + (size_t)pref_slot * H + (size_t)g * Hp; }
+    K5CHK(k5_launch_attn_flags(ustats + (size_t)g * Hp, ustats + H + (size_t)g * Hp, P, 2 * H, Hp, 0, d->ws_attn_flags.as<int>(),
+                               d->ws_attn_cnt.as<unsigned long long>(), s, kmax_w, pref, nullptr, nullptr, P, 2 * H, kmax_w && d->anchor));
+  }
+  HIPCHK(hipStreamWaitEvent(s, d->ev_gathered, 0));
+  const bf16_t* qs = d->ws_u_qrecv.as<bf16_t>();
+  const bf16_t* kall = d->ws_u_recv.as<bf16_t>();
+  K5CHK(d->ws_attn_bal.ensure(k5_attention_balance_bytes(Hp, Ms)));
+  K5KeyCentre kcen{nullptr, nullptr, nullptr};
+  if (kmax && d->anchor) {   // anchored offsets: each query row's own 64-token block sits at key index q0 + row
+    K5CHK(d->ws_attn_anchor.ensure((size_t)Hp * Ms * 4));
+    Scope sc(d, s, "elementwise");
+    K5CHK(k5_launch_attn_row_anchor(qs, kall, Hp, Ms, N, Dp, Dp, q0, N, kmax, d->ws_attn_anchor.as<float>(), s));
+    kcen.row_anchor = d->ws_attn_anchor.as<float>();
+  }
+  {
+    Scope sc(d, s, "attn_self");
+    K5CHK(k5_launch_attention_bf16_range(qs, kall, d->ws_u_vrecv.p, d->ws_u_o.p, Hp, Ms, N, Dp, Dp, rows_pad, Dp, 0.f, rows_pad,
+                                         (long long)Dp * rows_pad, 0, -1, 0x7fffffff, 0, nullptr, 0, s, d->ws_attn_bal.as<float>(), true, hflags,
+                                         d->attn_mode, nullptr, kmax, 0, nullptr, kcen.row_anchor ? &kcen : nullptr));
+  }
+  if (kmax) K5CHK(k5_launch_attn_pref_update(d->ws_attn_bal.as<float>(), Hp, Ms, 4, pref, s));
+  HIPCHK(hipEventRecord(d->ev_u_o, s));
+  HIPCHK(hipStreamWaitEvent(cs, d->ev_u_o, 0));
+  {
+    Scope sc(d, cs, "comm");
+    K5CHK(d->comm.exchange(d->ws_u_o.p, d->ws_u_orecv.p, d->sp_plan[SP_O].data(), cs));
+  }
+  HIPCHK(hipEventRecord(d->ev_u_back, cs));
+  HIPCHK(hipStreamWaitEvent(s, d->ev_u_back, 0));
+  {
+    Scope sc(d, s, "elementwise");
+    K5CHK(k5_launch_ulysses_unpack_o(d->ws_u_orecv.p, o, rows, rows_pad, D, G, s));
+  }
+  {
+    Scope sc(d, s, "gemm");
+    K5CHK(k5_launch_gemm_bf16(o, a.wo.p, a.bo.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s));
+  }
+  return K5_OK;
+}
+
 // keys and V^T of every visual block's cross-attention from the text stream (k5_dit::cross_kv_batched): ws_ck_all [L][blocks * D] (normalised
 // keys), ws_cvt_all [blocks * D][rup(L, 8)].  The key projection is the launch it was per block (128 x 128 tiles for 256 rows); the V^T one is forced
 // onto the same 128 x 128 kernel the per-block call took (57 344 weight rows would otherwise pick a 256-row kernel: another summation order).
@@ -1441,6 +1628,21 @@ int sp_autotune_run(k5_dit* d, hipStream_t s, int N, int L, const NablaArgs* nab
   return K5_OK;
 }
 
+// which self-attention schedule a sharded forward runs (0 gather, 1 Ulysses, 2 two-level): the dispatch's predicate, shared with "fp8_effective".
+// "sp_mode" 2 runs Ulysses where G = gcd(heads, P) = P, the gather where G = 1; NABLA and the timing-only layout keep the gather as under "sp_mode" 1,
+// except that the two-level schedule does run under "emulate_world" (rank 0's layout, collectives move nothing: its per-rank compute).
+int sp_schedule(const k5_dit* d, bool nabla) {
+  const int P = d->sp_world, H = d->Hh;
+  if (!d->comm.active() || P <= 1 || nabla) return 0;
+  if (d->sp_mode == 1) return (H % P == 0 && !d->emulated) ? 1 : 0;
+  if (d->sp_mode == 2) {
+    const int G = sp_gcd(H, P);
+    if (G == P) return d->emulated ? 0 : 1;
+    return G > 1 ? 2 : 0;
+  }
+  return 0;
+}
+
 int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, float time, const float* x,
                  int x_channels, void* out_velocity, hipStream_t s, const float* tvec = nullptr, const int* step = nullptr,
                  int text_slot = -1) {
@@ -1585,18 +1787,22 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   const bool cx_all = !mag_skip && d->cross_kv_batched && c.num_visual_blocks > 1 && d->cx_wk_all.p;
   if (cx_all) K5CHK(cross_kv_batched_run(d, s, d->ws_text.p, L));
   const int Lr8 = (int)rup(L, 8);
+  const int sched = sp ? sp_schedule(d, nabla) : 0;
+  if (sp) d->sp_mode_used = sched;
   for (int i = 0; i < (mag_skip ? 0 : c.num_visual_blocks); ++i) {
     const BlockW& b = d->vblocks[i];
     const float* m = mod + b.mod_off;
     const float* vcos = d->ws_vcos.as<float>() + (size_t)tok0 * 32;
     const float* vsin = d->ws_vsin.as<float>() + (size_t)tok0 * 32;
-    const bool ulysses = sp && d->sp_mode == 1 && !nabla && d->sp_world > 1 && d->Hh % d->sp_world == 0 && !d->emulated;
+    const bool ulysses = sched == 1, two_level = sched == 2;
     // fp8 modes: the LayerNorm writes the e4m3 rows the projections read (no bf16 h, no quantisation pass) — "fp8_fuse_ln" = 0 keeps the two passes
-    const bool h8_sa = d->fp8_fuse_ln && !ulysses && (sp ? sa_sp_fp8_in(d, b.self_attn, n, n_pad, nabla) : sa_fp8_in(d, b.self_attn, n));
+    const bool h8_sa = d->fp8_fuse_ln && sched == 0 && (sp ? sa_sp_fp8_in(d, b.self_attn, n, n_pad, nabla) : sa_fp8_in(d, b.self_attn, n));
     K5CHK(ln_mod(d, s, d->ws_vis.p, m, d->ws_h.p, n, h8_sa));
     if (d->profiling) ++d->prof_self_blocks;   // bench.py: FLOPs of the roofline kernel = per-block FLOPs x the blocks that RAN
     if (ulysses) {
       K5CHK(run_self_attention_ulysses(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, text_slot > 0 ? 1 : 0));
+    } else if (two_level) {
+      K5CHK(run_self_attention_2d(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, text_slot > 0 ? 1 : 0));
     } else if (sp) {
       K5CHK(run_self_attention_sp(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, nabla ? &na : nullptr, text_slot > 0 ? 1 : 0, h8_sa));
     } else {
@@ -2071,6 +2277,12 @@ extern "C" int k5_comm_unique_id(const char* rccl_lib_path, void* out128) {
 static int comm_common_init(k5_dit* d, int rank, int world) {
   d->comm.rank = rank; d->comm.world = world;
   if (const char* e = getenv("K5_SP_AUTOTUNE")) d->sp_autotune = atoi(e) != 0;   // K5_SP_AUTOTUNE=1: time the admissible exchanges at the first sharded forward (opt-in)
+  const char* spm = (d->sp_user_set & 1) ? nullptr : getenv("K5_SP_MODE");
+  if (const char* e = spm) {   // K5_SP_MODE=0/1/2: the schedule of "sp_mode" from the launch line (k5_dit_set_option, before or after, wins)
+    const int v = atoi(e);
+    if (v < 0 || v > 2 || !e[0]) { k5_set_error("K5_SP_MODE must be 0, 1 or 2 (got '%s')", e); return K5_ERR_ARG; }
+    d->sp_mode = v; d->sp_user_set |= 1;
+  }
   if (d->comm.loop) d->sp_autotune = false;   // loopback ranks (tests of specific schedules on one GPU) tune only when asked to ("sp_autotune" = 1)
   d->sp_rank = rank; d->sp_world = world;
   HIPCHK(hipStreamCreateWithFlags(&d->comm_stream, hipStreamNonBlocking));
@@ -2219,7 +2431,10 @@ extern "C" int k5_dit_cfg_pair_init_ipc(k5_dit* d, const char* shm_name, int bra
 //                     rank's own key blocks while the other ranks' keys travel, the rest after the gather (costs 12 % of the attention
 //                     in compute, emulated P = 4; pays when the exposed part of the gather is longer than that — a property of the node)
 //   "sp_mode"         0 (default): every rank gathers all K / V^T (any rank count, dense and NABLA); 1: Ulysses — two all-to-alls trade token rows
-//                     for heads and back (run_self_attention_ulysses; needs heads % ranks == 0 and dense attention, else the gather is used)
+//                     for heads and back (run_self_attention_ulysses; needs heads % ranks == 0 and dense attention, else the gather is used);
+//                     2: two-level — G = gcd(heads, ranks) head groups x ranks / G query splits (run_self_attention_2d; dense attention; G = ranks
+//                     runs Ulysses, G = 1 the gather).  K5_SP_MODE=0/1/2 sets it at communicator init; this call still wins.
+//   "sp_mode_used"    (read-only) what the last sharded forward ran: 0 gather, 1 Ulysses, 2 two-level (-1: none yet)
 //   "sp_autotune"     0 (default since round 5) / 1: the first sharded forward of a handle with more than one rank times one block's self-attention section under
 //                     every admissible schedule (all-gather; 2 slices; Ulysses — NABLA: one / two passes) and keeps the fastest (max over ranks; every
 //                     rank takes the same decision from the gathered table).  A knob set explicitly through this call is left alone, and a run only assigns
@@ -2240,7 +2455,7 @@ extern "C" int k5_dit_set_option(k5_dit* d, const char* name, int value) {
     d->attn_mode = value; return K5_OK;
   }
   if (!strcmp(name, "sp_pass1_tiles")) { if (value < 0) return K5_ERR_ARG; d->sp_pass1_tiles = value; return K5_OK; }
-  if (!strcmp(name, "sp_mode")) { if (value < 0 || value > 1) return K5_ERR_ARG; d->sp_mode = value; d->sp_user_set |= 1; return K5_OK; }
+  if (!strcmp(name, "sp_mode")) { if (value < 0 || value > 2) return K5_ERR_ARG; d->sp_mode = value; d->sp_user_set |= 1; return K5_OK; }
   if (!strcmp(name, "sp_autotune")) { d->sp_autotune = value != 0; if (value > 1) d->sp_tuned = false; return K5_OK; }   // 2 = tune again at the next sharded forward
   if (!strcmp(name, "attn_row_offsets")) { d->row_offsets = value != 0; return K5_OK; }
   if (!strcmp(name, "attn_anchor")) { d->anchor = value != 0; return K5_OK; }
@@ -2272,6 +2487,7 @@ extern "C" int k5_dit_get_option(k5_dit* d, const char* name, int* value) {
   if (!strcmp(name, "attn_mode")) *value = d->attn_mode;
   else if (!strcmp(name, "sp_pass1_tiles")) *value = d->sp_pass1_tiles;
   else if (!strcmp(name, "sp_mode")) *value = d->sp_mode;
+  else if (!strcmp(name, "sp_mode_used")) *value = d->sp_mode_used;
   else if (!strcmp(name, "sp_slices")) *value = d->sp_slices;
   else if (!strcmp(name, "attn_row_offsets")) *value = d->row_offsets ? 1 : 0;
   else if (!strcmp(name, "attn_anchor")) *value = d->anchor ? 1 : 0;
@@ -2283,7 +2499,7 @@ extern "C" int k5_dit_get_option(k5_dit* d, const char* name, int* value) {
   else if (!strcmp(name, "sp_tuned")) *value = d->sp_tuned ? 1 : 0;
   else if (!strcmp(name, "fp8_effective")) {   // the classes of k5_dit_set_fp8 that RUN in e4m3 on this handle's path — the sharded schedules keep the out
     int m = d->fp8_mask;                       // projection in bf16 (bit 4), Ulysses also the q | k | V^T projections (bit 2); a bench must label its line with THIS mask
-    if (d->comm.active()) { m &= ~4; if (d->sp_mode == 1 && !d->last_nabla && d->sp_world > 1 && d->Hh % d->sp_world == 0 && !d->emulated) m &= ~2; }   // the dispatch's own predicate (forward_impl: `ulysses`), with the attention type of the LAST forward
+    if (d->comm.active()) { m &= ~4; if (sp_schedule(d, d->last_nabla) != 0) m &= ~2; }   // the dispatch's own predicate (forward_impl: sp_schedule), with the attention type of the LAST forward
     *value = m;
   }
   else if (!strcmp(name, "rccl_ranks")) {   // the size the RCCL communicator reports (ncclCommCount): 0 = no communicator, -1 = a loopback group / no such symbol
@@ -2371,6 +2587,20 @@ extern "C" int k5_dit_sp_schedule(k5_dit* d, char* buf, int len) {
 }
 // The selection rule of that tuner as a plain function (tests): times[rank * ncand + cand] in ms (<= 0 or non-finite = did not run), valid
 // (nullable) = admissible candidates; returns the chosen candidate or -1, and max-over-ranks per candidate in cost_out (nullable, -1 = out).
+// the two-level schedule's exchange plan (sp_plan_2d), for tests without a GPU: table[(src * ranks + dst) * 3 + {0, 1, 2}] = (offset in src's send
+// buffer, offset in dst's receive buffer, bytes) of exchange `which` (0 k', 1 V^T, 2 q, 3 o); returns the schedule "sp_mode" 2 runs at this
+// (heads, ranks): 2 two-level, 1 Ulysses (G = ranks), 0 the gather (G = 1); G in *groups.  table and groups may be null.
+extern "C" int k5_sp_plan_2d(int heads, int ranks, int rows_pad, int dim, int which, int* groups, long long* table) {
+  g_err[0] = 0;
+  if (ranks < 1 || ranks > 64) return -K5_ERR_ARG;
+  std::vector<k5ipc::Xfer> tab((size_t)ranks * ranks);
+  const int G = sp_plan_2d(heads, ranks, rows_pad, dim, which, tab.data());
+  if (G <= 0 || (dim / G) % 8) { k5_set_error("k5_sp_plan_2d: bad arguments"); return -K5_ERR_ARG; }
+  if (groups) *groups = G;
+  if (table) for (size_t i = 0; i < tab.size(); ++i) { table[3 * i] = tab[i].send_off; table[3 * i + 1] = tab[i].recv_off; table[3 * i + 2] = tab[i].bytes; }
+  return G == 1 ? 0 : (G == ranks ? 1 : 2);
+}
+
 extern "C" int k5_sp_pick_schedule(const float* times, int ncand, int world, const int* valid, float* cost_out) {
   if (!times || ncand <= 0 || world <= 0) return -1;
   return sp_pick(times, ncand, world, valid, cost_out);

@@ -65,6 +65,8 @@ struct Shm {
 };
 
 struct PeerFlags { uint32_t* f[MAXR]; };
+// one entry of a planned exchange (Group::exchange; engine.hip sp_plan_2d): send_off into the sender's buffer, recv_off into the receiver's
+struct Xfer { long long send_off, recv_off, bytes; };
 
 // ---- device side ----
 // flag buffer of a rank (uint32): [0, MAXR) READY | [MAXR, 2 MAXR) PULLED | [ERRW] first timed-out wait | [CTR] the epoch of the collective in flight.
@@ -344,6 +346,29 @@ struct Group {
       const int p = (rank + i) % world;
       wait(p, 1, 0, s);
       if (copy((char*)recv + (size_t)p * block_bytes, (const char*)peer[p] + (size_t)rank * block_bytes, block_bytes, s)) return -1;
+    }
+    signal(1, s);
+    wait(0, world, 1, s);
+    return 0;
+  }
+
+  // planned exchange: tab[src * world + dst] = what rank src sends to rank dst (offset in src's `send`, offset in dst's `recv`, bytes; 0 bytes =
+  // nothing).  Every rank holds the whole table (the same one), so a rank pulls peer p's entry for itself; the rank's own entry is the caller's
+  // copy.  All ranks issue the call, including those with nothing to move: the epoch and the PULLED wait stay world-wide.
+  int exchange(const void* send, void* recv, const Xfer* tab, hipStream_t s) {
+    if (world == 1) return 0;
+    size_t total = 0;   // the same on every rank (one table): resolve's size check
+    for (int i = 0; i < world * world; ++i) total += (size_t)tab[i].bytes;
+    void* peer[MAXR];
+    if (resolve(send, total, peer)) return -1;
+    ++collectives;
+    signal(0, s);
+    for (int i = 1; i < world; ++i) {
+      const int p = (rank + i) % world;
+      const Xfer& e = tab[p * world + rank];
+      if (e.bytes <= 0) continue;
+      wait(p, 1, 0, s);
+      if (copy((char*)recv + e.recv_off, (const char*)peer[p] + e.send_off, (size_t)e.bytes, s)) return -1;
     }
     signal(1, s);
     wait(0, world, 1, s);

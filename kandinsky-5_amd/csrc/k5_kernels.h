@@ -131,6 +131,7 @@ size_t k5_rmsnorm_stats_workspace_bytes(int H);
 // Ulysses sequence parallelism: (q | k) rows [rows][2 D] -> per-destination blocks [P][slot_rows][2 D / P]; outputs [P][slot_rows][D / P] -> [rows][D]
 int k5_launch_ulysses_pack_qk(const void* x, void* out, int rows, int slot_rows, int D, int P, hipStream_t s);
 int k5_launch_ulysses_unpack_o(const void* in, void* out, int rows, int slot_rows, int D, int P, hipStream_t s);   // stats_ws: scratch of this size whenever stats is given
+int k5_launch_sp2d_pack_qk(const void* x, void* q_out, void* k_out, int rows, int slot_rows, int D, int G, hipStream_t s);   // two-level schedule: q / k' send planes [G][slot_rows][D / G]
 // heads >= scale_from_head are multiplied by out_scale before the bf16 rounding — in place, or (scaled_out != null) into
 // scaled_out[row][(head - scale_from_head) * 64 ...] while the unscaled values stay in place.
 // stats (device, [H] floats, zeroed by the consumer): stats[h] = max(stats[h], |x_row,h|^2) over the rows of the call, of the

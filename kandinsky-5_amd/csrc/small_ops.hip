@@ -560,6 +560,18 @@ __global__ __launch_bounds__(256) void ulysses_unpack_o_kernel(const bf16_t* __r
   }
 }
 
+// two-level schedule (engine.hip run_self_attention_2d): x [rows][2 D] = (q heads | k' heads) of the rank's rows -> q_out / k_out, each
+// [G][slot_rows][Dp] (block g = head group g): the per-destination send planes of the two exchanges, contiguous per destination
+__global__ __launch_bounds__(256) void sp2d_pack_qk_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ q_out, bf16_t* __restrict__ k_out, int rows,
+                                                           int slot_rows, int D, int Dp) {
+  const int cpr = 2 * D / 8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)rows * cpr; i += (int64_t)gridDim.x * 256) {
+    const int row = (int)(i / cpr), col = (int)(i % cpr) * 8;
+    const int part = col >= D ? 1 : 0, cc = col - part * D, g = cc / Dp, within = cc - g * Dp;
+    *reinterpret_cast<u32x4*>((part ? k_out : q_out) + ((size_t)g * slot_rows + row) * Dp + within) = *reinterpret_cast<const u32x4*>(x + (size_t)row * 2 * D + col);
+  }
+}
+
 size_t k5_rmsnorm_stats_workspace_bytes(int H) { return (size_t)4096 * 2 * H * sizeof(float); }   // partial rows of up to 2 H entries (norms + radii)
 
 int k5_launch_rmsnorm_rope(void* x, const float* weight, const float* cosT, const float* sinT, int rows, int H,
@@ -618,6 +630,13 @@ int k5_launch_ulysses_pack_qk(const void* x, void* out, int rows, int slot_rows,
 int k5_launch_ulysses_unpack_o(const void* in, void* out, int rows, int slot_rows, int D, int P, hipStream_t s) {
   if (rows <= 0 || slot_rows < rows || P <= 0 || D % P || (D / P) % 8) return K5_ERR_ARG;
   hipLaunchKernelGGL(ulysses_unpack_o_kernel, dim3(grid_for((int64_t)rows * (D / 8))), dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, rows, slot_rows, D, D / P);
+  return done();
+}
+
+int k5_launch_sp2d_pack_qk(const void* x, void* q_out, void* k_out, int rows, int slot_rows, int D, int G, hipStream_t s) {
+  if (rows <= 0 || slot_rows < rows || G <= 0 || D % G || (D / G) % 8) return K5_ERR_ARG;
+  hipLaunchKernelGGL(sp2d_pack_qk_kernel, dim3(grid_for((int64_t)rows * (2 * D / 8))), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)q_out, (bf16_t*)k_out, rows,
+                     slot_rows, D, D / G);
   return done();
 }
 

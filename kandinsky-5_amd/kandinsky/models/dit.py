@@ -408,7 +408,10 @@ class DiffusionTransformer3D(nn.Module):
         key blocks while the gather is in flight; default 1),
         "sp_slices" (sequence parallelism: exchange K / V^T in this many slices, attend each as it lands; default 1),
         "sp_mode" (sequence parallelism: 0 = K / V^T all-gather (default), 1 = Ulysses all-to-all — token rows traded for heads and back;
-        needs heads % ranks == 0 and dense attention, otherwise the gather is used),
+        needs heads % ranks == 0 and dense attention, otherwise the gather is used; 2 = two-level — gcd(heads, ranks) head groups x
+        ranks / gcd query splits, e.g. 28 heads at 8 ranks: 4 groups of 7 heads x 2 splits; Ulysses where the heads divide, the gather
+        where gcd = 1 or for NABLA; K5_SP_MODE=0/1/2 in the ranks' environment sets it at communicator init, this call wins;
+        get_option("sp_mode_used") reads what the last sharded forward ran: 0 gather, 1 Ulysses, 2 two-level),
         "sp_pass1_tiles", "emulate_world" (timing only)."""
         if self._handle is not None:     # no engine yet: remembered and applied when it is built (_reapply_settings)
             E.check(E.lib().k5_dit_set_option(self._handle, name.encode(), int(value)), f"k5_dit_set_option({name})")
