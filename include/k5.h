@@ -31,7 +31,7 @@ typedef enum { K5_EPI_BIAS = 0, K5_EPI_BIAS_M = 1, K5_EPI_GELU = 2, K5_EPI_GATE 
 
 /* bumped whenever an entry point is added or changes meaning; the host binding checks it BEFORE binding symbols, so that a stale
  * libk5.so fails with a clear message instead of a missing-symbol lookup (round 3: 4) */
-#define K5_ABI_VERSION 10
+#define K5_ABI_VERSION 11
 int k5_abi_version(void);
 const char* k5_last_error(void);
 
@@ -479,9 +479,10 @@ int k5_blend_bf16(const void* a, void* b, int64_t outer, int len_a, int len_b, i
  * explicit outer strides in elements (a decoded tile minus its first frame; the output video); dst[:, y] = y < extent ? the cross-fade of k5_blend_bf16
  * (a[:, len_a - extent + y], b[:, y]) : b[:, y], y < keep.  a = NULL: no cross-fade (the first tile).  inner a multiple of 8, 16-byte aligned pointers.
  * Neither a nor b is written: the previous tile's tail is read as the decoder left it, which is what the reference blends with while tiles are at
- * least 2 * extent long (the host mirror falls back to k5_blend_bf16 otherwise). */
-int k5_blend_place_bf16(const void* a, int64_t a_stride, int len_a, const void* b, int64_t b_stride, void* dst, int64_t dst_stride, int64_t outer,
-                        int64_t inner, int extent, int keep, void* stream);
+ * least 2 * extent long (the host mirror falls back to k5_blend_bf16 otherwise).  (ABI 11) len_b: the frames of b from the passed pointer on;
+ * K5_ERR_ARG before any launch when keep > len_b, extent > len_b, extent > len_a or extent > keep. */
+int k5_blend_place_bf16(const void* a, int64_t a_stride, int len_a, const void* b, int64_t b_stride, int len_b, void* dst, int64_t dst_stride,
+                        int64_t outer, int64_t inner, int extent, int keep, void* stream);
 /* (ABI 8) the pipeline's uint8 frames, ((x.clamp(-1, 1) + 1) * 127.5).to(torch.uint8) (reference generation_utils.py:222-224) in one pass with torch's
  * bf16 rounding after every elementwise op and the truncating conversion; n a multiple of 8 */
 int k5_frames_to_uint8(const void* x_bf16, void* out_u8, int64_t n, void* stream);

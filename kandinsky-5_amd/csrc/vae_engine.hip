@@ -515,9 +515,9 @@ extern "C" int k5_vae_path_counts(k5_vae* v, long long* out8, int reset) {
 extern "C" int k5_blend_bf16(const void* a, void* b, int64_t outer, int len_a, int len_b, int64_t inner, int extent, void* stream) {
   return k5_launch_blend_bf16(a, b, outer, len_a, len_b, inner, extent, (hipStream_t)stream);
 }
-extern "C" int k5_blend_place_bf16(const void* a, int64_t a_stride, int len_a, const void* b, int64_t b_stride, void* dst, int64_t dst_stride, int64_t outer,
-                                   int64_t inner, int extent, int keep, void* stream) {
-  return k5_launch_blend_place_bf16(a, a_stride, len_a, b, b_stride, dst, dst_stride, outer, inner, extent, keep, (hipStream_t)stream);
+extern "C" int k5_blend_place_bf16(const void* a, int64_t a_stride, int len_a, const void* b, int64_t b_stride, int len_b, void* dst, int64_t dst_stride,
+                                   int64_t outer, int64_t inner, int extent, int keep, void* stream) {
+  return k5_launch_blend_place_bf16(a, a_stride, len_a, b, b_stride, len_b, dst, dst_stride, outer, inner, extent, keep, (hipStream_t)stream);
 }
 extern "C" int k5_frames_to_uint8(const void* x_bf16, void* out_u8, int64_t n, void* stream) {
   return k5_launch_frames_to_uint8(x_bf16, out_u8, n, (hipStream_t)stream);

@@ -389,10 +389,11 @@ int k5_launch_nchw_to_mc(const float* z, void* out, int C, int64_t M, int Cpad, 
   return done();
 }
 
-int k5_launch_blend_place_bf16(const void* a, int64_t a_stride, int len_a, const void* b, int64_t b_stride, void* dst, int64_t dst_stride, int64_t outer,
-                               int64_t inner, int extent, int keep, hipStream_t s) {
+int k5_launch_blend_place_bf16(const void* a, int64_t a_stride, int len_a, const void* b, int64_t b_stride, int len_b, void* dst, int64_t dst_stride,
+                               int64_t outer, int64_t inner, int extent, int keep, hipStream_t s) {
   if (!b || !dst || outer <= 0 || inner <= 0 || keep <= 0 || extent < 0 || (inner & 7)) return K5_ERR_ARG;
-  if (a && (extent > len_a || extent > keep)) return K5_ERR_ARG;
+  if (keep > len_b) return K5_ERR_ARG;                       // the kernel reads b[o][0 .. keep): all of it must be there
+  if (a && (extent > len_a || extent > len_b || extent > keep)) return K5_ERR_ARG;
   if (((uintptr_t)b | (uintptr_t)dst | (uintptr_t)a) & 15 || ((b_stride | dst_stride | a_stride) & 7)) return K5_ERR_ALIGN;
   hipLaunchKernelGGL(blend_place_kernel, dim3(grid_for(outer * keep * (inner / 8))), dim3(256), 0, s, (const bf16_t*)a, a_stride, len_a, (const bf16_t*)b, b_stride,
                      (bf16_t*)dst, dst_stride, outer, inner / 8, a ? extent : 0, keep);

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("K5_LIB", os.path.join(os.path.dirname(_HERE), "lib", "libk5.so"))
 
 K5_OK = 0
-ABI_VERSION = 10         # include/k5.h K5_ABI_VERSION
+ABI_VERSION = 11         # include/k5.h K5_ABI_VERSION
 K5_F32, K5_BF16, K5_F16 = 0, 1, 2
 EPI_BIAS, EPI_BIAS_M, EPI_GELU, EPI_GATE = 0, 1, 2, 3
 
@@ -149,7 +149,7 @@ SYMBOLS = {
     "k5_vae_encode_tile": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "k5_vae_has_encoder": (_I, [_P]),
     "k5_blend_bf16": (_I, [_P, _P, _I64, _I, _I, _I64, _I, _P]),
-    "k5_blend_place_bf16": (_I, [_P, _I64, _I, _P, _I64, _P, _I64, _I64, _I64, _I, _I, _P]),
+    "k5_blend_place_bf16": (_I, [_P, _I64, _I, _P, _I64, _I, _P, _I64, _I64, _I64, _I, _I, _P]),
     "k5_frames_to_uint8": (_I, [_P, _P, _I64, _P]),
     "k5_vae_decode_tile_strided": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P]),
     "k5_dit_set_graph": (_I, [_P, _I]),

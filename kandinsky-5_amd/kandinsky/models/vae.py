@@ -354,27 +354,31 @@ class AutoencoderKLHunyuanVideo(nn.Module):
         # into its frames of the output in ONE pass (k5_blend_place_bf16); the slices, .contiguous() copies and torch.cat of the loop below are gone
         # (the same numbers: blend_t only ever reads the previous tile's LAST bf frames, which its own cross-fade — the first bf — did not touch).
         sn, mn = self.tile_sample_stride_num_frames, self.tile_sample_min_num_frames
-        if (tp is None or tp[1] <= 1) and len(starts) > 1 and mn >= 2 * bf and os.environ.get("K5_VAE_LEGACY_GLUE", "0") != "1":
+        if (tp is None or tp[1] <= 1) and len(starts) > 1 and 0 <= bf and mn >= 2 * bf and os.environ.get("K5_VAE_LEGACY_GLUE", "0") != "1":
             total = (nf - 1) * 4 + 1
+            # (drop, keep) per tile, from the geometry alone: the loop below keeps tile[:, :, :sn + 1], then tile[:, :, 1:][:, :, :sn] and last
+            # tile[:, :, 1:][:, :, :mn] — each clamped to what the tile holds.  The last start can be nf - mf: that tile has mf latent frames, decodes
+            # to 4 (mf - 1) + 1 and keeps at most 4 (mf - 1) of them.
+            held = [4 * (min(mf + 1, nf - i) - 1) + 1 for i in starts]
+            plan = [(0, min(sn + 1, held[0]))] + [(1, min(sn, h - 1)) for h in held[1:-1]] + [(1, min(mn, held[-1] - 1))]
             first = decode_one(starts[0])
             _, C3, F0, Ho, Wo = first.shape
             if first.is_cuda and first.dtype == torch.bfloat16 and first.is_contiguous() and F0 == mn + 1 and (Ho * Wo) % 8 == 0:
-                dec = torch.empty(1, C3, sn + 1 + sn * (len(starts) - 2) + mn, Ho, Wo, dtype=first.dtype, device=first.device)
+                dec = torch.empty(1, C3, sum(keep for _, keep in plan), Ho, Wo, dtype=first.dtype, device=first.device)
                 inner, stream = Ho * Wo, E.stream_ptr(first.device)
 
                 def place(prev, cur, drop, f0, keep):   # frames [drop, drop + keep) of cur -> dec[:, :, f0 : f0 + keep], the first bf cross-faded with prev's tail
                     a_ptr = 0 if prev is None else prev[0].data_ptr() + prev[1] * inner * 2
                     E.check(E.lib().k5_blend_place_bf16(a_ptr, 0 if prev is None else prev[0].stride(1), 0 if prev is None else prev[0].shape[2] - prev[1],
-                                                        cur.data_ptr() + drop * inner * 2, cur.stride(1), dec.data_ptr() + f0 * inner * 2, dec.stride(1),
-                                                        C3, inner, 0 if prev is None else bf, keep, stream), "k5_blend_place_bf16")
+                                                        cur.data_ptr() + drop * inner * 2, cur.stride(1), cur.shape[2] - drop,
+                                                        dec.data_ptr() + f0 * inner * 2, dec.stride(1), C3, inner, 0 if prev is None else bf, keep, stream),
+                            "k5_blend_place_bf16")
                 with torch.cuda.device(first.device):
-                    place(None, first, 0, 0, sn + 1)
-                    prev, f0 = (first, 0), sn + 1
-                    for k in range(1, len(starts)):
-                        cur = decode_one(starts[k])
-                        keep = mn if k == len(starts) - 1 else sn
-                        place(prev, cur, 1, f0, keep)
-                        prev, f0 = (cur, 1), f0 + keep
+                    prev, f0 = None, 0
+                    for k, (drop, keep) in enumerate(plan):
+                        cur = first if k == 0 else decode_one(starts[k])
+                        place(prev, cur, drop, f0, keep)
+                        prev, f0 = (cur, drop), f0 + keep
                 dec = dec[:, :, :total]
                 return DecoderOutput(dec) if return_dict else (dec,)
             decoded = [first] + [decode_one(i) for i in starts[1:]]

@@ -234,14 +234,20 @@ def test_single_frame_tile(vae):
     assert rel(out, V.decoder_forward(sd, z, CFG, "bf16")) <= 2e-2
 
 
-@pytest.mark.parametrize("shape,tile,stride", [((1, 16, 7, 4, 4), (1, 9, 32, 32), (4, 32, 32)),      # temporal tiles
+@pytest.mark.parametrize("shape,tile,stride", [((1, 16, 7, 4, 4), (1, 9, 32, 32), (4, 32, 32)),      # temporal tiles, short last tile
                                                ((1, 16, 2, 10, 14), (1, 9, 48, 48), (8, 32, 32)),    # spatial tiles
-                                               ((1, 16, 5, 10, 10), (1, 9, 48, 48), (4, 32, 32))])   # both
+                                               ((1, 16, 5, 10, 10), (1, 9, 48, 48), (4, 32, 32)),    # both
+                                               ((1, 16, 8, 4, 4), (1, 17, 32, 32), (8, 32, 32)),     # 17 / 8, short last tile
+                                               ((1, 16, 6, 11, 13), (1, 17, 48, 48), (8, 32, 32))])  # temporal x ragged spatial
 def test_tiled_decode_vs_oracle(vae, shape, tile, stride):
     m, sd = vae
     z = torch.randn(*shape, generator=torch.Generator().manual_seed(3))
     m.apply_tiling(tile, stride)
     out = m._decode(z.cuda()).sample
+    # the oracle's glue driven by the engine's tile decode of a CONTIGUOUS copy, while _decode reads its tiles in place out of the long
+    # latent (k5_vae_decode_tile_strided): the decode is deterministic, so this pins the glue and the strided read bit for bit
+    glue = V.tiled_decode(None, z, None, tile, stride, "bf16", decode_tile=lambda t: m._decode_tile(t.cuda()).float().cpu())
+    assert out.shape == glue.shape and torch.equal(out.float().cpu(), glue), rel(out, glue)
     ref = V.tiled_decode(sd, z, CFG, tile, stride, "bf16")
     assert out.shape == ref.shape
     assert rel(out, ref) <= 2e-2, rel(out, ref)
@@ -348,6 +354,171 @@ def test_config5_spatial_tiling_at_real_size():
     assert tuple(out.shape) == tuple(ref.shape) == (1, 3, 33, 768, 1280)
     assert torch.isfinite(out.float()).all() and out.float().std().item() > 1e-3
     assert torch.equal(out.float(), ref.float()), rel(out, ref)
+
+
+# ------------------------------------------------------------------------------------------ tiling glue, bit for bit
+# The host glue (tile origins, dropped frames, cross-fades, crops) against the oracle's own glue, both fed the SAME tiles from a cheap
+# synthetic stand-in for the decoder.  The stand-in carries ramps in the tile's own frame / row / column, so overlapping tiles differ and every
+# blend weight, extent, crop and origin reaches the output bits; a relative-L2 bound on real decoder tiles would not see most of those.
+def _synthetic_decode_tile(z):
+    """(1, C, t, h, w) -> (1, 3, 4 (t - 1) + 1, 8 h, 8 w) bf16 on the GPU: nearest upsample of 3 channels x 0.5 (frame 0 once, every later
+    latent frame 4 times) plus linear ramps in tile-local coordinates.  A function of the values only: a slice, a contiguous copy or a CPU
+    copy of the same latent give the same bits."""
+    z = z.cuda().float()
+    x = z[:, :3]
+    x = torch.cat([x[:, :, :1], x[:, :, 1:].repeat_interleave(4, dim=2)], 2).repeat_interleave(8, 3).repeat_interleave(8, 4) * 0.5
+    F, H, W = x.shape[2:]
+    ar = lambda n: torch.arange(n, device=x.device, dtype=torch.float32) / n
+    x = x + 0.375 * ar(F).view(F, 1, 1) + 0.25 * ar(H).view(H, 1) + 0.125 * ar(W)
+    return x.to(torch.bfloat16).contiguous()
+
+
+class _PlaceSpy:
+    """Stands in for libk5's k5_blend_place_bf16 (ABI 11 signature).  Every tile the glue decodes is recorded (and kept alive, so no
+    allocation is reused under a recorded range); a call whose reads of b (`keep` frames per channel) or of a's tail (`len_a` frames) leave
+    one recorded tile raises BEFORE the library is called.  Writes are checked against the returned video afterwards."""
+
+    def __init__(self, m, monkeypatch):
+        from kandinsky import _engine as E
+        from kandinsky.models.vae import AutoencoderKLHunyuanVideo
+        self.real, self.tiles, self.alive, self.writes = E.lib().k5_blend_place_bf16, [], [], []
+        monkeypatch.setattr(E.lib(), "k5_blend_place_bf16", self)
+
+        def decode_tile(z):
+            return self.record(_synthetic_decode_tile(z))
+
+        def tiled_decode(z, return_dict=True):   # a spatially tiled temporal tile is a decoded tile of the temporal glue
+            out = AutoencoderKLHunyuanVideo.tiled_decode(m, z, return_dict)
+            self.record(out.sample if return_dict else out[0])
+            return out
+
+        m._decode_tile, m.tiled_decode = decode_tile, tiled_decode
+
+    def record(self, t):
+        self.alive.append(t)
+        self.tiles.append((t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()))
+        return t
+
+    def _inside(self, lo, hi):
+        return any(t0 <= lo and hi <= t1 for t0, t1 in self.tiles)
+
+    def __call__(self, a, a_stride, len_a, b, b_stride, len_b, dst, dst_stride, outer, inner, extent, keep, stream):
+        end_b = b + 2 * ((outer - 1) * b_stride + keep * inner)
+        if not self._inside(b, end_b):
+            raise AssertionError(f"k5_blend_place_bf16 would read b past its tile: keep={keep} len_b={len_b} outer={outer} inner={inner}")
+        if a and extent > 0 and not self._inside(a, a + 2 * ((outer - 1) * a_stride + len_a * inner)):
+            raise AssertionError(f"k5_blend_place_bf16 would read a past its tile: len_a={len_a} extent={extent}")
+        self.writes.append((dst, dst + 2 * ((outer - 1) * dst_stride + keep * inner)))
+        return self.real(a, a_stride, len_a, b, b_stride, len_b, dst, dst_stride, outer, inner, extent, keep, stream)
+
+
+def _glue_vae():
+    from kandinsky.models.vae import AutoencoderKLHunyuanVideo
+    with torch.device("meta"):
+        return AutoencoderKLHunyuanVideo()
+
+
+def _one_pass_expected(nf, tile, stride):
+    mn, sn = tile[1] - 1, stride[0]
+    bf, mf, sf = mn - sn, mn // 4, sn // 4
+    return nf > mf + 1 and len(range(0, nf - mf + 1, sf)) > 1 and 0 <= bf and mn >= 2 * bf
+
+
+def _temporal_glue_cases():
+    cases = []
+    for ft, fs in ((9, 4), (17, 8), (17, 12), (17, 16), (13, 4), (13, 8), (21, 12), (21, 16), (9, 12)):   # 17/16: no overlap; 13/4: mn < 2 bf;
+        # 9/12: gaps between tiles (negative overlap), which the one-pass glue leaves to the loop
+        mf = (ft - 1) // 4
+        cases += [pytest.param((1, 16, nf, 2, 3), (1, ft, 256, 256), (fs, 256, 256), id=f"{ft}/{fs}-nf{nf}") for nf in range(mf + 2, mf + 9)]
+    for ft, fs, nf in ((9, 4, 5), (9, 4, 6), (17, 8, 6), (17, 8, 7), (13, 4, 7), (21, 16, 9)):   # temporal tiles tiled spatially, 11 x 13 latent
+        cases.append(pytest.param((1, 16, nf, 11, 13), (1, ft, 48, 48), (fs, 32, 32), id=f"{ft}/{fs}-nf{nf}-11x13"))
+    from kandinsky.models.vae import OPT_TEMPORAL_TILING
+    for frames, (ft, fs) in sorted(OPT_TEMPORAL_TILING.items()):
+        cases.append(pytest.param((1, 16, (frames - 1) // 4 + 1, 2, 2), (1, ft, 256, 256), (fs, 256, 256), id=f"table{frames}"))
+    return cases
+
+
+@pytest.mark.parametrize("legacy", ["0", "1"])
+@pytest.mark.parametrize("shape,tile,stride", _temporal_glue_cases())
+def test_temporal_decode_glue_equals_oracle_glue(shape, tile, stride, legacy, monkeypatch):
+    """`_decode` over temporal tilings — short last tiles, tilings that stop short of the clip, single tiles, no overlap, the legacy-only
+    branch (mn < 2 bf), spatially tiled temporal tiles and every entry of the temporal table — equals the oracle's tiled_decode fed the same
+    tiles, under the one-pass glue (k5_blend_place_bf16, every read bounded by the spy) and under the slice / blend / cat loop."""
+    monkeypatch.setenv("K5_VAE_LEGACY_GLUE", legacy)
+    m = _glue_vae()
+    spy = _PlaceSpy(m, monkeypatch)
+    z = torch.randn(*shape, generator=torch.Generator().manual_seed(shape[2]))
+    m.apply_tiling(tile, stride)
+    out = m._decode(z.cuda()).sample
+    ref = V.tiled_decode(None, z, None, tile, stride, "bf16", decode_tile=lambda t: _synthetic_decode_tile(t).float().cpu())
+    assert tuple(out.shape) == tuple(ref.shape)
+    assert torch.equal(out.float().cpu(), ref), rel(out, ref)
+    assert bool(spy.writes) == (legacy == "0" and _one_pass_expected(shape[2], tile, stride))   # the one-pass glue ran where it should
+    lo = out.untyped_storage().data_ptr()
+    hi = lo + out.untyped_storage().nbytes()
+    assert all(lo <= w0 and w1 <= hi for w0, w1 in spy.writes), (lo, hi, spy.writes)
+
+
+def test_blend_place_launcher_contract():
+    """k5_blend_place_bf16 (ABI 11) against the oracle's blend_t + slice, with the glue's offsets (a and b past a dropped first frame, dst
+    one frame into a longer buffer); calls that would read past what a or b hold are refused with K5_ERR_ARG before any launch."""
+    from kandinsky import _engine as E
+    L = E.lib()
+    assert L.k5_abi_version() == 11                     # the ABI that gave the launcher b's length
+    g = torch.Generator().manual_seed(12)
+    outer, la, lb, h, w, extent, keep = 3, 9, 12, 5, 8, 4, 7
+    inner = h * w
+    a = bfr(torch.randn(1, outer, la, h, w, generator=g))
+    b = bfr(torch.randn(1, outer, lb, h, w, generator=g))
+    ref = V.blend(a[:, :, 1:].clone(), b[:, :, 1:].clone(), extent, 2, "bf16")[:, :, :keep]
+    ad, bd = a.cuda().bfloat16(), b.cuda().bfloat16()
+    dst = torch.full((1, outer, lb + 2, h, w), 7.0, dtype=torch.bfloat16, device="cuda")
+    stream = E.stream_ptr()
+
+    def call(len_a, len_b, extent, keep):   # the buffers hold more than len_a / len_b frames: even a call the launcher should refuse stays in bounds
+        return L.k5_blend_place_bf16(ad.data_ptr() + inner * 2, ad.stride(1), len_a, bd.data_ptr() + inner * 2, bd.stride(1), len_b,
+                                     dst.data_ptr() + inner * 2, dst.stride(1), outer, inner, extent, keep, stream)
+
+    assert call(la - 1, lb - 1, extent, keep) == E.K5_OK
+    torch.cuda.synchronize()
+    assert torch.equal(dst[:, :, 1:1 + keep].float().cpu(), ref)
+    assert (dst[:, :, 0] == 7.0).all() and (dst[:, :, 1 + keep:] == 7.0).all()
+    K5_ERR_ARG = 1
+    assert call(la - 1, 6, extent, 7) == K5_ERR_ARG      # keep > len_b
+    assert call(la - 1, 3, 4, 3) == K5_ERR_ARG           # extent > len_b
+    assert call(3, lb - 1, 4, keep) == K5_ERR_ARG        # extent > len_a
+    assert call(la - 1, lb - 1, 5, 4) == K5_ERR_ARG      # extent > keep
+    torch.cuda.synchronize()
+    assert (dst[:, :, 0] == 7.0).all() and (dst[:, :, 1 + keep:] == 7.0).all()
+
+
+def _spatial_decode_cases():
+    from kandinsky.models.vae import OPT_SPATIAL_TILING
+    cases = []
+    for n, (px, (t, s)) in enumerate(sorted(OPT_SPATIAL_TILING.items())):
+        nf = 1 + n % 2
+        cases.append(pytest.param((1, 16, nf, px // 8, t // 8), (1, 17, t, t), (8, s, s), id=f"H{px}"))   # the other axis one tile wide
+        cases.append(pytest.param((1, 16, nf, t // 8, px // 8), (1, 17, t, t), (8, s, s), id=f"W{px}"))
+    # ragged planes, (H - tile) % stride != 0: the last row / column of tiles stops short of the plane
+    cases += [pytest.param((1, 16, 2, 11, 13), (1, 17, 48, 48), (8, 32, 32), id="ragged-11x13"),
+              pytest.param((1, 16, 1, 23, 9), (1, 17, 64, 64), (8, 40, 40), id="ragged-23x9"),
+              pytest.param((1, 16, 2, 30, 17), (1, 17, 96, 96), (8, 64, 64), id="ragged-30x17")]
+    return cases
+
+
+@pytest.mark.parametrize("shape,tile,stride", _spatial_decode_cases())
+def test_spatial_decode_glue_equals_oracle_glue(shape, tile, stride):
+    """`_decode` over spatial tilings — each entry of the spatial table along H and along W, and ragged planes — equals the oracle's
+    tiled_decode fed the same synthetic tiles, bit for bit.  Widths between stride / 8 and tile / 8, where the reference's own _decode
+    (its width test uses the stride) finds no tile at all, are left out."""
+    m = _glue_vae()
+    m._decode_tile = _synthetic_decode_tile
+    z = torch.randn(*shape, generator=torch.Generator().manual_seed(shape[3] + shape[4]))
+    m.apply_tiling(tile, stride)
+    out = m._decode(z.cuda()).sample
+    ref = V.tiled_decode(None, z, None, tile, stride, "bf16", decode_tile=lambda t: _synthetic_decode_tile(t).float().cpu())
+    assert tuple(out.shape) == tuple(ref.shape)
+    assert torch.equal(out.float().cpu(), ref), rel(out, ref)
 
 
 # ------------------------------------------------------------------------------------------ production width (VERDICT r2 #1)

@@ -126,3 +126,56 @@ def test_encode_api_and_round_trip(vae):
     assert torch.isfinite(m2.decode(post.mean).sample.float()).all()         # decode works without the encoder half
     with pytest.raises(RuntimeError, match="without its encoder"):
         m2.encode(x)
+
+
+# ------------------------------------------------------------------------------------------ tiling glue, bit for bit
+# As tests/test_gpu_vae.py does for decode: the host mirror's encode glue against the oracle's tiled_encode, both fed the same tiles from a
+# cheap synthetic stand-in for the encoder whose ramps in tile-local coordinates make every origin, dropped frame, blend and crop visible.
+def _synthetic_encode_tile(x):
+    """(1, 3, T, H, W) -> (1, 3, (T - 1) // 4 + 1, H // 8, W // 8) bf16 on the GPU: every 4th frame averaged over 8 x 8 pixels, x 0.5, plus
+    linear ramps in tile-local latent coordinates.  A function of the values only."""
+    x = x.cuda().float()[:, :, ::4]
+    x = torch.nn.functional.avg_pool3d(x, (1, 8, 8)) * 0.5
+    F, H, W = x.shape[2:]
+    ar = lambda n: torch.arange(n, device=x.device, dtype=torch.float32) / n
+    x = x + 0.375 * ar(F).view(F, 1, 1) + 0.25 * ar(H).view(H, 1) + 0.125 * ar(W)
+    return x.to(torch.bfloat16).contiguous()
+
+
+def _glue_vae():
+    from kandinsky.models.vae import AutoencoderKLHunyuanVideo
+    with torch.device("meta"):
+        m = AutoencoderKLHunyuanVideo()
+    m._encode_tile = _synthetic_encode_tile
+    return m
+
+
+def _encode_glue_cases():
+    cases = []
+    for ft, fs in ((9, 4), (17, 8), (17, 12), (17, 16), (13, 4), (13, 8), (21, 12), (21, 16)):
+        mf = ft - 1    # pixel frames: 7 consecutive clip lengths past one tile give short last tiles and last tiles that stop short of the clip
+        cases += [pytest.param((nf, 16, 24), (1, ft, 256, 256), (fs, 256, 256), id=f"{ft}/{fs}-nf{nf}") for nf in range(mf + 2, mf + 9)]
+        cases.append(pytest.param((mf + 1 + 2 * fs, 16, 24), (1, ft, 256, 256), (fs, 256, 256), id=f"{ft}/{fs}-nf{mf + 1 + 2 * fs}"))
+    for ft, fs, nf in ((9, 4, 17), (9, 4, 19), (17, 8, 30)):   # temporal tiles tiled spatially, ragged 88 x 104 plane
+        cases.append(pytest.param((nf, 88, 104), (1, ft, 48, 48), (fs, 32, 32), id=f"{ft}/{fs}-nf{nf}-88x104"))
+    from kandinsky.models.vae import OPT_SPATIAL_TILING
+    for n, (px, (t, s)) in enumerate(sorted(OPT_SPATIAL_TILING.items())):   # each spatial table entry along H and along W, 1 or 2 latent frames
+        nf = 1 + 4 * (n % 2)
+        cases.append(pytest.param((nf, px, t), (1, 17, t, t), (8, s, s), id=f"H{px}"))
+        cases.append(pytest.param((nf, t, px), (1, 17, t, t), (8, s, s), id=f"W{px}"))
+    cases += [pytest.param((5, 88, 104), (1, 17, 48, 48), (8, 32, 32), id="ragged-88x104"),      # (H - tile) % stride != 0
+              pytest.param((1, 184, 72), (1, 17, 64, 64), (8, 40, 40), id="ragged-184x72")]
+    return cases
+
+
+@pytest.mark.parametrize("shape,tile,stride", _encode_glue_cases())
+def test_encode_glue_equals_oracle_glue(shape, tile, stride):
+    """`_encode` over temporal tilings (short last tiles, tilings that stop short of the clip, no overlap), temporal tiles tiled spatially,
+    every spatial table entry along H and W, and ragged planes equals the oracle's tiled_encode fed the same synthetic tiles, bit for bit."""
+    m = _glue_vae()
+    x = torch.randn(1, 3, *shape, generator=torch.Generator().manual_seed(sum(shape))).clamp(-1, 1)
+    m.apply_tiling(tile, stride)
+    got = m._encode(x.cuda())
+    ref = V.tiled_encode(None, x, None, tile, stride, "bf16", encode_tile=lambda t: _synthetic_encode_tile(t).float().cpu())
+    assert tuple(got.shape) == tuple(ref.shape)
+    assert torch.equal(got.float().cpu(), ref), rel(got, ref)
