@@ -255,6 +255,10 @@ int k5_rope_table_f32(float* cos_tab, float* sin_tab, const int32_t* pos_t, cons
  * channels in [x_channels, Cin_total) read as zero (generation_utils.py:107-112); tok_perm = fractal order. */
 int k5_patchify_bf16(const float* x, void* out, int T, int H, int W, int x_channels, int Cin_total, int Kpad,
                      const int32_t* tok_perm, void* stream);
+/* k5_patchify_bf16 of torch.cat([x, vcond], -1) read from the two sources: x fp32 (T,H,W,x_channels), vcond fp32
+ * (T,H,W,Cin_total-x_channels), 0 < x_channels < Cin_total; bit-identical output. */
+int k5_patchify_cond_bf16(const float* x, const float* vcond, void* out, int T, int H, int W, int x_channels, int Cin_total,
+                          int Kpad, const int32_t* tok_perm, void* stream);
 /* OutLayer un-patchify nn.py:384-399: [Ntok][4C] (c,ph,pw) -> (T,2Hp,2Wp,C) bf16. */
 int k5_unpatchify_bf16(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx,
                        const int32_t* tok_perm, void* stream);
@@ -322,6 +326,11 @@ int k5_dit_missing_keys(k5_dit* dit);
 int k5_dit_forward(k5_dit* dit, const k5_forward_args* args, void* out_velocity, void* stream);
 /* whole Euler loop on device (generate, generation_utils.py:80-129) */
 int k5_sample(k5_dit* dit, const k5_sample_args* args, void* stream);
+/* k5_sample with the conditioning channels of a visual_cond model filled (image-to-video, latent continuation): visual_cond is a
+ * borrowed device fp32 (T,H,W,in_visual_dim+1) tensor — channels 0..in_visual_dim-1 the conditioning latent, the last one the mask —
+ * constant for the call; every forward patchifies cat([latent, visual_cond], -1).  NULL = k5_sample.  K5_ERR_ARG when visual_cond is
+ * given to a handle created with visual_cond = 0 or is not 4-byte aligned. */
+int k5_sample_cond(k5_dit* dit, const k5_sample_args* args, const float* visual_cond, void* stream);
 
 /* Sequence parallelism (replaces the reference's DTensor head-parallel plan, kandinsky/models/parallelize.py:11-102,
  * keeps its launch contract LOCAL_RANK/WORLD_SIZE, kandinsky/utils.py:40-55): one process per GPU, rank r owns the

@@ -1645,7 +1645,7 @@ int sp_schedule(const k5_dit* d, bool nabla) {
 
 int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, float time, const float* x,
                  int x_channels, void* out_velocity, hipStream_t s, const float* tvec = nullptr, const int* step = nullptr,
-                 int text_slot = -1) {
+                 int text_slot = -1, const float* vcond = nullptr) {
   const k5_dit_config& c = d->cfg;
   if (!d->finalized) { k5_set_error("k5_dit_forward before k5_dit_finalize"); return K5_ERR_STATE; }
   if (a->attention_type == 1) {   // NABLA workgroup size of this forward (see nabla_group_rows)
@@ -1663,6 +1663,7 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   const int Cin = c.visual_cond ? 2 * c.in_visual_dim + 1 : c.in_visual_dim;
   if (N <= 0 || L <= 0 || (a->H & 1) || (a->W & 1)) { k5_set_error("bad shapes"); return K5_ERR_ARG; }
   if (x_channels != Cin && x_channels != c.in_visual_dim) { k5_set_error("x_channels must be %d or %d", Cin, c.in_visual_dim); return K5_ERR_ARG; }
+  if (vcond && (!c.visual_cond || x_channels != c.in_visual_dim)) { k5_set_error("visual_cond needs a visual_cond model and x of in_visual_dim channels"); return K5_ERR_ARG; }
   const int P = d->sp_world;
   const bool sp = d->comm.active();  // a communicator (even of size 1) selects the sharded code path
   if (sp && P > 1 && !d->emulated && d->sp_autotune && !d->sp_tuned && !d->vblocks.empty() && N % 64 == 0) {
@@ -1746,7 +1747,8 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     // every Modulation layer of the network in one GEMV (they all consume the same time_embed)
     K5CHK(k5_launch_gemv_f32(d->ws_temb.as<float>(), d->mod_w.as<float>(), d->mod_b.as<float>(), d->ws_mod.as<float>(),
                              (int)d->mod_rows, d->TD, 1, nullptr, s));
-    K5CHK(k5_launch_patchify(x, d->ws_xp.p, a->T, a->H, a->W, x_channels, Cin, d->KvisPad, perm, s));
+    if (vcond) K5CHK(k5_launch_patchify_cond(x, vcond, d->ws_xp.p, a->T, a->H, a->W, x_channels, Cin, d->KvisPad, perm, s));
+    else K5CHK(k5_launch_patchify(x, d->ws_xp.p, a->T, a->H, a->W, x_channels, Cin, d->KvisPad, perm, s));
     K5CHK(k5_launch_gemm_bf16(d->ws_xp.as<bf16_t>() + (size_t)tok0 * d->KvisPad, d->vis_w.p, d->vis_b.as<float>(), d->ws_vis.p,
                               n, D, d->KvisPad, d->KvisPad, d->KvisPad, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
   }
@@ -2109,11 +2111,13 @@ extern "C" int k5_dit_forward(k5_dit* d, const k5_forward_args* a, void* out_vel
   return st;
 }
 
-extern "C" int k5_sample(k5_dit* d, const k5_sample_args* a, void* stream) {
+extern "C" int k5_sample_cond(k5_dit* d, const k5_sample_args* a, const float* vcond, void* stream) {
   g_err[0] = 0;
   if (!d || !a || !a->latent || !a->sigmas || a->num_steps <= 0) return K5_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const k5_dit_config& c = d->cfg;
+  if (vcond && !c.visual_cond) { k5_set_error("k5_sample_cond: the handle was created with visual_cond = 0"); return K5_ERR_ARG; }
+  if (vcond && (reinterpret_cast<uintptr_t>(vcond) & 3)) { k5_set_error("k5_sample_cond: visual_cond is not 4-byte aligned"); return K5_ERR_ARG; }
   const int64_t n = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W * c.out_visual_dim;
   if (c.in_visual_dim != c.out_visual_dim) return K5_ERR_UNSUPPORTED;
   const bool cfg_on = fabsf(a->guidance_weight - 1.0f) > 1e-6f;  // generation_utils.py:63
@@ -2184,8 +2188,8 @@ extern "C" int k5_sample(k5_dit* d, const k5_sample_args* a, void* stream) {
     if (pair) {
       // my branch only; then the pair's velocities change hands on the side stream (fork / join by events: capturable) and both
       // handles hold [v_cond | v_uncond] — every rank of both groups applies the same update to the same numbers
-      if (d->cfg_branch == 0) K5CHK(forward_impl(d, &a->fwd, a->fwd.cond, t1000, a->latent, c.in_visual_dim, vel_c, s, tvec, step, 0));
-      else K5CHK(forward_impl(d, &a->fwd, a->null_cond, t1000, a->latent, c.in_visual_dim, vel_u, s, tvec, step, 1));
+      if (d->cfg_branch == 0) K5CHK(forward_impl(d, &a->fwd, a->fwd.cond, t1000, a->latent, c.in_visual_dim, vel_c, s, tvec, step, 0, vcond));
+      else K5CHK(forward_impl(d, &a->fwd, a->null_cond, t1000, a->latent, c.in_visual_dim, vel_u, s, tvec, step, 1, vcond));
       Scope sc(d, s, "comm");
       HIPCHK(hipEventRecord(d->ev_vel_ready, s));
       HIPCHK(hipStreamWaitEvent(d->pair_stream, d->ev_vel_ready, 0));
@@ -2193,8 +2197,8 @@ extern "C" int k5_sample(k5_dit* d, const k5_sample_args* a, void* stream) {
       HIPCHK(hipEventRecord(d->ev_vel_done, d->pair_stream));
       HIPCHK(hipStreamWaitEvent(s, d->ev_vel_done, 0));
     } else {
-      K5CHK(forward_impl(d, &a->fwd, a->fwd.cond, t1000, a->latent, c.in_visual_dim, vel_c, s, tvec, step, 0));
-      if (cfg_on) K5CHK(forward_impl(d, &a->fwd, a->null_cond, t1000, a->latent, c.in_visual_dim, vel_u, s, tvec, step, 1));
+      K5CHK(forward_impl(d, &a->fwd, a->fwd.cond, t1000, a->latent, c.in_visual_dim, vel_c, s, tvec, step, 0, vcond));
+      if (cfg_on) K5CHK(forward_impl(d, &a->fwd, a->null_cond, t1000, a->latent, c.in_visual_dim, vel_u, s, tvec, step, 1, vcond));
     }
     {
       Scope sc(d, s, "elementwise");
@@ -2230,6 +2234,8 @@ extern "C" int k5_sample(k5_dit* d, const k5_sample_args* a, void* stream) {
   (void)caller;
   return status;
 }
+
+extern "C" int k5_sample(k5_dit* d, const k5_sample_args* a, void* stream) { return k5_sample_cond(d, a, nullptr, stream); }
 
 // W8A8 e4m3 feed-forward (BASELINE config 5).  Quantises W1 / W2 of every visual block per output channel on first enable.
 extern "C" int k5_dit_set_fp8(k5_dit* d, int enabled) {

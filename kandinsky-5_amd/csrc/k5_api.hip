@@ -316,6 +316,12 @@ int k5_patchify_bf16(const float* x, void* out, int T, int H, int W, int x_chann
              "k5_patchify_bf16");
 }
 
+int k5_patchify_cond_bf16(const float* x, const float* vcond, void* out, int T, int H, int W, int x_channels, int Cin_total,
+                          int Kpad, const int32_t* tok_perm, void* stream) {
+  return ret(k5_launch_patchify_cond(x, vcond, out, T, H, W, x_channels, Cin_total, Kpad, tok_perm, (hipStream_t)stream),
+             "k5_patchify_cond_bf16");
+}
+
 int k5_unpatchify_bf16(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx, const int32_t* tok_perm,
                        void* stream) {
   return ret(k5_launch_unpatchify(x, out, T, Hp, Wp, C, ldx, tok_perm, (hipStream_t)stream), "k5_unpatchify_bf16");

@@ -157,6 +157,10 @@ int k5_launch_ln_affine(const void* x, const float* w, const float* b, void* out
 // token permutation (fractal order, K16)
 int k5_launch_patchify(const float* x, void* out, int T, int H, int W, int C, int Cin_total, int Kpad,
                        const int32_t* tok_perm, hipStream_t stream);
+// patchify of torch.cat([x, vcond], -1) from the two sources: x fp32 (T,H,W,C), vcond fp32 (T,H,W,Cin_total-C) (the visual_cond
+// latent and mask); the same bits as k5_launch_patchify on the concatenated tensor
+int k5_launch_patchify_cond(const float* x, const float* vcond, void* out, int T, int H, int W, int C, int Cin_total, int Kpad,
+                            const int32_t* tok_perm, hipStream_t stream);
 // un-patchify (K17 tail): [Ntok][C*4] bf16 (feature order c,ph,pw) -> (T,H,W,C) bf16, token perm optional
 int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx,
                          const int32_t* tok_perm, hipStream_t stream);

@@ -477,6 +477,28 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
   }
 }
 
+__global__ __launch_bounds__(256) void patchify_cond_kernel(const float* __restrict__ x, const float* __restrict__ vc,
+                                                            bf16_t* __restrict__ out, int T, int H, int W, int Cx, int Cin,
+                                                            int Kpad, const int32_t* __restrict__ tok_perm) {
+  // patchify_kernel on torch.cat([x, vc], -1) without the concatenation: channels [0, Cx) from the latent x (T,H,W,Cx), channels
+  // [Cx, Cin) from the conditioning vc (T,H,W,Cin-Cx); same feature order, permutation, zero pad and RNE cast
+  const int Hp = H / 2, Wp = W / 2, Cv = Cin - Cx;
+  const int64_t total = (int64_t)T * Hp * Wp * Kpad;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+    const int f = (int)(g % Kpad);
+    const int64_t row = g / Kpad;
+    float v = 0.f;
+    if (f < 4 * Cin) {
+      const int64_t tok = tok_perm ? tok_perm[row] : row;
+      const int wp = (int)(tok % Wp), hp = (int)((tok / Wp) % Hp), t = (int)(tok / ((int64_t)Wp * Hp));
+      const int c = f % Cin, pp = f / Cin, ph = pp >> 1, pw = pp & 1;
+      const int64_t pix = ((int64_t)t * H + 2 * hp + ph) * W + 2 * wp + pw;
+      v = c < Cx ? x[pix * Cx + c] : vc[pix * Cv + (c - Cx)];
+    }
+    out[g] = f2bf(v);
+  }
+}
+
 __global__ __launch_bounds__(256) void unpatchify_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ out, int T,
                                                          int Hp, int Wp, int C, int ldx, const int32_t* __restrict__ tok_perm) {
   // x [Ntok][C*4] feature (c, ph, pw) -> out (T, 2Hp, 2Wp, C)
@@ -684,6 +706,16 @@ int k5_launch_patchify(const float* x, void* out, int T, int H, int W, int C, in
   const int64_t total = (int64_t)T * (H / 2) * (W / 2) * Kpad;
   hipLaunchKernelGGL(patchify_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, (bf16_t*)out, T, H, W, C, Cin_total, Kpad,
                      tok_perm);
+  return done();
+}
+
+int k5_launch_patchify_cond(const float* x, const float* vcond, void* out, int T, int H, int W, int C, int Cin_total, int Kpad,
+                            const int32_t* tok_perm, hipStream_t s) {
+  if (!x || !vcond || T <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || Kpad < 4 * Cin_total || C <= 0 || C >= Cin_total)
+    return K5_ERR_ARG;
+  const int64_t total = (int64_t)T * (H / 2) * (W / 2) * Kpad;
+  hipLaunchKernelGGL(patchify_cond_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, vcond, (bf16_t*)out, T, H, W, C, Cin_total,
+                     Kpad, tok_perm);
   return done();
 }
 

@@ -122,6 +122,7 @@ SYMBOLS = {
     "k5_ln_affine_bf16": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "k5_rope_table_f32": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P]),
     "k5_patchify_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "k5_patchify_cond_bf16": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "k5_unpatchify_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "k5_cfg_euler": (_I, [_P, _P, _P, _F, _F, _I64, _P]),
     "k5_dit_create": (_I, [C.POINTER(DitConfig), C.POINTER(_P)]),
@@ -131,6 +132,7 @@ SYMBOLS = {
     "k5_dit_missing_keys": (_I, [_P]),
     "k5_dit_forward": (_I, [_P, C.POINTER(ForwardArgs), _P, _P]),
     "k5_sample": (_I, [_P, C.POINTER(SampleArgs), _P]),
+    "k5_sample_cond": (_I, [_P, C.POINTER(SampleArgs), _P, _P]),
     "k5_comm_unique_id": (_I, [C.c_char_p, _P]),
     "k5_dit_comm_init": (_I, [_P, C.c_char_p, _I, _I, _P]),
     "k5_conv3d_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),

@@ -2,7 +2,8 @@
 
 `generate` keeps the reference's positional signature (generation_utils.py:81-96) and its noise /
 sigma-schedule construction, but runs the Euler / CFG loop on the MI355X engine: in one C call
-(`DiffusionTransformer3D.sample` -> k5_sample) when `model` is the engine-backed DiT, otherwise step by
+(`DiffusionTransformer3D.sample` -> k5_sample, k5_sample_cond with visual conditioning) when `model` is the engine-backed
+DiT, otherwise step by
 step through `model(...)` (duck-typed models, e.g. a MagCache wrapper) with the fused CFG+Euler kernel.
 """
 import os
@@ -68,8 +69,11 @@ def sigma_schedule(num_steps, scheduler_scale, device="cpu"):
 
 @torch.no_grad()
 def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
-             null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=False, seed=6554, noise=None):
-    """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw."""
+             null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=False, seed=6554, noise=None, *,
+             visual_cond=None, visual_cond_mask=None):
+    """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
+    `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
+    the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other."""
     if noise is None:
         g = torch.Generator(device="cuda")
         g.manual_seed(seed)
@@ -77,6 +81,19 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     else:
         img = noise.to(device=device, dtype=torch.float32).clone()
     img = img.contiguous()
+
+    cond_in = None
+    if visual_cond is not None or visual_cond_mask is not None:
+        if not getattr(model, "visual_cond", False):
+            raise ValueError("visual_cond / visual_cond_mask need a model built with visual_cond=True")
+        mask_shape = tuple(img.shape[:-1]) + (1,)
+        vc = torch.zeros_like(img) if visual_cond is None else visual_cond.to(device=img.device, dtype=torch.float32)
+        vm = (torch.zeros(mask_shape, dtype=torch.float32, device=img.device) if visual_cond_mask is None
+              else visual_cond_mask.to(device=img.device, dtype=torch.float32))
+        if tuple(vc.shape) != tuple(img.shape) or tuple(vm.shape) != mask_shape:
+            raise ValueError(f"visual_cond must be {tuple(img.shape)} and visual_cond_mask {mask_shape}, got {tuple(vc.shape)} and "
+                             f"{tuple(vm.shape)}")
+        cond_in = (vc, vm)
 
     sparse_params = get_sparse_params(conf, {"visual": img}, device)
     timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()  # one sync, before the loop
@@ -98,7 +115,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         mine, mine_pos = (text_embeds, text_rope_pos) if branch == 0 else (null_text_embeds, null_text_rope_pos)
         both = None
         for timestep, timestep_diff in zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist()):
-            v = model(img, mine["text_embeds"], mine["pooled_embed"], torch.tensor([timestep]) * 1000, visual_rope_pos,
+            x = img if cond_in is None else torch.cat([img, *cond_in], dim=-1)
+            v = model(x, mine["text_embeds"], mine["pooled_embed"], torch.tensor([timestep]) * 1000, visual_rope_pos,
                       mine_pos, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
             if both is None:
                 both = torch.empty((2,) + tuple(v.shape), dtype=v.dtype, device=v.device)
@@ -109,14 +127,18 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         # whole loop inside the engine: no per-step host work at all
         model.sample(img, timesteps.tolist(), text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                      null_text_rope_pos, guidance_weight, scale_factor=conf.metrics.scale_factor,
-                     sparse_params=sparse_params)
+                     sparse_params=sparse_params,
+                     visual_cond=None if cond_in is None else torch.cat(cond_in, dim=-1).contiguous())
         return img
 
     for timestep, timestep_diff in zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist()):
         if model.visual_cond:
-            visual_cond = torch.zeros_like(img)
-            visual_cond_mask = torch.zeros([*img.shape[:-1], 1], dtype=img.dtype, device=img.device)
-            model_input = torch.cat([img, visual_cond, visual_cond_mask], dim=-1)
+            if cond_in is None:
+                vc = torch.zeros_like(img)
+                vm = torch.zeros([*img.shape[:-1], 1], dtype=img.dtype, device=img.device)
+            else:
+                vc, vm = cond_in
+            model_input = torch.cat([img, vc, vm], dim=-1)
         else:
             model_input = img
         t1000 = torch.tensor([timestep]) * 1000
@@ -166,10 +188,22 @@ def frames_to_uint8(frames):
 
 def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25, guidance_weight=5.0,
                     scheduler_scale=1, negative_caption="", seed=6554, device="cuda", vae_device="cuda",
-                    text_embedder_device="cuda", progress=True, offload=False):
+                    text_embedder_device="cuda", progress=True, offload=False, image=None):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
-    With `offload` each of the three models visits the GPU only for its own stage."""
+    With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
+    tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
+    sample."""
     batch, frames, height, width, channels = shape
+    cond_kw = {}
+    if image is not None:
+        from .conditioning import image_to_visual_cond
+        if offload:
+            vae.to(vae_device)
+        vc, vm = image_to_visual_cond(image, vae, frames, 8 * height, 8 * width, device=device, vae_device=vae_device)
+        if offload:
+            vae.to("cpu")
+            torch.cuda.empty_cache()
+        cond_kw = {"visual_cond": vc.repeat(batch, 1, 1, 1), "visual_cond_mask": vm.repeat(batch, 1, 1, 1)}
     kind = "image" if frames == 1 else "video"
     (cond, n_cond), (uncond, n_uncond) = _encode_prompts(text_embedder, (caption, negative_caption), kind, device)
     if offload:
@@ -182,7 +216,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     with torch.no_grad():
         latent = generate(dit, device, (batch * frames, height, width, channels), num_steps, cond, uncond, grid,
                           torch.arange(n_cond), torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
-                          progress=progress)
+                          progress=progress, **cond_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

@@ -279,14 +279,28 @@ class DiffusionTransformer3D(nn.Module):
 
     @torch.no_grad()
     def sample(self, latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
-               null_text_rope_pos, guidance_weight, scale_factor=(1.0, 1.0, 1.0), sparse_params=None):
+               null_text_rope_pos, guidance_weight, scale_factor=(1.0, 1.0, 1.0), sparse_params=None, visual_cond=None):
         """Whole Euler/CFG loop on device (generation_utils.py:80-129) in one C call.  `latent` fp32
-        (T,H,W,in_visual_dim) is updated in place; `sigmas` = the sigma schedule (num_steps+1 floats, host)."""
+        (T,H,W,in_visual_dim) is updated in place; `sigmas` = the sigma schedule (num_steps+1 floats, host).
+        `visual_cond` (optional, a model with visual_cond only): contiguous fp32 (T,H,W,in_visual_dim+1) on the latent's device, the
+        conditioning latent and its mask that fill the input channels the reference leaves zero (k5_sample_cond); None = k5_sample."""
         if not latent.is_cuda or latent.dtype != torch.float32 or not latent.is_contiguous():
             raise RuntimeError("latent must be a contiguous fp32 CUDA tensor")
+        T, H, W, _ = latent.shape
+        if visual_cond is not None:
+            if not self.visual_cond:
+                raise ValueError("visual_cond given to a model built with visual_cond=False")
+            want = (T, H, W, self.in_visual_dim + 1)
+            if not torch.is_tensor(visual_cond) or tuple(visual_cond.shape) != want:
+                raise ValueError(f"visual_cond must have shape {want}, got {tuple(getattr(visual_cond, 'shape', ()))}")
+            if visual_cond.dtype != torch.float32:
+                raise ValueError(f"visual_cond must be float32, got {visual_cond.dtype}")
+            if visual_cond.device != latent.device:
+                raise ValueError(f"visual_cond must be on {latent.device}, got {visual_cond.device}")
+            if not visual_cond.is_contiguous():
+                raise ValueError("visual_cond must be contiguous")
         h = self.engine(latent.device)
         dev = latent.device
-        T, H, W, _ = latent.shape
         keep = []
         te, pe = text_embeds["text_embeds"].to(dev), text_embeds["pooled_embed"].to(dev)
         s = E.SampleArgs()
@@ -299,7 +313,10 @@ class DiffusionTransformer3D(nn.Module):
         arr = (C.c_float * len(sig))(*sig)
         s.latent, s.num_steps, s.sigmas, s.guidance_weight = latent.data_ptr(), len(sig) - 1, arr, float(guidance_weight)
         with torch.cuda.device(dev):
-            E.check(E.lib().k5_sample(h, C.byref(s), E.stream_ptr(dev)), "k5_sample")
+            if visual_cond is None:
+                E.check(E.lib().k5_sample(h, C.byref(s), E.stream_ptr(dev)), "k5_sample")
+            else:
+                E.check(E.lib().k5_sample_cond(h, C.byref(s), visual_cond.data_ptr(), E.stream_ptr(dev)), "k5_sample_cond")
         return latent
 
     # ---------------------------------------------------------------- multi-GPU

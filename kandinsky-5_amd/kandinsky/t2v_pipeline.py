@@ -80,9 +80,13 @@ class Kandinsky5T2VPipeline:
     def __call__(self, text: str, time_length: int = 5, width: int = 768, height: int = 512, seed: int = None,
                  num_steps: int = None, guidance_weight: float = None, scheduler_scale: float = 10.0,
                  negative_caption: str = _NEG, expand_prompts: bool = True, save_path: str = None,
-                 progress: bool = True):
+                 progress: bool = True, image=None):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
-        rank 0 / list of PIL images for time_length = 0, None on the other ranks)."""
+        rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
+        the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
+        passes the same picture."""
+        if image is not None and time_length == 0:
+            raise ValueError("image conditioning needs a video (time_length > 0)")
         steps = self.num_steps if num_steps is None else num_steps
         weight = self.guidance_weight if guidance_weight is None else guidance_weight
         if seed is None:
@@ -95,6 +99,7 @@ class Kandinsky5T2VPipeline:
                                  text_embedder=self.text_embedder, num_steps=steps, guidance_weight=weight,
                                  scheduler_scale=scheduler_scale, negative_caption=negative_caption, seed=seed,
                                  device=self.device_map["dit"], vae_device=self.device_map["vae"],
-                                 text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload)
+                                 text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload,
+                                 image=image)
         torch.cuda.empty_cache()
         return self._save(images, time_length, save_path) if self.local_dit_rank == 0 else None

@@ -2,6 +2,7 @@
 README launch lines keep working against this package:
 
     python test.py --prompt "a cat in a blue hat" --config ./configs/config_5s_sft.yaml
+    python test.py --prompt "the cat turns its head" --image cat.png     # image-to-video: the clip starts from cat.png
     PYTHONPATH=. torchrun --nproc-per-node 8 --master-addr 127.0.0.1 test.py --config ./configs/config_10s_sft.yaml ...
 
 Multi-GPU: one process per GPU (LOCAL_RANK / WORLD_SIZE from the launcher); `get_T2V_pipeline` sets up token-sharded
@@ -35,6 +36,7 @@ def build_parser():
     p.add_argument("--scheduler_scale", type=float, default=5.0, help="sigma-schedule scale s in s*t/(1+(s-1)*t)")
     p.add_argument("--output_filename", type=str, default="./test.mp4", help="output path (.mp4 / .avi / .png)")
     p.add_argument("--offload", action="store_true", default=False, help="keep only the active model on the GPU")
+    p.add_argument("--image", type=str, default=None, help="image-to-video: a picture (PNG / JPEG) the clip starts from")
     p.add_argument("--magcache", action="store_true", default=False, help="MagCache: skip the visual blocks on low-error steps (50-step configs)")
     return p
 
@@ -53,10 +55,14 @@ def main(argv=None):
                             offload=args.offload, magcache=args.magcache)
     if args.output_filename is None:
         args.output_filename = "./" + args.prompt.replace(" ", "_") + ".mp4"
+    image = None
+    if args.image is not None:
+        from PIL import Image
+        image = Image.open(args.image).convert("RGB")
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
-         negative_caption=args.negative_prompt, save_path=args.output_filename)
+         negative_caption=args.negative_prompt, save_path=args.output_filename, image=image)
     print(f"TIME ELAPSED: {time.perf_counter() - t0}")
     print(f"Generated video is saved to {args.output_filename}")
 
