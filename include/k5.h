@@ -332,6 +332,33 @@ int k5_sample(k5_dit* dit, const k5_sample_args* args, void* stream);
  * given to a handle created with visual_cond = 0 or is not 4-byte aligned. */
 int k5_sample_cond(k5_dit* dit, const k5_sample_args* args, const float* visual_cond, void* stream);
 
+/* Several samples in one call (generate_sample's shape = (bs, frames, h, w, c), reference generation_utils.py:150): a CONVENIENCE entry point,
+ * not a batched kernel path.  The B samples of one (T, H, W) run ONE AFTER ANOTHER on the stream, each as k5_sample_cond on its own slice of
+ * the latents and the conditioning with its own prompts: the launches, the kernels and the cost per sample are those of B separate calls
+ * (DESIGN.md §5, §8), and every sample is bit-identical to the same sample (noise, prompt, negative prompt, conditioning) run alone through
+ * k5_sample / k5_sample_cond on the same handle with the same options.
+ * Refused (K5_ERR_STATE + message) on a handle in a sequence-parallel group or a CFG pair (any transport), with MagCache set or with
+ * k5_dit_set_graph on; K5_ERR_ARG for B < 1, a NULL or non-4-byte-aligned latents / visual_cond pointer, missing conds or null conds,
+ * or visual_cond on a handle created with visual_cond = 0.  Nothing is enqueued when the call is refused. */
+typedef struct k5_sample_many_args {
+  int B;
+  k5_forward_args fwd;               /* shared shape, RoPE positions, scale factor, attention type; fwd.x, fwd.cond, fwd.time ignored */
+  const k5_text_cond* conds;         /* HOST [B]: the prompt of each sample */
+  const k5_text_cond* null_conds;    /* HOST [B]: the negative prompt of each sample; used (and required) when |guidance_weight-1| > 1e-6 */
+  float* latents;                    /* device fp32 [B][T][H][W][in_visual_dim], in: noise, out: final latents */
+  const float* visual_cond;          /* device fp32 [B][T][H][W][in_visual_dim+1] (as k5_sample_cond, per sample) or NULL */
+  int num_steps;
+  const float* sigmas;               /* HOST [num_steps+1] */
+  float guidance_weight;
+} k5_sample_many_args;
+int k5_sample_many(k5_dit* dit, const k5_sample_many_args* args, void* stream);
+/* S forwards of the same (T, H, W) in one call, one after another (a convenience entry point like k5_sample_many): args->x is device fp32
+ * [S][T][H][W][args->x_channels], conds HOST [S], args->time shared; out_velocity bf16 [S][T][H][W][out_visual_dim].  Sequence i is
+ * k5_dit_forward(x[i], conds[i]) — the same entry point — on the handle as it was when the call began: the softmax-form memory that
+ * k5_dit_forward reads and updates is put back to its state at entry before every sequence and again at the end, so the call leaves the
+ * handle as it found it.  Refusals as k5_sample_many (S < 1 is K5_ERR_ARG). */
+int k5_dit_forward_many(k5_dit* dit, const k5_forward_args* args, int S, const k5_text_cond* conds, void* out_velocity, void* stream);
+
 /* Sequence parallelism (replaces the reference's DTensor head-parallel plan, kandinsky/models/parallelize.py:11-102,
  * keeps its launch contract LOCAL_RANK/WORLD_SIZE, kandinsky/utils.py:40-55): one process per GPU, rank r owns the
  * visual-token rows [r*N/world, (r+1)*N/world) (N a multiple of 64*world); K and V^T of every block are

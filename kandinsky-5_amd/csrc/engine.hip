@@ -427,6 +427,7 @@ struct k5_dit {
   bool fuse_now = false, leave_collect = false;
   int fuse_last = -1;                              // "attn_fuse_qnorm_used": what the last k5_sample decided (1 fused from step 1 on, 0 not, -1 not evaluated)
   DevBuf ws_leave_sig;
+  DevBuf ws_pref_snap;                             // k5_dit_forward_many: every block's AttnW::pref as the call found it
   unsigned int* h_leave_sig = nullptr;             // pinned
   bool row_offsets = true;                         // "attn_row_offsets": per-row offsets of the fixed-offset softmax (bound up to 190)
   bool anchor = true;                              // "attn_anchor": heads beyond that window run the fixed form on anchored offsets (one-GPU path)
@@ -2236,6 +2237,102 @@ extern "C" int k5_sample_cond(k5_dit* d, const k5_sample_args* a, const float* v
 }
 
 extern "C" int k5_sample(k5_dit* d, const k5_sample_args* a, void* stream) { return k5_sample_cond(d, a, nullptr, stream); }
+
+// What k5_sample_many / k5_dit_forward_many refuse before anything is enqueued: handle states whose per-call bookkeeping is not per sample (rank
+// groups exchange per forward, MagCache counts calls, a captured step is per call).
+static int many_state_ok(const k5_dit* d, const char* who) {
+  if (!d->finalized) { k5_set_error("%s before k5_dit_finalize", who); return K5_ERR_STATE; }
+  if (d->comm.active()) { k5_set_error("%s: the handle is in a sequence-parallel group", who); return K5_ERR_STATE; }
+  if (d->pair.active()) { k5_set_error("%s: the handle is in a CFG pair", who); return K5_ERR_STATE; }
+  if (d->mag.on) { k5_set_error("%s: MagCache is set on the handle", who); return K5_ERR_STATE; }
+  if (d->use_graph) { k5_set_error("%s: graph capture is on (k5_dit_set_graph)", who); return K5_ERR_STATE; }
+  return K5_OK;
+}
+
+// Several samples in one call, one after another: sample b is k5_sample_cond on its own slice of the latents / conditioning with its own
+// prompts, so it resets exactly the per-call state a call of its own would (text prologue cache, softmax-form memory, the query-norm
+// decision) and moves no bits.  No launch is shared between samples: the cost per sample is that of a separate call.
+extern "C" int k5_sample_many(k5_dit* d, const k5_sample_many_args* a, void* stream) {
+  g_err[0] = 0;
+  if (!d || !a) { k5_set_error("k5_sample_many: null handle or arguments"); return K5_ERR_ARG; }
+  K5CHK(many_state_ok(d, "k5_sample_many"));
+  const k5_dit_config& c = d->cfg;
+  if (a->B < 1) { k5_set_error("k5_sample_many: B must be >= 1 (got %d)", a->B); return K5_ERR_ARG; }
+  if (!a->latents || (reinterpret_cast<uintptr_t>(a->latents) & 3)) { k5_set_error("k5_sample_many: latents is NULL or not 4-byte aligned"); return K5_ERR_ARG; }
+  if (a->visual_cond && !c.visual_cond) { k5_set_error("k5_sample_many: visual_cond given to a handle created with visual_cond = 0"); return K5_ERR_ARG; }
+  if (a->visual_cond && (reinterpret_cast<uintptr_t>(a->visual_cond) & 3)) { k5_set_error("k5_sample_many: visual_cond is not 4-byte aligned"); return K5_ERR_ARG; }
+  if (!a->sigmas || a->num_steps <= 0) { k5_set_error("k5_sample_many: sigmas / num_steps"); return K5_ERR_ARG; }
+  const bool cfg_on = fabsf(a->guidance_weight - 1.0f) > 1e-6f;
+  if (!a->conds || (cfg_on && !a->null_conds)) { k5_set_error("k5_sample_many: conds%s missing", cfg_on ? " / null_conds" : ""); return K5_ERR_ARG; }
+  if (a->fwd.T <= 0 || a->fwd.H <= 0 || a->fwd.W <= 0) { k5_set_error("k5_sample_many: bad shapes"); return K5_ERR_ARG; }
+  const size_t thw = (size_t)a->fwd.T * a->fwd.H * a->fwd.W;
+  for (int b = 0; b < a->B; ++b) {
+    k5_sample_args one{};
+    one.fwd = a->fwd;
+    one.fwd.x = nullptr;
+    one.fwd.cond = a->conds[b];
+    if (cfg_on) one.null_cond = a->null_conds[b];
+    one.latent = a->latents + (size_t)b * thw * c.in_visual_dim;
+    one.num_steps = a->num_steps;
+    one.sigmas = a->sigmas;
+    one.guidance_weight = a->guidance_weight;
+    const float* vc = a->visual_cond ? a->visual_cond + (size_t)b * thw * (c.in_visual_dim + 1) : nullptr;
+    const int st = k5_sample_cond(d, &one, vc, stream);
+    if (st != K5_OK) {
+      if (!g_err[0]) k5_set_error("k5_sample_many: sample %d failed with status %d", b, st);
+      return st;
+    }
+  }
+  return K5_OK;
+}
+
+// S forwards of one (T, H, W), one after another: sequence i is k5_dit_forward on x[i] / conds[i] with the handle as the call found it.
+// k5_dit_forward reads and updates the softmax-form memory (AttnW::pref, which decides bits), so every block's memory is saved at entry and
+// put back before every sequence after the first and once more at the end.  A block whose memory was not allocated yet holds zeros in
+// effect (ensure_zeroed allocates it zeroed), so putting it back means zeroing what a sequence allocated.
+extern "C" int k5_dit_forward_many(k5_dit* d, const k5_forward_args* a, int S, const k5_text_cond* conds, void* out_velocity,
+                                    void* stream) {
+  g_err[0] = 0;
+  if (!d || !a) { k5_set_error("k5_dit_forward_many: null handle or arguments"); return K5_ERR_ARG; }
+  K5CHK(many_state_ok(d, "k5_dit_forward_many"));
+  if (S < 1) { k5_set_error("k5_dit_forward_many: S must be >= 1 (got %d)", S); return K5_ERR_ARG; }
+  if (!conds || !out_velocity) { k5_set_error("k5_dit_forward_many: conds / out_velocity missing"); return K5_ERR_ARG; }
+  if (!a->x || (reinterpret_cast<uintptr_t>(a->x) & 3)) { k5_set_error("k5_dit_forward_many: x is NULL or not 4-byte aligned"); return K5_ERR_ARG; }
+  if (reinterpret_cast<uintptr_t>(out_velocity) & 1) { k5_set_error("k5_dit_forward_many: out_velocity is not 2-byte aligned"); return K5_ERR_ARG; }
+  if (a->T <= 0 || a->H <= 0 || a->W <= 0 || a->x_channels <= 0) { k5_set_error("k5_dit_forward_many: bad shapes"); return K5_ERR_ARG; }
+  hipStream_t s = (hipStream_t)stream;
+  const size_t slot = (size_t)2 * d->Hh * 4;           // AttnW::pref of one block: [2][H] int
+  std::vector<char> had(d->vblocks.size(), 0);
+  size_t saved = 0;
+  for (size_t j = 0; j < d->vblocks.size(); ++j) had[j] = d->vblocks[j].self_attn.pref.p != nullptr;
+  for (char h : had) saved += h ? slot : 0;
+  if (saved) K5CHK(d->ws_pref_snap.ensure(d->vblocks.size() * slot));
+  auto put_back = [&](bool save) -> int {
+    for (size_t j = 0; j < d->vblocks.size(); ++j) {
+      DevBuf& pref = d->vblocks[j].self_attn.pref;
+      if (had[j]) {
+        char* snap = static_cast<char*>(d->ws_pref_snap.p) + j * slot;
+        HIPCHK(save ? hipMemcpyAsync(snap, pref.p, slot, hipMemcpyDeviceToDevice, s)
+                              : hipMemcpyAsync(pref.p, snap, slot, hipMemcpyDeviceToDevice, s));
+      } else if (!save && pref.p) HIPCHK(hipMemsetAsync(pref.p, 0, pref.bytes, s));
+    }
+    return K5_OK;
+  };
+  K5CHK(put_back(true));
+  const size_t thw = (size_t)a->T * a->H * a->W;
+  for (int i = 0; i < S; ++i) {
+    if (i) K5CHK(put_back(false));
+    k5_forward_args one = *a;
+    one.x = a->x + (size_t)i * thw * a->x_channels;
+    one.cond = conds[i];
+    const int st = k5_dit_forward(d, &one, static_cast<bf16_t*>(out_velocity) + (size_t)i * thw * d->cfg.out_visual_dim, stream);
+    if (st != K5_OK) {
+      if (!g_err[0]) k5_set_error("k5_dit_forward_many: sequence %d failed with status %d", i, st);
+      return st;
+    }
+  }
+  return put_back(false);
+}
 
 // W8A8 e4m3 feed-forward (BASELINE config 5).  Quantises W1 / W2 of every visual block per output channel on first enable.
 extern "C" int k5_dit_set_fp8(k5_dit* d, int enabled) {

@@ -48,6 +48,12 @@ class SampleArgs(C.Structure):
                 ("sigmas", C.POINTER(C.c_float)), ("guidance_weight", C.c_float)]
 
 
+class SampleManyArgs(C.Structure):
+    _fields_ = [("B", C.c_int), ("fwd", ForwardArgs), ("conds", C.POINTER(TextCond)), ("null_conds", C.POINTER(TextCond)),
+                ("latents", C.c_void_p), ("visual_cond", C.c_void_p), ("num_steps", C.c_int), ("sigmas", C.POINTER(C.c_float)),
+                ("guidance_weight", C.c_float)]
+
+
 class VaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int), ("out_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -133,6 +139,8 @@ SYMBOLS = {
     "k5_dit_forward": (_I, [_P, C.POINTER(ForwardArgs), _P, _P]),
     "k5_sample": (_I, [_P, C.POINTER(SampleArgs), _P]),
     "k5_sample_cond": (_I, [_P, C.POINTER(SampleArgs), _P, _P]),
+    "k5_sample_many": (_I, [_P, C.POINTER(SampleManyArgs), _P]),
+    "k5_dit_forward_many": (_I, [_P, C.POINTER(ForwardArgs), _I, C.POINTER(TextCond), _P, _P]),
     "k5_comm_unique_id": (_I, [C.c_char_p, _P]),
     "k5_dit_comm_init": (_I, [_P, C.c_char_p, _I, _I, _P]),
     "k5_conv3d_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P]),

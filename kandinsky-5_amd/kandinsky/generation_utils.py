@@ -70,10 +70,23 @@ def sigma_schedule(num_steps, scheduler_scale, device="cpu"):
 @torch.no_grad()
 def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
              null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=False, seed=6554, noise=None, *,
-             visual_cond=None, visual_cond_mask=None):
+             visual_cond=None, visual_cond_mask=None, batch=1):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
-    the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other."""
+    the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
+    `batch` (extension): `shape` = (batch*T, H, W, C) holds `batch` samples of T frames, sample b = frames [bT, (b+1)T) of the
+    one noise draw of the full shape (and of visual_cond / visual_cond_mask).  `text_embeds`, `null_text_embeds` and their rope
+    positions are then one value shared by all samples or a list of `batch`.  Every sample is bit-identical to a call of its own
+    with its noise slice: a single-rank engine DiT runs them in one k5_sample_many call, any other model one after another."""
+    from .models.dit import split_per_sample
+    batch = int(batch)
+    if batch < 1 or shape[0] % batch:
+        raise ValueError(f"shape[0] = {shape[0]} frames do not divide into batch={batch} samples")
+    many = any(isinstance(v, (list, tuple)) for v in (text_embeds, null_text_embeds))
+    if batch == 1 and many:
+        text_embeds, null_text_embeds, text_rope_pos, null_text_rope_pos = (
+            split_per_sample(v, 1, n)[0] for v, n in ((text_embeds, "text_embeds"), (null_text_embeds, "null_text_embeds"),
+                                                 (text_rope_pos, "text_rope_pos"), (null_text_rope_pos, "null_text_rope_pos")))
     if noise is None:
         g = torch.Generator(device="cuda")
         g.manual_seed(seed)
@@ -81,6 +94,10 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     else:
         img = noise.to(device=device, dtype=torch.float32).clone()
     img = img.contiguous()
+    if batch > 1:
+        return _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
+                               null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond,
+                               visual_cond_mask)
 
     cond_in = None
     if visual_cond is not None or visual_cond_mask is not None:
@@ -153,6 +170,49 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     return img
 
 
+def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
+                    null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond, visual_cond_mask):
+    """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
+    from .models.dit import split_per_sample
+    T = img.shape[0] // batch
+    tes, nes = split_per_sample(text_embeds, batch, "text_embeds"), split_per_sample(null_text_embeds, batch, "null_text_embeds")
+    tps = split_per_sample(text_rope_pos, batch, "text_rope_pos")
+    nps = split_per_sample(null_text_rope_pos, batch, "null_text_rope_pos")
+    for v, n in ((visual_cond, "visual_cond"), (visual_cond_mask, "visual_cond_mask")):
+        if v is not None and v.shape[0] != img.shape[0]:
+            raise ValueError(f"{n} must have {img.shape[0]} frames (batch={batch} x {T}), got {v.shape[0]}")
+
+    def part(v, b):
+        return None if v is None else v[b * T:(b + 1) * T]
+
+    from .models.dit import DiffusionTransformer3D
+    if type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) and model.many_ready() \
+            and getattr(model, "_cfg_parallel", None) is None:
+        cond = None
+        if visual_cond is not None or visual_cond_mask is not None:
+            if not model.visual_cond:
+                raise ValueError("visual_cond / visual_cond_mask need a model built with visual_cond=True")
+            vc = torch.zeros_like(img) if visual_cond is None else visual_cond.to(device=img.device, dtype=torch.float32)
+            vm = (torch.zeros(tuple(img.shape[:-1]) + (1,), dtype=torch.float32, device=img.device) if visual_cond_mask is None
+                  else visual_cond_mask.to(device=img.device, dtype=torch.float32))
+            if tuple(vc.shape) != tuple(img.shape) or tuple(vm.shape) != tuple(img.shape[:-1]) + (1,):
+                raise ValueError(f"visual_cond must be {tuple(img.shape)} and visual_cond_mask {tuple(img.shape[:-1]) + (1,)}, got "
+                                 f"{tuple(vc.shape)} and {tuple(vm.shape)}")
+            cond = torch.cat([vc, vm], dim=-1).reshape(batch, T, *img.shape[1:-1], img.shape[-1] + 1).contiguous()
+        sparse_params = get_sparse_params(conf, {"visual": img[:T]}, device)
+        timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()
+        model.sample_many(img.view(batch, T, *img.shape[1:]), timesteps.tolist(), tes, nes, visual_rope_pos, tps, nps,
+                           guidance_weight, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params, visual_cond=cond)
+        return img
+    # any other model (rank groups, MagCache, graph replay, wrapped or duck-typed models): today's path, one sample at a time
+    for b in range(batch):
+        img[b * T:(b + 1) * T] = generate(model, device, (T,) + tuple(img.shape[1:]), num_steps, tes[b], nes[b], visual_rope_pos,
+                                          tps[b], nps[b], guidance_weight, scheduler_scale, conf, progress=progress, seed=seed,
+                                          noise=img[b * T:(b + 1) * T], visual_cond=part(visual_cond, b),
+                                          visual_cond_mask=part(visual_cond_mask, b))
+    return img
+
+
 def _encode_prompts(text_embedder, prompts, kind, device):
     """[(embeds dict on `device`, number of text tokens)] for each prompt (reference generation_utils.py:153-176)."""
     out = []
@@ -192,8 +252,12 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
-    sample."""
+    sample.  `caption` (extension): one prompt for every sample, or a list of `bs` prompts, one per sample; the samples come from
+    one noise draw of the whole shape (see `generate`)."""
     batch, frames, height, width, channels = shape
+    captions = list(caption) if isinstance(caption, (list, tuple)) else [caption] * batch
+    if len(captions) != batch:
+        raise ValueError(f"{len(captions)} captions for bs={batch} samples")
     cond_kw = {}
     if image is not None:
         from .conditioning import image_to_visual_cond
@@ -205,7 +269,15 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
             torch.cuda.empty_cache()
         cond_kw = {"visual_cond": vc.repeat(batch, 1, 1, 1), "visual_cond_mask": vm.repeat(batch, 1, 1, 1)}
     kind = "image" if frames == 1 else "video"
-    (cond, n_cond), (uncond, n_uncond) = _encode_prompts(text_embedder, (caption, negative_caption), kind, device)
+    if batch == 1:
+        (cond, n_cond), (uncond, n_uncond) = _encode_prompts(text_embedder, (captions[0], negative_caption), kind, device)
+        text_pos = torch.arange(n_cond)
+    else:
+        distinct = list(dict.fromkeys(captions))   # a prompt shared by several samples is encoded once
+        *encoded, (uncond, n_uncond) = _encode_prompts(text_embedder, distinct + [negative_caption], kind, device)
+        by_prompt = dict(zip(distinct, encoded))
+        cond = [by_prompt[p][0] for p in captions]
+        text_pos = [torch.arange(by_prompt[p][1]) for p in captions]
     if offload:
         text_embedder = text_embedder.to("cpu")
 
@@ -215,8 +287,8 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         dit.to(device, non_blocking=True)
     with torch.no_grad():
         latent = generate(dit, device, (batch * frames, height, width, channels), num_steps, cond, uncond, grid,
-                          torch.arange(n_cond), torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
-                          progress=progress, **cond_kw)
+                          text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
+                          progress=progress, batch=batch, **cond_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

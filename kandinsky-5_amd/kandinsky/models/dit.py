@@ -56,6 +56,16 @@ def _broadcast_ipc_name(kind, is_root, world, group, src):
     return payload[0]
 
 
+def split_per_sample(value, n, name):
+    """One value per sample for the many-sample paths (`sample_many`, `generate(batch=)`): a list / tuple of `n` entries is taken as
+    it is; anything else — a dict of embeddings, a tensor of positions, a plain list of int positions — is shared by every sample."""
+    if isinstance(value, (list, tuple)) and not (len(value) > 0 and isinstance(value[0], int)):
+        if len(value) != n:
+            raise ValueError(f"{name} has {len(value)} entries for batch={n}")
+        return list(value)
+    return [value] * n
+
+
 class DiffusionTransformer3D(nn.Module):
     def __init__(
         self,
@@ -287,18 +297,7 @@ class DiffusionTransformer3D(nn.Module):
         if not latent.is_cuda or latent.dtype != torch.float32 or not latent.is_contiguous():
             raise RuntimeError("latent must be a contiguous fp32 CUDA tensor")
         T, H, W, _ = latent.shape
-        if visual_cond is not None:
-            if not self.visual_cond:
-                raise ValueError("visual_cond given to a model built with visual_cond=False")
-            want = (T, H, W, self.in_visual_dim + 1)
-            if not torch.is_tensor(visual_cond) or tuple(visual_cond.shape) != want:
-                raise ValueError(f"visual_cond must have shape {want}, got {tuple(getattr(visual_cond, 'shape', ()))}")
-            if visual_cond.dtype != torch.float32:
-                raise ValueError(f"visual_cond must be float32, got {visual_cond.dtype}")
-            if visual_cond.device != latent.device:
-                raise ValueError(f"visual_cond must be on {latent.device}, got {visual_cond.device}")
-            if not visual_cond.is_contiguous():
-                raise ValueError("visual_cond must be contiguous")
+        self._check_visual_cond(visual_cond, latent)
         h = self.engine(latent.device)
         dev = latent.device
         keep = []
@@ -318,6 +317,98 @@ class DiffusionTransformer3D(nn.Module):
             else:
                 E.check(E.lib().k5_sample_cond(h, C.byref(s), visual_cond.data_ptr(), E.stream_ptr(dev)), "k5_sample_cond")
         return latent
+
+    def _check_visual_cond(self, visual_cond, latent):
+        """visual_cond must be a contiguous fp32 tensor of latent.shape[:-1] + (in_visual_dim + 1,) on the latent's device."""
+        if visual_cond is None:
+            return
+        if not self.visual_cond:
+            raise ValueError("visual_cond given to a model built with visual_cond=False")
+        want = tuple(latent.shape[:-1]) + (self.in_visual_dim + 1,)
+        if not torch.is_tensor(visual_cond) or tuple(visual_cond.shape) != want:
+            raise ValueError(f"visual_cond must have shape {want}, got {tuple(getattr(visual_cond, 'shape', ()))}")
+        if visual_cond.dtype != torch.float32:
+            raise ValueError(f"visual_cond must be float32, got {visual_cond.dtype}")
+        if visual_cond.device != latent.device:
+            raise ValueError(f"visual_cond must be on {latent.device}, got {visual_cond.device}")
+        if not visual_cond.is_contiguous():
+            raise ValueError("visual_cond must be contiguous")
+
+    def many_ready(self):
+        """True when `sample_many` / `forward_many` are accepted: a single-rank handle without MagCache or graph replay."""
+        return (self._sp is None and self._cfg_pair is None and getattr(self, "mag_ratios", None) is None
+                and not self._settings["graph"])
+
+    @torch.no_grad()
+    def sample_many(self, latents, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
+                     guidance_weight, scale_factor=(1.0, 1.0, 1.0), sparse_params=None, visual_cond=None):
+        """B samples of one shape in one C call (k5_sample_many).  The samples run one after another inside the engine, at the cost of B
+        `sample` calls: a convenience, not a batched kernel path.  `latents` contiguous fp32 (B,T,H,W,in_visual_dim), updated in
+        place.  `text_embeds` / `text_rope_pos`: a list of B (a single dict / positions = the same prompt for every sample); likewise
+        `null_text_embeds` / `null_text_rope_pos`.  `visual_cond` (optional): fp32 (B,T,H,W,in_visual_dim+1).  Sample b is
+        bit-identical to `sample(latents[b], ...)` with its own prompts."""
+        if not torch.is_tensor(latents) or latents.dim() != 5:
+            raise ValueError(f"latents must be a (B,T,H,W,C) tensor, got {tuple(getattr(latents, 'shape', ()))}")
+        if not latents.is_cuda or latents.dtype != torch.float32 or not latents.is_contiguous():
+            raise RuntimeError("latents must be a contiguous fp32 CUDA tensor")
+        B, T, H, W, _ = latents.shape
+        if B < 1:
+            raise ValueError("latents must hold at least one sample")
+        self._check_visual_cond(visual_cond, latents)
+
+        cfg_on = abs(guidance_weight - 1.0) > 1e-6
+        tes, tps = split_per_sample(text_embeds, B, "text_embeds"), split_per_sample(text_rope_pos, B, "text_rope_pos")
+        h = self.engine(latents.device)
+        dev = latents.device
+        keep = []
+        conds = (E.TextCond * B)()
+        nulls = (E.TextCond * B)() if cfg_on else None
+        for b in range(B):
+            conds[b] = self._text_cond(tes[b]["text_embeds"].to(dev), tes[b]["pooled_embed"].to(dev), tps[b], keep)
+        if cfg_on:
+            nes, nps = split_per_sample(null_text_embeds, B, "null_text_embeds"), split_per_sample(null_text_rope_pos, B, "null_text_rope_pos")
+            for b in range(B):
+                nulls[b] = self._text_cond(nes[b]["text_embeds"].to(dev), nes[b]["pooled_embed"].to(dev), nps[b], keep)
+        s = E.SampleManyArgs()
+        s.B = B
+        s.fwd = self._forward_args((T, H, W), None, self.in_visual_dim, tes[0]["text_embeds"].to(dev), tes[0]["pooled_embed"].to(dev),
+                                   0.0, visual_rope_pos, tps[0], scale_factor, sparse_params, keep)
+        s.conds, s.null_conds = conds, nulls
+        sig = [float(v) for v in sigmas]
+        arr = (C.c_float * len(sig))(*sig)
+        s.latents, s.visual_cond = latents.data_ptr(), E.ptr(visual_cond)
+        s.num_steps, s.sigmas, s.guidance_weight = len(sig) - 1, arr, float(guidance_weight)
+        with torch.cuda.device(dev):
+            E.check(E.lib().k5_sample_many(h, C.byref(s), E.stream_ptr(dev)), "k5_sample_many")
+        return latents
+
+    @torch.no_grad()
+    def forward_many(self, x, text_embeds, time, visual_rope_pos, text_rope_pos, scale_factor=(1.0, 1.0, 1.0),
+                      sparse_params=None):
+        """S forwards in one C call, one after another (k5_dit_forward_many): x (S,T,H,W,C_in), `text_embeds` / `text_rope_pos` lists
+        of S.  Returns velocities (S,T,H,W,out_visual_dim) bf16; sequence i is bit-identical to `forward(x[i], ...)` on the model as it
+        was when the call began, and the call leaves the softmax-form memory as it found it."""
+        if not x.is_cuda:
+            raise RuntimeError("DiffusionTransformer3D.forward_many needs CUDA (HIP) tensors; there is no CPU fallback")
+        x = x.float().contiguous()
+        S, T, H, W, Cx = x.shape
+        if len(text_embeds) != S or len(text_rope_pos) != S:
+            raise ValueError(f"text_embeds / text_rope_pos need {S} entries")
+        h = self.engine(x.device)
+        keep = [x]
+        conds = (E.TextCond * S)()
+        for i in range(S):
+            conds[i] = self._text_cond(text_embeds[i]["text_embeds"].to(x.device), text_embeds[i]["pooled_embed"].to(x.device),
+                                       text_rope_pos[i], keep)
+        t_val = float(time.reshape(-1)[0]) if torch.is_tensor(time) else float(time)
+        a = self._forward_args((T, H, W), x.data_ptr(), Cx, text_embeds[0]["text_embeds"].to(x.device),
+                               text_embeds[0]["pooled_embed"].to(x.device), t_val, visual_rope_pos, text_rope_pos[0], scale_factor,
+                               sparse_params, keep)
+        out = torch.empty(S, T, H, W, self.out_visual_dim, dtype=torch.bfloat16, device=x.device)
+        with torch.cuda.device(x.device):
+            E.check(E.lib().k5_dit_forward_many(h, C.byref(a), S, conds, out.data_ptr(), E.stream_ptr(x.device)),
+                    "k5_dit_forward_many")
+        return out
 
     # ---------------------------------------------------------------- multi-GPU
     def enable_sequence_parallel(self, rank, world, device=None, group=None, src=0, transport=None):

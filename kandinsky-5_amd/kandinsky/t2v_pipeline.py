@@ -77,14 +77,15 @@ class Kandinsky5T2VPipeline:
                 write_video(path, clip.permute(1, 2, 3, 0).cpu(), fps=24)
         return images
 
-    def __call__(self, text: str, time_length: int = 5, width: int = 768, height: int = 512, seed: int = None,
+    def __call__(self, text: Union[str, list], time_length: int = 5, width: int = 768, height: int = 512, seed: int = None,
                  num_steps: int = None, guidance_weight: float = None, scheduler_scale: float = 10.0,
                  negative_caption: str = _NEG, expand_prompts: bool = True, save_path: str = None,
                  progress: bool = True, image=None):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
-        passes the same picture."""
+        passes the same picture.  `text` (extension) may be a list of prompts: they are sampled together (generate_sample with
+        bs = len(text), one seed) and one output is returned per prompt — uint8 (len(text),3,F,H,W) / a PIL list of len(text)."""
         if image is not None and time_length == 0:
             raise ValueError("image conditioning needs a video (time_length > 0)")
         steps = self.num_steps if num_steps is None else num_steps
@@ -93,9 +94,17 @@ class Kandinsky5T2VPipeline:
             seed = self._agree_on(lambda: int(torch.randint(2 ** 63 - 1, (1,)).item()))
         self._check_size(height, width)
         frames = 1 if time_length == 0 else time_length * 24 // 4 + 1
-        caption = self._agree_on(lambda: self._beautified(text), as_object=True) if expand_prompts else text
+        if isinstance(text, (list, tuple)):
+            if len(text) == 0:
+                raise ValueError("text must hold at least one prompt")
+            texts = list(text)
+            caption = (self._agree_on(lambda: [self._beautified(t) for t in texts], as_object=True) if expand_prompts
+                       else texts)
+        else:
+            caption = self._agree_on(lambda: self._beautified(text), as_object=True) if expand_prompts else text
+        bs = len(caption) if isinstance(caption, list) else 1
 
-        images = generate_sample((1, frames, height // 8, width // 8, 16), caption, self.dit, self.vae, self.conf,
+        images = generate_sample((bs, frames, height // 8, width // 8, 16), caption, self.dit, self.vae, self.conf,
                                  text_embedder=self.text_embedder, num_steps=steps, guidance_weight=weight,
                                  scheduler_scale=scheduler_scale, negative_caption=negative_caption, seed=seed,
                                  device=self.device_map["dit"], vae_device=self.device_map["vae"],
