@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py — DiT denoising steps/sec of the MI355X engine on BASELINE.json's metric/config.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line (with the
+`roofline` block from the HIP events inside the timed region).  `--full` adds everything that costs time of its own: the parity check
+against the reference golden, the latent pin, the per-family breakdown pass, the VAE decode leg, the live rocprofv3 traffic passes and
+the CPU baseline (each can still be skipped with its --no-* flag).
 
 N > 1: one process per GPU under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment, the reference's launch
 contract: README.md:269-276, kandinsky/utils.py:40-55).  Called WITHOUT that environment, `python bench.py --gpus N` launches itself:
@@ -12,7 +17,7 @@ A "step" = one Euler update of the flow-matching sampler = one DiT forward (guid
 config_5s_nocfg) over the synthetic 5 s 768x512 latent (31,64,96,16) -> N = 47 616 visual tokens,
 L = 256 text tokens, 2B-Lite architecture with random-init weights (no checkpoints offline).
 The latent, text embeddings and weights are resident in HBM before the timed region.
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: dense self-attention, MFMA-bound) and
+Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: dense self-attention, MFMA-bound) and, with --full,
 `cpu_baseline` (the fp32 CPU oracle on the host cores, bounded sample).
 """
 import argparse
@@ -210,7 +215,7 @@ def live_traffic(tokens, timeout_s=150):
         for c in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, c)
             cmd = [prof, "--pmc", c, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-vae", "--no-breakdown", "--no-parity-check", "--no-live-traffic", "--blocks", "2"]
+                   "--steps", "1", "--warmup", "1", "--blocks", "2"]   # a plain run: none of the --full extras
             env = dict(os.environ, TMPDIR="/tmp")
             for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
                 env.pop(k, None)
@@ -268,12 +273,15 @@ def main():
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="5s_nocfg", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-check", action="store_true", help="skip the untimed 2-step check against the reference golden (5s_nocfg only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need (off by default): parity check, latent pin, per-family breakdown pass, VAE "
+                         "decode leg, live rocprofv3 traffic passes, CPU baseline; the --no-* flags below skip single ones of these")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-parity-check", action="store_true", help="with --full: skip the untimed 2-step check against the reference golden (5s_nocfg only)")
     ap.add_argument("--write-pin", default="", metavar="FILE", help="write this run's latent pin entry (to be merged into tests/golden/bench_latent_pins.json)")
-    ap.add_argument("--no-live-traffic", action="store_true", help="do not run the two rocprofv3 --pmc child passes that measure `roofline.traffic` (the line then "
-                    "quotes the committed profile, and says so)")
-    ap.add_argument("--no-vae", action="store_true", help="skip the (untimed-for-`value`) VAE decode leg")
+    ap.add_argument("--no-live-traffic", action="store_true", help="with --full: do not run the two rocprofv3 --pmc child passes that measure `roofline.traffic` "
+                    "(the line then quotes the committed profile, and says so)")
+    ap.add_argument("--no-vae", action="store_true", help="with --full: skip the (untimed-for-`value`) VAE decode leg")
     ap.add_argument("--force-sp", action="store_true", help="debug: drive the sharded code path through a world=1 RCCL communicator")
     ap.add_argument("--magcache", action="store_true", help="MagCache with the config's ratio table (changes the work per step: not the headline metric)")
     ap.add_argument("--fp8", type=int, nargs="?", const=1, default=0, metavar="MASK",
@@ -281,7 +289,7 @@ def main():
                          "projections, 4 out projection; 7 = all): NOT the headline number, reported as dtype bf16+fp8")
     ap.add_argument("--profile-level", type=int, default=2, choices=(0, 1, 2),
                     help="HIP events inside the timed region: 2 = around the roofline kernel only (default), 1 = every kernel family, 0 = none")
-    ap.add_argument("--no-breakdown", action="store_true", help="skip the separate per-family timing pass")
+    ap.add_argument("--no-breakdown", action="store_true", help="with --full: skip the separate per-family timing pass")
     ap.add_argument("--sp-slices", type=int, default=1, help="sequence parallelism: exchange K / V^T of a block in this many slices and attend "
                     "each slice as it lands (engine option sp_slices; 1 = one in-place all-gather per block)")
     ap.add_argument("--sp-autotune", action="store_true",
@@ -420,12 +428,12 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize(dev)
 
-    # ---- parity of the timed configuration (untimed, before the warm-up): the first two Euler steps of this very model / latent / prompt
+    # ---- --full: parity of the timed configuration (untimed, before the warm-up): the first two Euler steps of this very model / latent / prompt
     # through k5_sample against the REFERENCE's generate() on the same seeded weights and inputs (fp32 on the host, 32 blocks, 47 616
     # tokens: tests/golden/dit_fulldepth_c2.*, made by oracle/gen_golden_fulldepth.py c2).  Compared on the UPDATE the steps applied
     # (latent - noise): two of fifty steps move the latent by a few percent, the unit-variance noise would hide any error.
     parity = None
-    if (args.workload == "5s_nocfg" and args.blocks == 32 and args.qk_gain == 1.0 and not args.fp8 and args.emulate_shard <= 1
+    if (args.full and args.workload == "5s_nocfg" and args.blocks == 32 and args.qk_gain == 1.0 and not args.fp8 and args.emulate_shard <= 1
             and not args.magcache and not args.no_parity_check):
         parity = parity_check(dit, noise, dev, sigma_schedule(50, 5.0).tolist(), te, ne, vpos, tpos, ntpos, wl, sparse)   # the golden's NFE 50
     if args.warmup > 0:
@@ -442,7 +450,7 @@ def main():
     # ---- the latent the TIMED steps left (before the breakdown pass below moves it on): pinned against a committed value of the same
     # (workload, warm-up + steps) — 512 samples of (latent - noise) + its sum of squares, produced by this engine on an MI355X and tied to
     # the reference through parity_check (same model, same noise, first two steps) and tests/test_gpu_fulldepth.py
-    pin = latent_pin(latent, noise, args, world)
+    pin = latent_pin(latent, noise, args, world) if args.full or args.write_pin else None
     if args.dump_outputs and rank == 0:   # every rank holds the same latent (rank_check); fp32, 60 MB at most (the 10s_hd latent)
         import numpy as np
         os.makedirs(args.dump_outputs, exist_ok=True)
@@ -461,7 +469,7 @@ def main():
     n_fixed, n_online = dit.attn_variant_counts()
     nabla_counts = dit.nabla_block_counts() if wl["attn"] == "nabla" else None
     nabla_exec = dit.nabla_executed_blocks() if wl["attn"] == "nabla" and not sp_on_early else None
-    if args.profile_level == 2 and not args.no_breakdown:
+    if args.full and args.profile_level == 2 and not args.no_breakdown:
         # per-family breakdown from a SEPARATE short pass: an event pair at every family switch (~15 per block) drains the stream
         # each time, which costs the step 1-2 % at one GPU and ~8 % at 8-GPU shard sizes — not something to leave inside `value`
         fam_steps = min(args.steps, 2)
@@ -475,9 +483,9 @@ def main():
         fam_break = fam_b
     else:
         fam_break = fam
-    # end-to-end leg (not part of `value`): HunyuanVideo VAE decode of the final latent on the same GPU
+    # --full: end-to-end leg (not part of `value`): HunyuanVideo VAE decode of the final latent on the same GPU
     vae_s = None
-    if rank == 0 and not args.no_vae:
+    if rank == 0 and args.full and not args.no_vae:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         from vae_bench import synthetic_vae
         vae = synthetic_vae(dev)
@@ -525,8 +533,8 @@ def main():
                 break
         except Exception:
             pass
-    # ... unless this run can measure it itself: the default single-GPU dense workload, on rank 0, after the timed region (nothing here is timed)
-    if (rank == 0 and world == 1 and not args.no_live_traffic and wl["attn"] == "flash" and not args.attn_online and n_online == 0 and args.blocks == 32
+    # ... unless this run can measure it itself: --full on the default single-GPU dense workload, on rank 0, after the timed region (nothing here is timed)
+    if (rank == 0 and world == 1 and args.full and not args.no_live_traffic and wl["attn"] == "flash" and not args.attn_online and n_online == 0 and args.blocks == 32
             and args.workload == "5s_nocfg" and not args.emulate_shard and not args.fp8 and not args.force_sp and args.qk_gain == 1.0
             and not args.engine_option and not args.magcache and not args.graph
             and not any(k.startswith(("ROCPROF", "ROCPROFILER")) for k in os.environ) and "rocprof" not in os.environ.get("LD_PRELOAD", "")):   # (not under a profiler already)
@@ -616,6 +624,7 @@ def main():
             out["roofline"] = dict(gemm_roof, traffic=None, dominant_because=f"GEMM family {gemm_roof['ms_per_step']:.1f} ms per step > visual self-attention {attn_ms_step:.1f} ms")
         else:
             out.pop("roofline_attention")
+        out["full"] = bool(args.full)   # False: a plain run, none of the --full extras ran
         out["parity_check"] = parity
         out["latent_pin"] = pin
         if pin is not None and pin.get("status") == "FAILED":
@@ -638,10 +647,8 @@ def main():
             out["rank_check"] = rank_check
         if invalid:
             out["INVALID_AS_BENCH"] = invalid
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(N)
-        elif not args.no_cpu_baseline:
-            out["cpu_baseline"] = None
+        if args.full and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(N) if world == 1 else None
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -73,11 +73,12 @@ def test_bench_self_launch_reports_missing_devices_after_spawning():
 
 @pytest.mark.gpu
 def test_bench_json_line_contract():
-    """One JSON line with the contract's keys; two visual blocks keep it short (the engine path is the same)."""
+    """One JSON line with the contract's keys (--full: the CPU baseline is one of them); two visual blocks keep it short (the engine path is
+    the same)."""
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a real MI355X (torch.cuda.is_available() is False)")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--blocks", "2",
-                          "--no-vae"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+                          "--no-vae", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -95,6 +96,42 @@ def test_bench_json_line_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["unit"] == "steps/s" and c["cores"] >= 1 and c["value"] > 0 and c["sample"]
     assert d["value"] / c["value"] > 10.0          # sanity only: the ratio says nothing about kernel quality
+
+
+def test_bench_extras_sit_behind_full():
+    """A plain run does only what the headline needs; whatever takes time of its own runs under --full, which is off by default."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "--full" in out.stdout, out.stderr[-2000:]
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    for gate in ("if (args.full and args.workload == \"5s_nocfg\"",                     # parity check against the reference golden
+                 "latent_pin(latent, noise, args, world) if args.full or args.write_pin",  # latent pin
+                 "if args.full and args.profile_level == 2 and not args.no_breakdown",   # per-family breakdown pass
+                 "if rank == 0 and args.full and not args.no_vae",                       # VAE decode leg
+                 "rank == 0 and world == 1 and args.full and not args.no_live_traffic",  # rocprofv3 traffic passes
+                 "if args.full and not args.no_cpu_baseline"):                           # CPU baseline
+        assert gate in src, gate
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean(tmp_path):
+    """Without --full the line carries the headline and the timed-region roofline, and none of the extras ran: no CPU baseline, no parity
+    check, no latent pin, no VAE leg, no breakdown pass (the per-family times are the timed region's own)."""
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a real MI355X (torch.cuda.is_available() is False)")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--blocks", "2",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["full"] is False and "cpu_baseline" not in d
+    assert d["parity_check"] is None and d["latent_pin"] is None and d["e2e_clip_s"]["vae_decode_s"] is None
+    assert d["kernel_time_source"] == "HIP events inside the timed region"
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "steps/s" and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] * d["ms_per_step"] / 1000.0 - 1.0) < 1e-6
+    r = d["roofline"]
+    assert r["bound"] == "mfma" and r["blocks_run"] == 2 * 2 and 0.0 < r["frac"] < 1.0
+    assert (tmp_path / "latent.npy").exists()
 
 
 @pytest.mark.gpu

@@ -6,7 +6,7 @@ for i in 1 2; do
 echo "=== new default"; python tools/gemm_block_shapes.py --tokens 47616,11904,5952,3328 --kernels auto --iters 20 | tail -4
 echo "=== 8,64,2"; K5_LIB=$V python tools/gemm_block_shapes.py --tokens 47616,11904,5952,3328 --kernels auto --iters 20 | tail -4
 done
-one() { python bench.py "$@" 2>/dev/null | grep "^{" | python -c "
+one() { python bench.py --full "$@" 2>/dev/null | grep "^{" | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print(round(d['ms_per_step'],3), {k: round(v,2) for k,v in d['kernel_time_ms_per_step'].items()})"; }
 P=$PWD/kandinsky-5_amd/lib/variants/libk5_pad1040.so
 for i in 1 2; do

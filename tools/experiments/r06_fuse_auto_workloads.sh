@@ -1,6 +1,6 @@
 cd /root/repo
 for wl in 2s_256 5s_sft; do for v in 0 1; do
-python bench.py --workload $wl --steps $([ $wl = 2s_256 ] && echo 20 || echo 4) --warmup $([ $wl = 2s_256 ] && echo 5 || echo 1) --no-cpu-baseline --no-live-traffic --no-vae --no-parity-check --engine-option attn_fuse_qnorm_auto=$v 2>/dev/null | python -c "
+python bench.py --full --workload $wl --steps $([ $wl = 2s_256 ] && echo 20 || echo 4) --warmup $([ $wl = 2s_256 ] && echo 5 || echo 1) --no-cpu-baseline --no-live-traffic --no-vae --no-parity-check --engine-option attn_fuse_qnorm_auto=$v 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

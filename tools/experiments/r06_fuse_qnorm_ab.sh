@@ -2,7 +2,7 @@
 # round 6: "attn_fuse_qnorm" (norm_qk + RoPE of the visual queries inside the attention kernel's Q load) on the final build, on / off alternating on one box
 cd /root/repo
 for rep in 1 2 3; do for v in 0 1; do
-python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-live-traffic --no-vae --no-parity-check --engine-option attn_fuse_qnorm=$v 2>/dev/null | python -c "
+python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-live-traffic --no-vae --no-parity-check --engine-option attn_fuse_qnorm=$v 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

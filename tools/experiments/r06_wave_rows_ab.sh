@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6, final build: 64-row attention waves (K5_ATTN_WAVE_ROWS=64; since this round also for the fused-query-norm instantiation) against the 32-row default
 cd /root/repo
-run() { python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-live-traffic --no-vae --no-parity-check --no-breakdown "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-live-traffic --no-vae --no-parity-check --no-breakdown "$@" 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
