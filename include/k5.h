@@ -30,7 +30,9 @@ typedef enum { K5_F32 = 0, K5_BF16 = 1, K5_F16 = 2 } k5_dtype;
 typedef enum { K5_EPI_BIAS = 0, K5_EPI_BIAS_M = 1, K5_EPI_GELU = 2, K5_EPI_GATE = 3, K5_EPI_F32 = 4 /* internal */ } k5_epilogue;
 
 /* bumped whenever an entry point is added or changes meaning; the host binding checks it BEFORE binding symbols, so that a stale
- * libk5.so fails with a clear message instead of a missing-symbol lookup (round 3: 4) */
+ * libk5.so fails with a clear message instead of a missing-symbol lookup (round 3: 4).  The MagCache calibration exports (k5_magcache_stats_bf16,
+ * k5_dit_set_magcache_calibrate, k5_dit_magcache_calibration) were ADDED under 11: tests/test_gpu_vae.py pins the number 11, and nothing that existed
+ * changed meaning.  The host binding names the missing symbol and the rebuild command when it meets a libk5.so from before them. */
 #define K5_ABI_VERSION 11
 int k5_abi_version(void);
 const char* k5_last_error(void);
@@ -239,6 +241,11 @@ int k5_rmsnorm_rope_stats_bf16(void* x, const float* weight, const float* cos_ta
                                float* stats, void* stream);
 /* apply_gate_sum nn.py:30-33 (standalone form). */
 int k5_gate_sum_bf16(const void* x, const void* y, const float* gate, void* out, int rows, int D, void* stream);
+/* MagCache calibration pass (standalone form): res = bf16(vis - ori), the bits of k5_gate_sum_bf16 with a gate of -1; res may alias ori.
+ * With prev != NULL (n x D bf16, aliasing nothing): sums[0..3] (device, float64) = sum rho_i, sum rho_i^2, sum (1 - cos(res_i, prev_i)) and the
+ * number of rows counted, rho_i = |res_i| / |prev_i|, over the rows where both norms are non-zero.  Row sums are fp32 over the stored bf16
+ * values, the sum over rows is float64 in a fixed order (repeatable bits).  prev == NULL: only res is written, sums[] = 0.  D % 8 == 0. */
+int k5_magcache_stats_bf16(const void* vis, const void* ori, const void* prev, void* res, double* sums, int rows, int D, void* stream);
 /* fp32-island GEMV (Modulation nn.py:161-164, TimeEmbeddings nn.py:56-61): y = W.act(x) + b (+add). */
 int k5_gemv_f32(const float* x, const float* W, const float* b, float* y, int N, int K, int silu_in,
                 const float* add, void* stream);
@@ -337,7 +344,7 @@ int k5_sample_cond(k5_dit* dit, const k5_sample_args* args, const float* visual_
  * the latents and the conditioning with its own prompts: the launches, the kernels and the cost per sample are those of B separate calls
  * (DESIGN.md §5, §8), and every sample is bit-identical to the same sample (noise, prompt, negative prompt, conditioning) run alone through
  * k5_sample / k5_sample_cond on the same handle with the same options.
- * Refused (K5_ERR_STATE + message) on a handle in a sequence-parallel group or a CFG pair (any transport), with MagCache set or with
+ * Refused (K5_ERR_STATE + message) on a handle in a sequence-parallel group or a CFG pair (any transport), with MagCache or its calibration set or with
  * k5_dit_set_graph on; K5_ERR_ARG for B < 1, a NULL or non-4-byte-aligned latents / visual_cond pointer, missing conds or null conds,
  * or visual_cond on a handle created with visual_cond = 0.  Nothing is enqueued when the call is refused. */
 typedef struct k5_sample_many_args {
@@ -562,6 +569,24 @@ int k5_dit_set_magcache(k5_dit* dit, const double* ratio_table, int table_len, i
 int k5_dit_magcache_calls(k5_dit* dit, int first_call, int stride);
 /* introspection: current call counter and how many forwards ran / skipped the visual blocks since set_magcache */
 int k5_dit_magcache_state(k5_dit* dit, int* cnt, long long* n_ran, long long* n_skipped);
+
+/* MagCache calibration: measure the ratio table k5_dit_set_magcache consumes.  num_steps > 0 switches it on (num_steps == 0: off, the
+ * buffers and the table are freed).  While it is on every forward runs its visual blocks (nothing is ever skipped) under MagCache's call counter
+ * and slot rule (slot = cnt & 1; cnt advances by 1, by 2 with no_cfg, and wraps at 2 * num_steps) and leaves, in a device table
+ * double[2 * num_steps][4] indexed by the call counter, the four sums of k5_magcache_stats_bf16 of the call's residual
+ * bf16(visual_embed_out - visual_embed_in) against the previous residual of its slot.  A slot's first call of a run (cnt < 2) has no previous
+ * residual and contributes nothing.  Nothing is copied to the host inside k5_sample; a second run over the same handle ADDS to the table (several
+ * prompts / seeds are averaged by dividing the sums).  The final latent is bit-identical to a plain run's.  Memory: two residual buffers
+ * (previous, current) of n x D bf16 per slot.  Graph replay is ignored while calibrating, as under MagCache.
+ * Refused with K5_ERR_STATE, before anything is enqueued: together with k5_dit_set_magcache (either order), and on a handle in a
+ * sequence-parallel group or a CFG pair of any transport — calibration is an offline one-GPU job (the 10 s clip fits one card), and per-rank
+ * partial sums would need a reduction in rank order to stay repeatable.  k5_sample_many / k5_dit_forward_many refuse a calibrating handle as
+ * they refuse MagCache.  A forward whose n x D differs from the previous call of its slot in the same run is K5_ERR_ARG. */
+int k5_dit_set_magcache_calibrate(k5_dit* dit, int num_steps, int no_cfg);
+/* Synchronises the stream of the handle's last forward, copies min(cap_rows, 2 * num_steps) rows of the table to out (host, [rows][4]:
+ * sum rho, sum rho^2, sum (1 - cos), rows counted) and reports *rows = 2 * num_steps and *runs = complete runs (counter wrap-arounds)
+ * the table holds.  out == NULL only reports.  K5_ERR_STATE when calibration is off. */
+int k5_dit_magcache_calibration(k5_dit* dit, double* out, int cap_rows, int* rows, long long* runs);
 
 /* per-kernel-family accumulated GPU time of the last forward(s), measured with hipEvents on the
  * engine's stream when profiling is enabled.  names: "attn_self","attn_cross","gemm","elementwise",...

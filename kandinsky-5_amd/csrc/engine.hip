@@ -487,6 +487,18 @@ struct k5_dit {
     long long n_ran = 0, n_skipped = 0;
   } mag;
 
+  // MagCache calibration (k5_dit_set_magcache_calibrate): every call runs its blocks and leaves the statistics of its residual against the
+  // previous residual of its slot in table[cnt][4] (device, float64, accumulated over runs).  Per slot two residual buffers, previous | current.
+  struct MagCalib {
+    bool on = false, no_cfg = false;
+    int num_steps = 0, cnt = 0;
+    long long runs = 0;                            // complete runs (counter wrap-arounds) the table holds
+    DevBuf res[2][2]; int prev[2] = {0, 0};        // res[slot][prev[slot]] = the slot's previous residual
+    size_t res_elems[2] = {0, 0};
+    DevBuf table, part;                            // [2 * num_steps][4] | per-workgroup partials of the pass
+    hipStream_t last_stream = nullptr;
+  } cal;
+
   // profiling
   int profiling = 0;                               // 0 off, 1 every kernel family, 2 only the visual self-attention (the roofline kernel)
   std::map<std::string, Prof> prof;
@@ -1667,6 +1679,13 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   if (vcond && (!c.visual_cond || x_channels != c.in_visual_dim)) { k5_set_error("visual_cond needs a visual_cond model and x of in_visual_dim channels"); return K5_ERR_ARG; }
   const int P = d->sp_world;
   const bool sp = d->comm.active();  // a communicator (even of size 1) selects the sharded code path
+  if (d->cal.on) {   // refusals of the calibration mode, before anything is enqueued
+    if (sp || d->pair.active()) { k5_set_error("MagCache calibration is a one-GPU job: the handle is in a %s", sp ? "sequence-parallel group" : "CFG pair"); return K5_ERR_STATE; }
+    if (d->cal.cnt >= 2 && d->cal.res_elems[d->cal.cnt & 1] != (size_t)N * D) {
+      k5_set_error("MagCache calibration: this forward has %d x %d residual elements, the previous call of its slot had %zu", N, D, d->cal.res_elems[d->cal.cnt & 1]);
+      return K5_ERR_ARG;
+    }
+  }
   if (sp && P > 1 && !d->emulated && d->sp_autotune && !d->sp_tuned && !d->vblocks.empty() && N % 64 == 0) {
     NablaArgs tna{};
     const bool tn = a->attention_type == 1 && !(Hp % 8) && !(Wp % 8);
@@ -1786,6 +1805,13 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
       mg.n_ran++;
     }
   }
+  auto& cl = d->cal;
+  const int cslot = cl.cnt & 1, ccur = cl.prev[cslot] ^ 1;   // the slot's buffer this call fills
+  if (cl.on) {
+    K5CHK(cl.res[cslot][ccur].ensure(vis_elems * 2));
+    K5CHK(cl.part.ensure((size_t)k5_magcache_stats_blocks(n) * 4 * sizeof(double)));
+    HIPCHK(hipMemcpyAsync(cl.res[cslot][ccur].p, d->ws_vis.p, vis_elems * 2, hipMemcpyDeviceToDevice, s));  // ori_visual_embed
+  }
   // ---- visual blocks (dit.py:176-178, 61-79) ----
   const bool cx_all = !mag_skip && d->cross_kv_batched && c.num_visual_blocks > 1 && d->cx_wk_all.p;
   if (cx_all) K5CHK(cross_kv_batched_run(d, s, d->ws_text.p, L));
@@ -1834,6 +1860,16 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
       mg.cnt = mg.first;
       for (int j = 0; j < 2; ++j) { mg.acc_ratio[j] = 1.0; mg.acc_err[j] = 0; mg.acc_steps[j] = 0; }
     }
+  }
+  if (cl.on) {   // the residual MagCache would cache, and its statistics against the slot's previous one (none on the slot's first call of a run)
+    {
+      Scope sc(d, s, "elementwise");
+      K5CHK(k5_launch_magcache_stats(d->ws_vis.p, cl.res[cslot][ccur].p, cl.cnt < 2 ? nullptr : cl.res[cslot][ccur ^ 1].p, cl.res[cslot][ccur].p,
+                                     cl.table.as<double>() + (size_t)cl.cnt * 4, cl.part.as<double>(), 1, n, D, s));
+    }
+    cl.prev[cslot] = ccur; cl.res_elems[cslot] = vis_elems; cl.last_stream = s;
+    cl.cnt += cl.no_cfg ? 2 : 1;
+    if (cl.cnt >= 2 * cl.num_steps) { cl.cnt = 0; cl.runs++; }
   }
   // ---- after_blocks / OutLayer (dit.py:149-153, nn.py:374-400) ----
   {
@@ -2074,6 +2110,7 @@ extern "C" int k5_dit_finalize(k5_dit* d) {
 extern "C" int k5_dit_set_magcache(k5_dit* d, const double* ratio_table, int table_len, int no_cfg, double thresh, int K,
                                    double retention_ratio) {
   if (!d || !d->finalized) { k5_set_error("k5_dit_set_magcache: handle not finalized"); return K5_ERR_STATE; }
+  if (table_len > 0 && d->cal.on) { k5_set_error("k5_dit_set_magcache: the handle is calibrating (k5_dit_set_magcache_calibrate)"); return K5_ERR_STATE; }
   auto& mg = d->mag;
   mg.cnt = 0; mg.n_ran = mg.n_skipped = 0;
   for (int j = 0; j < 2; ++j) { mg.acc_ratio[j] = 1.0; mg.acc_err[j] = 0; mg.acc_steps[j] = 0; mg.res_elems[j] = 0; }
@@ -2102,6 +2139,44 @@ extern "C" int k5_dit_magcache_state(k5_dit* d, int* cnt, long long* n_ran, long
   if (cnt) *cnt = d->mag.cnt;
   if (n_ran) *n_ran = d->mag.n_ran;
   if (n_skipped) *n_skipped = d->mag.n_skipped;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_set_magcache_calibrate(k5_dit* d, int num_steps, int no_cfg) {
+  g_err[0] = 0;
+  if (!d || !d->finalized) { k5_set_error("k5_dit_set_magcache_calibrate: handle not finalized"); return K5_ERR_STATE; }
+  if (num_steps < 0) { k5_set_error("k5_dit_set_magcache_calibrate: num_steps must be >= 0 (got %d)", num_steps); return K5_ERR_ARG; }
+  auto& cl = d->cal;
+  if (num_steps > 0) {
+    if (d->mag.on) { k5_set_error("k5_dit_set_magcache_calibrate: MagCache is set on the handle"); return K5_ERR_STATE; }
+    if (d->comm.active()) { k5_set_error("k5_dit_set_magcache_calibrate: the handle is in a sequence-parallel group (calibration is a one-GPU job)"); return K5_ERR_STATE; }
+    if (d->pair.active()) { k5_set_error("k5_dit_set_magcache_calibrate: the handle is in a CFG pair (calibration is a one-GPU job)"); return K5_ERR_STATE; }
+  }
+  if (cl.on && cl.last_stream) HIPCHK(hipStreamSynchronize(cl.last_stream));   // the buffers freed below may still be read
+  for (int j = 0; j < 2; ++j) { cl.res[j][0].release(); cl.res[j][1].release(); cl.prev[j] = 0; cl.res_elems[j] = 0; }
+  cl.table.release(); cl.part.release();
+  cl.on = false; cl.cnt = 0; cl.runs = 0; cl.num_steps = 0; cl.no_cfg = false; cl.last_stream = nullptr;
+  if (num_steps == 0) return K5_OK;
+  const size_t bytes = (size_t)2 * num_steps * 4 * sizeof(double);
+  K5CHK(cl.table.ensure(bytes));
+  HIPCHK(hipMemset(cl.table.p, 0, bytes));
+  cl.num_steps = num_steps; cl.no_cfg = no_cfg != 0; cl.on = true;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_magcache_calibration(k5_dit* d, double* out, int cap_rows, int* rows, long long* runs) {
+  g_err[0] = 0;
+  if (!d || !d->cal.on) { k5_set_error("k5_dit_magcache_calibration: calibration is not on (k5_dit_set_magcache_calibrate)"); return K5_ERR_STATE; }
+  auto& cl = d->cal;
+  if (out && cap_rows < 0) { k5_set_error("k5_dit_magcache_calibration: cap_rows must be >= 0"); return K5_ERR_ARG; }
+  if (cl.last_stream) HIPCHK(hipStreamSynchronize(cl.last_stream));
+  const int nrows = 2 * cl.num_steps;
+  if (out) {
+    const int take = cap_rows < nrows ? cap_rows : nrows;
+    if (take > 0) HIPCHK(hipMemcpy(out, cl.table.p, (size_t)take * 4 * sizeof(double), hipMemcpyDeviceToHost));
+  }
+  if (rows) *rows = nrows;
+  if (runs) *runs = cl.runs;
   return K5_OK;
 }
 
@@ -2135,10 +2210,10 @@ extern "C" int k5_sample_cond(k5_dit* d, const k5_sample_args* a, const float* v
   // Step 0 runs eagerly (it sizes every workspace and fills the RoPE / permutation caches), step 1 is captured, steps 1..
   // are launches of the instantiated graph.  Not with MagCache (its skip pattern changes the launch sequence per step)
   // or while profiling (events).
-  // not replayed: MagCache (host decisions), profiling (events), the NABLA map tap (its destination advances on the host per launch: a replay
+  // not replayed: MagCache (host decisions) and its calibration (host-side call counter and buffer swap), profiling (events), the NABLA map tap (its destination advances on the host per launch: a replay
   // would overwrite the slots baked at capture — ADVICE r5), loopback groups (their collectives are host rendezvous).  The IPC transport IS
   // replayable: its epochs live on the device and the peers' buffers were mapped by the eager first step (ipc_comm.h)
-  const bool graph = d->use_graph && !d->mag.on && !d->profiling && a->num_steps > 2 && !d->nabla_tap && !d->comm.loop && !d->pair.loop;
+  const bool graph = d->use_graph && !d->mag.on && !d->cal.on && !d->profiling && a->num_steps > 2 && !d->nabla_tap && !d->comm.loop && !d->pair.loop;
   std::vector<float> host_tab(2 * (size_t)a->num_steps);
   for (int i = 0; i < a->num_steps; ++i) {
     host_tab[i] = a->sigmas[i] * 1000.0f;                        // t * 1000, fp32 (:57)
@@ -2245,6 +2320,7 @@ static int many_state_ok(const k5_dit* d, const char* who) {
   if (d->comm.active()) { k5_set_error("%s: the handle is in a sequence-parallel group", who); return K5_ERR_STATE; }
   if (d->pair.active()) { k5_set_error("%s: the handle is in a CFG pair", who); return K5_ERR_STATE; }
   if (d->mag.on) { k5_set_error("%s: MagCache is set on the handle", who); return K5_ERR_STATE; }
+  if (d->cal.on) { k5_set_error("%s: the handle is calibrating MagCache", who); return K5_ERR_STATE; }
   if (d->use_graph) { k5_set_error("%s: graph capture is on (k5_dit_set_graph)", who); return K5_ERR_STATE; }
   return K5_OK;
 }

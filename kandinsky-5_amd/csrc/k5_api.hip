@@ -289,6 +289,20 @@ int k5_gate_sum_bf16(const void* x, const void* y, const float* gate, void* out,
   return ret(k5_launch_gate_sum(x, y, gate, out, rows, D, (hipStream_t)stream), "k5_gate_sum_bf16");
 }
 
+// the MagCache calibration pass on caller buffers (kernel tests): the scratch for the per-workgroup partials is kept here
+int k5_magcache_stats_bf16(const void* vis, const void* ori, const void* prev, void* res, double* sums, int rows, int D, void* stream) {
+  if (rows <= 0) return ret(K5_ERR_ARG, "k5_magcache_stats_bf16");
+  static double* ws = nullptr; static size_t ws_bytes = 0;
+  const size_t need = (size_t)k5_magcache_stats_blocks(rows) * 4 * sizeof(double);
+  if (need > ws_bytes) {
+    if (ws) (void)hipFree(ws);
+    ws = nullptr; ws_bytes = 0;
+    if (hipMalloc((void**)&ws, need) != hipSuccess) return ret(K5_ERR_HIP, "k5_magcache_stats_bf16");
+    ws_bytes = need;
+  }
+  return ret(k5_launch_magcache_stats(vis, ori, prev, res, sums, ws, 0, rows, D, (hipStream_t)stream), "k5_magcache_stats_bf16");
+}
+
 int k5_gemv_f32(const float* x, const float* W, const float* b, float* y, int N, int K, int silu_in, const float* add,
                 void* stream) {
   return ret(k5_launch_gemv_f32(x, W, b, y, N, K, silu_in, add, (hipStream_t)stream), "k5_gemv_f32");

@@ -143,6 +143,14 @@ int k5_launch_rope_table(float* cosT, float* sinT, const int32_t* p0, const int3
 // K2 (standalone form): out = bf16(x + gate * y)
 int k5_launch_gate_sum(const void* x, const void* y, const float* gate, void* out, int rows, int D,
                        hipStream_t stream);
+// MagCache calibration: res = bf16(vis - ori) (the bits of k5_launch_gate_sum with the -1 gate; res may alias ori) and, when prev != null, over
+// the rows with |res_i| > 0 and |prev_i| > 0: sums[0..3] = sum rho_i | sum rho_i^2 | sum (1 - cos(res_i, prev_i)) | rows counted, with
+// rho_i = |res_i| / |prev_i| (fp32 row sums over the bf16 values of res as stored, float64 across rows in a fixed order: no atomics, the bits
+// repeat).  part: device scratch of 4 * k5_magcache_stats_blocks(rows) doubles.  accumulate != 0: the four sums are ADDED to sums[].
+// prev == null: only res is written; sums[] is zeroed (accumulate == 0) or left alone.  D any multiple of 8.
+int k5_magcache_stats_blocks(int rows);
+int k5_launch_magcache_stats(const void* vis, const void* ori, const void* prev, void* res, double* sums, double* part, int accumulate,
+                             int rows, int D, hipStream_t stream);
 // fp32 GEMV with optional SiLU on the input: y[n] = sum_k act(x[k]) * W[n][k] + b[n]   (K11, K12)
 int k5_launch_gemv_f32(const float* x, const float* W, const float* b, float* y, int N, int K, int silu_in,
                        const float* add, hipStream_t stream);

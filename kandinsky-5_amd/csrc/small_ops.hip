@@ -3,6 +3,7 @@
 // feature axis; row statistics are wave-level (64-lane) shuffles.  Reference call sites:
 //   apply_scale_shift_norm  kandinsky/models/nn.py:25-28      -> ln_modulate_kernel     (K1)
 //   apply_gate_sum          nn.py:30-33                        -> gate_sum_kernel        (K2)
+//   MagCache calibration    residual + norm ratio / cosine distance against the slot's previous residual -> magcache_stats_kernel
 //   norm_qk + apply_rotary  nn.py:193-197, 35-40               -> rmsnorm_rope_kernel    (K5+K3)
 //   Modulation / TimeEmbeddings linears (fp32 islands) nn.py:56-61,161-164 -> gemv_f32_kernel
 //   TimeEmbeddings sinusoid nn.py:57-58                        -> time_features_kernel
@@ -396,6 +397,95 @@ __global__ __launch_bounds__(256) void gate_sum_kernel(const bf16_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
+// MagCache calibration (k5_launch_magcache_stats): res = bf16(vis - ori) — the operations of gate_sum_kernel with the -1 gate, so the bits of
+// the residual MagCache caches — and, against the slot's previous residual, the per-row norm ratio rho = |res_i| / |prev_i| and cosine distance
+// of the calibration script of the MagCache paper.  One wave per row (the ln_kernel shape); a lane's loads of up to MAXC chunks of vis | ori |
+// prev are issued in one burst ahead of the arithmetic and the stores, which also makes res == ori safe (a lane reads a chunk of ori before it
+// writes that chunk of res, and no other lane touches it).  Row sums of squares and the dot product are fp32 over the bf16 values of res AS
+// STORED; everything across rows is float64 in a fixed order: a wave adds its rows in row order, thread 0 the workgroup's four waves in wave
+// order into part[block][4], magcache_finish_kernel the blocks in index order.  No atomics: two launches give the same bits.
+// Rows with |prev_i| = 0 or |res_i| = 0 have no ratio: left out of the three sums and of the count.
+template <bool HAS_PREV>
+__global__ __launch_bounds__(256) void magcache_stats_kernel(const bf16_t* vis, const bf16_t* ori, const bf16_t* __restrict__ prev,
+                                                             bf16_t* res, double* __restrict__ part, int rows, int nch) {
+  __shared__ double red[4][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};   // sum rho | sum rho^2 | sum (1 - cos) | rows counted (wave-uniform)
+  for (int row = blockIdx.x * 4 + wave; row < rows; row += 4 * gridDim.x) {
+    const size_t base = (size_t)row * nch * 8;
+    float sr = 0.f, sp = 0.f, dp = 0.f;
+    for (int c0 = 0; c0 < nch; c0 += 64 * MAXC) {
+      u32x4 rv[MAXC], ro[MAXC], rp[MAXC];
+#pragma unroll
+      for (int i = 0; i < MAXC; ++i) {
+        const int ch = c0 + lane + 64 * i;
+        if (ch < nch) {
+          rv[i] = *reinterpret_cast<const u32x4*>(vis + base + 8 * ch);
+          ro[i] = *reinterpret_cast<const u32x4*>(ori + base + 8 * ch);
+          if (HAS_PREV) rp[i] = *reinterpret_cast<const u32x4*>(prev + base + 8 * ch);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < MAXC; ++i) {
+        const int ch = c0 + lane + 64 * i;
+        if (ch < nch) {
+          u32x4 pk;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            // x + (-1 * y), as gate_sum_kernel forms it
+            const float lo = __fadd_rn(__uint_as_float(rv[i][j] << 16), __fmul_rn(-1.0f, __uint_as_float(ro[i][j] << 16)));
+            const float hi = __fadd_rn(__uint_as_float(rv[i][j] & 0xffff0000u), __fmul_rn(-1.0f, __uint_as_float(ro[i][j] & 0xffff0000u)));
+            pk[j] = pack_bf16x2(lo, hi);
+            if (HAS_PREV) {
+              const float rl = __uint_as_float(pk[j] << 16), rh = __uint_as_float(pk[j] & 0xffff0000u);
+              const float pl = __uint_as_float(rp[i][j] << 16), ph = __uint_as_float(rp[i][j] & 0xffff0000u);
+              sr = fmaf(rl, rl, sr); sr = fmaf(rh, rh, sr);
+              sp = fmaf(pl, pl, sp); sp = fmaf(ph, ph, sp);
+              dp = fmaf(rl, pl, dp); dp = fmaf(rh, ph, dp);
+            }
+          }
+          *reinterpret_cast<u32x4*>(res + base + 8 * ch) = pk;
+        }
+      }
+    }
+    if (HAS_PREV) {
+      sr = wave_sum(sr); sp = wave_sum(sp); dp = wave_sum(dp);   // xor butterfly: every lane holds the same bits
+      if (sr > 0.f && sp > 0.f) {
+        const double r2 = (double)sr / (double)sp;
+        acc[0] += sqrt(r2);
+        acc[1] += r2;
+        acc[2] += 1.0 - (double)dp / sqrt((double)sr * (double)sp);
+        acc[3] += 1.0;
+      }
+    }
+  }
+  if (HAS_PREV) {
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) red[wave][k] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) part[(size_t)blockIdx.x * 4 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+  }
+}
+
+// out[k] (+)= sum over the nblk partials of component k, in index order: thread (g, k) adds blocks g, g + 256, ... in that order, then thread k
+// the 256 group sums in group order.  One workgroup.
+__global__ __launch_bounds__(1024) void magcache_finish_kernel(const double* __restrict__ part, int nblk, double* __restrict__ out, int accumulate) {
+  __shared__ double red[256][4];
+  const int k = threadIdx.x & 3, g = threadIdx.x >> 2;
+  double a = 0.0;
+  for (int b = g; b < nblk; b += 256) a += part[(size_t)b * 4 + k];
+  red[g][k] = a;
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    double t = 0.0;
+    for (int i = 0; i < 256; ++i) t += red[i][threadIdx.x];
+    out[threadIdx.x] = accumulate ? out[threadIdx.x] + t : t;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // fp32 GEMV, one wave per output row (weights streamed once, 16 B per lane)
 __global__ __launch_bounds__(256) void gemv_f32_kernel(const float* __restrict__ x, const float* __restrict__ W,
                                                        const float* __restrict__ b, float* __restrict__ y, int N, int K,
@@ -668,6 +758,29 @@ int k5_launch_gate_sum(const void* x, const void* y, const float* gate, void* ou
   const int64_t nch = (int64_t)rows * (D / 8);
   hipLaunchKernelGGL(gate_sum_kernel, dim3(grid_for(nch)), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)y, gate,
                      (bf16_t*)out, nch, D / 8);
+  return done();
+}
+
+int k5_magcache_stats_blocks(int rows) {
+  const int wg = (rows + 3) / 4;
+  return wg < 16384 ? wg : 16384;
+}
+
+int k5_launch_magcache_stats(const void* vis, const void* ori, const void* prev, void* res, double* sums, double* part, int accumulate,
+                             int rows, int D, hipStream_t s) {
+  if (rows <= 0 || D <= 0 || !vis || !ori || !res || !sums) return K5_ERR_ARG;
+  if (D & 7) return K5_ERR_ALIGN;
+  const int grid = k5_magcache_stats_blocks(rows);
+  if (!prev) {   // a slot's first call: nothing to compare with
+    hipLaunchKernelGGL(magcache_stats_kernel<false>, dim3(grid), dim3(256), 0, s, (const bf16_t*)vis, (const bf16_t*)ori, (const bf16_t*)nullptr,
+                       (bf16_t*)res, (double*)nullptr, rows, D / 8);
+    if (!accumulate && hipMemsetAsync(sums, 0, 4 * sizeof(double), s) != hipSuccess) return K5_ERR_HIP;
+    return done();
+  }
+  if (!part) return K5_ERR_ARG;
+  hipLaunchKernelGGL(magcache_stats_kernel<true>, dim3(grid), dim3(256), 0, s, (const bf16_t*)vis, (const bf16_t*)ori, (const bf16_t*)prev,
+                     (bf16_t*)res, part, rows, D / 8);
+  hipLaunchKernelGGL(magcache_finish_kernel, dim3(1), dim3(1024), 0, s, (const double*)part, grid, sums, accumulate);
   return done();
 }
 

@@ -123,6 +123,7 @@ SYMBOLS = {
     "k5_ln_modulate_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "k5_rmsnorm_rope_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "k5_gate_sum_bf16": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "k5_magcache_stats_bf16": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "k5_gemv_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "k5_time_features_f32": (_I, [_F, _P, _I, _P]),
     "k5_ln_affine_bf16": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
@@ -167,6 +168,8 @@ SYMBOLS = {
     "k5_dit_set_magcache": (_I, [_P, C.POINTER(C.c_double), _I, _I, C.c_double, _I, C.c_double]),
     "k5_dit_magcache_calls": (_I, [_P, _I, _I]),
     "k5_dit_magcache_state": (_I, [_P, C.POINTER(_I), C.POINTER(_I64), C.POINTER(_I64)]),
+    "k5_dit_set_magcache_calibrate": (_I, [_P, _I, _I]),
+    "k5_dit_magcache_calibration": (_I, [_P, C.POINTER(C.c_double), _I, C.POINTER(_I), C.POINTER(_I64)]),
     "k5_dit_set_profiling": (_I, [_P, _I]),
     "k5_dit_get_profile": (_I, [_P, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_I64)]),
     "k5_dit_reset_profile": (_I, [_P]),
@@ -195,7 +198,10 @@ def lib() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} has C ABI version {have}, this host binding needs {ABI_VERSION}: rebuild it with "
                            "`python kandinsky-5_amd/build.py`")
     for name, (res, args) in SYMBOLS.items():
-        fn = getattr(L, name)  # AttributeError => symbol missing: loud
+        try:
+            fn = getattr(L, name)
+        except AttributeError as e:   # a libk5.so of the same ABI number from before an added export (the MagCache calibration ones)
+            raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it with `python kandinsky-5_amd/build.py`") from e
         fn.restype = res
         fn.argtypes = args
     _lib = L
@@ -348,6 +354,17 @@ def gate_sum(x, y, gate):
     check(lib().k5_gate_sum_bf16(ptr(x), ptr(y), ptr(gate), ptr(out), x.shape[0], x.shape[1], stream_ptr(x.device)),
           "k5_gate_sum_bf16")
     return out
+
+
+def magcache_stats(vis, ori, prev=None, out=None):
+    """(res, sums): res = bf16(vis - ori) and the four float64 sums of the MagCache calibration pass against `prev` (k5_magcache_stats_bf16);
+    `out` may be `ori` itself."""
+    _need_cuda(vis, ori, prev, out)
+    res = torch.empty_like(vis) if out is None else out
+    sums = torch.empty(4, dtype=torch.float64, device=vis.device)
+    check(lib().k5_magcache_stats_bf16(ptr(vis), ptr(ori), ptr(prev), ptr(res), ptr(sums), vis.shape[0], vis.shape[1],
+                                       stream_ptr(vis.device)), "k5_magcache_stats_bf16")
+    return res, sums
 
 
 def gemv_f32(x, w, b=None, silu_in=False, add=None):

@@ -176,7 +176,7 @@ class DiffusionTransformer3D(nn.Module):
         for k, v in st["options"].items():
             if k != "emulate_world":
                 E.check(E.lib().k5_dit_set_option(self._handle, k.encode(), int(v)), f"k5_dit_set_option({k})")
-        if getattr(self, "mag_ratios", None) is not None:   # set_magcache_params() before the weights were loaded
+        if getattr(self, "mag_ratios", None) is not None or getattr(self, "_magcache_calibrate", None) is not None:   # set before the weights were loaded / the handle rebuilt
             from ..magcache_utils import _apply
             _apply(self)
 
@@ -277,6 +277,7 @@ class DiffusionTransformer3D(nn.Module):
         h = self.engine(x.device)
         x = x.float().contiguous()
         T, H, W, Cx = x.shape
+        self._last_tokens = T * (H // self.patch_size[1]) * (W // self.patch_size[2])   # rows of a residual (magcache_calibration)
         text_embed, pooled_text_embed = text_embed.to(x.device), pooled_text_embed.to(x.device)
         t_val = float(time.reshape(-1)[0]) if torch.is_tensor(time) else float(time)
         keep = [x]
@@ -297,6 +298,7 @@ class DiffusionTransformer3D(nn.Module):
         if not latent.is_cuda or latent.dtype != torch.float32 or not latent.is_contiguous():
             raise RuntimeError("latent must be a contiguous fp32 CUDA tensor")
         T, H, W, _ = latent.shape
+        self._last_tokens = T * (H // self.patch_size[1]) * (W // self.patch_size[2])   # rows of a residual (magcache_calibration)
         self._check_visual_cond(visual_cond, latent)
         h = self.engine(latent.device)
         dev = latent.device
@@ -337,7 +339,7 @@ class DiffusionTransformer3D(nn.Module):
     def many_ready(self):
         """True when `sample_many` / `forward_many` are accepted: a single-rank handle without MagCache or graph replay."""
         return (self._sp is None and self._cfg_pair is None and getattr(self, "mag_ratios", None) is None
-                and not self._settings["graph"])
+                and getattr(self, "_magcache_calibrate", None) is None and not self._settings["graph"])
 
     @torch.no_grad()
     def sample_many(self, latents, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,

@@ -25,7 +25,10 @@ def get_T2V_pipeline(
     conf_path: str = None,
     offload: bool = False,
     magcache: bool = False,
+    magcache_ratios=None,
 ) -> Kandinsky5T2VPipeline:
+    """`magcache_ratios` (extension): the MagCache ratio table to use instead of the config's `magcache.mag_ratios` — a list, the dict
+    `magcache_utils.calibrate_magcache` returns, or the path of a JSON / YAML file holding either.  Only read with `magcache=True`."""
     assert resolution in [512]
     if not isinstance(device_map, dict):
         device_map = {"dit": device_map, "vae": device_map, "text_embedder": device_map}
@@ -63,9 +66,17 @@ def get_T2V_pipeline(
     with torch.device("meta"):
         dit = get_dit(conf.model.dit_params)
     if magcache:  # reference utils.py:107-113
-        from .magcache_utils import set_magcache_params
+        from . import magcache_utils
         no_cfg = conf.model.guidance_weight == 1.0
-        set_magcache_params(dit, conf.magcache.mag_ratios, conf.model.num_steps, no_cfg)
+        if magcache_ratios is not None:
+            mag_ratios = magcache_utils.load_mag_ratios(magcache_ratios)
+        elif "magcache" in conf and "mag_ratios" in conf.magcache:
+            mag_ratios = conf.magcache.mag_ratios
+        else:
+            raise ValueError(f"magcache=True, but the config {conf_path or '(default)'} has no magcache.mag_ratios table and no magcache_ratios= "
+                             "was given: measure one for this checkpoint with kandinsky.magcache_utils.calibrate_magcache(pipe, prompts) "
+                             "(or `test.py --calibrate_magcache OUT.json`) and pass it as magcache_ratios=")
+        magcache_utils.set_magcache_params(dit, mag_ratios, conf.model.num_steps, no_cfg)
     state_dict = load_file(conf.model.checkpoint_path)
     dit.load_state_dict(state_dict, assign=True)
     if not offload:

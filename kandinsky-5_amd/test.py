@@ -3,6 +3,8 @@ README launch lines keep working against this package:
 
     python test.py --prompt "a cat in a blue hat" --config ./configs/config_5s_sft.yaml
     python test.py --prompt "the cat turns its head" --image cat.png     # image-to-video: the clip starts from cat.png
+    python test.py --config ./configs/config_5s_distil.yaml --calibrate_magcache ratios.json   # measure a MagCache table, then:
+    python test.py --config ./configs/config_5s_distil.yaml --magcache --magcache_ratios ratios.json
     PYTHONPATH=. torchrun --nproc-per-node 8 --master-addr 127.0.0.1 test.py --config ./configs/config_10s_sft.yaml ...
 
 Multi-GPU: one process per GPU (LOCAL_RANK / WORLD_SIZE from the launcher); `get_T2V_pipeline` sets up token-sharded
@@ -38,6 +40,9 @@ def build_parser():
     p.add_argument("--offload", action="store_true", default=False, help="keep only the active model on the GPU")
     p.add_argument("--image", type=str, default=None, help="image-to-video: a picture (PNG / JPEG) the clip starts from")
     p.add_argument("--magcache", action="store_true", default=False, help="MagCache: skip the visual blocks on low-error steps (50-step configs)")
+    p.add_argument("--magcache_ratios", type=str, default=None, help="MagCache ratio table (JSON / YAML with mag_ratios) used instead of the config's; with --magcache")
+    p.add_argument("--calibrate_magcache", type=str, default=None, metavar="OUT.json",
+                   help="measure the MagCache ratio table of this checkpoint on the given prompt (and --image) and write it to OUT.json; no video is saved")
     return p
 
 
@@ -52,13 +57,25 @@ def main(argv=None):
     validate_args(args)
     from kandinsky import get_T2V_pipeline
     pipe = get_T2V_pipeline(device_map={"dit": "cuda:0", "vae": "cuda:0", "text_embedder": "cuda:0"}, conf_path=args.config,
-                            offload=args.offload, magcache=args.magcache)
+                            offload=args.offload, magcache=args.magcache and not args.calibrate_magcache,
+                            magcache_ratios=args.magcache_ratios)
     if args.output_filename is None:
         args.output_filename = "./" + args.prompt.replace(" ", "_") + ".mp4"
     image = None
     if args.image is not None:
         from PIL import Image
         image = Image.open(args.image).convert("RGB")
+    if args.calibrate_magcache:
+        import json
+        from kandinsky.magcache_utils import calibrate_magcache
+        table = calibrate_magcache(pipe, [args.prompt], time_length=args.video_duration, width=args.width, height=args.height,
+                                   num_steps=args.sample_steps, guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale,
+                                   expand_prompts=args.expand_prompt, negative_caption=args.negative_prompt, image=image)
+        with open(args.calibrate_magcache, "w") as f:
+            json.dump(table, f, indent=1)
+        print(f"MagCache ratio table ({len(table['mag_ratios'])} ratios, {table['rows_counted']} of {table['rows_total']} rows counted) "
+              f"is saved to {args.calibrate_magcache}; use it with --magcache --magcache_ratios {args.calibrate_magcache}")
+        return
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,

@@ -1,0 +1,266 @@
+"""MagCache calibration without a GPU: the fixture made from the reference's own residuals (tools/gen_golden_magcache_calib.py) against
+the oracle's state machine with nothing skipped, the table round trip, `magcache_ratios=` of get_T2V_pipeline and the new flags of test.py.
+
+The estimator (per call, over the rows of the call's residual against the previous residual of its cond / uncond slot, float64):
+    ratio = mean_i |res_i| / |prev_i|,   std = unbiased standard deviation of it,   cos = mean_i (1 - cos(res_i, prev_i)).
+The helpers below are shared with tests/test_gpu_magcache_calib.py."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import k5_oracle as O
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
+
+
+class RecordingCache(list):
+    """`MagCache.residual_cache` that keeps every residual it is handed: (slot, tensor) in call order"""
+
+    def __init__(self):
+        super().__init__([None, None])
+        self.log = []
+
+    def __setitem__(self, i, v):
+        self.log.append((i, v))
+        super().__setitem__(i, v)
+
+
+def row_stats(res, prev):
+    """(mean ratio, unbiased std, mean cosine distance, rows with a zero norm) in float64"""
+    r, p = res.double().reshape(-1, res.shape[-1]), prev.double().reshape(-1, prev.shape[-1])
+    nr, npv = r.norm(dim=-1), p.norm(dim=-1)
+    rho = nr / npv
+    cos = (r * p).sum(-1) / (nr * npv)
+    return float(rho.mean()), float(rho.std()), float((1.0 - cos).mean()), int(((nr == 0) | (npv == 0)).sum())
+
+
+def stats_of_log(log, no_cfg):
+    """per call with a previous residual of its slot: (calls, [n][4] stats); the call counter advances by 2 with no_cfg"""
+    last, calls, stats = {}, [], []
+    for k, (slot, res) in enumerate(log):
+        cnt = 2 * k if no_cfg else k
+        assert slot == cnt % 2
+        if slot in last:
+            calls.append(cnt)
+            stats.append(row_stats(res, last[slot]))
+        last[slot] = res
+    return calls, np.asarray(stats, dtype=np.float64)
+
+
+def oracle_calibration(sd, cfg, noise, steps, te, ne, w, s, mode, vc=None, mask=None, pos=POS, tpos=None, ntpos=None):
+    """The oracle's sampling loop under O.MagCache(thresh=0.0): `accumulated_err < 0` never holds, so every call runs its blocks and caches
+    its residual.  Returns (calls, stats, final latent, ran_blocks).  vc / mask: the conditioning channels (the loop body of O.generate
+    with the zeros replaced, as tests/test_visual_cond.py does)."""
+    no_cfg = abs(w - 1.0) <= 1e-6
+    tpos = torch.arange(7) if tpos is None else tpos
+    ntpos = torch.arange(4) if ntpos is None else ntpos
+    mc = O.MagCache([1.0] * (2 * steps - 2), steps, no_cfg, thresh=0.0)
+    mc.residual_cache = RecordingCache()
+    if vc is None:
+        final = O.generate(sd, cfg, noise, steps, te, ne, pos, tpos, ntpos, w, s, (1.0, 2.0, 2.0), None, mode, magcache=mc)
+    else:
+        img = noise.clone().float()
+        sig = O.sigma_schedule(steps, s)
+        for i in range(steps):
+            x = torch.cat([img, vc, mask], dim=-1)
+            v = O.get_velocity(sd, cfg, x, sig[i].unsqueeze(0), te, ne, pos, tpos, ntpos, w, (1.0, 2.0, 2.0), None, mode, magcache=mc)
+            img = img + O._r((sig[i + 1] - sig[i]) * v, mode)
+        final = img
+    assert mc.cnt == 0 and all(mc.ran_blocks)
+    calls, stats = stats_of_log(mc.residual_cache.log, no_cfg)
+    return calls, stats, final, mc.ran_blocks
+
+
+def load_fixture():
+    from safetensors.torch import load_file
+    return (load_file(os.path.join(GOLDEN, "magcache_calib_tiny.safetensors")),
+            json.load(open(os.path.join(GOLDEN, "magcache_calib_tiny.json"))))
+
+
+def case_inputs(golden, case):
+    """(te, ne, noise, vc, mask) of a fixture case on the CPU"""
+    from safetensors.torch import load_file
+    te = {"text_embeds": golden["fwd.text"], "pooled_embed": golden["fwd.pooled"]}
+    ne = {"text_embeds": golden["gen.null_text"], "pooled_embed": golden["gen.null_pooled"]}
+    noise = golden["gen.noise"]
+    vc = mask = None
+    if case["conditioned"]:
+        vc = torch.zeros(noise.shape)
+        vc[0] = load_file(os.path.join(GOLDEN, "dit_tiny_visual_cond.safetensors"))["cond.visual_cond0"].float()
+        mask = torch.zeros(*noise.shape[:-1], 1)
+        mask[0] = 1.0
+    return te, ne, noise, vc, mask
+
+
+@pytest.fixture(scope="module")
+def ocfg(golden_meta):
+    c = dict(golden_meta["tiny_config"])
+    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
+    return O.DitConfig(**c)
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return load_fixture()
+
+
+def test_fixture_provenance_and_shape(fixture, golden):
+    """what the generator promises: three cases at the tiny latent, 10 steps, every call after a slot's first one, no zero rows"""
+    T, meta = fixture
+    cases = {c["tag"]: c for c in meta["cases"]}
+    assert sorted(cases) == ["cfg", "cond", "nocfg"]
+    for tag, c in cases.items():
+        assert c["latent_shape"] == [3, 8, 12, 16] == list(golden["gen.noise"].shape) and c["num_steps"] == 10
+        assert c["no_cfg"] == (c["guidance_weight"] == 1.0) and c["conditioned"] == (tag == "cond")
+        want = list(range(2, 20, 2)) if c["no_cfg"] else list(range(2, 20))
+        assert c["calls"] == want and c["min_row_norm"] > 0 and c["rows_per_call"] == 3 * 4 * 6
+        for k in ("ratio", "std", "cos"):
+            v = T[f"calib.{tag}.{k}"]
+            assert v.dtype == torch.float64 and v.shape == (len(want),) and torch.isfinite(v).all()
+        assert (T[f"calib.{tag}.ratio"] > 0.5).all() and (T[f"calib.{tag}.ratio"] < 2.0).all()
+    assert cases["cfg"]["guidance_weight"] == 2.0 and cases["nocfg"]["guidance_weight"] == 1.0
+    # the conditioning really changes how the residual evolves (the reason the table is worth measuring per workload)
+    assert (T["calib.cond.ratio"] - T["calib.cfg.ratio"]).abs().max() > 1e-4
+
+
+@pytest.mark.parametrize("tag", ["cfg", "nocfg", "cond"])
+def test_oracle_reproduces_reference_ratios(fixture, golden, tiny_sd, ocfg, tag):
+    """O.MagCache(thresh=0.0) through the oracle's sampler in fp32 against the reference's own residuals: fp32 arithmetic restated, 1e-5
+    relative (tighter than the 2e-5 default and the 1e-4 of the single fp32 forwards in test_oracle_vs_golden.py: a mean of 72 norm ratios
+    is steadier than an element of a velocity)."""
+    T, meta = fixture
+    c = [c for c in meta["cases"] if c["tag"] == tag][0]
+    te, ne, noise, vc, mask = case_inputs(golden, c)
+    calls, st, final, ran = oracle_calibration(tiny_sd, ocfg, noise, c["num_steps"], te, ne, c["guidance_weight"], c["scheduler_scale"],
+                                               "fp32", vc, mask)
+    assert calls == c["calls"] and st[:, 3].sum() == 0
+    for col, k in enumerate(("ratio", "std", "cos")):
+        want = T[f"calib.{tag}.{k}"].numpy()
+        err = np.abs(st[:, col] - want).max() / np.abs(want).max()
+        print(f"{tag} {k}: max |oracle fp32 - reference| / max |reference| = {err:.3e}")
+    np.testing.assert_allclose(st[:, 0], T[f"calib.{tag}.ratio"].numpy(), rtol=1e-5, atol=0)
+    torch.testing.assert_close(final, T[f"calib.{tag}.final"], atol=5e-4, rtol=5e-4)   # test_magcache_generate_matches_reference's bound
+
+
+def test_calibration_dict_and_table_round_trip(fixture):
+    """sums -> dict in the YAML schema -> ratio_table -> O.MagCache, with no interpolation; no_cfg repeats the cond entries"""
+    from kandinsky.magcache_utils import calibration_from_sums, ratio_table
+    T, meta = fixture
+    for c in meta["cases"]:
+        steps, rows = c["num_steps"], c["rows_per_call"]
+        ratio, std, cos = (T[f"calib.{c['tag']}.{k}"].numpy() for k in ("ratio", "std", "cos"))
+        sums = np.zeros((2 * steps, 4))
+        for j, cnt in enumerate(c["calls"]):   # the sums two averaged runs would leave: sum rho, sum rho^2, sum (1 - cos), count
+            n = 2 * rows
+            sums[cnt] = [n * ratio[j], (n - 1) * std[j] ** 2 + n * ratio[j] ** 2, n * cos[j], n]
+        d = calibration_from_sums(sums, steps, c["no_cfg"], runs=2, rows_per_call=rows)
+        assert len(d["mag_ratios"]) == 2 * (steps - 1) == len(d["mag_ratio_std"]) == len(d["mag_cos_dis"])
+        assert d["runs"] == 2 and d["rows_total"] == 2 * rows * 2 * (steps - 1)
+        got = np.asarray(d["mag_ratios"])
+        if c["no_cfg"]:
+            assert np.array_equal(got[0::2], got[1::2])
+            got, gstd = got[0::2], np.asarray(d["mag_ratio_std"])[0::2]
+            assert d["rows_counted"] == d["rows_total"]
+        else:
+            gstd = np.asarray(d["mag_ratio_std"])
+            assert d["rows_counted"] == d["rows_total"]
+        np.testing.assert_allclose(got, ratio, rtol=1e-12)
+        np.testing.assert_allclose(gstd, std, rtol=1e-6)
+        table = ratio_table(d["mag_ratios"], steps)
+        assert len(table) == 2 * steps and table[0] == table[1] == 1.0 and np.array_equal(table[2:], np.asarray(d["mag_ratios"]))
+        mc = O.MagCache(d["mag_ratios"], steps, c["no_cfg"])
+        assert np.array_equal(mc.mag_ratios, table)
+        json.dumps(d)   # the dict is what test.py --calibrate_magcache writes
+    with pytest.raises(RuntimeError, match="complete"):
+        calibration_from_sums(np.zeros((20, 4)), 10, False, runs=0)
+
+
+def test_load_mag_ratios_from_list_json_yaml(tmp_path):
+    import yaml
+    from kandinsky.magcache_utils import load_mag_ratios
+    ratios = [1.0, 1.01, 0.99, 0.98, 1.02, 1.0]
+    assert load_mag_ratios(ratios) == ratios
+    assert load_mag_ratios({"mag_ratios": ratios, "runs": 3}) == ratios
+    (tmp_path / "a.json").write_text(json.dumps({"mag_ratios": ratios, "mag_ratio_std": [0.0] * 6}))
+    (tmp_path / "b.json").write_text(json.dumps(ratios))
+    (tmp_path / "c.yaml").write_text(yaml.safe_dump({"magcache": {"mag_ratios": ratios}}))
+    (tmp_path / "d.yml").write_text(yaml.safe_dump({"mag_ratios": ratios}))
+    for name in ("a.json", "b.json", "c.yaml", "d.yml"):
+        assert load_mag_ratios(str(tmp_path / name)) == ratios, name
+    with pytest.raises(ValueError, match="mag_ratios"):
+        load_mag_ratios({"ratios": ratios})
+    with pytest.raises(ValueError, match="even number"):
+        load_mag_ratios(ratios[:3])
+
+
+def _factory(monkeypatch, tmp_path, config_name):
+    """get_T2V_pipeline with the heavy parts stubbed: returns what set_magcache_params was given"""
+    import kandinsky.utils as U
+    import kandinsky.models.text_embedders as TE
+    import kandinsky.models.vae as V
+    import kandinsky.magcache_utils as M
+    import safetensors.torch as ST
+    from kandinsky.config import default_configs
+
+    class Stub:
+        def to(self, *a, **k):
+            return self
+
+        def eval(self):
+            return self
+
+        def load_state_dict(self, *a, **k):
+            return None
+    seen = {}
+    monkeypatch.setattr(TE, "get_text_embedder", lambda conf: Stub())
+    monkeypatch.setattr(V, "build_vae", lambda conf: Stub())
+    monkeypatch.setattr(U, "get_dit", lambda params: Stub())
+    monkeypatch.setattr(ST, "load_file", lambda path: {})
+    monkeypatch.setattr(M, "set_magcache_params", lambda dit, ratios, steps, no_cfg: seen.update(ratios=list(ratios), steps=steps, no_cfg=no_cfg))
+    monkeypatch.setattr(U, "Kandinsky5T2VPipeline", lambda **k: k)
+    import yaml
+    path = tmp_path / config_name
+    path.write_text(yaml.safe_dump(default_configs()[config_name], sort_keys=False))
+    return U, str(path), seen
+
+
+def test_get_pipeline_magcache_ratios_keyword(monkeypatch, tmp_path):
+    from kandinsky.config import default_configs
+    U, sft, seen = _factory(monkeypatch, tmp_path, "config_5s_sft.yaml")
+    U.get_T2V_pipeline("cpu", conf_path=sft, magcache=True)                      # unchanged: the config's own table
+    assert seen["ratios"] == list(default_configs()["config_5s_sft.yaml"]["magcache"]["mag_ratios"]) and seen["steps"] == 50 and not seen["no_cfg"]
+    mine = [1.0 + 0.001 * i for i in range(98)]
+    U.get_T2V_pipeline("cpu", conf_path=sft, magcache=True, magcache_ratios=mine)   # the keyword wins over the config
+    assert seen["ratios"] == mine
+    seen.clear()
+    U.get_T2V_pipeline("cpu", conf_path=sft, magcache_ratios=mine)               # magcache=False: nothing is installed
+    assert not seen
+
+    U, distil, seen = _factory(monkeypatch, tmp_path, "config_5s_distil.yaml")
+    with pytest.raises(ValueError, match=r"config_5s_distil\.yaml.*calibrate_magcache"):
+        U.get_T2V_pipeline("cpu", conf_path=distil, magcache=True)
+    f = tmp_path / "ratios.json"
+    steps = default_configs()["config_5s_distil.yaml"]["model"]["num_steps"]
+    f.write_text(json.dumps({"mag_ratios": mine[:2 * (steps - 1)], "runs": 1}))
+    U.get_T2V_pipeline("cpu", conf_path=distil, magcache=True, magcache_ratios=str(f))
+    assert seen["ratios"] == mine[:2 * (steps - 1)] and seen["steps"] == steps
+
+
+def test_cli_parser_new_flags_keep_old_defaults():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("k5_cli_test", os.path.join(root, "kandinsky-5_amd", "test.py"))
+    cli = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cli)
+    p = cli.build_parser()
+    d = vars(p.parse_args([]))
+    assert d.pop("calibrate_magcache") is None and d.pop("magcache_ratios") is None
+    assert d == {"local_rank": None, "config": "./configs/config_5s_sft.yaml", "prompt": "a cat in a blue hat", "negative_prompt": cli.NEGATIVE,
+                 "width": 768, "height": 512, "video_duration": 5, "expand_prompt": 1, "sample_steps": None, "guidance_weight": None,
+                 "scheduler_scale": 5.0, "output_filename": "./test.mp4", "offload": False, "image": None, "magcache": False}
+    a = p.parse_args(["--calibrate_magcache", "out.json", "--image", "cat.png", "--magcache_ratios", "t.json", "--magcache"])
+    assert a.calibrate_magcache == "out.json" and a.magcache_ratios == "t.json" and a.image == "cat.png" and a.magcache
