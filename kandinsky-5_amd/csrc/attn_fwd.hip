@@ -1356,55 +1356,107 @@ int k5_launch_attn_row_anchor(const void* Q, const void* Kc, int H, int q_len, i
   return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
 }
 
-// Dense attention over a key-tile range (see AttnP).  With a workspace `ws` (k5_attention_balance_bytes) and final output
-// requested (flags & 2 == 0), the launch is BALANCED: the jobs that fill whole rounds of the device's resident-workgroup
-// slots run as usual; the jobs of the last, partially filled round are split 2-4 ways along the key sequence into short
-// workgroups that fill the slots, and a merge kernel combines their states.  5208 jobs on 512 slots: 10.25 rounds instead
-// of 11; an 8-GPU shard's 672 jobs: 1.33 instead of 2.
-// variant (pre-scaled keys only): K5_ATTN_AUTO = by score_bound / head_flags, K5_ATTN_ONLINE = force the lazy online max.
-int k5_launch_attention_bf16_range(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len,
-                                   int kv_len, int ldq, int ldk, int ldvt, int ldo, float score_bound,
-                                   int vt_chunk_keys, long long vt_chunk_stride, int tile_off0, int tile_cnt, int tile_skip_at,
-                                   int tile_skip_n, float* state, int flags, hipStream_t stream, float* ws, bool k_prescaled,
-                                   const int* head_flags, int variant, const K5TileSegments* seg, const float* kmax, int late_pass,
-                                   const K5QueryNorm* qn, const K5KeyCentre* kc) {
-  if (H <= 0 || q_len <= 0 || kv_len <= 0) return K5_ERR_ARG;
-  if ((ldq & 7) || (ldk & 7) || (ldvt & 7) || (ldo & 3)) return K5_ERR_ALIGN;
-  if (vt_chunk_keys < 0 || (vt_chunk_keys % KB) || (vt_chunk_stride & 7)) return K5_ERR_ALIGN;
-  AttnP p;
-  p.Q = (const bf16_t*)Q; p.K = (const bf16_t*)K; p.Vt = (const bf16_t*)Vt; p.O = (bf16_t*)O;
-  p.H = H; p.q_len = q_len; p.kv_len = kv_len; p.ldq = ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = ldo;
-  p.nqb = (q_len + QB - 1) / QB;
+namespace {
+// What both launchers check and fill the same way.  job_rows: query rows per (head, query block) job; state / flags / late_pass / qn: the
+// launch's pass of a schedule (the range launcher's own arguments, the list launcher's K5SparsePass).
+struct AttnForms { bool bounded, run_fixed, run_online; };   // which softmax form(s) run: fixed offset, online max; per head when head_flags is given
+int attn_common(const K5AttnArgs& a, int job_rows, float* state, int flags, int late_pass, const K5QueryNorm* qn, AttnP& p, AttnForms& f) {
+  if (a.H <= 0 || a.q_len <= 0 || a.kv_len <= 0) return K5_ERR_ARG;
+  if ((a.ldq & 7) || (a.ldk & 7) || (a.ldvt & 7) || (a.ldo & 3)) return K5_ERR_ALIGN;
+  if (a.vt_chunk_keys < 0 || (a.vt_chunk_keys % KB) || (a.vt_chunk_stride & 7)) return K5_ERR_ALIGN;
+  if ((a.head_flags || a.variant != K5_ATTN_AUTO) && !a.k_prescaled) return K5_ERR_ARG;
+  if (a.k_prescaled && (a.kv_len % KB)) return K5_ERR_ARG;      // pre-scaled keys: whole key tiles only (no ragged-tile code)
+  const float* kmax = a.row_offset_kmax;
+  const K5KeyCentre* kc = a.key_centre;
+  p.Q = (const bf16_t*)a.Q; p.K = (const bf16_t*)a.K; p.Vt = (const bf16_t*)a.Vt; p.O = (bf16_t*)a.O;
+  p.H = a.H; p.q_len = a.q_len; p.kv_len = a.kv_len; p.ldq = a.ldq; p.ldk = a.ldk; p.ldvt = a.ldvt; p.ldo = a.ldo;
+  p.nqb = (a.q_len + job_rows - 1) / job_rows;
   p.c = 0.125f * 1.44269504088896340736f;
-  p.head_flags = nullptr; p.my_flag = 0;
-  if (kmax && (!head_flags || !k_prescaled || variant != K5_ATTN_AUTO)) return K5_ERR_ARG;   // per-row offsets need the per-head flags (late fallback)
+  if (kmax && (!a.head_flags || !a.k_prescaled || a.variant != K5_ATTN_AUTO)) return K5_ERR_ARG;   // per-row offsets need the per-head flags (late fallback)
   p.kmax = kmax;
   p.kcentre = (kc && kmax) ? kc->centre : nullptr; p.krad = (kc && kmax) ? kc->radius : nullptr;
   p.row_anchor = (kc && kmax) ? kc->row_anchor : nullptr;
   if ((p.kcentre == nullptr) != (p.krad == nullptr)) return K5_ERR_ARG;
+  if ((flags & 3) && !state) return K5_ERR_ARG;
   if (late_pass < 0 || late_pass > 2 || (late_pass && !kmax)) return K5_ERR_ARG;
-  p.late_pass = late_pass; p.late_total = (kv_len + KB - 1) / KB;
+  p.late_pass = late_pass; p.late_total = (a.kv_len + KB - 1) / KB;
   p.job_flags = nullptr;
-  if (kmax && ws) {   // per-row offsets with a workspace: fallback per job; the first pass of a schedule (it does not resume) clears the flags
-    p.job_flags = attn_job_flags(ws, H, q_len);
-    if (!(flags & 1) && hipMemsetAsync(const_cast<int*>(p.job_flags), 0, attn_job_flags_bytes(H, q_len), stream) != hipSuccess) return K5_ERR_HIP;
+  if (kmax && a.balance_ws) {   // per-row offsets with a workspace: fallback per job; the first pass of a schedule (it does not resume) clears the flags
+    p.job_flags = attn_job_flags(a.balance_ws, a.H, a.q_len);
+    if (!(flags & 1) && hipMemsetAsync(const_cast<int*>(p.job_flags), 0, attn_job_flags_bytes(a.H, a.q_len), a.stream) != hipSuccess) return K5_ERR_HIP;
   }
   p.q_norm_w = qn ? qn->w : nullptr; p.q_cos = qn ? qn->cos : nullptr; p.q_sin = qn ? qn->sin : nullptr;
   p.variant_counters = qn ? qn->counters : nullptr;
+  p.vt_chunk_keys = a.vt_chunk_keys; p.vt_chunk_stride = a.vt_chunk_stride;
+  p.sp_list = nullptr; p.sp_cnt = nullptr; p.sp_stride = 0; p.sp_begin = nullptr;
+  p.tile_off0 = 0; p.tile_cnt = 0; p.tile_skip_at = 0x7fffffff; p.tile_skip_n = 0;
+  p.seg_len = 0; p.seg_stride = 0; p.seg_skip = 0x7fffffff;
+  p.state = state; p.flags = flags;
+  p.job0 = 0; p.splits = 1; p.split_state = nullptr; p.split_stride = 0;
+  f.bounded = a.score_bound > 0.f && a.score_bound * p.c <= K5_ATTN_EXP_LIMIT;
+  f.run_fixed = a.head_flags ? a.variant == K5_ATTN_AUTO : (a.variant == K5_ATTN_AUTO && f.bounded);
+  f.run_online = a.head_flags ? true : !f.run_fixed;
+  // pre-scaled keys: the two forms partition the heads by the device flags (my_flag is set per launch)
+  p.head_flags = (f.run_fixed && f.run_online) ? a.head_flags : nullptr; p.my_flag = 0;
+  return K5_OK;
+}
+
+// BALANCED launch (balance, a workspace, and at least two parts): the jobs that fill whole rounds of the device's resident-workgroup slots
+// run as usual; the jobs of the last, partially filled round are split 2-6 ways (at most max_parts) along the key sequence / the lists
+// into short workgroups that fill the slots, and a merge kernel combines their states.  5208 jobs on 512 slots: 10.25 rounds instead
+// of 11; an 8-GPU shard's 672 jobs: 1.33 instead of 2; the 2576 list jobs of a 4-GPU shard of the 10 s clip: 5.03 instead of 6.
+// launch(njobs, ranged) picks the kernel(s); `ranged`: what the unsplit launch needs, the split one always does.
+template <class L>
+int attn_launch_balanced(const K5AttnArgs& a, AttnP& p, const AttnForms& f, bool balance, int max_parts, bool ranged, L launch) {
+  const int jobs = a.H * p.nqb, slots = attn_slots();
+  const int full = jobs / slots * slots, rem = jobs - full;
+  int S = rem > 0 ? slots / rem : 1;
+  if (S > K5_ATTN_MAX_SPLITS) S = K5_ATTN_MAX_SPLITS;
+  if (S > max_parts) S = max_parts;
+  static const bool no_balance = getenv("K5_ATTN_NO_BALANCE") != nullptr;   // A/B switch for benchmarking
+  float* ws = a.balance_ws;
+  if (!balance || !ws || S < 2 || no_balance) {
+    launch(jobs, ranged);
+    return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
+  }
+  if (full > 0) launch(full, ranged);
+  // tail jobs, S parts each: part 0 resumes the caller's state if there is one, every part leaves its state
+  const long long stride = (long long)(k5_attention_state_bytes(a.H, a.q_len) / sizeof(float));
+  const int flags = p.flags;
+  float* state = p.state;
+  const bool to_state = (flags & 2) != 0;
+  float* base = (flags & 1) ? state : ws;
+  p.job0 = full; p.splits = S; p.state = base; p.split_state = ws + stride; p.split_stride = stride;
+  p.flags = (flags & 1) | 2;
+  launch(rem * S, true);
+  // merge weights: 1 for the fixed-offset heads, exp2(m_s - max m) for the online ones (exp2 domain when the keys are pre-scaled)
+  hipLaunchKernelGGL(attn_merge_kernel, dim3(rem), dim3(256), 0, a.stream, base, ws + stride, stride, S, full, a.H, a.q_len, p.nqb,
+                     a.k_prescaled ? 1.f : p.c, (bf16_t*)a.O, a.ldo, (a.k_prescaled ? (f.run_fixed && !f.run_online) : f.bounded) ? 1 : 0,
+                     (a.k_prescaled && f.run_fixed && f.run_online) ? a.head_flags : nullptr, to_state ? state : nullptr, p.job_flags);
+  return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
+}
+}  // namespace
+
+// Dense attention over a key-tile range (see AttnP).  With a workspace (k5_attention_balance_bytes) the launch is balanced; a pass that
+// leaves its state (flags & 2) only when the keys are pre-scaled (the engine's path): its merge writes the merged state instead of O.
+// variant (pre-scaled keys only): K5_ATTN_AUTO = by score_bound / head_flags, K5_ATTN_ONLINE = force the lazy online max.
+int k5_launch_attention_bf16_range(const K5AttnRangeArgs& a) {
+  AttnP p; AttnForms f;
+  const int rc = attn_common(a, QB, a.state, a.flags, a.late_pass, a.query_norm, p, f);
+  if (rc != K5_OK) return rc;
+  hipStream_t stream = a.stream;
   if (p.q_norm_w) {
-    if (k_prescaled) {   // visual self-attention: norm + RoPE; both forms carry it; with per-row offsets the fixed form decides per head
-      if (!p.q_cos || !p.q_sin || (kmax && !head_flags)) return K5_ERR_ARG;
-    } else if (!(score_bound > 0.f && score_bound * p.c <= K5_ATTN_EXP_LIMIT)) {
+    if (a.k_prescaled) {   // visual self-attention: norm + RoPE; both forms carry it; with per-row offsets the fixed form decides per head
+      if (!p.q_cos || !p.q_sin || (a.row_offset_kmax && !a.head_flags)) return K5_ERR_ARG;
+    } else if (!f.bounded) {
       return K5_ERR_UNSUPPORTED;   // unscaled keys (cross-attention): only the fixed-offset 16x16x32 kernel carries the fused norm
     }
   }
-  p.vt_chunk_keys = vt_chunk_keys; p.vt_chunk_stride = vt_chunk_stride;
   const dim3 block(512);
-  const bool bounded = score_bound > 0.f && score_bound * p.c <= K5_ATTN_EXP_LIMIT;
-  p.sp_list = nullptr; p.sp_cnt = nullptr; p.sp_stride = 0;
-  const int total_tiles = (kv_len + KB - 1) / KB;
+  const int total_tiles = (a.kv_len + KB - 1) / KB;
+  int tile_off0 = a.tile_off0, tile_cnt = a.tile_cnt, tile_skip_at = a.tile_skip_at, tile_skip_n = a.tile_skip_n;
   if (tile_cnt < 0) tile_cnt = total_tiles - tile_off0;
-  p.seg_len = 0; p.seg_stride = 0; p.seg_skip = 0x7fffffff;
+  const K5TileSegments* seg = a.segments;
   if (seg && seg->len > 0) {   // segmented walk: the last position must still be a real tile
     if (tile_off0 < 0 || tile_cnt <= 0 || seg->stride < seg->len || seg->skip < 0) return K5_ERR_ARG;
     int si = (tile_cnt - 1) / seg->len;
@@ -1414,20 +1466,12 @@ int k5_launch_attention_bf16_range(const void* Q, const void* K, const void* Vt,
     p.seg_len = seg->len; p.seg_stride = seg->stride; p.seg_skip = seg->skip;
     tile_skip_at = 0x7fffffff; tile_skip_n = 0;
   } else if (tile_off0 < 0 || tile_skip_n < 0 || tile_off0 + tile_cnt + (tile_skip_at < total_tiles ? tile_skip_n : 0) > total_tiles) return K5_ERR_ARG;
-  if ((flags & 3) && !state) return K5_ERR_ARG;
   p.tile_off0 = tile_off0; p.tile_cnt = tile_cnt; p.tile_skip_at = tile_skip_at; p.tile_skip_n = tile_skip_n;
-  p.state = state; p.flags = flags;
-  p.job0 = 0; p.splits = 1; p.split_state = nullptr; p.split_stride = 0;
-  const bool range = tile_off0 != 0 || tile_cnt != total_tiles || (flags & 3) || p.seg_len > 0;
-  if (k_prescaled && (kv_len % KB)) return K5_ERR_ARG;      // pre-scaled keys: whole key tiles only (no ragged-tile code)
-  if ((head_flags || variant != K5_ATTN_AUTO) && !k_prescaled) return K5_ERR_ARG;
-  // which softmax form(s) run: 1 = fixed offset, 0 = online max; per head when head_flags is given
-  const bool run_fixed = head_flags ? variant == K5_ATTN_AUTO : (variant == K5_ATTN_AUTO && bounded);
-  const bool run_online = head_flags ? true : !run_fixed;
+  const bool range = tile_off0 != 0 || tile_cnt != total_tiles || (a.flags & 3) || p.seg_len > 0;
+  const bool run_fixed = f.run_fixed, run_online = f.run_online;
   auto launch = [&](int njobs, bool use_range) {
     const dim3 grid(njobs);
-    if (k_prescaled) {   // always the RANGE instantiation (a superset; with the plain one the register allocator spills)
-      p.head_flags = (run_fixed && run_online) ? head_flags : nullptr;
+    if (a.k_prescaled) {   // always the RANGE instantiation (a superset; with the plain one the register allocator spills)
       if (p.q_norm_w) {
         if (run_fixed) { p.my_flag = 1; hipLaunchKernelGGL((attn_fwd_kernel<true, false, true, true, true>), grid, block, 0, stream, p); }
         if (run_online) { p.my_flag = 0; hipLaunchKernelGGL((attn_fwd_kernel<false, false, true, true, true>), grid, block, 0, stream, p); }
@@ -1458,141 +1502,50 @@ int k5_launch_attention_bf16_range(const void* Q, const void* K, const void* Vt,
         if (run_online) { p.my_flag = 0; hipLaunchKernelGGL((attn_fwd_kernel<false, false, true, true>), grid, block, 0, stream, p); }
       }
     }
-    else if (bounded) hipLaunchKernelGGL((attn_fwd_kernel<true, false, true>), grid, block, 0, stream, p);
+    else if (f.bounded) hipLaunchKernelGGL((attn_fwd_kernel<true, false, true>), grid, block, 0, stream, p);
     else if (use_range) hipLaunchKernelGGL((attn_fwd32_kernel<false, false, true>), grid, block, 0, stream, p);
     else hipLaunchKernelGGL((attn_fwd32_kernel<false, false, false>), grid, block, 0, stream, p);
   };
-  const int jobs = H * p.nqb, slots = attn_slots();
-  const int full = jobs / slots * slots, rem = jobs - full;
-  int S = rem > 0 ? slots / rem : 1;
-  if (S > K5_ATTN_MAX_SPLITS) S = K5_ATTN_MAX_SPLITS;
-  if (S > tile_cnt / 8) S = tile_cnt / 8;          // keep >= 8 key tiles per part
-  static const bool no_balance = getenv("K5_ATTN_NO_BALANCE") != nullptr;   // A/B switch for benchmarking
-  // a pass that leaves its state (flags & 2) is balanced the same way when the keys are pre-scaled (the engine's path): its merge
-  // writes the merged state instead of O
-  if (!ws || ((flags & 2) && !k_prescaled) || S < 2 || no_balance) {
-    launch(jobs, range);
-    return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
-  }
-  if (full > 0) launch(full, range);
-  // tail jobs, S parts each: part 0 resumes the caller's state if there is one, every part leaves its state
-  const long long stride = (long long)(k5_attention_state_bytes(H, q_len) / sizeof(float));
-  const bool to_state = (flags & 2) != 0;
-  float* base = (flags & 1) ? state : ws;
-  p.job0 = full; p.splits = S; p.state = base; p.split_state = ws + stride; p.split_stride = stride;
-  p.flags = (flags & 1) | 2;
-  launch(rem * S, true);
-  // merge weights: 1 for the fixed-offset heads, exp2(m_s - max m) for the online ones (exp2 domain when the keys are pre-scaled)
-  hipLaunchKernelGGL(attn_merge_kernel, dim3(rem), dim3(256), 0, stream, base, ws + stride, stride, S, full, H, q_len, p.nqb,
-                     k_prescaled ? 1.f : p.c, (bf16_t*)O, ldo, (k_prescaled ? (run_fixed && !run_online) : bounded) ? 1 : 0,
-                     (k_prescaled && run_fixed && run_online) ? head_flags : nullptr, to_state ? state : nullptr, p.job_flags);
-  return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
-}
-
-int k5_launch_attention_bf16_chunked(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len,
-                                     int kv_len, int ldq, int ldk, int ldvt, int ldo, float score_bound,
-                                     int vt_chunk_keys, long long vt_chunk_stride, hipStream_t stream) {
-  return k5_launch_attention_bf16_range(Q, K, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, score_bound, vt_chunk_keys,
-                                        vt_chunk_stride, 0, -1, 0x7fffffff, 0, nullptr, 0, stream, nullptr, false);
+  return attn_launch_balanced(a, p, f, !(a.flags & 2) || a.k_prescaled, tile_cnt / 8 /* keep >= 8 key tiles per part */, range, launch);
 }
 
 // NABLA block-sparse attention (flex_attention(q,k,v,block_mask) nn.py:257-280): `list`/`cnt` are the per-workgroup
 // union lists produced by k5_launch_nabla_select[_rect] (stride = number of 64-key blocks).  q_len, kv_len multiples of 64;
-// V^T optionally in per-rank chunks (sequence parallel).
-int k5_launch_attention_bf16_sparse(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len, int kv_len, int ldq,
-                                    int ldk, int ldvt, int ldo, float score_bound, const int* list, const int* cnt, int list_stride,
-                                    int vt_chunk_keys, long long vt_chunk_stride, hipStream_t stream, bool k_prescaled,
-                                    const int* head_flags, int variant, const float* kmax, const K5SparsePass* pass, float* ws,
-                                    int group_rows, bool balance, const K5KeyCentre* kc, int pair_stride) {
-  if (H <= 0 || q_len <= 0 || kv_len <= 0 || (q_len % KB) || (kv_len % KB) || !list || !cnt) return K5_ERR_ARG;
-  if (pair_stride < 0 || (pair_stride > 0 && group_rows != 2)) return K5_ERR_ARG;
-  if ((ldq & 7) || (ldk & 7) || (ldvt & 7) || (ldo & 3)) return K5_ERR_ALIGN;
-  if (vt_chunk_keys < 0 || (vt_chunk_keys % KB) || (vt_chunk_stride & 7)) return K5_ERR_ALIGN;
-  if ((head_flags || variant != K5_ATTN_AUTO) && !k_prescaled) return K5_ERR_ARG;
-  AttnP p;
-  p.Q = (const bf16_t*)Q; p.K = (const bf16_t*)K; p.Vt = (const bf16_t*)Vt; p.O = (bf16_t*)O;
-  p.H = H; p.q_len = q_len; p.kv_len = kv_len; p.ldq = ldq; p.ldk = ldk; p.ldvt = ldvt; p.ldo = ldo;
-  if (group_rows != 4 && ((group_rows != 2 && group_rows != 1) || !k_prescaled || pass)) return K5_ERR_ARG;   // lists of 2 rows / 1 row: 128- / 64-query workgroups (ws: job flags only)
-  const bool half = group_rows != 4;
-  p.nqb = (q_len + 64 * group_rows - 1) / (64 * group_rows);
-  p.c = 0.125f * 1.44269504088896340736f;
-  p.head_flags = nullptr; p.my_flag = 0;
-  if (kmax && (!head_flags || !k_prescaled || variant != K5_ATTN_AUTO)) return K5_ERR_ARG;
-  p.kmax = kmax; p.late_pass = 0; p.late_total = 0; p.q_norm_w = nullptr; p.q_cos = p.q_sin = nullptr; p.variant_counters = nullptr;
-  p.kcentre = (kc && kmax) ? kc->centre : nullptr; p.krad = (kc && kmax) ? kc->radius : nullptr;
-  p.row_anchor = (kc && kmax) ? kc->row_anchor : nullptr;
-  if ((p.kcentre == nullptr) != (p.krad == nullptr)) return K5_ERR_ARG;
-  p.job_flags = nullptr;
-  if (kmax && ws) {
-    p.job_flags = attn_job_flags(ws, H, q_len);
-    if (!(pass && (pass->flags & 1)) && hipMemsetAsync(const_cast<int*>(p.job_flags), 0, attn_job_flags_bytes(H, q_len), stream) != hipSuccess) return K5_ERR_HIP;
-  }
-  p.vt_chunk_keys = vt_chunk_keys; p.vt_chunk_stride = vt_chunk_stride;
-  p.sp_list = list; p.sp_cnt = cnt; p.sp_stride = list_stride; p.sp_begin = nullptr;
-  p.pair_stride = pair_stride;
-  p.tile_off0 = 0; p.tile_cnt = 0; p.tile_skip_at = 0x7fffffff; p.tile_skip_n = 0; p.state = nullptr; p.flags = 0;
-  if (pass) {   // one pass of a two-pass walk of the lists (sequence parallelism): [begin, cnt) of every list, fp32 state in / out
-    if (!k_prescaled || !pass->state || (pass->flags & ~3) || pass->late_pass < 0 || pass->late_pass > 2 || (pass->late_pass && !kmax)) return K5_ERR_ARG;
-    p.sp_begin = pass->begin; p.state = pass->state; p.flags = pass->flags; p.late_pass = pass->late_pass;
-  }
-  p.seg_len = 0; p.seg_stride = 0; p.seg_skip = 0x7fffffff;
-  p.job0 = 0; p.splits = 1; p.split_state = nullptr; p.split_stride = 0;
-  const dim3 grid(H * p.nqb), block(512);
-  const bool bounded = score_bound > 0.f && score_bound * p.c <= K5_ATTN_EXP_LIMIT;
-  if (k_prescaled) {
-    const bool run_fixed = head_flags ? variant == K5_ATTN_AUTO : (variant == K5_ATTN_AUTO && bounded);
-    const bool run_online = head_flags ? true : !run_fixed;
-    p.head_flags = (run_fixed && run_online) ? head_flags : nullptr;
-    auto launch = [&](int njobs, bool rangek) {
-      const dim3 g(njobs);
-      if (group_rows == 1) {
-        if (run_fixed) { p.my_flag = 1; hipLaunchKernelGGL((attn_fwd_kernel<true, true, false, true, false, 1>), g, dim3(128), 0, stream, p); }
-        if (run_online) { p.my_flag = 0; hipLaunchKernelGGL((attn_fwd_kernel<false, true, false, true, false, 1>), g, dim3(128), 0, stream, p); }
-      } else if (half) {
-        if (run_fixed) { p.my_flag = 1; hipLaunchKernelGGL((attn_fwd_kernel<true, true, false, true, false, 2>), g, dim3(256), 0, stream, p); }
-        if (run_online) { p.my_flag = 0; hipLaunchKernelGGL((attn_fwd_kernel<false, true, false, true, false, 2>), g, dim3(256), 0, stream, p); }
-      } else if (rangek) {
-        if (run_fixed) { p.my_flag = 1; hipLaunchKernelGGL((attn_fwd_kernel<true, true, true, true>), g, block, 0, stream, p); }
-        if (run_online) { p.my_flag = 0; hipLaunchKernelGGL((attn_fwd_kernel<false, true, true, true>), g, block, 0, stream, p); }
-      } else {
-        if (run_fixed) { p.my_flag = 1; hipLaunchKernelGGL((attn_fwd_kernel<true, true, false, true>), g, block, 0, stream, p); }
-        if (run_online) { p.my_flag = 0; hipLaunchKernelGGL((attn_fwd_kernel<false, true, false, true>), g, block, 0, stream, p); }
-      }
-    };
-    // balanced like the dense launches: the (head, 256-query) jobs of the last, partly filled round of resident workgroups are cut
-    // S ways along their lists (every part leaves its fp32 state) and merged — 2576 jobs of a 4-GPU shard of the 10 s clip are 5.03
-    // rounds: without this the launch takes 6
-    const int jobs = H * p.nqb, slots = attn_slots();
-    const int full = jobs / slots * slots, rem = jobs - full;
-    int S = rem > 0 ? slots / rem : 1;
-    if (S > K5_ATTN_MAX_SPLITS) S = K5_ATTN_MAX_SPLITS;
-    static const bool no_balance = getenv("K5_ATTN_NO_BALANCE") != nullptr;   // A/B switch for benchmarking
-    if (!ws || S < 2 || no_balance || half || !balance) {
-      launch(jobs, pass != nullptr);
+// V^T optionally in per-rank chunks (sequence parallel).  Balanced like the dense launches (256-query jobs, pre-scaled keys).
+int k5_launch_attention_bf16_sparse(const K5AttnSparseArgs& a) {
+  if ((a.q_len % KB) || (a.kv_len % KB) || !a.list || !a.cnt) return K5_ERR_ARG;
+  if (a.pair_stride < 0 || (a.pair_stride > 0 && a.group_rows != 2)) return K5_ERR_ARG;
+  const K5SparsePass* pass = a.pass;
+  const int group_rows = a.group_rows;
+  if (group_rows != 4 && ((group_rows != 2 && group_rows != 1) || !a.k_prescaled || pass)) return K5_ERR_ARG;   // lists of 2 rows / 1 row: 128- / 64-query workgroups (ws: job flags only)
+  // one pass of a two-pass walk of the lists (sequence parallelism): [begin, cnt) of every list, fp32 state in / out
+  if (pass && (!a.k_prescaled || !pass->state || (pass->flags & ~3))) return K5_ERR_ARG;
+  AttnP p; AttnForms f;
+  const int rc = attn_common(a, 64 * group_rows, pass ? pass->state : nullptr, pass ? pass->flags : 0, pass ? pass->late_pass : 0, nullptr, p, f);
+  if (rc != K5_OK) return rc;
+  hipStream_t stream = a.stream;
+  p.sp_list = a.list; p.sp_cnt = a.cnt; p.sp_stride = a.list_stride; p.sp_begin = pass ? pass->begin : nullptr;
+  p.pair_stride = a.pair_stride;
+  const dim3 block(512);
+  const bool run_fixed = f.run_fixed, run_online = f.run_online;
+  auto launch = [&](int njobs, bool rangek) {
+    const dim3 g(njobs);
+    if (!a.k_prescaled) {
+      if (f.bounded) hipLaunchKernelGGL((attn_fwd_kernel<true, true, false>), g, block, 0, stream, p);
+      else hipLaunchKernelGGL((attn_fwd32_kernel<false, true, false>), g, block, 0, stream, p);
+    } else if (group_rows == 1) {
+      if (run_fixed) { p.my_flag = 1; hipLaunchKernelGGL((attn_fwd_kernel<true, true, false, true, false, 1>), g, dim3(128), 0, stream, p); }
+      if (run_online) { p.my_flag = 0; hipLaunchKernelGGL((attn_fwd_kernel<false, true, false, true, false, 1>), g, dim3(128), 0, stream, p); }
+    } else if (group_rows == 2) {
+      if (run_fixed) { p.my_flag = 1; hipLaunchKernelGGL((attn_fwd_kernel<true, true, false, true, false, 2>), g, dim3(256), 0, stream, p); }
+      if (run_online) { p.my_flag = 0; hipLaunchKernelGGL((attn_fwd_kernel<false, true, false, true, false, 2>), g, dim3(256), 0, stream, p); }
+    } else if (rangek) {
+      if (run_fixed) { p.my_flag = 1; hipLaunchKernelGGL((attn_fwd_kernel<true, true, true, true>), g, block, 0, stream, p); }
+      if (run_online) { p.my_flag = 0; hipLaunchKernelGGL((attn_fwd_kernel<false, true, true, true>), g, block, 0, stream, p); }
     } else {
-      if (full > 0) launch(full, pass != nullptr);
-      const long long stride = (long long)(k5_attention_state_bytes(H, q_len) / sizeof(float));
-      const int flags = p.flags;
-      float* state = p.state;
-      const bool to_state = (flags & 2) != 0;
-      float* base = (flags & 1) ? state : ws;
-      p.job0 = full; p.splits = S; p.state = base; p.split_state = ws + stride; p.split_stride = stride;
-      p.flags = (flags & 1) | 2;
-      launch(rem * S, true);
-      hipLaunchKernelGGL(attn_merge_kernel, dim3(rem), dim3(256), 0, stream, base, ws + stride, stride, S, full, H, q_len, p.nqb, 1.f,
-                         (bf16_t*)O, ldo, (run_fixed && !run_online) ? 1 : 0, (run_fixed && run_online) ? head_flags : nullptr,
-                         to_state ? state : nullptr, p.job_flags);
+      if (run_fixed) { p.my_flag = 1; hipLaunchKernelGGL((attn_fwd_kernel<true, true, false, true>), g, block, 0, stream, p); }
+      if (run_online) { p.my_flag = 0; hipLaunchKernelGGL((attn_fwd_kernel<false, true, false, true>), g, block, 0, stream, p); }
     }
-  } else if (bounded) {
-    hipLaunchKernelGGL((attn_fwd_kernel<true, true, false>), grid, block, 0, stream, p);
-  } else {
-    hipLaunchKernelGGL((attn_fwd32_kernel<false, true, false>), grid, block, 0, stream, p);
-  }
-  return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
-}
-
-int k5_launch_attention_bf16_bounded(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len,
-                                     int kv_len, int ldq, int ldk, int ldvt, int ldo, float score_bound,
-                                     hipStream_t stream) {
-  return k5_launch_attention_bf16_chunked(Q, K, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, score_bound, 0, 0, stream);
+  };
+  return attn_launch_balanced(a, p, f, a.k_prescaled && group_rows == 4 && a.balance, K5_ATTN_MAX_SPLITS, pass != nullptr, launch);
 }

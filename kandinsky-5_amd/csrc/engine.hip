@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <map>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -177,101 +178,74 @@ struct Comm {
     }
     return K5_OK;
   }
-  // in-place all-gather: every rank's chunk already sits at buf + rank*count*elem
-  int all_gather_inplace(void* buf, size_t count_per_rank, size_t elem_bytes, hipStream_t s) {
-    char* b = (char*)buf;
-    if (ipc) return ipc_status(ipc->all_gather_inplace(buf, count_per_rank * elem_bytes, s));
-    if (loop) {
-      // pull every peer's chunk out of the peer's copy of the buffer; the call completes (stream-wise) only when every peer
-      // has pulled mine, as an RCCL all-gather does — the caller may overwrite its own slot afterwards
-      const size_t chunk = count_per_rank * elem_bytes;
-      loop->ptr[rank] = buf;
-      HIPCHK(hipEventRecord(loop->ready[rank], s));
-      pthread_barrier_wait(&loop->bar);
-      for (int p = 0; p < world; ++p) {
-        if (p == rank) continue;
-        HIPCHK(hipStreamWaitEvent(s, loop->ready[p], 0));
-        HIPCHK(hipMemcpyAsync(b + (size_t)p * chunk, (const char*)loop->ptr[p] + (size_t)p * chunk, chunk, hipMemcpyDeviceToDevice, s));
-      }
-      HIPCHK(hipEventRecord(loop->pulled[rank], s));
-      pthread_barrier_wait(&loop->bar);
-      for (int p = 0; p < world; ++p)
-        if (p != rank) HIPCHK(hipStreamWaitEvent(s, loop->pulled[p], 0));
-      return K5_OK;
+  // loopback rendezvous shared by the four collectives: publish my buffer, pull what `pull(p, peer's buffer)` names out of every peer's
+  // (skip: nothing to trade with that peer, its ready event is not waited on); the call completes (stream-wise) only when every peer has
+  // pulled mine, as an RCCL collective does — the caller may overwrite what it published afterwards
+  struct Pull { void* dst; const void* src; size_t bytes; bool skip; };
+  template <class F> int loop_pull(void* my_ptr, hipStream_t s, F pull) {
+    loop->ptr[rank] = my_ptr;
+    HIPCHK(hipEventRecord(loop->ready[rank], s));
+    pthread_barrier_wait(&loop->bar);
+    for (int p = 0; p < world; ++p) {
+      if (p == rank) continue;
+      const Pull c = pull(p, (const char*)loop->ptr[p]);
+      if (c.skip) continue;
+      HIPCHK(hipStreamWaitEvent(s, loop->ready[p], 0));
+      HIPCHK(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, s));
     }
-    const ncclResult_t r = AllGather(b + (size_t)rank * count_per_rank * elem_bytes, b, count_per_rank * elem_bytes,
-                                     ncclUint8, comm, s);
-    if (r != ncclSuccess) { k5_set_error("ncclAllGather: %s", GetErrorString(r)); return K5_ERR_HIP; }
+    HIPCHK(hipEventRecord(loop->pulled[rank], s));
+    pthread_barrier_wait(&loop->bar);
+    for (int p = 0; p < world; ++p)
+      if (p != rank) HIPCHK(hipStreamWaitEvent(s, loop->pulled[p], 0));
+    return K5_OK;
+  }
+  // one grouped send / recv per peer (all xGMI links at once): send_recv(p) issues what this rank trades with peer p
+  template <class F> int rccl_group(const char* what, F send_recv) {
+    if (!can_exchange()) { k5_set_error("RCCL library lacks ncclSend / ncclRecv / ncclGroup*"); return K5_ERR_STATE; }
+    ncclResult_t r = GroupStart();
+    for (int p = 0; p < world && r == ncclSuccess; ++p)
+      if (p != rank) r = send_recv(p);
+    const ncclResult_t e = GroupEnd();
+    if (r == ncclSuccess) r = e;
+    if (r != ncclSuccess) { k5_set_error("ncclSend/ncclRecv group%s: %s", what, GetErrorString(r)); return K5_ERR_HIP; }
     return K5_OK;
   }
   bool can_exchange() const { return loop || ipc || (Send && Recv && GroupStart && GroupEnd); }
+  // in-place all-gather: every rank's chunk already sits at buf + rank*count*elem
+  int all_gather_inplace(void* buf, size_t count_per_rank, size_t elem_bytes, hipStream_t s) {
+    char* b = (char*)buf;
+    const size_t chunk = count_per_rank * elem_bytes;
+    if (ipc) return ipc_status(ipc->all_gather_inplace(buf, chunk, s));
+    if (loop) return loop_pull(buf, s, [&](int p, const char* peer) { return Pull{b + (size_t)p * chunk, peer + (size_t)p * chunk, chunk, false}; });
+    const ncclResult_t r = AllGather(b + (size_t)rank * chunk, b, chunk, ncclUint8, comm, s);
+    if (r != ncclSuccess) { k5_set_error("ncclAllGather: %s", GetErrorString(r)); return K5_ERR_HIP; }
+    return K5_OK;
+  }
   // all-to-all (Ulysses): block p of `send` (block_bytes each) goes to rank p, block p of `recv` comes from rank p; send != recv.
-  // One grouped send/recv per peer (all xGMI links at once); the rank's own block is a device-to-device copy.
+  // The rank's own block is a device-to-device copy.
   int all_to_all(const void* send, void* recv, size_t block_bytes, hipStream_t s) {
     const char* sb = (const char*)send; char* rb = (char*)recv;
     HIPCHK(hipMemcpyAsync(rb + (size_t)rank * block_bytes, sb + (size_t)rank * block_bytes, block_bytes, hipMemcpyDeviceToDevice, s));
     if (world == 1) return K5_OK;
     if (ipc) return ipc_status(ipc->all_to_all(send, recv, block_bytes, s));
-    if (loop) {
-      loop->ptr[rank] = const_cast<void*>(send);
-      HIPCHK(hipEventRecord(loop->ready[rank], s));
-      pthread_barrier_wait(&loop->bar);
-      for (int p = 0; p < world; ++p) {
-        if (p == rank) continue;
-        HIPCHK(hipStreamWaitEvent(s, loop->ready[p], 0));
-        HIPCHK(hipMemcpyAsync(rb + (size_t)p * block_bytes, (const char*)loop->ptr[p] + (size_t)rank * block_bytes, block_bytes, hipMemcpyDeviceToDevice, s));
-      }
-      HIPCHK(hipEventRecord(loop->pulled[rank], s));
-      pthread_barrier_wait(&loop->bar);
-      for (int p = 0; p < world; ++p)
-        if (p != rank) HIPCHK(hipStreamWaitEvent(s, loop->pulled[p], 0));   // the peers have read my send buffer: it may be rewritten
-      return K5_OK;
-    }
-    if (!can_exchange()) { k5_set_error("RCCL library lacks ncclSend / ncclRecv / ncclGroup*"); return K5_ERR_STATE; }
-    ncclResult_t r = GroupStart();
-    for (int p = 0; p < world && r == ncclSuccess; ++p) {
-      if (p == rank) continue;
-      r = Send(sb + (size_t)p * block_bytes, block_bytes, ncclUint8, p, comm, s);
-      if (r == ncclSuccess) r = Recv(rb + (size_t)p * block_bytes, block_bytes, ncclUint8, p, comm, s);
-    }
-    const ncclResult_t e = GroupEnd();
-    if (r == ncclSuccess) r = e;
-    if (r != ncclSuccess) { k5_set_error("ncclSend/ncclRecv group (all-to-all): %s", GetErrorString(r)); return K5_ERR_HIP; }
-    return K5_OK;
+    if (loop) return loop_pull(const_cast<void*>(send), s, [&](int p, const char* peer) {
+      return Pull{rb + (size_t)p * block_bytes, peer + (size_t)rank * block_bytes, block_bytes, false}; });
+    return rccl_group(" (all-to-all)", [&](int p) {
+      const ncclResult_t r = Send(sb + (size_t)p * block_bytes, block_bytes, ncclUint8, p, comm, s);
+      return r == ncclSuccess ? Recv(rb + (size_t)p * block_bytes, block_bytes, ncclUint8, p, comm, s) : r; });
   }
   // part of an in-place all-gather: the bytes [off, off + cnt) of every rank's slot (slot_bytes each, rank p's at p * slot_bytes)
-  // travel to every peer — one grouped send/recv per peer, i.e. all seven xGMI links of the GPU at once, so the first slice of ALL
+  // travel to every peer — all seven xGMI links of the GPU at once, so the first slice of ALL
   // peers has landed when a fraction cnt / slot_bytes of the gather time has passed (a ring all-gather completes nothing early).
   int slot_exchange(void* buf, size_t slot_bytes, size_t off, size_t cnt, hipStream_t s) {
     char* b = (char*)buf;
     if (cnt == 0 || world == 1) return K5_OK;
     if (ipc) return ipc_status(ipc->slot_exchange(buf, slot_bytes, off, cnt, s));
-    if (loop) {
-      loop->ptr[rank] = buf;
-      HIPCHK(hipEventRecord(loop->ready[rank], s));
-      pthread_barrier_wait(&loop->bar);
-      for (int p = 0; p < world; ++p) {
-        if (p == rank) continue;
-        HIPCHK(hipStreamWaitEvent(s, loop->ready[p], 0));
-        HIPCHK(hipMemcpyAsync(b + (size_t)p * slot_bytes + off, (const char*)loop->ptr[p] + (size_t)p * slot_bytes + off, cnt, hipMemcpyDeviceToDevice, s));
-      }
-      HIPCHK(hipEventRecord(loop->pulled[rank], s));
-      pthread_barrier_wait(&loop->bar);
-      for (int p = 0; p < world; ++p)
-        if (p != rank) HIPCHK(hipStreamWaitEvent(s, loop->pulled[p], 0));
-      return K5_OK;
-    }
-    if (!can_exchange()) { k5_set_error("RCCL library lacks ncclSend / ncclRecv / ncclGroup*"); return K5_ERR_STATE; }
-    ncclResult_t r = GroupStart();
-    for (int p = 0; p < world && r == ncclSuccess; ++p) {
-      if (p == rank) continue;
-      r = Send(b + (size_t)rank * slot_bytes + off, cnt, ncclUint8, p, comm, s);
-      if (r == ncclSuccess) r = Recv(b + (size_t)p * slot_bytes + off, cnt, ncclUint8, p, comm, s);
-    }
-    const ncclResult_t e = GroupEnd();
-    if (r == ncclSuccess) r = e;
-    if (r != ncclSuccess) { k5_set_error("ncclSend/ncclRecv group: %s", GetErrorString(r)); return K5_ERR_HIP; }
-    return K5_OK;
+    if (loop) return loop_pull(buf, s, [&](int p, const char* peer) {
+      return Pull{b + (size_t)p * slot_bytes + off, peer + (size_t)p * slot_bytes + off, cnt, false}; });
+    return rccl_group("", [&](int p) {
+      const ncclResult_t r = Send(b + (size_t)rank * slot_bytes + off, cnt, ncclUint8, p, comm, s);
+      return r == ncclSuccess ? Recv(b + (size_t)p * slot_bytes + off, cnt, ncclUint8, p, comm, s) : r; });
   }
   // planned exchange (two-level schedule, sp_plan_2d): tab[src * world + dst] = (offset in src's `send`, offset in dst's `recv`, bytes) — the
   // same table on every rank; 0 bytes = the pair has nothing to trade (peers outside a sub-group).  Every rank of the world issues every call.
@@ -282,39 +256,20 @@ struct Comm {
     if (me.bytes > 0) HIPCHK(hipMemcpyAsync(rb + me.recv_off, sb + me.send_off, (size_t)me.bytes, hipMemcpyDeviceToDevice, s));
     if (world == 1) return K5_OK;
     if (ipc) return ipc_status(ipc->exchange(send, recv, tab, s));
-    if (loop) {
-      loop->ptr[rank] = const_cast<void*>(send);
-      HIPCHK(hipEventRecord(loop->ready[rank], s));
-      pthread_barrier_wait(&loop->bar);
-      for (int p = 0; p < world; ++p) {
-        const k5ipc::Xfer& e = tab[(size_t)p * world + rank];
-        if (p == rank || e.bytes <= 0) continue;
-        HIPCHK(hipStreamWaitEvent(s, loop->ready[p], 0));
-        HIPCHK(hipMemcpyAsync(rb + e.recv_off, (const char*)loop->ptr[p] + e.send_off, (size_t)e.bytes, hipMemcpyDeviceToDevice, s));
-      }
-      HIPCHK(hipEventRecord(loop->pulled[rank], s));
-      pthread_barrier_wait(&loop->bar);
-      for (int p = 0; p < world; ++p)
-        if (p != rank) HIPCHK(hipStreamWaitEvent(s, loop->pulled[p], 0));
-      return K5_OK;
-    }
-    if (!can_exchange()) { k5_set_error("RCCL library lacks ncclSend / ncclRecv / ncclGroup*"); return K5_ERR_STATE; }
-    ncclResult_t r = GroupStart();
-    for (int p = 0; p < world && r == ncclSuccess; ++p) {
-      if (p == rank) continue;
+    if (loop) return loop_pull(const_cast<void*>(send), s, [&](int p, const char* peer) {
+      const k5ipc::Xfer& e = tab[(size_t)p * world + rank];
+      return Pull{rb + e.recv_off, peer + e.send_off, (size_t)e.bytes, e.bytes <= 0}; });
+    return rccl_group(" (planned exchange)", [&](int p) {
       const k5ipc::Xfer& out = tab[(size_t)rank * world + p];
       const k5ipc::Xfer& in = tab[(size_t)p * world + rank];
+      ncclResult_t r = ncclSuccess;
       if (out.bytes > 0) r = Send(sb + out.send_off, (size_t)out.bytes, ncclUint8, p, comm, s);
       if (r == ncclSuccess && in.bytes > 0) r = Recv(rb + in.recv_off, (size_t)in.bytes, ncclUint8, p, comm, s);
-    }
-    const ncclResult_t e = GroupEnd();
-    if (r == ncclSuccess) r = e;
-    if (r != ncclSuccess) { k5_set_error("ncclSend/ncclRecv group (planned exchange): %s", GetErrorString(r)); return K5_ERR_HIP; }
-    return K5_OK;
+      return r; });
   }
 };
 
-// ---- the two-level schedule's exchange plan ("sp_mode" = 2; run_self_attention_2d) ----
+// ---- the two-level schedule's exchange plan ("sp_mode" = 2; run_self_attention_heads) ----
 // G = gcd(heads, P) head groups of Hp = heads / G heads (Dp = D / G columns); S = P / G query splits.  Rank r serves head group r % G for the
 // queries of split r / G = the token shards of ranks sG .. sG + G - 1 (one contiguous token range).  Every block below is rows_pad x Dp bf16.
 //   SP_K   k' of the rank's rows, send [G][rows_pad][Dp] (block = head group) -> every peer p gets block g(p); recv [P][rows_pad][Dp] = token order
@@ -436,7 +391,7 @@ struct k5_dit {
   int sp_mode = 0;                                 // "sp_mode": 0 = K / V^T all-gather (any rank count), 1 = Ulysses all-to-all (heads % ranks == 0, dense attention)
   DevBuf ws_u_send, ws_u_recv, ws_u_vsend, ws_u_vrecv, ws_u_o, ws_u_orecv, ws_u_stats;   // Ulysses exchange buffers
   hipEvent_t ev_u_o = nullptr, ev_u_back = nullptr;
-  // two-level schedule ("sp_mode" = 2, run_self_attention_2d): the split's queries of the rank's head group, and the exchange plans of the
+  // two-level schedule ("sp_mode" = 2, run_self_attention_heads): the split's queries of the rank's head group, and the exchange plans of the
   // current shape (sp_plan_2d: SP_K, SP_VT, SP_Q, SP_O) — the other buffers are the Ulysses ones, grown to this schedule's sizes
   DevBuf ws_u_qrecv;
   std::vector<k5ipc::Xfer> sp_plan[4];
@@ -707,6 +662,78 @@ bool nabla_means_fused(const k5_dit* d, int rows, int heads) {
 }
 bool ff_fp8_in(const k5_dit* d, const BlockW& b, int rows) { return d->use_fp8 && b.w1_f8.p && rows >= 256; }
 
+// ---- the steps the self-attention schedules share ----
+// Softmax form per head, decided from the data (by_data): k5_launch_attn_flags turns the |q|^2 / |k'|^2 maxima the norm passes left into the
+// per-head flags both attention launches read.  With per-row softmax offsets ("row_offsets") heads with a Cauchy-Schwarz bound up to 190 keep
+// the fixed-offset kernel, each query row on its own constant offset |q| max|k'| - 90 (kmax), and the module's prefer-online table of this
+// branch (pref) is read here and updated after the attention (attn_pref_update).  Heads beyond the window: anchored offsets (anchor), sampled
+// by k5_launch_attn_row_anchor — dense attention only, and it needs the normalised queries in memory (not with the fused query norm).
+struct SoftmaxFormIn {
+  float* qstat = nullptr; float* kstat = nullptr;      // per head nq / nk partial maxima at strides qstride / kstride floats
+  int nk = 1, kstride = 0, nq = 1, qstride = 0;
+  int heads = 0, head0 = 0;                            // heads decided here; index of the first in the prefer-online table
+  float* centre = nullptr; float* rstat = nullptr;     // one GPU: the keys' centre and squared radii the norm pass left -> centred offsets (K5KeyCentre)
+  unsigned int* leave_sig = nullptr;                   // one GPU
+  hipEvent_t stats_ready = nullptr;                    // sharded: the gathered statistics arrive with this event
+  hipEvent_t data_ready = nullptr;                     // head-parallel: q / k' / V^T arrive with this event (waited for after the flags, by_data or not)
+  bool anchor = false;
+  const void* aq = nullptr; const void* ak = nullptr;  // the anchor's queries and the keys it samples (the gather: the rank's OWN keys, in place before
+  int aq_rows = 0, ak_rows = 0, ldq = 0, ldk = 0, key0 = 0, kv_total = 0;   // the gather); key0 = key index of query row 0's token
+  const char* anchor_fam = nullptr;                    // profiling family of the anchor launch where it does not sit inside a scope already
+};
+struct SoftmaxForm {
+  const int* hflags = nullptr; const float* kmax = nullptr; int* pref = nullptr;
+  K5KeyCentre kcen{nullptr, nullptr, nullptr};
+  bool centred = false;                                // kcen carries a centre + radius and / or row anchors
+  const K5KeyCentre* key_centre() const { return centred ? &kcen : nullptr; }
+};
+int softmax_form(k5_dit* d, hipStream_t s, const AttnW& a, int pref_slot, bool by_data, const SoftmaxFormIn& in, SoftmaxForm& f) {
+  const int H = d->Hh;
+  if (by_data) {
+    if (in.stats_ready) HIPCHK(hipStreamWaitEvent(s, in.stats_ready, 0));
+    f.hflags = d->ws_attn_flags.as<int>();
+    float* kmax_w = d->row_offsets ? d->ws_attn_flags.as<float>() + H : nullptr;
+    f.kmax = kmax_w;
+    if (kmax_w) { K5CHK(ensure_zeroed(a.pref, (size_t)2 * H * 4, s)); f.pref = a.pref.as<int>() + (size_t)pref_slot * H + in.head0; }
+    K5CHK(k5_launch_attn_flags(in.qstat, in.kstat, in.nk, in.kstride, in.heads, 0, d->ws_attn_flags.as<int>(), d->ws_attn_cnt.as<unsigned long long>(), s, kmax_w,
+                               f.pref, in.centre ? in.rstat : nullptr, in.centre ? kmax_w + H : nullptr, in.nq, in.qstride, kmax_w && in.anchor, in.leave_sig));
+    if (in.centre) { f.kcen.centre = in.centre; f.kcen.radius = kmax_w + H; f.centred = true; }
+  }
+  if (in.data_ready) HIPCHK(hipStreamWaitEvent(s, in.data_ready, 0));
+  if (f.kmax && in.anchor) {
+    K5CHK(d->ws_attn_anchor.ensure((size_t)in.heads * in.aq_rows * 4));
+    std::optional<Scope> sc;
+    if (in.anchor_fam) sc.emplace(d, s, in.anchor_fam);
+    K5CHK(k5_launch_attn_row_anchor(in.aq, in.ak, in.heads, in.aq_rows, in.ak_rows, in.ldq, in.ldk, in.key0, in.kv_total, f.kmax, d->ws_attn_anchor.as<float>(), s));
+    f.kcen.row_anchor = d->ws_attn_anchor.as<float>();
+    f.centred = true;
+  }
+  return K5_OK;
+}
+// 64-query rows per key-tile list = per workgroup of a NABLA attention launch (4: the 256-query form, which every dense launch uses too).
+// Sharded: the 128- / 64-query workgroups only without the two-pass machinery, which lives on the 256-query form.
+int attn_group_rows(const k5_dit* d, bool nabla, bool sharded) {
+  if (!nabla) return 4;
+  return (!sharded || (d->nabla_grp_now < 4 && d->sp_nabla_passes == 1)) ? d->nabla_grp_now : 4;
+}
+// after the attention: a head more than a quarter of whose (head, query block) jobs fell back goes to the online form the next time
+int attn_pref_update(k5_dit* d, hipStream_t s, const SoftmaxForm& f, int heads, int q_rows, int group_rows, unsigned int* leave_sig = nullptr) {
+  if (!f.kmax) return K5_OK;
+  return k5_launch_attn_pref_update(d->ws_attn_bal.as<float>(), heads, q_rows, group_rows, f.pref, s, leave_sig);
+}
+// x_resid += gate * out_l(o), fused in the out GEMM; f8_out: e4m3 activations (opt-in, k5_dit_set_fp8 bit 2)
+int attn_out_projection(k5_dit* d, hipStream_t s, const AttnW& a, const void* o, int rows, void* resid, const float* gate, bool f8_out = false) {
+  const int D = d->D;
+  if (f8_out) {
+    K5CHK(d->ws_h8.ensure((size_t)rows * D));
+    Scope sc(d, s, "elementwise");
+    K5CHK(k5_launch_quant_rows_fp8(o, d->ws_h8.p, nullptr, rows, D, D, D, s));
+  }
+  Scope sc(d, s, "gemm");
+  if (f8_out) return k5_launch_gemm_fp8(d->ws_h8.p, a.wo8.p, a.so.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s, a.bo.as<float>(), 0);
+  return k5_launch_gemm_bf16(o, a.wo.p, a.bo.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s);
+}
+
 int run_self_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, int rows, void* qk, void* vt,
                        void* o, const float* cosT, const float* sinT, void* resid, const float* gate,
                        const char* fam_attn, const NablaArgs* nabla = nullptr, int pref_slot = 0, bool h8_ready = false) {
@@ -732,15 +759,12 @@ int run_self_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, 
   }
   const bool pre = vis && rows % 64 == 0;   // visual blocks only (not the text blocks)
   const bool by_data = pre && d->attn_mode == K5_ATTN_AUTO;            // per-head flags from the data
-  const int* hflags = nullptr;
-  // per-row softmax offsets: heads with a Cauchy-Schwarz bound up to 190 keep the fixed-offset kernel, each query row on its own
-  // constant offset |q| max|k'| - 90
-  const float* kmax = nullptr;
-  K5KeyCentre kcen{nullptr, nullptr};
-  const K5KeyCentre* kcp = nullptr;
+  SoftmaxForm sf;
   // dense visual blocks: norm_qk + RoPE of the queries happen in the attention kernel's Q load ("attn_fuse_qnorm")
   const bool fuse_q = pre && !nabla && (d->fuse_qnorm || d->fuse_now) && ((by_data && d->row_offsets) || d->attn_mode == K5_ATTN_ONLINE);
   unsigned int* leave_sig = (d->leave_collect && d->ws_leave_sig.p) ? d->ws_leave_sig.as<unsigned int>() : nullptr;
+  const bool fuse_means = pre && nabla && nabla_means_fused(d, rows, 2 * H);   // NABLA: the norm pass takes the block means itself
+  const int grp = pre ? attn_group_rows(d, nabla != nullptr, false) : 4;
   if (by_data) K5CHK(ensure_attn_flags(d, s));   // before the counters' address is taken
   const K5QueryNorm qn{a.norm.as<float>(), cosT, sinT, by_data ? d->ws_attn_cnt.as<unsigned long long>() : nullptr};
   {
@@ -751,7 +775,6 @@ int run_self_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, 
     // 1-3) the unscaled keys stay in place for k5_launch_nabla_select_rect's own means pass and the scaled copy goes to its own buffer.
     void* kc = nullptr;
     void *mq = nullptr, *mk = nullptr;
-    const bool fuse_means = pre && nabla && nabla_means_fused(d, rows, 2 * H);
     if (fuse_means) {
       K5CHK(d->ws_nabla.ensure(nabla_ws_bytes(d, H, rows / 64, rows / 64)));
       k5_nabla_workspace_means(d->ws_nabla.p, H, rows / 64, &mq, &mk);
@@ -766,33 +789,24 @@ int run_self_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, 
     else
       K5CHK(k5_launch_rmsnorm_rope(qk, a.norm.as<float>(), cosT, sinT, rows, 2 * H, 2 * D, hc, s, K5_SOFTMAX_C, pre ? H : 0x7fffffff, kc, D, stats, d->ws_attn_part.as<float>(),
                                    pre ? centre : nullptr, mq, rows / 64, mk, rows / 64));
-    if (by_data) {
-      hflags = d->ws_attn_flags.as<int>();
-      float* kmax_w = d->row_offsets ? d->ws_attn_flags.as<float>() + H : nullptr;
-      kmax = kmax_w;
-      if (kmax_w) K5CHK(ensure_zeroed(a.pref, (size_t)2 * H * 4, s));
-      // heads beyond the Cauchy-Schwarz window: anchored offsets (needs the normalised queries in memory: not with the fused query norm)
-      const bool anchored = centre && d->anchor && !fuse_q && !nabla;   // dense attention only (k5_launch_attn_row_anchor)
-      K5CHK(k5_launch_attn_flags(stats, stats + H, 1, H, H, 0, d->ws_attn_flags.as<int>(), d->ws_attn_cnt.as<unsigned long long>(), s, kmax_w,
-                                 kmax_w ? (a.pref.as<int>() + (size_t)pref_slot * H) : nullptr, centre ? stats + 2 * H : nullptr, centre ? kmax_w + H : nullptr, 1, 0, anchored, leave_sig));
-      if (centre) { kcen.centre = centre; kcen.radius = kmax_w + H; kcp = &kcen; }
-      if (anchored) {
-        K5CHK(d->ws_attn_anchor.ensure((size_t)H * rows * 4));
-        K5CHK(k5_launch_attn_row_anchor(qk, (const bf16_t*)qk + D, H, rows, rows, 2 * D, 2 * D, 0, rows, kmax_w, d->ws_attn_anchor.as<float>(), s));
-        kcen.row_anchor = d->ws_attn_anchor.as<float>();
-      }
+    if (by_data) {   // the only schedule with centred offsets and the leave signal; the anchor launch is booked under this scope
+      SoftmaxFormIn in;
+      in.qstat = stats; in.kstat = stats + H; in.nk = 1; in.kstride = H; in.heads = H;
+      in.centre = centre; in.rstat = stats + 2 * H; in.leave_sig = leave_sig;
+      in.anchor = d->anchor && !fuse_q && !nabla;
+      in.aq = qk; in.ak = (const bf16_t*)qk + D; in.aq_rows = rows; in.ak_rows = rows; in.ldq = 2 * D; in.ldk = 2 * D; in.key0 = 0; in.kv_total = rows;
+      K5CHK(softmax_form(d, s, a, pref_slot, true, in, sf));
     }
   }
   const int variant = pre ? d->attn_mode : K5_ATTN_AUTO;
   if (nabla) {  // nablaT_v2 map (utils.py:136-163) + block-sparse attention (nn.py:257-280)
     const int nb = rows / 64;
-    const int grp = pre ? d->nabla_grp_now : 4;   // 64-query rows per key-tile list = per attention workgroup
     const int pair = (grp == 2 && d->nabla_pair_frames) ? nabla->Hb * nabla->Wb : 0;
     K5CHK(d->ws_nabla.ensure(nabla_ws_bytes(d, H, nb, nb)));
     {
       Scope sc(d, s, "nabla_map");
-      const bool fm = pre && nabla_means_fused(d, rows, 2 * H);   // the means are in the workspace already
-      K5CHK(k5_launch_nabla_select_rect(fm ? nullptr : qk, fm ? nullptr : (const bf16_t*)qk + D, 2 * D, 2 * D, H, rows, 0, rows, nabla->T, nabla->Hb, nabla->Wb, nabla->wT,
+      // fuse_means: the means are in the workspace already
+      K5CHK(k5_launch_nabla_select_rect(fuse_means ? nullptr : qk, fuse_means ? nullptr : (const bf16_t*)qk + D, 2 * D, 2 * D, H, rows, 0, rows, nabla->T, nabla->Hb, nabla->Wb, nabla->wT,
                                         nabla->wH, nabla->wW, nabla->P, d->ws_nabla.p, s, 0, 0, grp, pair));
     }
     if (d->nabla_tap) {   // diagnostics (k5_dit_set_nabla_tap): this launch's map, expanded, behind the ones already taken
@@ -815,33 +829,29 @@ int run_self_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, 
     Scope sc(d, s, fam_attn);
     // (no tail balancing here: 10 248 jobs are 20 rounds of unequal lists — measured -0.6 % at density 0.81, +1 % at 0.12, +2.4 % at
     // 0.05; a token shard's 5 rounds are another matter, run_self_attention_sp)
-    const bool kin = !pre || nabla_means_fused(d, rows, 2 * H);   // keys in place in the fused q | k buffer (scaled there when pre)
-    K5CHK(k5_launch_attention_bf16_sparse(qk, kin ? (const bf16_t*)qk + D : d->ws_kc.as<bf16_t>(), vt, o, H, rows, rows, 2 * D, kin ? 2 * D : D,
-                                          ldvt, D, pre ? 0.f : a.score_bound, list, cnt, nb, 0, 0, s, pre, hflags, variant, kmax, nullptr,
-                                          pre ? d->ws_attn_bal.as<float>() : nullptr, grp, false, kcp, pair));
+    const bool kin = !pre || fuse_means;   // keys in place in the fused q | k buffer (scaled there when pre)
+    K5AttnSparseArgs at;
+    at.Q = qk; at.K = kin ? (const bf16_t*)qk + D : d->ws_kc.as<bf16_t>(); at.Vt = vt; at.O = o;
+    at.H = H; at.q_len = rows; at.kv_len = rows; at.ldq = 2 * D; at.ldk = kin ? 2 * D : D; at.ldvt = ldvt; at.ldo = D;
+    at.score_bound = pre ? 0.f : a.score_bound; at.stream = s;
+    at.k_prescaled = pre; at.head_flags = sf.hflags; at.variant = variant; at.row_offset_kmax = sf.kmax; at.key_centre = sf.key_centre();
+    at.list = list; at.cnt = cnt; at.list_stride = nb;
+    at.balance_ws = pre ? d->ws_attn_bal.as<float>() : nullptr; at.balance = false;
+    at.group_rows = grp; at.pair_stride = pair;
+    K5CHK(k5_launch_attention_bf16_sparse(at));
   } else {
     K5CHK(d->ws_attn_bal.ensure(k5_attention_balance_bytes(H, rows)));
     Scope sc(d, s, fam_attn);
-    K5CHK(k5_launch_attention_bf16_range(qk, (const bf16_t*)qk + D, vt, o, H, rows, rows, 2 * D, 2 * D, ldvt, D, pre ? 0.f : a.score_bound, 0, 0, 0, -1,
-                                         0x7fffffff, 0, nullptr, 0, s, d->ws_attn_bal.as<float>(), pre, hflags, variant, nullptr, kmax, 0,
-                                         fuse_q ? &qn : nullptr, kcp));
+    K5AttnRangeArgs at;
+    at.Q = qk; at.K = (const bf16_t*)qk + D; at.Vt = vt; at.O = o;
+    at.H = H; at.q_len = rows; at.kv_len = rows; at.ldq = 2 * D; at.ldk = 2 * D; at.ldvt = ldvt; at.ldo = D;
+    at.score_bound = pre ? 0.f : a.score_bound; at.stream = s; at.balance_ws = d->ws_attn_bal.as<float>();
+    at.k_prescaled = pre; at.head_flags = sf.hflags; at.variant = variant; at.row_offset_kmax = sf.kmax; at.key_centre = sf.key_centre();
+    at.query_norm = fuse_q ? &qn : nullptr;
+    K5CHK(k5_launch_attention_bf16_range(at));
   }
-  if (kmax) K5CHK(k5_launch_attn_pref_update(d->ws_attn_bal.as<float>(), H, rows, nabla ? (pre ? d->nabla_grp_now : 4) : 4, (a.pref.as<int>() + (size_t)pref_slot * H), s, leave_sig));
-  if (f8_out) {
-    K5CHK(d->ws_h8.ensure((size_t)rows * D));
-    {
-      Scope sc(d, s, "elementwise");
-      K5CHK(k5_launch_quant_rows_fp8(o, d->ws_h8.p, nullptr, rows, D, D, D, s));
-    }
-    Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_fp8(d->ws_h8.p, a.wo8.p, a.so.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s, a.bo.as<float>(), 0));
-    return K5_OK;
-  }
-  {
-    Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(o, a.wo.p, a.bo.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s));
-  }
-  return K5_OK;
+  K5CHK(attn_pref_update(d, s, sf, H, rows, grp, leave_sig));
+  return attn_out_projection(d, s, a, o, rows, resid, gate, f8_out);
 }
 
 // Sequence-parallel visual self-attention: `rows` = this rank's token rows, N = rows * world keys in total.
@@ -868,7 +878,7 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
   // keys stay local (ws_kc), their means (28 x 64 values per block) travel with the gather, and the gathered keys are the scaled ones —
   // the same kernels, flags and per-row offsets as on one GPU (round 1 / early round 2: unscaled keys, weight-derived bound, and
   // with it the online-max 32x32 kernel for any checkpoint whose QK-norm gains exceed max|w_q| max|w_k| = 3.96).
-  const bool pre = true;
+  const bool fuse_means = nabla && nabla_means_fused(d, rows, H);   // NABLA: the norm passes take the block means themselves
   const bool by_data = d->attn_mode == K5_ATTN_AUTO;
   float *qstat = nullptr, *kstat = nullptr;
   if (by_data) { K5CHK(ensure_attn_flags(d, s)); qstat = d->ws_attn_stats.as<float>(); kstat = qstat + H; }
@@ -900,12 +910,11 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
     Scope sc(d, s, "elementwise");
     // dense: scaled in place; NABLA: unscaled in place (kun), the scaled copy goes to this rank's slot of the gather buffer
     // NABLA: the unscaled keys' block means (all the map needs of them) come out of this pass ("nabla_fuse_means"; before: a second pass over kun)
-    const bool fm = nabla && nabla_means_fused(d, rows, H);
     K5CHK(k5_launch_rmsnorm_rope(kun, a.norm.as<float>() + 64, cosT, sinT, rows, H, D, nullptr, s, K5_SOFTMAX_C, 0,
                                  nabla ? kloc : nullptr, nabla ? D : 0, by_data ? kstat + (size_t)r * H : nullptr, d->ws_attn_part.as<float>(), nullptr,
-                                 nullptr, 0, fm ? kmeans + (size_t)r * H * slot_blocks * 64 : nullptr, slot_blocks));
+                                 nullptr, 0, fuse_means ? kmeans + (size_t)r * H * slot_blocks * 64 : nullptr, slot_blocks));
   }
-  if (nabla && !nabla_means_fused(d, rows, H)) {
+  if (nabla && !fuse_means) {
     Scope sc(d, s, "nabla_map");
     K5CHK(k5_launch_nabla_block_means(kun, D, H, rows / 64, slot_blocks, kmeans + (size_t)r * H * slot_blocks * 64, s));
   }
@@ -939,7 +948,7 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
   const K5QueryNorm* qnp = fuse_q ? &qn : nullptr;
   if (!fuse_q) {
     void* mq = nullptr;
-    if (nabla && nabla_means_fused(d, rows, H)) {   // the query-block means of the rank's rows, straight into the map's workspace
+    if (fuse_means) {   // the query-block means of the rank's rows, straight into the map's workspace
       K5CHK(d->ws_nabla.ensure(nabla_ws_bytes(d, H, N / 64, rows / 64)));
       k5_nabla_workspace_means(d->ws_nabla.p, H, N / 64, &mq, nullptr);
     }
@@ -975,46 +984,40 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
     }
   }
   HIPCHK(hipEventRecord(d->ev_gathered, cs));
-  const int* hflags = nullptr;
   // per-row softmax offsets (§4.1) across the passes: a row that underflows in ANY pass marks its head late (flag 2), the fixed
   // form then skips the head and the online form of the LAST pass recomputes it from scratch over all keys (late_pass 1 / 2)
-  const float* kmax = nullptr;
-  K5KeyCentre kcen{nullptr, nullptr, nullptr};
-  const K5KeyCentre* kcp = nullptr;
-  if (by_data) {
-    HIPCHK(hipStreamWaitEvent(s, d->ev_stats, 0));
-    hflags = d->ws_attn_flags.as<int>();
-    float* kmax_w = d->row_offsets ? d->ws_attn_flags.as<float>() + H : nullptr;
-    kmax = kmax_w;
-    if (kmax_w) K5CHK(ensure_zeroed(a.pref, (size_t)2 * H * 4, s));
-    // heads beyond the window of the plain offsets: anchored offsets, sampled from the rank's OWN keys (the row's own block is among them;
+  SoftmaxForm sf;
+  {
+    // plain offsets; heads beyond their window: anchored offsets, sampled from the rank's OWN keys (the row's own block is among them;
     // they are in place before the gather) — every pass of the schedule then runs the head on them
-    const bool anchored = kmax_w && d->anchor && !fuse_q && !nabla;   // dense attention only
-    K5CHK(k5_launch_attn_flags(qstat, kstat, P, H, H, 0, d->ws_attn_flags.as<int>(), d->ws_attn_cnt.as<unsigned long long>(), s, kmax_w,
-                               kmax_w ? (a.pref.as<int>() + (size_t)pref_slot * H) : nullptr, nullptr, nullptr, 1, 0, anchored));
-    if (anchored) {
-      K5CHK(d->ws_attn_anchor.ensure((size_t)H * rows * 4));
-      K5CHK(k5_launch_attn_row_anchor(q, kloc, H, rows, rows, D, D, 0, N, kmax_w, d->ws_attn_anchor.as<float>(), s));
-      kcen.row_anchor = d->ws_attn_anchor.as<float>();
-      kcp = &kcen;
-    }
+    SoftmaxFormIn in;
+    in.qstat = qstat; in.kstat = kstat; in.nk = P; in.kstride = H; in.heads = H; in.stats_ready = d->ev_stats;
+    in.anchor = d->anchor && !fuse_q && !nabla;
+    in.aq = q; in.ak = kloc; in.aq_rows = rows; in.ak_rows = rows; in.ldq = D; in.ldk = D; in.key0 = 0; in.kv_total = N;
+    K5CHK(softmax_form(d, s, a, pref_slot, by_data, in, sf));
   }
-  const int variant = pre ? d->attn_mode : K5_ATTN_AUTO;
+  const int grp = attn_group_rows(d, nabla != nullptr, true);
+  // what every attention launch of the schedule shares: the rank's queries against the gathered K' / V^T (chunked per rank)
+  K5AttnArgs common;
+  common.Q = q; common.K = kfull; common.Vt = vtfull; common.O = o;
+  common.H = H; common.q_len = rows; common.kv_len = N; common.ldq = D; common.ldk = D; common.ldvt = ldv; common.ldo = D;
+  common.vt_chunk_keys = rows_pad; common.vt_chunk_stride = (long long)D * ldv;
+  common.stream = s;   // balance_ws: set per branch once ws_attn_bal is sized
+  common.k_prescaled = true; common.head_flags = sf.hflags; common.variant = d->attn_mode; common.row_offset_kmax = sf.kmax; common.key_centre = sf.key_centre();
+  const float* kmax = sf.kmax;
   if (nabla) {
     // NABLA under sequence parallelism: the map rows of this rank's query blocks need the block means of
     // ALL keys -> wait for the gathered means, bring them into the map's layout, select (local query blocks x all key blocks)
     // while K' / V^T are still on their way; then the list-driven attention on the chunked V^T layout (single pass).
     HIPCHK(hipStreamWaitEvent(s, d->ev_means, 0));
     const int nb = N / 64;
-    // sparse maps: 128-query workgroups (lists per two rows, see nabla_group_rows) — without the split-job / two-pass machinery, which
-    // lives on the 256-query form; dense maps: that form, balanced
-    const int grp = (d->nabla_grp_now < 4 && d->sp_nabla_passes == 1) ? d->nabla_grp_now : 4;
+    // sparse maps: 128-query workgroups (lists per two rows, see nabla_group_rows; attn_group_rows); dense maps: the 256-query form, balanced
     const int pair = (grp == 2 && d->nabla_pair_frames) ? nabla->Hb * nabla->Wb : 0;   // rows l and l + S of the rank's shard: same tile, next frame
     K5CHK(d->ws_nabla.ensure(nabla_ws_bytes(d, H, nb, rows / 64)));   // the logits and list regions by the rank's own query-block rows
     {
       Scope sc(d, s, "nabla_map");
       K5CHK(k5_launch_nabla_key_means_from_slots(kmeans, H, nb, slot_blocks, d->ws_nabla.p, s));
-      K5CHK(k5_launch_nabla_select_rect(nabla_means_fused(d, rows, H) ? nullptr : q, nullptr, D, 0, H, rows, r * slot_blocks, N, nabla->T, nabla->Hb, nabla->Wb, nabla->wT,
+      K5CHK(k5_launch_nabla_select_rect(fuse_means ? nullptr : q, nullptr, D, 0, H, rows, r * slot_blocks, N, nabla->T, nabla->Hb, nabla->Wb, nabla->wT,
                                         nabla->wH, nabla->wW, nabla->P, d->ws_nabla.p, s, r * slot_blocks, rows / 64, grp, pair));   // own key blocks lead the lists
     }
     if (d->profiling) {
@@ -1026,11 +1029,15 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
     k5_nabla_workspace_views(d->ws_nabla.p, H, nb, nullptr, nullptr, &list, &cnt, &cnt_local, rows / 64);
     K5CHK(d->ws_attn_bal.ensure(k5_attention_balance_bytes(H, rows)));
     K5CHK(nabla_density_hint(d, H, rows / 64, nb, s));
+    K5AttnSparseArgs at;
+    static_cast<K5AttnArgs&>(at) = common;
+    at.balance_ws = d->ws_attn_bal.as<float>();
+    at.list = list; at.cnt = cnt; at.list_stride = nb; at.group_rows = grp;
     if (grp < 4) {
       HIPCHK(hipStreamWaitEvent(s, d->ev_gathered, 0));
       Scope sc(d, s, "attn_self");
-      K5CHK(k5_launch_attention_bf16_sparse(q, kfull, vtfull, o, H, rows, N, D, D, ldv, D, 0.f, list, cnt, nb, rows_pad,
-                                            (long long)D * ldv, s, true, hflags, variant, kmax, nullptr, d->ws_attn_bal.as<float>(), grp, true, kcp, pair));
+      at.pair_stride = pair;
+      K5CHK(k5_launch_attention_bf16_sparse(at));
     } else if (d->sp_nabla_passes > 1 && P > 1) {
       // two passes over every list: the rank's own key blocks (they lead the lists; K' / V^T of them are in place) while the other
       // ranks' keys travel — state out —, then the rest once the gather has landed (resume, normalise); late fallback as in the dense
@@ -1039,19 +1046,18 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
       {
         const K5SparsePass p1{nullptr, d->ws_attn_state.as<float>(), 2, kmax ? 1 : 0};
         Scope sc(d, s, "attn_self");
-        K5CHK(k5_launch_attention_bf16_sparse(q, kfull, vtfull, o, H, rows, N, D, D, ldv, D, 0.f, list, cnt_local, nb, rows_pad,
-                                              (long long)D * ldv, s, true, hflags, variant, kmax, &p1, d->ws_attn_bal.as<float>(), 4, true, kcp));
+        at.cnt = cnt_local; at.pass = &p1;
+        K5CHK(k5_launch_attention_bf16_sparse(at));
       }
       HIPCHK(hipStreamWaitEvent(s, d->ev_gathered, 0));
       const K5SparsePass p2{cnt_local, d->ws_attn_state.as<float>(), 1, kmax ? 2 : 0};
       Scope sc(d, s, "attn_self");
-      K5CHK(k5_launch_attention_bf16_sparse(q, kfull, vtfull, o, H, rows, N, D, D, ldv, D, 0.f, list, cnt, nb, rows_pad,
-                                            (long long)D * ldv, s, true, hflags, variant, kmax, &p2, d->ws_attn_bal.as<float>(), 4, true, kcp));
+      at.cnt = cnt; at.pass = &p2;
+      K5CHK(k5_launch_attention_bf16_sparse(at));
     } else {
       HIPCHK(hipStreamWaitEvent(s, d->ev_gathered, 0));
       Scope sc(d, s, "attn_self");
-      K5CHK(k5_launch_attention_bf16_sparse(q, kfull, vtfull, o, H, rows, N, D, D, ldv, D, 0.f, list, cnt, nb, rows_pad,
-                                            (long long)D * ldv, s, true, hflags, variant, kmax, nullptr, d->ws_attn_bal.as<float>(), 4, true, kcp));
+      K5CHK(k5_launch_attention_bf16_sparse(at));
     }
   } else {
     // ... while the main stream attends the local query rows to the LOCAL key chunk (pass 1, leaves the fp32 state),
@@ -1067,19 +1073,21 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
     k1 = k1 > tpc ? tpc : k1;
     K5CHK(d->ws_attn_state.ensure(k5_attention_state_bytes(H, rows)));
     K5CHK(d->ws_attn_bal.ensure(k5_attention_balance_bytes(H, rows)));
+    K5AttnRangeArgs at;
+    static_cast<K5AttnArgs&>(at) = common;
+    at.balance_ws = d->ws_attn_bal.as<float>();
+    at.state = d->ws_attn_state.as<float>(); at.query_norm = qnp;
+    if (S > 1) { at.ldvt = cols; at.vt_chunk_keys = cols; at.vt_chunk_stride = (long long)D * cols; }   // P S chunks of rows_pad / S keys
     {
       Scope sc(d, s, "attn_self");
-      K5CHK(k5_launch_attention_bf16_range(q, kfull, vtfull, o, H, rows, N, D, D, S > 1 ? cols : ldv, D, 0.f, S > 1 ? cols : rows_pad,
-                                           S > 1 ? (long long)D * cols : (long long)D * ldv,
-                                           r * tpc_pad, k1, 0x7fffffff, 0, d->ws_attn_state.as<float>(), 2, s, d->ws_attn_bal.as<float>(), true, hflags, variant,
-                                           nullptr, kmax, kmax ? 1 : 0, qnp, kcp));
+      at.tile_off0 = r * tpc_pad; at.tile_cnt = k1; at.flags = 2; at.late_pass = kmax ? 1 : 0;
+      K5CHK(k5_launch_attention_bf16_range(at));
     }
     if (S == 1) {
       HIPCHK(hipStreamWaitEvent(s, d->ev_gathered, 0));
       Scope sc(d, s, "attn_self");
-      K5CHK(k5_launch_attention_bf16_range(q, kfull, vtfull, o, H, rows, N, D, D, ldv, D, 0.f, rows_pad, (long long)D * ldv,
-                                           0, total - k1, r * tpc_pad, k1, d->ws_attn_state.as<float>(), 1, s, d->ws_attn_bal.as<float>(),
-                                           true, hflags, variant, nullptr, kmax, kmax ? 2 : 0, qnp, kcp));
+      at.tile_off0 = 0; at.tile_cnt = total - k1; at.tile_skip_at = r * tpc_pad; at.tile_skip_n = k1; at.flags = 1; at.late_pass = kmax ? 2 : 0;
+      K5CHK(k5_launch_attention_bf16_range(at));
     } else {
       // one pass per slice, as soon as that slice of every peer has landed: slice sl of rank p = key tiles [p tpc_pad + sl tps, + tps)
       // (P - 1 segments: mine was pass 1; the last rank's slot may end early — it is the last segment, so the count is cut short).
@@ -1092,25 +1100,21 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
         if (r != P - 1) cnts[sl] -= tps - std::max(0, std::min(tps, last_rank_tiles - sl * tps));
         if (cnts[sl] > 0) last_pass = sl;                                     // slice 0 always has tiles
       }
+      const K5TileSegments seg{tps, tpc_pad, r};
+      at.segments = &seg;
       for (int sl = 0; sl < S; ++sl) {
         const int cnt = cnts[sl];
         HIPCHK(hipStreamWaitEvent(s, d->ev_slice[sl], 0));
         if (cnt <= 0) continue;
-        const K5TileSegments seg{tps, tpc_pad, r};
         const bool fin = sl == last_pass;
         Scope sc(d, s, "attn_self");
-        K5CHK(k5_launch_attention_bf16_range(q, kfull, vtfull, o, H, rows, N, D, D, cols, D, 0.f, cols, (long long)D * cols,
-                                             sl * tps, cnt, 0x7fffffff, 0, d->ws_attn_state.as<float>(), fin ? 1 : 3, s,
-                                             d->ws_attn_bal.as<float>(), true, hflags, variant, &seg, kmax, kmax ? (fin ? 2 : 1) : 0, qnp, kcp));
+        at.tile_off0 = sl * tps; at.tile_cnt = cnt; at.flags = fin ? 1 : 3; at.late_pass = kmax ? (fin ? 2 : 1) : 0;
+        K5CHK(k5_launch_attention_bf16_range(at));
       }
     }
   }
-  if (kmax) K5CHK(k5_launch_attn_pref_update(d->ws_attn_bal.as<float>(), H, rows, (nabla && d->nabla_grp_now < 4 && d->sp_nabla_passes == 1) ? d->nabla_grp_now : 4, (a.pref.as<int>() + (size_t)pref_slot * H), s));
-  {
-    Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(o, a.wo.p, a.bo.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s));
-  }
-  return K5_OK;
+  K5CHK(attn_pref_update(d, s, sf, H, rows, grp));
+  return attn_out_projection(d, s, a, o, rows, resid, gate);
 }
 
 // Ulysses-style sequence parallelism (north_star; "sp_mode" = 1): instead of gathering every rank's K / V^T, the ranks trade token rows for
@@ -1125,98 +1129,6 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
 // (rank-major = token order: slots are contiguous token ranges) of this rank's heads; V^T [D][rows_pad] is destination-major as the GEMM
 // writes it (block g = rows g Dp ..) -> vrecv [P][Dp][rows_pad] = the chunked V^T layout of the attention kernel; o [P rows_pad][Dp]
 // -> orecv [P][rows_pad][Dp] (block g: the outputs of rank g's heads for this rank's rows) -> unpacked to [rows][D].
-int run_self_attention_ulysses(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, int rows, int rows_pad, int N, void* o,
-                               const float* cosT, const float* sinT, void* resid, const float* gate, int pref_slot = 0) {
-  const int D = d->D, H = d->Hh, P = d->sp_world, r = d->sp_rank, Hp = H / P, Dp = D / P;
-  const bool by_data = d->attn_mode == K5_ATTN_AUTO;
-  K5CHK(d->ws_qk.ensure((size_t)rows * 2 * D * 2));
-  K5CHK(d->ws_u_send.ensure((size_t)P * rows_pad * 2 * Dp * 2)); K5CHK(d->ws_u_recv.ensure((size_t)P * rows_pad * 2 * Dp * 2));
-  K5CHK(d->ws_u_vsend.ensure((size_t)D * rows_pad * 2)); K5CHK(d->ws_u_vrecv.ensure((size_t)D * rows_pad * 2));
-  K5CHK(d->ws_u_o.ensure((size_t)P * rows_pad * Dp * 2)); K5CHK(d->ws_u_orecv.ensure((size_t)P * rows_pad * Dp * 2));
-  K5CHK(ensure_zeroed(d->ws_u_stats, (size_t)P * 2 * H * 4, s));
-  if (!d->ev_u_o) { HIPCHK(hipEventCreateWithFlags(&d->ev_u_o, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&d->ev_u_back, hipEventDisableTiming)); }
-  if (by_data) K5CHK(ensure_attn_flags(d, s));
-  float* ustats = d->ws_u_stats.as<float>();         // [P][2 H]: rank p's maxima of |q_h|^2 (H) and |k'_h|^2 (H) over ITS rows
-  if (by_data) HIPCHK(hipMemsetAsync(ustats + (size_t)r * 2 * H, 0, (size_t)2 * H * 4, s));   // the norm pass max-accumulates; only my heads' entries were consumed
-  bf16_t* qk = d->ws_qk.as<bf16_t>();
-  {
-    Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(h, a.wqk.p, a.bqk.as<float>(), qk, rows, 2 * D, D, D, D, 2 * D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-  }
-  {
-    Scope sc(d, s, "elementwise");
-    const int32_t hc[2] = {H, 2 * H};
-    K5CHK(k5_launch_rmsnorm_rope(qk, a.norm.as<float>(), cosT, sinT, rows, 2 * H, 2 * D, hc, s, K5_SOFTMAX_C, H, nullptr, 0,
-                                 by_data ? ustats + (size_t)r * 2 * H : nullptr, d->ws_attn_part.as<float>()));
-    K5CHK(k5_launch_ulysses_pack_qk(qk, d->ws_u_send.p, rows, rows_pad, D, P, s));
-  }
-  HIPCHK(hipEventRecord(d->ev_k, s));
-  hipStream_t cs = d->comm_stream;
-  HIPCHK(hipStreamWaitEvent(cs, d->ev_k, 0));
-  {
-    Scope sc(d, cs, "comm");
-    if (by_data) { K5CHK(d->comm.all_gather_inplace(ustats, (size_t)2 * H, 4, cs)); HIPCHK(hipEventRecord(d->ev_stats, cs)); }
-    K5CHK(d->comm.all_to_all(d->ws_u_send.p, d->ws_u_recv.p, (size_t)rows_pad * 2 * Dp * 2, cs));
-  }
-  {
-    Scope sc(d, s, "gemm");   // V^T of the rank's rows while q | k travel
-    K5CHK(k5_launch_gemm_bf16(a.wv.p, h, a.bv.as<float>(), d->ws_u_vsend.p, D, rows, D, D, D, rows_pad, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
-  }
-  HIPCHK(hipEventRecord(d->ev_v, s));
-  HIPCHK(hipStreamWaitEvent(cs, d->ev_v, 0));
-  {
-    Scope sc(d, cs, "comm");
-    K5CHK(d->comm.all_to_all(d->ws_u_vsend.p, d->ws_u_vrecv.p, (size_t)Dp * rows_pad * 2, cs));
-  }
-  HIPCHK(hipEventRecord(d->ev_gathered, cs));
-  const int* hflags = nullptr;
-  const float* kmax = nullptr;
-  if (by_data) {   // flags of MY heads from every rank's maxima (each rank held some rows of them)
-    HIPCHK(hipStreamWaitEvent(s, d->ev_stats, 0));
-    hflags = d->ws_attn_flags.as<int>();
-    float* kmax_w = d->row_offsets ? d->ws_attn_flags.as<float>() + H : nullptr;
-    kmax = kmax_w;
-    if (kmax_w) K5CHK(ensure_zeroed(a.pref, (size_t)2 * H * 4, s));
-    K5CHK(k5_launch_attn_flags(ustats + (size_t)r * Hp, ustats + H + (size_t)r * Hp, P, 2 * H, Hp, 0, d->ws_attn_flags.as<int>(),
-                               d->ws_attn_cnt.as<unsigned long long>(), s, kmax_w, kmax_w ? (a.pref.as<int>() + (size_t)pref_slot * H) + (size_t)r * Hp : nullptr, nullptr, nullptr, P, 2 * H,
-                               kmax_w && d->anchor));
-  }
-  HIPCHK(hipStreamWaitEvent(s, d->ev_gathered, 0));
-  const bf16_t* qall = d->ws_u_recv.as<bf16_t>();
-  K5CHK(d->ws_attn_bal.ensure(k5_attention_balance_bytes(Hp, N)));
-  K5KeyCentre kcen{nullptr, nullptr, nullptr};
-  if (kmax && d->anchor) {   // anchored offsets of the heads beyond the window: this rank holds all rows of its heads
-    K5CHK(d->ws_attn_anchor.ensure((size_t)Hp * N * 4));
-    Scope sc(d, s, "elementwise");
-    K5CHK(k5_launch_attn_row_anchor(qall, qall + Dp, Hp, N, N, 2 * Dp, 2 * Dp, 0, N, kmax, d->ws_attn_anchor.as<float>(), s));
-    kcen.row_anchor = d->ws_attn_anchor.as<float>();
-  }
-  {
-    Scope sc(d, s, "attn_self");
-    K5CHK(k5_launch_attention_bf16_range(qall, qall + Dp, d->ws_u_vrecv.p, d->ws_u_o.p, Hp, N, N, 2 * Dp, 2 * Dp, rows_pad, Dp, 0.f, rows_pad,
-                                         (long long)Dp * rows_pad, 0, -1, 0x7fffffff, 0, nullptr, 0, s, d->ws_attn_bal.as<float>(), true, hflags,
-                                         d->attn_mode, nullptr, kmax, 0, nullptr, kcen.row_anchor ? &kcen : nullptr));
-  }
-  if (kmax) K5CHK(k5_launch_attn_pref_update(d->ws_attn_bal.as<float>(), Hp, N, 4, (a.pref.as<int>() + (size_t)pref_slot * H) + (size_t)r * Hp, s));
-  HIPCHK(hipEventRecord(d->ev_u_o, s));
-  HIPCHK(hipStreamWaitEvent(cs, d->ev_u_o, 0));
-  {
-    Scope sc(d, cs, "comm");
-    K5CHK(d->comm.all_to_all(d->ws_u_o.p, d->ws_u_orecv.p, (size_t)rows_pad * Dp * 2, cs));
-  }
-  HIPCHK(hipEventRecord(d->ev_u_back, cs));
-  HIPCHK(hipStreamWaitEvent(s, d->ev_u_back, 0));
-  {
-    Scope sc(d, s, "elementwise");
-    K5CHK(k5_launch_ulysses_unpack_o(d->ws_u_orecv.p, o, rows, rows_pad, D, P, s));
-  }
-  {
-    Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(o, a.wo.p, a.bo.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s));
-  }
-  return K5_OK;
-}
-
 // Two-level sequence parallelism ("sp_mode" = 2): Ulysses needs heads % P == 0, which 28 heads at P = 8 (or 6) miss.  With G = gcd(heads, P)
 // head groups and S = P / G query splits, rank r attends head group g = r % G for the queries of split s = r / G (the G consecutive token
 // shards of ranks sG .. sG + G - 1) against all N keys in ONE pass — the one-GPU attention, no fp32 state between passes, as in Ulysses:
@@ -1228,33 +1140,50 @@ int run_self_attention_ulysses(k5_dit* d, hipStream_t s, const AttnW& a, const v
 //   4. attention: Hp heads, the split's rows x all N keys (anchored offsets sampled around each row's own block, as in Ulysses)
 //   5. o back inside the split, unpacked as in Ulysses with G head groups, gated out-projection.
 // Per rank and block (P = 8, G = 4, config 2) 107 MB arrive instead of the gather's 299 MB.  Callers: G = 1 -> gather,
-// G = P -> Ulysses (sp_schedule); the same routine does both ends correctly, they are simply not this schedule's business.
-int run_self_attention_2d(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, int rows, int rows_pad, int N, void* o,
-                          const float* cosT, const float* sinT, void* resid, const float* gate, int pref_slot = 0) {
+// G = P -> Ulysses (sp_schedule).
+// Both are run_self_attention_heads: the same projections, norm + RoPE, softmax-form step, one balanced attention launch, unpack and
+// out-projection; what differs is the layout below, the pack kernel and the collectives — Ulysses keeps its own wire pattern (one interleaved
+// q | k' all-to-all of rows_pad x 2 Dp blocks, then V^T, then o back), the two-level schedule its planned exchanges (stats, k', q, V^T, o).
+struct HeadsLayout {
+  int G;                        // head groups (Ulysses: P); also the group count of the unpack
+  int Hp, Dp, hg;               // heads / columns per group, and the group this rank attends
+  int q0, Ms;                   // the query rows this rank attends: [q0, q0 + Ms) of the N tokens
+  const bf16_t* q; const bf16_t* k; int ldq, ldk;   // where they and all N keys of the group land
+};
+int run_self_attention_heads(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, int rows, int rows_pad, int N, void* o,
+                             const float* cosT, const float* sinT, void* resid, const float* gate, bool two_level, int pref_slot = 0) {
   const int D = d->D, H = d->Hh, P = d->sp_world, r = d->sp_rank;
-  const int G = sp_gcd(H, P), Hp = H / G, Dp = D / G, g = r % G, sp = r / G;
-  const int q0 = sp * G * rows_pad, Ms = std::min(N, q0 + G * rows_pad) - q0;   // the split's token rows [q0, q0 + Ms)
-  if (Ms <= 0) { k5_set_error("internal: two-level split without rows"); return K5_ERR_STATE; }
-  if (d->sp_plan_key[0] != P || d->sp_plan_key[1] != rows_pad) {
-    for (int w = SP_K; w <= SP_O; ++w) { d->sp_plan[w].resize((size_t)P * P); sp_plan_2d(H, P, rows_pad, D, w, d->sp_plan[w].data()); }
-    d->sp_plan_key[0] = P; d->sp_plan_key[1] = rows_pad;
+  HeadsLayout L;
+  L.G = two_level ? sp_gcd(H, P) : P;
+  L.Hp = H / L.G; L.Dp = D / L.G; L.hg = r % L.G;
+  const int G = L.G, Hp = L.Hp, Dp = L.Dp;
+  L.q0 = two_level ? (r / G) * G * rows_pad : 0;   // the split's token rows
+  L.Ms = std::min(N, L.q0 + G * rows_pad) - L.q0;
+  const size_t blk = (size_t)rows_pad * Dp * 2;   // bytes of one rows_pad x Dp block
+  if (two_level) {
+    if (L.Ms <= 0) { k5_set_error("internal: two-level split without rows"); return K5_ERR_STATE; }
+    if (d->sp_plan_key[0] != P || d->sp_plan_key[1] != rows_pad) {
+      for (int w = SP_K; w <= SP_O; ++w) { d->sp_plan[w].resize((size_t)P * P); sp_plan_2d(H, P, rows_pad, D, w, d->sp_plan[w].data()); }
+      d->sp_plan_key[0] = P; d->sp_plan_key[1] = rows_pad;
+    }
   }
-  const size_t blk = (size_t)rows_pad * Dp * 2;   // bytes of one exchange block
   const bool by_data = d->attn_mode == K5_ATTN_AUTO;
   K5CHK(d->ws_qk.ensure((size_t)rows * 2 * D * 2));
-  K5CHK(d->ws_u_send.ensure(2 * G * blk));                       // q plane [G][rows_pad][Dp] | k' plane [G][rows_pad][Dp]
-  K5CHK(d->ws_u_recv.ensure(P * blk));                           // k' of all N rows, my heads
+  K5CHK(d->ws_u_send.ensure(2 * G * blk));       // Ulysses: [P][rows_pad][2 Dp]; two-level: q plane [G][rows_pad][Dp] | k' plane [G][rows_pad][Dp]
+  K5CHK(d->ws_u_recv.ensure((two_level ? 1 : 2) * P * blk));   // Ulysses: q | k' of all N rows, my heads; two-level: k' only
   K5CHK(d->ws_u_vsend.ensure((size_t)D * rows_pad * 2)); K5CHK(d->ws_u_vrecv.ensure(P * blk));
-  K5CHK(d->ws_u_qrecv.ensure(G * blk));
+  if (two_level) K5CHK(d->ws_u_qrecv.ensure(G * blk));
   K5CHK(d->ws_u_o.ensure(G * blk)); K5CHK(d->ws_u_orecv.ensure(G * blk));
   K5CHK(ensure_zeroed(d->ws_u_stats, (size_t)P * 2 * H * 4, s));
   if (!d->ev_u_o) { HIPCHK(hipEventCreateWithFlags(&d->ev_u_o, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&d->ev_u_back, hipEventDisableTiming)); }
   if (by_data) K5CHK(ensure_attn_flags(d, s));
-  float* ustats = d->ws_u_stats.as<float>();         // [P][2 H], as in Ulysses
-  if (by_data) HIPCHK(hipMemsetAsync(ustats + (size_t)r * 2 * H, 0, (size_t)2 * H * 4, s));
+  float* ustats = d->ws_u_stats.as<float>();         // [P][2 H]: rank p's maxima of |q_h|^2 (H) and |k'_h|^2 (H) over ITS rows
+  if (by_data) HIPCHK(hipMemsetAsync(ustats + (size_t)r * 2 * H, 0, (size_t)2 * H * 4, s));   // the norm pass max-accumulates; only my heads' entries were consumed
   bf16_t* qk = d->ws_qk.as<bf16_t>();
   bf16_t* qsend = d->ws_u_send.as<bf16_t>();
-  bf16_t* ksend = qsend + (size_t)G * rows_pad * Dp;
+  bf16_t* ksend = qsend + (size_t)G * rows_pad * Dp;   // two-level
+  if (two_level) { L.q = d->ws_u_qrecv.as<bf16_t>(); L.k = d->ws_u_recv.as<bf16_t>(); L.ldq = L.ldk = Dp; }
+  else { L.q = d->ws_u_recv.as<bf16_t>(); L.k = L.q + Dp; L.ldq = L.ldk = 2 * Dp; }
   {
     Scope sc(d, s, "gemm");
     K5CHK(k5_launch_gemm_bf16(h, a.wqk.p, a.bqk.as<float>(), qk, rows, 2 * D, D, D, D, 2 * D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
@@ -1264,63 +1193,61 @@ int run_self_attention_2d(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
     const int32_t hc[2] = {H, 2 * H};
     K5CHK(k5_launch_rmsnorm_rope(qk, a.norm.as<float>(), cosT, sinT, rows, 2 * H, 2 * D, hc, s, K5_SOFTMAX_C, H, nullptr, 0,
                                  by_data ? ustats + (size_t)r * 2 * H : nullptr, d->ws_attn_part.as<float>()));
-    K5CHK(k5_launch_sp2d_pack_qk(qk, qsend, ksend, rows, rows_pad, D, G, s));
+    if (two_level) K5CHK(k5_launch_sp2d_pack_qk(qk, qsend, ksend, rows, rows_pad, D, G, s));
+    else K5CHK(k5_launch_ulysses_pack_qk(qk, d->ws_u_send.p, rows, rows_pad, D, P, s));
   }
   HIPCHK(hipEventRecord(d->ev_k, s));
   hipStream_t cs = d->comm_stream;
   HIPCHK(hipStreamWaitEvent(cs, d->ev_k, 0));
   {
-    Scope sc(d, cs, "comm");   // the same collectives in the same order on every rank: stats, k', q, V^T, o
+    Scope sc(d, cs, "comm");   // the same collectives in the same order on every rank
     if (by_data) { K5CHK(d->comm.all_gather_inplace(ustats, (size_t)2 * H, 4, cs)); HIPCHK(hipEventRecord(d->ev_stats, cs)); }
-    K5CHK(d->comm.exchange(ksend, d->ws_u_recv.p, d->sp_plan[SP_K].data(), cs));
-    K5CHK(d->comm.exchange(qsend, d->ws_u_qrecv.p, d->sp_plan[SP_Q].data(), cs));
+    if (two_level) {
+      K5CHK(d->comm.exchange(ksend, d->ws_u_recv.p, d->sp_plan[SP_K].data(), cs));
+      K5CHK(d->comm.exchange(qsend, d->ws_u_qrecv.p, d->sp_plan[SP_Q].data(), cs));
+    } else K5CHK(d->comm.all_to_all(d->ws_u_send.p, d->ws_u_recv.p, 2 * blk, cs));
   }
   {
-    Scope sc(d, s, "gemm");   // V^T of the rank's rows while k' / q travel
+    Scope sc(d, s, "gemm");   // V^T of the rank's rows while q | k' travel
     K5CHK(k5_launch_gemm_bf16(a.wv.p, h, a.bv.as<float>(), d->ws_u_vsend.p, D, rows, D, D, D, rows_pad, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
   }
   HIPCHK(hipEventRecord(d->ev_v, s));
   HIPCHK(hipStreamWaitEvent(cs, d->ev_v, 0));
   {
     Scope sc(d, cs, "comm");
-    K5CHK(d->comm.exchange(d->ws_u_vsend.p, d->ws_u_vrecv.p, d->sp_plan[SP_VT].data(), cs));
+    if (two_level) K5CHK(d->comm.exchange(d->ws_u_vsend.p, d->ws_u_vrecv.p, d->sp_plan[SP_VT].data(), cs));
+    else K5CHK(d->comm.all_to_all(d->ws_u_vsend.p, d->ws_u_vrecv.p, blk, cs));
   }
   HIPCHK(hipEventRecord(d->ev_gathered, cs));
-  const int* hflags = nullptr;
-  const float* kmax = nullptr;
-  int* pref = nullptr;
-  if (by_data) {   // flags of MY head group from every rank's maxima (all N rows)
-    HIPCHK(hipStreamWaitEvent(s, d->ev_stats, 0));
-    hflags = d->ws_attn_flags.as<int>();
-    float* kmax_w = d->row_offsets ? d->ws_attn_flags.as<float>() + H : nullptr;
-    kmax = kmax_w;
-    if (kmax_w) { K5CHK(ensure_zeroed(a.pref, (size_t)2 * H * 4, s)); pref = a.pref.as<int>() + (size_t)pref_slot * H + (size_t)g * Hp; }
-    K5CHK(k5_launch_attn_flags(ustats + (size_t)g * Hp, ustats + H + (size_t)g * Hp, P, 2 * H, Hp, 0, d->ws_attn_flags.as<int>(),
-                               d->ws_attn_cnt.as<unsigned long long>(), s, kmax_w, pref, nullptr, nullptr, P, 2 * H, kmax_w && d->anchor));
-  }
-  HIPCHK(hipStreamWaitEvent(s, d->ev_gathered, 0));
-  const bf16_t* qs = d->ws_u_qrecv.as<bf16_t>();
-  const bf16_t* kall = d->ws_u_recv.as<bf16_t>();
-  K5CHK(d->ws_attn_bal.ensure(k5_attention_balance_bytes(Hp, Ms)));
-  K5KeyCentre kcen{nullptr, nullptr, nullptr};
-  if (kmax && d->anchor) {   // anchored offsets: each query row's own 64-token block sits at key index q0 + row
-    K5CHK(d->ws_attn_anchor.ensure((size_t)Hp * Ms * 4));
-    Scope sc(d, s, "elementwise");
-    K5CHK(k5_launch_attn_row_anchor(qs, kall, Hp, Ms, N, Dp, Dp, q0, N, kmax, d->ws_attn_anchor.as<float>(), s));
-    kcen.row_anchor = d->ws_attn_anchor.as<float>();
+  K5CHK(d->ws_attn_bal.ensure(k5_attention_balance_bytes(Hp, L.Ms)));
+  SoftmaxForm sf;
+  {
+    // flags of MY head group from every rank's maxima (each rank held some rows of them; the ranks of a head group take the same form);
+    // anchored offsets: this rank holds all keys of its heads, each query row's own 64-token block sits at key index q0 + row
+    SoftmaxFormIn in;
+    in.qstat = ustats + (size_t)L.hg * Hp; in.kstat = ustats + H + (size_t)L.hg * Hp; in.nk = P; in.kstride = 2 * H; in.nq = P; in.qstride = 2 * H;
+    in.heads = Hp; in.head0 = L.hg * Hp; in.stats_ready = d->ev_stats; in.data_ready = d->ev_gathered;
+    in.anchor = d->anchor != 0; in.anchor_fam = "elementwise";
+    in.aq = L.q; in.ak = L.k; in.aq_rows = L.Ms; in.ak_rows = N; in.ldq = L.ldq; in.ldk = L.ldk; in.key0 = L.q0; in.kv_total = N;
+    K5CHK(softmax_form(d, s, a, pref_slot, by_data, in, sf));
   }
   {
     Scope sc(d, s, "attn_self");
-    K5CHK(k5_launch_attention_bf16_range(qs, kall, d->ws_u_vrecv.p, d->ws_u_o.p, Hp, Ms, N, Dp, Dp, rows_pad, Dp, 0.f, rows_pad,
-                                         (long long)Dp * rows_pad, 0, -1, 0x7fffffff, 0, nullptr, 0, s, d->ws_attn_bal.as<float>(), true, hflags,
-                                         d->attn_mode, nullptr, kmax, 0, nullptr, kcen.row_anchor ? &kcen : nullptr));
+    K5AttnRangeArgs at;
+    at.Q = L.q; at.K = L.k; at.Vt = d->ws_u_vrecv.p; at.O = d->ws_u_o.p;
+    at.H = Hp; at.q_len = L.Ms; at.kv_len = N; at.ldq = L.ldq; at.ldk = L.ldk; at.ldvt = rows_pad; at.ldo = Dp;
+    at.vt_chunk_keys = rows_pad; at.vt_chunk_stride = (long long)Dp * rows_pad;
+    at.stream = s; at.balance_ws = d->ws_attn_bal.as<float>();
+    at.k_prescaled = true; at.head_flags = sf.hflags; at.variant = d->attn_mode; at.row_offset_kmax = sf.kmax; at.key_centre = sf.key_centre();
+    K5CHK(k5_launch_attention_bf16_range(at));
   }
-  if (kmax) K5CHK(k5_launch_attn_pref_update(d->ws_attn_bal.as<float>(), Hp, Ms, 4, pref, s));
+  K5CHK(attn_pref_update(d, s, sf, Hp, L.Ms, 4));
   HIPCHK(hipEventRecord(d->ev_u_o, s));
   HIPCHK(hipStreamWaitEvent(cs, d->ev_u_o, 0));
   {
     Scope sc(d, cs, "comm");
-    K5CHK(d->comm.exchange(d->ws_u_o.p, d->ws_u_orecv.p, d->sp_plan[SP_O].data(), cs));
+    if (two_level) K5CHK(d->comm.exchange(d->ws_u_o.p, d->ws_u_orecv.p, d->sp_plan[SP_O].data(), cs));
+    else K5CHK(d->comm.all_to_all(d->ws_u_o.p, d->ws_u_orecv.p, blk, cs));
   }
   HIPCHK(hipEventRecord(d->ev_u_back, cs));
   HIPCHK(hipStreamWaitEvent(s, d->ev_u_back, 0));
@@ -1328,11 +1255,7 @@ int run_self_attention_2d(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
     Scope sc(d, s, "elementwise");
     K5CHK(k5_launch_ulysses_unpack_o(d->ws_u_orecv.p, o, rows, rows_pad, D, G, s));
   }
-  {
-    Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(o, a.wo.p, a.bo.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s));
-  }
-  return K5_OK;
+  return attn_out_projection(d, s, a, o, rows, resid, gate);
 }
 
 // keys and V^T of every visual block's cross-attention from the text stream (k5_dit::cross_kv_batched): ws_ck_all [L][blocks * D] (normalised
@@ -1377,17 +1300,14 @@ int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h,
   {
     Scope sc(d, s, "attn_cross");
     const K5QueryNorm qn{a.norm.as<float>(), nullptr, nullptr, nullptr};
-    if (fuse_qnorm)
-      K5CHK(k5_launch_attention_bf16_range(q, ck, cvt, o, H, rows, L, D, ldck, ldvt, D, a.score_bound, 0, 0, 0, -1, 0x7fffffff, 0, nullptr, 0, s,
-                                           nullptr, false, nullptr, K5_ATTN_AUTO, nullptr, nullptr, 0, &qn));
-    else
-      K5CHK(k5_launch_attention_bf16_bounded(q, ck, cvt, o, H, rows, L, D, ldck, ldvt, D, a.score_bound, s));
+    K5AttnRangeArgs at;
+    at.Q = q; at.K = ck; at.Vt = cvt; at.O = o;
+    at.H = H; at.q_len = rows; at.kv_len = L; at.ldq = D; at.ldk = ldck; at.ldvt = ldvt; at.ldo = D;
+    at.score_bound = a.score_bound; at.stream = s;
+    at.query_norm = fuse_qnorm ? &qn : nullptr;
+    K5CHK(k5_launch_attention_bf16_range(at));
   }
-  {
-    Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(o, a.wo.p, a.bo.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s));
-  }
-  return K5_OK;
+  return attn_out_projection(d, s, a, o, rows, resid, gate);
 }
 
 int run_ff(k5_dit* d, hipStream_t s, const BlockW& b, const void* h, int rows, void* ff, void* resid, const float* gate, bool h8_ready = false) {
@@ -1584,7 +1504,7 @@ int sp_autotune_run(k5_dit* d, hipStream_t s, int N, int L, const NablaArgs* nab
     int trial_rc = K5_OK;   // a candidate that REFUSES its arguments does so on every rank alike (argument checks only): it is disqualified, not fatal
     for (int it = 0; it < 3 && trial_rc == K5_OK; ++it) {
       if (it == 1) HIPCHK(hipEventRecord(e0, s));
-      trial_rc = uly ? run_self_attention_ulysses(d, s, a, d->ws_h.p, n, n_pad, N, d->ws_o.p, cosT, sinT, d->ws_vis.p, d->ws_mod.as<float>())
+      trial_rc = uly ? run_self_attention_heads(d, s, a, d->ws_h.p, n, n_pad, N, d->ws_o.p, cosT, sinT, d->ws_vis.p, d->ws_mod.as<float>(), false)
                      : run_self_attention_sp(d, s, a, d->ws_h.p, n, n_pad, N, d->ws_o.p, cosT, sinT, d->ws_vis.p, d->ws_mod.as<float>(), nabla);
     }
     if (trial_rc != K5_OK) {
@@ -1828,10 +1748,8 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     const bool h8_sa = d->fp8_fuse_ln && sched == 0 && (sp ? sa_sp_fp8_in(d, b.self_attn, n, n_pad, nabla) : sa_fp8_in(d, b.self_attn, n));
     K5CHK(ln_mod(d, s, d->ws_vis.p, m, d->ws_h.p, n, h8_sa));
     if (d->profiling) ++d->prof_self_blocks;   // bench.py: FLOPs of the roofline kernel = per-block FLOPs x the blocks that RAN
-    if (ulysses) {
-      K5CHK(run_self_attention_ulysses(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, text_slot > 0 ? 1 : 0));
-    } else if (two_level) {
-      K5CHK(run_self_attention_2d(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, text_slot > 0 ? 1 : 0));
+    if (ulysses || two_level) {
+      K5CHK(run_self_attention_heads(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, two_level, text_slot > 0 ? 1 : 0));
     } else if (sp) {
       K5CHK(run_self_attention_sp(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, nabla ? &na : nullptr, text_slot > 0 ? 1 : 0, h8_sa));
     } else {
@@ -2610,8 +2528,8 @@ extern "C" int k5_dit_cfg_pair_init_ipc(k5_dit* d, const char* shm_name, int bra
 //                     rank's own key blocks while the other ranks' keys travel, the rest after the gather (costs 12 % of the attention
 //                     in compute, emulated P = 4; pays when the exposed part of the gather is longer than that — a property of the node)
 //   "sp_mode"         0 (default): every rank gathers all K / V^T (any rank count, dense and NABLA); 1: Ulysses — two all-to-alls trade token rows
-//                     for heads and back (run_self_attention_ulysses; needs heads % ranks == 0 and dense attention, else the gather is used);
-//                     2: two-level — G = gcd(heads, ranks) head groups x ranks / G query splits (run_self_attention_2d; dense attention; G = ranks
+//                     for heads and back (run_self_attention_heads; needs heads % ranks == 0 and dense attention, else the gather is used);
+//                     2: two-level — G = gcd(heads, ranks) head groups x ranks / G query splits (the same routine, two_level; dense attention; G = ranks
 //                     runs Ulysses, G = 1 the gather).  K5_SP_MODE=0/1/2 sets it at communicator init; this call still wins.
 //   "sp_mode_used"    (read-only) what the last sharded forward ran: 0 gather, 1 Ulysses, 2 two-level (-1: none yet)
 //   "sp_autotune"     0 (default since round 5) / 1: the first sharded forward of a handle with more than one rank times one block's self-attention section under

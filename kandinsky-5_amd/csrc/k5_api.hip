@@ -12,6 +12,17 @@ static int ret(int st, const char* what) {
   return st;
 }
 
+// the tensors and their geometry, which every attention entry point passes on as it got them
+template <class A>
+static A attn_args(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len, int kv_len, int ldq, int ldk, int ldvt, int ldo,
+                   void* stream) {
+  A a;
+  a.Q = Q; a.K = K; a.Vt = Vt; a.O = O;
+  a.H = H; a.q_len = q_len; a.kv_len = kv_len; a.ldq = ldq; a.ldk = ldk; a.ldvt = ldvt; a.ldo = ldo;
+  a.stream = (hipStream_t)stream;
+  return a;
+}
+
 extern "C" {
 
 int k5_gemm_bf16(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int lda, int ldw,
@@ -44,8 +55,8 @@ int k5_gemm_bf16_f32out(const void* A, const void* W, float* C, int M, int N, in
 
 int k5_attention_bf16(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len, int kv_len, int ldq,
                       int ldk, int ldvt, int ldo, void* stream) {
-  return ret(k5_launch_attention_bf16_bounded(Q, K, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, 0.f, (hipStream_t)stream),
-             "k5_attention_bf16");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, K, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16");
 }
 
 int64_t k5_attention_state_size(int H, int q_len) { return (int64_t)k5_attention_state_bytes(H, q_len); }
@@ -53,9 +64,11 @@ int64_t k5_attention_state_size(int H, int q_len) { return (int64_t)k5_attention
 int k5_attention_bf16_range(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len, int kv_len, int ldq,
                             int ldk, int ldvt, int ldo, float score_bound, int tile_off0, int tile_cnt, int tile_skip_at,
                             int tile_skip_n, void* state, int flags, void* stream) {
-  return ret(k5_launch_attention_bf16_range(Q, K, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, score_bound, 0, 0, tile_off0,
-                                            tile_cnt, tile_skip_at, tile_skip_n, (float*)state, flags, (hipStream_t)stream),
-             "k5_attention_bf16_range");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, K, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  a.score_bound = score_bound;
+  a.tile_off0 = tile_off0; a.tile_cnt = tile_cnt; a.tile_skip_at = tile_skip_at; a.tile_skip_n = tile_skip_n;
+  a.state = (float*)state; a.flags = flags;
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16_range");
 }
 
 int k5_gemm_fp8(const void* A8, const void* W8, const float* w_scale, void* C, int M, int N, int K, int lda, int ldw, int ldc, int epi,
@@ -69,15 +82,16 @@ int k5_quant_rows_fp8(const void* x, void* out, float* scale, int rows, int K, i
 
 int k5_attention_bf16_prescaled(const void* Q, const void* Kc, const void* Vt, void* O, int H, int q_len, int kv_len, int ldq,
                                 int ldk, int ldvt, int ldo, float score_bound, void* stream) {
-  return ret(k5_launch_attention_bf16_range(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, score_bound, 0, 0, 0, -1, 0x7fffffff, 0,
-                                            nullptr, 0, (hipStream_t)stream, nullptr, true), "k5_attention_bf16_prescaled");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  a.score_bound = score_bound; a.k_prescaled = true;
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16_prescaled");
 }
 
 int k5_attention_bf16_prescaled_auto(const void* Q, const void* Kc, const void* Vt, void* O, int H, int q_len, int kv_len, int ldq,
                                      int ldk, int ldvt, int ldo, const int* head_flags, int variant, void* workspace, void* stream) {
-  return ret(k5_launch_attention_bf16_range(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, 0.f, 0, 0, 0, -1, 0x7fffffff, 0,
-                                            nullptr, 0, (hipStream_t)stream, (float*)workspace, true, head_flags, variant),
-             "k5_attention_bf16_prescaled_auto");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  a.balance_ws = (float*)workspace; a.k_prescaled = true; a.head_flags = head_flags; a.variant = variant;
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16_prescaled_auto");
 }
 
 int k5_attention_flags(float* qstat, float* kstat, int nk, int kstride, int H, int force_online, int* flags, void* stream) {
@@ -102,9 +116,9 @@ int k5_attention_bf16_prescaled_rows_centred(const void* Q, const void* Kc, cons
                                              void* workspace, void* stream) {
   if (!head_flags || !kmax || !centre || !krad) return ret(K5_ERR_ARG, "k5_attention_bf16_prescaled_rows_centred");
   const K5KeyCentre kc{centre, krad};
-  return ret(k5_launch_attention_bf16_range(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, 0.f, 0, 0, 0, -1, 0x7fffffff, 0,
-                                            nullptr, 0, (hipStream_t)stream, (float*)workspace, true, head_flags, K5_ATTN_AUTO, nullptr, kmax, 0, nullptr, &kc),
-             "k5_attention_bf16_prescaled_rows_centred");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  a.balance_ws = (float*)workspace; a.k_prescaled = true; a.head_flags = head_flags; a.row_offset_kmax = kmax; a.key_centre = &kc;
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16_prescaled_rows_centred");
 }
 // anchored offsets for the heads beyond the window (include/k5.h): flags with the marker, the offsets, the attention that reads them
 int k5_attention_flags_rows_anchored(float* qstat, float* kstat, int nk, int kstride, int H, int force_online, int* flags, float* kmax, float* rstat,
@@ -122,16 +136,16 @@ int k5_attention_bf16_prescaled_rows_anchored(const void* Q, const void* Kc, con
                                               const float* anchor, void* workspace, void* stream) {
   if (!head_flags || !kmax || !centre || !krad || !anchor) return ret(K5_ERR_ARG, "k5_attention_bf16_prescaled_rows_anchored");
   const K5KeyCentre kc{centre, krad, anchor};
-  return ret(k5_launch_attention_bf16_range(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, 0.f, 0, 0, 0, -1, 0x7fffffff, 0,
-                                            nullptr, 0, (hipStream_t)stream, (float*)workspace, true, head_flags, K5_ATTN_AUTO, nullptr, kmax, 0, nullptr, &kc),
-             "k5_attention_bf16_prescaled_rows_anchored");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  a.balance_ws = (float*)workspace; a.k_prescaled = true; a.head_flags = head_flags; a.row_offset_kmax = kmax; a.key_centre = &kc;
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16_prescaled_rows_anchored");
 }
 int k5_attention_bf16_prescaled_rows(const void* Q, const void* Kc, const void* Vt, void* O, int H, int q_len, int kv_len, int ldq,
                                      int ldk, int ldvt, int ldo, int* head_flags, const float* kmax, void* workspace, void* stream) {
   if (!head_flags || !kmax) return ret(K5_ERR_ARG, "k5_attention_bf16_prescaled_rows");
-  return ret(k5_launch_attention_bf16_range(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, 0.f, 0, 0, 0, -1, 0x7fffffff, 0,
-                                            nullptr, 0, (hipStream_t)stream, (float*)workspace, true, head_flags, K5_ATTN_AUTO, nullptr, kmax),
-             "k5_attention_bf16_prescaled_rows");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  a.balance_ws = (float*)workspace; a.k_prescaled = true; a.head_flags = head_flags; a.row_offset_kmax = kmax;
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16_prescaled_rows");
 }
 
 // one pass of a multi-pass schedule with per-row offsets (what the sequence-parallel engine runs): key tiles tile_off0 .. +tile_cnt,
@@ -140,9 +154,10 @@ int k5_attention_bf16_prescaled_rows_pass(const void* Q, const void* Kc, const v
                                           int ldk, int ldvt, int ldo, int* head_flags, const float* kmax, int tile_off0, int tile_cnt,
                                           float* state, int flags, int late_pass, void* workspace, void* stream) {
   if (!head_flags || !kmax) return ret(K5_ERR_ARG, "k5_attention_bf16_prescaled_rows_pass");
-  return ret(k5_launch_attention_bf16_range(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, 0.f, 0, 0, tile_off0, tile_cnt, 0x7fffffff, 0,
-                                            state, flags, (hipStream_t)stream, (float*)workspace, true, head_flags, K5_ATTN_AUTO, nullptr, kmax,
-                                            late_pass), "k5_attention_bf16_prescaled_rows_pass");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  a.balance_ws = (float*)workspace; a.k_prescaled = true; a.head_flags = head_flags; a.row_offset_kmax = kmax;
+  a.tile_off0 = tile_off0; a.tile_cnt = tile_cnt; a.state = state; a.flags = flags; a.late_pass = late_pass;
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16_prescaled_rows_pass");
 }
 
 // the same pass with norm_qk + apply_rotary of the QUERIES fused into the kernel's Q load (K5QueryNorm): Q holds the raw projection.
@@ -154,10 +169,11 @@ int k5_attention_bf16_prescaled_qnorm_pass(const void* Q, const void* Kc, const 
                                            int late_pass, void* workspace, void* stream) {
   if (!q_norm_w || !q_cos || !q_sin || (!head_flags != !kmax)) return ret(K5_ERR_ARG, "k5_attention_bf16_prescaled_qnorm_pass");
   const K5QueryNorm qn{q_norm_w, q_cos, q_sin, nullptr};
-  return ret(k5_launch_attention_bf16_range(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, 0.f, 0, 0, tile_off0, tile_cnt, 0x7fffffff, 0,
-                                            state, flags, (hipStream_t)stream, (float*)workspace, true, head_flags,
-                                            head_flags ? K5_ATTN_AUTO : K5_ATTN_ONLINE, nullptr, kmax, late_pass, &qn),
-             "k5_attention_bf16_prescaled_qnorm_pass");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, Kc, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  a.balance_ws = (float*)workspace; a.k_prescaled = true; a.head_flags = head_flags; a.row_offset_kmax = kmax;
+  a.tile_off0 = tile_off0; a.tile_cnt = tile_cnt; a.state = state; a.flags = flags; a.late_pass = late_pass;
+  a.variant = head_flags ? K5_ATTN_AUTO : K5_ATTN_ONLINE; a.query_norm = &qn;
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16_prescaled_qnorm_pass");
 }
 
 int64_t k5_attention_balance_size(int H, int q_len) { return (int64_t)k5_attention_balance_bytes(H, q_len); }
@@ -165,8 +181,9 @@ int64_t k5_attention_balance_size(int H, int q_len) { return (int64_t)k5_attenti
 int k5_attention_bf16_balanced(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len, int kv_len, int ldq,
                                int ldk, int ldvt, int ldo, float score_bound, void* workspace, void* stream) {
   if (!workspace) return ret(K5_ERR_ARG, "k5_attention_bf16_balanced");
-  return ret(k5_launch_attention_bf16_range(Q, K, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, score_bound, 0, 0, 0, -1, 0x7fffffff, 0,
-                                            nullptr, 0, (hipStream_t)stream, (float*)workspace), "k5_attention_bf16_balanced");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, K, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  a.score_bound = score_bound; a.balance_ws = (float*)workspace;
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16_balanced");
 }
 
 int64_t k5_nabla_workspace_size(int H, int num_blocks) { return (int64_t)k5_nabla_workspace_bytes(H, num_blocks); }
@@ -182,8 +199,9 @@ int k5_attention_nabla_bf16(const void* Q, const void* K, const void* Vt, void* 
   if (!workspace || N <= 0 || (N % 64)) return ret(K5_ERR_ARG, "k5_attention_nabla_bf16");
   const int *list, *cnt;
   k5_nabla_workspace_views(const_cast<void*>(workspace), H, N / 64, nullptr, nullptr, &list, &cnt);
-  return ret(k5_launch_attention_bf16_sparse(Q, K, Vt, O, H, N, N, ldq, ldk, ldvt, ldo, score_bound, list, cnt, N / 64, 0, 0,
-                                             (hipStream_t)stream), "k5_attention_nabla_bf16");
+  K5AttnSparseArgs a = attn_args<K5AttnSparseArgs>(Q, K, Vt, O, H, N, N, ldq, ldk, ldvt, ldo, stream);
+  a.score_bound = score_bound; a.list = list; a.cnt = cnt; a.list_stride = N / 64;
+  return ret(k5_launch_attention_bf16_sparse(a), "k5_attention_nabla_bf16");
 }
 
 int k5_nabla_mask_u8(const void* workspace, int H, int num_blocks, void* out_u8, void* stream) {
@@ -202,9 +220,10 @@ int k5_attention_nabla_rect_bf16(const void* Q, const void* K, const void* Vt, v
   if (!workspace || N <= 0 || (N % 64) || Nq <= 0 || (Nq % 64)) return ret(K5_ERR_ARG, "k5_attention_nabla_rect_bf16");
   const int *list, *cnt;
   k5_nabla_workspace_views(const_cast<void*>(workspace), H, N / 64, nullptr, nullptr, &list, &cnt, nullptr, Nq / 64);   // as k5_nabla_select_rect_bf16 laid it out
-  return ret(k5_launch_attention_bf16_sparse(Q, K, Vt, O, H, Nq, N, ldq, ldk, ldvt, ldo, score_bound, list, cnt, N / 64,
-                                             vt_chunk_keys, (long long)vt_chunk_stride, (hipStream_t)stream),
-             "k5_attention_nabla_rect_bf16");
+  K5AttnSparseArgs a = attn_args<K5AttnSparseArgs>(Q, K, Vt, O, H, Nq, N, ldq, ldk, ldvt, ldo, stream);
+  a.score_bound = score_bound; a.list = list; a.cnt = cnt; a.list_stride = N / 64;
+  a.vt_chunk_keys = vt_chunk_keys; a.vt_chunk_stride = (long long)vt_chunk_stride;
+  return ret(k5_launch_attention_bf16_sparse(a), "k5_attention_nabla_rect_bf16");
 }
 
 // what the sequence-parallel engine runs: the map with the rank's own key blocks leading every list, and the list-driven attention on
@@ -225,10 +244,12 @@ int k5_attention_nabla_rect_prescaled_pass(const void* Q, const void* Kc, const 
   if (Nq <= 0 || (Nq % 64)) return ret(K5_ERR_ARG, "k5_attention_nabla_rect_prescaled_pass");
   k5_nabla_workspace_views(const_cast<void*>(workspace), H, N / 64, nullptr, nullptr, &list, &cnt, &cnt_local, Nq / 64);
   const K5SparsePass p1{nullptr, state, 2, 1}, p2{cnt_local, state, 1, 2};
-  return ret(k5_launch_attention_bf16_sparse(Q, Kc, Vt, O, H, Nq, N, ldq, ldk, ldvt, ldo, 0.f, list, pass == 1 ? cnt_local : cnt, N / 64,
-                                             vt_chunk_keys, (long long)vt_chunk_stride, (hipStream_t)stream, true, head_flags, K5_ATTN_AUTO,
-                                             kmax, pass == 0 ? nullptr : (pass == 1 ? &p1 : &p2)),
-             "k5_attention_nabla_rect_prescaled_pass");
+  K5AttnSparseArgs a = attn_args<K5AttnSparseArgs>(Q, Kc, Vt, O, H, Nq, N, ldq, ldk, ldvt, ldo, stream);
+  a.list = list; a.cnt = pass == 1 ? cnt_local : cnt; a.list_stride = N / 64;
+  a.vt_chunk_keys = vt_chunk_keys; a.vt_chunk_stride = (long long)vt_chunk_stride;
+  a.k_prescaled = true; a.head_flags = head_flags; a.row_offset_kmax = kmax;
+  a.pass = pass == 0 ? nullptr : (pass == 1 ? &p1 : &p2);
+  return ret(k5_launch_attention_bf16_sparse(a), "k5_attention_nabla_rect_prescaled_pass");
 }
 
 int k5_nabla_mask_rect_u8(const void* workspace, int H, int q_blocks, int num_blocks, void* out_u8, void* stream) {
@@ -237,8 +258,9 @@ int k5_nabla_mask_rect_u8(const void* workspace, int H, int q_blocks, int num_bl
 
 int k5_attention_bf16_bounded(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len, int kv_len,
                               int ldq, int ldk, int ldvt, int ldo, float score_bound, void* stream) {
-  return ret(k5_launch_attention_bf16_bounded(Q, K, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, score_bound,
-                                              (hipStream_t)stream), "k5_attention_bf16_bounded");
+  K5AttnRangeArgs a = attn_args<K5AttnRangeArgs>(Q, K, Vt, O, H, q_len, kv_len, ldq, ldk, ldvt, ldo, stream);
+  a.score_bound = score_bound;
+  return ret(k5_launch_attention_bf16_range(a), "k5_attention_bf16_bounded");
 }
 
 int k5_ln_modulate_bf16(const void* x, const float* scale, const float* shift, void* out, int rows, int D, int ldx,

@@ -13,17 +13,6 @@ int k5_launch_gemm_bf16(const void* A, const void* W, const float* bias, void* C
 
 // Attention: O[q][h*64+d] = softmax(Q K^T / 8) V, bf16, head_dim 64, non-causal.
 //   Q  [q_len][ldq]  (head h at columns h*64..), K [kv_len][ldk], Vt [H*64][ldvt] = V transposed, O [q_len][ldo].
-// Dense attention with a caller-proved bound |q.k| <= score_bound (0 = unknown -> online running max).
-int k5_launch_attention_bf16_bounded(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len,
-                                     int kv_len, int ldq, int ldk, int ldvt, int ldo, float score_bound,
-                                     hipStream_t stream);
-
-// Same, with V^T stored as per-rank chunks (sequence parallelism): keys [c*chunk_keys, (c+1)*chunk_keys) live at
-// Vt + c*chunk_stride, row stride ldvt.
-int k5_launch_attention_bf16_chunked(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len,
-                                     int kv_len, int ldq, int ldk, int ldvt, int ldo, float score_bound,
-                                     int vt_chunk_keys, long long vt_chunk_stride, hipStream_t stream);
-
 // General form: process key tiles  e -> e + tile_off0 (+ tile_skip_n once >= tile_skip_at), e < tile_cnt (-1 = to the end);
 // flags & 1: resume from `state`, flags & 2: write `state` instead of O (k5_attention_state_bytes floats-as-bytes).
 size_t k5_attention_state_bytes(int H, int q_len);
@@ -44,18 +33,31 @@ struct K5QueryNorm { const float* w; const float* cos; const float* sin; unsigne
 // row_anchor (nullable, [H][q_len]): anchored offsets of the heads k5_launch_attn_flags(anchored) marked with a negative kmax entry
 // (k5_launch_attn_row_anchor) — AttnP::row_anchor
 struct K5KeyCentre { const float* centre; const float* radius; const float* row_anchor = nullptr; };
-int k5_launch_attention_bf16_range(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len,
-                                   int kv_len, int ldq, int ldk, int ldvt, int ldo, float score_bound,
-                                   int vt_chunk_keys, long long vt_chunk_stride, int tile_off0, int tile_cnt, int tile_skip_at,
-                                   int tile_skip_n, float* state, int flags, hipStream_t stream, float* balance_ws = nullptr, bool k_prescaled = false,
-                                   const int* head_flags = nullptr, int variant = 0, const K5TileSegments* segments = nullptr,
-                                   const float* row_offset_kmax = nullptr, int late_pass = 0,   // late_pass: AttnP::late_pass (multi-pass + per-row offsets)
-                                   const K5QueryNorm* query_norm = nullptr,   // fused norm_qk (+ RoPE) of the query rows, see K5QueryNorm
-                                   const K5KeyCentre* key_centre = nullptr);   // centred per-row offsets (with row_offset_kmax), see K5KeyCentre
-size_t k5_attention_balance_bytes(int H, int q_len);
 // softmax form of the pre-scaled-key launches: AUTO = fixed offset where the bound (score_bound, or the per-head device
 // flags) allows it and the lazy online max elsewhere; ONLINE = the online max everywhere
 enum { K5_ATTN_AUTO = 0, K5_ATTN_ONLINE = 1 };
+// Arguments of the attention launchers: what both take, then what only one of them does.  The defaults are a plain one-launch call.
+struct K5AttnArgs {
+  const void* Q = nullptr; const void* K = nullptr; const void* Vt = nullptr; void* O = nullptr;
+  int H = 0, q_len = 0, kv_len = 0, ldq = 0, ldk = 0, ldvt = 0, ldo = 0;
+  float score_bound = 0.f;                          // caller-proved bound |q.k| <= score_bound (0 = unknown -> online running max)
+  int vt_chunk_keys = 0; long long vt_chunk_stride = 0;   // V^T stored as per-rank chunks (sequence parallelism): keys [c*chunk_keys, (c+1)*chunk_keys) live at Vt + c*chunk_stride, row stride ldvt
+  hipStream_t stream = nullptr;
+  float* balance_ws = nullptr;                      // k5_attention_balance_bytes: balanced launch + the per-job fallback flags of the per-row-offset form
+  bool k_prescaled = false;
+  const int* head_flags = nullptr; int variant = K5_ATTN_AUTO;
+  const float* row_offset_kmax = nullptr;           // per-row offsets of the fixed-offset form (k5_launch_attn_flags kmax_out)
+  const K5KeyCentre* key_centre = nullptr;          // centred / anchored per-row offsets (with row_offset_kmax), see K5KeyCentre
+};
+struct K5AttnRangeArgs : K5AttnArgs {
+  int tile_off0 = 0, tile_cnt = -1, tile_skip_at = 0x7fffffff, tile_skip_n = 0;
+  float* state = nullptr; int flags = 0;
+  int late_pass = 0;                                // AttnP::late_pass (multi-pass + per-row offsets)
+  const K5TileSegments* segments = nullptr;
+  const K5QueryNorm* query_norm = nullptr;          // fused norm_qk (+ RoPE) of the query rows, see K5QueryNorm
+};
+int k5_launch_attention_bf16_range(const K5AttnRangeArgs& a);
+size_t k5_attention_balance_bytes(int H, int q_len);
 // per-head flags from the |q|^2 / |k'|^2 maxima that k5_launch_rmsnorm_rope(stats) left (consumed: reset to 0); kstat holds
 // nk partial maxima at stride kstride floats; counters (optional, device u64[2]) += heads sent to {fixed, online}
 // kmax_out (nullable, H floats): max |k'_h| with margin for the per-row offsets of the fixed-offset form (row_offset_kmax of the
@@ -100,15 +102,14 @@ int k5_launch_nabla_mask_u8(const void* workspace, int H, int nqb, int nb, void*
 // *acc += number of kept (query block, key block) pairs of the map in `workspace` (H x nqb rows)
 int k5_launch_nabla_count(const void* workspace, int H, int nqb, int nb, unsigned long long* acc, hipStream_t s);
 int k5_launch_nabla_count_lists(const void* workspace, int H, int nqb, int nb, int group_rows, unsigned long long* acc, hipStream_t s);
-int k5_launch_attention_bf16_sparse(const void* Q, const void* K, const void* Vt, void* O, int H, int q_len, int kv_len, int ldq,
-                                    int ldk, int ldvt, int ldo, float score_bound, const int* list, const int* cnt, int list_stride,
-                                    int vt_chunk_keys, long long vt_chunk_stride, hipStream_t stream, bool k_prescaled = false,
-                                    const int* head_flags = nullptr, int variant = 0, const float* row_offset_kmax = nullptr,
-                                    const K5SparsePass* pass = nullptr, float* balance_ws = nullptr,   // k5_attention_balance_bytes; pre-scaled keys
-                                    int group_rows = 4,    // 2: lists per TWO 64-query rows (k5_launch_nabla_select_rect group_rows = 2), 128-query workgroups
-                                    bool balance = true,   // false: balance_ws only carries the per-job fallback flags of the per-row-offset form
-                                    const K5KeyCentre* key_centre = nullptr,
-                                    int pair_stride = 0);  // group_rows 2: rows of a group per k5_pair_row (the stride the lists were built with)
+struct K5AttnSparseArgs : K5AttnArgs {
+  const int* list = nullptr; const int* cnt = nullptr; int list_stride = 0;
+  const K5SparsePass* pass = nullptr;               // pre-scaled keys
+  int group_rows = 4;    // 2: lists per TWO 64-query rows (k5_launch_nabla_select_rect group_rows = 2), 128-query workgroups
+  bool balance = true;   // false: balance_ws only carries the per-job fallback flags of the per-row-offset form
+  int pair_stride = 0;   // group_rows 2: rows of a group per k5_pair_row (the stride the lists were built with)
+};
+int k5_launch_attention_bf16_sparse(const K5AttnSparseArgs& a);
 
 // K1: out = bf16( LayerNorm(x; eps 1e-5, no affine) * (scale + 1) + shift )
 // out_e4m3 (nullable, [rows][D] bytes): also — or, with out == nullptr, only — e4m3(bf16(.)) at the static scale 1: the activation operand of

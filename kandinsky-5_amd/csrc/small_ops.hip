@@ -652,7 +652,7 @@ int k5_launch_ln_affine(const void* x, const float* w, const float* b, void* out
   return done();
 }
 
-// Ulysses sequence parallelism (engine.hip run_self_attention_ulysses): head-group repacking around the two all-to-alls.
+// Ulysses sequence parallelism (engine.hip run_self_attention_heads): head-group repacking around the two all-to-alls.
 // pack: x [rows][2 D] = (q heads | k heads) of the rank's token rows -> out [P][slot_rows][2 Dp], block g = (q | k) of the heads rank g attends
 __global__ __launch_bounds__(256) void ulysses_pack_qk_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ out, int rows, int slot_rows, int D, int Dp) {
   const int cpr = 2 * D / 8;                                   // 16-B chunks per row
@@ -672,7 +672,7 @@ __global__ __launch_bounds__(256) void ulysses_unpack_o_kernel(const bf16_t* __r
   }
 }
 
-// two-level schedule (engine.hip run_self_attention_2d): x [rows][2 D] = (q heads | k' heads) of the rank's rows -> q_out / k_out, each
+// two-level schedule (engine.hip run_self_attention_heads, two_level): x [rows][2 D] = (q heads | k' heads) of the rank's rows -> q_out / k_out, each
 // [G][slot_rows][Dp] (block g = head group g): the per-destination send planes of the two exchanges, contiguous per destination
 __global__ __launch_bounds__(256) void sp2d_pack_qk_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ q_out, bf16_t* __restrict__ k_out, int rows,
                                                            int slot_rows, int D, int Dp) {

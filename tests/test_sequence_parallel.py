@@ -52,7 +52,7 @@ def _sp_forward(sd, cfg, x, text, pooled, time, vpos, tpos, rank, world, ulysses
         q, k = O.apply_rotary(q, cos, sin, mode), O.apply_rotary(k, cos, sin, mode)
         # every rank's slot holds `slot` rows; only the last rank's may be partly unused (its tail is never read)
         if ulysses:
-            # run_self_attention_ulysses: all-to-all trades this rank's rows of ALL heads for ALL rows of its H / world heads (blocks of
+            # run_self_attention_heads (Ulysses): all-to-all trades this rank's rows of ALL heads for ALL rows of its H / world heads (blocks of
             # `slot` rows per rank, the last one short), one full-sequence attention per owned head, all-to-all of the outputs back
             Hg = H // world                                    # heads per rank (Hp is the patched height here)
             def to_heads(t):                                   # (n, H, 64) -> (N, Hg, 64)
