@@ -10,6 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
+from oracle import parity as P  # noqa: E402
 
 BF = torch.bfloat16
 
@@ -35,8 +36,9 @@ def bfr(x):
 def assert_bf16_close(got, ref, ulps=2, atol=1e-3, what=""):
     got, ref = got.float().cpu(), ref.float()
     tol = atol + ulps * 2.0 ** -7 * ref.abs()
-    bad = (got - ref).abs() > tol
-    assert not bad.any(), f"{what}: {int(bad.sum())} / {bad.numel()} off; max abs err {(got - ref).abs().max():.4g}"
+    assert torch.isfinite(got).all(), f"{what}: {int((~torch.isfinite(got)).sum())} / {got.numel()} values are not finite"
+    err = (got - ref).abs()
+    assert (err <= tol).all(), f"{what}: {int((~(err <= tol)).sum())} / {err.numel()} off; max abs err {err.max():.4g}"
 
 
 # ------------------------------------------------------------------------------------------ GEMM
@@ -105,7 +107,8 @@ def test_gemm_four_wave_kernel_is_race_free_and_handles_edges(E):
     ref = bfr(resid + gate * inner)                                                 # summation order) is worth |gate| ulp(inner) outside
     err = (got.float().cpu() - ref).abs()
     tol = 1e-3 + 3 * 2.0 ** -7 * ref.abs() + gate.abs() * 2.0 ** -7 * inner.abs()
-    assert not (err > tol).any(), f"4-wave gemm gate: {int((err > tol).sum())} off, max abs err {err.max():.4g}"
+    assert torch.isfinite(got).all()
+    assert (err <= tol).all(), f"4-wave gemm gate: {int((err > tol).sum())} off, max abs err {err.max():.4g}"
     assert (err > 3 * 2.0 ** -7 * ref.abs() + 1e-3).float().mean().item() < 1e-5   # ... and such flips are rare
     bm = bfr(rnd(M, seed=76))
     ld = (N + 7) // 8 * 8 + 8                                                     # padded leading dimension (the V^T layout)
@@ -149,7 +152,8 @@ def test_gemm_four_wave_token_tile_heights(E, M, N, K):
     inner = bfr(acc)
     ref = bfr(resid + gate * inner)
     err = (base["gate_nobias"].float().cpu() - ref).abs()
-    assert not (err > 1e-3 + 3 * 2.0 ** -7 * ref.abs() + gate.abs() * 2.0 ** -7 * inner.abs()).any(), f"128x128 gate without bias: max abs err {err.max():.4g}"
+    assert torch.isfinite(base["gate_nobias"]).all()
+    assert (err <= 1e-3 + 3 * 2.0 ** -7 * ref.abs() + gate.abs() * 2.0 ** -7 * inner.abs()).all(), f"128x128 gate without bias: max abs err {err.max():.4g}"
     for tile in (256, 192, 128):
         for rep in range(3):
             got = run(4, tile)
@@ -256,7 +260,8 @@ def attn_ref(q, k, v):
                                      (64, 640, 1), (1, 1, 1)])
 def test_attention_matches_oracle(E, Sq, Sk, H):
     q, k, v = bfr(rnd(Sq, H, 64, seed=1)), bfr(rnd(Sk, H, 64, seed=2)), bfr(rnd(Sk, H, 64, seed=3))
-    ref = attn_ref(q, k, v)
+    R = P.AttentionRef(q, k, v)
+    ref = R.bf16
     ld = (Sk + 7) // 8 * 8
     vt = torch.zeros(H * 64, ld, dtype=BF, device="cuda")
     vt[:, :Sk] = v.reshape(Sk, H * 64).t().to(BF)
@@ -264,6 +269,7 @@ def test_attention_matches_oracle(E, Sq, Sk, H):
     torch.cuda.synchronize()
     # P is rounded to bf16 before P.V (as in flash-attn): allow 1e-2 absolute on O(1) outputs
     assert_bf16_close(got, ref, ulps=4, atol=1e-2, what=f"attention {Sq}x{Sk}x{H}")
+    R.close(got, P.MARGIN_ONLINE, f"attention {Sq}x{Sk}x{H}")
 
 
 def test_attention_strided_qk_views(E):
@@ -271,11 +277,13 @@ def test_attention_strided_qk_views(E):
     S, H = 200, 2
     qk = bfr(rnd(S, 2 * H * 64, seed=7))
     v = bfr(rnd(S, H, 64, seed=8))
-    ref = attn_ref(qk[:, :H * 64].reshape(S, H, 64), qk[:, H * 64:].reshape(S, H, 64), v)
+    R = P.AttentionRef(qk[:, :H * 64].reshape(S, H, 64), qk[:, H * 64:].reshape(S, H, 64), v)
+    ref = R.bf16
     d = qk.cuda().to(BF)
     vt = v.reshape(S, -1).t().contiguous().cuda().to(BF)
     got = E.attention(d[:, :H * 64], d[:, H * 64:], vt, H)
     assert_bf16_close(got, ref, ulps=4, atol=1e-2, what="strided attention")
+    R.close(got, P.MARGIN_ONLINE, "strided attention")
 
 
 def test_attention_online_softmax_rescale_branch(E):
@@ -285,10 +293,13 @@ def test_attention_online_softmax_rescale_branch(E):
     q, k, v = bfr(rnd(S, H, 64, seed=1)), bfr(rnd(S, H, 64, seed=2)), bfr(rnd(S, H, 64, seed=3))
     k[600, 0] = q[5, 0] * 4.0  # spikes q5.k600 far above everything seen before
     k[900, 0] = q[700, 0] * 6.0
-    ref = attn_ref(q, k, v)
+    k = bfr(k)          # 6 q is no bf16 value: the kernel is handed the rounded key, and the reference must see that one
+    R = P.AttentionRef(q, k, v)
+    ref = R.bf16
     vt = v.reshape(S, -1).t().contiguous().cuda().to(BF)
     got = E.attention(q.reshape(S, -1).cuda().to(BF), k.reshape(S, -1).cuda().to(BF), vt, H)
     assert_bf16_close(got, ref, ulps=4, atol=1e-2, what="rescale branch")
+    R.close(got, P.MARGIN_ONLINE, "rescale branch")
 
 
 def test_attention_full_size_properties(E):
@@ -303,9 +314,11 @@ def test_attention_full_size_properties(E):
     o = E.attention(q, k, vt, H)
     # (1) sampled query rows vs the CPU oracle
     rows = torch.tensor([0, 1, 31, 32, 255, 256, 4097, 23808, 47615 - 64, 47615])
-    ref = attn_ref(q[rows].float().cpu().reshape(-1, H, 64), k.float().cpu().reshape(N, H, 64),
-                   v.float().cpu().reshape(N, H, 64))
+    R = P.AttentionRef(q[rows].float().cpu().reshape(-1, H, 64), k.float().cpu().reshape(N, H, 64),
+                       v.float().cpu().reshape(N, H, 64))
+    ref = R.bf16
     assert_bf16_close(o[rows], ref, ulps=4, atol=5e-3, what="full-size sampled rows")
+    R.close(o[rows], P.MARGIN_ONLINE, "full-size sampled rows")
     # (2) softmax rows sum to one: V = const  ->  O = const
     vc = torch.full_like(vt, 0.75)
     oc = E.attention(q, k, vc, H)
@@ -436,7 +449,8 @@ def test_attention_bounded_scores_equals_online_max(E):
     def rmsn(x):
         return bfr(x / x.pow(2).mean(-1, keepdim=True).sqrt())
     q, k, v = rmsn(rnd(S, H, 64, seed=1)), rmsn(rnd(S, H, 64, seed=2)), bfr(rnd(S, H, 64, seed=3))
-    ref = attn_ref(q, k, v)
+    R = P.AttentionRef(q, k, v)
+    ref = R.bf16
     vt = torch.zeros(H * 64, 704, dtype=BF, device="cuda")  # leading dimension must be a multiple of 8
     vt[:, :S] = v.reshape(S, -1).t().to(BF)
     qd, kd = q.reshape(S, -1).cuda().to(BF), k.reshape(S, -1).cuda().to(BF)
@@ -445,6 +459,8 @@ def test_attention_bounded_scores_equals_online_max(E):
     a = E.attention(qd, kd, vt, H, kv_len=S, score_bound=64 * 1.05)
     b = E.attention(qd, kd, vt, H, kv_len=S)
     assert_bf16_close(a, ref, ulps=4, atol=1e-2, what="bounded attention")
+    R.close(a, P.MARGIN_FIXED, "bounded attention")
+    R.close(b, P.MARGIN_ONLINE, "unbounded attention on the same data")
     assert (a.float() - b.float()).abs().max().item() <= 2 ** -7
     # a bound too large for a fixed offset silently falls back to the online-max kernel (still correct)
     c = E.attention(qd, kd, vt, H, kv_len=S, score_bound=1e4)
@@ -475,7 +491,9 @@ def test_attention_split_key_passes_equal_single_pass(E, Sq, Sk, split, bound):
     assert torch.isnan(out.float()).all()                       # pass 1 writes only the state
     E.check(E.lib().k5_attention_bf16_range(*args, 0, total - n1, split, n1, state.data_ptr(), 1, E.stream_ptr()))
     assert_bf16_close(out, one.float().cpu(), ulps=2, atol=2e-3, what="two-pass attention")
-    assert_bf16_close(out, attn_ref(q, k, v), ulps=4, atol=1e-2, what="two-pass attention vs oracle")
+    R = P.AttentionRef(q, k, v)
+    assert_bf16_close(out, R.bf16, ulps=4, atol=1e-2, what="two-pass attention vs oracle")
+    R.close(out, P.MARGIN_ONLINE if bound is None else P.MARGIN_FIXED, f"two-pass attention {Sq}x{Sk} split {split} bound {bound}")
 
 
 @pytest.mark.parametrize("Sq,Sk,H,bound", [(47616 // 8, 47616, 28, 64 * 1.05), (5952, 8192, 28, None), (2600, 1500, 9, None),
@@ -500,6 +518,13 @@ def test_attention_balanced_tail_split_equals_single_launch(E, Sq, Sk, H, bound)
                                          ws.data_ptr(), E.stream_ptr()))
     assert not torch.isnan(out.float()).any()
     assert_bf16_close(out, one.float().cpu(), ulps=2, atol=2e-3, what="balanced attention")
+    # sampled rows (whole-round jobs and the split tail jobs at the end) of both launches against float64
+    rows = torch.unique(torch.tensor([0, 1, 255, 256, Sq // 2, max(Sq - 700, 0), max(Sq - 257, 0), Sq - 65, Sq - 1]))
+    R = P.AttentionRef(q[rows].float().cpu().reshape(-1, H, 64), k.float().cpu().reshape(Sk, H, 64),
+                       vt[:, :Sk].t().float().cpu().reshape(Sk, H, 64))
+    margin = P.MARGIN_ONLINE if bound is None else P.MARGIN_FIXED
+    R.close(out[rows], margin, f"balanced attention {Sq}x{Sk}x{H} bound {bound}")
+    R.close(one[rows], margin, f"single-launch attention {Sq}x{Sk}x{H} bound {bound}")
 
 
 # ------------------------------------------------------------------------------------------ fp8 (e4m3) GEMM, opt-in path
@@ -588,7 +613,9 @@ def test_attention_prescaled_keys(E):
     L = E.lib()
     E.check(L.k5_attention_bf16_prescaled(qd.data_ptr(), kcd.data_ptr(), vt.data_ptr(), out.data_ptr(), H, Sq, Sk, qd.stride(0),
                                           kcd.stride(0), vt.stride(0), out.stride(0), 64 * 1.05, E.stream_ptr()))
-    assert_bf16_close(out, O.sdpa(q, kc, v, "bf16", None, base2=True), ulps=4, atol=1e-2, what="prescaled attention vs base-2 oracle")
+    R = P.AttentionRef(q, kc, v, base2=True)
+    assert_bf16_close(out, R.bf16, ulps=4, atol=1e-2, what="prescaled attention vs base-2 oracle")
+    R.close(out, P.MARGIN_FIXED, "prescaled attention, fixed offset")
     plain = E.attention(qd, kd, vt, H, kv_len=Sk, score_bound=64 * 1.05)
     assert (out.float() - plain.float()).abs().max().item() <= 3e-2        # re-rounded keys: bf16-level differences only
     # without a usable bound the same entry runs the online-max form (tests/test_gpu_softmax_variants.py): same softmax
@@ -596,6 +623,7 @@ def test_attention_prescaled_keys(E):
     E.check(L.k5_attention_bf16_prescaled(qd.data_ptr(), kcd.data_ptr(), vt.data_ptr(), out2.data_ptr(), H, Sq, Sk, qd.stride(0),
                                           kcd.stride(0), vt.stride(0), out2.stride(0), 0.0, E.stream_ptr()))
     assert (out2.float() - out.float()).abs().max().item() <= 2 ** -6
+    R.close(out2, P.MARGIN_ONLINE, "prescaled attention, online max")
     with pytest.raises(RuntimeError):                                       # ... and whole key tiles
         E.check(L.k5_attention_bf16_prescaled(qd.data_ptr(), kcd.data_ptr(), vt.data_ptr(), out.data_ptr(), H, Sq, Sk - 8, qd.stride(0),
                                               kcd.stride(0), vt.stride(0), out.stride(0), 64 * 1.05, E.stream_ptr()))

@@ -10,6 +10,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
+from oracle import parity as P  # noqa: E402
 
 BF = torch.bfloat16
 C = torch.tensor(O.SOFTMAX_C, dtype=torch.float32)
@@ -34,8 +35,9 @@ def bfr(x):
 
 def close(got, ref, ulps=4, atol=1e-2, what=""):
     got, ref = got.float().cpu(), ref.float()
-    bad = (got - ref).abs() > atol + ulps * 2.0 ** -7 * ref.abs()
-    assert not bad.any(), f"{what}: {int(bad.sum())} / {bad.numel()} off; max abs err {(got - ref).abs().max():.4g}"
+    assert torch.isfinite(got).all(), f"{what}: {int((~torch.isfinite(got)).sum())} / {got.numel()} values are not finite"
+    err, tol = (got - ref).abs(), atol + ulps * 2.0 ** -7 * ref.abs()
+    assert (err <= tol).all(), f"{what}: {int((~(err <= tol)).sum())} / {err.numel()} off; max abs err {err.max():.4g}"
 
 
 def vt_of(v):
@@ -93,7 +95,9 @@ def test_prescaled_online_max_matches_oracle(E, Sq, Sk, H, gain):
     q, k, v = rmsn(rnd(Sq, H, 64, seed=61)), rmsn(rnd(Sk, H, 64, seed=62)), bfr(rnd(Sk, H, 64, seed=63))
     kc = bfr(k * C)
     out = run_auto(E, q.reshape(Sq, -1).cuda().to(BF), kc.reshape(Sk, -1).cuda().to(BF), vt_of(v), H, None, 1)
-    close(out, O.sdpa(q, kc, v, "bf16", None, base2=True), what=f"online max, gain {gain}")
+    R = P.AttentionRef(q, kc, v, base2=True)
+    close(out, R.bf16, what=f"online max, gain {gain}")
+    R.close(out, P.MARGIN_ONLINE, f"online max {Sq}x{Sk}x{H}, gain {gain}")
 
 
 def test_prescaled_online_max_rescale_branch(E):
@@ -105,9 +109,11 @@ def test_prescaled_online_max_rescale_branch(E):
     k[600, 0] = q[5, 0] * 40.0        # q5.k600 ~ 40 |q5|^2 ~ 2500 raw -> ~450 in the exp2 domain
     k[900, 1] = q[700, 1] * 6.0
     k[:64, 0] = -q[33, 0] * 30.0      # row 33, head 0: first tile ~ -350 (exp2 domain): offset must start there
-    ref = O.sdpa(q, bfr(k * C), v, "bf16", None, base2=True)
+    R = P.AttentionRef(q, bfr(k * C), v, base2=True)
+    ref = R.bf16
     out = run_auto(E, q.reshape(S, -1).cuda().to(BF), bfr(k * C).reshape(S, -1).cuda().to(BF), vt_of(v), H, None, 1)
     close(out, ref, what="online rescale branch")
+    R.close(out, P.MARGIN_ONLINE, "online rescale branch")
     assert not torch.isnan(out.float()).any()
 
 
@@ -126,9 +132,12 @@ def test_prescaled_online_two_pass_and_balanced_merge(E):
     # split parts exponentiate against their own offsets: the bf16 roundings of P differ from the single launch's
     close(bal, one.cpu(), ulps=4, atol=1e-2, what="balanced online")
     rows = torch.tensor([0, 77, 255, 256, 3000, Sq - 1])
-    ref = O.sdpa(q[rows].float().cpu().reshape(-1, H, 64), kc.float().cpu().reshape(Sk, H, 64), vt.t().float().cpu().reshape(Sk, H, 64),
-                 "bf16", None, base2=True)
+    R = P.AttentionRef(q[rows].float().cpu().reshape(-1, H, 64), kc.float().cpu().reshape(Sk, H, 64), vt.t().float().cpu().reshape(Sk, H, 64),
+                       base2=True)
+    ref = R.bf16
     close(one[rows], ref, what="online sampled rows")
+    R.close(one[rows], P.MARGIN_ONLINE, "online sampled rows, single launch")
+    R.close(bal[rows], P.MARGIN_ONLINE, "online sampled rows, balanced launch")
 
 
 # ------------------------------------------------------------------------------------------ per-head choice on the device
@@ -153,10 +162,13 @@ def test_per_head_flags_from_the_data_and_mixed_launch(E):
     assert flags.tolist() == [int(b * 1.002 <= 90.0) for b in bound.tolist()] == [1, 0, 1, 0], (flags, bound)
     assert float(qstat.abs().max()) == 0.0 and float(kstat.abs().max()) == 0.0          # consumed
     qd, kd, vt = q.reshape(S, -1).cuda().to(BF), kc.reshape(S, -1).cuda().to(BF), vt_of(v)
-    ref = O.sdpa(q, kc, v, "bf16", None, base2=True)
+    R = P.AttentionRef(q, kc, v, base2=True)
+    ref = R.bf16
     for balanced in (False, True):
         out = run_auto(E, qd, kd, vt, H, flags, 0, balanced)
         close(out, ref, what=f"mixed launch (balanced={balanced})")
+        R.close(out, P.MARGIN_FIXED, f"mixed launch (balanced={balanced}), fixed-offset heads", heads=[0, 2])
+        R.close(out, P.MARGIN_ONLINE, f"mixed launch (balanced={balanced}), online heads", heads=[1, 3])
     # forcing: every head online
     qstat.fill_(1.0); kstat.fill_(1.0)
     E.check(E.lib().k5_attention_flags(qstat.data_ptr(), kstat.data_ptr(), 2, H, H, 1, flags.data_ptr(), E.stream_ptr()))
@@ -181,7 +193,9 @@ def test_fixed_offset_window_edge(E):
     v = bfr(rnd(S, H, 64, seed=23))
     flags = torch.ones(H, dtype=torch.int32, device="cuda")
     out = run_auto(E, q.reshape(S, -1).cuda().to(BF), kc.reshape(S, -1).cuda().to(BF), vt_of(v), H, flags, 0)
-    close(out, O.sdpa(q, kc, v, "bf16", None, base2=True), what="window edge")
+    R = P.AttentionRef(q, kc, v, base2=True)
+    close(out, R.bf16, what="window edge")
+    R.close(out, P.MARGIN_FIXED, "window edge")
 
 
 def test_config2_size_both_forms_sampled_rows_vs_oracle(E):
@@ -204,8 +218,11 @@ def test_config2_size_both_forms_sampled_rows_vs_oracle(E):
     assert flags.tolist() == [1] * 14 + [0] * 14, flags
     out = run_auto(E, q, kc, vt, H, flags, 0, balanced=True)
     rows = torch.tensor([0, 1, 31, 255, 256, 4097, 23808, 40000, 47104, 47615 - 64, 47615])   # incl. rows of the split tail jobs
-    ref = O.sdpa(qf[rows].cpu(), kf.cpu(), v.float().cpu().reshape(N, H, 64), "bf16", None, base2=True)
+    R = P.AttentionRef(qf[rows].cpu(), kf.cpu(), v.float().cpu().reshape(N, H, 64), base2=True)
+    ref = R.bf16
     close(out[rows], ref, ulps=4, atol=5e-3, what="config-2 sampled rows")
+    R.close(out[rows], P.MARGIN_FIXED, "config-2 sampled rows, fixed-offset heads", heads=list(range(14)))
+    R.close(out[rows], P.MARGIN_ONLINE, "config-2 sampled rows, online heads", heads=list(range(14, 28)))
     oc = run_auto(E, q, kc, torch.full_like(vt, 0.75), H, flags, 0, balanced=True)
     assert (oc.float() - 0.75).abs().max().item() <= 2 ** -8
 
@@ -230,8 +247,11 @@ def test_config5_size_both_forms_sampled_rows_vs_oracle(E):
     assert flags.tolist() == [1, 0], flags
     out = run_auto(E, q, kc, vt, H, flags, 0, balanced=True)
     rows = torch.tensor([0, 63, 64, 4097, 117120, 200000, N - 65, N - 1])
-    ref = O.sdpa(qf[rows].cpu(), kf.cpu(), v.float().cpu().reshape(N, H, 64), "bf16", None, base2=True)
+    R = P.AttentionRef(qf[rows].cpu(), kf.cpu(), v.float().cpu().reshape(N, H, 64), base2=True)
+    ref = R.bf16
     close(out[rows], ref, ulps=4, atol=5e-3, what="config-5 sampled rows")
+    R.close(out[rows], P.MARGIN_FIXED, "config-5 sampled rows, fixed-offset head", heads=[0])
+    R.close(out[rows], P.MARGIN_ONLINE, "config-5 sampled rows, online head", heads=[1])
     oc = run_auto(E, q, kc, torch.full_like(vt, 0.75), H, flags, 0, balanced=True)
     assert (oc.float() - 0.75).abs().max().item() <= 2 ** -8
 
@@ -276,7 +296,9 @@ def test_row_offsets_keep_large_norm_heads_on_the_fixed_form(E, Sq, Sk, H):
     out = run_rows(E, q.reshape(Sq, -1).cuda().to(BF), k.reshape(Sk, -1).cuda().to(BF), vt_of(v), H, flags, kmax)
     assert flags.tolist() == [1, 1, 1, 1], flags
     rows = torch.arange(Sq) if Sq < 2000 else torch.tensor([0, 5, 255, 256, 4097, 20000, 32767, 32768, 33000, Sq - 1])
-    close(out[rows], O.sdpa(q[rows], k, v, "bf16", None, base2=True), ulps=4, atol=5e-3, what="per-row offsets")
+    R = P.AttentionRef(q[rows], k, v, base2=True)
+    close(out[rows], R.bf16, ulps=4, atol=5e-3, what="per-row offsets")
+    R.close(out[rows], P.MARGIN_ROWS, f"per-row offsets {Sq}x{Sk}")
 
 
 def test_row_offsets_late_fallback_when_a_row_underflows(E):
@@ -300,16 +322,19 @@ def test_row_offsets_late_fallback_when_a_row_underflows(E):
     assert flags.tolist() == [1, 1], flags                                 # both bounds are <= 190: the fixed form is tried first
     s0 = (q[:, 0] @ k[:, 0].t())
     assert s0.max().item() < -100 and (kmax[0].item() * q[:, 0].norm(dim=-1).min().item()) > 130
-    ref = O.sdpa(q, k, v, "bf16", None, base2=True)
+    R = P.AttentionRef(q, k, v, base2=True)
+    ref = R.bf16
     # with a workspace the fallback is per JOB (round 3): the underflowing (head, 256-query) jobs are redone by the online launch of the
     # same call and the head's flag is left alone
     out = run_rows(E, q.reshape(Sq, -1).cuda().to(BF), k.reshape(Sk, -1).cuda().to(BF), vt_of(v), H, flags, kmax)
     assert flags.tolist() == [1, 1], flags
     close(out, ref, ulps=4, atol=5e-3, what="late fallback, per job")
+    R.close(out, P.MARGIN_ROWS, "late fallback, per job")
     # without one (no room for job flags): the whole head, as in round 2
     out = run_rows(E, q.reshape(Sq, -1).cuda().to(BF), k.reshape(Sk, -1).cuda().to(BF), vt_of(v), H, flags, kmax, balanced=False)
     assert flags.tolist() == [0, 1], flags                                 # head 0 fell back late, head 1 did not
     close(out, ref, ulps=4, atol=5e-3, what="late fallback, per head")
+    R.close(out, P.MARGIN_ROWS, "late fallback, per head")
 
 
 def test_row_offsets_fallback_is_per_job(E):
@@ -339,7 +364,9 @@ def test_row_offsets_fallback_is_per_job(E):
     out = run_rows(E, q.reshape(Sq, -1).cuda().to(BF), k.reshape(Sk, -1).cuda().to(BF), vt_of(v), H, flags, kmax)
     assert flags.tolist() == [1, 1, 1, 1], flags
     rows = torch.cat([torch.arange(0, Sq, 1237), torch.arange(256 * 3, 256 * 4, 17), torch.arange(Sq - 256, Sq, 13), torch.arange(Sq - 2048, Sq - 256, 211)])
-    close(out[rows], O.sdpa(q[rows], k, v, "bf16", None, base2=True), ulps=4, atol=5e-3, what="per-job fallback")
+    R = P.AttentionRef(q[rows], k, v, base2=True)
+    close(out[rows], R.bf16, ulps=4, atol=5e-3, what="per-job fallback")
+    R.close(out[rows], P.MARGIN_ROWS, "per-job fallback")
 
 
 @pytest.mark.parametrize("bad_half", ["first", "both"])
@@ -380,7 +407,9 @@ def test_row_offsets_late_fallback_across_passes(E, bad_half):
     assert flags.tolist() == [1, 1], flags            # per-job flags (in the workspace): head 0's jobs went late in pass A, its head flag stays
     run_pass(T // 2, T - T // 2, 1, 2)
     assert flags.tolist() == [1, 1], flags
-    close(out, O.sdpa(q, k, v, "bf16", None, base2=True), ulps=4, atol=5e-3, what=f"late fallback across passes ({bad_half})")
+    R = P.AttentionRef(q, k, v, base2=True)
+    close(out, R.bf16, ulps=4, atol=5e-3, what=f"late fallback across passes ({bad_half})")
+    R.close(out, P.MARGIN_ROWS, f"late fallback across passes ({bad_half})")
 
 
 # ------------------------------------------------------------------------------------------ norm_qk + RoPE of the queries fused into the Q load
@@ -463,10 +492,14 @@ def test_fused_query_norm_matches_the_standalone_norm(E, Sq, Sk, H):
     # -ffp-contract=fast had picked one per kernel: tools/probes/qn_arith_probe.hip).  Before: 1e-4 of the (row, head) pairs differed in one query element.
     assert torch.equal(out, ref_k), ((out.float() - ref_k.float()).abs().max().item(), (out != ref_k).float().mean().item())
     rows = torch.arange(Sq) if Sq < 2000 else torch.tensor([0, 5, 255, 256, 4097, 20000, 32767, 32768, 33000, Sq - 1])
-    close(out[rows], O.sdpa(qnf[rows], k, v, "bf16", None, base2=True), ulps=4, atol=5e-3, what="fused query norm")
+    R = P.AttentionRef(qnf[rows], k, v, base2=True)
+    close(out[rows], R.bf16, ulps=4, atol=5e-3, what="fused query norm")
+    R.close(out[rows], P.MARGIN_ROWS, f"fused query norm {Sq}x{Sk}, heads on the fixed form", heads=[0, 1, 2])
+    R.close(out[rows], P.MARGIN_ONLINE, f"fused query norm {Sq}x{Sk}, head sent to the online form", heads=[3])
     # forced online max (no flags): the same queries through the other form
     out_on = run_qnorm(E, qraw.reshape(Sq, -1).cuda().to(BF), wd, cd, sd, kd, vt, H, None, None)
-    close(out_on[rows], O.sdpa(qnf[rows], k, v, "bf16", None, base2=True), ulps=4, atol=5e-3, what="fused query norm, online")
+    close(out_on[rows], R.bf16, ulps=4, atol=5e-3, what="fused query norm, online")
+    R.close(out_on[rows], P.MARGIN_ONLINE, f"fused query norm {Sq}x{Sk}, online")
 
 
 def test_fused_query_norm_one_large_row_flips_its_head(E):
@@ -489,7 +522,9 @@ def test_fused_query_norm_one_large_row_flips_its_head(E):
     flags, kmax = kflags(E, k, H)
     out = run_qnorm(E, qraw.reshape(Sq, -1).cuda().to(BF), wd, cd, sd, kd, vt, H, flags, kmax)
     assert flags.tolist() == [0, 1], flags
-    close(out, O.sdpa(qnf, k, v, "bf16", None, base2=True), ulps=4, atol=5e-3, what="one large row")
+    R = P.AttentionRef(qnf, k, v, base2=True)
+    close(out, R.bf16, ulps=4, atol=5e-3, what="one large row")
+    R.close(out, P.MARGIN_ROWS, "one large row")
 
 
 def test_fused_query_norm_across_passes(E):
@@ -508,7 +543,9 @@ def test_fused_query_norm_across_passes(E):
     out = run_qnorm(E, qraw.reshape(Sq, -1).cuda().to(BF), wd, cd, sd, kd, vt, H, flags, kmax,
                     passes=[(0, T // 2, 2, 1), (T // 2, T - T // 2, 1, 2)])
     assert flags.tolist() == [1, 1, 2], flags       # a flip in a multi-pass schedule is always the LATE flag (recompute from scratch)
-    close(out, O.sdpa(qnf, k, v, "bf16", None, base2=True), ulps=4, atol=5e-3, what="fused query norm across passes")
+    R = P.AttentionRef(qnf, k, v, base2=True)
+    close(out, R.bf16, ulps=4, atol=5e-3, what="fused query norm across passes")
+    R.close(out, P.MARGIN_ROWS, "fused query norm across passes")
 
 
 def test_fused_query_norm_flip_from_a_tail_job_across_passes(E):
@@ -536,7 +573,9 @@ def test_fused_query_norm_flip_from_a_tail_job_across_passes(E):
                     passes=[(0, T // 2, 2, 1), (T // 2, T - T // 2, 1, 2)])
     assert flags.tolist() == [1, 1, 1, 2], flags
     rows = torch.cat([torch.arange(0, Sq - 2048, 997), torch.arange(Sq - 2048, Sq, 61), torch.tensor([Sq - 3, Sq - 1])])
-    close(out[rows], O.sdpa(qnf[rows], k, v, "bf16", None, base2=True), ulps=4, atol=5e-3, what="flip from a tail job across passes")
+    R = P.AttentionRef(qnf[rows], k, v, base2=True)
+    close(out[rows], R.bf16, ulps=4, atol=5e-3, what="flip from a tail job across passes")
+    R.close(out[rows], P.MARGIN_ROWS, "flip from a tail job across passes")
 
 
 # ------------------------------------------------------------------------------------------ centred per-row offsets (round 3)
@@ -596,14 +635,18 @@ def test_centred_offsets_on_keys_with_a_common_component(E, Sq, Sk):
     assert flags.tolist() == [1, 1, 1, 1] and (nqR[:2] < 190).all() and nqR[2] < 190, (flags, nqR)
     qd, kd, vt = q.reshape(Sq, -1).cuda().to(BF), k.reshape(Sk, -1).cuda().to(BF), vt_of(v)
     rows = torch.arange(Sq) if Sq < 2000 else torch.tensor([0, 5, 255, 256, 4097, 20000, 32767, 32768, 33000, Sq - 1])
-    ref = O.sdpa(q[rows], k, v, "bf16", None, base2=True)
+    R = P.AttentionRef(q[rows], k, v, base2=True)
+    ref = R.bf16
     for balanced in (False, True):
         out = run_rows_centred(E, qd, kd, vt, H, flags, kmax, centre, krad, balanced=balanced)
         assert flags.tolist() == [1, 1, 1, 1], (balanced, flags)           # nothing underflowed: no head was sent to the online form late
         close(out[rows], ref, ulps=4, atol=5e-3, what=f"centred offsets (balanced={balanced})")
+        R.close(out[rows], P.MARGIN_ROWS, f"centred offsets {Sq}x{Sk} (balanced={balanced})")
     # the plain form of the same call: heads 0 and 1 on the online max — the same numbers
     out_p = run_rows(E, qd, kd, vt, H, f_plain, kmax_plain)
     close(out_p[rows], ref, ulps=4, atol=5e-3, what="plain offsets / online form")
+    R.close(out_p[rows], P.MARGIN_ONLINE, f"plain offsets {Sq}x{Sk}: heads beyond the plain window on the online form", heads=[0, 1])
+    R.close(out_p[rows], P.MARGIN_ROWS, f"plain offsets {Sq}x{Sk}: heads on the fixed form", heads=[2, 3])
 
 
 def test_key_centre_and_radius_from_the_norm_pass(E):
@@ -710,10 +753,12 @@ def test_anchored_offsets_beyond_the_window(E, Sq, Sk):
     assert torch.allclose(-kmax[:2].cpu(), k.norm(dim=-1).amax(0)[:2] * 1.002, rtol=1e-3), kmax
     qd, kd, vt = q.reshape(Sq, -1).cuda().to(BF), k.reshape(Sk, -1).cuda().to(BF), vt_of(v)
     rows = torch.arange(Sq) if Sq < 2000 else torch.tensor([0, 5, 255, 256, 4097, 20000, 32767, 32768, 33000, Sq - 1])
-    ref = O.sdpa(q[rows], k, v, "bf16", None, base2=True)
+    R = P.AttentionRef(q[rows], k, v, base2=True)
+    ref = R.bf16
     out, anchor = run_rows_anchored(E, qd, kd, vt, H, flags, kmax, centre, krad, balanced=True)
     assert flags.tolist() == [1, 1, 1, 1], flags
     close(out[rows], ref, ulps=4, atol=5e-3, what="anchored offsets")
+    R.close(out[rows], P.MARGIN_ROWS, f"anchored offsets {Sq}x{Sk}")
     beyond = 0
     for h in (0, 1):
         smax, want = _anchor_offsets(q[:, h], k[:, h])
@@ -729,6 +774,7 @@ def test_anchored_offsets_beyond_the_window(E, Sq, Sk):
         out2, _ = run_rows_anchored(E, qd, kd, vt, H, flags2, kmax2, centre2, krad2, balanced=False)
         assert flags2.tolist() == [1, 1, 1, 1], flags2
         close(out2[rows], ref, ulps=4, atol=5e-3, what="anchored offsets (no workspace)")
+        R.close(out2[rows], P.MARGIN_ROWS, f"anchored offsets {Sq}x{Sk} (no workspace)")
 
 
 def test_marked_heads_attended_without_anchors_fall_back_safely(E):
@@ -750,16 +796,19 @@ def test_marked_heads_attended_without_anchors_fall_back_safely(E):
     q, k = bfr(q), bfr(k)
     v = bfr(torch.randn(Sk, H, 64, generator=g))
     qd, kd, vt = q.reshape(Sq, -1).cuda().to(BF), k.reshape(Sk, -1).cuda().to(BF), vt_of(v)
-    ref = O.sdpa(q, k, v, "bf16", None, base2=True)
+    R = P.AttentionRef(q, k, v, base2=True)
+    ref = R.bf16
     for balanced in (True, False):
         flags, kmax, krad, centre = flags_rows_anchored(E, q, k, H)
         assert flags.tolist() == [1, 1, 1, 1] and (kmax[:2] < 0).all()
         out = run_rows_centred(E, qd, kd, vt, H, flags, kmax, centre, krad, balanced=balanced)       # marked heads, NO anchors
         assert torch.isfinite(out.float()).all()
         close(out, ref, ulps=4, atol=5e-3, what=f"marked heads without anchors (balanced={balanced})")
+        R.close(out, P.MARGIN_ROWS, f"marked heads without anchors (balanced={balanced})")
         flags, kmax, _, _ = flags_rows_anchored(E, q, k, H)
         out_p = run_rows(E, qd, kd, vt, H, flags, kmax)                                             # the plain per-row-offset entry point
         close(out_p, ref, ulps=4, atol=5e-3, what="marked heads through k5_attention_bf16_prescaled_rows")
+        R.close(out_p, P.MARGIN_ROWS, "marked heads through k5_attention_bf16_prescaled_rows")
 
 
 def test_anchored_offsets_overflow_falls_back_per_job(E):
@@ -786,13 +835,16 @@ def test_anchored_offsets_overflow_falls_back_per_job(E):
     out, anchor = run_rows_anchored(E, qd, kd, vt, H, flags, kmax, centre, krad, balanced=True)
     assert flags.tolist() == [1, 1], flags                                  # a job fell back, not the head
     assert ((q[300:311, 0] @ k[:, 0].t()).amax(-1) - anchor[0, 300:311].cpu() > 300).all()   # the anchors really were too low
-    ref = O.sdpa(q, k, v, "bf16", None, base2=True)
+    R = P.AttentionRef(q, k, v, base2=True)
+    ref = R.bf16
     close(out, ref, ulps=4, atol=5e-3, what="anchored offsets with one overflowing job")
+    R.close(out, P.MARGIN_ROWS, "anchored offsets with one overflowing job")
     # without a workspace there are no job flags: the head itself is sent to the online form late (flag 0), same numbers
     flags2, kmax2, krad2, centre2 = flags_rows_anchored(E, q, k, H)
     out2, _ = run_rows_anchored(E, qd, kd, vt, H, flags2, kmax2, centre2, krad2, balanced=False)
     assert flags2.tolist() == [0, 1], flags2
     close(out2, ref, ulps=4, atol=5e-3, what="anchored offsets, head-level fallback")
+    R.close(out2, P.MARGIN_ROWS, "anchored offsets, head-level fallback")
     # a head whose jobs kept falling back is not anchored again
     prefer = torch.tensor([1, 0], dtype=torch.int32, device="cuda")
     flags3, kmax3, _, _ = flags_rows_anchored(E, q, k, H, prefer=prefer)
@@ -819,8 +871,10 @@ def test_config2_size_anchored_offsets_sampled_rows_vs_oracle(E):
     out, anchor = run_rows_anchored(E, q, kc, vt, H, flags, kmax, centre, krad, balanced=True)
     assert flags.tolist() == [1] * H, flags                                     # no head left the fixed form
     rows = torch.tensor([0, 1, 31, 255, 256, 4097, 23808, 40000, 47104, 47615 - 64, 47615])   # incl. rows of the split tail jobs
-    ref = O.sdpa(qf[rows].cpu(), kf.cpu(), v.float().cpu().reshape(N, H, 64), "bf16", None, base2=True)
+    R = P.AttentionRef(qf[rows].cpu(), kf.cpu(), v.float().cpu().reshape(N, H, 64), base2=True)
+    ref = R.bf16
     close(out[rows], ref, ulps=4, atol=5e-3, what="config-2 sampled rows, anchored offsets")
+    R.close(out[rows], P.MARGIN_ROWS, "config-2 sampled rows, anchored offsets")
     smax = torch.stack([(qf[rows, h] @ kf[:, h].t()).amax(-1) for h in range(H)]).cpu()   # the rows' true maxima: inside the exact range
     assert (smax - anchor[:, rows].cpu() < 112).all() and (smax - anchor[:, rows].cpu() > -81).all()
     oc, _ = run_rows_anchored(E, q, kc, torch.full_like(vt, 0.75), H, flags, kmax, centre, krad, balanced=True)

@@ -113,7 +113,8 @@ def test_conv3d_four_wave_kernel(vae, Cin, Cout, up, dims):
         tgt = bfr(want + resid) if use_res else want
         err = (out.float().cpu() - tgt).abs()
         tol = 2.0 ** -6 * tgt.abs().clamp(min=1.0) + (2.0 ** -7 * want.abs() if use_res else 0)   # + a 1-ulp flip of the inner rounding
-        assert not (err > tol).any(), (Cin, Cout, up, use_res, float(err.max()), int((err > tol).sum()))
+        assert torch.isfinite(out.float()).all(), (Cin, Cout, up, use_res)
+        assert (err <= tol).all(), (Cin, Cout, up, use_res, float(err.max()), int((err > tol).sum()))
         again = out.clone()
         E.check(E.lib().k5_conv3d_bf16(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), out.data_ptr(), Ts, Hs, Ws, Cin, Cout, up_t, up_s,
                                        Cout, rd.data_ptr() if use_res else None, Cout, E.stream_ptr()))
@@ -142,7 +143,8 @@ def test_conv3d_three_output_channels(vae, Cin, dims):
                                    E.stream_ptr()))
     torch.cuda.synchronize()
     err = (out.float().cpu() - want).abs()
-    assert not (err > 2.0 ** -6 * want.abs().clamp(min=1.0)).any(), float(err.max())
+    assert torch.isfinite(out.float()).all(), int((~torch.isfinite(out.float())).sum())      # the buffer was pre-filled with NaN: every row written
+    assert (err <= 2.0 ** -6 * want.abs().clamp(min=1.0)).all(), float(err.max())
 
 
 @pytest.mark.parametrize("M,C,G", [(90, 64, 16), (1000, 128, 16), (3000, 512, 32), (77, 256, 32)])
@@ -212,7 +214,7 @@ def test_mid_block_attention_kernel_c512(S, hw):
     assert torch.isfinite(out.float()).all()
     err = (out.float() - ref).abs()
     tol = 2.0 ** -6 * ref.abs() + 6e-3         # bf16 probabilities and outputs: two roundings on top of the fp32 reference
-    assert not (err > tol).any(), (float(err.max()), int((err > tol).sum()))
+    assert (err <= tol).all(), (float(err.max()), int((err > tol).sum()))
 
 
 def test_decode_tile_vs_oracle(vae):
@@ -568,7 +570,8 @@ def test_conv_statistics_feed_groupnorm_vs_oracle(Cin, Cout, dims, up, use_res):
     assert torch.isfinite(qs).all()
     err = (out.float().cpu() - want).abs()
     tol = 2.0 ** -6 * want.abs().clamp(min=1.0) + (2.0 ** -7 * want.abs() if use_res else 0)
-    assert not (err > tol).any(), (float(err.max()), int((err > tol).sum()))
+    assert torch.isfinite(out.float()).all()
+    assert (err <= tol).all(), (float(err.max()), int((err > tol).sum()))
     # the statistics are those of the STORED tensor: fold them on the host and compare with the tensor's own sums
     q = qs.view(-1, Cout // 4, 2).double().sum(0).cpu()                                       # [Cout / 4][sum, sum of squares]
     o64 = out.double().cpu().view(M, Cout // 4, 4)
@@ -590,7 +593,8 @@ def test_conv_statistics_feed_groupnorm_vs_oracle(Cin, Cout, dims, up, use_res):
         # conv outputs differ from the oracle's by a bf16 ulp here and there (2^-8 relative), amplified by gamma / sigma ~ 1.2
         # plus one bf16 ulp of the conv output itself (2^-8 |x| each way) through the norm's gain gamma / sigma (<= 2 here)
         t = 2.0 ** -6 * ref.abs().clamp(min=1.0) + 2.0 ** -6 * want.abs()
-        assert not (e > t).any(), (silu, float(e.max()), int((e > t).sum()))
+        assert torch.isfinite(y.float()).all(), silu
+        assert (e <= t).all(), (silu, float(e.max()), int((e > t).sum()))
         d = (y.float() - y2.float()).abs()
         assert d.max().item() <= 2.0 ** -7 * max(1.0, y2.float().abs().max().item()) and (d > 0).float().mean().item() < 2e-3, \
             (float(d.max()), float((d > 0).float().mean()))     # same tensor, statistics summed in another order
