@@ -272,6 +272,15 @@ int k5_unpatchify_bf16(const void* x, void* out, int T, int Hp, int Wp, int C, i
 /* CFG combine + Euler, generation_utils.py:74-76,128.  v_uncond NULL => no guidance. */
 int k5_cfg_euler(float* img, const void* v_cond, const void* v_uncond, float w, float dt, int64_t n,
                  void* stream);
+/* LoRA merge, in place on a row-major matrix (added under ABI 11, as the MagCache calibration exports were): W'[n][k] = W[n][k] + scale *
+ * sum_r B[n][r] A[r][k].  W [rows][ld] (cols <= ld) of w_dtype K5_BF16 or K5_F32;
+ * A [R][cols], B [rows][R], each K5_F32 / K5_BF16 / K5_F16, device pointers, converted to fp32 on load; 1 <= R <= 256.  The arithmetic is
+ * fixed: acc = fma(B[n][r], A[r][k], acc) for r = 0 .. R-1 from acc = 0, then fma(scale, acc, W[n][k]), both in float64 (an fp32 chain misses the
+ * bf16 neighbours of the exact value where W and the update cancel), rounded to fp32 and, for a bf16 W, from there to bf16 (nearest-even).  Columns cols .. ld-1 are
+ * neither read nor written; scale == 0 launches nothing.  Stands where a front end would merge `W + scale * (B @ A)` on the host before
+ * load_state_dict (the reference has no adapter code of its own). */
+int k5_lora_merge(void* W, int w_dtype, int rows, int cols, int ld, const void* A, int a_dtype, const void* B, int b_dtype, int R,
+                  float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Engine: DiffusionTransformer3D (kandinsky/models/dit.py:82-181) + sampler loop
@@ -548,6 +557,25 @@ int k5_quant_rows_fp8(const void* x_bf16, void* out_fp8, float* scale, int rows,
  * GEMMs run on the four-wave e4m3 kernel (gemm_fp8.hip, round 4).  The sequence-parallel schedules keep the out projection in bf16 and the Ulysses
  * schedule also the q | k | V^T projections: k5_dit_get_option(dit, "fp8_effective") returns the mask that is in effect on the handle's path. */
 int k5_dit_set_fp8(k5_dit* dit, int enabled);
+
+/* LoRA adapters on a finalized handle (added under ABI 11): merged in place into the packed weights, and undone.
+ * k5_dit_add_lora: `key` is a state_dict weight key with a rank-2 tensor; B is [rows][R] and A is [R][cols] for that key's
+ * [rows][cols], host or device pointers of dtype K5_F32 / K5_BF16 / K5_F16.  The packed buffer the key went into receives k5_lora_merge:
+ * self-attention to_query / to_key = rows 0..D-1 / D..2D-1 of the fused q|k buffer; cross-attention to_key / to_value = that block's rows of
+ * the stacked buffers; visual_embeddings.in_layer with its padded leading dimension; time_embeddings.* and every *modulation.out_layer in
+ * fp32 (no rounding), the latter at their rows of the stacked modulation matrix.  The first merge into a matrix saves its packed bits in a
+ * device backup; later calls merge onto the current bits, one rounding per call, in call order.
+ * k5_dit_clear_lora copies every backup back and frees it: the handle then gives the bits it gave before the first k5_dit_add_lora.
+ * k5_dit_lora_state: matrices with a live backup and the bytes the backups hold.
+ * add and clear run on the null stream and end with a device synchronise (a one-time operation, as finalize); no pointer moves, so a captured
+ * step stays valid.  They also drop what was computed from the old weights: the text prologue cache, the softmax-form memory, the MagCache
+ * counter and residuals (and a calibration's), and they re-make the e4m3 copy and scales of a touched matrix that has one (k5_dit_set_fp8).
+ * Handles of a sequence-parallel group or a CFG pair are accepted: weights are replicated, every rank makes the same calls.
+ * Refused with a message and nothing enqueued: before finalize K5_ERR_STATE; unknown key K5_ERR_KEY; a bias or norm key K5_ERR_UNSUPPORTED;
+ * R outside 1..256, a bad dtype or a null pointer K5_ERR_ARG. */
+int k5_dit_add_lora(k5_dit* dit, const char* key, const void* A, int a_dtype, const void* B, int b_dtype, int R, float scale);
+int k5_dit_clear_lora(k5_dit* dit);
+int k5_dit_lora_state(k5_dit* dit, int* matrices_touched, long long* backup_bytes);
 
 /* k5_sample replays ONE hipGraph-captured sampler step (forwards + CFG/Euler, per-step scalars read from device tables at a
  * device-side step counter) instead of launching ~500 kernels per step from the host; results are bit-identical.  Ignored

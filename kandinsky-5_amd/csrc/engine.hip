@@ -7,6 +7,7 @@
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <map>
@@ -453,6 +454,11 @@ struct k5_dit {
     DevBuf table, part;                            // [2 * num_steps][4] | per-workgroup partials of the pass
     hipStream_t last_stream = nullptr;
   } cal;
+
+  // LoRA adapters merged into the packed weights (k5_dit_add_lora): the packed bits of every touched matrix as they were before the first
+  // merge, keyed by the matrix's address (a region of a fused / stacked buffer counts as its own matrix); k5_dit_clear_lora copies them back
+  struct LoraBackup { DevBuf copy; size_t bytes = 0; int vblock = -1, f8 = 0; };   // f8: which e4m3 copy of visual block `vblock` mirrors it (lora_requant)
+  std::map<void*, LoraBackup> lora_backup;
 
   // profiling
   int profiling = 0;                               // 0 off, 1 every kernel family, 2 only the visual self-attention (the roofline kernel)
@@ -2350,6 +2356,159 @@ extern "C" int k5_dit_set_fp8(k5_dit* d, int enabled) {
   HIPCHK(hipDeviceSynchronize());
   d->use_fp8 = (enabled & 1) != 0;
   d->fp8_mask = enabled;
+  return K5_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// LoRA adapters: merge into the packed weights in place, and undo (include/k5.h)
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct LoraTarget { void* p = nullptr; bool bf16 = true; size_t rows = 0, cols = 0, ld = 0; int vblock = -1, f8 = 0; };
+enum { LORA_F8_NONE = 0, LORA_F8_W1, LORA_F8_W2, LORA_F8_QK, LORA_F8_V, LORA_F8_O };
+
+// state_dict weight key -> the packed matrix it went into (k5_dit_finalize / pack_attn).  K5_ERR_KEY: not a key of this layout;
+// K5_ERR_UNSUPPORTED: a rank-1 tensor (bias, norm)
+int lora_target(k5_dit* d, const std::string& key, LoraTarget& t) {
+  bool known = false;
+  for (auto& e : d->expected) if (e == key) { known = true; break; }
+  if (!known) { k5_set_error("k5_dit_add_lora: %s is not a state_dict key of this model", key.c_str()); return K5_ERR_KEY; }
+  const std::string w = ".weight";
+  const bool is_weight = key.size() > w.size() && key.compare(key.size() - w.size(), w.size(), w) == 0;
+  if (!is_weight || key.find("norm.weight") != std::string::npos) {
+    k5_set_error("k5_dit_add_lora: %s is a rank-1 tensor (bias / norm): LoRA applies to linear weights only", key.c_str()); return K5_ERR_UNSUPPORTED;
+  }
+  const size_t D = d->D, FF = d->FF, TD = d->TD;
+  auto set = [&](void* p, bool bf16, size_t rows, size_t cols, size_t ld, int vb = -1, int f8 = LORA_F8_NONE) {
+    t.p = p; t.bf16 = bf16; t.rows = rows; t.cols = cols; t.ld = ld; t.vblock = vb; t.f8 = f8;
+  };
+  auto mod = [&](size_t off, size_t rows) { set(d->mod_w.as<float>() + off * TD, false, rows, TD, TD); };
+  if (key == "time_embeddings.in_layer.weight") set(d->time_w1.p, false, TD, D, D);
+  else if (key == "time_embeddings.out_layer.weight") set(d->time_w2.p, false, TD, TD, TD);
+  else if (key == "text_embeddings.in_layer.weight") set(d->text_w.p, true, D, d->cfg.in_text_dim, d->cfg.in_text_dim);
+  else if (key == "pooled_text_embeddings.in_layer.weight") set(d->pool_w.p, true, TD, d->cfg.in_text_dim2, d->cfg.in_text_dim2);
+  else if (key == "visual_embeddings.in_layer.weight") set(d->vis_w.p, true, D, d->Kvis, d->KvisPad);
+  else if (key == "out_layer.out_layer.weight") set(d->out_w.p, true, d->Fout, D, D);
+  else if (key == "out_layer.modulation.out_layer.weight") mod(d->out_mod_off, 2 * D);
+  else {
+    const bool text = key.rfind("text_transformer_blocks.", 0) == 0, vis = key.rfind("visual_transformer_blocks.", 0) == 0;
+    const size_t pre = text ? strlen("text_transformer_blocks.") : strlen("visual_transformer_blocks.");
+    const size_t dot = (text || vis) ? key.find('.', pre) : std::string::npos;
+    if (dot == std::string::npos) { k5_set_error("k5_dit_add_lora: no packed matrix for %s", key.c_str()); return K5_ERR_KEY; }
+    const int i = atoi(key.substr(pre, dot - pre).c_str());
+    auto& blocks = text ? d->tblocks : d->vblocks;
+    if (i < 0 || (size_t)i >= blocks.size()) { k5_set_error("k5_dit_add_lora: no packed matrix for %s", key.c_str()); return K5_ERR_KEY; }
+    BlockW& b = blocks[i];
+    const std::string rest = key.substr(dot + 1);
+    const int vb = vis ? i : -1;
+    if (rest == "text_modulation.out_layer.weight") mod(b.mod_off, 6 * D);
+    else if (rest == "visual_modulation.out_layer.weight") mod(b.mod_off, 9 * D);
+    else if (rest == "self_attention.to_query.weight") set(b.self_attn.wqk.p, true, D, D, D, vb, LORA_F8_QK);
+    else if (rest == "self_attention.to_key.weight") set(b.self_attn.wqk.as<bf16_t>() + D * D, true, D, D, D, vb, LORA_F8_QK);
+    else if (rest == "self_attention.to_value.weight") set(b.self_attn.wv.p, true, D, D, D, vb, LORA_F8_V);
+    else if (rest == "self_attention.out_layer.weight") set(b.self_attn.wo.p, true, D, D, D, vb, LORA_F8_O);
+    else if (rest == "cross_attention.to_query.weight") set(b.cross_attn.wq.p, true, D, D, D);
+    else if (rest == "cross_attention.to_key.weight") set(b.cross_attn.wk.p, true, D, D, D);      // a view into cx_wk_all
+    else if (rest == "cross_attention.to_value.weight") set(b.cross_attn.wv.p, true, D, D, D);    // a view into cx_wv_all
+    else if (rest == "cross_attention.out_layer.weight") set(b.cross_attn.wo.p, true, D, D, D);
+    else if (rest == "feed_forward.in_layer.weight") set(b.w1.p, true, FF, D, D, vb, LORA_F8_W1);
+    else if (rest == "feed_forward.out_layer.weight") set(b.w2.p, true, D, FF, FF, vb, LORA_F8_W2);
+    else { k5_set_error("k5_dit_add_lora: no packed matrix for %s", key.c_str()); return K5_ERR_KEY; }
+  }
+  if (!t.p) { k5_set_error("k5_dit_add_lora: internal: %s is not packed", key.c_str()); return K5_ERR_STATE; }
+  return K5_OK;
+}
+
+// the e4m3 copy and scales of a visual block's matrix, where k5_dit_set_fp8 made one: quantised again from the current bf16 bits (per output
+// channel, so rows an adapter did not touch come out as they were)
+int lora_requant(k5_dit* d, int vblock, int f8) {
+  if (vblock < 0 || f8 == LORA_F8_NONE) return K5_OK;
+  BlockW& b = d->vblocks[vblock];
+  const size_t D = d->D, FF = d->FF;
+  auto quant = [&](const DevBuf& w, DevBuf& w8, DevBuf& sc, size_t rows, size_t K) -> int {
+    if (!w8.p) return K5_OK;
+    return k5_launch_quant_rows_fp8(w.p, w8.p, sc.as<float>(), (int)rows, (int)K, (int)K, (int)K, nullptr);
+  };
+  switch (f8) {
+    case LORA_F8_W1: return quant(b.w1, b.w1_f8, b.s1_f8, FF, D);
+    case LORA_F8_W2: return quant(b.w2, b.w2_f8, b.s2_f8, D, FF);
+    case LORA_F8_QK: return quant(b.self_attn.wqk, b.self_attn.wqk8, b.self_attn.sqk, 2 * D, D);
+    case LORA_F8_V: return quant(b.self_attn.wv, b.self_attn.wv8, b.self_attn.sv, D, D);
+    case LORA_F8_O: return quant(b.self_attn.wo, b.self_attn.wo8, b.self_attn.so, D, D);
+  }
+  return K5_OK;
+}
+
+// everything the handle keeps that was computed from the weights as they were
+int lora_drop_derived(k5_dit* d) {
+  d->text_cache[0].valid = d->text_cache[1].valid = false;
+  K5CHK(reset_attn_pref(d, nullptr));
+  auto& mg = d->mag;
+  mg.cnt = mg.first;
+  for (int j = 0; j < 2; ++j) { mg.acc_ratio[j] = 1.0; mg.acc_err[j] = 0; mg.acc_steps[j] = 0; mg.res_elems[j] = 0; }
+  auto& cl = d->cal;
+  if (cl.on) {
+    cl.cnt = 0; cl.runs = 0;
+    for (int j = 0; j < 2; ++j) { cl.prev[j] = 0; cl.res_elems[j] = 0; }
+    HIPCHK(hipMemsetAsync(cl.table.p, 0, (size_t)2 * cl.num_steps * 4 * sizeof(double), nullptr));
+  }
+  return K5_OK;
+}
+}  // namespace
+
+extern "C" int k5_dit_add_lora(k5_dit* d, const char* key, const void* A, int a_dtype, const void* B, int b_dtype, int R, float scale) {
+  g_err[0] = 0;
+  if (!d) { k5_set_error("k5_dit_add_lora: null handle"); return K5_ERR_ARG; }
+  if (!d->finalized) { k5_set_error("k5_dit_add_lora before k5_dit_finalize"); return K5_ERR_STATE; }
+  if (!key || !A || !B) { k5_set_error("k5_dit_add_lora: null key or factor pointer"); return K5_ERR_ARG; }
+  if (R < 1 || R > 256) { k5_set_error("k5_dit_add_lora: rank %d outside 1..256", R); return K5_ERR_ARG; }
+  for (int dt : {a_dtype, b_dtype})
+    if (dt != K5_F32 && dt != K5_BF16 && dt != K5_F16) { k5_set_error("k5_dit_add_lora: factor dtype %d is none of f32 / bf16 / f16", dt); return K5_ERR_ARG; }
+  LoraTarget t;
+  K5CHK(lora_target(d, key, t));
+  HIPCHK(hipDeviceSynchronize());   // forwards still in flight on other streams read the weights
+  const size_t es = t.bf16 ? 2 : 4, bytes = t.rows * t.ld * es;
+  if (!d->lora_backup.count(t.p)) {
+    k5_dit::LoraBackup bk;
+    K5CHK(bk.copy.ensure(bytes));
+    HIPCHK(hipMemcpyAsync(bk.copy.p, t.p, bytes, hipMemcpyDeviceToDevice, nullptr));
+    bk.bytes = bytes; bk.vblock = t.vblock; bk.f8 = t.f8;
+    d->lora_backup[t.p] = std::move(bk);
+  }
+  // the factors: device copies of whatever memory they are in (hipMemcpyDefault, as k5_dit_load_tensor)
+  DevBuf fa, fb;
+  const size_t abytes = (size_t)R * t.cols * (a_dtype == K5_F32 ? 4 : 2), bbytes = t.rows * (size_t)R * (b_dtype == K5_F32 ? 4 : 2);
+  K5CHK(fa.ensure(abytes)); K5CHK(fb.ensure(bbytes));
+  HIPCHK(hipMemcpy(fa.p, A, abytes, hipMemcpyDefault));
+  HIPCHK(hipMemcpy(fb.p, B, bbytes, hipMemcpyDefault));
+  K5CHK(k5_launch_lora_merge(t.p, t.bf16 ? K5_BF16 : K5_F32, (int)t.rows, (int)t.cols, (int)t.ld, fa.p, a_dtype, fb.p, b_dtype, R, scale, nullptr));
+  K5CHK(lora_requant(d, t.vblock, t.f8));
+  K5CHK(lora_drop_derived(d));
+  HIPCHK(hipDeviceSynchronize());   // fa / fb are freed on return
+  return K5_OK;
+}
+
+extern "C" int k5_dit_clear_lora(k5_dit* d) {
+  g_err[0] = 0;
+  if (!d) { k5_set_error("k5_dit_clear_lora: null handle"); return K5_ERR_ARG; }
+  if (!d->finalized) { k5_set_error("k5_dit_clear_lora before k5_dit_finalize"); return K5_ERR_STATE; }
+  if (d->lora_backup.empty()) return K5_OK;
+  HIPCHK(hipDeviceSynchronize());
+  for (auto& kv : d->lora_backup)
+    HIPCHK(hipMemcpyAsync(kv.first, kv.second.copy.p, kv.second.bytes, hipMemcpyDeviceToDevice, nullptr));
+  for (auto& kv : d->lora_backup) K5CHK(lora_requant(d, kv.second.vblock, kv.second.f8));
+  K5CHK(lora_drop_derived(d));
+  HIPCHK(hipDeviceSynchronize());
+  d->lora_backup.clear();
+  return K5_OK;
+}
+
+extern "C" int k5_dit_lora_state(k5_dit* d, int* matrices_touched, long long* backup_bytes) {
+  g_err[0] = 0;
+  if (!d) { k5_set_error("k5_dit_lora_state: null handle"); return K5_ERR_ARG; }
+  long long bytes = 0;
+  for (auto& kv : d->lora_backup) bytes += (long long)kv.second.bytes;
+  if (matrices_touched) *matrices_touched = (int)d->lora_backup.size();
+  if (backup_bytes) *backup_bytes = bytes;
   return K5_OK;
 }
 

@@ -325,6 +325,11 @@ int k5_magcache_stats_bf16(const void* vis, const void* ori, const void* prev, v
   return ret(k5_launch_magcache_stats(vis, ori, prev, res, sums, ws, 0, rows, D, (hipStream_t)stream), "k5_magcache_stats_bf16");
 }
 
+int k5_lora_merge(void* W, int w_dtype, int rows, int cols, int ld, const void* A, int a_dtype, const void* B, int b_dtype, int R, float scale,
+                  void* stream) {
+  return ret(k5_launch_lora_merge(W, w_dtype, rows, cols, ld, A, a_dtype, B, b_dtype, R, scale, (hipStream_t)stream), "k5_lora_merge");
+}
+
 int k5_gemv_f32(const float* x, const float* W, const float* b, float* y, int N, int K, int silu_in, const float* add,
                 void* stream) {
   return ret(k5_launch_gemv_f32(x, W, b, y, N, K, silu_in, add, (hipStream_t)stream), "k5_gemv_f32");

@@ -180,6 +180,11 @@ int k5_launch_cfg_euler(float* img, const void* v_cond, const void* v_uncond, fl
 int k5_launch_cast_f32_bf16(const float* x, void* out, int64_t n, hipStream_t stream);
 // weight packing: src [rows][cols] (K5_F32 / K5_BF16 / K5_F16, device) -> dst [rows][ld] bf16 (RNE) or fp32, pad columns zeroed
 int k5_launch_pack_matrix(const void* src, int src_dtype, void* dst, int dst_bf16, int64_t rows, int cols, int ld, hipStream_t stream);
+// LoRA merge in place: W[n][k] = W[n][k] + scale * sum_r B[n][r] A[r][k] on a packed [rows][ld] matrix (K5_BF16 or
+// K5_F32), columns cols .. ld - 1 neither read nor written.  A [R][cols], B [rows][R] (K5_F32 / K5_BF16 / K5_F16, device), 1 <= R <= 256.  float64 fma
+// chain over r = 0 .. R - 1, then fma(scale, acc, W), rounded to fp32 and from there to W's type: the bits do not depend on the tiling.  scale == 0 launches nothing.
+int k5_launch_lora_merge(void* W, int w_dtype, int rows, int cols, int ld, const void* A, int a_dtype, const void* B, int b_dtype, int R,
+                         float scale, hipStream_t stream);
 
 // causal_hw > 0: frame-causal scores, tiles wholly at columns >= (row / causal_hw + 1) * causal_hw are skipped (left unwritten)
 int k5_launch_gemm_bf16_f32out(const void* A, const void* W, float* C, int M, int N, int K, int lda, int ldw, int ldc,

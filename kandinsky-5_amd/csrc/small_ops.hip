@@ -888,3 +888,124 @@ int k5_launch_cast_f32_bf16(const float* x, void* out, int64_t n, hipStream_t s)
   hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, (bf16_t*)out, n);
   return done();
 }
+
+namespace {
+// LoRA merge (k5_dit_add_lora, k5_lora_merge): W[n][k] += s * sum_r B[n][r] A[r][k], in place on a packed [rows][ld] matrix.
+// The bits are spelled out so that they depend neither on the tiling nor on -ffp-contract: acc = fma(B[n][r], A[r][k], acc) for r = 0 .. R-1 in
+// that order from acc = 0, then fma(s, acc, W[n][k]), rounded to fp32 and from there to the matrix's type (nearest-even both; the fp32 step can turn a bf16
+// rounding at an exact fp32 tie, 2^-16 of the elements, never past a neighbour).  The chain runs in
+// FLOAT64 (the factors are exact in it; explicit builtins): the same chain in fp32 carries an absolute error of R * 2^-24 * sum|B||A|, and where W and
+// the update cancel (|W'| ~ 1e-6 against terms of 1e-2) that is ten bf16 steps — 2 of 131 072 outputs of a 256 x 512, R = 128 merge then miss
+// both bf16 neighbours of the exact value (measured, and reproduced by an fp32 emulation on the host).  v_fma_f64 runs at half the fp32 VALU rate
+// on gfx950, and the pass is dominated by reading and writing W either way.  No MFMA: a bf16 MFMA would round the factors.
+// A workgroup owns 64 rows x 128 columns; a thread 4 rows x 8 columns; the factors come through LDS as fp32 in slabs of 32 ranks.
+//   As[r][slot]: column k of the tile sits at slot ((k >> 2) & 1) * 64 + (k >> 3) * 4 + (k & 3), so the two 16-byte reads of a thread's
+//                8 columns are each contiguous over the 16 lanes that share a row group (a whole 256-byte bank row: no conflict)
+//   Bs[r][n]:    transposed, 4 consecutive rows per 16-byte read (4 distinct addresses per wave, broadcast); row stride 68 floats keeps
+//                the reads 16-byte aligned and spreads the transposing writes over 8 banks
+constexpr int LM_ROWS = 64, LM_COLS = 128, LM_RC = 32, LM_BLD = 68;
+
+K5_DEV float lora_factor(const void* p, int dt, int64_t i) {
+  if (dt == K5_F32) return reinterpret_cast<const float*>(p)[i];
+  if (dt == K5_BF16) return __uint_as_float((uint32_t)reinterpret_cast<const uint16_t*>(p)[i] << 16);
+  return (float)reinterpret_cast<const _Float16*>(p)[i];
+}
+
+template <typename T>   // T = bf16_t or float: the packed matrix
+__global__ __launch_bounds__(256) void lora_merge_kernel(T* W, int rows, int cols, int64_t ld, const void* __restrict__ A, int adt,
+                                                         const void* __restrict__ B, int bdt, int R, float s, int tiles_n) {
+  __shared__ __attribute__((aligned(16))) float As[LM_RC][LM_COLS];
+  __shared__ __attribute__((aligned(16))) float Bs[LM_RC][LM_BLD];
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+  const int tm = (int)blockIdx.x / tiles_n, tn = (int)blockIdx.x - tm * tiles_n;
+  const int row0 = tm * LM_ROWS, col0 = tn * LM_COLS;
+  double acc[4][8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[i][j] = 0.0;
+  for (int r0 = 0; r0 < R; r0 += LM_RC) {
+    const int rc = R - r0 < LM_RC ? R - r0 : LM_RC;
+    if (r0) __syncthreads();
+    for (int i = tid; i < LM_RC * LM_COLS; i += 256) {
+      const int r = i >> 7, k = i & (LM_COLS - 1);
+      float v = 0.f;
+      if (r < rc && col0 + k < cols) v = lora_factor(A, adt, (int64_t)(r0 + r) * cols + col0 + k);
+      As[r][((k >> 2) & 1) * 64 + (k >> 3) * 4 + (k & 3)] = v;
+    }
+    for (int i = tid; i < LM_ROWS * LM_RC; i += 256) {
+      const int n = i >> 5, r = i & (LM_RC - 1);
+      float v = 0.f;
+      if (r < rc && row0 + n < rows) v = lora_factor(B, bdt, (int64_t)(row0 + n) * R + r0 + r);
+      Bs[r][n] = v;
+    }
+    __syncthreads();
+    // exactly rc ranks: a padded rank would add a signed zero to the chain
+#pragma unroll 4
+    for (int r = 0; r < rc; ++r) {
+      const f32x4 a0 = *reinterpret_cast<const f32x4*>(&As[r][tx * 4]);
+      const f32x4 a1 = *reinterpret_cast<const f32x4*>(&As[r][64 + tx * 4]);
+      const f32x4 b = *reinterpret_cast<const f32x4*>(&Bs[r][ty * 4]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          acc[i][j] = __builtin_fma((double)b[i], (double)a0[j], acc[i][j]);
+          acc[i][4 + j] = __builtin_fma((double)b[i], (double)a1[j], acc[i][4 + j]);
+        }
+    }
+  }
+  const int c = col0 + tx * 8;
+  const double sd = (double)s;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = row0 + ty * 4 + i;
+    if (row >= rows || c >= cols) continue;
+    T* p = W + (int64_t)row * ld + c;
+    if (c + 8 <= cols && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {   // 16-byte accesses where the row start allows them
+      if constexpr (sizeof(T) == 2) {
+        const u32x4 w = *reinterpret_cast<const u32x4*>(p);
+        u32x4 o;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          o[q] = pack_bf16x2((float)__builtin_fma(sd, acc[i][2 * q], (double)__uint_as_float(w[q] << 16)),
+                             (float)__builtin_fma(sd, acc[i][2 * q + 1], (double)__uint_as_float(w[q] & 0xffff0000u)));
+        *reinterpret_cast<u32x4*>(p) = o;
+      } else {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          f32x4 w = *reinterpret_cast<const f32x4*>(p + 4 * h);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) w[j] = (float)__builtin_fma(sd, acc[i][4 * h + j], (double)w[j]);
+          *reinterpret_cast<f32x4*>(p + 4 * h) = w;
+        }
+      }
+    } else {   // ragged edge, or a row that does not start on 16 bytes: element by element, never past column cols - 1
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (c + j < cols) p[j] = (T)(float)__builtin_fma(sd, acc[i][j], (double)(float)p[j]);
+    }
+  }
+}
+}  // namespace
+
+int k5_launch_lora_merge(void* W, int w_dtype, int rows, int cols, int ld, const void* A, int a_dtype, const void* B, int b_dtype, int R,
+                         float scale, hipStream_t s) {
+  if (!W || !A || !B || rows <= 0 || cols <= 0 || ld < cols || R < 1 || R > 256) return K5_ERR_ARG;
+  if (w_dtype != K5_F32 && w_dtype != K5_BF16) return K5_ERR_ARG;
+  for (int dt : {a_dtype, b_dtype})
+    if (dt != K5_F32 && dt != K5_BF16 && dt != K5_F16) return K5_ERR_ARG;
+  if (reinterpret_cast<uintptr_t>(W) & (w_dtype == K5_F32 ? 3 : 1)) return K5_ERR_ALIGN;
+  if ((reinterpret_cast<uintptr_t>(A) & (a_dtype == K5_F32 ? 3 : 1)) || (reinterpret_cast<uintptr_t>(B) & (b_dtype == K5_F32 ? 3 : 1))) return K5_ERR_ALIGN;
+  if (scale == 0.f) return K5_OK;   // nothing to add: nothing launched
+  const int tiles_n = (cols + LM_COLS - 1) / LM_COLS;
+  const int64_t blocks = (int64_t)((rows + LM_ROWS - 1) / LM_ROWS) * tiles_n;
+  if (blocks > 0x7fffffff) return K5_ERR_ARG;
+  if (w_dtype == K5_BF16)
+    hipLaunchKernelGGL(lora_merge_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, s, (bf16_t*)W, rows, cols, (int64_t)ld, A, a_dtype, B,
+                       b_dtype, R, scale, tiles_n);
+  else
+    hipLaunchKernelGGL(lora_merge_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, (float*)W, rows, cols, (int64_t)ld, A, a_dtype, B,
+                       b_dtype, R, scale, tiles_n);
+  return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
+}

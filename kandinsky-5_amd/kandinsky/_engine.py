@@ -165,6 +165,10 @@ SYMBOLS = {
     "k5_vae_decode_tile_strided": (_I, [_P, _P, _I64, _I, _I, _I, _P, _P]),
     "k5_dit_set_graph": (_I, [_P, _I]),
     "k5_dit_set_fp8": (_I, [_P, _I]),
+    "k5_lora_merge": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _F, _P]),
+    "k5_dit_add_lora": (_I, [_P, C.c_char_p, _P, _I, _P, _I, _I, _F]),
+    "k5_dit_clear_lora": (_I, [_P]),
+    "k5_dit_lora_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong)]),
     "k5_dit_set_magcache": (_I, [_P, C.POINTER(C.c_double), _I, _I, C.c_double, _I, C.c_double]),
     "k5_dit_magcache_calls": (_I, [_P, _I, _I]),
     "k5_dit_magcache_state": (_I, [_P, C.POINTER(_I), C.POINTER(_I64), C.POINTER(_I64)]),
@@ -200,7 +204,7 @@ def lib() -> C.CDLL:
     for name, (res, args) in SYMBOLS.items():
         try:
             fn = getattr(L, name)
-        except AttributeError as e:   # a libk5.so of the same ABI number from before an added export (the MagCache calibration ones)
+        except AttributeError as e:   # a libk5.so of the same ABI number from before an added export (the MagCache calibration and LoRA ones)
             raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it with `python kandinsky-5_amd/build.py`") from e
         fn.restype = res
         fn.argtypes = args
@@ -365,6 +369,18 @@ def magcache_stats(vis, ori, prev=None, out=None):
     check(lib().k5_magcache_stats_bf16(ptr(vis), ptr(ori), ptr(prev), ptr(res), ptr(sums), vis.shape[0], vis.shape[1],
                                        stream_ptr(vis.device)), "k5_magcache_stats_bf16")
     return res, sums
+
+
+def lora_merge_(w, a, b, scale, cols=None):
+    """In place: w[:, :cols] += scale * (b @ a) (k5_lora_merge).  w bf16 or fp32 [rows][ld] with a unit inner stride, a [R][cols], b [rows][R],
+    each f32 / bf16 / f16 and contiguous; fixed float64 fma order, one rounding to w's dtype."""
+    _need_cuda(w, a, b)
+    cols = a.shape[1] if cols is None else int(cols)
+    if w.stride(1) != 1 or not a.is_contiguous() or not b.is_contiguous():
+        raise ValueError("lora_merge_: w needs a unit inner stride, a and b must be contiguous")
+    check(lib().k5_lora_merge(ptr(w), k5_dtype(w), w.shape[0], cols, w.stride(0), ptr(a), k5_dtype(a), ptr(b), k5_dtype(b), a.shape[0],
+                              float(scale), stream_ptr(w.device)), "k5_lora_merge")
+    return w
 
 
 def gemv_f32(x, w, b=None, silu_in=False, add=None):

@@ -112,6 +112,8 @@ class DiffusionTransformer3D(nn.Module):
         self._sp = None              # (rank, world) once a communicator lives on the handle
         self._cfg_pair = None        # CFG-parallel branch (0 / 1) once the pair communicator lives on the handle
         self._settings = {"fp8": False, "graph": False, "options": {}}   # re-applied when the engine is rebuilt
+        self._lora = []              # (entries, strength) merged into the ENGINE's packed weights: re-added when the engine is rebuilt
+        self._lora_saved = {}        # parameters as they were before a merge done in torch (no engine yet): key -> tensor
 
     # ---------------------------------------------------------------- engine lifetime
     def _destroy_engine(self, force=False):
@@ -176,6 +178,8 @@ class DiffusionTransformer3D(nn.Module):
         for k, v in st["options"].items():
             if k != "emulate_world":
                 E.check(E.lib().k5_dit_set_option(self._handle, k.encode(), int(v)), f"k5_dit_set_option({k})")
+        for entries, strength in getattr(self, "_lora", []):   # the rebuilt engine packed the parameters, which an engine-side merge never touched
+            self._engine_add_lora(entries, strength)
         if getattr(self, "mag_ratios", None) is not None or getattr(self, "_magcache_calibrate", None) is not None:   # set before the weights were loaded / the handle rebuilt
             from ..magcache_utils import _apply
             _apply(self)
@@ -213,6 +217,7 @@ class DiffusionTransformer3D(nn.Module):
     def load_state_dict(self, state_dict, strict=True, assign=False):
         out = super().load_state_dict(state_dict, strict=strict, assign=assign)
         self._destroy_engine()
+        self._lora, self._lora_saved = [], {}   # adapters belonged to the weights that were just replaced
         return out
 
     def _apply(self, fn, *a, **k):
@@ -585,6 +590,71 @@ class DiffusionTransformer3D(nn.Module):
         self._settings["fp8"] = mask
         return self
 
+    # ---------------------------------------------------------------- LoRA adapters
+    def _engine_add_lora(self, entries, strength):
+        from ..lora import lora_scale
+        with torch.cuda.device(self._handle_device):
+            for key, (A, B, alpha) in entries.items():
+                A, B = [t.detach() if t.dtype in E._DT else t.detach().float() for t in (A, B)]
+                A, B = A.contiguous(), B.contiguous()
+                E.check(E.lib().k5_dit_add_lora(self._handle, key.encode(), A.data_ptr(), E.k5_dtype(A), B.data_ptr(), E.k5_dtype(B),
+                                                int(A.shape[0]), lora_scale(strength, alpha, A.shape[0])), f"k5_dit_add_lora({key})")
+
+    @torch.no_grad()
+    def add_lora(self, adapter, strength=1.0):
+        """Merge a LoRA adapter into the weights: `adapter` is a .safetensors path, a state dict of adapter tensors (peft, diffusers or kohya
+        names, kandinsky/lora.py) or what `load_lora` returned; the scale is strength * alpha / R (strength alone without an alpha).  With the
+        engine built, the packed weights are updated in place (k5_dit_add_lora: no upload, no re-pack; the parameters stay as loaded).  Before
+        the engine exists the same merge is done on the parameters in torch, in fp32, and the engine packs the merged weights when it is
+        built.  Several adapters add up in call order; `clear_lora` undoes them all."""
+        from ..lora import load_lora, lora_scale, merge_torch
+        sd = self.state_dict()
+        entries = adapter if _is_loaded_lora(adapter) else load_lora(adapter, known_keys=sd.keys())
+        for key, (A, B, alpha) in entries.items():
+            if key not in sd:
+                raise KeyError(f"LoRA module {key[:-7]!r}: the model has no {key}")
+            want = tuple(sd[key].shape)
+            if sd[key].dim() != 2 or (B.shape[0], A.shape[1]) != want or not 1 <= A.shape[0] <= 256:
+                raise ValueError(f"LoRA adapter for {key}: A {tuple(A.shape)} / B {tuple(B.shape)} do not fit the weight {want} "
+                                 "(B [out][R], A [R][in], 1 <= R <= 256)")
+        if self._handle is not None:
+            self._engine_add_lora(entries, strength)
+            self._lora.append((entries, float(strength)))
+            return self
+        for key, (A, B, alpha) in entries.items():
+            p = sd[key]
+            if p.is_meta:
+                raise RuntimeError(f"parameter {key} is on the meta device: load a checkpoint first")
+            self._lora_saved.setdefault(key, p.detach().clone())
+            p.copy_(merge_torch(p, A, B, lora_scale(strength, alpha, A.shape[0])))
+        return self
+
+    @torch.no_grad()
+    def clear_lora(self):
+        """Undo every `add_lora`: the engine copies its backups of the packed weights back (k5_dit_clear_lora), parameters merged in torch get
+        their saved values back (an engine packed from them in between is rebuilt on next use)."""
+        if self._handle is not None and self._lora:
+            with torch.cuda.device(self._handle_device):
+                E.check(E.lib().k5_dit_clear_lora(self._handle), "k5_dit_clear_lora")
+        self._lora = []
+        if self._lora_saved:
+            sd = self.state_dict()
+            for key, saved in self._lora_saved.items():
+                sd[key].copy_(saved)
+            self._lora_saved = {}
+            self._destroy_engine()
+        return self
+
+    def lora_state(self):
+        """{"adapters": add_lora calls in effect, "matrices": weights with a saved copy, "backup_bytes": what those copies hold} —
+        the engine's own count (k5_dit_lora_state) plus the parameters saved by a merge in torch."""
+        n, b = C.c_int(0), C.c_longlong(0)
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_lora_state(self._handle, C.byref(n), C.byref(b)), "k5_dit_lora_state")
+        saved = self._lora_saved
+        return {"adapters": len(self._lora) + (1 if saved else 0), "matrices": n.value + len(saved),
+                "backup_bytes": b.value + sum(t.numel() * t.element_size() for t in saved.values())}
+
     def set_graph(self, on=True):
         """sample() replays one hipGraph-captured step (k5_dit_set_graph); bit-identical results"""
         E.check(E.lib().k5_dit_set_graph(self._handle, int(on)))
@@ -602,6 +672,11 @@ class DiffusionTransformer3D(nn.Module):
         ms, n = C.c_double(), C.c_int64()
         E.check(E.lib().k5_dit_get_profile(self._handle, family.encode(), C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+
+def _is_loaded_lora(adapter):
+    """what `kandinsky.lora.load_lora` returns: {engine key: (A, B, alpha)}"""
+    return isinstance(adapter, dict) and all(isinstance(v, tuple) and len(v) == 3 for v in adapter.values()) and len(adapter) > 0
 
 
 def get_dit(conf):

@@ -29,6 +29,17 @@ class Kandinsky5T2VPipeline:
         Delegated to the text embedder wrapper, which owns the HF model."""
         return self.text_embedder.expand_prompt(prompt)
 
+    def set_lora(self, lora=None, lora_scale=1.0):
+        """(extension) The LoRA adapters in effect from now on: every earlier one is removed (`dit.clear_lora()`), then `lora` — a
+        .safetensors path / state dict, or a list of them — is merged with `lora_scale` (one strength, or one per adapter).  None removes
+        them all.  Every rank of a multi-GPU run makes the same call."""
+        from .lora import as_list
+        loras, scales = as_list(lora, lora_scale)
+        self.dit.clear_lora()
+        for adapter, s in zip(loras, scales):
+            self.dit.add_lora(adapter, strength=s)
+        return self
+
     # ------------------------------------------------------------------ helpers of __call__
     def _agree_on(self, value_fn, as_object=False):
         """rank 0 computes `value_fn()`, every rank returns the same value (reference t2v_pipeline.py:108-118,131-141)."""

@@ -26,8 +26,12 @@ def get_T2V_pipeline(
     offload: bool = False,
     magcache: bool = False,
     magcache_ratios=None,
+    lora=None,
+    lora_scale=1.0,
 ) -> Kandinsky5T2VPipeline:
-    """`magcache_ratios` (extension): the MagCache ratio table to use instead of the config's `magcache.mag_ratios` — a list, the dict
+    """`lora` (extension): a LoRA adapter (.safetensors path or state dict; peft, diffusers or kohya names) or a list of them, merged into
+    the DiT's weights with `lora_scale` (one strength, or one per adapter): strength * alpha / R.  `pipe.set_lora(...)` changes them later.
+    `magcache_ratios` (extension): the MagCache ratio table to use instead of the config's `magcache.mag_ratios` — a list, the dict
     `magcache_utils.calibrate_magcache` returns, or the path of a JSON / YAML file holding either.  Only read with `magcache=True`."""
     assert resolution in [512]
     if not isinstance(device_map, dict):
@@ -95,9 +99,12 @@ def get_T2V_pipeline(
         dit = parallelize_dit(dit, local_rank, world_size, device=device_map["dit"], cfg_parallel=cfg_parallel)
         vae.enable_tile_parallel(local_rank, world_size)
 
-    return Kandinsky5T2VPipeline(device_map=device_map, dit=dit, text_embedder=text_embedder, vae=vae,
+    pipe = Kandinsky5T2VPipeline(device_map=device_map, dit=dit, text_embedder=text_embedder, vae=vae,
                                  resolution=resolution, local_dit_rank=local_rank, world_size=world_size, conf=conf,
                                  offload=offload)
+    if lora is not None:
+        pipe.set_lora(lora, lora_scale)
+    return pipe
 
 
 def rank_device_index(local_rank: int) -> int:

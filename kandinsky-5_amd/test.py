@@ -5,6 +5,7 @@ README launch lines keep working against this package:
     python test.py --prompt "the cat turns its head" --image cat.png     # image-to-video: the clip starts from cat.png
     python test.py --config ./configs/config_5s_distil.yaml --calibrate_magcache ratios.json   # measure a MagCache table, then:
     python test.py --config ./configs/config_5s_distil.yaml --magcache --magcache_ratios ratios.json
+    python test.py --prompt "a cat in a blue hat" --lora style.safetensors --lora_scale 0.8   # LoRA adapter(s) merged into the DiT
     PYTHONPATH=. torchrun --nproc-per-node 8 --master-addr 127.0.0.1 test.py --config ./configs/config_10s_sft.yaml ...
 
 Multi-GPU: one process per GPU (LOCAL_RANK / WORLD_SIZE from the launcher); `get_T2V_pipeline` sets up token-sharded
@@ -43,6 +44,11 @@ def build_parser():
     p.add_argument("--magcache_ratios", type=str, default=None, help="MagCache ratio table (JSON / YAML with mag_ratios) used instead of the config's; with --magcache")
     p.add_argument("--calibrate_magcache", type=str, default=None, metavar="OUT.json",
                    help="measure the MagCache ratio table of this checkpoint on the given prompt (and --image) and write it to OUT.json; no video is saved")
+    # absent from the namespace unless given (argparse.SUPPRESS): the flags the reference's CLI has keep their exact set of defaults
+    p.add_argument("--lora", action="append", default=argparse.SUPPRESS, metavar="FILE",
+                   help="LoRA adapter (.safetensors; peft, diffusers or kohya names) merged into the DiT; repeat the flag for several")
+    p.add_argument("--lora_scale", type=float, nargs="+", default=argparse.SUPPRESS, metavar="S",
+                   help="adapter strength: one value for all --lora files or one per file (default 1.0)")
     return p
 
 
@@ -58,7 +64,8 @@ def main(argv=None):
     from kandinsky import get_T2V_pipeline
     pipe = get_T2V_pipeline(device_map={"dit": "cuda:0", "vae": "cuda:0", "text_embedder": "cuda:0"}, conf_path=args.config,
                             offload=args.offload, magcache=args.magcache and not args.calibrate_magcache,
-                            magcache_ratios=args.magcache_ratios)
+                            magcache_ratios=args.magcache_ratios, lora=getattr(args, "lora", None),
+                            lora_scale=getattr(args, "lora_scale", 1.0))
     if args.output_filename is None:
         args.output_filename = "./" + args.prompt.replace(" ", "_") + ".mp4"
     image = None
