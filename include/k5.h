@@ -272,6 +272,15 @@ int k5_unpatchify_bf16(const void* x, void* out, int T, int Hp, int Wp, int C, i
 /* CFG combine + Euler, generation_utils.py:74-76,128.  v_uncond NULL => no guidance. */
 int k5_cfg_euler(float* img, const void* v_cond, const void* v_uncond, float w, float dt, int64_t n,
                  void* stream);
+/* Editing kernels (added under ABI 11, as the LoRA and MagCache calibration exports were).  Flow matching: x_sigma = (1 - sigma) x0 + sigma eps.
+ * k5_edit_renoise: out[i] = rn(rn(a * source[i]) + rn(sigma * noise[i])), a = fp32(1 - sigma), every operation rounded to fp32 on its own
+ * (nothing contracted): the torch expression `a * x0 + sigma * eps` as separate ops, bit for bit; sigma = 1 gives noise, sigma = 0 source. */
+int k5_edit_renoise(float* out, const float* source, const float* noise, float sigma, int64_t n, void* stream);
+/* k5_cfg_euler on cells * C elements (the same bits), then the keep rule with known = renoise(sigma_next): keep_mask fp32 [cells] in
+ * [0, 1], one value per C channels; m == 1 -> known, m == 0 -> the Euler result, otherwise rn(x + rn(m * rn(known - x))).  keep_mask
+ * NULL = k5_cfg_euler (source / noise then unused).  One pass over the latent. */
+int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source, const float* noise,
+                      const float* keep_mask, float sigma_next, int64_t cells, int C, void* stream);
 /* LoRA merge, in place on a row-major matrix (added under ABI 11, as the MagCache calibration exports were): W'[n][k] = W[n][k] + scale *
  * sum_r B[n][r] A[r][k].  W [rows][ld] (cols <= ld) of w_dtype K5_BF16 or K5_F32;
  * A [R][cols], B [rows][R], each K5_F32 / K5_BF16 / K5_F16, device pointers, converted to fp32 on load; 1 <= R <= 256.  The arithmetic is
@@ -347,6 +356,21 @@ int k5_sample(k5_dit* dit, const k5_sample_args* args, void* stream);
  * constant for the call; every forward patchifies cat([latent, visual_cond], -1).  NULL = k5_sample.  K5_ERR_ARG when visual_cond is
  * given to a handle created with visual_cond = 0 or is not 4-byte aligned. */
 int k5_sample_cond(k5_dit* dit, const k5_sample_args* args, const float* visual_cond, void* stream);
+
+/* Video-to-video and masked editing (SDEdit / inpainting; extends the loop of generation_utils.py:102-128, which starts from pure noise only).
+ * The latent starts as renoise(sigmas[0]) of `source` with `noise` (k5_edit_renoise) and after the CFG + Euler update of every step i the
+ * kept region is put back at sigmas[i+1] (k5_cfg_euler_edit), on the device next to the update, so the captured step replays it.  After the
+ * last step sigma = 0 and the cells with keep_mask == 1 hold `source` bit for bit.  A strength below 1 is a shorter schedule: the caller
+ * hands sigmas[first:] and num_steps - first.  edit == NULL is k5_sample_cond.  Otherwise args->latent is OUTPUT ONLY; source, noise
+ * (device fp32 (T,H,W,in_visual_dim)) and keep_mask (device fp32 (T,H,W,1), 1 = keep the source, or NULL) are borrowed and constant for
+ * the call.  K5_ERR_ARG + message, before anything is enqueued: a NULL source or noise, a pointer that is not 4-byte aligned, or source /
+ * noise / keep_mask overlapping latent.  Works in every mode of the loop (eager, captured step, MagCache, rank groups and the CFG pair). */
+typedef struct k5_edit_args {
+  const float* source;
+  const float* noise;
+  const float* keep_mask;   /* device; NULL = no mask */
+} k5_edit_args;
+int k5_sample_edit(k5_dit* dit, const k5_sample_args* args, const float* visual_cond /* nullable */, const k5_edit_args* edit, void* stream);
 
 /* Several samples in one call (generate_sample's shape = (bs, frames, h, w, c), reference generation_utils.py:150): a CONVENIENCE entry point,
  * not a batched kernel path.  The B samples of one (T, H, W) run ONE AFTER ANOTHER on the stream, each as k5_sample_cond on its own slice of

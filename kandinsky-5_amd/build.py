@@ -19,6 +19,9 @@ LIB = os.path.join(LIBDIR, "libk5.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", "/opt/rocm/include", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
          "-fno-slp-vectorize", "-Wno-unused-result", "-Rpass-analysis=kernel-resource-usage"]
+# no -ffp-contract here: hipcc's default (fast-honor-pragmas) is what `#pragma clang fp contract(off)` in small_ops.hip relies on; an explicit
+# -ffp-contract=fast would override the pragma and change the bits of the editing kernels
+assert not any(f.startswith("-ffp-contract") for f in FLAGS)
 RESOURCES = os.path.join(OBJDIR, "resources.json")   # per-kernel VGPR / AGPR / scratch / spill report of the last compile
 
 

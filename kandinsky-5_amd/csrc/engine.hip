@@ -2111,15 +2111,30 @@ extern "C" int k5_dit_forward(k5_dit* d, const k5_forward_args* a, void* out_vel
   return st;
 }
 
-extern "C" int k5_sample_cond(k5_dit* d, const k5_sample_args* a, const float* vcond, void* stream) {
+// The sampler loop behind k5_sample / k5_sample_cond (edit == nullptr: their launches, their bits) and k5_sample_edit.
+static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream, const char* who) {
   g_err[0] = 0;
   if (!d || !a || !a->latent || !a->sigmas || a->num_steps <= 0) return K5_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   const k5_dit_config& c = d->cfg;
-  if (vcond && !c.visual_cond) { k5_set_error("k5_sample_cond: the handle was created with visual_cond = 0"); return K5_ERR_ARG; }
-  if (vcond && (reinterpret_cast<uintptr_t>(vcond) & 3)) { k5_set_error("k5_sample_cond: visual_cond is not 4-byte aligned"); return K5_ERR_ARG; }
+  if (vcond && !c.visual_cond) { k5_set_error("%s: the handle was created with visual_cond = 0", who); return K5_ERR_ARG; }
+  if (vcond && (reinterpret_cast<uintptr_t>(vcond) & 3)) { k5_set_error("%s: visual_cond is not 4-byte aligned", who); return K5_ERR_ARG; }
   const int64_t n = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W * c.out_visual_dim;
   if (c.in_visual_dim != c.out_visual_dim) return K5_ERR_UNSUPPORTED;
+  if (edit) {   // refused before anything is enqueued: the latent is output only and must not be one of the borrowed inputs
+    if (!edit->source || !edit->noise) { k5_set_error("%s: edit needs source and noise", who); return K5_ERR_ARG; }
+    if (n <= 0) { k5_set_error("%s: bad shapes", who); return K5_ERR_ARG; }
+    const uintptr_t l0 = reinterpret_cast<uintptr_t>(a->latent), l1 = l0 + (uintptr_t)n * 4;
+    const struct { const float* p; int64_t elems; const char* name; } in[3] = {
+        {edit->source, n, "source"}, {edit->noise, n, "noise"}, {edit->keep_mask, n / c.out_visual_dim, "keep_mask"}};
+    if (l0 & 3) { k5_set_error("%s: latent is not 4-byte aligned", who); return K5_ERR_ARG; }
+    for (const auto& t : in) {
+      if (!t.p) continue;
+      const uintptr_t p0 = reinterpret_cast<uintptr_t>(t.p), p1 = p0 + (uintptr_t)t.elems * 4;
+      if (p0 & 3) { k5_set_error("%s: edit %s is not 4-byte aligned", who, t.name); return K5_ERR_ARG; }
+      if (p0 < l1 && l0 < p1) { k5_set_error("%s: edit %s overlaps latent (latent is output only)", who, t.name); return K5_ERR_ARG; }
+    }
+  }
   const bool cfg_on = fabsf(a->guidance_weight - 1.0f) > 1e-6f;  // generation_utils.py:63
   const bool pair = cfg_on && d->pair.active();                  // CFG-parallel: one branch here, the other on the paired handle
   if (pair) K5CHK(d->ws_vel_pair.ensure(2 * n * 2));
@@ -2138,12 +2153,13 @@ extern "C" int k5_sample_cond(k5_dit* d, const k5_sample_args* a, const float* v
   // would overwrite the slots baked at capture — ADVICE r5), loopback groups (their collectives are host rendezvous).  The IPC transport IS
   // replayable: its epochs live on the device and the peers' buffers were mapped by the eager first step (ipc_comm.h)
   const bool graph = d->use_graph && !d->mag.on && !d->cal.on && !d->profiling && a->num_steps > 2 && !d->nabla_tap && !d->comm.loop && !d->pair.loop;
-  std::vector<float> host_tab(2 * (size_t)a->num_steps);
+  std::vector<float> host_tab(3 * (size_t)a->num_steps);
   for (int i = 0; i < a->num_steps; ++i) {
     host_tab[i] = a->sigmas[i] * 1000.0f;                        // t * 1000, fp32 (:57)
     host_tab[a->num_steps + i] = a->sigmas[i + 1] - a->sigmas[i];  // torch.diff(timesteps) (:105)
+    host_tab[2 * a->num_steps + i] = a->sigmas[i + 1];             // where the kept region is re-noised to after step i (k5_sample_edit)
   }
-  const float* tvec = nullptr; const float* dtvec = nullptr; int* step = nullptr;
+  const float* tvec = nullptr; const float* dtvec = nullptr; const float* signext = nullptr; int* step = nullptr;
   hipStream_t caller = s;
   if (graph) {
     if (!d->graph_stream) {
@@ -2158,7 +2174,11 @@ extern "C" int k5_sample_cond(k5_dit* d, const k5_sample_args* a, const float* v
     step = reinterpret_cast<int*>(d->ws_sched.as<float>() + host_tab.size());
     HIPCHK(hipMemsetAsync(step, 0, 4, s));
     HIPCHK(hipStreamSynchronize(s));   // host_tab is a local
-    tvec = d->ws_sched.as<float>(); dtvec = tvec + a->num_steps;
+    tvec = d->ws_sched.as<float>(); dtvec = tvec + a->num_steps; signext = dtvec + a->num_steps;
+  }
+  if (edit) {   // the start latent: the source at sigmas[0] everywhere, whatever the mask
+    Scope sc(d, s, "elementwise");
+    K5CHK(k5_launch_edit_renoise(a->latent, edit->source, edit->noise, a->sigmas[0], n, s));
   }
   d->text_cache[0].valid = d->text_cache[1].valid = false;   // the prompt tensors are constant for THIS call only
   K5CHK(reset_attn_pref(d, s));                              // ... and so is what the softmax-form memory of the layers is worth
@@ -2202,7 +2222,10 @@ extern "C" int k5_sample_cond(k5_dit* d, const k5_sample_args* a, const float* v
     }
     {
       Scope sc(d, s, "elementwise");
-      K5CHK(k5_launch_cfg_euler(a->latent, vel_c, cfg_on ? vel_u : nullptr, a->guidance_weight, dt, n, s, dtvec, step));
+      if (!edit) K5CHK(k5_launch_cfg_euler(a->latent, vel_c, cfg_on ? vel_u : nullptr, a->guidance_weight, dt, n, s, dtvec, step));
+      else K5CHK(k5_launch_cfg_euler_edit(a->latent, vel_c, cfg_on ? vel_u : nullptr, a->guidance_weight, dt, edit->source, edit->noise,
+                                          edit->keep_mask, host_tab[2 * a->num_steps + i], n / c.out_visual_dim, c.out_visual_dim, s, dtvec,
+                                          signext, step));
     }
     if (step) K5CHK(k5_launch_step_inc(step, s));
     return K5_OK;
@@ -2235,7 +2258,15 @@ extern "C" int k5_sample_cond(k5_dit* d, const k5_sample_args* a, const float* v
   return status;
 }
 
+extern "C" int k5_sample_cond(k5_dit* d, const k5_sample_args* a, const float* vcond, void* stream) {
+  return sample_impl(d, a, vcond, nullptr, stream, "k5_sample_cond");
+}
+
 extern "C" int k5_sample(k5_dit* d, const k5_sample_args* a, void* stream) { return k5_sample_cond(d, a, nullptr, stream); }
+
+extern "C" int k5_sample_edit(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream) {
+  return sample_impl(d, a, vcond, edit, stream, edit ? "k5_sample_edit" : "k5_sample_cond");
+}
 
 // What k5_sample_many / k5_dit_forward_many refuse before anything is enqueued: handle states whose per-call bookkeeping is not per sample (rank
 // groups exchange per forward, MagCache counts calls, a captured step is per call).

@@ -372,6 +372,16 @@ int k5_cfg_euler(float* img, const void* v_cond, const void* v_uncond, float w, 
   return ret(k5_launch_cfg_euler(img, v_cond, v_uncond, w, dt, n, (hipStream_t)stream), "k5_cfg_euler");
 }
 
+int k5_edit_renoise(float* out, const float* source, const float* noise, float sigma, int64_t n, void* stream) {
+  return ret(k5_launch_edit_renoise(out, source, noise, sigma, n, (hipStream_t)stream), "k5_edit_renoise");
+}
+
+int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source, const float* noise,
+                      const float* keep_mask, float sigma_next, int64_t cells, int C, void* stream) {
+  return ret(k5_launch_cfg_euler_edit(img, v_cond, v_uncond, w, dt, source, noise, keep_mask, sigma_next, cells, C, (hipStream_t)stream),
+             "k5_cfg_euler_edit");
+}
+
 int k5_conv3d_bf16(const void* X, const void* W, const float* bias, void* out, int Ts, int Hs, int Ws, int Cin, int Cout,
                    int up_t, int up_s, int ldc, const void* resid, int ldr, void* stream) {
   return ret(k5_launch_conv3d_bf16(X, W, bias, out, Ts, Hs, Ws, Cin, Cout, up_t, up_s, ldc, resid, ldr, (hipStream_t)stream),

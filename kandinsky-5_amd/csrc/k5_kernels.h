@@ -176,6 +176,14 @@ int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C,
 // K18: CFG combine + Euler.  v = cond (bf16) or bf16(u + bf16(w * bf16(c-u))); img += float(bf16(dt*v))
 int k5_launch_cfg_euler(float* img, const void* v_cond, const void* v_uncond, float w, float dt, int64_t n,
                         hipStream_t stream, const float* dtvec = nullptr, const int* step = nullptr);
+// editing: out = rn(rn((1 - sigma) * source) + rn(sigma * noise)), nothing contracted
+int k5_launch_edit_renoise(float* out, const float* source, const float* noise, float sigma, int64_t n, hipStream_t stream);
+// K18 + keep mask: the update of k5_launch_cfg_euler on cells * C elements, then with known = renoise(sigma_next) the cells of mask 1 take
+// known, those of mask 0 keep the Euler result and the others x + m * (known - x) (uncontracted); keep_mask fp32 [cells] or null (= K18's bits).
+// dtvec / signext / step: the captured step reads dt and sigma_next at the device step counter.
+int k5_launch_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source,
+                             const float* noise, const float* keep_mask, float sigma_next, int64_t cells, int C, hipStream_t stream,
+                             const float* dtvec = nullptr, const float* signext = nullptr, const int* step = nullptr);
 // fp32 -> bf16 cast, bf16 -> fp32
 int k5_launch_cast_f32_bf16(const float* x, void* out, int64_t n, hipStream_t stream);
 // weight packing: src [rows][cols] (K5_F32 / K5_BF16 / K5_F16, device) -> dst [rows][ld] bf16 (RNE) or fp32, pad columns zeroed

@@ -618,6 +618,59 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ img,
   }
 }
 
+// Editing (video-to-video, keep mask): x_sigma = (1 - sigma) * x0 + sigma * eps with each of the three operations rounded to fp32 on its own, so
+// that the torch expression `a * x0 + sigma * eps` as separate ops is the oracle bit for bit.  __fmul_rn / __fadd_rn are plain * and + to this
+// compiler (see the rotation above) and hipcc contracts by default, hence the pragma: nothing in these two functions may fuse.  The pragma holds only
+// under hipcc's DEFAULT contraction mode (fast-honor-pragmas), which is what build.py compiles with: an explicit -ffp-contract=fast on the command
+// line makes the compiler ignore it and fuse one product of each sum (seen in the ISA), which breaks the bit-exact tests.  Do not add that flag.
+__device__ __forceinline__ float renoise_at(float a, float sigma, float x0, float eps) {
+#pragma clang fp contract(off)
+  const float p = a * x0;
+  const float q = sigma * eps;
+  return p + q;
+}
+// x with the kept part put back: m == 1 -> known, m == 0 -> x, otherwise x + m * (known - x)
+__device__ __forceinline__ float keep_blend(float x, float known, float m) {
+#pragma clang fp contract(off)
+  if (m == 1.0f) return known;
+  if (m == 0.0f) return x;
+  const float d = known - x;
+  const float md = m * d;
+  return x + md;
+}
+
+__global__ __launch_bounds__(256) void edit_renoise_kernel(float* __restrict__ out, const float* __restrict__ x0,
+                                                           const float* __restrict__ eps, float sigma, int64_t n) {
+  const float a = 1.0f - sigma;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256)
+    out[g] = renoise_at(a, sigma, x0[g], eps[g]);
+}
+
+// cfg_euler_kernel (the same expressions, the same bits) followed by the keep rule at sigma_next, one pass: element g of cell g / C reads
+// mask[g / C].  In the captured step dt and sigma_next come from the device tables at the device step counter.
+__global__ __launch_bounds__(256) void cfg_euler_edit_kernel(float* __restrict__ img, const bf16_t* __restrict__ vc,
+                                                             const bf16_t* __restrict__ vu, float w, float dt,
+                                                             const float* __restrict__ x0, const float* __restrict__ eps,
+                                                             const float* __restrict__ mask, float sigma_next, int C,
+                                                             const float* __restrict__ dtvec, const float* __restrict__ signext,
+                                                             const int* __restrict__ step, int64_t n) {
+  if (dtvec) { dt = dtvec[*step]; sigma_next = signext[*step]; }
+  const float a = 1.0f - sigma_next;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
+    float v = bf2f(vc[g]);
+    if (vu) {
+      const float u = bf2f(vu[g]);
+      v = bf_round(__fadd_rn(u, bf_round(__fmul_rn(w, bf_round(__fsub_rn(v, u))))));
+    }
+    float x = __fadd_rn(img[g], bf_round(__fmul_rn(dt, v)));
+    if (mask) {
+      const float m = mask[g / C];
+      if (m != 0.0f) x = keep_blend(x, renoise_at(a, sigma_next, x0[g], eps[g]), m);
+    }
+    img[g] = x;
+  }
+}
+
 __global__ void step_inc_kernel(int* step) { *step += 1; }
 
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, int64_t n) {
@@ -846,6 +899,24 @@ int k5_launch_cfg_euler(float* img, const void* vc, const void* vu, float w, flo
   if (n <= 0 || ((dtvec != nullptr) != (step != nullptr))) return K5_ERR_ARG;
   hipLaunchKernelGGL(cfg_euler_kernel, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, w,
                      dt, dtvec, step, n);
+  return done();
+}
+
+int k5_launch_edit_renoise(float* out, const float* source, const float* noise, float sigma, int64_t n, hipStream_t s) {
+  if (!out || !source || !noise || n <= 0) return K5_ERR_ARG;
+  hipLaunchKernelGGL(edit_renoise_kernel, dim3(grid_for(n)), dim3(256), 0, s, out, source, noise, sigma, n);
+  return done();
+}
+
+int k5_launch_cfg_euler_edit(float* img, const void* vc, const void* vu, float w, float dt, const float* source, const float* noise,
+                             const float* keep_mask, float sigma_next, int64_t cells, int C, hipStream_t s, const float* dtvec,
+                             const float* signext, const int* step) {
+  if (!img || !vc || cells <= 0 || C <= 0 || ((dtvec != nullptr) != (step != nullptr)) || ((dtvec != nullptr) != (signext != nullptr)))
+    return K5_ERR_ARG;
+  if (keep_mask && (!source || !noise)) return K5_ERR_ARG;
+  const int64_t n = cells * C;
+  hipLaunchKernelGGL(cfg_euler_edit_kernel, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, w, dt, source,
+                     noise, keep_mask, sigma_next, C, dtvec, signext, step, n);
   return done();
 }
 

@@ -54,6 +54,10 @@ class SampleManyArgs(C.Structure):
                 ("guidance_weight", C.c_float)]
 
 
+class EditArgs(C.Structure):
+    _fields_ = [("source", C.c_void_p), ("noise", C.c_void_p), ("keep_mask", C.c_void_p)]
+
+
 class VaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int), ("out_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -141,6 +145,9 @@ SYMBOLS = {
     "k5_sample": (_I, [_P, C.POINTER(SampleArgs), _P]),
     "k5_sample_cond": (_I, [_P, C.POINTER(SampleArgs), _P, _P]),
     "k5_sample_many": (_I, [_P, C.POINTER(SampleManyArgs), _P]),
+    "k5_sample_edit": (_I, [_P, C.POINTER(SampleArgs), _P, C.POINTER(EditArgs), _P]),
+    "k5_edit_renoise": (_I, [_P, _P, _P, _F, _I64, _P]),
+    "k5_cfg_euler_edit": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _F, _I64, _I, _P]),
     "k5_dit_forward_many": (_I, [_P, C.POINTER(ForwardArgs), _I, C.POINTER(TextCond), _P, _P]),
     "k5_comm_unique_id": (_I, [C.c_char_p, _P]),
     "k5_dit_comm_init": (_I, [_P, C.c_char_p, _I, _I, _P]),
@@ -204,7 +211,7 @@ def lib() -> C.CDLL:
     for name, (res, args) in SYMBOLS.items():
         try:
             fn = getattr(L, name)
-        except AttributeError as e:   # a libk5.so of the same ABI number from before an added export (the MagCache calibration and LoRA ones)
+        except AttributeError as e:   # a libk5.so of the same ABI number from before an added export (the MagCache calibration, LoRA and editing ones)
             raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it with `python kandinsky-5_amd/build.py`") from e
         fn.restype = res
         fn.argtypes = args
@@ -395,4 +402,33 @@ def cfg_euler_(img, v_cond, v_uncond, w, dt):
     _need_cuda(img, v_cond, v_uncond)
     check(lib().k5_cfg_euler(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), img.numel(),
                              stream_ptr(img.device)), "k5_cfg_euler")
+    return img
+
+
+def renoise(source, noise, sigma, out=None):
+    """rn(rn((1 - sigma) * source) + rn(sigma * noise)) (k5_edit_renoise): contiguous fp32 tensors of one shape; a new tensor unless `out`."""
+    _need_cuda(source, noise, out)
+    if out is None:
+        out = torch.empty_like(source)
+    for t in (source, noise, out):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != source.shape:
+            raise ValueError("renoise: source, noise and out must be contiguous fp32 tensors of one shape")
+    check(lib().k5_edit_renoise(ptr(out), ptr(source), ptr(noise), float(sigma), source.numel(), stream_ptr(source.device)),
+          "k5_edit_renoise")
+    return out
+
+
+def cfg_euler_edit_(img, v_cond, v_uncond, w, dt, source, noise, keep_mask, sigma_next):
+    """cfg_euler_ followed by the keep rule at sigma_next (k5_cfg_euler_edit): img, source, noise fp32 (..., C), keep_mask fp32 (..., 1) or
+    None (= cfg_euler_)."""
+    _need_cuda(img, v_cond, v_uncond, source, noise, keep_mask)
+    C_ = img.shape[-1]
+    cells = img.numel() // C_
+    for t in (img, source, noise):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != img.shape:
+            raise ValueError("cfg_euler_edit_: img, source and noise must be contiguous fp32 tensors of one shape")
+    if keep_mask is not None and (keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous() or keep_mask.numel() != cells):
+        raise ValueError("cfg_euler_edit_: keep_mask must be a contiguous fp32 tensor with one value per cell")
+    check(lib().k5_cfg_euler_edit(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), ptr(source), ptr(noise), ptr(keep_mask),
+                                  float(sigma_next), cells, C_, stream_ptr(img.device)), "k5_cfg_euler_edit")
     return img

@@ -5,6 +5,9 @@ Every shipped config builds the DiT with `visual_cond: true`: its input is `cat(
 them: `image_to_visual_cond` puts the VAE latent of a picture on latent frame 0, `latents_to_visual_cond` puts k given latent
 frames on frames 0..k-1.  Both return `(visual_cond (T,H,W,16), visual_cond_mask (T,H,W,1))` fp32, the keyword arguments of
 `generate`.
+
+Video-to-video and masked editing start from a source clip instead: `encode_video` gives `generate`'s `init_latent`,
+`pixel_mask_to_latent` its `keep_mask`.
 """
 import torch
 import torch.nn.functional as F
@@ -59,6 +62,65 @@ def encode_image(image, vae, height, width, vae_device="cuda"):
     return (mean.float() * vae.config.scaling_factor)[:, :, 0].permute(0, 2, 3, 1).contiguous()
 
 
+def preprocess_video(frames, height, width):
+    """The clip as the VAE sees it: float32 (F, 3, height, width) in [-1, 1], `preprocess_image`'s rule applied to every frame.
+    `frames`: uint8 (F, h, w, 3) or float (F, 3, h, w) in [-1, 1]."""
+    if not torch.is_tensor(frames):
+        import numpy as np
+        frames = torch.from_numpy(np.ascontiguousarray(frames))
+    if frames.dim() != 4:
+        raise ValueError(f"video must be uint8 (F, H, W, 3) or float (F, 3, H, W), got shape {tuple(frames.shape)}")
+    if frames.dtype == torch.uint8:
+        if frames.shape[-1] != 3:
+            raise ValueError(f"uint8 video must be (F, H, W, 3), got shape {tuple(frames.shape)}")
+    elif not frames.is_floating_point() or frames.shape[1] != 3:
+        raise ValueError(f"float video must be (F, 3, H, W), got {frames.dtype} of shape {tuple(frames.shape)}")
+    if frames.shape[0] < 1:
+        raise ValueError("video has no frames")
+    return torch.stack([preprocess_image(f, height, width) for f in frames])
+
+
+@torch.no_grad()
+def encode_video(video, vae, num_frames, height, width, vae_device="cuda"):
+    """Clean latent of a source clip for video-to-video: posterior mean of the VAE encoder (through `vae.encode` and its tiling) on the
+    first 4 * (num_frames - 1) + 1 preprocessed pixel frames, times `scaling_factor`: fp32 (num_frames, height/8, width/8, C) on
+    `vae_device`.  ValueError when the clip is shorter."""
+    if height % 8 or width % 8:
+        raise ValueError(f"height and width must be multiples of 8, got {height} x {width}")
+    need = 4 * (int(num_frames) - 1) + 1
+    if len(video) < need:
+        raise ValueError(f"a {num_frames}-frame latent needs {need} pixel frames, the video has {len(video)}")
+    x = preprocess_video(video[:need], height, width).to(vae_device).permute(1, 0, 2, 3)[None]   # (1, 3, F, H, W)
+    mean = vae.encode(x).latent_dist.mean                                                    # (1, C, T, H/8, W/8)
+    return (mean.float() * vae.config.scaling_factor)[0].permute(1, 2, 3, 0).contiguous()
+
+
+def pixel_mask_to_latent(mask, T, H, W):
+    """Pixel keep mask -> latent keep mask fp32 (T, H/8, W/8, 1), pooled conservatively: a latent cell is 1 only if every pixel of its
+    8x8 block is >= 0.5 in every pixel frame it covers (latent frame 0 = pixel frame 0, latent frame t >= 1 = pixel frames
+    4t-3 .. 4t), otherwise 0 — nothing is kept that the mask did not cover entirely.  `mask`: (H, W), applied to all frames, or
+    (F, H, W) with F >= 4 * (T - 1) + 1; bool, integer or float."""
+    if not torch.is_tensor(mask):
+        import numpy as np
+        mask = torch.from_numpy(np.ascontiguousarray(mask))
+    if H % 8 or W % 8:
+        raise ValueError(f"height and width must be multiples of 8, got {H} x {W}")
+    need = 4 * (int(T) - 1) + 1
+    m = mask.detach().cpu().float() >= 0.5
+    if m.dim() == 2:
+        m = m[None].expand(need, -1, -1)
+    if m.dim() != 3 or tuple(m.shape[1:]) != (H, W):
+        raise ValueError(f"mask must be ({H}, {W}) or (F, {H}, {W}), got shape {tuple(mask.shape)}")
+    if m.shape[0] < need:
+        raise ValueError(f"a {T}-frame latent needs a mask of {need} pixel frames, got {m.shape[0]}")
+    cell = m[:need].reshape(need, H // 8, 8, W // 8, 8).all(dim=4).all(dim=2)            # (F, H/8, W/8)
+    out = torch.empty((T, H // 8, W // 8), dtype=torch.bool)
+    out[0] = cell[0]
+    if T > 1:
+        out[1:] = cell[1:].reshape(T - 1, 4, H // 8, W // 8).all(dim=1)
+    return out.float()[..., None].contiguous()
+
+
 def latents_to_visual_cond(latents, num_frames):
     """k latent frames (k, H, W, C) -> (visual_cond (num_frames, H, W, C), mask (num_frames, H, W, 1)): frames 0..k-1 hold the
     given latents with mask 1, the rest are zero."""
@@ -86,4 +148,5 @@ def image_to_visual_cond(image, vae, num_frames, height, width, device=None, vae
     return vc, mask
 
 
-__all__ = ["preprocess_image", "encode_image", "latents_to_visual_cond", "image_to_visual_cond"]
+__all__ = ["preprocess_image", "encode_image", "latents_to_visual_cond", "image_to_visual_cond", "preprocess_video", "encode_video",
+           "pixel_mask_to_latent"]

@@ -6,6 +6,7 @@ sigma-schedule construction, but runs the Euler / CFG loop on the MI355X engine:
 DiT, otherwise step by
 step through `model(...)` (duck-typed models, e.g. a MagCache wrapper) with the fused CFG+Euler kernel.
 """
+import math
 import os
 
 os.environ.setdefault("TOKENIZERS_PARALLELISM", "False")
@@ -67,21 +68,62 @@ def sigma_schedule(num_steps, scheduler_scale, device="cpu"):
     return scheduler_scale * timesteps / (1 + (scheduler_scale - 1) * timesteps)
 
 
+def edit_first_step(num_steps, strength):
+    """Video-to-video `strength` in (0, 1] -> the first step that runs: run = min(num_steps, max(1, floor(num_steps * strength + 0.5)))
+    steps, the tail of the schedule, so first = num_steps - run (strength 1 = the whole schedule)."""
+    strength = float(strength)
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f"strength must be in (0, 1], got {strength}")
+    run = min(int(num_steps), max(1, int(math.floor(num_steps * strength + 0.5))))
+    return int(num_steps) - run
+
+
+def _has_magcache(model):
+    """True when the model (or a module inside a wrapper) carries a MagCache ratio table or is calibrating one."""
+    mods = list(model.modules()) if isinstance(model, torch.nn.Module) else [model]
+    return any(getattr(m, "mag_ratios", None) is not None or getattr(m, "_magcache_calibrate", None) is not None for m in mods)
+
+
+def _check_edit_args(model, shape, init_latent, strength, keep_mask):
+    """The ValueErrors of `generate`'s editing keywords."""
+    edit_first_step(1, strength)   # strength in (0, 1]
+    if init_latent is None:
+        if float(strength) < 1.0:
+            raise ValueError("strength < 1 needs init_latent (the clip to start from)")
+        if keep_mask is not None:
+            raise ValueError("keep_mask needs init_latent (the clip whose region is kept)")
+        return
+    if tuple(init_latent.shape) != tuple(shape):
+        raise ValueError(f"init_latent must be {tuple(shape)}, got {tuple(init_latent.shape)}")
+    if keep_mask is not None and tuple(keep_mask.shape) != tuple(shape[:-1]) + (1,):
+        raise ValueError(f"keep_mask must be {tuple(shape[:-1]) + (1,)}, got {tuple(keep_mask.shape)}")
+    if float(strength) < 1.0 and _has_magcache(model):
+        raise ValueError("strength < 1 with MagCache: the ratio table is indexed by the step of a full run, a truncated schedule would "
+                         "read the wrong rows (a keep_mask at strength 1 is allowed)")
+
+
 @torch.no_grad()
 def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
              null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=False, seed=6554, noise=None, *,
-             visual_cond=None, visual_cond_mask=None, batch=1):
+             visual_cond=None, visual_cond_mask=None, batch=1, init_latent=None, strength=1.0, keep_mask=None):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
     `batch` (extension): `shape` = (batch*T, H, W, C) holds `batch` samples of T frames, sample b = frames [bT, (b+1)T) of the
     one noise draw of the full shape (and of visual_cond / visual_cond_mask).  `text_embeds`, `null_text_embeds` and their rope
     positions are then one value shared by all samples or a list of `batch`.  Every sample is bit-identical to a call of its own
-    with its noise slice: a single-rank engine DiT runs them in one k5_sample_many call, any other model one after another."""
+    with its noise slice: a single-rank engine DiT runs them in one k5_sample_many call, any other model one after another.
+    `init_latent`, `strength`, `keep_mask` (optional, extension): video-to-video and masked editing.  `init_latent` (shape) is the clean
+    latent of the source clip (`conditioning.encode_video`), the drawn or passed `noise` is the eps it is noised with: the loop starts
+    from (1 - sigma) * init_latent + sigma * noise at step `first = edit_first_step(num_steps, strength)` and runs the tail of the
+    schedule.  `keep_mask` (shape[:-1] + (1,)) in [0, 1]: where it is 1 the result is `init_latent` bit for bit, the rest is
+    generated around it (the kept region is re-imposed at every step's sigma on the device).  strength = 1 without a mask is the
+    plain run on `noise`, bit for bit.  With batch > 1 the samples run one at a time."""
     from .models.dit import split_per_sample
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
         raise ValueError(f"shape[0] = {shape[0]} frames do not divide into batch={batch} samples")
+    _check_edit_args(model, shape, init_latent, strength, keep_mask)
     many = any(isinstance(v, (list, tuple)) for v in (text_embeds, null_text_embeds))
     if batch == 1 and many:
         text_embeds, null_text_embeds, text_rope_pos, null_text_rope_pos = (
@@ -97,7 +139,13 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     if batch > 1:
         return _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                                null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond,
-                               visual_cond_mask)
+                               visual_cond_mask, init_latent, strength, keep_mask)
+    edit = None
+    if init_latent is not None:   # img (the draw) is eps from here on; the latent is a buffer of its own that the engine fills
+        src = init_latent.to(device=img.device, dtype=torch.float32).contiguous()
+        km = None if keep_mask is None else keep_mask.to(device=img.device, dtype=torch.float32).contiguous()
+        edit = (src, img, km)
+        img = torch.empty_like(img)
 
     cond_in = None
     if visual_cond is not None or visual_cond_mask is not None:
@@ -114,6 +162,15 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
 
     sparse_params = get_sparse_params(conf, {"visual": img}, device)
     timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()  # one sync, before the loop
+    if edit is not None:
+        timesteps = timesteps[edit_first_step(num_steps, strength):]   # strength is a truncation of the schedule, nothing more
+
+    def update(v, u, timestep_diff, sigma_next):
+        """CFG combine + Euler (+ the keep rule when editing) on img, in place"""
+        if edit is None:
+            E.cfg_euler_(img, v, u, guidance_weight, timestep_diff)
+        else:
+            E.cfg_euler_edit_(img, v, u, guidance_weight, timestep_diff, edit[0], edit[1], edit[2], sigma_next)
 
     from .models.dit import DiffusionTransformer3D
     if isinstance(model, torch.nn.Module):      # per-step paths below: a new sampling run starts with no softmax-form memory (k5_sample resets its own)
@@ -131,24 +188,28 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         branch, pair_group = cfg_parallel
         mine, mine_pos = (text_embeds, text_rope_pos) if branch == 0 else (null_text_embeds, null_text_rope_pos)
         both = None
-        for timestep, timestep_diff in zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist()):
+        if edit is not None:
+            E.renoise(edit[0], edit[1], float(timesteps[0]), out=img)
+        for timestep, timestep_diff, sigma_next in zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(), timesteps[1:].tolist()):
             x = img if cond_in is None else torch.cat([img, *cond_in], dim=-1)
             v = model(x, mine["text_embeds"], mine["pooled_embed"], torch.tensor([timestep]) * 1000, visual_rope_pos,
                       mine_pos, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
             if both is None:
                 both = torch.empty((2,) + tuple(v.shape), dtype=v.dtype, device=v.device)
             vc, vu = exchange_velocity(v, pair_group, out=both)
-            E.cfg_euler_(img, vc, vu, guidance_weight, timestep_diff)
+            update(vc, vu, timestep_diff, sigma_next)
         return img
     if type(model) is DiffusionTransformer3D and model.visual_cond in (True, False):
         # whole loop inside the engine: no per-step host work at all
         model.sample(img, timesteps.tolist(), text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                      null_text_rope_pos, guidance_weight, scale_factor=conf.metrics.scale_factor,
                      sparse_params=sparse_params,
-                     visual_cond=None if cond_in is None else torch.cat(cond_in, dim=-1).contiguous())
+                     visual_cond=None if cond_in is None else torch.cat(cond_in, dim=-1).contiguous(), edit=edit)
         return img
 
-    for timestep, timestep_diff in zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist()):
+    if edit is not None:
+        E.renoise(edit[0], edit[1], float(timesteps[0]), out=img)
+    for timestep, timestep_diff, sigma_next in zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(), timesteps[1:].tolist()):
         if model.visual_cond:
             if cond_in is None:
                 vc = torch.zeros_like(img)
@@ -166,12 +227,13 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
             u = model(model_input, null_text_embeds["text_embeds"], null_text_embeds["pooled_embed"], t1000,
                       visual_rope_pos, null_text_rope_pos, scale_factor=conf.metrics.scale_factor,
                       sparse_params=sparse_params)
-        E.cfg_euler_(img, v.contiguous(), None if u is None else u.contiguous(), guidance_weight, timestep_diff)
+        update(v.contiguous(), None if u is None else u.contiguous(), timestep_diff, sigma_next)
     return img
 
 
 def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
-                    null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond, visual_cond_mask):
+                    null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond, visual_cond_mask,
+                    init_latent=None, strength=1.0, keep_mask=None):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
     from .models.dit import split_per_sample
     T = img.shape[0] // batch
@@ -186,7 +248,7 @@ def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text
         return None if v is None else v[b * T:(b + 1) * T]
 
     from .models.dit import DiffusionTransformer3D
-    if type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) and model.many_ready() \
+    if init_latent is None and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) and model.many_ready() \
             and getattr(model, "_cfg_parallel", None) is None:
         cond = None
         if visual_cond is not None or visual_cond_mask is not None:
@@ -204,12 +266,13 @@ def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text
         model.sample_many(img.view(batch, T, *img.shape[1:]), timesteps.tolist(), tes, nes, visual_rope_pos, tps, nps,
                            guidance_weight, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params, visual_cond=cond)
         return img
-    # any other model (rank groups, MagCache, graph replay, wrapped or duck-typed models): today's path, one sample at a time
+    # any other model (rank groups, MagCache, graph replay, wrapped or duck-typed models) and editing: today's path, one sample at a time
     for b in range(batch):
         img[b * T:(b + 1) * T] = generate(model, device, (T,) + tuple(img.shape[1:]), num_steps, tes[b], nes[b], visual_rope_pos,
                                           tps[b], nps[b], guidance_weight, scheduler_scale, conf, progress=progress, seed=seed,
                                           noise=img[b * T:(b + 1) * T], visual_cond=part(visual_cond, b),
-                                          visual_cond_mask=part(visual_cond_mask, b))
+                                          visual_cond_mask=part(visual_cond_mask, b), init_latent=part(init_latent, b),
+                                          strength=strength, keep_mask=part(keep_mask, b))
     return img
 
 
@@ -248,17 +311,34 @@ def frames_to_uint8(frames):
 
 def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25, guidance_weight=5.0,
                     scheduler_scale=1, negative_caption="", seed=6554, device="cuda", vae_device="cuda",
-                    text_embedder_device="cuda", progress=True, offload=False, image=None):
+                    text_embedder_device="cuda", progress=True, offload=False, image=None, video=None, strength=1.0, mask=None):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
     sample.  `caption` (extension): one prompt for every sample, or a list of `bs` prompts, one per sample; the samples come from
-    one noise draw of the whole shape (see `generate`)."""
+    one noise draw of the whole shape (see `generate`).  `video`, `strength`, `mask` (optional, extension): video-to-video and masked
+    editing.  `video` is the source clip (uint8 (F,H,W,3) or float (F,3,H,W) frames, see conditioning.preprocess_video), `strength`
+    in (0, 1] how much of the schedule runs on it and `mask` a pixel keep mask ((H,W) or (F,H,W), >= 0.5 = keep the source there, at
+    8 * height x 8 * width, see conditioning.pixel_mask_to_latent); every sample of the batch edits the same clip."""
     batch, frames, height, width, channels = shape
     captions = list(caption) if isinstance(caption, (list, tuple)) else [caption] * batch
     if len(captions) != batch:
         raise ValueError(f"{len(captions)} captions for bs={batch} samples")
+    edit_first_step(num_steps, strength)
+    if video is None and (float(strength) < 1.0 or mask is not None):
+        raise ValueError("strength < 1 and mask need a source video")
     cond_kw = {}
+    if video is not None:
+        from .conditioning import encode_video, pixel_mask_to_latent
+        if offload:
+            vae.to(vae_device)
+        z = encode_video(video, vae, frames, 8 * height, 8 * width, vae_device=vae_device).to(device)
+        if offload:
+            vae.to("cpu")
+            torch.cuda.empty_cache()
+        cond_kw.update(init_latent=z.repeat(batch, 1, 1, 1), strength=strength)
+        if mask is not None:
+            cond_kw["keep_mask"] = pixel_mask_to_latent(mask, frames, 8 * height, 8 * width).to(device).repeat(batch, 1, 1, 1)
     if image is not None:
         from .conditioning import image_to_visual_cond
         if offload:
@@ -267,7 +347,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         if offload:
             vae.to("cpu")
             torch.cuda.empty_cache()
-        cond_kw = {"visual_cond": vc.repeat(batch, 1, 1, 1), "visual_cond_mask": vm.repeat(batch, 1, 1, 1)}
+        cond_kw.update(visual_cond=vc.repeat(batch, 1, 1, 1), visual_cond_mask=vm.repeat(batch, 1, 1, 1))
     kind = "image" if frames == 1 else "video"
     if batch == 1:
         (cond, n_cond), (uncond, n_uncond) = _encode_prompts(text_embedder, (captions[0], negative_caption), kind, device)

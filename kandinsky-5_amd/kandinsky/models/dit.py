@@ -295,16 +295,20 @@ class DiffusionTransformer3D(nn.Module):
 
     @torch.no_grad()
     def sample(self, latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
-               null_text_rope_pos, guidance_weight, scale_factor=(1.0, 1.0, 1.0), sparse_params=None, visual_cond=None):
+               null_text_rope_pos, guidance_weight, scale_factor=(1.0, 1.0, 1.0), sparse_params=None, visual_cond=None, edit=None):
         """Whole Euler/CFG loop on device (generation_utils.py:80-129) in one C call.  `latent` fp32
         (T,H,W,in_visual_dim) is updated in place; `sigmas` = the sigma schedule (num_steps+1 floats, host).
         `visual_cond` (optional, a model with visual_cond only): contiguous fp32 (T,H,W,in_visual_dim+1) on the latent's device, the
-        conditioning latent and its mask that fill the input channels the reference leaves zero (k5_sample_cond); None = k5_sample."""
+        conditioning latent and its mask that fill the input channels the reference leaves zero (k5_sample_cond); None = k5_sample.
+        `edit` (optional): `(source, noise, keep_mask | None)`, contiguous fp32 on the latent's device, source and noise of the latent's
+        shape and keep_mask (T,H,W,1): video-to-video / masked editing (k5_sample_edit).  `latent` is then output only: it starts as
+        the source noised to sigmas[0] and the kept region (mask 1) is held on the source through every step."""
         if not latent.is_cuda or latent.dtype != torch.float32 or not latent.is_contiguous():
             raise RuntimeError("latent must be a contiguous fp32 CUDA tensor")
         T, H, W, _ = latent.shape
         self._last_tokens = T * (H // self.patch_size[1]) * (W // self.patch_size[2])   # rows of a residual (magcache_calibration)
         self._check_visual_cond(visual_cond, latent)
+        edit = self._check_edit(edit, latent)
         h = self.engine(latent.device)
         dev = latent.device
         keep = []
@@ -319,7 +323,10 @@ class DiffusionTransformer3D(nn.Module):
         arr = (C.c_float * len(sig))(*sig)
         s.latent, s.num_steps, s.sigmas, s.guidance_weight = latent.data_ptr(), len(sig) - 1, arr, float(guidance_weight)
         with torch.cuda.device(dev):
-            if visual_cond is None:
+            if edit is not None:
+                ea = E.EditArgs(edit[0].data_ptr(), edit[1].data_ptr(), E.ptr(edit[2]))
+                E.check(E.lib().k5_sample_edit(h, C.byref(s), E.ptr(visual_cond), C.byref(ea), E.stream_ptr(dev)), "k5_sample_edit")
+            elif visual_cond is None:
                 E.check(E.lib().k5_sample(h, C.byref(s), E.stream_ptr(dev)), "k5_sample")
             else:
                 E.check(E.lib().k5_sample_cond(h, C.byref(s), visual_cond.data_ptr(), E.stream_ptr(dev)), "k5_sample_cond")
@@ -340,6 +347,29 @@ class DiffusionTransformer3D(nn.Module):
             raise ValueError(f"visual_cond must be on {latent.device}, got {visual_cond.device}")
         if not visual_cond.is_contiguous():
             raise ValueError("visual_cond must be contiguous")
+
+    def _check_edit(self, edit, latent):
+        """edit = (source, noise, keep_mask | None): contiguous fp32 tensors on the latent's device, source and noise of the latent's shape,
+        keep_mask of latent.shape[:-1] + (1,).  Returns the triple (or None)."""
+        if edit is None:
+            return None
+        if not isinstance(edit, (tuple, list)) or len(edit) != 3:
+            raise ValueError("edit must be (source, noise, keep_mask or None)")
+        want = {"source": tuple(latent.shape), "noise": tuple(latent.shape), "keep_mask": tuple(latent.shape[:-1]) + (1,)}
+        for (name, shape), t in zip(want.items(), edit):
+            if t is None:
+                if name == "keep_mask":
+                    continue
+                raise ValueError(f"edit {name} is missing")
+            if not torch.is_tensor(t) or tuple(t.shape) != shape:
+                raise ValueError(f"edit {name} must have shape {shape}, got {tuple(getattr(t, 'shape', ()))}")
+            if t.dtype != torch.float32:
+                raise ValueError(f"edit {name} must be float32, got {t.dtype}")
+            if t.device != latent.device:
+                raise ValueError(f"edit {name} must be on {latent.device}, got {t.device}")
+            if not t.is_contiguous():
+                raise ValueError(f"edit {name} must be contiguous")
+        return tuple(edit)
 
     def many_ready(self):
         """True when `sample_many` / `forward_many` are accepted: a single-rank handle without MagCache or graph replay."""

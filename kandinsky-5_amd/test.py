@@ -3,6 +3,7 @@ README launch lines keep working against this package:
 
     python test.py --prompt "a cat in a blue hat" --config ./configs/config_5s_sft.yaml
     python test.py --prompt "the cat turns its head" --image cat.png     # image-to-video: the clip starts from cat.png
+    python test.py --prompt "the same street at night" --video clip.mp4 --strength 0.6 --mask keep.png   # video-to-video, masked
     python test.py --config ./configs/config_5s_distil.yaml --calibrate_magcache ratios.json   # measure a MagCache table, then:
     python test.py --config ./configs/config_5s_distil.yaml --magcache --magcache_ratios ratios.json
     python test.py --prompt "a cat in a blue hat" --lora style.safetensors --lora_scale 0.8   # LoRA adapter(s) merged into the DiT
@@ -49,7 +50,33 @@ def build_parser():
                    help="LoRA adapter (.safetensors; peft, diffusers or kohya names) merged into the DiT; repeat the flag for several")
     p.add_argument("--lora_scale", type=float, nargs="+", default=argparse.SUPPRESS, metavar="S",
                    help="adapter strength: one value for all --lora files or one per file (default 1.0)")
+    p.add_argument("--video", type=str, default=argparse.SUPPRESS, metavar="PATH",
+                   help="video-to-video: the source clip (container, animated PNG / GIF, .npy / .pt of uint8 frames, or a directory of images)")
+    p.add_argument("--strength", type=float, default=argparse.SUPPRESS, metavar="S",
+                   help="with --video: the part of the schedule that runs on the source, in (0, 1] (default 1.0 = only --mask ties the result to it)")
+    p.add_argument("--mask", type=str, default=argparse.SUPPRESS, metavar="PATH",
+                   help="with --video: keep mask (an image, or a clip as for --video); white = keep the source there, black = generate; "
+                        "resized and centre-cropped to the output size like the frames of --video")
     return p
+
+
+def load_edit_inputs(args):
+    """--video / --strength / --mask -> the pipeline's keywords"""
+    kw = {}
+    if getattr(args, "video", None) is None:
+        if hasattr(args, "strength") or hasattr(args, "mask"):
+            raise ValueError("--strength and --mask need --video")
+        return kw
+    from kandinsky.video_io import read_video
+    kw["video"] = read_video(args.video)
+    if hasattr(args, "strength"):
+        kw["strength"] = args.strength
+    if hasattr(args, "mask"):
+        # the mask goes through the frames' own resize-and-crop rule, so a mask drawn on the source clip lands where the clip does
+        from kandinsky.conditioning import preprocess_video
+        m = (preprocess_video(read_video(args.mask), args.height, args.width).mean(dim=1) + 1.0) / 2.0   # (F, height, width) in [0, 1]
+        kw["mask"] = m[0] if m.shape[0] == 1 else m
+    return kw
 
 
 def validate_args(args):
@@ -72,6 +99,7 @@ def main(argv=None):
     if args.image is not None:
         from PIL import Image
         image = Image.open(args.image).convert("RGB")
+    edit_kw = load_edit_inputs(args)
     if args.calibrate_magcache:
         import json
         from kandinsky.magcache_utils import calibrate_magcache
@@ -86,7 +114,7 @@ def main(argv=None):
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
-         negative_caption=args.negative_prompt, save_path=args.output_filename, image=image)
+         negative_caption=args.negative_prompt, save_path=args.output_filename, image=image, **edit_kw)
     print(f"TIME ELAPSED: {time.perf_counter() - t0}")
     print(f"Generated video is saved to {args.output_filename}")
 
