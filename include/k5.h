@@ -281,6 +281,20 @@ int k5_edit_renoise(float* out, const float* source, const float* noise, float s
  * NULL = k5_cfg_euler (source / noise then unused).  One pass over the latent. */
 int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source, const float* noise,
                       const float* keep_mask, float sigma_next, int64_t cells, int C, void* stream);
+/* Sampler preview (added under ABI 11, as the exports above were): the denoised estimate of a flow-matching step and a cheap RGB view of it, one
+ * pass.  After the update of a step the latent x (fp32, cells * C) sits at sigma_next and v_cond / v_uncond (bf16, v_uncond NULL = no guidance)
+ * still hold that step's velocities: v is combined exactly as in k5_cfg_euler, x0 = rn(x - rn(sigma_next * v)) in fp32 (sigma_next == 0 gives
+ * x bit for bit), and with keep_mask (fp32 [cells], as k5_cfg_euler_edit) x0 = keep rule(x0, source, m), so kept cells show the source.
+ * x0_out (fp32 cells * C, or NULL) receives x0; rgb (uint8 cells * 3, or NULL) receives
+ *   rgb[cell][j] = sat_u8(rint((b[j] + sum_k W[k][j] x0[k]) * 127.5 + 127.5)), NaN -> 0,
+ * W = rgb_w [C][3] and b = rgb_b [3] (NULL = zeros), fp32 on the DEVICE.  The sum has a fixed order (deterministic bits): four lanes share a
+ * cell, lane q takes channels 4(q + 4i) .. 4(q + 4i) + 3 for i = 0, 1, .. in ascending order as acc = fma(W[k][j], x0[k], acc) from 0; the four
+ * partial sums add as (a0 + a1) + (a2 + a3); then fma(b[j] + sum, 127.5, 127.5).  rgb and rgb_w are given together or not at all and one of
+ * rgb / x0_out is needed (K5_ERR_ARG); x, x0_out, source 16-byte and the velocities 8-byte aligned (K5_ERR_ARG); C % 4 == 0 and C <= 64,
+ * anything else is K5_ERR_UNSUPPORTED.  Nothing is launched when the call is refused. */
+int k5_x0_preview(const float* x, const void* v_cond, const void* v_uncond, float w, float sigma_next, const float* source,
+                  const float* keep_mask, const float* rgb_w, const float* rgb_b, float* x0_out, uint8_t* rgb, int64_t cells, int C,
+                  void* stream);
 /* LoRA merge, in place on a row-major matrix (added under ABI 11, as the MagCache calibration exports were): W'[n][k] = W[n][k] + scale *
  * sum_r B[n][r] A[r][k].  W [rows][ld] (cols <= ld) of w_dtype K5_BF16 or K5_F32;
  * A [R][cols], B [rows][R], each K5_F32 / K5_BF16 / K5_F16, device pointers, converted to fp32 on load; 1 <= R <= 256.  The arithmetic is
@@ -392,6 +406,45 @@ typedef struct k5_sample_many_args {
   float guidance_weight;
 } k5_sample_many_args;
 int k5_sample_many(k5_dit* dit, const k5_sample_many_args* args, void* stream);
+/* A watch on the handle (added under ABI 11): progress, cancel and live previews out of k5_sample / k5_sample_cond / k5_sample_edit /
+ * k5_sample_many, which otherwise return only when the whole loop is done.  With a watch installed the engine calls `fn` once per completed
+ * step, in order, on the thread that called k5_sample*, and a non-zero return stops the run.  Without one the sampler enqueues exactly what it
+ * always did: not one launch, event or synchronisation more.
+ *   After step i the engine enqueues on the sampler's stream — on preview steps only — k5_x0_preview (sigma_next = sigmas[i+1], the call's
+ *   guidance weight, source / keep_mask of k5_sample_edit) and a device-to-host copy of the RGB into one of TWO pinned slots it owns, then
+ *   records an event.  The callback of step i runs once that event has completed and only after step i+1 has been enqueued (one step of
+ *   look-ahead): the GPU never waits for the host, and the slot (rgb and x0) the callback reads is not the one being written.  In the captured-step
+ *   mode the preview launches sit between the graph launches; nothing is added to the captured graph.
+ *   Stop: after a non-zero return nothing more is enqueued, the stream is synchronised, the callback is not called again and k5_sample* returns
+ *   K5_OK.  The latent is then the state after `steps_done` steps (k5_dit_watch_state), at most one step past the one the callback saw;
+ *   k5_sample_many leaves the remaining samples untouched (steps_done counts the steps of the sample that was stopped).
+ *   info->rgb / info->x0 are valid during the callback only.  THE CALLBACK MUST NOT CALL INTO THE SAME HANDLE (another handle, or plain HIP work
+ *   on another stream, is fine).
+ * Works in eager mode, the captured step, with MagCache and its calibration, with visual conditioning and editing.  Refused with K5_ERR_STATE
+ * and a message, by k5_dit_set_watch and — when the group was formed later — by k5_sample* before anything is enqueued, on a handle in a
+ * sequence-parallel group or a CFG pair (any transport): a rank that stops alone would leave its peers inside a collective.  K5_ERR_ARG:
+ * fn NULL, preview_every < 0, previews without rgb_w, want_x0 without previews; K5_ERR_UNSUPPORTED: previews on a handle whose in_visual_dim
+ * is not a multiple of 4 or exceeds 64.  The pinned slots and the device buffers are freed by k5_dit_destroy. */
+typedef struct k5_watch_info {
+  int step, num_steps;      /* step just completed, 0-based */
+  int sample, num_samples;  /* k5_sample_many; 0 / 1 otherwise */
+  float sigma_next;
+  const uint8_t* rgb;       /* HOST (pinned, engine-owned) (T,H,W,3) or NULL on a step without a preview */
+  const float* x0;          /* DEVICE (engine-owned) (T,H,W,C) or NULL */
+  int T, H, W, C;
+} k5_watch_info;
+typedef int (*k5_watch_fn)(void* user, const k5_watch_info* info);   /* non-zero = stop */
+typedef struct k5_watch {
+  k5_watch_fn fn; void* user;
+  int preview_every;        /* 0 = never; k > 0 = steps with (step+1) % k == 0, and always the last step */
+  int want_x0;
+  const float* rgb_w;       /* HOST [C][3], copied at set time; NULL only when preview_every == 0 */
+  const float* rgb_b;       /* HOST [3] or NULL = zeros */
+} k5_watch;
+int k5_dit_set_watch(k5_dit* dit, const k5_watch* watch /* NULL clears */);
+/* of the last k5_sample* call: steps enqueued and completed, and whether the callback stopped it (0 / 1) */
+int k5_dit_watch_state(k5_dit* dit, int* steps_done, int* stopped);
+
 /* S forwards of the same (T, H, W) in one call, one after another (a convenience entry point like k5_sample_many): args->x is device fp32
  * [S][T][H][W][args->x_channels], conds HOST [S], args->time shared; out_velocity bf16 [S][T][H][W][out_visual_dim].  Sequence i is
  * k5_dit_forward(x[i], conds[i]) — the same entry point — on the handle as it was when the call began: the softmax-form memory that

@@ -345,6 +345,20 @@ struct k5_dit {
   bool use_graph = false;                          // k5_sample replays one captured step (k5_dit_set_graph)
   hipStream_t graph_stream = nullptr;              // capture needs a real stream: the caller's may be the legacy null stream
   hipEvent_t ev_graph = nullptr;
+  // The watch of k5_dit_set_watch (progress / cancel / previews out of the sampler loop).  Two slots, used alternately by the
+  // steps: the callback of step i reads slot i & 1 while the preview of step i + 1 is written into the other.
+  struct Watch {
+    bool on = false;
+    k5_watch_fn fn = nullptr; void* user = nullptr;
+    int every = 0; bool want_x0 = false;
+    DevBuf wb;                                     // device copy of rgb_w [C][3] | rgb_b [3]
+    DevBuf rgb[2], x0[2];                          // device RGB (T,H,W,3) uint8 and x0 (T,H,W,C) fp32 of a slot
+    uint8_t* h_rgb[2] = {nullptr, nullptr};        // pinned host copies of rgb[]
+    size_t h_bytes = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};         // "step i and its preview are complete"
+    int steps_done = 0, stopped = 0;               // of the last k5_sample* call (k5_dit_watch_state)
+    int sample = 0, num_samples = 1;               // set by k5_sample_many around each sample
+  } watch;
   DevBuf ws_kc;                                    // NABLA: keys pre-multiplied by the softmax scale (separate from the map's keys);
                                                    // under sequence parallelism the reverse: the rank's UNSCALED keys (the scaled ones are gathered)
   DevBuf ws_kmeans;                                // NABLA under sequence parallelism: gathered key-block means [P][H][slot blocks][64]
@@ -1863,6 +1877,12 @@ extern "C" void k5_dit_destroy(k5_dit* d) {
   for (hipEvent_t e : {d->ev_vel_ready, d->ev_vel_done, d->ev_u_o, d->ev_u_back}) if (e) (void)hipEventDestroy(e);
   if (d->pair.comm) (void)d->pair.CommDestroy(d->pair.comm);
   d->ws_vel_pair.release();
+  d->watch.wb.release();
+  for (int i = 0; i < 2; ++i) {
+    d->watch.rgb[i].release(); d->watch.x0[i].release();
+    if (d->watch.h_rgb[i]) (void)hipHostFree(d->watch.h_rgb[i]);
+    if (d->watch.ev[i]) (void)hipEventDestroy(d->watch.ev[i]);
+  }
   auto rel_attn = [](AttnW& a) {
     DevBuf* bs[] = {&a.wqk, &a.wq, &a.wk, &a.wv, &a.wo, &a.bqk, &a.bq, &a.bk, &a.bv, &a.bo, &a.norm};
     for (DevBuf* b : bs) b->release();
@@ -2135,6 +2155,32 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
       if (p0 < l1 && l0 < p1) { k5_set_error("%s: edit %s overlaps latent (latent is output only)", who, t.name); return K5_ERR_ARG; }
     }
   }
+  k5_dit::Watch& wt = d->watch;
+  const bool watching = wt.on;   // false: every line below that mentions the watch is skipped, the call enqueues what it always did
+  if (watching && (d->comm.active() || d->pair.active())) {
+    k5_set_error("%s: a watch is installed (k5_dit_set_watch) and the handle is in a %s: a rank that stops alone would leave its peers inside a "
+                 "collective", who, d->comm.active() ? "sequence-parallel group" : "CFG pair");
+    return K5_ERR_STATE;
+  }
+  wt.steps_done = 0; wt.stopped = 0;
+  const int64_t cells = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W;
+  if (watching) {
+    if (n <= 0) { k5_set_error("%s: bad shapes", who); return K5_ERR_ARG; }
+    for (hipEvent_t& e : wt.ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (wt.every > 0) {
+      const size_t rb = (size_t)cells * 3;
+      for (int i = 0; i < 2; ++i) {
+        K5CHK(wt.rgb[i].ensure(rb));
+        if (wt.want_x0) K5CHK(wt.x0[i].ensure((size_t)n * 4));
+      }
+      if (wt.h_bytes < rb) {
+        for (uint8_t*& h : wt.h_rgb) { if (h) (void)hipHostFree(h); h = nullptr; }
+        wt.h_bytes = 0;
+        for (uint8_t*& h : wt.h_rgb) HIPCHK(hipHostMalloc((void**)&h, rb, hipHostMallocDefault));
+        wt.h_bytes = rb;
+      }
+    }
+  }
   const bool cfg_on = fabsf(a->guidance_weight - 1.0f) > 1e-6f;  // generation_utils.py:63
   const bool pair = cfg_on && d->pair.active();                  // CFG-parallel: one branch here, the other on the paired handle
   if (pair) K5CHK(d->ws_vel_pair.ensure(2 * n * 2));
@@ -2230,15 +2276,63 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     if (step) K5CHK(k5_launch_step_inc(step, s));
     return K5_OK;
   };
+  // The watch: after_step(i) follows the launches of step i on the stream (on a preview step the preview kernel and the copy of its RGB to the
+  // slot's pinned buffer, then the slot's event); deliver(i) waits for that event on the host and calls back.  The loops below run
+  // deliver(i - 1) only once step i is enqueued, so the GPU has a step of work queued while the host waits and calls.
+  auto preview_at = [&](int i) { return wt.every > 0 && ((i + 1) % wt.every == 0 || i == a->num_steps - 1); };
+  auto after_step = [&](int i) -> int {
+    const int slot = i & 1;
+    if (preview_at(i)) {
+      Scope sc(d, s, "elementwise");
+      const float* wb = wt.wb.as<float>();
+      K5CHK(k5_launch_x0_preview(a->latent, vel_c, cfg_on ? vel_u : nullptr, a->guidance_weight, host_tab[2 * a->num_steps + i],
+                                 edit ? edit->source : nullptr, edit ? edit->keep_mask : nullptr, wb, wb + 3 * c.in_visual_dim,
+                                 wt.want_x0 ? wt.x0[slot].as<float>() : nullptr, wt.rgb[slot].as<uint8_t>(), cells, c.in_visual_dim, s));
+      HIPCHK(hipMemcpyAsync(wt.h_rgb[slot], wt.rgb[slot].p, (size_t)cells * 3, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipEventRecord(wt.ev[slot], s));
+    wt.steps_done = i + 1;
+    return K5_OK;
+  };
+  auto deliver = [&](int i) -> int {
+    const int slot = i & 1;
+    HIPCHK(hipEventSynchronize(wt.ev[slot]));
+    const bool pv = preview_at(i);
+    k5_watch_info info{};
+    info.step = i; info.num_steps = a->num_steps; info.sample = wt.sample; info.num_samples = wt.num_samples;
+    info.sigma_next = host_tab[2 * a->num_steps + i];
+    info.rgb = pv ? wt.h_rgb[slot] : nullptr;
+    info.x0 = pv && wt.want_x0 ? wt.x0[slot].as<float>() : nullptr;
+    info.T = a->fwd.T; info.H = a->fwd.H; info.W = a->fwd.W; info.C = c.in_visual_dim;
+    if (wt.fn(wt.user, &info) != 0) wt.stopped = 1;
+    return K5_OK;
+  };
+  auto watch_step = [&](int i) -> int {   // after step i is enqueued; the caller leaves its loop when wt.stopped
+    K5CHK(after_step(i));
+    if (i > 0) K5CHK(deliver(i - 1));
+    return K5_OK;
+  };
+  auto watch_end = [&]() -> int {   // the last step's callback; a stopped run ends with the stream drained
+    if (!wt.stopped) K5CHK(deliver(wt.steps_done - 1));
+    if (wt.stopped) HIPCHK(hipStreamSynchronize(s));
+    return K5_OK;
+  };
   if (!graph) {
     for (int i = 0; i < a->num_steps; ++i) {
       K5CHK(one_step(i));
       if (i == 0) K5CHK(decide_fuse());
+      if (watching) {
+        K5CHK(watch_step(i));
+        if (wt.stopped) break;
+      }
     }
+    if (watching) K5CHK(watch_end());
+    else wt.steps_done = a->num_steps;
     return K5_OK;
   }
   K5CHK(one_step(0));
   K5CHK(decide_fuse());
+  if (watching) K5CHK(watch_step(0));   // ahead of the capture: these launches are not part of the graph
   hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
   HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   const int rc = one_step(1);
@@ -2250,8 +2344,15 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   }
   if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(g); k5_set_error("hipGraphInstantiate failed"); return K5_ERR_HIP; }
   int status = K5_OK;
-  for (int i = 1; i < a->num_steps && status == K5_OK; ++i)
+  for (int i = 1; i < a->num_steps && status == K5_OK; ++i) {
     if (hipGraphLaunch(ge, s) != hipSuccess) { k5_set_error("hipGraphLaunch failed"); status = K5_ERR_HIP; }
+    else if (watching) {   // between graph launches, sigma_next as a host scalar
+      status = watch_step(i);
+      if (wt.stopped) break;
+    }
+  }
+  if (watching && status == K5_OK) status = watch_end();
+  if (!watching && status == K5_OK) wt.steps_done = a->num_steps;
   (void)hipStreamSynchronize(s);   // the executable graph must outlive its launches (this also orders the caller's stream after us)
   (void)hipGraphExecDestroy(ge); (void)hipGraphDestroy(g);
   (void)caller;
@@ -2308,12 +2409,49 @@ extern "C" int k5_sample_many(k5_dit* d, const k5_sample_many_args* a, void* str
     one.sigmas = a->sigmas;
     one.guidance_weight = a->guidance_weight;
     const float* vc = a->visual_cond ? a->visual_cond + (size_t)b * thw * (c.in_visual_dim + 1) : nullptr;
+    d->watch.sample = b; d->watch.num_samples = a->B;
     const int st = k5_sample_cond(d, &one, vc, stream);
+    d->watch.sample = 0; d->watch.num_samples = 1;
     if (st != K5_OK) {
       if (!g_err[0]) k5_set_error("k5_sample_many: sample %d failed with status %d", b, st);
       return st;
     }
+    if (d->watch.stopped) break;   // the callback stopped sample b: the samples after it stay as they came
   }
+  return K5_OK;
+}
+
+extern "C" int k5_dit_set_watch(k5_dit* d, const k5_watch* w) {
+  g_err[0] = 0;
+  if (!d) { k5_set_error("k5_dit_set_watch: null handle"); return K5_ERR_ARG; }
+  k5_dit::Watch& wt = d->watch;
+  if (!w) { wt.on = false; wt.fn = nullptr; wt.user = nullptr; wt.every = 0; wt.want_x0 = false; return K5_OK; }
+  if (!w->fn) { k5_set_error("k5_dit_set_watch: fn is NULL (pass a NULL watch to clear)"); return K5_ERR_ARG; }
+  if (w->preview_every < 0) { k5_set_error("k5_dit_set_watch: preview_every must be >= 0 (got %d)", w->preview_every); return K5_ERR_ARG; }
+  if (w->preview_every > 0 && !w->rgb_w) { k5_set_error("k5_dit_set_watch: previews (preview_every = %d) need rgb_w", w->preview_every); return K5_ERR_ARG; }
+  if (w->want_x0 && w->preview_every == 0) { k5_set_error("k5_dit_set_watch: want_x0 needs preview_every > 0 (x0 comes with the preview steps)"); return K5_ERR_ARG; }
+  if (d->comm.active() || d->pair.active()) {
+    k5_set_error("k5_dit_set_watch: the handle is in a %s: a rank that stops alone would leave its peers inside a collective",
+                 d->comm.active() ? "sequence-parallel group" : "CFG pair");
+    return K5_ERR_STATE;
+  }
+  if (w->preview_every > 0) {
+    const int C = d->cfg.in_visual_dim;
+    if (C <= 0 || (C & 3) || C > 64) { k5_set_error("k5_dit_set_watch: previews need in_visual_dim %% 4 == 0 and <= 64 (got %d)", C); return K5_ERR_UNSUPPORTED; }
+    std::vector<float> h((size_t)3 * C + 3, 0.0f);
+    memcpy(h.data(), w->rgb_w, (size_t)3 * C * sizeof(float));
+    if (w->rgb_b) memcpy(h.data() + 3 * C, w->rgb_b, 3 * sizeof(float));
+    K5CHK(wt.wb.ensure(h.size() * sizeof(float)));
+    HIPCHK(hipMemcpy(wt.wb.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  wt.fn = w->fn; wt.user = w->user; wt.every = w->preview_every; wt.want_x0 = w->want_x0 != 0; wt.on = true;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_watch_state(k5_dit* d, int* steps_done, int* stopped) {
+  if (!d) { k5_set_error("k5_dit_watch_state: null handle"); return K5_ERR_ARG; }
+  if (steps_done) *steps_done = d->watch.steps_done;
+  if (stopped) *stopped = d->watch.stopped;
   return K5_OK;
 }
 

@@ -382,6 +382,13 @@ int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, floa
              "k5_cfg_euler_edit");
 }
 
+int k5_x0_preview(const float* x, const void* v_cond, const void* v_uncond, float w, float sigma_next, const float* source,
+                  const float* keep_mask, const float* rgb_w, const float* rgb_b, float* x0_out, uint8_t* rgb, int64_t cells, int C,
+                  void* stream) {
+  return ret(k5_launch_x0_preview(x, v_cond, v_uncond, w, sigma_next, source, keep_mask, rgb_w, rgb_b, x0_out, rgb, cells, C,
+                                  (hipStream_t)stream), "k5_x0_preview");
+}
+
 int k5_conv3d_bf16(const void* X, const void* W, const float* bias, void* out, int Ts, int Hs, int Ws, int Cin, int Cout,
                    int up_t, int up_s, int ldc, const void* resid, int ldr, void* stream) {
   return ret(k5_launch_conv3d_bf16(X, W, bias, out, Ts, Hs, Ws, Cin, Cout, up_t, up_s, ldc, resid, ldr, (hipStream_t)stream),

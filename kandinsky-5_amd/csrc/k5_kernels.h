@@ -184,6 +184,13 @@ int k5_launch_edit_renoise(float* out, const float* source, const float* noise, 
 int k5_launch_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source,
                              const float* noise, const float* keep_mask, float sigma_next, int64_t cells, int C, hipStream_t stream,
                              const float* dtvec = nullptr, const float* signext = nullptr, const int* step = nullptr);
+// sampler preview: with v combined as in K18, x0 = x - sigma_next * v (fp32, uncontracted; keep_blend(x0, source, m) under a keep mask) on cells * C
+// elements, optionally stored as fp32 (x0_out), and rgb[cell][j] = sat_u8(rint((b[j] + sum_k W[k][j] x0[k]) * 127.5 + 127.5)), NaN -> 0, with
+// W [C][3] / b [3] (null = zeros) fp32 on the device.  rgb and rgb_w come together or not at all; one of rgb / x0_out is needed.  C % 4 == 0 and
+// C <= 64, otherwise K5_ERR_UNSUPPORTED; x, x0_out and source 16-byte aligned, the velocities 8-byte.  Nothing is launched when it refuses.
+int k5_launch_x0_preview(const float* x, const void* v_cond, const void* v_uncond, float w, float sigma_next, const float* source,
+                         const float* keep_mask, const float* rgb_w, const float* rgb_b, float* x0_out, uint8_t* rgb, int64_t cells, int C,
+                         hipStream_t stream);
 // fp32 -> bf16 cast, bf16 -> fp32
 int k5_launch_cast_f32_bf16(const float* x, void* out, int64_t n, hipStream_t stream);
 // weight packing: src [rows][cols] (K5_F32 / K5_BF16 / K5_F16, device) -> dst [rows][ld] bf16 (RNE) or fp32, pad columns zeroed

@@ -1080,3 +1080,95 @@ int k5_launch_lora_merge(void* W, int w_dtype, int rows, int cols, int ld, const
                        b_dtype, R, scale, tiles_n);
   return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
 }
+
+// ---------------------------------------------------------------------------------------------
+// (kept at the end of the file: the kernels above stay where they were in the code object)
+namespace {
+
+// Live preview of the sampler (the watch of k5_dit_set_watch, k5_x0_preview): after the update of a step the latent x sits at sigma_next and the
+// velocity buffers still hold that step's velocities, so the denoised estimate of flow matching is x0 = x - sigma_next * v with v combined as
+// in cfg_euler_kernel (the same expression, the same bf16 rounding points).  The product and the difference round to fp32 each on its own
+// (nothing contracted), sigma_next == 0 hands x through, and with a keep mask x0 = keep_blend(x0, source, m): kept cells show the source.
+__device__ __forceinline__ float x0_estimate(float x, float sigma, float v) {
+#pragma clang fp contract(off)
+  const float p = sigma * v;
+  return x - p;
+}
+
+// Four lanes per latent cell (a quad), one 16-byte load of the latent per lane and round: lane q of the quad owns the 4-channel chunks q, q + 4,
+// q + 8, q + 12 of its cell, so a quad reads 64 consecutive bytes and (C = 16) a wave 1 KiB.  RGB: rgb[j] = sat_u8(rint((b[j] + sum_k W[k][j]
+// x0[k]) * 127.5 + 127.5)), NaN -> 0.  The order of the sum is fixed: lane q runs acc = fma(W[k][j], x0[k], acc) from acc = 0 over its own
+// channels in ascending k; then s = acc + acc(lane ^ 1), s = s + s(lane ^ 2) — the same bits in all four lanes, fp32 addition commutes —
+// t = b[j] + s and one fma(t, 127.5, 127.5).  Lanes 0..2 of the quad store one byte each.  Every lane of a wave reaches the two exchanges (a
+// lane past the last cell carries zeros and stores nothing): a wave-wide exchange must not sit under a lane-dependent branch.
+__global__ __launch_bounds__(256) void x0_preview_kernel(const float* __restrict__ x, const bf16_t* __restrict__ vc,
+                                                         const bf16_t* __restrict__ vu, float w, float sigma_next,
+                                                         const float* __restrict__ source, const float* __restrict__ mask,
+                                                         const float* __restrict__ rgb_w, const float* __restrict__ rgb_b,
+                                                         float* __restrict__ x0_out, uint8_t* __restrict__ rgb, int C, int64_t cells) {
+  __shared__ float sw[64 * 3 + 3];   // W [C][3], then b [3]
+  for (int i = threadIdx.x; i < 3 * C + 3; i += 256)
+    sw[i] = !rgb_w ? 0.f : (i < 3 * C ? rgb_w[i] : (rgb_b ? rgb_b[i - 3 * C] : 0.f));
+  __syncthreads();
+  const int q = threadIdx.x & 3, nch = C >> 2;
+  const int64_t rounds = (cells + 63) / 64;   // 64 cells per workgroup and round
+  for (int64_t r = blockIdx.x; r < rounds; r += gridDim.x) {
+    const int64_t cell = r * 64 + (threadIdx.x >> 2);
+    const bool live = cell < cells;
+    float acc[3] = {0.f, 0.f, 0.f};
+    if (live) {
+      const float m = mask ? mask[cell] : 0.0f;
+      for (int ch = q; ch < nch; ch += 4) {
+        const int64_t e = cell * C + 4 * ch;
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + e);
+        const u32x2 cr = *reinterpret_cast<const u32x2*>(vc + e);
+        u32x2 ur = {0u, 0u};
+        if (vu) ur = *reinterpret_cast<const u32x2*>(vu + e);
+        f32x4 sv = {0.f, 0.f, 0.f, 0.f};
+        if (m != 0.0f) sv = *reinterpret_cast<const f32x4*>(source + e);
+        f32x4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const uint32_t cw = cr[k >> 1], uw = ur[k >> 1];
+          float v = __uint_as_float((k & 1) ? (cw & 0xffff0000u) : (cw << 16));
+          if (vu) {  // as cfg_euler_kernel
+            const float u = __uint_as_float((k & 1) ? (uw & 0xffff0000u) : (uw << 16));
+            v = bf_round(__fadd_rn(u, bf_round(__fmul_rn(w, bf_round(__fsub_rn(v, u))))));
+          }
+          float z = sigma_next == 0.0f ? xv[k] : x0_estimate(xv[k], sigma_next, v);
+          if (m != 0.0f) z = keep_blend(z, sv[k], m);
+          o[k] = z;
+          const float* wk = sw + (4 * ch + k) * 3;
+          acc[0] = fmaf(wk[0], z, acc[0]); acc[1] = fmaf(wk[1], z, acc[1]); acc[2] = fmaf(wk[2], z, acc[2]);
+        }
+        if (x0_out) *reinterpret_cast<f32x4*>(x0_out + e) = o;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      acc[j] = acc[j] + __shfl_xor(acc[j], 1);
+      acc[j] = acc[j] + __shfl_xor(acc[j], 2);
+    }
+    if (live && rgb && q < 3) {
+      const float s = q == 0 ? acc[0] : (q == 1 ? acc[1] : acc[2]);
+      const float val = rintf(fmaf(sw[3 * C + q] + s, 127.5f, 127.5f));
+      rgb[cell * 3 + q] = !(val >= 0.0f) ? (uint8_t)0 : (val > 255.0f ? (uint8_t)255 : (uint8_t)val);   // NaN fails the first test
+    }
+  }
+}
+
+}  // namespace
+
+int k5_launch_x0_preview(const float* x, const void* vc, const void* vu, float w, float sigma_next, const float* source,
+                         const float* keep_mask, const float* rgb_w, const float* rgb_b, float* x0_out, uint8_t* rgb, int64_t cells, int C,
+                         hipStream_t s) {
+  if (C <= 0 || (C & 3) || C > 64) return K5_ERR_UNSUPPORTED;   // a quad's 16-byte loads and the LDS copy of W
+  if (!x || !vc || cells <= 0 || (!rgb && !x0_out) || ((rgb != nullptr) != (rgb_w != nullptr)) || (keep_mask && !source)) return K5_ERR_ARG;
+  const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
+  if (misaligned(x, 16) || misaligned(x0_out, 16) || (keep_mask && misaligned(source, 16)) || misaligned(vc, 8) || misaligned(vu, 8) ||
+      misaligned(keep_mask, 4) || misaligned(rgb_w, 4) || misaligned(rgb_b, 4))
+    return K5_ERR_ARG;
+  hipLaunchKernelGGL(x0_preview_kernel, dim3(grid_for(cells, 64)), dim3(256), 0, s, x, (const bf16_t*)vc, (const bf16_t*)vu, w, sigma_next,
+                     keep_mask ? source : nullptr, keep_mask, rgb_w, rgb_b, x0_out, rgb, C, cells);
+  return done();
+}

@@ -58,6 +58,50 @@ class EditArgs(C.Structure):
     _fields_ = [("source", C.c_void_p), ("noise", C.c_void_p), ("keep_mask", C.c_void_p)]
 
 
+class WatchInfo(C.Structure):   # k5_watch_info
+    _fields_ = [("step", C.c_int), ("num_steps", C.c_int), ("sample", C.c_int), ("num_samples", C.c_int), ("sigma_next", C.c_float),
+                ("rgb", C.POINTER(C.c_uint8)), ("x0", C.POINTER(C.c_float)), ("T", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int)]
+
+
+WATCH_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(WatchInfo))   # k5_watch_fn: non-zero = stop
+
+
+class Watch(C.Structure):       # k5_watch
+    _fields_ = [("fn", WATCH_FN), ("user", C.c_void_p), ("preview_every", C.c_int), ("want_x0", C.c_int),
+                ("rgb_w", C.POINTER(C.c_float)), ("rgb_b", C.POINTER(C.c_float))]
+
+
+class WatchTrampoline:
+    """The C side of a Python watch callback.  ctypes prints and swallows an exception that escapes a callback, so the trampoline catches
+    it, keeps it in `error` for the caller of k5_sample* to re-raise, and answers "stop".  `stop_requested` tells a stop the callback asked
+    for (a truthy return) from one forced by an exception.  `wrap(info)` turns the k5_watch_info into what the callback receives."""
+
+    def __init__(self, callback, wrap=None):
+        self.callback, self.wrap = callback, (wrap or (lambda info: info))
+        self.error, self.stop_requested, self.last_sample = None, False, 0
+        self.c_fn = WATCH_FN(self._call)   # kept alive with the trampoline: the engine holds the raw pointer
+
+    def reset(self):
+        self.error, self.stop_requested, self.last_sample = None, False, 0
+
+    def _call(self, user, info):
+        try:
+            self.last_sample = int(getattr(info.contents, "sample", 0))   # which sample of a k5_sample_many call the callback last saw
+            if self.callback(self.wrap(info.contents)):
+                self.stop_requested = True
+                return 1
+            return 0
+        except BaseException as e:   # noqa: BLE001 — KeyboardInterrupt too: it must come out of sample(), not vanish in ctypes
+            self.error = e
+            return 1
+
+    def reraise(self):
+        """Raise what the callback raised during the last call, once."""
+        e, self.error = self.error, None
+        if e is not None:
+            raise e
+
+
 class VaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int), ("out_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -148,6 +192,9 @@ SYMBOLS = {
     "k5_sample_edit": (_I, [_P, C.POINTER(SampleArgs), _P, C.POINTER(EditArgs), _P]),
     "k5_edit_renoise": (_I, [_P, _P, _P, _F, _I64, _P]),
     "k5_cfg_euler_edit": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _F, _I64, _I, _P]),
+    "k5_x0_preview": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I64, _I, _P]),
+    "k5_dit_set_watch": (_I, [_P, C.POINTER(Watch)]),
+    "k5_dit_watch_state": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
     "k5_dit_forward_many": (_I, [_P, C.POINTER(ForwardArgs), _I, C.POINTER(TextCond), _P, _P]),
     "k5_comm_unique_id": (_I, [C.c_char_p, _P]),
     "k5_dit_comm_init": (_I, [_P, C.c_char_p, _I, _I, _P]),
@@ -211,7 +258,7 @@ def lib() -> C.CDLL:
     for name, (res, args) in SYMBOLS.items():
         try:
             fn = getattr(L, name)
-        except AttributeError as e:   # a libk5.so of the same ABI number from before an added export (the MagCache calibration, LoRA and editing ones)
+        except AttributeError as e:   # a libk5.so of the same ABI number from before an added export (the MagCache calibration, LoRA, editing and watch ones)
             raise RuntimeError(f"{LIB_PATH} does not export {name}: rebuild it with `python kandinsky-5_amd/build.py`") from e
         fn.restype = res
         fn.argtypes = args
@@ -432,3 +479,48 @@ def cfg_euler_edit_(img, v_cond, v_uncond, w, dt, source, noise, keep_mask, sigm
     check(lib().k5_cfg_euler_edit(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), ptr(source), ptr(noise), ptr(keep_mask),
                                   float(sigma_next), cells, C_, stream_ptr(img.device)), "k5_cfg_euler_edit")
     return img
+
+
+def x0_preview(img, v_cond, v_uncond, w, sigma_next, rgb_factors=None, rgb_bias=None, source=None, keep_mask=None, want_x0=False,
+               out_rgb=None, out_x0=None):
+    """(preview, x0) of the latent `img` (fp32 (..., C), C % 4 == 0 and <= 64) just after the update of a step that took it to sigma_next, with
+    the step's velocities still in v_cond / v_uncond (k5_x0_preview): x0 = img - sigma_next * v, v combined as in cfg_euler_; under a
+    keep_mask ((..., 1), with `source`) kept cells show the source.  preview: uint8 (..., 3) from rgb_factors [C][3] / rgb_bias [3] (fp32, moved
+    to the device), None without factors; x0: fp32 like img, None unless want_x0.  out_rgb / out_x0: buffers to fill instead of new ones."""
+    _need_cuda(img, v_cond, v_uncond, source, keep_mask, out_rgb, out_x0)
+    C_ = img.shape[-1]
+    cells = img.numel() // C_
+    for t in (img, source):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != img.shape):
+            raise ValueError("x0_preview: img and source must be contiguous fp32 tensors of one shape")
+    if keep_mask is not None and (source is None or keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous() or keep_mask.numel() != cells):
+        raise ValueError("x0_preview: keep_mask must be a contiguous fp32 tensor with one value per cell and needs source")
+    for v in (v_cond, v_uncond):
+        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != img.numel()):
+            raise ValueError("x0_preview: the velocities must be contiguous bf16 tensors of img's size")
+    wd = bd = None
+    if rgb_factors is not None:
+        wd = torch.as_tensor(rgb_factors, dtype=torch.float32).to(img.device).contiguous()
+        if tuple(wd.shape) != (C_, 3):
+            raise ValueError(f"x0_preview: rgb_factors must be [{C_}][3], got {tuple(wd.shape)}")
+        if rgb_bias is not None:
+            bd = torch.as_tensor(rgb_bias, dtype=torch.float32).to(img.device).contiguous()
+            if bd.numel() != 3:
+                raise ValueError("x0_preview: rgb_bias must hold 3 values")
+        if out_rgb is None:
+            out_rgb = torch.empty(tuple(img.shape[:-1]) + (3,), dtype=torch.uint8, device=img.device)
+    else:
+        out_rgb = None
+    if want_x0 and out_x0 is None:
+        out_x0 = torch.empty_like(img)
+    if not want_x0:
+        out_x0 = None
+    if out_rgb is not None and (out_rgb.dtype != torch.uint8 or not out_rgb.is_contiguous() or out_rgb.numel() != cells * 3):
+        raise ValueError("x0_preview: out_rgb must be a contiguous uint8 tensor of 3 values per cell")
+    if out_x0 is not None and (out_x0.dtype != torch.float32 or not out_x0.is_contiguous() or out_x0.numel() != img.numel()):
+        raise ValueError("x0_preview: out_x0 must be a contiguous fp32 tensor of img's size")
+    with torch.cuda.device(img.device):
+        check(lib().k5_x0_preview(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(sigma_next), ptr(source if keep_mask is not None else None),
+                                  ptr(keep_mask), ptr(wd), ptr(bd), ptr(out_x0), ptr(out_rgb), cells, C_, stream_ptr(img.device)),
+              "k5_x0_preview")
+    return out_rgb, out_x0

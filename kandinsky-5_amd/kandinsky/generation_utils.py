@@ -102,10 +102,78 @@ def _check_edit_args(model, shape, init_latent, strength, keep_mask):
                          "read the wrong rows (a keep_mask at strength 1 is allowed)")
 
 
+def _is_multi_rank_engine(model):
+    from .models.dit import DiffusionTransformer3D
+    return type(model) is DiffusionTransformer3D and (model._sp is not None or model._cfg_pair is not None)
+
+
+class _StepWatch:
+    """`generate`'s progress bar and callback as one per-step hook, shared by the fused path (installed as the engine's watch) and the
+    per-step Python paths (called from the loop), so a callback sees the same sequence whichever ran."""
+
+    def __init__(self, model, callback, preview_every, preview_factors, want_x0, progress, total, channels):
+        from .models.dit import check_watch_args
+        from .preview import as_factors
+        W, b = as_factors(preview_factors)
+        self.W, self.every = check_watch_args(callback, preview_every, W, want_x0, channels)
+        self.b = None if (b is None or self.W is None) else torch.as_tensor(b, dtype=torch.float32).reshape(-1)
+        self.callback, self.want_x0 = callback, bool(want_x0)
+        self.sample, self.num_samples = 0, 1
+        self.bar = None
+        if _is_multi_rank_engine(model):
+            if callback is not None:
+                raise ValueError("callback= needs a single-rank model: on a sequence-parallel group or a CFG pair a rank that stops alone "
+                                 "would leave its peers inside a collective (watching is single-rank only)")
+        elif progress:
+            try:
+                from tqdm import tqdm
+                self.bar = tqdm(total=int(total))
+            except ImportError:   # progress is a courtesy: without tqdm there is simply no bar
+                self.bar = None
+        self.active = callback is not None or self.bar is not None
+
+    def preview_at(self, i, n):
+        return self.every > 0 and ((i + 1) % self.every == 0 or i == n - 1)
+
+    def step(self, info):
+        if self.num_samples > 1 and info.num_samples == 1:   # samples that run as calls of their own (generate(batch=) off the many-sample path)
+            info.sample, info.num_samples = self.sample, self.num_samples
+        if self.bar is not None:
+            self.bar.update(1)
+        return bool(self.callback(info)) if self.callback is not None else False
+
+    def close(self):
+        if self.bar is not None:
+            self.bar.close()
+            self.bar = None
+
+    def installed(self, model):
+        """Context: this hook as the watch of an engine-backed model for one sample / sample_many call; what was there before comes back."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            if not self.active:
+                yield
+                return
+            before = model._watch
+            try:
+                model.set_watch(self.step, self.every, self.W, self.b, self.want_x0)
+                yield
+            finally:
+                model._watch = before
+                if before is not None:
+                    model._install_watch()
+                else:
+                    model.clear_watch()
+        return ctx()
+
+
 @torch.no_grad()
 def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
              null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=False, seed=6554, noise=None, *,
-             visual_cond=None, visual_cond_mask=None, batch=1, init_latent=None, strength=1.0, keep_mask=None):
+             visual_cond=None, visual_cond_mask=None, batch=1, init_latent=None, strength=1.0, keep_mask=None,
+             callback=None, preview_every=0, preview_factors=None, preview_x0=False, _watch=None):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -118,7 +186,15 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     from (1 - sigma) * init_latent + sigma * noise at step `first = edit_first_step(num_steps, strength)` and runs the tail of the
     schedule.  `keep_mask` (shape[:-1] + (1,)) in [0, 1]: where it is 1 the result is `init_latent` bit for bit, the rest is
     generated around it (the kept region is re-imposed at every step's sigma on the device).  strength = 1 without a mask is the
-    plain run on `noise`, bit for bit.  With batch > 1 the samples run one at a time."""
+    plain run on `noise`, bit for bit.  With batch > 1 the samples run one at a time.
+    `progress` draws a tqdm bar over batch x steps when tqdm is installed (nothing otherwise, and nothing on a multi-rank engine model).
+    `callback`, `preview_every`, `preview_factors`, `preview_x0` (optional, extension): `callback(info)` runs after every step with a
+    `kandinsky.models.dit.StepInfo`; a truthy return stops the run (`SamplingInterrupted` carries steps_done and the latent), an exception
+    comes out as itself.  `preview_every` = k > 0 puts a CPU uint8 (T,H,W,3) `info.preview` of the denoised estimate on the steps with
+    (step + 1) % k == 0 and on the last one, through `preview_factors` (a JSON path or (W [C][3], b [3]); `kandinsky.preview`;
+    no default table ships), and with `preview_x0` the estimate itself as `info.x0` (device, valid during the call).  The engine-backed
+    model keeps its in-engine loop (k5_dit_set_watch: the callback runs one step behind the GPU); the per-step paths call back from their
+    Python loop with the same kernel, so the sequence and the preview bits are the same.  ValueError on a multi-rank engine model."""
     from .models.dit import split_per_sample
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
@@ -129,6 +205,17 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         text_embeds, null_text_embeds, text_rope_pos, null_text_rope_pos = (
             split_per_sample(v, 1, n)[0] for v, n in ((text_embeds, "text_embeds"), (null_text_embeds, "null_text_embeds"),
                                                  (text_rope_pos, "text_rope_pos"), (null_text_rope_pos, "null_text_rope_pos")))
+    if _watch is None:   # the outermost call owns the hook (and closes the bar); the per-sample calls of a batch share it
+        steps_run = num_steps - (edit_first_step(num_steps, strength) if init_latent is not None else 0)
+        watch = _StepWatch(model, callback, preview_every, preview_factors, preview_x0, progress, batch * steps_run, shape[-1])
+        try:
+            return generate(model, device, shape, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
+                            null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=progress, seed=seed, noise=noise,
+                            visual_cond=visual_cond, visual_cond_mask=visual_cond_mask, batch=batch, init_latent=init_latent,
+                            strength=strength, keep_mask=keep_mask, _watch=watch)
+        finally:
+            watch.close()
+    watch = _watch
     if noise is None:
         g = torch.Generator(device="cuda")
         g.manual_seed(seed)
@@ -139,7 +226,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     if batch > 1:
         return _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                                null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond,
-                               visual_cond_mask, init_latent, strength, keep_mask)
+                               visual_cond_mask, init_latent, strength, keep_mask, watch)
     edit = None
     if init_latent is not None:   # img (the draw) is eps from here on; the latent is a buffer of its own that the engine fills
         src = init_latent.to(device=img.device, dtype=torch.float32).contiguous()
@@ -172,6 +259,22 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         else:
             E.cfg_euler_edit_(img, v, u, guidance_weight, timestep_diff, edit[0], edit[1], edit[2], sigma_next)
 
+    def after_step(i, v, u, sigma_next):
+        """the per-step paths' side of the watch: the preview of the step just applied (the engine's kernel, the engine's rule for which
+        steps carry one) and the callback"""
+        if not watch.active:
+            return
+        from .models.dit import SamplingInterrupted, StepInfo
+        n = len(timesteps) - 1
+        preview = x0 = None
+        if watch.preview_at(i, n):
+            km = None if edit is None else edit[2]
+            rgb, x0 = E.x0_preview(img, v, u, guidance_weight, sigma_next, watch.W, watch.b, source=None if km is None else edit[0],
+                                   keep_mask=km, want_x0=watch.want_x0)
+            preview = rgb.cpu()
+        if watch.step(StepInfo(i, n, watch.sample, watch.num_samples, sigma_next, preview, x0)):
+            raise SamplingInterrupted(i + 1, img, watch.sample)
+
     from .models.dit import DiffusionTransformer3D
     if isinstance(model, torch.nn.Module):      # per-step paths below: a new sampling run starts with no softmax-form memory (k5_sample resets its own)
         for m in model.modules():
@@ -190,7 +293,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         both = None
         if edit is not None:
             E.renoise(edit[0], edit[1], float(timesteps[0]), out=img)
-        for timestep, timestep_diff, sigma_next in zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(), timesteps[1:].tolist()):
+        for i, (timestep, timestep_diff, sigma_next) in enumerate(zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(),
+                                                                      timesteps[1:].tolist())):
             x = img if cond_in is None else torch.cat([img, *cond_in], dim=-1)
             v = model(x, mine["text_embeds"], mine["pooled_embed"], torch.tensor([timestep]) * 1000, visual_rope_pos,
                       mine_pos, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
@@ -198,18 +302,21 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
                 both = torch.empty((2,) + tuple(v.shape), dtype=v.dtype, device=v.device)
             vc, vu = exchange_velocity(v, pair_group, out=both)
             update(vc, vu, timestep_diff, sigma_next)
+            after_step(i, vc, vu, sigma_next)
         return img
     if type(model) is DiffusionTransformer3D and model.visual_cond in (True, False):
         # whole loop inside the engine: no per-step host work at all
-        model.sample(img, timesteps.tolist(), text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
-                     null_text_rope_pos, guidance_weight, scale_factor=conf.metrics.scale_factor,
-                     sparse_params=sparse_params,
-                     visual_cond=None if cond_in is None else torch.cat(cond_in, dim=-1).contiguous(), edit=edit)
+        with watch.installed(model):
+            model.sample(img, timesteps.tolist(), text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
+                         null_text_rope_pos, guidance_weight, scale_factor=conf.metrics.scale_factor,
+                         sparse_params=sparse_params,
+                         visual_cond=None if cond_in is None else torch.cat(cond_in, dim=-1).contiguous(), edit=edit)
         return img
 
     if edit is not None:
         E.renoise(edit[0], edit[1], float(timesteps[0]), out=img)
-    for timestep, timestep_diff, sigma_next in zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(), timesteps[1:].tolist()):
+    for i, (timestep, timestep_diff, sigma_next) in enumerate(zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(),
+                                                                  timesteps[1:].tolist())):
         if model.visual_cond:
             if cond_in is None:
                 vc = torch.zeros_like(img)
@@ -227,13 +334,15 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
             u = model(model_input, null_text_embeds["text_embeds"], null_text_embeds["pooled_embed"], t1000,
                       visual_rope_pos, null_text_rope_pos, scale_factor=conf.metrics.scale_factor,
                       sparse_params=sparse_params)
-        update(v.contiguous(), None if u is None else u.contiguous(), timestep_diff, sigma_next)
+        v, u = v.contiguous(), None if u is None else u.contiguous()
+        update(v, u, timestep_diff, sigma_next)
+        after_step(i, v, u, sigma_next)
     return img
 
 
 def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                     null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond, visual_cond_mask,
-                    init_latent=None, strength=1.0, keep_mask=None):
+                    init_latent=None, strength=1.0, keep_mask=None, watch=None):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
     from .models.dit import split_per_sample
     T = img.shape[0] // batch
@@ -263,16 +372,19 @@ def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text
             cond = torch.cat([vc, vm], dim=-1).reshape(batch, T, *img.shape[1:-1], img.shape[-1] + 1).contiguous()
         sparse_params = get_sparse_params(conf, {"visual": img[:T]}, device)
         timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()
-        model.sample_many(img.view(batch, T, *img.shape[1:]), timesteps.tolist(), tes, nes, visual_rope_pos, tps, nps,
-                           guidance_weight, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params, visual_cond=cond)
+        with watch.installed(model):
+            model.sample_many(img.view(batch, T, *img.shape[1:]), timesteps.tolist(), tes, nes, visual_rope_pos, tps, nps,
+                               guidance_weight, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params, visual_cond=cond)
         return img
     # any other model (rank groups, MagCache, graph replay, wrapped or duck-typed models) and editing: today's path, one sample at a time
+    watch.num_samples = batch
     for b in range(batch):
+        watch.sample = b
         img[b * T:(b + 1) * T] = generate(model, device, (T,) + tuple(img.shape[1:]), num_steps, tes[b], nes[b], visual_rope_pos,
                                           tps[b], nps[b], guidance_weight, scheduler_scale, conf, progress=progress, seed=seed,
                                           noise=img[b * T:(b + 1) * T], visual_cond=part(visual_cond, b),
                                           visual_cond_mask=part(visual_cond_mask, b), init_latent=part(init_latent, b),
-                                          strength=strength, keep_mask=part(keep_mask, b))
+                                          strength=strength, keep_mask=part(keep_mask, b), _watch=watch)
     return img
 
 
@@ -311,7 +423,8 @@ def frames_to_uint8(frames):
 
 def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25, guidance_weight=5.0,
                     scheduler_scale=1, negative_caption="", seed=6554, device="cuda", vae_device="cuda",
-                    text_embedder_device="cuda", progress=True, offload=False, image=None, video=None, strength=1.0, mask=None):
+                    text_embedder_device="cuda", progress=True, offload=False, image=None, video=None, strength=1.0, mask=None,
+                    callback=None, preview_every=0, preview_factors=None):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -319,7 +432,9 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     one noise draw of the whole shape (see `generate`).  `video`, `strength`, `mask` (optional, extension): video-to-video and masked
     editing.  `video` is the source clip (uint8 (F,H,W,3) or float (F,3,H,W) frames, see conditioning.preprocess_video), `strength`
     in (0, 1] how much of the schedule runs on it and `mask` a pixel keep mask ((H,W) or (F,H,W), >= 0.5 = keep the source there, at
-    8 * height x 8 * width, see conditioning.pixel_mask_to_latent); every sample of the batch edits the same clip."""
+    8 * height x 8 * width, see conditioning.pixel_mask_to_latent); every sample of the batch edits the same clip.
+    `progress` draws a tqdm bar over the sampling steps when tqdm is installed; `callback`, `preview_every`, `preview_factors`
+    (optional, extension): per-step callback, cancel and live previews, see `generate`."""
     batch, frames, height, width, channels = shape
     captions = list(caption) if isinstance(caption, (list, tuple)) else [caption] * batch
     if len(captions) != batch:
@@ -368,7 +483,8 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     with torch.no_grad():
         latent = generate(dit, device, (batch * frames, height, width, channels), num_steps, cond, uncond, grid,
                           text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
-                          progress=progress, batch=batch, **cond_kw)
+                          progress=progress, batch=batch, callback=callback, preview_every=preview_every,
+                          preview_factors=preview_factors, **cond_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

@@ -66,6 +66,64 @@ def split_per_sample(value, n, name):
     return [value] * n
 
 
+class SamplingInterrupted(RuntimeError):
+    """A watch callback (`DiffusionTransformer3D.set_watch`, `generate(callback=)`) returned a truthy value: the run stopped after
+    `steps_done` steps — at most one past the step the callback saw — and `latent` holds the state at that point (of sample `sample` of a
+    `sample_many` call; the samples after it are as they came)."""
+
+    def __init__(self, steps_done, latent, sample=0):
+        super().__init__(f"sampling interrupted by the callback after {steps_done} steps" + (f" of sample {sample}" if sample else ""))
+        self.steps_done, self.latent, self.sample = int(steps_done), latent, int(sample)
+
+
+class StepInfo:
+    """What a watch callback receives after every step: `step` (0-based, just completed) of `num_steps`, `sample` of `num_samples`
+    (`sample_many` / `generate(batch=)`; 0 of 1 otherwise), `sigma` the latent now sits at, `preview` a CPU uint8 tensor (T,H,W,3) on a
+    preview step (None otherwise) and `x0` the denoised estimate, a device fp32 (T,H,W,C) tensor valid ONLY during the call (clone it to
+    keep it; None unless asked for with want_x0, and on steps without a preview)."""
+    __slots__ = ("step", "num_steps", "sample", "num_samples", "sigma", "preview", "x0")
+
+    def __init__(self, step, num_steps, sample, num_samples, sigma, preview, x0):
+        self.step, self.num_steps, self.sample, self.num_samples = int(step), int(num_steps), int(sample), int(num_samples)
+        self.sigma, self.preview, self.x0 = float(sigma), preview, x0
+
+    def __repr__(self):
+        return (f"StepInfo(step={self.step}/{self.num_steps}, sample={self.sample}/{self.num_samples}, sigma={self.sigma:.4f}, "
+                f"preview={'yes' if self.preview is not None else 'no'}, x0={'yes' if self.x0 is not None else 'no'})")
+
+
+class _DeviceView:
+    """A raw device pointer as something torch.as_tensor can view without a copy (the CUDA array interface)."""
+
+    def __init__(self, address, shape):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "<f4", "data": (int(address), False), "version": 2,
+                                         "strides": None}
+
+
+def check_watch_args(callback, preview_every, rgb_factors, want_x0, channels):
+    """The ValueErrors of `set_watch` / `generate(callback=, preview_every=, preview_factors=)`; returns (W [C][3], preview_every)."""
+    preview_every = int(preview_every)
+    if callback is not None and not callable(callback):
+        raise ValueError("callback must be callable")
+    if preview_every < 0:
+        raise ValueError(f"preview_every must be >= 0, got {preview_every}")
+    if preview_every > 0 and callback is None:
+        raise ValueError("preview_every needs a callback to hand the previews to")
+    if preview_every > 0 and rgb_factors is None:
+        raise ValueError("previews need latent -> RGB factors and no default table ships: fit one from a generation of your checkpoint "
+                         "with kandinsky.preview.fit_rgb_factors (test.py --fit_preview_factors OUT.json) and pass it")
+    if want_x0 and preview_every == 0:
+        raise ValueError("want_x0 needs preview_every > 0: x0 is computed on the preview steps")
+    W = None
+    if preview_every > 0:
+        W = torch.as_tensor(rgb_factors, dtype=torch.float32).cpu().contiguous()
+        if tuple(W.shape) != (channels, 3):
+            raise ValueError(f"rgb_factors must be [{channels}][3], got {tuple(W.shape)}")
+        if channels % 4 or channels > 64:
+            raise ValueError(f"previews need a latent of C % 4 == 0 and C <= 64 channels, got {channels}")
+    return W, preview_every
+
+
 class DiffusionTransformer3D(nn.Module):
     def __init__(
         self,
@@ -114,6 +172,7 @@ class DiffusionTransformer3D(nn.Module):
         self._settings = {"fp8": False, "graph": False, "options": {}}   # re-applied when the engine is rebuilt
         self._lora = []              # (entries, strength) merged into the ENGINE's packed weights: re-added when the engine is rebuilt
         self._lora_saved = {}        # parameters as they were before a merge done in torch (no engine yet): key -> tensor
+        self._watch = None           # (trampoline, k5_watch and the arrays it points to) of set_watch: re-installed when the engine is rebuilt
 
     # ---------------------------------------------------------------- engine lifetime
     def _destroy_engine(self, force=False):
@@ -180,6 +239,8 @@ class DiffusionTransformer3D(nn.Module):
                 E.check(E.lib().k5_dit_set_option(self._handle, k.encode(), int(v)), f"k5_dit_set_option({k})")
         for entries, strength in getattr(self, "_lora", []):   # the rebuilt engine packed the parameters, which an engine-side merge never touched
             self._engine_add_lora(entries, strength)
+        if getattr(self, "_watch", None) is not None:
+            self._install_watch()
         if getattr(self, "mag_ratios", None) is not None or getattr(self, "_magcache_calibrate", None) is not None:   # set before the weights were loaded / the handle rebuilt
             from ..magcache_utils import _apply
             _apply(self)
@@ -322,6 +383,7 @@ class DiffusionTransformer3D(nn.Module):
         sig = [float(v) for v in sigmas]
         arr = (C.c_float * len(sig))(*sig)
         s.latent, s.num_steps, s.sigmas, s.guidance_weight = latent.data_ptr(), len(sig) - 1, arr, float(guidance_weight)
+        self._watch_begin()
         with torch.cuda.device(dev):
             if edit is not None:
                 ea = E.EditArgs(edit[0].data_ptr(), edit[1].data_ptr(), E.ptr(edit[2]))
@@ -330,7 +392,89 @@ class DiffusionTransformer3D(nn.Module):
                 E.check(E.lib().k5_sample(h, C.byref(s), E.stream_ptr(dev)), "k5_sample")
             else:
                 E.check(E.lib().k5_sample_cond(h, C.byref(s), visual_cond.data_ptr(), E.stream_ptr(dev)), "k5_sample_cond")
+        self._watch_end(latent)
         return latent
+
+    # ---------------------------------------------------------------- watch: progress, cancel, previews
+    def set_watch(self, callback=None, preview_every=0, rgb_factors=None, rgb_bias=None, want_x0=False):
+        """Progress, cancel and live previews out of `sample` / `sample_many` (k5_dit_set_watch).  `callback(info)` runs after every step on
+        the calling thread with a `StepInfo`; a truthy return stops the run and `sample` raises `SamplingInterrupted(steps_done, latent)`,
+        an exception raised in the callback stops it too and comes out of `sample` as itself.  `preview_every` = k > 0: the steps with
+        (step + 1) % k == 0 and always the last one carry `info.preview`, a CPU uint8 (T,H,W,3) view of the denoised estimate through
+        `rgb_factors` [C][3] and `rgb_bias` [3] (`kandinsky.preview.fit_rgb_factors`; no default table ships), and with `want_x0` also
+        `info.x0`.  The engine runs one step ahead of the callback, so the GPU never waits for it; the callback must not use this model.
+        A single-rank model only: a rank that stops alone would leave its peers inside a collective.  callback None = `clear_watch`."""
+        if callback is None:
+            return self.clear_watch()
+        W, every = check_watch_args(callback, preview_every, rgb_factors, want_x0, self.in_visual_dim)
+        if self._sp is not None or self._cfg_pair is not None:
+            raise RuntimeError("set_watch: this model is a rank of a sequence-parallel group or a CFG pair; watching is single-rank only "
+                               "(a rank that stops alone would leave its peers inside a collective)")
+        keep = []
+        w = E.Watch()
+        tr = E.WatchTrampoline(callback, self._step_info)
+        w.fn, w.user, w.preview_every, w.want_x0 = tr.c_fn, None, every, int(bool(want_x0))
+        if every > 0:
+            wa = (C.c_float * W.numel())(*W.reshape(-1).tolist())
+            keep.append(wa)
+            w.rgb_w = C.cast(wa, C.POINTER(C.c_float))
+            if rgb_bias is not None:
+                b = [float(v) for v in torch.as_tensor(rgb_bias, dtype=torch.float32).reshape(-1).tolist()]
+                if len(b) != 3:
+                    raise ValueError("rgb_bias must hold 3 values")
+                ba = (C.c_float * 3)(*b)
+                keep.append(ba)
+                w.rgb_b = C.cast(ba, C.POINTER(C.c_float))
+        self._watch = (tr, w, keep)
+        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
+            try:
+                self._install_watch()
+            except Exception:
+                self._watch = None
+                raise
+        return self
+
+    def _install_watch(self):
+        with torch.cuda.device(self._handle_device):
+            E.check(E.lib().k5_dit_set_watch(self._handle, C.byref(self._watch[1])), "k5_dit_set_watch")
+
+    def clear_watch(self):
+        """Remove the watch: `sample` enqueues exactly what it did before `set_watch`."""
+        self._watch = None
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_set_watch(self._handle, None), "k5_dit_set_watch")
+        return self
+
+    def watch_state(self):
+        """(steps_done, stopped) of the last `sample` / `sample_many` call (k5_dit_watch_state)."""
+        n, st = C.c_int(0), C.c_int(0)
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_watch_state(self._handle, C.byref(n), C.byref(st)), "k5_dit_watch_state")
+        return n.value, bool(st.value)
+
+    def _step_info(self, info):
+        shape = (info.T, info.H, info.W)
+        preview = x0 = None
+        if info.rgb:
+            import numpy as np
+            preview = torch.from_numpy(np.ctypeslib.as_array(info.rgb, shape=shape + (3,)).copy())   # the pinned slot is reused two steps on
+        if info.x0:
+            x0 = torch.as_tensor(_DeviceView(C.cast(info.x0, C.c_void_p).value, shape + (info.C,)), device=self._handle_device)
+        return StepInfo(info.step, info.num_steps, info.sample, info.num_samples, info.sigma_next, preview, x0)
+
+    def _watch_begin(self):
+        if self._watch is not None:
+            self._watch[0].reset()
+
+    def _watch_end(self, latent):
+        """After a k5_sample* call that returned K5_OK: re-raise what the callback raised, or SamplingInterrupted if it asked to stop."""
+        if self._watch is None:
+            return
+        tr = self._watch[0]
+        tr.reraise()
+        if tr.stop_requested:
+            steps, _ = self.watch_state()
+            raise SamplingInterrupted(steps, latent, tr.last_sample)
 
     def _check_visual_cond(self, visual_cond, latent):
         """visual_cond must be a contiguous fp32 tensor of latent.shape[:-1] + (in_visual_dim + 1,) on the latent's device."""
@@ -415,8 +559,10 @@ class DiffusionTransformer3D(nn.Module):
         arr = (C.c_float * len(sig))(*sig)
         s.latents, s.visual_cond = latents.data_ptr(), E.ptr(visual_cond)
         s.num_steps, s.sigmas, s.guidance_weight = len(sig) - 1, arr, float(guidance_weight)
+        self._watch_begin()
         with torch.cuda.device(dev):
             E.check(E.lib().k5_sample_many(h, C.byref(s), E.stream_ptr(dev)), "k5_sample_many")
+        self._watch_end(latents)
         return latents
 
     @torch.no_grad()

@@ -91,7 +91,8 @@ class Kandinsky5T2VPipeline:
     def __call__(self, text: Union[str, list], time_length: int = 5, width: int = 768, height: int = 512, seed: int = None,
                  num_steps: int = None, guidance_weight: float = None, scheduler_scale: float = 10.0,
                  negative_caption: str = _NEG, expand_prompts: bool = True, save_path: str = None,
-                 progress: bool = True, image=None, video=None, strength: float = None, mask=None):
+                 progress: bool = True, image=None, video=None, strength: float = None, mask=None, callback=None,
+                 preview_every: int = 0, preview_factors=None):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -100,7 +101,11 @@ class Kandinsky5T2VPipeline:
         `video`, `strength`, `mask` (optional, extension): video-to-video and masked editing.  `video` is the source clip (uint8
         (F,H,W,3) or float (F,3,H,W) frames, at least as long as the output; resized and cropped per frame like `image`), `strength`
         in (0, 1] (None = 1) the part of the schedule that runs on it, `mask` a pixel keep mask (height, width) or (F, height, width),
-        >= 0.5 = keep the source there.  Every rank passes the same inputs, as with `image`."""
+        >= 0.5 = keep the source there.  Every rank passes the same inputs, as with `image`.
+        `progress` draws a tqdm bar over the sampling steps (single-rank, tqdm installed).  `callback`, `preview_every`,
+        `preview_factors` (optional, extension; single-rank only): `callback(info)` after every sampling step (a truthy return stops
+        the run with `kandinsky.models.dit.SamplingInterrupted`), with a uint8 (T,H,W,3) `info.preview` of the denoised latent on every
+        `preview_every`-th step through the latent -> RGB factors `preview_factors` (`kandinsky.preview`), see `generate`."""
         strength = 1.0 if strength is None else float(strength)
         if not 0.0 < strength <= 1.0:
             raise ValueError(f"strength must be in (0, 1], got {strength}")
@@ -129,6 +134,7 @@ class Kandinsky5T2VPipeline:
                                  scheduler_scale=scheduler_scale, negative_caption=negative_caption, seed=seed,
                                  device=self.device_map["dit"], vae_device=self.device_map["vae"],
                                  text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload,
-                                 image=image, video=video, strength=strength, mask=mask)
+                                 image=image, video=video, strength=strength, mask=mask, callback=callback,
+                                 preview_every=preview_every, preview_factors=preview_factors)
         torch.cuda.empty_cache()
         return self._save(images, time_length, save_path) if self.local_dit_rank == 0 else None

@@ -7,6 +7,8 @@ README launch lines keep working against this package:
     python test.py --config ./configs/config_5s_distil.yaml --calibrate_magcache ratios.json   # measure a MagCache table, then:
     python test.py --config ./configs/config_5s_distil.yaml --magcache --magcache_ratios ratios.json
     python test.py --prompt "a cat in a blue hat" --lora style.safetensors --lora_scale 0.8   # LoRA adapter(s) merged into the DiT
+    python test.py --fit_preview_factors factors.json                      # fit latent -> RGB preview factors from one generation, then:
+    python test.py --preview ./steps --preview_every 5 --preview_factors factors.json   # a PNG of the denoised estimate every 5 steps
     PYTHONPATH=. torchrun --nproc-per-node 8 --master-addr 127.0.0.1 test.py --config ./configs/config_10s_sft.yaml ...
 
 Multi-GPU: one process per GPU (LOCAL_RANK / WORLD_SIZE from the launcher); `get_T2V_pipeline` sets up token-sharded
@@ -57,7 +59,32 @@ def build_parser():
     p.add_argument("--mask", type=str, default=argparse.SUPPRESS, metavar="PATH",
                    help="with --video: keep mask (an image, or a clip as for --video); white = keep the source there, black = generate; "
                         "resized and centre-cropped to the output size like the frames of --video")
+    p.add_argument("--fit_preview_factors", type=str, default=argparse.SUPPRESS, metavar="OUT.json",
+                   help="fit the latent -> RGB factors of the live previews from one generation of the given prompt (its own latent and decoded "
+                        "frames) and write them to OUT.json; no video is saved")
+    p.add_argument("--preview", type=str, default=argparse.SUPPRESS, metavar="DIR",
+                   help="write DIR/step_###.png, the middle frame of the denoised estimate, while sampling; needs --preview_factors")
+    p.add_argument("--preview_every", type=int, default=argparse.SUPPRESS, metavar="K", help="with --preview: a picture every K steps and after the last (default 1)")
+    p.add_argument("--preview_factors", type=str, default=argparse.SUPPRESS, metavar="FILE", help="with --preview: factors written by --fit_preview_factors")
     return p
+
+
+def preview_keywords(args):
+    """--preview / --preview_every / --preview_factors -> the pipeline's keywords"""
+    if not hasattr(args, "preview"):
+        if hasattr(args, "preview_every") or hasattr(args, "preview_factors"):
+            raise ValueError("--preview_every and --preview_factors need --preview DIR")
+        return {}
+    if not hasattr(args, "preview_factors"):
+        raise ValueError("--preview needs --preview_factors FILE (no default table ships: make one with --fit_preview_factors OUT.json)")
+    from kandinsky.preview import load_factors, preview_to_image
+    os.makedirs(args.preview, exist_ok=True)
+
+    def save(info):
+        if info.preview is not None:
+            preview_to_image(info.preview).save(os.path.join(args.preview, f"step_{info.step:03d}.png"))
+
+    return {"callback": save, "preview_every": getattr(args, "preview_every", 1), "preview_factors": load_factors(args.preview_factors)}
 
 
 def load_edit_inputs(args):
@@ -111,6 +138,16 @@ def main(argv=None):
         print(f"MagCache ratio table ({len(table['mag_ratios'])} ratios, {table['rows_counted']} of {table['rows_total']} rows counted) "
               f"is saved to {args.calibrate_magcache}; use it with --magcache --magcache_ratios {args.calibrate_magcache}")
         return
+    if hasattr(args, "fit_preview_factors"):
+        from kandinsky.preview import fit_from_pipeline, save_factors
+        W, b = fit_from_pipeline(pipe, args.prompt, time_length=args.video_duration, width=args.width, height=args.height,
+                                 num_steps=args.sample_steps, guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale,
+                                 expand_prompts=args.expand_prompt, negative_caption=args.negative_prompt, image=image, **edit_kw)
+        save_factors(args.fit_preview_factors, W, b, note=f"fitted on one generation of {args.config}")
+        print(f"Preview factors ({W.shape[0]} channels) are saved to {args.fit_preview_factors}; use them with --preview DIR "
+              f"--preview_factors {args.fit_preview_factors}")
+        return
+    edit_kw.update(preview_keywords(args))
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
