@@ -281,6 +281,16 @@ int k5_edit_renoise(float* out, const float* source, const float* noise, float s
  * NULL = k5_cfg_euler (source / noise then unused).  One pass over the latent. */
 int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source, const float* noise,
                       const float* keep_mask, float sigma_next, int64_t cells, int C, void* stream);
+/* k5_cfg_euler over temporal context windows (added under ABI 11, as the exports above were): a clip of T frames whose velocities come from
+ * nwin <= 64 windows of F frames.  img fp32 [T][frame_elems]; v_cond / v_uncond (NULL = no guidance) bf16 [nwin][F][frame_elems]; starts_dev
+ * DEVICE int32 [nwin], window i covers frames starts[i] .. starts[i] + F - 1; weights_dev DEVICE fp32 [nwin][F], the share of window i's local
+ * frame j (kandinsky.generation_utils.context_windows builds both).  Every element of frame t walks the windows that cover t in window order:
+ * v_i as k5_cfg_euler forms it (the same three bf16 roundings), acc = rn(wt_0 * v_0), then acc = rn(acc + rn(wt_i * v_i)), nothing contracted;
+ * img = rn(img + bf16(rn(dt * acc))).  One window of weight 1 is k5_cfg_euler bit for bit.  One pass over img.  K5_ERR_ARG + message, nothing
+ * launched: a NULL pointer, nwin outside 1..64, F < 1, or a window reaching outside 0..T-1 (the nwin starts are read back once, which
+ * synchronises the stream). */
+int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts_dev,
+                         const float* weights_dev, int nwin, int F, int T, int64_t frame_elems, void* stream);
 /* Sampler preview (added under ABI 11, as the exports above were): the denoised estimate of a flow-matching step and a cheap RGB view of it, one
  * pass.  After the update of a step the latent x (fp32, cells * C) sits at sigma_next and v_cond / v_uncond (bf16, v_uncond NULL = no guidance)
  * still hold that step's velocities: v is combined exactly as in k5_cfg_euler, x0 = rn(x - rn(sigma_next * v)) in fp32 (sigma_next == 0 gives
@@ -385,6 +395,31 @@ typedef struct k5_edit_args {
   const float* keep_mask;   /* device; NULL = no mask */
 } k5_edit_args;
 int k5_sample_edit(k5_dit* dit, const k5_sample_args* args, const float* visual_cond /* nullable */, const k5_edit_args* edit, void* stream);
+
+/* Long clips: temporal context windows (added under ABI 11; extends the loop of generation_utils.py:102-128, which runs one forward over the whole
+ * clip).  A clip of total_T latent frames, longer than the model's trained length, is sampled as nwin overlapping windows of sample.fwd.T frames:
+ * at every step each window runs the forward(s) on its own contiguous slice of the latent (and of visual_cond) with the window's RoPE positions
+ * sample.fwd.pos_t = 0 .. T-1, in window order and conditional before unconditional, and one k5_cfg_euler_windows pass cross-fades the
+ * windows' velocities into the update of the whole latent.  The result is bit-identical to the same forwards issued one by one through
+ * k5_dit_forward on a fresh softmax-form memory followed by k5_cfg_euler_windows per step.
+ *   sample: as k5_sample, except that fwd.T (and pos_t) is the WINDOW and latent is device fp32 (total_T,H,W,in_visual_dim).
+ *   starts HOST [nwin], ascending, 0 <= starts[i], starts[i] + fwd.T <= total_T, every frame covered; weights HOST [nwin][fwd.T].
+ *   conds / null_conds: HOST [nwin] prompts, one per window, or NULL = sample.fwd.cond / sample.null_cond for every window.
+ *   visual_cond (k5_sample_cond): device fp32 (total_T,H,W,in_visual_dim+1) or NULL.
+ * total_T <= fwd.T (one window) is k5_sample_cond on total_T frames.  Always eager, also with k5_dit_set_graph on.  A watch without previews
+ * works (progress, cancel; info->T = total_T).  Refused before anything is enqueued, with a message: K5_ERR_STATE on a handle in a
+ * sequence-parallel group or a CFG pair (any transport), with MagCache or its calibration set (the table is indexed by the call of a plain run),
+ * with a watch that has previews (the preview reads one velocity pair per cell); K5_ERR_ARG for nwin outside 1..64, starts that do not ascend or
+ * leave 0..total_T, a frame without a window, NULL starts / weights. */
+typedef struct k5_sample_windows_args {
+  k5_sample_args sample;
+  int total_T, nwin;
+  const int32_t* starts;             /* HOST [nwin] */
+  const float* weights;              /* HOST [nwin][sample.fwd.T] */
+  const k5_text_cond* conds;         /* HOST [nwin] or NULL */
+  const k5_text_cond* null_conds;    /* HOST [nwin] or NULL */
+} k5_sample_windows_args;
+int k5_sample_windows(k5_dit* dit, const k5_sample_windows_args* args, const float* visual_cond /* nullable */, void* stream);
 
 /* Several samples in one call (generate_sample's shape = (bs, frames, h, w, c), reference generation_utils.py:150): a CONVENIENCE entry point,
  * not a batched kernel path.  The B samples of one (T, H, W) run ONE AFTER ANOTHER on the stream, each as k5_sample_cond on its own slice of

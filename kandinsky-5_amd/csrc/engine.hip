@@ -318,6 +318,7 @@ struct k5_dit {
   DevBuf ws_xp, ws_vis, ws_h, ws_qk, ws_vt, ws_o, ws_ff, ws_ck, ws_cvt, ws_y;
   DevBuf ws_vcos, ws_vsin, ws_pos;
   DevBuf ws_vel_c, ws_vel_u;
+  DevBuf ws_win;                                   // k5_sample_windows: the call's plan, [nwin] int32 starts then [nwin][F] fp32 weights
   // sequence parallelism (token shards): this rank owns rows [sp_rank*n_loc, (sp_rank+1)*n_loc) of the N visual
   // tokens; K and V^T of every block are all-gathered in place into ws_kfull [N][D] / ws_vtfull [P][D][n_loc]
   Comm comm;
@@ -1876,7 +1877,7 @@ extern "C" void k5_dit_destroy(k5_dit* d) {
   if (d->pair_stream) { (void)hipStreamSynchronize(d->pair_stream); (void)hipStreamDestroy(d->pair_stream); }
   for (hipEvent_t e : {d->ev_vel_ready, d->ev_vel_done, d->ev_u_o, d->ev_u_back}) if (e) (void)hipEventDestroy(e);
   if (d->pair.comm) (void)d->pair.CommDestroy(d->pair.comm);
-  d->ws_vel_pair.release();
+  d->ws_vel_pair.release(); d->ws_win.release();
   d->watch.wb.release();
   for (int i = 0; i < 2; ++i) {
     d->watch.rgb[i].release(); d->watch.x0[i].release();
@@ -2131,8 +2132,10 @@ extern "C" int k5_dit_forward(k5_dit* d, const k5_forward_args* a, void* out_vel
   return st;
 }
 
-// The sampler loop behind k5_sample / k5_sample_cond (edit == nullptr: their launches, their bits) and k5_sample_edit.
-static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream, const char* who) {
+// The sampler loop behind k5_sample / k5_sample_cond (edit == nullptr: their launches, their bits), k5_sample_edit and k5_sample_windows
+// (win != nullptr: a->fwd is the window, a->latent / vcond the whole clip of win->total_T frames; never together with edit).
+static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream, const char* who,
+                       const k5_sample_windows_args* win = nullptr) {
   g_err[0] = 0;
   if (!d || !a || !a->latent || !a->sigmas || a->num_steps <= 0) return K5_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
@@ -2162,6 +2165,43 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
                  "collective", who, d->comm.active() ? "sequence-parallel group" : "CFG pair");
     return K5_ERR_STATE;
   }
+  if (win) {   // every refusal before anything is enqueued or any per-call state is touched
+    if (edit) { k5_set_error("%s: editing with context windows is not supported", who); return K5_ERR_UNSUPPORTED; }
+    if (d->comm.active() || d->pair.active()) {
+      k5_set_error("%s: the handle is in a %s (context windows are single-rank only)", who, d->comm.active() ? "sequence-parallel group" : "CFG pair");
+      return K5_ERR_STATE;
+    }
+    if (d->mag.on || d->cal.on) {
+      k5_set_error("%s: %s on the handle: the ratio table is indexed by the call of a plain run, a windowed run makes nwin calls per step", who,
+                   d->mag.on ? "MagCache is set" : "MagCache calibration is");
+      return K5_ERR_STATE;
+    }
+    if (watching && wt.every > 0) {
+      k5_set_error("%s: the watch has previews (preview_every = %d): the preview reads one velocity pair per cell, a windowed step has up to nwin; "
+                   "install the watch with preview_every = 0", who, wt.every);
+      return K5_ERR_STATE;
+    }
+    const int F = a->fwd.T;
+    if (win->nwin < 1 || win->nwin > 64 || !win->starts || !win->weights || F < 1 || n <= 0) {
+      k5_set_error("%s: nwin must be 1..64 (got %d) with starts, weights and a window shape", who, win->nwin);
+      return K5_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(a->latent) & 3) { k5_set_error("%s: latent is not 4-byte aligned", who); return K5_ERR_ARG; }
+    for (int i = 0; i < win->nwin; ++i) {
+      const int st = win->starts[i];
+      if (st < 0 || (int64_t)st + F > win->total_T) {
+        k5_set_error("%s: window %d (frames %d .. %lld) reaches outside the %d frames", who, i, st, (long long)st + F - 1, win->total_T);
+        return K5_ERR_ARG;
+      }
+      if (i > 0 && st <= win->starts[i - 1]) { k5_set_error("%s: starts must ascend (starts[%d] = %d after %d)", who, i, st, win->starts[i - 1]); return K5_ERR_ARG; }
+      const int covered_to = i == 0 ? 0 : win->starts[i - 1] + F;   // first frame the windows before i leave uncovered
+      if (st > covered_to) { k5_set_error("%s: no window covers frame %d", who, covered_to); return K5_ERR_ARG; }
+    }
+    if (win->starts[win->nwin - 1] + F < win->total_T) {
+      k5_set_error("%s: no window covers frame %d", who, win->starts[win->nwin - 1] + F);
+      return K5_ERR_ARG;
+    }
+  }
   wt.steps_done = 0; wt.stopped = 0;
   const int64_t cells = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W;
   if (watching) {
@@ -2184,9 +2224,9 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   const bool cfg_on = fabsf(a->guidance_weight - 1.0f) > 1e-6f;  // generation_utils.py:63
   const bool pair = cfg_on && d->pair.active();                  // CFG-parallel: one branch here, the other on the paired handle
   if (pair) K5CHK(d->ws_vel_pair.ensure(2 * n * 2));
-  else {
-    K5CHK(d->ws_vel_c.ensure(n * 2));
-    if (cfg_on) K5CHK(d->ws_vel_u.ensure(n * 2));
+  else {   // one slot per window
+    K5CHK(d->ws_vel_c.ensure((win ? win->nwin : 1) * n * 2));
+    if (cfg_on) K5CHK(d->ws_vel_u.ensure((win ? win->nwin : 1) * n * 2));
   }
   void* vel_c = pair ? d->ws_vel_pair.p : d->ws_vel_c.p;
   void* vel_u = pair ? (void*)(d->ws_vel_pair.as<bf16_t>() + n) : d->ws_vel_u.p;
@@ -2198,7 +2238,8 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   // not replayed: MagCache (host decisions) and its calibration (host-side call counter and buffer swap), profiling (events), the NABLA map tap (its destination advances on the host per launch: a replay
   // would overwrite the slots baked at capture — ADVICE r5), loopback groups (their collectives are host rendezvous).  The IPC transport IS
   // replayable: its epochs live on the device and the peers' buffers were mapped by the eager first step (ipc_comm.h)
-  const bool graph = d->use_graph && !d->mag.on && !d->cal.on && !d->profiling && a->num_steps > 2 && !d->nabla_tap && !d->comm.loop && !d->pair.loop;
+  const bool graph = d->use_graph && !d->mag.on && !d->cal.on && !d->profiling && a->num_steps > 2 && !d->nabla_tap && !d->comm.loop && !d->pair.loop &&
+                     !win;   // windows run eagerly: the captured step holds one forward pair
   std::vector<float> host_tab(3 * (size_t)a->num_steps);
   for (int i = 0; i < a->num_steps; ++i) {
     host_tab[i] = a->sigmas[i] * 1000.0f;                        // t * 1000, fp32 (:57)
@@ -2226,6 +2267,15 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     Scope sc(d, s, "elementwise");
     K5CHK(k5_launch_edit_renoise(a->latent, edit->source, edit->noise, a->sigmas[0], n, s));
   }
+  const int32_t* win_starts = nullptr; const float* win_weights = nullptr;
+  if (win) {   // the plan, uploaded once per call: [nwin] int32 starts, then [nwin][F] fp32 weights
+    const size_t sb = (size_t)win->nwin * 4, wb = (size_t)win->nwin * a->fwd.T * 4;
+    K5CHK(d->ws_win.ensure(sb + wb));
+    HIPCHK(hipMemcpyAsync(d->ws_win.p, win->starts, sb, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(static_cast<char*>(d->ws_win.p) + sb, win->weights, wb, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));   // the caller's tables are host memory
+    win_starts = d->ws_win.as<int32_t>(); win_weights = reinterpret_cast<const float*>(static_cast<char*>(d->ws_win.p) + sb);
+  }
   d->text_cache[0].valid = d->text_cache[1].valid = false;   // the prompt tensors are constant for THIS call only
   K5CHK(reset_attn_pref(d, s));                              // ... and so is what the softmax-form memory of the layers is worth
   // where the visual queries are normalised (see k5_dit::fuse_qnorm_auto): a plain one-handle dense run decides after its first step
@@ -2249,8 +2299,30 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     d->fuse_last = d->fuse_now ? 1 : 0;
     return K5_OK;
   };
+  const void* slot_prompt[2] = {nullptr, nullptr};   // windows with prompts of their own: whose prologue each text cache slot holds
   auto one_step = [&](int i) -> int {
     const float t1000 = host_tab[i], dt = host_tab[a->num_steps + i];
+    if (win) {
+      // every window on its own slice of the latent (T is outermost: a temporal window is contiguous), cond then uncond, into slot k of the
+      // velocity buffers; then one pass over the whole clip blends the windows and applies the step
+      const int64_t frame = n / a->fwd.T, vframe = frame / c.out_visual_dim * (c.in_visual_dim + 1);
+      for (int k = 0; k < win->nwin; ++k) {
+        const k5_text_cond& ck = win->conds ? win->conds[k] : a->fwd.cond;
+        const k5_text_cond& uk = win->null_conds ? win->null_conds[k] : a->null_cond;
+        const float* xk = a->latent + (int64_t)win->starts[k] * frame;
+        const float* vk = vcond ? vcond + (int64_t)win->starts[k] * vframe : nullptr;
+        if (slot_prompt[0] != ck.text_embed) { d->text_cache[0].valid = false; slot_prompt[0] = ck.text_embed; }
+        K5CHK(forward_impl(d, &a->fwd, ck, t1000, xk, c.in_visual_dim, static_cast<bf16_t*>(vel_c) + k * n, s, nullptr, nullptr, 0, vk));
+        if (cfg_on) {
+          if (slot_prompt[1] != uk.text_embed) { d->text_cache[1].valid = false; slot_prompt[1] = uk.text_embed; }
+          K5CHK(forward_impl(d, &a->fwd, uk, t1000, xk, c.in_visual_dim, static_cast<bf16_t*>(vel_u) + k * n, s, nullptr, nullptr, 1, vk));
+        }
+      }
+      Scope sc(d, s, "elementwise");
+      K5CHK(k5_launch_cfg_euler_windows(a->latent, vel_c, cfg_on ? vel_u : nullptr, a->guidance_weight, dt, win_starts, win_weights, win->nwin,
+                                        a->fwd.T, win->total_T, frame, s));
+      return K5_OK;
+    }
     if (pair) {
       // my branch only; then the pair's velocities change hands on the side stream (fork / join by events: capturable) and both
       // handles hold [v_cond | v_uncond] — every rank of both groups applies the same update to the same numbers
@@ -2303,7 +2375,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     info.sigma_next = host_tab[2 * a->num_steps + i];
     info.rgb = pv ? wt.h_rgb[slot] : nullptr;
     info.x0 = pv && wt.want_x0 ? wt.x0[slot].as<float>() : nullptr;
-    info.T = a->fwd.T; info.H = a->fwd.H; info.W = a->fwd.W; info.C = c.in_visual_dim;
+    info.T = win ? win->total_T : a->fwd.T; info.H = a->fwd.H; info.W = a->fwd.W; info.C = c.in_visual_dim;
     if (wt.fn(wt.user, &info) != 0) wt.stopped = 1;
     return K5_OK;
   };
@@ -2367,6 +2439,20 @@ extern "C" int k5_sample(k5_dit* d, const k5_sample_args* a, void* stream) { ret
 
 extern "C" int k5_sample_edit(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream) {
   return sample_impl(d, a, vcond, edit, stream, edit ? "k5_sample_edit" : "k5_sample_cond");
+}
+
+extern "C" int k5_sample_windows(k5_dit* d, const k5_sample_windows_args* w, const float* vcond, void* stream) {
+  g_err[0] = 0;
+  if (!d || !w) { k5_set_error("k5_sample_windows: null handle or arguments"); return K5_ERR_ARG; }
+  if (w->total_T < 1) { k5_set_error("k5_sample_windows: total_T must be >= 1 (got %d)", w->total_T); return K5_ERR_ARG; }
+  if (w->total_T <= w->sample.fwd.T) {   // one window: the plain run on total_T frames (pos_t's first total_T entries are its positions)
+    k5_sample_args one = w->sample;
+    one.fwd.T = w->total_T;
+    if (w->conds) one.fwd.cond = w->conds[0];
+    if (w->null_conds) one.null_cond = w->null_conds[0];
+    return sample_impl(d, &one, vcond, nullptr, stream, "k5_sample_windows");
+  }
+  return sample_impl(d, &w->sample, vcond, nullptr, stream, "k5_sample_windows", w);
 }
 
 // What k5_sample_many / k5_dit_forward_many refuse before anything is enqueued: handle states whose per-call bookkeeping is not per sample (rank

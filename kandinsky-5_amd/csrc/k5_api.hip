@@ -382,6 +382,26 @@ int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, floa
              "k5_cfg_euler_edit");
 }
 
+int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts_dev,
+                         const float* weights_dev, int nwin, int F, int T, int64_t frame_elems, void* stream) {
+  if (!img || !v_cond || !starts_dev || !weights_dev || nwin < 1 || nwin > 64 || F < 1 || T < 1 || frame_elems < 1) {
+    k5_set_error("k5_cfg_euler_windows: null pointer, or nwin (1..64) / F / T / frame_elems out of range");
+    return K5_ERR_ARG;
+  }
+  // the plan is checked on the host: nwin ints come back once (this entry is the per-step paths' and the tests'; k5_sample_windows holds its plan on the host)
+  int32_t st[64];
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpyAsync(st, starts_dev, (size_t)nwin * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return ret(K5_ERR_HIP, "k5_cfg_euler_windows");
+  for (int i = 0; i < nwin; ++i)
+    if (st[i] < 0 || (int64_t)st[i] + F > T) {
+      k5_set_error("k5_cfg_euler_windows: window %d (frames %d .. %lld) reaches outside the %d frames", i, st[i], (long long)st[i] + F - 1, T);
+      return K5_ERR_ARG;
+    }
+  return ret(k5_launch_cfg_euler_windows(img, v_cond, v_uncond, w, dt, starts_dev, weights_dev, nwin, F, T, frame_elems, s),
+             "k5_cfg_euler_windows");
+}
+
 int k5_x0_preview(const float* x, const void* v_cond, const void* v_uncond, float w, float sigma_next, const float* source,
                   const float* keep_mask, const float* rgb_w, const float* rgb_b, float* x0_out, uint8_t* rgb, int64_t cells, int C,
                   void* stream) {

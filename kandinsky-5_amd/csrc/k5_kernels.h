@@ -184,6 +184,13 @@ int k5_launch_edit_renoise(float* out, const float* source, const float* noise, 
 int k5_launch_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source,
                              const float* noise, const float* keep_mask, float sigma_next, int64_t cells, int C, hipStream_t stream,
                              const float* dtvec = nullptr, const float* signext = nullptr, const int* step = nullptr);
+// K18 over temporal context windows: img fp32 [T][frame_elems]; v_cond / v_uncond (null = no guidance) bf16 [nwin][F][frame_elems], window i
+// covering frames starts[i] .. starts[i] + F - 1 (device int32 [nwin]) with the share weights[i][j] (device fp32 [nwin][F]) of its local frame j.
+// Per element the windows that cover its frame are walked in order: v_i as K18 forms it, acc = wt_0 * v_0, then acc = acc + wt_i * v_i
+// (every product and sum rounded to fp32 on its own), img += float(bf16(dt * acc)): one window of weight 1 is K18 bit for bit.  One pass;
+// 16-byte latent accesses when frame_elems % 4 == 0 and img is 16-byte, the velocities 8-byte aligned.  A frame without a window stays as it is.
+int k5_launch_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts,
+                                const float* weights, int nwin, int F, int T, int64_t frame_elems, hipStream_t stream);
 // sampler preview: with v combined as in K18, x0 = x - sigma_next * v (fp32, uncontracted; keep_blend(x0, source, m) under a keep mask) on cells * C
 // elements, optionally stored as fp32 (x0_out), and rgb[cell][j] = sat_u8(rint((b[j] + sum_k W[k][j] x0[k]) * 127.5 + 127.5)), NaN -> 0, with
 // W [C][3] / b [3] (null = zeros) fp32 on the device.  rgb and rgb_w come together or not at all; one of rgb / x0_out is needed.  C % 4 == 0 and

@@ -54,6 +54,11 @@ class SampleManyArgs(C.Structure):
                 ("guidance_weight", C.c_float)]
 
 
+class SampleWindowsArgs(C.Structure):   # k5_sample_windows_args
+    _fields_ = [("sample", SampleArgs), ("total_T", C.c_int), ("nwin", C.c_int), ("starts", C.POINTER(C.c_int32)),
+                ("weights", C.POINTER(C.c_float)), ("conds", C.POINTER(TextCond)), ("null_conds", C.POINTER(TextCond))]
+
+
 class EditArgs(C.Structure):
     _fields_ = [("source", C.c_void_p), ("noise", C.c_void_p), ("keep_mask", C.c_void_p)]
 
@@ -192,6 +197,8 @@ SYMBOLS = {
     "k5_sample_edit": (_I, [_P, C.POINTER(SampleArgs), _P, C.POINTER(EditArgs), _P]),
     "k5_edit_renoise": (_I, [_P, _P, _P, _F, _I64, _P]),
     "k5_cfg_euler_edit": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _F, _I64, _I, _P]),
+    "k5_cfg_euler_windows": (_I, [_P, _P, _P, _F, _F, _P, _P, _I, _I, _I, _I64, _P]),
+    "k5_sample_windows": (_I, [_P, C.POINTER(SampleWindowsArgs), _P, _P]),
     "k5_x0_preview": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I64, _I, _P]),
     "k5_dit_set_watch": (_I, [_P, C.POINTER(Watch)]),
     "k5_dit_watch_state": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
@@ -449,6 +456,34 @@ def cfg_euler_(img, v_cond, v_uncond, w, dt):
     _need_cuda(img, v_cond, v_uncond)
     check(lib().k5_cfg_euler(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), img.numel(),
                              stream_ptr(img.device)), "k5_cfg_euler")
+    return img
+
+
+def window_tables(starts, weights, device):
+    """The plan of `generation_utils.context_windows` as the device tables of `cfg_euler_windows_`: (int32 [nwin], fp32 [nwin][F])."""
+    st = torch.tensor([int(v) for v in starts], dtype=torch.int32, device=device)
+    wt = torch.tensor([[float(v) for v in row] for row in weights], dtype=torch.float32, device=device)
+    if wt.dim() != 2 or wt.shape[0] != st.numel():
+        raise ValueError("window_tables: weights must hold one row of F values per window")
+    return st, wt.contiguous()
+
+
+def cfg_euler_windows_(img, v_cond, v_uncond, w, dt, starts, weights):
+    """cfg_euler_ over temporal context windows (k5_cfg_euler_windows): img fp32 (T, ...), v_cond / v_uncond (None = no guidance) bf16
+    (nwin, F, ...) with the frame shape of img, `starts` int32 [nwin] and `weights` fp32 [nwin][F] on img's device (`window_tables`)."""
+    _need_cuda(img, v_cond, v_uncond, starts, weights)
+    if img.dtype != torch.float32 or not img.is_contiguous() or img.dim() < 2:
+        raise ValueError("cfg_euler_windows_: img must be a contiguous fp32 tensor (T, ...)")
+    if starts.dtype != torch.int32 or weights.dtype != torch.float32 or not starts.is_contiguous() or not weights.is_contiguous() \
+            or weights.dim() != 2 or weights.shape[0] != starts.numel():
+        raise ValueError("cfg_euler_windows_: starts must be int32 [nwin] and weights fp32 [nwin][F], contiguous")
+    nwin, F = weights.shape
+    T, frame = img.shape[0], img[0].numel()
+    for v in (v_cond, v_uncond):
+        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != nwin * F * frame):
+            raise ValueError("cfg_euler_windows_: the velocities must be contiguous bf16 tensors (nwin, F) + img's frame shape")
+    check(lib().k5_cfg_euler_windows(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), ptr(starts), ptr(weights), int(nwin), int(F),
+                                     int(T), int(frame), stream_ptr(img.device)), "k5_cfg_euler_windows")
     return img
 
 

@@ -78,6 +78,56 @@ def edit_first_step(num_steps, strength):
     return int(num_steps) - run
 
 
+def context_windows(T, frames, overlap):
+    """The plan of a long clip sampled as temporal context windows: `(starts, weights)` for T latent frames, windows of `frames` = F frames
+    and 0 <= `overlap` < F.  T <= F: one window of T frames with weight 1.  Otherwise nwin = ceil((T - overlap) / (F - overlap)) windows
+    evenly spread, starts[i] = (i * (T - F)) // (nwin - 1), so the first starts at 0 and the last ends at T.  weights (float32 tensor
+    [nwin][F]): local frame j of a window weighs the triangle min(j + 1, F - j), normalised over the windows that cover the frame (float64,
+    rounded once), so the shares of every frame sum to 1 and the windows cross-fade where they overlap.  ValueError for nwin > 64."""
+    T, F, overlap = int(T), int(frames), int(overlap)
+    if T < 1 or F < 1:
+        raise ValueError(f"context_windows: T and frames must be >= 1, got T={T}, frames={F}")
+    if not 0 <= overlap < F:
+        raise ValueError(f"context_windows: overlap must be in [0, frames), got overlap={overlap} with frames={F}")
+    if T <= F:
+        return [0], torch.ones(1, T, dtype=torch.float32)
+    nwin = -(-(T - overlap) // (F - overlap))
+    if nwin > 64:
+        raise ValueError(f"context_windows: T={T}, frames={F}, overlap={overlap} needs nwin = {nwin} windows, at most 64 are supported")
+    starts = [(i * (T - F)) // (nwin - 1) for i in range(nwin)]
+    raw = torch.tensor([min(j + 1, F - j) for j in range(F)], dtype=torch.float64)
+    total = torch.zeros(T, dtype=torch.float64)
+    for st in starts:
+        total[st:st + F] += raw
+    weights = torch.stack([raw / total[st:st + F] for st in starts]).to(torch.float32)
+    return starts, weights
+
+
+def _context_plan(model, T, context_frames, context_overlap, context_text, init_latent, preview_every):
+    """`generate`'s context keywords -> (F, starts, weights) or None for a plain run, with the ValueErrors of the combinations that are refused."""
+    if context_frames is None:
+        if context_overlap is not None or context_text is not None:
+            raise ValueError("context_overlap / context_text need context_frames")
+        return None
+    F = int(context_frames)
+    overlap = F // 4 if context_overlap is None else int(context_overlap)
+    starts, weights = context_windows(T, F, overlap)
+    nwin = len(starts)
+    if context_text is not None and len(context_text) != nwin:
+        raise ValueError(f"context_text holds {len(context_text)} prompts, the plan of T={T}, frames={F}, overlap={overlap} has nwin = {nwin} windows")
+    if nwin == 1:
+        return None if context_text is None else (T, starts, weights)
+    if init_latent is not None:
+        raise ValueError("init_latent (editing) together with context_frames is not supported")
+    if int(preview_every) > 0:
+        raise ValueError("preview_every > 0 together with context_frames is not supported: the preview reads one velocity pair per cell")
+    if _has_magcache(model):
+        raise ValueError("context_frames with MagCache: the ratio table is indexed by the call of a plain run")
+    if _is_multi_rank_engine(model) or getattr(model, "_cfg_parallel", None) is not None:
+        raise ValueError("context_frames needs a single-rank model (no sequence-parallel group, no CFG pair)")
+    return F, starts, weights
+
+
 def _has_magcache(model):
     """True when the model (or a module inside a wrapper) carries a MagCache ratio table or is calibrating one."""
     mods = list(model.modules()) if isinstance(model, torch.nn.Module) else [model]
@@ -173,7 +223,8 @@ class _StepWatch:
 def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
              null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=False, seed=6554, noise=None, *,
              visual_cond=None, visual_cond_mask=None, batch=1, init_latent=None, strength=1.0, keep_mask=None,
-             callback=None, preview_every=0, preview_factors=None, preview_x0=False, _watch=None):
+             callback=None, preview_every=0, preview_factors=None, preview_x0=False, context_frames=None, context_overlap=None,
+             context_text=None, _watch=None):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -194,12 +245,20 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     (step + 1) % k == 0 and on the last one, through `preview_factors` (a JSON path or (W [C][3], b [3]); `kandinsky.preview`;
     no default table ships), and with `preview_x0` the estimate itself as `info.x0` (device, valid during the call).  The engine-backed
     model keeps its in-engine loop (k5_dit_set_watch: the callback runs one step behind the GPU); the per-step paths call back from their
-    Python loop with the same kernel, so the sequence and the preview bits are the same.  ValueError on a multi-rank engine model."""
+    Python loop with the same kernel, so the sequence and the preview bits are the same.  ValueError on a multi-rank engine model.
+    `context_frames`, `context_overlap`, `context_text` (optional, extension): a clip longer than the model's trained length.  With
+    `context_frames` = F below the sample's T frames the model runs at every step on the overlapping windows of `context_windows(T, F,
+    context_overlap)` (overlap default F // 4) and the windows' velocities are cross-faded into one update (k5_cfg_euler_windows);
+    `visual_rope_pos[0]` (its first F entries when it holds the clip's) and the NABLA parameters are the window's.  `context_text`: a
+    list of nwin `(text_embeds, text_rope_pos)` pairs, a prompt per window in order, instead of `text_embeds` / `text_rope_pos`.  F >= T
+    is the plain run, bit for bit.  The engine-backed model runs the whole loop in one call (k5_sample_windows), any other callable the
+    same forwards in the same order from Python.  ValueError with init_latent, preview_every > 0, MagCache or a multi-rank model."""
     from .models.dit import split_per_sample
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
         raise ValueError(f"shape[0] = {shape[0]} frames do not divide into batch={batch} samples")
     _check_edit_args(model, shape, init_latent, strength, keep_mask)
+    plan = _context_plan(model, shape[0] // batch, context_frames, context_overlap, context_text, init_latent, preview_every)
     many = any(isinstance(v, (list, tuple)) for v in (text_embeds, null_text_embeds))
     if batch == 1 and many:
         text_embeds, null_text_embeds, text_rope_pos, null_text_rope_pos = (
@@ -212,7 +271,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
             return generate(model, device, shape, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                             null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=progress, seed=seed, noise=noise,
                             visual_cond=visual_cond, visual_cond_mask=visual_cond_mask, batch=batch, init_latent=init_latent,
-                            strength=strength, keep_mask=keep_mask, _watch=watch)
+                            strength=strength, keep_mask=keep_mask, context_frames=context_frames, context_overlap=context_overlap,
+                            context_text=context_text, _watch=watch)
         finally:
             watch.close()
     watch = _watch
@@ -226,7 +286,16 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     if batch > 1:
         return _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                                null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond,
-                               visual_cond_mask, init_latent, strength, keep_mask, watch)
+                               visual_cond_mask, init_latent, strength, keep_mask, watch,
+                               context=None if context_frames is None else (context_frames, context_overlap, context_text))
+    if plan is not None:
+        F, starts, weights = plan
+        if context_text is not None:   # the first window's prompt stands where the one prompt of a plain run does
+            text_embeds, text_rope_pos = context_text[0]
+        if len(starts) == 1:
+            plan = None
+        else:
+            visual_rope_pos = [torch.as_tensor(visual_rope_pos[0])[:F], visual_rope_pos[1], visual_rope_pos[2]]
     edit = None
     if init_latent is not None:   # img (the draw) is eps from here on; the latent is a buffer of its own that the engine fills
         src = init_latent.to(device=img.device, dtype=torch.float32).contiguous()
@@ -247,7 +316,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
                              f"{tuple(vm.shape)}")
         cond_in = (vc, vm)
 
-    sparse_params = get_sparse_params(conf, {"visual": img}, device)
+    sparse_params = get_sparse_params(conf, {"visual": img if plan is None else img[:plan[0]]}, device)
     timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()  # one sync, before the loop
     if edit is not None:
         timesteps = timesteps[edit_first_step(num_steps, strength):]   # strength is a truncation of the schedule, nothing more
@@ -310,7 +379,36 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
             model.sample(img, timesteps.tolist(), text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                          null_text_rope_pos, guidance_weight, scale_factor=conf.metrics.scale_factor,
                          sparse_params=sparse_params,
-                         visual_cond=None if cond_in is None else torch.cat(cond_in, dim=-1).contiguous(), edit=edit)
+                         visual_cond=None if cond_in is None else torch.cat(cond_in, dim=-1).contiguous(), edit=edit,
+                         windows=None if plan is None else (plan[1], plan[2]), window_text=None if plan is None else context_text)
+        return img
+
+    if plan is not None:
+        # context windows, step by step: the forwards of k5_sample_windows in its order (window by window, cond then uncond, each on its
+        # own slice of the latent), then the one blend + Euler pass over the clip
+        F, starts, weights = plan
+        nwin = len(starts)
+        st_dev, wt_dev = E.window_tables(starts, weights, img.device)
+        vbuf = torch.empty((nwin, F) + tuple(img.shape[1:]), dtype=torch.bfloat16, device=img.device)
+        ubuf = torch.empty_like(vbuf) if cfg_on else None
+        for i, (timestep, timestep_diff, sigma_next) in enumerate(zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(),
+                                                                      timesteps[1:].tolist())):
+            t1000 = torch.tensor([timestep]) * 1000
+            for k, st in enumerate(starts):
+                x = img[st:st + F]
+                if model.visual_cond:
+                    if cond_in is None:
+                        x = torch.cat([x, torch.zeros_like(x), torch.zeros([*x.shape[:-1], 1], dtype=x.dtype, device=x.device)], dim=-1)
+                    else:
+                        x = torch.cat([x, cond_in[0][st:st + F], cond_in[1][st:st + F]], dim=-1)
+                te, tp = (text_embeds, text_rope_pos) if context_text is None else context_text[k]
+                vbuf[k] = model(x, te["text_embeds"], te["pooled_embed"], t1000, visual_rope_pos, tp,
+                                scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
+                if cfg_on:
+                    ubuf[k] = model(x, null_text_embeds["text_embeds"], null_text_embeds["pooled_embed"], t1000, visual_rope_pos,
+                                    null_text_rope_pos, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
+            E.cfg_euler_windows_(img, vbuf, ubuf, guidance_weight, timestep_diff, st_dev, wt_dev)
+            after_step(i, None, None, sigma_next)
         return img
 
     if edit is not None:
@@ -342,7 +440,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
 
 def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                     null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond, visual_cond_mask,
-                    init_latent=None, strength=1.0, keep_mask=None, watch=None):
+                    init_latent=None, strength=1.0, keep_mask=None, watch=None, context=None):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
     from .models.dit import split_per_sample
     T = img.shape[0] // batch
@@ -357,8 +455,9 @@ def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text
         return None if v is None else v[b * T:(b + 1) * T]
 
     from .models.dit import DiffusionTransformer3D
-    if init_latent is None and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) and model.many_ready() \
-            and getattr(model, "_cfg_parallel", None) is None:
+    ctx_kw = {} if context is None else dict(context_frames=context[0], context_overlap=context[1], context_text=context[2])
+    if init_latent is None and context is None and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) \
+            and model.many_ready() and getattr(model, "_cfg_parallel", None) is None:
         cond = None
         if visual_cond is not None or visual_cond_mask is not None:
             if not model.visual_cond:
@@ -376,7 +475,7 @@ def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text
             model.sample_many(img.view(batch, T, *img.shape[1:]), timesteps.tolist(), tes, nes, visual_rope_pos, tps, nps,
                                guidance_weight, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params, visual_cond=cond)
         return img
-    # any other model (rank groups, MagCache, graph replay, wrapped or duck-typed models) and editing: today's path, one sample at a time
+    # any other model (rank groups, MagCache, graph replay, wrapped or duck-typed models), editing and context windows: one sample at a time
     watch.num_samples = batch
     for b in range(batch):
         watch.sample = b
@@ -384,7 +483,7 @@ def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text
                                           tps[b], nps[b], guidance_weight, scheduler_scale, conf, progress=progress, seed=seed,
                                           noise=img[b * T:(b + 1) * T], visual_cond=part(visual_cond, b),
                                           visual_cond_mask=part(visual_cond_mask, b), init_latent=part(init_latent, b),
-                                          strength=strength, keep_mask=part(keep_mask, b), _watch=watch)
+                                          strength=strength, keep_mask=part(keep_mask, b), _watch=watch, **ctx_kw)
     return img
 
 
@@ -424,7 +523,7 @@ def frames_to_uint8(frames):
 def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25, guidance_weight=5.0,
                     scheduler_scale=1, negative_caption="", seed=6554, device="cuda", vae_device="cuda",
                     text_embedder_device="cuda", progress=True, offload=False, image=None, video=None, strength=1.0, mask=None,
-                    callback=None, preview_every=0, preview_factors=None):
+                    callback=None, preview_every=0, preview_factors=None, context_frames=None, context_overlap=None):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -434,8 +533,22 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     in (0, 1] how much of the schedule runs on it and `mask` a pixel keep mask ((H,W) or (F,H,W), >= 0.5 = keep the source there, at
     8 * height x 8 * width, see conditioning.pixel_mask_to_latent); every sample of the batch edits the same clip.
     `progress` draws a tqdm bar over the sampling steps when tqdm is installed; `callback`, `preview_every`, `preview_factors`
-    (optional, extension): per-step callback, cancel and live previews, see `generate`."""
+    (optional, extension): per-step callback, cancel and live previews, see `generate`.  `context_frames`, `context_overlap` (optional,
+    extension): a clip longer than the model's trained length, sampled as overlapping temporal windows of `context_frames` latent frames
+    (see `generate` and `context_windows`).  With bs = 1 `caption` may then be a list of nwin prompts, one per window in order."""
     batch, frames, height, width, channels = shape
+    ctx_kw, window_captions = {}, None
+    if context_frames is not None:
+        overlap = int(context_frames) // 4 if context_overlap is None else int(context_overlap)
+        nwin = len(context_windows(frames, context_frames, overlap)[0])
+        ctx_kw = dict(context_frames=int(context_frames), context_overlap=overlap)
+        if batch == 1 and isinstance(caption, (list, tuple)):
+            if len(caption) != nwin:
+                raise ValueError(f"{len(caption)} prompts for a plan of nwin = {nwin} windows ({frames} frames as windows of "
+                                 f"{int(context_frames)} with overlap {overlap}): pass one prompt, or one per window")
+            window_captions, caption = list(caption), caption[0]
+    elif context_overlap is not None:
+        raise ValueError("context_overlap needs context_frames")
     captions = list(caption) if isinstance(caption, (list, tuple)) else [caption] * batch
     if len(captions) != batch:
         raise ValueError(f"{len(captions)} captions for bs={batch} samples")
@@ -464,7 +577,13 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
             torch.cuda.empty_cache()
         cond_kw.update(visual_cond=vc.repeat(batch, 1, 1, 1), visual_cond_mask=vm.repeat(batch, 1, 1, 1))
     kind = "image" if frames == 1 else "video"
-    if batch == 1:
+    if window_captions is not None:
+        distinct = list(dict.fromkeys(window_captions))
+        *encoded, (uncond, n_uncond) = _encode_prompts(text_embedder, distinct + [negative_caption], kind, device)
+        by_prompt = dict(zip(distinct, encoded))
+        ctx_kw["context_text"] = [(by_prompt[p][0], torch.arange(by_prompt[p][1])) for p in window_captions]
+        cond, text_pos = ctx_kw["context_text"][0]
+    elif batch == 1:
         (cond, n_cond), (uncond, n_uncond) = _encode_prompts(text_embedder, (captions[0], negative_caption), kind, device)
         text_pos = torch.arange(n_cond)
     else:
@@ -484,7 +603,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         latent = generate(dit, device, (batch * frames, height, width, channels), num_steps, cond, uncond, grid,
                           text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
                           progress=progress, batch=batch, callback=callback, preview_every=preview_every,
-                          preview_factors=preview_factors, **cond_kw)
+                          preview_factors=preview_factors, **cond_kw, **ctx_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

@@ -356,14 +356,27 @@ class DiffusionTransformer3D(nn.Module):
 
     @torch.no_grad()
     def sample(self, latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
-               null_text_rope_pos, guidance_weight, scale_factor=(1.0, 1.0, 1.0), sparse_params=None, visual_cond=None, edit=None):
+               null_text_rope_pos, guidance_weight, scale_factor=(1.0, 1.0, 1.0), sparse_params=None, visual_cond=None, edit=None,
+               windows=None, window_text=None):
         """Whole Euler/CFG loop on device (generation_utils.py:80-129) in one C call.  `latent` fp32
         (T,H,W,in_visual_dim) is updated in place; `sigmas` = the sigma schedule (num_steps+1 floats, host).
         `visual_cond` (optional, a model with visual_cond only): contiguous fp32 (T,H,W,in_visual_dim+1) on the latent's device, the
         conditioning latent and its mask that fill the input channels the reference leaves zero (k5_sample_cond); None = k5_sample.
         `edit` (optional): `(source, noise, keep_mask | None)`, contiguous fp32 on the latent's device, source and noise of the latent's
         shape and keep_mask (T,H,W,1): video-to-video / masked editing (k5_sample_edit).  `latent` is then output only: it starts as
-        the source noised to sigmas[0] and the kept region (mask 1) is held on the source through every step."""
+        the source noised to sigmas[0] and the kept region (mask 1) is held on the source through every step.
+        `windows` (optional): `(starts, weights)` of `generation_utils.context_windows(T, F, overlap)`: a clip longer than the model's trained
+        length runs as overlapping temporal windows of F frames whose velocities are cross-faded at every step (k5_sample_windows).
+        `visual_rope_pos[0]` and `sparse_params` are then the WINDOW's (F positions), `latent` and `visual_cond` the whole clip's.
+        `window_text` (optional, with `windows`): a prompt per window, a list of nwin `(text_embeds, text_rope_pos)` pairs that replaces
+        `text_embeds` / `text_rope_pos`.  Not with `edit`; a single-rank model without MagCache only, and a watch without previews."""
+        if windows is None and window_text is not None:
+            raise ValueError("window_text needs windows")
+        if windows is not None:
+            if edit is not None:
+                raise ValueError("edit together with windows is not supported")
+            return self._sample_windows(latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
+                                        guidance_weight, scale_factor, sparse_params, visual_cond, windows, window_text)
         if not latent.is_cuda or latent.dtype != torch.float32 or not latent.is_contiguous():
             raise RuntimeError("latent must be a contiguous fp32 CUDA tensor")
         T, H, W, _ = latent.shape
@@ -392,6 +405,52 @@ class DiffusionTransformer3D(nn.Module):
                 E.check(E.lib().k5_sample(h, C.byref(s), E.stream_ptr(dev)), "k5_sample")
             else:
                 E.check(E.lib().k5_sample_cond(h, C.byref(s), visual_cond.data_ptr(), E.stream_ptr(dev)), "k5_sample_cond")
+        self._watch_end(latent)
+        return latent
+
+    def _sample_windows(self, latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
+                        guidance_weight, scale_factor, sparse_params, visual_cond, windows, window_text):
+        """`sample(windows=...)`: the k5_sample_windows call."""
+        if not latent.is_cuda or latent.dtype != torch.float32 or not latent.is_contiguous():
+            raise RuntimeError("latent must be a contiguous fp32 CUDA tensor")
+        starts, weights = windows
+        starts = [int(v) for v in starts]
+        weights = [[float(v) for v in row] for row in weights]
+        nwin = len(starts)
+        if nwin < 1 or len(weights) != nwin or len({len(r) for r in weights}) != 1:
+            raise ValueError("windows must be (starts [nwin], weights [nwin][F])")
+        F = len(weights[0])
+        T, H, W, _ = latent.shape
+        if window_text is not None and len(window_text) != nwin:
+            raise ValueError(f"window_text holds {len(window_text)} prompts, the plan has nwin = {nwin} windows")
+        self._last_tokens = F * (H // self.patch_size[1]) * (W // self.patch_size[2])
+        self._check_visual_cond(visual_cond, latent)
+        h = self.engine(latent.device)
+        dev = latent.device
+        keep = []
+        if window_text is not None:
+            text_embeds, text_rope_pos = window_text[0]
+        a = E.SampleWindowsArgs()
+        s = a.sample
+        s.fwd = self._forward_args((F, H, W), None, self.in_visual_dim, text_embeds["text_embeds"].to(dev), text_embeds["pooled_embed"].to(dev),
+                                   0.0, visual_rope_pos, text_rope_pos, scale_factor, sparse_params, keep)
+        if abs(guidance_weight - 1.0) > 1e-6:
+            s.null_cond = self._text_cond(null_text_embeds["text_embeds"].to(dev), null_text_embeds["pooled_embed"].to(dev),
+                                          null_text_rope_pos, keep)
+        if window_text is not None:
+            conds = (E.TextCond * nwin)()
+            for i, (te, tp) in enumerate(window_text):
+                conds[i] = self._text_cond(te["text_embeds"].to(dev), te["pooled_embed"].to(dev), tp, keep)
+            a.conds = conds
+        sig = [float(v) for v in sigmas]
+        arr = (C.c_float * len(sig))(*sig)
+        s.latent, s.num_steps, s.sigmas, s.guidance_weight = latent.data_ptr(), len(sig) - 1, arr, float(guidance_weight)
+        st = E.i32_array(starts)
+        wt = (C.c_float * (nwin * F))(*[v for row in weights for v in row])
+        a.total_T, a.nwin, a.starts, a.weights = T, nwin, st, wt
+        self._watch_begin()
+        with torch.cuda.device(dev):
+            E.check(E.lib().k5_sample_windows(h, C.byref(a), E.ptr(visual_cond), E.stream_ptr(dev)), "k5_sample_windows")
         self._watch_end(latent)
         return latent
 

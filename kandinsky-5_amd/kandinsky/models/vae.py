@@ -30,6 +30,14 @@ OPT_TEMPORAL_TILING = {int(k): tuple(v) for k, v in _T["temporal"].items()}
 OPT_SPATIAL_TILING = {int(k): tuple(v) for k, v in _T["spatial"].items()}
 
 
+def temporal_tiling_key(num_frames):
+    """The row of OPT_TEMPORAL_TILING for a clip of `num_frames` pixel frames.  The table ends at 241 frames (10 s) and repeats with a period of
+    48 frames (12 latent frames) from 73 on, so a longer clip (context windows) reads the row one or more periods lower, in 193 .. 240.  The
+    strides of those rows (2, 3 or 4 latent frames) divide a period: the last temporal tile stays full.  Up to 241 frames: the row itself."""
+    num_frames = int(num_frames)
+    return num_frames if num_frames <= 241 else 193 + (num_frames - 193) % 48
+
+
 class DecoderOutput:
     def __init__(self, sample):
         self.sample = sample
@@ -293,7 +301,7 @@ class AutoencoderKLHunyuanVideo(nn.Module):
         if math.sqrt(height * width) < 450 and num_frames <= 97:
             ft = fs = num_frames
         else:
-            ft, fs = OPT_TEMPORAL_TILING[num_frames]
+            ft, fs = OPT_TEMPORAL_TILING[temporal_tiling_key(num_frames)]
         if math.sqrt(height * width) > 900:
             (ht, hs), (wt, ws) = OPT_SPATIAL_TILING[height], OPT_SPATIAL_TILING[width]
         else:

@@ -92,7 +92,7 @@ class Kandinsky5T2VPipeline:
                  num_steps: int = None, guidance_weight: float = None, scheduler_scale: float = 10.0,
                  negative_caption: str = _NEG, expand_prompts: bool = True, save_path: str = None,
                  progress: bool = True, image=None, video=None, strength: float = None, mask=None, callback=None,
-                 preview_every: int = 0, preview_factors=None):
+                 preview_every: int = 0, preview_factors=None, context_seconds: float = None, context_overlap_seconds: float = None):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -105,7 +105,23 @@ class Kandinsky5T2VPipeline:
         `progress` draws a tqdm bar over the sampling steps (single-rank, tqdm installed).  `callback`, `preview_every`,
         `preview_factors` (optional, extension; single-rank only): `callback(info)` after every sampling step (a truthy return stops
         the run with `kandinsky.models.dit.SamplingInterrupted`), with a uint8 (T,H,W,3) `info.preview` of the denoised latent on every
-        `preview_every`-th step through the latent -> RGB factors `preview_factors` (`kandinsky.preview`), see `generate`."""
+        `preview_every`-th step through the latent -> RGB factors `preview_factors` (`kandinsky.preview`), see `generate`.
+        `context_seconds`, `context_overlap_seconds` (optional, extension): a clip longer than the checkpoint's trained length, e.g.
+        `pipe(text, time_length=20, context_seconds=10, context_overlap_seconds=2.5)`: the model runs on overlapping windows of
+        `context_seconds` (s * 24 // 4 + 1 latent frames, overlapping by s * 6; default a quarter of the window) whose velocities are
+        cross-faded at every step.  `text` may then be a list of nwin prompts, one per window in order (one clip comes back).
+        Single-rank, without `video`, previews or MagCache."""
+        ctx = {}
+        if context_seconds is not None:
+            if time_length == 0:
+                raise ValueError("context_seconds needs a video (time_length > 0)")
+            if context_seconds <= 0:
+                raise ValueError(f"context_seconds must be > 0, got {context_seconds}")
+            ctx["context_frames"] = int(context_seconds * 24 // 4 + 1)
+            if context_overlap_seconds is not None:
+                ctx["context_overlap"] = int(context_overlap_seconds * 6)
+        elif context_overlap_seconds is not None:
+            raise ValueError("context_overlap_seconds needs context_seconds")
         strength = 1.0 if strength is None else float(strength)
         if not 0.0 < strength <= 1.0:
             raise ValueError(f"strength must be in (0, 1], got {strength}")
@@ -127,7 +143,7 @@ class Kandinsky5T2VPipeline:
                        else texts)
         else:
             caption = self._agree_on(lambda: self._beautified(text), as_object=True) if expand_prompts else text
-        bs = len(caption) if isinstance(caption, list) else 1
+        bs = len(caption) if isinstance(caption, list) and not ctx else 1   # with context windows a list is one prompt per window of ONE clip
 
         images = generate_sample((bs, frames, height // 8, width // 8, 16), caption, self.dit, self.vae, self.conf,
                                  text_embedder=self.text_embedder, num_steps=steps, guidance_weight=weight,
@@ -135,6 +151,6 @@ class Kandinsky5T2VPipeline:
                                  device=self.device_map["dit"], vae_device=self.device_map["vae"],
                                  text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload,
                                  image=image, video=video, strength=strength, mask=mask, callback=callback,
-                                 preview_every=preview_every, preview_factors=preview_factors)
+                                 preview_every=preview_every, preview_factors=preview_factors, **ctx)
         torch.cuda.empty_cache()
         return self._save(images, time_length, save_path) if self.local_dit_rank == 0 else None

@@ -66,7 +66,24 @@ def build_parser():
                    help="write DIR/step_###.png, the middle frame of the denoised estimate, while sampling; needs --preview_factors")
     p.add_argument("--preview_every", type=int, default=argparse.SUPPRESS, metavar="K", help="with --preview: a picture every K steps and after the last (default 1)")
     p.add_argument("--preview_factors", type=str, default=argparse.SUPPRESS, metavar="FILE", help="with --preview: factors written by --fit_preview_factors")
+    p.add_argument("--context_seconds", type=float, default=argparse.SUPPRESS, metavar="S",
+                   help="a clip longer than the checkpoint's trained length: sample --video_duration as overlapping temporal windows of S seconds "
+                        "(e.g. --video_duration 20 --context_seconds 10)")
+    p.add_argument("--context_overlap_seconds", type=float, default=argparse.SUPPRESS, metavar="S",
+                   help="with --context_seconds: how far neighbouring windows overlap (default a quarter of the window)")
     return p
+
+
+def context_keywords(args):
+    """--context_seconds / --context_overlap_seconds -> the pipeline's keywords"""
+    if not hasattr(args, "context_seconds"):
+        if hasattr(args, "context_overlap_seconds"):
+            raise ValueError("--context_overlap_seconds needs --context_seconds")
+        return {}
+    kw = {"context_seconds": args.context_seconds}
+    if hasattr(args, "context_overlap_seconds"):
+        kw["context_overlap_seconds"] = args.context_overlap_seconds
+    return kw
 
 
 def preview_keywords(args):
@@ -148,6 +165,7 @@ def main(argv=None):
               f"--preview_factors {args.fit_preview_factors}")
         return
     edit_kw.update(preview_keywords(args))
+    edit_kw.update(context_keywords(args))
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
