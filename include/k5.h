@@ -305,6 +305,21 @@ int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, f
 int k5_x0_preview(const float* x, const void* v_cond, const void* v_uncond, float w, float sigma_next, const float* source,
                   const float* keep_mask, const float* rgb_w, const float* rgb_b, float* x0_out, uint8_t* rgb, int64_t cells, int C,
                   void* stream);
+/* Normalized attention guidance, the combine (added under ABI 11, as the exports above were): z_pos and z_neg are the outputs of ONE cross-attention
+ * against the positive and the negative text (the same queries), bf16 [rows][ld] of which D columns are used; out likewise, and out == z_pos is
+ * allowed.  Per row, in fp32, every operation rounded on its own except the one written fma:
+ *   d = zp - zn;  g = fma(s - 1, d, zp)                          (= zp + (s - 1)(zp - zn))
+ *   n_pos = sum_k |zp_k|,  n_g = sum_k |g_k|                     over all D channels (all heads)
+ *   f = 1 if n_g <= tau * n_pos (this includes 0 <= 0), else (tau * n_pos) / n_g
+ *   out = bf16(zp + alpha * (f * g - zp))                         nearest-even
+ * which is the published rule (Chen et al. 2025: extrapolate s zp - (s - 1) zn, clamp the growth of the row's L1 norm at tau, blend with alpha)
+ * arranged so that finite inputs give no NaN (a zero row gives zero) and that z_neg == z_pos, s == 1 and alpha == 0 each return z_pos bit for
+ * bit.  The two sums have a fixed order (one wave per row: a lane adds its 8-column chunks lane, lane + 64, .. in ascending column order, then an
+ * xor butterfly over the 64 lanes), so equal inputs give equal bits.  One pass: both inputs read once, out written once, 16 bytes per lane.
+ * K5_ERR_ARG: a NULL or not 16-byte aligned pointer, rows < 1, D % 8, ld < D, ld % 8, s < 1, tau < 1, alpha outside [0, 1]; K5_ERR_UNSUPPORTED:
+ * D > 2048 (the row is held in registers).  Nothing is launched when the call is refused. */
+int k5_nag_combine_bf16(const void* z_pos, const void* z_neg, void* out, int rows, int D, int ld, float s, float tau, float alpha,
+                        void* stream);
 /* LoRA merge, in place on a row-major matrix (added under ABI 11, as the MagCache calibration exports were): W'[n][k] = W[n][k] + scale *
  * sum_r B[n][r] A[r][k].  W [rows][ld] (cols <= ld) of w_dtype K5_BF16 or K5_F32;
  * A [R][cols], B [rows][R], each K5_F32 / K5_BF16 / K5_F16, device pointers, converted to fp32 on load; 1 <= R <= 256.  The arithmetic is
@@ -479,6 +494,24 @@ typedef struct k5_watch {
 int k5_dit_set_watch(k5_dit* dit, const k5_watch* watch /* NULL clears */);
 /* of the last k5_sample* call: steps enqueued and completed, and whether the callback stopped it (0 / 1) */
 int k5_dit_watch_state(k5_dit* dit, int* steps_done, int* stopped);
+
+/* Normalized attention guidance on the handle (added under ABI 11): a negative prompt inside the cross-attention of ONE forward, for runs
+ * without classifier-free guidance.  While set, every CONDITIONAL forward (k5_dit_forward, k5_dit_forward_many, the conditional branch of
+ * k5_sample* — never the unconditional one) carries a second text stream: the negative prompt's tokens go through the text prologue and the
+ * text blocks as the positive ones do, with their own RoPE positions and the forward's own time embedding (a forward has one: it is built from
+ * the POSITIVE prompt's pooled embedding, negative->pooled_embed is not read); every visual block projects and normalises its queries once,
+ * attends once to each stream and k5_nag_combine_bf16(scale, tau, alpha) joins the two outputs in front of the out projection.  Per block that
+ * is one cross-attention launch and one memory-bound pass more; the text side runs twice.  Not set, a forward enqueues exactly what it always
+ * did.  `negative` is BORROWED: the struct and what it points to stay valid until the guidance is cleared; its pointers are read at every
+ * forward (k5_sample* caches the negative prologue per call, as it does for the two other prompts).  One negative prompt serves every sample of
+ * k5_sample_many and every window of k5_sample_windows.  Works on sequence-parallel shards (the text is replicated, the rule is per token:
+ * no collective is added), on the conditional handle of a CFG pair, in the captured step, under k5_sample_edit, and with MagCache (a skipped
+ * step runs no visual block and so no guidance; the shipped ratio tables were measured without it — calibrate with it set).
+ * K5_ERR_ARG: scale < 1, tau < 1, alpha outside [0, 1], text_len < 1, a NULL text_embed or text_rope_pos.  scale == 1 or alpha == 0 is accepted
+ * and means off (the combine would return z_pos).  NULL clears.  k5_dit_nag_state: whether guidance is on, and how many combines the handle
+ * has enqueued (num_visual_blocks per guided forward), optionally resetting the count. */
+int k5_dit_set_nag(k5_dit* dit, const k5_text_cond* negative /* NULL clears */, float scale, float tau, float alpha);
+int k5_dit_nag_state(k5_dit* dit, int* on, long long* combines, int reset);
 
 /* S forwards of the same (T, H, W) in one call, one after another (a convenience entry point like k5_sample_many): args->x is device fp32
  * [S][T][H][W][args->x_channels], conds HOST [S], args->time shared; out_velocity bf16 [S][T][H][W][out_visual_dim].  Sequence i is

@@ -441,7 +441,18 @@ struct k5_dit {
   // prompt only, so k5_sample computes them once per call and branch (slot 0 = cond, 1 = uncond) and every later step copies
   // 0.9 MB instead of re-running two GEMMs + two LayerNorms.  k5_dit_forward (one call per step, caller-owned buffers that
   // may change between calls) does not cache.
-  struct TextCache { DevBuf text, pool; bool valid = false; int L = 0; } text_cache[2];
+  struct TextCache { DevBuf text, pool; bool valid = false; int L = 0; } text_cache[3];   // [2]: the negative prompt of k5_dit_set_nag (text only)
+
+  // Normalized attention guidance (k5_dit_set_nag): a second, negative text stream through the text blocks (the forward's own
+  // time embedding) and, per visual block, a second cross-attention of the same queries joined to the first by k5_launch_nag_combine.
+  // Conditional forwards only (text_slot != 1).  The buffers below exist only once a guided forward has run.
+  struct Nag {
+    bool on = false;
+    const k5_text_cond* neg = nullptr;             // borrowed: valid until cleared, read at every forward
+    float scale = 1.f, tau = 1.f, alpha = 0.f;
+    long long combines = 0;                        // k5_launch_nag_combine launches enqueued so far (k5_dit_nag_state)
+    DevBuf text, ck_all, cvt_all, ck, cvt, o;      // the negative stream | its stacked keys / V^T | the per-block ones | its attention output [n][D]
+  } nag;
 
   // MagCache (reference kandinsky/magcache_utils.py:16-101): skip the visual blocks on some calls and re-apply the
   // cached bf16 residual of the same cond / uncond slot.  Decisions depend on the ratio table and the call counter only.
@@ -1282,32 +1293,45 @@ int run_self_attention_heads(k5_dit* d, hipStream_t s, const AttnW& a, const voi
 // keys and V^T of every visual block's cross-attention from the text stream (k5_dit::cross_kv_batched): ws_ck_all [L][blocks * D] (normalised
 // keys), ws_cvt_all [blocks * D][rup(L, 8)].  The key projection is the launch it was per block (128 x 128 tiles for 256 rows); the V^T one is forced
 // onto the same 128 x 128 kernel the per-block call took (57 344 weight rows would otherwise pick a 256-row kernel: another summation order).
-int cross_kv_batched_run(k5_dit* d, hipStream_t s, const void* text, int L) {
+// ck_all / cvt_all: where they go (the negative stream of k5_dit_set_nag has a pair of its own)
+int cross_kv_batched_run(k5_dit* d, hipStream_t s, const void* text, int L, DevBuf& ck_all, DevBuf& cvt_all) {
   const int D = d->D, H = d->Hh, nbv = (int)d->vblocks.size();
   const int ldvt = (int)rup(L, 8);
-  K5CHK(d->ws_ck_all.ensure((size_t)L * nbv * D * 2)); K5CHK(d->ws_cvt_all.ensure((size_t)nbv * D * ldvt * 2));
+  K5CHK(ck_all.ensure((size_t)L * nbv * D * 2)); K5CHK(cvt_all.ensure((size_t)nbv * D * ldvt * 2));
   {
     Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(text, d->cx_wk_all.p, d->cx_bk_all.as<float>(), d->ws_ck_all.p, L, nbv * D, D, D, D, nbv * D, K5_EPI_BIAS, nullptr, 0, nullptr, s, 2));
-    K5CHK(k5_launch_gemm_bf16(d->cx_wv_all.p, text, d->cx_bv_all.as<float>(), d->ws_cvt_all.p, nbv * D, L, D, D, D, ldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s, 2));
+    K5CHK(k5_launch_gemm_bf16(text, d->cx_wk_all.p, d->cx_bk_all.as<float>(), ck_all.p, L, nbv * D, D, D, D, nbv * D, K5_EPI_BIAS, nullptr, 0, nullptr, s, 2));
+    K5CHK(k5_launch_gemm_bf16(d->cx_wv_all.p, text, d->cx_bv_all.as<float>(), cvt_all.p, nbv * D, L, D, D, D, ldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s, 2));
   }
   Scope sc(d, s, "elementwise");
   const int32_t hc[2] = {H, 0};   // one norm weight per block's H heads, no RoPE
-  return k5_launch_rmsnorm_rope(d->ws_ck_all.p, d->cx_knorm_all.as<float>(), nullptr, nullptr, L, nbv * H, nbv * D, hc, s);
+  return k5_launch_rmsnorm_rope(ck_all.p, d->cx_knorm_all.as<float>(), nullptr, nullptr, L, nbv * H, nbv * D, hc, s);
 }
 
+// the negative side of a guided cross-attention (k5_dit_set_nag): its text stream, where its keys / V^T are or go, and its output rows
+struct NagCross { const void* text; int L; void* ck; void* cvt; int ldck; void* o; };
+
+
 // kv_ready: ck (row stride ldck) / cvt already hold this block's normalised keys and V^T (cross_kv_batched_run)
+// nag: attend the same queries to the negative stream as well and join the two outputs (k5_launch_nag_combine, in place on o) in front of
+// the out projection; with kv_ready its keys / V^T are ready too
 int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, int rows, const void* text,
-                        int L, void* q, void* ck, void* cvt, void* o, void* resid, const float* gate, bool kv_ready = false, int ldck = 0) {
+                        int L, void* q, void* ck, void* cvt, void* o, void* resid, const float* gate, bool kv_ready = false, int ldck = 0,
+                        const NagCross* nag = nullptr) {
   const int D = d->D, H = d->Hh;
   const int ldvt = (int)rup(L, 8);
   if (!kv_ready) ldck = D;
+  const int nldvt = nag ? (int)rup(nag->L, 8) : 0, nldck = nag ? (kv_ready ? nag->ldck : D) : 0;
   {
     Scope sc(d, s, "gemm");
     K5CHK(k5_launch_gemm_bf16(h, a.wq.p, a.bq.as<float>(), q, rows, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
     if (!kv_ready) {
       K5CHK(k5_launch_gemm_bf16(text, a.wk.p, a.bk.as<float>(), ck, L, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
       K5CHK(k5_launch_gemm_bf16(a.wv.p, text, a.bv.as<float>(), cvt, D, L, D, D, D, ldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
+      if (nag) {
+        K5CHK(k5_launch_gemm_bf16(nag->text, a.wk.p, a.bk.as<float>(), nag->ck, nag->L, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+        K5CHK(k5_launch_gemm_bf16(a.wv.p, nag->text, a.bv.as<float>(), nag->cvt, D, nag->L, D, D, D, nldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
+      }
     }
   }
   // RMSNorm of the queries (no RoPE in cross-attention, nn.py:330-334) is fused into the attention kernel's Q-fragment load when the
@@ -1317,6 +1341,7 @@ int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h,
     Scope sc(d, s, "elementwise");
     if (!fuse_qnorm) K5CHK(k5_launch_rmsnorm_rope(q, a.norm.as<float>(), nullptr, nullptr, rows, H, D, nullptr, s));
     if (!kv_ready) K5CHK(k5_launch_rmsnorm_rope(ck, a.norm.as<float>() + 64, nullptr, nullptr, L, H, D, nullptr, s));
+    if (!kv_ready && nag) K5CHK(k5_launch_rmsnorm_rope(nag->ck, a.norm.as<float>() + 64, nullptr, nullptr, nag->L, H, D, nullptr, s));
   }
   {
     Scope sc(d, s, "attn_cross");
@@ -1327,6 +1352,16 @@ int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h,
     at.score_bound = a.score_bound; at.stream = s;
     at.query_norm = fuse_qnorm ? &qn : nullptr;
     K5CHK(k5_launch_attention_bf16_range(at));
+    if (nag) {   // the same (normalised or to-be-normalised) queries against the negative stream
+      at.K = nag->ck; at.Vt = nag->cvt; at.O = nag->o;
+      at.kv_len = nag->L; at.ldk = nldck; at.ldvt = nldvt;
+      K5CHK(k5_launch_attention_bf16_range(at));
+    }
+  }
+  if (nag) {
+    Scope sc(d, s, "elementwise");
+    K5CHK(k5_launch_nag_combine(o, nag->o, o, rows, D, D, d->nag.scale, d->nag.tau, d->nag.alpha, s));
+    ++d->nag.combines;
   }
   return attn_out_projection(d, s, a, o, rows, resid, gate);
 }
@@ -1644,7 +1679,10 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     n = N - tok0 < n_pad ? N - tok0 : n_pad;
     if ((long long)(P - 1) * n_pad >= N) { k5_set_error("sequence parallel x%d: %d token blocks leave a rank without work", P, N / 64); return K5_ERR_UNSUPPORTED; }
   }
-  K5CHK(ensure_workspaces(d, sp ? P * n_pad : N, L));
+  // normalized attention guidance: the conditional branch only (slot 1 is the unconditional forward of k5_sample*)
+  const k5_text_cond* ncond = d->nag.on && text_slot != 1 ? d->nag.neg : nullptr;
+  const int Ln = ncond ? ncond->text_len : 0;
+  K5CHK(ensure_workspaces(d, sp ? P * n_pad : N, Ln > L ? Ln : L));   // the negative stream borrows the text blocks' scratch
   if (sp) {
     K5CHK(d->ws_q.ensure((size_t)n_pad * D * 2)); K5CHK(d->ws_kfull.ensure((size_t)P * n_pad * D * 2));
     K5CHK(d->ws_vtfull.ensure((size_t)P * n_pad * D * 2));
@@ -1755,8 +1793,46 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   }
   // ---- visual blocks (dit.py:176-178, 61-79) ----
   const bool cx_all = !mag_skip && d->cross_kv_batched && c.num_visual_blocks > 1 && d->cx_wk_all.p;
-  if (cx_all) K5CHK(cross_kv_batched_run(d, s, d->ws_text.p, L));
+  if (cx_all) K5CHK(cross_kv_batched_run(d, s, d->ws_text.p, L, d->ws_ck_all, d->ws_cvt_all));
   const int Lr8 = (int)rup(L, 8);
+  // ---- the negative text stream of k5_dit_set_nag: prologue and text blocks as above, with its own RoPE positions and THIS forward's
+  // modulation (one time embedding per forward: the positive prompt's pooled embedding); nothing of it on a step MagCache skips ----
+  const bool nag = ncond && !mag_skip && c.num_visual_blocks > 0;
+  const int Lnr8 = (int)rup(Ln, 8);
+  if (nag) {
+    auto& ng = d->nag;
+    const float *ncos = nullptr, *nsin = nullptr;
+    K5CHK(prepare_text_rope(d, s, *ncond, &ncos, &nsin));
+    K5CHK(ng.text.ensure((size_t)Ln * D * 2)); K5CHK(ng.o.ensure((size_t)n * D * 2));
+    {
+      Scope sc(d, s, "prologue");
+      k5_dit::TextCache* tc = text_slot >= 0 ? &d->text_cache[2] : nullptr;
+      if (tc && tc->valid && tc->L == Ln) {
+        HIPCHK(hipMemcpyAsync(ng.text.p, tc->text.p, (size_t)Ln * D * 2, hipMemcpyDeviceToDevice, s));
+      } else {
+        const void* text_bf;
+        K5CHK(to_bf16(d, s, ncond->text_embed, ncond->text_dtype, (size_t)Ln * c.in_text_dim, d->ws_text_in, &text_bf));
+        K5CHK(k5_launch_gemm_bf16(text_bf, d->text_w.p, d->text_b.as<float>(), d->ws_th.p, Ln, D, c.in_text_dim, c.in_text_dim,
+                                  c.in_text_dim, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+        K5CHK(k5_launch_ln_affine(d->ws_th.p, d->text_lnw.as<float>(), d->text_lnb.as<float>(), ng.text.p, nullptr, Ln, D, s));
+        if (tc) {
+          K5CHK(tc->text.ensure((size_t)Ln * D * 2));
+          HIPCHK(hipMemcpyAsync(tc->text.p, ng.text.p, (size_t)Ln * D * 2, hipMemcpyDeviceToDevice, s));
+          tc->valid = true; tc->L = Ln;
+        }
+      }
+    }
+    for (int i = 0; i < c.num_text_blocks; ++i) {
+      const BlockW& b = d->tblocks[i];
+      const float* m = mod + b.mod_off;
+      K5CHK(ln_mod(d, s, ng.text.p, m, d->ws_th.p, Ln));
+      K5CHK(run_self_attention(d, s, b.self_attn, d->ws_th.p, Ln, d->ws_tqk.p, d->ws_tvt.p, d->ws_to.p, ncos, nsin, ng.text.p, m + 2 * D, "attn_text"));
+      K5CHK(ln_mod(d, s, ng.text.p, m + 3 * D, d->ws_th.p, Ln));
+      K5CHK(run_ff(d, s, b, d->ws_th.p, Ln, d->ws_tff.p, ng.text.p, m + 5 * D));
+    }
+    if (cx_all) K5CHK(cross_kv_batched_run(d, s, ng.text.p, Ln, ng.ck_all, ng.cvt_all));
+    else { K5CHK(ng.ck.ensure((size_t)Ln * D * 2)); K5CHK(ng.cvt.ensure((size_t)D * Lnr8 * 2)); }
+  }
   const int sched = sp ? sp_schedule(d, nabla) : 0;
   if (sp) d->sp_mode_used = sched;
   for (int i = 0; i < (mag_skip ? 0 : c.num_visual_blocks); ++i) {
@@ -1778,12 +1854,19 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
                                m + 2 * D, "attn_self", nabla ? &na : nullptr, text_slot > 0 ? 1 : 0, h8_sa));
     }
     K5CHK(ln_mod(d, s, d->ws_vis.p, m + 3 * D, d->ws_h.p, n));
+    NagCross nx{};
+    if (nag) {
+      auto& ng = d->nag;
+      if (cx_all) nx = NagCross{ng.text.p, Ln, ng.ck_all.as<bf16_t>() + (size_t)i * D, ng.cvt_all.as<bf16_t>() + (size_t)i * D * Lnr8, c.num_visual_blocks * D, ng.o.p};
+      else nx = NagCross{ng.text.p, Ln, ng.ck.p, ng.cvt.p, D, ng.o.p};
+    }
     if (cx_all)
       K5CHK(run_cross_attention(d, s, b.cross_attn, d->ws_h.p, n, d->ws_text.p, L, d->ws_qk.p, d->ws_ck_all.as<bf16_t>() + (size_t)i * D,
-                                d->ws_cvt_all.as<bf16_t>() + (size_t)i * D * Lr8, d->ws_o.p, d->ws_vis.p, m + 5 * D, true, c.num_visual_blocks * D));
+                                d->ws_cvt_all.as<bf16_t>() + (size_t)i * D * Lr8, d->ws_o.p, d->ws_vis.p, m + 5 * D, true, c.num_visual_blocks * D,
+                                nag ? &nx : nullptr));
     else
       K5CHK(run_cross_attention(d, s, b.cross_attn, d->ws_h.p, n, d->ws_text.p, L, d->ws_qk.p, d->ws_ck.p, d->ws_cvt.p,
-                                d->ws_o.p, d->ws_vis.p, m + 5 * D));
+                                d->ws_o.p, d->ws_vis.p, m + 5 * D, false, 0, nag ? &nx : nullptr));
     const bool h8_ff = d->fp8_fuse_ln && ff_fp8_in(d, b, n);
     K5CHK(ln_mod(d, s, d->ws_vis.p, m + 6 * D, d->ws_h.p, n, h8_ff));
     K5CHK(run_ff(d, s, b, d->ws_h.p, n, d->ws_ff.p, d->ws_vis.p, m + 8 * D, h8_ff));
@@ -1866,6 +1949,7 @@ extern "C" void k5_dit_destroy(k5_dit* d) {
   d->ws_attn_stats.release(); d->ws_attn_flags.release(); d->ws_attn_cnt.release(); d->ws_attn_part.release(); d->ws_leave_sig.release();
   if (d->h_leave_sig) { (void)hipHostFree(d->h_leave_sig); d->h_leave_sig = nullptr; }
   for (auto& t : d->text_cache) { t.text.release(); t.pool.release(); }
+  for (DevBuf* b : {&d->nag.text, &d->nag.ck_all, &d->nag.cvt_all, &d->nag.ck, &d->nag.cvt, &d->nag.o}) b->release();
   for (auto& kv : d->staged) kv.second.dev.release();   // a handle destroyed before finalize still holds its staged matrices
   d->mag.residual[0].release(); d->mag.residual[1].release(); d->mag.pm_one.release();
   for (auto& b : d->vblocks) { b.w1_f8.release(); b.w2_f8.release(); b.s1_f8.release(); b.s2_f8.release(); }
@@ -2276,7 +2360,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     HIPCHK(hipStreamSynchronize(s));   // the caller's tables are host memory
     win_starts = d->ws_win.as<int32_t>(); win_weights = reinterpret_cast<const float*>(static_cast<char*>(d->ws_win.p) + sb);
   }
-  d->text_cache[0].valid = d->text_cache[1].valid = false;   // the prompt tensors are constant for THIS call only
+  d->text_cache[0].valid = d->text_cache[1].valid = d->text_cache[2].valid = false;   // the prompt tensors are constant for THIS call only
   K5CHK(reset_attn_pref(d, s));                              // ... and so is what the softmax-form memory of the layers is worth
   // where the visual queries are normalised (see k5_dit::fuse_qnorm_auto): a plain one-handle dense run decides after its first step
   struct FuseGuard { k5_dit* d; ~FuseGuard() { d->fuse_now = false; d->leave_collect = false; } } fuse_guard{d};
@@ -2407,7 +2491,9 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   if (watching) K5CHK(watch_step(0));   // ahead of the capture: these launches are not part of the graph
   hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
   HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  const long long nag_before = d->nag.combines;
   const int rc = one_step(1);
+  const long long nag_per_step = d->nag.combines - nag_before;   // k5_dit_nag_state counts launches: the capture stands for step 1's, every further replay adds as many
   const hipError_t ec = hipStreamEndCapture(s, &g);
   if (rc != K5_OK || ec != hipSuccess || !g) {
     if (g) (void)hipGraphDestroy(g);
@@ -2417,8 +2503,9 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(g); k5_set_error("hipGraphInstantiate failed"); return K5_ERR_HIP; }
   int status = K5_OK;
   for (int i = 1; i < a->num_steps && status == K5_OK; ++i) {
-    if (hipGraphLaunch(ge, s) != hipSuccess) { k5_set_error("hipGraphLaunch failed"); status = K5_ERR_HIP; }
-    else if (watching) {   // between graph launches, sigma_next as a host scalar
+    if (hipGraphLaunch(ge, s) != hipSuccess) { k5_set_error("hipGraphLaunch failed"); status = K5_ERR_HIP; break; }
+    if (i > 1) d->nag.combines += nag_per_step;
+    if (watching) {   // between graph launches, sigma_next as a host scalar
       status = watch_step(i);
       if (wt.stopped) break;
     }
@@ -2531,6 +2618,30 @@ extern "C" int k5_dit_set_watch(k5_dit* d, const k5_watch* w) {
     HIPCHK(hipMemcpy(wt.wb.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
   }
   wt.fn = w->fn; wt.user = w->user; wt.every = w->preview_every; wt.want_x0 = w->want_x0 != 0; wt.on = true;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_set_nag(k5_dit* d, const k5_text_cond* negative, float scale, float tau, float alpha) {
+  g_err[0] = 0;
+  if (!d) { k5_set_error("k5_dit_set_nag: null handle"); return K5_ERR_ARG; }
+  k5_dit::Nag& ng = d->nag;
+  if (!negative) { ng.on = false; ng.neg = nullptr; d->text_cache[2].valid = false; return K5_OK; }
+  if (!(scale >= 1.0f)) { k5_set_error("k5_dit_set_nag: scale must be >= 1 (got %g)", (double)scale); return K5_ERR_ARG; }
+  if (!(tau >= 1.0f)) { k5_set_error("k5_dit_set_nag: tau must be >= 1 (got %g)", (double)tau); return K5_ERR_ARG; }
+  if (!(alpha >= 0.0f && alpha <= 1.0f)) { k5_set_error("k5_dit_set_nag: alpha must be in [0, 1] (got %g)", (double)alpha); return K5_ERR_ARG; }
+  if (negative->text_len < 1) { k5_set_error("k5_dit_set_nag: text_len must be >= 1 (got %d)", negative->text_len); return K5_ERR_ARG; }
+  if (!negative->text_embed || !negative->text_rope_pos) { k5_set_error("k5_dit_set_nag: the negative prompt needs text_embed and text_rope_pos"); return K5_ERR_ARG; }
+  ng.neg = negative; ng.scale = scale; ng.tau = tau; ng.alpha = alpha;
+  ng.on = scale != 1.0f && alpha != 0.0f;   // otherwise the combine hands z_pos through: run nothing
+  d->text_cache[2].valid = false;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_nag_state(k5_dit* d, int* on, long long* combines, int reset) {
+  if (!d) { k5_set_error("k5_dit_nag_state: null handle"); return K5_ERR_ARG; }
+  if (on) *on = d->nag.on ? 1 : 0;
+  if (combines) *combines = d->nag.combines;
+  if (reset) d->nag.combines = 0;
   return K5_OK;
 }
 
@@ -2695,7 +2806,7 @@ int lora_requant(k5_dit* d, int vblock, int f8) {
 
 // everything the handle keeps that was computed from the weights as they were
 int lora_drop_derived(k5_dit* d) {
-  d->text_cache[0].valid = d->text_cache[1].valid = false;
+  d->text_cache[0].valid = d->text_cache[1].valid = d->text_cache[2].valid = false;
   K5CHK(reset_attn_pref(d, nullptr));
   auto& mg = d->mag;
   mg.cnt = mg.first;

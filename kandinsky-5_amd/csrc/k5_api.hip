@@ -409,6 +409,18 @@ int k5_x0_preview(const float* x, const void* v_cond, const void* v_uncond, floa
                                   (hipStream_t)stream), "k5_x0_preview");
 }
 
+int k5_nag_combine_bf16(const void* z_pos, const void* z_neg, void* out, int rows, int D, int ld, float s, float tau, float alpha,
+                        void* stream) {
+  const int st = k5_launch_nag_combine(z_pos, z_neg, out, rows, D, ld, s, tau, alpha, (hipStream_t)stream);
+  if (st == K5_ERR_UNSUPPORTED) { k5_set_error("k5_nag_combine_bf16: D = %d is more than the register-resident row holds (2048)", D); return st; }
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_nag_combine_bf16: need 16-byte aligned non-null pointers, rows > 0, D %% 8 == 0, ld >= D, ld %% 8 == 0, s >= 1, tau >= 1, "
+                 "0 <= alpha <= 1 (rows %d, D %d, ld %d, s %g, tau %g, alpha %g)", rows, D, ld, (double)s, (double)tau, (double)alpha);
+    return st;
+  }
+  return ret(st, "k5_nag_combine_bf16");
+}
+
 int k5_conv3d_bf16(const void* X, const void* W, const float* bias, void* out, int Ts, int Hs, int Ws, int Cin, int Cout,
                    int up_t, int up_s, int ldc, const void* resid, int ldr, void* stream) {
   return ret(k5_launch_conv3d_bf16(X, W, bias, out, Ts, Hs, Ws, Cin, Cout, up_t, up_s, ldc, resid, ldr, (hipStream_t)stream),

@@ -198,6 +198,12 @@ int k5_launch_cfg_euler_windows(float* img, const void* v_cond, const void* v_un
 int k5_launch_x0_preview(const float* x, const void* v_cond, const void* v_uncond, float w, float sigma_next, const float* source,
                          const float* keep_mask, const float* rgb_w, const float* rgb_b, float* x0_out, uint8_t* rgb, int64_t cells, int C,
                          hipStream_t stream);
+// normalized attention guidance on two cross-attention outputs of the same queries, bf16 [rows][ld] (D columns used): per row d = zp - zn,
+// g = fma(s - 1, d, zp), f = sum|g| <= tau * sum|zp| ? 1 : tau * sum|zp| / sum|g|, out = bf16(zp + alpha * (f * g - zp)), fp32, one pass, out may be
+// z_pos.  D % 8 == 0, ld >= D, ld % 8 == 0, 16-byte pointers, s >= 1, tau >= 1, 0 <= alpha <= 1 (K5_ERR_ARG); D <= 2048 (K5_ERR_UNSUPPORTED).
+// Nothing is launched when it refuses.
+int k5_launch_nag_combine(const void* z_pos, const void* z_neg, void* out, int rows, int D, int ld, float s, float tau, float alpha,
+                          hipStream_t stream);
 // fp32 -> bf16 cast, bf16 -> fp32
 int k5_launch_cast_f32_bf16(const float* x, void* out, int64_t n, hipStream_t stream);
 // weight packing: src [rows][cols] (K5_F32 / K5_BF16 / K5_F16, device) -> dst [rows][ld] bf16 (RNE) or fp32, pad columns zeroed

@@ -1259,3 +1259,90 @@ int k5_launch_x0_preview(const float* x, const void* vc, const void* vu, float w
                      keep_mask ? source : nullptr, keep_mask, rgb_w, rgb_b, x0_out, rgb, C, cells);
   return done();
 }
+
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// Normalized attention guidance (k5_nag_combine_bf16): z_pos / z_neg are the outputs of one cross-attention against the positive
+// and the negative text, same queries.  Per row, fp32, every operation rounded on its own except the one named fma:
+//   d = zp - zn;  g = fma(s - 1, d, zp);  n_pos = sum |zp|,  n_g = sum |g| over the D channels;
+//   f = n_g <= tau * n_pos ? 1 : (tau * n_pos) / n_g;  out = bf16(zp + alpha * (f * g - zp))
+// zn == zp, s == 1 and alpha == 0 each give zp bit for bit (d or s - 1 is 0, so g is zp, the two sums are the same additions and f is 1; alpha *
+// (f * g - zp) is then an exact 0, and an exact 0 hands zp through with its sign); finite inputs give no NaN (n_g > tau * n_pos >= 0 before the division).
+// One wave per row (the ln_kernel shape): a lane's up to MAXC 16-byte chunks of both inputs are loaded in one burst, the row stays in
+// registers between the sums and the store, so each input is read once and out written once; out may be z_pos (or z_neg): a lane has read a
+// chunk before it writes it and no other lane touches it.  Order of the sums: a lane adds its elements in ascending column order from 0, then
+// the xor butterfly of wave_sum — the same bits on every launch.  D = 128 keeps 16 of the 64 lanes busy: those rows are 256 bytes, nothing to win.
+// The blend's product, difference, product and sum must not contract (nag_blend, under `#pragma clang fp contract(off)` like x0_estimate).
+__device__ __forceinline__ float nag_blend(float p, float g, float f, float alpha) {
+#pragma clang fp contract(off)
+  const float fg = f * g;
+  const float t = fg - p;
+  const float at = alpha * t;
+  return at == 0.0f ? p : p + at;   // p + 0 would turn a -0 of z_pos into +0
+}
+
+__global__ __launch_bounds__(256) void nag_combine_kernel(const bf16_t* zp, const bf16_t* zn, bf16_t* out, int rows, int D, int ld,
+                                                          float sm1, float tau, float alpha) {
+  const int lane = threadIdx.x & 63, nch = D >> 3;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;   // wave-uniform
+  const size_t base = (size_t)row * ld;
+  u32x4 rp[MAXC], rn[MAXC];
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+    const int ch = lane + 64 * i;
+    if (ch < nch) {
+      rp[i] = *reinterpret_cast<const u32x4*>(zp + base + 8 * ch);
+      rn[i] = *reinterpret_cast<const u32x4*>(zn + base + 8 * ch);
+    }
+  }
+  float g[MAXC][8];
+  float n_pos = 0.f, n_g = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+    if (lane + 64 * i < nch) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint32_t pw = rp[i][j >> 1], nw = rn[i][j >> 1];
+        const float p = __uint_as_float((j & 1) ? (pw & 0xffff0000u) : (pw << 16));
+        const float q = __uint_as_float((j & 1) ? (nw & 0xffff0000u) : (nw << 16));
+        g[i][j] = fmaf(sm1, __fsub_rn(p, q), p);
+        n_pos = __fadd_rn(n_pos, fabsf(p));
+        n_g = __fadd_rn(n_g, fabsf(g[i][j]));
+      }
+    }
+  }
+  n_pos = wave_sum(n_pos); n_g = wave_sum(n_g);   // every lane of the wave is here (a lane without chunks carries zeros)
+  const float cap = __fmul_rn(tau, n_pos);
+  const float f = n_g <= cap ? 1.0f : __fdiv_rn(cap, n_g);
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+    const int ch = lane + 64 * i;
+    if (ch < nch) {
+      float o[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const uint32_t pw = rp[i][j >> 1];
+        const float p = __uint_as_float((j & 1) ? (pw & 0xffff0000u) : (pw << 16));
+        o[j] = nag_blend(p, g[i][j], f, alpha);
+      }
+      const u32x4 pk = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
+      *reinterpret_cast<u32x4*>(out + base + 8 * ch) = pk;
+    }
+  }
+}
+
+}  // namespace
+
+int k5_launch_nag_combine(const void* z_pos, const void* z_neg, void* out, int rows, int D, int ld, float s, float tau, float alpha,
+                          hipStream_t stream) {
+  if (!z_pos || !z_neg || !out || rows <= 0 || D <= 0 || ld < D || !(s >= 1.0f) || !(tau >= 1.0f) || !(alpha >= 0.0f && alpha <= 1.0f))
+    return K5_ERR_ARG;
+  const auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if ((D & 7) || (ld & 7) || misaligned(z_pos) || misaligned(z_neg) || misaligned(out)) return K5_ERR_ARG;
+  if (D > 64 * 8 * MAXC) return K5_ERR_UNSUPPORTED;   // the register-resident row
+  hipLaunchKernelGGL(nag_combine_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, (const bf16_t*)z_pos, (const bf16_t*)z_neg, (bf16_t*)out,
+                     rows, D, ld, s - 1.0f, tau, alpha);
+  return done();
+}

@@ -202,6 +202,9 @@ SYMBOLS = {
     "k5_x0_preview": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I64, _I, _P]),
     "k5_dit_set_watch": (_I, [_P, C.POINTER(Watch)]),
     "k5_dit_watch_state": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "k5_nag_combine_bf16": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _P]),
+    "k5_dit_set_nag": (_I, [_P, C.POINTER(TextCond), _F, _F, _F]),
+    "k5_dit_nag_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), _I]),
     "k5_dit_forward_many": (_I, [_P, C.POINTER(ForwardArgs), _I, C.POINTER(TextCond), _P, _P]),
     "k5_comm_unique_id": (_I, [C.c_char_p, _P]),
     "k5_dit_comm_init": (_I, [_P, C.c_char_p, _I, _I, _P]),
@@ -514,6 +517,22 @@ def cfg_euler_edit_(img, v_cond, v_uncond, w, dt, source, noise, keep_mask, sigm
     check(lib().k5_cfg_euler_edit(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), ptr(source), ptr(noise), ptr(keep_mask),
                                   float(sigma_next), cells, C_, stream_ptr(img.device)), "k5_cfg_euler_edit")
     return img
+
+
+def nag_combine_(z_pos, z_neg, s, tau, alpha, out=None, D=None):
+    """Normalized attention guidance on two cross-attention outputs, in place on z_pos unless `out` is given (k5_nag_combine_bf16): per row
+    g = z_pos + (s - 1)(z_pos - z_neg), the growth of the row's L1 norm clamped at tau, blended back with alpha.  bf16 [rows][ld] tensors with
+    a unit column stride; D (default: all ld columns) of each row are used, the rest is not touched."""
+    out = z_pos if out is None else out
+    for x in (z_pos, z_neg, out):
+        if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1 or x.shape != z_pos.shape or x.stride(0) != z_pos.stride(0):
+            raise ValueError("nag_combine_: z_pos, z_neg and out must be bf16 [rows][ld] tensors of one shape and row stride")
+    rows, ld = z_pos.shape[0], z_pos.stride(0)
+    D = z_pos.shape[1] if D is None else int(D)
+    with torch.cuda.device(z_pos.device):
+        check(lib().k5_nag_combine_bf16(ptr(z_pos), ptr(z_neg), ptr(out), rows, D, ld, float(s), float(tau), float(alpha),
+                                        stream_ptr(z_pos.device)), "k5_nag_combine_bf16")
+    return out
 
 
 def x0_preview(img, v_cond, v_uncond, w, sigma_next, rgb_factors=None, rgb_bias=None, source=None, keep_mask=None, want_x0=False,

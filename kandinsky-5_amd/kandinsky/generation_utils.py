@@ -224,7 +224,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
              null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=False, seed=6554, noise=None, *,
              visual_cond=None, visual_cond_mask=None, batch=1, init_latent=None, strength=1.0, keep_mask=None,
              callback=None, preview_every=0, preview_factors=None, preview_x0=False, context_frames=None, context_overlap=None,
-             context_text=None, _watch=None):
+             context_text=None, nag_text_embeds=None, nag_text_rope_pos=None, nag_scale=None, nag_tau=2.5, nag_alpha=0.25, _watch=None):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -252,7 +252,14 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     `visual_rope_pos[0]` (its first F entries when it holds the clip's) and the NABLA parameters are the window's.  `context_text`: a
     list of nwin `(text_embeds, text_rope_pos)` pairs, a prompt per window in order, instead of `text_embeds` / `text_rope_pos`.  F >= T
     is the plain run, bit for bit.  The engine-backed model runs the whole loop in one call (k5_sample_windows), any other callable the
-    same forwards in the same order from Python.  ValueError with init_latent, preview_every > 0, MagCache or a multi-rank model."""
+    same forwards in the same order from Python.  ValueError with init_latent, preview_every > 0, MagCache or a multi-rank model.
+    `nag_scale`, `nag_tau`, `nag_alpha`, `nag_text_embeds`, `nag_text_rope_pos` (optional, extension): normalized attention guidance, a
+    negative prompt inside the cross-attention of the conditional forward (`DiffusionTransformer3D.set_nag`) — the way to a negative
+    prompt at guidance_weight 1, where `null_text_embeds` is never read.  `nag_scale` None (default) is off and nothing changes;
+    otherwise `nag_text_embeds` (a dict like `text_embeds`) and `nag_text_rope_pos` are the negative prompt, one for every sample and
+    window.  Set on the model for this call and removed afterwards, also when the call raises; every rank of a group or a CFG pair
+    passes the same values.  The unconditional forward of a CFG run is not touched.  5 / 2.5 / 0.25 are the values commonly quoted for
+    NAG: starting points, not tuned on any Kandinsky checkpoint.  ValueError on a model without the engine (wrapped or duck-typed)."""
     from .models.dit import split_per_sample
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
@@ -264,6 +271,26 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         text_embeds, null_text_embeds, text_rope_pos, null_text_rope_pos = (
             split_per_sample(v, 1, n)[0] for v, n in ((text_embeds, "text_embeds"), (null_text_embeds, "null_text_embeds"),
                                                  (text_rope_pos, "text_rope_pos"), (null_text_rope_pos, "null_text_rope_pos")))
+    if _watch is None and nag_scale is not None:   # guidance for exactly this call: set, run without the keywords, put back what was there
+        from .models.dit import DiffusionTransformer3D, check_nag_args
+        check_nag_args(nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha)
+        if type(model) is not DiffusionTransformer3D:
+            raise ValueError("nag_scale needs the engine-backed DiffusionTransformer3D: normalized attention guidance runs inside its "
+                             "forward, a wrapped or duck-typed model has no hook for it")
+        before = model._nag
+        try:
+            model.set_nag(nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha)
+            return generate(model, device, shape, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
+                            null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=progress, seed=seed, noise=noise,
+                            visual_cond=visual_cond, visual_cond_mask=visual_cond_mask, batch=batch, init_latent=init_latent,
+                            strength=strength, keep_mask=keep_mask, callback=callback, preview_every=preview_every,
+                            preview_factors=preview_factors, preview_x0=preview_x0, context_frames=context_frames,
+                            context_overlap=context_overlap, context_text=context_text)
+        finally:
+            if before is not None:
+                model.set_nag({"text_embeds": before["text"], "pooled_embed": before["pooled"]}, before["pos"], *before["args"])
+            else:
+                model.clear_nag()
     if _watch is None:   # the outermost call owns the hook (and closes the bar); the per-sample calls of a batch share it
         steps_run = num_steps - (edit_first_step(num_steps, strength) if init_latent is not None else 0)
         watch = _StepWatch(model, callback, preview_every, preview_factors, preview_x0, progress, batch * steps_run, shape[-1])
@@ -523,7 +550,8 @@ def frames_to_uint8(frames):
 def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25, guidance_weight=5.0,
                     scheduler_scale=1, negative_caption="", seed=6554, device="cuda", vae_device="cuda",
                     text_embedder_device="cuda", progress=True, offload=False, image=None, video=None, strength=1.0, mask=None,
-                    callback=None, preview_every=0, preview_factors=None, context_frames=None, context_overlap=None):
+                    callback=None, preview_every=0, preview_factors=None, context_frames=None, context_overlap=None,
+                    nag_scale=None, nag_tau=2.5, nag_alpha=0.25):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -535,7 +563,9 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     `progress` draws a tqdm bar over the sampling steps when tqdm is installed; `callback`, `preview_every`, `preview_factors`
     (optional, extension): per-step callback, cancel and live previews, see `generate`.  `context_frames`, `context_overlap` (optional,
     extension): a clip longer than the model's trained length, sampled as overlapping temporal windows of `context_frames` latent frames
-    (see `generate` and `context_windows`).  With bs = 1 `caption` may then be a list of nwin prompts, one per window in order."""
+    (see `generate` and `context_windows`).  With bs = 1 `caption` may then be a list of nwin prompts, one per window in order.
+    `nag_scale`, `nag_tau`, `nag_alpha` (optional, extension): normalized attention guidance with the already encoded `negative_caption` as
+    the negative prompt (see `generate`); what makes `negative_caption` count at guidance_weight 1.  None (default) is off."""
     batch, frames, height, width, channels = shape
     ctx_kw, window_captions = {}, None
     if context_frames is not None:
@@ -549,6 +579,11 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
             window_captions, caption = list(caption), caption[0]
     elif context_overlap is not None:
         raise ValueError("context_overlap needs context_frames")
+    if nag_scale is not None:   # before any model runs
+        from .models.dit import DiffusionTransformer3D, check_nag_numbers
+        check_nag_numbers(nag_scale, nag_tau, nag_alpha)
+        if type(dit) is not DiffusionTransformer3D:
+            raise ValueError("nag_scale needs the engine-backed DiffusionTransformer3D (see `generate`)")
     captions = list(caption) if isinstance(caption, (list, tuple)) else [caption] * batch
     if len(captions) != batch:
         raise ValueError(f"{len(captions)} captions for bs={batch} samples")
@@ -595,6 +630,8 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     if offload:
         text_embedder = text_embedder.to("cpu")
 
+    nag_kw = {} if nag_scale is None else dict(nag_text_embeds=uncond, nag_text_rope_pos=torch.arange(n_uncond), nag_scale=nag_scale,
+                                               nag_tau=nag_tau, nag_alpha=nag_alpha)
     patch = conf.model.dit_params.patch_size
     grid = [torch.arange(frames), torch.arange(height // patch[1]), torch.arange(width // patch[2])]
     if offload:
@@ -603,7 +640,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         latent = generate(dit, device, (batch * frames, height, width, channels), num_steps, cond, uncond, grid,
                           text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
                           progress=progress, batch=batch, callback=callback, preview_every=preview_every,
-                          preview_factors=preview_factors, **cond_kw, **ctx_kw)
+                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

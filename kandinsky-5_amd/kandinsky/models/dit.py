@@ -100,6 +100,35 @@ class _DeviceView:
                                          "strides": None}
 
 
+def check_nag_numbers(scale, tau, alpha):
+    """The ValueErrors of the three numbers of normalized attention guidance; returns them as floats."""
+    import math
+    try:
+        scale, tau, alpha = float(scale), float(tau), float(alpha)
+    except (TypeError, ValueError):
+        raise ValueError("nag: scale, tau and alpha must be numbers") from None
+    if not math.isfinite(scale) or scale < 1.0:
+        raise ValueError(f"nag: scale must be a finite number >= 1 (got {scale})")
+    if not math.isfinite(tau) or tau < 1.0:
+        raise ValueError(f"nag: tau must be a finite number >= 1 (got {tau})")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"nag: alpha must be in [0, 1] (got {alpha})")
+    return scale, tau, alpha
+
+
+def check_nag_args(text_embeds, text_rope_pos, scale, tau, alpha):
+    """The ValueErrors of `set_nag` / `generate(nag_scale=, nag_tau=, nag_alpha=, nag_text_embeds=)`; returns (scale, tau, alpha) as floats."""
+    scale, tau, alpha = check_nag_numbers(scale, tau, alpha)
+    if not isinstance(text_embeds, dict) or not torch.is_tensor(text_embeds.get("text_embeds")):
+        raise ValueError('nag: the negative prompt must be a dict with a "text_embeds" tensor (what `generate` takes)')
+    te = text_embeds["text_embeds"]
+    if te.dim() != 2 or te.shape[0] < 1:
+        raise ValueError(f"nag: text_embeds must be [tokens][in_text_dim] with at least one token (got {tuple(te.shape)})")
+    if text_rope_pos is None or len(torch.as_tensor(text_rope_pos).reshape(-1)) != te.shape[0]:
+        raise ValueError("nag: text_rope_pos must have one position per token of the negative prompt")
+    return scale, tau, alpha
+
+
 def check_watch_args(callback, preview_every, rgb_factors, want_x0, channels):
     """The ValueErrors of `set_watch` / `generate(callback=, preview_every=, preview_factors=)`; returns (W [C][3], preview_every)."""
     preview_every = int(preview_every)
@@ -173,6 +202,7 @@ class DiffusionTransformer3D(nn.Module):
         self._lora = []              # (entries, strength) merged into the ENGINE's packed weights: re-added when the engine is rebuilt
         self._lora_saved = {}        # parameters as they were before a merge done in torch (no engine yet): key -> tensor
         self._watch = None           # (trampoline, k5_watch and the arrays it points to) of set_watch: re-installed when the engine is rebuilt
+        self._nag = None             # the negative prompt of set_nag, its k5_text_cond and what that points to: re-installed likewise
 
     # ---------------------------------------------------------------- engine lifetime
     def _destroy_engine(self, force=False):
@@ -241,6 +271,8 @@ class DiffusionTransformer3D(nn.Module):
             self._engine_add_lora(entries, strength)
         if getattr(self, "_watch", None) is not None:
             self._install_watch()
+        if getattr(self, "_nag", None) is not None:
+            self._install_nag()
         if getattr(self, "mag_ratios", None) is not None or getattr(self, "_magcache_calibrate", None) is not None:   # set before the weights were loaded / the handle rebuilt
             from ..magcache_utils import _apply
             _apply(self)
@@ -510,6 +542,55 @@ class DiffusionTransformer3D(nn.Module):
         if self._handle is not None:
             E.check(E.lib().k5_dit_watch_state(self._handle, C.byref(n), C.byref(st)), "k5_dit_watch_state")
         return n.value, bool(st.value)
+
+    # ---------------------------------------------------------------- normalized attention guidance: a negative prompt without CFG
+    def set_nag(self, text_embeds, text_rope_pos, scale=5.0, tau=2.5, alpha=0.25):
+        """A negative prompt inside the cross-attention of ONE forward (k5_dit_set_nag; Normalized Attention Guidance, Chen et al. 2025), for
+        runs at guidance 1 where `null_text_embeds` is never read.  `text_embeds` is the dict `generate` takes ("text_embeds" [L][in_text_dim];
+        "pooled_embed" is not read: a forward has one time embedding, the positive prompt's) and `text_rope_pos` its L positions.  Every
+        conditional forward — `forward`, `forward_many`, the conditional branch of `sample*` — then attends each visual block's queries to the
+        positive and to the negative text and joins the outputs: g = z+ + (scale - 1)(z+ - z-), the growth of the token's L1 norm clamped at
+        `tau`, blended back with `alpha`.  scale >= 1, tau >= 1, 0 <= alpha <= 1; scale == 1 or alpha == 0 is accepted and means off.  The
+        defaults are the values commonly quoted for NAG — starting points, not tuned on any Kandinsky checkpoint.  The model keeps the tensors
+        alive until `clear_nag`."""
+        scale, tau, alpha = check_nag_args(text_embeds, text_rope_pos, scale, tau, alpha)
+        if text_embeds["text_embeds"].shape[1] != self._cfg["in_text_dim"]:
+            raise ValueError(f"nag: text_embeds has {text_embeds['text_embeds'].shape[1]} features, the model takes {self._cfg['in_text_dim']}")
+        self._nag = {"text": text_embeds["text_embeds"], "pooled": text_embeds.get("pooled_embed"), "pos": text_rope_pos,
+                     "args": (scale, tau, alpha), "cond": None, "keep": None}
+        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
+            try:
+                self._install_nag()
+            except Exception:
+                self._nag = None
+                raise
+        return self
+
+    def _install_nag(self):
+        n = self._nag
+        dev = self._handle_device
+        te = n["text"].to(dev)
+        pe = n["pooled"].to(dev) if n["pooled"] is not None else te.new_zeros(1, self._cfg["in_text_dim2"])
+        keep = []
+        cond = self._text_cond(te, pe, n["pos"], keep)
+        n["cond"], n["keep"] = cond, keep    # the engine borrows the struct and what it points to
+        with torch.cuda.device(dev):
+            E.check(E.lib().k5_dit_set_nag(self._handle, C.byref(cond), *n["args"]), "k5_dit_set_nag")
+
+    def clear_nag(self):
+        """Remove the guidance: a forward enqueues exactly what it did before `set_nag`."""
+        self._nag = None
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_set_nag(self._handle, None, 1.0, 1.0, 0.0), "k5_dit_set_nag")
+        return self
+
+    def nag_state(self, reset=False):
+        """(on, combines): whether guidance is on, and how many combine launches the engine has enqueued — num_visual_blocks per guided
+        forward (k5_dit_nag_state).  `reset` zeroes the count afterwards."""
+        on, n = C.c_int(0), C.c_longlong(0)
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_nag_state(self._handle, C.byref(on), C.byref(n), int(bool(reset))), "k5_dit_nag_state")
+        return bool(on.value), n.value
 
     def _step_info(self, info):
         shape = (info.T, info.H, info.W)

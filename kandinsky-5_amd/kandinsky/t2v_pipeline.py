@@ -92,7 +92,8 @@ class Kandinsky5T2VPipeline:
                  num_steps: int = None, guidance_weight: float = None, scheduler_scale: float = 10.0,
                  negative_caption: str = _NEG, expand_prompts: bool = True, save_path: str = None,
                  progress: bool = True, image=None, video=None, strength: float = None, mask=None, callback=None,
-                 preview_every: int = 0, preview_factors=None, context_seconds: float = None, context_overlap_seconds: float = None):
+                 preview_every: int = 0, preview_factors=None, context_seconds: float = None, context_overlap_seconds: float = None,
+                 nag_scale: float = None, nag_tau: float = 2.5, nag_alpha: float = 0.25):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -110,8 +111,16 @@ class Kandinsky5T2VPipeline:
         `pipe(text, time_length=20, context_seconds=10, context_overlap_seconds=2.5)`: the model runs on overlapping windows of
         `context_seconds` (s * 24 // 4 + 1 latent frames, overlapping by s * 6; default a quarter of the window) whose velocities are
         cross-faded at every step.  `text` may then be a list of nwin prompts, one per window in order (one clip comes back).
-        Single-rank, without `video`, previews or MagCache."""
+        Single-rank, without `video`, previews or MagCache.
+        `nag_scale`, `nag_tau`, `nag_alpha` (optional, extension): normalized attention guidance — `negative_caption` steers inside the
+        cross-attention of the one conditional forward, which is what makes it count on the checkpoints that run without classifier-free
+        guidance (nocfg, distil).  `nag_scale` None (default) is off; 5 / 2.5 / 0.25 are the commonly quoted values, starting points that
+        were not tuned on any Kandinsky checkpoint.  See `generate`."""
         ctx = {}
+        if nag_scale is not None:
+            from .models.dit import check_nag_numbers
+            check_nag_numbers(nag_scale, nag_tau, nag_alpha)
+            ctx.update(nag_scale=float(nag_scale), nag_tau=float(nag_tau), nag_alpha=float(nag_alpha))
         if context_seconds is not None:
             if time_length == 0:
                 raise ValueError("context_seconds needs a video (time_length > 0)")

@@ -71,7 +71,24 @@ def build_parser():
                         "(e.g. --video_duration 20 --context_seconds 10)")
     p.add_argument("--context_overlap_seconds", type=float, default=argparse.SUPPRESS, metavar="S",
                    help="with --context_seconds: how far neighbouring windows overlap (default a quarter of the window)")
+    p.add_argument("--nag_scale", type=float, default=argparse.SUPPRESS, metavar="S",
+                   help="normalized attention guidance: --negative_prompt steers inside the cross-attention of the one forward (what makes it "
+                        "count without classifier-free guidance); S >= 1, commonly 5 — a starting point, not tuned on these checkpoints")
+    p.add_argument("--nag_tau", type=float, default=argparse.SUPPRESS, metavar="T", help="with --nag_scale: clamp on the growth of a token's L1 norm, >= 1 (default 2.5)")
+    p.add_argument("--nag_alpha", type=float, default=argparse.SUPPRESS, metavar="A", help="with --nag_scale: blend of the guided output, in [0, 1] (default 0.25)")
     return p
+
+
+def nag_keywords(args):
+    """--nag_scale / --nag_tau / --nag_alpha -> the pipeline's keywords"""
+    if not hasattr(args, "nag_scale"):
+        if hasattr(args, "nag_tau") or hasattr(args, "nag_alpha"):
+            raise ValueError("--nag_tau and --nag_alpha need --nag_scale")
+        return {}
+    kw = {"nag_scale": args.nag_scale, "nag_tau": getattr(args, "nag_tau", 2.5), "nag_alpha": getattr(args, "nag_alpha", 0.25)}
+    if not kw["nag_scale"] >= 1.0 or not kw["nag_tau"] >= 1.0 or not 0.0 <= kw["nag_alpha"] <= 1.0:
+        raise ValueError(f"--nag_scale and --nag_tau must be >= 1 and --nag_alpha in [0, 1] (got {kw['nag_scale']}, {kw['nag_tau']}, {kw['nag_alpha']})")
+    return kw
 
 
 def context_keywords(args):
@@ -132,6 +149,7 @@ def main(argv=None):
     warnings.filterwarnings("ignore")
     args = build_parser().parse_args(argv)
     validate_args(args)
+    nag_kw = nag_keywords(args)   # refused before the models load
     from kandinsky import get_T2V_pipeline
     pipe = get_T2V_pipeline(device_map={"dit": "cuda:0", "vae": "cuda:0", "text_embedder": "cuda:0"}, conf_path=args.config,
                             offload=args.offload, magcache=args.magcache and not args.calibrate_magcache,
@@ -166,6 +184,7 @@ def main(argv=None):
         return
     edit_kw.update(preview_keywords(args))
     edit_kw.update(context_keywords(args))
+    edit_kw.update(nag_kw)
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
