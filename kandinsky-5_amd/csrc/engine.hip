@@ -296,6 +296,8 @@ int sp_plan_2d(int H, int P, int rows_pad, int D, int which, k5ipc::Xfer* tab) {
 
 }  // namespace
 
+namespace { struct SampleRun; }   // what one sample_impl call works on (defined with it)
+
 struct k5_dit {
   k5_dit_config cfg{};
   int D = 0, FF = 0, TD = 0, Hh = 0, Kvis = 0, KvisPad = 0, Fout = 0;
@@ -359,6 +361,12 @@ struct k5_dit {
     hipEvent_t ev[2] = {nullptr, nullptr};         // "step i and its preview are complete"
     int steps_done = 0, stopped = 0;               // of the last k5_sample* call (k5_dit_watch_state)
     int sample = 0, num_samples = 1;               // set by k5_sample_many around each sample
+    // the per-call side, driven by sample_impl (defined next to it): begin, step(i) after step i is enqueued, end
+    int begin(const SampleRun& r, const char* who);   // resets steps_done / stopped; watching: sizes the two slots and the pinned buffers
+    bool preview_at(const SampleRun& r, int i) const;
+    int step(const SampleRun& r, int i);              // enqueues the preview, its copy to the host and the slot's event; delivers step i - 1
+    int deliver(const SampleRun& r, int i);           // step i's callback
+    int end(const SampleRun& r);                      // the last delivery, and the drain of a stopped run
   } watch;
   DevBuf ws_kc;                                    // NABLA: keys pre-multiplied by the softmax scale (separate from the map's keys);
                                                    // under sequence parallelism the reverse: the rank's UNSCALED keys (the scaled ones are gathered)
@@ -2216,19 +2224,22 @@ extern "C" int k5_dit_forward(k5_dit* d, const k5_forward_args* a, void* out_vel
   return st;
 }
 
-// The sampler loop behind k5_sample / k5_sample_cond (edit == nullptr: their launches, their bits), k5_sample_edit and k5_sample_windows
-// (win != nullptr: a->fwd is the window, a->latent / vcond the whole clip of win->total_T frames; never together with edit).
-static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream, const char* who,
-                       const k5_sample_windows_args* win = nullptr) {
-  g_err[0] = 0;
+// "sequence-parallel group" or "CFG pair": the rank group the handle is in (nullptr: none), for the refusals of what is single-rank only
+static const char* rank_group(const k5_dit* d) {
+  return d->comm.active() ? "sequence-parallel group" : d->pair.active() ? "CFG pair" : nullptr;
+}
+
+// Everything sample_impl refuses, before anything is enqueued or allocated and before any per-call state is touched: no HIP call and no
+// write to the handle here.  (A watched call's shape check comes later, where it always was: Watch::begin.)
+static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit,
+                           const k5_sample_windows_args* win, const char* who) {
   if (!d || !a || !a->latent || !a->sigmas || a->num_steps <= 0) return K5_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
   const k5_dit_config& c = d->cfg;
   if (vcond && !c.visual_cond) { k5_set_error("%s: the handle was created with visual_cond = 0", who); return K5_ERR_ARG; }
   if (vcond && (reinterpret_cast<uintptr_t>(vcond) & 3)) { k5_set_error("%s: visual_cond is not 4-byte aligned", who); return K5_ERR_ARG; }
   const int64_t n = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W * c.out_visual_dim;
   if (c.in_visual_dim != c.out_visual_dim) return K5_ERR_UNSUPPORTED;
-  if (edit) {   // refused before anything is enqueued: the latent is output only and must not be one of the borrowed inputs
+  if (edit) {   // the latent is output only and must not be one of the borrowed inputs
     if (!edit->source || !edit->noise) { k5_set_error("%s: edit needs source and noise", who); return K5_ERR_ARG; }
     if (n <= 0) { k5_set_error("%s: bad shapes", who); return K5_ERR_ARG; }
     const uintptr_t l0 = reinterpret_cast<uintptr_t>(a->latent), l1 = l0 + (uintptr_t)n * 4;
@@ -2242,25 +2253,21 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
       if (p0 < l1 && l0 < p1) { k5_set_error("%s: edit %s overlaps latent (latent is output only)", who, t.name); return K5_ERR_ARG; }
     }
   }
-  k5_dit::Watch& wt = d->watch;
-  const bool watching = wt.on;   // false: every line below that mentions the watch is skipped, the call enqueues what it always did
-  if (watching && (d->comm.active() || d->pair.active())) {
+  const k5_dit::Watch& wt = d->watch;
+  if (wt.on && rank_group(d)) {
     k5_set_error("%s: a watch is installed (k5_dit_set_watch) and the handle is in a %s: a rank that stops alone would leave its peers inside a "
-                 "collective", who, d->comm.active() ? "sequence-parallel group" : "CFG pair");
+                 "collective", who, rank_group(d));
     return K5_ERR_STATE;
   }
-  if (win) {   // every refusal before anything is enqueued or any per-call state is touched
+  if (win) {
     if (edit) { k5_set_error("%s: editing with context windows is not supported", who); return K5_ERR_UNSUPPORTED; }
-    if (d->comm.active() || d->pair.active()) {
-      k5_set_error("%s: the handle is in a %s (context windows are single-rank only)", who, d->comm.active() ? "sequence-parallel group" : "CFG pair");
-      return K5_ERR_STATE;
-    }
+    if (rank_group(d)) { k5_set_error("%s: the handle is in a %s (context windows are single-rank only)", who, rank_group(d)); return K5_ERR_STATE; }
     if (d->mag.on || d->cal.on) {
       k5_set_error("%s: %s on the handle: the ratio table is indexed by the call of a plain run, a windowed run makes nwin calls per step", who,
                    d->mag.on ? "MagCache is set" : "MagCache calibration is");
       return K5_ERR_STATE;
     }
-    if (watching && wt.every > 0) {
+    if (wt.on && wt.every > 0) {
       k5_set_error("%s: the watch has previews (preview_every = %d): the preview reads one velocity pair per cell, a windowed step has up to nwin; "
                    "install the watch with preview_every = 0", who, wt.every);
       return K5_ERR_STATE;
@@ -2286,79 +2293,227 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
       return K5_ERR_ARG;
     }
   }
-  wt.steps_done = 0; wt.stopped = 0;
-  const int64_t cells = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W;
-  if (watching) {
-    if (n <= 0) { k5_set_error("%s: bad shapes", who); return K5_ERR_ARG; }
-    for (hipEvent_t& e : wt.ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (wt.every > 0) {
-      const size_t rb = (size_t)cells * 3;
-      for (int i = 0; i < 2; ++i) {
-        K5CHK(wt.rgb[i].ensure(rb));
-        if (wt.want_x0) K5CHK(wt.x0[i].ensure((size_t)n * 4));
+  return K5_OK;
+}
+
+namespace {
+
+// What one sample_impl call works on: filled top to bottom by sample_impl before the first step, read by step(i) and by the watch.
+struct SampleRun {
+  k5_dit* d; const k5_sample_args* a; const float* vcond; const k5_edit_args* edit; const k5_sample_windows_args* win;
+  hipStream_t s = nullptr;
+  int64_t n = 0, cells = 0;                 // elements and cells of the latent one forward sees (with win: a window's)
+  bool cfg_on = false, pair = false;        // pair: CFG-parallel, one branch here, the other on the paired handle
+  void* vel_c = nullptr; void* vel_u = nullptr;
+  std::vector<float> host_tab;              // the schedule, three tables of num_steps entries:
+  const float* t1000 = nullptr;             //   t * 1000, fp32 (:57)
+  const float* dt = nullptr;                //   torch.diff(timesteps) (:105)
+  const float* sigma_next = nullptr;        //   where the kept region is re-noised to after step i (k5_sample_edit)
+  const float* tvec = nullptr; const float* dtvec = nullptr; const float* signext = nullptr;   // graph mode: the same tables on the device ...
+  int* step_ctr = nullptr;                                                                      // ... and the device-side step counter
+  const int32_t* win_starts = nullptr; const float* win_weights = nullptr;   // the window plan on the device
+  const void* slot_prompt[2] = {nullptr, nullptr};   // windows with prompts of their own: whose prologue each text cache slot holds
+
+  // One forward of step i: the text condition through text cache slot `slot`, on the latent slice `x` with its conditioning slice `vc`, into
+  // `vel`.  `tables`: the forward reads its time through the device-side step tables when the step is captured; windows pass none.
+  int forward(int i, const k5_text_cond& cond, int slot, const float* x, void* vel, const float* vc, bool tables = true) {
+    return forward_impl(d, &a->fwd, cond, t1000[i], x, d->cfg.in_visual_dim, vel, s, tables ? tvec : nullptr, tables ? step_ctr : nullptr, slot, vc);
+  }
+
+  int step(int i) {   // enqueue step i: the forwards, then CFG + Euler
+    const k5_dit_config& c = d->cfg;
+    void* const vu = cfg_on ? vel_u : nullptr;
+    if (win) {
+      // every window on its own slice of the latent (T is outermost: a temporal window is contiguous), cond then uncond, into slot k of the
+      // velocity buffers; then one pass over the whole clip blends the windows and applies the step
+      const int64_t frame = n / a->fwd.T, vframe = frame / c.out_visual_dim * (c.in_visual_dim + 1);
+      for (int k = 0; k < win->nwin; ++k) {
+        const k5_text_cond& ck = win->conds ? win->conds[k] : a->fwd.cond;
+        const k5_text_cond& uk = win->null_conds ? win->null_conds[k] : a->null_cond;
+        const float* xk = a->latent + (int64_t)win->starts[k] * frame;
+        const float* vk = vcond ? vcond + (int64_t)win->starts[k] * vframe : nullptr;
+        if (slot_prompt[0] != ck.text_embed) { d->text_cache[0].valid = false; slot_prompt[0] = ck.text_embed; }
+        K5CHK(forward(i, ck, 0, xk, static_cast<bf16_t*>(vel_c) + k * n, vk, false));
+        if (cfg_on) {
+          if (slot_prompt[1] != uk.text_embed) { d->text_cache[1].valid = false; slot_prompt[1] = uk.text_embed; }
+          K5CHK(forward(i, uk, 1, xk, static_cast<bf16_t*>(vel_u) + k * n, vk, false));
+        }
       }
-      if (wt.h_bytes < rb) {
-        for (uint8_t*& h : wt.h_rgb) { if (h) (void)hipHostFree(h); h = nullptr; }
-        wt.h_bytes = 0;
-        for (uint8_t*& h : wt.h_rgb) HIPCHK(hipHostMalloc((void**)&h, rb, hipHostMallocDefault));
-        wt.h_bytes = rb;
-      }
+      Scope sc(d, s, "elementwise");
+      K5CHK(k5_launch_cfg_euler_windows(a->latent, vel_c, vu, a->guidance_weight, dt[i], win_starts, win_weights, win->nwin, a->fwd.T,
+                                        win->total_T, frame, s));
+      return K5_OK;
+    }
+    if (pair) {
+      // my branch only; then the pair's velocities change hands on the side stream (fork / join by events: capturable) and both
+      // handles hold [v_cond | v_uncond] — every rank of both groups applies the same update to the same numbers
+      if (d->cfg_branch == 0) K5CHK(forward(i, a->fwd.cond, 0, a->latent, vel_c, vcond));
+      else K5CHK(forward(i, a->null_cond, 1, a->latent, vel_u, vcond));
+      Scope sc(d, s, "comm");
+      HIPCHK(hipEventRecord(d->ev_vel_ready, s));
+      HIPCHK(hipStreamWaitEvent(d->pair_stream, d->ev_vel_ready, 0));
+      K5CHK(d->pair.all_gather_inplace(d->ws_vel_pair.p, (size_t)n, 2, d->pair_stream));
+      HIPCHK(hipEventRecord(d->ev_vel_done, d->pair_stream));
+      HIPCHK(hipStreamWaitEvent(s, d->ev_vel_done, 0));
+    } else {
+      K5CHK(forward(i, a->fwd.cond, 0, a->latent, vel_c, vcond));
+      if (cfg_on) K5CHK(forward(i, a->null_cond, 1, a->latent, vel_u, vcond));
+    }
+    {
+      Scope sc(d, s, "elementwise");
+      if (!edit) K5CHK(k5_launch_cfg_euler(a->latent, vel_c, vu, a->guidance_weight, dt[i], n, s, dtvec, step_ctr));
+      else K5CHK(k5_launch_cfg_euler_edit(a->latent, vel_c, vu, a->guidance_weight, dt[i], edit->source, edit->noise, edit->keep_mask,
+                                          sigma_next[i], n / c.out_visual_dim, c.out_visual_dim, s, dtvec, signext, step_ctr));
+    }
+    if (step_ctr) K5CHK(k5_launch_step_inc(step_ctr, s));
+    return K5_OK;
+  }
+};
+
+// The captured step and its executable.  On every way out the stream is drained before they go: the executable graph must outlive its
+// launches (this also orders the caller's stream after the sampler).  An eager run holds neither and is not synchronised.
+struct GraphGuard {
+  hipStream_t s; hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
+  ~GraphGuard() {
+    if (ge) { (void)hipStreamSynchronize(s); (void)hipGraphExecDestroy(ge); }
+    if (g) (void)hipGraphDestroy(g);
+  }
+};
+
+}  // namespace
+
+// The watch's side of a sample_impl call.  step(i) follows the launches of step i on the stream (on a preview step the preview kernel and the
+// copy of its RGB to the slot's pinned buffer, then the slot's event); deliver(i) waits for that event on the host and calls back.  step(i)
+// runs deliver(i - 1) only once step i is enqueued, so the GPU has a step of work queued while the host waits and calls.
+int k5_dit::Watch::begin(const SampleRun& r, const char* who) {
+  steps_done = 0; stopped = 0;
+  if (!on) return K5_OK;   // nothing below runs, here or in step: the call enqueues what it always did
+  if (r.n <= 0) { k5_set_error("%s: bad shapes", who); return K5_ERR_ARG; }
+  for (hipEvent_t& e : ev) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (every > 0) {
+    const size_t rb = (size_t)r.cells * 3;
+    for (int i = 0; i < 2; ++i) {
+      K5CHK(rgb[i].ensure(rb));
+      if (want_x0) K5CHK(x0[i].ensure((size_t)r.n * 4));
+    }
+    if (h_bytes < rb) {
+      for (uint8_t*& h : h_rgb) { if (h) (void)hipHostFree(h); h = nullptr; }
+      h_bytes = 0;
+      for (uint8_t*& h : h_rgb) HIPCHK(hipHostMalloc((void**)&h, rb, hipHostMallocDefault));
+      h_bytes = rb;
     }
   }
-  const bool cfg_on = fabsf(a->guidance_weight - 1.0f) > 1e-6f;  // generation_utils.py:63
-  const bool pair = cfg_on && d->pair.active();                  // CFG-parallel: one branch here, the other on the paired handle
-  if (pair) K5CHK(d->ws_vel_pair.ensure(2 * n * 2));
-  else {   // one slot per window
-    K5CHK(d->ws_vel_c.ensure((win ? win->nwin : 1) * n * 2));
-    if (cfg_on) K5CHK(d->ws_vel_u.ensure((win ? win->nwin : 1) * n * 2));
+  return K5_OK;
+}
+
+bool k5_dit::Watch::preview_at(const SampleRun& r, int i) const { return every > 0 && ((i + 1) % every == 0 || i == r.a->num_steps - 1); }
+
+int k5_dit::Watch::step(const SampleRun& r, int i) {   // after step i is enqueued; the caller leaves its loop when `stopped`
+  const int slot = i & 1;
+  if (preview_at(r, i)) {
+    Scope sc(r.d, r.s, "elementwise");
+    const int C = r.d->cfg.in_visual_dim;
+    const float* w = wb.as<float>();
+    K5CHK(k5_launch_x0_preview(r.a->latent, r.vel_c, r.cfg_on ? r.vel_u : nullptr, r.a->guidance_weight, r.sigma_next[i],
+                               r.edit ? r.edit->source : nullptr, r.edit ? r.edit->keep_mask : nullptr, w, w + 3 * C,
+                               want_x0 ? x0[slot].as<float>() : nullptr, rgb[slot].as<uint8_t>(), r.cells, C, r.s));
+    HIPCHK(hipMemcpyAsync(h_rgb[slot], rgb[slot].p, (size_t)r.cells * 3, hipMemcpyDeviceToHost, r.s));
   }
-  void* vel_c = pair ? d->ws_vel_pair.p : d->ws_vel_c.p;
-  void* vel_u = pair ? (void*)(d->ws_vel_pair.as<bf16_t>() + n) : d->ws_vel_u.p;
+  HIPCHK(hipEventRecord(ev[slot], r.s));
+  steps_done = i + 1;
+  if (i > 0) K5CHK(deliver(r, i - 1));
+  return K5_OK;
+}
+
+int k5_dit::Watch::deliver(const SampleRun& r, int i) {
+  const int slot = i & 1;
+  HIPCHK(hipEventSynchronize(ev[slot]));
+  const bool pv = preview_at(r, i);
+  k5_watch_info info{};
+  info.step = i; info.num_steps = r.a->num_steps; info.sample = sample; info.num_samples = num_samples;
+  info.sigma_next = r.sigma_next[i];
+  info.rgb = pv ? h_rgb[slot] : nullptr;
+  info.x0 = pv && want_x0 ? x0[slot].as<float>() : nullptr;
+  info.T = r.win ? r.win->total_T : r.a->fwd.T; info.H = r.a->fwd.H; info.W = r.a->fwd.W; info.C = r.d->cfg.in_visual_dim;
+  if (fn(user, &info) != 0) stopped = 1;
+  return K5_OK;
+}
+
+int k5_dit::Watch::end(const SampleRun& r) {   // the last step's callback; a stopped run ends with the stream drained
+  if (!on) { steps_done = r.a->num_steps; return K5_OK; }
+  if (!stopped) K5CHK(deliver(r, steps_done - 1));
+  if (stopped) HIPCHK(hipStreamSynchronize(r.s));
+  return K5_OK;
+}
+
+// The sampler loop behind k5_sample / k5_sample_cond (edit == nullptr: their launches, their bits), k5_sample_edit and k5_sample_windows
+// (win != nullptr: a->fwd is the window, a->latent / vcond the whole clip of win->total_T frames; never together with edit).
+static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream, const char* who,
+                       const k5_sample_windows_args* win = nullptr) {
+  g_err[0] = 0;
+  K5CHK(sample_refusals(d, a, vcond, edit, win, who));
+  const k5_dit_config& c = d->cfg;
+  k5_dit::Watch& wt = d->watch;
+  SampleRun r{d, a, vcond, edit, win};
+  r.s = (hipStream_t)stream;
+  r.cells = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W;
+  r.n = r.cells * c.out_visual_dim;
+  K5CHK(wt.begin(r, who));
+  r.cfg_on = fabsf(a->guidance_weight - 1.0f) > 1e-6f;  // generation_utils.py:63
+  r.pair = r.cfg_on && d->pair.active();
+  if (r.pair) K5CHK(d->ws_vel_pair.ensure(2 * r.n * 2));
+  else {   // one slot per window
+    K5CHK(d->ws_vel_c.ensure((win ? win->nwin : 1) * r.n * 2));
+    if (r.cfg_on) K5CHK(d->ws_vel_u.ensure((win ? win->nwin : 1) * r.n * 2));
+  }
+  r.vel_c = r.pair ? d->ws_vel_pair.p : d->ws_vel_c.p;
+  r.vel_u = r.pair ? (void*)(d->ws_vel_pair.as<bf16_t>() + r.n) : d->ws_vel_u.p;
   // hipGraph mode (BASELINE config 5 "hipGraph-captured step"): the per-step scalars live in device tables indexed by a
   // device-side step counter, so ONE captured step (forward(s) + CFG/Euler + counter increment) replays for every step.
   // Step 0 runs eagerly (it sizes every workspace and fills the RoPE / permutation caches), step 1 is captured, steps 1..
-  // are launches of the instantiated graph.  Not with MagCache (its skip pattern changes the launch sequence per step)
-  // or while profiling (events).
-  // not replayed: MagCache (host decisions) and its calibration (host-side call counter and buffer swap), profiling (events), the NABLA map tap (its destination advances on the host per launch: a replay
-  // would overwrite the slots baked at capture — ADVICE r5), loopback groups (their collectives are host rendezvous).  The IPC transport IS
-  // replayable: its epochs live on the device and the peers' buffers were mapped by the eager first step (ipc_comm.h)
+  // are launches of the instantiated graph.
+  // Not replayed: MagCache (host decisions: its skip pattern changes the launch sequence per step) and its calibration (host-side call
+  // counter and buffer swap), profiling (events), the NABLA map tap (its destination advances on the host per launch: a replay would
+  // overwrite the slots baked at capture — ADVICE r5), loopback groups (their collectives are host rendezvous), windows (the captured step
+  // holds one forward pair).  The IPC transport IS replayable: its epochs live on the device and the peers' buffers were mapped by the eager
+  // first step (ipc_comm.h)
   const bool graph = d->use_graph && !d->mag.on && !d->cal.on && !d->profiling && a->num_steps > 2 && !d->nabla_tap && !d->comm.loop && !d->pair.loop &&
-                     !win;   // windows run eagerly: the captured step holds one forward pair
-  std::vector<float> host_tab(3 * (size_t)a->num_steps);
-  for (int i = 0; i < a->num_steps; ++i) {
-    host_tab[i] = a->sigmas[i] * 1000.0f;                        // t * 1000, fp32 (:57)
-    host_tab[a->num_steps + i] = a->sigmas[i + 1] - a->sigmas[i];  // torch.diff(timesteps) (:105)
-    host_tab[2 * a->num_steps + i] = a->sigmas[i + 1];             // where the kept region is re-noised to after step i (k5_sample_edit)
+                     !win;
+  const int N = a->num_steps;
+  r.host_tab.resize(3 * (size_t)N);
+  for (int i = 0; i < N; ++i) {
+    r.host_tab[i] = a->sigmas[i] * 1000.0f;
+    r.host_tab[N + i] = a->sigmas[i + 1] - a->sigmas[i];
+    r.host_tab[2 * N + i] = a->sigmas[i + 1];
   }
-  const float* tvec = nullptr; const float* dtvec = nullptr; const float* signext = nullptr; int* step = nullptr;
-  hipStream_t caller = s;
+  r.t1000 = r.host_tab.data(); r.dt = r.t1000 + N; r.sigma_next = r.dt + N;
   if (graph) {
     if (!d->graph_stream) {
       HIPCHK(hipStreamCreateWithFlags(&d->graph_stream, hipStreamNonBlocking));
       HIPCHK(hipEventCreateWithFlags(&d->ev_graph, hipEventDisableTiming));
     }
-    HIPCHK(hipEventRecord(d->ev_graph, caller));          // everything the caller enqueued so far happens before the sampler
-    s = d->graph_stream;
-    HIPCHK(hipStreamWaitEvent(s, d->ev_graph, 0));
-    K5CHK(d->ws_sched.ensure(host_tab.size() * 4 + 16));
-    HIPCHK(hipMemcpyAsync(d->ws_sched.p, host_tab.data(), host_tab.size() * 4, hipMemcpyHostToDevice, s));
-    step = reinterpret_cast<int*>(d->ws_sched.as<float>() + host_tab.size());
-    HIPCHK(hipMemsetAsync(step, 0, 4, s));
-    HIPCHK(hipStreamSynchronize(s));   // host_tab is a local
-    tvec = d->ws_sched.as<float>(); dtvec = tvec + a->num_steps; signext = dtvec + a->num_steps;
+    HIPCHK(hipEventRecord(d->ev_graph, r.s));             // everything the caller enqueued so far happens before the sampler
+    r.s = d->graph_stream;
+    HIPCHK(hipStreamWaitEvent(r.s, d->ev_graph, 0));
+    K5CHK(d->ws_sched.ensure(r.host_tab.size() * 4 + 16));
+    HIPCHK(hipMemcpyAsync(d->ws_sched.p, r.host_tab.data(), r.host_tab.size() * 4, hipMemcpyHostToDevice, r.s));
+    r.step_ctr = reinterpret_cast<int*>(d->ws_sched.as<float>() + r.host_tab.size());
+    HIPCHK(hipMemsetAsync(r.step_ctr, 0, 4, r.s));
+    HIPCHK(hipStreamSynchronize(r.s));   // host_tab lives in this call only
+    r.tvec = d->ws_sched.as<float>(); r.dtvec = r.tvec + N; r.signext = r.dtvec + N;
   }
+  const hipStream_t s = r.s;
   if (edit) {   // the start latent: the source at sigmas[0] everywhere, whatever the mask
     Scope sc(d, s, "elementwise");
-    K5CHK(k5_launch_edit_renoise(a->latent, edit->source, edit->noise, a->sigmas[0], n, s));
+    K5CHK(k5_launch_edit_renoise(a->latent, edit->source, edit->noise, a->sigmas[0], r.n, s));
   }
-  const int32_t* win_starts = nullptr; const float* win_weights = nullptr;
   if (win) {   // the plan, uploaded once per call: [nwin] int32 starts, then [nwin][F] fp32 weights
     const size_t sb = (size_t)win->nwin * 4, wb = (size_t)win->nwin * a->fwd.T * 4;
     K5CHK(d->ws_win.ensure(sb + wb));
     HIPCHK(hipMemcpyAsync(d->ws_win.p, win->starts, sb, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(static_cast<char*>(d->ws_win.p) + sb, win->weights, wb, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));   // the caller's tables are host memory
-    win_starts = d->ws_win.as<int32_t>(); win_weights = reinterpret_cast<const float*>(static_cast<char*>(d->ws_win.p) + sb);
+    r.win_starts = d->ws_win.as<int32_t>(); r.win_weights = reinterpret_cast<const float*>(static_cast<char*>(d->ws_win.p) + sb);
   }
   d->text_cache[0].valid = d->text_cache[1].valid = d->text_cache[2].valid = false;   // the prompt tensors are constant for THIS call only
   K5CHK(reset_attn_pref(d, s));                              // ... and so is what the softmax-form memory of the layers is worth
@@ -2366,7 +2521,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   struct FuseGuard { k5_dit* d; ~FuseGuard() { d->fuse_now = false; d->leave_collect = false; } } fuse_guard{d};
   d->fuse_now = false; d->leave_collect = false; d->fuse_last = -1;
   const bool auto_fuse = d->fuse_qnorm_auto && !d->fuse_qnorm && !d->comm.active() && d->attn_mode == K5_ATTN_AUTO && d->row_offsets &&   // (a CFG pair's handles decide each for itself)
-                         a->fwd.attention_type == 0 && a->num_steps >= 2;
+                         a->fwd.attention_type == 0 && N >= 2;
   if (auto_fuse) {
     K5CHK(d->ws_leave_sig.ensure(4));
     if (!d->h_leave_sig) HIPCHK(hipHostMalloc((void**)&d->h_leave_sig, 4, hipHostMallocDefault));
@@ -2383,139 +2538,33 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     d->fuse_last = d->fuse_now ? 1 : 0;
     return K5_OK;
   };
-  const void* slot_prompt[2] = {nullptr, nullptr};   // windows with prompts of their own: whose prologue each text cache slot holds
-  auto one_step = [&](int i) -> int {
-    const float t1000 = host_tab[i], dt = host_tab[a->num_steps + i];
-    if (win) {
-      // every window on its own slice of the latent (T is outermost: a temporal window is contiguous), cond then uncond, into slot k of the
-      // velocity buffers; then one pass over the whole clip blends the windows and applies the step
-      const int64_t frame = n / a->fwd.T, vframe = frame / c.out_visual_dim * (c.in_visual_dim + 1);
-      for (int k = 0; k < win->nwin; ++k) {
-        const k5_text_cond& ck = win->conds ? win->conds[k] : a->fwd.cond;
-        const k5_text_cond& uk = win->null_conds ? win->null_conds[k] : a->null_cond;
-        const float* xk = a->latent + (int64_t)win->starts[k] * frame;
-        const float* vk = vcond ? vcond + (int64_t)win->starts[k] * vframe : nullptr;
-        if (slot_prompt[0] != ck.text_embed) { d->text_cache[0].valid = false; slot_prompt[0] = ck.text_embed; }
-        K5CHK(forward_impl(d, &a->fwd, ck, t1000, xk, c.in_visual_dim, static_cast<bf16_t*>(vel_c) + k * n, s, nullptr, nullptr, 0, vk));
-        if (cfg_on) {
-          if (slot_prompt[1] != uk.text_embed) { d->text_cache[1].valid = false; slot_prompt[1] = uk.text_embed; }
-          K5CHK(forward_impl(d, &a->fwd, uk, t1000, xk, c.in_visual_dim, static_cast<bf16_t*>(vel_u) + k * n, s, nullptr, nullptr, 1, vk));
-        }
+  // Step 0 is always eager.  In graph mode step 1 is captured and instantiated (after the watch has followed step 0: those launches are not
+  // part of the graph) and steps 1.. are launches of the executable; between them the watch reads sigma_next as a host scalar.
+  GraphGuard cap{s};
+  long long nag_per_step = 0;
+  for (int i = 0; i < N; ++i) {
+    if (i == 0 || !graph) K5CHK(r.step(i));
+    else {
+      if (i == 1) {
+        HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        const long long nag_before = d->nag.combines;
+        const int rc = r.step(1);
+        nag_per_step = d->nag.combines - nag_before;   // k5_dit_nag_state counts launches: the capture stands for step 1's, every further replay adds as many
+        const hipError_t ec = hipStreamEndCapture(s, &cap.g);
+        if (rc != K5_OK) return rc;
+        if (ec != hipSuccess || !cap.g) { k5_set_error("hipStreamEndCapture: %s", hipGetErrorString(ec)); return K5_ERR_HIP; }
+        if (hipGraphInstantiate(&cap.ge, cap.g, nullptr, nullptr, 0) != hipSuccess) { k5_set_error("hipGraphInstantiate failed"); return K5_ERR_HIP; }
       }
-      Scope sc(d, s, "elementwise");
-      K5CHK(k5_launch_cfg_euler_windows(a->latent, vel_c, cfg_on ? vel_u : nullptr, a->guidance_weight, dt, win_starts, win_weights, win->nwin,
-                                        a->fwd.T, win->total_T, frame, s));
-      return K5_OK;
+      if (hipGraphLaunch(cap.ge, s) != hipSuccess) { k5_set_error("hipGraphLaunch failed"); return K5_ERR_HIP; }
+      if (i > 1) d->nag.combines += nag_per_step;
     }
-    if (pair) {
-      // my branch only; then the pair's velocities change hands on the side stream (fork / join by events: capturable) and both
-      // handles hold [v_cond | v_uncond] — every rank of both groups applies the same update to the same numbers
-      if (d->cfg_branch == 0) K5CHK(forward_impl(d, &a->fwd, a->fwd.cond, t1000, a->latent, c.in_visual_dim, vel_c, s, tvec, step, 0, vcond));
-      else K5CHK(forward_impl(d, &a->fwd, a->null_cond, t1000, a->latent, c.in_visual_dim, vel_u, s, tvec, step, 1, vcond));
-      Scope sc(d, s, "comm");
-      HIPCHK(hipEventRecord(d->ev_vel_ready, s));
-      HIPCHK(hipStreamWaitEvent(d->pair_stream, d->ev_vel_ready, 0));
-      K5CHK(d->pair.all_gather_inplace(d->ws_vel_pair.p, (size_t)n, 2, d->pair_stream));
-      HIPCHK(hipEventRecord(d->ev_vel_done, d->pair_stream));
-      HIPCHK(hipStreamWaitEvent(s, d->ev_vel_done, 0));
-    } else {
-      K5CHK(forward_impl(d, &a->fwd, a->fwd.cond, t1000, a->latent, c.in_visual_dim, vel_c, s, tvec, step, 0, vcond));
-      if (cfg_on) K5CHK(forward_impl(d, &a->fwd, a->null_cond, t1000, a->latent, c.in_visual_dim, vel_u, s, tvec, step, 1, vcond));
-    }
-    {
-      Scope sc(d, s, "elementwise");
-      if (!edit) K5CHK(k5_launch_cfg_euler(a->latent, vel_c, cfg_on ? vel_u : nullptr, a->guidance_weight, dt, n, s, dtvec, step));
-      else K5CHK(k5_launch_cfg_euler_edit(a->latent, vel_c, cfg_on ? vel_u : nullptr, a->guidance_weight, dt, edit->source, edit->noise,
-                                          edit->keep_mask, host_tab[2 * a->num_steps + i], n / c.out_visual_dim, c.out_visual_dim, s, dtvec,
-                                          signext, step));
-    }
-    if (step) K5CHK(k5_launch_step_inc(step, s));
-    return K5_OK;
-  };
-  // The watch: after_step(i) follows the launches of step i on the stream (on a preview step the preview kernel and the copy of its RGB to the
-  // slot's pinned buffer, then the slot's event); deliver(i) waits for that event on the host and calls back.  The loops below run
-  // deliver(i - 1) only once step i is enqueued, so the GPU has a step of work queued while the host waits and calls.
-  auto preview_at = [&](int i) { return wt.every > 0 && ((i + 1) % wt.every == 0 || i == a->num_steps - 1); };
-  auto after_step = [&](int i) -> int {
-    const int slot = i & 1;
-    if (preview_at(i)) {
-      Scope sc(d, s, "elementwise");
-      const float* wb = wt.wb.as<float>();
-      K5CHK(k5_launch_x0_preview(a->latent, vel_c, cfg_on ? vel_u : nullptr, a->guidance_weight, host_tab[2 * a->num_steps + i],
-                                 edit ? edit->source : nullptr, edit ? edit->keep_mask : nullptr, wb, wb + 3 * c.in_visual_dim,
-                                 wt.want_x0 ? wt.x0[slot].as<float>() : nullptr, wt.rgb[slot].as<uint8_t>(), cells, c.in_visual_dim, s));
-      HIPCHK(hipMemcpyAsync(wt.h_rgb[slot], wt.rgb[slot].p, (size_t)cells * 3, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipEventRecord(wt.ev[slot], s));
-    wt.steps_done = i + 1;
-    return K5_OK;
-  };
-  auto deliver = [&](int i) -> int {
-    const int slot = i & 1;
-    HIPCHK(hipEventSynchronize(wt.ev[slot]));
-    const bool pv = preview_at(i);
-    k5_watch_info info{};
-    info.step = i; info.num_steps = a->num_steps; info.sample = wt.sample; info.num_samples = wt.num_samples;
-    info.sigma_next = host_tab[2 * a->num_steps + i];
-    info.rgb = pv ? wt.h_rgb[slot] : nullptr;
-    info.x0 = pv && wt.want_x0 ? wt.x0[slot].as<float>() : nullptr;
-    info.T = win ? win->total_T : a->fwd.T; info.H = a->fwd.H; info.W = a->fwd.W; info.C = c.in_visual_dim;
-    if (wt.fn(wt.user, &info) != 0) wt.stopped = 1;
-    return K5_OK;
-  };
-  auto watch_step = [&](int i) -> int {   // after step i is enqueued; the caller leaves its loop when wt.stopped
-    K5CHK(after_step(i));
-    if (i > 0) K5CHK(deliver(i - 1));
-    return K5_OK;
-  };
-  auto watch_end = [&]() -> int {   // the last step's callback; a stopped run ends with the stream drained
-    if (!wt.stopped) K5CHK(deliver(wt.steps_done - 1));
-    if (wt.stopped) HIPCHK(hipStreamSynchronize(s));
-    return K5_OK;
-  };
-  if (!graph) {
-    for (int i = 0; i < a->num_steps; ++i) {
-      K5CHK(one_step(i));
-      if (i == 0) K5CHK(decide_fuse());
-      if (watching) {
-        K5CHK(watch_step(i));
-        if (wt.stopped) break;
-      }
-    }
-    if (watching) K5CHK(watch_end());
-    else wt.steps_done = a->num_steps;
-    return K5_OK;
-  }
-  K5CHK(one_step(0));
-  K5CHK(decide_fuse());
-  if (watching) K5CHK(watch_step(0));   // ahead of the capture: these launches are not part of the graph
-  hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
-  HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  const long long nag_before = d->nag.combines;
-  const int rc = one_step(1);
-  const long long nag_per_step = d->nag.combines - nag_before;   // k5_dit_nag_state counts launches: the capture stands for step 1's, every further replay adds as many
-  const hipError_t ec = hipStreamEndCapture(s, &g);
-  if (rc != K5_OK || ec != hipSuccess || !g) {
-    if (g) (void)hipGraphDestroy(g);
-    if (rc == K5_OK) k5_set_error("hipStreamEndCapture: %s", hipGetErrorString(ec));
-    return rc != K5_OK ? rc : K5_ERR_HIP;
-  }
-  if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) { (void)hipGraphDestroy(g); k5_set_error("hipGraphInstantiate failed"); return K5_ERR_HIP; }
-  int status = K5_OK;
-  for (int i = 1; i < a->num_steps && status == K5_OK; ++i) {
-    if (hipGraphLaunch(ge, s) != hipSuccess) { k5_set_error("hipGraphLaunch failed"); status = K5_ERR_HIP; break; }
-    if (i > 1) d->nag.combines += nag_per_step;
-    if (watching) {   // between graph launches, sigma_next as a host scalar
-      status = watch_step(i);
+    if (i == 0) K5CHK(decide_fuse());
+    if (wt.on) {
+      K5CHK(wt.step(r, i));
       if (wt.stopped) break;
     }
   }
-  if (watching && status == K5_OK) status = watch_end();
-  if (!watching && status == K5_OK) wt.steps_done = a->num_steps;
-  (void)hipStreamSynchronize(s);   // the executable graph must outlive its launches (this also orders the caller's stream after us)
-  (void)hipGraphExecDestroy(ge); (void)hipGraphDestroy(g);
-  (void)caller;
-  return status;
+  return wt.end(r);
 }
 
 extern "C" int k5_sample_cond(k5_dit* d, const k5_sample_args* a, const float* vcond, void* stream) {
@@ -2546,8 +2595,7 @@ extern "C" int k5_sample_windows(k5_dit* d, const k5_sample_windows_args* w, con
 // groups exchange per forward, MagCache counts calls, a captured step is per call).
 static int many_state_ok(const k5_dit* d, const char* who) {
   if (!d->finalized) { k5_set_error("%s before k5_dit_finalize", who); return K5_ERR_STATE; }
-  if (d->comm.active()) { k5_set_error("%s: the handle is in a sequence-parallel group", who); return K5_ERR_STATE; }
-  if (d->pair.active()) { k5_set_error("%s: the handle is in a CFG pair", who); return K5_ERR_STATE; }
+  if (rank_group(d)) { k5_set_error("%s: the handle is in a %s", who, rank_group(d)); return K5_ERR_STATE; }
   if (d->mag.on) { k5_set_error("%s: MagCache is set on the handle", who); return K5_ERR_STATE; }
   if (d->cal.on) { k5_set_error("%s: the handle is calibrating MagCache", who); return K5_ERR_STATE; }
   if (d->use_graph) { k5_set_error("%s: graph capture is on (k5_dit_set_graph)", who); return K5_ERR_STATE; }
@@ -2603,9 +2651,8 @@ extern "C" int k5_dit_set_watch(k5_dit* d, const k5_watch* w) {
   if (w->preview_every < 0) { k5_set_error("k5_dit_set_watch: preview_every must be >= 0 (got %d)", w->preview_every); return K5_ERR_ARG; }
   if (w->preview_every > 0 && !w->rgb_w) { k5_set_error("k5_dit_set_watch: previews (preview_every = %d) need rgb_w", w->preview_every); return K5_ERR_ARG; }
   if (w->want_x0 && w->preview_every == 0) { k5_set_error("k5_dit_set_watch: want_x0 needs preview_every > 0 (x0 comes with the preview steps)"); return K5_ERR_ARG; }
-  if (d->comm.active() || d->pair.active()) {
-    k5_set_error("k5_dit_set_watch: the handle is in a %s: a rank that stops alone would leave its peers inside a collective",
-                 d->comm.active() ? "sequence-parallel group" : "CFG pair");
+  if (rank_group(d)) {
+    k5_set_error("k5_dit_set_watch: the handle is in a %s: a rank that stops alone would leave its peers inside a collective", rank_group(d));
     return K5_ERR_STATE;
   }
   if (w->preview_every > 0) {

@@ -6,6 +6,7 @@ sigma-schedule construction, but runs the Euler / CFG loop on the MI355X engine:
 DiT, otherwise step by
 step through `model(...)` (duck-typed models, e.g. a MagCache wrapper) with the fused CFG+Euler kernel.
 """
+import contextlib
 import math
 import os
 
@@ -197,26 +198,73 @@ class _StepWatch:
             self.bar.close()
             self.bar = None
 
+    @contextlib.contextmanager
     def installed(self, model):
         """Context: this hook as the watch of an engine-backed model for one sample / sample_many call; what was there before comes back."""
-        import contextlib
+        if not self.active:
+            yield
+            return
+        before = model._watch
+        try:
+            model.set_watch(self.step, self.every, self.W, self.b, self.want_x0)
+            yield
+        finally:
+            model._watch = before
+            if before is not None:
+                model._install_watch()
+            else:
+                model.clear_watch()
 
-        @contextlib.contextmanager
-        def ctx():
-            if not self.active:
-                yield
-                return
-            before = model._watch
-            try:
-                model.set_watch(self.step, self.every, self.W, self.b, self.want_x0)
-                yield
-            finally:
-                model._watch = before
-                if before is not None:
-                    model._install_watch()
-                else:
-                    model.clear_watch()
-        return ctx()
+
+@contextlib.contextmanager
+def _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha):
+    """`generate`'s NAG keywords as guidance for exactly one call: set on the model, and what was there before put back, also on an exception.
+    nag_scale None: nothing is touched."""
+    if nag_scale is None:
+        yield
+        return
+    from .models.dit import DiffusionTransformer3D, check_nag_args
+    check_nag_args(nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha)
+    if type(model) is not DiffusionTransformer3D:
+        raise ValueError("nag_scale needs the engine-backed DiffusionTransformer3D: normalized attention guidance runs inside its "
+                         "forward, a wrapped or duck-typed model has no hook for it")
+    before = model._nag
+    try:
+        model.set_nag(nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha)
+        yield
+    finally:
+        if before is not None:
+            model.set_nag({"text_embeds": before["text"], "pooled_embed": before["pooled"]}, before["pos"], *before["args"])
+        else:
+            model.clear_nag()
+
+
+def _conditioning(model, img, visual_cond, visual_cond_mask):
+    """`(vc, vm)` of img's shape and of img.shape[:-1] + (1,), fp32 on img's device, from `visual_cond` / `visual_cond_mask` (zeros for the one
+    that is missing); None when neither is given."""
+    if visual_cond is None and visual_cond_mask is None:
+        return None
+    if not getattr(model, "visual_cond", False):
+        raise ValueError("visual_cond / visual_cond_mask need a model built with visual_cond=True")
+    mask_shape = tuple(img.shape[:-1]) + (1,)
+    vc = torch.zeros_like(img) if visual_cond is None else visual_cond.to(device=img.device, dtype=torch.float32)
+    vm = (torch.zeros(mask_shape, dtype=torch.float32, device=img.device) if visual_cond_mask is None
+          else visual_cond_mask.to(device=img.device, dtype=torch.float32))
+    if tuple(vc.shape) != tuple(img.shape) or tuple(vm.shape) != mask_shape:
+        raise ValueError(f"visual_cond must be {tuple(img.shape)} and visual_cond_mask {mask_shape}, got {tuple(vc.shape)} and "
+                         f"{tuple(vm.shape)}")
+    return vc, vm
+
+
+def _model_input(model, img, cond_in, frames=slice(None)):
+    """What a per-step forward is given for `frames` of the latent: latent | conditioning | mask (zeros for the last two when none was
+    given) for a visual_cond model, the bare latent otherwise."""
+    x = img[frames]
+    if not getattr(model, "visual_cond", False):
+        return x
+    if cond_in is None:
+        return torch.cat([x, torch.zeros_like(x), torch.zeros([*x.shape[:-1], 1], dtype=x.dtype, device=x.device)], dim=-1)
+    return torch.cat([x, cond_in[0][frames], cond_in[1][frames]], dim=-1)
 
 
 @torch.no_grad()
@@ -224,7 +272,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
              null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=False, seed=6554, noise=None, *,
              visual_cond=None, visual_cond_mask=None, batch=1, init_latent=None, strength=1.0, keep_mask=None,
              callback=None, preview_every=0, preview_factors=None, preview_x0=False, context_frames=None, context_overlap=None,
-             context_text=None, nag_text_embeds=None, nag_text_rope_pos=None, nag_scale=None, nag_tau=2.5, nag_alpha=0.25, _watch=None):
+             context_text=None, nag_text_embeds=None, nag_text_rope_pos=None, nag_scale=None, nag_tau=2.5, nag_alpha=0.25):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -265,56 +313,38 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     if batch < 1 or shape[0] % batch:
         raise ValueError(f"shape[0] = {shape[0]} frames do not divide into batch={batch} samples")
     _check_edit_args(model, shape, init_latent, strength, keep_mask)
-    plan = _context_plan(model, shape[0] // batch, context_frames, context_overlap, context_text, init_latent, preview_every)
+    context = (context_frames, context_overlap, context_text)
+    plan = _context_plan(model, shape[0] // batch, *context, init_latent, preview_every)
     many = any(isinstance(v, (list, tuple)) for v in (text_embeds, null_text_embeds))
     if batch == 1 and many:
         text_embeds, null_text_embeds, text_rope_pos, null_text_rope_pos = (
             split_per_sample(v, 1, n)[0] for v, n in ((text_embeds, "text_embeds"), (null_text_embeds, "null_text_embeds"),
                                                  (text_rope_pos, "text_rope_pos"), (null_text_rope_pos, "null_text_rope_pos")))
-    if _watch is None and nag_scale is not None:   # guidance for exactly this call: set, run without the keywords, put back what was there
-        from .models.dit import DiffusionTransformer3D, check_nag_args
-        check_nag_args(nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha)
-        if type(model) is not DiffusionTransformer3D:
-            raise ValueError("nag_scale needs the engine-backed DiffusionTransformer3D: normalized attention guidance runs inside its "
-                             "forward, a wrapped or duck-typed model has no hook for it")
-        before = model._nag
-        try:
-            model.set_nag(nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha)
-            return generate(model, device, shape, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
-                            null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=progress, seed=seed, noise=noise,
-                            visual_cond=visual_cond, visual_cond_mask=visual_cond_mask, batch=batch, init_latent=init_latent,
-                            strength=strength, keep_mask=keep_mask, callback=callback, preview_every=preview_every,
-                            preview_factors=preview_factors, preview_x0=preview_x0, context_frames=context_frames,
-                            context_overlap=context_overlap, context_text=context_text)
-        finally:
-            if before is not None:
-                model.set_nag({"text_embeds": before["text"], "pooled_embed": before["pooled"]}, before["pos"], *before["args"])
-            else:
-                model.clear_nag()
-    if _watch is None:   # the outermost call owns the hook (and closes the bar); the per-sample calls of a batch share it
-        steps_run = num_steps - (edit_first_step(num_steps, strength) if init_latent is not None else 0)
+    steps_run = num_steps - (edit_first_step(num_steps, strength) if init_latent is not None else 0)
+    with _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha):
+        # one hook for the whole call (it owns the bar): the samples of a batch share it
         watch = _StepWatch(model, callback, preview_every, preview_factors, preview_x0, progress, batch * steps_run, shape[-1])
         try:
-            return generate(model, device, shape, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
-                            null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=progress, seed=seed, noise=noise,
-                            visual_cond=visual_cond, visual_cond_mask=visual_cond_mask, batch=batch, init_latent=init_latent,
-                            strength=strength, keep_mask=keep_mask, context_frames=context_frames, context_overlap=context_overlap,
-                            context_text=context_text, _watch=watch)
+            if noise is None:
+                g = torch.Generator(device="cuda")
+                g.manual_seed(seed)
+                img = torch.randn(*shape, device=device, generator=g)
+            else:
+                img = noise.to(device=device, dtype=torch.float32).clone()
+            run = (model, device, img.contiguous(), num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
+                   null_text_rope_pos, guidance_weight, scheduler_scale, conf, watch)
+            what = (context, visual_cond, visual_cond_mask, init_latent, strength, keep_mask)
+            return _generate_batch(*run, batch, *what) if batch > 1 else _generate_one(*run, plan, *what)
         finally:
             watch.close()
-    watch = _watch
-    if noise is None:
-        g = torch.Generator(device="cuda")
-        g.manual_seed(seed)
-        img = torch.randn(*shape, device=device, generator=g)
-    else:
-        img = noise.to(device=device, dtype=torch.float32).clone()
-    img = img.contiguous()
-    if batch > 1:
-        return _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
-                               null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond,
-                               visual_cond_mask, init_latent, strength, keep_mask, watch,
-                               context=None if context_frames is None else (context_frames, context_overlap, context_text))
+
+
+def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
+                  guidance_weight, scheduler_scale, conf, watch, plan, context, visual_cond, visual_cond_mask, init_latent, strength,
+                  keep_mask):
+    """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch` and the checked `plan` of
+    `_context_plan`; returns the latent."""
+    context_text = context[2]
     if plan is not None:
         F, starts, weights = plan
         if context_text is not None:   # the first window's prompt stands where the one prompt of a plain run does
@@ -329,47 +359,12 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         km = None if keep_mask is None else keep_mask.to(device=img.device, dtype=torch.float32).contiguous()
         edit = (src, img, km)
         img = torch.empty_like(img)
-
-    cond_in = None
-    if visual_cond is not None or visual_cond_mask is not None:
-        if not getattr(model, "visual_cond", False):
-            raise ValueError("visual_cond / visual_cond_mask need a model built with visual_cond=True")
-        mask_shape = tuple(img.shape[:-1]) + (1,)
-        vc = torch.zeros_like(img) if visual_cond is None else visual_cond.to(device=img.device, dtype=torch.float32)
-        vm = (torch.zeros(mask_shape, dtype=torch.float32, device=img.device) if visual_cond_mask is None
-              else visual_cond_mask.to(device=img.device, dtype=torch.float32))
-        if tuple(vc.shape) != tuple(img.shape) or tuple(vm.shape) != mask_shape:
-            raise ValueError(f"visual_cond must be {tuple(img.shape)} and visual_cond_mask {mask_shape}, got {tuple(vc.shape)} and "
-                             f"{tuple(vm.shape)}")
-        cond_in = (vc, vm)
+    cond_in = _conditioning(model, img, visual_cond, visual_cond_mask)
 
     sparse_params = get_sparse_params(conf, {"visual": img if plan is None else img[:plan[0]]}, device)
     timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()  # one sync, before the loop
     if edit is not None:
         timesteps = timesteps[edit_first_step(num_steps, strength):]   # strength is a truncation of the schedule, nothing more
-
-    def update(v, u, timestep_diff, sigma_next):
-        """CFG combine + Euler (+ the keep rule when editing) on img, in place"""
-        if edit is None:
-            E.cfg_euler_(img, v, u, guidance_weight, timestep_diff)
-        else:
-            E.cfg_euler_edit_(img, v, u, guidance_weight, timestep_diff, edit[0], edit[1], edit[2], sigma_next)
-
-    def after_step(i, v, u, sigma_next):
-        """the per-step paths' side of the watch: the preview of the step just applied (the engine's kernel, the engine's rule for which
-        steps carry one) and the callback"""
-        if not watch.active:
-            return
-        from .models.dit import SamplingInterrupted, StepInfo
-        n = len(timesteps) - 1
-        preview = x0 = None
-        if watch.preview_at(i, n):
-            km = None if edit is None else edit[2]
-            rgb, x0 = E.x0_preview(img, v, u, guidance_weight, sigma_next, watch.W, watch.b, source=None if km is None else edit[0],
-                                   keep_mask=km, want_x0=watch.want_x0)
-            preview = rgb.cpu()
-        if watch.step(StepInfo(i, n, watch.sample, watch.num_samples, sigma_next, preview, x0)):
-            raise SamplingInterrupted(i + 1, img, watch.sample)
 
     from .models.dit import DiffusionTransformer3D
     if isinstance(model, torch.nn.Module):      # per-step paths below: a new sampling run starts with no softmax-form memory (k5_sample resets its own)
@@ -378,29 +373,12 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
                 m.reset_softmax_memory()
     cfg_on = abs(guidance_weight - 1.0) > 1e-6
     cfg_parallel = getattr(model, "_cfg_parallel", None)
-    if cfg_parallel is not None and cfg_on and getattr(model, "_cfg_pair", None) is None:
-        # CFG-parallel for a model WITHOUT the engine-side pair (a wrapped / duck-typed model): this rank's group
-        # runs ONE of the two forwards; the pair exchanges the velocities (6 MB at 5 s) over torch.distributed and every rank applies
-        # the identical bf16 combine + Euler update.  A DiffusionTransformer3D set up by parallelize_dit does the same INSIDE
-        # k5_sample (k5_dit_cfg_pair_init) and takes the fused path below.
-        from .models.parallelize import exchange_velocity
-        branch, pair_group = cfg_parallel
-        mine, mine_pos = (text_embeds, text_rope_pos) if branch == 0 else (null_text_embeds, null_text_rope_pos)
-        both = None
-        if edit is not None:
-            E.renoise(edit[0], edit[1], float(timesteps[0]), out=img)
-        for i, (timestep, timestep_diff, sigma_next) in enumerate(zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(),
-                                                                      timesteps[1:].tolist())):
-            x = img if cond_in is None else torch.cat([img, *cond_in], dim=-1)
-            v = model(x, mine["text_embeds"], mine["pooled_embed"], torch.tensor([timestep]) * 1000, visual_rope_pos,
-                      mine_pos, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
-            if both is None:
-                both = torch.empty((2,) + tuple(v.shape), dtype=v.dtype, device=v.device)
-            vc, vu = exchange_velocity(v, pair_group, out=both)
-            update(vc, vu, timestep_diff, sigma_next)
-            after_step(i, vc, vu, sigma_next)
-        return img
-    if type(model) is DiffusionTransformer3D and model.visual_cond in (True, False):
+    # CFG-parallel for a model WITHOUT the engine-side pair (a wrapped / duck-typed model): this rank's group
+    # runs ONE of the two forwards; the pair exchanges the velocities (6 MB at 5 s) over torch.distributed and every rank applies
+    # the identical bf16 combine + Euler update.  A DiffusionTransformer3D set up by parallelize_dit does the same INSIDE
+    # k5_sample (k5_dit_cfg_pair_init) and takes the fused path below.
+    exchange = cfg_parallel is not None and cfg_on and getattr(model, "_cfg_pair", None) is None
+    if not exchange and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False):
         # whole loop inside the engine: no per-step host work at all
         with watch.installed(model):
             model.sample(img, timesteps.tolist(), text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
@@ -410,64 +388,77 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
                          windows=None if plan is None else (plan[1], plan[2]), window_text=None if plan is None else context_text)
         return img
 
-    if plan is not None:
-        # context windows, step by step: the forwards of k5_sample_windows in its order (window by window, cond then uncond, each on its
-        # own slice of the latent), then the one blend + Euler pass over the clip
-        F, starts, weights = plan
-        nwin = len(starts)
-        st_dev, wt_dev = E.window_tables(starts, weights, img.device)
-        vbuf = torch.empty((nwin, F) + tuple(img.shape[1:]), dtype=torch.bfloat16, device=img.device)
-        ubuf = torch.empty_like(vbuf) if cfg_on else None
-        for i, (timestep, timestep_diff, sigma_next) in enumerate(zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(),
-                                                                      timesteps[1:].tolist())):
-            t1000 = torch.tensor([timestep]) * 1000
-            for k, st in enumerate(starts):
-                x = img[st:st + F]
-                if model.visual_cond:
-                    if cond_in is None:
-                        x = torch.cat([x, torch.zeros_like(x), torch.zeros([*x.shape[:-1], 1], dtype=x.dtype, device=x.device)], dim=-1)
-                    else:
-                        x = torch.cat([x, cond_in[0][st:st + F], cond_in[1][st:st + F]], dim=-1)
-                te, tp = (text_embeds, text_rope_pos) if context_text is None else context_text[k]
-                vbuf[k] = model(x, te["text_embeds"], te["pooled_embed"], t1000, visual_rope_pos, tp,
-                                scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
-                if cfg_on:
-                    ubuf[k] = model(x, null_text_embeds["text_embeds"], null_text_embeds["pooled_embed"], t1000, visual_rope_pos,
-                                    null_text_rope_pos, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
-            E.cfg_euler_windows_(img, vbuf, ubuf, guidance_weight, timestep_diff, st_dev, wt_dev)
-            after_step(i, None, None, sigma_next)
-        return img
+    # The per-step loop.  Each step takes (v_cond, v_uncond) from one of three sources, applies the matching update and calls the hook.
+    def forward(x, te, tp, t1000):
+        return model(x, te["text_embeds"], te["pooled_embed"], t1000, visual_rope_pos, tp, scale_factor=conf.metrics.scale_factor,
+                     sparse_params=sparse_params)
 
+    def plain_velocities(t1000):   # cond, then uncond
+        x = _model_input(model, img, cond_in)
+        v = forward(x, text_embeds, text_rope_pos, t1000)
+        u = forward(x, null_text_embeds, null_text_rope_pos, t1000) if cfg_on else None
+        return v.contiguous(), None if u is None else u.contiguous()
+
+    def pair_velocities(t1000):   # my branch, then the pair's exchange into the reused buffer
+        nonlocal both
+        v = forward(_model_input(model, img, cond_in), *mine, t1000)
+        if both is None:
+            both = torch.empty((2,) + tuple(v.shape), dtype=v.dtype, device=v.device)
+        return exchange_velocity(v, cfg_parallel[1], out=both)
+
+    def window_velocities(t1000):
+        # the forwards of k5_sample_windows in its order: window by window, cond then uncond, each on its own slice of the latent
+        for k, st in enumerate(starts):
+            x = _model_input(model, img, cond_in, slice(st, st + F))
+            vbuf[k] = forward(x, *((text_embeds, text_rope_pos) if context_text is None else context_text[k]), t1000)
+            if cfg_on:
+                ubuf[k] = forward(x, null_text_embeds, null_text_rope_pos, t1000)
+        return vbuf, ubuf
+
+    if exchange:
+        from .models.parallelize import exchange_velocity
+        mine = (text_embeds, text_rope_pos) if cfg_parallel[0] == 0 else (null_text_embeds, null_text_rope_pos)
+        both = None
+        velocities = pair_velocities
+    elif plan is not None:
+        st_dev, wt_dev = E.window_tables(starts, weights, img.device)
+        vbuf = torch.empty((len(starts), F) + tuple(img.shape[1:]), dtype=torch.bfloat16, device=img.device)
+        ubuf = torch.empty_like(vbuf) if cfg_on else None
+        velocities = window_velocities
+    else:
+        velocities = plain_velocities
+
+    from .models.dit import SamplingInterrupted, StepInfo
+    n = len(timesteps) - 1
     if edit is not None:
         E.renoise(edit[0], edit[1], float(timesteps[0]), out=img)
     for i, (timestep, timestep_diff, sigma_next) in enumerate(zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(),
                                                                   timesteps[1:].tolist())):
-        if model.visual_cond:
-            if cond_in is None:
-                vc = torch.zeros_like(img)
-                vm = torch.zeros([*img.shape[:-1], 1], dtype=img.dtype, device=img.device)
-            else:
-                vc, vm = cond_in
-            model_input = torch.cat([img, vc, vm], dim=-1)
-        else:
-            model_input = img
-        t1000 = torch.tensor([timestep]) * 1000
-        v = model(model_input, text_embeds["text_embeds"], text_embeds["pooled_embed"], t1000, visual_rope_pos,
-                  text_rope_pos, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
-        u = None
-        if cfg_on:
-            u = model(model_input, null_text_embeds["text_embeds"], null_text_embeds["pooled_embed"], t1000,
-                      visual_rope_pos, null_text_rope_pos, scale_factor=conf.metrics.scale_factor,
-                      sparse_params=sparse_params)
-        v, u = v.contiguous(), None if u is None else u.contiguous()
-        update(v, u, timestep_diff, sigma_next)
-        after_step(i, v, u, sigma_next)
+        v, u = velocities(torch.tensor([timestep]) * 1000)
+        if plan is not None:       # the one blend + Euler pass over the clip
+            E.cfg_euler_windows_(img, v, u, guidance_weight, timestep_diff, st_dev, wt_dev)
+        elif edit is None:         # CFG combine + Euler on img, in place
+            E.cfg_euler_(img, v, u, guidance_weight, timestep_diff)
+        else:                      # ... and the keep rule
+            E.cfg_euler_edit_(img, v, u, guidance_weight, timestep_diff, edit[0], edit[1], edit[2], sigma_next)
+        if not watch.active:
+            continue
+        # the per-step paths' side of the watch: the preview of the step just applied (the engine's kernel, the engine's rule for which steps
+        # carry one; never on a windowed run, whose preview_every is refused) and the callback
+        preview = x0 = None
+        if watch.preview_at(i, n):
+            km = None if edit is None else edit[2]
+            rgb, x0 = E.x0_preview(img, v, u, guidance_weight, sigma_next, watch.W, watch.b, source=None if km is None else edit[0],
+                                   keep_mask=km, want_x0=watch.want_x0)
+            preview = rgb.cpu()
+        if watch.step(StepInfo(i, n, watch.sample, watch.num_samples, sigma_next, preview, x0)):
+            raise SamplingInterrupted(i + 1, img, watch.sample)
     return img
 
 
-def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
-                    null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress, seed, visual_cond, visual_cond_mask,
-                    init_latent=None, strength=1.0, keep_mask=None, watch=None, context=None):
+def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
+                    guidance_weight, scheduler_scale, conf, watch, batch, context, visual_cond, visual_cond_mask, init_latent, strength,
+                    keep_mask):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
     from .models.dit import split_per_sample
     T = img.shape[0] // batch
@@ -478,39 +469,29 @@ def _generate_batch(model, device, img, batch, num_steps, text_embeds, null_text
         if v is not None and v.shape[0] != img.shape[0]:
             raise ValueError(f"{n} must have {img.shape[0]} frames (batch={batch} x {T}), got {v.shape[0]}")
 
-    def part(v, b):
-        return None if v is None else v[b * T:(b + 1) * T]
-
     from .models.dit import DiffusionTransformer3D
-    ctx_kw = {} if context is None else dict(context_frames=context[0], context_overlap=context[1], context_text=context[2])
-    if init_latent is None and context is None and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) \
+    if init_latent is None and context[0] is None and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) \
             and model.many_ready() and getattr(model, "_cfg_parallel", None) is None:
-        cond = None
-        if visual_cond is not None or visual_cond_mask is not None:
-            if not model.visual_cond:
-                raise ValueError("visual_cond / visual_cond_mask need a model built with visual_cond=True")
-            vc = torch.zeros_like(img) if visual_cond is None else visual_cond.to(device=img.device, dtype=torch.float32)
-            vm = (torch.zeros(tuple(img.shape[:-1]) + (1,), dtype=torch.float32, device=img.device) if visual_cond_mask is None
-                  else visual_cond_mask.to(device=img.device, dtype=torch.float32))
-            if tuple(vc.shape) != tuple(img.shape) or tuple(vm.shape) != tuple(img.shape[:-1]) + (1,):
-                raise ValueError(f"visual_cond must be {tuple(img.shape)} and visual_cond_mask {tuple(img.shape[:-1]) + (1,)}, got "
-                                 f"{tuple(vc.shape)} and {tuple(vm.shape)}")
-            cond = torch.cat([vc, vm], dim=-1).reshape(batch, T, *img.shape[1:-1], img.shape[-1] + 1).contiguous()
+        cond = _conditioning(model, img, visual_cond, visual_cond_mask)
+        if cond is not None:
+            cond = torch.cat(cond, dim=-1).reshape(batch, T, *img.shape[1:-1], img.shape[-1] + 1).contiguous()
         sparse_params = get_sparse_params(conf, {"visual": img[:T]}, device)
         timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()
         with watch.installed(model):
             model.sample_many(img.view(batch, T, *img.shape[1:]), timesteps.tolist(), tes, nes, visual_rope_pos, tps, nps,
                                guidance_weight, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params, visual_cond=cond)
         return img
-    # any other model (rank groups, MagCache, graph replay, wrapped or duck-typed models), editing and context windows: one sample at a time
+    # any other model (rank groups, MagCache, graph replay, wrapped or duck-typed models), editing and context windows: one sample at a time,
+    # each checked and planned as the call of its own that it equals
     watch.num_samples = batch
     for b in range(batch):
+        rows = slice(b * T, (b + 1) * T)
+        vc, vm, src, km = (None if v is None else v[rows] for v in (visual_cond, visual_cond_mask, init_latent, keep_mask))
+        _check_edit_args(model, img[rows].shape, src, strength, km)
+        plan = _context_plan(model, T, *context, src, watch.every)
         watch.sample = b
-        img[b * T:(b + 1) * T] = generate(model, device, (T,) + tuple(img.shape[1:]), num_steps, tes[b], nes[b], visual_rope_pos,
-                                          tps[b], nps[b], guidance_weight, scheduler_scale, conf, progress=progress, seed=seed,
-                                          noise=img[b * T:(b + 1) * T], visual_cond=part(visual_cond, b),
-                                          visual_cond_mask=part(visual_cond_mask, b), init_latent=part(init_latent, b),
-                                          strength=strength, keep_mask=part(keep_mask, b), _watch=watch, **ctx_kw)
+        img[rows] = _generate_one(model, device, img[rows].clone(), num_steps, tes[b], nes[b], visual_rope_pos, tps[b], nps[b], guidance_weight,
+                                  scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km)
     return img
 
 

@@ -409,42 +409,53 @@ class DiffusionTransformer3D(nn.Module):
                 raise ValueError("edit together with windows is not supported")
             return self._sample_windows(latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                                         guidance_weight, scale_factor, sparse_params, visual_cond, windows, window_text)
+        s = E.SampleArgs()
+        keep, edit = self._fill_sample_args(s, latent, None, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
+                                            null_text_rope_pos, guidance_weight, scale_factor, sparse_params, visual_cond, edit)
+        if edit is not None:
+            ea = E.EditArgs(edit[0].data_ptr(), edit[1].data_ptr(), E.ptr(edit[2]))
+            return self._run_sampler("k5_sample_edit", latent, C.byref(s), E.ptr(visual_cond), C.byref(ea))
+        if visual_cond is None:
+            return self._run_sampler("k5_sample", latent, C.byref(s))
+        return self._run_sampler("k5_sample_cond", latent, C.byref(s), visual_cond.data_ptr())
+
+    def _fill_sample_args(self, s, latent, frames, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
+                          guidance_weight, scale_factor, sparse_params, visual_cond, edit=None):
+        """Check what a k5_sample* call borrows and fill its SampleArgs `s`, for a forward that sees `frames` frames: the latent's T in a plain
+        run (`frames` None), F in a window.  Returns (what must stay alive as long as `s` is used, the checked `edit` triple or None)."""
         if not latent.is_cuda or latent.dtype != torch.float32 or not latent.is_contiguous():
             raise RuntimeError("latent must be a contiguous fp32 CUDA tensor")
         T, H, W, _ = latent.shape
-        self._last_tokens = T * (H // self.patch_size[1]) * (W // self.patch_size[2])   # rows of a residual (magcache_calibration)
+        frames = T if frames is None else frames
+        self._last_tokens = frames * (H // self.patch_size[1]) * (W // self.patch_size[2])   # rows of a residual (magcache_calibration)
         self._check_visual_cond(visual_cond, latent)
         edit = self._check_edit(edit, latent)
-        h = self.engine(latent.device)
         dev = latent.device
+        self.engine(dev)
         keep = []
-        te, pe = text_embeds["text_embeds"].to(dev), text_embeds["pooled_embed"].to(dev)
-        s = E.SampleArgs()
-        s.fwd = self._forward_args((T, H, W), None, self.in_visual_dim, te, pe, 0.0, visual_rope_pos, text_rope_pos,
-                                   scale_factor, sparse_params, keep)
+        s.fwd = self._forward_args((frames, H, W), None, self.in_visual_dim, text_embeds["text_embeds"].to(dev), text_embeds["pooled_embed"].to(dev),
+                                   0.0, visual_rope_pos, text_rope_pos, scale_factor, sparse_params, keep)
         if abs(guidance_weight - 1.0) > 1e-6:
             s.null_cond = self._text_cond(null_text_embeds["text_embeds"].to(dev), null_text_embeds["pooled_embed"].to(dev),
                                           null_text_rope_pos, keep)
         sig = [float(v) for v in sigmas]
         arr = (C.c_float * len(sig))(*sig)
+        keep.append(arr)
         s.latent, s.num_steps, s.sigmas, s.guidance_weight = latent.data_ptr(), len(sig) - 1, arr, float(guidance_weight)
+        return keep, edit
+
+    def _run_sampler(self, name, latent, *args):
+        """The k5_sample* call `name` on the latent's device and stream, between the watch's begin and end."""
+        dev = latent.device
         self._watch_begin()
         with torch.cuda.device(dev):
-            if edit is not None:
-                ea = E.EditArgs(edit[0].data_ptr(), edit[1].data_ptr(), E.ptr(edit[2]))
-                E.check(E.lib().k5_sample_edit(h, C.byref(s), E.ptr(visual_cond), C.byref(ea), E.stream_ptr(dev)), "k5_sample_edit")
-            elif visual_cond is None:
-                E.check(E.lib().k5_sample(h, C.byref(s), E.stream_ptr(dev)), "k5_sample")
-            else:
-                E.check(E.lib().k5_sample_cond(h, C.byref(s), visual_cond.data_ptr(), E.stream_ptr(dev)), "k5_sample_cond")
+            E.check(getattr(E.lib(), name)(self._handle, *args, E.stream_ptr(dev)), name)
         self._watch_end(latent)
         return latent
 
     def _sample_windows(self, latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                         guidance_weight, scale_factor, sparse_params, visual_cond, windows, window_text):
         """`sample(windows=...)`: the k5_sample_windows call."""
-        if not latent.is_cuda or latent.dtype != torch.float32 or not latent.is_contiguous():
-            raise RuntimeError("latent must be a contiguous fp32 CUDA tensor")
         starts, weights = windows
         starts = [int(v) for v in starts]
         weights = [[float(v) for v in row] for row in weights]
@@ -452,39 +463,23 @@ class DiffusionTransformer3D(nn.Module):
         if nwin < 1 or len(weights) != nwin or len({len(r) for r in weights}) != 1:
             raise ValueError("windows must be (starts [nwin], weights [nwin][F])")
         F = len(weights[0])
-        T, H, W, _ = latent.shape
         if window_text is not None and len(window_text) != nwin:
             raise ValueError(f"window_text holds {len(window_text)} prompts, the plan has nwin = {nwin} windows")
-        self._last_tokens = F * (H // self.patch_size[1]) * (W // self.patch_size[2])
-        self._check_visual_cond(visual_cond, latent)
-        h = self.engine(latent.device)
-        dev = latent.device
-        keep = []
         if window_text is not None:
             text_embeds, text_rope_pos = window_text[0]
         a = E.SampleWindowsArgs()
-        s = a.sample
-        s.fwd = self._forward_args((F, H, W), None, self.in_visual_dim, text_embeds["text_embeds"].to(dev), text_embeds["pooled_embed"].to(dev),
-                                   0.0, visual_rope_pos, text_rope_pos, scale_factor, sparse_params, keep)
-        if abs(guidance_weight - 1.0) > 1e-6:
-            s.null_cond = self._text_cond(null_text_embeds["text_embeds"].to(dev), null_text_embeds["pooled_embed"].to(dev),
-                                          null_text_rope_pos, keep)
+        keep, _ = self._fill_sample_args(a.sample, latent, F, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
+                                         null_text_rope_pos, guidance_weight, scale_factor, sparse_params, visual_cond)
         if window_text is not None:
+            dev = latent.device
             conds = (E.TextCond * nwin)()
             for i, (te, tp) in enumerate(window_text):
                 conds[i] = self._text_cond(te["text_embeds"].to(dev), te["pooled_embed"].to(dev), tp, keep)
             a.conds = conds
-        sig = [float(v) for v in sigmas]
-        arr = (C.c_float * len(sig))(*sig)
-        s.latent, s.num_steps, s.sigmas, s.guidance_weight = latent.data_ptr(), len(sig) - 1, arr, float(guidance_weight)
         st = E.i32_array(starts)
         wt = (C.c_float * (nwin * F))(*[v for row in weights for v in row])
-        a.total_T, a.nwin, a.starts, a.weights = T, nwin, st, wt
-        self._watch_begin()
-        with torch.cuda.device(dev):
-            E.check(E.lib().k5_sample_windows(h, C.byref(a), E.ptr(visual_cond), E.stream_ptr(dev)), "k5_sample_windows")
-        self._watch_end(latent)
-        return latent
+        a.total_T, a.nwin, a.starts, a.weights = latent.shape[0], nwin, st, wt
+        return self._run_sampler("k5_sample_windows", latent, C.byref(a), E.ptr(visual_cond))
 
     # ---------------------------------------------------------------- watch: progress, cancel, previews
     def set_watch(self, callback=None, preview_every=0, rgb_factors=None, rgb_bias=None, want_x0=False):
