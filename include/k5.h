@@ -320,6 +320,31 @@ int k5_x0_preview(const float* x, const void* v_cond, const void* v_uncond, floa
  * D > 2048 (the row is held in registers).  Nothing is launched when the call is refused. */
 int k5_nag_combine_bf16(const void* z_pos, const void* z_neg, void* out, int rows, int D, int ld, float s, float tau, float alpha,
                         void* stream);
+/* Regional prompts, the rule (added under ABI 11).  The base prompt is the forward's ordinary prompt; there are R region prompts,
+ * 1 <= R <= 8, each with a mask m_r in [0, 1] on the latent cells (T, H, W), the grid of the keep mask.
+ *   Token weights.  A token is a patch_size block of cells; m_r(token) is the fp32 mean of its cells.  raw_0 = base_weight + max(0, 1 - sum_r m_r)
+ *   with base_weight in [0, 1]; raw_r = m_r; s = sum raw; w_i = raw_i / s.  s >= 1 always (sum m < 1: s = base_weight + 1, otherwise
+ *   s = base_weight + sum m).  An uncovered token has the base prompt only; masks that partition the frame with base_weight 0 give each token
+ *   exactly one prompt.
+ *   Blend.  In every visual block, on the conditional forward only, the queries are projected and normalised once and attend to the base
+ *   stream (z_0) and to each region stream (z_r); the out projection sees out = sum_i w_i z_i per token.
+ * k5_region_combine_bf16 is the blend: z0 bf16 [rows][ld] of which D columns are used, region r at zr + r * zr_stride ELEMENTS (same layout), w
+ * fp32 [rows][ldw] with ldw >= R + 1 (column 0 the base stream's weight), out like z0 and out == z0 is allowed.  Per element in fp32: the first
+ * stream with a non-zero weight gives acc = w z (one rounded product), every later non-zero one acc = fmaf(w, z, acc), ascending from the base
+ * stream; out = bf16(acc), nearest-even, once.  A stream whose weight is exactly 0 for a row is not read and not added (NaN there does not reach
+ * out); a row whose only non-zero weight is 1.0 is that stream's bits, negative zeros included; a row without a non-zero weight is +0.  One wave
+ * per row, 16 bytes per lane, each used input read once, out written once; equal inputs give equal bits.
+ * K5_ERR_ARG: a NULL pointer, rows or D < 1, ld < D, D % 8, ld % 8, zr_stride % 8, a pointer not 16-byte aligned (w: 4-byte), R outside 1..8,
+ * ldw < R + 1; K5_ERR_UNSUPPORTED: D > 2048 (the row is held in registers).  Nothing is launched when the call is refused.
+ * k5_region_weights_f32 is the token weights: masks device fp32 [R][T][H][W], patch (pt, ph, pw) dividing (T, H, W), perm the order of the N =
+ * (T / pt)(H / ph)(W / pw) tokens (row i of w is token perm[i] of the row-major grid; NULL: i), w fp32 [N][R + 1].  Every cell is clamped to
+ * [0, 1] (NaN counts as 0); a token's cells are added in ascending (t, h, w) order and divided by their count; sm = m_1 + .. + m_R ascending;
+ * raw_0 = base_weight + max(0, 1 - sm); s = raw_0 + m_1 + .. + m_R ascending; each operation rounded on its own, no atomics.  K5_ERR_ARG: a NULL
+ * or not 4-byte aligned masks / w, R outside 1..8, a shape < 1 or not divisible by the patch, base_weight outside [0, 1] or NaN. */
+int k5_region_combine_bf16(const void* z0, const void* zr, long long zr_stride, int R, const float* w, int ldw, void* out, int rows, int D,
+                           int ld, void* stream);
+int k5_region_weights_f32(const float* masks, int R, int T, int H, int W, int pt, int ph, int pw, float base_weight, const int32_t* perm,
+                          float* w, void* stream);
 /* LoRA merge, in place on a row-major matrix (added under ABI 11, as the MagCache calibration exports were): W'[n][k] = W[n][k] + scale *
  * sum_r B[n][r] A[r][k].  W [rows][ld] (cols <= ld) of w_dtype K5_BF16 or K5_F32;
  * A [R][cols], B [rows][R], each K5_F32 / K5_BF16 / K5_F16, device pointers, converted to fp32 on load; 1 <= R <= 256.  The arithmetic is
@@ -512,6 +537,29 @@ int k5_dit_watch_state(k5_dit* dit, int* steps_done, int* stopped);
  * has enqueued (num_visual_blocks per guided forward), optionally resetting the count. */
 int k5_dit_set_nag(k5_dit* dit, const k5_text_cond* negative /* NULL clears */, float scale, float tau, float alpha);
 int k5_dit_nag_state(k5_dit* dit, int* on, long long* combines, int reset);
+
+/* Regional prompts on the handle (added under ABI 11; the rule is written at k5_region_combine_bf16): a prompt per masked region inside the
+ * cross-attention of ONE forward.  While set, every CONDITIONAL forward (as for k5_dit_set_nag: never the unconditional one) carries R more
+ * text streams: each region's tokens go through the text prologue and the text blocks as the NAG negative stream does, with their own RoPE
+ * positions and the forward's own time embedding (built from the BASE prompt's pooled embedding: regions[r].pooled_embed is not read); every
+ * visual block projects and normalises its queries once, attends once to the base stream and once to each region stream, and
+ * k5_region_combine_bf16 joins the R + 1 outputs by the token weights in front of the out projection.  With k5_dit_set_nag also set the
+ * regional blend is the positive side: it is done in place, then k5_nag_combine_bf16 runs against the negative output.  Per block that is R
+ * cross-attention launches and one memory-bound pass more; the text side runs R + 1 times.  The token weights are computed by
+ * k5_region_weights_f32 at most once per k5_dit_set_regions call and token order (row-major; NABLA's fractal order) and kept.  Not set, a
+ * forward enqueues exactly what it always did.  `regions` (HOST [R]), what its entries point to, and `masks` (device fp32 [R][T][H][W], the
+ * latent cells) are BORROWED until cleared; k5_sample* caches each region's prologue per call.  One region set serves every sample of
+ * k5_sample_many.  Works on sequence-parallel shards in every sp_mode (the text is replicated, the rule is per token, a rank reads its own
+ * rows of the weights: no collective is added), on the conditional handle of a CFG pair, in the captured step, under k5_sample_edit and with
+ * MagCache (a skipped step runs no visual block and so no blend).
+ * K5_ERR_ARG: R > 8 or < 0, base_weight outside [0, 1] or NaN, a region with text_len < 1 or a NULL text_embed / text_rope_pos, a NULL or not
+ * 4-byte aligned masks, T, H or W < 1 or not divisible by the patch; later, a forward or k5_sample* whose (T, H, W) is not the masks' (the message
+ * names both shapes).  K5_ERR_STATE: k5_sample_windows while regions are set (the masks cover the clip, a window sees a slice: not built).  All
+ * before anything is enqueued.  R == 0 or regions == NULL clears.  k5_dit_regions_state: whether regions are on, how many, and how many combines
+ * the handle has enqueued (num_visual_blocks per regional forward), optionally resetting the count. */
+int k5_dit_set_regions(k5_dit* dit, const k5_text_cond* regions /* HOST [R]; NULL clears */, int R, const float* masks, int T, int H, int W,
+                       float base_weight);
+int k5_dit_regions_state(k5_dit* dit, int* on, int* R, long long* combines, int reset);
 
 /* S forwards of the same (T, H, W) in one call, one after another (a convenience entry point like k5_sample_many): args->x is device fp32
  * [S][T][H][W][args->x_channels], conds HOST [S], args->time shared; out_velocity bf16 [S][T][H][W][out_visual_dim].  Sequence i is

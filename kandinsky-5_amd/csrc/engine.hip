@@ -449,7 +449,8 @@ struct k5_dit {
   // prompt only, so k5_sample computes them once per call and branch (slot 0 = cond, 1 = uncond) and every later step copies
   // 0.9 MB instead of re-running two GEMMs + two LayerNorms.  k5_dit_forward (one call per step, caller-owned buffers that
   // may change between calls) does not cache.
-  struct TextCache { DevBuf text, pool; bool valid = false; int L = 0; } text_cache[3];   // [2]: the negative prompt of k5_dit_set_nag (text only)
+  struct TextCache { DevBuf text, pool; bool valid = false; int L = 0; } text_cache[3 + 8];   // [2]: the negative prompt of k5_dit_set_nag (text only); [3 + r]: region r of k5_dit_set_regions (likewise)
+  void drop_text_cache() { for (auto& t : text_cache) t.valid = false; }
 
   // Normalized attention guidance (k5_dit_set_nag): a second, negative text stream through the text blocks (the forward's own
   // time embedding) and, per visual block, a second cross-attention of the same queries joined to the first by k5_launch_nag_combine.
@@ -461,6 +462,22 @@ struct k5_dit {
     long long combines = 0;                        // k5_launch_nag_combine launches enqueued so far (k5_dit_nag_state)
     DevBuf text, ck_all, cvt_all, ck, cvt, o;      // the negative stream | its stacked keys / V^T | the per-block ones | its attention output [n][D]
   } nag;
+
+  // Regional prompts (k5_dit_set_regions): R more text streams through the text blocks (the forward's own time embedding) and, per
+  // visual block, R more cross-attentions of the same queries; k5_launch_region_combine joins the R + 1 outputs by per-token weights in front
+  // of the out projection (and of the NAG combine, if that is set too).  Conditional forwards only.  Buffers exist once such a forward has run.
+  struct Regions {
+    bool on = false;
+    int R = 0;
+    const k5_text_cond* conds = nullptr;           // HOST [R], borrowed: valid until cleared, read at every forward
+    const float* masks = nullptr;                  // device fp32 [R][T][H][W], borrowed
+    int T = 0, H = 0, W = 0;
+    float base_weight = 0.f;
+    long long combines = 0;                        // k5_launch_region_combine launches enqueued so far (k5_dit_regions_state)
+    DevBuf text[8], ck_all[8], cvt_all[8], ck[8], cvt[8];   // per region, as Nag's
+    DevBuf o;                                      // the regions' attention outputs, [R][n][D]
+    DevBuf w; int w_order = -1;                    // token weights [N][R + 1] of this region set; -1: not computed, 0: row-major tokens, 1: NABLA's perm order
+  } regions;
 
   // MagCache (reference kandinsky/magcache_utils.py:16-101): skip the visual blocks on some calls and re-apply the
   // cached bf16 residual of the same cond / uncond slot.  Decisions depend on the ratio table and the call counter only.
@@ -1318,14 +1335,18 @@ int cross_kv_batched_run(k5_dit* d, hipStream_t s, const void* text, int L, DevB
 
 // the negative side of a guided cross-attention (k5_dit_set_nag): its text stream, where its keys / V^T are or go, and its output rows
 struct NagCross { const void* text; int L; void* ck; void* cvt; int ldck; void* o; };
+// the region streams of a cross-attention (k5_dit_set_regions): one NagCross each (o = o0 + r * o_stride elements) and this rank's token weights
+struct RegionCross { int R; NagCross r[8]; const void* o0; long long o_stride; const float* w; };
 
 
 // kv_ready: ck (row stride ldck) / cvt already hold this block's normalised keys and V^T (cross_kv_batched_run)
 // nag: attend the same queries to the negative stream as well and join the two outputs (k5_launch_nag_combine, in place on o) in front of
 // the out projection; with kv_ready its keys / V^T are ready too
+// reg: attend the same queries to every region stream as well; k5_launch_region_combine (in place on o) makes o the positive side before the
+// NAG combine, if any
 int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, int rows, const void* text,
                         int L, void* q, void* ck, void* cvt, void* o, void* resid, const float* gate, bool kv_ready = false, int ldck = 0,
-                        const NagCross* nag = nullptr) {
+                        const NagCross* nag = nullptr, const RegionCross* reg = nullptr) {
   const int D = d->D, H = d->Hh;
   const int ldvt = (int)rup(L, 8);
   if (!kv_ready) ldck = D;
@@ -1340,6 +1361,11 @@ int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h,
         K5CHK(k5_launch_gemm_bf16(nag->text, a.wk.p, a.bk.as<float>(), nag->ck, nag->L, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
         K5CHK(k5_launch_gemm_bf16(a.wv.p, nag->text, a.bv.as<float>(), nag->cvt, D, nag->L, D, D, D, nldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
       }
+      for (int r = 0; reg && r < reg->R; ++r) {
+        const NagCross& x = reg->r[r];
+        K5CHK(k5_launch_gemm_bf16(x.text, a.wk.p, a.bk.as<float>(), x.ck, x.L, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+        K5CHK(k5_launch_gemm_bf16(a.wv.p, x.text, a.bv.as<float>(), x.cvt, D, x.L, D, D, D, (int)rup(x.L, 8), K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
+      }
     }
   }
   // RMSNorm of the queries (no RoPE in cross-attention, nn.py:330-334) is fused into the attention kernel's Q-fragment load when the
@@ -1350,6 +1376,8 @@ int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h,
     if (!fuse_qnorm) K5CHK(k5_launch_rmsnorm_rope(q, a.norm.as<float>(), nullptr, nullptr, rows, H, D, nullptr, s));
     if (!kv_ready) K5CHK(k5_launch_rmsnorm_rope(ck, a.norm.as<float>() + 64, nullptr, nullptr, L, H, D, nullptr, s));
     if (!kv_ready && nag) K5CHK(k5_launch_rmsnorm_rope(nag->ck, a.norm.as<float>() + 64, nullptr, nullptr, nag->L, H, D, nullptr, s));
+    for (int r = 0; !kv_ready && reg && r < reg->R; ++r)
+      K5CHK(k5_launch_rmsnorm_rope(reg->r[r].ck, a.norm.as<float>() + 64, nullptr, nullptr, reg->r[r].L, H, D, nullptr, s));
   }
   {
     Scope sc(d, s, "attn_cross");
@@ -1365,6 +1393,17 @@ int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h,
       at.kv_len = nag->L; at.ldk = nldck; at.ldvt = nldvt;
       K5CHK(k5_launch_attention_bf16_range(at));
     }
+    for (int r = 0; reg && r < reg->R; ++r) {   // ... and against every region stream
+      const NagCross& x = reg->r[r];
+      at.K = x.ck; at.Vt = x.cvt; at.O = x.o;
+      at.kv_len = x.L; at.ldk = kv_ready ? x.ldck : D; at.ldvt = (int)rup(x.L, 8);
+      K5CHK(k5_launch_attention_bf16_range(at));
+    }
+  }
+  if (reg) {
+    Scope sc(d, s, "elementwise");
+    K5CHK(k5_launch_region_combine(o, reg->o0, reg->o_stride, reg->R, reg->w, reg->R + 1, o, rows, D, D, s));
+    ++d->regions.combines;
   }
   if (nag) {
     Scope sc(d, s, "elementwise");
@@ -1461,7 +1500,7 @@ int prepare_text_rope(k5_dit* d, hipStream_t s, const k5_text_cond& c, const flo
   std::vector<int32_t> key(c.text_rope_pos, c.text_rope_pos + c.text_len);
   for (auto& e : d->text_rope)
     if (e.key == key) { *cosT = e.cosT.as<float>(); *sinT = e.sinT.as<float>(); return K5_OK; }
-  if (d->text_rope.size() >= 8) {
+  if (d->text_rope.size() >= 16) {   // two prompts, a negative one and eight regions fit: a captured step must find its tables here
     HIPCHK(hipStreamSynchronize(s));
     for (auto& e : d->text_rope) { e.cosT.release(); e.sinT.release(); e.pos.release(); }
     d->text_rope.clear();
@@ -1690,7 +1729,16 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   // normalized attention guidance: the conditional branch only (slot 1 is the unconditional forward of k5_sample*)
   const k5_text_cond* ncond = d->nag.on && text_slot != 1 ? d->nag.neg : nullptr;
   const int Ln = ncond ? ncond->text_len : 0;
-  K5CHK(ensure_workspaces(d, sp ? P * n_pad : N, Ln > L ? Ln : L));   // the negative stream borrows the text blocks' scratch
+  // regional prompts: the same branch; a forward of another shape than the masks' is refused before anything is enqueued
+  auto& rg = d->regions;
+  if (rg.on && (a->T != rg.T || a->H != rg.H || a->W != rg.W)) {
+    k5_set_error("regional prompts: the masks are (%d, %d, %d), this forward is (%d, %d, %d)", rg.T, rg.H, rg.W, a->T, a->H, a->W);
+    return K5_ERR_ARG;
+  }
+  const int Rg = rg.on && text_slot != 1 ? rg.R : 0;
+  int Lmax = Ln > L ? Ln : L;   // the extra streams borrow the text blocks' scratch: size it by the longest
+  for (int r = 0; r < Rg; ++r) Lmax = rg.conds[r].text_len > Lmax ? rg.conds[r].text_len : Lmax;
+  K5CHK(ensure_workspaces(d, sp ? P * n_pad : N, Lmax));
   if (sp) {
     K5CHK(d->ws_q.ensure((size_t)n_pad * D * 2)); K5CHK(d->ws_kfull.ensure((size_t)P * n_pad * D * 2));
     K5CHK(d->ws_vtfull.ensure((size_t)P * n_pad * D * 2));
@@ -1807,39 +1855,61 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   // modulation (one time embedding per forward: the positive prompt's pooled embedding); nothing of it on a step MagCache skips ----
   const bool nag = ncond && !mag_skip && c.num_visual_blocks > 0;
   const int Lnr8 = (int)rup(Ln, 8);
-  if (nag) {
-    auto& ng = d->nag;
-    const float *ncos = nullptr, *nsin = nullptr;
-    K5CHK(prepare_text_rope(d, s, *ncond, &ncos, &nsin));
-    K5CHK(ng.text.ensure((size_t)Ln * D * 2)); K5CHK(ng.o.ensure((size_t)n * D * 2));
+  // one more text stream (the negative prompt, a region's): `text` receives what ws_text holds for the forward's own prompt; `cache`: the
+  // slot of text_cache that keeps its prologue for the k5_sample* call
+  auto extra_text_stream = [&](const k5_text_cond& xc, DevBuf& text, int cache, DevBuf& ck_all, DevBuf& cvt_all, DevBuf& ck, DevBuf& cvt) -> int {
+    const int Lx = xc.text_len;
+    const float *xcos = nullptr, *xsin = nullptr;
+    K5CHK(prepare_text_rope(d, s, xc, &xcos, &xsin));
+    K5CHK(text.ensure((size_t)Lx * D * 2));
     {
       Scope sc(d, s, "prologue");
-      k5_dit::TextCache* tc = text_slot >= 0 ? &d->text_cache[2] : nullptr;
-      if (tc && tc->valid && tc->L == Ln) {
-        HIPCHK(hipMemcpyAsync(ng.text.p, tc->text.p, (size_t)Ln * D * 2, hipMemcpyDeviceToDevice, s));
+      k5_dit::TextCache* tc = text_slot >= 0 ? &d->text_cache[cache] : nullptr;
+      if (tc && tc->valid && tc->L == Lx) {
+        HIPCHK(hipMemcpyAsync(text.p, tc->text.p, (size_t)Lx * D * 2, hipMemcpyDeviceToDevice, s));
       } else {
         const void* text_bf;
-        K5CHK(to_bf16(d, s, ncond->text_embed, ncond->text_dtype, (size_t)Ln * c.in_text_dim, d->ws_text_in, &text_bf));
-        K5CHK(k5_launch_gemm_bf16(text_bf, d->text_w.p, d->text_b.as<float>(), d->ws_th.p, Ln, D, c.in_text_dim, c.in_text_dim,
+        K5CHK(to_bf16(d, s, xc.text_embed, xc.text_dtype, (size_t)Lx * c.in_text_dim, d->ws_text_in, &text_bf));
+        K5CHK(k5_launch_gemm_bf16(text_bf, d->text_w.p, d->text_b.as<float>(), d->ws_th.p, Lx, D, c.in_text_dim, c.in_text_dim,
                                   c.in_text_dim, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-        K5CHK(k5_launch_ln_affine(d->ws_th.p, d->text_lnw.as<float>(), d->text_lnb.as<float>(), ng.text.p, nullptr, Ln, D, s));
+        K5CHK(k5_launch_ln_affine(d->ws_th.p, d->text_lnw.as<float>(), d->text_lnb.as<float>(), text.p, nullptr, Lx, D, s));
         if (tc) {
-          K5CHK(tc->text.ensure((size_t)Ln * D * 2));
-          HIPCHK(hipMemcpyAsync(tc->text.p, ng.text.p, (size_t)Ln * D * 2, hipMemcpyDeviceToDevice, s));
-          tc->valid = true; tc->L = Ln;
+          K5CHK(tc->text.ensure((size_t)Lx * D * 2));
+          HIPCHK(hipMemcpyAsync(tc->text.p, text.p, (size_t)Lx * D * 2, hipMemcpyDeviceToDevice, s));
+          tc->valid = true; tc->L = Lx;
         }
       }
     }
     for (int i = 0; i < c.num_text_blocks; ++i) {
       const BlockW& b = d->tblocks[i];
       const float* m = mod + b.mod_off;
-      K5CHK(ln_mod(d, s, ng.text.p, m, d->ws_th.p, Ln));
-      K5CHK(run_self_attention(d, s, b.self_attn, d->ws_th.p, Ln, d->ws_tqk.p, d->ws_tvt.p, d->ws_to.p, ncos, nsin, ng.text.p, m + 2 * D, "attn_text"));
-      K5CHK(ln_mod(d, s, ng.text.p, m + 3 * D, d->ws_th.p, Ln));
-      K5CHK(run_ff(d, s, b, d->ws_th.p, Ln, d->ws_tff.p, ng.text.p, m + 5 * D));
+      K5CHK(ln_mod(d, s, text.p, m, d->ws_th.p, Lx));
+      K5CHK(run_self_attention(d, s, b.self_attn, d->ws_th.p, Lx, d->ws_tqk.p, d->ws_tvt.p, d->ws_to.p, xcos, xsin, text.p, m + 2 * D, "attn_text"));
+      K5CHK(ln_mod(d, s, text.p, m + 3 * D, d->ws_th.p, Lx));
+      K5CHK(run_ff(d, s, b, d->ws_th.p, Lx, d->ws_tff.p, text.p, m + 5 * D));
     }
-    if (cx_all) K5CHK(cross_kv_batched_run(d, s, ng.text.p, Ln, ng.ck_all, ng.cvt_all));
-    else { K5CHK(ng.ck.ensure((size_t)Ln * D * 2)); K5CHK(ng.cvt.ensure((size_t)D * Lnr8 * 2)); }
+    if (cx_all) K5CHK(cross_kv_batched_run(d, s, text.p, Lx, ck_all, cvt_all));
+    else { K5CHK(ck.ensure((size_t)Lx * D * 2)); K5CHK(cvt.ensure((size_t)D * rup(Lx, 8) * 2)); }
+    return K5_OK;
+  };
+  if (nag) {
+    auto& ng = d->nag;
+    K5CHK(ng.o.ensure((size_t)n * D * 2));
+    K5CHK(extra_text_stream(*ncond, ng.text, 2, ng.ck_all, ng.cvt_all, ng.ck, ng.cvt));
+  }
+  // ---- the region streams of k5_dit_set_regions, likewise, and the token weights in this forward's token order (computed once per region
+  // set and order; a sequence-parallel rank reads its rows from tok0 on) ----
+  const bool regional = Rg > 0 && !mag_skip && c.num_visual_blocks > 0;
+  if (regional) {
+    K5CHK(rg.o.ensure((size_t)Rg * n * D * 2));
+    for (int r = 0; r < Rg; ++r) K5CHK(extra_text_stream(rg.conds[r], rg.text[r], 3 + r, rg.ck_all[r], rg.cvt_all[r], rg.ck[r], rg.cvt[r]));
+    if (rg.w_order != (nabla ? 1 : 0)) {
+      Scope sc(d, s, "elementwise");
+      K5CHK(rg.w.ensure((size_t)N * (Rg + 1) * 4));
+      K5CHK(k5_launch_region_weights(rg.masks, Rg, rg.T, rg.H, rg.W, c.patch_size[0], c.patch_size[1], c.patch_size[2], rg.base_weight, perm,
+                                     rg.w.as<float>(), s));
+      rg.w_order = nabla ? 1 : 0;
+    }
   }
   const int sched = sp ? sp_schedule(d, nabla) : 0;
   if (sp) d->sp_mode_used = sched;
@@ -1868,13 +1938,23 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
       if (cx_all) nx = NagCross{ng.text.p, Ln, ng.ck_all.as<bf16_t>() + (size_t)i * D, ng.cvt_all.as<bf16_t>() + (size_t)i * D * Lnr8, c.num_visual_blocks * D, ng.o.p};
       else nx = NagCross{ng.text.p, Ln, ng.ck.p, ng.cvt.p, D, ng.o.p};
     }
+    RegionCross rx{};
+    if (regional) {
+      rx.R = Rg; rx.o0 = rg.o.p; rx.o_stride = (long long)n * D; rx.w = rg.w.as<float>() + (size_t)tok0 * (Rg + 1);
+      for (int r = 0; r < Rg; ++r) {
+        const int Lx = rg.conds[r].text_len;
+        void* o_r = rg.o.as<bf16_t>() + (size_t)r * n * D;
+        if (cx_all) rx.r[r] = NagCross{rg.text[r].p, Lx, rg.ck_all[r].as<bf16_t>() + (size_t)i * D, rg.cvt_all[r].as<bf16_t>() + (size_t)i * D * rup(Lx, 8), c.num_visual_blocks * D, o_r};
+        else rx.r[r] = NagCross{rg.text[r].p, Lx, rg.ck[r].p, rg.cvt[r].p, D, o_r};
+      }
+    }
     if (cx_all)
       K5CHK(run_cross_attention(d, s, b.cross_attn, d->ws_h.p, n, d->ws_text.p, L, d->ws_qk.p, d->ws_ck_all.as<bf16_t>() + (size_t)i * D,
                                 d->ws_cvt_all.as<bf16_t>() + (size_t)i * D * Lr8, d->ws_o.p, d->ws_vis.p, m + 5 * D, true, c.num_visual_blocks * D,
-                                nag ? &nx : nullptr));
+                                nag ? &nx : nullptr, regional ? &rx : nullptr));
     else
       K5CHK(run_cross_attention(d, s, b.cross_attn, d->ws_h.p, n, d->ws_text.p, L, d->ws_qk.p, d->ws_ck.p, d->ws_cvt.p,
-                                d->ws_o.p, d->ws_vis.p, m + 5 * D, false, 0, nag ? &nx : nullptr));
+                                d->ws_o.p, d->ws_vis.p, m + 5 * D, false, 0, nag ? &nx : nullptr, regional ? &rx : nullptr));
     const bool h8_ff = d->fp8_fuse_ln && ff_fp8_in(d, b, n);
     K5CHK(ln_mod(d, s, d->ws_vis.p, m + 6 * D, d->ws_h.p, n, h8_ff));
     K5CHK(run_ff(d, s, b, d->ws_h.p, n, d->ws_ff.p, d->ws_vis.p, m + 8 * D, h8_ff));
@@ -1958,6 +2038,9 @@ extern "C" void k5_dit_destroy(k5_dit* d) {
   if (d->h_leave_sig) { (void)hipHostFree(d->h_leave_sig); d->h_leave_sig = nullptr; }
   for (auto& t : d->text_cache) { t.text.release(); t.pool.release(); }
   for (DevBuf* b : {&d->nag.text, &d->nag.ck_all, &d->nag.cvt_all, &d->nag.ck, &d->nag.cvt, &d->nag.o}) b->release();
+  for (int r = 0; r < 8; ++r)
+    for (DevBuf* b : {&d->regions.text[r], &d->regions.ck_all[r], &d->regions.cvt_all[r], &d->regions.ck[r], &d->regions.cvt[r]}) b->release();
+  d->regions.o.release(); d->regions.w.release();
   for (auto& kv : d->staged) kv.second.dev.release();   // a handle destroyed before finalize still holds its staged matrices
   d->mag.residual[0].release(); d->mag.residual[1].release(); d->mag.pm_one.release();
   for (auto& b : d->vblocks) { b.w1_f8.release(); b.w2_f8.release(); b.s1_f8.release(); b.s2_f8.release(); }
@@ -2259,6 +2342,15 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
                  "collective", who, rank_group(d));
     return K5_ERR_STATE;
   }
+  const k5_dit::Regions& rg = d->regions;
+  if (rg.on && win) {
+    k5_set_error("%s: regional prompts are set (k5_dit_set_regions): the masks cover the clip, a context window sees a slice of it", who);
+    return K5_ERR_STATE;
+  }
+  if (rg.on && (a->fwd.T != rg.T || a->fwd.H != rg.H || a->fwd.W != rg.W)) {
+    k5_set_error("%s: regional prompts: the masks are (%d, %d, %d), this sample is (%d, %d, %d)", who, rg.T, rg.H, rg.W, a->fwd.T, a->fwd.H, a->fwd.W);
+    return K5_ERR_ARG;
+  }
   if (win) {
     if (edit) { k5_set_error("%s: editing with context windows is not supported", who); return K5_ERR_UNSUPPORTED; }
     if (rank_group(d)) { k5_set_error("%s: the handle is in a %s (context windows are single-rank only)", who, rank_group(d)); return K5_ERR_STATE; }
@@ -2515,7 +2607,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     HIPCHK(hipStreamSynchronize(s));   // the caller's tables are host memory
     r.win_starts = d->ws_win.as<int32_t>(); r.win_weights = reinterpret_cast<const float*>(static_cast<char*>(d->ws_win.p) + sb);
   }
-  d->text_cache[0].valid = d->text_cache[1].valid = d->text_cache[2].valid = false;   // the prompt tensors are constant for THIS call only
+  d->drop_text_cache();                                      // the prompt tensors are constant for THIS call only
   K5CHK(reset_attn_pref(d, s));                              // ... and so is what the softmax-form memory of the layers is worth
   // where the visual queries are normalised (see k5_dit::fuse_qnorm_auto): a plain one-handle dense run decides after its first step
   struct FuseGuard { k5_dit* d; ~FuseGuard() { d->fuse_now = false; d->leave_collect = false; } } fuse_guard{d};
@@ -2541,14 +2633,15 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   // Step 0 is always eager.  In graph mode step 1 is captured and instantiated (after the watch has followed step 0: those launches are not
   // part of the graph) and steps 1.. are launches of the executable; between them the watch reads sigma_next as a host scalar.
   GraphGuard cap{s};
-  long long nag_per_step = 0;
+  long long nag_per_step = 0, reg_per_step = 0;
   for (int i = 0; i < N; ++i) {
     if (i == 0 || !graph) K5CHK(r.step(i));
     else {
       if (i == 1) {
         HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const long long nag_before = d->nag.combines;
+        const long long nag_before = d->nag.combines, reg_before = d->regions.combines;
         const int rc = r.step(1);
+        reg_per_step = d->regions.combines - reg_before;
         nag_per_step = d->nag.combines - nag_before;   // k5_dit_nag_state counts launches: the capture stands for step 1's, every further replay adds as many
         const hipError_t ec = hipStreamEndCapture(s, &cap.g);
         if (rc != K5_OK) return rc;
@@ -2556,7 +2649,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
         if (hipGraphInstantiate(&cap.ge, cap.g, nullptr, nullptr, 0) != hipSuccess) { k5_set_error("hipGraphInstantiate failed"); return K5_ERR_HIP; }
       }
       if (hipGraphLaunch(cap.ge, s) != hipSuccess) { k5_set_error("hipGraphLaunch failed"); return K5_ERR_HIP; }
-      if (i > 1) d->nag.combines += nag_per_step;
+      if (i > 1) { d->nag.combines += nag_per_step; d->regions.combines += reg_per_step; }
     }
     if (i == 0) K5CHK(decide_fuse());
     if (wt.on) {
@@ -2681,6 +2774,43 @@ extern "C" int k5_dit_set_nag(k5_dit* d, const k5_text_cond* negative, float sca
   ng.neg = negative; ng.scale = scale; ng.tau = tau; ng.alpha = alpha;
   ng.on = scale != 1.0f && alpha != 0.0f;   // otherwise the combine hands z_pos through: run nothing
   d->text_cache[2].valid = false;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_set_regions(k5_dit* d, const k5_text_cond* regions, int R, const float* masks, int T, int H, int W, float base_weight) {
+  g_err[0] = 0;
+  if (!d) { k5_set_error("k5_dit_set_regions: null handle"); return K5_ERR_ARG; }
+  k5_dit::Regions& rg = d->regions;
+  const auto clear = [&]() {
+    rg.on = false; rg.R = 0; rg.conds = nullptr; rg.masks = nullptr; rg.w_order = -1;
+    for (int r = 0; r < 8; ++r) d->text_cache[3 + r].valid = false;
+  };
+  if (!regions || R == 0) { clear(); return K5_OK; }
+  if (R < 0 || R > 8) { k5_set_error("k5_dit_set_regions: R must be 1..8 (got %d)", R); return K5_ERR_ARG; }
+  if (!(base_weight >= 0.0f && base_weight <= 1.0f)) { k5_set_error("k5_dit_set_regions: base_weight must be in [0, 1] (got %g)", (double)base_weight); return K5_ERR_ARG; }
+  if (!masks) { k5_set_error("k5_dit_set_regions: masks is NULL"); return K5_ERR_ARG; }
+  if (reinterpret_cast<uintptr_t>(masks) & 3) { k5_set_error("k5_dit_set_regions: masks is not 4-byte aligned"); return K5_ERR_ARG; }
+  const int* ps = d->cfg.patch_size;
+  if (T < 1 || H < 1 || W < 1 || ps[0] < 1 || ps[1] < 1 || ps[2] < 1 || (T % ps[0]) || (H % ps[1]) || (W % ps[2])) {
+    k5_set_error("k5_dit_set_regions: the masks' shape (%d, %d, %d) must be positive and divisible by the patch (%d, %d, %d)", T, H, W, ps[0], ps[1], ps[2]);
+    return K5_ERR_ARG;
+  }
+  for (int r = 0; r < R; ++r) {
+    if (regions[r].text_len < 1) { k5_set_error("k5_dit_set_regions: region %d: text_len must be >= 1 (got %d)", r, regions[r].text_len); return K5_ERR_ARG; }
+    if (!regions[r].text_embed || !regions[r].text_rope_pos) { k5_set_error("k5_dit_set_regions: region %d needs text_embed and text_rope_pos", r); return K5_ERR_ARG; }
+  }
+  clear();
+  rg.conds = regions; rg.R = R; rg.masks = masks; rg.T = T; rg.H = H; rg.W = W; rg.base_weight = base_weight;
+  rg.on = true;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_regions_state(k5_dit* d, int* on, int* R, long long* combines, int reset) {
+  if (!d) { k5_set_error("k5_dit_regions_state: null handle"); return K5_ERR_ARG; }
+  if (on) *on = d->regions.on ? 1 : 0;
+  if (R) *R = d->regions.on ? d->regions.R : 0;
+  if (combines) *combines = d->regions.combines;
+  if (reset) d->regions.combines = 0;
   return K5_OK;
 }
 
@@ -2853,7 +2983,7 @@ int lora_requant(k5_dit* d, int vblock, int f8) {
 
 // everything the handle keeps that was computed from the weights as they were
 int lora_drop_derived(k5_dit* d) {
-  d->text_cache[0].valid = d->text_cache[1].valid = d->text_cache[2].valid = false;
+  d->drop_text_cache();
   K5CHK(reset_attn_pref(d, nullptr));
   auto& mg = d->mag;
   mg.cnt = mg.first;

@@ -421,6 +421,30 @@ int k5_nag_combine_bf16(const void* z_pos, const void* z_neg, void* out, int row
   return ret(st, "k5_nag_combine_bf16");
 }
 
+int k5_region_combine_bf16(const void* z0, const void* zr, long long zr_stride, int R, const float* w, int ldw, void* out, int rows, int D,
+                           int ld, void* stream) {
+  const int st = k5_launch_region_combine(z0, zr, zr_stride, R, w, ldw, out, rows, D, ld, (hipStream_t)stream);
+  if (st == K5_ERR_UNSUPPORTED) { k5_set_error("k5_region_combine_bf16: D = %d is more than the register-resident row holds (2048)", D); return st; }
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_region_combine_bf16: need 16-byte aligned non-null pointers (w: 4-byte), rows > 0, D %% 8 == 0, ld >= D, ld %% 8 == 0, "
+                 "zr_stride %% 8 == 0, 1 <= R <= 8, ldw >= R + 1 (rows %d, D %d, ld %d, R %d, ldw %d, zr_stride %lld)", rows, D, ld, R, ldw, zr_stride);
+    return st;
+  }
+  return ret(st, "k5_region_combine_bf16");
+}
+
+int k5_region_weights_f32(const float* masks, int R, int T, int H, int W, int pt, int ph, int pw, float base_weight, const int32_t* perm,
+                          float* w, void* stream) {
+  const int st = k5_launch_region_weights(masks, R, T, H, W, pt, ph, pw, base_weight, perm, w, (hipStream_t)stream);
+  if (st == K5_ERR_UNSUPPORTED) { k5_set_error("k5_region_weights_f32: %d x %d x %d cells are more than 2^31 - 1", T, H, W); return st; }
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_region_weights_f32: need 4-byte aligned non-null masks and w, 1 <= R <= 8, T, H, W >= 1 and divisible by the patch, "
+                 "0 <= base_weight <= 1 (R %d, shape %d x %d x %d, patch %d x %d x %d, base_weight %g)", R, T, H, W, pt, ph, pw, (double)base_weight);
+    return st;
+  }
+  return ret(st, "k5_region_weights_f32");
+}
+
 int k5_conv3d_bf16(const void* X, const void* W, const float* bias, void* out, int Ts, int Hs, int Ws, int Cin, int Cout,
                    int up_t, int up_s, int ldc, const void* resid, int ldr, void* stream) {
   return ret(k5_launch_conv3d_bf16(X, W, bias, out, Ts, Hs, Ws, Cin, Cout, up_t, up_s, ldc, resid, ldr, (hipStream_t)stream),

@@ -204,6 +204,17 @@ int k5_launch_x0_preview(const float* x, const void* v_cond, const void* v_uncon
 // Nothing is launched when it refuses.
 int k5_launch_nag_combine(const void* z_pos, const void* z_neg, void* out, int rows, int D, int ld, float s, float tau, float alpha,
                           hipStream_t stream);
+// regional prompts, the (R+1)-way weighted combine of cross-attention outputs of the same queries: z0 [rows][ld] bf16 (D columns used), region r
+// at zr + r * zr_stride elements, w fp32 [rows][ldw] (column 0 the base stream's weight); per element acc = w z for the first non-zero weight,
+// fmaf(w, z, acc) for every later one, ascending, out = bf16(acc); a zero-weight stream is not read.  out may be z0.  1 <= R <= 8, ldw >= R + 1,
+// D % 8 == 0, ld >= D, ld % 8 == 0, zr_stride % 8 == 0, 16-byte pointers (w 4-byte) (K5_ERR_ARG); D <= 2048 (K5_ERR_UNSUPPORTED).  Nothing is
+// launched when it refuses.
+int k5_launch_region_combine(const void* z0, const void* zr, long long zr_stride, int R, const float* w, int ldw, void* out, int rows, int D,
+                             int ld, hipStream_t stream);
+// regional prompts, cell masks [R][T][H][W] fp32 -> token weights w [N][R + 1] fp32, row i = token perm[i] (perm NULL: i) of the row-major
+// (T / pt, H / ph, W / pw) grid: m_r = mean of the token's cells (clamped to [0, 1]), raw_0 = base_weight + max(0, 1 - sum m), w = raw / sum raw
+int k5_launch_region_weights(const float* masks, int R, int T, int H, int W, int pt, int ph, int pw, float base_weight, const int32_t* perm,
+                             float* w, hipStream_t stream);
 // fp32 -> bf16 cast, bf16 -> fp32
 int k5_launch_cast_f32_bf16(const float* x, void* out, int64_t n, hipStream_t stream);
 // weight packing: src [rows][cols] (K5_F32 / K5_BF16 / K5_F16, device) -> dst [rows][ld] bf16 (RNE) or fp32, pad columns zeroed

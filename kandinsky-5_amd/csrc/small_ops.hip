@@ -1346,3 +1346,135 @@ int k5_launch_nag_combine(const void* z_pos, const void* z_neg, void* out, int r
                      rows, D, ld, s - 1.0f, tau, alpha);
   return done();
 }
+
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// Regional prompts (k5_region_combine_bf16): z_0 .. z_R are the outputs of one cross-attention against the base text and R region
+// texts, same queries; w is the row's R + 1 token weights.  Per element, fp32: the first stream with a non-zero weight gives acc = w z (one
+// rounded product), every later non-zero one acc = fmaf(w, z, acc), ascending from the base stream; out = bf16(acc) once.  A stream whose weight
+// is exactly 0 for the row is not read (NaN there does not reach out); a row whose only non-zero weight is 1.0 is that stream's bits (1 z is z,
+// the sign of a zero included, and a bf16 value rounds to itself); a row without a non-zero weight is +0.
+// One wave per row (the nag_combine_kernel shape): the weights are per row, so the skip is wave-uniform; a used stream's up to MAXC 16-byte
+// chunks per lane are loaded in one burst, the accumulator row stays in registers, out is written once.  out may be z_0 (or any z_r): a lane
+// has read every chunk it writes and no other lane touches it.  The product and the fma must stay what they are written as (region_first /
+// region_next, under `#pragma clang fp contract(off)` like nag_blend).
+__device__ __forceinline__ float region_first(float w, float z) {
+#pragma clang fp contract(off)
+  return w * z;
+}
+__device__ __forceinline__ float region_next(float w, float z, float acc) {
+#pragma clang fp contract(off)
+  return fmaf(w, z, acc);
+}
+
+__global__ __launch_bounds__(256) void region_combine_kernel(const bf16_t* z0, const bf16_t* zr, long long zr_stride, int R, const float* w, int ldw,
+                                                             bf16_t* out, int rows, int D, int ld) {
+  const int lane = threadIdx.x & 63, nch = D >> 3;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;   // wave-uniform
+  const size_t base = (size_t)row * ld;
+  float acc[MAXC][8];
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
+  bool first = true;
+  for (int k = 0; k <= R; ++k) {
+    const float wk = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(w[(size_t)row * ldw + k])));   // one value per wave
+    if (wk == 0.0f) continue;
+    const bf16_t* z = (k == 0 ? z0 : zr + (size_t)(k - 1) * zr_stride) + base;
+    u32x4 raw[MAXC];
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+      const int ch = lane + 64 * i;
+      if (ch < nch) raw[i] = *reinterpret_cast<const u32x4*>(z + 8 * ch);
+    }
+#pragma unroll
+    for (int i = 0; i < MAXC; ++i) {
+      if (lane + 64 * i < nch) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const uint32_t pw = raw[i][j >> 1];
+          const float v = __uint_as_float((j & 1) ? (pw & 0xffff0000u) : (pw << 16));
+          acc[i][j] = first ? region_first(wk, v) : region_next(wk, v, acc[i][j]);
+        }
+      }
+    }
+    first = false;
+  }
+#pragma unroll
+  for (int i = 0; i < MAXC; ++i) {
+    const int ch = lane + 64 * i;
+    if (ch < nch) {
+      const u32x4 pk = {pack_bf16x2(acc[i][0], acc[i][1]), pack_bf16x2(acc[i][2], acc[i][3]), pack_bf16x2(acc[i][4], acc[i][5]),
+                        pack_bf16x2(acc[i][6], acc[i][7])};
+      *reinterpret_cast<u32x4*>(out + base + 8 * ch) = pk;
+    }
+  }
+}
+
+// Token weights of the regional prompts (k5_region_weights_f32): one thread per token i of the engine's order, token perm[i] (or i) of the
+// row-major (T / pt, H / ph, W / pw) token grid.  m_r = mean of the token's pt ph pw cells of mask r, each cell clamped to [0, 1] (a NaN cell counts as 0), added
+// in ascending (t, h, w) order and divided by the count; sm = m_1 + .. + m_R ascending; raw_0 = base_weight + max(0, 1 - sm);
+// s = raw_0 + m_1 + .. + m_R ascending (>= 1); w_0 = raw_0 / s, w_r = m_r / s.  Every operation rounded on its own, no atomics.
+__global__ __launch_bounds__(256) void region_weights_kernel(const float* masks, int R, int T, int H, int W, int pt, int ph, int pw, float bw,
+                                                             const int32_t* perm, float* w, int N) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const int Hp = H / ph, Wp = W / pw;
+  const int tok = perm ? perm[i] : i;
+  const int tw = tok % Wp, th = (tok / Wp) % Hp, tt = tok / (Wp * Hp);
+  const float cells = (float)(pt * ph * pw);
+  float m[8];
+  float sm = 0.f;
+  for (int r = 0; r < 8; ++r) {
+    m[r] = 0.f;
+    if (r < R) {
+      float a = 0.f;
+      for (int dt = 0; dt < pt; ++dt)
+        for (int dh = 0; dh < ph; ++dh)
+          for (int dw = 0; dw < pw; ++dw) {
+            const float c = masks[(((size_t)r * T + (size_t)(tt * pt + dt)) * H + (size_t)(th * ph + dh)) * W + (size_t)(tw * pw + dw)];
+            a += fminf(fmaxf(c, 0.f), 1.f);
+          }
+      m[r] = a / cells;
+      sm += m[r];
+    }
+  }
+  const float raw0 = bw + fmaxf(0.f, 1.f - sm);
+  float s = raw0;
+  for (int r = 0; r < 8; ++r)
+    if (r < R) s += m[r];
+  float* wi = w + (size_t)i * (R + 1);
+  wi[0] = raw0 / s;
+  for (int r = 0; r < 8; ++r)
+    if (r < R) wi[r + 1] = m[r] / s;
+}
+
+}  // namespace
+
+int k5_launch_region_combine(const void* z0, const void* zr, long long zr_stride, int R, const float* w, int ldw, void* out, int rows, int D,
+                             int ld, hipStream_t stream) {
+  if (!z0 || !zr || !w || !out || rows <= 0 || D <= 0 || ld < D || R < 1 || R > 8 || ldw < R + 1) return K5_ERR_ARG;
+  const auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if ((D & 7) || (ld & 7) || (zr_stride & 7) || misaligned(z0) || misaligned(zr) || misaligned(out) || (reinterpret_cast<uintptr_t>(w) & 3))
+    return K5_ERR_ARG;
+  if (D > 64 * 8 * MAXC) return K5_ERR_UNSUPPORTED;   // the register-resident row
+  hipLaunchKernelGGL(region_combine_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, (const bf16_t*)z0, (const bf16_t*)zr, zr_stride, R, w, ldw,
+                     (bf16_t*)out, rows, D, ld);
+  return done();
+}
+
+int k5_launch_region_weights(const float* masks, int R, int T, int H, int W, int pt, int ph, int pw, float base_weight, const int32_t* perm,
+                             float* w, hipStream_t stream) {
+  if (!masks || !w || R < 1 || R > 8 || T < 1 || H < 1 || W < 1 || pt < 1 || ph < 1 || pw < 1 || (T % pt) || (H % ph) || (W % pw)) return K5_ERR_ARG;
+  if (!(base_weight >= 0.0f && base_weight <= 1.0f)) return K5_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(masks) & 3) || (reinterpret_cast<uintptr_t>(w) & 3) || (reinterpret_cast<uintptr_t>(perm) & 3)) return K5_ERR_ARG;
+  const long long N = (long long)(T / pt) * (H / ph) * (W / pw);
+  if (N > 0x7fffffffLL || (long long)T * H * W > 0x7fffffffLL) return K5_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(region_weights_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, masks, R, T, H, W, pt, ph, pw, base_weight, perm,
+                     w, (int)N);
+  return done();
+}

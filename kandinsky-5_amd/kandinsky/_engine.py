@@ -205,6 +205,10 @@ SYMBOLS = {
     "k5_nag_combine_bf16": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _P]),
     "k5_dit_set_nag": (_I, [_P, C.POINTER(TextCond), _F, _F, _F]),
     "k5_dit_nag_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), _I]),
+    "k5_region_combine_bf16": (_I, [_P, _P, C.c_longlong, _I, _P, _I, _P, _I, _I, _I, _P]),
+    "k5_region_weights_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "k5_dit_set_regions": (_I, [_P, C.POINTER(TextCond), _I, _P, _I, _I, _I, _F]),
+    "k5_dit_regions_state": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_longlong), _I]),
     "k5_dit_forward_many": (_I, [_P, C.POINTER(ForwardArgs), _I, C.POINTER(TextCond), _P, _P]),
     "k5_comm_unique_id": (_I, [C.c_char_p, _P]),
     "k5_dit_comm_init": (_I, [_P, C.c_char_p, _I, _I, _P]),
@@ -533,6 +537,45 @@ def nag_combine_(z_pos, z_neg, s, tau, alpha, out=None, D=None):
         check(lib().k5_nag_combine_bf16(ptr(z_pos), ptr(z_neg), ptr(out), rows, D, ld, float(s), float(tau), float(alpha),
                                         stream_ptr(z_pos.device)), "k5_nag_combine_bf16")
     return out
+
+
+def region_combine_(z0, zr, w, out=None, D=None):
+    """The regional-prompt blend, in place on z0 unless `out` is given (k5_region_combine_bf16): out = sum_i w_i z_i per row, stream 0 = z0
+    (bf16 [rows][ld]), streams 1..R = zr (bf16 [R][rows][ld], the same row stride), w fp32 [rows][ldw] with ldw >= R + 1; a stream whose
+    weight is 0 for a row is not read.  D (default: all ld columns) of each row are used, the rest is not touched."""
+    out = z0 if out is None else out
+    for x in (z0, out):
+        if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1 or x.shape != z0.shape or x.stride(0) != z0.stride(0):
+            raise ValueError("region_combine_: z0 and out must be bf16 [rows][ld] tensors of one shape and row stride")
+    if (zr.dtype != torch.bfloat16 or zr.dim() != 3 or zr.shape[1:] != z0.shape or zr.stride(2) != 1 or zr.stride(1) != z0.stride(0)):
+        raise ValueError("region_combine_: zr must be bf16 [R][rows][ld] with z0's row stride")
+    if w.dtype != torch.float32 or w.dim() != 2 or w.shape[0] != z0.shape[0] or w.stride(1) != 1:
+        raise ValueError("region_combine_: w must be fp32 [rows][ldw]")
+    rows, ld = z0.shape[0], z0.stride(0)
+    D = z0.shape[1] if D is None else int(D)
+    with torch.cuda.device(z0.device):
+        check(lib().k5_region_combine_bf16(ptr(z0), ptr(zr), zr.stride(0) if zr.shape[0] > 1 else rows * ld, zr.shape[0], ptr(w), w.stride(0),
+                                           ptr(out), rows, D, ld, stream_ptr(z0.device)), "k5_region_combine_bf16")
+    return out
+
+
+def region_weights(masks, patch, base_weight, perm=None):
+    """Token weights of regional prompts (k5_region_weights_f32): masks fp32 (R, T, H, W) on the device, patch (pt, ph, pw); returns fp32
+    (N, R + 1), row i = token perm[i] (int32 tensor on the device; None: i) of the row-major token grid."""
+    if masks.dtype != torch.float32 or masks.dim() != 4 or not masks.is_contiguous():
+        raise ValueError("region_weights: masks must be a contiguous fp32 (R, T, H, W) tensor")
+    R, T, H, W = masks.shape
+    pt, ph, pw = (int(p) for p in patch)
+    if pt < 1 or ph < 1 or pw < 1 or T % pt or H % ph or W % pw:
+        raise ValueError(f"region_weights: ({T}, {H}, {W}) is not divisible by the patch {(pt, ph, pw)}")
+    N = (T // pt) * (H // ph) * (W // pw)
+    if perm is not None and (perm.dtype != torch.int32 or perm.numel() != N or not perm.is_contiguous() or perm.device != masks.device):
+        raise ValueError("region_weights: perm must be a contiguous int32 tensor of N tokens on the masks' device")
+    w = torch.empty(N, R + 1, dtype=torch.float32, device=masks.device)
+    with torch.cuda.device(masks.device):
+        check(lib().k5_region_weights_f32(ptr(masks), R, T, H, W, pt, ph, pw, float(base_weight), ptr(perm) if perm is not None else None, ptr(w),
+                                          stream_ptr(masks.device)), "k5_region_weights_f32")
+    return w
 
 
 def x0_preview(img, v_cond, v_uncond, w, sigma_next, rgb_factors=None, rgb_bias=None, source=None, keep_mask=None, want_x0=False,

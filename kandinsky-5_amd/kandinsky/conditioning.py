@@ -121,6 +121,33 @@ def pixel_mask_to_latent(mask, T, H, W):
     return out.float()[..., None].contiguous()
 
 
+def region_masks_to_latent(masks, T, H, W):
+    """Pixel region masks -> latent region masks fp32 (R, T, H/8, W/8) for `set_regions` / `generate(region_masks=)`: the mean over each 8x8
+    block and over the pixel frames of each latent frame (`pixel_mask_to_latent`'s frame rule — latent frame 0 = pixel frame 0, latent frame
+    t >= 1 = pixel frames 4t-3 .. 4t — with a mean where that function takes `all`), clamped to [0, 1].  `masks`: (R, H, W), applied to all
+    frames, or (R, F, H, W) with F >= 4 * (T - 1) + 1; any real dtype (bool: False / True = 0 / 1)."""
+    if not torch.is_tensor(masks):
+        import numpy as np
+        masks = torch.from_numpy(np.ascontiguousarray(masks))
+    if H % 8 or W % 8:
+        raise ValueError(f"height and width must be multiples of 8, got {H} x {W}")
+    need = 4 * (int(T) - 1) + 1
+    m = masks.detach().cpu().float()
+    if m.dim() == 3:
+        m = m[:, None].expand(-1, need, -1, -1)
+    if m.dim() != 4 or tuple(m.shape[2:]) != (H, W):
+        raise ValueError(f"masks must be (R, {H}, {W}) or (R, F, {H}, {W}), got shape {tuple(masks.shape)}")
+    if m.shape[1] < need:
+        raise ValueError(f"a {T}-frame latent needs masks of {need} pixel frames, got {m.shape[1]}")
+    R = m.shape[0]
+    cell = m[:, :need].reshape(R, need, H // 8, 8, W // 8, 8).mean(dim=(3, 5))            # (R, F, H/8, W/8)
+    out = torch.empty((R, T, H // 8, W // 8), dtype=torch.float32)
+    out[:, 0] = cell[:, 0]
+    if T > 1:
+        out[:, 1:] = cell[:, 1:].reshape(R, T - 1, 4, H // 8, W // 8).mean(dim=2)
+    return out.clamp_(0.0, 1.0).contiguous()
+
+
 def latents_to_visual_cond(latents, num_frames):
     """k latent frames (k, H, W, C) -> (visual_cond (num_frames, H, W, C), mask (num_frames, H, W, 1)): frames 0..k-1 hold the
     given latents with mask 1, the rest are zero."""

@@ -239,6 +239,29 @@ def _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau,
             model.clear_nag()
 
 
+@contextlib.contextmanager
+def _regions_for_call(model, region_text_embeds, region_text_rope_pos, region_masks, region_base_weight):
+    """`generate`'s region keywords as regional prompts for exactly one call: set on the model, and what was there before put back, also on
+    an exception.  region_text_embeds None: nothing is touched."""
+    if region_text_embeds is None:
+        yield
+        return
+    from .models.dit import DiffusionTransformer3D, check_region_args
+    check_region_args(region_text_embeds, region_text_rope_pos, region_masks, region_base_weight)
+    if type(model) is not DiffusionTransformer3D:
+        raise ValueError("region_text_embeds needs the engine-backed DiffusionTransformer3D: regional prompts run inside its forward, a "
+                         "wrapped or duck-typed model has no hook for them")
+    before = model._regions
+    try:
+        model.set_regions(region_text_embeds, region_text_rope_pos, region_masks, region_base_weight)
+        yield
+    finally:
+        if before is not None:
+            model.set_regions([{"text_embeds": t} for t in before["text"]], before["pos"], before["masks"], before["base_weight"])
+        else:
+            model.clear_regions()
+
+
 def _conditioning(model, img, visual_cond, visual_cond_mask):
     """`(vc, vm)` of img's shape and of img.shape[:-1] + (1,), fp32 on img's device, from `visual_cond` / `visual_cond_mask` (zeros for the one
     that is missing); None when neither is given."""
@@ -272,7 +295,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
              null_text_rope_pos, guidance_weight, scheduler_scale, conf, progress=False, seed=6554, noise=None, *,
              visual_cond=None, visual_cond_mask=None, batch=1, init_latent=None, strength=1.0, keep_mask=None,
              callback=None, preview_every=0, preview_factors=None, preview_x0=False, context_frames=None, context_overlap=None,
-             context_text=None, nag_text_embeds=None, nag_text_rope_pos=None, nag_scale=None, nag_tau=2.5, nag_alpha=0.25):
+             context_text=None, nag_text_embeds=None, nag_text_rope_pos=None, nag_scale=None, nag_tau=2.5, nag_alpha=0.25,
+             region_text_embeds=None, region_text_rope_pos=None, region_masks=None, region_base_weight=0.0):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -307,7 +331,15 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     otherwise `nag_text_embeds` (a dict like `text_embeds`) and `nag_text_rope_pos` are the negative prompt, one for every sample and
     window.  Set on the model for this call and removed afterwards, also when the call raises; every rank of a group or a CFG pair
     passes the same values.  The unconditional forward of a CFG run is not touched.  5 / 2.5 / 0.25 are the values commonly quoted for
-    NAG: starting points, not tuned on any Kandinsky checkpoint.  ValueError on a model without the engine (wrapped or duck-typed)."""
+    NAG: starting points, not tuned on any Kandinsky checkpoint.  ValueError on a model without the engine (wrapped or duck-typed).
+    `region_text_embeds`, `region_text_rope_pos`, `region_masks`, `region_base_weight` (optional, extension): regional prompts, a prompt
+    per masked region inside the cross-attention of the conditional forward (`DiffusionTransformer3D.set_regions`).  `region_text_embeds`
+    None (default) is off and nothing changes; otherwise a list of 1 to 8 dicts like `text_embeds`, `region_text_rope_pos` their positions
+    and `region_masks` (R, T, H, W) in [0, 1] on one sample's latent cells (`conditioning.region_masks_to_latent`); `text_embeds` is the base
+    prompt, which uncovered cells see alone and which weighs `region_base_weight` in [0, 1] under the regions.  One region set for every
+    sample of a batch.  Set on the model for this call and removed afterwards, also when the call raises; every rank of a group or a CFG
+    pair passes the same values.  The unconditional forward of a CFG run is not touched.  ValueError on a model without the engine and
+    together with `context_frames` below the clip's length (the masks cover the clip, a window sees a slice)."""
     from .models.dit import split_per_sample
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
@@ -321,7 +353,10 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
             split_per_sample(v, 1, n)[0] for v, n in ((text_embeds, "text_embeds"), (null_text_embeds, "null_text_embeds"),
                                                  (text_rope_pos, "text_rope_pos"), (null_text_rope_pos, "null_text_rope_pos")))
     steps_run = num_steps - (edit_first_step(num_steps, strength) if init_latent is not None else 0)
-    with _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha):
+    if region_text_embeds is not None and plan is not None and len(plan[1]) > 1:
+        raise ValueError("region_text_embeds together with context windows is not supported: the masks cover the clip, a window sees a slice")
+    with _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
+            _regions_for_call(model, region_text_embeds, region_text_rope_pos, region_masks, region_base_weight):
         # one hook for the whole call (it owns the bar): the samples of a batch share it
         watch = _StepWatch(model, callback, preview_every, preview_factors, preview_x0, progress, batch * steps_run, shape[-1])
         try:
@@ -532,7 +567,8 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                     scheduler_scale=1, negative_caption="", seed=6554, device="cuda", vae_device="cuda",
                     text_embedder_device="cuda", progress=True, offload=False, image=None, video=None, strength=1.0, mask=None,
                     callback=None, preview_every=0, preview_factors=None, context_frames=None, context_overlap=None,
-                    nag_scale=None, nag_tau=2.5, nag_alpha=0.25):
+                    nag_scale=None, nag_tau=2.5, nag_alpha=0.25, region_text_embeds=None, region_text_rope_pos=None, region_masks=None,
+                    region_base_weight=0.0):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -546,7 +582,12 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     extension): a clip longer than the model's trained length, sampled as overlapping temporal windows of `context_frames` latent frames
     (see `generate` and `context_windows`).  With bs = 1 `caption` may then be a list of nwin prompts, one per window in order.
     `nag_scale`, `nag_tau`, `nag_alpha` (optional, extension): normalized attention guidance with the already encoded `negative_caption` as
-    the negative prompt (see `generate`); what makes `negative_caption` count at guidance_weight 1.  None (default) is off."""
+    the negative prompt (see `generate`); what makes `negative_caption` count at guidance_weight 1.  None (default) is off.
+    `region_text_embeds`, `region_text_rope_pos`, `region_masks`, `region_base_weight` (optional, extension): regional prompts (see
+    `generate`): `caption` is the base prompt, `region_masks` (R, frames, height, width) lies on the latent cells of one sample
+    (`conditioning.region_masks_to_latent`).  `region_text_embeds` is a list of already encoded dicts with their `region_text_rope_pos`, or
+    a list of R prompt strings: those are encoded by the same embedder call as the caption (only their token embeddings are used) and take
+    positions 0 .. n-1.  One region set for every sample of a batch."""
     batch, frames, height, width, channels = shape
     ctx_kw, window_captions = {}, None
     if context_frames is not None:
@@ -560,6 +601,25 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
             window_captions, caption = list(caption), caption[0]
     elif context_overlap is not None:
         raise ValueError("context_overlap needs context_frames")
+    region_kw, region_prompts = {}, []
+    if region_text_embeds is not None:   # before any model runs
+        from .models.dit import DiffusionTransformer3D, check_region_args
+        if isinstance(region_text_embeds, (list, tuple)) and region_text_embeds and all(isinstance(p, str) for p in region_text_embeds):
+            if region_text_rope_pos is not None:
+                raise ValueError("regions: prompts given as strings take positions 0 .. n-1, region_text_rope_pos must be None")
+            region_prompts = list(region_text_embeds)   # checked now with stand-ins of one token, encoded with the caption below
+            check_region_args([{"text_embeds": torch.zeros(1, 1)}] * len(region_prompts), [[0]] * len(region_prompts), region_masks,
+                              region_base_weight)
+        else:
+            check_region_args(region_text_embeds, region_text_rope_pos, region_masks, region_base_weight)
+        if context_frames is not None:
+            raise ValueError("regions together with context_frames is not supported: the masks cover the clip, a window sees a slice")
+        if tuple(region_masks.shape[1:]) != (frames, height, width):
+            raise ValueError(f"regions: the masks are {tuple(region_masks.shape[1:])}, one sample's latent is {(frames, height, width)}")
+        if type(dit) is not DiffusionTransformer3D:
+            raise ValueError("region_text_embeds needs the engine-backed DiffusionTransformer3D (see `generate`)")
+        region_kw = dict(region_text_embeds=region_text_embeds, region_text_rope_pos=region_text_rope_pos, region_masks=region_masks,
+                         region_base_weight=region_base_weight)
     if nag_scale is not None:   # before any model runs
         from .models.dit import DiffusionTransformer3D, check_nag_numbers
         check_nag_numbers(nag_scale, nag_tau, nag_alpha)
@@ -600,17 +660,22 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         ctx_kw["context_text"] = [(by_prompt[p][0], torch.arange(by_prompt[p][1])) for p in window_captions]
         cond, text_pos = ctx_kw["context_text"][0]
     elif batch == 1:
-        (cond, n_cond), (uncond, n_uncond) = _encode_prompts(text_embedder, (captions[0], negative_caption), kind, device)
+        (cond, n_cond), (uncond, n_uncond), *region_enc = _encode_prompts(text_embedder, [captions[0], negative_caption] + region_prompts, kind,
+                                                                          device)
         text_pos = torch.arange(n_cond)
     else:
         distinct = list(dict.fromkeys(captions))   # a prompt shared by several samples is encoded once
-        *encoded, (uncond, n_uncond) = _encode_prompts(text_embedder, distinct + [negative_caption], kind, device)
+        *encoded, (uncond, n_uncond) = _encode_prompts(text_embedder, distinct + region_prompts + [negative_caption], kind, device)
+        encoded, region_enc = encoded[:len(distinct)], encoded[len(distinct):]
         by_prompt = dict(zip(distinct, encoded))
         cond = [by_prompt[p][0] for p in captions]
         text_pos = [torch.arange(by_prompt[p][1]) for p in captions]
     if offload:
         text_embedder = text_embedder.to("cpu")
 
+    if region_prompts:
+        region_kw.update(region_text_embeds=[{"text_embeds": e["text_embeds"]} for e, _ in region_enc],
+                         region_text_rope_pos=[torch.arange(n) for _, n in region_enc])
     nag_kw = {} if nag_scale is None else dict(nag_text_embeds=uncond, nag_text_rope_pos=torch.arange(n_uncond), nag_scale=nag_scale,
                                                nag_tau=nag_tau, nag_alpha=nag_alpha)
     patch = conf.model.dit_params.patch_size
@@ -621,7 +686,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         latent = generate(dit, device, (batch * frames, height, width, channels), num_steps, cond, uncond, grid,
                           text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
                           progress=progress, batch=batch, callback=callback, preview_every=preview_every,
-                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw)
+                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

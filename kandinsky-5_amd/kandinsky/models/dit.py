@@ -129,6 +129,37 @@ def check_nag_args(text_embeds, text_rope_pos, scale, tau, alpha):
     return scale, tau, alpha
 
 
+def check_region_args(text_embeds_list, rope_pos_list, masks, base_weight):
+    """The ValueErrors of `set_regions` / `generate(region_text_embeds=, region_text_rope_pos=, region_masks=, region_base_weight=)`; returns
+    base_weight as a float."""
+    import math
+    try:
+        base_weight = float(base_weight)
+    except (TypeError, ValueError):
+        raise ValueError("regions: base_weight must be a number") from None
+    if math.isnan(base_weight) or not 0.0 <= base_weight <= 1.0:
+        raise ValueError(f"regions: base_weight must be in [0, 1] (got {base_weight})")
+    if not isinstance(text_embeds_list, (list, tuple)) or not isinstance(rope_pos_list, (list, tuple)):
+        raise ValueError("regions: the prompts and their positions must be lists, one entry per region")
+    R = len(text_embeds_list)
+    if not 1 <= R <= 8:
+        raise ValueError(f"regions: 1 to 8 regions (got {R})")
+    if len(rope_pos_list) != R:
+        raise ValueError(f"regions: {R} prompts but {len(rope_pos_list)} position vectors")
+    for r, (te, pos) in enumerate(zip(text_embeds_list, rope_pos_list)):
+        if not isinstance(te, dict) or not torch.is_tensor(te.get("text_embeds")):
+            raise ValueError(f'regions: prompt {r} must be a dict with a "text_embeds" tensor (what `generate` takes)')
+        t = te["text_embeds"]
+        if t.dim() != 2 or t.shape[0] < 1:
+            raise ValueError(f"regions: prompt {r}: text_embeds must be [tokens][in_text_dim] with at least one token (got {tuple(t.shape)})")
+        if pos is None or len(torch.as_tensor(pos).reshape(-1)) != t.shape[0]:
+            raise ValueError(f"regions: prompt {r}: text_rope_pos must have one position per token")
+    if not torch.is_tensor(masks) or masks.dim() != 4 or masks.shape[0] != R or masks.is_complex():
+        raise ValueError(f"regions: masks must be a real (R, T, H, W) tensor on the latent cells with R = {R} "
+                         f"(got {tuple(masks.shape) if torch.is_tensor(masks) else type(masks).__name__})")
+    return base_weight
+
+
 def check_watch_args(callback, preview_every, rgb_factors, want_x0, channels):
     """The ValueErrors of `set_watch` / `generate(callback=, preview_every=, preview_factors=)`; returns (W [C][3], preview_every)."""
     preview_every = int(preview_every)
@@ -203,6 +234,7 @@ class DiffusionTransformer3D(nn.Module):
         self._lora_saved = {}        # parameters as they were before a merge done in torch (no engine yet): key -> tensor
         self._watch = None           # (trampoline, k5_watch and the arrays it points to) of set_watch: re-installed when the engine is rebuilt
         self._nag = None             # the negative prompt of set_nag, its k5_text_cond and what that points to: re-installed likewise
+        self._regions = None         # the prompts and masks of set_regions, their k5_text_cond array and what it points to: likewise
 
     # ---------------------------------------------------------------- engine lifetime
     def _destroy_engine(self, force=False):
@@ -273,6 +305,8 @@ class DiffusionTransformer3D(nn.Module):
             self._install_watch()
         if getattr(self, "_nag", None) is not None:
             self._install_nag()
+        if getattr(self, "_regions", None) is not None:
+            self._install_regions()
         if getattr(self, "mag_ratios", None) is not None or getattr(self, "_magcache_calibrate", None) is not None:   # set before the weights were loaded / the handle rebuilt
             from ..magcache_utils import _apply
             _apply(self)
@@ -586,6 +620,64 @@ class DiffusionTransformer3D(nn.Module):
         if self._handle is not None:
             E.check(E.lib().k5_dit_nag_state(self._handle, C.byref(on), C.byref(n), int(bool(reset))), "k5_dit_nag_state")
         return bool(on.value), n.value
+
+    # ---------------------------------------------------------------- regional prompts: a prompt per masked region in one forward
+    def set_regions(self, text_embeds_list, rope_pos_list, masks, base_weight=0.0):
+        """A prompt per masked region inside the cross-attention of ONE forward (k5_dit_set_regions; "attention couple").  `text_embeds_list`:
+        1 to 8 dicts as `generate` takes ("text_embeds" [L][in_text_dim]; "pooled_embed" is not read: a forward has one time embedding, the
+        base prompt's), `rope_pos_list` their positions, `masks` (R, T, H, W) in [0, 1] on the latent cells (the grid of `keep_mask`;
+        `conditioning.region_masks_to_latent` pools pixel masks to it).  Every conditional forward — `forward`, `forward_many`, the
+        conditional branch of `sample*` — then attends each visual block's queries to the base prompt and to every region prompt and blends
+        the outputs per token: a token's mask value is the mean of its cells, the base prompt weighs base_weight + max(0, 1 - sum of the
+        masks), the weights are normalised to sum 1.  An uncovered token sees the base prompt only; masks that partition the frame at
+        base_weight 0 give every token exactly one prompt.  The model keeps the tensors alive until `clear_regions`.  `sample(windows=)`
+        refuses while regions are set.  No checkpoint was at hand when this was written: what it does to a picture is not claimed."""
+        base_weight = check_region_args(text_embeds_list, rope_pos_list, masks, base_weight)
+        for r, te in enumerate(text_embeds_list):
+            if te["text_embeds"].shape[1] != self._cfg["in_text_dim"]:
+                raise ValueError(f"regions: prompt {r} has {te['text_embeds'].shape[1]} features, the model takes {self._cfg['in_text_dim']}")
+        pt, ph, pw = self.patch_size
+        if masks.shape[1] % pt or masks.shape[2] % ph or masks.shape[3] % pw:
+            raise ValueError(f"regions: the masks' shape {tuple(masks.shape[1:])} is not divisible by the patch {(pt, ph, pw)}")
+        self._regions = {"text": [te["text_embeds"] for te in text_embeds_list], "pos": list(rope_pos_list), "masks": masks,
+                         "base_weight": base_weight, "conds": None, "keep": None}
+        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
+            try:
+                self._install_regions()
+            except Exception:
+                self._regions = None
+                raise
+        return self
+
+    def _install_regions(self):
+        g = self._regions
+        dev = self._handle_device
+        keep = []
+        R = len(g["text"])
+        conds = (E.TextCond * R)()
+        for r in range(R):
+            te = g["text"][r].to(dev)
+            conds[r] = self._text_cond(te, te.new_zeros(1, self._cfg["in_text_dim2"]), g["pos"][r], keep)
+        masks = g["masks"].to(device=dev, dtype=torch.float32).contiguous()
+        keep.append(masks)
+        g["conds"], g["keep"] = conds, keep    # the engine borrows the array and what it points to
+        with torch.cuda.device(dev):
+            E.check(E.lib().k5_dit_set_regions(self._handle, conds, R, E.ptr(masks), *masks.shape[1:], g["base_weight"]), "k5_dit_set_regions")
+
+    def clear_regions(self):
+        """Remove the regions: a forward enqueues exactly what it did before `set_regions`."""
+        self._regions = None
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_set_regions(self._handle, None, 0, None, 0, 0, 0, 0.0), "k5_dit_set_regions")
+        return self
+
+    def regions_state(self, reset=False):
+        """(on, R, combines): whether regions are on, how many, and how many combine launches the engine has enqueued — num_visual_blocks per
+        regional forward (k5_dit_regions_state).  `reset` zeroes the count afterwards."""
+        on, R, n = C.c_int(0), C.c_int(0), C.c_longlong(0)
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_regions_state(self._handle, C.byref(on), C.byref(R), C.byref(n), int(bool(reset))), "k5_dit_regions_state")
+        return bool(on.value), R.value, n.value
 
     def _step_info(self, info):
         shape = (info.T, info.H, info.W)

@@ -93,7 +93,7 @@ class Kandinsky5T2VPipeline:
                  negative_caption: str = _NEG, expand_prompts: bool = True, save_path: str = None,
                  progress: bool = True, image=None, video=None, strength: float = None, mask=None, callback=None,
                  preview_every: int = 0, preview_factors=None, context_seconds: float = None, context_overlap_seconds: float = None,
-                 nag_scale: float = None, nag_tau: float = 2.5, nag_alpha: float = 0.25):
+                 nag_scale: float = None, nag_tau: float = 2.5, nag_alpha: float = 0.25, regions=None, region_base_weight: float = 0.0):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -115,8 +115,32 @@ class Kandinsky5T2VPipeline:
         `nag_scale`, `nag_tau`, `nag_alpha` (optional, extension): normalized attention guidance — `negative_caption` steers inside the
         cross-attention of the one conditional forward, which is what makes it count on the checkpoints that run without classifier-free
         guidance (nocfg, distil).  `nag_scale` None (default) is off; 5 / 2.5 / 0.25 are the commonly quoted values, starting points that
-        were not tuned on any Kandinsky checkpoint.  See `generate`."""
+        were not tuned on any Kandinsky checkpoint.  See `generate`.
+        `regions`, `region_base_weight` (optional, extension): regional prompts, `pipe(text, regions=[(prompt, mask), ...])` — 1 to 8 pairs of
+        a prompt and a pixel mask in [0, 1], (height, width) or (F, height, width), that says where the prompt applies; `text` is the base
+        prompt, which the uncovered pixels see alone and which weighs `region_base_weight` in [0, 1] under the regions.  The masks are
+        pooled to the latent cells by their mean (`conditioning.region_masks_to_latent`), the region prompts are encoded with the caption
+        (not expanded) and every visual block blends its cross-attention to the prompts per token (`DiffusionTransformer3D.set_regions`).  A
+        list of texts shares one region set.  Not together with `context_seconds`.  No checkpoint was at hand when this was written:
+        what it does to a picture is not claimed."""
         ctx = {}
+        region_kw = {}
+        if regions is not None:
+            from .conditioning import region_masks_to_latent
+            from .models.dit import check_region_args
+            if context_seconds is not None:
+                raise ValueError("regions together with context_seconds is not supported: the masks cover the clip, a window sees a slice")
+            pairs = list(regions)
+            if not 1 <= len(pairs) <= 8 or not all(isinstance(p, (list, tuple)) and len(p) == 2 and isinstance(p[0], str) for p in pairs):
+                raise ValueError("regions must be a list of 1 to 8 (prompt, mask) pairs")
+            self._check_size(height, width)
+            lat_frames = 1 if time_length == 0 else time_length * 24 // 4 + 1
+            masks = [torch.as_tensor(m) for _, m in pairs]
+            if any(m.dim() != masks[0].dim() or m.shape != masks[0].shape for m in masks):
+                raise ValueError("regions: the masks must all have one shape, (height, width) or (F, height, width)")
+            lat = region_masks_to_latent(torch.stack([m.float() for m in masks]), lat_frames, height, width)
+            check_region_args([{"text_embeds": torch.zeros(1, 1)}] * len(pairs), [[0]] * len(pairs), lat, region_base_weight)
+            region_kw = dict(region_text_embeds=[p for p, _ in pairs], region_masks=lat, region_base_weight=float(region_base_weight))
         if nag_scale is not None:
             from .models.dit import check_nag_numbers
             check_nag_numbers(nag_scale, nag_tau, nag_alpha)
@@ -160,6 +184,6 @@ class Kandinsky5T2VPipeline:
                                  device=self.device_map["dit"], vae_device=self.device_map["vae"],
                                  text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload,
                                  image=image, video=video, strength=strength, mask=mask, callback=callback,
-                                 preview_every=preview_every, preview_factors=preview_factors, **ctx)
+                                 preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw)
         torch.cuda.empty_cache()
         return self._save(images, time_length, save_path) if self.local_dit_rank == 0 else None

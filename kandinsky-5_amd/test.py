@@ -76,7 +76,38 @@ def build_parser():
                         "count without classifier-free guidance); S >= 1, commonly 5 — a starting point, not tuned on these checkpoints")
     p.add_argument("--nag_tau", type=float, default=argparse.SUPPRESS, metavar="T", help="with --nag_scale: clamp on the growth of a token's L1 norm, >= 1 (default 2.5)")
     p.add_argument("--nag_alpha", type=float, default=argparse.SUPPRESS, metavar="A", help="with --nag_scale: blend of the guided output, in [0, 1] (default 0.25)")
+    p.add_argument("--region", nargs=2, action="append", default=argparse.SUPPRESS, metavar=("PROMPT", "MASKFILE"),
+                   help="regional prompt (repeatable, up to 8): PROMPT applies where MASKFILE (an image, or a clip as for --video) is white; "
+                        "--prompt is the base prompt and holds alone where no mask reaches")
+    p.add_argument("--region_base_weight", type=float, default=argparse.SUPPRESS, metavar="W",
+                   help="with --region: weight of --prompt under the regions, in [0, 1] (default 0)")
     return p
+
+
+def region_keywords(args, load_mask=None):
+    """--region PROMPT MASKFILE (repeatable) / --region_base_weight -> the pipeline's keywords; the mask files go through --mask's resize
+    and centre-crop (`load_mask(path)` -> (height, width) or (F, height, width) in [0, 1])"""
+    if not hasattr(args, "region"):
+        if hasattr(args, "region_base_weight"):
+            raise ValueError("--region_base_weight needs --region")
+        return {}
+    w = getattr(args, "region_base_weight", 0.0)
+    if not 0.0 <= w <= 1.0:
+        raise ValueError(f"--region_base_weight must be in [0, 1] (got {w})")
+    if len(args.region) > 8:
+        raise ValueError(f"at most 8 --region arguments (got {len(args.region)})")
+    if hasattr(args, "context_seconds"):
+        raise ValueError("--region together with --context_seconds is not supported")
+    load_mask = load_mask or (lambda path: pixel_mask_file(path, args.height, args.width))
+    return {"regions": [(prompt, load_mask(path)) for prompt, path in args.region], "region_base_weight": w}
+
+
+def pixel_mask_file(path, height, width):
+    """a mask file (an image, or a clip) through the frames' own resize-and-crop rule: (height, width) or (F, height, width) in [0, 1]"""
+    from kandinsky.conditioning import preprocess_video
+    from kandinsky.video_io import read_video
+    m = (preprocess_video(read_video(path), height, width).mean(dim=1) + 1.0) / 2.0
+    return m[0] if m.shape[0] == 1 else m
 
 
 def nag_keywords(args):
@@ -150,6 +181,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     validate_args(args)
     nag_kw = nag_keywords(args)   # refused before the models load
+    region_kw = region_keywords(args)
     from kandinsky import get_T2V_pipeline
     pipe = get_T2V_pipeline(device_map={"dit": "cuda:0", "vae": "cuda:0", "text_embedder": "cuda:0"}, conf_path=args.config,
                             offload=args.offload, magcache=args.magcache and not args.calibrate_magcache,
@@ -185,6 +217,7 @@ def main(argv=None):
     edit_kw.update(preview_keywords(args))
     edit_kw.update(context_keywords(args))
     edit_kw.update(nag_kw)
+    edit_kw.update(region_kw)
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
