@@ -315,9 +315,9 @@ struct k5_dit {
   std::vector<BlockW> tblocks, vblocks;
 
   // workspaces
-  DevBuf ws_text_in, ws_text, ws_th, ws_tqk, ws_tvt, ws_to, ws_tff;
+  DevBuf ws_text_in, ws_th, ws_tqk, ws_tvt, ws_to, ws_tff;       // the text side's scratch, shared by every text stream of a forward
   DevBuf ws_pool_in, ws_pool_lin, ws_pool_f32, ws_time, ws_tfeat, ws_th1, ws_temb, ws_mod;
-  DevBuf ws_xp, ws_vis, ws_h, ws_qk, ws_vt, ws_o, ws_ff, ws_ck, ws_cvt, ws_y;
+  DevBuf ws_xp, ws_vis, ws_h, ws_qk, ws_vt, ws_o, ws_ff, ws_y;
   DevBuf ws_vcos, ws_vsin, ws_pos;
   DevBuf ws_vel_c, ws_vel_u;
   DevBuf ws_win;                                   // k5_sample_windows: the call's plan, [nwin] int32 starts then [nwin][F] fp32 weights
@@ -341,8 +341,9 @@ struct k5_dit {
   DevBuf ws_h8, ws_ff8;                            // fp8 activations of that path
   // Cross-attention keys / values of ALL visual blocks in one go (round 4, "cross_kv_batched"): they depend on the text stream only, so the 2 x
   // num_visual_blocks projections of 256 text rows (34 + 32 us each: 28-tile launches) become two GEMMs against the stacked weights
-  // [blocks * D][D] before the visual stack, the key RMSNorms one launch — same kernels on the same per-element sums: bit-identical
-  DevBuf cx_wk_all, cx_wv_all, cx_bk_all, cx_bv_all, cx_knorm_all, ws_ck_all, ws_cvt_all;
+  // [blocks * D][D] before the visual stack, the key RMSNorms one launch — same kernels on the same per-element sums: bit-identical.  Every text
+  // stream keeps the result in its own TextStream::ck_all / cvt_all
+  DevBuf cx_wk_all, cx_wv_all, cx_bk_all, cx_bv_all, cx_knorm_all;
   int cross_kv_batched = 1;
   DevBuf ws_sched;                                 // sampler tables on the device: t*1000 [steps] | dt [steps] | step counter
   bool use_graph = false;                          // k5_sample replays one captured step (k5_dit_set_graph)
@@ -452,20 +453,32 @@ struct k5_dit {
   struct TextCache { DevBuf text, pool; bool valid = false; int L = 0; } text_cache[3 + 8];   // [2]: the negative prompt of k5_dit_set_nag (text only); [3 + r]: region r of k5_dit_set_regions (likewise)
   void drop_text_cache() { for (auto& t : text_cache) t.valid = false; }
 
-  // Normalized attention guidance (k5_dit_set_nag): a second, negative text stream through the text blocks (the forward's own
-  // time embedding) and, per visual block, a second cross-attention of the same queries joined to the first by k5_launch_nag_combine.
-  // Conditional forwards only (text_slot != 1).  The buffers below exist only once a guided forward has run.
+  // What one prompt leaves behind in a forward: every prompt — the forward's own, the negative one of k5_dit_set_nag, a region's of
+  // k5_dit_set_regions — goes through the text blocks into a stream of its own (text_stream_run) and from there into every visual block's
+  // cross-attention (cross_view, run_cross_attention).  A stream's buffers are sized by its own L and exist once a forward has used it.
+  struct TextStream {
+    int L = 0;                                     // rows of the prompt that last went through
+    DevBuf text;                                   // its rows after the text blocks, [L][D]
+    DevBuf ck_all, cvt_all;                        // "cross_kv_batched": normalised keys [L][blocks * D] and V^T [blocks * D][rup(L, 8)] of all visual blocks
+    DevBuf ck, cvt;                                // otherwise: one block's keys [L][D] and V^T [D][rup(L, 8)], projected by the block itself
+    void release() { for (DevBuf* b : {&text, &ck_all, &cvt_all, &ck, &cvt}) b->release(); }
+  } streams[1 + 1 + 8];                            // [0]: the forward's own prompt (cond and uncond alike); [1]: the negative prompt; [2 + r]: region r
+  // the slot of text_cache that keeps stream k's TextEmbeddings during a k5_sample* call: stream 0 has one per CFG branch (text_slot 0 / 1)
+  TextCache* stream_cache(int k, int text_slot) { return text_slot < 0 ? nullptr : &text_cache[k == 0 ? text_slot : 1 + k]; }
+
+  // Normalized attention guidance (k5_dit_set_nag): the negative prompt is text stream 1 and, per visual block, a second
+  // cross-attention of the same queries joined to the first by k5_launch_nag_combine.  Conditional forwards only (text_slot != 1).
   struct Nag {
     bool on = false;
     const k5_text_cond* neg = nullptr;             // borrowed: valid until cleared, read at every forward
     float scale = 1.f, tau = 1.f, alpha = 0.f;
     long long combines = 0;                        // k5_launch_nag_combine launches enqueued so far (k5_dit_nag_state)
-    DevBuf text, ck_all, cvt_all, ck, cvt, o;      // the negative stream | its stacked keys / V^T | the per-block ones | its attention output [n][D]
+    DevBuf o;                                      // the negative stream's attention output [n][D]; exists once a guided forward has run
   } nag;
 
-  // Regional prompts (k5_dit_set_regions): R more text streams through the text blocks (the forward's own time embedding) and, per
-  // visual block, R more cross-attentions of the same queries; k5_launch_region_combine joins the R + 1 outputs by per-token weights in front
-  // of the out projection (and of the NAG combine, if that is set too).  Conditional forwards only.  Buffers exist once such a forward has run.
+  // Regional prompts (k5_dit_set_regions): region r's prompt is text stream 2 + r and, per visual block, one more cross-attention
+  // of the same queries; k5_launch_region_combine joins the R + 1 outputs by per-token weights in front of the out projection (and of the NAG
+  // combine, if that is set too).  Conditional forwards only.  o and w exist once such a forward has run.
   struct Regions {
     bool on = false;
     int R = 0;
@@ -474,7 +487,6 @@ struct k5_dit {
     int T = 0, H = 0, W = 0;
     float base_weight = 0.f;
     long long combines = 0;                        // k5_launch_region_combine launches enqueued so far (k5_dit_regions_state)
-    DevBuf text[8], ck_all[8], cvt_all[8], ck[8], cvt[8];   // per region, as Nag's
     DevBuf o;                                      // the regions' attention outputs, [R][n][D]
     DevBuf w; int w_order = -1;                    // token weights [N][R + 1] of this region set; -1: not computed, 0: row-major tokens, 1: NABLA's perm order
   } regions;
@@ -1315,57 +1327,50 @@ int run_self_attention_heads(k5_dit* d, hipStream_t s, const AttnW& a, const voi
   return attn_out_projection(d, s, a, o, rows, resid, gate);
 }
 
-// keys and V^T of every visual block's cross-attention from the text stream (k5_dit::cross_kv_batched): ws_ck_all [L][blocks * D] (normalised
-// keys), ws_cvt_all [blocks * D][rup(L, 8)].  The key projection is the launch it was per block (128 x 128 tiles for 256 rows); the V^T one is forced
+// keys and V^T of every visual block's cross-attention from a text stream (k5_dit::cross_kv_batched): st.ck_all [L][blocks * D] (normalised
+// keys), st.cvt_all [blocks * D][rup(L, 8)].  The key projection is the launch it was per block (128 x 128 tiles for 256 rows); the V^T one is forced
 // onto the same 128 x 128 kernel the per-block call took (57 344 weight rows would otherwise pick a 256-row kernel: another summation order).
-// ck_all / cvt_all: where they go (the negative stream of k5_dit_set_nag has a pair of its own)
-int cross_kv_batched_run(k5_dit* d, hipStream_t s, const void* text, int L, DevBuf& ck_all, DevBuf& cvt_all) {
-  const int D = d->D, H = d->Hh, nbv = (int)d->vblocks.size();
+int cross_kv_batched_run(k5_dit* d, hipStream_t s, k5_dit::TextStream& st) {
+  const int D = d->D, H = d->Hh, nbv = (int)d->vblocks.size(), L = st.L;
   const int ldvt = (int)rup(L, 8);
-  K5CHK(ck_all.ensure((size_t)L * nbv * D * 2)); K5CHK(cvt_all.ensure((size_t)nbv * D * ldvt * 2));
+  K5CHK(st.ck_all.ensure((size_t)L * nbv * D * 2)); K5CHK(st.cvt_all.ensure((size_t)nbv * D * ldvt * 2));
   {
     Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(text, d->cx_wk_all.p, d->cx_bk_all.as<float>(), ck_all.p, L, nbv * D, D, D, D, nbv * D, K5_EPI_BIAS, nullptr, 0, nullptr, s, 2));
-    K5CHK(k5_launch_gemm_bf16(d->cx_wv_all.p, text, d->cx_bv_all.as<float>(), cvt_all.p, nbv * D, L, D, D, D, ldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s, 2));
+    K5CHK(k5_launch_gemm_bf16(st.text.p, d->cx_wk_all.p, d->cx_bk_all.as<float>(), st.ck_all.p, L, nbv * D, D, D, D, nbv * D, K5_EPI_BIAS, nullptr, 0, nullptr, s, 2));
+    K5CHK(k5_launch_gemm_bf16(d->cx_wv_all.p, st.text.p, d->cx_bv_all.as<float>(), st.cvt_all.p, nbv * D, L, D, D, D, ldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s, 2));
   }
   Scope sc(d, s, "elementwise");
   const int32_t hc[2] = {H, 0};   // one norm weight per block's H heads, no RoPE
-  return k5_launch_rmsnorm_rope(ck_all.p, d->cx_knorm_all.as<float>(), nullptr, nullptr, L, nbv * H, nbv * D, hc, s);
+  return k5_launch_rmsnorm_rope(st.ck_all.p, d->cx_knorm_all.as<float>(), nullptr, nullptr, L, nbv * H, nbv * D, hc, s);
 }
 
-// the negative side of a guided cross-attention (k5_dit_set_nag): its text stream, where its keys / V^T are or go, and its output rows
-struct NagCross { const void* text; int L; void* ck; void* cvt; int ldck; void* o; };
-// the region streams of a cross-attention (k5_dit_set_regions): one NagCross each (o = o0 + r * o_stride elements) and this rank's token weights
-struct RegionCross { int R; NagCross r[8]; const void* o0; long long o_stride; const float* w; };
+// One text stream as a visual block's cross-attention sees it: its rows, where the block's normalised keys (row stride ldck) and V^T (row
+// stride ldvt) are or go, and the rows its attention output goes to
+struct CrossView { const void* text; int L; void* ck; void* cvt; int ldck, ldvt; void* o; };
+// the view of stream st for visual block i.  stacked: what cross_kv_batched_run left (this is the only reader of that layout); otherwise the
+// stream's per-block buffers, which run_cross_attention fills
+CrossView cross_view(const k5_dit* d, const k5_dit::TextStream& st, int i, bool stacked, void* o) {
+  const int D = d->D, nbv = (int)d->vblocks.size(), ldvt = (int)rup(st.L, 8);
+  if (!stacked) return CrossView{st.text.p, st.L, st.ck.p, st.cvt.p, D, ldvt, o};
+  return CrossView{st.text.p, st.L, st.ck_all.as<bf16_t>() + (size_t)i * D, st.cvt_all.as<bf16_t>() + (size_t)i * D * ldvt, nbv * D, ldvt, o};
+}
+// The streams of one cross-attention, in launch order: v[0] the forward's own prompt (its o receives the result), then the negative prompt if
+// nag, then (last) R regions, whose outputs lie region_o_stride elements apart and are weighed per token by region_w [rows][R + 1]
+struct CrossStreams { CrossView v[1 + 1 + 8]; int n = 0; bool kv_ready = false, nag = false; int R = 0; long long region_o_stride = 0; const float* region_w = nullptr; };
 
-
-// kv_ready: ck (row stride ldck) / cvt already hold this block's normalised keys and V^T (cross_kv_batched_run)
-// nag: attend the same queries to the negative stream as well and join the two outputs (k5_launch_nag_combine, in place on o) in front of
-// the out projection; with kv_ready its keys / V^T are ready too
-// reg: attend the same queries to every region stream as well; k5_launch_region_combine (in place on o) makes o the positive side before the
-// NAG combine, if any
-int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, int rows, const void* text,
-                        int L, void* q, void* ck, void* cvt, void* o, void* resid, const float* gate, bool kv_ready = false, int ldck = 0,
-                        const NagCross* nag = nullptr, const RegionCross* reg = nullptr) {
+// The same queries (h through wq, into q) against every stream of cx.  kv_ready: the views already hold this block's normalised keys and V^T
+// (cross_kv_batched_run); otherwise they are projected and normalised here.  k5_launch_region_combine (in place on v[0].o) makes the positive
+// side of the regions' outputs, k5_launch_nag_combine (likewise) joins it to the negative stream's, in front of the out projection.
+int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, int rows, void* q, const CrossStreams& cx, void* resid, const float* gate) {
   const int D = d->D, H = d->Hh;
-  const int ldvt = (int)rup(L, 8);
-  if (!kv_ready) ldck = D;
-  const int nldvt = nag ? (int)rup(nag->L, 8) : 0, nldck = nag ? (kv_ready ? nag->ldck : D) : 0;
+  void* o = cx.v[0].o;
   {
     Scope sc(d, s, "gemm");
     K5CHK(k5_launch_gemm_bf16(h, a.wq.p, a.bq.as<float>(), q, rows, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-    if (!kv_ready) {
-      K5CHK(k5_launch_gemm_bf16(text, a.wk.p, a.bk.as<float>(), ck, L, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-      K5CHK(k5_launch_gemm_bf16(a.wv.p, text, a.bv.as<float>(), cvt, D, L, D, D, D, ldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
-      if (nag) {
-        K5CHK(k5_launch_gemm_bf16(nag->text, a.wk.p, a.bk.as<float>(), nag->ck, nag->L, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-        K5CHK(k5_launch_gemm_bf16(a.wv.p, nag->text, a.bv.as<float>(), nag->cvt, D, nag->L, D, D, D, nldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
-      }
-      for (int r = 0; reg && r < reg->R; ++r) {
-        const NagCross& x = reg->r[r];
-        K5CHK(k5_launch_gemm_bf16(x.text, a.wk.p, a.bk.as<float>(), x.ck, x.L, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-        K5CHK(k5_launch_gemm_bf16(a.wv.p, x.text, a.bv.as<float>(), x.cvt, D, x.L, D, D, D, (int)rup(x.L, 8), K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
-      }
+    for (int k = 0; !cx.kv_ready && k < cx.n; ++k) {
+      const CrossView& v = cx.v[k];
+      K5CHK(k5_launch_gemm_bf16(v.text, a.wk.p, a.bk.as<float>(), v.ck, v.L, D, D, D, D, v.ldck, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+      K5CHK(k5_launch_gemm_bf16(a.wv.p, v.text, a.bv.as<float>(), v.cvt, D, v.L, D, D, D, v.ldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
     }
   }
   // RMSNorm of the queries (no RoPE in cross-attention, nn.py:330-334) is fused into the attention kernel's Q-fragment load when the
@@ -1374,40 +1379,31 @@ int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h,
   {
     Scope sc(d, s, "elementwise");
     if (!fuse_qnorm) K5CHK(k5_launch_rmsnorm_rope(q, a.norm.as<float>(), nullptr, nullptr, rows, H, D, nullptr, s));
-    if (!kv_ready) K5CHK(k5_launch_rmsnorm_rope(ck, a.norm.as<float>() + 64, nullptr, nullptr, L, H, D, nullptr, s));
-    if (!kv_ready && nag) K5CHK(k5_launch_rmsnorm_rope(nag->ck, a.norm.as<float>() + 64, nullptr, nullptr, nag->L, H, D, nullptr, s));
-    for (int r = 0; !kv_ready && reg && r < reg->R; ++r)
-      K5CHK(k5_launch_rmsnorm_rope(reg->r[r].ck, a.norm.as<float>() + 64, nullptr, nullptr, reg->r[r].L, H, D, nullptr, s));
+    for (int k = 0; !cx.kv_ready && k < cx.n; ++k)
+      K5CHK(k5_launch_rmsnorm_rope(cx.v[k].ck, a.norm.as<float>() + 64, nullptr, nullptr, cx.v[k].L, H, cx.v[k].ldck, nullptr, s));
   }
   {
     Scope sc(d, s, "attn_cross");
     const K5QueryNorm qn{a.norm.as<float>(), nullptr, nullptr, nullptr};
     K5AttnRangeArgs at;
-    at.Q = q; at.K = ck; at.Vt = cvt; at.O = o;
-    at.H = H; at.q_len = rows; at.kv_len = L; at.ldq = D; at.ldk = ldck; at.ldvt = ldvt; at.ldo = D;
+    at.Q = q; at.H = H; at.q_len = rows; at.ldq = D; at.ldo = D;
     at.score_bound = a.score_bound; at.stream = s;
     at.query_norm = fuse_qnorm ? &qn : nullptr;
-    K5CHK(k5_launch_attention_bf16_range(at));
-    if (nag) {   // the same (normalised or to-be-normalised) queries against the negative stream
-      at.K = nag->ck; at.Vt = nag->cvt; at.O = nag->o;
-      at.kv_len = nag->L; at.ldk = nldck; at.ldvt = nldvt;
-      K5CHK(k5_launch_attention_bf16_range(at));
-    }
-    for (int r = 0; reg && r < reg->R; ++r) {   // ... and against every region stream
-      const NagCross& x = reg->r[r];
-      at.K = x.ck; at.Vt = x.cvt; at.O = x.o;
-      at.kv_len = x.L; at.ldk = kv_ready ? x.ldck : D; at.ldvt = (int)rup(x.L, 8);
+    for (int k = 0; k < cx.n; ++k) {   // the same (normalised or to-be-normalised) queries against every stream
+      const CrossView& v = cx.v[k];
+      at.K = v.ck; at.Vt = v.cvt; at.O = v.o;
+      at.kv_len = v.L; at.ldk = v.ldck; at.ldvt = v.ldvt;
       K5CHK(k5_launch_attention_bf16_range(at));
     }
   }
-  if (reg) {
+  if (cx.R) {
     Scope sc(d, s, "elementwise");
-    K5CHK(k5_launch_region_combine(o, reg->o0, reg->o_stride, reg->R, reg->w, reg->R + 1, o, rows, D, D, s));
+    K5CHK(k5_launch_region_combine(o, cx.v[cx.n - cx.R].o, cx.region_o_stride, cx.R, cx.region_w, cx.R + 1, o, rows, D, D, s));
     ++d->regions.combines;
   }
-  if (nag) {
+  if (cx.nag) {
     Scope sc(d, s, "elementwise");
-    K5CHK(k5_launch_nag_combine(o, nag->o, o, rows, D, D, d->nag.scale, d->nag.tau, d->nag.alpha, s));
+    K5CHK(k5_launch_nag_combine(o, cx.v[1].o, o, rows, D, D, d->nag.scale, d->nag.tau, d->nag.alpha, s));
     ++d->nag.combines;
   }
   return attn_out_projection(d, s, a, o, rows, resid, gate);
@@ -1456,18 +1452,19 @@ int ln_mod(k5_dit* d, hipStream_t s, const void* x, const float* mod3, void* out
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
+// N visual tokens; L: the longest prompt of the forward, which sizes the text side's shared scratch (a text stream sizes what it keeps itself)
 int ensure_workspaces(k5_dit* d, int N, int L) {
   const size_t D = d->D, FF = d->FF;
   const size_t Lr = rup(L, 8), Nr = rup(N, 8);
   K5CHK(d->ws_text_in.ensure((size_t)L * d->cfg.in_text_dim * 2));
-  K5CHK(d->ws_text.ensure(L * D * 2)); K5CHK(d->ws_th.ensure(L * D * 2)); K5CHK(d->ws_tqk.ensure(L * 2 * D * 2));
+  K5CHK(d->ws_th.ensure(L * D * 2)); K5CHK(d->ws_tqk.ensure(L * 2 * D * 2));
   K5CHK(d->ws_tvt.ensure(D * Lr * 2)); K5CHK(d->ws_to.ensure(L * D * 2)); K5CHK(d->ws_tff.ensure(L * FF * 2));
   K5CHK(d->ws_pool_in.ensure((size_t)rup(d->cfg.in_text_dim2, 8) * 2)); K5CHK(d->ws_pool_lin.ensure(d->TD * 2));
   K5CHK(d->ws_pool_f32.ensure(d->TD * 4)); K5CHK(d->ws_time.ensure(16)); K5CHK(d->ws_tfeat.ensure(D * 4));
   K5CHK(d->ws_th1.ensure(d->TD * 4)); K5CHK(d->ws_temb.ensure(d->TD * 4)); K5CHK(d->ws_mod.ensure(d->mod_rows * 4));
   K5CHK(d->ws_xp.ensure((size_t)N * d->KvisPad * 2)); K5CHK(d->ws_vis.ensure(N * D * 2)); K5CHK(d->ws_h.ensure(N * D * 2));
   K5CHK(d->ws_qk.ensure((size_t)N * 2 * D * 2)); K5CHK(d->ws_vt.ensure(D * Nr * 2)); K5CHK(d->ws_o.ensure(N * D * 2));
-  K5CHK(d->ws_ff.ensure((size_t)N * FF * 2)); K5CHK(d->ws_ck.ensure(L * D * 2)); K5CHK(d->ws_cvt.ensure(D * Lr * 2));
+  K5CHK(d->ws_ff.ensure((size_t)N * FF * 2));
   K5CHK(d->ws_y.ensure((size_t)N * d->Fout * 2));
   K5CHK(d->ws_vcos.ensure((size_t)N * 32 * 4)); K5CHK(d->ws_vsin.ensure((size_t)N * 32 * 4));
   return K5_OK;
@@ -1679,6 +1676,73 @@ int sp_schedule(const k5_dit* d, bool nabla) {
   return 0;
 }
 
+// ---- a prompt's way through the text side of a forward, in three parts: text_stream_run is all of them ----
+// TextEmbeddings of prompt c into st.text (dit.py:132), inside the caller's "prologue" bracket; pooled: with its pooled projection into
+// ws_pool_f32 (dit.py:134).  tc: restored from there if it holds this prompt, otherwise left there for the later steps of the k5_sample* call
+int text_embeddings(k5_dit* d, hipStream_t s, const k5_text_cond& c, k5_dit::TextStream& st, k5_dit::TextCache* tc, bool pooled) {
+  const k5_dit_config& cfg = d->cfg;
+  const int L = st.L = c.text_len, D = d->D;
+  K5CHK(st.text.ensure((size_t)L * D * 2));
+  if (tc && tc->valid && tc->L == L) {   // the text blocks update st.text in place: restore their input
+    HIPCHK(hipMemcpyAsync(st.text.p, tc->text.p, (size_t)L * D * 2, hipMemcpyDeviceToDevice, s));
+    if (pooled) HIPCHK(hipMemcpyAsync(d->ws_pool_f32.p, tc->pool.p, (size_t)d->TD * 4, hipMemcpyDeviceToDevice, s));
+    return K5_OK;
+  }
+  const void* text_bf; const void* pool_bf;
+  K5CHK(to_bf16(d, s, c.text_embed, c.text_dtype, (size_t)L * cfg.in_text_dim, d->ws_text_in, &text_bf));
+  if (pooled) K5CHK(to_bf16(d, s, c.pooled_embed, c.text_dtype, (size_t)cfg.in_text_dim2, d->ws_pool_in, &pool_bf));
+  K5CHK(k5_launch_gemm_bf16(text_bf, d->text_w.p, d->text_b.as<float>(), d->ws_th.p, L, D, cfg.in_text_dim, cfg.in_text_dim,
+                            cfg.in_text_dim, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+  K5CHK(k5_launch_ln_affine(d->ws_th.p, d->text_lnw.as<float>(), d->text_lnb.as<float>(), st.text.p, nullptr, L, D, s));
+  if (pooled) {
+    K5CHK(k5_launch_gemm_bf16(pool_bf, d->pool_w.p, d->pool_b.as<float>(), d->ws_pool_lin.p, 1, d->TD, cfg.in_text_dim2,
+                              cfg.in_text_dim2, cfg.in_text_dim2, d->TD, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+    K5CHK(k5_launch_ln_affine(d->ws_pool_lin.p, d->pool_lnw.as<float>(), d->pool_lnb.as<float>(), nullptr,
+                              d->ws_pool_f32.as<float>(), 1, d->TD, s));
+  }
+  if (tc) {
+    K5CHK(tc->text.ensure((size_t)L * D * 2));
+    if (pooled) K5CHK(tc->pool.ensure((size_t)d->TD * 4));
+    HIPCHK(hipMemcpyAsync(tc->text.p, st.text.p, (size_t)L * D * 2, hipMemcpyDeviceToDevice, s));
+    if (pooled) HIPCHK(hipMemcpyAsync(tc->pool.p, d->ws_pool_f32.p, (size_t)d->TD * 4, hipMemcpyDeviceToDevice, s));
+    tc->valid = true; tc->L = L;
+  }
+  return K5_OK;
+}
+
+// the text blocks on st.text, in place (dit.py:170-171, 33-44); mod: the forward's modulation, whichever stream runs
+int text_blocks_run(k5_dit* d, hipStream_t s, k5_dit::TextStream& st, const float* tcos, const float* tsin, const float* mod) {
+  const int D = d->D, L = st.L;
+  for (const BlockW& b : d->tblocks) {
+    const float* m = mod + b.mod_off;
+    K5CHK(ln_mod(d, s, st.text.p, m, d->ws_th.p, L));
+    K5CHK(run_self_attention(d, s, b.self_attn, d->ws_th.p, L, d->ws_tqk.p, d->ws_tvt.p, d->ws_to.p, tcos, tsin, st.text.p, m + 2 * D, "attn_text"));
+    K5CHK(ln_mod(d, s, st.text.p, m + 3 * D, d->ws_th.p, L));
+    K5CHK(run_ff(d, s, b, d->ws_th.p, L, d->ws_tff.p, st.text.p, m + 5 * D));
+  }
+  return K5_OK;
+}
+
+// what the visual blocks' cross-attention needs of st: stacked, the keys / V^T of all blocks now; otherwise room for one block's
+int text_cross_kv(k5_dit* d, hipStream_t s, k5_dit::TextStream& st, bool stacked) {
+  if (stacked) return cross_kv_batched_run(d, s, st);
+  K5CHK(st.ck.ensure((size_t)st.L * d->D * 2));
+  return st.cvt.ensure((size_t)d->D * rup(st.L, 8) * 2);
+}
+
+// all of it for a prompt whose stream has nothing else in its prologue: its own RoPE positions, THIS forward's modulation (one time embedding
+// per forward: that of the forward's own pooled embedding)
+int text_stream_run(k5_dit* d, hipStream_t s, const k5_text_cond& c, k5_dit::TextStream& st, k5_dit::TextCache* tc, const float* mod, bool stacked) {
+  const float *tcos = nullptr, *tsin = nullptr;
+  K5CHK(prepare_text_rope(d, s, c, &tcos, &tsin));
+  {
+    Scope sc(d, s, "prologue");
+    K5CHK(text_embeddings(d, s, c, st, tc, false));
+  }
+  K5CHK(text_blocks_run(d, s, st, tcos, tsin, mod));
+  return text_cross_kv(d, s, st, stacked);
+}
+
 int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, float time, const float* x,
                  int x_channels, void* out_velocity, hipStream_t s, const float* tvec = nullptr, const int* step = nullptr,
                  int text_slot = -1, const float* vcond = nullptr) {
@@ -1728,7 +1792,6 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   }
   // normalized attention guidance: the conditional branch only (slot 1 is the unconditional forward of k5_sample*)
   const k5_text_cond* ncond = d->nag.on && text_slot != 1 ? d->nag.neg : nullptr;
-  const int Ln = ncond ? ncond->text_len : 0;
   // regional prompts: the same branch; a forward of another shape than the masks' is refused before anything is enqueued
   auto& rg = d->regions;
   if (rg.on && (a->T != rg.T || a->H != rg.H || a->W != rg.W)) {
@@ -1736,7 +1799,7 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     return K5_ERR_ARG;
   }
   const int Rg = rg.on && text_slot != 1 ? rg.R : 0;
-  int Lmax = Ln > L ? Ln : L;   // the extra streams borrow the text blocks' scratch: size it by the longest
+  int Lmax = ncond && ncond->text_len > L ? ncond->text_len : L;   // every stream borrows the text blocks' scratch: size it by the longest
   for (int r = 0; r < Rg; ++r) Lmax = rg.conds[r].text_len > Lmax ? rg.conds[r].text_len : Lmax;
   K5CHK(ensure_workspaces(d, sp ? P * n_pad : N, Lmax));
   if (sp) {
@@ -1769,31 +1832,11 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   K5CHK(prepare_text_rope(d, s, cond, &tcos, &tsin));
 
   const float* mod = d->ws_mod.as<float>();
+  k5_dit::TextStream& base = d->streams[0];
   // ---- before_text_transformer_blocks (dit.py:129-137) ----
   {
     Scope sc(d, s, "prologue");
-    k5_dit::TextCache* tc = text_slot >= 0 ? &d->text_cache[text_slot] : nullptr;
-    if (tc && tc->valid && tc->L == L) {   // the text blocks update ws_text in place: restore their input
-      HIPCHK(hipMemcpyAsync(d->ws_text.p, tc->text.p, (size_t)L * D * 2, hipMemcpyDeviceToDevice, s));
-      HIPCHK(hipMemcpyAsync(d->ws_pool_f32.p, tc->pool.p, (size_t)d->TD * 4, hipMemcpyDeviceToDevice, s));
-    } else {
-      const void* text_bf; const void* pool_bf;
-      K5CHK(to_bf16(d, s, cond.text_embed, cond.text_dtype, (size_t)L * c.in_text_dim, d->ws_text_in, &text_bf));
-      K5CHK(to_bf16(d, s, cond.pooled_embed, cond.text_dtype, (size_t)c.in_text_dim2, d->ws_pool_in, &pool_bf));
-      K5CHK(k5_launch_gemm_bf16(text_bf, d->text_w.p, d->text_b.as<float>(), d->ws_th.p, L, D, c.in_text_dim, c.in_text_dim,
-                                c.in_text_dim, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-      K5CHK(k5_launch_ln_affine(d->ws_th.p, d->text_lnw.as<float>(), d->text_lnb.as<float>(), d->ws_text.p, nullptr, L, D, s));
-      K5CHK(k5_launch_gemm_bf16(pool_bf, d->pool_w.p, d->pool_b.as<float>(), d->ws_pool_lin.p, 1, d->TD, c.in_text_dim2,
-                                c.in_text_dim2, c.in_text_dim2, d->TD, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-      K5CHK(k5_launch_ln_affine(d->ws_pool_lin.p, d->pool_lnw.as<float>(), d->pool_lnb.as<float>(), nullptr,
-                                d->ws_pool_f32.as<float>(), 1, d->TD, s));
-      if (tc) {
-        K5CHK(tc->text.ensure((size_t)L * D * 2)); K5CHK(tc->pool.ensure((size_t)d->TD * 4));
-        HIPCHK(hipMemcpyAsync(tc->text.p, d->ws_text.p, (size_t)L * D * 2, hipMemcpyDeviceToDevice, s));
-        HIPCHK(hipMemcpyAsync(tc->pool.p, d->ws_pool_f32.p, (size_t)d->TD * 4, hipMemcpyDeviceToDevice, s));
-        tc->valid = true; tc->L = L;
-      }
-    }
+    K5CHK(text_embeddings(d, s, cond, base, d->stream_cache(0, text_slot), true));
     K5CHK(k5_launch_time_features(time, d->ws_tfeat.as<float>(), D, s, tvec, step));
     K5CHK(k5_launch_gemv_f32(d->ws_tfeat.as<float>(), d->time_w1.as<float>(), d->time_b1.as<float>(), d->ws_th1.as<float>(),
                              d->TD, D, 0, nullptr, s));
@@ -1807,15 +1850,7 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     K5CHK(k5_launch_gemm_bf16(d->ws_xp.as<bf16_t>() + (size_t)tok0 * d->KvisPad, d->vis_w.p, d->vis_b.as<float>(), d->ws_vis.p,
                               n, D, d->KvisPad, d->KvisPad, d->KvisPad, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
   }
-  // ---- text blocks (dit.py:170-171, 33-44) ----
-  for (int i = 0; i < c.num_text_blocks; ++i) {
-    const BlockW& b = d->tblocks[i];
-    const float* m = mod + b.mod_off;
-    K5CHK(ln_mod(d, s, d->ws_text.p, m, d->ws_th.p, L));
-    K5CHK(run_self_attention(d, s, b.self_attn, d->ws_th.p, L, d->ws_tqk.p, d->ws_tvt.p, d->ws_to.p, tcos, tsin, d->ws_text.p, m + 2 * D, "attn_text"));
-    K5CHK(ln_mod(d, s, d->ws_text.p, m + 3 * D, d->ws_th.p, L));
-    K5CHK(run_ff(d, s, b, d->ws_th.p, L, d->ws_tff.p, d->ws_text.p, m + 5 * D));
-  }
+  K5CHK(text_blocks_run(d, s, base, tcos, tsin, mod));
   // ---- MagCache decision (magcache_utils.py:59-76), float64 like the reference's numpy scalars ----
   auto& mg = d->mag;
   bool mag_skip = false;
@@ -1849,60 +1884,27 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   }
   // ---- visual blocks (dit.py:176-178, 61-79) ----
   const bool cx_all = !mag_skip && d->cross_kv_batched && c.num_visual_blocks > 1 && d->cx_wk_all.p;
-  if (cx_all) K5CHK(cross_kv_batched_run(d, s, d->ws_text.p, L, d->ws_ck_all, d->ws_cvt_all));
-  const int Lr8 = (int)rup(L, 8);
-  // ---- the negative text stream of k5_dit_set_nag: prologue and text blocks as above, with its own RoPE positions and THIS forward's
-  // modulation (one time embedding per forward: the positive prompt's pooled embedding); nothing of it on a step MagCache skips ----
-  const bool nag = ncond && !mag_skip && c.num_visual_blocks > 0;
-  const int Lnr8 = (int)rup(Ln, 8);
-  // one more text stream (the negative prompt, a region's): `text` receives what ws_text holds for the forward's own prompt; `cache`: the
-  // slot of text_cache that keeps its prologue for the k5_sample* call
-  auto extra_text_stream = [&](const k5_text_cond& xc, DevBuf& text, int cache, DevBuf& ck_all, DevBuf& cvt_all, DevBuf& ck, DevBuf& cvt) -> int {
-    const int Lx = xc.text_len;
-    const float *xcos = nullptr, *xsin = nullptr;
-    K5CHK(prepare_text_rope(d, s, xc, &xcos, &xsin));
-    K5CHK(text.ensure((size_t)Lx * D * 2));
-    {
-      Scope sc(d, s, "prologue");
-      k5_dit::TextCache* tc = text_slot >= 0 ? &d->text_cache[cache] : nullptr;
-      if (tc && tc->valid && tc->L == Lx) {
-        HIPCHK(hipMemcpyAsync(text.p, tc->text.p, (size_t)Lx * D * 2, hipMemcpyDeviceToDevice, s));
-      } else {
-        const void* text_bf;
-        K5CHK(to_bf16(d, s, xc.text_embed, xc.text_dtype, (size_t)Lx * c.in_text_dim, d->ws_text_in, &text_bf));
-        K5CHK(k5_launch_gemm_bf16(text_bf, d->text_w.p, d->text_b.as<float>(), d->ws_th.p, Lx, D, c.in_text_dim, c.in_text_dim,
-                                  c.in_text_dim, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-        K5CHK(k5_launch_ln_affine(d->ws_th.p, d->text_lnw.as<float>(), d->text_lnb.as<float>(), text.p, nullptr, Lx, D, s));
-        if (tc) {
-          K5CHK(tc->text.ensure((size_t)Lx * D * 2));
-          HIPCHK(hipMemcpyAsync(tc->text.p, text.p, (size_t)Lx * D * 2, hipMemcpyDeviceToDevice, s));
-          tc->valid = true; tc->L = Lx;
-        }
-      }
+  if (!mag_skip) K5CHK(text_cross_kv(d, s, base, cx_all));
+  // ---- the text streams of this forward's cross-attentions, in launch order, and where each one's attention output goes: the forward's own
+  // prompt, then the negative one of k5_dit_set_nag, then the regions' of k5_dit_set_regions; nothing but the first on a step MagCache skips ----
+  struct { const k5_text_cond* cond; int stream; void* o; } act[1 + 1 + 8] = {{&cond, 0, d->ws_o.p}};   // stream: its index in k5_dit::streams
+  CrossStreams cx;
+  cx.n = 1; cx.kv_ready = cx_all;
+  if (!mag_skip && c.num_visual_blocks > 0) {
+    if (ncond) {
+      K5CHK(d->nag.o.ensure((size_t)n * D * 2));
+      act[cx.n++] = {ncond, 1, d->nag.o.p};
+      cx.nag = true;
     }
-    for (int i = 0; i < c.num_text_blocks; ++i) {
-      const BlockW& b = d->tblocks[i];
-      const float* m = mod + b.mod_off;
-      K5CHK(ln_mod(d, s, text.p, m, d->ws_th.p, Lx));
-      K5CHK(run_self_attention(d, s, b.self_attn, d->ws_th.p, Lx, d->ws_tqk.p, d->ws_tvt.p, d->ws_to.p, xcos, xsin, text.p, m + 2 * D, "attn_text"));
-      K5CHK(ln_mod(d, s, text.p, m + 3 * D, d->ws_th.p, Lx));
-      K5CHK(run_ff(d, s, b, d->ws_th.p, Lx, d->ws_tff.p, text.p, m + 5 * D));
-    }
-    if (cx_all) K5CHK(cross_kv_batched_run(d, s, text.p, Lx, ck_all, cvt_all));
-    else { K5CHK(ck.ensure((size_t)Lx * D * 2)); K5CHK(cvt.ensure((size_t)D * rup(Lx, 8) * 2)); }
-    return K5_OK;
-  };
-  if (nag) {
-    auto& ng = d->nag;
-    K5CHK(ng.o.ensure((size_t)n * D * 2));
-    K5CHK(extra_text_stream(*ncond, ng.text, 2, ng.ck_all, ng.cvt_all, ng.ck, ng.cvt));
+    if (Rg) K5CHK(rg.o.ensure((size_t)Rg * n * D * 2));
+    for (int r = 0; r < Rg; ++r) act[cx.n++] = {&rg.conds[r], 2 + r, rg.o.as<bf16_t>() + (size_t)r * n * D};
+    cx.R = Rg; cx.region_o_stride = (long long)n * D;
   }
-  // ---- the region streams of k5_dit_set_regions, likewise, and the token weights in this forward's token order (computed once per region
-  // set and order; a sequence-parallel rank reads its rows from tok0 on) ----
-  const bool regional = Rg > 0 && !mag_skip && c.num_visual_blocks > 0;
-  if (regional) {
-    K5CHK(rg.o.ensure((size_t)Rg * n * D * 2));
-    for (int r = 0; r < Rg; ++r) K5CHK(extra_text_stream(rg.conds[r], rg.text[r], 3 + r, rg.ck_all[r], rg.cvt_all[r], rg.ck[r], rg.cvt[r]));
+  for (int k = 1; k < cx.n; ++k)
+    K5CHK(text_stream_run(d, s, *act[k].cond, d->streams[act[k].stream], d->stream_cache(act[k].stream, text_slot), mod, cx_all));
+  // the regions' token weights in this forward's token order (computed once per region set and order; a sequence-parallel rank reads its rows
+  // from tok0 on)
+  if (cx.R) {
     if (rg.w_order != (nabla ? 1 : 0)) {
       Scope sc(d, s, "elementwise");
       K5CHK(rg.w.ensure((size_t)N * (Rg + 1) * 4));
@@ -1910,6 +1912,7 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
                                      rg.w.as<float>(), s));
       rg.w_order = nabla ? 1 : 0;
     }
+    cx.region_w = rg.w.as<float>() + (size_t)tok0 * (Rg + 1);
   }
   const int sched = sp ? sp_schedule(d, nabla) : 0;
   if (sp) d->sp_mode_used = sched;
@@ -1932,29 +1935,8 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
                                m + 2 * D, "attn_self", nabla ? &na : nullptr, text_slot > 0 ? 1 : 0, h8_sa));
     }
     K5CHK(ln_mod(d, s, d->ws_vis.p, m + 3 * D, d->ws_h.p, n));
-    NagCross nx{};
-    if (nag) {
-      auto& ng = d->nag;
-      if (cx_all) nx = NagCross{ng.text.p, Ln, ng.ck_all.as<bf16_t>() + (size_t)i * D, ng.cvt_all.as<bf16_t>() + (size_t)i * D * Lnr8, c.num_visual_blocks * D, ng.o.p};
-      else nx = NagCross{ng.text.p, Ln, ng.ck.p, ng.cvt.p, D, ng.o.p};
-    }
-    RegionCross rx{};
-    if (regional) {
-      rx.R = Rg; rx.o0 = rg.o.p; rx.o_stride = (long long)n * D; rx.w = rg.w.as<float>() + (size_t)tok0 * (Rg + 1);
-      for (int r = 0; r < Rg; ++r) {
-        const int Lx = rg.conds[r].text_len;
-        void* o_r = rg.o.as<bf16_t>() + (size_t)r * n * D;
-        if (cx_all) rx.r[r] = NagCross{rg.text[r].p, Lx, rg.ck_all[r].as<bf16_t>() + (size_t)i * D, rg.cvt_all[r].as<bf16_t>() + (size_t)i * D * rup(Lx, 8), c.num_visual_blocks * D, o_r};
-        else rx.r[r] = NagCross{rg.text[r].p, Lx, rg.ck[r].p, rg.cvt[r].p, D, o_r};
-      }
-    }
-    if (cx_all)
-      K5CHK(run_cross_attention(d, s, b.cross_attn, d->ws_h.p, n, d->ws_text.p, L, d->ws_qk.p, d->ws_ck_all.as<bf16_t>() + (size_t)i * D,
-                                d->ws_cvt_all.as<bf16_t>() + (size_t)i * D * Lr8, d->ws_o.p, d->ws_vis.p, m + 5 * D, true, c.num_visual_blocks * D,
-                                nag ? &nx : nullptr, regional ? &rx : nullptr));
-    else
-      K5CHK(run_cross_attention(d, s, b.cross_attn, d->ws_h.p, n, d->ws_text.p, L, d->ws_qk.p, d->ws_ck.p, d->ws_cvt.p,
-                                d->ws_o.p, d->ws_vis.p, m + 5 * D, false, 0, nag ? &nx : nullptr, regional ? &rx : nullptr));
+    for (int k = 0; k < cx.n; ++k) cx.v[k] = cross_view(d, d->streams[act[k].stream], i, cx_all, act[k].o);
+    K5CHK(run_cross_attention(d, s, b.cross_attn, d->ws_h.p, n, d->ws_qk.p, cx, d->ws_vis.p, m + 5 * D));
     const bool h8_ff = d->fp8_fuse_ln && ff_fp8_in(d, b, n);
     K5CHK(ln_mod(d, s, d->ws_vis.p, m + 6 * D, d->ws_h.p, n, h8_ff));
     K5CHK(run_ff(d, s, b, d->ws_h.p, n, d->ws_ff.p, d->ws_vis.p, m + 8 * D, h8_ff));
@@ -2026,10 +2008,10 @@ extern "C" void k5_dit_destroy(k5_dit* d) {
   // DevBufs are released with the process; explicit frees for long-lived hosts:
   DevBuf* all[] = {&d->time_w1, &d->time_b1, &d->time_w2, &d->time_b2, &d->text_w, &d->text_b, &d->text_lnw, &d->text_lnb,
                    &d->pool_w, &d->pool_b, &d->pool_lnw, &d->pool_lnb, &d->vis_w, &d->vis_b, &d->out_w, &d->out_b, &d->mod_w,
-                   &d->mod_b, &d->ws_text_in, &d->ws_text, &d->ws_th, &d->ws_tqk, &d->ws_tvt, &d->ws_to, &d->ws_tff,
+                   &d->mod_b, &d->ws_text_in, &d->ws_th, &d->ws_tqk, &d->ws_tvt, &d->ws_to, &d->ws_tff,
                    &d->ws_pool_in, &d->ws_pool_lin, &d->ws_pool_f32, &d->ws_time, &d->ws_tfeat, &d->ws_th1, &d->ws_temb,
-                   &d->ws_mod, &d->ws_xp, &d->ws_vis, &d->ws_h, &d->ws_qk, &d->ws_vt, &d->ws_o, &d->ws_ff, &d->ws_ck,
-                   &d->ws_cvt, &d->ws_y, &d->ws_vcos, &d->ws_vsin, &d->ws_pos, &d->ws_vel_c,
+                   &d->ws_mod, &d->ws_xp, &d->ws_vis, &d->ws_h, &d->ws_qk, &d->ws_vt, &d->ws_o, &d->ws_ff,
+                   &d->ws_y, &d->ws_vcos, &d->ws_vsin, &d->ws_pos, &d->ws_vel_c,
                    &d->ws_vel_u};
   for (DevBuf* b : all) b->release();
   for (auto& e : d->text_rope) { e.cosT.release(); e.sinT.release(); e.pos.release(); }
@@ -2037,10 +2019,8 @@ extern "C" void k5_dit_destroy(k5_dit* d) {
   d->ws_attn_stats.release(); d->ws_attn_flags.release(); d->ws_attn_cnt.release(); d->ws_attn_part.release(); d->ws_leave_sig.release();
   if (d->h_leave_sig) { (void)hipHostFree(d->h_leave_sig); d->h_leave_sig = nullptr; }
   for (auto& t : d->text_cache) { t.text.release(); t.pool.release(); }
-  for (DevBuf* b : {&d->nag.text, &d->nag.ck_all, &d->nag.cvt_all, &d->nag.ck, &d->nag.cvt, &d->nag.o}) b->release();
-  for (int r = 0; r < 8; ++r)
-    for (DevBuf* b : {&d->regions.text[r], &d->regions.ck_all[r], &d->regions.cvt_all[r], &d->regions.ck[r], &d->regions.cvt[r]}) b->release();
-  d->regions.o.release(); d->regions.w.release();
+  for (auto& st : d->streams) st.release();
+  d->nag.o.release(); d->regions.o.release(); d->regions.w.release();
   for (auto& kv : d->staged) kv.second.dev.release();   // a handle destroyed before finalize still holds its staged matrices
   d->mag.residual[0].release(); d->mag.residual[1].release(); d->mag.pm_one.release();
   for (auto& b : d->vblocks) { b.w1_f8.release(); b.w2_f8.release(); b.s1_f8.release(); b.s2_f8.release(); }
@@ -2761,6 +2741,16 @@ extern "C" int k5_dit_set_watch(k5_dit* d, const k5_watch* w) {
   return K5_OK;
 }
 
+namespace {
+// a prompt the handle borrows until it is cleared (k5_dit_set_nag, k5_dit_set_regions).  who: the refusing call; whose: the prompt in the
+// sentence about its pointers; len_of: what stands in front of "text_len" in the one about its length
+int check_borrowed_prompt(const k5_text_cond& c, const char* who, const char* whose, const char* len_of) {
+  if (c.text_len < 1) { k5_set_error("%s: %stext_len must be >= 1 (got %d)", who, len_of, c.text_len); return K5_ERR_ARG; }
+  if (!c.text_embed || !c.text_rope_pos) { k5_set_error("%s: %s needs text_embed and text_rope_pos", who, whose); return K5_ERR_ARG; }
+  return K5_OK;
+}
+}  // namespace
+
 extern "C" int k5_dit_set_nag(k5_dit* d, const k5_text_cond* negative, float scale, float tau, float alpha) {
   g_err[0] = 0;
   if (!d) { k5_set_error("k5_dit_set_nag: null handle"); return K5_ERR_ARG; }
@@ -2769,8 +2759,7 @@ extern "C" int k5_dit_set_nag(k5_dit* d, const k5_text_cond* negative, float sca
   if (!(scale >= 1.0f)) { k5_set_error("k5_dit_set_nag: scale must be >= 1 (got %g)", (double)scale); return K5_ERR_ARG; }
   if (!(tau >= 1.0f)) { k5_set_error("k5_dit_set_nag: tau must be >= 1 (got %g)", (double)tau); return K5_ERR_ARG; }
   if (!(alpha >= 0.0f && alpha <= 1.0f)) { k5_set_error("k5_dit_set_nag: alpha must be in [0, 1] (got %g)", (double)alpha); return K5_ERR_ARG; }
-  if (negative->text_len < 1) { k5_set_error("k5_dit_set_nag: text_len must be >= 1 (got %d)", negative->text_len); return K5_ERR_ARG; }
-  if (!negative->text_embed || !negative->text_rope_pos) { k5_set_error("k5_dit_set_nag: the negative prompt needs text_embed and text_rope_pos"); return K5_ERR_ARG; }
+  K5CHK(check_borrowed_prompt(*negative, "k5_dit_set_nag", "the negative prompt", ""));
   ng.neg = negative; ng.scale = scale; ng.tau = tau; ng.alpha = alpha;
   ng.on = scale != 1.0f && alpha != 0.0f;   // otherwise the combine hands z_pos through: run nothing
   d->text_cache[2].valid = false;
@@ -2796,8 +2785,9 @@ extern "C" int k5_dit_set_regions(k5_dit* d, const k5_text_cond* regions, int R,
     return K5_ERR_ARG;
   }
   for (int r = 0; r < R; ++r) {
-    if (regions[r].text_len < 1) { k5_set_error("k5_dit_set_regions: region %d: text_len must be >= 1 (got %d)", r, regions[r].text_len); return K5_ERR_ARG; }
-    if (!regions[r].text_embed || !regions[r].text_rope_pos) { k5_set_error("k5_dit_set_regions: region %d needs text_embed and text_rope_pos", r); return K5_ERR_ARG; }
+    char whose[16], len_of[20];
+    snprintf(whose, sizeof whose, "region %d", r); snprintf(len_of, sizeof len_of, "region %d: ", r);
+    K5CHK(check_borrowed_prompt(regions[r], "k5_dit_set_regions", whose, len_of));
   }
   clear();
   rg.conds = regions; rg.R = R; rg.masks = masks; rg.T = T; rg.H = H; rg.W = W; rg.base_weight = base_weight;
