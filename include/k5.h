@@ -680,7 +680,11 @@ int k5_groupnorm_bf16(const void* x, const float* gamma, const float* beta, void
  * conv also emits the GroupNorm statistics of the outputs it STORES — per 128 rows and 4 consecutive channels (sum, sum of squares),
  * quad_stats: k5_conv3d_stats_size(M, Cout) bytes, M = To*Ho*Wo — and k5_groupnorm_bf16_quads normalises from them without a
  * statistics pass of its own (workspace as for k5_groupnorm_bf16).  Only the 4-wave implicit-GEMM kernel emits statistics:
- * K5_ERR_UNSUPPORTED (nothing launched) outside its range (Cin % 128, Cout = 128 or % 256, >= 5/8 of a round of 256-row tiles). */
+ * K5_ERR_UNSUPPORTED (nothing launched) outside its range (Cin % 128, Cout = 128 or % 256, >= 5/8 of a round of 256-row tiles);
+ * K5_ERR_ARG (nothing launched) for an extent < 1 or a factor outside {1, 2}.
+ * quad_stats is [2 ceil(M / 256)][Cout / 4][2] fp32; rows past M count nothing.  Statistics block b holds output rows 128 b .. 128 b + 127,
+ * except where the output frames split into whole 8 x 32 patches (Ho % 8 == 0 and Wo % 32 == 0): there blocks 2 j and 2 j + 1 are the upper
+ * and the lower four pixel rows of patch j (frame-major, then row-major over the patches).  A consumer that folds all blocks need not care. */
 int64_t k5_conv3d_stats_size(int M, int Cout);
 int k5_conv3d_bf16_stats(const void* X, const void* W, const float* bias, void* out, int Ts, int Hs, int Ws, int Cin, int Cout,
                          int up_t, int up_s, int ldc, const void* resid, int ldr, float* quad_stats, void* stream);

@@ -610,6 +610,8 @@ int launch_conv_halo(const ConvW4P& p, int num_cu, hipStream_t stream) {
 // outputs per channel quad — GroupNorm statistics without another pass over the tensor (k5_launch_groupnorm_bf16_quads).
 int k5_launch_conv3d_w4(const void* X, const void* W, const float* bias, void* out, int Ts, int Hs, int Ws, int Cin, int Cout,
                         int up_t, int up_s, int ldc, const void* resid, int ldr, float* quad_stats, hipStream_t stream) {
+  // k5_conv3d_bf16_stats comes here without the checks of k5_launch_conv3d_bf16_strided: any other factor would gather as if it were 1
+  if (Ts <= 0 || Hs <= 0 || Ws <= 0 || (up_t != 1 && up_t != 2) || (up_s != 1 && up_s != 2)) return K5_ERR_ARG;
   if (Cin <= 0 || (Cin % 128) || !(Cout == 128 || (Cout % 256) == 0) || (ldc & 7) || (resid && (ldr & 3)) || !bias) return K5_ERR_UNSUPPORTED;
   ConvW4P p;
   p.X = (const bf16_t*)X; p.W = (const bf16_t*)W; p.C = (bf16_t*)out; p.bias = bias; p.resid = (const bf16_t*)resid;
