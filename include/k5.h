@@ -281,6 +281,28 @@ int k5_edit_renoise(float* out, const float* source, const float* noise, float s
  * NULL = k5_cfg_euler (source / noise then unused).  One pass over the latent. */
 int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source, const float* noise,
                       const float* keep_mask, float sigma_next, int64_t cells, int C, void* stream);
+/* Guidance coefficients and the guided update (added under ABI 11, as the exports above were).  The guided velocity of a
+ * step is v = alpha c + beta u with one (alpha, beta) per sample, formed on the device from five float64 sums over the step's two velocities:
+ *   Sc = sum c, Su = sum u, Scc = sum c^2, Suu = sum u^2, Scu = sum c u          (each product exact: two bf16 factors)
+ *   s = zero_star ? Scu / (Suu + 1e-8) : 1                                        (CFG-Zero*, Fan et al. 2025: the projection of c on u)
+ *   alpha = w, beta = s (1 - w)                                                   (v = s u + w (c - s u))
+ *   rescale > 0: var_c = Scc - Sc^2 / n, var_v = alpha^2 var_c + 2 alpha beta (Scu - Sc Su / n) + beta^2 (Suu - Su^2 / n),
+ *                k = (var_v > 0 and var_c >= 0) ? rescale sqrt(var_c / var_v) + (1 - rescale) : 1, alpha *= k, beta *= k
+ *                                                                                 (CFG rescale, Lin et al. 2024: std over the sample)
+ * v_cond, v_uncond: bf16 [n] on the device; part: device scratch of k5_guidance_stats_blocks(n) x 5 doubles; sums: device double[5], receives
+ * the five sums in the order above; ab: device float[2], receives {(float)alpha, (float)beta}.  The summation order is fixed (a lane its
+ * 16-byte chunks in index order, an xor butterfly over the wave, the four waves in order, the blocks in index order) and nothing is atomic:
+ * every launch, rank and handle gives the same bits.  K5_ERR_ARG: a NULL or not 16-byte aligned pointer, n < 1, rescale outside [0, 1];
+ * K5_ERR_ALIGN: n % 8 != 0.  Nothing is launched when the call is refused. */
+int k5_guidance_stats_blocks(int64_t n);
+int k5_guidance_coeffs_bf16(const void* v_cond, const void* v_uncond, int64_t n, float w, int zero_star, float rescale, double* part,
+                            double* sums, float* ab, void* stream);
+/* k5_cfg_euler_edit with the combine replaced: ab = {alpha, beta} fp32 on the DEVICE (k5_guidance_coeffs_bf16 writes it),
+ * v = bf16(rn(rn(alpha c) + rn(beta u))), img = rn(img + bf16(rn(dt v))), then the keep rule of k5_cfg_euler_edit (keep_mask NULL = none; source
+ * and noise are needed with a mask).  v_out (bf16 [cells * C], NULL = not wanted, may be v_cond) receives v: k5_x0_preview with v_uncond = NULL
+ * on it is the preview of a guided step.  The rounding points differ from k5_cfg_euler's, so ab = {w, 1 - w} need not give its bits. */
+int k5_guided_euler(float* img, const void* v_cond, const void* v_uncond, const float* ab, float dt, const float* source, const float* noise,
+                    const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, void* stream);
 /* k5_cfg_euler over temporal context windows (added under ABI 11, as the exports above were): a clip of T frames whose velocities come from
  * nwin <= 64 windows of F frames.  img fp32 [T][frame_elems]; v_cond / v_uncond (NULL = no guidance) bf16 [nwin][F][frame_elems]; starts_dev
  * DEVICE int32 [nwin], window i covers frames starts[i] .. starts[i] + F - 1; weights_dev DEVICE fp32 [nwin][F], the share of window i's local
@@ -537,6 +559,33 @@ int k5_dit_watch_state(k5_dit* dit, int* steps_done, int* stopped);
  * has enqueued (num_visual_blocks per guided forward), optionally resetting the count. */
 int k5_dit_set_nag(k5_dit* dit, const k5_text_cond* negative /* NULL clears */, float scale, float tau, float alpha);
 int k5_dit_nag_state(k5_dit* dit, int* on, long long* combines, int reset);
+/* Guidance plan (added under ABI 11, as the exports above were): what the sampler does with the two velocities of a step.
+ *   weights          per-step guidance weight w_i, HOST [num_weights], copied by the call; NULL = the call's guidance_weight at every step.
+ *   zero_star        CFG-Zero* (Fan et al. 2025): the unconditional velocity is scaled by s = <c, u> / (<u, u> + 1e-8) per sample.
+ *   zero_init_steps  the first K steps have velocity 0: no forward and no update runs, the latent stays as it is.
+ *   rescale          CFG rescale (Lin et al. 2024) phi in [0, 1]: v *= phi std(c) / std(v) + 1 - phi, std over the sample; 0 = off.
+ * Step i of a k5_sample* call is then one of three kinds: zero (i < zero_init_steps); unguided (|w_i - 1| <= 1e-6): the conditional forward and
+ * k5_cfg_euler[_edit] without v_uncond, the bits of a run at guidance 1; guided: both forwards, then — with zero_star or rescale —
+ * k5_guidance_coeffs_bf16 and k5_guided_euler, otherwise k5_cfg_euler[_edit] with w_i, so a constant weights table is the plain run bit for
+ * bit.  The reduction is deterministic and every rank of a sequence-parallel group and both handles of a CFG pair hold both whole velocities, so
+ * they compute identical coefficients without a further collective.  A watch's preview of a guided step shows the guided velocity.
+ * The captured step (k5_dit_set_graph) is used for uniform plans — every step guided or every step unguided, no zero-init; without zero_star /
+ * rescale also one weight for all steps, since k5_cfg_euler takes it by value — with w_i read from a device table; any other plan runs eagerly.
+ * Refused by k5_sample* before anything is enqueued, with a message: K5_ERR_ARG num_weights != num_steps, or zero_star / rescale at a call
+ * whose every weight is 1; K5_ERR_STATE a plan with guided and unguided steps or with zero-init on a handle in a CFG pair (the unconditional
+ * group would have steps with nothing to exchange) or with MagCache / its calibration (the ratio table is indexed by the call of a plain
+ * run), and any plan at k5_sample_windows with more than one window (one statistic per window is not the published rule);
+ * K5_ERR_UNSUPPORTED zero-init together with editing; K5_ERR_ALIGN zero_star / rescale on a latent that is not a multiple of 8 elements.
+ * k5_dit_set_guidance itself: K5_ERR_ARG for a weight that is not finite, weights with num_weights < 1, zero_init_steps < 0, rescale outside
+ * [0, 1]; NULL clears.  k5_dit_guidance_state: whether a plan is set and how many steps of each kind the handle has enqueued under one. */
+typedef struct k5_guidance {
+  const float* weights; int num_weights;  /* HOST [num_steps] per-step weight, copied at set time; NULL = the call's guidance_weight at every step */
+  int zero_star;                          /* CFG-Zero* projected scale */
+  int zero_init_steps;                    /* first K steps: velocity 0 */
+  float rescale;                          /* phi in [0,1]; 0 = off */
+} k5_guidance;
+int k5_dit_set_guidance(k5_dit* dit, const k5_guidance* guidance /* NULL clears */);
+int k5_dit_guidance_state(k5_dit* dit, int* on, long long* guided_steps, long long* unguided_steps, long long* zero_steps, int reset);
 
 /* Regional prompts on the handle (added under ABI 11; the rule is written at k5_region_combine_bf16): a prompt per masked region inside the
  * cross-attention of ONE forward.  While set, every CONDITIONAL forward (as for k5_dit_set_nag: never the unconditional one) carries R more

@@ -491,6 +491,17 @@ struct k5_dit {
     DevBuf w; int w_order = -1;                    // token weights [N][R + 1] of this region set; -1: not computed, 0: row-major tokens, 1: NABLA's perm order
   } regions;
 
+  // The guidance plan of k5_dit_set_guidance: per-step weights, CFG-Zero* (projected scale, zero-init of the first steps) and
+  // CFG rescale.  Read by sample_impl only; off = the call's guidance_weight at every step through the launches it always made.
+  struct Guidance {
+    bool on = false;
+    std::vector<float> weights;                    // [num_steps] of the calls to come (copied at set time); empty: the call's guidance_weight
+    bool zero_star = false; int zero_init = 0; float rescale = 0.f;
+    long long guided = 0, unguided = 0, zero = 0;  // steps enqueued so far by kind (k5_dit_guidance_state)
+    DevBuf ws;                                     // sums double[5] | ab float[2] at byte 48 | part [blocks][5] doubles at byte 64
+    bool stats() const { return zero_star || rescale > 0.f; }   // the step needs the coefficients from the device
+  } guide;
+
   // MagCache (reference kandinsky/magcache_utils.py:16-101): skip the visual blocks on some calls and re-apply the
   // cached bf16 residual of the same cond / uncond slot.  Decisions depend on the ratio table and the call counter only.
   struct MagCache {
@@ -2331,6 +2342,39 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
     k5_set_error("%s: regional prompts: the masks are (%d, %d, %d), this sample is (%d, %d, %d)", who, rg.T, rg.H, rg.W, a->fwd.T, a->fwd.H, a->fwd.W);
     return K5_ERR_ARG;
   }
+  const k5_dit::Guidance& gd = d->guide;
+  if (gd.on) {
+    const int N = a->num_steps;
+    if (!gd.weights.empty() && (int)gd.weights.size() != N) {
+      k5_set_error("%s: the guidance plan has %d weights, this call %d steps", who, (int)gd.weights.size(), N);
+      return K5_ERR_ARG;
+    }
+    int guided = 0, unguided = 0;
+    for (int i = 0; i < N; ++i) (fabsf((gd.weights.empty() ? a->guidance_weight : gd.weights[i]) - 1.0f) > 1e-6f ? guided : unguided) += 1;
+    const bool mixed = guided && unguided, zinit = gd.zero_init > 0;
+    const char* what = zinit ? "zero-init steps" : "guided and unguided steps";
+    if (win) {
+      k5_set_error("%s: a guidance plan is set (k5_dit_set_guidance): one statistic per window is not the published rule", who);
+      return K5_ERR_STATE;
+    }
+    if (gd.stats() && !guided) {
+      k5_set_error("%s: the guidance plan has %s but every weight of this call is 1: there is nothing to guide", who,
+                   gd.zero_star ? "zero_star" : "rescale");
+      return K5_ERR_ARG;
+    }
+    if ((mixed || zinit) && d->pair.active()) {
+      k5_set_error("%s: the guidance plan has %s and the handle is in a CFG pair: the unconditional group would have steps with nothing to exchange",
+                   who, what);
+      return K5_ERR_STATE;
+    }
+    if ((mixed || zinit) && (d->mag.on || d->cal.on)) {
+      k5_set_error("%s: the guidance plan has %s and %s on the handle: the ratio table is indexed by the call of a plain run", who, what,
+                   d->mag.on ? "MagCache is set" : "MagCache calibration is");
+      return K5_ERR_STATE;
+    }
+    if (zinit && edit) { k5_set_error("%s: zero-init steps together with editing are not supported", who); return K5_ERR_UNSUPPORTED; }
+    if (gd.stats() && (n < 1 || (n & 7))) { k5_set_error("%s: zero_star / rescale need a latent of a multiple of 8 elements (got %lld)", who, (long long)n); return K5_ERR_ALIGN; }
+  }
   if (win) {
     if (edit) { k5_set_error("%s: editing with context windows is not supported", who); return K5_ERR_UNSUPPORTED; }
     if (rank_group(d)) { k5_set_error("%s: the handle is in a %s (context windows are single-rank only)", who, rank_group(d)); return K5_ERR_STATE; }
@@ -2385,6 +2429,19 @@ struct SampleRun {
   int* step_ctr = nullptr;                                                                      // ... and the device-side step counter
   const int32_t* win_starts = nullptr; const float* win_weights = nullptr;   // the window plan on the device
   const void* slot_prompt[2] = {nullptr, nullptr};   // windows with prompts of their own: whose prologue each text cache slot holds
+  // the guidance plan (k5_dit_set_guidance; nullptr: none, every step is of the call's one kind and enqueues what it always did)
+  const k5_dit::Guidance* plan = nullptr;
+  bool stats = false, want_v = false;       // stats: guided steps take their coefficients from the device; want_v: ... and leave v in vel_c (previews)
+  const float* wvec = nullptr;              // graph mode: the per-step weights on the device, next to dtvec
+  double* g_sums = nullptr; float* g_ab = nullptr; double* g_part = nullptr;
+  enum Kind { GUIDED, UNGUIDED, ZERO };
+  float w_at(int i) const { return plan && !plan->weights.empty() ? plan->weights[i] : a->guidance_weight; }
+  Kind kind(int i) const {
+    if (plan && i < plan->zero_init) return ZERO;
+    return fabsf(w_at(i) - 1.0f) > 1e-6f ? GUIDED : UNGUIDED;   // generation_utils.py:63
+  }
+  // what the watch's preview of step i combines: a guided step with coefficients left its v in vel_c, a zero step has velocity 0 there
+  const void* preview_vu(int i) const { return win ? (cfg_on ? vel_u : nullptr) : kind(i) == GUIDED && !stats ? vel_u : nullptr; }
 
   // One forward of step i: the text condition through text cache slot `slot`, on the latent slice `x` with its conditioning slice `vc`, into
   // `vel`.  `tables`: the forward reads its time through the device-side step tables when the step is captured; windows pass none.
@@ -2394,7 +2451,7 @@ struct SampleRun {
 
   int step(int i) {   // enqueue step i: the forwards, then CFG + Euler
     const k5_dit_config& c = d->cfg;
-    void* const vu = cfg_on ? vel_u : nullptr;
+    void* const vu = (win ? cfg_on : kind(i) == GUIDED) ? vel_u : nullptr;
     if (win) {
       // every window on its own slice of the latent (T is outermost: a temporal window is contiguous), cond then uncond, into slot k of the
       // velocity buffers; then one pass over the whole clip blends the windows and applies the step
@@ -2416,6 +2473,7 @@ struct SampleRun {
                                         win->total_T, frame, s));
       return K5_OK;
     }
+    if (kind(i) == ZERO) return K5_OK;   // velocity 0: no forward, no update
     if (pair) {
       // my branch only; then the pair's velocities change hands on the side stream (fork / join by events: capturable) and both
       // handles hold [v_cond | v_uncond] — every rank of both groups applies the same update to the same numbers
@@ -2429,12 +2487,17 @@ struct SampleRun {
       HIPCHK(hipStreamWaitEvent(s, d->ev_vel_done, 0));
     } else {
       K5CHK(forward(i, a->fwd.cond, 0, a->latent, vel_c, vcond));
-      if (cfg_on) K5CHK(forward(i, a->null_cond, 1, a->latent, vel_u, vcond));
+      if (vu) K5CHK(forward(i, a->null_cond, 1, a->latent, vel_u, vcond));
     }
     {
       Scope sc(d, s, "elementwise");
-      if (!edit) K5CHK(k5_launch_cfg_euler(a->latent, vel_c, vu, a->guidance_weight, dt[i], n, s, dtvec, step_ctr));
-      else K5CHK(k5_launch_cfg_euler_edit(a->latent, vel_c, vu, a->guidance_weight, dt[i], edit->source, edit->noise, edit->keep_mask,
+      if (vu && stats) {   // the sample's coefficients, reduced and applied on the device
+        K5CHK(k5_launch_guidance_coeffs(vel_c, vel_u, n, w_at(i), plan->zero_star, plan->rescale, g_part, g_sums, g_ab, s, wvec, step_ctr));
+        K5CHK(k5_launch_guided_euler(a->latent, vel_c, vel_u, g_ab, dt[i], edit ? edit->source : nullptr, edit ? edit->noise : nullptr,
+                                     edit ? edit->keep_mask : nullptr, sigma_next[i], n / c.out_visual_dim, c.out_visual_dim,
+                                     want_v ? vel_c : nullptr, s, dtvec, signext, step_ctr));
+      } else if (!edit) K5CHK(k5_launch_cfg_euler(a->latent, vel_c, vu, w_at(i), dt[i], n, s, dtvec, step_ctr));
+      else K5CHK(k5_launch_cfg_euler_edit(a->latent, vel_c, vu, w_at(i), dt[i], edit->source, edit->noise, edit->keep_mask,
                                           sigma_next[i], n / c.out_visual_dim, c.out_visual_dim, s, dtvec, signext, step_ctr));
     }
     if (step_ctr) K5CHK(k5_launch_step_inc(step_ctr, s));
@@ -2486,7 +2549,8 @@ int k5_dit::Watch::step(const SampleRun& r, int i) {   // after step i is enqueu
     Scope sc(r.d, r.s, "elementwise");
     const int C = r.d->cfg.in_visual_dim;
     const float* w = wb.as<float>();
-    K5CHK(k5_launch_x0_preview(r.a->latent, r.vel_c, r.cfg_on ? r.vel_u : nullptr, r.a->guidance_weight, r.sigma_next[i],
+    if (!r.win && r.kind(i) == SampleRun::ZERO) HIPCHK(hipMemsetAsync(r.vel_c, 0, (size_t)r.n * 2, r.s));   // a zero-init step: x0 = x
+    K5CHK(k5_launch_x0_preview(r.a->latent, r.vel_c, r.preview_vu(i), r.w_at(i), r.sigma_next[i],
                                r.edit ? r.edit->source : nullptr, r.edit ? r.edit->keep_mask : nullptr, w, w + 3 * C,
                                want_x0 ? x0[slot].as<float>() : nullptr, rgb[slot].as<uint8_t>(), r.cells, C, r.s));
     HIPCHK(hipMemcpyAsync(h_rgb[slot], rgb[slot].p, (size_t)r.cells * 3, hipMemcpyDeviceToHost, r.s));
@@ -2531,7 +2595,31 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   r.cells = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W;
   r.n = r.cells * c.out_visual_dim;
   K5CHK(wt.begin(r, who));
+  const int N = a->num_steps;
+  k5_dit::Guidance& gd = d->guide;
   r.cfg_on = fabsf(a->guidance_weight - 1.0f) > 1e-6f;  // generation_utils.py:63
+  int first = 0;          // the first step that runs a forward (N: none does)
+  bool uniform = true;    // every step enqueues the same launches, so one captured step can stand for all of them
+  if (gd.on) {
+    r.plan = &gd;
+    int guided = 0, unguided = 0;
+    bool const_w = true;
+    first = gd.zero_init < N ? gd.zero_init : N;
+    for (int i = first; i < N; ++i) {
+      (r.kind(i) == SampleRun::GUIDED ? guided : unguided) += 1;
+      const_w = const_w && r.w_at(i) == r.w_at(first);
+    }
+    r.cfg_on = guided > 0;   // the unconditional side is sized before the loop, wherever its first step is
+    r.stats = gd.stats() && guided > 0;
+    r.want_v = r.stats && wt.on && wt.every > 0;
+    // cfg_euler_kernel takes its weight by value: without coefficients only a constant weight replays
+    uniform = first == 0 && !(guided && unguided) && (r.stats || !guided || const_w);
+    if (r.stats) {
+      K5CHK(gd.ws.ensure(64 + (size_t)k5_guidance_blocks(r.n) * 5 * sizeof(double)));
+      r.g_sums = gd.ws.as<double>(); r.g_ab = reinterpret_cast<float*>(static_cast<char*>(gd.ws.p) + 48);
+      r.g_part = reinterpret_cast<double*>(static_cast<char*>(gd.ws.p) + 64);
+    }
+  }
   r.pair = r.cfg_on && d->pair.active();
   if (r.pair) K5CHK(d->ws_vel_pair.ensure(2 * r.n * 2));
   else {   // one slot per window
@@ -2550,13 +2638,13 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   // holds one forward pair).  The IPC transport IS replayable: its epochs live on the device and the peers' buffers were mapped by the eager
   // first step (ipc_comm.h)
   const bool graph = d->use_graph && !d->mag.on && !d->cal.on && !d->profiling && a->num_steps > 2 && !d->nabla_tap && !d->comm.loop && !d->pair.loop &&
-                     !win;
-  const int N = a->num_steps;
-  r.host_tab.resize(3 * (size_t)N);
+                     !win && uniform;
+  r.host_tab.resize((gd.on ? 4 : 3) * (size_t)N);
   for (int i = 0; i < N; ++i) {
     r.host_tab[i] = a->sigmas[i] * 1000.0f;
     r.host_tab[N + i] = a->sigmas[i + 1] - a->sigmas[i];
     r.host_tab[2 * N + i] = a->sigmas[i + 1];
+    if (gd.on) r.host_tab[3 * N + i] = r.w_at(i);   // a fourth table with a plan: the weight the coefficients read in the captured step
   }
   r.t1000 = r.host_tab.data(); r.dt = r.t1000 + N; r.sigma_next = r.dt + N;
   if (graph) {
@@ -2573,6 +2661,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     HIPCHK(hipMemsetAsync(r.step_ctr, 0, 4, r.s));
     HIPCHK(hipStreamSynchronize(r.s));   // host_tab lives in this call only
     r.tvec = d->ws_sched.as<float>(); r.dtvec = r.tvec + N; r.signext = r.dtvec + N;
+    if (gd.on) r.wvec = r.signext + N;
   }
   const hipStream_t s = r.s;
   if (edit) {   // the start latent: the source at sigmas[0] everywhere, whatever the mask
@@ -2593,14 +2682,14 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   struct FuseGuard { k5_dit* d; ~FuseGuard() { d->fuse_now = false; d->leave_collect = false; } } fuse_guard{d};
   d->fuse_now = false; d->leave_collect = false; d->fuse_last = -1;
   const bool auto_fuse = d->fuse_qnorm_auto && !d->fuse_qnorm && !d->comm.active() && d->attn_mode == K5_ATTN_AUTO && d->row_offsets &&   // (a CFG pair's handles decide each for itself)
-                         a->fwd.attention_type == 0 && N >= 2;
+                         a->fwd.attention_type == 0 && N - first >= 2;
   if (auto_fuse) {
     K5CHK(d->ws_leave_sig.ensure(4));
     if (!d->h_leave_sig) HIPCHK(hipHostMalloc((void**)&d->h_leave_sig, 4, hipHostMallocDefault));
     HIPCHK(hipMemsetAsync(d->ws_leave_sig.p, 0, 4, s));
     d->leave_collect = true;
   }
-  auto decide_fuse = [&]() -> int {   // after step 0
+  auto decide_fuse = [&]() -> int {   // after the first step that ran a forward
     if (!auto_fuse) return K5_OK;
     d->leave_collect = false;
     *d->h_leave_sig = 1u;
@@ -2631,7 +2720,8 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
       if (hipGraphLaunch(cap.ge, s) != hipSuccess) { k5_set_error("hipGraphLaunch failed"); return K5_ERR_HIP; }
       if (i > 1) { d->nag.combines += nag_per_step; d->regions.combines += reg_per_step; }
     }
-    if (i == 0) K5CHK(decide_fuse());
+    if (i == first) K5CHK(decide_fuse());
+    if (gd.on) (r.kind(i) == SampleRun::GUIDED ? gd.guided : r.kind(i) == SampleRun::UNGUIDED ? gd.unguided : gd.zero) += 1;
     if (wt.on) {
       K5CHK(wt.step(r, i));
       if (wt.stopped) break;
@@ -2697,7 +2787,7 @@ extern "C" int k5_sample_many(k5_dit* d, const k5_sample_many_args* a, void* str
     one.fwd = a->fwd;
     one.fwd.x = nullptr;
     one.fwd.cond = a->conds[b];
-    if (cfg_on) one.null_cond = a->null_conds[b];
+    if (cfg_on || (d->guide.on && a->null_conds)) one.null_cond = a->null_conds[b];   // a guidance plan may guide where the call's weight is 1
     one.latent = a->latents + (size_t)b * thw * c.in_visual_dim;
     one.num_steps = a->num_steps;
     one.sigmas = a->sigmas;
@@ -2801,6 +2891,33 @@ extern "C" int k5_dit_regions_state(k5_dit* d, int* on, int* R, long long* combi
   if (R) *R = d->regions.on ? d->regions.R : 0;
   if (combines) *combines = d->regions.combines;
   if (reset) d->regions.combines = 0;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_set_guidance(k5_dit* d, const k5_guidance* g) {
+  g_err[0] = 0;
+  if (!d) { k5_set_error("k5_dit_set_guidance: null handle"); return K5_ERR_ARG; }
+  k5_dit::Guidance& gd = d->guide;
+  if (!g) { gd.on = false; gd.weights.clear(); gd.zero_star = false; gd.zero_init = 0; gd.rescale = 0.f; return K5_OK; }
+  if (g->weights && g->num_weights < 1) { k5_set_error("k5_dit_set_guidance: weights with num_weights = %d", g->num_weights); return K5_ERR_ARG; }
+  for (int i = 0; g->weights && i < g->num_weights; ++i)
+    if (!isfinite(g->weights[i])) { k5_set_error("k5_dit_set_guidance: weights[%d] is not finite", i); return K5_ERR_ARG; }
+  if (g->zero_init_steps < 0) { k5_set_error("k5_dit_set_guidance: zero_init_steps must be >= 0 (got %d)", g->zero_init_steps); return K5_ERR_ARG; }
+  if (!(g->rescale >= 0.0f && g->rescale <= 1.0f)) { k5_set_error("k5_dit_set_guidance: rescale must be in [0, 1] (got %g)", (double)g->rescale); return K5_ERR_ARG; }
+  gd.weights.assign(g->weights, g->weights ? g->weights + g->num_weights : g->weights);
+  gd.zero_star = g->zero_star != 0; gd.zero_init = g->zero_init_steps; gd.rescale = g->rescale;
+  gd.on = true;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_guidance_state(k5_dit* d, int* on, long long* guided_steps, long long* unguided_steps, long long* zero_steps, int reset) {
+  if (!d) { k5_set_error("k5_dit_guidance_state: null handle"); return K5_ERR_ARG; }
+  k5_dit::Guidance& gd = d->guide;
+  if (on) *on = gd.on ? 1 : 0;
+  if (guided_steps) *guided_steps = gd.guided;
+  if (unguided_steps) *unguided_steps = gd.unguided;
+  if (zero_steps) *zero_steps = gd.zero;
+  if (reset) gd.guided = gd.unguided = gd.zero = 0;
   return K5_OK;
 }
 

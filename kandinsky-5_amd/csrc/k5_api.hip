@@ -382,6 +382,31 @@ int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, floa
              "k5_cfg_euler_edit");
 }
 
+int k5_guidance_stats_blocks(int64_t n) { return k5_guidance_blocks(n); }
+
+int k5_guidance_coeffs_bf16(const void* v_cond, const void* v_uncond, int64_t n, float w, int zero_star, float rescale, double* part,
+                            double* sums, float* ab, void* stream) {
+  const int st = k5_launch_guidance_coeffs(v_cond, v_uncond, n, w, zero_star, rescale, part, sums, ab, (hipStream_t)stream);
+  if (st == K5_ERR_ALIGN) { k5_set_error("k5_guidance_coeffs_bf16: n = %lld is not a multiple of 8", (long long)n); return st; }
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_guidance_coeffs_bf16: need 16-byte aligned non-null pointers, n >= 1, 0 <= rescale <= 1 (n %lld, rescale %g)", (long long)n,
+                 (double)rescale);
+    return st;
+  }
+  return ret(st, "k5_guidance_coeffs_bf16");
+}
+
+int k5_guided_euler(float* img, const void* v_cond, const void* v_uncond, const float* ab, float dt, const float* source, const float* noise,
+                    const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, void* stream) {
+  const int st = k5_launch_guided_euler(img, v_cond, v_uncond, ab, dt, source, noise, keep_mask, sigma_next, cells, C, v_out, (hipStream_t)stream);
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_guided_euler: need img, v_cond, v_uncond and ab, cells and C >= 1, and source and noise with a keep_mask (cells %lld, C %d)",
+                 (long long)cells, C);
+    return st;
+  }
+  return ret(st, "k5_guided_euler");
+}
+
 int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts_dev,
                          const float* weights_dev, int nwin, int F, int T, int64_t frame_elems, void* stream) {
   if (!img || !v_cond || !starts_dev || !weights_dev || nwin < 1 || nwin > 64 || F < 1 || T < 1 || frame_elems < 1) {

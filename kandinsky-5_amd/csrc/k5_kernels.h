@@ -184,6 +184,19 @@ int k5_launch_edit_renoise(float* out, const float* source, const float* noise, 
 int k5_launch_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source,
                              const float* noise, const float* keep_mask, float sigma_next, int64_t cells, int C, hipStream_t stream,
                              const float* dtvec = nullptr, const float* signext = nullptr, const int* step = nullptr);
+// guidance coefficients of one sample: the five float64 sums Sc, Su, Scc, Suu, Scu of the bf16 velocities v_cond / v_uncond [n] in a fixed order
+// (no atomics: the same bits on every launch, rank and handle) into sums[5], then ab = {alpha, beta} (fp32) of v = alpha c + beta u:
+// s = zero_star ? Scu / (Suu + 1e-8) : 1, alpha = w, beta = s (1 - w), both times rescale * sqrt(var c / var v) + 1 - rescale when rescale > 0.
+// part: k5_guidance_blocks(n) x 5 doubles of scratch.  wvec / step: the captured step reads w at the device step counter.
+// K5_ERR_ARG: a NULL or not 16-byte aligned pointer, n < 1, rescale outside [0, 1]; K5_ERR_ALIGN: n % 8.  Nothing is launched when it refuses.
+int k5_guidance_blocks(int64_t n);
+int k5_launch_guidance_coeffs(const void* v_cond, const void* v_uncond, int64_t n, float w, int zero_star, float rescale, double* part,
+                              double* sums, float* ab, hipStream_t stream, const float* wvec = nullptr, const int* step = nullptr);
+// k5_launch_cfg_euler_edit with the combine v = bf16(rn(rn(alpha c) + rn(beta u))), ab = {alpha, beta} fp32 on the device; v_out (bf16 [cells * C],
+// nullable, may be v_cond) receives v.  keep_mask null = no edit tail.
+int k5_launch_guided_euler(float* img, const void* v_cond, const void* v_uncond, const float* ab, float dt, const float* source,
+                           const float* noise, const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, hipStream_t stream,
+                           const float* dtvec = nullptr, const float* signext = nullptr, const int* step = nullptr);
 // K18 over temporal context windows: img fp32 [T][frame_elems]; v_cond / v_uncond (null = no guidance) bf16 [nwin][F][frame_elems], window i
 // covering frames starts[i] .. starts[i] + F - 1 (device int32 [nwin]) with the share weights[i][j] (device fp32 [nwin][F]) of its local frame j.
 // Per element the windows that cover its frame are walked in order: v_i as K18 forms it, acc = wt_0 * v_0, then acc = acc + wt_i * v_i

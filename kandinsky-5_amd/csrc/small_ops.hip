@@ -671,6 +671,120 @@ __global__ __launch_bounds__(256) void cfg_euler_edit_kernel(float* __restrict__
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Guidance coefficients (k5_launch_guidance_coeffs): the guided velocity of a step is v = alpha * c + beta * u with alpha, beta
+// per SAMPLE, from five sums over the two velocities — Sc = sum c, Su = sum u, Scc = sum c^2, Suu = sum u^2, Scu = sum c u.  Everything is
+// float64: a product of two bf16 values is exact there, and the order is fixed as in magcache_stats_kernel — a lane adds its 16-byte chunks
+// in index order (the eight elements of a chunk in order), an xor butterfly adds the wave, thread 0 the four waves in wave order into
+// part[block][5], guidance_finish_kernel the blocks in index order.  No atomics: two launches, two ranks, the two handles of a pair give the
+// same bits.
+K5_DEV double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void guidance_stats_kernel(const bf16_t* __restrict__ vc, const bf16_t* __restrict__ vu,
+                                                             double* __restrict__ part, int64_t nch) {
+  __shared__ double red[4][5];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // Sc | Su | Scc | Suu | Scu
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < nch; g += (int64_t)gridDim.x * 256) {
+    const u32x4 rc = *reinterpret_cast<const u32x4*>(vc + g * 8);
+    const u32x4 ru = *reinterpret_cast<const u32x4*>(vu + g * 8);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {   // low half first: the element of the lower index
+        const double c = (double)__uint_as_float(h ? rc[j] & 0xffff0000u : rc[j] << 16);
+        const double u = (double)__uint_as_float(h ? ru[j] & 0xffff0000u : ru[j] << 16);
+        acc[0] += c; acc[1] += u;
+        acc[2] += c * c; acc[3] += u * u; acc[4] += c * u;   // the products are exact, fused or not
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k) acc[k] = wave_sum_f64(acc[k]);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k) red[wave][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) part[(size_t)blockIdx.x * 5 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// sums[k] = the nblk partials of component k in index order (thread (g, k) adds blocks g, g + 64, ..., then thread k the 64 group sums in group
+// order), then thread 0 forms the coefficients in float64:
+//   s = zero_star ? Scu / (Suu + 1e-8) : 1                    (CFG-Zero*: the projection of c on u)
+//   alpha = w, beta = s (1 - w)                               (v = s u + w (c - s u))
+//   rescale > 0: k = rescale * sqrt(var c / var v) + (1 - rescale) with the variances from the sums (CFG rescale, std over the sample);
+//                var v <= 0 or var c < 0 (rounding of a constant tensor) leaves k = 1
+// and writes ab = {(float)alpha, (float)beta}.  One workgroup.  In the captured step w = wvec[*step].
+__global__ __launch_bounds__(320) void guidance_finish_kernel(const double* __restrict__ part, int nblk, double n, float w, int zero_star,
+                                                              float rescale, const float* __restrict__ wvec, const int* __restrict__ step,
+                                                              double* __restrict__ sums, float* __restrict__ ab) {
+  __shared__ double red[64][5];
+  __shared__ double tot[5];
+  const int k = threadIdx.x % 5, g = threadIdx.x / 5;
+  double a = 0.0;
+  for (int b = g; b < nblk; b += 64) a += part[(size_t)b * 5 + k];
+  red[g][k] = a;
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    double t = 0.0;
+    for (int i = 0; i < 64; ++i) t += red[i][threadIdx.x];
+    tot[threadIdx.x] = t;
+    sums[threadIdx.x] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double Sc = tot[0], Su = tot[1], Scc = tot[2], Suu = tot[3], Scu = tot[4];
+    const double wd = (double)(wvec ? wvec[*step] : w);
+    const double s = zero_star ? Scu / (Suu + 1e-8) : 1.0;
+    double alpha = wd, beta = s * (1.0 - wd);
+    if (rescale > 0.0f) {
+      const double phi = (double)rescale;
+      const double var_c = Scc - Sc * Sc / n;
+      const double var_v = alpha * alpha * var_c + 2.0 * alpha * beta * (Scu - Sc * Su / n) + beta * beta * (Suu - Su * Su / n);
+      const double kf = (var_v > 0.0 && var_c >= 0.0) ? phi * sqrt(var_c / var_v) + (1.0 - phi) : 1.0;
+      alpha *= kf; beta *= kf;
+    }
+    ab[0] = (float)alpha;
+    ab[1] = (float)beta;
+  }
+}
+
+// v = bf16(alpha * c + beta * u) with the two products and the sum rounded to fp32 each on its own (the pragma: see renoise_at)
+__device__ __forceinline__ float guided_velocity(float alpha, float beta, float c, float u) {
+#pragma clang fp contract(off)
+  const float p = alpha * c;
+  const float q = beta * u;
+  return bf_round(p + q);
+}
+
+// cfg_euler_edit_kernel with the combine replaced: the coefficients come from device memory (guidance_finish_kernel wrote them), the rest — the
+// bf16 rounding of dt * v, the fp32 update, the keep rule at sigma_next — is that kernel's.  v_out (nullable, may be vc: element g is read
+// before it is written, by the same thread) receives the guided velocity, for the watch's preview.
+__global__ __launch_bounds__(256) void guided_euler_kernel(float* __restrict__ img, const bf16_t* vc, const bf16_t* __restrict__ vu,
+                                                           const float* __restrict__ ab, float dt, const float* __restrict__ x0,
+                                                           const float* __restrict__ eps, const float* __restrict__ mask, float sigma_next,
+                                                           int C, bf16_t* v_out, const float* __restrict__ dtvec,
+                                                           const float* __restrict__ signext, const int* __restrict__ step, int64_t n) {
+  if (dtvec) { dt = dtvec[*step]; sigma_next = signext[*step]; }
+  const float alpha = ab[0], beta = ab[1];
+  const float a = 1.0f - sigma_next;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
+    const float v = guided_velocity(alpha, beta, bf2f(vc[g]), bf2f(vu[g]));
+    float x = __fadd_rn(img[g], bf_round(__fmul_rn(dt, v)));
+    if (mask) {
+      const float m = mask[g / C];
+      if (m != 0.0f) x = keep_blend(x, renoise_at(a, sigma_next, x0[g], eps[g]), m);
+    }
+    img[g] = x;
+    if (v_out) v_out[g] = f2bf(v);
+  }
+}
+
 // Temporal context windows: one term of the cross-fade, acc = wt_0 * v_0 for the first window that covers the frame and acc + wt_i * v_i for
 // every later one.  The product and the sum round to fp32 each on its own (the pragma: see renoise_at), so the torch expression with separate
 // ops is the oracle bit for bit, and one window of weight 1 leaves v itself.
@@ -987,6 +1101,38 @@ int k5_launch_cfg_euler_edit(float* img, const void* vc, const void* vu, float w
   const int64_t n = cells * C;
   hipLaunchKernelGGL(cfg_euler_edit_kernel, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, w, dt, source,
                      noise, keep_mask, sigma_next, C, dtvec, signext, step, n);
+  return done();
+}
+
+int k5_guidance_blocks(int64_t n) {
+  const int64_t wg = (n / 8 + 255) / 256;
+  return wg < 1 ? 1 : wg < 1024 ? (int)wg : 1024;
+}
+
+int k5_launch_guidance_coeffs(const void* vc, const void* vu, int64_t n, float w, int zero_star, float rescale, double* part, double* sums,
+                              float* ab, hipStream_t s, const float* wvec, const int* step) {
+  const auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if (!vc || !vu || !part || !sums || !ab || n < 1 || !(rescale >= 0.0f && rescale <= 1.0f) || ((wvec != nullptr) != (step != nullptr)))
+    return K5_ERR_ARG;
+  if (misaligned(vc) || misaligned(vu) || misaligned(part) || misaligned(sums) || misaligned(ab)) return K5_ERR_ARG;
+  if (n & 7) return K5_ERR_ALIGN;
+  const int grid = k5_guidance_blocks(n);
+  hipLaunchKernelGGL(guidance_stats_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)vc, (const bf16_t*)vu, part, n / 8);
+  hipLaunchKernelGGL(guidance_finish_kernel, dim3(1), dim3(320), 0, s, (const double*)part, grid, (double)n, w, zero_star, rescale, wvec, step,
+                     sums, ab);
+  return done();
+}
+
+int k5_launch_guided_euler(float* img, const void* vc, const void* vu, const float* ab, float dt, const float* source, const float* noise,
+                           const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, hipStream_t s, const float* dtvec,
+                           const float* signext, const int* step) {
+  if (!img || !vc || !vu || !ab || cells <= 0 || C <= 0 || ((dtvec != nullptr) != (step != nullptr)) ||
+      ((dtvec != nullptr) != (signext != nullptr)))
+    return K5_ERR_ARG;
+  if (keep_mask && (!source || !noise)) return K5_ERR_ARG;
+  const int64_t n = cells * C;
+  hipLaunchKernelGGL(guided_euler_kernel, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, ab, dt, source, noise,
+                     keep_mask, sigma_next, C, (bf16_t*)v_out, dtvec, signext, step, n);
   return done();
 }
 

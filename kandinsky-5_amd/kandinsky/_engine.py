@@ -107,6 +107,12 @@ class WatchTrampoline:
             raise e
 
 
+class Guidance(C.Structure):
+    """k5_guidance: the plan of k5_dit_set_guidance (weights is HOST memory, copied by the call)."""
+    _fields_ = [("weights", C.POINTER(C.c_float)), ("num_weights", C.c_int), ("zero_star", C.c_int), ("zero_init_steps", C.c_int),
+                ("rescale", C.c_float)]
+
+
 class VaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int), ("out_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -197,6 +203,9 @@ SYMBOLS = {
     "k5_sample_edit": (_I, [_P, C.POINTER(SampleArgs), _P, C.POINTER(EditArgs), _P]),
     "k5_edit_renoise": (_I, [_P, _P, _P, _F, _I64, _P]),
     "k5_cfg_euler_edit": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _F, _I64, _I, _P]),
+    "k5_guidance_stats_blocks": (_I, [_I64]),
+    "k5_guidance_coeffs_bf16": (_I, [_P, _P, _I64, _F, _I, _F, _P, _P, _P, _P]),
+    "k5_guided_euler": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _F, _I64, _I, _P, _P]),
     "k5_cfg_euler_windows": (_I, [_P, _P, _P, _F, _F, _P, _P, _I, _I, _I, _I64, _P]),
     "k5_sample_windows": (_I, [_P, C.POINTER(SampleWindowsArgs), _P, _P]),
     "k5_x0_preview": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I64, _I, _P]),
@@ -205,6 +214,8 @@ SYMBOLS = {
     "k5_nag_combine_bf16": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _P]),
     "k5_dit_set_nag": (_I, [_P, C.POINTER(TextCond), _F, _F, _F]),
     "k5_dit_nag_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), _I]),
+    "k5_dit_set_guidance": (_I, [_P, C.POINTER(Guidance)]),
+    "k5_dit_guidance_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _I]),
     "k5_region_combine_bf16": (_I, [_P, _P, C.c_longlong, _I, _P, _I, _P, _I, _I, _I, _P]),
     "k5_region_weights_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "k5_dit_set_regions": (_I, [_P, C.POINTER(TextCond), _I, _P, _I, _I, _I, _F]),
@@ -520,6 +531,55 @@ def cfg_euler_edit_(img, v_cond, v_uncond, w, dt, source, noise, keep_mask, sigm
         raise ValueError("cfg_euler_edit_: keep_mask must be a contiguous fp32 tensor with one value per cell")
     check(lib().k5_cfg_euler_edit(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), ptr(source), ptr(noise), ptr(keep_mask),
                                   float(sigma_next), cells, C_, stream_ptr(img.device)), "k5_cfg_euler_edit")
+    return img
+
+
+def guidance_coeffs(v_cond, v_uncond, w, zero_star=False, rescale=0.0, ab=None, sums=None):
+    """(ab, sums) of one sample's two velocities (k5_guidance_coeffs_bf16): sums = float64 [5] (sum c, sum u, sum c^2, sum u^2, sum c u) in a fixed
+    order, ab = fp32 [2] = (alpha, beta) of the guided velocity v = alpha c + beta u — alpha = w, beta = s (1 - w) with s = <c, u> / (<u, u> + 1e-8)
+    under zero_star (else 1), both times rescale * std(c) / std(v) + 1 - rescale when rescale > 0.  Contiguous bf16 tensors of one size, a multiple
+    of 8 elements; both results stay on the device (`ab`, `sums`: buffers to fill instead of new ones)."""
+    for v in (v_cond, v_uncond):
+        if v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != v_cond.numel():
+            raise ValueError("guidance_coeffs: the velocities must be contiguous bf16 tensors of one size")
+    _need_cuda(v_cond, v_uncond, ab, sums)
+    n = v_cond.numel()
+    if ab is None:
+        ab = torch.empty(2, dtype=torch.float32, device=v_cond.device)
+    if sums is None:
+        sums = torch.empty(5, dtype=torch.float64, device=v_cond.device)
+    if ab.dtype != torch.float32 or ab.numel() != 2 or sums.dtype != torch.float64 or sums.numel() != 5:
+        raise ValueError("guidance_coeffs: ab must be fp32 [2] and sums float64 [5]")
+    with torch.cuda.device(v_cond.device):
+        part = torch.empty(max(1, lib().k5_guidance_stats_blocks(n)) * 5, dtype=torch.float64, device=v_cond.device)
+        check(lib().k5_guidance_coeffs_bf16(ptr(v_cond), ptr(v_uncond), n, float(w), int(bool(zero_star)), float(rescale), ptr(part), ptr(sums),
+                                            ptr(ab), stream_ptr(v_cond.device)), "k5_guidance_coeffs_bf16")
+    return ab, sums
+
+
+def guided_euler_(img, v_cond, v_uncond, ab, dt, source=None, noise=None, keep_mask=None, sigma_next=0.0, v_out=None):
+    """The update of a guided step with coefficients from the device (k5_guided_euler): v = bf16(ab[0] * v_cond + ab[1] * v_uncond),
+    img += bf16(dt * v), then with a keep_mask the keep rule of cfg_euler_edit_ at sigma_next.  v_out (bf16 of img's size, may be v_cond)
+    receives v."""
+    _need_cuda(img, v_cond, v_uncond, ab, source, noise, keep_mask, v_out)
+    C_ = img.shape[-1]
+    cells = img.numel() // C_
+    for t in (img, source, noise):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != img.shape):
+            raise ValueError("guided_euler_: img, source and noise must be contiguous fp32 tensors of one shape")
+    for v in (v_cond, v_uncond, v_out):
+        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != img.numel()):
+            raise ValueError("guided_euler_: the velocities must be contiguous bf16 tensors of img's size")
+    if v_cond is None or v_uncond is None:
+        raise ValueError("guided_euler_: a guided step has both velocities")
+    if ab.dtype != torch.float32 or ab.numel() != 2 or not ab.is_contiguous():
+        raise ValueError("guided_euler_: ab must be a contiguous fp32 [2] tensor on the device")
+    if keep_mask is not None and (source is None or noise is None or keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous()
+                                  or keep_mask.numel() != cells):
+        raise ValueError("guided_euler_: keep_mask must be a contiguous fp32 tensor with one value per cell and needs source and noise")
+    with torch.cuda.device(img.device):
+        check(lib().k5_guided_euler(ptr(img), ptr(v_cond), ptr(v_uncond), ptr(ab), float(dt), ptr(source), ptr(noise), ptr(keep_mask),
+                                    float(sigma_next), cells, C_, ptr(v_out), stream_ptr(img.device)), "k5_guided_euler")
     return img
 
 

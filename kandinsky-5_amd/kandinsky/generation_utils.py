@@ -79,6 +79,88 @@ def edit_first_step(num_steps, strength):
     return int(num_steps) - run
 
 
+def guidance_plan(sigmas, guidance_weight, guidance_schedule=None, guidance_interval=None):
+    """The per-step guidance weights of a run over `sigmas` (num_steps + 1 values, step i goes from sigmas[i] to sigmas[i + 1]): a list of
+    num_steps floats.  `guidance_schedule`: a list of num_steps weights, or a callable `(i, sigma_i) -> weight`; None = `guidance_weight` at
+    every step.  `guidance_interval` = (lo, hi) (Kynkaanniemi et al. 2024): the weight stays on the steps with lo <= sigmas[i] <= hi and is
+    1 elsewhere, where the sampler then runs the conditional forward alone.  Host only."""
+    sig = [float(v) for v in sigmas]
+    n = len(sig) - 1
+    if n < 1:
+        raise ValueError("guidance_plan: sigmas must hold num_steps + 1 >= 2 values")
+    if guidance_schedule is None:
+        weights = [float(guidance_weight)] * n
+    elif callable(guidance_schedule):
+        weights = [float(guidance_schedule(i, sig[i])) for i in range(n)]
+    else:
+        weights = [float(w) for w in guidance_schedule]
+        if len(weights) != n:
+            raise ValueError(f"guidance_schedule holds {len(weights)} weights, the run has {n} steps")
+    if not all(math.isfinite(w) for w in weights):
+        raise ValueError("guidance_plan: every weight must be a finite number")
+    if guidance_interval is not None:
+        try:
+            lo, hi = (float(v) for v in guidance_interval)
+        except (TypeError, ValueError):
+            raise ValueError("guidance_interval must be (lo, hi)") from None
+        if not lo <= hi:
+            raise ValueError(f"guidance_interval must be (lo, hi) with lo <= hi, got ({lo}, {hi})")
+        weights = [w if lo <= sig[i] <= hi else 1.0 for i, w in enumerate(weights)]
+    return weights
+
+
+def _is_guided(w):
+    return abs(w - 1.0) > 1e-6   # the engine's rule (reference generation_utils.py:63)
+
+
+def _guidance_for_run(model, sigmas, first, guidance_weight, guidance_schedule, guidance_interval, cfg_zero_star, cfg_zero_init, cfg_rescale,
+                      init_latent, windowed):
+    """`generate`'s guidance keywords -> None when all are off (nothing changes), otherwise (weights of the steps that run | None, zero_star,
+    zero_init_steps, rescale) with the ValueErrors of what the engine refuses.  `sigmas`: the full schedule, of which steps `first`.. run."""
+    if guidance_schedule is None and guidance_interval is None and not cfg_zero_star and not cfg_zero_init and not cfg_rescale:
+        return None
+    from .models.dit import check_guidance_args
+    weights = None
+    if guidance_schedule is not None or guidance_interval is not None:
+        weights = guidance_plan(sigmas, guidance_weight, guidance_schedule, guidance_interval)[first:]   # cut with the schedule
+    weights, zero_star, zero_init, rescale = check_guidance_args(weights, cfg_zero_star, cfg_zero_init, cfg_rescale)
+    per_step = weights if weights is not None else [float(guidance_weight)] * (len(sigmas) - 1 - first)
+    guided = [_is_guided(w) for w in per_step]
+    if windowed:
+        raise ValueError("guidance_schedule / guidance_interval / cfg_zero_star / cfg_zero_init / cfg_rescale together with context windows "
+                         "are not supported: one statistic per window is not the published rule")
+    if (zero_star or rescale > 0.0) and not any(guided):
+        raise ValueError("cfg_zero_star / cfg_rescale at a run whose every guidance weight is 1: there is nothing to guide")
+    if zero_init > 0 and init_latent is not None:
+        raise ValueError("cfg_zero_init together with init_latent (editing) is not supported")
+    if zero_init > 0 or (any(guided) and not all(guided)):
+        if _has_magcache(model):
+            raise ValueError("a guidance plan with guided and unguided steps, or with cfg_zero_init, with MagCache: the ratio table is indexed "
+                             "by the call of a plain run")
+        if getattr(model, "_cfg_pair", None) is not None or getattr(model, "_cfg_parallel", None) is not None:
+            raise ValueError("a guidance plan with guided and unguided steps, or with cfg_zero_init, on a CFG pair: the unconditional group "
+                             "would have steps with nothing to exchange")
+    return weights, zero_star, zero_init, rescale
+
+
+@contextlib.contextmanager
+def _guidance_for_call(model, guide):
+    """A guidance plan on the engine-backed model for exactly one sample / sample_many call; what was there before comes back, also on an
+    exception.  guide None: nothing is touched."""
+    if guide is None:
+        yield
+        return
+    before = model._guidance
+    try:
+        model.set_guidance(*guide)
+        yield
+    finally:
+        if before is not None:
+            model.set_guidance(*before)
+        else:
+            model.clear_guidance()
+
+
 def context_windows(T, frames, overlap):
     """The plan of a long clip sampled as temporal context windows: `(starts, weights)` for T latent frames, windows of `frames` = F frames
     and 0 <= `overlap` < F.  T <= F: one window of T frames with weight 1.  Otherwise nwin = ceil((T - overlap) / (F - overlap)) windows
@@ -296,7 +378,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
              visual_cond=None, visual_cond_mask=None, batch=1, init_latent=None, strength=1.0, keep_mask=None,
              callback=None, preview_every=0, preview_factors=None, preview_x0=False, context_frames=None, context_overlap=None,
              context_text=None, nag_text_embeds=None, nag_text_rope_pos=None, nag_scale=None, nag_tau=2.5, nag_alpha=0.25,
-             region_text_embeds=None, region_text_rope_pos=None, region_masks=None, region_base_weight=0.0):
+             region_text_embeds=None, region_text_rope_pos=None, region_masks=None, region_base_weight=0.0,
+             guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0, cfg_rescale=0.0):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -339,7 +422,18 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     prompt, which uncovered cells see alone and which weighs `region_base_weight` in [0, 1] under the regions.  One region set for every
     sample of a batch.  Set on the model for this call and removed afterwards, also when the call raises; every rank of a group or a CFG
     pair passes the same values.  The unconditional forward of a CFG run is not touched.  ValueError on a model without the engine and
-    together with `context_frames` below the clip's length (the masks cover the clip, a window sees a slice)."""
+    together with `context_frames` below the clip's length (the masks cover the clip, a window sees a slice).
+    `guidance_schedule`, `guidance_interval`, `cfg_zero_star`, `cfg_zero_init`, `cfg_rescale` (optional, extension): what the sampler does
+    with the two velocities of a step; all off (default) nothing changes.  `guidance_schedule` (a list of num_steps weights or a callable
+    `(i, sigma_i)`) and `guidance_interval` = (lo, hi) give every step its own weight (`guidance_plan`); a step whose weight is 1 runs the
+    conditional forward alone, so an interval saves one forward on every step outside it.  With strength < 1 the plan is that of the full
+    schedule, cut with it.  `cfg_zero_star`: CFG-Zero* (Fan et al. 2025), the unconditional velocity scaled by <c, u> / <u, u> per sample,
+    and `cfg_zero_init` = K: the first K steps leave the latent as it is.  `cfg_rescale` = phi in [0, 1]: CFG rescale (Lin et al. 2024),
+    v *= phi std(c) / std(v) + 1 - phi.  The engine-backed model runs them inside its loop (`DiffusionTransformer3D.set_guidance`, set for
+    this call and removed afterwards), any other model through the same two kernels from the per-step loop: the same bits.  ValueError
+    together with context windows; for cfg_zero_star / cfg_rescale when every weight is 1; for cfg_zero_init with init_latent; for a plan
+    with guided and unguided steps or cfg_zero_init with MagCache or on a CFG pair.  No checkpoint was at hand when this was built: the
+    rules are the published ones, their effect on quality is not measured here."""
     from .models.dit import split_per_sample
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
@@ -352,7 +446,13 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         text_embeds, null_text_embeds, text_rope_pos, null_text_rope_pos = (
             split_per_sample(v, 1, n)[0] for v, n in ((text_embeds, "text_embeds"), (null_text_embeds, "null_text_embeds"),
                                                  (text_rope_pos, "text_rope_pos"), (null_text_rope_pos, "null_text_rope_pos")))
-    steps_run = num_steps - (edit_first_step(num_steps, strength) if init_latent is not None else 0)
+    first = edit_first_step(num_steps, strength) if init_latent is not None else 0
+    steps_run = num_steps - first
+    guide_kw = (guidance_schedule, guidance_interval, cfg_zero_star, cfg_zero_init, cfg_rescale)
+    guide = None
+    if any(v is not None for v in guide_kw[:2]) or any(guide_kw[2:]):   # the schedule as `_generate_one` draws it: the same bits
+        guide = _guidance_for_run(model, sigma_schedule(num_steps, scheduler_scale, device=device).cpu().tolist(), first, guidance_weight,
+                                  *guide_kw, init_latent, plan is not None and len(plan[1]) > 1)
     if region_text_embeds is not None and plan is not None and len(plan[1]) > 1:
         raise ValueError("region_text_embeds together with context windows is not supported: the masks cover the clip, a window sees a slice")
     with _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
@@ -369,16 +469,16 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
             run = (model, device, img.contiguous(), num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                    null_text_rope_pos, guidance_weight, scheduler_scale, conf, watch)
             what = (context, visual_cond, visual_cond_mask, init_latent, strength, keep_mask)
-            return _generate_batch(*run, batch, *what) if batch > 1 else _generate_one(*run, plan, *what)
+            return _generate_batch(*run, batch, *what, guide=guide) if batch > 1 else _generate_one(*run, plan, *what, guide=guide)
         finally:
             watch.close()
 
 
 def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                   guidance_weight, scheduler_scale, conf, watch, plan, context, visual_cond, visual_cond_mask, init_latent, strength,
-                  keep_mask):
-    """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch` and the checked `plan` of
-    `_context_plan`; returns the latent."""
+                  keep_mask, guide=None):
+    """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch`, the checked `plan` of
+    `_context_plan` and the checked guidance plan `guide` of `_guidance_for_run`; returns the latent."""
     context_text = context[2]
     if plan is not None:
         F, starts, weights = plan
@@ -407,6 +507,9 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
             if isinstance(m, DiffusionTransformer3D):
                 m.reset_softmax_memory()
     cfg_on = abs(guidance_weight - 1.0) > 1e-6
+    g_weights, g_zero_star, g_zero_init, g_rescale = guide if guide is not None else (None, False, 0, 0.0)
+    if g_weights is not None:   # some step is guided: the pair exchanges, the buffers of the unconditional side exist
+        cfg_on = any(_is_guided(w) for w in g_weights)
     cfg_parallel = getattr(model, "_cfg_parallel", None)
     # CFG-parallel for a model WITHOUT the engine-side pair (a wrapped / duck-typed model): this rank's group
     # runs ONE of the two forwards; the pair exchanges the velocities (6 MB at 5 s) over torch.distributed and every rank applies
@@ -415,7 +518,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     exchange = cfg_parallel is not None and cfg_on and getattr(model, "_cfg_pair", None) is None
     if not exchange and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False):
         # whole loop inside the engine: no per-step host work at all
-        with watch.installed(model):
+        with watch.installed(model), _guidance_for_call(model, guide):
             model.sample(img, timesteps.tolist(), text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                          null_text_rope_pos, guidance_weight, scale_factor=conf.metrics.scale_factor,
                          sparse_params=sparse_params,
@@ -428,20 +531,20 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         return model(x, te["text_embeds"], te["pooled_embed"], t1000, visual_rope_pos, tp, scale_factor=conf.metrics.scale_factor,
                      sparse_params=sparse_params)
 
-    def plain_velocities(t1000):   # cond, then uncond
+    def plain_velocities(t1000, guided):   # cond, then uncond
         x = _model_input(model, img, cond_in)
         v = forward(x, text_embeds, text_rope_pos, t1000)
-        u = forward(x, null_text_embeds, null_text_rope_pos, t1000) if cfg_on else None
+        u = forward(x, null_text_embeds, null_text_rope_pos, t1000) if guided else None
         return v.contiguous(), None if u is None else u.contiguous()
 
-    def pair_velocities(t1000):   # my branch, then the pair's exchange into the reused buffer
+    def pair_velocities(t1000, guided):   # my branch, then the pair's exchange into the reused buffer
         nonlocal both
         v = forward(_model_input(model, img, cond_in), *mine, t1000)
         if both is None:
             both = torch.empty((2,) + tuple(v.shape), dtype=v.dtype, device=v.device)
         return exchange_velocity(v, cfg_parallel[1], out=both)
 
-    def window_velocities(t1000):
+    def window_velocities(t1000, guided):
         # the forwards of k5_sample_windows in its order: window by window, cond then uncond, each on its own slice of the latent
         for k, st in enumerate(starts):
             x = _model_input(model, img, cond_in, slice(st, st + F))
@@ -469,13 +572,27 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         E.renoise(edit[0], edit[1], float(timesteps[0]), out=img)
     for i, (timestep, timestep_diff, sigma_next) in enumerate(zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(),
                                                                   timesteps[1:].tolist())):
-        v, u = velocities(torch.tensor([timestep]) * 1000)
-        if plan is not None:       # the one blend + Euler pass over the clip
-            E.cfg_euler_windows_(img, v, u, guidance_weight, timestep_diff, st_dev, wt_dev)
-        elif edit is None:         # CFG combine + Euler on img, in place
-            E.cfg_euler_(img, v, u, guidance_weight, timestep_diff)
-        else:                      # ... and the keep rule
-            E.cfg_euler_edit_(img, v, u, guidance_weight, timestep_diff, edit[0], edit[1], edit[2], sigma_next)
+        # the guidance plan's kind of step, as the engine's loop decides it: zero (no forward, no update), unguided (the conditional
+        # forward alone), guided; without a plan every step is of the call's one kind
+        w = guidance_weight if g_weights is None else g_weights[i]
+        guided = cfg_on if guide is None else _is_guided(w)
+        wants_preview = watch.active and watch.preview_at(i, n)
+        if i < g_zero_init:
+            v, u = (torch.zeros(img.shape, dtype=torch.bfloat16, device=img.device) if wants_preview else None), None   # velocity 0: x0 = x
+        else:
+            v, u = velocities(torch.tensor([timestep]) * 1000, guided)
+            if plan is not None:       # the one blend + Euler pass over the clip
+                E.cfg_euler_windows_(img, v, u, guidance_weight, timestep_diff, st_dev, wt_dev)
+            elif guided and (g_zero_star or g_rescale > 0.0):   # coefficients reduced on the device, then the update that reads them
+                ab, _ = E.guidance_coeffs(v, u, w, g_zero_star, g_rescale)
+                km = None if edit is None else edit[2]
+                E.guided_euler_(img, v, u, ab, timestep_diff, None if km is None else edit[0], None if km is None else edit[1], km, sigma_next,
+                                v_out=v if wants_preview else None)
+                u = None               # v now holds the guided velocity
+            elif edit is None:         # CFG combine + Euler on img, in place
+                E.cfg_euler_(img, v, u, w, timestep_diff)
+            else:                      # ... and the keep rule
+                E.cfg_euler_edit_(img, v, u, w, timestep_diff, edit[0], edit[1], edit[2], sigma_next)
         if not watch.active:
             continue
         # the per-step paths' side of the watch: the preview of the step just applied (the engine's kernel, the engine's rule for which steps
@@ -483,7 +600,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         preview = x0 = None
         if watch.preview_at(i, n):
             km = None if edit is None else edit[2]
-            rgb, x0 = E.x0_preview(img, v, u, guidance_weight, sigma_next, watch.W, watch.b, source=None if km is None else edit[0],
+            rgb, x0 = E.x0_preview(img, v, u, w, sigma_next, watch.W, watch.b, source=None if km is None else edit[0],
                                    keep_mask=km, want_x0=watch.want_x0)
             preview = rgb.cpu()
         if watch.step(StepInfo(i, n, watch.sample, watch.num_samples, sigma_next, preview, x0)):
@@ -493,7 +610,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
 
 def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                     guidance_weight, scheduler_scale, conf, watch, batch, context, visual_cond, visual_cond_mask, init_latent, strength,
-                    keep_mask):
+                    keep_mask, guide=None):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
     from .models.dit import split_per_sample
     T = img.shape[0] // batch
@@ -512,7 +629,7 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
             cond = torch.cat(cond, dim=-1).reshape(batch, T, *img.shape[1:-1], img.shape[-1] + 1).contiguous()
         sparse_params = get_sparse_params(conf, {"visual": img[:T]}, device)
         timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()
-        with watch.installed(model):
+        with watch.installed(model), _guidance_for_call(model, guide):
             model.sample_many(img.view(batch, T, *img.shape[1:]), timesteps.tolist(), tes, nes, visual_rope_pos, tps, nps,
                                guidance_weight, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params, visual_cond=cond)
         return img
@@ -526,7 +643,7 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         plan = _context_plan(model, T, *context, src, watch.every)
         watch.sample = b
         img[rows] = _generate_one(model, device, img[rows].clone(), num_steps, tes[b], nes[b], visual_rope_pos, tps[b], nps[b], guidance_weight,
-                                  scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km)
+                                  scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide)
     return img
 
 
@@ -568,7 +685,8 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                     text_embedder_device="cuda", progress=True, offload=False, image=None, video=None, strength=1.0, mask=None,
                     callback=None, preview_every=0, preview_factors=None, context_frames=None, context_overlap=None,
                     nag_scale=None, nag_tau=2.5, nag_alpha=0.25, region_text_embeds=None, region_text_rope_pos=None, region_masks=None,
-                    region_base_weight=0.0):
+                    region_base_weight=0.0, guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0,
+                    cfg_rescale=0.0):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -587,8 +705,18 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     `generate`): `caption` is the base prompt, `region_masks` (R, frames, height, width) lies on the latent cells of one sample
     (`conditioning.region_masks_to_latent`).  `region_text_embeds` is a list of already encoded dicts with their `region_text_rope_pos`, or
     a list of R prompt strings: those are encoded by the same embedder call as the caption (only their token embeddings are used) and take
-    positions 0 .. n-1.  One region set for every sample of a batch."""
+    positions 0 .. n-1.  One region set for every sample of a batch.
+    `guidance_schedule`, `guidance_interval`, `cfg_zero_star`, `cfg_zero_init`, `cfg_rescale` (optional, extension): per-step guidance
+    weights, a guidance interval, CFG-Zero* and CFG rescale, passed to `generate` (see there).  All off by default."""
     batch, frames, height, width, channels = shape
+    guide_kw = {k: v for k, v in dict(guidance_schedule=guidance_schedule, guidance_interval=guidance_interval, cfg_zero_star=cfg_zero_star,
+                                      cfg_zero_init=cfg_zero_init, cfg_rescale=cfg_rescale).items() if v}
+    if guide_kw:   # before any model runs: the numbers (what depends on the schedule is checked by `generate`)
+        from .models.dit import check_guidance_args
+        check_guidance_args(None if guidance_schedule is None or callable(guidance_schedule) else guidance_schedule, cfg_zero_star,
+                            cfg_zero_init, cfg_rescale)
+        if guidance_interval is not None:
+            guidance_plan([1.0, 0.0], guidance_weight, None, guidance_interval)
     ctx_kw, window_captions = {}, None
     if context_frames is not None:
         overlap = int(context_frames) // 4 if context_overlap is None else int(context_overlap)
@@ -686,7 +814,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         latent = generate(dit, device, (batch * frames, height, width, channels), num_steps, cond, uncond, grid,
                           text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
                           progress=progress, batch=batch, callback=callback, preview_every=preview_every,
-                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw)
+                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw, **guide_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

@@ -9,6 +9,7 @@ the library, or with CPU tensors, `forward` raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 from torch import nn
@@ -114,6 +115,27 @@ def check_nag_numbers(scale, tau, alpha):
     if not 0.0 <= alpha <= 1.0:
         raise ValueError(f"nag: alpha must be in [0, 1] (got {alpha})")
     return scale, tau, alpha
+
+
+def check_guidance_args(weights, zero_star, zero_init_steps, rescale):
+    """The ValueErrors of `set_guidance` / `generate(guidance_schedule=, cfg_zero_star=, cfg_zero_init=, cfg_rescale=)`; returns
+    (weights as a list of floats or None, zero_star, zero_init_steps, rescale)."""
+    if weights is not None:
+        try:
+            weights = [float(w) for w in weights]
+        except (TypeError, ValueError):
+            raise ValueError("guidance: weights must be a sequence of numbers, one per step") from None
+        if not weights or not all(math.isfinite(w) for w in weights):
+            raise ValueError("guidance: weights must hold one finite number per step")
+    try:
+        k, phi = int(zero_init_steps), float(rescale)
+    except (TypeError, ValueError):
+        raise ValueError("guidance: zero_init_steps must be an integer and rescale a number") from None
+    if k < 0 or k != zero_init_steps:
+        raise ValueError(f"guidance: zero_init_steps must be an integer >= 0 (got {zero_init_steps})")
+    if not 0.0 <= phi <= 1.0:
+        raise ValueError(f"guidance: rescale must be in [0, 1] (got {rescale})")
+    return weights, bool(zero_star), k, phi
 
 
 def check_nag_args(text_embeds, text_rope_pos, scale, tau, alpha):
@@ -235,6 +257,7 @@ class DiffusionTransformer3D(nn.Module):
         self._watch = None           # (trampoline, k5_watch and the arrays it points to) of set_watch: re-installed when the engine is rebuilt
         self._nag = None             # the negative prompt of set_nag, its k5_text_cond and what that points to: re-installed likewise
         self._regions = None         # the prompts and masks of set_regions, their k5_text_cond array and what it points to: likewise
+        self._guidance = None        # the plan of set_guidance (weights list | None, zero_star, zero_init_steps, rescale): likewise
 
     # ---------------------------------------------------------------- engine lifetime
     def _destroy_engine(self, force=False):
@@ -307,6 +330,8 @@ class DiffusionTransformer3D(nn.Module):
             self._install_nag()
         if getattr(self, "_regions", None) is not None:
             self._install_regions()
+        if getattr(self, "_guidance", None) is not None:
+            self._install_guidance()
         if getattr(self, "mag_ratios", None) is not None or getattr(self, "_magcache_calibrate", None) is not None:   # set before the weights were loaded / the handle rebuilt
             from ..magcache_utils import _apply
             _apply(self)
@@ -469,7 +494,8 @@ class DiffusionTransformer3D(nn.Module):
         keep = []
         s.fwd = self._forward_args((frames, H, W), None, self.in_visual_dim, text_embeds["text_embeds"].to(dev), text_embeds["pooled_embed"].to(dev),
                                    0.0, visual_rope_pos, text_rope_pos, scale_factor, sparse_params, keep)
-        if abs(guidance_weight - 1.0) > 1e-6:
+        plan = getattr(self, "_guidance", None)
+        if abs(guidance_weight - 1.0) > 1e-6 or (plan is not None and plan[0] is not None and any(abs(w - 1.0) > 1e-6 for w in plan[0])):
             s.null_cond = self._text_cond(null_text_embeds["text_embeds"].to(dev), null_text_embeds["pooled_embed"].to(dev),
                                           null_text_rope_pos, keep)
         sig = [float(v) for v in sigmas]
@@ -621,6 +647,52 @@ class DiffusionTransformer3D(nn.Module):
             E.check(E.lib().k5_dit_nag_state(self._handle, C.byref(on), C.byref(n), int(bool(reset))), "k5_dit_nag_state")
         return bool(on.value), n.value
 
+    # ---------------------------------------------------------------- guidance plan: per-step weights, CFG-Zero*, CFG rescale
+    def set_guidance(self, weights=None, zero_star=False, zero_init_steps=0, rescale=0.0):
+        """What `sample` / `sample_many` do with the two velocities of a step (k5_dit_set_guidance).  `weights`: one guidance weight per step of
+        the calls to come (`generation_utils.guidance_plan` builds it; None = the call's guidance_weight at every step): a step whose weight is
+        1 runs the conditional forward alone.  `zero_star`: CFG-Zero* — the unconditional velocity is scaled by <c, u> / <u, u> per sample —
+        and `zero_init_steps` = K: the first K steps leave the latent as it is, without a forward.  `rescale` = phi in [0, 1]: CFG rescale,
+        v *= phi std(c) / std(v) + 1 - phi.  The statistics are reduced on the device in a fixed order.  `sample` refuses, before anything
+        runs: a `weights` list of another length than its steps; a plan with guided and unguided steps, or with zero-init, on a CFG pair or
+        with MagCache or its calibration; zero-init with `edit`; any plan with `windows`; zero_star / rescale when every weight is 1.
+        No checkpoint was at hand when this was built: the rules are the published ones, their effect on quality is not measured here."""
+        weights, zero_star, zero_init_steps, rescale = check_guidance_args(weights, zero_star, zero_init_steps, rescale)
+        self._guidance = (weights, zero_star, zero_init_steps, rescale)
+        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
+            try:
+                self._install_guidance()
+            except Exception:
+                self._guidance = None
+                raise
+        return self
+
+    def _install_guidance(self):
+        weights, zero_star, zero_init_steps, rescale = self._guidance
+        g = E.Guidance()
+        arr = None
+        if weights is not None:
+            arr = (C.c_float * len(weights))(*weights)    # copied by the call
+            g.weights, g.num_weights = C.cast(arr, C.POINTER(C.c_float)), len(weights)
+        g.zero_star, g.zero_init_steps, g.rescale = int(zero_star), int(zero_init_steps), float(rescale)
+        E.check(E.lib().k5_dit_set_guidance(self._handle, C.byref(g)), "k5_dit_set_guidance")
+
+    def clear_guidance(self):
+        """Remove the plan: `sample` enqueues exactly what it did before `set_guidance`."""
+        self._guidance = None
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_set_guidance(self._handle, None), "k5_dit_set_guidance")
+        return self
+
+    def guidance_state(self, reset=False):
+        """(on, guided, unguided, zero): whether a plan is set, and how many steps of each kind the engine has enqueued under one
+        (k5_dit_guidance_state).  `reset` zeroes the counts afterwards."""
+        on, a, b, z = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_guidance_state(self._handle, C.byref(on), C.byref(a), C.byref(b), C.byref(z), int(bool(reset))),
+                    "k5_dit_guidance_state")
+        return bool(on.value), a.value, b.value, z.value
+
     # ---------------------------------------------------------------- regional prompts: a prompt per masked region in one forward
     def set_regions(self, text_embeds_list, rope_pos_list, masks, base_weight=0.0):
         """A prompt per masked region inside the cross-attention of ONE forward (k5_dit_set_regions; "attention couple").  `text_embeds_list`:
@@ -764,7 +836,8 @@ class DiffusionTransformer3D(nn.Module):
             raise ValueError("latents must hold at least one sample")
         self._check_visual_cond(visual_cond, latents)
 
-        cfg_on = abs(guidance_weight - 1.0) > 1e-6
+        plan = getattr(self, "_guidance", None)   # a plan's weights may guide where the call's guidance_weight is 1
+        cfg_on = abs(guidance_weight - 1.0) > 1e-6 or (plan is not None and plan[0] is not None and any(abs(w - 1.0) > 1e-6 for w in plan[0]))
         tes, tps = split_per_sample(text_embeds, B, "text_embeds"), split_per_sample(text_rope_pos, B, "text_rope_pos")
         h = self.engine(latents.device)
         dev = latents.device

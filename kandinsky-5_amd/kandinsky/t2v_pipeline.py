@@ -93,7 +93,8 @@ class Kandinsky5T2VPipeline:
                  negative_caption: str = _NEG, expand_prompts: bool = True, save_path: str = None,
                  progress: bool = True, image=None, video=None, strength: float = None, mask=None, callback=None,
                  preview_every: int = 0, preview_factors=None, context_seconds: float = None, context_overlap_seconds: float = None,
-                 nag_scale: float = None, nag_tau: float = 2.5, nag_alpha: float = 0.25, regions=None, region_base_weight: float = 0.0):
+                 nag_scale: float = None, nag_tau: float = 2.5, nag_alpha: float = 0.25, regions=None, region_base_weight: float = 0.0,
+                 guidance_schedule=None, guidance_interval=None, cfg_zero_star: bool = False, cfg_zero_init: int = 0, cfg_rescale: float = 0.0):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -122,8 +123,22 @@ class Kandinsky5T2VPipeline:
         pooled to the latent cells by their mean (`conditioning.region_masks_to_latent`), the region prompts are encoded with the caption
         (not expanded) and every visual block blends its cross-attention to the prompts per token (`DiffusionTransformer3D.set_regions`).  A
         list of texts shares one region set.  Not together with `context_seconds`.  No checkpoint was at hand when this was written:
-        what it does to a picture is not claimed."""
+        what it does to a picture is not claimed.
+        `guidance_schedule`, `guidance_interval`, `cfg_zero_star`, `cfg_zero_init`, `cfg_rescale` (optional, extension): a guidance weight
+        per step (a list of num_steps values or a callable `(i, sigma_i)`), a sigma interval outside which the unconditional forward is
+        not run, CFG-Zero* with its zero-init of the first K steps, and CFG rescale in [0, 1]; see `generate`.  All off by default, every
+        rank passes the same values.  Not together with `context_seconds`.  No checkpoint was at hand when this was written: the rules are
+        the published ones, what they do to a picture is not claimed."""
         ctx = {}
+        guide_kw = {k: v for k, v in dict(guidance_schedule=guidance_schedule, guidance_interval=guidance_interval, cfg_zero_star=cfg_zero_star,
+                                          cfg_zero_init=cfg_zero_init, cfg_rescale=cfg_rescale).items() if v}
+        if guide_kw:
+            from .models.dit import check_guidance_args
+            if context_seconds is not None:
+                raise ValueError("guidance_schedule / guidance_interval / cfg_zero_star / cfg_zero_init / cfg_rescale together with "
+                                 "context_seconds are not supported: one statistic per window is not the published rule")
+            check_guidance_args(None if guidance_schedule is None or callable(guidance_schedule) else guidance_schedule, cfg_zero_star,
+                                cfg_zero_init, cfg_rescale)
         region_kw = {}
         if regions is not None:
             from .conditioning import region_masks_to_latent
@@ -184,6 +199,6 @@ class Kandinsky5T2VPipeline:
                                  device=self.device_map["dit"], vae_device=self.device_map["vae"],
                                  text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload,
                                  image=image, video=video, strength=strength, mask=mask, callback=callback,
-                                 preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw)
+                                 preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw, **guide_kw)
         torch.cuda.empty_cache()
         return self._save(images, time_length, save_path) if self.local_dit_rank == 0 else None

@@ -81,7 +81,36 @@ def build_parser():
                         "--prompt is the base prompt and holds alone where no mask reaches")
     p.add_argument("--region_base_weight", type=float, default=argparse.SUPPRESS, metavar="W",
                    help="with --region: weight of --prompt under the regions, in [0, 1] (default 0)")
+    p.add_argument("--guidance_schedule", type=float, nargs="+", default=argparse.SUPPRESS, metavar="W",
+                   help="a guidance weight per sampling step (as many values as steps); a step of weight 1 runs the conditional forward alone")
+    p.add_argument("--guidance_interval", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("LO", "HI"),
+                   help="guide only on the steps whose sigma lies in [LO, HI] (weight 1, one forward, elsewhere)")
+    p.add_argument("--cfg_zero_star", action="store_true", default=argparse.SUPPRESS,
+                   help="CFG-Zero*: scale the unconditional velocity by its projection on the conditional one, per sample")
+    p.add_argument("--cfg_zero_init", type=int, default=argparse.SUPPRESS, metavar="K", help="CFG-Zero* zero-init: the first K steps leave the latent as it is")
+    p.add_argument("--cfg_rescale", type=float, default=argparse.SUPPRESS, metavar="PHI",
+                   help="CFG rescale: pull the guided velocity's std towards the conditional one's, PHI in [0, 1]")
     return p
+
+
+def guidance_keywords(args):
+    """--guidance_schedule / --guidance_interval / --cfg_zero_star / --cfg_zero_init / --cfg_rescale -> the pipeline's keywords"""
+    kw = {k: getattr(args, k) for k in ("guidance_schedule", "guidance_interval", "cfg_zero_star", "cfg_zero_init", "cfg_rescale") if hasattr(args, k)}
+    if "guidance_schedule" in kw and args.sample_steps is not None and len(kw["guidance_schedule"]) != args.sample_steps:
+        raise ValueError(f"--guidance_schedule holds {len(kw['guidance_schedule'])} weights, --sample_steps is {args.sample_steps}")
+    if "guidance_interval" in kw:
+        lo, hi = kw["guidance_interval"]
+        if not lo <= hi:
+            raise ValueError(f"--guidance_interval needs LO <= HI (got {lo}, {hi})")
+        kw["guidance_interval"] = (lo, hi)
+    if kw.get("cfg_zero_init", 0) < 0:
+        raise ValueError(f"--cfg_zero_init must be >= 0 (got {kw['cfg_zero_init']})")
+    if not 0.0 <= kw.get("cfg_rescale", 0.0) <= 1.0:
+        raise ValueError(f"--cfg_rescale must be in [0, 1] (got {kw['cfg_rescale']})")
+    if kw and hasattr(args, "context_seconds"):
+        raise ValueError("--guidance_schedule / --guidance_interval / --cfg_zero_star / --cfg_zero_init / --cfg_rescale together with "
+                         "--context_seconds are not supported")
+    return kw
 
 
 def region_keywords(args, load_mask=None):
@@ -182,6 +211,7 @@ def main(argv=None):
     validate_args(args)
     nag_kw = nag_keywords(args)   # refused before the models load
     region_kw = region_keywords(args)
+    guide_kw = guidance_keywords(args)
     from kandinsky import get_T2V_pipeline
     pipe = get_T2V_pipeline(device_map={"dit": "cuda:0", "vae": "cuda:0", "text_embedder": "cuda:0"}, conf_path=args.config,
                             offload=args.offload, magcache=args.magcache and not args.calibrate_magcache,
@@ -218,6 +248,7 @@ def main(argv=None):
     edit_kw.update(context_keywords(args))
     edit_kw.update(nag_kw)
     edit_kw.update(region_kw)
+    edit_kw.update(guide_kw)
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
