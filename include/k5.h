@@ -269,7 +269,8 @@ int k5_patchify_cond_bf16(const float* x, const float* vcond, void* out, int T, 
 /* OutLayer un-patchify nn.py:384-399: [Ntok][4C] (c,ph,pw) -> (T,2Hp,2Wp,C) bf16. */
 int k5_unpatchify_bf16(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx,
                        const int32_t* tok_perm, void* stream);
-/* CFG combine + Euler, generation_utils.py:74-76,128.  v_uncond NULL => no guidance. */
+/* CFG combine + Euler, generation_utils.py:74-76,128.  v_uncond NULL => no guidance.  This entry, k5_cfg_euler_edit and k5_guided_euler are
+ * one kernel behind one launcher: a NULL img or v_cond, or n < 1, is K5_ERR_ARG and nothing is launched. */
 int k5_cfg_euler(float* img, const void* v_cond, const void* v_uncond, float w, float dt, int64_t n,
                  void* stream);
 /* Editing kernels (added under ABI 11, as the LoRA and MagCache calibration exports were).  Flow matching: x_sigma = (1 - sigma) x0 + sigma eps.

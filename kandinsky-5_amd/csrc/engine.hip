@@ -2491,14 +2491,15 @@ struct SampleRun {
     }
     {
       Scope sc(d, s, "elementwise");
-      if (vu && stats) {   // the sample's coefficients, reduced and applied on the device
-        K5CHK(k5_launch_guidance_coeffs(vel_c, vel_u, n, w_at(i), plan->zero_star, plan->rescale, g_part, g_sums, g_ab, s, wvec, step_ctr));
-        K5CHK(k5_launch_guided_euler(a->latent, vel_c, vel_u, g_ab, dt[i], edit ? edit->source : nullptr, edit ? edit->noise : nullptr,
-                                     edit ? edit->keep_mask : nullptr, sigma_next[i], n / c.out_visual_dim, c.out_visual_dim,
-                                     want_v ? vel_c : nullptr, s, dtvec, signext, step_ctr));
-      } else if (!edit) K5CHK(k5_launch_cfg_euler(a->latent, vel_c, vu, w_at(i), dt[i], n, s, dtvec, step_ctr));
-      else K5CHK(k5_launch_cfg_euler_edit(a->latent, vel_c, vu, w_at(i), dt[i], edit->source, edit->noise, edit->keep_mask,
-                                          sigma_next[i], n / c.out_visual_dim, c.out_visual_dim, s, dtvec, signext, step_ctr));
+      const bool coeffs = vu && stats;   // the sample's coefficients, reduced and applied on the device
+      if (coeffs) K5CHK(k5_launch_guidance_coeffs(vel_c, vel_u, n, w_at(i), plan->zero_star, plan->rescale, g_part, g_sums, g_ab, s, wvec, step_ctr));
+      K5EulerStepArgs e;
+      e.img = a->latent; e.v_cond = vel_c; e.v_uncond = vu; e.w = w_at(i); e.dt = dt[i];
+      if (coeffs) { e.ab = g_ab; e.v_out = want_v ? vel_c : nullptr; }
+      if (edit) { e.source = edit->source; e.noise = edit->noise; e.keep_mask = edit->keep_mask; e.sigma_next = sigma_next[i]; e.signext = signext; }
+      e.cells = cells; e.C = c.out_visual_dim;
+      e.dtvec = dtvec; e.step = step_ctr; e.stream = s;
+      K5CHK(k5_launch_euler_step(e));
     }
     if (step_ctr) K5CHK(k5_launch_step_inc(step_ctr, s));
     return K5_OK;
@@ -2612,7 +2613,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     r.cfg_on = guided > 0;   // the unconditional side is sized before the loop, wherever its first step is
     r.stats = gd.stats() && guided > 0;
     r.want_v = r.stats && wt.on && wt.every > 0;
-    // cfg_euler_kernel takes its weight by value: without coefficients only a constant weight replays
+    // euler_step_kernel takes its CFG weight by value: without coefficients only a constant weight replays
     uniform = first == 0 && !(guided && unguided) && (r.stats || !guided || const_w);
     if (r.stats) {
       K5CHK(gd.ws.ensure(64 + (size_t)k5_guidance_blocks(r.n) * 5 * sizeof(double)));

@@ -369,7 +369,11 @@ int k5_unpatchify_bf16(const void* x, void* out, int T, int Hp, int Wp, int C, i
 }
 
 int k5_cfg_euler(float* img, const void* v_cond, const void* v_uncond, float w, float dt, int64_t n, void* stream) {
-  return ret(k5_launch_cfg_euler(img, v_cond, v_uncond, w, dt, n, (hipStream_t)stream), "k5_cfg_euler");
+  K5EulerStepArgs a;
+  a.img = img; a.v_cond = v_cond; a.v_uncond = v_uncond; a.w = w; a.dt = dt;
+  a.cells = n; a.C = 1;   // C only matters with a mask
+  a.stream = (hipStream_t)stream;
+  return ret(k5_launch_euler_step(a), "k5_cfg_euler");
 }
 
 int k5_edit_renoise(float* out, const float* source, const float* noise, float sigma, int64_t n, void* stream) {
@@ -378,8 +382,12 @@ int k5_edit_renoise(float* out, const float* source, const float* noise, float s
 
 int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source, const float* noise,
                       const float* keep_mask, float sigma_next, int64_t cells, int C, void* stream) {
-  return ret(k5_launch_cfg_euler_edit(img, v_cond, v_uncond, w, dt, source, noise, keep_mask, sigma_next, cells, C, (hipStream_t)stream),
-             "k5_cfg_euler_edit");
+  K5EulerStepArgs a;
+  a.img = img; a.v_cond = v_cond; a.v_uncond = v_uncond; a.w = w; a.dt = dt;
+  a.source = source; a.noise = noise; a.keep_mask = keep_mask; a.sigma_next = sigma_next;
+  a.cells = cells; a.C = C;
+  a.stream = (hipStream_t)stream;
+  return ret(k5_launch_euler_step(a), "k5_cfg_euler_edit");
 }
 
 int k5_guidance_stats_blocks(int64_t n) { return k5_guidance_blocks(n); }
@@ -398,7 +406,12 @@ int k5_guidance_coeffs_bf16(const void* v_cond, const void* v_uncond, int64_t n,
 
 int k5_guided_euler(float* img, const void* v_cond, const void* v_uncond, const float* ab, float dt, const float* source, const float* noise,
                     const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, void* stream) {
-  const int st = k5_launch_guided_euler(img, v_cond, v_uncond, ab, dt, source, noise, keep_mask, sigma_next, cells, C, v_out, (hipStream_t)stream);
+  K5EulerStepArgs a;
+  a.img = img; a.v_cond = v_cond; a.v_uncond = v_uncond; a.ab = ab; a.dt = dt;
+  a.source = source; a.noise = noise; a.keep_mask = keep_mask; a.sigma_next = sigma_next;
+  a.cells = cells; a.C = C; a.v_out = v_out;
+  a.stream = (hipStream_t)stream;
+  const int st = ab ? k5_launch_euler_step(a) : K5_ERR_ARG;   // without ab the launcher would take the CFG combine
   if (st == K5_ERR_ARG) {
     k5_set_error("k5_guided_euler: need img, v_cond, v_uncond and ab, cells and C >= 1, and source and noise with a keep_mask (cells %lld, C %d)",
                  (long long)cells, C);

@@ -173,17 +173,25 @@ int k5_launch_patchify_cond(const float* x, const float* vcond, void* out, int T
 // un-patchify (K17 tail): [Ntok][C*4] bf16 (feature order c,ph,pw) -> (T,H,W,C) bf16, token perm optional
 int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx,
                          const int32_t* tok_perm, hipStream_t stream);
-// K18: CFG combine + Euler.  v = cond (bf16) or bf16(u + bf16(w * bf16(c-u))); img += float(bf16(dt*v))
-int k5_launch_cfg_euler(float* img, const void* v_cond, const void* v_uncond, float w, float dt, int64_t n,
-                        hipStream_t stream, const float* dtvec = nullptr, const int* step = nullptr);
+// K18: the sampler's update of one step on cells * C elements, one pass over img.  The velocity: v = cond (bf16) when v_uncond is null, else
+// bf16(u + bf16(w * bf16(c - u))) (CFG), or with ab = {alpha, beta} fp32 on the device (k5_launch_guidance_coeffs writes it)
+// bf16(rn(rn(alpha c) + rn(beta u))).  The step: img += float(bf16(dt * v)).  The keep rule (keep_mask fp32 [cells], null = none): with
+// known = rn(rn((1 - sigma_next) source) + rn(sigma_next noise)) the cells of mask 1 take known, those of mask 0 keep the Euler result and the
+// others x + m * (known - x), nothing contracted.  v_out (bf16 [cells * C], may be v_cond) receives v.  dtvec / signext / step: the captured step
+// reads dt (and, when signext is given, sigma_next) at the device step counter.
+// K5_ERR_ARG: img or v_cond null, cells or C < 1, ab without v_uncond, v_out without ab, keep_mask without source and noise, dtvec without step
+// or step without dtvec, signext without dtvec.  Nothing is launched when it refuses.
+struct K5EulerStepArgs {
+  float* img = nullptr; const void* v_cond = nullptr; const void* v_uncond = nullptr;
+  float w = 1.f; const float* ab = nullptr; float dt = 0.f;
+  const float* source = nullptr; const float* noise = nullptr; const float* keep_mask = nullptr; float sigma_next = 0.f;
+  int64_t cells = 0; int C = 1; void* v_out = nullptr;
+  const float* dtvec = nullptr; const float* signext = nullptr; const int* step = nullptr;
+  hipStream_t stream = nullptr;
+};
+int k5_launch_euler_step(const K5EulerStepArgs& a);
 // editing: out = rn(rn((1 - sigma) * source) + rn(sigma * noise)), nothing contracted
 int k5_launch_edit_renoise(float* out, const float* source, const float* noise, float sigma, int64_t n, hipStream_t stream);
-// K18 + keep mask: the update of k5_launch_cfg_euler on cells * C elements, then with known = renoise(sigma_next) the cells of mask 1 take
-// known, those of mask 0 keep the Euler result and the others x + m * (known - x) (uncontracted); keep_mask fp32 [cells] or null (= K18's bits).
-// dtvec / signext / step: the captured step reads dt and sigma_next at the device step counter.
-int k5_launch_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source,
-                             const float* noise, const float* keep_mask, float sigma_next, int64_t cells, int C, hipStream_t stream,
-                             const float* dtvec = nullptr, const float* signext = nullptr, const int* step = nullptr);
 // guidance coefficients of one sample: the five float64 sums Sc, Su, Scc, Suu, Scu of the bf16 velocities v_cond / v_uncond [n] in a fixed order
 // (no atomics: the same bits on every launch, rank and handle) into sums[5], then ab = {alpha, beta} (fp32) of v = alpha c + beta u:
 // s = zero_star ? Scu / (Suu + 1e-8) : 1, alpha = w, beta = s (1 - w), both times rescale * sqrt(var c / var v) + 1 - rescale when rescale > 0.
@@ -192,11 +200,6 @@ int k5_launch_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncon
 int k5_guidance_blocks(int64_t n);
 int k5_launch_guidance_coeffs(const void* v_cond, const void* v_uncond, int64_t n, float w, int zero_star, float rescale, double* part,
                               double* sums, float* ab, hipStream_t stream, const float* wvec = nullptr, const int* step = nullptr);
-// k5_launch_cfg_euler_edit with the combine v = bf16(rn(rn(alpha c) + rn(beta u))), ab = {alpha, beta} fp32 on the device; v_out (bf16 [cells * C],
-// nullable, may be v_cond) receives v.  keep_mask null = no edit tail.
-int k5_launch_guided_euler(float* img, const void* v_cond, const void* v_uncond, const float* ab, float dt, const float* source,
-                           const float* noise, const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, hipStream_t stream,
-                           const float* dtvec = nullptr, const float* signext = nullptr, const int* step = nullptr);
 // K18 over temporal context windows: img fp32 [T][frame_elems]; v_cond / v_uncond (null = no guidance) bf16 [nwin][F][frame_elems], window i
 // covering frames starts[i] .. starts[i] + F - 1 (device int32 [nwin]) with the share weights[i][j] (device fp32 [nwin][F]) of its local frame j.
 // Per element the windows that cover its frame are walked in order: v_i as K18 forms it, acc = wt_0 * v_0, then acc = acc + wt_i * v_i

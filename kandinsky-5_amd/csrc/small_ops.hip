@@ -10,7 +10,7 @@
 //   TextEmbeddings.norm     nn.py:67,72                        -> ln_affine_kernel       (K13)
 //   VisualEmbeddings patchify nn.py:81-95 (+ fractal_flatten models/utils.py:31-41) -> patchify_kernel
 //   OutLayer un-patchify    nn.py:384-399 (+ fractal_unflatten :44-51)             -> unpatchify_kernel
-//   CFG combine + Euler     generation_utils.py:74-76,128      -> cfg_euler_kernel       (K18)
+//   CFG combine + Euler     generation_utils.py:74-76,128      -> euler_step_kernel      (K18)
 //   RoPE1D/RoPE3D tables    nn.py:99-150                        -> rope_table_kernel      (K15)
 #include <stdlib.h>
 
@@ -604,18 +604,18 @@ __global__ __launch_bounds__(256) void unpatchify_kernel(const bf16_t* __restric
   }
 }
 
-__global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ img, const bf16_t* __restrict__ vc,
-                                                        const bf16_t* __restrict__ vu, float w, float dt,
-                                                        const float* __restrict__ dtvec, const int* __restrict__ step, int64_t n) {
-  if (dtvec) dt = dtvec[*step];
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
-    float v = bf2f(vc[g]);
-    if (vu) {  // uncond + w * (cond - uncond), each eager bf16 op rounds (generation_utils.py:74-76)
-      const float u = bf2f(vu[g]);
-      v = bf_round(__fadd_rn(u, bf_round(__fmul_rn(w, bf_round(__fsub_rn(v, u))))));
-    }
-    img[g] = __fadd_rn(img[g], bf_round(__fmul_rn(dt, v)));  // :128, (0-dim fp32)*(bf16) -> bf16
-  }
+// Element k of a vector of packed bf16 pairs (u32x2 / u32x4) as float: the low half of a word is the element of the lower index.
+template <typename V>
+__device__ __forceinline__ float bf16_at(V r, int k) {
+  const uint32_t p = r[k >> 1];
+  return __uint_as_float((k & 1) ? (p & 0xffff0000u) : (p << 16));
+}
+
+// The CFG combine, uncond + w * (cond - uncond), with each eager bf16 op rounded (generation_utils.py:74-76): bf16 after the difference, after
+// the product and after the sum.  Every product feeds a bf16 rounding before it meets an add, so nothing here can contract and no pragma is
+// needed; keep it that way.  The step, the windows and the preview all combine through this one function: their bits agree by construction.
+__device__ __forceinline__ float cfg_velocity(float w, float c, float u) {
+  return bf_round(__fadd_rn(u, bf_round(__fmul_rn(w, bf_round(__fsub_rn(c, u))))));
 }
 
 // Editing (video-to-video, keep mask): x_sigma = (1 - sigma) * x0 + sigma * eps with each of the three operations rounded to fp32 on its own, so
@@ -638,37 +638,52 @@ __device__ __forceinline__ float keep_blend(float x, float known, float m) {
   const float md = m * d;
   return x + md;
 }
+// v = bf16(alpha * c + beta * u) with the two products and the sum rounded to fp32 each on its own (the pragma: see renoise_at)
+__device__ __forceinline__ float guided_velocity(float alpha, float beta, float c, float u) {
+#pragma clang fp contract(off)
+  const float p = alpha * c;
+  const float q = beta * u;
+  return bf_round(p + q);
+}
+
+// The sampler's update of one step, one pass over the latent (K18): the velocity is v = guided_velocity(ab[0], ab[1], c, u) with coefficients
+// from device memory (guidance_finish_kernel wrote them), else cfg_velocity(w, c, u), else (vu NULL) c itself; img += bf16(dt * v)
+// (generation_utils.py:128, (0-dim fp32) * (bf16) -> bf16); then, under a keep mask, the keep rule at sigma_next: element g of cell g / C reads
+// mask[g / C].  v_out (nullable, may be vc, hence no __restrict__ on either: element g is read before it is written, by the same thread)
+// receives v, for the watch's preview.  In the captured step dt and sigma_next come from the device tables at the device step counter;
+// signext is given only when something reads sigma_next.  Two instantiations, coefficients from the device (AB: ab and v_out are read) or not:
+// with that choice made at run time the plain update measured 1.1 - 1.6 us slower per launch at the 5 s clip's 3.0 M elements.
+template <bool AB>
+__global__ __launch_bounds__(256) void euler_step_kernel(float* __restrict__ img, const bf16_t* vc, const bf16_t* __restrict__ vu, float w,
+                                                         const float* __restrict__ ab, float dt, const float* __restrict__ x0,
+                                                         const float* __restrict__ eps, const float* __restrict__ mask, float sigma_next,
+                                                         int C, bf16_t* v_out, const float* __restrict__ dtvec,
+                                                         const float* __restrict__ signext, const int* __restrict__ step, int64_t n) {
+  if (dtvec) dt = dtvec[*step];
+  if (signext) sigma_next = signext[*step];
+  const float alpha = AB ? ab[0] : 0.0f, beta = AB ? ab[1] : 0.0f;
+  const float a = 1.0f - sigma_next;
+  const bf16_t* up = vu ? vu : vc;   // without guidance u is unused: the same address again costs no traffic, a branch around the load would cost a wait
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
+    // every load that does not hang on a value first, so that they are in flight together: a thread has one or two elements, latency is the cost
+    const bf16_t cb = vc[g];
+    const bf16_t ub = up[g];
+    float x = img[g];
+    const float m = mask ? mask[g / C] : 0.0f;
+    const float c = bf2f(cb), u = bf2f(ub);
+    const float v = AB ? guided_velocity(alpha, beta, c, u) : (vu ? cfg_velocity(w, c, u) : c);
+    x = __fadd_rn(x, bf_round(__fmul_rn(dt, v)));
+    if (m != 0.0f) x = keep_blend(x, renoise_at(a, sigma_next, x0[g], eps[g]), m);
+    img[g] = x;
+    if (AB && v_out) v_out[g] = f2bf(v);
+  }
+}
 
 __global__ __launch_bounds__(256) void edit_renoise_kernel(float* __restrict__ out, const float* __restrict__ x0,
                                                            const float* __restrict__ eps, float sigma, int64_t n) {
   const float a = 1.0f - sigma;
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256)
     out[g] = renoise_at(a, sigma, x0[g], eps[g]);
-}
-
-// cfg_euler_kernel (the same expressions, the same bits) followed by the keep rule at sigma_next, one pass: element g of cell g / C reads
-// mask[g / C].  In the captured step dt and sigma_next come from the device tables at the device step counter.
-__global__ __launch_bounds__(256) void cfg_euler_edit_kernel(float* __restrict__ img, const bf16_t* __restrict__ vc,
-                                                             const bf16_t* __restrict__ vu, float w, float dt,
-                                                             const float* __restrict__ x0, const float* __restrict__ eps,
-                                                             const float* __restrict__ mask, float sigma_next, int C,
-                                                             const float* __restrict__ dtvec, const float* __restrict__ signext,
-                                                             const int* __restrict__ step, int64_t n) {
-  if (dtvec) { dt = dtvec[*step]; sigma_next = signext[*step]; }
-  const float a = 1.0f - sigma_next;
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
-    float v = bf2f(vc[g]);
-    if (vu) {
-      const float u = bf2f(vu[g]);
-      v = bf_round(__fadd_rn(u, bf_round(__fmul_rn(w, bf_round(__fsub_rn(v, u))))));
-    }
-    float x = __fadd_rn(img[g], bf_round(__fmul_rn(dt, v)));
-    if (mask) {
-      const float m = mask[g / C];
-      if (m != 0.0f) x = keep_blend(x, renoise_at(a, sigma_next, x0[g], eps[g]), m);
-    }
-    img[g] = x;
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -693,14 +708,10 @@ __global__ __launch_bounds__(256) void guidance_stats_kernel(const bf16_t* __res
     const u32x4 rc = *reinterpret_cast<const u32x4*>(vc + g * 8);
     const u32x4 ru = *reinterpret_cast<const u32x4*>(vu + g * 8);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {   // low half first: the element of the lower index
-        const double c = (double)__uint_as_float(h ? rc[j] & 0xffff0000u : rc[j] << 16);
-        const double u = (double)__uint_as_float(h ? ru[j] & 0xffff0000u : ru[j] << 16);
-        acc[0] += c; acc[1] += u;
-        acc[2] += c * c; acc[3] += u * u; acc[4] += c * u;   // the products are exact, fused or not
-      }
+    for (int k = 0; k < 8; ++k) {   // element index order: the low half of a word first
+      const double c = (double)bf16_at(rc, k), u = (double)bf16_at(ru, k);
+      acc[0] += c; acc[1] += u;
+      acc[2] += c * c; acc[3] += u * u; acc[4] += c * u;   // the products are exact, fused or not
     }
   }
 #pragma unroll
@@ -754,37 +765,6 @@ __global__ __launch_bounds__(320) void guidance_finish_kernel(const double* __re
   }
 }
 
-// v = bf16(alpha * c + beta * u) with the two products and the sum rounded to fp32 each on its own (the pragma: see renoise_at)
-__device__ __forceinline__ float guided_velocity(float alpha, float beta, float c, float u) {
-#pragma clang fp contract(off)
-  const float p = alpha * c;
-  const float q = beta * u;
-  return bf_round(p + q);
-}
-
-// cfg_euler_edit_kernel with the combine replaced: the coefficients come from device memory (guidance_finish_kernel wrote them), the rest — the
-// bf16 rounding of dt * v, the fp32 update, the keep rule at sigma_next — is that kernel's.  v_out (nullable, may be vc: element g is read
-// before it is written, by the same thread) receives the guided velocity, for the watch's preview.
-__global__ __launch_bounds__(256) void guided_euler_kernel(float* __restrict__ img, const bf16_t* vc, const bf16_t* __restrict__ vu,
-                                                           const float* __restrict__ ab, float dt, const float* __restrict__ x0,
-                                                           const float* __restrict__ eps, const float* __restrict__ mask, float sigma_next,
-                                                           int C, bf16_t* v_out, const float* __restrict__ dtvec,
-                                                           const float* __restrict__ signext, const int* __restrict__ step, int64_t n) {
-  if (dtvec) { dt = dtvec[*step]; sigma_next = signext[*step]; }
-  const float alpha = ab[0], beta = ab[1];
-  const float a = 1.0f - sigma_next;
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
-    const float v = guided_velocity(alpha, beta, bf2f(vc[g]), bf2f(vu[g]));
-    float x = __fadd_rn(img[g], bf_round(__fmul_rn(dt, v)));
-    if (mask) {
-      const float m = mask[g / C];
-      if (m != 0.0f) x = keep_blend(x, renoise_at(a, sigma_next, x0[g], eps[g]), m);
-    }
-    img[g] = x;
-    if (v_out) v_out[g] = f2bf(v);
-  }
-}
-
 // Temporal context windows: one term of the cross-fade, acc = wt_0 * v_0 for the first window that covers the frame and acc + wt_i * v_i for
 // every later one.  The product and the sum round to fp32 each on its own (the pragma: see renoise_at), so the torch expression with separate
 // ops is the oracle bit for bit, and one window of weight 1 leaves v itself.
@@ -795,10 +775,10 @@ __device__ __forceinline__ float window_term(float acc, float wt, float v, bool 
   return acc + p;
 }
 
-// cfg_euler_kernel over a clip of T frames whose velocities come from nwin windows of F frames: vc / vu [nwin][F][frame_elems] bf16, window i
+// euler_step_kernel's CFG update over a clip of T frames whose velocities come from nwin windows of F frames: vc / vu [nwin][F][frame_elems] bf16, window i
 // covers frames starts[i] .. starts[i] + F - 1 and weights[i][j] is the share of its local frame j.  One pass over img: a lane owns VEC
 // consecutive elements of one frame (frame = g / (frame_elems / VEC), VEC divides frame_elems, so no lane straddles two frames), walks the
-// windows in order, forms each window's guided velocity with cfg_euler_kernel's expression and rounding points, blends (window_term) and
+// windows in order, forms each window's guided velocity with cfg_velocity, blends (window_term) and
 // applies img += bf16(dt * acc).  Only slots (i, t - starts[i]) with 0 <= t - starts[i] < F are read, so whatever the tables hold no read
 // leaves the [nwin][F] velocity buffers; a frame no window covers is left as it is.
 template <int VEC>
@@ -824,19 +804,12 @@ __global__ __launch_bounds__(256) void cfg_euler_windows_kernel(float* __restric
         if (vu) ur = *reinterpret_cast<const u32x2*>(vu + off);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const uint32_t cw = cr[k >> 1], uw = ur[k >> 1];
-          v[k] = __uint_as_float((k & 1) ? (cw & 0xffff0000u) : (cw << 16));
-          if (vu) {  // as cfg_euler_kernel
-            const float u = __uint_as_float((k & 1) ? (uw & 0xffff0000u) : (uw << 16));
-            v[k] = bf_round(__fadd_rn(u, bf_round(__fmul_rn(w, bf_round(__fsub_rn(v[k], u))))));
-          }
+          v[k] = bf16_at(cr, k);
+          if (vu) v[k] = cfg_velocity(w, v[k], bf16_at(ur, k));
         }
       } else {
         v[0] = bf2f(vc[off]);
-        if (vu) {
-          const float u = bf2f(vu[off]);
-          v[0] = bf_round(__fadd_rn(u, bf_round(__fmul_rn(w, bf_round(__fsub_rn(v[0], u))))));
-        }
+        if (vu) v[0] = cfg_velocity(w, v[0], bf2f(vu[off]));
       }
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] = window_term(first ? 0.0f : acc[k], wt, v[k], first);
@@ -1078,29 +1051,19 @@ int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C,
   return done();
 }
 
-int k5_launch_cfg_euler(float* img, const void* vc, const void* vu, float w, float dt, int64_t n, hipStream_t s,
-                        const float* dtvec, const int* step) {
-  if (n <= 0 || ((dtvec != nullptr) != (step != nullptr))) return K5_ERR_ARG;
-  hipLaunchKernelGGL(cfg_euler_kernel, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, w,
-                     dt, dtvec, step, n);
+int k5_launch_euler_step(const K5EulerStepArgs& a) {
+  if (!a.img || !a.v_cond || a.cells <= 0 || a.C <= 0) return K5_ERR_ARG;
+  if ((a.ab && !a.v_uncond) || (a.v_out && !a.ab) || (a.keep_mask && (!a.source || !a.noise))) return K5_ERR_ARG;
+  if (((a.dtvec != nullptr) != (a.step != nullptr)) || (a.signext && !a.dtvec)) return K5_ERR_ARG;
+  const int64_t n = a.cells * a.C;
+  hipLaunchKernelGGL(a.ab ? euler_step_kernel<true> : euler_step_kernel<false>, dim3(grid_for(n)), dim3(256), 0, a.stream, a.img, (const bf16_t*)a.v_cond, (const bf16_t*)a.v_uncond,
+                     a.w, a.ab, a.dt, a.source, a.noise, a.keep_mask, a.sigma_next, a.C, (bf16_t*)a.v_out, a.dtvec, a.signext, a.step, n);
   return done();
 }
 
 int k5_launch_edit_renoise(float* out, const float* source, const float* noise, float sigma, int64_t n, hipStream_t s) {
   if (!out || !source || !noise || n <= 0) return K5_ERR_ARG;
   hipLaunchKernelGGL(edit_renoise_kernel, dim3(grid_for(n)), dim3(256), 0, s, out, source, noise, sigma, n);
-  return done();
-}
-
-int k5_launch_cfg_euler_edit(float* img, const void* vc, const void* vu, float w, float dt, const float* source, const float* noise,
-                             const float* keep_mask, float sigma_next, int64_t cells, int C, hipStream_t s, const float* dtvec,
-                             const float* signext, const int* step) {
-  if (!img || !vc || cells <= 0 || C <= 0 || ((dtvec != nullptr) != (step != nullptr)) || ((dtvec != nullptr) != (signext != nullptr)))
-    return K5_ERR_ARG;
-  if (keep_mask && (!source || !noise)) return K5_ERR_ARG;
-  const int64_t n = cells * C;
-  hipLaunchKernelGGL(cfg_euler_edit_kernel, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, w, dt, source,
-                     noise, keep_mask, sigma_next, C, dtvec, signext, step, n);
   return done();
 }
 
@@ -1120,19 +1083,6 @@ int k5_launch_guidance_coeffs(const void* vc, const void* vu, int64_t n, float w
   hipLaunchKernelGGL(guidance_stats_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)vc, (const bf16_t*)vu, part, n / 8);
   hipLaunchKernelGGL(guidance_finish_kernel, dim3(1), dim3(320), 0, s, (const double*)part, grid, (double)n, w, zero_star, rescale, wvec, step,
                      sums, ab);
-  return done();
-}
-
-int k5_launch_guided_euler(float* img, const void* vc, const void* vu, const float* ab, float dt, const float* source, const float* noise,
-                           const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, hipStream_t s, const float* dtvec,
-                           const float* signext, const int* step) {
-  if (!img || !vc || !vu || !ab || cells <= 0 || C <= 0 || ((dtvec != nullptr) != (step != nullptr)) ||
-      ((dtvec != nullptr) != (signext != nullptr)))
-    return K5_ERR_ARG;
-  if (keep_mask && (!source || !noise)) return K5_ERR_ARG;
-  const int64_t n = cells * C;
-  hipLaunchKernelGGL(guided_euler_kernel, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, ab, dt, source, noise,
-                     keep_mask, sigma_next, C, (bf16_t*)v_out, dtvec, signext, step, n);
   return done();
 }
 
@@ -1319,8 +1269,8 @@ int k5_launch_lora_merge(void* W, int w_dtype, int rows, int cols, int ld, const
 namespace {
 
 // Live preview of the sampler (the watch of k5_dit_set_watch, k5_x0_preview): after the update of a step the latent x sits at sigma_next and the
-// velocity buffers still hold that step's velocities, so the denoised estimate of flow matching is x0 = x - sigma_next * v with v combined as
-// in cfg_euler_kernel (the same expression, the same bf16 rounding points).  The product and the difference round to fp32 each on its own
+// velocity buffers still hold that step's velocities, so the denoised estimate of flow matching is x0 = x - sigma_next * v with v combined by
+// cfg_velocity (the step kernel's combine).  The product and the difference round to fp32 each on its own
 // (nothing contracted), sigma_next == 0 hands x through, and with a keep mask x0 = keep_blend(x0, source, m): kept cells show the source.
 __device__ __forceinline__ float x0_estimate(float x, float sigma, float v) {
 #pragma clang fp contract(off)
@@ -1362,12 +1312,8 @@ __global__ __launch_bounds__(256) void x0_preview_kernel(const float* __restrict
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const uint32_t cw = cr[k >> 1], uw = ur[k >> 1];
-          float v = __uint_as_float((k & 1) ? (cw & 0xffff0000u) : (cw << 16));
-          if (vu) {  // as cfg_euler_kernel
-            const float u = __uint_as_float((k & 1) ? (uw & 0xffff0000u) : (uw << 16));
-            v = bf_round(__fadd_rn(u, bf_round(__fmul_rn(w, bf_round(__fsub_rn(v, u))))));
-          }
+          float v = bf16_at(cr, k);
+          if (vu) v = cfg_velocity(w, v, bf16_at(ur, k));
           float z = sigma_next == 0.0f ? xv[k] : x0_estimate(xv[k], sigma_next, v);
           if (m != 0.0f) z = keep_blend(z, sv[k], m);
           o[k] = z;
@@ -1450,9 +1396,7 @@ __global__ __launch_bounds__(256) void nag_combine_kernel(const bf16_t* zp, cons
     if (lane + 64 * i < nch) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const uint32_t pw = rp[i][j >> 1], nw = rn[i][j >> 1];
-        const float p = __uint_as_float((j & 1) ? (pw & 0xffff0000u) : (pw << 16));
-        const float q = __uint_as_float((j & 1) ? (nw & 0xffff0000u) : (nw << 16));
+        const float p = bf16_at(rp[i], j), q = bf16_at(rn[i], j);
         g[i][j] = fmaf(sm1, __fsub_rn(p, q), p);
         n_pos = __fadd_rn(n_pos, fabsf(p));
         n_g = __fadd_rn(n_g, fabsf(g[i][j]));
@@ -1469,9 +1413,7 @@ __global__ __launch_bounds__(256) void nag_combine_kernel(const bf16_t* zp, cons
       float o[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const uint32_t pw = rp[i][j >> 1];
-        const float p = __uint_as_float((j & 1) ? (pw & 0xffff0000u) : (pw << 16));
-        o[j] = nag_blend(p, g[i][j], f, alpha);
+        o[j] = nag_blend(bf16_at(rp[i], j), g[i][j], f, alpha);
       }
       const u32x4 pk = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
       *reinterpret_cast<u32x4*>(out + base + 8 * ch) = pk;
@@ -1541,8 +1483,7 @@ __global__ __launch_bounds__(256) void region_combine_kernel(const bf16_t* z0, c
       if (lane + 64 * i < nch) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const uint32_t pw = raw[i][j >> 1];
-          const float v = __uint_as_float((j & 1) ? (pw & 0xffff0000u) : (pw << 16));
+          const float v = bf16_at(raw[i], j);
           acc[i][j] = first ? region_first(wk, v) : region_next(wk, v, acc[i][j]);
         }
       }

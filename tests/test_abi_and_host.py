@@ -92,6 +92,23 @@ def test_engine_rejects_bad_config_without_gpu(built_lib):
     E.lib().k5_dit_destroy(h)
 
 
+def test_step_update_entries_refuse_without_gpu(built_lib):
+    """The three entries of the sampler's update share one launcher and one set of refusals: a NULL img, a NULL v_cond and a keep mask without
+    its source are K5_ERR_ARG before any HIP call.  The pointers are host memory: a refusal never reads them, and nothing here may launch."""
+    import ctypes as C
+    from kandinsky import _engine as E
+    L = E.lib()
+    buf = [C.create_string_buffer(64) for _ in range(6)]
+    img, vc, vu, ab, noise, mask = (C.addressof(b) for b in buf)
+    cfg = lambda img, vc: L.k5_cfg_euler(img, vc, vu, 5.0, -0.0625, 8, None)
+    edit = lambda img, vc, m=None: L.k5_cfg_euler_edit(img, vc, vu, 5.0, -0.0625, None, noise, m, 0.5, 4, 2, None)
+    guided = lambda img, vc, m=None: L.k5_guided_euler(img, vc, vu, ab, -0.0625, None, noise, m, 0.5, 4, 2, None, None)
+    for entry in (cfg, edit, guided):
+        assert entry(None, vc) == 1 and entry(img, None) == 1
+    assert edit(img, vc, mask) == 1 and guided(img, vc, mask) == 1
+    assert "k5_guided_euler: need img, v_cond, v_uncond and ab" in E.last_error()
+
+
 def test_state_dict_layout_matches_reference_manifest():
     from kandinsky.models.dit import DiffusionTransformer3D
     from oracle import k5_oracle as O

@@ -443,6 +443,61 @@ def test_cfg_euler(E):
     assert torch.equal(d.cpu(), img + bfr(dt * c))
 
 
+@pytest.mark.parametrize("w,guided", [(1.0, False), (5.0, True)])
+def test_step_update_entries_agree(E, w, guided):
+    """One kernel behind k5_cfg_euler and k5_cfg_euler_edit: the plain entry, the edit entry without a mask and the edit entry with an all-zero
+    mask give the same bits (and the torch expression's)."""
+    cells, Cc = 5 * 7, 16
+    n = cells * Cc
+    img, c, u = rnd(n, seed=1).cuda(), rnd(n, seed=2).cuda().to(BF), rnd(n, seed=3).cuda().to(BF)
+    x0, eps, zero = rnd(n, seed=4).cuda(), rnd(n, seed=5).cuda(), torch.zeros(cells, device="cuda")
+    dt, up, L, s = -0.0625, u.data_ptr() if guided else None, E.lib(), E.stream_ptr()
+    cf, uf = c.float(), u.float()
+    want = img + (dt * ((uf + (w * (cf - uf).to(BF).float()).to(BF).float()).to(BF).float() if guided else cf)).to(BF).float()
+    plain, nomask, zeromask = img.clone(), img.clone(), img.clone()
+    E.check(L.k5_cfg_euler(plain.data_ptr(), c.data_ptr(), up, w, dt, n, s), "k5_cfg_euler")
+    E.check(L.k5_cfg_euler_edit(nomask.data_ptr(), c.data_ptr(), up, w, dt, None, None, None, 0.37, cells, Cc, s), "k5_cfg_euler_edit")
+    E.check(L.k5_cfg_euler_edit(zeromask.data_ptr(), c.data_ptr(), up, w, dt, x0.data_ptr(), eps.data_ptr(), zero.data_ptr(), 0.37, cells, Cc, s),
+            "k5_cfg_euler_edit")
+    assert torch.equal(plain, want) and torch.equal(nomask, plain) and torch.equal(zeromask, plain)
+
+
+def test_step_update_grid_stride(E):
+    """More elements than the capped grid has threads: some threads take a second trip and the last trip is ragged.  k5_cfg_euler against the
+    expression of test_cfg_euler; k5_guided_euler with a keep mask per element (C = 1), without v_out and with v_out on v_cond, against the
+    expression of test_guided_euler_bit_exact.  The guard regions behind the latent and the velocity stay as they were."""
+    import numpy as np
+    n, G = 8192 * 256 + 257, 64
+    f32 = lambda v: float(np.float32(v))
+    img, c, u = rnd(n, seed=1), bfr(rnd(n, seed=2)), bfr(rnd(n, seed=3))
+    L, s = E.lib(), E.stream_ptr()
+    w, dt = 5.0, -0.0625
+    buf = torch.full((n + G,), 7.0, device="cuda")
+    buf[:n] = img
+    cd, ud = c.cuda().to(BF), u.cuda().to(BF)
+    E.check(L.k5_cfg_euler(buf.data_ptr(), cd.data_ptr(), ud.data_ptr(), w, dt, n, s), "k5_cfg_euler")
+    assert torch.equal(buf[:n].cpu(), img + bfr(dt * bfr(u + bfr(w * bfr(c - u))))) and (buf[n:] == 7.0).all()
+
+    x0, eps = (rnd(n, seed=4) * 3).cuda(), rnd(n, seed=5).cuda()
+    mask = torch.tensor([0.0, 1.0, 0.25])[torch.randint(0, 3, (n,), generator=torch.Generator().manual_seed(6))].cuda()
+    al, be, sigma, dtg = f32(2.2), f32(-1.3137), 0.37, f32(-0.0625 * 1.3)
+    abd = torch.tensor([al, be], dtype=torch.float32, device="cuda")
+    imgd = img.cuda()
+    v = (al * cd.float() + be * ud.float()).to(BF)
+    x = imgd + (dtg * v.float()).to(BF).float()
+    known = f32(np.float32(1.0) - np.float32(sigma)) * x0 + f32(sigma) * eps
+    want = torch.where(mask == 1, known, torch.where(mask == 0, x, x + mask * (known - x)))
+    for alias in (False, True):
+        buf = torch.full((n + G,), 7.0, device="cuda")
+        buf[:n] = imgd
+        cc = torch.full((n + G,), 3.0, dtype=BF, device="cuda")
+        cc[:n] = cd
+        E.check(L.k5_guided_euler(buf.data_ptr(), cc.data_ptr(), ud.data_ptr(), abd.data_ptr(), dtg, x0.data_ptr(), eps.data_ptr(), mask.data_ptr(),
+                                  sigma, n, 1, cc.data_ptr() if alias else None, s), "k5_guided_euler")
+        assert torch.equal(buf[:n], want) and (buf[n:] == 7.0).all()
+        assert torch.equal(cc[:n], v if alias else cd) and (cc[n:] == 3.0).all()
+
+
 def test_attention_bounded_scores_equals_online_max(E):
     """RMS-normalised q,k (|q|=|k|=8 -> |q.k| <= 64): the fixed-offset kernel is the same softmax."""
     S, H = 700, 2

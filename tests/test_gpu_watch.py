@@ -44,7 +44,7 @@ def factors(Cc=16, seed=5, scale=1.0):
 # ------------------------------------------------------------------------------------------ kernel
 def preview_reference(x, c, u, w, sigma, W, b, source=None, mask=None):
     """float64 restatement: (x0 unmasked, x0 with the keep rule, value before rounding to a code, the dot-product bound), all on the CPU"""
-    v = c if u is None else u + w * (c - u)                        # eager bf16: every op rounds, as cfg_euler_kernel does
+    v = c if u is None else u + w * (c - u)                        # eager bf16: every op rounds, as cfg_velocity in small_ops.hip does
     sv = np.float64(f32(sigma)) * v.double()
     x0 = x.double() - sv
     x0_bound = 2.0 ** -22 * (x.double().abs() + sv.abs())
