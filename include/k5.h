@@ -304,6 +304,18 @@ int k5_guidance_coeffs_bf16(const void* v_cond, const void* v_uncond, int64_t n,
  * on it is the preview of a guided step.  The rounding points differ from k5_cfg_euler's, so ab = {w, 1 - w} need not give its bits. */
 int k5_guided_euler(float* img, const void* v_cond, const void* v_uncond, const float* ab, float dt, const float* source, const float* noise,
                     const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, void* stream);
+/* The three-velocity update of skip-layer guidance (added under ABI 11, as the exports above were): v_skip is the
+ * conditional velocity of a forward with some visual blocks skipped (k5_dit_forward_skip), g > 0 the scale, by value.  Per element, nothing
+ * contracted:
+ *   base = ab ? bf16(rn(rn(ab[0] c) + rn(ab[1] u)))  (k5_guided_euler's bits)  :  v_uncond ? bf16(u + bf16(w bf16(c - u)))  (k5_cfg_euler's)  :  c
+ *   d = bf16(rn(c - s)),  e = bf16(rn(g d)),  v = bf16(rn(base + e))          (torch eager `base + g * (c - s)` on bf16 tensors, bit for bit)
+ *   img = rn(img + bf16(rn(dt v))), then the keep rule of k5_cfg_euler_edit (keep_mask NULL = none).
+ * v_out (NULL = not wanted, may be v_cond) receives v whether or not ab is given.  The same kernel and launcher as the three entries above, a
+ * further instantiation.  K5_ERR_ARG, nothing launched: a NULL img, v_cond or v_skip, g not finite or <= 0, ab without v_uncond, cells or
+ * C < 1, a keep_mask without source and noise. */
+int k5_skip_euler(float* img, const void* v_cond, const void* v_uncond /* nullable */, const void* v_skip, float w,
+                  const float* ab /* nullable, device */, float g, float dt, const float* source, const float* noise, const float* keep_mask,
+                  float sigma_next, int64_t cells, int C, void* v_out, void* stream);
 /* k5_cfg_euler over temporal context windows (added under ABI 11, as the exports above were): a clip of T frames whose velocities come from
  * nwin <= 64 windows of F frames.  img fp32 [T][frame_elems]; v_cond / v_uncond (NULL = no guidance) bf16 [nwin][F][frame_elems]; starts_dev
  * DEVICE int32 [nwin], window i covers frames starts[i] .. starts[i] + F - 1; weights_dev DEVICE fp32 [nwin][F], the share of window i's local
@@ -587,6 +599,41 @@ typedef struct k5_guidance {
 } k5_guidance;
 int k5_dit_set_guidance(k5_dit* dit, const k5_guidance* guidance /* NULL clears */);
 int k5_dit_guidance_state(k5_dit* dit, int* on, long long* guided_steps, long long* unguided_steps, long long* zero_steps, int reset);
+
+/* Skip-layer guidance on the handle (added under ABI 11, as the exports above were): at a skip step the model runs once
+ * more with the listed visual blocks disabled (mode 0: the block is the identity on the visual stream; mode 1: only its self-attention residual
+ * is dropped, its cross-attention and feed-forward run) and the step's velocity is pushed away from that weakened prediction,
+ *   v = v_cfg + scale * (c - c_skip)                                              (k5_skip_euler has the rounding points)
+ * with v_cfg what the step would otherwise use (CFG, the guidance plan's coefficients, or c alone at guidance 1; a plan's statistics are over c
+ * and u as always, the skip term is added after them).  The skip branch is the conditional forward up to the first listed block k0, so it
+ * is not run from the start: k5_dit_forward_skip is ONE conditional forward that copies its visual stream (this rank's rows, bf16) aside when
+ * it reaches block k0, finishes as k5_dit_forward does (the same bits), then restores the copy and runs blocks k0.. under the skip rule and an
+ * out-layer epilogue of its own (under sequence parallelism its own all-gather) into out_velocity_skip.  Text streams, the modulation vector,
+ * the stacked cross-attention K/V, NAG and regional prompts are the conditional forward's.  The skip branch's blocks keep their softmax-form
+ * memory in a third row, so the two other branches decide as they would without it.  Option "skip_share_prefix" 0 (diagnostic) runs every
+ * non-skipped block of the skip branch from the visual embedding on.
+ * A step i of k5_sample* is a skip step when this is on (scale > 0), steps == NULL or steps[i] != 0, and it is not a zero-init step.  It
+ * enqueues the forking forward, the unconditional forward when guided, the plan's coefficients when it has statistics, and k5_skip_euler's
+ * kernel; any other step enqueues what it always did, and so does every run while this is off.  The captured step is used only when every
+ * forward-running step is of one kind.  Works with editing, k5_sample_cond, k5_sample_many, sequence-parallel groups, NABLA, fp8 and LoRA.
+ * Refused by k5_sample* before anything is enqueued, with a message: K5_ERR_STATE on a handle in a CFG pair (the pair exchanges two velocities),
+ * with MagCache or its calibration (the table is indexed by the calls of a plain run), at k5_sample_windows with more than one window;
+ * K5_ERR_ARG when num_steps differs from the call's.
+ * k5_dit_set_skip_guidance: K5_ERR_ARG for a block index outside 0..num_visual_blocks-1 or repeated, num_blocks < 1, a mode outside {0, 1}, a
+ * scale that is negative or not finite, steps with num_steps < 1; scale == 0 is accepted and means off; NULL clears.  blocks and steps are
+ * copied.  k5_dit_skip_state: whether it is on, the skip steps enqueued so far, and how many visual blocks the skip branches took from the
+ * conditional forward (blocks_shared) and ran themselves (blocks_run). */
+typedef struct k5_skip_guidance {
+  const int* blocks; int num_blocks;      /* HOST, copied */
+  int mode;                               /* 0 = whole block is identity on the visual stream, 1 = only its self-attention residual is dropped */
+  float scale;                            /* g */
+  const unsigned char* steps; int num_steps;   /* HOST per-step 0/1 mask, copied; NULL = every step */
+} k5_skip_guidance;
+int k5_dit_set_skip_guidance(k5_dit* dit, const k5_skip_guidance* skip /* NULL clears */);
+int k5_dit_skip_state(k5_dit* dit, int* on, long long* skip_steps, long long* blocks_shared, long long* blocks_run, int reset);
+/* k5_dit_forward with the skip branch: out_velocity is k5_dit_forward's bit for bit, out_velocity_skip (bf16, the same shape) the skip
+ * branch's.  K5_ERR_STATE without a skip set on the handle (a set with scale 0 still forks here), with MagCache or its calibration. */
+int k5_dit_forward_skip(k5_dit* dit, const k5_forward_args* args, void* out_velocity, void* out_velocity_skip, void* stream);
 
 /* Regional prompts on the handle (added under ABI 11; the rule is written at k5_region_combine_bf16): a prompt per masked region inside the
  * cross-attention of ONE forward.  While set, every CONDITIONAL forward (as for k5_dit_set_nag: never the unconditional one) carries R more

@@ -111,8 +111,8 @@ struct AttnW {  // one attention module, packed
   DevBuf bqk, bq, bk, bv, bo, norm; // fp32 (bias values bf16-rounded); norm = [q_norm | k_norm]
   DevBuf wqk8, wv8, wo8, sqk, sv, so;   // opt-in e4m3 copies (k5_dit_set_fp8 bits 1 / 2): weights + per-output-channel scales
   float score_bound = 0.f;          // |q.k| <= 64 max|w_q| max|w_k| after norm_qk (RoPE preserves norms)
-  mutable DevBuf pref;              // visual self-attention: [2][H] heads the per-row-offset softmax served badly the last time this layer ran for
-                                    // the cond (0) / uncond (1) branch (k5_launch_attn_pref_update); zeroed at the start of every k5_sample and
+  mutable DevBuf pref;              // visual self-attention: [3][H] heads the per-row-offset softmax served badly the last time this layer ran for
+                                    // the cond (0) / uncond (1) / skip (2, k5_dit_forward_skip's own blocks) branch (k5_launch_attn_pref_update); zeroed at the start of every k5_sample and
                                     // by k5_dit_set_option("attn_pref_reset") — never carried from one sampling run, prompt or shape to the next
 };
 struct BlockW {
@@ -502,6 +502,21 @@ struct k5_dit {
     bool stats() const { return zero_star || rescale > 0.f; }   // the step needs the coefficients from the device
   } guide;
 
+  // Skip-layer guidance (k5_dit_set_skip_guidance): a third velocity from the conditional forward with some visual blocks skipped.
+  // forward_impl forks at the first skipped block (Fork below); sample_impl decides per step.  on: a set is held; live(): it also has a scale.
+  struct Skip {
+    bool on = false;
+    std::vector<char> skipped;                     // [num_visual_blocks] 0 / 1
+    int k0 = 0, mode = 0; float scale = 0.f;       // k0: the smallest skipped index
+    std::vector<unsigned char> steps;              // per-step mask of the calls to come; empty: every step
+    int share_prefix = 1;                          // option "skip_share_prefix"
+    long long skip_steps = 0, blocks_shared = 0, blocks_run = 0;
+    DevBuf vis;                                    // the conditional forward's visual stream [n][D] as it entered block k0
+    DevBuf vel;                                    // the sampler's third velocity
+    bool live() const { return on && scale > 0.f; }
+    bool at(int i) const { return live() && (steps.empty() || steps[i] != 0); }
+  } skip;
+
   // MagCache (reference kandinsky/magcache_utils.py:16-101): skip the visual blocks on some calls and re-apply the
   // cached bf16 residual of the same cond / uncond slot.  Decisions depend on the ratio table and the call counter only.
   struct MagCache {
@@ -774,7 +789,7 @@ int softmax_form(k5_dit* d, hipStream_t s, const AttnW& a, int pref_slot, bool b
     f.hflags = d->ws_attn_flags.as<int>();
     float* kmax_w = d->row_offsets ? d->ws_attn_flags.as<float>() + H : nullptr;
     f.kmax = kmax_w;
-    if (kmax_w) { K5CHK(ensure_zeroed(a.pref, (size_t)2 * H * 4, s)); f.pref = a.pref.as<int>() + (size_t)pref_slot * H + in.head0; }
+    if (kmax_w) { K5CHK(ensure_zeroed(a.pref, (size_t)3 * H * 4, s)); f.pref = a.pref.as<int>() + (size_t)pref_slot * H + in.head0; }
     K5CHK(k5_launch_attn_flags(in.qstat, in.kstat, in.nk, in.kstride, in.heads, 0, d->ws_attn_flags.as<int>(), d->ws_attn_cnt.as<unsigned long long>(), s, kmax_w,
                                f.pref, in.centre ? in.rstat : nullptr, in.centre ? kmax_w + H : nullptr, in.nq, in.qstride, kmax_w && in.anchor, in.leave_sig));
     if (in.centre) { f.kcen.centre = in.centre; f.kcen.radius = kmax_w + H; f.centred = true; }
@@ -1756,7 +1771,7 @@ int text_stream_run(k5_dit* d, hipStream_t s, const k5_text_cond& c, k5_dit::Tex
 
 int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, float time, const float* x,
                  int x_channels, void* out_velocity, hipStream_t s, const float* tvec = nullptr, const int* step = nullptr,
-                 int text_slot = -1, const float* vcond = nullptr) {
+                 int text_slot = -1, const float* vcond = nullptr, void* out_skip = nullptr) {
   const k5_dit_config& c = d->cfg;
   if (!d->finalized) { k5_set_error("k5_dit_forward before k5_dit_finalize"); return K5_ERR_STATE; }
   if (a->attention_type == 1) {   // NABLA workgroup size of this forward (see nabla_group_rows)
@@ -1777,6 +1792,14 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   if (vcond && (!c.visual_cond || x_channels != c.in_visual_dim)) { k5_set_error("visual_cond needs a visual_cond model and x of in_visual_dim channels"); return K5_ERR_ARG; }
   const int P = d->sp_world;
   const bool sp = d->comm.active();  // a communicator (even of size 1) selects the sharded code path
+  auto& sk = d->skip;
+  if (out_skip) {   // the forking forward (k5_dit_forward_skip, a skip step of k5_sample*): refused before anything is enqueued
+    if (!sk.on) { k5_set_error("k5_dit_forward_skip: no skip set on the handle (k5_dit_set_skip_guidance)"); return K5_ERR_STATE; }
+    if (d->mag.on || d->cal.on) {
+      k5_set_error("k5_dit_forward_skip: %s on the handle: the ratio table is indexed by the calls of a plain run", d->mag.on ? "MagCache is set" : "MagCache calibration is");
+      return K5_ERR_STATE;
+    }
+  }
   if (d->cal.on) {   // refusals of the calibration mode, before anything is enqueued
     if (sp || d->pair.active()) { k5_set_error("MagCache calibration is a one-GPU job: the handle is in a %s", sp ? "sequence-parallel group" : "CFG pair"); return K5_ERR_STATE; }
     if (d->cal.cnt >= 2 && d->cal.res_elems[d->cal.cnt & 1] != (size_t)N * D) {
@@ -1927,7 +1950,9 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   }
   const int sched = sp ? sp_schedule(d, nabla) : 0;
   if (sp) d->sp_mode_used = sched;
-  for (int i = 0; i < (mag_skip ? 0 : c.num_visual_blocks); ++i) {
+  // one visual block on ws_vis.  pref_slot: the row of the softmax-form memory (0 cond, 1 uncond, 2 the skip branch); drop_sa: skip-layer
+  // guidance mode 1, the block without its self-attention residual (its first LayerNorm goes with it)
+  auto run_block = [&](int i, int pref_slot, bool drop_sa) -> int {
     const BlockW& b = d->vblocks[i];
     const float* m = mod + b.mod_off;
     const float* vcos = d->ws_vcos.as<float>() + (size_t)tok0 * 32;
@@ -1935,15 +1960,17 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     const bool ulysses = sched == 1, two_level = sched == 2;
     // fp8 modes: the LayerNorm writes the e4m3 rows the projections read (no bf16 h, no quantisation pass) — "fp8_fuse_ln" = 0 keeps the two passes
     const bool h8_sa = d->fp8_fuse_ln && sched == 0 && (sp ? sa_sp_fp8_in(d, b.self_attn, n, n_pad, nabla) : sa_fp8_in(d, b.self_attn, n));
-    K5CHK(ln_mod(d, s, d->ws_vis.p, m, d->ws_h.p, n, h8_sa));
-    if (d->profiling) ++d->prof_self_blocks;   // bench.py: FLOPs of the roofline kernel = per-block FLOPs x the blocks that RAN
-    if (ulysses || two_level) {
-      K5CHK(run_self_attention_heads(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, two_level, text_slot > 0 ? 1 : 0));
-    } else if (sp) {
-      K5CHK(run_self_attention_sp(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, nabla ? &na : nullptr, text_slot > 0 ? 1 : 0, h8_sa));
-    } else {
-      K5CHK(run_self_attention(d, s, b.self_attn, d->ws_h.p, n, d->ws_qk.p, d->ws_vt.p, d->ws_o.p, vcos, vsin, d->ws_vis.p,
-                               m + 2 * D, "attn_self", nabla ? &na : nullptr, text_slot > 0 ? 1 : 0, h8_sa));
+    if (!drop_sa) {
+      K5CHK(ln_mod(d, s, d->ws_vis.p, m, d->ws_h.p, n, h8_sa));
+      if (d->profiling) ++d->prof_self_blocks;   // bench.py: FLOPs of the roofline kernel = per-block FLOPs x the blocks that RAN
+      if (ulysses || two_level) {
+        K5CHK(run_self_attention_heads(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, two_level, pref_slot));
+      } else if (sp) {
+        K5CHK(run_self_attention_sp(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, nabla ? &na : nullptr, pref_slot, h8_sa));
+      } else {
+        K5CHK(run_self_attention(d, s, b.self_attn, d->ws_h.p, n, d->ws_qk.p, d->ws_vt.p, d->ws_o.p, vcos, vsin, d->ws_vis.p,
+                                 m + 2 * D, "attn_self", nabla ? &na : nullptr, pref_slot, h8_sa));
+      }
     }
     K5CHK(ln_mod(d, s, d->ws_vis.p, m + 3 * D, d->ws_h.p, n));
     for (int k = 0; k < cx.n; ++k) cx.v[k] = cross_view(d, d->streams[act[k].stream], i, cx_all, act[k].o);
@@ -1951,6 +1978,15 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     const bool h8_ff = d->fp8_fuse_ln && ff_fp8_in(d, b, n);
     K5CHK(ln_mod(d, s, d->ws_vis.p, m + 6 * D, d->ws_h.p, n, h8_ff));
     K5CHK(run_ff(d, s, b, d->ws_h.p, n, d->ws_ff.p, d->ws_vis.p, m + 8 * D, h8_ff));
+    return K5_OK;
+  };
+  // the fork of skip-layer guidance: the visual stream as it enters block `fork_at` (the first skipped one; 0 with "skip_share_prefix" = 0) is
+  // copied aside, the skip branch starts from it below
+  const int fork_at = out_skip ? (sk.share_prefix ? sk.k0 : 0) : -1;
+  if (out_skip) K5CHK(sk.vis.ensure(vis_elems * 2));
+  for (int i = 0; i < (mag_skip ? 0 : c.num_visual_blocks); ++i) {
+    if (i == fork_at) HIPCHK(hipMemcpyAsync(sk.vis.p, d->ws_vis.p, vis_elems * 2, hipMemcpyDeviceToDevice, s));
+    K5CHK(run_block(i, text_slot > 0 ? 1 : 0, false));
   }
   if (mg.on) {
     if (!mag_skip) {  // residual = visual_embed - ori_visual_embed (bf16), :84
@@ -1975,7 +2011,7 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     if (cl.cnt >= 2 * cl.num_steps) { cl.cnt = 0; cl.runs++; }
   }
   // ---- after_blocks / OutLayer (dit.py:149-153, nn.py:374-400) ----
-  {
+  auto out_layer = [&](void* out) -> int {
     Scope sc(d, s, "epilogue");
     const float* m = mod + d->out_mod_off;  // [shift | scale]
     K5CHK(k5_launch_ln_modulate(d->ws_vis.p, m + D, m, d->ws_h.p, n, D, D, D, s));
@@ -1983,7 +2019,21 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
                               d->Fout, D, D, D, d->Fout, K5_EPI_BIAS, nullptr, 0, nullptr, s));
     // every rank needs the whole velocity: the (replicated) latent is advanced identically on all ranks
     if (sp) K5CHK(d->comm.all_gather_inplace(d->ws_y.p, (size_t)n_pad * d->Fout, 2, s));
-    K5CHK(k5_launch_unpatchify(d->ws_y.p, out_velocity, Tp, Hp, Wp, c.out_visual_dim, d->Fout, perm, s));
+    K5CHK(k5_launch_unpatchify(d->ws_y.p, out, Tp, Hp, Wp, c.out_visual_dim, d->Fout, perm, s));
+    return K5_OK;
+  };
+  K5CHK(out_layer(out_velocity));
+  // ---- the skip branch: the same latent, prompt and time, so the text streams, the modulation vector and the stacked cross-attention K/V above
+  // are its own; it restores the visual stream of the fork and runs the blocks from there under the skip rule, on row 2 of the form memory ----
+  if (out_skip) {
+    HIPCHK(hipMemcpyAsync(d->ws_vis.p, sk.vis.p, vis_elems * 2, hipMemcpyDeviceToDevice, s));
+    for (int i = fork_at; i < c.num_visual_blocks; ++i) {
+      if (sk.skipped[i] && sk.mode == 0) continue;   // the identity: nothing is launched
+      K5CHK(run_block(i, 2, sk.skipped[i] != 0));
+      ++sk.blocks_run;
+    }
+    sk.blocks_shared += fork_at;
+    K5CHK(out_layer(out_skip));
   }
   return K5_OK;
 }
@@ -2031,7 +2081,7 @@ extern "C" void k5_dit_destroy(k5_dit* d) {
   if (d->h_leave_sig) { (void)hipHostFree(d->h_leave_sig); d->h_leave_sig = nullptr; }
   for (auto& t : d->text_cache) { t.text.release(); t.pool.release(); }
   for (auto& st : d->streams) st.release();
-  d->nag.o.release(); d->regions.o.release(); d->regions.w.release();
+  d->nag.o.release(); d->regions.o.release(); d->regions.w.release(); d->skip.vis.release(); d->skip.vel.release();
   for (auto& kv : d->staged) kv.second.dev.release();   // a handle destroyed before finalize still holds its staged matrices
   d->mag.residual[0].release(); d->mag.residual[1].release(); d->mag.pm_one.release();
   for (auto& b : d->vblocks) { b.w1_f8.release(); b.w2_f8.release(); b.s1_f8.release(); b.s2_f8.release(); }
@@ -2375,6 +2425,26 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
     if (zinit && edit) { k5_set_error("%s: zero-init steps together with editing are not supported", who); return K5_ERR_UNSUPPORTED; }
     if (gd.stats() && (n < 1 || (n & 7))) { k5_set_error("%s: zero_star / rescale need a latent of a multiple of 8 elements (got %lld)", who, (long long)n); return K5_ERR_ALIGN; }
   }
+  const k5_dit::Skip& sg = d->skip;
+  if (sg.live()) {
+    if (!sg.steps.empty() && (int)sg.steps.size() != a->num_steps) {
+      k5_set_error("%s: the skip-guidance mask has %d steps, this call %d", who, (int)sg.steps.size(), a->num_steps);
+      return K5_ERR_ARG;
+    }
+    if (d->pair.active()) {
+      k5_set_error("%s: skip-layer guidance is set (k5_dit_set_skip_guidance) and the handle is in a CFG pair: the pair exchanges two velocities, a skip step has three", who);
+      return K5_ERR_STATE;
+    }
+    if (d->mag.on || d->cal.on) {
+      k5_set_error("%s: skip-layer guidance is set (k5_dit_set_skip_guidance) and %s on the handle: the ratio table is indexed by the calls of a plain run",
+                   who, d->mag.on ? "MagCache is set" : "MagCache calibration is");
+      return K5_ERR_STATE;
+    }
+    if (win) {
+      k5_set_error("%s: skip-layer guidance is set (k5_dit_set_skip_guidance): a windowed step has one velocity pair per window, the skip branch is not built for it", who);
+      return K5_ERR_STATE;
+    }
+  }
   if (win) {
     if (edit) { k5_set_error("%s: editing with context windows is not supported", who); return K5_ERR_UNSUPPORTED; }
     if (rank_group(d)) { k5_set_error("%s: the handle is in a %s (context windows are single-rank only)", who, rank_group(d)); return K5_ERR_STATE; }
@@ -2421,6 +2491,7 @@ struct SampleRun {
   int64_t n = 0, cells = 0;                 // elements and cells of the latent one forward sees (with win: a window's)
   bool cfg_on = false, pair = false;        // pair: CFG-parallel, one branch here, the other on the paired handle
   void* vel_c = nullptr; void* vel_u = nullptr;
+  void* vel_s = nullptr;                    // skip-layer guidance: the skip branch's velocity (sized when the call has a skip step)
   std::vector<float> host_tab;              // the schedule, three tables of num_steps entries:
   const float* t1000 = nullptr;             //   t * 1000, fp32 (:57)
   const float* dt = nullptr;                //   torch.diff(timesteps) (:105)
@@ -2440,13 +2511,17 @@ struct SampleRun {
     if (plan && i < plan->zero_init) return ZERO;
     return fabsf(w_at(i) - 1.0f) > 1e-6f ? GUIDED : UNGUIDED;   // generation_utils.py:63
   }
-  // what the watch's preview of step i combines: a guided step with coefficients left its v in vel_c, a zero step has velocity 0 there
-  const void* preview_vu(int i) const { return win ? (cfg_on ? vel_u : nullptr) : kind(i) == GUIDED && !stats ? vel_u : nullptr; }
+  // a skip step (k5_dit_set_skip_guidance): the conditional forward forks and the update reads three velocities
+  bool skip_at(int i) const { return !win && d->skip.at(i) && kind(i) != ZERO; }
+  // what the watch's preview of step i combines: a guided step with coefficients and a skip step left their v in vel_c, a zero step has velocity 0 there
+  const void* preview_vu(int i) const { return win ? (cfg_on ? vel_u : nullptr) : kind(i) == GUIDED && !stats && !skip_at(i) ? vel_u : nullptr; }
 
   // One forward of step i: the text condition through text cache slot `slot`, on the latent slice `x` with its conditioning slice `vc`, into
   // `vel`.  `tables`: the forward reads its time through the device-side step tables when the step is captured; windows pass none.
-  int forward(int i, const k5_text_cond& cond, int slot, const float* x, void* vel, const float* vc, bool tables = true) {
-    return forward_impl(d, &a->fwd, cond, t1000[i], x, d->cfg.in_visual_dim, vel, s, tables ? tvec : nullptr, tables ? step_ctr : nullptr, slot, vc);
+  // `skip_vel`: the forward forks and leaves the skip branch's velocity there.
+  int forward(int i, const k5_text_cond& cond, int slot, const float* x, void* vel, const float* vc, bool tables = true, void* skip_vel = nullptr) {
+    return forward_impl(d, &a->fwd, cond, t1000[i], x, d->cfg.in_visual_dim, vel, s, tables ? tvec : nullptr, tables ? step_ctr : nullptr, slot, vc,
+                        skip_vel);
   }
 
   int step(int i) {   // enqueue step i: the forwards, then CFG + Euler
@@ -2474,6 +2549,7 @@ struct SampleRun {
       return K5_OK;
     }
     if (kind(i) == ZERO) return K5_OK;   // velocity 0: no forward, no update
+    const bool skip = skip_at(i);
     if (pair) {
       // my branch only; then the pair's velocities change hands on the side stream (fork / join by events: capturable) and both
       // handles hold [v_cond | v_uncond] — every rank of both groups applies the same update to the same numbers
@@ -2486,7 +2562,7 @@ struct SampleRun {
       HIPCHK(hipEventRecord(d->ev_vel_done, d->pair_stream));
       HIPCHK(hipStreamWaitEvent(s, d->ev_vel_done, 0));
     } else {
-      K5CHK(forward(i, a->fwd.cond, 0, a->latent, vel_c, vcond));
+      K5CHK(forward(i, a->fwd.cond, 0, a->latent, vel_c, vcond, true, skip ? vel_s : nullptr));
       if (vu) K5CHK(forward(i, a->null_cond, 1, a->latent, vel_u, vcond));
     }
     {
@@ -2496,6 +2572,7 @@ struct SampleRun {
       K5EulerStepArgs e;
       e.img = a->latent; e.v_cond = vel_c; e.v_uncond = vu; e.w = w_at(i); e.dt = dt[i];
       if (coeffs) { e.ab = g_ab; e.v_out = want_v ? vel_c : nullptr; }
+      if (skip) { e.v_skip = vel_s; e.skip_scale = d->skip.scale; e.v_out = want_v ? vel_c : nullptr; }   // the skip term comes after the coefficients
       if (edit) { e.source = edit->source; e.noise = edit->noise; e.keep_mask = edit->keep_mask; e.sigma_next = sigma_next[i]; e.signext = signext; }
       e.cells = cells; e.C = c.out_visual_dim;
       e.dtvec = dtvec; e.step = step_ctr; e.stream = s;
@@ -2621,6 +2698,14 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
       r.g_part = reinterpret_cast<double*>(static_cast<char*>(gd.ws.p) + 64);
     }
   }
+  int nskip = 0;
+  for (int i = first; i < N; ++i) nskip += r.skip_at(i) ? 1 : 0;
+  if (nskip) {   // the third velocity, sized before the loop; the captured step stands for every step only when all of them fork or none does
+    K5CHK(d->skip.vel.ensure(r.n * 2));
+    r.vel_s = d->skip.vel.p;
+    r.want_v = r.want_v || (wt.on && wt.every > 0);
+    uniform = uniform && nskip == N - first;
+  }
   r.pair = r.cfg_on && d->pair.active();
   if (r.pair) K5CHK(d->ws_vel_pair.ensure(2 * r.n * 2));
   else {   // one slot per window
@@ -2703,14 +2788,16 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   // Step 0 is always eager.  In graph mode step 1 is captured and instantiated (after the watch has followed step 0: those launches are not
   // part of the graph) and steps 1.. are launches of the executable; between them the watch reads sigma_next as a host scalar.
   GraphGuard cap{s};
-  long long nag_per_step = 0, reg_per_step = 0;
+  long long nag_per_step = 0, reg_per_step = 0, shared_per_step = 0, run_per_step = 0;
   for (int i = 0; i < N; ++i) {
     if (i == 0 || !graph) K5CHK(r.step(i));
     else {
       if (i == 1) {
         HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         const long long nag_before = d->nag.combines, reg_before = d->regions.combines;
+        const long long shared_before = d->skip.blocks_shared, run_before = d->skip.blocks_run;
         const int rc = r.step(1);
+        shared_per_step = d->skip.blocks_shared - shared_before; run_per_step = d->skip.blocks_run - run_before;
         reg_per_step = d->regions.combines - reg_before;
         nag_per_step = d->nag.combines - nag_before;   // k5_dit_nag_state counts launches: the capture stands for step 1's, every further replay adds as many
         const hipError_t ec = hipStreamEndCapture(s, &cap.g);
@@ -2719,10 +2806,11 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
         if (hipGraphInstantiate(&cap.ge, cap.g, nullptr, nullptr, 0) != hipSuccess) { k5_set_error("hipGraphInstantiate failed"); return K5_ERR_HIP; }
       }
       if (hipGraphLaunch(cap.ge, s) != hipSuccess) { k5_set_error("hipGraphLaunch failed"); return K5_ERR_HIP; }
-      if (i > 1) { d->nag.combines += nag_per_step; d->regions.combines += reg_per_step; }
+      if (i > 1) { d->nag.combines += nag_per_step; d->regions.combines += reg_per_step; d->skip.blocks_shared += shared_per_step; d->skip.blocks_run += run_per_step; }
     }
     if (i == first) K5CHK(decide_fuse());
     if (gd.on) (r.kind(i) == SampleRun::GUIDED ? gd.guided : r.kind(i) == SampleRun::UNGUIDED ? gd.unguided : gd.zero) += 1;
+    if (r.skip_at(i)) d->skip.skip_steps += 1;
     if (wt.on) {
       K5CHK(wt.step(r, i));
       if (wt.stopped) break;
@@ -2922,6 +3010,48 @@ extern "C" int k5_dit_guidance_state(k5_dit* d, int* on, long long* guided_steps
   return K5_OK;
 }
 
+extern "C" int k5_dit_set_skip_guidance(k5_dit* d, const k5_skip_guidance* g) {
+  g_err[0] = 0;
+  if (!d) { k5_set_error("k5_dit_set_skip_guidance: null handle"); return K5_ERR_ARG; }
+  k5_dit::Skip& sk = d->skip;
+  if (!g) { sk.on = false; sk.skipped.clear(); sk.steps.clear(); sk.k0 = 0; sk.mode = 0; sk.scale = 0.f; return K5_OK; }
+  const int nb = d->cfg.num_visual_blocks;
+  if (!g->blocks || g->num_blocks < 1) { k5_set_error("k5_dit_set_skip_guidance: blocks with num_blocks = %d", g->num_blocks); return K5_ERR_ARG; }
+  if (g->mode != 0 && g->mode != 1) { k5_set_error("k5_dit_set_skip_guidance: mode must be 0 (block) or 1 (attention), got %d", g->mode); return K5_ERR_ARG; }
+  if (!(g->scale >= 0.0f) || !isfinite(g->scale)) { k5_set_error("k5_dit_set_skip_guidance: scale must be finite and >= 0 (got %g)", (double)g->scale); return K5_ERR_ARG; }
+  if (g->steps && g->num_steps < 1) { k5_set_error("k5_dit_set_skip_guidance: steps with num_steps = %d", g->num_steps); return K5_ERR_ARG; }
+  std::vector<char> skipped((size_t)nb, 0);
+  int k0 = nb;
+  for (int j = 0; j < g->num_blocks; ++j) {
+    const int b = g->blocks[j];
+    if (b < 0 || b >= nb) { k5_set_error("k5_dit_set_skip_guidance: block %d is outside 0..%d", b, nb - 1); return K5_ERR_ARG; }
+    if (skipped[b]) { k5_set_error("k5_dit_set_skip_guidance: block %d is listed twice", b); return K5_ERR_ARG; }
+    skipped[b] = 1;
+    k0 = b < k0 ? b : k0;
+  }
+  sk.skipped.swap(skipped); sk.k0 = k0; sk.mode = g->mode; sk.scale = g->scale;
+  sk.steps.assign(g->steps, g->steps ? g->steps + g->num_steps : g->steps);
+  sk.on = true;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_skip_state(k5_dit* d, int* on, long long* skip_steps, long long* blocks_shared, long long* blocks_run, int reset) {
+  if (!d) { k5_set_error("k5_dit_skip_state: null handle"); return K5_ERR_ARG; }
+  k5_dit::Skip& sk = d->skip;
+  if (on) *on = sk.live() ? 1 : 0;
+  if (skip_steps) *skip_steps = sk.skip_steps;
+  if (blocks_shared) *blocks_shared = sk.blocks_shared;
+  if (blocks_run) *blocks_run = sk.blocks_run;
+  if (reset) sk.skip_steps = sk.blocks_shared = sk.blocks_run = 0;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_forward_skip(k5_dit* d, const k5_forward_args* a, void* out_velocity, void* out_velocity_skip, void* stream) {
+  g_err[0] = 0;
+  if (!d || !a || !out_velocity || !out_velocity_skip || !a->x) return K5_ERR_ARG;
+  return forward_impl(d, a, a->cond, a->time, a->x, a->x_channels, out_velocity, (hipStream_t)stream, nullptr, nullptr, -1, nullptr, out_velocity_skip);
+}
+
 extern "C" int k5_dit_nag_state(k5_dit* d, int* on, long long* combines, int reset) {
   if (!d) { k5_set_error("k5_dit_nag_state: null handle"); return K5_ERR_ARG; }
   if (on) *on = d->nag.on ? 1 : 0;
@@ -2952,7 +3082,7 @@ extern "C" int k5_dit_forward_many(k5_dit* d, const k5_forward_args* a, int S, c
   if (reinterpret_cast<uintptr_t>(out_velocity) & 1) { k5_set_error("k5_dit_forward_many: out_velocity is not 2-byte aligned"); return K5_ERR_ARG; }
   if (a->T <= 0 || a->H <= 0 || a->W <= 0 || a->x_channels <= 0) { k5_set_error("k5_dit_forward_many: bad shapes"); return K5_ERR_ARG; }
   hipStream_t s = (hipStream_t)stream;
-  const size_t slot = (size_t)2 * d->Hh * 4;           // AttnW::pref of one block: [2][H] int
+  const size_t slot = (size_t)3 * d->Hh * 4;           // AttnW::pref of one block: [3][H] int
   std::vector<char> had(d->vblocks.size(), 0);
   size_t saved = 0;
   for (size_t j = 0; j < d->vblocks.size(); ++j) had[j] = d->vblocks[j].self_attn.pref.p != nullptr;
@@ -3328,6 +3458,8 @@ extern "C" int k5_dit_cfg_pair_init_ipc(k5_dit* d, const char* shm_name, int bra
 //   "ipc_flags_finegrained" (read-only): 1 when the IPC group's flag page is fine-grained device memory (csrc/ipc_comm.h Group::open; K5_IPC_COARSE_FLAGS=1 forces plain memory)
 //   "cross_kv_batched" 1 (default) / 0: the cross-attention key / V^T projections of all visual blocks as two GEMMs against stacked weights before
 //                     the visual stack (they depend on the text stream only), their key norms as one launch; same bits as the per-block launches
+//   "skip_share_prefix" 1 (default) / 0 (diagnostic): the skip branch of k5_dit_forward_skip starts from the conditional forward's visual stream at the
+//                     first skipped block; 0 = it runs every non-skipped block itself from the visual embedding on (the text side is still shared)
 //   "nabla_fuse_means" 1 (default: where the launch has >= 150 k threads) / 2 (always) / 0: the 64-token block means NABLA's map is built from are taken by the norm + RoPE pass itself (one read of q | k
 //                     less per block, and on one GPU the keys are scaled in place: no scaled copy); same bits as with 0
 //   "fp8_fuse_ln"     1 (default) / 0: under k5_dit_set_fp8 the LayerNorm in front of an e4m3 projection writes the e4m3 rows itself (no bf16 h, no
@@ -3368,6 +3500,7 @@ extern "C" int k5_dit_set_option(k5_dit* d, const char* name, int value) {
   if (!strcmp(name, "attn_anchor")) { d->anchor = value != 0; return K5_OK; }
   if (!strcmp(name, "attn_pref_reset")) return reset_attn_pref(d, nullptr, true);   // an action, not a state: the per-step path (k5_dit_forward) calls it per run
   if (!strcmp(name, "cross_kv_batched")) { if (value != 0 && value != 1) return K5_ERR_ARG; d->cross_kv_batched = value; return K5_OK; }
+  if (!strcmp(name, "skip_share_prefix")) { if (value != 0 && value != 1) return K5_ERR_ARG; d->skip.share_prefix = value; return K5_OK; }
   if (!strcmp(name, "nabla_fuse_means")) { if (value < 0 || value > 2) return K5_ERR_ARG; d->nabla_fuse_means = value; return K5_OK; }
   if (!strcmp(name, "fp8_fuse_ln")) { if (value != 0 && value != 1) return K5_ERR_ARG; d->fp8_fuse_ln = value; return K5_OK; }
   if (!strcmp(name, "nabla_pair_frames")) { if (value != 0 && value != 1) return K5_ERR_ARG; d->nabla_pair_frames = value; return K5_OK; }
@@ -3428,6 +3561,7 @@ extern "C" int k5_dit_get_option(k5_dit* d, const char* name, int* value) {
   else if (!strcmp(name, "fp8_fuse_ln")) *value = d->fp8_fuse_ln;
   else if (!strcmp(name, "nabla_fuse_means")) *value = d->nabla_fuse_means;
   else if (!strcmp(name, "cross_kv_batched")) *value = d->cross_kv_batched;
+  else if (!strcmp(name, "skip_share_prefix")) *value = d->skip.share_prefix;
   else if (!strcmp(name, "emulate_world")) *value = d->emulated ? d->sp_world : 0;
   else if (!strcmp(name, "emulated")) *value = d->emulated ? 1 : 0;
   else { k5_set_error("unknown option %s", name); return K5_ERR_ARG; }

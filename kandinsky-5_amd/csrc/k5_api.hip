@@ -420,6 +420,23 @@ int k5_guided_euler(float* img, const void* v_cond, const void* v_uncond, const 
   return ret(st, "k5_guided_euler");
 }
 
+int k5_skip_euler(float* img, const void* v_cond, const void* v_uncond, const void* v_skip, float w, const float* ab, float g, float dt,
+                  const float* source, const float* noise, const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out,
+                  void* stream) {
+  K5EulerStepArgs a;
+  a.img = img; a.v_cond = v_cond; a.v_uncond = v_uncond; a.w = w; a.ab = ab; a.dt = dt;
+  a.source = source; a.noise = noise; a.keep_mask = keep_mask; a.sigma_next = sigma_next;
+  a.cells = cells; a.C = C; a.v_out = v_out; a.v_skip = v_skip; a.skip_scale = g;
+  a.stream = (hipStream_t)stream;
+  const int st = v_skip ? k5_launch_euler_step(a) : K5_ERR_ARG;   // without v_skip the launcher would take a two-velocity update
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_skip_euler: need img, v_cond and v_skip, a finite g > 0, cells and C >= 1, v_uncond with ab, and source and noise with a "
+                 "keep_mask (g %g, cells %lld, C %d)", (double)g, (long long)cells, C);
+    return st;
+  }
+  return ret(st, "k5_skip_euler");
+}
+
 int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts_dev,
                          const float* weights_dev, int nwin, int F, int T, int64_t frame_elems, void* stream) {
   if (!img || !v_cond || !starts_dev || !weights_dev || nwin < 1 || nwin > 64 || F < 1 || T < 1 || frame_elems < 1) {

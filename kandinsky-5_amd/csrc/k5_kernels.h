@@ -181,12 +181,16 @@ int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C,
 // reads dt (and, when signext is given, sigma_next) at the device step counter.
 // K5_ERR_ARG: img or v_cond null, cells or C < 1, ab without v_uncond, v_out without ab, keep_mask without source and noise, dtvec without step
 // or step without dtvec, signext without dtvec.  Nothing is launched when it refuses.
+// Skip-layer guidance (v_skip bf16 [cells * C], skip_scale g by value): with the velocity above as base, d = bf16(c - s), e = bf16(g d),
+// v = bf16(base + e) — torch eager `base + g * (c - s)` on bf16 tensors — and v_out receives v with or without ab.  K5_ERR_ARG: v_skip without
+// g > 0, a g that is not finite or is negative, a g without v_skip.
 struct K5EulerStepArgs {
   float* img = nullptr; const void* v_cond = nullptr; const void* v_uncond = nullptr;
   float w = 1.f; const float* ab = nullptr; float dt = 0.f;
   const float* source = nullptr; const float* noise = nullptr; const float* keep_mask = nullptr; float sigma_next = 0.f;
   int64_t cells = 0; int C = 1; void* v_out = nullptr;
   const float* dtvec = nullptr; const float* signext = nullptr; const int* step = nullptr;
+  const void* v_skip = nullptr; float skip_scale = 0.f;
   hipStream_t stream = nullptr;
 };
 int k5_launch_euler_step(const K5EulerStepArgs& a);

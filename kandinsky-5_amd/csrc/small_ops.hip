@@ -645,6 +645,14 @@ __device__ __forceinline__ float guided_velocity(float alpha, float beta, float 
   const float q = beta * u;
   return bf_round(p + q);
 }
+// Skip-layer guidance on top of a step's velocity: v = bf16(base + bf16(g * bf16(c - s))), the eager bf16 expression `base + g * (c - s)` with
+// every op rounded; each product and difference meets a bf16 rounding before the next op, the pragma only says so
+__device__ __forceinline__ float skip_velocity(float base, float g, float c, float s) {
+#pragma clang fp contract(off)
+  const float d = bf_round(c - s);
+  const float e = bf_round(g * d);
+  return bf_round(base + e);
+}
 
 // The sampler's update of one step, one pass over the latent (K18): the velocity is v = guided_velocity(ab[0], ab[1], c, u) with coefficients
 // from device memory (guidance_finish_kernel wrote them), else cfg_velocity(w, c, u), else (vu NULL) c itself; img += bf16(dt * v)
@@ -653,29 +661,36 @@ __device__ __forceinline__ float guided_velocity(float alpha, float beta, float 
 // receives v, for the watch's preview.  In the captured step dt and sigma_next come from the device tables at the device step counter;
 // signext is given only when something reads sigma_next.  Two instantiations, coefficients from the device (AB: ab and v_out are read) or not:
 // with that choice made at run time the plain update measured 1.1 - 1.6 us slower per launch at the 5 s clip's 3.0 M elements.
-template <bool AB>
+// A third instantiation (SK) is the skip-layer-guidance step: a third stream vs, the conditional velocity with some blocks skipped, and a scale
+// sg by value; the velocity above is the base and v = skip_velocity(base, sg, c, s).  There ab is looked at at run time (the step runs a third
+// forward, a branch on a uniform is nothing next to it) and v_out receives v with or without coefficients.
+template <bool AB, bool SK>
 __global__ __launch_bounds__(256) void euler_step_kernel(float* __restrict__ img, const bf16_t* vc, const bf16_t* __restrict__ vu, float w,
                                                          const float* __restrict__ ab, float dt, const float* __restrict__ x0,
                                                          const float* __restrict__ eps, const float* __restrict__ mask, float sigma_next,
                                                          int C, bf16_t* v_out, const float* __restrict__ dtvec,
-                                                         const float* __restrict__ signext, const int* __restrict__ step, int64_t n) {
+                                                         const float* __restrict__ signext, const int* __restrict__ step, int64_t n,
+                                                         const bf16_t* __restrict__ vs, float sg) {
   if (dtvec) dt = dtvec[*step];
   if (signext) sigma_next = signext[*step];
-  const float alpha = AB ? ab[0] : 0.0f, beta = AB ? ab[1] : 0.0f;
+  const bool coeffs = SK ? ab != nullptr : AB;
+  const float alpha = coeffs ? ab[0] : 0.0f, beta = coeffs ? ab[1] : 0.0f;
   const float a = 1.0f - sigma_next;
   const bf16_t* up = vu ? vu : vc;   // without guidance u is unused: the same address again costs no traffic, a branch around the load would cost a wait
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
     // every load that does not hang on a value first, so that they are in flight together: a thread has one or two elements, latency is the cost
     const bf16_t cb = vc[g];
     const bf16_t ub = up[g];
+    const bf16_t sb = SK ? vs[g] : cb;
     float x = img[g];
     const float m = mask ? mask[g / C] : 0.0f;
     const float c = bf2f(cb), u = bf2f(ub);
-    const float v = AB ? guided_velocity(alpha, beta, c, u) : (vu ? cfg_velocity(w, c, u) : c);
+    float v = coeffs ? guided_velocity(alpha, beta, c, u) : (vu ? cfg_velocity(w, c, u) : c);
+    if (SK) v = skip_velocity(v, sg, c, bf2f(sb));
     x = __fadd_rn(x, bf_round(__fmul_rn(dt, v)));
     if (m != 0.0f) x = keep_blend(x, renoise_at(a, sigma_next, x0[g], eps[g]), m);
     img[g] = x;
-    if (AB && v_out) v_out[g] = f2bf(v);
+    if ((AB || SK) && v_out) v_out[g] = f2bf(v);
   }
 }
 
@@ -1053,11 +1068,14 @@ int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C,
 
 int k5_launch_euler_step(const K5EulerStepArgs& a) {
   if (!a.img || !a.v_cond || a.cells <= 0 || a.C <= 0) return K5_ERR_ARG;
-  if ((a.ab && !a.v_uncond) || (a.v_out && !a.ab) || (a.keep_mask && (!a.source || !a.noise))) return K5_ERR_ARG;
+  if ((a.ab && !a.v_uncond) || (a.v_out && !a.ab && !a.v_skip) || (a.keep_mask && (!a.source || !a.noise))) return K5_ERR_ARG;
   if (((a.dtvec != nullptr) != (a.step != nullptr)) || (a.signext && !a.dtvec)) return K5_ERR_ARG;
+  if (a.v_skip ? !(a.skip_scale > 0.0f && __builtin_isfinite(a.skip_scale)) : a.skip_scale != 0.0f) return K5_ERR_ARG;   // also a NaN or negative scale
   const int64_t n = a.cells * a.C;
-  hipLaunchKernelGGL(a.ab ? euler_step_kernel<true> : euler_step_kernel<false>, dim3(grid_for(n)), dim3(256), 0, a.stream, a.img, (const bf16_t*)a.v_cond, (const bf16_t*)a.v_uncond,
-                     a.w, a.ab, a.dt, a.source, a.noise, a.keep_mask, a.sigma_next, a.C, (bf16_t*)a.v_out, a.dtvec, a.signext, a.step, n);
+  const auto kernel = a.v_skip ? euler_step_kernel<false, true> : a.ab ? euler_step_kernel<true, false> : euler_step_kernel<false, false>;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(256), 0, a.stream, a.img, (const bf16_t*)a.v_cond, (const bf16_t*)a.v_uncond,
+                     a.w, a.ab, a.dt, a.source, a.noise, a.keep_mask, a.sigma_next, a.C, (bf16_t*)a.v_out, a.dtvec, a.signext, a.step, n,
+                     (const bf16_t*)a.v_skip, a.skip_scale);
   return done();
 }
 

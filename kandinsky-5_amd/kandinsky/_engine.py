@@ -113,6 +113,12 @@ class Guidance(C.Structure):
                 ("rescale", C.c_float)]
 
 
+class SkipGuidance(C.Structure):
+    """k5_skip_guidance: the set of k5_dit_set_skip_guidance (blocks and steps are HOST memory, copied by the call)."""
+    _fields_ = [("blocks", C.POINTER(C.c_int)), ("num_blocks", C.c_int), ("mode", C.c_int), ("scale", C.c_float),
+                ("steps", C.POINTER(C.c_ubyte)), ("num_steps", C.c_int)]
+
+
 class VaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int), ("out_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -206,6 +212,7 @@ SYMBOLS = {
     "k5_guidance_stats_blocks": (_I, [_I64]),
     "k5_guidance_coeffs_bf16": (_I, [_P, _P, _I64, _F, _I, _F, _P, _P, _P, _P]),
     "k5_guided_euler": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _F, _I64, _I, _P, _P]),
+    "k5_skip_euler": (_I, [_P, _P, _P, _P, _F, _P, _F, _F, _P, _P, _P, _F, _I64, _I, _P, _P]),
     "k5_cfg_euler_windows": (_I, [_P, _P, _P, _F, _F, _P, _P, _I, _I, _I, _I64, _P]),
     "k5_sample_windows": (_I, [_P, C.POINTER(SampleWindowsArgs), _P, _P]),
     "k5_x0_preview": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I64, _I, _P]),
@@ -216,6 +223,9 @@ SYMBOLS = {
     "k5_dit_nag_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), _I]),
     "k5_dit_set_guidance": (_I, [_P, C.POINTER(Guidance)]),
     "k5_dit_guidance_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _I]),
+    "k5_dit_set_skip_guidance": (_I, [_P, C.POINTER(SkipGuidance)]),
+    "k5_dit_skip_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _I]),
+    "k5_dit_forward_skip": (_I, [_P, C.POINTER(ForwardArgs), _P, _P, _P]),
     "k5_region_combine_bf16": (_I, [_P, _P, C.c_longlong, _I, _P, _I, _P, _I, _I, _I, _P]),
     "k5_region_weights_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "k5_dit_set_regions": (_I, [_P, C.POINTER(TextCond), _I, _P, _I, _I, _I, _F]),
@@ -580,6 +590,32 @@ def guided_euler_(img, v_cond, v_uncond, ab, dt, source=None, noise=None, keep_m
     with torch.cuda.device(img.device):
         check(lib().k5_guided_euler(ptr(img), ptr(v_cond), ptr(v_uncond), ptr(ab), float(dt), ptr(source), ptr(noise), ptr(keep_mask),
                                     float(sigma_next), cells, C_, ptr(v_out), stream_ptr(img.device)), "k5_guided_euler")
+    return img
+
+
+def skip_euler_(img, v_cond, v_uncond, v_skip, w, g, dt, ab=None, source=None, noise=None, keep_mask=None, sigma_next=0.0, v_out=None):
+    """The update of a skip-layer-guidance step (k5_skip_euler): with base = the velocity cfg_euler_ (v_uncond, w), guided_euler_ (ab) or a run
+    at guidance 1 (v_uncond None) would use, v = base + g * (v_cond - v_skip) as eager bf16 ops, img += bf16(dt * v), then with a keep_mask the
+    keep rule of cfg_euler_edit_ at sigma_next.  v_out (bf16 of img's size, may be v_cond) receives v."""
+    C_ = img.shape[-1]
+    cells = img.numel() // C_
+    for t in (img, source, noise):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != img.shape):
+            raise ValueError("skip_euler_: img, source and noise must be contiguous fp32 tensors of one shape")
+    for v in (v_cond, v_uncond, v_skip, v_out):
+        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != img.numel()):
+            raise ValueError("skip_euler_: the velocities must be contiguous bf16 tensors of img's size")
+    if v_cond is None or v_skip is None:
+        raise ValueError("skip_euler_: a skip step has the conditional and the skip velocity")
+    if ab is not None and (ab.dtype != torch.float32 or ab.numel() != 2 or not ab.is_contiguous()):
+        raise ValueError("skip_euler_: ab must be a contiguous fp32 [2] tensor on the device")
+    if keep_mask is not None and (source is None or noise is None or keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous()
+                                  or keep_mask.numel() != cells):
+        raise ValueError("skip_euler_: keep_mask must be a contiguous fp32 tensor with one value per cell and needs source and noise")
+    _need_cuda(img, v_cond, v_uncond, v_skip, ab, source, noise, keep_mask, v_out)
+    with torch.cuda.device(img.device):
+        check(lib().k5_skip_euler(ptr(img), ptr(v_cond), ptr(v_uncond), ptr(v_skip), float(w), ptr(ab), float(g), float(dt), ptr(source),
+                                  ptr(noise), ptr(keep_mask), float(sigma_next), cells, C_, ptr(v_out), stream_ptr(img.device)), "k5_skip_euler")
     return img
 
 

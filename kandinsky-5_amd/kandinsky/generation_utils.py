@@ -161,6 +161,66 @@ def _guidance_for_call(model, guide):
             model.clear_guidance()
 
 
+def skip_plan(sigmas, slg_interval=None):
+    """The per-step mask of skip-layer guidance over `sigmas` (num_steps + 1 values): a list of num_steps 0 / 1, 1 on the steps with
+    lo <= sigmas[i] <= hi of `slg_interval` = (lo, hi); None = every step.  Host only, like `guidance_plan`."""
+    sig = [float(v) for v in sigmas]
+    n = len(sig) - 1
+    if n < 1:
+        raise ValueError("skip_plan: sigmas must hold num_steps + 1 >= 2 values")
+    if slg_interval is None:
+        return [1] * n
+    try:
+        lo, hi = (float(v) for v in slg_interval)
+    except (TypeError, ValueError):
+        raise ValueError("slg_interval must be (lo, hi)") from None
+    if not lo <= hi:
+        raise ValueError(f"slg_interval must be (lo, hi) with lo <= hi, got ({lo}, {hi})")
+    return [1 if lo <= sig[i] <= hi else 0 for i in range(n)]
+
+
+def _skip_for_run(model, sigmas, first, slg_blocks, slg_scale, slg_interval, slg_mode, windowed):
+    """`generate`'s skip-layer-guidance keywords -> None when they are off (no blocks, scale 0 or an interval without a step: nothing changes),
+    otherwise (blocks, scale, mode, mask of the steps that run) with the ValueErrors of what the engine refuses.  `sigmas`: the full schedule,
+    of which steps `first`.. run."""
+    if slg_blocks is None and not slg_scale and slg_interval is None:
+        return None
+    from .models.dit import check_skip_args
+    nb = getattr(model, "num_visual_blocks", None)   # a wrapped model that does not say is checked by the engine
+    mask = skip_plan(sigmas, slg_interval)[first:]   # cut with the schedule
+    if slg_blocks is None or len(slg_blocks) == 0:
+        check_skip_args([0], slg_scale, slg_mode, mask, 1)   # the numbers are still checked
+        return None
+    blocks, scale, mode, mask = check_skip_args(slg_blocks, slg_scale, slg_mode, mask, nb if nb is not None else max(int(b) for b in slg_blocks) + 1)
+    if scale == 0.0 or not any(mask):
+        return None
+    if windowed:
+        raise ValueError("slg_blocks together with context windows is not supported: a windowed step has one velocity pair per window")
+    if _has_magcache(model):
+        raise ValueError("slg_blocks with MagCache: the ratio table is indexed by the call of a plain run")
+    if getattr(model, "_cfg_pair", None) is not None or getattr(model, "_cfg_parallel", None) is not None:
+        raise ValueError("slg_blocks on a CFG pair: the pair exchanges two velocities, a skip step has three")
+    return blocks, scale, mode, mask
+
+
+@contextlib.contextmanager
+def _skip_for_call(model, skip):
+    """A skip set on a model that takes one (`set_skip_guidance`) for exactly one run; what was there before comes back, also on an exception.
+    skip None: nothing is touched."""
+    if skip is None or not hasattr(model, "set_skip_guidance"):
+        yield
+        return
+    before = getattr(model, "_skip", None)
+    try:
+        model.set_skip_guidance(skip[0], skip[1], skip[2], skip[3])
+        yield
+    finally:
+        if before is not None:
+            model.set_skip_guidance(*before)
+        else:
+            model.clear_skip_guidance()
+
+
 def context_windows(T, frames, overlap):
     """The plan of a long clip sampled as temporal context windows: `(starts, weights)` for T latent frames, windows of `frames` = F frames
     and 0 <= `overlap` < F.  T <= F: one window of T frames with weight 1.  Otherwise nwin = ceil((T - overlap) / (F - overlap)) windows
@@ -379,7 +439,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
              callback=None, preview_every=0, preview_factors=None, preview_x0=False, context_frames=None, context_overlap=None,
              context_text=None, nag_text_embeds=None, nag_text_rope_pos=None, nag_scale=None, nag_tau=2.5, nag_alpha=0.25,
              region_text_embeds=None, region_text_rope_pos=None, region_masks=None, region_base_weight=0.0,
-             guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0, cfg_rescale=0.0):
+             guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0, cfg_rescale=0.0,
+             slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block"):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -433,7 +494,16 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     this call and removed afterwards), any other model through the same two kernels from the per-step loop: the same bits.  ValueError
     together with context windows; for cfg_zero_star / cfg_rescale when every weight is 1; for cfg_zero_init with init_latent; for a plan
     with guided and unguided steps or cfg_zero_init with MagCache or on a CFG pair.  No checkpoint was at hand when this was built: the
-    rules are the published ones, their effect on quality is not measured here."""
+    rules are the published ones, their effect on quality is not measured here.
+
+    `slg_blocks`, `slg_scale`, `slg_interval`, `slg_mode` (optional, extension): skip-layer guidance.  On the steps with
+    lo <= sigma_i <= hi of `slg_interval` (None = every step) the conditional forward forks at the first of the visual blocks `slg_blocks`
+    into a branch that skips them (`slg_mode` "block": the whole block; "attention": only its self-attention) and the step's velocity is
+    v_cfg + slg_scale * (c - c_skip), v_cfg being what the step would otherwise use (CFG, the guidance plan's coefficients — computed over
+    c and u, the skip term is added after them — or c alone at guidance 1).  No blocks, scale 0 or an interval without a step is off and
+    nothing changes.  A `strength < 1` run cuts the mask with the schedule.  ValueError, before anything runs: bad indices, scale or mode;
+    together with MagCache, context windows or a CFG pair; at a wrapped model without `forward_skip`.  The values commonly quoted for other
+    models (blocks 9, 10 at scale 3 on 0.2 <= sigma <= 0.99) are examples: no Kandinsky checkpoint was at hand, visual quality is not claimed."""
     from .models.dit import split_per_sample
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
@@ -453,9 +523,17 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     if any(v is not None for v in guide_kw[:2]) or any(guide_kw[2:]):   # the schedule as `_generate_one` draws it: the same bits
         guide = _guidance_for_run(model, sigma_schedule(num_steps, scheduler_scale, device=device).cpu().tolist(), first, guidance_weight,
                                   *guide_kw, init_latent, plan is not None and len(plan[1]) > 1)
+    skip = None
+    if slg_blocks is not None or slg_scale or slg_interval is not None:
+        skip = _skip_for_run(model, sigma_schedule(num_steps, scheduler_scale, device=device).cpu().tolist(), first, slg_blocks, slg_scale,
+                             slg_interval, slg_mode, plan is not None and len(plan[1]) > 1)
+        from .models.dit import DiffusionTransformer3D
+        if skip is not None and not (type(model) is DiffusionTransformer3D or hasattr(model, "forward_skip")):
+            raise ValueError("slg_blocks needs a model with forward_skip (the engine-backed DiffusionTransformer3D has it): the skip branch runs "
+                             "inside its forward, a wrapped callable without one cannot take it")
     if region_text_embeds is not None and plan is not None and len(plan[1]) > 1:
         raise ValueError("region_text_embeds together with context windows is not supported: the masks cover the clip, a window sees a slice")
-    with _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
+    with _skip_for_call(model, skip), _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
             _regions_for_call(model, region_text_embeds, region_text_rope_pos, region_masks, region_base_weight):
         # one hook for the whole call (it owns the bar): the samples of a batch share it
         watch = _StepWatch(model, callback, preview_every, preview_factors, preview_x0, progress, batch * steps_run, shape[-1])
@@ -469,16 +547,19 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
             run = (model, device, img.contiguous(), num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                    null_text_rope_pos, guidance_weight, scheduler_scale, conf, watch)
             what = (context, visual_cond, visual_cond_mask, init_latent, strength, keep_mask)
-            return _generate_batch(*run, batch, *what, guide=guide) if batch > 1 else _generate_one(*run, plan, *what, guide=guide)
+            if batch > 1:
+                return _generate_batch(*run, batch, *what, guide=guide, skip=skip)
+            return _generate_one(*run, plan, *what, guide=guide, skip=skip)
         finally:
             watch.close()
 
 
 def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                   guidance_weight, scheduler_scale, conf, watch, plan, context, visual_cond, visual_cond_mask, init_latent, strength,
-                  keep_mask, guide=None):
+                  keep_mask, guide=None, skip=None):
     """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch`, the checked `plan` of
-    `_context_plan` and the checked guidance plan `guide` of `_guidance_for_run`; returns the latent."""
+    `_context_plan`, the checked guidance plan `guide` of `_guidance_for_run` and the checked skip set `skip` of `_skip_for_run` (installed on
+    the model by `generate`); returns the latent."""
     context_text = context[2]
     if plan is not None:
         F, starts, weights = plan
@@ -537,6 +618,13 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         u = forward(x, null_text_embeds, null_text_rope_pos, t1000) if guided else None
         return v.contiguous(), None if u is None else u.contiguous()
 
+    def skip_velocities(t1000, guided):   # cond + skip in one forking forward, then uncond: the engine's order
+        x = _model_input(model, img, cond_in)
+        v, sv = model.forward_skip(x, text_embeds["text_embeds"], text_embeds["pooled_embed"], t1000, visual_rope_pos, text_rope_pos,
+                                   scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
+        u = forward(x, null_text_embeds, null_text_rope_pos, t1000) if guided else None
+        return v.contiguous(), None if u is None else u.contiguous(), sv.contiguous()
+
     def pair_velocities(t1000, guided):   # my branch, then the pair's exchange into the reused buffer
         nonlocal both
         v = forward(_model_input(model, img, cond_in), *mine, t1000)
@@ -579,6 +667,13 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         wants_preview = watch.active and watch.preview_at(i, n)
         if i < g_zero_init:
             v, u = (torch.zeros(img.shape, dtype=torch.bfloat16, device=img.device) if wants_preview else None), None   # velocity 0: x0 = x
+        elif skip is not None and skip[3][i]:   # a skip step: three velocities, the skip term added after the step's own combine
+            v, u, sv = skip_velocities(torch.tensor([timestep]) * 1000, guided)
+            ab = E.guidance_coeffs(v, u, w, g_zero_star, g_rescale)[0] if guided and (g_zero_star or g_rescale > 0.0) else None
+            km = None if edit is None else edit[2]
+            E.skip_euler_(img, v, u, sv, w, skip[1], timestep_diff, ab, None if km is None else edit[0], None if km is None else edit[1], km,
+                          sigma_next, v_out=v if wants_preview else None)
+            u = None                   # v now holds the step's velocity (where a preview wants it)
         else:
             v, u = velocities(torch.tensor([timestep]) * 1000, guided)
             if plan is not None:       # the one blend + Euler pass over the clip
@@ -610,7 +705,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
 
 def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                     guidance_weight, scheduler_scale, conf, watch, batch, context, visual_cond, visual_cond_mask, init_latent, strength,
-                    keep_mask, guide=None):
+                    keep_mask, guide=None, skip=None):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
     from .models.dit import split_per_sample
     T = img.shape[0] // batch
@@ -643,7 +738,7 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         plan = _context_plan(model, T, *context, src, watch.every)
         watch.sample = b
         img[rows] = _generate_one(model, device, img[rows].clone(), num_steps, tes[b], nes[b], visual_rope_pos, tps[b], nps[b], guidance_weight,
-                                  scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide)
+                                  scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide, skip=skip)
     return img
 
 
@@ -686,7 +781,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                     callback=None, preview_every=0, preview_factors=None, context_frames=None, context_overlap=None,
                     nag_scale=None, nag_tau=2.5, nag_alpha=0.25, region_text_embeds=None, region_text_rope_pos=None, region_masks=None,
                     region_base_weight=0.0, guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0,
-                    cfg_rescale=0.0):
+                    cfg_rescale=0.0, slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block"):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -707,8 +802,17 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     a list of R prompt strings: those are encoded by the same embedder call as the caption (only their token embeddings are used) and take
     positions 0 .. n-1.  One region set for every sample of a batch.
     `guidance_schedule`, `guidance_interval`, `cfg_zero_star`, `cfg_zero_init`, `cfg_rescale` (optional, extension): per-step guidance
-    weights, a guidance interval, CFG-Zero* and CFG rescale, passed to `generate` (see there).  All off by default."""
+    weights, a guidance interval, CFG-Zero* and CFG rescale, passed to `generate` (see there).  All off by default.
+    `slg_blocks`, `slg_scale`, `slg_interval`, `slg_mode` (optional, extension): skip-layer guidance, passed to `generate` (see there).  Off by
+    default."""
     batch, frames, height, width, channels = shape
+    skip_kw = {}
+    if slg_blocks is not None or slg_scale or slg_interval is not None:   # before any model runs: the numbers and what the handle's state refuses
+        skip_plan([1.0, 0.0], slg_interval)   # (what depends on the schedule is checked by `generate`)
+        windowed = context_frames is not None and len(context_windows(
+            frames, context_frames, int(context_frames) // 4 if context_overlap is None else int(context_overlap))[0]) > 1
+        _skip_for_run(dit, [1.0, 0.0], 0, slg_blocks, slg_scale, None, slg_mode, windowed)
+        skip_kw = dict(slg_blocks=slg_blocks, slg_scale=slg_scale, slg_interval=slg_interval, slg_mode=slg_mode)
     guide_kw = {k: v for k, v in dict(guidance_schedule=guidance_schedule, guidance_interval=guidance_interval, cfg_zero_star=cfg_zero_star,
                                       cfg_zero_init=cfg_zero_init, cfg_rescale=cfg_rescale).items() if v}
     if guide_kw:   # before any model runs: the numbers (what depends on the schedule is checked by `generate`)
@@ -814,7 +918,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         latent = generate(dit, device, (batch * frames, height, width, channels), num_steps, cond, uncond, grid,
                           text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
                           progress=progress, batch=batch, callback=callback, preview_every=preview_every,
-                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw, **guide_kw)
+                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw, **guide_kw, **skip_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

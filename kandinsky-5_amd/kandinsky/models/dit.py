@@ -138,6 +138,38 @@ def check_guidance_args(weights, zero_star, zero_init_steps, rescale):
     return weights, bool(zero_star), k, phi
 
 
+SKIP_MODES = {"block": 0, "attention": 1}
+
+
+def check_skip_args(blocks, scale, mode, steps, num_visual_blocks):
+    """The ValueErrors of `set_skip_guidance` / `generate(slg_blocks=, slg_scale=, slg_mode=)`; returns (blocks as a list of ints, scale, mode
+    name, steps as a list of 0 / 1 or None)."""
+    try:
+        idx = [int(b) for b in blocks]
+        ok = all(i == b for i, b in zip(idx, blocks))
+    except (TypeError, ValueError):
+        raise ValueError("skip guidance: blocks must be a sequence of visual block indices") from None
+    if not idx or not ok:
+        raise ValueError("skip guidance: blocks must hold at least one integer block index")
+    if any(i < 0 or i >= int(num_visual_blocks) for i in idx):
+        raise ValueError(f"skip guidance: block indices must be in 0..{int(num_visual_blocks) - 1} (got {idx})")
+    if len(set(idx)) != len(idx):
+        raise ValueError(f"skip guidance: a block is listed twice ({idx})")
+    try:
+        scale = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError("skip guidance: scale must be a number") from None
+    if not math.isfinite(scale) or scale < 0.0:
+        raise ValueError(f"skip guidance: scale must be a finite number >= 0 (got {scale})")
+    if mode not in SKIP_MODES:
+        raise ValueError(f"skip guidance: mode must be 'block' or 'attention' (got {mode!r})")
+    if steps is not None:
+        steps = [1 if bool(v) else 0 for v in steps]
+        if not steps:
+            raise ValueError("skip guidance: steps must hold one 0 / 1 per step")
+    return idx, scale, mode, steps
+
+
 def check_nag_args(text_embeds, text_rope_pos, scale, tau, alpha):
     """The ValueErrors of `set_nag` / `generate(nag_scale=, nag_tau=, nag_alpha=, nag_text_embeds=)`; returns (scale, tau, alpha) as floats."""
     scale, tau, alpha = check_nag_numbers(scale, tau, alpha)
@@ -228,6 +260,7 @@ class DiffusionTransformer3D(nn.Module):
         self.out_visual_dim = out_visual_dim
         self.model_dim = model_dim
         self.patch_size = tuple(patch_size)
+        self.num_visual_blocks = int(num_visual_blocks)
         self.visual_cond = visual_cond
         self._cfg = dict(in_visual_dim=in_visual_dim, in_text_dim=in_text_dim, in_text_dim2=in_text_dim2,
                          time_dim=time_dim, out_visual_dim=out_visual_dim, patch_size=tuple(patch_size),
@@ -257,6 +290,7 @@ class DiffusionTransformer3D(nn.Module):
         self._watch = None           # (trampoline, k5_watch and the arrays it points to) of set_watch: re-installed when the engine is rebuilt
         self._nag = None             # the negative prompt of set_nag, its k5_text_cond and what that points to: re-installed likewise
         self._regions = None         # the prompts and masks of set_regions, their k5_text_cond array and what it points to: likewise
+        self._skip = None            # the set of set_skip_guidance (blocks, scale, mode, steps | None): likewise
         self._guidance = None        # the plan of set_guidance (weights list | None, zero_star, zero_init_steps, rescale): likewise
 
     # ---------------------------------------------------------------- engine lifetime
@@ -332,6 +366,8 @@ class DiffusionTransformer3D(nn.Module):
             self._install_regions()
         if getattr(self, "_guidance", None) is not None:
             self._install_guidance()
+        if getattr(self, "_skip", None) is not None:
+            self._install_skip()
         if getattr(self, "mag_ratios", None) is not None or getattr(self, "_magcache_calibrate", None) is not None:   # set before the weights were loaded / the handle rebuilt
             from ..magcache_utils import _apply
             _apply(self)
@@ -692,6 +728,71 @@ class DiffusionTransformer3D(nn.Module):
             E.check(E.lib().k5_dit_guidance_state(self._handle, C.byref(on), C.byref(a), C.byref(b), C.byref(z), int(bool(reset))),
                     "k5_dit_guidance_state")
         return bool(on.value), a.value, b.value, z.value
+
+    # ---------------------------------------------------------------- skip-layer guidance: a third, block-skipping forward
+    def set_skip_guidance(self, blocks, scale, mode="block", steps=None):
+        """Skip-layer guidance (k5_dit_set_skip_guidance): at a skip step the conditional forward forks at the first of `blocks` (visual block
+        indices) into a branch that skips them — mode "block": the whole block is the identity on the visual stream; "attention": only its
+        self-attention residual is dropped — and the step's velocity becomes v_cfg + scale * (c - c_skip).  `steps`: one 0 / 1 per step of the
+        calls to come (`generation_utils.skip_plan` builds it; None = every step).  scale == 0 is accepted and means off.  `sample` refuses,
+        before anything runs: a `steps` list of another length than its steps, a CFG pair, MagCache or its calibration, and `windows`.
+        No checkpoint was at hand when this was built: the rule is the published one, its effect on quality is not measured here."""
+        self._skip = check_skip_args(blocks, scale, mode, steps, self.num_visual_blocks)
+        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
+            try:
+                self._install_skip()
+            except Exception:
+                self._skip = None
+                raise
+        return self
+
+    def _install_skip(self):
+        blocks, scale, mode, steps = self._skip
+        g = E.SkipGuidance()
+        barr = (C.c_int * len(blocks))(*blocks)           # both copied by the call
+        g.blocks, g.num_blocks = C.cast(barr, C.POINTER(C.c_int)), len(blocks)
+        g.mode, g.scale = SKIP_MODES[mode], float(scale)
+        sarr = None
+        if steps is not None:
+            sarr = (C.c_ubyte * len(steps))(*steps)
+            g.steps, g.num_steps = C.cast(sarr, C.POINTER(C.c_ubyte)), len(steps)
+        E.check(E.lib().k5_dit_set_skip_guidance(self._handle, C.byref(g)), "k5_dit_set_skip_guidance")
+
+    def clear_skip_guidance(self):
+        """Remove the skip set: `sample` enqueues exactly what it did before `set_skip_guidance`."""
+        self._skip = None
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_set_skip_guidance(self._handle, None), "k5_dit_set_skip_guidance")
+        return self
+
+    def skip_state(self, reset=False):
+        """(on, skip_steps, blocks_shared, blocks_run): whether skip guidance is on, how many skip steps the engine has enqueued, and how many
+        visual blocks the skip branches took from the conditional forward / ran themselves (k5_dit_skip_state).  `reset` zeroes the counts."""
+        on, a, b, r = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        if self._handle is not None:
+            E.check(E.lib().k5_dit_skip_state(self._handle, C.byref(on), C.byref(a), C.byref(b), C.byref(r), int(bool(reset))), "k5_dit_skip_state")
+        return bool(on.value), a.value, b.value, r.value
+
+    @torch.no_grad()
+    def forward_skip(self, x, text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos,
+                     scale_factor=(1.0, 1.0, 1.0), sparse_params=None):
+        """`forward` with the skip branch of `set_skip_guidance` (k5_dit_forward_skip): returns (v_cond, v_skip), v_cond being `forward`'s bits."""
+        if getattr(self, "_skip", None) is None:
+            raise ValueError("forward_skip: no skip set (set_skip_guidance)")
+        if not x.is_cuda:
+            raise RuntimeError("DiffusionTransformer3D.forward_skip needs CUDA (HIP) tensors; there is no CPU fallback")
+        h = self.engine(x.device)
+        x = x.float().contiguous()
+        T, H, W, Cx = x.shape
+        text_embed, pooled_text_embed = text_embed.to(x.device), pooled_text_embed.to(x.device)
+        t_val = float(time.reshape(-1)[0]) if torch.is_tensor(time) else float(time)
+        keep = [x]
+        a = self._forward_args((T, H, W), x.data_ptr(), Cx, text_embed, pooled_text_embed, t_val, visual_rope_pos,
+                               text_rope_pos, scale_factor, sparse_params, keep)
+        out = torch.empty(2, T, H, W, self.out_visual_dim, dtype=torch.bfloat16, device=x.device)
+        with torch.cuda.device(x.device):
+            E.check(E.lib().k5_dit_forward_skip(h, C.byref(a), out[0].data_ptr(), out[1].data_ptr(), E.stream_ptr(x.device)), "k5_dit_forward_skip")
+        return out[0], out[1]
 
     # ---------------------------------------------------------------- regional prompts: a prompt per masked region in one forward
     def set_regions(self, text_embeds_list, rope_pos_list, masks, base_weight=0.0):

@@ -94,7 +94,8 @@ class Kandinsky5T2VPipeline:
                  progress: bool = True, image=None, video=None, strength: float = None, mask=None, callback=None,
                  preview_every: int = 0, preview_factors=None, context_seconds: float = None, context_overlap_seconds: float = None,
                  nag_scale: float = None, nag_tau: float = 2.5, nag_alpha: float = 0.25, regions=None, region_base_weight: float = 0.0,
-                 guidance_schedule=None, guidance_interval=None, cfg_zero_star: bool = False, cfg_zero_init: int = 0, cfg_rescale: float = 0.0):
+                 guidance_schedule=None, guidance_interval=None, cfg_zero_star: bool = False, cfg_zero_init: int = 0, cfg_rescale: float = 0.0,
+                 slg_blocks=None, slg_scale: float = 0.0, slg_interval=None, slg_mode: str = "block"):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -128,8 +129,20 @@ class Kandinsky5T2VPipeline:
         per step (a list of num_steps values or a callable `(i, sigma_i)`), a sigma interval outside which the unconditional forward is
         not run, CFG-Zero* with its zero-init of the first K steps, and CFG rescale in [0, 1]; see `generate`.  All off by default, every
         rank passes the same values.  Not together with `context_seconds`.  No checkpoint was at hand when this was written: the rules are
-        the published ones, what they do to a picture is not claimed."""
+        the published ones, what they do to a picture is not claimed.
+        `slg_blocks`, `slg_scale`, `slg_interval`, `slg_mode` (optional, extension): skip-layer guidance,
+        `pipe(text, slg_blocks=[9, 10], slg_scale=3.0, slg_interval=(0.2, 0.99))` — on the steps whose sigma lies in the interval the model
+        runs once more with the listed visual blocks (mode "attention": only their self-attention) skipped and the velocity is pushed away
+        from that weakened prediction; see `generate`.  Off by default, every rank passes the same values.  Not together with
+        `context_seconds`, MagCache or a CFG pair.  The values shown are the ones commonly quoted for other models: no Kandinsky checkpoint
+        was at hand when this was written, what they do to a picture is not claimed."""
         ctx = {}
+        skip_kw = {}
+        if slg_blocks is not None or slg_scale or slg_interval is not None:
+            from .generation_utils import _skip_for_run, skip_plan
+            skip_plan([1.0, 0.0], slg_interval)
+            _skip_for_run(self.dit, [1.0, 0.0], 0, slg_blocks, slg_scale, None, slg_mode, context_seconds is not None)
+            skip_kw = dict(slg_blocks=slg_blocks, slg_scale=slg_scale, slg_interval=slg_interval, slg_mode=slg_mode)
         guide_kw = {k: v for k, v in dict(guidance_schedule=guidance_schedule, guidance_interval=guidance_interval, cfg_zero_star=cfg_zero_star,
                                           cfg_zero_init=cfg_zero_init, cfg_rescale=cfg_rescale).items() if v}
         if guide_kw:
@@ -199,6 +212,6 @@ class Kandinsky5T2VPipeline:
                                  device=self.device_map["dit"], vae_device=self.device_map["vae"],
                                  text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload,
                                  image=image, video=video, strength=strength, mask=mask, callback=callback,
-                                 preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw, **guide_kw)
+                                 preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw, **guide_kw, **skip_kw)
         torch.cuda.empty_cache()
         return self._save(images, time_length, save_path) if self.local_dit_rank == 0 else None

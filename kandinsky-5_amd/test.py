@@ -90,7 +90,41 @@ def build_parser():
     p.add_argument("--cfg_zero_init", type=int, default=argparse.SUPPRESS, metavar="K", help="CFG-Zero* zero-init: the first K steps leave the latent as it is")
     p.add_argument("--cfg_rescale", type=float, default=argparse.SUPPRESS, metavar="PHI",
                    help="CFG rescale: pull the guided velocity's std towards the conditional one's, PHI in [0, 1]")
+    p.add_argument("--slg_blocks", type=int, nargs="+", default=argparse.SUPPRESS, metavar="B",
+                   help="skip-layer guidance: the visual blocks a third forward skips (e.g. 9 10); needs --slg_scale")
+    p.add_argument("--slg_scale", type=float, default=argparse.SUPPRESS, metavar="G",
+                   help="with --slg_blocks: how far the velocity is pushed away from the block-skipping prediction, >= 0 (commonly 3 — not tuned "
+                        "on these checkpoints)")
+    p.add_argument("--slg_interval", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("LO", "HI"),
+                   help="with --slg_blocks: only on the steps whose sigma lies in [LO, HI] (default every step)")
+    p.add_argument("--slg_mode", choices=("block", "attention"), default=argparse.SUPPRESS,
+                   help="with --slg_blocks: skip the whole block (default) or only its self-attention")
     return p
+
+
+def skip_keywords(args):
+    """--slg_blocks / --slg_scale / --slg_interval / --slg_mode -> the pipeline's keywords"""
+    if not hasattr(args, "slg_blocks"):
+        if hasattr(args, "slg_scale") or hasattr(args, "slg_interval") or hasattr(args, "slg_mode"):
+            raise ValueError("--slg_scale, --slg_interval and --slg_mode need --slg_blocks")
+        return {}
+    if not hasattr(args, "slg_scale"):
+        raise ValueError("--slg_blocks needs --slg_scale")
+    kw = {"slg_blocks": list(args.slg_blocks), "slg_scale": args.slg_scale, "slg_mode": getattr(args, "slg_mode", "block")}
+    if any(b < 0 for b in kw["slg_blocks"]) or len(set(kw["slg_blocks"])) != len(kw["slg_blocks"]):
+        raise ValueError(f"--slg_blocks must be distinct block indices >= 0 (got {kw['slg_blocks']})")
+    if not kw["slg_scale"] >= 0.0 or kw["slg_scale"] == float("inf"):
+        raise ValueError(f"--slg_scale must be a finite number >= 0 (got {kw['slg_scale']})")
+    if hasattr(args, "slg_interval"):
+        lo, hi = args.slg_interval
+        if not lo <= hi:
+            raise ValueError(f"--slg_interval needs LO <= HI (got {lo}, {hi})")
+        kw["slg_interval"] = (lo, hi)
+    if hasattr(args, "context_seconds"):
+        raise ValueError("--slg_blocks together with --context_seconds is not supported")
+    if getattr(args, "magcache", False):
+        raise ValueError("--slg_blocks together with --magcache is not supported: the ratio table is indexed by the call of a plain run")
+    return kw
 
 
 def guidance_keywords(args):
@@ -212,6 +246,7 @@ def main(argv=None):
     nag_kw = nag_keywords(args)   # refused before the models load
     region_kw = region_keywords(args)
     guide_kw = guidance_keywords(args)
+    skip_kw = skip_keywords(args)
     from kandinsky import get_T2V_pipeline
     pipe = get_T2V_pipeline(device_map={"dit": "cuda:0", "vae": "cuda:0", "text_embedder": "cuda:0"}, conf_path=args.config,
                             offload=args.offload, magcache=args.magcache and not args.calibrate_magcache,
@@ -249,6 +284,7 @@ def main(argv=None):
     edit_kw.update(nag_kw)
     edit_kw.update(region_kw)
     edit_kw.update(guide_kw)
+    edit_kw.update(skip_kw)
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
