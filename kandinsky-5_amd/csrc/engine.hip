@@ -1769,6 +1769,11 @@ int text_stream_run(k5_dit* d, hipStream_t s, const k5_text_cond& c, k5_dit::Tex
   return text_cross_kv(d, s, st, stacked);
 }
 
+// which MagCache mode the handle is in, as the refusal messages say it ("... %s on the handle"); nullptr = neither
+static const char* magcache_mode(const k5_dit* d) {
+  return d->mag.on ? "MagCache is set" : d->cal.on ? "MagCache calibration is" : nullptr;
+}
+
 int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, float time, const float* x,
                  int x_channels, void* out_velocity, hipStream_t s, const float* tvec = nullptr, const int* step = nullptr,
                  int text_slot = -1, const float* vcond = nullptr, void* out_skip = nullptr) {
@@ -1795,8 +1800,8 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
   auto& sk = d->skip;
   if (out_skip) {   // the forking forward (k5_dit_forward_skip, a skip step of k5_sample*): refused before anything is enqueued
     if (!sk.on) { k5_set_error("k5_dit_forward_skip: no skip set on the handle (k5_dit_set_skip_guidance)"); return K5_ERR_STATE; }
-    if (d->mag.on || d->cal.on) {
-      k5_set_error("k5_dit_forward_skip: %s on the handle: the ratio table is indexed by the calls of a plain run", d->mag.on ? "MagCache is set" : "MagCache calibration is");
+    if (const char* mode = magcache_mode(d)) {
+      k5_set_error("k5_dit_forward_skip: %s on the handle: the ratio table is indexed by the calls of a plain run", mode);
       return K5_ERR_STATE;
     }
   }
@@ -2359,6 +2364,7 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
                            const k5_sample_windows_args* win, const char* who) {
   if (!d || !a || !a->latent || !a->sigmas || a->num_steps <= 0) return K5_ERR_ARG;
   const k5_dit_config& c = d->cfg;
+  const char* const mag = magcache_mode(d);
   if (vcond && !c.visual_cond) { k5_set_error("%s: the handle was created with visual_cond = 0", who); return K5_ERR_ARG; }
   if (vcond && (reinterpret_cast<uintptr_t>(vcond) & 3)) { k5_set_error("%s: visual_cond is not 4-byte aligned", who); return K5_ERR_ARG; }
   const int64_t n = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W * c.out_visual_dim;
@@ -2417,9 +2423,8 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
                    who, what);
       return K5_ERR_STATE;
     }
-    if ((mixed || zinit) && (d->mag.on || d->cal.on)) {
-      k5_set_error("%s: the guidance plan has %s and %s on the handle: the ratio table is indexed by the call of a plain run", who, what,
-                   d->mag.on ? "MagCache is set" : "MagCache calibration is");
+    if ((mixed || zinit) && mag) {
+      k5_set_error("%s: the guidance plan has %s and %s on the handle: the ratio table is indexed by the call of a plain run", who, what, mag);
       return K5_ERR_STATE;
     }
     if (zinit && edit) { k5_set_error("%s: zero-init steps together with editing are not supported", who); return K5_ERR_UNSUPPORTED; }
@@ -2435,9 +2440,9 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
       k5_set_error("%s: skip-layer guidance is set (k5_dit_set_skip_guidance) and the handle is in a CFG pair: the pair exchanges two velocities, a skip step has three", who);
       return K5_ERR_STATE;
     }
-    if (d->mag.on || d->cal.on) {
+    if (mag) {
       k5_set_error("%s: skip-layer guidance is set (k5_dit_set_skip_guidance) and %s on the handle: the ratio table is indexed by the calls of a plain run",
-                   who, d->mag.on ? "MagCache is set" : "MagCache calibration is");
+                   who, mag);
       return K5_ERR_STATE;
     }
     if (win) {
@@ -2448,9 +2453,8 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
   if (win) {
     if (edit) { k5_set_error("%s: editing with context windows is not supported", who); return K5_ERR_UNSUPPORTED; }
     if (rank_group(d)) { k5_set_error("%s: the handle is in a %s (context windows are single-rank only)", who, rank_group(d)); return K5_ERR_STATE; }
-    if (d->mag.on || d->cal.on) {
-      k5_set_error("%s: %s on the handle: the ratio table is indexed by the call of a plain run, a windowed run makes nwin calls per step", who,
-                   d->mag.on ? "MagCache is set" : "MagCache calibration is");
+    if (mag) {
+      k5_set_error("%s: %s on the handle: the ratio table is indexed by the call of a plain run, a windowed run makes nwin calls per step", who, mag);
       return K5_ERR_STATE;
     }
     if (wt.on && wt.every > 0) {
@@ -2585,6 +2589,17 @@ struct SampleRun {
 
 // The captured step and its executable.  On every way out the stream is drained before they go: the executable graph must outlive its
 // launches (this also orders the caller's stream after the sampler).  An eager run holds neither and is not synchronised.
+// The handle's launch counters that a step advances from host code.  A replay of the captured step enqueues the same launches without that
+// host code, so sample_impl takes the difference over the capture and adds it per further replay.  A new counter is one more entry of `of` (and of K).
+struct ReplayCounts {
+  static constexpr int K = 4;
+  long long per_step[K] = {};
+  static void of(k5_dit* d, long long* (&c)[K]) { c[0] = &d->nag.combines; c[1] = &d->regions.combines; c[2] = &d->skip.blocks_shared; c[3] = &d->skip.blocks_run; }
+  void snapshot(k5_dit* d) { long long* c[K]; of(d, c); for (int i = 0; i < K; ++i) per_step[i] = *c[i]; }
+  void difference(k5_dit* d) { long long* c[K]; of(d, c); for (int i = 0; i < K; ++i) per_step[i] = *c[i] - per_step[i]; }
+  void add(k5_dit* d) const { long long* c[K]; of(d, c); for (int i = 0; i < K; ++i) *c[i] += per_step[i]; }
+};
+
 struct GraphGuard {
   hipStream_t s; hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
   ~GraphGuard() {
@@ -2788,25 +2803,22 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   // Step 0 is always eager.  In graph mode step 1 is captured and instantiated (after the watch has followed step 0: those launches are not
   // part of the graph) and steps 1.. are launches of the executable; between them the watch reads sigma_next as a host scalar.
   GraphGuard cap{s};
-  long long nag_per_step = 0, reg_per_step = 0, shared_per_step = 0, run_per_step = 0;
+  ReplayCounts counts;
   for (int i = 0; i < N; ++i) {
     if (i == 0 || !graph) K5CHK(r.step(i));
     else {
       if (i == 1) {
         HIPCHK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const long long nag_before = d->nag.combines, reg_before = d->regions.combines;
-        const long long shared_before = d->skip.blocks_shared, run_before = d->skip.blocks_run;
+        counts.snapshot(d);
         const int rc = r.step(1);
-        shared_per_step = d->skip.blocks_shared - shared_before; run_per_step = d->skip.blocks_run - run_before;
-        reg_per_step = d->regions.combines - reg_before;
-        nag_per_step = d->nag.combines - nag_before;   // k5_dit_nag_state counts launches: the capture stands for step 1's, every further replay adds as many
+        counts.difference(d);   // the state getters count launches: the capture stands for step 1's, every further replay adds as many
         const hipError_t ec = hipStreamEndCapture(s, &cap.g);
         if (rc != K5_OK) return rc;
         if (ec != hipSuccess || !cap.g) { k5_set_error("hipStreamEndCapture: %s", hipGetErrorString(ec)); return K5_ERR_HIP; }
         if (hipGraphInstantiate(&cap.ge, cap.g, nullptr, nullptr, 0) != hipSuccess) { k5_set_error("hipGraphInstantiate failed"); return K5_ERR_HIP; }
       }
       if (hipGraphLaunch(cap.ge, s) != hipSuccess) { k5_set_error("hipGraphLaunch failed"); return K5_ERR_HIP; }
-      if (i > 1) { d->nag.combines += nag_per_step; d->regions.combines += reg_per_step; d->skip.blocks_shared += shared_per_step; d->skip.blocks_run += run_per_step; }
+      if (i > 1) counts.add(d);
     }
     if (i == first) K5CHK(decide_fuse());
     if (gd.on) (r.kind(i) == SampleRun::GUIDED ? gd.guided : r.kind(i) == SampleRun::UNGUIDED ? gd.unguided : gd.zero) += 1;

@@ -15,6 +15,8 @@ os.environ.setdefault("TOKENIZERS_PARALLELISM", "False")
 import torch
 
 from . import _engine as E
+from .models.dit import (DiffusionTransformer3D, SamplingInterrupted, StepInfo, _is_guided, check_guidance_args, check_nag_args,
+                         check_nag_numbers, check_region_args, check_skip_args, check_watch_args, split_per_sample)
 
 
 def _attr(obj, name, default=None):
@@ -55,7 +57,7 @@ def get_velocity(dit, x, t, text_embeds, null_text_embeds, visual_rope_pos, text
     """reference generation_utils.py:39-77 (two forwards + bf16 CFG combine)."""
     pred_velocity = dit(x, text_embeds["text_embeds"], text_embeds["pooled_embed"], t * 1000, visual_rope_pos,
                         text_rope_pos, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params)
-    if abs(guidance_weight - 1.0) > 1e-6:
+    if _is_guided(guidance_weight):
         uncond_pred_velocity = dit(x, null_text_embeds["text_embeds"], null_text_embeds["pooled_embed"], t * 1000,
                                    visual_rope_pos, null_text_rope_pos, scale_factor=conf.metrics.scale_factor,
                                    sparse_params=sparse_params)
@@ -109,17 +111,12 @@ def guidance_plan(sigmas, guidance_weight, guidance_schedule=None, guidance_inte
     return weights
 
 
-def _is_guided(w):
-    return abs(w - 1.0) > 1e-6   # the engine's rule (reference generation_utils.py:63)
-
-
 def _guidance_for_run(model, sigmas, first, guidance_weight, guidance_schedule, guidance_interval, cfg_zero_star, cfg_zero_init, cfg_rescale,
                       init_latent, windowed):
     """`generate`'s guidance keywords -> None when all are off (nothing changes), otherwise (weights of the steps that run | None, zero_star,
     zero_init_steps, rescale) with the ValueErrors of what the engine refuses.  `sigmas`: the full schedule, of which steps `first`.. run."""
     if guidance_schedule is None and guidance_interval is None and not cfg_zero_star and not cfg_zero_init and not cfg_rescale:
         return None
-    from .models.dit import check_guidance_args
     weights = None
     if guidance_schedule is not None or guidance_interval is not None:
         weights = guidance_plan(sigmas, guidance_weight, guidance_schedule, guidance_interval)[first:]   # cut with the schedule
@@ -137,28 +134,10 @@ def _guidance_for_run(model, sigmas, first, guidance_weight, guidance_schedule, 
         if _has_magcache(model):
             raise ValueError("a guidance plan with guided and unguided steps, or with cfg_zero_init, with MagCache: the ratio table is indexed "
                              "by the call of a plain run")
-        if getattr(model, "_cfg_pair", None) is not None or getattr(model, "_cfg_parallel", None) is not None:
+        if _is_cfg_pair(model):
             raise ValueError("a guidance plan with guided and unguided steps, or with cfg_zero_init, on a CFG pair: the unconditional group "
                              "would have steps with nothing to exchange")
     return weights, zero_star, zero_init, rescale
-
-
-@contextlib.contextmanager
-def _guidance_for_call(model, guide):
-    """A guidance plan on the engine-backed model for exactly one sample / sample_many call; what was there before comes back, also on an
-    exception.  guide None: nothing is touched."""
-    if guide is None:
-        yield
-        return
-    before = model._guidance
-    try:
-        model.set_guidance(*guide)
-        yield
-    finally:
-        if before is not None:
-            model.set_guidance(*before)
-        else:
-            model.clear_guidance()
 
 
 def skip_plan(sigmas, slg_interval=None):
@@ -185,7 +164,6 @@ def _skip_for_run(model, sigmas, first, slg_blocks, slg_scale, slg_interval, slg
     of which steps `first`.. run."""
     if slg_blocks is None and not slg_scale and slg_interval is None:
         return None
-    from .models.dit import check_skip_args
     nb = getattr(model, "num_visual_blocks", None)   # a wrapped model that does not say is checked by the engine
     mask = skip_plan(sigmas, slg_interval)[first:]   # cut with the schedule
     if slg_blocks is None or len(slg_blocks) == 0:
@@ -198,7 +176,7 @@ def _skip_for_run(model, sigmas, first, slg_blocks, slg_scale, slg_interval, slg
         raise ValueError("slg_blocks together with context windows is not supported: a windowed step has one velocity pair per window")
     if _has_magcache(model):
         raise ValueError("slg_blocks with MagCache: the ratio table is indexed by the call of a plain run")
-    if getattr(model, "_cfg_pair", None) is not None or getattr(model, "_cfg_parallel", None) is not None:
+    if _is_cfg_pair(model):
         raise ValueError("slg_blocks on a CFG pair: the pair exchanges two velocities, a skip step has three")
     return blocks, scale, mode, mask
 
@@ -206,19 +184,23 @@ def _skip_for_run(model, sigmas, first, slg_blocks, slg_scale, slg_interval, slg
 @contextlib.contextmanager
 def _skip_for_call(model, skip):
     """A skip set on a model that takes one (`set_skip_guidance`) for exactly one run; what was there before comes back, also on an exception.
-    skip None: nothing is touched."""
+    skip None, or a model without `set_skip_guidance`: nothing is touched.  The engine-backed model does it itself (`setting_for_call`); a
+    wrapper that only hands `set_skip_guidance`, `clear_skip_guidance` and `_skip` on to one is served through those."""
     if skip is None or not hasattr(model, "set_skip_guidance"):
         yield
-        return
-    before = getattr(model, "_skip", None)
-    try:
-        model.set_skip_guidance(skip[0], skip[1], skip[2], skip[3])
-        yield
-    finally:
-        if before is not None:
-            model.set_skip_guidance(*before)
-        else:
-            model.clear_skip_guidance()
+    elif hasattr(model, "setting_for_call"):
+        with model.setting_for_call("skip_guidance", skip):
+            yield
+    else:
+        before = getattr(model, "_skip", None)
+        try:
+            model.set_skip_guidance(*skip)
+            yield
+        finally:
+            if before is not None:
+                model.set_skip_guidance(*before)
+            else:
+                model.clear_skip_guidance()
 
 
 def context_windows(T, frames, overlap):
@@ -277,6 +259,11 @@ def _has_magcache(model):
     return any(getattr(m, "mag_ratios", None) is not None or getattr(m, "_magcache_calibrate", None) is not None for m in mods)
 
 
+def _is_cfg_pair(model):
+    """True when the model is one branch of classifier-free guidance: an engine-side CFG pair or the CFG-parallel of a wrapped model."""
+    return getattr(model, "_cfg_pair", None) is not None or getattr(model, "_cfg_parallel", None) is not None
+
+
 def _check_edit_args(model, shape, init_latent, strength, keep_mask):
     """The ValueErrors of `generate`'s editing keywords."""
     edit_first_step(1, strength)   # strength in (0, 1]
@@ -296,7 +283,6 @@ def _check_edit_args(model, shape, init_latent, strength, keep_mask):
 
 
 def _is_multi_rank_engine(model):
-    from .models.dit import DiffusionTransformer3D
     return type(model) is DiffusionTransformer3D and (model._sp is not None or model._cfg_pair is not None)
 
 
@@ -305,7 +291,6 @@ class _StepWatch:
     per-step Python paths (called from the loop), so a callback sees the same sequence whichever ran."""
 
     def __init__(self, model, callback, preview_every, preview_factors, want_x0, progress, total, channels):
-        from .models.dit import check_watch_args
         from .preview import as_factors
         W, b = as_factors(preview_factors)
         self.W, self.every = check_watch_args(callback, preview_every, W, want_x0, channels)
@@ -340,68 +325,32 @@ class _StepWatch:
             self.bar.close()
             self.bar = None
 
-    @contextlib.contextmanager
-    def installed(self, model):
-        """Context: this hook as the watch of an engine-backed model for one sample / sample_many call; what was there before comes back."""
-        if not self.active:
-            yield
-            return
-        before = model._watch
-        try:
-            model.set_watch(self.step, self.every, self.W, self.b, self.want_x0)
-            yield
-        finally:
-            model._watch = before
-            if before is not None:
-                model._install_watch()
-            else:
-                model.clear_watch()
+    def watch_args(self):
+        """This hook as the arguments of `set_watch` for one sample / sample_many call of an engine-backed model (`setting_for_call`); None
+        when there is nothing to watch."""
+        return (self.step, self.every, self.W, self.b, self.want_x0) if self.active else None
 
 
-@contextlib.contextmanager
 def _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha):
-    """`generate`'s NAG keywords as guidance for exactly one call: set on the model, and what was there before put back, also on an exception.
-    nag_scale None: nothing is touched."""
+    """`generate`'s NAG keywords, checked, as the model's context for exactly one call.  nag_scale None: nothing is touched."""
     if nag_scale is None:
-        yield
-        return
-    from .models.dit import DiffusionTransformer3D, check_nag_args
+        return contextlib.nullcontext()
     check_nag_args(nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha)
     if type(model) is not DiffusionTransformer3D:
         raise ValueError("nag_scale needs the engine-backed DiffusionTransformer3D: normalized attention guidance runs inside its "
                          "forward, a wrapped or duck-typed model has no hook for it")
-    before = model._nag
-    try:
-        model.set_nag(nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha)
-        yield
-    finally:
-        if before is not None:
-            model.set_nag({"text_embeds": before["text"], "pooled_embed": before["pooled"]}, before["pos"], *before["args"])
-        else:
-            model.clear_nag()
+    return model.setting_for_call("nag", (nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha))
 
 
-@contextlib.contextmanager
 def _regions_for_call(model, region_text_embeds, region_text_rope_pos, region_masks, region_base_weight):
-    """`generate`'s region keywords as regional prompts for exactly one call: set on the model, and what was there before put back, also on
-    an exception.  region_text_embeds None: nothing is touched."""
+    """`generate`'s region keywords, checked, as the model's context for exactly one call.  region_text_embeds None: nothing is touched."""
     if region_text_embeds is None:
-        yield
-        return
-    from .models.dit import DiffusionTransformer3D, check_region_args
+        return contextlib.nullcontext()
     check_region_args(region_text_embeds, region_text_rope_pos, region_masks, region_base_weight)
     if type(model) is not DiffusionTransformer3D:
         raise ValueError("region_text_embeds needs the engine-backed DiffusionTransformer3D: regional prompts run inside its forward, a "
                          "wrapped or duck-typed model has no hook for them")
-    before = model._regions
-    try:
-        model.set_regions(region_text_embeds, region_text_rope_pos, region_masks, region_base_weight)
-        yield
-    finally:
-        if before is not None:
-            model.set_regions([{"text_embeds": t} for t in before["text"]], before["pos"], before["masks"], before["base_weight"])
-        else:
-            model.clear_regions()
+    return model.setting_for_call("regions", (region_text_embeds, region_text_rope_pos, region_masks, region_base_weight))
 
 
 def _conditioning(model, img, visual_cond, visual_cond_mask):
@@ -504,7 +453,6 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     nothing changes.  A `strength < 1` run cuts the mask with the schedule.  ValueError, before anything runs: bad indices, scale or mode;
     together with MagCache, context windows or a CFG pair; at a wrapped model without `forward_skip`.  The values commonly quoted for other
     models (blocks 9, 10 at scale 3 on 0.2 <= sigma <= 0.99) are examples: no Kandinsky checkpoint was at hand, visual quality is not claimed."""
-    from .models.dit import split_per_sample
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
         raise ValueError(f"shape[0] = {shape[0]} frames do not divide into batch={batch} samples")
@@ -519,19 +467,20 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     first = edit_first_step(num_steps, strength) if init_latent is not None else 0
     steps_run = num_steps - first
     guide_kw = (guidance_schedule, guidance_interval, cfg_zero_star, cfg_zero_init, cfg_rescale)
-    guide = None
-    if any(v is not None for v in guide_kw[:2]) or any(guide_kw[2:]):   # the schedule as `_generate_one` draws it: the same bits
-        guide = _guidance_for_run(model, sigma_schedule(num_steps, scheduler_scale, device=device).cpu().tolist(), first, guidance_weight,
-                                  *guide_kw, init_latent, plan is not None and len(plan[1]) > 1)
-    skip = None
-    if slg_blocks is not None or slg_scale or slg_interval is not None:
-        skip = _skip_for_run(model, sigma_schedule(num_steps, scheduler_scale, device=device).cpu().tolist(), first, slg_blocks, slg_scale,
-                             slg_interval, slg_mode, plan is not None and len(plan[1]) > 1)
-        from .models.dit import DiffusionTransformer3D
+    guide = skip = None
+    windowed = plan is not None and len(plan[1]) > 1
+    wants_guide = any(v is not None for v in guide_kw[:2]) or any(guide_kw[2:])
+    wants_skip = slg_blocks is not None or slg_scale or slg_interval is not None
+    if wants_guide or wants_skip:   # the schedule as `_generate_one` draws it: the same bits
+        sigmas = sigma_schedule(num_steps, scheduler_scale, device=device).cpu().tolist()
+    if wants_guide:
+        guide = _guidance_for_run(model, sigmas, first, guidance_weight, *guide_kw, init_latent, windowed)
+    if wants_skip:
+        skip = _skip_for_run(model, sigmas, first, slg_blocks, slg_scale, slg_interval, slg_mode, windowed)
         if skip is not None and not (type(model) is DiffusionTransformer3D or hasattr(model, "forward_skip")):
             raise ValueError("slg_blocks needs a model with forward_skip (the engine-backed DiffusionTransformer3D has it): the skip branch runs "
                              "inside its forward, a wrapped callable without one cannot take it")
-    if region_text_embeds is not None and plan is not None and len(plan[1]) > 1:
+    if region_text_embeds is not None and windowed:
         raise ValueError("region_text_embeds together with context windows is not supported: the masks cover the clip, a window sees a slice")
     with _skip_for_call(model, skip), _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
             _regions_for_call(model, region_text_embeds, region_text_rope_pos, region_masks, region_base_weight):
@@ -582,12 +531,11 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     if edit is not None:
         timesteps = timesteps[edit_first_step(num_steps, strength):]   # strength is a truncation of the schedule, nothing more
 
-    from .models.dit import DiffusionTransformer3D
     if isinstance(model, torch.nn.Module):      # per-step paths below: a new sampling run starts with no softmax-form memory (k5_sample resets its own)
         for m in model.modules():
             if isinstance(m, DiffusionTransformer3D):
                 m.reset_softmax_memory()
-    cfg_on = abs(guidance_weight - 1.0) > 1e-6
+    cfg_on = _is_guided(guidance_weight)
     g_weights, g_zero_star, g_zero_init, g_rescale = guide if guide is not None else (None, False, 0, 0.0)
     if g_weights is not None:   # some step is guided: the pair exchanges, the buffers of the unconditional side exist
         cfg_on = any(_is_guided(w) for w in g_weights)
@@ -599,7 +547,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     exchange = cfg_parallel is not None and cfg_on and getattr(model, "_cfg_pair", None) is None
     if not exchange and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False):
         # whole loop inside the engine: no per-step host work at all
-        with watch.installed(model), _guidance_for_call(model, guide):
+        with model.setting_for_call("watch", watch.watch_args()), model.setting_for_call("guidance", guide):
             model.sample(img, timesteps.tolist(), text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                          null_text_rope_pos, guidance_weight, scale_factor=conf.metrics.scale_factor,
                          sparse_params=sparse_params,
@@ -654,7 +602,6 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     else:
         velocities = plain_velocities
 
-    from .models.dit import SamplingInterrupted, StepInfo
     n = len(timesteps) - 1
     if edit is not None:
         E.renoise(edit[0], edit[1], float(timesteps[0]), out=img)
@@ -707,7 +654,6 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
                     guidance_weight, scheduler_scale, conf, watch, batch, context, visual_cond, visual_cond_mask, init_latent, strength,
                     keep_mask, guide=None, skip=None):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
-    from .models.dit import split_per_sample
     T = img.shape[0] // batch
     tes, nes = split_per_sample(text_embeds, batch, "text_embeds"), split_per_sample(null_text_embeds, batch, "null_text_embeds")
     tps = split_per_sample(text_rope_pos, batch, "text_rope_pos")
@@ -716,7 +662,6 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         if v is not None and v.shape[0] != img.shape[0]:
             raise ValueError(f"{n} must have {img.shape[0]} frames (batch={batch} x {T}), got {v.shape[0]}")
 
-    from .models.dit import DiffusionTransformer3D
     if init_latent is None and context[0] is None and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) \
             and model.many_ready() and getattr(model, "_cfg_parallel", None) is None:
         cond = _conditioning(model, img, visual_cond, visual_cond_mask)
@@ -724,7 +669,7 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
             cond = torch.cat(cond, dim=-1).reshape(batch, T, *img.shape[1:-1], img.shape[-1] + 1).contiguous()
         sparse_params = get_sparse_params(conf, {"visual": img[:T]}, device)
         timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()
-        with watch.installed(model), _guidance_for_call(model, guide):
+        with model.setting_for_call("watch", watch.watch_args()), model.setting_for_call("guidance", guide):
             model.sample_many(img.view(batch, T, *img.shape[1:]), timesteps.tolist(), tes, nes, visual_rope_pos, tps, nps,
                                guidance_weight, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params, visual_cond=cond)
         return img
@@ -816,7 +761,6 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     guide_kw = {k: v for k, v in dict(guidance_schedule=guidance_schedule, guidance_interval=guidance_interval, cfg_zero_star=cfg_zero_star,
                                       cfg_zero_init=cfg_zero_init, cfg_rescale=cfg_rescale).items() if v}
     if guide_kw:   # before any model runs: the numbers (what depends on the schedule is checked by `generate`)
-        from .models.dit import check_guidance_args
         check_guidance_args(None if guidance_schedule is None or callable(guidance_schedule) else guidance_schedule, cfg_zero_star,
                             cfg_zero_init, cfg_rescale)
         if guidance_interval is not None:
@@ -835,7 +779,6 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         raise ValueError("context_overlap needs context_frames")
     region_kw, region_prompts = {}, []
     if region_text_embeds is not None:   # before any model runs
-        from .models.dit import DiffusionTransformer3D, check_region_args
         if isinstance(region_text_embeds, (list, tuple)) and region_text_embeds and all(isinstance(p, str) for p in region_text_embeds):
             if region_text_rope_pos is not None:
                 raise ValueError("regions: prompts given as strings take positions 0 .. n-1, region_text_rope_pos must be None")
@@ -853,7 +796,6 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         region_kw = dict(region_text_embeds=region_text_embeds, region_text_rope_pos=region_text_rope_pos, region_masks=region_masks,
                          region_base_weight=region_base_weight)
     if nag_scale is not None:   # before any model runs
-        from .models.dit import DiffusionTransformer3D, check_nag_numbers
         check_nag_numbers(nag_scale, nag_tau, nag_alpha)
         if type(dit) is not DiffusionTransformer3D:
             raise ValueError("nag_scale needs the engine-backed DiffusionTransformer3D (see `generate`)")

@@ -8,6 +8,7 @@ the library, or with CPU tensors, `forward` raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 
@@ -103,7 +104,6 @@ class _DeviceView:
 
 def check_nag_numbers(scale, tau, alpha):
     """The ValueErrors of the three numbers of normalized attention guidance; returns them as floats."""
-    import math
     try:
         scale, tau, alpha = float(scale), float(tau), float(alpha)
     except (TypeError, ValueError):
@@ -186,7 +186,6 @@ def check_nag_args(text_embeds, text_rope_pos, scale, tau, alpha):
 def check_region_args(text_embeds_list, rope_pos_list, masks, base_weight):
     """The ValueErrors of `set_regions` / `generate(region_text_embeds=, region_text_rope_pos=, region_masks=, region_base_weight=)`; returns
     base_weight as a float."""
-    import math
     try:
         base_weight = float(base_weight)
     except (TypeError, ValueError):
@@ -236,6 +235,27 @@ def check_watch_args(callback, preview_every, rgb_factors, want_x0, channels):
         if channels % 4 or channels > 64:
             raise ValueError(f"previews need a latent of C % 4 == 0 and C <= 64 channels, got {channels}")
     return W, preview_every
+
+
+def _is_guided(w):
+    return abs(w - 1.0) > 1e-6   # the engine's rule (reference generation_utils.py:63)
+
+
+def _needs_uncond(guidance_weight, plan):
+    """Whether a sampling call reads the unconditional prompt: its own weight guides, or a weight of the guidance plan `plan` (`_guidance`) does."""
+    return _is_guided(guidance_weight) or (plan is not None and plan[0] is not None and any(_is_guided(w) for w in plan[0]))
+
+
+# The values the model keeps and pushes into the engine handle, in the order they are re-installed after a rebuild:
+# name -> (attribute of the stored value, library setter, the setter's clearing arguments); `_marshal_<name>` turns the stored value into the
+# setter's arguments and `set_<name>` is the public method that validates and stores one
+_SETTINGS = {
+    "watch":         ("_watch",    "k5_dit_set_watch",         (None,)),
+    "nag":           ("_nag",      "k5_dit_set_nag",           (None, 1.0, 1.0, 0.0)),
+    "regions":       ("_regions",  "k5_dit_set_regions",       (None, 0, None, 0, 0, 0, 0.0)),
+    "guidance":      ("_guidance", "k5_dit_set_guidance",      (None,)),
+    "skip_guidance": ("_skip",     "k5_dit_set_skip_guidance", (None,)),
+}
 
 
 class DiffusionTransformer3D(nn.Module):
@@ -288,10 +308,11 @@ class DiffusionTransformer3D(nn.Module):
         self._lora = []              # (entries, strength) merged into the ENGINE's packed weights: re-added when the engine is rebuilt
         self._lora_saved = {}        # parameters as they were before a merge done in torch (no engine yet): key -> tensor
         self._watch = None           # (trampoline, k5_watch and the arrays it points to) of set_watch: re-installed when the engine is rebuilt
-        self._nag = None             # the negative prompt of set_nag, its k5_text_cond and what that points to: re-installed likewise
-        self._regions = None         # the prompts and masks of set_regions, their k5_text_cond array and what it points to: likewise
+        self._nag = None             # the negative prompt of set_nag and its three numbers: re-installed likewise
+        self._regions = None         # the prompts, masks and base weight of set_regions: likewise
         self._skip = None            # the set of set_skip_guidance (blocks, scale, mode, steps | None): likewise
         self._guidance = None        # the plan of set_guidance (weights list | None, zero_star, zero_init_steps, rescale): likewise
+        self._borrowed = {}          # setting name -> what the live handle borrows from the stored value (structs, device copies, ctypes arrays)
 
     # ---------------------------------------------------------------- engine lifetime
     def _destroy_engine(self, force=False):
@@ -302,6 +323,7 @@ class DiffusionTransformer3D(nn.Module):
                                    "weights or moving it to another device would desynchronise the ranks")
             E.lib().k5_dit_destroy(self._handle)
         self._handle, self._handle_device, self._sp, self._cfg_pair = None, None, None, None
+        self._borrowed = {}          # nothing reads them any more
 
     def __del__(self):
         try:
@@ -358,16 +380,9 @@ class DiffusionTransformer3D(nn.Module):
                 E.check(E.lib().k5_dit_set_option(self._handle, k.encode(), int(v)), f"k5_dit_set_option({k})")
         for entries, strength in getattr(self, "_lora", []):   # the rebuilt engine packed the parameters, which an engine-side merge never touched
             self._engine_add_lora(entries, strength)
-        if getattr(self, "_watch", None) is not None:
-            self._install_watch()
-        if getattr(self, "_nag", None) is not None:
-            self._install_nag()
-        if getattr(self, "_regions", None) is not None:
-            self._install_regions()
-        if getattr(self, "_guidance", None) is not None:
-            self._install_guidance()
-        if getattr(self, "_skip", None) is not None:
-            self._install_skip()
+        for name, (attr, _, _) in _SETTINGS.items():
+            if getattr(self, attr, None) is not None:
+                self._put(name, getattr(self, attr))
         if getattr(self, "mag_ratios", None) is not None or getattr(self, "_magcache_calibrate", None) is not None:   # set before the weights were loaded / the handle rebuilt
             from ..magcache_utils import _apply
             _apply(self)
@@ -465,21 +480,31 @@ class DiffusionTransformer3D(nn.Module):
     def forward(self, x, text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos,
                 scale_factor=(1.0, 1.0, 1.0), sparse_params=None):
         """Reference signature dit.py:155-165.  x (T,H,W,C_in) ; returns velocity (T,H,W,out_visual_dim) bf16."""
+        a, out, keep = self._forward_prologue("forward", x, (), text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos, scale_factor,
+                                              sparse_params)
+        return self._call("k5_dit_forward", out, C.byref(a), out.data_ptr())
+
+    def _forward_prologue(self, who, x, lead, text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos, scale_factor, sparse_params):
+        """What `forward`, `forward_skip` and `forward_many` share for x (..., T, H, W, C_in): the CUDA check, the engine, and (the
+        k5_forward_args of x as contiguous fp32 with the prompt moved to its device, the bf16 output `lead` + (T, H, W, out_visual_dim), what
+        must stay alive until the call has been made)."""
         if not x.is_cuda:
-            raise RuntimeError("DiffusionTransformer3D.forward needs CUDA (HIP) tensors; there is no CPU fallback")
-        h = self.engine(x.device)
+            raise RuntimeError(f"DiffusionTransformer3D.{who} needs CUDA (HIP) tensors; there is no CPU fallback")
+        self.engine(x.device)
         x = x.float().contiguous()
-        T, H, W, Cx = x.shape
+        T, H, W, Cx = x.shape[-4:]
         self._last_tokens = T * (H // self.patch_size[1]) * (W // self.patch_size[2])   # rows of a residual (magcache_calibration)
-        text_embed, pooled_text_embed = text_embed.to(x.device), pooled_text_embed.to(x.device)
         t_val = float(time.reshape(-1)[0]) if torch.is_tensor(time) else float(time)
         keep = [x]
-        a = self._forward_args((T, H, W), x.data_ptr(), Cx, text_embed, pooled_text_embed, t_val, visual_rope_pos,
+        a = self._forward_args((T, H, W), x.data_ptr(), Cx, text_embed.to(x.device), pooled_text_embed.to(x.device), t_val, visual_rope_pos,
                                text_rope_pos, scale_factor, sparse_params, keep)
-        out = torch.empty(T, H, W, self.out_visual_dim, dtype=torch.bfloat16, device=x.device)
-        with torch.cuda.device(x.device):
-            E.check(E.lib().k5_dit_forward(h, C.byref(a), out.data_ptr(), E.stream_ptr(x.device)), "k5_dit_forward")
-        return out
+        return a, torch.empty(*lead, T, H, W, self.out_visual_dim, dtype=torch.bfloat16, device=x.device), keep
+
+    def _call(self, name, on, *args):
+        """The library call `name`(handle, *args, stream) on the device and stream of the tensor `on`, which it returns."""
+        with torch.cuda.device(on.device):
+            E.check(getattr(E.lib(), name)(self._handle, *args, E.stream_ptr(on.device)), name)
+        return on
 
     @torch.no_grad()
     def sample(self, latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
@@ -530,8 +555,7 @@ class DiffusionTransformer3D(nn.Module):
         keep = []
         s.fwd = self._forward_args((frames, H, W), None, self.in_visual_dim, text_embeds["text_embeds"].to(dev), text_embeds["pooled_embed"].to(dev),
                                    0.0, visual_rope_pos, text_rope_pos, scale_factor, sparse_params, keep)
-        plan = getattr(self, "_guidance", None)
-        if abs(guidance_weight - 1.0) > 1e-6 or (plan is not None and plan[0] is not None and any(abs(w - 1.0) > 1e-6 for w in plan[0])):
+        if _needs_uncond(guidance_weight, getattr(self, "_guidance", None)):
             s.null_cond = self._text_cond(null_text_embeds["text_embeds"].to(dev), null_text_embeds["pooled_embed"].to(dev),
                                           null_text_rope_pos, keep)
         sig = [float(v) for v in sigmas]
@@ -542,10 +566,8 @@ class DiffusionTransformer3D(nn.Module):
 
     def _run_sampler(self, name, latent, *args):
         """The k5_sample* call `name` on the latent's device and stream, between the watch's begin and end."""
-        dev = latent.device
         self._watch_begin()
-        with torch.cuda.device(dev):
-            E.check(getattr(E.lib(), name)(self._handle, *args, E.stream_ptr(dev)), name)
+        self._call(name, latent, *args)
         self._watch_end(latent)
         return latent
 
@@ -577,6 +599,52 @@ class DiffusionTransformer3D(nn.Module):
         a.total_T, a.nwin, a.starts, a.weights = latent.shape[0], nwin, st, wt
         return self._run_sampler("k5_sample_windows", latent, C.byref(a), E.ptr(visual_cond))
 
+    # ---------------------------------------------------------------- settings on the handle (_SETTINGS): put, clear, state, for one call
+    def _put(self, name, value):
+        """Store `value` as setting `name`, installed on the handle if there is one.  A refused install raises and changes nothing: the engine
+        setters check before they write, so the handle, the stored value and what the handle borrows stay those of the previous setting."""
+        attr, fn, _ = _SETTINGS[name]
+        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
+            args, keep = getattr(self, "_marshal_" + name)(value)
+            with torch.cuda.device(self._handle_device):
+                E.check(getattr(E.lib(), fn)(self._handle, *args), fn)
+            self._borrowed[name] = (args, keep)     # only now may the previous setting's go
+        setattr(self, attr, value)
+        return self
+
+    def _clear(self, name):
+        attr, fn, clear_args = _SETTINGS[name]
+        setattr(self, attr, None)
+        if self._handle is not None:
+            E.check(getattr(E.lib(), fn)(self._handle, *clear_args), fn)
+            self._borrowed.pop(name, None)
+        return self
+
+    def _state(self, fn, types, *tail):
+        """The out-parameters of the state getter `fn` (ctypes `types`, followed by the arguments `tail`) as values; zeros without a handle."""
+        out = [t(0) for t in types]
+        if self._handle is not None:
+            E.check(getattr(E.lib(), fn)(self._handle, *[C.byref(o) for o in out], *tail), fn)
+        return [o.value for o in out]
+
+    @contextlib.contextmanager
+    def setting_for_call(self, name, args):
+        """Context: setting `name` ("watch", "nag", "regions", "guidance", "skip_guidance") as `set_<name>(*args)` makes it, for one call; what was
+        stored before is installed again afterwards (the stored object itself, not a copy) or the setting is cleared, also on an exception.
+        args None: nothing is touched."""
+        if args is None:
+            yield
+            return
+        before = getattr(self, _SETTINGS[name][0])
+        try:
+            getattr(self, "set_" + name)(*args)
+            yield
+        finally:
+            if before is not None:
+                self._put(name, before)
+            else:
+                getattr(self, "clear_" + name)()
+
     # ---------------------------------------------------------------- watch: progress, cancel, previews
     def set_watch(self, callback=None, preview_every=0, rgb_factors=None, rgb_bias=None, want_x0=False):
         """Progress, cancel and live previews out of `sample` / `sample_many` (k5_dit_set_watch).  `callback(info)` runs after every step on
@@ -607,32 +675,19 @@ class DiffusionTransformer3D(nn.Module):
                 ba = (C.c_float * 3)(*b)
                 keep.append(ba)
                 w.rgb_b = C.cast(ba, C.POINTER(C.c_float))
-        self._watch = (tr, w, keep)
-        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
-            try:
-                self._install_watch()
-            except Exception:
-                self._watch = None
-                raise
-        return self
+        return self._put("watch", (tr, w, keep))
 
-    def _install_watch(self):
-        with torch.cuda.device(self._handle_device):
-            E.check(E.lib().k5_dit_set_watch(self._handle, C.byref(self._watch[1])), "k5_dit_set_watch")
+    def _marshal_watch(self, watch):
+        return (C.byref(watch[1]),), None    # the stored value holds the struct and its arrays itself
 
     def clear_watch(self):
         """Remove the watch: `sample` enqueues exactly what it did before `set_watch`."""
-        self._watch = None
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_set_watch(self._handle, None), "k5_dit_set_watch")
-        return self
+        return self._clear("watch")
 
     def watch_state(self):
         """(steps_done, stopped) of the last `sample` / `sample_many` call (k5_dit_watch_state)."""
-        n, st = C.c_int(0), C.c_int(0)
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_watch_state(self._handle, C.byref(n), C.byref(st)), "k5_dit_watch_state")
-        return n.value, bool(st.value)
+        n, st = self._state("k5_dit_watch_state", (C.c_int, C.c_int))
+        return n, bool(st)
 
     # ---------------------------------------------------------------- normalized attention guidance: a negative prompt without CFG
     def set_nag(self, text_embeds, text_rope_pos, scale=5.0, tau=2.5, alpha=0.25):
@@ -647,41 +702,25 @@ class DiffusionTransformer3D(nn.Module):
         scale, tau, alpha = check_nag_args(text_embeds, text_rope_pos, scale, tau, alpha)
         if text_embeds["text_embeds"].shape[1] != self._cfg["in_text_dim"]:
             raise ValueError(f"nag: text_embeds has {text_embeds['text_embeds'].shape[1]} features, the model takes {self._cfg['in_text_dim']}")
-        self._nag = {"text": text_embeds["text_embeds"], "pooled": text_embeds.get("pooled_embed"), "pos": text_rope_pos,
-                     "args": (scale, tau, alpha), "cond": None, "keep": None}
-        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
-            try:
-                self._install_nag()
-            except Exception:
-                self._nag = None
-                raise
-        return self
+        return self._put("nag", {"text": text_embeds["text_embeds"], "pooled": text_embeds.get("pooled_embed"), "pos": text_rope_pos,
+                                 "args": (scale, tau, alpha)})
 
-    def _install_nag(self):
-        n = self._nag
-        dev = self._handle_device
-        te = n["text"].to(dev)
-        pe = n["pooled"].to(dev) if n["pooled"] is not None else te.new_zeros(1, self._cfg["in_text_dim2"])
+    def _marshal_nag(self, n):
+        te = n["text"].to(self._handle_device)
+        pe = n["pooled"].to(self._handle_device) if n["pooled"] is not None else te.new_zeros(1, self._cfg["in_text_dim2"])
         keep = []
         cond = self._text_cond(te, pe, n["pos"], keep)
-        n["cond"], n["keep"] = cond, keep    # the engine borrows the struct and what it points to
-        with torch.cuda.device(dev):
-            E.check(E.lib().k5_dit_set_nag(self._handle, C.byref(cond), *n["args"]), "k5_dit_set_nag")
+        return (C.byref(cond), *n["args"]), keep     # the engine borrows the struct and what it points to
 
     def clear_nag(self):
         """Remove the guidance: a forward enqueues exactly what it did before `set_nag`."""
-        self._nag = None
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_set_nag(self._handle, None, 1.0, 1.0, 0.0), "k5_dit_set_nag")
-        return self
+        return self._clear("nag")
 
     def nag_state(self, reset=False):
         """(on, combines): whether guidance is on, and how many combine launches the engine has enqueued — num_visual_blocks per guided
         forward (k5_dit_nag_state).  `reset` zeroes the count afterwards."""
-        on, n = C.c_int(0), C.c_longlong(0)
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_nag_state(self._handle, C.byref(on), C.byref(n), int(bool(reset))), "k5_dit_nag_state")
-        return bool(on.value), n.value
+        on, n = self._state("k5_dit_nag_state", (C.c_int, C.c_longlong), int(bool(reset)))
+        return bool(on), n
 
     # ---------------------------------------------------------------- guidance plan: per-step weights, CFG-Zero*, CFG rescale
     def set_guidance(self, weights=None, zero_star=False, zero_init_steps=0, rescale=0.0):
@@ -693,41 +732,27 @@ class DiffusionTransformer3D(nn.Module):
         runs: a `weights` list of another length than its steps; a plan with guided and unguided steps, or with zero-init, on a CFG pair or
         with MagCache or its calibration; zero-init with `edit`; any plan with `windows`; zero_star / rescale when every weight is 1.
         No checkpoint was at hand when this was built: the rules are the published ones, their effect on quality is not measured here."""
-        weights, zero_star, zero_init_steps, rescale = check_guidance_args(weights, zero_star, zero_init_steps, rescale)
-        self._guidance = (weights, zero_star, zero_init_steps, rescale)
-        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
-            try:
-                self._install_guidance()
-            except Exception:
-                self._guidance = None
-                raise
-        return self
+        return self._put("guidance", check_guidance_args(weights, zero_star, zero_init_steps, rescale))
 
-    def _install_guidance(self):
-        weights, zero_star, zero_init_steps, rescale = self._guidance
+    def _marshal_guidance(self, plan):
+        weights, zero_star, zero_init_steps, rescale = plan
         g = E.Guidance()
         arr = None
         if weights is not None:
             arr = (C.c_float * len(weights))(*weights)    # copied by the call
             g.weights, g.num_weights = C.cast(arr, C.POINTER(C.c_float)), len(weights)
         g.zero_star, g.zero_init_steps, g.rescale = int(zero_star), int(zero_init_steps), float(rescale)
-        E.check(E.lib().k5_dit_set_guidance(self._handle, C.byref(g)), "k5_dit_set_guidance")
+        return (C.byref(g),), arr
 
     def clear_guidance(self):
         """Remove the plan: `sample` enqueues exactly what it did before `set_guidance`."""
-        self._guidance = None
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_set_guidance(self._handle, None), "k5_dit_set_guidance")
-        return self
+        return self._clear("guidance")
 
     def guidance_state(self, reset=False):
         """(on, guided, unguided, zero): whether a plan is set, and how many steps of each kind the engine has enqueued under one
         (k5_dit_guidance_state).  `reset` zeroes the counts afterwards."""
-        on, a, b, z = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_guidance_state(self._handle, C.byref(on), C.byref(a), C.byref(b), C.byref(z), int(bool(reset))),
-                    "k5_dit_guidance_state")
-        return bool(on.value), a.value, b.value, z.value
+        on, *counts = self._state("k5_dit_guidance_state", (C.c_int,) + (C.c_longlong,) * 3, int(bool(reset)))
+        return (bool(on), *counts)
 
     # ---------------------------------------------------------------- skip-layer guidance: a third, block-skipping forward
     def set_skip_guidance(self, blocks, scale, mode="block", steps=None):
@@ -737,17 +762,10 @@ class DiffusionTransformer3D(nn.Module):
         calls to come (`generation_utils.skip_plan` builds it; None = every step).  scale == 0 is accepted and means off.  `sample` refuses,
         before anything runs: a `steps` list of another length than its steps, a CFG pair, MagCache or its calibration, and `windows`.
         No checkpoint was at hand when this was built: the rule is the published one, its effect on quality is not measured here."""
-        self._skip = check_skip_args(blocks, scale, mode, steps, self.num_visual_blocks)
-        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
-            try:
-                self._install_skip()
-            except Exception:
-                self._skip = None
-                raise
-        return self
+        return self._put("skip_guidance", check_skip_args(blocks, scale, mode, steps, self.num_visual_blocks))
 
-    def _install_skip(self):
-        blocks, scale, mode, steps = self._skip
+    def _marshal_skip_guidance(self, skip):
+        blocks, scale, mode, steps = skip
         g = E.SkipGuidance()
         barr = (C.c_int * len(blocks))(*blocks)           # both copied by the call
         g.blocks, g.num_blocks = C.cast(barr, C.POINTER(C.c_int)), len(blocks)
@@ -756,22 +774,17 @@ class DiffusionTransformer3D(nn.Module):
         if steps is not None:
             sarr = (C.c_ubyte * len(steps))(*steps)
             g.steps, g.num_steps = C.cast(sarr, C.POINTER(C.c_ubyte)), len(steps)
-        E.check(E.lib().k5_dit_set_skip_guidance(self._handle, C.byref(g)), "k5_dit_set_skip_guidance")
+        return (C.byref(g),), (barr, sarr)
 
     def clear_skip_guidance(self):
         """Remove the skip set: `sample` enqueues exactly what it did before `set_skip_guidance`."""
-        self._skip = None
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_set_skip_guidance(self._handle, None), "k5_dit_set_skip_guidance")
-        return self
+        return self._clear("skip_guidance")
 
     def skip_state(self, reset=False):
         """(on, skip_steps, blocks_shared, blocks_run): whether skip guidance is on, how many skip steps the engine has enqueued, and how many
         visual blocks the skip branches took from the conditional forward / ran themselves (k5_dit_skip_state).  `reset` zeroes the counts."""
-        on, a, b, r = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_skip_state(self._handle, C.byref(on), C.byref(a), C.byref(b), C.byref(r), int(bool(reset))), "k5_dit_skip_state")
-        return bool(on.value), a.value, b.value, r.value
+        on, *counts = self._state("k5_dit_skip_state", (C.c_int,) + (C.c_longlong,) * 3, int(bool(reset)))
+        return (bool(on), *counts)
 
     @torch.no_grad()
     def forward_skip(self, x, text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos,
@@ -779,19 +792,9 @@ class DiffusionTransformer3D(nn.Module):
         """`forward` with the skip branch of `set_skip_guidance` (k5_dit_forward_skip): returns (v_cond, v_skip), v_cond being `forward`'s bits."""
         if getattr(self, "_skip", None) is None:
             raise ValueError("forward_skip: no skip set (set_skip_guidance)")
-        if not x.is_cuda:
-            raise RuntimeError("DiffusionTransformer3D.forward_skip needs CUDA (HIP) tensors; there is no CPU fallback")
-        h = self.engine(x.device)
-        x = x.float().contiguous()
-        T, H, W, Cx = x.shape
-        text_embed, pooled_text_embed = text_embed.to(x.device), pooled_text_embed.to(x.device)
-        t_val = float(time.reshape(-1)[0]) if torch.is_tensor(time) else float(time)
-        keep = [x]
-        a = self._forward_args((T, H, W), x.data_ptr(), Cx, text_embed, pooled_text_embed, t_val, visual_rope_pos,
-                               text_rope_pos, scale_factor, sparse_params, keep)
-        out = torch.empty(2, T, H, W, self.out_visual_dim, dtype=torch.bfloat16, device=x.device)
-        with torch.cuda.device(x.device):
-            E.check(E.lib().k5_dit_forward_skip(h, C.byref(a), out[0].data_ptr(), out[1].data_ptr(), E.stream_ptr(x.device)), "k5_dit_forward_skip")
+        a, out, keep = self._forward_prologue("forward_skip", x, (2,), text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos,
+                                              scale_factor, sparse_params)
+        self._call("k5_dit_forward_skip", out, C.byref(a), out[0].data_ptr(), out[1].data_ptr())
         return out[0], out[1]
 
     # ---------------------------------------------------------------- regional prompts: a prompt per masked region in one forward
@@ -812,18 +815,10 @@ class DiffusionTransformer3D(nn.Module):
         pt, ph, pw = self.patch_size
         if masks.shape[1] % pt or masks.shape[2] % ph or masks.shape[3] % pw:
             raise ValueError(f"regions: the masks' shape {tuple(masks.shape[1:])} is not divisible by the patch {(pt, ph, pw)}")
-        self._regions = {"text": [te["text_embeds"] for te in text_embeds_list], "pos": list(rope_pos_list), "masks": masks,
-                         "base_weight": base_weight, "conds": None, "keep": None}
-        if self._handle is not None:     # no engine yet: installed when it is built (_reapply_settings)
-            try:
-                self._install_regions()
-            except Exception:
-                self._regions = None
-                raise
-        return self
+        return self._put("regions", {"text": [te["text_embeds"] for te in text_embeds_list], "pos": list(rope_pos_list), "masks": masks,
+                                     "base_weight": base_weight})
 
-    def _install_regions(self):
-        g = self._regions
+    def _marshal_regions(self, g):
         dev = self._handle_device
         keep = []
         R = len(g["text"])
@@ -833,24 +828,17 @@ class DiffusionTransformer3D(nn.Module):
             conds[r] = self._text_cond(te, te.new_zeros(1, self._cfg["in_text_dim2"]), g["pos"][r], keep)
         masks = g["masks"].to(device=dev, dtype=torch.float32).contiguous()
         keep.append(masks)
-        g["conds"], g["keep"] = conds, keep    # the engine borrows the array and what it points to
-        with torch.cuda.device(dev):
-            E.check(E.lib().k5_dit_set_regions(self._handle, conds, R, E.ptr(masks), *masks.shape[1:], g["base_weight"]), "k5_dit_set_regions")
+        return (conds, R, E.ptr(masks), *masks.shape[1:], g["base_weight"]), keep    # the engine borrows the array and what it points to
 
     def clear_regions(self):
         """Remove the regions: a forward enqueues exactly what it did before `set_regions`."""
-        self._regions = None
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_set_regions(self._handle, None, 0, None, 0, 0, 0, 0.0), "k5_dit_set_regions")
-        return self
+        return self._clear("regions")
 
     def regions_state(self, reset=False):
         """(on, R, combines): whether regions are on, how many, and how many combine launches the engine has enqueued — num_visual_blocks per
         regional forward (k5_dit_regions_state).  `reset` zeroes the count afterwards."""
-        on, R, n = C.c_int(0), C.c_int(0), C.c_longlong(0)
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_regions_state(self._handle, C.byref(on), C.byref(R), C.byref(n), int(bool(reset))), "k5_dit_regions_state")
-        return bool(on.value), R.value, n.value
+        on, R, n = self._state("k5_dit_regions_state", (C.c_int, C.c_int, C.c_longlong), int(bool(reset)))
+        return bool(on), R, n
 
     def _step_info(self, info):
         shape = (info.T, info.H, info.W)
@@ -937,11 +925,10 @@ class DiffusionTransformer3D(nn.Module):
             raise ValueError("latents must hold at least one sample")
         self._check_visual_cond(visual_cond, latents)
 
-        plan = getattr(self, "_guidance", None)   # a plan's weights may guide where the call's guidance_weight is 1
-        cfg_on = abs(guidance_weight - 1.0) > 1e-6 or (plan is not None and plan[0] is not None and any(abs(w - 1.0) > 1e-6 for w in plan[0]))
+        cfg_on = _needs_uncond(guidance_weight, getattr(self, "_guidance", None))   # a plan's weights may guide where the call's weight is 1
         tes, tps = split_per_sample(text_embeds, B, "text_embeds"), split_per_sample(text_rope_pos, B, "text_rope_pos")
-        h = self.engine(latents.device)
         dev = latents.device
+        self.engine(dev)
         keep = []
         conds = (E.TextCond * B)()
         nulls = (E.TextCond * B)() if cfg_on else None
@@ -960,11 +947,7 @@ class DiffusionTransformer3D(nn.Module):
         arr = (C.c_float * len(sig))(*sig)
         s.latents, s.visual_cond = latents.data_ptr(), E.ptr(visual_cond)
         s.num_steps, s.sigmas, s.guidance_weight = len(sig) - 1, arr, float(guidance_weight)
-        self._watch_begin()
-        with torch.cuda.device(dev):
-            E.check(E.lib().k5_sample_many(h, C.byref(s), E.stream_ptr(dev)), "k5_sample_many")
-        self._watch_end(latents)
-        return latents
+        return self._run_sampler("k5_sample_many", latents, C.byref(s))
 
     @torch.no_grad()
     def forward_many(self, x, text_embeds, time, visual_rope_pos, text_rope_pos, scale_factor=(1.0, 1.0, 1.0),
@@ -972,27 +955,16 @@ class DiffusionTransformer3D(nn.Module):
         """S forwards in one C call, one after another (k5_dit_forward_many): x (S,T,H,W,C_in), `text_embeds` / `text_rope_pos` lists
         of S.  Returns velocities (S,T,H,W,out_visual_dim) bf16; sequence i is bit-identical to `forward(x[i], ...)` on the model as it
         was when the call began, and the call leaves the softmax-form memory as it found it."""
-        if not x.is_cuda:
-            raise RuntimeError("DiffusionTransformer3D.forward_many needs CUDA (HIP) tensors; there is no CPU fallback")
-        x = x.float().contiguous()
-        S, T, H, W, Cx = x.shape
+        S = x.shape[0]
         if len(text_embeds) != S or len(text_rope_pos) != S:
             raise ValueError(f"text_embeds / text_rope_pos need {S} entries")
-        h = self.engine(x.device)
-        keep = [x]
+        a, out, keep = self._forward_prologue("forward_many", x, (S,), text_embeds[0]["text_embeds"], text_embeds[0]["pooled_embed"], time,
+                                              visual_rope_pos, text_rope_pos[0], scale_factor, sparse_params)
         conds = (E.TextCond * S)()
         for i in range(S):
             conds[i] = self._text_cond(text_embeds[i]["text_embeds"].to(x.device), text_embeds[i]["pooled_embed"].to(x.device),
                                        text_rope_pos[i], keep)
-        t_val = float(time.reshape(-1)[0]) if torch.is_tensor(time) else float(time)
-        a = self._forward_args((T, H, W), x.data_ptr(), Cx, text_embeds[0]["text_embeds"].to(x.device),
-                               text_embeds[0]["pooled_embed"].to(x.device), t_val, visual_rope_pos, text_rope_pos[0], scale_factor,
-                               sparse_params, keep)
-        out = torch.empty(S, T, H, W, self.out_visual_dim, dtype=torch.bfloat16, device=x.device)
-        with torch.cuda.device(x.device):
-            E.check(E.lib().k5_dit_forward_many(h, C.byref(a), S, conds, out.data_ptr(), E.stream_ptr(x.device)),
-                    "k5_dit_forward_many")
-        return out
+        return self._call("k5_dit_forward_many", out, C.byref(a), S, conds, out.data_ptr())
 
     # ---------------------------------------------------------------- multi-GPU
     def enable_sequence_parallel(self, rank, world, device=None, group=None, src=0, transport=None):
@@ -1225,12 +1197,10 @@ class DiffusionTransformer3D(nn.Module):
     def lora_state(self):
         """{"adapters": add_lora calls in effect, "matrices": weights with a saved copy, "backup_bytes": what those copies hold} —
         the engine's own count (k5_dit_lora_state) plus the parameters saved by a merge in torch."""
-        n, b = C.c_int(0), C.c_longlong(0)
-        if self._handle is not None:
-            E.check(E.lib().k5_dit_lora_state(self._handle, C.byref(n), C.byref(b)), "k5_dit_lora_state")
+        n, b = self._state("k5_dit_lora_state", (C.c_int, C.c_longlong))
         saved = self._lora_saved
-        return {"adapters": len(self._lora) + (1 if saved else 0), "matrices": n.value + len(saved),
-                "backup_bytes": b.value + sum(t.numel() * t.element_size() for t in saved.values())}
+        return {"adapters": len(self._lora) + (1 if saved else 0), "matrices": n + len(saved),
+                "backup_bytes": b + sum(t.numel() * t.element_size() for t in saved.values())}
 
     def set_graph(self, on=True):
         """sample() replays one hipGraph-captured step (k5_dit_set_graph); bit-identical results"""
