@@ -316,6 +316,30 @@ int k5_guided_euler(float* img, const void* v_cond, const void* v_uncond, const 
 int k5_skip_euler(float* img, const void* v_cond, const void* v_uncond /* nullable */, const void* v_skip, float w,
                   const float* ab /* nullable, device */, float g, float dt, const float* source, const float* noise, const float* keep_mask,
                   float sigma_next, int64_t cells, int C, void* v_out, void* stream);
+/* Counter-based noise and the stochastic update (added under ABI 11, as the exports above were).  The generator is
+ * Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds): key = (low, high word of seed),
+ * counter = (low, high word of the block index, c2, c3).  Nothing is read from memory and no generator state exists: two launches, two ranks,
+ * the two handles of a CFG pair and a replayed graph all form the same words from the same arguments.
+ * k5_philox_words: the raw words of blocks blk0 .. blk0 + nblk - 1 (the index wraps mod 2^64) into out [nblk][4] (device).
+ * k5_noise_normal_f32: out[g] = z[g & 3] of block g >> 2 with counter words (stream_id, 0): u_j = ((r_j >> 9) + 0.5) 2^-23 (exact, inside
+ * (0, 1)), (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from (u2, u3) likewise; fp32 throughout, no fast-math intrinsic.  Any n >= 1;
+ * nothing past out[n - 1] is written.  K5_ERR_ARG: a NULL out, nblk or n < 1. */
+int k5_philox_words(uint32_t* out /* [nblk][4] */, uint64_t blk0, int64_t nblk, uint64_t seed, uint32_t c2, uint32_t c3, void* stream);
+int k5_noise_normal_f32(float* out, int64_t n, uint64_t seed, uint32_t stream_id, void* stream);
+/* The stochastic flow-matching step (x_sigma = (1 - sigma) x0 + sigma eps; from s to t with churn eta: sigma_down = t (1 + (t / s - 1) eta),
+ * a = (1 - t) / (1 - sigma_down), c = s_noise sqrt(max(0, t^2 - (sigma_down a)^2)); kandinsky.generation_utils.stochastic_plan builds
+ * dt_down = sigma_down - s, scale = a and noise_coef = c per step).  Per element, nothing contracted:
+ *   v    as k5_skip_euler forms it (v_skip NULL: as k5_guided_euler with ab, else as k5_cfg_euler)
+ *   x1 = rn(img + bf16(rn(dt_down v)))
+ *   x2 = noise_coef != 0 ? rn(rn(scale x1) + rn(noise_coef z)) : x1,   z = noise ? noise[g] : k5_noise_normal_f32(seed, stream_id)[g]
+ *   img = the keep rule of k5_cfg_euler_edit on x2 at sigma_next (keep_mask NULL = none; eps is the edit's noise, not z).
+ * noise_coef == 0 gives the bits of the matching entry above.  The same kernel and launcher, one more instantiation: a thread owns the four
+ * elements of one generator block.  K5_ERR_ARG, nothing launched: what k5_skip_euler refuses (g == 0 goes with v_skip NULL), a scale or
+ * noise_coef that is not finite, noise_coef < 0. */
+int k5_stochastic_euler(float* img, const void* v_cond, const void* v_uncond /* nullable */, const void* v_skip /* nullable */, float w,
+                        const float* ab /* nullable, device */, float g, float dt_down, const float* source, const float* eps,
+                        const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, float scale, float noise_coef,
+                        const float* noise /* nullable, device fp32 [cells * C] */, uint64_t seed, uint32_t stream_id, void* stream);
 /* k5_cfg_euler over temporal context windows (added under ABI 11, as the exports above were): a clip of T frames whose velocities come from
  * nwin <= 64 windows of F frames.  img fp32 [T][frame_elems]; v_cond / v_uncond (NULL = no guidance) bf16 [nwin][F][frame_elems]; starts_dev
  * DEVICE int32 [nwin], window i covers frames starts[i] .. starts[i] + F - 1; weights_dev DEVICE fp32 [nwin][F], the share of window i's local
@@ -634,6 +658,28 @@ int k5_dit_skip_state(k5_dit* dit, int* on, long long* skip_steps, long long* bl
 /* k5_dit_forward with the skip branch: out_velocity is k5_dit_forward's bit for bit, out_velocity_skip (bf16, the same shape) the skip
  * branch's.  K5_ERR_STATE without a skip set on the handle (a set with scale 0 still forks here), with MagCache or its calibration. */
 int k5_dit_forward_skip(k5_dit* dit, const k5_forward_args* args, void* out_velocity, void* out_velocity_skip, void* stream);
+
+/* Stochastic sampling on the handle (added under ABI 11, as the exports above were; the rule is written at k5_stochastic_euler): while a plan is
+ * set, step i of k5_sample / k5_sample_cond / k5_sample_edit takes dt_down[i] as its dt and applies k5_stochastic_euler's kernel with scale[i],
+ * noise_coef[i] and stream id first_stream + i; the time the forwards see is unchanged.  The noise is generated inside the update kernel: no
+ * launch is added, a zero-init step of a guidance plan still does nothing, and the launch sequence does not depend on noise_coef, so the captured
+ * step replays (it reads the three values and the stream id at the device step counter).  Every rank of a sequence-parallel group and both
+ * handles of a CFG pair hold the same plan and so draw the same bits, with no exchange.  Works with editing (the keep rule comes last),
+ * k5_sample_cond, guidance plans, skip-layer guidance, NAG and regional prompts.
+ * Refused by k5_sample* before anything is enqueued, with a message: K5_ERR_ARG when num_steps differs from the call's; K5_ERR_STATE at
+ * k5_sample_windows with more than one window, at k5_sample_many, with MagCache or its calibration (the tables were measured on ODE
+ * trajectories), and with a watch that has previews (the preview reads x0 = x - sigma_next v, which no longer holds after the noise is added;
+ * a watch with preview_every = 0 — progress and cancel — works).
+ * k5_dit_set_stochastic: the three tables are HOST [num_steps] and are copied; K5_ERR_ARG for num_steps < 1, a NULL table, a value that is not
+ * finite, a noise_coef < 0; NULL clears.  k5_dit_stochastic_state: whether a plan is set and how many steps so far drew noise (noise_coef != 0,
+ * not a zero-init step); counted per step by the host loop, so it is right under graph replay. */
+typedef struct k5_stochastic {
+  int num_steps;
+  const float* dt_down; const float* scale; const float* noise_coef;   /* HOST [num_steps], copied */
+  uint64_t seed; uint32_t first_stream;
+} k5_stochastic;
+int k5_dit_set_stochastic(k5_dit* dit, const k5_stochastic* plan /* NULL clears */);
+int k5_dit_stochastic_state(k5_dit* dit, int* on, long long* noisy_steps, int reset);
 
 /* Regional prompts on the handle (added under ABI 11; the rule is written at k5_region_combine_bf16): a prompt per masked region inside the
  * cross-attention of ONE forward.  While set, every CONDITIONAL forward (as for k5_dit_set_nag: never the unconditional one) carries R more

@@ -517,6 +517,15 @@ struct k5_dit {
     bool at(int i) const { return live() && (steps.empty() || steps[i] != 0); }
   } skip;
 
+  // Stochastic sampling (k5_dit_set_stochastic): per-step dt_down / scale / noise_coef and the key of the in-kernel generator.
+  // sample_impl writes dt_down where the schedule's dt stands and hands the rest to the update kernel; no buffer, no state.
+  struct Stochastic {
+    bool on = false;
+    std::vector<float> dt_down, scale, coef;       // [num_steps] of the calls to come
+    uint64_t seed = 0; uint32_t first_stream = 0;
+    long long noisy_steps = 0;
+  } sto;
+
   // MagCache (reference kandinsky/magcache_utils.py:16-101): skip the visual blocks on some calls and re-apply the
   // cached bf16 residual of the same cond / uncond slot.  Decisions depend on the ratio table and the call counter only.
   struct MagCache {
@@ -2450,6 +2459,26 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
       return K5_ERR_STATE;
     }
   }
+  const k5_dit::Stochastic& so = d->sto;
+  if (so.on) {
+    if ((int)so.dt_down.size() != a->num_steps) {
+      k5_set_error("%s: the stochastic plan has %d steps, this call %d", who, (int)so.dt_down.size(), a->num_steps);
+      return K5_ERR_ARG;
+    }
+    if (win) {
+      k5_set_error("%s: a stochastic plan is set (k5_dit_set_stochastic): the windowed update blends one velocity pair per window and has no noise term", who);
+      return K5_ERR_STATE;
+    }
+    if (mag) {
+      k5_set_error("%s: a stochastic plan is set (k5_dit_set_stochastic) and %s on the handle: the ratio table was measured on ODE trajectories", who, mag);
+      return K5_ERR_STATE;
+    }
+    if (wt.on && wt.every > 0) {
+      k5_set_error("%s: a stochastic plan is set (k5_dit_set_stochastic) and the watch has previews (preview_every = %d): the preview reads "
+                   "x0 = x - sigma_next v, which no longer holds after the noise is added; install the watch with preview_every = 0", who, wt.every);
+      return K5_ERR_STATE;
+    }
+  }
   if (win) {
     if (edit) { k5_set_error("%s: editing with context windows is not supported", who); return K5_ERR_UNSUPPORTED; }
     if (rank_group(d)) { k5_set_error("%s: the handle is in a %s (context windows are single-rank only)", who, rank_group(d)); return K5_ERR_STATE; }
@@ -2509,6 +2538,10 @@ struct SampleRun {
   bool stats = false, want_v = false;       // stats: guided steps take their coefficients from the device; want_v: ... and leave v in vel_c (previews)
   const float* wvec = nullptr;              // graph mode: the per-step weights on the device, next to dtvec
   double* g_sums = nullptr; float* g_ab = nullptr; double* g_part = nullptr;
+  // the stochastic plan (k5_dit_set_stochastic; nullptr: none).  Its dt_down stands in `dt` / `dtvec`; graph mode: scale and noise_coef on the device
+  const k5_dit::Stochastic* sto = nullptr;
+  const float* scalevec = nullptr; const float* coefvec = nullptr;
+  bool noisy_at(int i) const { return sto && sto->coef[i] != 0.0f && kind(i) != ZERO; }
   enum Kind { GUIDED, UNGUIDED, ZERO };
   float w_at(int i) const { return plan && !plan->weights.empty() ? plan->weights[i] : a->guidance_weight; }
   Kind kind(int i) const {
@@ -2578,6 +2611,11 @@ struct SampleRun {
       if (coeffs) { e.ab = g_ab; e.v_out = want_v ? vel_c : nullptr; }
       if (skip) { e.v_skip = vel_s; e.skip_scale = d->skip.scale; e.v_out = want_v ? vel_c : nullptr; }   // the skip term comes after the coefficients
       if (edit) { e.source = edit->source; e.noise = edit->noise; e.keep_mask = edit->keep_mask; e.sigma_next = sigma_next[i]; e.signext = signext; }
+      if (sto) {   // the same launch whatever noise_coef is; the captured step adds the device step counter to the stream id itself
+        e.stochastic = true; e.scale = sto->scale[i]; e.noise_coef = sto->coef[i]; e.seed = sto->seed;
+        e.stream_id = sto->first_stream + (step_ctr ? 0u : (uint32_t)i);
+        e.scalevec = scalevec; e.coefvec = coefvec;
+      }
       e.cells = cells; e.C = c.out_visual_dim;
       e.dtvec = dtvec; e.step = step_ctr; e.stream = s;
       K5CHK(k5_launch_euler_step(e));
@@ -2740,12 +2778,15 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   // first step (ipc_comm.h)
   const bool graph = d->use_graph && !d->mag.on && !d->cal.on && !d->profiling && a->num_steps > 2 && !d->nabla_tap && !d->comm.loop && !d->pair.loop &&
                      !win && uniform;
-  r.host_tab.resize((gd.on ? 4 : 3) * (size_t)N);
+  if (d->sto.on) r.sto = &d->sto;
+  const size_t sto_at = (gd.on ? 4 : 3) * (size_t)N;   // with a stochastic plan two more tables: scale and noise_coef
+  r.host_tab.resize(sto_at + (r.sto ? 2 : 0) * (size_t)N);
   for (int i = 0; i < N; ++i) {
     r.host_tab[i] = a->sigmas[i] * 1000.0f;
-    r.host_tab[N + i] = a->sigmas[i + 1] - a->sigmas[i];
+    r.host_tab[N + i] = r.sto ? r.sto->dt_down[i] : a->sigmas[i + 1] - a->sigmas[i];   // a step without noise has dt_down == this difference
     r.host_tab[2 * N + i] = a->sigmas[i + 1];
     if (gd.on) r.host_tab[3 * N + i] = r.w_at(i);   // a fourth table with a plan: the weight the coefficients read in the captured step
+    if (r.sto) { r.host_tab[sto_at + i] = r.sto->scale[i]; r.host_tab[sto_at + N + i] = r.sto->coef[i]; }
   }
   r.t1000 = r.host_tab.data(); r.dt = r.t1000 + N; r.sigma_next = r.dt + N;
   if (graph) {
@@ -2763,6 +2804,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     HIPCHK(hipStreamSynchronize(r.s));   // host_tab lives in this call only
     r.tvec = d->ws_sched.as<float>(); r.dtvec = r.tvec + N; r.signext = r.dtvec + N;
     if (gd.on) r.wvec = r.signext + N;
+    if (r.sto) { r.scalevec = r.tvec + sto_at; r.coefvec = r.scalevec + N; }
   }
   const hipStream_t s = r.s;
   if (edit) {   // the start latent: the source at sigmas[0] everywhere, whatever the mask
@@ -2823,6 +2865,8 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     if (i == first) K5CHK(decide_fuse());
     if (gd.on) (r.kind(i) == SampleRun::GUIDED ? gd.guided : r.kind(i) == SampleRun::UNGUIDED ? gd.unguided : gd.zero) += 1;
     if (r.skip_at(i)) d->skip.skip_steps += 1;
+    // per step on the host, not through ReplayCounts: the captured step's difference would count the last step, which draws nothing, as step 1
+    if (r.noisy_at(i)) d->sto.noisy_steps += 1;
     if (wt.on) {
       K5CHK(wt.step(r, i));
       if (wt.stopped) break;
@@ -2863,6 +2907,10 @@ static int many_state_ok(const k5_dit* d, const char* who) {
   if (d->mag.on) { k5_set_error("%s: MagCache is set on the handle", who); return K5_ERR_STATE; }
   if (d->cal.on) { k5_set_error("%s: the handle is calibrating MagCache", who); return K5_ERR_STATE; }
   if (d->use_graph) { k5_set_error("%s: graph capture is on (k5_dit_set_graph)", who); return K5_ERR_STATE; }
+  if (d->sto.on && !strcmp(who, "k5_sample_many")) {
+    k5_set_error("%s: a stochastic plan is set (k5_dit_set_stochastic): it holds one seed, the samples of a batch need one each — run them one at a time", who);
+    return K5_ERR_STATE;
+  }
   return K5_OK;
 }
 
@@ -3055,6 +3103,38 @@ extern "C" int k5_dit_skip_state(k5_dit* d, int* on, long long* skip_steps, long
   if (blocks_shared) *blocks_shared = sk.blocks_shared;
   if (blocks_run) *blocks_run = sk.blocks_run;
   if (reset) sk.skip_steps = sk.blocks_shared = sk.blocks_run = 0;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_set_stochastic(k5_dit* d, const k5_stochastic* p) {
+  g_err[0] = 0;
+  if (!d) { k5_set_error("k5_dit_set_stochastic: null handle"); return K5_ERR_ARG; }
+  k5_dit::Stochastic& so = d->sto;
+  if (!p) { so.on = false; so.dt_down.clear(); so.scale.clear(); so.coef.clear(); so.seed = 0; so.first_stream = 0; return K5_OK; }
+  if (p->num_steps < 1 || !p->dt_down || !p->scale || !p->noise_coef) {
+    k5_set_error("k5_dit_set_stochastic: dt_down, scale and noise_coef with num_steps = %d", p->num_steps);
+    return K5_ERR_ARG;
+  }
+  for (int i = 0; i < p->num_steps; ++i) {
+    if (!isfinite(p->dt_down[i]) || !isfinite(p->scale[i]) || !isfinite(p->noise_coef[i]) || p->noise_coef[i] < 0.0f) {
+      k5_set_error("k5_dit_set_stochastic: step %d: dt_down %g, scale %g, noise_coef %g must be finite and noise_coef >= 0", i, (double)p->dt_down[i],
+                   (double)p->scale[i], (double)p->noise_coef[i]);
+      return K5_ERR_ARG;
+    }
+  }
+  so.dt_down.assign(p->dt_down, p->dt_down + p->num_steps);
+  so.scale.assign(p->scale, p->scale + p->num_steps);
+  so.coef.assign(p->noise_coef, p->noise_coef + p->num_steps);
+  so.seed = p->seed; so.first_stream = p->first_stream;
+  so.on = true;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_stochastic_state(k5_dit* d, int* on, long long* noisy_steps, int reset) {
+  if (!d) { k5_set_error("k5_dit_stochastic_state: null handle"); return K5_ERR_ARG; }
+  if (on) *on = d->sto.on ? 1 : 0;
+  if (noisy_steps) *noisy_steps = d->sto.noisy_steps;
+  if (reset) d->sto.noisy_steps = 0;
   return K5_OK;
 }
 

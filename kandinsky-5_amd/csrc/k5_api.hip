@@ -437,6 +437,37 @@ int k5_skip_euler(float* img, const void* v_cond, const void* v_uncond, const vo
   return ret(st, "k5_skip_euler");
 }
 
+int k5_philox_words(uint32_t* out, uint64_t blk0, int64_t nblk, uint64_t seed, uint32_t c2, uint32_t c3, void* stream) {
+  const int st = k5_launch_philox_words(out, blk0, nblk, seed, c2, c3, (hipStream_t)stream);
+  if (st == K5_ERR_ARG) { k5_set_error("k5_philox_words: need a 4-byte aligned out and nblk >= 1 (nblk %lld)", (long long)nblk); return st; }
+  return ret(st, "k5_philox_words");
+}
+
+int k5_noise_normal_f32(float* out, int64_t n, uint64_t seed, uint32_t stream_id, void* stream) {
+  const int st = k5_launch_noise_normal(out, n, seed, stream_id, (hipStream_t)stream);
+  if (st == K5_ERR_ARG) { k5_set_error("k5_noise_normal_f32: need a 4-byte aligned out and n >= 1 (n %lld)", (long long)n); return st; }
+  return ret(st, "k5_noise_normal_f32");
+}
+
+int k5_stochastic_euler(float* img, const void* v_cond, const void* v_uncond, const void* v_skip, float w, const float* ab, float g, float dt_down,
+                        const float* source, const float* eps, const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out,
+                        float scale, float noise_coef, const float* noise, uint64_t seed, uint32_t stream_id, void* stream) {
+  K5EulerStepArgs a;
+  a.img = img; a.v_cond = v_cond; a.v_uncond = v_uncond; a.w = w; a.ab = ab; a.dt = dt_down;
+  a.source = source; a.noise = eps; a.keep_mask = keep_mask; a.sigma_next = sigma_next;
+  a.cells = cells; a.C = C; a.v_out = v_out; a.v_skip = v_skip; a.skip_scale = g;
+  a.stochastic = true; a.scale = scale; a.noise_coef = noise_coef; a.znoise = noise; a.seed = seed; a.stream_id = stream_id;
+  a.stream = (hipStream_t)stream;
+  const int st = k5_launch_euler_step(a);
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_stochastic_euler: need img and v_cond, cells and C >= 1, v_uncond with ab, a finite g > 0 with v_skip and g = 0 without, v_out "
+                 "only with ab or v_skip, source and eps with a keep_mask, a finite scale and a finite noise_coef >= 0 (g %g, scale %g, noise_coef "
+                 "%g, cells %lld, C %d)", (double)g, (double)scale, (double)noise_coef, (long long)cells, C);
+    return st;
+  }
+  return ret(st, "k5_stochastic_euler");
+}
+
 int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts_dev,
                          const float* weights_dev, int nwin, int F, int T, int64_t frame_elems, void* stream) {
   if (!img || !v_cond || !starts_dev || !weights_dev || nwin < 1 || nwin > 64 || F < 1 || T < 1 || frame_elems < 1) {

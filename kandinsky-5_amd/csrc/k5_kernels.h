@@ -184,6 +184,11 @@ int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C,
 // Skip-layer guidance (v_skip bf16 [cells * C], skip_scale g by value): with the velocity above as base, d = bf16(c - s), e = bf16(g d),
 // v = bf16(base + e) — torch eager `base + g * (c - s)` on bf16 tensors — and v_out receives v with or without ab.  K5_ERR_ARG: v_skip without
 // g > 0, a g that is not finite or is negative, a g without v_skip.
+// The stochastic step (stochastic = true; dt is then the step's dt_down): x1 = the update above, x2 = rn(rn(scale x1) + rn(noise_coef z)) when
+// noise_coef != 0 and x1 when it is 0, then the keep rule.  z = znoise[g] (fp32 [cells * C]) or, znoise null, normal g & 3 of Philox block g >> 2
+// of (seed, stream_id) — k5_launch_noise_normal's bits.  ab, v_skip and v_out are taken at run time, as in the skip step.  scalevec / coefvec
+// (both or neither, with step): the captured step reads scale and noise_coef at the step counter and draws from stream stream_id + *step.
+// K5_ERR_ARG: a scale or noise_coef that is not finite, noise_coef < 0, znoise / scalevec / coefvec without stochastic.
 struct K5EulerStepArgs {
   float* img = nullptr; const void* v_cond = nullptr; const void* v_uncond = nullptr;
   float w = 1.f; const float* ab = nullptr; float dt = 0.f;
@@ -191,9 +196,15 @@ struct K5EulerStepArgs {
   int64_t cells = 0; int C = 1; void* v_out = nullptr;
   const float* dtvec = nullptr; const float* signext = nullptr; const int* step = nullptr;
   const void* v_skip = nullptr; float skip_scale = 0.f;
+  bool stochastic = false; float scale = 1.f, noise_coef = 0.f; const float* znoise = nullptr; uint64_t seed = 0; uint32_t stream_id = 0;
+  const float* scalevec = nullptr; const float* coefvec = nullptr;
   hipStream_t stream = nullptr;
 };
 int k5_launch_euler_step(const K5EulerStepArgs& a);
+// Philox4x32-10 raw words: out [nblk][4] of blocks blk0 .. blk0 + nblk - 1 (mod 2^64) under key = seed and counter words 2 / 3 = c2 / c3
+int k5_launch_philox_words(uint32_t* out, uint64_t blk0, int64_t nblk, uint64_t seed, uint32_t c2, uint32_t c3, hipStream_t stream);
+// out[g] = normal g & 3 of Philox block g >> 2 (counter (blk lo, blk hi, stream_id, 0), key = seed; Box-Muller in fp32), any n >= 1
+int k5_launch_noise_normal(float* out, int64_t n, uint64_t seed, uint32_t stream_id, hipStream_t stream);
 // editing: out = rn(rn((1 - sigma) * source) + rn(sigma * noise)), nothing contracted
 int k5_launch_edit_renoise(float* out, const float* source, const float* noise, float sigma, int64_t n, hipStream_t stream);
 // guidance coefficients of one sample: the five float64 sums Sc, Su, Scc, Suu, Scu of the bf16 velocities v_cond / v_uncond [n] in a fixed order

@@ -12,6 +12,7 @@
 //   OutLayer un-patchify    nn.py:384-399 (+ fractal_unflatten :44-51)             -> unpatchify_kernel
 //   CFG combine + Euler     generation_utils.py:74-76,128      -> euler_step_kernel      (K18)
 //   RoPE1D/RoPE3D tables    nn.py:99-150                        -> rope_table_kernel      (K15)
+//   stochastic step noise   (none: the reference's loop is the ODE step)   -> philox_normal4 inside euler_step_kernel, noise_normal_kernel
 #include <stdlib.h>
 
 #include "k5_common.h"
@@ -654,6 +655,65 @@ __device__ __forceinline__ float skip_velocity(float base, float g, float c, flo
   return bf_round(base + e);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Counter-based noise (stochastic sampling): Philox4x32-10 (Salmon et al. 2011) — multipliers 0xD2511F53 / 0xCD9E8D57, Weyl
+// constants 0x9E3779B9 / 0xBB67AE85, ten rounds, the key bumped between rounds.  Nothing is read from memory and no state lives anywhere: the
+// words of a block are a pure function of (counter, key).  A round is two 32 x 32 -> 64 products, each a v_mul_hi_u32 and a v_mul_lo_u32, both
+// quarter-rate: 40 of them per block are the generator's cost, far above the four transcendentals that follow, so one thread evaluates a
+// whole block and keeps all four words — a thread per ELEMENT would pay the forty multiplies four times for the same bits.
+K5_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&r)[4]) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+// u = ((r >> 9) + 0.5) * 2^-23: 23 bits and the half fit fp32's 24, the scaling is a power of two — exact, and inside (0, 1)
+K5_DEV float philox_unit(uint32_t r) { return ((float)(r >> 9) + 0.5f) * 0x1p-23f; }
+
+// The four standard normals of block `blk` of stream `stream_id` under `seed`: key = (low, high word of the seed), counter = (low, high word
+// of blk, stream_id, 0); (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1) and (z2, z3) from (u2, u3) likewise (Box-Muller).  fp32 throughout with
+// the library's logf / sqrtf / sincospif, no fast-math intrinsic; sincospif takes 2 u1 (exact) and so spares the rounding of 2 pi u1.
+K5_DEV void philox_normal4(uint64_t blk, uint64_t seed, uint32_t stream_id, float (&z)[4]) {
+  uint32_t r[4];
+  philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), stream_id, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+#pragma unroll
+  for (int j = 0; j < 4; j += 2) {
+    const float rad = sqrtf(-2.0f * logf(philox_unit(r[j])));
+    float sn, cs;
+    sincospif(2.0f * philox_unit(r[j + 1]), &sn, &cs);
+    z[j] = rad * cs;
+    z[j + 1] = rad * sn;
+  }
+}
+
+__global__ __launch_bounds__(256) void philox_words_kernel(uint32_t* __restrict__ out, uint64_t blk0, int64_t nblk, uint64_t seed, uint32_t c2,
+                                                           uint32_t c3) {
+  for (int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x; b < nblk; b += (int64_t)gridDim.x * 256) {
+    const uint64_t blk = blk0 + (uint64_t)b;   // wraps mod 2^64
+    uint32_t r[4];
+    philox4x32_10((uint32_t)blk, (uint32_t)(blk >> 32), c2, c3, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[b * 4 + k] = r[k];
+  }
+}
+
+// out[g] = z[g & 3] of block g >> 2: a thread per block; the thread of a last, partial block evaluates it whole and stores what exists
+__global__ __launch_bounds__(256) void noise_normal_kernel(float* __restrict__ out, int64_t n, uint64_t seed, uint32_t stream_id) {
+  const int64_t nblk = (n + 3) >> 2;
+  for (int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x; b < nblk; b += (int64_t)gridDim.x * 256) {
+    float z[4];
+    philox_normal4((uint64_t)b, seed, stream_id, z);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (b * 4 + k < n) out[b * 4 + k] = z[k];
+  }
+}
+
 // The sampler's update of one step, one pass over the latent (K18): the velocity is v = guided_velocity(ab[0], ab[1], c, u) with coefficients
 // from device memory (guidance_finish_kernel wrote them), else cfg_velocity(w, c, u), else (vu NULL) c itself; img += bf16(dt * v)
 // (generation_utils.py:128, (0-dim fp32) * (bf16) -> bf16); then, under a keep mask, the keep rule at sigma_next: element g of cell g / C reads
@@ -664,33 +724,86 @@ __device__ __forceinline__ float skip_velocity(float base, float g, float c, flo
 // A third instantiation (SK) is the skip-layer-guidance step: a third stream vs, the conditional velocity with some blocks skipped, and a scale
 // sg by value; the velocity above is the base and v = skip_velocity(base, sg, c, s).  There ab is looked at at run time (the step runs a third
 // forward, a branch on a uniform is nothing next to it) and v_out receives v with or without coefficients.
-template <bool AB, bool SK>
+// A fourth instantiation (ST) is the stochastic step (k5_stochastic_euler): after x1 = x + bf16(dt v), with dt the step's dt_down, comes
+// x2 = renoise_at(scale, noise_coef, x1, z) when noise_coef != 0 (x1 itself when it is 0: the launch is the same, a branch on a uniform), z from
+// `znoise` or, without one, from philox_normal4 — then the keep rule.  There a thread owns the four elements of one Philox block (g >> 2), so
+// the forty quarter-rate multiplies of a block are paid once for four elements; ab and vs are looked at at run time as in SK.  The one thread
+// whose block reaches past n (n % 4 != 0) still evaluates the whole block — one block's arithmetic per launch, for one to three elements.
+// In the captured step scale and noise_coef come from device tables at the step counter, next to dtvec, and the stream id is stream_id + *step.
+// ST is a template parameter, not a branch: the three instantiations above keep one element per thread and their instruction stream
+// (the per-element body below is theirs, PER = 1 folds the inner loop away; 24 / 25 / 26 VGPRs as before).  Measured at the 5 s clip's 3.0 M
+// elements, legs alternated in one process (tools/stochastic_bench.py, profiles/stochastic_bench.jsonl): the plain update 5.98 us against 6.04 us
+// from the build without ST; ST with in-kernel noise 10.64 us, with znoise 9.23 us (+ 7.41 us for the launch that would write it), with
+// noise_coef == 0 7.93 us.
+template <bool AB, bool SK, bool ST>
 __global__ __launch_bounds__(256) void euler_step_kernel(float* __restrict__ img, const bf16_t* vc, const bf16_t* __restrict__ vu, float w,
                                                          const float* __restrict__ ab, float dt, const float* __restrict__ x0,
                                                          const float* __restrict__ eps, const float* __restrict__ mask, float sigma_next,
                                                          int C, bf16_t* v_out, const float* __restrict__ dtvec,
                                                          const float* __restrict__ signext, const int* __restrict__ step, int64_t n,
-                                                         const bf16_t* __restrict__ vs, float sg) {
+                                                         const bf16_t* __restrict__ vs, float sg, float scale, float noise_coef,
+                                                         const float* __restrict__ znoise, uint64_t seed, uint32_t stream_id,
+                                                         const float* __restrict__ scalevec, const float* __restrict__ coefvec) {
   if (dtvec) dt = dtvec[*step];
   if (signext) sigma_next = signext[*step];
-  const bool coeffs = SK ? ab != nullptr : AB;
+  if (ST && scalevec) { scale = scalevec[*step]; noise_coef = coefvec[*step]; stream_id += (uint32_t)*step; }
+  const bool skip = ST ? vs != nullptr : SK;
+  const bool coeffs = (SK || ST) ? ab != nullptr : AB;
+  const bool noisy = ST && noise_coef != 0.0f;
   const float alpha = coeffs ? ab[0] : 0.0f, beta = coeffs ? ab[1] : 0.0f;
   const float a = 1.0f - sigma_next;
   const bf16_t* up = vu ? vu : vc;   // without guidance u is unused: the same address again costs no traffic, a branch around the load would cost a wait
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < n; g += (int64_t)gridDim.x * 256) {
-    // every load that does not hang on a value first, so that they are in flight together: a thread has one or two elements, latency is the cost
-    const bf16_t cb = vc[g];
-    const bf16_t ub = up[g];
-    const bf16_t sb = SK ? vs[g] : cb;
-    float x = img[g];
-    const float m = mask ? mask[g / C] : 0.0f;
-    const float c = bf2f(cb), u = bf2f(ub);
-    float v = coeffs ? guided_velocity(alpha, beta, c, u) : (vu ? cfg_velocity(w, c, u) : c);
-    if (SK) v = skip_velocity(v, sg, c, bf2f(sb));
-    x = __fadd_rn(x, bf_round(__fmul_rn(dt, v)));
-    if (m != 0.0f) x = keep_blend(x, renoise_at(a, sigma_next, x0[g], eps[g]), m);
-    img[g] = x;
-    if ((AB || SK) && v_out) v_out[g] = f2bf(v);
+  constexpr int PER = ST ? 4 : 1;    // elements per thread
+  const int64_t items = ST ? (n + 3) >> 2 : n;
+  // ST: a thread's four elements are 16 B of the latent and 8 B of each velocity, so where n % 4 == 0 and the bases allow it they move as one
+  // access each; otherwise element by element (64 lanes x 4 B at a 16-B stride: the same lines, four instructions each)
+  const auto at = [](const void* q, uintptr_t m) { return (reinterpret_cast<uintptr_t>(q) & (m - 1)) == 0; };
+  const bool vec = ST && (n & 3) == 0 && at(img, 16) && at(vc, 8) && at(up, 8) && at(vs, 8) && at(znoise, 16) && at(v_out, 8);
+  for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (int64_t)gridDim.x * 256) {
+    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 xv = {0.0f, 0.0f, 0.0f, 0.0f}, zv = xv;
+    u32x2 cv = {0u, 0u}, uv = cv, sv = cv, ov = cv;
+    if (ST && vec) {   // every load ahead of the generator's arithmetic
+      xv = *reinterpret_cast<const f32x4*>(img + it * 4);
+      cv = *reinterpret_cast<const u32x2*>(vc + it * 4);
+      uv = *reinterpret_cast<const u32x2*>(up + it * 4);
+      sv = skip ? *reinterpret_cast<const u32x2*>(vs + it * 4) : cv;
+      if (noisy && znoise) zv = *reinterpret_cast<const f32x4*>(znoise + it * 4);
+    }
+    if (ST && noisy && !znoise) philox_normal4((uint64_t)it, seed, stream_id, z);
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      const int64_t g = ST ? it * 4 + k : it;
+      if (ST && g >= n) break;
+      float x, c, u, s3;
+      if (ST && vec) {
+        x = xv[k]; c = bf16_at(cv, k); u = bf16_at(uv, k); s3 = bf16_at(sv, k);
+      } else {
+        // every load that does not hang on a value first, so that they are in flight together: a thread has one or two elements, latency is the cost
+        const bf16_t cb = vc[g];
+        const bf16_t ub = up[g];
+        const bf16_t sb = (SK || ST) && skip ? vs[g] : cb;
+        x = img[g];
+        c = bf2f(cb); u = bf2f(ub); s3 = bf2f(sb);
+      }
+      const float m = mask ? mask[g / C] : 0.0f;
+      float v = coeffs ? guided_velocity(alpha, beta, c, u) : (vu ? cfg_velocity(w, c, u) : c);
+      if ((SK || ST) && skip) v = skip_velocity(v, sg, c, s3);
+      x = __fadd_rn(x, bf_round(__fmul_rn(dt, v)));
+      if (ST && noisy) x = renoise_at(scale, noise_coef, x, znoise ? (vec ? zv[k] : znoise[g]) : z[k]);
+      if (m != 0.0f) x = keep_blend(x, renoise_at(a, sigma_next, x0[g], eps[g]), m);
+      if (ST && vec) {
+        xv[k] = x;
+        ov[k >> 1] |= (__float_as_uint(bf_round(v)) >> 16) << (16 * (k & 1));   // bf_round(v) == v: its low half is zero
+      } else {
+        img[g] = x;
+        if ((AB || SK || ST) && v_out) v_out[g] = f2bf(v);
+      }
+    }
+    if (ST && vec) {
+      *reinterpret_cast<f32x4*>(img + it * 4) = xv;
+      if (v_out) *reinterpret_cast<u32x2*>(v_out + it * 4) = ov;
+    }
   }
 }
 
@@ -1071,11 +1184,31 @@ int k5_launch_euler_step(const K5EulerStepArgs& a) {
   if ((a.ab && !a.v_uncond) || (a.v_out && !a.ab && !a.v_skip) || (a.keep_mask && (!a.source || !a.noise))) return K5_ERR_ARG;
   if (((a.dtvec != nullptr) != (a.step != nullptr)) || (a.signext && !a.dtvec)) return K5_ERR_ARG;
   if (a.v_skip ? !(a.skip_scale > 0.0f && __builtin_isfinite(a.skip_scale)) : a.skip_scale != 0.0f) return K5_ERR_ARG;   // also a NaN or negative scale
+  if (a.stochastic) {
+    if (!__builtin_isfinite(a.scale) || !(a.noise_coef >= 0.0f && __builtin_isfinite(a.noise_coef))) return K5_ERR_ARG;   // also a NaN
+    if (((a.scalevec != nullptr) != (a.coefvec != nullptr)) || (a.scalevec && !a.step)) return K5_ERR_ARG;
+  } else if (a.znoise || a.scalevec || a.coefvec) return K5_ERR_ARG;
   const int64_t n = a.cells * a.C;
-  const auto kernel = a.v_skip ? euler_step_kernel<false, true> : a.ab ? euler_step_kernel<true, false> : euler_step_kernel<false, false>;
-  hipLaunchKernelGGL(kernel, dim3(grid_for(n)), dim3(256), 0, a.stream, a.img, (const bf16_t*)a.v_cond, (const bf16_t*)a.v_uncond,
-                     a.w, a.ab, a.dt, a.source, a.noise, a.keep_mask, a.sigma_next, a.C, (bf16_t*)a.v_out, a.dtvec, a.signext, a.step, n,
-                     (const bf16_t*)a.v_skip, a.skip_scale);
+  const auto kernel = a.stochastic ? euler_step_kernel<false, false, true>
+                      : a.v_skip   ? euler_step_kernel<false, true, false>
+                      : a.ab       ? euler_step_kernel<true, false, false>
+                                   : euler_step_kernel<false, false, false>;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(a.stochastic ? (n + 3) / 4 : n)), dim3(256), 0, a.stream, a.img, (const bf16_t*)a.v_cond,
+                     (const bf16_t*)a.v_uncond, a.w, a.ab, a.dt, a.source, a.noise, a.keep_mask, a.sigma_next, a.C, (bf16_t*)a.v_out, a.dtvec,
+                     a.signext, a.step, n, (const bf16_t*)a.v_skip, a.skip_scale, a.scale, a.noise_coef, a.znoise, a.seed, a.stream_id,
+                     a.scalevec, a.coefvec);
+  return done();
+}
+
+int k5_launch_philox_words(uint32_t* out, uint64_t blk0, int64_t nblk, uint64_t seed, uint32_t c2, uint32_t c3, hipStream_t s) {
+  if (!out || nblk < 1 || (reinterpret_cast<uintptr_t>(out) & 3)) return K5_ERR_ARG;
+  hipLaunchKernelGGL(philox_words_kernel, dim3(grid_for(nblk)), dim3(256), 0, s, out, blk0, nblk, seed, c2, c3);
+  return done();
+}
+
+int k5_launch_noise_normal(float* out, int64_t n, uint64_t seed, uint32_t stream_id, hipStream_t s) {
+  if (!out || n < 1 || (reinterpret_cast<uintptr_t>(out) & 3)) return K5_ERR_ARG;
+  hipLaunchKernelGGL(noise_normal_kernel, dim3(grid_for((n + 3) / 4, 256, 1024)), dim3(256), 0, s, out, n, seed, stream_id);
   return done();
 }
 

@@ -119,6 +119,12 @@ class SkipGuidance(C.Structure):
                 ("steps", C.POINTER(C.c_ubyte)), ("num_steps", C.c_int)]
 
 
+class Stochastic(C.Structure):
+    """k5_stochastic: the plan of k5_dit_set_stochastic (the three tables are HOST memory, copied by the call)."""
+    _fields_ = [("num_steps", C.c_int), ("dt_down", C.POINTER(C.c_float)), ("scale", C.POINTER(C.c_float)),
+                ("noise_coef", C.POINTER(C.c_float)), ("seed", C.c_uint64), ("first_stream", C.c_uint32)]
+
+
 class VaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int), ("out_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -213,6 +219,11 @@ SYMBOLS = {
     "k5_guidance_coeffs_bf16": (_I, [_P, _P, _I64, _F, _I, _F, _P, _P, _P, _P]),
     "k5_guided_euler": (_I, [_P, _P, _P, _P, _F, _P, _P, _P, _F, _I64, _I, _P, _P]),
     "k5_skip_euler": (_I, [_P, _P, _P, _P, _F, _P, _F, _F, _P, _P, _P, _F, _I64, _I, _P, _P]),
+    "k5_philox_words": (_I, [_P, C.c_uint64, _I64, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
+    "k5_noise_normal_f32": (_I, [_P, _I64, C.c_uint64, C.c_uint32, _P]),
+    "k5_stochastic_euler": (_I, [_P, _P, _P, _P, _F, _P, _F, _F, _P, _P, _P, _F, _I64, _I, _P, _F, _F, _P, C.c_uint64, C.c_uint32, _P]),
+    "k5_dit_set_stochastic": (_I, [_P, C.POINTER(Stochastic)]),
+    "k5_dit_stochastic_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), _I]),
     "k5_cfg_euler_windows": (_I, [_P, _P, _P, _F, _F, _P, _P, _I, _I, _I, _I64, _P]),
     "k5_sample_windows": (_I, [_P, C.POINTER(SampleWindowsArgs), _P, _P]),
     "k5_x0_preview": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I64, _I, _P]),
@@ -616,6 +627,62 @@ def skip_euler_(img, v_cond, v_uncond, v_skip, w, g, dt, ab=None, source=None, n
     with torch.cuda.device(img.device):
         check(lib().k5_skip_euler(ptr(img), ptr(v_cond), ptr(v_uncond), ptr(v_skip), float(w), ptr(ab), float(g), float(dt), ptr(source),
                                   ptr(noise), ptr(keep_mask), float(sigma_next), cells, C_, ptr(v_out), stream_ptr(img.device)), "k5_skip_euler")
+    return img
+
+
+def philox_words(blk0, nblk, seed, c2=0, c3=0, device="cuda"):
+    """The raw Philox4x32-10 words of blocks blk0 .. blk0 + nblk - 1 (mod 2^64) under key `seed` and counter words 2 / 3 = c2 / c3
+    (k5_philox_words): an int32 [nblk][4] tensor holding the uint32 bit patterns."""
+    out = torch.empty((int(nblk), 4), dtype=torch.int32, device=device)
+    _need_cuda(out)
+    with torch.cuda.device(out.device):
+        check(lib().k5_philox_words(ptr(out), int(blk0) & (2 ** 64 - 1), int(nblk), int(seed) & (2 ** 64 - 1), int(c2) & 0xffffffff,
+                                    int(c3) & 0xffffffff, stream_ptr(out.device)), "k5_philox_words")
+    return out
+
+
+def noise_normal_(out, seed, stream_id=0, n=None):
+    """out.view(-1)[g] = standard normal g of stream `stream_id` under `seed` for g < n (default: all of out), from the counter-based generator
+    (k5_noise_normal_f32): a pure function of (seed, stream_id, g).  out: a contiguous fp32 tensor on the device."""
+    _need_cuda(out)
+    if out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("noise_normal_: out must be a contiguous fp32 tensor")
+    n = out.numel() if n is None else int(n)
+    if not 1 <= n <= out.numel():
+        raise ValueError(f"noise_normal_: n must be in 1..{out.numel()} (got {n})")
+    with torch.cuda.device(out.device):
+        check(lib().k5_noise_normal_f32(ptr(out), n, int(seed) & (2 ** 64 - 1), int(stream_id) & 0xffffffff, stream_ptr(out.device)),
+              "k5_noise_normal_f32")
+    return out
+
+
+def stochastic_euler_(img, v_cond, v_uncond, w, dt_down, scale, noise_coef, seed, stream_id, z=None, v_skip=None, g=0.0, ab=None, source=None,
+                      noise=None, keep_mask=None, sigma_next=0.0, v_out=None):
+    """The update of a stochastic step (k5_stochastic_euler): the velocity as cfg_euler_ (v_uncond, w), guided_euler_ (ab) or skip_euler_
+    (v_skip, g) forms it, img += bf16(dt_down * v), then where noise_coef != 0 img = scale * img + noise_coef * z with z the fp32 tensor `z` or,
+    z None, the generator's normals of (seed, stream_id) — noise_normal_'s bits — and last, with a keep_mask, the keep rule of cfg_euler_edit_ at
+    sigma_next (`noise` is the edit's eps).  noise_coef == 0 is the matching plain update bit for bit."""
+    C_ = img.shape[-1]
+    cells = img.numel() // C_
+    for t in (img, source, noise, z):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != img.numel()):
+            raise ValueError("stochastic_euler_: img, source, noise and z must be contiguous fp32 tensors of one size")
+    for v in (v_cond, v_uncond, v_skip, v_out):
+        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != img.numel()):
+            raise ValueError("stochastic_euler_: the velocities must be contiguous bf16 tensors of img's size")
+    if v_cond is None:
+        raise ValueError("stochastic_euler_: a step has the conditional velocity")
+    if ab is not None and (ab.dtype != torch.float32 or ab.numel() != 2 or not ab.is_contiguous()):
+        raise ValueError("stochastic_euler_: ab must be a contiguous fp32 [2] tensor on the device")
+    if keep_mask is not None and (source is None or noise is None or keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous()
+                                  or keep_mask.numel() != cells):
+        raise ValueError("stochastic_euler_: keep_mask must be a contiguous fp32 tensor with one value per cell and needs source and noise")
+    _need_cuda(img, v_cond, v_uncond, v_skip, ab, source, noise, keep_mask, v_out, z)
+    with torch.cuda.device(img.device):
+        check(lib().k5_stochastic_euler(ptr(img), ptr(v_cond), ptr(v_uncond), ptr(v_skip), float(w), ptr(ab), float(g), float(dt_down),
+                                        ptr(source), ptr(noise), ptr(keep_mask), float(sigma_next), cells, C_, ptr(v_out), float(scale),
+                                        float(noise_coef), ptr(z), int(seed) & (2 ** 64 - 1), int(stream_id) & 0xffffffff,
+                                        stream_ptr(img.device)), "k5_stochastic_euler")
     return img
 
 

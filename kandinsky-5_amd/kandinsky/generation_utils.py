@@ -16,7 +16,7 @@ import torch
 
 from . import _engine as E
 from .models.dit import (DiffusionTransformer3D, SamplingInterrupted, StepInfo, _is_guided, check_guidance_args, check_nag_args,
-                         check_nag_numbers, check_region_args, check_skip_args, check_watch_args, split_per_sample)
+                         check_nag_numbers, check_region_args, check_skip_args, check_stochastic_args, check_watch_args, split_per_sample)
 
 
 def _attr(obj, name, default=None):
@@ -201,6 +201,75 @@ def _skip_for_call(model, skip):
                 model.set_skip_guidance(*before)
             else:
                 model.clear_skip_guidance()
+
+
+def stochastic_plan(sigmas, eta, s_noise=1.0, interval=None):
+    """The per-step tables of stochastic sampling over `sigmas` (num_steps + 1 values): `(dt_down, scale, noise_coef)`, three lists of
+    num_steps fp32 values.  Flow matching is x_sigma = (1 - sigma) x0 + sigma eps; step i goes from s = sigmas[i] to t = sigmas[i + 1] and,
+    with churn `eta` in [0, 1] and noise scale `s_noise`,
+        sigma_down = t (1 + (t / s - 1) eta)        a = (1 - t) / (1 - sigma_down)        c = s_noise sqrt(max(0, t^2 - (sigma_down a)^2))
+    the sampler takes the Euler step to sigma_down (dt_down = sigma_down - s) and then x = a x + c z with z ~ N(0, 1): at eta = s_noise = 1
+    the marginal is that of x_t.  Computed in float64 and rounded once to fp32.  `interval` = (lo, hi): only the steps with
+    lo <= sigmas[i] <= hi are stochastic; None = every step.  A step that is not (eta 0, outside the interval, c == 0 — the last step, where
+    t = 0, always) gets scale exactly 1, noise_coef 0 and as dt_down the fp32 difference sigmas[i + 1] - sigmas[i] the engine forms itself: the
+    plain step, bit for bit.  Host only, like `guidance_plan`."""
+    sig = [float(v) for v in sigmas]
+    n = len(sig) - 1
+    if n < 1:
+        raise ValueError("stochastic_plan: sigmas must hold num_steps + 1 >= 2 values")
+    try:
+        eta, s_noise = float(eta), float(s_noise)
+    except (TypeError, ValueError):
+        raise ValueError("stochastic_plan: eta and s_noise must be numbers") from None
+    if not 0.0 <= eta <= 1.0:   # also a NaN
+        raise ValueError(f"eta must be in [0, 1], got {eta}")
+    if not math.isfinite(s_noise) or s_noise < 0.0:
+        raise ValueError(f"s_noise must be a finite number >= 0, got {s_noise}")
+    lo, hi = -math.inf, math.inf
+    if interval is not None:
+        try:
+            lo, hi = (float(v) for v in interval)
+        except (TypeError, ValueError):
+            raise ValueError("sde_interval must be (lo, hi)") from None
+        if not lo <= hi:
+            raise ValueError(f"sde_interval must be (lo, hi) with lo <= hi, got ({lo}, {hi})")
+    f32 = torch.tensor(sig, dtype=torch.float32)
+    dt = (f32[1:] - f32[:-1]).tolist()   # the engine's own fp32 difference
+    dt_down, scale, coef = [], [], []
+    for i in range(n):
+        s, t = sig[i], sig[i + 1]
+        a = c = 0.0
+        if eta > 0.0 and lo <= s <= hi and s > 0.0:
+            down = t * (1.0 + (t / s - 1.0) * eta)
+            if 1.0 - down > 0.0:
+                a = (1.0 - t) / (1.0 - down)
+                c = s_noise * math.sqrt(max(0.0, t * t - (down * a) ** 2))
+                c = float(torch.tensor(c, dtype=torch.float64).to(torch.float32))
+        if c == 0.0:
+            step = (dt[i], 1.0, 0.0)
+        else:
+            step = (float(torch.tensor(down - s, dtype=torch.float64).to(torch.float32)), float(torch.tensor(a, dtype=torch.float64).to(torch.float32)), c)
+        for table, value in zip((dt_down, scale, coef), step):
+            table.append(value)
+    return dt_down, scale, coef
+
+
+def _stochastic_for_run(model, sigmas, first, eta, s_noise, sde_interval, sde_seed, windowed, preview_every):
+    """`generate`'s stochastic keywords -> None when they are off (eta 0, or no step draws noise: nothing changes), otherwise the checked plan
+    (dt_down, scale, noise_coef of the steps that run, seed, first stream 0) with the ValueErrors of what the engine refuses.  `sigmas`: the
+    full schedule, of which steps `first`.. run."""
+    dt_down, scale, coef = (t[first:] for t in stochastic_plan(sigmas, eta, s_noise, sde_interval))   # cut with the schedule
+    plan = check_stochastic_args(dt_down, scale, coef, sde_seed, 0)
+    if not any(coef):
+        return None
+    if windowed:
+        raise ValueError("eta > 0 together with context windows is not supported: the windowed update has no noise term")
+    if _has_magcache(model):
+        raise ValueError("eta > 0 with MagCache: the ratio table was measured on ODE trajectories")
+    if preview_every:
+        raise ValueError("eta > 0 with preview_every > 0: the preview reads x0 = x - sigma_next v, which no longer holds after the noise is added "
+                         "(a callback with preview_every = 0 — progress and cancel — works)")
+    return plan
 
 
 def context_windows(T, frames, overlap):
@@ -389,7 +458,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
              context_text=None, nag_text_embeds=None, nag_text_rope_pos=None, nag_scale=None, nag_tau=2.5, nag_alpha=0.25,
              region_text_embeds=None, region_text_rope_pos=None, region_masks=None, region_base_weight=0.0,
              guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0, cfg_rescale=0.0,
-             slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block"):
+             slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0, sde_interval=None, sde_seed=None):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -452,7 +521,19 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     c and u, the skip term is added after them — or c alone at guidance 1).  No blocks, scale 0 or an interval without a step is off and
     nothing changes.  A `strength < 1` run cuts the mask with the schedule.  ValueError, before anything runs: bad indices, scale or mode;
     together with MagCache, context windows or a CFG pair; at a wrapped model without `forward_skip`.  The values commonly quoted for other
-    models (blocks 9, 10 at scale 3 on 0.2 <= sigma <= 0.99) are examples: no Kandinsky checkpoint was at hand, visual quality is not claimed."""
+    models (blocks 9, 10 at scale 3 on 0.2 <= sigma <= 0.99) are examples: no Kandinsky checkpoint was at hand, visual quality is not claimed.
+    `eta`, `s_noise`, `sde_interval`, `sde_seed` (optional, extension): stochastic sampling ("euler ancestral" for rectified flow).  On the
+    steps with lo <= sigma_i <= hi of `sde_interval` (None = every step) the Euler step goes only to sigma_down = t (1 + (t / s - 1) eta) and
+    the latent is re-noised to t = sigma_{i+1}: x = a x + c z with a = (1 - t) / (1 - sigma_down), c = s_noise sqrt(t^2 - (sigma_down a)^2)
+    (`stochastic_plan`); the last step, which ends at 0, never is.  z comes from a counter-based generator inside the update kernel: element
+    g of step i is a pure function of (`sde_seed`, i, g) (`sde_seed` None = `seed`), so a run repeats exactly, a captured step replays and
+    the ranks of a group or a CFG pair draw the same bits without an exchange.  eta 0 (default), or an interval that holds no step, is off
+    and nothing changes.  A `strength < 1` run cuts the plan with the schedule; with batch > 1 the samples run one at a time, sample b with
+    seed sde_seed + b.  The engine-backed model runs it inside its loop (`DiffusionTransformer3D.set_stochastic`, set for this call and
+    removed afterwards), any other model through the same kernel from the per-step loop: the same bits.  ValueError, before anything runs:
+    eta outside [0, 1], a negative or non-finite s_noise, a bad interval; together with context windows, MagCache or preview_every > 0
+    (the preview's x0 = x - sigma v does not hold after the noise; a callback without previews works).  No checkpoint was at hand, visual
+    quality is not claimed."""
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
         raise ValueError(f"shape[0] = {shape[0]} frames do not divide into batch={batch} samples")
@@ -471,7 +552,9 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     windowed = plan is not None and len(plan[1]) > 1
     wants_guide = any(v is not None for v in guide_kw[:2]) or any(guide_kw[2:])
     wants_skip = slg_blocks is not None or slg_scale or slg_interval is not None
-    if wants_guide or wants_skip:   # the schedule as `_generate_one` draws it: the same bits
+    sto = None
+    wants_sto = bool(eta) or sde_interval is not None or float(s_noise) != 1.0
+    if wants_guide or wants_skip or wants_sto:   # the schedule as `_generate_one` draws it: the same bits
         sigmas = sigma_schedule(num_steps, scheduler_scale, device=device).cpu().tolist()
     if wants_guide:
         guide = _guidance_for_run(model, sigmas, first, guidance_weight, *guide_kw, init_latent, windowed)
@@ -480,6 +563,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         if skip is not None and not (type(model) is DiffusionTransformer3D or hasattr(model, "forward_skip")):
             raise ValueError("slg_blocks needs a model with forward_skip (the engine-backed DiffusionTransformer3D has it): the skip branch runs "
                              "inside its forward, a wrapped callable without one cannot take it")
+    if wants_sto:
+        sto = _stochastic_for_run(model, sigmas, first, eta, s_noise, sde_interval, seed if sde_seed is None else sde_seed, windowed, preview_every)
     if region_text_embeds is not None and windowed:
         raise ValueError("region_text_embeds together with context windows is not supported: the masks cover the clip, a window sees a slice")
     with _skip_for_call(model, skip), _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
@@ -497,18 +582,18 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
                    null_text_rope_pos, guidance_weight, scheduler_scale, conf, watch)
             what = (context, visual_cond, visual_cond_mask, init_latent, strength, keep_mask)
             if batch > 1:
-                return _generate_batch(*run, batch, *what, guide=guide, skip=skip)
-            return _generate_one(*run, plan, *what, guide=guide, skip=skip)
+                return _generate_batch(*run, batch, *what, guide=guide, skip=skip, sto=sto)
+            return _generate_one(*run, plan, *what, guide=guide, skip=skip, sto=sto)
         finally:
             watch.close()
 
 
 def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                   guidance_weight, scheduler_scale, conf, watch, plan, context, visual_cond, visual_cond_mask, init_latent, strength,
-                  keep_mask, guide=None, skip=None):
+                  keep_mask, guide=None, skip=None, sto=None):
     """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch`, the checked `plan` of
-    `_context_plan`, the checked guidance plan `guide` of `_guidance_for_run` and the checked skip set `skip` of `_skip_for_run` (installed on
-    the model by `generate`); returns the latent."""
+    `_context_plan`, the checked guidance plan `guide` of `_guidance_for_run`, the checked skip set `skip` of `_skip_for_run` (installed on
+    the model by `generate`) and the checked stochastic plan `sto` of `_stochastic_for_run`; returns the latent."""
     context_text = context[2]
     if plan is not None:
         F, starts, weights = plan
@@ -547,7 +632,8 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     exchange = cfg_parallel is not None and cfg_on and getattr(model, "_cfg_pair", None) is None
     if not exchange and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False):
         # whole loop inside the engine: no per-step host work at all
-        with model.setting_for_call("watch", watch.watch_args()), model.setting_for_call("guidance", guide):
+        with model.setting_for_call("watch", watch.watch_args()), model.setting_for_call("guidance", guide), \
+                model.setting_for_call("stochastic", sto):
             model.sample(img, timesteps.tolist(), text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                          null_text_rope_pos, guidance_weight, scale_factor=conf.metrics.scale_factor,
                          sparse_params=sparse_params,
@@ -614,6 +700,15 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         wants_preview = watch.active and watch.preview_at(i, n)
         if i < g_zero_init:
             v, u = (torch.zeros(img.shape, dtype=torch.bfloat16, device=img.device) if wants_preview else None), None   # velocity 0: x0 = x
+        elif sto is not None:   # a step of a stochastic run: the velocity of its kind, then the one update that also draws the noise
+            is_skip = skip is not None and bool(skip[3][i])
+            t1000 = torch.tensor([timestep]) * 1000
+            (v, u, sv) = skip_velocities(t1000, guided) if is_skip else (*velocities(t1000, guided), None)
+            ab = E.guidance_coeffs(v, u, w, g_zero_star, g_rescale)[0] if guided and (g_zero_star or g_rescale > 0.0) else None
+            km = None if edit is None else edit[2]
+            E.stochastic_euler_(img, v, u, w, sto[0][i], sto[1][i], sto[2][i], sto[3], sto[4] + i, v_skip=sv, g=skip[1] if is_skip else 0.0,
+                                ab=ab, source=None if km is None else edit[0], noise=None if km is None else edit[1], keep_mask=km,
+                                sigma_next=sigma_next)
         elif skip is not None and skip[3][i]:   # a skip step: three velocities, the skip term added after the step's own combine
             v, u, sv = skip_velocities(torch.tensor([timestep]) * 1000, guided)
             ab = E.guidance_coeffs(v, u, w, g_zero_star, g_rescale)[0] if guided and (g_zero_star or g_rescale > 0.0) else None
@@ -652,7 +747,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
 
 def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                     guidance_weight, scheduler_scale, conf, watch, batch, context, visual_cond, visual_cond_mask, init_latent, strength,
-                    keep_mask, guide=None, skip=None):
+                    keep_mask, guide=None, skip=None, sto=None):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
     T = img.shape[0] // batch
     tes, nes = split_per_sample(text_embeds, batch, "text_embeds"), split_per_sample(null_text_embeds, batch, "null_text_embeds")
@@ -662,7 +757,7 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         if v is not None and v.shape[0] != img.shape[0]:
             raise ValueError(f"{n} must have {img.shape[0]} frames (batch={batch} x {T}), got {v.shape[0]}")
 
-    if init_latent is None and context[0] is None and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) \
+    if sto is None and init_latent is None and context[0] is None and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) \
             and model.many_ready() and getattr(model, "_cfg_parallel", None) is None:
         cond = _conditioning(model, img, visual_cond, visual_cond_mask)
         if cond is not None:
@@ -683,7 +778,8 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         plan = _context_plan(model, T, *context, src, watch.every)
         watch.sample = b
         img[rows] = _generate_one(model, device, img[rows].clone(), num_steps, tes[b], nes[b], visual_rope_pos, tps[b], nps[b], guidance_weight,
-                                  scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide, skip=skip)
+                                  scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide, skip=skip,
+                                  sto=None if sto is None else (*sto[:3], (sto[3] + b) & (2 ** 64 - 1), sto[4]))   # a seed per sample
     return img
 
 
@@ -726,7 +822,8 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                     callback=None, preview_every=0, preview_factors=None, context_frames=None, context_overlap=None,
                     nag_scale=None, nag_tau=2.5, nag_alpha=0.25, region_text_embeds=None, region_text_rope_pos=None, region_masks=None,
                     region_base_weight=0.0, guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0,
-                    cfg_rescale=0.0, slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block"):
+                    cfg_rescale=0.0, slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0,
+                    sde_interval=None, sde_seed=None):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -749,8 +846,16 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     `guidance_schedule`, `guidance_interval`, `cfg_zero_star`, `cfg_zero_init`, `cfg_rescale` (optional, extension): per-step guidance
     weights, a guidance interval, CFG-Zero* and CFG rescale, passed to `generate` (see there).  All off by default.
     `slg_blocks`, `slg_scale`, `slg_interval`, `slg_mode` (optional, extension): skip-layer guidance, passed to `generate` (see there).  Off by
-    default."""
+    default.
+    `eta`, `s_noise`, `sde_interval`, `sde_seed` (optional, extension): stochastic sampling, passed to `generate` (see there).  Off by default."""
     batch, frames, height, width, channels = shape
+    sto_kw = {}
+    if eta or sde_interval is not None or float(s_noise) != 1.0:   # before any model runs: the numbers and what the handle's state refuses
+        windowed = context_frames is not None and len(context_windows(
+            frames, context_frames, int(context_frames) // 4 if context_overlap is None else int(context_overlap))[0]) > 1
+        _stochastic_for_run(dit, [1.0, 0.5, 0.0], 0, eta, s_noise, None, seed if sde_seed is None else sde_seed, windowed, preview_every)
+        stochastic_plan([1.0, 0.0], eta, s_noise, sde_interval)   # (what depends on the schedule is checked by `generate`)
+        sto_kw = dict(eta=eta, s_noise=s_noise, sde_interval=sde_interval, sde_seed=sde_seed)
     skip_kw = {}
     if slg_blocks is not None or slg_scale or slg_interval is not None:   # before any model runs: the numbers and what the handle's state refuses
         skip_plan([1.0, 0.0], slg_interval)   # (what depends on the schedule is checked by `generate`)
@@ -860,7 +965,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         latent = generate(dit, device, (batch * frames, height, width, channels), num_steps, cond, uncond, grid,
                           text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
                           progress=progress, batch=batch, callback=callback, preview_every=preview_every,
-                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw, **guide_kw, **skip_kw)
+                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw, **guide_kw, **skip_kw, **sto_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

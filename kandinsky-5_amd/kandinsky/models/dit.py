@@ -170,6 +170,32 @@ def check_skip_args(blocks, scale, mode, steps, num_visual_blocks):
     return idx, scale, mode, steps
 
 
+def check_stochastic_args(dt_down, scale, noise_coef, seed, first_stream=0):
+    """The ValueErrors of `set_stochastic`; returns (dt_down, scale, noise_coef as lists of floats, seed as a 64-bit and first_stream as a
+    32-bit unsigned int)."""
+    try:
+        tabs = [[float(v) for v in t] for t in (dt_down, scale, noise_coef)]
+    except (TypeError, ValueError):
+        raise ValueError("stochastic: dt_down, scale and noise_coef must be sequences of numbers, one per step") from None
+    n = len(tabs[0])
+    if n < 1 or any(len(t) != n for t in tabs):
+        raise ValueError(f"stochastic: dt_down, scale and noise_coef must hold one value per step each (got {[len(t) for t in tabs]})")
+    if not all(math.isfinite(v) for t in tabs for v in t):
+        raise ValueError("stochastic: every dt_down, scale and noise_coef must be a finite number")
+    if any(v < 0.0 for v in tabs[2]):
+        raise ValueError("stochastic: noise_coef must be >= 0")
+    try:
+        seed_i, first_i = int(seed), int(first_stream)
+        ok = seed_i == seed and first_i == first_stream
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or isinstance(seed, bool):
+        raise ValueError(f"stochastic: seed and first_stream must be integers (got {seed!r}, {first_stream!r})")
+    if not 0 <= first_i <= 0xffffffff - n:
+        raise ValueError(f"stochastic: first_stream must be in 0..2^32 - 1 - num_steps (got {first_stream})")
+    return tabs[0], tabs[1], tabs[2], seed_i & (2 ** 64 - 1), first_i
+
+
 def check_nag_args(text_embeds, text_rope_pos, scale, tau, alpha):
     """The ValueErrors of `set_nag` / `generate(nag_scale=, nag_tau=, nag_alpha=, nag_text_embeds=)`; returns (scale, tau, alpha) as floats."""
     scale, tau, alpha = check_nag_numbers(scale, tau, alpha)
@@ -255,6 +281,7 @@ _SETTINGS = {
     "regions":       ("_regions",  "k5_dit_set_regions",       (None, 0, None, 0, 0, 0, 0.0)),
     "guidance":      ("_guidance", "k5_dit_set_guidance",      (None,)),
     "skip_guidance": ("_skip",     "k5_dit_set_skip_guidance", (None,)),
+    "stochastic":    ("_stochastic", "k5_dit_set_stochastic",  (None,)),
 }
 
 
@@ -311,6 +338,7 @@ class DiffusionTransformer3D(nn.Module):
         self._nag = None             # the negative prompt of set_nag and its three numbers: re-installed likewise
         self._regions = None         # the prompts, masks and base weight of set_regions: likewise
         self._skip = None            # the set of set_skip_guidance (blocks, scale, mode, steps | None): likewise
+        self._stochastic = None      # the plan of set_stochastic (dt_down, scale, noise_coef, seed, first_stream): likewise
         self._guidance = None        # the plan of set_guidance (weights list | None, zero_star, zero_init_steps, rescale): likewise
         self._borrowed = {}          # setting name -> what the live handle borrows from the stored value (structs, device copies, ctypes arrays)
 
@@ -629,7 +657,7 @@ class DiffusionTransformer3D(nn.Module):
 
     @contextlib.contextmanager
     def setting_for_call(self, name, args):
-        """Context: setting `name` ("watch", "nag", "regions", "guidance", "skip_guidance") as `set_<name>(*args)` makes it, for one call; what was
+        """Context: setting `name` ("watch", "nag", "regions", "guidance", "skip_guidance", "stochastic") as `set_<name>(*args)` makes it, for one call; what was
         stored before is installed again afterwards (the stored object itself, not a copy) or the setting is cleared, also on an exception.
         args None: nothing is touched."""
         if args is None:
@@ -785,6 +813,36 @@ class DiffusionTransformer3D(nn.Module):
         visual blocks the skip branches took from the conditional forward / ran themselves (k5_dit_skip_state).  `reset` zeroes the counts."""
         on, *counts = self._state("k5_dit_skip_state", (C.c_int,) + (C.c_longlong,) * 3, int(bool(reset)))
         return (bool(on), *counts)
+
+    # ---------------------------------------------------------------- stochastic sampling: noise from a counter-based generator inside the update
+    def set_stochastic(self, dt_down, scale, noise_coef, seed, first_stream=0):
+        """Stochastic sampling in `sample` (k5_dit_set_stochastic): step i takes `dt_down[i]` as its dt and then re-noises,
+        x = scale[i] * x + noise_coef[i] * z with z ~ N(0, 1) per element, where noise_coef[i] != 0 (`generation_utils.stochastic_plan` builds the
+        three tables from the schedule, a churn eta and a noise scale).  z is not read from anywhere: element g of step i is a pure function of
+        (`seed`, `first_stream` + i, g), computed by a Philox4x32-10 generator inside the update kernel, so a captured step replays, every rank
+        of a group and both handles of a CFG pair draw the same bits, and a run repeats exactly.  `sample` refuses, before anything runs:
+        tables of another length than its steps, `windows`, MagCache or its calibration, a watch with previews; `sample_many` refuses the
+        plan (one seed).  No checkpoint was at hand when this was built: the rule is the published one, visual quality is not claimed."""
+        return self._put("stochastic", check_stochastic_args(dt_down, scale, noise_coef, seed, first_stream))
+
+    def _marshal_stochastic(self, plan):
+        dt_down, scale, coef, seed, first = plan
+        p = E.Stochastic()
+        arrs = tuple((C.c_float * len(t))(*t) for t in (dt_down, scale, coef))    # copied by the call
+        p.num_steps = len(dt_down)
+        p.dt_down, p.scale, p.noise_coef = (C.cast(a, C.POINTER(C.c_float)) for a in arrs)
+        p.seed, p.first_stream = seed, first
+        return (C.byref(p),), arrs
+
+    def clear_stochastic(self):
+        """Remove the plan: `sample` enqueues exactly what it did before `set_stochastic`."""
+        return self._clear("stochastic")
+
+    def stochastic_state(self, reset=False):
+        """(on, noisy_steps): whether a plan is set and how many steps the engine has enqueued that drew noise (k5_dit_stochastic_state).
+        `reset` zeroes the count afterwards."""
+        on, n = self._state("k5_dit_stochastic_state", (C.c_int, C.c_longlong), int(bool(reset)))
+        return bool(on), n
 
     @torch.no_grad()
     def forward_skip(self, x, text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos,

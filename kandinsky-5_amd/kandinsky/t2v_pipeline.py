@@ -95,7 +95,8 @@ class Kandinsky5T2VPipeline:
                  preview_every: int = 0, preview_factors=None, context_seconds: float = None, context_overlap_seconds: float = None,
                  nag_scale: float = None, nag_tau: float = 2.5, nag_alpha: float = 0.25, regions=None, region_base_weight: float = 0.0,
                  guidance_schedule=None, guidance_interval=None, cfg_zero_star: bool = False, cfg_zero_init: int = 0, cfg_rescale: float = 0.0,
-                 slg_blocks=None, slg_scale: float = 0.0, slg_interval=None, slg_mode: str = "block"):
+                 slg_blocks=None, slg_scale: float = 0.0, slg_interval=None, slg_mode: str = "block", eta: float = 0.0, s_noise: float = 1.0,
+                 sde_interval=None, sde_seed: int = None):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -135,8 +136,20 @@ class Kandinsky5T2VPipeline:
         runs once more with the listed visual blocks (mode "attention": only their self-attention) skipped and the velocity is pushed away
         from that weakened prediction; see `generate`.  Off by default, every rank passes the same values.  Not together with
         `context_seconds`, MagCache or a CFG pair.  The values shown are the ones commonly quoted for other models: no Kandinsky checkpoint
-        was at hand when this was written, what they do to a picture is not claimed."""
+        was at hand when this was written, what they do to a picture is not claimed.
+        `eta`, `s_noise`, `sde_interval`, `sde_seed` (optional, extension): stochastic sampling, `pipe(text, eta=1.0)` — on the steps whose
+        sigma lies in `sde_interval` (None = all) the Euler step stops short and the latent is re-noised to the next sigma with noise
+        generated inside the update kernel from (`sde_seed`, step, element) (`sde_seed` None = `seed`); see `generate`.  eta 0 (default) is
+        off, every rank passes the same values.  Not together with `context_seconds`, MagCache or previews.  No checkpoint was at hand when
+        this was written: visual quality is not claimed."""
         ctx = {}
+        sto_kw = {}
+        if eta or sde_interval is not None or float(s_noise) != 1.0:
+            from .generation_utils import _stochastic_for_run, stochastic_plan
+            stochastic_plan([1.0, 0.0], eta, s_noise, sde_interval)
+            _stochastic_for_run(self.dit, [1.0, 0.5, 0.0], 0, eta, s_noise, None, 0 if sde_seed is None else sde_seed, context_seconds is not None,
+                                preview_every)
+            sto_kw = dict(eta=eta, s_noise=s_noise, sde_interval=sde_interval, sde_seed=sde_seed)
         skip_kw = {}
         if slg_blocks is not None or slg_scale or slg_interval is not None:
             from .generation_utils import _skip_for_run, skip_plan
@@ -212,6 +225,6 @@ class Kandinsky5T2VPipeline:
                                  device=self.device_map["dit"], vae_device=self.device_map["vae"],
                                  text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload,
                                  image=image, video=video, strength=strength, mask=mask, callback=callback,
-                                 preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw, **guide_kw, **skip_kw)
+                                 preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw, **guide_kw, **skip_kw, **sto_kw)
         torch.cuda.empty_cache()
         return self._save(images, time_length, save_path) if self.local_dit_rank == 0 else None

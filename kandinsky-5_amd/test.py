@@ -99,7 +99,43 @@ def build_parser():
                    help="with --slg_blocks: only on the steps whose sigma lies in [LO, HI] (default every step)")
     p.add_argument("--slg_mode", choices=("block", "attention"), default=argparse.SUPPRESS,
                    help="with --slg_blocks: skip the whole block (default) or only its self-attention")
+    p.add_argument("--eta", type=float, default=argparse.SUPPRESS, metavar="E",
+                   help="stochastic sampling: churn in [0, 1]; 1 re-noises every step to the next sigma (euler ancestral), 0 is the plain run")
+    p.add_argument("--s_noise", type=float, default=argparse.SUPPRESS, metavar="S", help="with --eta: scale of the added noise, >= 0 (default 1)")
+    p.add_argument("--sde_interval", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("LO", "HI"),
+                   help="with --eta: only on the steps whose sigma lies in [LO, HI] (default every step)")
+    p.add_argument("--sde_seed", type=int, default=argparse.SUPPRESS, metavar="N", help="with --eta: seed of the step noise (default: the run's seed)")
     return p
+
+
+def stochastic_keywords(args):
+    """--eta / --s_noise / --sde_interval / --sde_seed -> the pipeline's keywords"""
+    if not hasattr(args, "eta"):
+        if hasattr(args, "s_noise") or hasattr(args, "sde_interval") or hasattr(args, "sde_seed"):
+            raise ValueError("--s_noise, --sde_interval and --sde_seed need --eta")
+        return {}
+    kw = {"eta": args.eta}
+    if not 0.0 <= args.eta <= 1.0:
+        raise ValueError(f"--eta must be in [0, 1] (got {args.eta})")
+    if hasattr(args, "s_noise"):
+        if not args.s_noise >= 0.0 or args.s_noise == float("inf"):
+            raise ValueError(f"--s_noise must be a finite number >= 0 (got {args.s_noise})")
+        kw["s_noise"] = args.s_noise
+    if hasattr(args, "sde_interval"):
+        lo, hi = args.sde_interval
+        if not lo <= hi:
+            raise ValueError(f"--sde_interval needs LO <= HI (got {lo}, {hi})")
+        kw["sde_interval"] = (lo, hi)
+    if hasattr(args, "sde_seed"):
+        kw["sde_seed"] = args.sde_seed
+    if args.eta > 0.0:
+        if hasattr(args, "context_seconds"):
+            raise ValueError("--eta together with --context_seconds is not supported")
+        if getattr(args, "magcache", False) or getattr(args, "calibrate_magcache", None):
+            raise ValueError("--eta together with --magcache is not supported: the ratio table was measured on ODE trajectories")
+        if hasattr(args, "preview"):
+            raise ValueError("--eta together with --preview is not supported: the preview's x0 does not hold after the noise is added")
+    return kw
 
 
 def skip_keywords(args):
@@ -247,6 +283,7 @@ def main(argv=None):
     region_kw = region_keywords(args)
     guide_kw = guidance_keywords(args)
     skip_kw = skip_keywords(args)
+    sto_kw = stochastic_keywords(args)
     from kandinsky import get_T2V_pipeline
     pipe = get_T2V_pipeline(device_map={"dit": "cuda:0", "vae": "cuda:0", "text_embedder": "cuda:0"}, conf_path=args.config,
                             offload=args.offload, magcache=args.magcache and not args.calibrate_magcache,
@@ -285,6 +322,7 @@ def main(argv=None):
     edit_kw.update(region_kw)
     edit_kw.update(guide_kw)
     edit_kw.update(skip_kw)
+    edit_kw.update(sto_kw)
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
