@@ -269,17 +269,16 @@ int k5_patchify_cond_bf16(const float* x, const float* vcond, void* out, int T, 
 /* OutLayer un-patchify nn.py:384-399: [Ntok][4C] (c,ph,pw) -> (T,2Hp,2Wp,C) bf16. */
 int k5_unpatchify_bf16(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx,
                        const int32_t* tok_perm, void* stream);
-/* CFG combine + Euler, generation_utils.py:74-76,128.  v_uncond NULL => no guidance.  This entry, k5_cfg_euler_edit and k5_guided_euler are
- * one kernel behind one launcher: a NULL img or v_cond, or n < 1, is K5_ERR_ARG and nothing is launched. */
+/* CFG combine + Euler, generation_utils.py:74-76,128.  v_uncond NULL => no guidance.  A fixed form of k5_euler_step (the rule is written at
+ * k5_euler_step_args): img, v_cond, v_uncond, w, dt with cells = n, C = 1.  A NULL img or v_cond, or n < 1, is K5_ERR_ARG and nothing is launched. */
 int k5_cfg_euler(float* img, const void* v_cond, const void* v_uncond, float w, float dt, int64_t n,
                  void* stream);
 /* Editing kernels (added under ABI 11, as the LoRA and MagCache calibration exports were).  Flow matching: x_sigma = (1 - sigma) x0 + sigma eps.
  * k5_edit_renoise: out[i] = rn(rn(a * source[i]) + rn(sigma * noise[i])), a = fp32(1 - sigma), every operation rounded to fp32 on its own
  * (nothing contracted): the torch expression `a * x0 + sigma * eps` as separate ops, bit for bit; sigma = 1 gives noise, sigma = 0 source. */
 int k5_edit_renoise(float* out, const float* source, const float* noise, float sigma, int64_t n, void* stream);
-/* k5_cfg_euler on cells * C elements (the same bits), then the keep rule with known = renoise(sigma_next): keep_mask fp32 [cells] in
- * [0, 1], one value per C channels; m == 1 -> known, m == 0 -> the Euler result, otherwise rn(x + rn(m * rn(known - x))).  keep_mask
- * NULL = k5_cfg_euler (source / noise then unused).  One pass over the latent. */
+/* k5_cfg_euler on cells * C elements (the same bits), then the keep rule of k5_euler_step_args at sigma_next: the fixed form of k5_euler_step
+ * with source, noise and keep_mask.  keep_mask NULL = k5_cfg_euler (source / noise then unused).  One pass over the latent. */
 int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const float* source, const float* noise,
                       const float* keep_mask, float sigma_next, int64_t cells, int C, void* stream);
 /* Guidance coefficients and the guided update (added under ABI 11, as the exports above were).  The guided velocity of a
@@ -298,21 +297,14 @@ int k5_cfg_euler_edit(float* img, const void* v_cond, const void* v_uncond, floa
 int k5_guidance_stats_blocks(int64_t n);
 int k5_guidance_coeffs_bf16(const void* v_cond, const void* v_uncond, int64_t n, float w, int zero_star, float rescale, double* part,
                             double* sums, float* ab, void* stream);
-/* k5_cfg_euler_edit with the combine replaced: ab = {alpha, beta} fp32 on the DEVICE (k5_guidance_coeffs_bf16 writes it),
- * v = bf16(rn(rn(alpha c) + rn(beta u))), img = rn(img + bf16(rn(dt v))), then the keep rule of k5_cfg_euler_edit (keep_mask NULL = none; source
- * and noise are needed with a mask).  v_out (bf16 [cells * C], NULL = not wanted, may be v_cond) receives v: k5_x0_preview with v_uncond = NULL
- * on it is the preview of a guided step.  The rounding points differ from k5_cfg_euler's, so ab = {w, 1 - w} need not give its bits. */
+/* k5_cfg_euler_edit with the combine replaced by the coefficients ab = {alpha, beta}, fp32 on the DEVICE (k5_guidance_coeffs_bf16 writes them):
+ * the fixed form of k5_euler_step with ab, which this entry requires (K5_ERR_ARG without).  v_out on v_cond and then k5_x0_preview with
+ * v_uncond = NULL is the preview of a guided step.  The rounding points differ from k5_cfg_euler's, so ab = {w, 1 - w} need not give its bits. */
 int k5_guided_euler(float* img, const void* v_cond, const void* v_uncond, const float* ab, float dt, const float* source, const float* noise,
                     const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, void* stream);
 /* The three-velocity update of skip-layer guidance (added under ABI 11, as the exports above were): v_skip is the
- * conditional velocity of a forward with some visual blocks skipped (k5_dit_forward_skip), g > 0 the scale, by value.  Per element, nothing
- * contracted:
- *   base = ab ? bf16(rn(rn(ab[0] c) + rn(ab[1] u)))  (k5_guided_euler's bits)  :  v_uncond ? bf16(u + bf16(w bf16(c - u)))  (k5_cfg_euler's)  :  c
- *   d = bf16(rn(c - s)),  e = bf16(rn(g d)),  v = bf16(rn(base + e))          (torch eager `base + g * (c - s)` on bf16 tensors, bit for bit)
- *   img = rn(img + bf16(rn(dt v))), then the keep rule of k5_cfg_euler_edit (keep_mask NULL = none).
- * v_out (NULL = not wanted, may be v_cond) receives v whether or not ab is given.  The same kernel and launcher as the three entries above, a
- * further instantiation.  K5_ERR_ARG, nothing launched: a NULL img, v_cond or v_skip, g not finite or <= 0, ab without v_uncond, cells or
- * C < 1, a keep_mask without source and noise. */
+ * conditional velocity of a forward with some visual blocks skipped (k5_dit_forward_skip), g > 0 the scale, by value.  The fixed form of
+ * k5_euler_step with v_skip and skip_scale = g, which this entry requires (K5_ERR_ARG without v_skip); ab, v_uncond and v_out as there. */
 int k5_skip_euler(float* img, const void* v_cond, const void* v_uncond /* nullable */, const void* v_skip, float w,
                   const float* ab /* nullable, device */, float g, float dt, const float* source, const float* noise, const float* keep_mask,
                   float sigma_next, int64_t cells, int C, void* v_out, void* stream);
@@ -328,18 +320,55 @@ int k5_philox_words(uint32_t* out /* [nblk][4] */, uint64_t blk0, int64_t nblk, 
 int k5_noise_normal_f32(float* out, int64_t n, uint64_t seed, uint32_t stream_id, void* stream);
 /* The stochastic flow-matching step (x_sigma = (1 - sigma) x0 + sigma eps; from s to t with churn eta: sigma_down = t (1 + (t / s - 1) eta),
  * a = (1 - t) / (1 - sigma_down), c = s_noise sqrt(max(0, t^2 - (sigma_down a)^2)); kandinsky.generation_utils.stochastic_plan builds
- * dt_down = sigma_down - s, scale = a and noise_coef = c per step).  Per element, nothing contracted:
- *   v    as k5_skip_euler forms it (v_skip NULL: as k5_guided_euler with ab, else as k5_cfg_euler)
- *   x1 = rn(img + bf16(rn(dt_down v)))
- *   x2 = noise_coef != 0 ? rn(rn(scale x1) + rn(noise_coef z)) : x1,   z = noise ? noise[g] : k5_noise_normal_f32(seed, stream_id)[g]
- *   img = the keep rule of k5_cfg_euler_edit on x2 at sigma_next (keep_mask NULL = none; eps is the edit's noise, not z).
- * noise_coef == 0 gives the bits of the matching entry above.  The same kernel and launcher, one more instantiation: a thread owns the four
- * elements of one generator block.  K5_ERR_ARG, nothing launched: what k5_skip_euler refuses (g == 0 goes with v_skip NULL), a scale or
- * noise_coef that is not finite, noise_coef < 0. */
+ * dt_down = sigma_down - s, scale = a and noise_coef = c per step).  The fixed form of k5_euler_step with stochastic = 1, always (noise_coef == 0
+ * included): dt = dt_down, skip_scale = g, noise = eps (the edit's noise), znoise = noise. */
 int k5_stochastic_euler(float* img, const void* v_cond, const void* v_uncond /* nullable */, const void* v_skip /* nullable */, float w,
                         const float* ab /* nullable, device */, float g, float dt_down, const float* source, const float* eps,
                         const float* keep_mask, float sigma_next, int64_t cells, int C, void* v_out, float scale, float noise_coef,
                         const float* noise /* nullable, device fp32 [cells * C] */, uint64_t seed, uint32_t stream_id, void* stream);
+/* The sampler's update of one step, one pass over the latent (added under ABI 11, as the exports above were): the one
+ * entry, of which k5_cfg_euler, k5_cfg_euler_edit, k5_guided_euler, k5_skip_euler and k5_stochastic_euler are fixed forms.  A zeroed struct
+ * with w = 1, C = 1 and scale = 1 is the starting point; every pointer is device memory and NULL where it says "NULL =".  Per element g of
+ * cells * C, with c, u, s the bf16 values of v_cond, v_uncond, v_skip, every operation rounded on its own (nothing contracted):
+ *   base = ab ? bf16(rn(rn(ab[0] c) + rn(ab[1] u)))  :  v_uncond ? bf16(u + bf16(w bf16(c - u)))  :  c
+ *          (ab = {alpha, beta} fp32, written by k5_guidance_coeffs_bf16; the middle form is generation_utils.py:74-76, v_uncond NULL = no guidance)
+ *   v    = v_skip ? bf16(rn(base + e)), d = bf16(rn(c - s)), e = bf16(rn(skip_scale d))  :  base
+ *          (torch eager `base + g * (c - s)` on bf16 tensors, bit for bit; skip_scale > 0 goes with v_skip, 0 with NULL)
+ *   x1   = rn(img + bf16(rn(dt v)))                                              (generation_utils.py:128; a stochastic step passes its dt_down)
+ *   x2   = stochastic && noise_coef != 0 ? rn(rn(scale x1) + rn(noise_coef z))  :  x1
+ *          (z = znoise ? znoise[g] : k5_noise_normal_f32(seed, stream_id)[g]; stochastic with noise_coef == 0 gives the bits of the plain form)
+ *   img  = keep_mask ? keep rule(x2)  :  x2
+ *          (keep_mask fp32 [cells] in [0, 1], one value per C channels; known = rn(rn((1 - sigma_next) source) + rn(sigma_next noise)), k5_edit_renoise's
+ *          bits; m == 1 -> known, m == 0 -> x2, otherwise rn(x2 + rn(m rn(known - x2))); `noise` is the edit's eps, not z)
+ * v_out (bf16 [cells * C], NULL = not wanted, may be v_cond) receives v; it goes with ab or v_skip.  `stochastic` != 0 selects the
+ * instantiation in which a thread owns the four elements of one generator block.
+ * K5_ERR_ARG with a message that names the condition, nothing launched: a NULL args, img or v_cond; cells or C < 1; ab without v_uncond;
+ * v_out without ab or v_skip; keep_mask without source and noise; v_skip without a finite skip_scale > 0, a skip_scale != 0 without v_skip;
+ * stochastic with a scale that is not finite or a noise_coef that is negative or not finite; znoise without stochastic. */
+typedef struct k5_euler_step_args {
+  float* img;              /* fp32 [cells * C], updated in place */
+  const void* v_cond;
+  const void* v_uncond;    /* NULL = no guidance */
+  const void* v_skip;      /* NULL = no skip term */
+  void* v_out;             /* NULL = not wanted */
+  const float* ab;         /* NULL = the CFG combine with w */
+  float w;
+  float dt;
+  float skip_scale;
+  const float* source;
+  const float* noise;
+  const float* keep_mask;  /* NULL = no keep rule */
+  float sigma_next;
+  int64_t cells;
+  int C;
+  int stochastic;
+  float scale;
+  float noise_coef;
+  const float* znoise;     /* NULL = the generator's normals */
+  uint64_t seed;
+  uint32_t stream_id;
+} k5_euler_step_args;
+int k5_euler_step(const k5_euler_step_args* args, void* stream);
 /* k5_cfg_euler over temporal context windows (added under ABI 11, as the exports above were): a clip of T frames whose velocities come from
  * nwin <= 64 windows of F frames.  img fp32 [T][frame_elems]; v_cond / v_uncond (NULL = no guidance) bf16 [nwin][F][frame_elems]; starts_dev
  * DEVICE int32 [nwin], window i covers frames starts[i] .. starts[i] + F - 1; weights_dev DEVICE fp32 [nwin][F], the share of window i's local
@@ -627,7 +656,7 @@ int k5_dit_guidance_state(k5_dit* dit, int* on, long long* guided_steps, long lo
 /* Skip-layer guidance on the handle (added under ABI 11, as the exports above were): at a skip step the model runs once
  * more with the listed visual blocks disabled (mode 0: the block is the identity on the visual stream; mode 1: only its self-attention residual
  * is dropped, its cross-attention and feed-forward run) and the step's velocity is pushed away from that weakened prediction,
- *   v = v_cfg + scale * (c - c_skip)                                              (k5_skip_euler has the rounding points)
+ *   v = v_cfg + scale * (c - c_skip)                                              (k5_euler_step_args has the rounding points)
  * with v_cfg what the step would otherwise use (CFG, the guidance plan's coefficients, or c alone at guidance 1; a plan's statistics are over c
  * and u as always, the skip term is added after them).  The skip branch is the conditional forward up to the first listed block k0, so it
  * is not run from the start: k5_dit_forward_skip is ONE conditional forward that copies its visual stream (this rank's rows, bf16) aside when
@@ -659,7 +688,7 @@ int k5_dit_skip_state(k5_dit* dit, int* on, long long* skip_steps, long long* bl
  * branch's.  K5_ERR_STATE without a skip set on the handle (a set with scale 0 still forks here), with MagCache or its calibration. */
 int k5_dit_forward_skip(k5_dit* dit, const k5_forward_args* args, void* out_velocity, void* out_velocity_skip, void* stream);
 
-/* Stochastic sampling on the handle (added under ABI 11, as the exports above were; the rule is written at k5_stochastic_euler): while a plan is
+/* Stochastic sampling on the handle (added under ABI 11, as the exports above were; the rule is written at k5_euler_step_args): while a plan is
  * set, step i of k5_sample / k5_sample_cond / k5_sample_edit takes dt_down[i] as its dt and applies k5_stochastic_euler's kernel with scale[i],
  * noise_coef[i] and stream id first_stream + i; the time the forwards see is unchanged.  The noise is generated inside the update kernel: no
  * launch is added, a zero-init step of a guidance plan still does nothing, and the launch sequence does not depend on noise_coef, so the captured

@@ -468,6 +468,34 @@ int k5_stochastic_euler(float* img, const void* v_cond, const void* v_uncond, co
   return ret(st, "k5_stochastic_euler");
 }
 
+// The words for what k5_launch_euler_step refused: the launcher decides, this only names the condition among those a caller of the public
+// struct can reach (the message of k5_euler_step).
+static const char* euler_step_refusal(const k5_euler_step_args& a) {
+  if (!a.img) return "img is NULL";
+  if (!a.v_cond) return "v_cond is NULL";
+  if (a.cells < 1 || a.C < 1) return "cells and C must be >= 1";
+  if (a.ab && !a.v_uncond) return "ab needs v_uncond";
+  if (a.v_out && !a.ab && !a.v_skip) return "v_out needs ab or v_skip";
+  if (a.keep_mask && (!a.source || !a.noise)) return "keep_mask needs source and noise";
+  if (a.v_skip && !(a.skip_scale > 0.0f && __builtin_isfinite(a.skip_scale))) return "v_skip needs a finite skip_scale > 0";
+  if (!a.v_skip && a.skip_scale != 0.0f) return "a skip_scale != 0 needs v_skip";
+  if (a.stochastic && !__builtin_isfinite(a.scale)) return "stochastic needs a finite scale";
+  if (a.stochastic && !(a.noise_coef >= 0.0f && __builtin_isfinite(a.noise_coef))) return "stochastic needs a finite noise_coef >= 0";
+  if (!a.stochastic && a.znoise) return "znoise needs stochastic";
+  return "refused by the launcher";
+}
+
+int k5_euler_step(const k5_euler_step_args* args, void* stream) {
+  if (!args) { k5_set_error("k5_euler_step: args is NULL"); return K5_ERR_ARG; }
+  const int st = k5_launch_euler_step(K5EulerStepArgs(*args, (hipStream_t)stream));
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_euler_step: %s (cells %lld, C %d, skip_scale %g, scale %g, noise_coef %g)", euler_step_refusal(*args), (long long)args->cells,
+                 args->C, (double)args->skip_scale, (double)args->scale, (double)args->noise_coef);
+    return st;
+  }
+  return ret(st, "k5_euler_step");
+}
+
 int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts_dev,
                          const float* weights_dev, int nwin, int F, int T, int64_t frame_elems, void* stream) {
   if (!img || !v_cond || !starts_dev || !weights_dev || nwin < 1 || nwin > 64 || F < 1 || T < 1 || frame_elems < 1) {

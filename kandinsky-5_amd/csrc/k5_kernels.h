@@ -173,32 +173,18 @@ int k5_launch_patchify_cond(const float* x, const float* vcond, void* out, int T
 // un-patchify (K17 tail): [Ntok][C*4] bf16 (feature order c,ph,pw) -> (T,H,W,C) bf16, token perm optional
 int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx,
                          const int32_t* tok_perm, hipStream_t stream);
-// K18: the sampler's update of one step on cells * C elements, one pass over img.  The velocity: v = cond (bf16) when v_uncond is null, else
-// bf16(u + bf16(w * bf16(c - u))) (CFG), or with ab = {alpha, beta} fp32 on the device (k5_launch_guidance_coeffs writes it)
-// bf16(rn(rn(alpha c) + rn(beta u))).  The step: img += float(bf16(dt * v)).  The keep rule (keep_mask fp32 [cells], null = none): with
-// known = rn(rn((1 - sigma_next) source) + rn(sigma_next noise)) the cells of mask 1 take known, those of mask 0 keep the Euler result and the
-// others x + m * (known - x), nothing contracted.  v_out (bf16 [cells * C], may be v_cond) receives v.  dtvec / signext / step: the captured step
-// reads dt (and, when signext is given, sigma_next) at the device step counter.
-// K5_ERR_ARG: img or v_cond null, cells or C < 1, ab without v_uncond, v_out without ab, keep_mask without source and noise, dtvec without step
-// or step without dtvec, signext without dtvec.  Nothing is launched when it refuses.
-// Skip-layer guidance (v_skip bf16 [cells * C], skip_scale g by value): with the velocity above as base, d = bf16(c - s), e = bf16(g d),
-// v = bf16(base + e) — torch eager `base + g * (c - s)` on bf16 tensors — and v_out receives v with or without ab.  K5_ERR_ARG: v_skip without
-// g > 0, a g that is not finite or is negative, a g without v_skip.
-// The stochastic step (stochastic = true; dt is then the step's dt_down): x1 = the update above, x2 = rn(rn(scale x1) + rn(noise_coef z)) when
-// noise_coef != 0 and x1 when it is 0, then the keep rule.  z = znoise[g] (fp32 [cells * C]) or, znoise null, normal g & 3 of Philox block g >> 2
-// of (seed, stream_id) — k5_launch_noise_normal's bits.  ab, v_skip and v_out are taken at run time, as in the skip step.  scalevec / coefvec
-// (both or neither, with step): the captured step reads scale and noise_coef at the step counter and draws from stream stream_id + *step.
-// K5_ERR_ARG: a scale or noise_coef that is not finite, noise_coef < 0, znoise / scalevec / coefvec without stochastic.
-struct K5EulerStepArgs {
-  float* img = nullptr; const void* v_cond = nullptr; const void* v_uncond = nullptr;
-  float w = 1.f; const float* ab = nullptr; float dt = 0.f;
-  const float* source = nullptr; const float* noise = nullptr; const float* keep_mask = nullptr; float sigma_next = 0.f;
-  int64_t cells = 0; int C = 1; void* v_out = nullptr;
+// K18: the sampler's update of one step on cells * C elements, one pass over img.  The rule, field by field, is written once, at
+// k5_euler_step_args in include/k5.h; K5EulerStepArgs is that struct (w = 1, C = 1, scale = 1, the rest zero) plus what only the engine sets:
+// dtvec / signext / step — the captured step reads dt (and, when signext is given, sigma_next) at the device step counter — scalevec / coefvec
+// (both or neither, with step) — it reads scale and noise_coef there and draws from stream stream_id + *step — and the stream.
+// K5_ERR_ARG, nothing launched: what k5_euler_step_args lists, and dtvec without step or step without dtvec, signext without dtvec,
+// scalevec / coefvec one without the other, without step or without stochastic.
+struct K5EulerStepArgs : k5_euler_step_args {
   const float* dtvec = nullptr; const float* signext = nullptr; const int* step = nullptr;
-  const void* v_skip = nullptr; float skip_scale = 0.f;
-  bool stochastic = false; float scale = 1.f, noise_coef = 0.f; const float* znoise = nullptr; uint64_t seed = 0; uint32_t stream_id = 0;
   const float* scalevec = nullptr; const float* coefvec = nullptr;
   hipStream_t stream = nullptr;
+  K5EulerStepArgs() : k5_euler_step_args{} { w = 1.f; C = 1; scale = 1.f; }
+  K5EulerStepArgs(const k5_euler_step_args& pub, hipStream_t s) : k5_euler_step_args(pub), stream(s) {}
 };
 int k5_launch_euler_step(const K5EulerStepArgs& a);
 // Philox4x32-10 raw words: out [nblk][4] of blocks blk0 .. blk0 + nblk - 1 (mod 2^64) under key = seed and counter words 2 / 3 = c2 / c3

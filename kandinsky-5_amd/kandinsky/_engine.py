@@ -125,6 +125,16 @@ class Stochastic(C.Structure):
                 ("noise_coef", C.POINTER(C.c_float)), ("seed", C.c_uint64), ("first_stream", C.c_uint32)]
 
 
+class EulerStep(C.Structure):
+    """k5_euler_step_args: the sampler's update of one step, field for field (every pointer is device memory)."""
+    _fields_ = [("img", C.c_void_p), ("v_cond", C.c_void_p), ("v_uncond", C.c_void_p), ("v_skip", C.c_void_p), ("v_out", C.c_void_p),
+                ("ab", C.c_void_p), ("w", C.c_float), ("dt", C.c_float), ("skip_scale", C.c_float),
+                ("source", C.c_void_p), ("noise", C.c_void_p), ("keep_mask", C.c_void_p), ("sigma_next", C.c_float),
+                ("cells", C.c_int64), ("C", C.c_int),
+                ("stochastic", C.c_int), ("scale", C.c_float), ("noise_coef", C.c_float), ("znoise", C.c_void_p), ("seed", C.c_uint64),
+                ("stream_id", C.c_uint32)]
+
+
 class VaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int), ("out_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -222,6 +232,7 @@ SYMBOLS = {
     "k5_philox_words": (_I, [_P, C.c_uint64, _I64, C.c_uint64, C.c_uint32, C.c_uint32, _P]),
     "k5_noise_normal_f32": (_I, [_P, _I64, C.c_uint64, C.c_uint32, _P]),
     "k5_stochastic_euler": (_I, [_P, _P, _P, _P, _F, _P, _F, _F, _P, _P, _P, _F, _I64, _I, _P, _F, _F, _P, C.c_uint64, C.c_uint32, _P]),
+    "k5_euler_step": (_I, [C.POINTER(EulerStep), _P]),
     "k5_dit_set_stochastic": (_I, [_P, C.POINTER(Stochastic)]),
     "k5_dit_stochastic_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), _I]),
     "k5_cfg_euler_windows": (_I, [_P, _P, _P, _F, _F, _P, _P, _I, _I, _I, _I64, _P]),
@@ -491,10 +502,59 @@ def gemv_f32(x, w, b=None, silu_in=False, add=None):
     return y
 
 
+def _check_step(name, img, v_cond, v_uncond=None, v_skip=None, v_out=None, ab=None, source=None, noise=None, keep_mask=None, z=None, need=()):
+    """The checks that every wrapper of the sampler's update shares, raised under the wrapper's `name`: img, source, noise and z contiguous fp32
+    tensors of one size, the velocities contiguous bf16 tensors of that size, ab fp32 [2], a keep_mask with one value per cell together with
+    source and noise, v_cond and the tensors named in `need` given, all of them on one device, which is a GPU.  Returns (cells, C) of an img
+    (..., C)."""
+    given = dict(v_cond=v_cond, v_uncond=v_uncond, v_skip=v_skip, v_out=v_out, ab=ab, source=source, noise=noise, keep_mask=keep_mask, z=z)
+    C_ = img.shape[-1]
+    cells = img.numel() // C_
+    for t in (img, source, noise, z):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != img.numel()):
+            raise ValueError(f"{name}: img, source, noise and z must be contiguous fp32 tensors of one size")
+    for v in (v_cond, v_uncond, v_skip, v_out):
+        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != img.numel()):
+            raise ValueError(f"{name}: the velocities must be contiguous bf16 tensors of img's size")
+    missing = [k for k in ("v_cond",) + tuple(need) if given[k] is None]
+    if missing:
+        raise ValueError(f"{name}: this update needs {' and '.join(missing)}")
+    if ab is not None and (ab.dtype != torch.float32 or ab.numel() != 2 or not ab.is_contiguous()):
+        raise ValueError(f"{name}: ab must be a contiguous fp32 [2] tensor on the device")
+    if keep_mask is not None and (source is None or noise is None or keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous()
+                                  or keep_mask.numel() != cells):
+        raise ValueError(f"{name}: keep_mask must be a contiguous fp32 tensor with one value per cell and needs source and noise")
+    if any(t is not None and t.device != img.device for t in given.values()):
+        raise ValueError(f"{name}: img and every other tensor must be on one device")
+    _need_cuda(img)
+    return cells, C_
+
+
+def euler_step_(img, v_cond, v_uncond=None, *, w=1.0, dt, ab=None, v_skip=None, g=0.0, source=None, noise=None, keep_mask=None, sigma_next=0.0,
+                v_out=None, stochastic=None):
+    """The sampler's update of one step, in place on img fp32 (..., C) (k5_euler_step; the rule is written at k5_euler_step_args in
+    include/k5.h).  The velocity: v_cond itself, with v_uncond the CFG combine at weight w or, with ab (fp32 [2] on the device, from
+    `guidance_coeffs`), ab[0] v_cond + ab[1] v_uncond; with v_skip, + g (v_cond - v_skip).  img += bf16(dt v).  stochastic = (scale, noise_coef,
+    seed, stream_id[, z]): then, where noise_coef != 0, img = scale img + noise_coef z with z the fp32 tensor `z` or, without one, the
+    generator's normals of (seed, stream_id) — `noise_normal_`'s bits; dt is then the step's dt_down.  Last, with a keep_mask (fp32 (..., 1), with
+    source and noise, the edit's eps), the keep rule at sigma_next.  v_out (bf16 of img's size, may be v_cond; with ab or v_skip) receives v.
+    The five wrappers below are fixed forms of this call."""
+    scale, noise_coef, seed, stream_id, z = (1.0, 0.0, 0, 0, None) if stochastic is None else (*stochastic, None)[:5]
+    cells, C_ = _check_step("euler_step_", img, v_cond, v_uncond, v_skip, v_out, ab, source, noise, keep_mask, z)
+    a = EulerStep(img=ptr(img), v_cond=ptr(v_cond), v_uncond=ptr(v_uncond), v_skip=ptr(v_skip), v_out=ptr(v_out), ab=ptr(ab), w=float(w),
+                  dt=float(dt), skip_scale=float(g), source=ptr(source), noise=ptr(noise), keep_mask=ptr(keep_mask), sigma_next=float(sigma_next),
+                  cells=cells, C=C_, stochastic=int(stochastic is not None), scale=float(scale), noise_coef=float(noise_coef), znoise=ptr(z),
+                  seed=int(seed) & (2 ** 64 - 1), stream_id=int(stream_id) & 0xffffffff)
+    with torch.cuda.device(img.device):
+        check(lib().k5_euler_step(C.byref(a), stream_ptr(img.device)), "k5_euler_step")
+    return img
+
+
 def cfg_euler_(img, v_cond, v_uncond, w, dt):
-    _need_cuda(img, v_cond, v_uncond)
-    check(lib().k5_cfg_euler(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), img.numel(),
-                             stream_ptr(img.device)), "k5_cfg_euler")
+    """euler_step_(img, v_cond, v_uncond, w=w, dt=dt) through its own entry (k5_cfg_euler)."""
+    _check_step("cfg_euler_", img, v_cond, v_uncond)
+    with torch.cuda.device(img.device):
+        check(lib().k5_cfg_euler(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), img.numel(), stream_ptr(img.device)), "k5_cfg_euler")
     return img
 
 
@@ -542,16 +602,10 @@ def renoise(source, noise, sigma, out=None):
 def cfg_euler_edit_(img, v_cond, v_uncond, w, dt, source, noise, keep_mask, sigma_next):
     """cfg_euler_ followed by the keep rule at sigma_next (k5_cfg_euler_edit): img, source, noise fp32 (..., C), keep_mask fp32 (..., 1) or
     None (= cfg_euler_)."""
-    _need_cuda(img, v_cond, v_uncond, source, noise, keep_mask)
-    C_ = img.shape[-1]
-    cells = img.numel() // C_
-    for t in (img, source, noise):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != img.shape:
-            raise ValueError("cfg_euler_edit_: img, source and noise must be contiguous fp32 tensors of one shape")
-    if keep_mask is not None and (keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous() or keep_mask.numel() != cells):
-        raise ValueError("cfg_euler_edit_: keep_mask must be a contiguous fp32 tensor with one value per cell")
-    check(lib().k5_cfg_euler_edit(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), ptr(source), ptr(noise), ptr(keep_mask),
-                                  float(sigma_next), cells, C_, stream_ptr(img.device)), "k5_cfg_euler_edit")
+    cells, C_ = _check_step("cfg_euler_edit_", img, v_cond, v_uncond, source=source, noise=noise, keep_mask=keep_mask)
+    with torch.cuda.device(img.device):
+        check(lib().k5_cfg_euler_edit(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), ptr(source), ptr(noise), ptr(keep_mask),
+                                      float(sigma_next), cells, C_, stream_ptr(img.device)), "k5_cfg_euler_edit")
     return img
 
 
@@ -579,25 +633,8 @@ def guidance_coeffs(v_cond, v_uncond, w, zero_star=False, rescale=0.0, ab=None, 
 
 
 def guided_euler_(img, v_cond, v_uncond, ab, dt, source=None, noise=None, keep_mask=None, sigma_next=0.0, v_out=None):
-    """The update of a guided step with coefficients from the device (k5_guided_euler): v = bf16(ab[0] * v_cond + ab[1] * v_uncond),
-    img += bf16(dt * v), then with a keep_mask the keep rule of cfg_euler_edit_ at sigma_next.  v_out (bf16 of img's size, may be v_cond)
-    receives v."""
-    _need_cuda(img, v_cond, v_uncond, ab, source, noise, keep_mask, v_out)
-    C_ = img.shape[-1]
-    cells = img.numel() // C_
-    for t in (img, source, noise):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != img.shape):
-            raise ValueError("guided_euler_: img, source and noise must be contiguous fp32 tensors of one shape")
-    for v in (v_cond, v_uncond, v_out):
-        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != img.numel()):
-            raise ValueError("guided_euler_: the velocities must be contiguous bf16 tensors of img's size")
-    if v_cond is None or v_uncond is None:
-        raise ValueError("guided_euler_: a guided step has both velocities")
-    if ab.dtype != torch.float32 or ab.numel() != 2 or not ab.is_contiguous():
-        raise ValueError("guided_euler_: ab must be a contiguous fp32 [2] tensor on the device")
-    if keep_mask is not None and (source is None or noise is None or keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous()
-                                  or keep_mask.numel() != cells):
-        raise ValueError("guided_euler_: keep_mask must be a contiguous fp32 tensor with one value per cell and needs source and noise")
+    """The update of a guided step with coefficients from the device (k5_guided_euler): euler_step_ with both velocities and ab."""
+    cells, C_ = _check_step("guided_euler_", img, v_cond, v_uncond, None, v_out, ab, source, noise, keep_mask, need=("v_uncond", "ab"))
     with torch.cuda.device(img.device):
         check(lib().k5_guided_euler(ptr(img), ptr(v_cond), ptr(v_uncond), ptr(ab), float(dt), ptr(source), ptr(noise), ptr(keep_mask),
                                     float(sigma_next), cells, C_, ptr(v_out), stream_ptr(img.device)), "k5_guided_euler")
@@ -605,25 +642,8 @@ def guided_euler_(img, v_cond, v_uncond, ab, dt, source=None, noise=None, keep_m
 
 
 def skip_euler_(img, v_cond, v_uncond, v_skip, w, g, dt, ab=None, source=None, noise=None, keep_mask=None, sigma_next=0.0, v_out=None):
-    """The update of a skip-layer-guidance step (k5_skip_euler): with base = the velocity cfg_euler_ (v_uncond, w), guided_euler_ (ab) or a run
-    at guidance 1 (v_uncond None) would use, v = base + g * (v_cond - v_skip) as eager bf16 ops, img += bf16(dt * v), then with a keep_mask the
-    keep rule of cfg_euler_edit_ at sigma_next.  v_out (bf16 of img's size, may be v_cond) receives v."""
-    C_ = img.shape[-1]
-    cells = img.numel() // C_
-    for t in (img, source, noise):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape != img.shape):
-            raise ValueError("skip_euler_: img, source and noise must be contiguous fp32 tensors of one shape")
-    for v in (v_cond, v_uncond, v_skip, v_out):
-        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != img.numel()):
-            raise ValueError("skip_euler_: the velocities must be contiguous bf16 tensors of img's size")
-    if v_cond is None or v_skip is None:
-        raise ValueError("skip_euler_: a skip step has the conditional and the skip velocity")
-    if ab is not None and (ab.dtype != torch.float32 or ab.numel() != 2 or not ab.is_contiguous()):
-        raise ValueError("skip_euler_: ab must be a contiguous fp32 [2] tensor on the device")
-    if keep_mask is not None and (source is None or noise is None or keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous()
-                                  or keep_mask.numel() != cells):
-        raise ValueError("skip_euler_: keep_mask must be a contiguous fp32 tensor with one value per cell and needs source and noise")
-    _need_cuda(img, v_cond, v_uncond, v_skip, ab, source, noise, keep_mask, v_out)
+    """The update of a skip-layer-guidance step (k5_skip_euler): euler_step_ with v_skip and g."""
+    cells, C_ = _check_step("skip_euler_", img, v_cond, v_uncond, v_skip, v_out, ab, source, noise, keep_mask, need=("v_skip",))
     with torch.cuda.device(img.device):
         check(lib().k5_skip_euler(ptr(img), ptr(v_cond), ptr(v_uncond), ptr(v_skip), float(w), ptr(ab), float(g), float(dt), ptr(source),
                                   ptr(noise), ptr(keep_mask), float(sigma_next), cells, C_, ptr(v_out), stream_ptr(img.device)), "k5_skip_euler")
@@ -658,26 +678,9 @@ def noise_normal_(out, seed, stream_id=0, n=None):
 
 def stochastic_euler_(img, v_cond, v_uncond, w, dt_down, scale, noise_coef, seed, stream_id, z=None, v_skip=None, g=0.0, ab=None, source=None,
                       noise=None, keep_mask=None, sigma_next=0.0, v_out=None):
-    """The update of a stochastic step (k5_stochastic_euler): the velocity as cfg_euler_ (v_uncond, w), guided_euler_ (ab) or skip_euler_
-    (v_skip, g) forms it, img += bf16(dt_down * v), then where noise_coef != 0 img = scale * img + noise_coef * z with z the fp32 tensor `z` or,
-    z None, the generator's normals of (seed, stream_id) — noise_normal_'s bits — and last, with a keep_mask, the keep rule of cfg_euler_edit_ at
-    sigma_next (`noise` is the edit's eps).  noise_coef == 0 is the matching plain update bit for bit."""
-    C_ = img.shape[-1]
-    cells = img.numel() // C_
-    for t in (img, source, noise, z):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != img.numel()):
-            raise ValueError("stochastic_euler_: img, source, noise and z must be contiguous fp32 tensors of one size")
-    for v in (v_cond, v_uncond, v_skip, v_out):
-        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != img.numel()):
-            raise ValueError("stochastic_euler_: the velocities must be contiguous bf16 tensors of img's size")
-    if v_cond is None:
-        raise ValueError("stochastic_euler_: a step has the conditional velocity")
-    if ab is not None and (ab.dtype != torch.float32 or ab.numel() != 2 or not ab.is_contiguous()):
-        raise ValueError("stochastic_euler_: ab must be a contiguous fp32 [2] tensor on the device")
-    if keep_mask is not None and (source is None or noise is None or keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous()
-                                  or keep_mask.numel() != cells):
-        raise ValueError("stochastic_euler_: keep_mask must be a contiguous fp32 tensor with one value per cell and needs source and noise")
-    _need_cuda(img, v_cond, v_uncond, v_skip, ab, source, noise, keep_mask, v_out, z)
+    """The update of a stochastic step (k5_stochastic_euler): euler_step_ with dt = dt_down and stochastic = (scale, noise_coef, seed, stream_id,
+    z).  noise_coef == 0 is the matching plain update bit for bit."""
+    cells, C_ = _check_step("stochastic_euler_", img, v_cond, v_uncond, v_skip, v_out, ab, source, noise, keep_mask, z)
     with torch.cuda.device(img.device):
         check(lib().k5_stochastic_euler(ptr(img), ptr(v_cond), ptr(v_uncond), ptr(v_skip), float(w), ptr(ab), float(g), float(dt_down),
                                         ptr(source), ptr(noise), ptr(keep_mask), float(sigma_next), cells, C_, ptr(v_out), float(scale),

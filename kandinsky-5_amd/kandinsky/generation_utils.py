@@ -81,6 +81,19 @@ def edit_first_step(num_steps, strength):
     return int(num_steps) - run
 
 
+def _interval(name, interval):
+    """`(lo, hi)` of the keyword `name` as two floats with lo <= hi; None = every sigma."""
+    if interval is None:
+        return -math.inf, math.inf
+    try:
+        lo, hi = (float(v) for v in interval)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be (lo, hi)") from None
+    if not lo <= hi:
+        raise ValueError(f"{name} must be (lo, hi) with lo <= hi, got ({lo}, {hi})")
+    return lo, hi
+
+
 def guidance_plan(sigmas, guidance_weight, guidance_schedule=None, guidance_interval=None):
     """The per-step guidance weights of a run over `sigmas` (num_steps + 1 values, step i goes from sigmas[i] to sigmas[i + 1]): a list of
     num_steps floats.  `guidance_schedule`: a list of num_steps weights, or a callable `(i, sigma_i) -> weight`; None = `guidance_weight` at
@@ -100,15 +113,8 @@ def guidance_plan(sigmas, guidance_weight, guidance_schedule=None, guidance_inte
             raise ValueError(f"guidance_schedule holds {len(weights)} weights, the run has {n} steps")
     if not all(math.isfinite(w) for w in weights):
         raise ValueError("guidance_plan: every weight must be a finite number")
-    if guidance_interval is not None:
-        try:
-            lo, hi = (float(v) for v in guidance_interval)
-        except (TypeError, ValueError):
-            raise ValueError("guidance_interval must be (lo, hi)") from None
-        if not lo <= hi:
-            raise ValueError(f"guidance_interval must be (lo, hi) with lo <= hi, got ({lo}, {hi})")
-        weights = [w if lo <= sig[i] <= hi else 1.0 for i, w in enumerate(weights)]
-    return weights
+    lo, hi = _interval("guidance_interval", guidance_interval)
+    return [w if lo <= sig[i] <= hi else 1.0 for i, w in enumerate(weights)]
 
 
 def _guidance_for_run(model, sigmas, first, guidance_weight, guidance_schedule, guidance_interval, cfg_zero_star, cfg_zero_init, cfg_rescale,
@@ -147,14 +153,7 @@ def skip_plan(sigmas, slg_interval=None):
     n = len(sig) - 1
     if n < 1:
         raise ValueError("skip_plan: sigmas must hold num_steps + 1 >= 2 values")
-    if slg_interval is None:
-        return [1] * n
-    try:
-        lo, hi = (float(v) for v in slg_interval)
-    except (TypeError, ValueError):
-        raise ValueError("slg_interval must be (lo, hi)") from None
-    if not lo <= hi:
-        raise ValueError(f"slg_interval must be (lo, hi) with lo <= hi, got ({lo}, {hi})")
+    lo, hi = _interval("slg_interval", slg_interval)
     return [1 if lo <= sig[i] <= hi else 0 for i in range(n)]
 
 
@@ -225,14 +224,7 @@ def stochastic_plan(sigmas, eta, s_noise=1.0, interval=None):
         raise ValueError(f"eta must be in [0, 1], got {eta}")
     if not math.isfinite(s_noise) or s_noise < 0.0:
         raise ValueError(f"s_noise must be a finite number >= 0, got {s_noise}")
-    lo, hi = -math.inf, math.inf
-    if interval is not None:
-        try:
-            lo, hi = (float(v) for v in interval)
-        except (TypeError, ValueError):
-            raise ValueError("sde_interval must be (lo, hi)") from None
-        if not lo <= hi:
-            raise ValueError(f"sde_interval must be (lo, hi) with lo <= hi, got ({lo}, {hi})")
+    lo, hi = _interval("sde_interval", interval)
     f32 = torch.tensor(sig, dtype=torch.float32)
     dt = (f32[1:] - f32[:-1]).tolist()   # the engine's own fp32 difference
     dt_down, scale, coef = [], [], []
@@ -641,7 +633,8 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
                          windows=None if plan is None else (plan[1], plan[2]), window_text=None if plan is None else context_text)
         return img
 
-    # The per-step loop.  Each step takes (v_cond, v_uncond) from one of three sources, applies the matching update and calls the hook.
+    # The per-step loop.  Each step takes (v_cond, v_uncond, v_skip) from one of three sources (a windowed run: its per-window buffers), makes
+    # the one update call and calls the hook.
     def forward(x, te, tp, t1000):
         return model(x, te["text_embeds"], te["pooled_embed"], t1000, visual_rope_pos, tp, scale_factor=conf.metrics.scale_factor,
                      sparse_params=sparse_params)
@@ -650,7 +643,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         x = _model_input(model, img, cond_in)
         v = forward(x, text_embeds, text_rope_pos, t1000)
         u = forward(x, null_text_embeds, null_text_rope_pos, t1000) if guided else None
-        return v.contiguous(), None if u is None else u.contiguous()
+        return v.contiguous(), None if u is None else u.contiguous(), None
 
     def skip_velocities(t1000, guided):   # cond + skip in one forking forward, then uncond: the engine's order
         x = _model_input(model, img, cond_in)
@@ -664,7 +657,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         v = forward(_model_input(model, img, cond_in), *mine, t1000)
         if both is None:
             both = torch.empty((2,) + tuple(v.shape), dtype=v.dtype, device=v.device)
-        return exchange_velocity(v, cfg_parallel[1], out=both)
+        return (*exchange_velocity(v, cfg_parallel[1], out=both), None)
 
     def window_velocities(t1000, guided):
         # the forwards of k5_sample_windows in its order: window by window, cond then uncond, each on its own slice of the latent
@@ -679,65 +672,48 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         from .models.parallelize import exchange_velocity
         mine = (text_embeds, text_rope_pos) if cfg_parallel[0] == 0 else (null_text_embeds, null_text_rope_pos)
         both = None
-        velocities = pair_velocities
     elif plan is not None:
         st_dev, wt_dev = E.window_tables(starts, weights, img.device)
         vbuf = torch.empty((len(starts), F) + tuple(img.shape[1:]), dtype=torch.bfloat16, device=img.device)
         ubuf = torch.empty_like(vbuf) if cfg_on else None
-        velocities = window_velocities
-    else:
-        velocities = plain_velocities
 
     n = len(timesteps) - 1
+    km = None if edit is None else edit[2]
+    keep = {} if km is None else dict(source=edit[0], noise=edit[1], keep_mask=km)
     if edit is not None:
         E.renoise(edit[0], edit[1], float(timesteps[0]), out=img)
     for i, (timestep, timestep_diff, sigma_next) in enumerate(zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(),
                                                                   timesteps[1:].tolist())):
-        # the guidance plan's kind of step, as the engine's loop decides it: zero (no forward, no update), unguided (the conditional
-        # forward alone), guided; without a plan every step is of the call's one kind
-        w = guidance_weight if g_weights is None else g_weights[i]
-        guided = cfg_on if guide is None else _is_guided(w)
+        # the step's weight, kind and fork, as the engine's loop (SampleRun in engine.hip) decides them: zero (no forward, no update), unguided
+        # (the conditional forward alone), guided; without a plan every step is of the call's one kind.  A skip step forks the conditional forward
+        w_at = guidance_weight if g_weights is None else g_weights[i]
+        kind = "zero" if i < g_zero_init else "guided" if (cfg_on if guide is None else _is_guided(w_at)) else "unguided"
+        skip_at = kind != "zero" and skip is not None and bool(skip[3][i])
         wants_preview = watch.active and watch.preview_at(i, n)
-        if i < g_zero_init:
+        t1000 = torch.tensor([timestep]) * 1000
+        if kind == "zero":
             v, u = (torch.zeros(img.shape, dtype=torch.bfloat16, device=img.device) if wants_preview else None), None   # velocity 0: x0 = x
-        elif sto is not None:   # a step of a stochastic run: the velocity of its kind, then the one update that also draws the noise
-            is_skip = skip is not None and bool(skip[3][i])
-            t1000 = torch.tensor([timestep]) * 1000
-            (v, u, sv) = skip_velocities(t1000, guided) if is_skip else (*velocities(t1000, guided), None)
-            ab = E.guidance_coeffs(v, u, w, g_zero_star, g_rescale)[0] if guided and (g_zero_star or g_rescale > 0.0) else None
-            km = None if edit is None else edit[2]
-            E.stochastic_euler_(img, v, u, w, sto[0][i], sto[1][i], sto[2][i], sto[3], sto[4] + i, v_skip=sv, g=skip[1] if is_skip else 0.0,
-                                ab=ab, source=None if km is None else edit[0], noise=None if km is None else edit[1], keep_mask=km,
-                                sigma_next=sigma_next)
-        elif skip is not None and skip[3][i]:   # a skip step: three velocities, the skip term added after the step's own combine
-            v, u, sv = skip_velocities(torch.tensor([timestep]) * 1000, guided)
-            ab = E.guidance_coeffs(v, u, w, g_zero_star, g_rescale)[0] if guided and (g_zero_star or g_rescale > 0.0) else None
-            km = None if edit is None else edit[2]
-            E.skip_euler_(img, v, u, sv, w, skip[1], timestep_diff, ab, None if km is None else edit[0], None if km is None else edit[1], km,
-                          sigma_next, v_out=v if wants_preview else None)
-            u = None                   # v now holds the step's velocity (where a preview wants it)
+        elif plan is not None:         # every window's pair, then the one blend + Euler pass over the clip: a kernel of its own
+            v, u = window_velocities(t1000, kind == "guided")
+            E.cfg_euler_windows_(img, v, u, guidance_weight, timestep_diff, st_dev, wt_dev)
         else:
-            v, u = velocities(torch.tensor([timestep]) * 1000, guided)
-            if plan is not None:       # the one blend + Euler pass over the clip
-                E.cfg_euler_windows_(img, v, u, guidance_weight, timestep_diff, st_dev, wt_dev)
-            elif guided and (g_zero_star or g_rescale > 0.0):   # coefficients reduced on the device, then the update that reads them
-                ab, _ = E.guidance_coeffs(v, u, w, g_zero_star, g_rescale)
-                km = None if edit is None else edit[2]
-                E.guided_euler_(img, v, u, ab, timestep_diff, None if km is None else edit[0], None if km is None else edit[1], km, sigma_next,
-                                v_out=v if wants_preview else None)
-                u = None               # v now holds the guided velocity
-            elif edit is None:         # CFG combine + Euler on img, in place
-                E.cfg_euler_(img, v, u, w, timestep_diff)
-            else:                      # ... and the keep rule
-                E.cfg_euler_edit_(img, v, u, w, timestep_diff, edit[0], edit[1], edit[2], sigma_next)
+            v, u, sv = (skip_velocities if skip_at else pair_velocities if exchange else plain_velocities)(t1000, kind == "guided")
+            # the plan's coefficients are reduced on the device and read there; the skip term comes after them
+            ab = E.guidance_coeffs(v, u, w_at, g_zero_star, g_rescale)[0] if kind == "guided" and (g_zero_star or g_rescale > 0.0) else None
+            v_out = v if wants_preview and (ab is not None or skip_at) else None
+            # a stochastic run takes its dt_down as dt and says so at every step, also where noise_coef is 0: the engine's one launch
+            E.euler_step_(img, v, u, w=w_at, dt=timestep_diff if sto is None else sto[0][i], ab=ab, v_skip=sv, g=skip[1] if skip_at else 0.0,
+                          sigma_next=sigma_next, v_out=v_out, stochastic=None if sto is None else (sto[1][i], sto[2][i], sto[3], sto[4] + i),
+                          **keep)
+            if v_out is not None:
+                u = None               # v now holds the step's velocity, where the preview reads it
         if not watch.active:
             continue
         # the per-step paths' side of the watch: the preview of the step just applied (the engine's kernel, the engine's rule for which steps
         # carry one; never on a windowed run, whose preview_every is refused) and the callback
         preview = x0 = None
-        if watch.preview_at(i, n):
-            km = None if edit is None else edit[2]
-            rgb, x0 = E.x0_preview(img, v, u, w, sigma_next, watch.W, watch.b, source=None if km is None else edit[0],
+        if wants_preview:
+            rgb, x0 = E.x0_preview(img, v, u, w_at, sigma_next, watch.W, watch.b, source=None if km is None else edit[0],
                                    keep_mask=km, want_x0=watch.want_x0)
             preview = rgb.cpu()
         if watch.step(StepInfo(i, n, watch.sample, watch.num_samples, sigma_next, preview, x0)):
@@ -850,17 +826,18 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     `eta`, `s_noise`, `sde_interval`, `sde_seed` (optional, extension): stochastic sampling, passed to `generate` (see there).  Off by default."""
     batch, frames, height, width, channels = shape
     sto_kw = {}
-    if eta or sde_interval is not None or float(s_noise) != 1.0:   # before any model runs: the numbers and what the handle's state refuses
+    wants_sto = eta or sde_interval is not None or float(s_noise) != 1.0
+    wants_skip = slg_blocks is not None or slg_scale or slg_interval is not None
+    if wants_sto or wants_skip:   # what both pre-checks refuse together with more than one context window
         windowed = context_frames is not None and len(context_windows(
             frames, context_frames, int(context_frames) // 4 if context_overlap is None else int(context_overlap))[0]) > 1
+    if wants_sto:   # before any model runs: the numbers and what the handle's state refuses
         _stochastic_for_run(dit, [1.0, 0.5, 0.0], 0, eta, s_noise, None, seed if sde_seed is None else sde_seed, windowed, preview_every)
         stochastic_plan([1.0, 0.0], eta, s_noise, sde_interval)   # (what depends on the schedule is checked by `generate`)
         sto_kw = dict(eta=eta, s_noise=s_noise, sde_interval=sde_interval, sde_seed=sde_seed)
     skip_kw = {}
-    if slg_blocks is not None or slg_scale or slg_interval is not None:   # before any model runs: the numbers and what the handle's state refuses
+    if wants_skip:   # before any model runs: the numbers and what the handle's state refuses
         skip_plan([1.0, 0.0], slg_interval)   # (what depends on the schedule is checked by `generate`)
-        windowed = context_frames is not None and len(context_windows(
-            frames, context_frames, int(context_frames) // 4 if context_overlap is None else int(context_overlap))[0]) > 1
         _skip_for_run(dit, [1.0, 0.0], 0, slg_blocks, slg_scale, None, slg_mode, windowed)
         skip_kw = dict(slg_blocks=slg_blocks, slg_scale=slg_scale, slg_interval=slg_interval, slg_mode=slg_mode)
     guide_kw = {k: v for k, v in dict(guidance_schedule=guidance_schedule, guidance_interval=guidance_interval, cfg_zero_star=cfg_zero_star,

@@ -498,6 +498,79 @@ def test_step_update_grid_stride(E):
         assert torch.equal(cc[:n], v if alias else cd) and (cc[n:] == 3.0).all()
 
 
+# k5_euler_step against the older entries, which are fixed forms of it: what each form sets besides img, v_cond, dt and the sizes
+STEP_FORMS = {
+    "plain, unguided": dict(old="k5_cfg_euler"),
+    "plain, guided": dict(old="k5_cfg_euler", u=True),
+    "edit with a mask of 0, 1, 0.25": dict(old="k5_cfg_euler_edit", u=True, mask=True),
+    "ab, with v_out on v_cond": dict(old="k5_guided_euler", u=True, ab=True, v_out=True, mask=True),
+    "ab, without v_out": dict(old="k5_guided_euler", u=True, ab=True),
+    "skip, with ab": dict(old="k5_skip_euler", u=True, ab=True, skip=True, v_out=True, mask=True),
+    "skip, without ab": dict(old="k5_skip_euler", u=True, skip=True),
+    "skip, without v_uncond": dict(old="k5_skip_euler", skip=True, v_out=True),
+    "stochastic, with znoise": dict(old="k5_stochastic_euler", u=True, ab=True, skip=True, v_out=True, mask=True, sto="znoise"),
+    "stochastic, in-kernel noise": dict(old="k5_stochastic_euler", u=True, mask=True, sto="kernel"),
+    "stochastic, noise_coef 0": dict(old="k5_stochastic_euler", u=True, sto="zero"),
+}
+
+
+@pytest.mark.parametrize("cells,Cc,lead", [(37, 3, 0), (64, 16, 0), (64, 16, 1)])
+@pytest.mark.parametrize("form", list(STEP_FORMS))
+def test_euler_step_entry_equals_each_older_entry(E, form, cells, Cc, lead):
+    """k5_euler_step and the older entry of each form on clones of the same buffers: the same latent and v_out, bit for bit, and every buffer's
+    guard of 64 poisoned elements untouched.  n = 111 is the element-wise path of the stochastic instantiation with a ragged last generator
+    block, n = 1024 its 16-byte path, and n = 1024 with v_cond one bf16 element into its allocation the element-wise path at n % 4 == 0."""
+    import ctypes as C
+    f = dict(dict(u=False, ab=False, skip=False, v_out=False, mask=False, sto=None), **STEP_FORMS[form])
+    n, G, L, s = cells * Cc, 64, E.lib(), E.stream_ptr()
+    mask = torch.tensor([0.0, 1.0, 0.25])[torch.randint(0, 3, (cells,), generator=torch.Generator().manual_seed(6))]
+    mask[:3] = torch.tensor([0.0, 1.0, 0.25])
+    host = dict(img=rnd(n, seed=1), v_cond=rnd(n, seed=2).to(BF), v_uncond=rnd(n, seed=3).to(BF), v_skip=rnd(n, seed=4).to(BF),
+                source=rnd(n, seed=5) * 3, noise=rnd(n, seed=6), keep_mask=mask, znoise=rnd(n, seed=7), ab=torch.tensor([2.2, -1.3137]))
+    first = {k: lead if k == "v_cond" else 0 for k in host}                # v_cond may start one element into its allocation
+    poison = {k: 3.0 if v.dtype == BF else 7.0 for k, v in host.items()}
+    w, dt, sigma, g = 5.0, -0.0625 * 1.3, 0.37, 3.0 if f["skip"] else 0.0
+    scale, coef, seed, stream_id = 0.9, 0.0 if f["sto"] == "zero" else 0.4, 9, 5
+
+    def run(new):
+        b = {}
+        for k, v in host.items():
+            b[k] = torch.full((first[k] + v.numel() + G,), poison[k], dtype=v.dtype, device="cuda")
+            b[k][first[k]:first[k] + v.numel()] = v.cuda()
+        p = lambda k, on=True: b[k].data_ptr() + first[k] * b[k].element_size() if on else None   # noqa: E731
+        img, vc, vu, vs, ab = p("img"), p("v_cond"), p("v_uncond", f["u"]), p("v_skip", f["skip"]), p("ab", f["ab"])
+        src, eps, km, vo, z = p("source", f["mask"]), p("noise", f["mask"]), p("keep_mask", f["mask"]), p("v_cond", f["v_out"]), p("znoise", f["sto"] == "znoise")
+        if new:
+            a = E.EulerStep(img=img, v_cond=vc, v_uncond=vu, v_skip=vs, v_out=vo, ab=ab, w=w, dt=dt, skip_scale=g, source=src, noise=eps, keep_mask=km,
+                            sigma_next=sigma, cells=cells, C=Cc, stochastic=int(f["sto"] is not None), scale=scale if f["sto"] else 1.0,
+                            noise_coef=coef if f["sto"] else 0.0, znoise=z, seed=seed, stream_id=stream_id)
+            E.check(L.k5_euler_step(C.byref(a), s), "k5_euler_step")
+        elif f["old"] == "k5_cfg_euler":
+            E.check(L.k5_cfg_euler(img, vc, vu, w, dt, n, s), f["old"])
+        elif f["old"] == "k5_cfg_euler_edit":
+            E.check(L.k5_cfg_euler_edit(img, vc, vu, w, dt, src, eps, km, sigma, cells, Cc, s), f["old"])
+        elif f["old"] == "k5_guided_euler":
+            E.check(L.k5_guided_euler(img, vc, vu, ab, dt, src, eps, km, sigma, cells, Cc, vo, s), f["old"])
+        elif f["old"] == "k5_skip_euler":
+            E.check(L.k5_skip_euler(img, vc, vu, vs, w, ab, g, dt, src, eps, km, sigma, cells, Cc, vo, s), f["old"])
+        else:
+            E.check(L.k5_stochastic_euler(img, vc, vu, vs, w, ab, g, dt, src, eps, km, sigma, cells, Cc, vo, scale, coef, z, seed, stream_id, s), f["old"])
+        return b
+
+    new, old = run(True), run(False)
+    for k, v in host.items():
+        lo, hi = first[k], first[k] + v.numel()
+        assert torch.equal(new[k], old[k]), k                              # the latent, v_out and what neither may touch
+        assert (new[k][:lo] == poison[k]).all() and (new[k][hi:] == poison[k]).all(), k
+        written = k == "img" or (k == "v_cond" and f["v_out"])
+        assert torch.equal(new[k][lo:hi], v.cuda()) != written, k
+    if f["sto"] == "kernel":   # the draw is the generator's: noise_normal_'s bits through znoise give the same latent
+        z = torch.empty(n, device="cuda")
+        E.noise_normal_(z, seed, stream_id)
+        host["znoise"], f["sto"] = z.cpu(), "znoise"
+        assert torch.equal(run(True)["img"], new["img"])
+
+
 def test_attention_bounded_scores_equals_online_max(E):
     """RMS-normalised q,k (|q|=|k|=8 -> |q.k| <= 64): the fixed-offset kernel is the same softmax."""
     S, H = 700, 2

@@ -1,12 +1,16 @@
 """CPU-only checks of `generate`'s per-step loop on a duck-typed model: the CFG-parallel exchange (one forward per step on this side, the
 pair's velocities through `exchange_velocity`) against the plain two-forward run, and what a batch off the many-sample path hands to the
 callback, the progress bar and the per-sample checks."""
+import os
 import sys
 import types
 from types import SimpleNamespace as NS
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import euler_step_reference as ER  # noqa: E402
 
 CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
 SHAPE, STEPS = (3, 4, 6, 16), 3
@@ -26,24 +30,6 @@ class FakeDit:
         return (0.5 * x + text_embed.mean() + pooled.mean() * float(t.reshape(-1)[0]) / 1000).to(torch.bfloat16)
 
 
-def cpu_cfg_euler(img, v, u, w, dt):
-    v = v if u is None else u + w * (v - u)
-    img.add_((dt * v.float()).to(torch.bfloat16).float())
-    return img
-
-
-def cpu_renoise(source, noise, sigma, out=None):
-    out = torch.empty_like(source) if out is None else out
-    return out.copy_((1 - sigma) * source + sigma * noise)
-
-
-def cpu_cfg_euler_edit(img, v, u, w, dt, source, noise, keep_mask, sigma_next):
-    cpu_cfg_euler(img, v, u, w, dt)
-    if keep_mask is not None:
-        img.copy_(keep_mask * cpu_renoise(source, noise, sigma_next) + (1 - keep_mask) * img)
-    return img
-
-
 def prompt(n, seed):
     g = torch.Generator().manual_seed(seed)
     return {"text_embeds": torch.randn(n, 8, generator=g), "pooled_embed": torch.randn(1, 4, generator=g)}
@@ -52,9 +38,8 @@ def prompt(n, seed):
 @pytest.fixture()
 def cpu_kernels(monkeypatch):
     from kandinsky import generation_utils as G
-    monkeypatch.setattr(G.E, "cfg_euler_", cpu_cfg_euler)
-    monkeypatch.setattr(G.E, "cfg_euler_edit_", cpu_cfg_euler_edit)
-    monkeypatch.setattr(G.E, "renoise", cpu_renoise)
+    monkeypatch.setattr(G.E, "euler_step_", ER.euler_step_)
+    monkeypatch.setattr(G.E, "renoise", ER.renoise)
     return G
 
 

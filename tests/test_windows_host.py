@@ -13,6 +13,9 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "kandinsky-5_amd")
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import euler_step_reference as ER  # noqa: E402
+
 CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
 
 
@@ -152,12 +155,6 @@ def cpu_cfg_euler_windows(img, vc, vu, w, dt, starts, weights):
     return img
 
 
-def cpu_cfg_euler(img, v, u, w, dt):
-    v = v if u is None else u + w * (v - u)
-    img.add_((dt * v.float()).to(torch.bfloat16).float())
-    return img
-
-
 def prompt(n, seed):
     g = torch.Generator().manual_seed(seed)
     return {"text_embeds": torch.randn(n, 8, generator=g), "pooled_embed": torch.randn(1, 4, generator=g)}
@@ -166,7 +163,7 @@ def prompt(n, seed):
 @pytest.fixture()
 def cpu_kernels(monkeypatch):
     from kandinsky import generation_utils as G
-    monkeypatch.setattr(G.E, "cfg_euler_", cpu_cfg_euler)
+    monkeypatch.setattr(G.E, "euler_step_", ER.euler_step_)
     monkeypatch.setattr(G.E, "cfg_euler_windows_", cpu_cfg_euler_windows)
     monkeypatch.setattr(G.E, "window_tables", cpu_window_tables)
     return G
