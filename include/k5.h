@@ -254,7 +254,9 @@ int k5_time_features_f32(float t, float* out, int D, void* stream);
 /* TextEmbeddings.norm nn.py:67,72 (LayerNorm affine on bf16 rows, bf16 and/or bf16-rounded fp32 out). */
 int k5_ln_affine_bf16(const void* x, const float* w, const float* b, void* out_bf16, float* out_f32, int rows,
                       int D, void* stream);
-/* RoPE3D/RoPE1D nn.py:99-150 cos/sin tables [T*H*W][n0+n1+n2]; positions are device int32. */
+/* RoPE3D/RoPE1D nn.py:99-150 cos/sin tables [T*H*W][32]: n0 | n1 | n2 columns for the three axes, n0 + n1 + n2 = 32 (the rotation
+ * pairs of a 64-wide head; an axis of width 0 needs no positions: the 1-D table is 32 | 0 | 0 with H = W = 1); positions are device
+ * int32.  K5_ERR_ARG for an extent < 1, widths that do not add up to 32, a NULL table or a NULL position vector of a used axis. */
 int k5_rope_table_f32(float* cos_tab, float* sin_tab, const int32_t* pos_t, const int32_t* pos_h,
                       const int32_t* pos_w, int T, int H, int W, int n0, int n1, int n2, float s0, float s1,
                       float s2, const int32_t* tok_perm, void* stream);

@@ -137,7 +137,7 @@ int k5_launch_sp2d_pack_qk(const void* x, void* q_out, void* k_out, int rows, in
 // scaled_out[row][(head - scale_from_head) * 64 ...] while the unscaled values stay in place.
 // stats (device, [H] floats, zeroed by the consumer): stats[h] = max(stats[h], |x_row,h|^2) over the rows of the call, of the
 // values the softmax reads (the scaled ones for heads >= scale_from_head) -> data-derived softmax bound (k5_launch_attn_flags)
-// K15: cos/sin tables [T*H*W][n0+n1+n2] for RoPE3D (RoPE1D: H=W=1, n1=n2=0), optional token permutation
+// K15: cos/sin tables [T*H*W][32] for RoPE3D, n0 + n1 + n2 = 32 (RoPE1D: H=W=1, n1=n2=0, p1 = p2 = null), optional token permutation
 int k5_launch_rope_table(float* cosT, float* sinT, const int32_t* p0, const int32_t* p1, const int32_t* p2, int T,
                          int H, int W, int n0, int n1, int n2, float s0, float s1, float s2, const int32_t* tok_perm,
                          hipStream_t stream);

@@ -972,7 +972,8 @@ inline int done() { return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
 
 int k5_launch_ln_modulate(const void* x, const float* scale, const float* shift, void* out, int rows, int D,
                           int ldx, int ldo, hipStream_t s, void* out_e4m3) {
-  if (rows <= 0 || D <= 0 || (!out && !out_e4m3)) return K5_ERR_ARG;
+  if (rows <= 0 || D <= 0 || (!out && !out_e4m3) || !x || !scale || !shift) return K5_ERR_ARG;
+  if (ldx < D || (out && ldo < D)) return K5_ERR_ARG;   // a row stride shorter than a row: rows would overlap
   if ((D & 7) || (ldx & 7) || (ldo & 7)) return K5_ERR_ALIGN;
   if (D > 64 * 8 * MAXC) return K5_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(ln_kernel<false>, dim3(ln_grid(rows)), dim3(256), 0, s, (const bf16_t*)x, scale, shift,
@@ -1028,7 +1029,11 @@ int k5_launch_rmsnorm_rope(void* x, const float* weight, const float* cosT, cons
                            int ld, const int32_t* heads_cfg, hipStream_t s, float out_scale, int scale_from_head, void* scaled_out,
                            int ld_scaled, float* stats, float* stats_ws, float* key_centre, void* mean_q, int mq_stride, void* mean_k, int mk_stride) {
   // heads_cfg (host pointer, optional): {heads_per_weight, rope_heads}; default: one weight, rope on all heads
-  if (rows <= 0 || H <= 0) return K5_ERR_ARG;
+  if (rows <= 0 || H <= 0 || !x || !weight) return K5_ERR_ARG;
+  if ((cosT != nullptr) != (sinT != nullptr)) return K5_ERR_ARG;   // the rotation needs both tables
+  // heads_per_weight divides the head index on the device and picks the weight row; rope_heads is an upper bound on the rotated heads
+  if (heads_cfg && (heads_cfg[0] <= 0 || heads_cfg[1] < 0)) return K5_ERR_ARG;
+  if (ld < 64 * (int64_t)H) return K5_ERR_ARG;   // H heads of 64 do not fit a row
   const bool means = mean_q || mean_k;
   if (means && ((rows & 63) || (mean_q && mq_stride < rows / 64) || (mean_k && mk_stride < rows / 64))) return K5_ERR_ARG;
   if (ld & 7) return K5_ERR_ALIGN;
@@ -1124,7 +1129,7 @@ int k5_launch_magcache_stats(const void* vis, const void* ori, const void* prev,
 
 int k5_launch_gemv_f32(const float* x, const float* W, const float* b, float* y, int N, int K, int silu_in,
                        const float* add, hipStream_t s) {
-  if (N <= 0 || K <= 0) return K5_ERR_ARG;
+  if (N <= 0 || K <= 0 || !x || !W || !y) return K5_ERR_ARG;
   if (K & 3) return K5_ERR_ALIGN;
   hipLaunchKernelGGL(gemv_f32_kernel, dim3((N + 3) / 4), dim3(256), 0, s, x, W, b, y, N, K, silu_in, add);
   return done();
@@ -1144,8 +1149,12 @@ int k5_launch_step_inc(int* step, hipStream_t s) {
 int k5_launch_rope_table(float* cosT, float* sinT, const int32_t* p0, const int32_t* p1, const int32_t* p2, int T,
                          int H, int W, int n0, int n1, int n2, float s0, float s1, float s2, const int32_t* tok_perm,
                          hipStream_t s) {
-  const int64_t total = (int64_t)T * H * W * (n0 + n1 + n2);
-  if (total <= 0) return K5_ERR_ARG;
+  // every extent on its own: a product of two negative extents is positive.  A table row is the 32 rotation pairs of a 64-wide head
+  // (rmsnorm_rope_kernel and the attention's fused query norm read rows of 32 floats), so the three axis widths add up to 32; an axis of
+  // width 0 has no positions (the 1-D text table is 32 | 0 | 0)
+  if (T <= 0 || H <= 0 || W <= 0 || n0 < 0 || n1 < 0 || n2 < 0 || n0 + n1 + n2 != 32) return K5_ERR_ARG;
+  if (!cosT || !sinT || (n0 && !p0) || (n1 && !p1) || (n2 && !p2)) return K5_ERR_ARG;
+  const int64_t total = (int64_t)T * H * W * 32;
   hipLaunchKernelGGL(rope_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, cosT, sinT, p0, p1, p2,
                      T, H, W, n0, n1, n2, s0, s1, s2, tok_perm);
   return done();
@@ -1153,7 +1162,7 @@ int k5_launch_rope_table(float* cosT, float* sinT, const int32_t* p0, const int3
 
 int k5_launch_patchify(const float* x, void* out, int T, int H, int W, int C, int Cin_total, int Kpad,
                        const int32_t* tok_perm, hipStream_t s) {
-  if (T <= 0 || (H & 1) || (W & 1) || Kpad < 4 * Cin_total || C <= 0 || C > Cin_total) return K5_ERR_ARG;
+  if (!x || !out || T <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || Kpad < 4 * Cin_total || C <= 0 || C > Cin_total) return K5_ERR_ARG;
   const int64_t total = (int64_t)T * (H / 2) * (W / 2) * Kpad;
   hipLaunchKernelGGL(patchify_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, (bf16_t*)out, T, H, W, C, Cin_total, Kpad,
                      tok_perm);
@@ -1162,7 +1171,7 @@ int k5_launch_patchify(const float* x, void* out, int T, int H, int W, int C, in
 
 int k5_launch_patchify_cond(const float* x, const float* vcond, void* out, int T, int H, int W, int C, int Cin_total, int Kpad,
                             const int32_t* tok_perm, hipStream_t s) {
-  if (!x || !vcond || T <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || Kpad < 4 * Cin_total || C <= 0 || C >= Cin_total)
+  if (!x || !vcond || !out || T <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || Kpad < 4 * Cin_total || C <= 0 || C >= Cin_total)
     return K5_ERR_ARG;
   const int64_t total = (int64_t)T * (H / 2) * (W / 2) * Kpad;
   hipLaunchKernelGGL(patchify_cond_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, vcond, (bf16_t*)out, T, H, W, C, Cin_total,
@@ -1172,8 +1181,8 @@ int k5_launch_patchify_cond(const float* x, const float* vcond, void* out, int T
 
 int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx, const int32_t* tok_perm,
                          hipStream_t s) {
+  if (!x || !out || T <= 0 || Hp <= 0 || Wp <= 0 || C <= 0 || ldx < 4 * (int64_t)C) return K5_ERR_ARG;   // every extent on its own, not their product
   const int64_t total = (int64_t)T * Hp * Wp * 4 * C;
-  if (total <= 0) return K5_ERR_ARG;
   hipLaunchKernelGGL(unpatchify_kernel, dim3(grid_for(total)), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)out, T, Hp, Wp,
                      C, ldx, tok_perm);
   return done();
