@@ -106,10 +106,66 @@ uint16_t f32_to_bf16_rne(float f) {
 }
 float bf16_round_host(float f) { uint32_t u = (uint32_t)f32_to_bf16_rne(f) << 16; float r; memcpy(&r, &u, 4); return r; }
 
+// One packed linear layer, or (rows()) a row range of one: bf16 weights [N][ld] (K <= ld input features; the GEMM runs over all ld columns, the
+// padding is zero), the bias as fp32 of bf16-rounded values (absent: the feed-forward has none) and, once k5_dit_set_fp8 asked for it, an e4m3
+// copy [N][K] with one fp32 scale per output channel.  load_linear fills it, linear() launches it.
+struct Linear {
+  DevBuf w, b, w8, sc;
+  int N = 0, K = 0, ld = 0;
+  bool has_e4m3() const { return w8.p != nullptr; }
+  // non-owning view of output channels [row0, row0 + n): weights, bias, e4m3 copy and scales move together
+  Linear rows(size_t row0, size_t n) const {
+    Linear v;
+    v.N = (int)n; v.K = K; v.ld = ld;
+    v.w.alias(w.as<bf16_t>() + row0 * ld, n * ld * 2);
+    if (b.p) v.b.alias(b.as<float>() + row0, n * 4);
+    if (w8.p) { v.w8.alias(w8.as<uint8_t>() + row0 * K, n * K); v.sc.alias(sc.as<float>() + row0, n * 4); }
+    return v;
+  }
+  // make (create) or refresh the e4m3 copy from the current bf16 bits; per output channel, so rows that did not change come out as they were
+  int quantise(bool create) {
+    if (!w8.p) {
+      if (!create) return K5_OK;
+      K5CHK(w8.ensure((size_t)N * K)); K5CHK(sc.ensure((size_t)N * 4));
+    }
+    return k5_launch_quant_rows_fp8(w.p, w8.p, sc.as<float>(), N, K, ld, K, nullptr);
+  }
+};
+// activation rows [rows][ld] in bf16 and, where the call runs in e4m3 (the shape rules sa_fp8_in / sa_sp_fp8_in / ff_fp8_in / f8_out decide,
+// e4m3_rows provides), the same rows in e4m3 at the same stride
+struct Act {
+  const void* bf = nullptr; const void* e4 = nullptr; int rows = 0, ld = 0;
+  Act from(size_t row0, int n) const { return Act{(const bf16_t*)bf + row0 * ld, e4 ? (const uint8_t*)e4 + row0 * ld : nullptr, n, ld}; }
+};
+// One linear layer on activation rows: out [x.rows][ldc] = epilogue(x W^T + bias).  weights_as_rows: the V^T form, out [N][ldc] = W x^T with
+// the bias per output ROW.  x.e4 set: both operands in e4m3 (gemm_fp8.hip), otherwise bf16.
+struct LinearArgs {
+  const Linear* lin; Act x; void* out; int ldc; hipStream_t stream;
+  LinearArgs(const Linear& l, const Act& x_, void* out_, int ldc_, hipStream_t s) : lin(&l), x(x_), out(out_), ldc(ldc_), stream(s) {}
+  int epi = K5_EPI_BIAS;
+  const void* resid = nullptr; int ldr = 0; const float* gate = nullptr;
+  bool weights_as_rows = false;
+  int force_kernel = 0;                // bf16 only: k5_launch_gemm_bf16's kernel id (2 keeps a summation order whatever the shape)
+};
+int linear(const LinearArgs& a) {
+  const Linear& l = *a.lin;
+  const bool t = a.weights_as_rows;
+  const int M = t ? l.N : a.x.rows, N = t ? a.x.rows : l.N;
+  if (a.x.e4) {
+    // the scales belong to the weights' channels: rows of the output in the V^T form (scale_m), where the bias then follows them under K5_EPI_BIAS
+    if (!l.has_e4m3()) { k5_set_error("internal: e4m3 activations for a layer without an e4m3 copy"); return K5_ERR_STATE; }
+    return k5_launch_gemm_fp8(t ? l.w8.p : a.x.e4, t ? a.x.e4 : l.w8.p, l.sc.as<float>(), a.out, M, N, l.K, t ? l.K : a.x.ld, t ? a.x.ld : l.K, a.ldc, a.epi,
+                              a.resid, a.ldr, a.gate, a.stream, l.b.as<float>(), t ? 1 : 0);
+  }
+  const int epi = (t && a.epi == K5_EPI_BIAS) ? K5_EPI_BIAS_M : a.epi;
+  return k5_launch_gemm_bf16(t ? l.w.p : a.x.bf, t ? a.x.bf : l.w.p, l.b.as<float>(), a.out, M, N, l.ld, t ? l.ld : a.x.ld, t ? a.x.ld : l.ld, a.ldc, epi,
+                             a.resid, a.ldr, a.gate, a.stream, a.force_kernel);
+}
+
 struct AttnW {  // one attention module, packed
-  DevBuf wqk, wq, wk, wv, wo;       // bf16
-  DevBuf bqk, bq, bk, bv, bo, norm; // fp32 (bias values bf16-rounded); norm = [q_norm | k_norm]
-  DevBuf wqk8, wv8, wo8, sqk, sv, so;   // opt-in e4m3 copies (k5_dit_set_fp8 bits 1 / 2): weights + per-output-channel scales
+  Linear wqk, wq, wk, wv, wo;       // self-attention: wqk (to_query stacked over to_key), wv, wo; cross-attention: wq, wo, and wk / wv as views
+                                    // of the handle's stacks over all visual blocks (k5_dit::cx_k / cx_v)
+  DevBuf norm;                      // fp32 [q_norm | k_norm]
   float score_bound = 0.f;          // |q.k| <= 64 max|w_q| max|w_k| after norm_qk (RoPE preserves norms)
   mutable DevBuf pref;              // visual self-attention: [3][H] heads the per-row-offset softmax served badly the last time this layer ran for
                                     // the cond (0) / uncond (1) / skip (2, k5_dit_forward_skip's own blocks) branch (k5_launch_attn_pref_update); zeroed at the start of every k5_sample and
@@ -117,8 +173,7 @@ struct AttnW {  // one attention module, packed
 };
 struct BlockW {
   AttnW self_attn, cross_attn;
-  DevBuf w1, w2;  // feed_forward in/out, bf16
-  DevBuf w1_f8, w2_f8, s1_f8, s2_f8;  // opt-in fp8 copies (k5_dit_set_fp8): e4m3 weights + per-output-channel scales
+  Linear w1, w2;  // feed_forward in/out (no bias)
   size_t mod_off = 0;  // offset (floats) of this block's modulation vector in mod_all
 };
 
@@ -307,9 +362,8 @@ struct k5_dit {
 
   // packed weights
   DevBuf time_w1, time_b1, time_w2, time_b2;                   // fp32
-  DevBuf text_w, text_b, text_lnw, text_lnb;                   // bf16 W, fp32 rest
-  DevBuf pool_w, pool_b, pool_lnw, pool_lnb;
-  DevBuf vis_w, vis_b, out_w, out_b;
+  Linear text_lin, pool_lin, vis_lin, out_lin;                 // the in_layers of the text / pooled / visual embeddings and the out layer
+  DevBuf text_lnw, text_lnb, pool_lnw, pool_lnb;               // fp32
   DevBuf mod_w, mod_b;                                         // all Modulation layers stacked, fp32
   size_t mod_rows = 0, out_mod_off = 0;
   std::vector<BlockW> tblocks, vblocks;
@@ -335,7 +389,6 @@ struct k5_dit {
   hipStream_t pair_stream = nullptr;
   hipEvent_t ev_vel_ready = nullptr, ev_vel_done = nullptr;
   DevBuf ws_vel_pair;                              // [2][T H W 16] bf16: slot 0 = conditional, 1 = unconditional velocity
-  bool use_fp8 = false;                            // visual feed-forward GEMMs in W8A8 e4m3 (k5_dit_set_fp8 bit 0)
   int fp8_fuse_ln = 1;                             // fp8 modes: the LayerNorm in front of an fp8 projection writes e4m3 directly (same bits as LayerNorm + quantisation pass)
   int fp8_mask = 0;                                // k5_dit_set_fp8: bit 0 feed-forward, bit 1 q | k | V^T projections, bit 2 out projection of the visual self-attention
   DevBuf ws_h8, ws_ff8;                            // fp8 activations of that path
@@ -343,7 +396,8 @@ struct k5_dit {
   // num_visual_blocks projections of 256 text rows (34 + 32 us each: 28-tile launches) become two GEMMs against the stacked weights
   // [blocks * D][D] before the visual stack, the key RMSNorms one launch — same kernels on the same per-element sums: bit-identical.  Every text
   // stream keeps the result in its own TextStream::ck_all / cvt_all
-  DevBuf cx_wk_all, cx_wv_all, cx_bk_all, cx_bv_all, cx_knorm_all;
+  Linear cx_k, cx_v;                               // to_key / to_value of every visual block's cross-attention, stacked: [blocks * D][D]
+  DevBuf cx_knorm_all;
   int cross_kv_batched = 1;
   DevBuf ws_sched;                                 // sampler tables on the device: t*1000 [steps] | dt [steps] | step counter
   bool use_graph = false;                          // k5_sample replays one captured step (k5_dit_set_graph)
@@ -555,7 +609,7 @@ struct k5_dit {
 
   // LoRA adapters merged into the packed weights (k5_dit_add_lora): the packed bits of every touched matrix as they were before the first
   // merge, keyed by the matrix's address (a region of a fused / stacked buffer counts as its own matrix); k5_dit_clear_lora copies them back
-  struct LoraBackup { DevBuf copy; size_t bytes = 0; int vblock = -1, f8 = 0; };   // f8: which e4m3 copy of visual block `vblock` mirrors it (lora_requant)
+  struct LoraBackup { DevBuf copy; size_t bytes = 0; Linear* lin = nullptr; };   // lin: the layer the matrix belongs to (its e4m3 copy follows the bf16 bits); null: an fp32 matrix
   std::map<void*, LoraBackup> lora_backup;
 
   // profiling
@@ -648,9 +702,6 @@ int pack_rows(DevBuf& dst, bool bf16, const HostTensor* t, size_t rows, size_t c
   K5CHK(dst.ensure(total_rows * ld * es));
   return k5_launch_pack_matrix(t->dev.p, t->dtype, (char*)dst.p + row0 * ld * es, bf16 ? 1 : 0, (int64_t)rows, (int)cols, (int)ld, nullptr);
 }
-int pack_bf16(DevBuf& dst, const HostTensor* t, size_t rows, size_t cols, size_t ld, size_t row0 = 0, size_t total_rows = 0) {
-  return pack_rows(dst, true, t, rows, cols, ld, row0, total_rows);
-}
 int pack_f32(DevBuf& dst, const HostTensor* t, size_t rows, size_t cols, size_t row0 = 0, size_t total_rows = 0) {
   return pack_rows(dst, false, t, rows, cols, cols, row0, total_rows);
 }
@@ -670,27 +721,33 @@ bool shape_ok(k5_dit* d, const std::string& k, size_t r, size_t c) {
   return ok;
 }
 
-int pack_attn(k5_dit* d, const std::string& p, AttnW& a, bool fuse_qk) {
-  const size_t D = d->D;
-  for (const char* nm : {".to_query", ".to_key", ".to_value", ".out_layer"})
-    if (!shape_ok(d, p + nm + ".weight", D, D) || !shape_ok(d, p + nm + ".bias", D, 0)) return K5_ERR_ARG;
-  if (!shape_ok(d, p + ".query_norm.weight", 64, 0) || !shape_ok(d, p + ".key_norm.weight", 64, 0)) return K5_ERR_ARG;
-  const HostTensor *wq = find(d, p + ".to_query.weight"), *wk = find(d, p + ".to_key.weight"),
-                   *wv = find(d, p + ".to_value.weight"), *wo = find(d, p + ".out_layer.weight"),
-                   *bq = find(d, p + ".to_query.bias"), *bk = find(d, p + ".to_key.bias"),
-                   *bv = find(d, p + ".to_value.bias"), *bo = find(d, p + ".out_layer.bias"),
-                   *nq = find(d, p + ".query_norm.weight"), *nk = find(d, p + ".key_norm.weight");
-  if (fuse_qk) {
-    std::vector<float> b(2 * D);
-    memcpy(b.data(), bq->data.data(), D * 4); memcpy(b.data() + D, bk->data.data(), D * 4);
-    K5CHK(pack_bf16(a.wqk, wq, D, D, D, 0, 2 * D)); K5CHK(pack_bf16(a.wqk, wk, D, D, D, D, 2 * D));
-    K5CHK(upload_bias_bf16r(a.bqk, b.data(), 2 * D));
-  } else {
-    K5CHK(pack_bf16(a.wq, wq, D, D, D)); K5CHK(upload_bias_bf16r(a.bq, bq->data.data(), D));
-    K5CHK(pack_bf16(a.wk, wk, D, D, D)); K5CHK(upload_bias_bf16r(a.bk, bk->data.data(), D));
+// One packed layer from the staged state_dict: `<prefix>.weight` [n][K] into bf16 rows of ld >= K elements and, unless the layer has none,
+// `<prefix>.bias` [n] bf16-rounded — both shape-checked.  Several prefixes: those layers stacked along the output channels in the order given
+// (to_query over to_key; one matrix of every visual block).
+int load_linear(k5_dit* d, Linear& l, const std::vector<std::string>& prefixes, size_t n, size_t K, size_t ld, bool bias = true) {
+  const size_t total = prefixes.size() * n;
+  std::vector<float> b(total);
+  for (size_t i = 0; i < prefixes.size(); ++i) {
+    const std::string& p = prefixes[i];
+    if (!shape_ok(d, p + ".weight", n, K) || (bias && !shape_ok(d, p + ".bias", n, 0))) return K5_ERR_ARG;
+    K5CHK(pack_rows(l.w, true, find(d, p + ".weight"), n, K, ld, i * n, total));
+    if (bias) memcpy(b.data() + i * n, find(d, p + ".bias")->data.data(), n * 4);
   }
-  K5CHK(pack_bf16(a.wv, wv, D, D, D)); K5CHK(upload_bias_bf16r(a.bv, bv->data.data(), D));
-  K5CHK(pack_bf16(a.wo, wo, D, D, D)); K5CHK(upload_bias_bf16r(a.bo, bo->data.data(), D));
+  if (bias) K5CHK(upload_bias_bf16r(l.b, b.data(), total));
+  l.N = (int)total; l.K = (int)K; l.ld = (int)ld;
+  return K5_OK;
+}
+
+// self: the module projects its own keys and values (q | k stacked); otherwise they come from the stacks of all visual blocks (k5_dit_finalize)
+int pack_attn(k5_dit* d, const std::string& p, AttnW& a, bool self) {
+  const size_t D = d->D;
+  if (self) {
+    K5CHK(load_linear(d, a.wqk, {p + ".to_query", p + ".to_key"}, D, D, D));
+    K5CHK(load_linear(d, a.wv, {p + ".to_value"}, D, D, D));
+  } else K5CHK(load_linear(d, a.wq, {p + ".to_query"}, D, D, D));
+  K5CHK(load_linear(d, a.wo, {p + ".out_layer"}, D, D, D));
+  if (!shape_ok(d, p + ".query_norm.weight", 64, 0) || !shape_ok(d, p + ".key_norm.weight", 64, 0)) return K5_ERR_ARG;
+  const HostTensor *nq = find(d, p + ".query_norm.weight"), *nk = find(d, p + ".key_norm.weight");
   std::vector<float> n(128);
   memcpy(n.data(), nq->data.data(), 64 * 4); memcpy(n.data() + 64, nk->data.data(), 64 * 4);
   K5CHK(upload_f32(a.norm, n.data(), 128));
@@ -747,11 +804,11 @@ int nabla_density_hint(k5_dit* d, int H, int nqb, int nb, hipStream_t s) {
 // do the q | k | V^T projections of the VISUAL self-attention take the e4m3 activations (k5_dit_set_fp8 bit 1)?  One rule for the callee and for
 // the block loop, which then lets the LayerNorm write ws_h8 directly (h8_ready) instead of a bf16 h + a quantisation pass
 bool sa_fp8_in(const k5_dit* d, const AttnW& a, int rows) {
-  return (d->fp8_mask & 2) && a.wqk8.p && rows >= 256 && !((int)rup(rows, 8) & 15);
+  return (d->fp8_mask & 2) && a.wqk.has_e4m3() && rows >= 256 && !((int)rup(rows, 8) & 15);
 }
 bool sa_sp_fp8_in(const k5_dit* d, const AttnW& a, int rows, int rows_pad, bool nabla) {
   const int P = d->sp_world;
-  return (d->fp8_mask & 2) && a.wqk8.p && rows >= 256 && !((rows_pad / ((!nabla && d->sp_slices > 1 && P > 1) ? d->sp_slices : 1)) & 15);
+  return (d->fp8_mask & 2) && a.wqk.has_e4m3() && rows >= 256 && !((rows_pad / ((!nabla && d->sp_slices > 1 && P > 1) ? d->sp_slices : 1)) & 15);
 }
 // "nabla_fuse_means": the fused form gives every thread 64 consecutive rows of one 16-byte column chunk, i.e. the launch has rows / 64 x heads x 8
 // threads — a sequence-parallel shard of the 10 s clip (366 blocks x 28 heads: 82 k threads, a sixth of the resident capacity) runs it latency-
@@ -764,7 +821,7 @@ size_t nabla_ws_bytes(const k5_dit* d, int H, int nb, int nqb) {
 bool nabla_means_fused(const k5_dit* d, int rows, int heads) {
   return d->nabla_fuse_means == 2 || (d->nabla_fuse_means == 1 && (long long)(rows / 64) * heads * 8 >= 150000);
 }
-bool ff_fp8_in(const k5_dit* d, const BlockW& b, int rows) { return d->use_fp8 && b.w1_f8.p && rows >= 256; }
+bool ff_fp8_in(const k5_dit* d, const BlockW& b, int rows) { return (d->fp8_mask & 1) && b.w1.has_e4m3() && rows >= 256; }
 
 // ---- the steps the self-attention schedules share ----
 // Softmax form per head, decided from the data (by_data): k5_launch_attn_flags turns the |q|^2 / |k'|^2 maxima the norm passes left into the
@@ -825,17 +882,29 @@ int attn_pref_update(k5_dit* d, hipStream_t s, const SoftmaxForm& f, int heads, 
   if (!f.kmax) return K5_OK;
   return k5_launch_attn_pref_update(d->ws_attn_bal.as<float>(), heads, q_rows, group_rows, f.pref, s, leave_sig);
 }
+// The rows x [rows][D] as a projection takes them.  want (the caller's shape rule): in e4m3 too, in ws_h8 — quantised here unless the LayerNorm
+// already wrote them there (ready; there is no bf16 x then).  A bf16 projection must not have been promised e4m3 rows.
+int e4m3_rows(k5_dit* d, hipStream_t s, const void* x, int rows, bool want, bool ready, Act& act) {
+  const int D = d->D;
+  act = Act{x, nullptr, rows, D};
+  if (ready && !want) { k5_set_error("internal: e4m3 activations handed to a bf16 projection"); return K5_ERR_ARG; }
+  if (!want) return K5_OK;
+  K5CHK(d->ws_h8.ensure((size_t)rows * D));
+  if (!ready) {
+    Scope sc(d, s, "elementwise");
+    K5CHK(k5_launch_quant_rows_fp8(x, d->ws_h8.p, nullptr, rows, D, D, D, s));
+  }
+  act.e4 = d->ws_h8.p;
+  return K5_OK;
+}
 // x_resid += gate * out_l(o), fused in the out GEMM; f8_out: e4m3 activations (opt-in, k5_dit_set_fp8 bit 2)
 int attn_out_projection(k5_dit* d, hipStream_t s, const AttnW& a, const void* o, int rows, void* resid, const float* gate, bool f8_out = false) {
-  const int D = d->D;
-  if (f8_out) {
-    K5CHK(d->ws_h8.ensure((size_t)rows * D));
-    Scope sc(d, s, "elementwise");
-    K5CHK(k5_launch_quant_rows_fp8(o, d->ws_h8.p, nullptr, rows, D, D, D, s));
-  }
+  Act x;
+  K5CHK(e4m3_rows(d, s, o, rows, f8_out, false, x));
+  LinearArgs g(a.wo, x, resid, d->D, s);
+  g.epi = K5_EPI_GATE; g.resid = resid; g.ldr = d->D; g.gate = gate;
   Scope sc(d, s, "gemm");
-  if (f8_out) return k5_launch_gemm_fp8(d->ws_h8.p, a.wo8.p, a.so.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s, a.bo.as<float>(), 0);
-  return k5_launch_gemm_bf16(o, a.wo.p, a.bo.as<float>(), resid, rows, D, D, D, D, D, K5_EPI_GATE, resid, D, gate, s);
+  return linear(g);
 }
 
 int run_self_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, int rows, void* qk, void* vt,
@@ -845,21 +914,15 @@ int run_self_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, 
   const int ldvt = (int)rup(rows, 8);
   const bool vis = !strcmp(fam_attn, "attn_self");
   const bool f8_in = vis && sa_fp8_in(d, a, rows);   // opt-in lossy mode: e4m3 projections (gemm_fp8.hip)
-  const bool f8_out = vis && (d->fp8_mask & 4) && a.wo8.p && rows >= 256;
-  if (h8_ready && !f8_in) { k5_set_error("internal: e4m3 activations handed to a bf16 projection"); return K5_ERR_ARG; }
-  if (f8_in) {
-    K5CHK(d->ws_h8.ensure((size_t)rows * D));
-    if (!h8_ready) {
-      Scope sc(d, s, "elementwise");
-      K5CHK(k5_launch_quant_rows_fp8(h, d->ws_h8.p, nullptr, rows, D, D, D, s));
-    }
+  const bool f8_out = vis && (d->fp8_mask & 4) && a.wo.has_e4m3() && rows >= 256;
+  {
+    Act x;
+    K5CHK(e4m3_rows(d, s, h, rows, f8_in, h8_ready, x));
+    LinearArgs gv(a.wv, x, vt, ldvt, s);
+    gv.weights_as_rows = true;
     Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_fp8(d->ws_h8.p, a.wqk8.p, a.sqk.as<float>(), qk, rows, 2 * D, D, D, D, 2 * D, K5_EPI_BIAS, nullptr, 0, nullptr, s, a.bqk.as<float>(), 0));
-    K5CHK(k5_launch_gemm_fp8(a.wv8.p, d->ws_h8.p, a.sv.as<float>(), vt, D, rows, D, D, D, ldvt, K5_EPI_BIAS, nullptr, 0, nullptr, s, a.bv.as<float>(), 1));
-  } else {
-    Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(h, a.wqk.p, a.bqk.as<float>(), qk, rows, 2 * D, D, D, D, 2 * D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-    K5CHK(k5_launch_gemm_bf16(a.wv.p, h, a.bv.as<float>(), vt, D, rows, D, D, D, ldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
+    K5CHK(linear(LinearArgs(a.wqk, x, qk, 2 * D, s)));
+    K5CHK(linear(gv));
   }
   const bool pre = vis && rows % 64 == 0;   // visual blocks only (not the text blocks)
   const bool by_data = pre && d->attn_mode == K5_ATTN_AUTO;            // per-head flags from the data
@@ -975,8 +1038,7 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
   bf16_t* vtfull = d->ws_vtfull.as<bf16_t>();
   bf16_t* kloc = kfull + (size_t)r * rows_pad * D;
   bf16_t* vtloc = vtfull + (size_t)r * D * ldv;
-  const bf16_t* wq = a.wqk.as<bf16_t>();
-  const bf16_t* wk = wq + (size_t)D * D;
+  const Linear wq = a.wqk.rows(0, D), wk = a.wqk.rows(D, D);
   // pre-scaled keys, softmax form per head from the data (the |k'|^2 maxima of all ranks are gathered with the keys) — dense AND
   // NABLA.  The NABLA map is computed from the UNSCALED keys, of which it only needs the 64-token block means: the unscaled
   // keys stay local (ws_kc), their means (28 x 64 values per block) travel with the gather, and the gathered keys are the scaled ones —
@@ -997,18 +1059,11 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
   }
   // opt-in e4m3 projections (k5_dit_set_fp8 bit 1), as on one GPU: the rank's rows of h are quantised once and feed the K, V^T and Q GEMMs
   const bool f8_in = sa_sp_fp8_in(d, a, rows, rows_pad, nabla != nullptr);
-  const uint8_t* wq8 = a.wqk8.as<uint8_t>();
-  const uint8_t* wk8 = wq8 ? wq8 + (size_t)D * D : nullptr;
-  if (h8_ready && !f8_in) { k5_set_error("internal: e4m3 activations handed to a bf16 projection"); return K5_ERR_ARG; }
-  if (f8_in && !h8_ready) {
-    K5CHK(d->ws_h8.ensure((size_t)rows * D));
-    Scope sc(d, s, "elementwise");
-    K5CHK(k5_launch_quant_rows_fp8(h, d->ws_h8.p, nullptr, rows, D, D, D, s));
-  }
+  Act x;
+  K5CHK(e4m3_rows(d, s, h, rows, f8_in, h8_ready, x));
   {
     Scope sc(d, s, "gemm");
-    if (f8_in) K5CHK(k5_launch_gemm_fp8(d->ws_h8.p, wk8, a.sqk.as<float>() + D, kun, rows, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s, a.bqk.as<float>() + D, 0));
-    else K5CHK(k5_launch_gemm_bf16(h, wk, a.bqk.as<float>() + D, kun, rows, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+    K5CHK(linear(LinearArgs(wk, x, kun, D, s)));
   }
   {
     Scope sc(d, s, "elementwise");
@@ -1033,17 +1088,15 @@ int run_self_attention_sp(k5_dit* d, hipStream_t s, const AttnW& a, const void* 
     for (int sl = 0; sl < S; ++sl) {
       const int nsl = std::min(cols, rows - sl * cols);
       if (nsl <= 0) break;
-      if (f8_in) K5CHK(k5_launch_gemm_fp8(a.wv8.p, d->ws_h8.as<uint8_t>() + (size_t)sl * cols * D, a.sv.as<float>(), vtloc + (size_t)sl * D * cols, D, nsl, D, D, D,
-                                          cols, K5_EPI_BIAS, nullptr, 0, nullptr, s, a.bv.as<float>(), 1));
-      else K5CHK(k5_launch_gemm_bf16(a.wv.p, (const bf16_t*)h + (size_t)sl * cols * D, a.bv.as<float>(), vtloc + (size_t)sl * D * cols, D, nsl, D, D, D,
-                                     cols, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
+      LinearArgs gv(a.wv, x.from((size_t)sl * cols, nsl), vtloc + (size_t)sl * D * cols, cols, s);
+      gv.weights_as_rows = true;
+      K5CHK(linear(gv));
     }
   }
   HIPCHK(hipEventRecord(d->ev_v, s));
   {
     Scope sc(d, s, "gemm");
-    if (f8_in) K5CHK(k5_launch_gemm_fp8(d->ws_h8.p, wq8, a.sqk.as<float>(), q, rows, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s, a.bqk.as<float>(), 0));
-    else K5CHK(k5_launch_gemm_bf16(h, wq, a.bqk.as<float>(), q, rows, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+    K5CHK(linear(LinearArgs(wq, x, q, D, s)));
   }
   // see run_self_attention; here only with "attn_fuse_qnorm" = 2: every pass of the schedule redoes the norm, and at shard sizes that
   // costs what the standalone pass over the local queries does (emulated P = 8: 82.8 vs 82.6 ms per step)
@@ -1284,13 +1337,14 @@ int run_self_attention_heads(k5_dit* d, hipStream_t s, const AttnW& a, const voi
   float* ustats = d->ws_u_stats.as<float>();         // [P][2 H]: rank p's maxima of |q_h|^2 (H) and |k'_h|^2 (H) over ITS rows
   if (by_data) HIPCHK(hipMemsetAsync(ustats + (size_t)r * 2 * H, 0, (size_t)2 * H * 4, s));   // the norm pass max-accumulates; only my heads' entries were consumed
   bf16_t* qk = d->ws_qk.as<bf16_t>();
+  const Act x{h, nullptr, rows, D};   // these schedules keep q | k | V^T in bf16 whatever k5_dit_set_fp8 asked for ("fp8_effective" says so)
   bf16_t* qsend = d->ws_u_send.as<bf16_t>();
   bf16_t* ksend = qsend + (size_t)G * rows_pad * Dp;   // two-level
   if (two_level) { L.q = d->ws_u_qrecv.as<bf16_t>(); L.k = d->ws_u_recv.as<bf16_t>(); L.ldq = L.ldk = Dp; }
   else { L.q = d->ws_u_recv.as<bf16_t>(); L.k = L.q + Dp; L.ldq = L.ldk = 2 * Dp; }
   {
     Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(h, a.wqk.p, a.bqk.as<float>(), qk, rows, 2 * D, D, D, D, 2 * D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+    K5CHK(linear(LinearArgs(a.wqk, x, qk, 2 * D, s)));
   }
   {
     Scope sc(d, s, "elementwise");
@@ -1313,7 +1367,9 @@ int run_self_attention_heads(k5_dit* d, hipStream_t s, const AttnW& a, const voi
   }
   {
     Scope sc(d, s, "gemm");   // V^T of the rank's rows while q | k' travel
-    K5CHK(k5_launch_gemm_bf16(a.wv.p, h, a.bv.as<float>(), d->ws_u_vsend.p, D, rows, D, D, D, rows_pad, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
+    LinearArgs gv(a.wv, x, d->ws_u_vsend.p, rows_pad, s);
+    gv.weights_as_rows = true;
+    K5CHK(linear(gv));
   }
   HIPCHK(hipEventRecord(d->ev_v, s));
   HIPCHK(hipStreamWaitEvent(cs, d->ev_v, 0));
@@ -1371,8 +1427,12 @@ int cross_kv_batched_run(k5_dit* d, hipStream_t s, k5_dit::TextStream& st) {
   K5CHK(st.ck_all.ensure((size_t)L * nbv * D * 2)); K5CHK(st.cvt_all.ensure((size_t)nbv * D * ldvt * 2));
   {
     Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(st.text.p, d->cx_wk_all.p, d->cx_bk_all.as<float>(), st.ck_all.p, L, nbv * D, D, D, D, nbv * D, K5_EPI_BIAS, nullptr, 0, nullptr, s, 2));
-    K5CHK(k5_launch_gemm_bf16(d->cx_wv_all.p, st.text.p, d->cx_bv_all.as<float>(), st.cvt_all.p, nbv * D, L, D, D, D, ldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s, 2));
+    const Act text{st.text.p, nullptr, L, D};
+    LinearArgs gk(d->cx_k, text, st.ck_all.p, nbv * D, s), gv(d->cx_v, text, st.cvt_all.p, ldvt, s);
+    gk.force_kernel = gv.force_kernel = 2;
+    gv.weights_as_rows = true;
+    K5CHK(linear(gk));
+    K5CHK(linear(gv));
   }
   Scope sc(d, s, "elementwise");
   const int32_t hc[2] = {H, 0};   // one norm weight per block's H heads, no RoPE
@@ -1401,11 +1461,14 @@ int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h,
   void* o = cx.v[0].o;
   {
     Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_bf16(h, a.wq.p, a.bq.as<float>(), q, rows, D, D, D, D, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+    K5CHK(linear(LinearArgs(a.wq, Act{h, nullptr, rows, D}, q, D, s)));
     for (int k = 0; !cx.kv_ready && k < cx.n; ++k) {
       const CrossView& v = cx.v[k];
-      K5CHK(k5_launch_gemm_bf16(v.text, a.wk.p, a.bk.as<float>(), v.ck, v.L, D, D, D, D, v.ldck, K5_EPI_BIAS, nullptr, 0, nullptr, s));
-      K5CHK(k5_launch_gemm_bf16(a.wv.p, v.text, a.bv.as<float>(), v.cvt, D, v.L, D, D, D, v.ldvt, K5_EPI_BIAS_M, nullptr, 0, nullptr, s));
+      const Act text{v.text, nullptr, v.L, D};
+      LinearArgs gv(a.wv, text, v.cvt, v.ldvt, s);
+      gv.weights_as_rows = true;
+      K5CHK(linear(LinearArgs(a.wk, text, v.ck, v.ldck, s)));
+      K5CHK(linear(gv));
     }
   }
   // RMSNorm of the queries (no RoPE in cross-attention, nn.py:330-334) is fused into the attention kernel's Q-fragment load when the
@@ -1446,24 +1509,18 @@ int run_cross_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h,
 
 int run_ff(k5_dit* d, hipStream_t s, const BlockW& b, const void* h, int rows, void* ff, void* resid, const float* gate, bool h8_ready = false) {
   const int D = d->D, FF = d->FF;
-  if (h8_ready && !ff_fp8_in(d, b, rows)) { k5_set_error("internal: e4m3 activations handed to a bf16 feed-forward"); return K5_ERR_ARG; }
-  if (ff_fp8_in(d, b, rows)) {
-    // opt-in lossy path: h -> e4m3 (static scale; by the LayerNorm itself when h8_ready), FF1 on the fp8 MFMA with the GELU epilogue writing
-    // e4m3, FF2 likewise with the gated-residual epilogue (gemm_fp8.hip)
-    K5CHK(d->ws_h8.ensure((size_t)rows * D)); K5CHK(d->ws_ff8.ensure((size_t)rows * FF));
-    if (!h8_ready) {
-      Scope sc(d, s, "elementwise");
-      K5CHK(k5_launch_quant_rows_fp8(h, d->ws_h8.p, nullptr, rows, D, D, D, s));
-    }
-    Scope sc(d, s, "gemm");
-    K5CHK(k5_launch_gemm_fp8(d->ws_h8.p, b.w1_f8.p, b.s1_f8.as<float>(), d->ws_ff8.p, rows, FF, D, D, D, FF, K5_EPI_GELU, nullptr, 0, nullptr, s));
-    K5CHK(k5_launch_gemm_fp8(d->ws_ff8.p, b.w2_f8.p, b.s2_f8.as<float>(), resid, rows, D, FF, FF, FF, D, K5_EPI_GATE, resid, D, gate, s));
-    return K5_OK;
-  }
+  // opt-in lossy path (ff_fp8_in): h -> e4m3 (static scale; by the LayerNorm itself when h8_ready), FF1 on the fp8 MFMA with the GELU epilogue
+  // writing e4m3 into ws_ff8, FF2 reading that, likewise with the gated-residual epilogue (gemm_fp8.hip)
+  const bool f8 = ff_fp8_in(d, b, rows);
+  if (f8) K5CHK(d->ws_ff8.ensure((size_t)rows * FF));
+  Act x;
+  K5CHK(e4m3_rows(d, s, h, rows, f8, h8_ready, x));
+  LinearArgs g1(b.w1, x, f8 ? d->ws_ff8.p : ff, FF, s), g2(b.w2, Act{ff, f8 ? d->ws_ff8.p : nullptr, rows, FF}, resid, D, s);
+  g1.epi = K5_EPI_GELU;
+  g2.epi = K5_EPI_GATE; g2.resid = resid; g2.ldr = D; g2.gate = gate;
   Scope sc(d, s, "gemm");
-  K5CHK(k5_launch_gemm_bf16(h, b.w1.p, nullptr, ff, rows, FF, D, D, D, FF, K5_EPI_GELU, nullptr, 0, nullptr, s));
-  K5CHK(k5_launch_gemm_bf16(ff, b.w2.p, nullptr, resid, rows, D, FF, FF, FF, D, K5_EPI_GATE, resid, D, gate, s));
-  return K5_OK;
+  K5CHK(linear(g1));
+  return linear(g2);
 }
 
 // forget which heads the per-row-offset softmax served badly (AttnW::pref): the memory is a speed hint for the NEXT step of the SAME sampling
@@ -1726,12 +1783,10 @@ int text_embeddings(k5_dit* d, hipStream_t s, const k5_text_cond& c, k5_dit::Tex
   const void* text_bf; const void* pool_bf;
   K5CHK(to_bf16(d, s, c.text_embed, c.text_dtype, (size_t)L * cfg.in_text_dim, d->ws_text_in, &text_bf));
   if (pooled) K5CHK(to_bf16(d, s, c.pooled_embed, c.text_dtype, (size_t)cfg.in_text_dim2, d->ws_pool_in, &pool_bf));
-  K5CHK(k5_launch_gemm_bf16(text_bf, d->text_w.p, d->text_b.as<float>(), d->ws_th.p, L, D, cfg.in_text_dim, cfg.in_text_dim,
-                            cfg.in_text_dim, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+  K5CHK(linear(LinearArgs(d->text_lin, Act{text_bf, nullptr, L, cfg.in_text_dim}, d->ws_th.p, D, s)));
   K5CHK(k5_launch_ln_affine(d->ws_th.p, d->text_lnw.as<float>(), d->text_lnb.as<float>(), st.text.p, nullptr, L, D, s));
   if (pooled) {
-    K5CHK(k5_launch_gemm_bf16(pool_bf, d->pool_w.p, d->pool_b.as<float>(), d->ws_pool_lin.p, 1, d->TD, cfg.in_text_dim2,
-                              cfg.in_text_dim2, cfg.in_text_dim2, d->TD, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+    K5CHK(linear(LinearArgs(d->pool_lin, Act{pool_bf, nullptr, 1, cfg.in_text_dim2}, d->ws_pool_lin.p, d->TD, s)));
     K5CHK(k5_launch_ln_affine(d->ws_pool_lin.p, d->pool_lnw.as<float>(), d->pool_lnb.as<float>(), nullptr,
                               d->ws_pool_f32.as<float>(), 1, d->TD, s));
   }
@@ -1895,8 +1950,7 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
                              (int)d->mod_rows, d->TD, 1, nullptr, s));
     if (vcond) K5CHK(k5_launch_patchify_cond(x, vcond, d->ws_xp.p, a->T, a->H, a->W, x_channels, Cin, d->KvisPad, perm, s));
     else K5CHK(k5_launch_patchify(x, d->ws_xp.p, a->T, a->H, a->W, x_channels, Cin, d->KvisPad, perm, s));
-    K5CHK(k5_launch_gemm_bf16(d->ws_xp.as<bf16_t>() + (size_t)tok0 * d->KvisPad, d->vis_w.p, d->vis_b.as<float>(), d->ws_vis.p,
-                              n, D, d->KvisPad, d->KvisPad, d->KvisPad, D, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+    K5CHK(linear(LinearArgs(d->vis_lin, Act{d->ws_xp.as<bf16_t>() + (size_t)tok0 * d->KvisPad, nullptr, n, d->KvisPad}, d->ws_vis.p, D, s)));
   }
   K5CHK(text_blocks_run(d, s, base, tcos, tsin, mod));
   // ---- MagCache decision (magcache_utils.py:59-76), float64 like the reference's numpy scalars ----
@@ -1931,7 +1985,7 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     HIPCHK(hipMemcpyAsync(cl.res[cslot][ccur].p, d->ws_vis.p, vis_elems * 2, hipMemcpyDeviceToDevice, s));  // ori_visual_embed
   }
   // ---- visual blocks (dit.py:176-178, 61-79) ----
-  const bool cx_all = !mag_skip && d->cross_kv_batched && c.num_visual_blocks > 1 && d->cx_wk_all.p;
+  const bool cx_all = !mag_skip && d->cross_kv_batched && c.num_visual_blocks > 1 && d->cx_k.w.p;
   if (!mag_skip) K5CHK(text_cross_kv(d, s, base, cx_all));
   // ---- the text streams of this forward's cross-attentions, in launch order, and where each one's attention output goes: the forward's own
   // prompt, then the negative one of k5_dit_set_nag, then the regions' of k5_dit_set_regions; nothing but the first on a step MagCache skips ----
@@ -2029,8 +2083,7 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     Scope sc(d, s, "epilogue");
     const float* m = mod + d->out_mod_off;  // [shift | scale]
     K5CHK(k5_launch_ln_modulate(d->ws_vis.p, m + D, m, d->ws_h.p, n, D, D, D, s));
-    K5CHK(k5_launch_gemm_bf16(d->ws_h.p, d->out_w.p, d->out_b.as<float>(), d->ws_y.as<bf16_t>() + (size_t)tok0 * d->Fout, n,
-                              d->Fout, D, D, D, d->Fout, K5_EPI_BIAS, nullptr, 0, nullptr, s));
+    K5CHK(linear(LinearArgs(d->out_lin, Act{d->ws_h.p, nullptr, n, D}, d->ws_y.as<bf16_t>() + (size_t)tok0 * d->Fout, d->Fout, s)));
     // every rank needs the whole velocity: the (replicated) latent is advanced identically on all ranks
     if (sp) K5CHK(d->comm.all_gather_inplace(d->ws_y.p, (size_t)n_pad * d->Fout, 2, s));
     K5CHK(k5_launch_unpatchify(d->ws_y.p, out, Tp, Hp, Wp, c.out_visual_dim, d->Fout, perm, s));
@@ -2081,8 +2134,7 @@ extern "C" int k5_dit_create(const k5_dit_config* cfg, k5_dit** out) {
 extern "C" void k5_dit_destroy(k5_dit* d) {
   if (!d) return;
   // DevBufs are released with the process; explicit frees for long-lived hosts:
-  DevBuf* all[] = {&d->time_w1, &d->time_b1, &d->time_w2, &d->time_b2, &d->text_w, &d->text_b, &d->text_lnw, &d->text_lnb,
-                   &d->pool_w, &d->pool_b, &d->pool_lnw, &d->pool_lnb, &d->vis_w, &d->vis_b, &d->out_w, &d->out_b, &d->mod_w,
+  DevBuf* all[] = {&d->time_w1, &d->time_b1, &d->time_w2, &d->time_b2, &d->text_lnw, &d->text_lnb, &d->pool_lnw, &d->pool_lnb, &d->mod_w,
                    &d->mod_b, &d->ws_text_in, &d->ws_th, &d->ws_tqk, &d->ws_tvt, &d->ws_to, &d->ws_tff,
                    &d->ws_pool_in, &d->ws_pool_lin, &d->ws_pool_f32, &d->ws_time, &d->ws_tfeat, &d->ws_th1, &d->ws_temb,
                    &d->ws_mod, &d->ws_xp, &d->ws_vis, &d->ws_h, &d->ws_qk, &d->ws_vt, &d->ws_o, &d->ws_ff,
@@ -2098,7 +2150,6 @@ extern "C" void k5_dit_destroy(k5_dit* d) {
   d->nag.o.release(); d->regions.o.release(); d->regions.w.release(); d->skip.vis.release(); d->skip.vel.release();
   for (auto& kv : d->staged) kv.second.dev.release();   // a handle destroyed before finalize still holds its staged matrices
   d->mag.residual[0].release(); d->mag.residual[1].release(); d->mag.pm_one.release();
-  for (auto& b : d->vblocks) { b.w1_f8.release(); b.w2_f8.release(); b.s1_f8.release(); b.s2_f8.release(); }
   if (d->graph_stream) { (void)hipStreamSynchronize(d->graph_stream); (void)hipStreamDestroy(d->graph_stream); (void)hipEventDestroy(d->ev_graph); }
   if (d->comm_stream) { (void)hipStreamSynchronize(d->comm_stream); (void)hipStreamDestroy(d->comm_stream); }
   for (hipEvent_t e : {d->ev_k, d->ev_v, d->ev_gathered, d->ev_stats, d->ev_means, d->ev_slice[0], d->ev_slice[1], d->ev_slice[2], d->ev_slice[3]}) if (e) (void)hipEventDestroy(e); d->ws_perm.release(); d->ws_nabla.release();
@@ -2114,13 +2165,7 @@ extern "C" void k5_dit_destroy(k5_dit* d) {
     if (d->watch.h_rgb[i]) (void)hipHostFree(d->watch.h_rgb[i]);
     if (d->watch.ev[i]) (void)hipEventDestroy(d->watch.ev[i]);
   }
-  auto rel_attn = [](AttnW& a) {
-    DevBuf* bs[] = {&a.wqk, &a.wq, &a.wk, &a.wv, &a.wo, &a.bqk, &a.bq, &a.bk, &a.bv, &a.bo, &a.norm};
-    for (DevBuf* b : bs) b->release();
-  };
-  for (auto* v : {&d->tblocks, &d->vblocks})
-    for (auto& b : *v) { rel_attn(b.self_attn); rel_attn(b.cross_attn); b.w1.release(); b.w2.release(); }
-  delete d;
+  delete d;   // the layers (Linear) and everything else a DevBuf holds go with the handle
 }
 
 extern "C" int k5_dit_load_tensor(k5_dit* d, const char* key, const void* host_ptr, int dtype, const int64_t* shape, int rank) {
@@ -2173,40 +2218,24 @@ extern "C" int k5_dit_finalize(k5_dit* d) {
   if (k5_dit_missing_keys(d)) return K5_ERR_KEY;
   const k5_dit_config& c = d->cfg;
   const size_t D = d->D, FF = d->FF, TD = d->TD;
-  auto shape_is = [&](const char* k, size_t r, size_t cc) -> bool {
-    const HostTensor* t = find(d, k);
-    const bool ok = t && ((cc == 0 && t->shape.size() == 1 && (size_t)t->shape[0] == r) ||
-                          (cc && t->shape.size() == 2 && (size_t)t->shape[0] == r && (size_t)t->shape[1] == cc));
-    if (!ok) k5_set_error("shape mismatch for %s", k);
-    return ok;
-  };
-  if (!shape_is("time_embeddings.in_layer.weight", TD, D) || !shape_is("time_embeddings.out_layer.weight", TD, TD) ||
-      !shape_is("text_embeddings.in_layer.weight", D, c.in_text_dim) ||
-      !shape_is("pooled_text_embeddings.in_layer.weight", TD, c.in_text_dim2) ||
-      !shape_is("visual_embeddings.in_layer.weight", D, d->Kvis) || !shape_is("out_layer.out_layer.weight", d->Fout, D) ||
-      !shape_is("out_layer.modulation.out_layer.weight", 2 * D, TD) ||
-      !shape_is("time_embeddings.in_layer.bias", TD, 0) || !shape_is("time_embeddings.out_layer.bias", TD, 0) ||
-      !shape_is("text_embeddings.in_layer.bias", D, 0) || !shape_is("text_embeddings.norm.weight", D, 0) ||
-      !shape_is("text_embeddings.norm.bias", D, 0) || !shape_is("pooled_text_embeddings.in_layer.bias", TD, 0) ||
-      !shape_is("pooled_text_embeddings.norm.weight", TD, 0) || !shape_is("pooled_text_embeddings.norm.bias", TD, 0) ||
-      !shape_is("visual_embeddings.in_layer.bias", D, 0) || !shape_is("out_layer.out_layer.bias", d->Fout, 0))
+  if (!shape_ok(d, "time_embeddings.in_layer.weight", TD, D) || !shape_ok(d, "time_embeddings.out_layer.weight", TD, TD) ||
+      !shape_ok(d, "out_layer.modulation.out_layer.weight", 2 * D, TD) ||
+      !shape_ok(d, "time_embeddings.in_layer.bias", TD, 0) || !shape_ok(d, "time_embeddings.out_layer.bias", TD, 0) ||
+      !shape_ok(d, "text_embeddings.norm.weight", D, 0) || !shape_ok(d, "text_embeddings.norm.bias", D, 0) ||
+      !shape_ok(d, "pooled_text_embeddings.norm.weight", TD, 0) || !shape_ok(d, "pooled_text_embeddings.norm.bias", TD, 0))
     return K5_ERR_ARG;
   K5CHK(pack_f32(d->time_w1, find(d, "time_embeddings.in_layer.weight"), TD, D));
   K5CHK(upload_f32(d->time_b1, find(d, "time_embeddings.in_layer.bias")->data.data(), TD));
   K5CHK(pack_f32(d->time_w2, find(d, "time_embeddings.out_layer.weight"), TD, TD));
   K5CHK(upload_f32(d->time_b2, find(d, "time_embeddings.out_layer.bias")->data.data(), TD));
-  K5CHK(pack_bf16(d->text_w, find(d, "text_embeddings.in_layer.weight"), D, c.in_text_dim, c.in_text_dim));
-  K5CHK(upload_bias_bf16r(d->text_b, find(d, "text_embeddings.in_layer.bias")->data.data(), D));
+  K5CHK(load_linear(d, d->text_lin, {"text_embeddings.in_layer"}, D, c.in_text_dim, c.in_text_dim));
   K5CHK(upload_f32(d->text_lnw, find(d, "text_embeddings.norm.weight")->data.data(), D));
   K5CHK(upload_f32(d->text_lnb, find(d, "text_embeddings.norm.bias")->data.data(), D));
-  K5CHK(pack_bf16(d->pool_w, find(d, "pooled_text_embeddings.in_layer.weight"), TD, c.in_text_dim2, c.in_text_dim2));
-  K5CHK(upload_bias_bf16r(d->pool_b, find(d, "pooled_text_embeddings.in_layer.bias")->data.data(), TD));
+  K5CHK(load_linear(d, d->pool_lin, {"pooled_text_embeddings.in_layer"}, TD, c.in_text_dim2, c.in_text_dim2));
   K5CHK(upload_f32(d->pool_lnw, find(d, "pooled_text_embeddings.norm.weight")->data.data(), TD));
   K5CHK(upload_f32(d->pool_lnb, find(d, "pooled_text_embeddings.norm.bias")->data.data(), TD));
-  K5CHK(pack_bf16(d->vis_w, find(d, "visual_embeddings.in_layer.weight"), D, d->Kvis, d->KvisPad));
-  K5CHK(upload_bias_bf16r(d->vis_b, find(d, "visual_embeddings.in_layer.bias")->data.data(), D));
-  K5CHK(pack_bf16(d->out_w, find(d, "out_layer.out_layer.weight"), d->Fout, D, D));
-  K5CHK(upload_bias_bf16r(d->out_b, find(d, "out_layer.out_layer.bias")->data.data(), d->Fout));
+  K5CHK(load_linear(d, d->vis_lin, {"visual_embeddings.in_layer"}, D, d->Kvis, d->KvisPad));
+  K5CHK(load_linear(d, d->out_lin, {"out_layer.out_layer"}, d->Fout, D, D));
 
   // stacked modulation
   d->mod_rows = (size_t)c.num_text_blocks * 6 * D + (size_t)c.num_visual_blocks * 9 * D + 2 * D;
@@ -2226,9 +2255,8 @@ extern "C" int k5_dit_finalize(k5_dit* d) {
     d->tblocks[i].mod_off = off;
     if (!put_mod(p + ".text_modulation.out_layer", 6 * D)) return K5_ERR_ARG;
     K5CHK(pack_attn(d, p + ".self_attention", d->tblocks[i].self_attn, true));
-    if (!shape_ok(d, p + ".feed_forward.in_layer.weight", FF, D) || !shape_ok(d, p + ".feed_forward.out_layer.weight", D, FF)) return K5_ERR_ARG;
-    K5CHK(pack_bf16(d->tblocks[i].w1, find(d, p + ".feed_forward.in_layer.weight"), FF, D, D));
-    K5CHK(pack_bf16(d->tblocks[i].w2, find(d, p + ".feed_forward.out_layer.weight"), D, FF, FF));
+    K5CHK(load_linear(d, d->tblocks[i].w1, {p + ".feed_forward.in_layer"}, FF, D, D, false));
+    K5CHK(load_linear(d, d->tblocks[i].w2, {p + ".feed_forward.out_layer"}, D, FF, FF, false));
   }
   for (int i = 0; i < c.num_visual_blocks; ++i) {
     const std::string p = "visual_transformer_blocks." + std::to_string(i);
@@ -2236,37 +2264,23 @@ extern "C" int k5_dit_finalize(k5_dit* d) {
     if (!put_mod(p + ".visual_modulation.out_layer", 9 * D)) return K5_ERR_ARG;
     K5CHK(pack_attn(d, p + ".self_attention", d->vblocks[i].self_attn, true));
     K5CHK(pack_attn(d, p + ".cross_attention", d->vblocks[i].cross_attn, false));
-    if (!shape_ok(d, p + ".feed_forward.in_layer.weight", FF, D) || !shape_ok(d, p + ".feed_forward.out_layer.weight", D, FF)) return K5_ERR_ARG;
-    K5CHK(pack_bf16(d->vblocks[i].w1, find(d, p + ".feed_forward.in_layer.weight"), FF, D, D));
-    K5CHK(pack_bf16(d->vblocks[i].w2, find(d, p + ".feed_forward.out_layer.weight"), D, FF, FF));
+    K5CHK(load_linear(d, d->vblocks[i].w1, {p + ".feed_forward.in_layer"}, FF, D, D, false));
+    K5CHK(load_linear(d, d->vblocks[i].w2, {p + ".feed_forward.out_layer"}, D, FF, FF, false));
   }
-  {   // stacked cross-attention key / value weights of the visual blocks (device-to-device copies of the packed per-block buffers)
-    const size_t nbv = (size_t)c.num_visual_blocks;
-    if (nbv) {
-      K5CHK(d->cx_wk_all.ensure(nbv * D * D * 2)); K5CHK(d->cx_wv_all.ensure(nbv * D * D * 2));
-      K5CHK(d->cx_bk_all.ensure(nbv * D * 4)); K5CHK(d->cx_bv_all.ensure(nbv * D * 4)); K5CHK(d->cx_knorm_all.ensure(nbv * 64 * 4));
-      bool complete = true;
-      for (size_t i = 0; i < nbv && complete; ++i) {
-        const AttnW& a = d->vblocks[i].cross_attn;
-        complete = a.wk.p && a.wv.p && a.bk.p && a.bv.p && a.norm.p;
-      }
-      if (!complete) {
-        d->cross_kv_batched = 0;
-        d->cx_wk_all.release(); d->cx_wv_all.release(); d->cx_bk_all.release(); d->cx_bv_all.release(); d->cx_knorm_all.release();
-      }
-      // the stacked copy REPLACES the per-block buffers (they become views into it) instead of doubling them — 4 nbv D^2 bytes, 411 MB on
-      // 2B-Lite; the per-block path ("cross_kv_batched" = 0) reads the same memory through the views
-      for (size_t i = 0; i < nbv && complete; ++i) {
-        AttnW& a = d->vblocks[i].cross_attn;
-        char* wk = (char*)d->cx_wk_all.p + i * D * D * 2; char* wv = (char*)d->cx_wv_all.p + i * D * D * 2;
-        char* bk = (char*)d->cx_bk_all.p + i * D * 4; char* bv = (char*)d->cx_bv_all.p + i * D * 4;
-        HIPCHK(hipMemcpy(wk, a.wk.p, D * D * 2, hipMemcpyDeviceToDevice));
-        HIPCHK(hipMemcpy(wv, a.wv.p, D * D * 2, hipMemcpyDeviceToDevice));
-        HIPCHK(hipMemcpy(bk, a.bk.p, D * 4, hipMemcpyDeviceToDevice));
-        HIPCHK(hipMemcpy(bv, a.bv.p, D * 4, hipMemcpyDeviceToDevice));
-        HIPCHK(hipMemcpy((char*)d->cx_knorm_all.p + i * 64 * 4, a.norm.as<float>() + 64, 64 * 4, hipMemcpyDeviceToDevice));
-        a.wk.alias(wk, D * D * 2); a.wv.alias(wv, D * D * 2); a.bk.alias(bk, D * 4); a.bv.alias(bv, D * 4);
-      }
+  // The cross-attention key / value layers of all visual blocks are packed once, stacked (4 nbv D^2 bytes, 411 MB on 2B-Lite, not
+  // held twice); a block's own wk / wv are views of its rows, so the per-block path ("cross_kv_batched" = 0) reads the same memory
+  if (const size_t nbv = (size_t)c.num_visual_blocks) {
+    std::vector<std::string> pk, pv;
+    for (size_t i = 0; i < nbv; ++i) {
+      const std::string p = "visual_transformer_blocks." + std::to_string(i) + ".cross_attention";
+      pk.push_back(p + ".to_key"); pv.push_back(p + ".to_value");
+    }
+    K5CHK(load_linear(d, d->cx_k, pk, D, D, D)); K5CHK(load_linear(d, d->cx_v, pv, D, D, D));
+    K5CHK(d->cx_knorm_all.ensure(nbv * 64 * 4));
+    for (size_t i = 0; i < nbv; ++i) {
+      AttnW& a = d->vblocks[i].cross_attn;
+      HIPCHK(hipMemcpy((char*)d->cx_knorm_all.p + i * 64 * 4, a.norm.as<float>() + 64, 64 * 4, hipMemcpyDeviceToDevice));
+      a.wk = d->cx_k.rows(i * D, D); a.wv = d->cx_v.rows(i * D, D);
     }
   }
   d->out_mod_off = off;
@@ -3215,19 +3229,14 @@ extern "C" int k5_dit_set_fp8(k5_dit* d, int enabled) {
   if (enabled && ((d->D % 128) || (d->FF % 128) || d->D < 256 || d->FF < 256)) {
     k5_set_error("k5_dit_set_fp8: model_dim and ff_dim must be multiples of 128 and >= 256"); return K5_ERR_UNSUPPORTED;
   }
-  const size_t D = d->D, FF = d->FF;
-  auto quant = [&](const DevBuf& w, DevBuf& w8, DevBuf& sc, size_t rows, size_t K) -> int {
-    if (w8.p) return K5_OK;
-    K5CHK(w8.ensure(rows * K)); K5CHK(sc.ensure(rows * 4));
-    return k5_launch_quant_rows_fp8(w.p, w8.p, sc.as<float>(), (int)rows, (int)K, (int)K, (int)K, nullptr);
-  };
+  // a copy that exists is current (the LoRA paths refresh it) and is kept when its bit goes away: only the mask decides what runs in e4m3
   for (auto& b : d->vblocks) {
-    if (enabled & 1) { K5CHK(quant(b.w1, b.w1_f8, b.s1_f8, FF, D)); K5CHK(quant(b.w2, b.w2_f8, b.s2_f8, D, FF)); }
-    if (enabled & 2) { K5CHK(quant(b.self_attn.wqk, b.self_attn.wqk8, b.self_attn.sqk, 2 * D, D)); K5CHK(quant(b.self_attn.wv, b.self_attn.wv8, b.self_attn.sv, D, D)); }
-    if (enabled & 4) K5CHK(quant(b.self_attn.wo, b.self_attn.wo8, b.self_attn.so, D, D));
+    auto ensure_e4m3 = [](Linear& l) { return l.has_e4m3() ? K5_OK : l.quantise(true); };
+    if (enabled & 1) { K5CHK(ensure_e4m3(b.w1)); K5CHK(ensure_e4m3(b.w2)); }
+    if (enabled & 2) { K5CHK(ensure_e4m3(b.self_attn.wqk)); K5CHK(ensure_e4m3(b.self_attn.wv)); }
+    if (enabled & 4) K5CHK(ensure_e4m3(b.self_attn.wo));
   }
   HIPCHK(hipDeviceSynchronize());
-  d->use_fp8 = (enabled & 1) != 0;
   d->fp8_mask = enabled;
   return K5_OK;
 }
@@ -3236,8 +3245,8 @@ extern "C" int k5_dit_set_fp8(k5_dit* d, int enabled) {
 // LoRA adapters: merge into the packed weights in place, and undo (include/k5.h)
 // ---------------------------------------------------------------------------------------------
 namespace {
-struct LoraTarget { void* p = nullptr; bool bf16 = true; size_t rows = 0, cols = 0, ld = 0; int vblock = -1, f8 = 0; };
-enum { LORA_F8_NONE = 0, LORA_F8_W1, LORA_F8_W2, LORA_F8_QK, LORA_F8_V, LORA_F8_O };
+// lin: the layer the matrix is (a row range of), whose e4m3 copy has to follow the merge; null: one of the fp32 matrices
+struct LoraTarget { void* p = nullptr; bool bf16 = true; size_t rows = 0, cols = 0, ld = 0; Linear* lin = nullptr; };
 
 // state_dict weight key -> the packed matrix it went into (k5_dit_finalize / pack_attn).  K5_ERR_KEY: not a key of this layout;
 // K5_ERR_UNSUPPORTED: a rank-1 tensor (bias, norm)
@@ -3250,17 +3259,19 @@ int lora_target(k5_dit* d, const std::string& key, LoraTarget& t) {
   if (!is_weight || key.find("norm.weight") != std::string::npos) {
     k5_set_error("k5_dit_add_lora: %s is a rank-1 tensor (bias / norm): LoRA applies to linear weights only", key.c_str()); return K5_ERR_UNSUPPORTED;
   }
-  const size_t D = d->D, FF = d->FF, TD = d->TD;
-  auto set = [&](void* p, bool bf16, size_t rows, size_t cols, size_t ld, int vb = -1, int f8 = LORA_F8_NONE) {
-    t.p = p; t.bf16 = bf16; t.rows = rows; t.cols = cols; t.ld = ld; t.vblock = vb; t.f8 = f8;
+  const size_t D = d->D, TD = d->TD;
+  auto f32 = [&](void* p, size_t rows, size_t cols) { t.p = p; t.bf16 = false; t.rows = rows; t.cols = t.ld = cols; };
+  auto mod = [&](size_t off, size_t rows) { f32(d->mod_w.as<float>() + off * TD, rows, TD); };
+  // rows [row0, row0 + n) of a layer; n = 0: all of it
+  auto lin = [&](Linear& l, size_t row0 = 0, size_t n = 0) {
+    t.p = l.w.as<bf16_t>() + row0 * l.ld; t.bf16 = true; t.rows = n ? n : (size_t)l.N; t.cols = l.K; t.ld = l.ld; t.lin = &l;
   };
-  auto mod = [&](size_t off, size_t rows) { set(d->mod_w.as<float>() + off * TD, false, rows, TD, TD); };
-  if (key == "time_embeddings.in_layer.weight") set(d->time_w1.p, false, TD, D, D);
-  else if (key == "time_embeddings.out_layer.weight") set(d->time_w2.p, false, TD, TD, TD);
-  else if (key == "text_embeddings.in_layer.weight") set(d->text_w.p, true, D, d->cfg.in_text_dim, d->cfg.in_text_dim);
-  else if (key == "pooled_text_embeddings.in_layer.weight") set(d->pool_w.p, true, TD, d->cfg.in_text_dim2, d->cfg.in_text_dim2);
-  else if (key == "visual_embeddings.in_layer.weight") set(d->vis_w.p, true, D, d->Kvis, d->KvisPad);
-  else if (key == "out_layer.out_layer.weight") set(d->out_w.p, true, d->Fout, D, D);
+  if (key == "time_embeddings.in_layer.weight") f32(d->time_w1.p, TD, D);
+  else if (key == "time_embeddings.out_layer.weight") f32(d->time_w2.p, TD, TD);
+  else if (key == "text_embeddings.in_layer.weight") lin(d->text_lin);
+  else if (key == "pooled_text_embeddings.in_layer.weight") lin(d->pool_lin);
+  else if (key == "visual_embeddings.in_layer.weight") lin(d->vis_lin);
+  else if (key == "out_layer.out_layer.weight") lin(d->out_lin);
   else if (key == "out_layer.modulation.out_layer.weight") mod(d->out_mod_off, 2 * D);
   else {
     const bool text = key.rfind("text_transformer_blocks.", 0) == 0, vis = key.rfind("visual_transformer_blocks.", 0) == 0;
@@ -3272,42 +3283,21 @@ int lora_target(k5_dit* d, const std::string& key, LoraTarget& t) {
     if (i < 0 || (size_t)i >= blocks.size()) { k5_set_error("k5_dit_add_lora: no packed matrix for %s", key.c_str()); return K5_ERR_KEY; }
     BlockW& b = blocks[i];
     const std::string rest = key.substr(dot + 1);
-    const int vb = vis ? i : -1;
     if (rest == "text_modulation.out_layer.weight") mod(b.mod_off, 6 * D);
     else if (rest == "visual_modulation.out_layer.weight") mod(b.mod_off, 9 * D);
-    else if (rest == "self_attention.to_query.weight") set(b.self_attn.wqk.p, true, D, D, D, vb, LORA_F8_QK);
-    else if (rest == "self_attention.to_key.weight") set(b.self_attn.wqk.as<bf16_t>() + D * D, true, D, D, D, vb, LORA_F8_QK);
-    else if (rest == "self_attention.to_value.weight") set(b.self_attn.wv.p, true, D, D, D, vb, LORA_F8_V);
-    else if (rest == "self_attention.out_layer.weight") set(b.self_attn.wo.p, true, D, D, D, vb, LORA_F8_O);
-    else if (rest == "cross_attention.to_query.weight") set(b.cross_attn.wq.p, true, D, D, D);
-    else if (rest == "cross_attention.to_key.weight") set(b.cross_attn.wk.p, true, D, D, D);      // a view into cx_wk_all
-    else if (rest == "cross_attention.to_value.weight") set(b.cross_attn.wv.p, true, D, D, D);    // a view into cx_wv_all
-    else if (rest == "cross_attention.out_layer.weight") set(b.cross_attn.wo.p, true, D, D, D);
-    else if (rest == "feed_forward.in_layer.weight") set(b.w1.p, true, FF, D, D, vb, LORA_F8_W1);
-    else if (rest == "feed_forward.out_layer.weight") set(b.w2.p, true, D, FF, FF, vb, LORA_F8_W2);
+    else if (rest == "self_attention.to_query.weight") lin(b.self_attn.wqk, 0, D);
+    else if (rest == "self_attention.to_key.weight") lin(b.self_attn.wqk, D, D);
+    else if (rest == "self_attention.to_value.weight") lin(b.self_attn.wv);
+    else if (rest == "self_attention.out_layer.weight") lin(b.self_attn.wo);
+    else if (rest == "cross_attention.to_query.weight") lin(b.cross_attn.wq);
+    else if (rest == "cross_attention.to_key.weight") lin(b.cross_attn.wk);      // a view into cx_k: the merge writes the stacked memory
+    else if (rest == "cross_attention.to_value.weight") lin(b.cross_attn.wv);    // a view into cx_v
+    else if (rest == "cross_attention.out_layer.weight") lin(b.cross_attn.wo);
+    else if (rest == "feed_forward.in_layer.weight") lin(b.w1);
+    else if (rest == "feed_forward.out_layer.weight") lin(b.w2);
     else { k5_set_error("k5_dit_add_lora: no packed matrix for %s", key.c_str()); return K5_ERR_KEY; }
   }
   if (!t.p) { k5_set_error("k5_dit_add_lora: internal: %s is not packed", key.c_str()); return K5_ERR_STATE; }
-  return K5_OK;
-}
-
-// the e4m3 copy and scales of a visual block's matrix, where k5_dit_set_fp8 made one: quantised again from the current bf16 bits (per output
-// channel, so rows an adapter did not touch come out as they were)
-int lora_requant(k5_dit* d, int vblock, int f8) {
-  if (vblock < 0 || f8 == LORA_F8_NONE) return K5_OK;
-  BlockW& b = d->vblocks[vblock];
-  const size_t D = d->D, FF = d->FF;
-  auto quant = [&](const DevBuf& w, DevBuf& w8, DevBuf& sc, size_t rows, size_t K) -> int {
-    if (!w8.p) return K5_OK;
-    return k5_launch_quant_rows_fp8(w.p, w8.p, sc.as<float>(), (int)rows, (int)K, (int)K, (int)K, nullptr);
-  };
-  switch (f8) {
-    case LORA_F8_W1: return quant(b.w1, b.w1_f8, b.s1_f8, FF, D);
-    case LORA_F8_W2: return quant(b.w2, b.w2_f8, b.s2_f8, D, FF);
-    case LORA_F8_QK: return quant(b.self_attn.wqk, b.self_attn.wqk8, b.self_attn.sqk, 2 * D, D);
-    case LORA_F8_V: return quant(b.self_attn.wv, b.self_attn.wv8, b.self_attn.sv, D, D);
-    case LORA_F8_O: return quant(b.self_attn.wo, b.self_attn.wo8, b.self_attn.so, D, D);
-  }
   return K5_OK;
 }
 
@@ -3344,7 +3334,7 @@ extern "C" int k5_dit_add_lora(k5_dit* d, const char* key, const void* A, int a_
     k5_dit::LoraBackup bk;
     K5CHK(bk.copy.ensure(bytes));
     HIPCHK(hipMemcpyAsync(bk.copy.p, t.p, bytes, hipMemcpyDeviceToDevice, nullptr));
-    bk.bytes = bytes; bk.vblock = t.vblock; bk.f8 = t.f8;
+    bk.bytes = bytes; bk.lin = t.lin;
     d->lora_backup[t.p] = std::move(bk);
   }
   // the factors: device copies of whatever memory they are in (hipMemcpyDefault, as k5_dit_load_tensor)
@@ -3354,7 +3344,7 @@ extern "C" int k5_dit_add_lora(k5_dit* d, const char* key, const void* A, int a_
   HIPCHK(hipMemcpy(fa.p, A, abytes, hipMemcpyDefault));
   HIPCHK(hipMemcpy(fb.p, B, bbytes, hipMemcpyDefault));
   K5CHK(k5_launch_lora_merge(t.p, t.bf16 ? K5_BF16 : K5_F32, (int)t.rows, (int)t.cols, (int)t.ld, fa.p, a_dtype, fb.p, b_dtype, R, scale, nullptr));
-  K5CHK(lora_requant(d, t.vblock, t.f8));
+  if (t.lin) K5CHK(t.lin->quantise(false));   // where k5_dit_set_fp8 made an e4m3 copy, it follows the merged bits
   K5CHK(lora_drop_derived(d));
   HIPCHK(hipDeviceSynchronize());   // fa / fb are freed on return
   return K5_OK;
@@ -3368,7 +3358,7 @@ extern "C" int k5_dit_clear_lora(k5_dit* d) {
   HIPCHK(hipDeviceSynchronize());
   for (auto& kv : d->lora_backup)
     HIPCHK(hipMemcpyAsync(kv.first, kv.second.copy.p, kv.second.bytes, hipMemcpyDeviceToDevice, nullptr));
-  for (auto& kv : d->lora_backup) K5CHK(lora_requant(d, kv.second.vblock, kv.second.f8));
+  for (auto& kv : d->lora_backup) if (kv.second.lin) K5CHK(kv.second.lin->quantise(false));
   K5CHK(lora_drop_derived(d));
   HIPCHK(hipDeviceSynchronize());
   d->lora_backup.clear();

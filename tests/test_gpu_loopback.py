@@ -370,11 +370,16 @@ def test_tiny_forward_sliced_exchange(golden_meta, tiny_sd, P, T, S):
 
 
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize("P,W,gain,S", [(8, 48, 1.0, 2), (4, 48, 3.0, 2), (4, 48, 1.0, 4)])
-def test_full_width_forward_sliced_exchange(P, W, gain, S):
+@pytest.mark.parametrize("P,W,gain,S,fp8", [(8, 48, 1.0, 2, 0), (4, 48, 3.0, 2, 0), (4, 48, 1.0, 4, 0), (2, 48, 1.0, 2, 3)])
+def test_full_width_forward_sliced_exchange(P, W, gain, S, fp8):
     """2B-Lite width, 2 visual blocks, the sliced exchange: (8, 48): 15 blocks in slots of 2 -> 7 x 2 + 1; gain 3 = online-max softmax
     on every head (the state that travels between the slice passes carries the running maximum); S = 4 on 15 blocks over 4 ranks:
-    slots of 4 -> 4 + 4 + 4 + 3."""
+    slots of 4 -> 4 + 4 + 4 + 3.
+    fp8 = 3 (k5_dit_set_fp8 mask, on the ranks and on the single handle): P = 2 -> slots of 8 + 7 blocks = 512 and 448 rows, so both
+    ranks take the e4m3 q | k projections and the V^T projection per slice from the e4m3 rows ("fp8_effective" = 3 on every rank).
+    Sharded vs single handle with the same mask: measured 1.0716e-2 (before and after the projections moved onto one Linear type: the
+    same bits).  The project's bound for this comparison is the 2.5e-2 of test_config5_sequence_length_P_ranks_on_one_gpu, 2.5 x its measured
+    1.0e-2; 1.0716e-2 leaves 2.33 x under it, so this case takes 2.5 x its own value: 2.679e-2."""
     from kandinsky.models.dit import DiffusionTransformer3D
     c = dict(O.LITE_2B, num_visual_blocks=2, num_text_blocks=1)
     sd = O.synthetic_state_dict(O.DitConfig(**c), seed=3)
@@ -391,17 +396,24 @@ def test_full_width_forward_sliced_exchange(P, W, gain, S):
     def make():
         d = DiffusionTransformer3D(**c)
         d.load_state_dict(sd, assign=True)
-        return d.to("cuda:0")
+        d = d.to("cuda:0")
+        if fp8:
+            d.engine("cuda:0")
+            d.set_fp8(fp8)
+        return d
 
     def call(d, r):
-        return d(x.cuda(), text.cuda(), pooled.cuda(), t, pos, torch.arange(37), scale_factor=(1.0, 2.0, 2.0))
+        out = d(x.cuda(), text.cuda(), pooled.cuda(), t, pos, torch.arange(37), scale_factor=(1.0, 2.0, 2.0))
+        return out, (d.get_option("fp8_effective") if fp8 else 0)
 
-    fused = call(make(), 0)
-    outs = run_ranks(P, make, call, slices=S)
+    fused, _ = call(make(), 0)
+    res = run_ranks(P, make, call, slices=S)
+    outs = [o for o, _ in res]
     for r in range(1, P):
         assert torch.equal(outs[r], outs[0]), f"rank {r} differs from rank 0"
-    print(f"sliced exchange P={P} S={S} gain={gain}: sharded vs fused rel-L2 {rel(outs[0], fused):.3e}")
-    assert rel(outs[0], fused) <= (6e-3 if gain == 1.0 else 1.5e-2), rel(outs[0], fused)
+    assert all(eff == fp8 for _, eff in res), [eff for _, eff in res]
+    print(f"sliced exchange P={P} S={S} gain={gain} fp8={fp8}: sharded vs fused rel-L2 {rel(outs[0], fused):.9e}")
+    assert rel(outs[0], fused) <= (2.679e-2 if fp8 else 6e-3 if gain == 1.0 else 1.5e-2), rel(outs[0], fused)
 
 
 # ------------------------------------------------------------------------------------------ CFG-parallel inside the engine
