@@ -410,6 +410,37 @@ int k5_x0_preview(const float* x, const void* v_cond, const void* v_uncond, floa
  * D > 2048 (the row is held in registers).  Nothing is launched when the call is refused. */
 int k5_nag_combine_bf16(const void* z_pos, const void* z_neg, void* out, int rows, int D, int ld, float s, float tau, float alpha,
                         void* stream);
+/* Enhance-A-Video, the rule (added under ABI 11, as the exports above were; Luo et al. 2025, "FETA" in the Wan /
+ * HunyuanVideo / CogVideoX wrappers).  For one forward and one visual block, let the latent have T frames and S = (H/2)(W/2) spatial
+ * positions, Hh heads of 64 columns; q[t,p,h] and k[t,p,h] are the query and the key after norm_qk + RoPE, weight >= 0:
+ *   z[t][u]  = (1/8) <q[t,p,h], k[u,p,h]>                  t, u in 0..T-1   (the block's own softmax scale)
+ *   P[t][.]  = softmax over u of z[t][.]                   row maximum subtracted; fp32
+ *   m(p,h)   = ( sum_{t != u} P[t][u] ) / (T (T - 1))
+ *   mean     = ( sum_{p,h} m(p,h) ) / (S Hh)               float64, fixed order, no atomics
+ *   score    = max(1, mean (T + weight))                   stored as fp32
+ *   o'       = bf16( float(o) score )                      the attention output, before the out projection
+ * This is the published feta_score / get_feta_scores form; ours: T < 2 (images) makes it inert, and the mean is per forward (the engine
+ * runs the conditional and the unconditional forward separately).  With d the mean diagonal probability, mean = (1 - d) / (T - 1): uniform
+ * attention gives score = 1 + weight / T.
+ * k5_enhance_scores_bf16 computes the score: Q and K are bf16 with 64 columns per head (row strides ldq / ldk elements; both may point into
+ * one fused [rows][2 * 64 Hh] buffer), the token row of (p, t) is frame_rows[p * T + t] (device int32 [S][T]; NULL: row = t * S + p; rows the
+ * table does not name and columns beyond 64 Hh are never read).  qk_scale multiplies the dot product and the softmax is taken in base 2: 1.0
+ * for keys already multiplied by log2(e) / 8, log2(e) / 8 for plain keys.  One workgroup per p, one wave per head; the T x T logits are K·Q^T
+ * on v_mfma_f32_32x32x16_bf16 with T padded to 32 or 64 (a padded key adds exactly 0, a padded query nothing); every wave writes its column's
+ * float64 sum to part[p * Hh + h] (part: device, k5_enhance_part_count(Hh, S) doubles) and a second, one-workgroup launch adds them in a fixed
+ * order and writes score_out[0] (device fp32).  No atomics: equal inputs give equal bits on every launch.
+ * K5_ERR_ARG: a NULL or not 16-byte aligned Q / K, a NULL part or score_out, ldq / ldk < 64 Hh or not a multiple of 8, Hh or S < 1, T < 2, a
+ * negative or non-finite weight, qk_scale <= 0 or not finite.  K5_ERR_UNSUPPORTED: T > 64 (a wave holds the column's logits in four 32 x 32
+ * accumulators).  Nothing is launched when the call is refused. */
+long long k5_enhance_part_count(int Hh, int S);
+int k5_enhance_scores_bf16(const void* Q, const void* K, int ldq, int ldk, int Hh, int T, int S,
+                           const int32_t* frame_rows /* device [S][T], NULL: row = t*S + p */,
+                           float qk_scale, float weight, double* part, float* score_out, void* stream);
+/* x bf16 [rows][ld] (D columns used) times the fp32 scalar at score_dev (device), in place: bf16(float(x) * s), nearest-even — torch's x * s
+ * for a bf16 tensor and a 0-dim fp32 tensor.  Grid-stride, 16 bytes per lane.  A workgroup that reads s == 1.0f returns without touching
+ * memory (NaN payloads, -0 and the pad columns stay as they are): a clamped block costs a launch and no traffic.
+ * K5_ERR_ARG: a NULL or not 16-byte aligned x, a NULL score_dev, rows < 1, D % 8, ld < D, ld % 8.  Nothing is launched when refused. */
+int k5_scale_by_dev_bf16(void* x, int rows, int D, int ld, const float* score_dev, void* stream);
 /* Regional prompts, the rule (added under ABI 11).  The base prompt is the forward's ordinary prompt; there are R region prompts,
  * 1 <= R <= 8, each with a mask m_r in [0, 1] on the latent cells (T, H, W), the grid of the keep mask.
  *   Token weights.  A token is a patch_size block of cells; m_r(token) is the fp32 mean of its cells.  raw_0 = base_weight + max(0, 1 - sum_r m_r)
@@ -689,6 +720,28 @@ int k5_dit_skip_state(k5_dit* dit, int* on, long long* skip_steps, long long* bl
 /* k5_dit_forward with the skip branch: out_velocity is k5_dit_forward's bit for bit, out_velocity_skip (bf16, the same shape) the skip
  * branch's.  K5_ERR_STATE without a skip set on the handle (a set with scale 0 still forks here), with MagCache or its calibration. */
 int k5_dit_forward_skip(k5_dit* dit, const k5_forward_args* args, void* out_velocity, void* out_velocity_skip, void* stream);
+
+/* Enhance-A-Video on the handle (added under ABI 11, as the exports above were; the rule is written at k5_enhance_scores_bf16): while set,
+ * every visual block's self-attention of a forward — dense or NABLA, conditional and unconditional alike, the re-run blocks of the skip
+ * branch too — enqueues k5_enhance_scores_bf16 on its normalised q | k after the norm + RoPE pass (into slot `block` of a per-handle device
+ * array) and k5_scale_by_dev_bf16 on the attention output in front of the out projection.  While it applies the queries are normalised by
+ * the standalone pass (the normalised q must exist in memory): "attn_fuse_qnorm" is not used for those launches and k5_sample* does not take
+ * the "attn_fuse_qnorm_auto" decision ("attn_fuse_qnorm_used" reports 0); the two forms give the same bits.  Under NABLA the token rows are in
+ * fractal order: the engine builds frame_rows on the host per shape.  In k5_sample* step i applies it when steps == NULL or steps[i] != 0
+ * (k5_dit_forward / k5_dit_forward_skip / k5_dit_forward_many: every forward); any other step, and every run while this is off, enqueues what
+ * it always did.  The captured step is used only when every step is of one kind.  T is the forward's frames (a context window's length under
+ * k5_sample_windows); T == 1 is accepted and inert: nothing is launched.  A forward MagCache skips launches nothing.  Each handle of a CFG pair
+ * computes its own forward's scores; nothing is exchanged.  Works with k5_sample_many, editing, visual_cond, fp8 and LoRA.
+ * Refused before anything is enqueued, with a message: K5_ERR_ARG when num_steps differs from the call's; K5_ERR_STATE on a rank of a
+ * sequence-parallel group of any transport and sp_mode (the frames of a column live on different ranks; the cross-rank reduction is not
+ * built); K5_ERR_UNSUPPORTED for T > 64.
+ * k5_dit_set_enhance: K5_ERR_ARG for a negative or non-finite weight, steps with num_steps < 1; weight 0 is a valid weight (score =
+ * max(1, mean T)); steps is copied; NULL clears.  k5_dit_enhance_state: whether it is on, the score launches enqueued so far (one per visual
+ * block and forward), and — after a synchronisation of the last forward's stream, one small copy — the last forward's per-block scores in
+ * scores[0 .. min(cap, *nblocks)) (*nblocks: num_visual_blocks once a forward applied it, 0 before); diagnostic: score 1.0 means the clamp held. */
+typedef struct k5_enhance { float weight; const unsigned char* steps; int num_steps; } k5_enhance;   /* steps HOST, copied; NULL: every step */
+int k5_dit_set_enhance(k5_dit* dit, const k5_enhance* enhance /* NULL clears */);
+int k5_dit_enhance_state(k5_dit* dit, int* on, long long* launches, float* scores /* host [cap], nullable */, int cap, int* nblocks, int reset);
 
 /* Stochastic sampling on the handle (added under ABI 11, as the exports above were; the rule is written at k5_euler_step_args): while a plan is
  * set, step i of k5_sample / k5_sample_cond / k5_sample_edit takes dt_down[i] as its dt and applies k5_stochastic_euler's kernel with scale[i],

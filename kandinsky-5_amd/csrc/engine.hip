@@ -580,6 +580,25 @@ struct k5_dit {
     long long noisy_steps = 0;
   } sto;
 
+  // Enhance-A-Video (k5_dit_set_enhance): per visual block the cross-frame attention score of the normalised q | k, and the
+  // attention output times that score in front of the out projection.  sample_impl sets `gate` per step; forward_impl decides `live` for the
+  // forward (and the column table under NABLA), run_block names the score's slot, run_self_attention enqueues.
+  struct Enhance {
+    bool on = false;
+    float weight = 0.f;
+    std::vector<unsigned char> steps;              // per-step mask of the calls to come; empty: every step
+    int gate = -1;                                 // inside k5_sample*: whether the current step applies it (0 / 1); -1: a forward of its own
+    bool live = false;                             // this forward applies it
+    int T = 0, S = 0, block = 0;                   // the forward's frames and spatial positions; the visual block being run
+    const int32_t* rows = nullptr;                 // the forward's frame_rows (NABLA's fractal order) or nullptr
+    long long launches = 0;                        // score launches enqueued so far (k5_dit_enhance_state)
+    int last_blocks = 0;                           // scores the last forward left
+    hipStream_t last_stream = nullptr;
+    DevBuf scores, part, frame_rows;               // fp32 [num_visual_blocks] | double [S Hh] | int32 [S][T]
+    int rows_shape[3] = {0, 0, 0};                 // the (T, H/2, W/2) frame_rows was built for
+    bool at(int i) const { return on && (steps.empty() || steps[i] != 0); }
+  } enh;
+
   // MagCache (reference kandinsky/magcache_utils.py:16-101): skip the visual blocks on some calls and re-apply the
   // cached bf16 residual of the same cond / uncond slot.  Decisions depend on the ratio table and the call counter only.
   struct MagCache {
@@ -928,7 +947,9 @@ int run_self_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, 
   const bool by_data = pre && d->attn_mode == K5_ATTN_AUTO;            // per-head flags from the data
   SoftmaxForm sf;
   // dense visual blocks: norm_qk + RoPE of the queries happen in the attention kernel's Q load ("attn_fuse_qnorm")
-  const bool fuse_q = pre && !nabla && (d->fuse_qnorm || d->fuse_now) && ((by_data && d->row_offsets) || d->attn_mode == K5_ATTN_ONLINE);
+  // Enhance-A-Video reads the normalised q from memory: the standalone pass, whatever "attn_fuse_qnorm" says (the same bits)
+  const bool enhance = vis && d->enh.live;
+  const bool fuse_q = pre && !nabla && !enhance && (d->fuse_qnorm || d->fuse_now) && ((by_data && d->row_offsets) || d->attn_mode == K5_ATTN_ONLINE);
   unsigned int* leave_sig = (d->leave_collect && d->ws_leave_sig.p) ? d->ws_leave_sig.as<unsigned int>() : nullptr;
   const bool fuse_means = pre && nabla && nabla_means_fused(d, rows, 2 * H);   // NABLA: the norm pass takes the block means itself
   const int grp = pre ? attn_group_rows(d, nabla != nullptr, false) : 4;
@@ -964,6 +985,15 @@ int run_self_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, 
       in.aq = qk; in.ak = (const bf16_t*)qk + D; in.aq_rows = rows; in.ak_rows = rows; in.ldq = 2 * D; in.ldk = 2 * D; in.key0 = 0; in.kv_total = rows;
       K5CHK(softmax_form(d, s, a, pref_slot, true, in, sf));
     }
+  }
+  float* const enh_score = enhance ? d->enh.scores.as<float>() + d->enh.block : nullptr;
+  if (enhance) {   // the block's cross-frame score, on the keys the attention launch below reads: pre-scaled (in place, or NABLA's copy when
+                   // the unscaled ones stay for its own means pass) with qk_scale 1, plain ones (rows % 64) with the softmax constant
+    Scope sc(d, s, "enhance");
+    const bool kin = !pre || !nabla || fuse_means;
+    K5CHK(k5_launch_enhance_scores(qk, kin ? (const bf16_t*)qk + D : d->ws_kc.as<bf16_t>(), 2 * D, kin ? 2 * D : D, H, d->enh.T, d->enh.S,
+                                   d->enh.rows, pre ? 1.0f : K5_SOFTMAX_C, d->enh.weight, d->enh.part.as<double>(), enh_score, s));
+    ++d->enh.launches;
   }
   const int variant = pre ? d->attn_mode : K5_ATTN_AUTO;
   if (nabla) {  // nablaT_v2 map (utils.py:136-163) + block-sparse attention (nn.py:257-280)
@@ -1018,6 +1048,10 @@ int run_self_attention(k5_dit* d, hipStream_t s, const AttnW& a, const void* h, 
     K5CHK(k5_launch_attention_bf16_range(at));
   }
   K5CHK(attn_pref_update(d, s, sf, H, rows, grp, leave_sig));
+  if (enhance) {
+    Scope sc(d, s, "enhance");
+    K5CHK(k5_launch_scale_by_dev(o, rows, D, D, enh_score, s));
+  }
   return attn_out_projection(d, s, a, o, rows, resid, gate, f8_out);
 }
 
@@ -1902,6 +1936,19 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     return K5_ERR_ARG;
   }
   const int Rg = rg.on && text_slot != 1 ? rg.R : 0;
+  // Enhance-A-Video: this forward applies it when it is set, the sampler's step (if any) has it on and there is more than one frame
+  auto& en = d->enh;
+  en.live = en.on && en.gate != 0 && Tp >= 2 && c.num_visual_blocks > 0;
+  if (en.live && sp) {
+    en.live = false;
+    k5_set_error("Enhance-A-Video is set (k5_dit_set_enhance) and the handle is in a sequence-parallel group: the frames of a column live on different ranks");
+    return K5_ERR_STATE;
+  }
+  if (en.live && Tp > 64) {
+    en.live = false;
+    k5_set_error("Enhance-A-Video is set (k5_dit_set_enhance): %d frames are more than a wave's four 32 x 32 accumulators hold (64)", Tp);
+    return K5_ERR_UNSUPPORTED;
+  }
   int Lmax = ncond && ncond->text_len > L ? ncond->text_len : L;   // every stream borrows the text blocks' scratch: size it by the longest
   for (int r = 0; r < Rg; ++r) Lmax = rg.conds[r].text_len > Lmax ? rg.conds[r].text_len : Lmax;
   K5CHK(ensure_workspaces(d, sp ? P * n_pad : N, Lmax));
@@ -1929,6 +1976,28 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
       d->perm_shape[0] = Tp; d->perm_shape[1] = Hp; d->perm_shape[2] = Wp;
     }
     perm = d->ws_perm.as<int32_t>();
+  }
+  if (en.live) {   // the score's workspaces, and under NABLA the token row of every (position, frame), cached per shape like the permutation
+    const int S = Hp * Wp;
+    K5CHK(en.scores.ensure((size_t)c.num_visual_blocks * 4));
+    K5CHK(en.part.ensure((size_t)k5_enhance_parts(d->Hh, S) * sizeof(double)));
+    en.T = Tp; en.S = S; en.rows = nullptr;
+    if (nabla) {
+      if (en.rows_shape[0] != Tp || en.rows_shape[1] != Hp || en.rows_shape[2] != Wp) {
+        std::vector<int32_t> fr((size_t)N);
+        const int Hb = Hp / 8, Wb = Wp / 8;
+        for (int i = 0; i < N; ++i) {   // row i of the fractal order holds token (t, y, x): see the permutation above
+          const int b = i >> 6, r = i & 63, t = b / (Hb * Wb), hb = (b / Wb) % Hb, wb = b % Wb;
+          const int p = (hb * 8 + (r >> 3)) * Wp + wb * 8 + (r & 7);
+          fr[(size_t)p * Tp + t] = i;
+        }
+        K5CHK(en.frame_rows.ensure((size_t)N * 4));
+        HIPCHK(hipMemcpy(en.frame_rows.p, fr.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+        en.rows_shape[0] = Tp; en.rows_shape[1] = Hp; en.rows_shape[2] = Wp;
+      }
+      en.rows = en.frame_rows.as<int32_t>();
+    }
+    en.last_stream = s;
   }
   K5CHK(prepare_rope(d, s, a, Tp, Hp, Wp, perm));
   const float *tcos = nullptr, *tsin = nullptr;
@@ -2026,6 +2095,7 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     const float* vcos = d->ws_vcos.as<float>() + (size_t)tok0 * 32;
     const float* vsin = d->ws_vsin.as<float>() + (size_t)tok0 * 32;
     const bool ulysses = sched == 1, two_level = sched == 2;
+    en.block = i;   // the slot of this block's Enhance-A-Video score
     // fp8 modes: the LayerNorm writes the e4m3 rows the projections read (no bf16 h, no quantisation pass) — "fp8_fuse_ln" = 0 keeps the two passes
     const bool h8_sa = d->fp8_fuse_ln && sched == 0 && (sp ? sa_sp_fp8_in(d, b.self_attn, n, n_pad, nabla) : sa_fp8_in(d, b.self_attn, n));
     if (!drop_sa) {
@@ -2056,6 +2126,7 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     if (i == fork_at) HIPCHK(hipMemcpyAsync(sk.vis.p, d->ws_vis.p, vis_elems * 2, hipMemcpyDeviceToDevice, s));
     K5CHK(run_block(i, text_slot > 0 ? 1 : 0, false));
   }
+  if (en.live && !mag_skip) en.last_blocks = c.num_visual_blocks;
   if (mg.on) {
     if (!mag_skip) {  // residual = visual_embed - ori_visual_embed (bf16), :84
       Scope sc(d, s, "elementwise");
@@ -2473,6 +2544,23 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
       return K5_ERR_STATE;
     }
   }
+  const k5_dit::Enhance& en = d->enh;
+  if (en.on) {
+    if (!en.steps.empty() && (int)en.steps.size() != a->num_steps) {
+      k5_set_error("%s: the Enhance-A-Video mask has %d steps, this call %d", who, (int)en.steps.size(), a->num_steps);
+      return K5_ERR_ARG;
+    }
+    if (d->comm.active()) {
+      k5_set_error("%s: Enhance-A-Video is set (k5_dit_set_enhance) and the handle is in a sequence-parallel group: the frames of a column live on "
+                   "different ranks, the cross-rank reduction is not built", who);
+      return K5_ERR_STATE;
+    }
+    if (a->fwd.T > 64) {
+      k5_set_error("%s: Enhance-A-Video is set (k5_dit_set_enhance): %d frames per forward are more than a wave's four 32 x 32 accumulators hold (64)",
+                   who, a->fwd.T);
+      return K5_ERR_UNSUPPORTED;
+    }
+  }
   const k5_dit::Stochastic& so = d->sto;
   if (so.on) {
     if ((int)so.dt_down.size() != a->num_steps) {
@@ -2577,6 +2665,7 @@ struct SampleRun {
 
   int step(int i) {   // enqueue step i: the forwards, then CFG + Euler
     const k5_dit_config& c = d->cfg;
+    d->enh.gate = d->enh.at(i) ? 1 : 0;   // Enhance-A-Video: this step's forwards apply it or enqueue what they always did
     void* const vu = (win ? cfg_on : kind(i) == GUIDED) ? vel_u : nullptr;
     if (win) {
       // every window on its own slice of the latent (T is outermost: a temporal window is contiguous), cond then uncond, into slot k of the
@@ -2644,9 +2733,9 @@ struct SampleRun {
 // The handle's launch counters that a step advances from host code.  A replay of the captured step enqueues the same launches without that
 // host code, so sample_impl takes the difference over the capture and adds it per further replay.  A new counter is one more entry of `of` (and of K).
 struct ReplayCounts {
-  static constexpr int K = 4;
+  static constexpr int K = 5;
   long long per_step[K] = {};
-  static void of(k5_dit* d, long long* (&c)[K]) { c[0] = &d->nag.combines; c[1] = &d->regions.combines; c[2] = &d->skip.blocks_shared; c[3] = &d->skip.blocks_run; }
+  static void of(k5_dit* d, long long* (&c)[K]) { c[0] = &d->nag.combines; c[1] = &d->regions.combines; c[2] = &d->skip.blocks_shared; c[3] = &d->skip.blocks_run; c[4] = &d->enh.launches; }
   void snapshot(k5_dit* d) { long long* c[K]; of(d, c); for (int i = 0; i < K; ++i) per_step[i] = *c[i]; }
   void difference(k5_dit* d) { long long* c[K]; of(d, c); for (int i = 0; i < K; ++i) per_step[i] = *c[i] - per_step[i]; }
   void add(k5_dit* d) const { long long* c[K]; of(d, c); for (int i = 0; i < K; ++i) *c[i] += per_step[i]; }
@@ -2773,6 +2862,11 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     r.want_v = r.want_v || (wt.on && wt.every > 0);
     uniform = uniform && nskip == N - first;
   }
+  // Enhance-A-Video: the steps whose forwards carry the score and scale launches; one captured step stands for all only when all or none do
+  int nenh = 0;
+  for (int i = first; i < N; ++i) nenh += d->enh.at(i) && a->fwd.T >= 2 ? 1 : 0;
+  uniform = uniform && (nenh == 0 || nenh == N - first);
+  struct EnhanceGuard { k5_dit* d; ~EnhanceGuard() { d->enh.gate = -1; } } enhance_guard{d};
   r.pair = r.cfg_on && d->pair.active();
   if (r.pair) K5CHK(d->ws_vel_pair.ensure(2 * r.n * 2));
   else {   // one slot per window
@@ -2839,7 +2933,8 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   struct FuseGuard { k5_dit* d; ~FuseGuard() { d->fuse_now = false; d->leave_collect = false; } } fuse_guard{d};
   d->fuse_now = false; d->leave_collect = false; d->fuse_last = -1;
   const bool auto_fuse = d->fuse_qnorm_auto && !d->fuse_qnorm && !d->comm.active() && d->attn_mode == K5_ATTN_AUTO && d->row_offsets &&   // (a CFG pair's handles decide each for itself)
-                         a->fwd.attention_type == 0 && N - first >= 2;
+                         a->fwd.attention_type == 0 && N - first >= 2 && !nenh;   // Enhance-A-Video needs the normalised q in memory
+  if (nenh) d->fuse_last = 0;
   if (auto_fuse) {
     K5CHK(d->ws_leave_sig.ensure(4));
     if (!d->h_leave_sig) HIPCHK(hipHostMalloc((void**)&d->h_leave_sig, 4, hipHostMallocDefault));
@@ -3149,6 +3244,35 @@ extern "C" int k5_dit_stochastic_state(k5_dit* d, int* on, long long* noisy_step
   if (on) *on = d->sto.on ? 1 : 0;
   if (noisy_steps) *noisy_steps = d->sto.noisy_steps;
   if (reset) d->sto.noisy_steps = 0;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_set_enhance(k5_dit* d, const k5_enhance* e) {
+  g_err[0] = 0;
+  if (!d) { k5_set_error("k5_dit_set_enhance: null handle"); return K5_ERR_ARG; }
+  k5_dit::Enhance& en = d->enh;
+  if (!e) { en.on = false; en.weight = 0.f; en.steps.clear(); return K5_OK; }
+  if (!(e->weight >= 0.0f) || !isfinite(e->weight)) { k5_set_error("k5_dit_set_enhance: weight must be finite and >= 0 (got %g)", (double)e->weight); return K5_ERR_ARG; }
+  if (e->steps && e->num_steps < 1) { k5_set_error("k5_dit_set_enhance: steps with num_steps = %d", e->num_steps); return K5_ERR_ARG; }
+  en.weight = e->weight;
+  en.steps.assign(e->steps, e->steps ? e->steps + e->num_steps : e->steps);
+  en.on = true;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_enhance_state(k5_dit* d, int* on, long long* launches, float* scores, int cap, int* nblocks, int reset) {
+  if (!d) { k5_set_error("k5_dit_enhance_state: null handle"); return K5_ERR_ARG; }
+  k5_dit::Enhance& en = d->enh;
+  if (scores && cap < 0) { k5_set_error("k5_dit_enhance_state: cap = %d", cap); return K5_ERR_ARG; }
+  if (on) *on = en.on ? 1 : 0;
+  if (launches) *launches = en.launches;
+  if (nblocks) *nblocks = en.last_blocks;
+  const int n = en.last_blocks < cap ? en.last_blocks : cap;
+  if (scores && n > 0) {   // diagnostic: the last forward's scores, once its stream has drained
+    HIPCHK(hipStreamSynchronize(en.last_stream));
+    HIPCHK(hipMemcpy(scores, en.scores.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  }
+  if (reset) en.launches = 0;
   return K5_OK;
 }
 

@@ -535,6 +535,31 @@ int k5_nag_combine_bf16(const void* z_pos, const void* z_neg, void* out, int row
   return ret(st, "k5_nag_combine_bf16");
 }
 
+long long k5_enhance_part_count(int Hh, int S) { return k5_enhance_parts(Hh, S); }
+
+int k5_enhance_scores_bf16(const void* Q, const void* K, int ldq, int ldk, int Hh, int T, int S, const int32_t* frame_rows, float qk_scale,
+                           float weight, double* part, float* score_out, void* stream) {
+  const int st = k5_launch_enhance_scores(Q, K, ldq, ldk, Hh, T, S, frame_rows, qk_scale, weight, part, score_out, (hipStream_t)stream);
+  if (st == K5_ERR_UNSUPPORTED) { k5_set_error("k5_enhance_scores_bf16: T = %d frames are more than the four 32 x 32 accumulators of a wave hold (64)", T); return st; }
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_enhance_scores_bf16: need 16-byte aligned non-null Q and K, non-null part and score_out, ld >= 64 Hh, ld %% 8 == 0, Hh >= 1, "
+                 "S >= 1, T >= 2, a finite weight >= 0 and a finite qk_scale > 0 (ldq %d, ldk %d, Hh %d, T %d, S %d, weight %g, qk_scale %g)",
+                 ldq, ldk, Hh, T, S, (double)weight, (double)qk_scale);
+    return st;
+  }
+  return ret(st, "k5_enhance_scores_bf16");
+}
+
+int k5_scale_by_dev_bf16(void* x, int rows, int D, int ld, const float* score_dev, void* stream) {
+  const int st = k5_launch_scale_by_dev(x, rows, D, ld, score_dev, (hipStream_t)stream);
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_scale_by_dev_bf16: need a 16-byte aligned non-null x, a non-null score_dev, rows > 0, D %% 8 == 0, ld >= D, ld %% 8 == 0 "
+                 "(rows %d, D %d, ld %d)", rows, D, ld);
+    return st;
+  }
+  return ret(st, "k5_scale_by_dev_bf16");
+}
+
 int k5_region_combine_bf16(const void* z0, const void* zr, long long zr_stride, int R, const float* w, int ldw, void* out, int rows, int D,
                            int ld, void* stream) {
   const int st = k5_launch_region_combine(z0, zr, zr_stride, R, w, ldw, out, rows, D, ld, (hipStream_t)stream);

@@ -232,6 +232,17 @@ int k5_launch_region_combine(const void* z0, const void* zr, long long zr_stride
 // (T / pt, H / ph, W / pw) grid: m_r = mean of the token's cells (clamped to [0, 1]), raw_0 = base_weight + max(0, 1 - sum m), w = raw / sum raw
 int k5_launch_region_weights(const float* masks, int R, int T, int H, int W, int pt, int ph, int pw, float base_weight, const int32_t* perm,
                              float* w, hipStream_t stream);
+// Enhance-A-Video (enhance.hip; the rule is written at k5_enhance_scores_bf16 in include/k5.h): the cross-frame attention score of one forward
+// and block from q | k after norm_qk + RoPE — one workgroup per spatial position, one wave per head, K·Qᵀ on the 32x32x16 MFMA, then a
+// one-workgroup float64 reduction of part [k5_enhance_parts(Hh, S)] in fixed order into score_out[0].  No atomics: equal inputs, equal bits.
+// K5_ERR_ARG: a NULL or misaligned pointer (Q, K 16 bytes), ld < 64 Hh or ld % 8, Hh / S < 1, T < 2, weight negative or not finite,
+// qk_scale <= 0 or not finite; K5_ERR_UNSUPPORTED: T > 64.  Nothing is launched when it refuses.
+long long k5_enhance_parts(int Hh, int S);
+int k5_launch_enhance_scores(const void* Q, const void* K, int ldq, int ldk, int Hh, int T, int S, const int32_t* frame_rows, float qk_scale,
+                             float weight, double* part, float* score_out, hipStream_t stream);
+// x [rows][ld] bf16 (D columns used) *= *score_dev in place: bf16(float(x) * s), 16 bytes per lane, grid-stride; a workgroup that reads s == 1
+// touches nothing.  Refusals as k5_launch_nag_combine's (without its D limit).
+int k5_launch_scale_by_dev(void* x, int rows, int D, int ld, const float* score_dev, hipStream_t stream);
 // fp32 -> bf16 cast, bf16 -> fp32
 int k5_launch_cast_f32_bf16(const float* x, void* out, int64_t n, hipStream_t stream);
 // weight packing: src [rows][cols] (K5_F32 / K5_BF16 / K5_F16, device) -> dst [rows][ld] bf16 (RNE) or fp32, pad columns zeroed

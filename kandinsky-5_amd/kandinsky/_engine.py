@@ -119,6 +119,11 @@ class SkipGuidance(C.Structure):
                 ("steps", C.POINTER(C.c_ubyte)), ("num_steps", C.c_int)]
 
 
+class Enhance(C.Structure):
+    """k5_enhance: the set of k5_dit_set_enhance (steps is HOST memory, copied by the call)."""
+    _fields_ = [("weight", C.c_float), ("steps", C.POINTER(C.c_ubyte)), ("num_steps", C.c_int)]
+
+
 class Stochastic(C.Structure):
     """k5_stochastic: the plan of k5_dit_set_stochastic (the three tables are HOST memory, copied by the call)."""
     _fields_ = [("num_steps", C.c_int), ("dt_down", C.POINTER(C.c_float)), ("scale", C.POINTER(C.c_float)),
@@ -248,6 +253,11 @@ SYMBOLS = {
     "k5_dit_set_skip_guidance": (_I, [_P, C.POINTER(SkipGuidance)]),
     "k5_dit_skip_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _I]),
     "k5_dit_forward_skip": (_I, [_P, C.POINTER(ForwardArgs), _P, _P, _P]),
+    "k5_enhance_part_count": (C.c_longlong, [_I, _I]),
+    "k5_enhance_scores_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _F, _F, _P, _P, _P]),
+    "k5_scale_by_dev_bf16": (_I, [_P, _I, _I, _I, _P, _P]),
+    "k5_dit_set_enhance": (_I, [_P, C.POINTER(Enhance)]),
+    "k5_dit_enhance_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), C.POINTER(C.c_float), _I, C.POINTER(_I), _I]),
     "k5_region_combine_bf16": (_I, [_P, _P, C.c_longlong, _I, _P, _I, _P, _I, _I, _I, _P]),
     "k5_region_weights_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "k5_dit_set_regions": (_I, [_P, C.POINTER(TextCond), _I, _P, _I, _I, _I, _F]),
@@ -703,6 +713,35 @@ def nag_combine_(z_pos, z_neg, s, tau, alpha, out=None, D=None):
         check(lib().k5_nag_combine_bf16(ptr(z_pos), ptr(z_neg), ptr(out), rows, D, ld, float(s), float(tau), float(alpha),
                                         stream_ptr(z_pos.device)), "k5_nag_combine_bf16")
     return out
+
+
+def enhance_scores(Q, K, Hh, T, S, weight, qk_scale, frame_rows=None):
+    """The Enhance-A-Video score of one block (k5_enhance_scores_bf16): Q and K bf16 [rows][ld] tensors with a unit column stride (views of one
+    fused buffer are fine) whose first 64 Hh columns are the heads, frame_rows int32 [S][T] on the device or None for row = t * S + p.  Returns
+    (score_out fp32 [1], part float64 [S * Hh]) on the device, not synchronised."""
+    for x in (Q, K):
+        if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+            raise ValueError("enhance_scores: Q and K must be bf16 [rows][ld] tensors with a unit column stride")
+    if frame_rows is not None and (frame_rows.dtype != torch.int32 or not frame_rows.is_contiguous()):
+        raise ValueError("enhance_scores: frame_rows must be a contiguous int32 tensor")
+    n = lib().k5_enhance_part_count(int(Hh), int(S))
+    part = torch.zeros(max(int(n), 1), dtype=torch.float64, device=Q.device)
+    score = torch.zeros(1, dtype=torch.float32, device=Q.device)
+    with torch.cuda.device(Q.device):
+        check(lib().k5_enhance_scores_bf16(ptr(Q), ptr(K), Q.stride(0), K.stride(0), int(Hh), int(T), int(S), ptr(frame_rows), float(qk_scale),
+                                           float(weight), ptr(part), ptr(score), stream_ptr(Q.device)), "k5_enhance_scores_bf16")
+    return score, part
+
+
+def scale_by_dev_(x, score, D=None):
+    """x *= score in place (k5_scale_by_dev_bf16): x bf16 [rows][ld] with a unit column stride of which D columns (default: all) are used,
+    score a fp32 tensor of one element on the device; bf16(float(x) * s), and nothing is touched when s == 1."""
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1 or score.dtype != torch.float32:
+        raise ValueError("scale_by_dev_: x must be a bf16 [rows][ld] tensor with a unit column stride, score fp32")
+    with torch.cuda.device(x.device):
+        check(lib().k5_scale_by_dev_bf16(ptr(x), x.shape[0], x.shape[1] if D is None else int(D), x.stride(0), ptr(score), stream_ptr(x.device)),
+              "k5_scale_by_dev_bf16")
+    return x
 
 
 def region_combine_(z0, zr, w, out=None, D=None):

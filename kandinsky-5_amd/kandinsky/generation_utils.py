@@ -16,7 +16,7 @@ import torch
 
 from . import _engine as E
 from .models.dit import (DiffusionTransformer3D, SamplingInterrupted, StepInfo, _is_guided, check_guidance_args, check_nag_args,
-                         check_nag_numbers, check_region_args, check_skip_args, check_stochastic_args, check_watch_args, split_per_sample)
+                         check_enhance_args, check_nag_numbers, check_region_args, check_skip_args, check_stochastic_args, check_watch_args, split_per_sample)
 
 
 def _attr(obj, name, default=None):
@@ -178,6 +178,66 @@ def _skip_for_run(model, sigmas, first, slg_blocks, slg_scale, slg_interval, slg
     if _is_cfg_pair(model):
         raise ValueError("slg_blocks on a CFG pair: the pair exchanges two velocities, a skip step has three")
     return blocks, scale, mode, mask
+
+
+def enhance_plan(sigmas, interval=None):
+    """The per-step mask of Enhance-A-Video over `sigmas` (num_steps + 1 values): a list of num_steps 0 / 1, 1 on the steps with
+    lo <= sigmas[i] <= hi of `interval` = (lo, hi); None = every step.  Host only, like `skip_plan`."""
+    sig = [float(v) for v in sigmas]
+    n = len(sig) - 1
+    if n < 1:
+        raise ValueError("enhance_plan: sigmas must hold num_steps + 1 >= 2 values")
+    lo, hi = _interval("enhance_interval", interval)
+    return [1 if lo <= sig[i] <= hi else 0 for i in range(n)]
+
+
+def _enhance_for_run(model, sigmas, first, enhance_weight, enhance_interval, frames):
+    """`generate`'s Enhance-A-Video keywords -> None when they are off (no weight, or an interval without a step: nothing changes), otherwise
+    (weight, mask of the steps that run) with the ValueErrors of what the engine refuses.  `sigmas`: the full schedule, of which steps
+    `first`.. run; `frames`: the latent frames one forward sees (a context window's length).  0.0 is a valid weight."""
+    if enhance_weight is None:
+        if enhance_interval is not None:
+            raise ValueError("enhance_interval needs enhance_weight")
+        return None
+    weight, mask = check_enhance_args(enhance_weight, enhance_plan(sigmas, enhance_interval)[first:])   # cut with the schedule
+    if not any(mask):
+        return None
+    if getattr(model, "_sp", None) is not None:
+        raise ValueError("enhance_weight on a rank of a sequence-parallel group: the frames of a column live on different ranks")
+    if int(frames) > 64:
+        raise ValueError(f"enhance_weight: {int(frames)} latent frames per forward are more than the score kernel holds (64)")
+    if not hasattr(model, "set_enhance"):
+        raise ValueError("enhance_weight needs a model with set_enhance (the engine-backed DiffusionTransformer3D has it): the score is taken "
+                         "inside its self-attention, a wrapped callable without one cannot take it")
+    return weight, mask
+
+
+@contextlib.contextmanager
+def _enhance_for_call(model, enhance):
+    """What `set_enhance` left on a model comes back after a run that set it step by step or for the call, also on an exception.  enhance None:
+    nothing is touched.  A wrapper that only hands `set_enhance`, `clear_enhance` and `_enhance` on to an engine-backed model is served too."""
+    if enhance is None:
+        yield
+        return
+    before = getattr(model, "_enhance", None)
+    try:
+        yield
+    finally:
+        if before is not None:
+            model.set_enhance(*before)
+        else:
+            model.clear_enhance()
+
+
+def _enhance_at(model, enhance, i):
+    """The per-step paths' side: step i's forwards apply the score (weight, every forward) or are the plain forwards, as the engine's loop
+    decides it from the mask."""
+    if enhance is None:
+        return
+    if enhance[1][i]:
+        model.set_enhance(enhance[0])
+    else:
+        model.clear_enhance()
 
 
 @contextlib.contextmanager
@@ -450,7 +510,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
              context_text=None, nag_text_embeds=None, nag_text_rope_pos=None, nag_scale=None, nag_tau=2.5, nag_alpha=0.25,
              region_text_embeds=None, region_text_rope_pos=None, region_masks=None, region_base_weight=0.0,
              guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0, cfg_rescale=0.0,
-             slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0, sde_interval=None, sde_seed=None):
+             slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0, sde_interval=None, sde_seed=None,
+             enhance_weight=None, enhance_interval=None):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -525,6 +586,15 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     removed afterwards), any other model through the same kernel from the per-step loop: the same bits.  ValueError, before anything runs:
     eta outside [0, 1], a negative or non-finite s_noise, a bad interval; together with context windows, MagCache or preview_every > 0
     (the preview's x0 = x - sigma v does not hold after the noise; a callback without previews works).  No checkpoint was at hand, visual
+    quality is not claimed.
+    `enhance_weight`, `enhance_interval` (optional, extension): Enhance-A-Video (Luo et al. 2025).  On the steps with lo <= sigma_i <= hi of
+    `enhance_interval` (None = every step) every visual block of every forward multiplies its self-attention output by
+    max(1, mean * (frames + enhance_weight)), mean being the mean attention mass the frames of one spatial position send to each other's
+    frames rather than to themselves (`DiffusionTransformer3D.set_enhance`).  `enhance_weight` None (default) is off and nothing changes; 0.0
+    is a valid weight.  A `strength < 1` run cuts the mask with the schedule; with context windows the frames are the window's; one frame is
+    inert.  The engine-backed model runs it inside its loop (set for this call and removed afterwards), a model that hands `set_enhance` on
+    step by step from the per-step loop: the same bits.  ValueError, before anything runs: a bad weight or interval; a rank of a
+    sequence-parallel group; more than 64 latent frames per forward; a model without `set_enhance`.  No checkpoint was at hand, visual
     quality is not claimed."""
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
@@ -546,7 +616,9 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     wants_skip = slg_blocks is not None or slg_scale or slg_interval is not None
     sto = None
     wants_sto = bool(eta) or sde_interval is not None or float(s_noise) != 1.0
-    if wants_guide or wants_skip or wants_sto:   # the schedule as `_generate_one` draws it: the same bits
+    enhance = None
+    wants_enhance = enhance_weight is not None or enhance_interval is not None
+    if wants_guide or wants_skip or wants_sto or wants_enhance:   # the schedule as `_generate_one` draws it: the same bits
         sigmas = sigma_schedule(num_steps, scheduler_scale, device=device).cpu().tolist()
     if wants_guide:
         guide = _guidance_for_run(model, sigmas, first, guidance_weight, *guide_kw, init_latent, windowed)
@@ -557,9 +629,11 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
                              "inside its forward, a wrapped callable without one cannot take it")
     if wants_sto:
         sto = _stochastic_for_run(model, sigmas, first, eta, s_noise, sde_interval, seed if sde_seed is None else sde_seed, windowed, preview_every)
+    if wants_enhance:
+        enhance = _enhance_for_run(model, sigmas, first, enhance_weight, enhance_interval, plan[0] if windowed else shape[0] // batch)
     if region_text_embeds is not None and windowed:
         raise ValueError("region_text_embeds together with context windows is not supported: the masks cover the clip, a window sees a slice")
-    with _skip_for_call(model, skip), _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
+    with _skip_for_call(model, skip), _enhance_for_call(model, enhance), _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
             _regions_for_call(model, region_text_embeds, region_text_rope_pos, region_masks, region_base_weight):
         # one hook for the whole call (it owns the bar): the samples of a batch share it
         watch = _StepWatch(model, callback, preview_every, preview_factors, preview_x0, progress, batch * steps_run, shape[-1])
@@ -574,18 +648,19 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
                    null_text_rope_pos, guidance_weight, scheduler_scale, conf, watch)
             what = (context, visual_cond, visual_cond_mask, init_latent, strength, keep_mask)
             if batch > 1:
-                return _generate_batch(*run, batch, *what, guide=guide, skip=skip, sto=sto)
-            return _generate_one(*run, plan, *what, guide=guide, skip=skip, sto=sto)
+                return _generate_batch(*run, batch, *what, guide=guide, skip=skip, sto=sto, enhance=enhance)
+            return _generate_one(*run, plan, *what, guide=guide, skip=skip, sto=sto, enhance=enhance)
         finally:
             watch.close()
 
 
 def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                   guidance_weight, scheduler_scale, conf, watch, plan, context, visual_cond, visual_cond_mask, init_latent, strength,
-                  keep_mask, guide=None, skip=None, sto=None):
+                  keep_mask, guide=None, skip=None, sto=None, enhance=None):
     """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch`, the checked `plan` of
     `_context_plan`, the checked guidance plan `guide` of `_guidance_for_run`, the checked skip set `skip` of `_skip_for_run` (installed on
-    the model by `generate`) and the checked stochastic plan `sto` of `_stochastic_for_run`; returns the latent."""
+    the model by `generate`), the checked stochastic plan `sto` of `_stochastic_for_run` and the checked Enhance-A-Video set `enhance` of
+    `_enhance_for_run` (`generate` puts back what the model held); returns the latent."""
     context_text = context[2]
     if plan is not None:
         F, starts, weights = plan
@@ -625,7 +700,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     if not exchange and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False):
         # whole loop inside the engine: no per-step host work at all
         with model.setting_for_call("watch", watch.watch_args()), model.setting_for_call("guidance", guide), \
-                model.setting_for_call("stochastic", sto):
+                model.setting_for_call("stochastic", sto), model.setting_for_call("enhance", enhance):
             model.sample(img, timesteps.tolist(), text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                          null_text_rope_pos, guidance_weight, scale_factor=conf.metrics.scale_factor,
                          sparse_params=sparse_params,
@@ -690,6 +765,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         kind = "zero" if i < g_zero_init else "guided" if (cfg_on if guide is None else _is_guided(w_at)) else "unguided"
         skip_at = kind != "zero" and skip is not None and bool(skip[3][i])
         wants_preview = watch.active and watch.preview_at(i, n)
+        _enhance_at(model, enhance, i)
         t1000 = torch.tensor([timestep]) * 1000
         if kind == "zero":
             v, u = (torch.zeros(img.shape, dtype=torch.bfloat16, device=img.device) if wants_preview else None), None   # velocity 0: x0 = x
@@ -723,7 +799,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
 
 def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                     guidance_weight, scheduler_scale, conf, watch, batch, context, visual_cond, visual_cond_mask, init_latent, strength,
-                    keep_mask, guide=None, skip=None, sto=None):
+                    keep_mask, guide=None, skip=None, sto=None, enhance=None):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
     T = img.shape[0] // batch
     tes, nes = split_per_sample(text_embeds, batch, "text_embeds"), split_per_sample(null_text_embeds, batch, "null_text_embeds")
@@ -740,7 +816,8 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
             cond = torch.cat(cond, dim=-1).reshape(batch, T, *img.shape[1:-1], img.shape[-1] + 1).contiguous()
         sparse_params = get_sparse_params(conf, {"visual": img[:T]}, device)
         timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()
-        with model.setting_for_call("watch", watch.watch_args()), model.setting_for_call("guidance", guide):
+        with model.setting_for_call("watch", watch.watch_args()), model.setting_for_call("guidance", guide), \
+                model.setting_for_call("enhance", enhance):
             model.sample_many(img.view(batch, T, *img.shape[1:]), timesteps.tolist(), tes, nes, visual_rope_pos, tps, nps,
                                guidance_weight, scale_factor=conf.metrics.scale_factor, sparse_params=sparse_params, visual_cond=cond)
         return img
@@ -754,7 +831,7 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         plan = _context_plan(model, T, *context, src, watch.every)
         watch.sample = b
         img[rows] = _generate_one(model, device, img[rows].clone(), num_steps, tes[b], nes[b], visual_rope_pos, tps[b], nps[b], guidance_weight,
-                                  scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide, skip=skip,
+                                  scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide, skip=skip, enhance=enhance,
                                   sto=None if sto is None else (*sto[:3], (sto[3] + b) & (2 ** 64 - 1), sto[4]))   # a seed per sample
     return img
 
@@ -799,7 +876,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                     nag_scale=None, nag_tau=2.5, nag_alpha=0.25, region_text_embeds=None, region_text_rope_pos=None, region_masks=None,
                     region_base_weight=0.0, guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0,
                     cfg_rescale=0.0, slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0,
-                    sde_interval=None, sde_seed=None):
+                    sde_interval=None, sde_seed=None, enhance_weight=None, enhance_interval=None):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -823,8 +900,17 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     weights, a guidance interval, CFG-Zero* and CFG rescale, passed to `generate` (see there).  All off by default.
     `slg_blocks`, `slg_scale`, `slg_interval`, `slg_mode` (optional, extension): skip-layer guidance, passed to `generate` (see there).  Off by
     default.
-    `eta`, `s_noise`, `sde_interval`, `sde_seed` (optional, extension): stochastic sampling, passed to `generate` (see there).  Off by default."""
+    `eta`, `s_noise`, `sde_interval`, `sde_seed` (optional, extension): stochastic sampling, passed to `generate` (see there).  Off by default.
+    `enhance_weight`, `enhance_interval` (optional, extension): Enhance-A-Video, passed to `generate` (see there).  None (default) is off."""
     batch, frames, height, width, channels = shape
+    enhance_kw = {}
+    if enhance_weight is not None or enhance_interval is not None:   # before any model runs: the numbers and what the handle's state refuses
+        fwd_frames = frames if context_frames is None else min(int(frames), int(context_frames))
+        _enhance_for_run(dit, [1.0, 0.0], 0, enhance_weight, None, fwd_frames)
+        enhance_plan([1.0, 0.0], enhance_interval)   # (what depends on the schedule is checked by `generate`)
+        if enhance_weight is None:
+            raise ValueError("enhance_interval needs enhance_weight")
+        enhance_kw = dict(enhance_weight=enhance_weight, enhance_interval=enhance_interval)
     sto_kw = {}
     wants_sto = eta or sde_interval is not None or float(s_noise) != 1.0
     wants_skip = slg_blocks is not None or slg_scale or slg_interval is not None
@@ -942,7 +1028,8 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         latent = generate(dit, device, (batch * frames, height, width, channels), num_steps, cond, uncond, grid,
                           text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
                           progress=progress, batch=batch, callback=callback, preview_every=preview_every,
-                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw, **guide_kw, **skip_kw, **sto_kw)
+                          preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw, **guide_kw, **skip_kw, **sto_kw,
+                          **enhance_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

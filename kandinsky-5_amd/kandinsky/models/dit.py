@@ -170,6 +170,25 @@ def check_skip_args(blocks, scale, mode, steps, num_visual_blocks):
     return idx, scale, mode, steps
 
 
+def check_enhance_args(weight, steps):
+    """The ValueErrors of `set_enhance` / `generate(enhance_weight=, enhance_interval=)`; returns (weight as a float, steps as a list of 0 / 1
+    or None).  0.0 is a valid weight (score = max(1, mean * T)); off is `clear_enhance`, not a weight."""
+    try:
+        ok = not isinstance(weight, bool)
+        weight = float(weight)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError("enhance: weight must be a number")
+    if not math.isfinite(weight) or weight < 0.0:
+        raise ValueError(f"enhance: weight must be a finite number >= 0 (got {weight})")
+    if steps is not None:
+        steps = [1 if bool(v) else 0 for v in steps]
+        if not steps:
+            raise ValueError("enhance: steps must hold one 0 / 1 per step")
+    return weight, steps
+
+
 def check_stochastic_args(dt_down, scale, noise_coef, seed, first_stream=0):
     """The ValueErrors of `set_stochastic`; returns (dt_down, scale, noise_coef as lists of floats, seed as a 64-bit and first_stream as a
     32-bit unsigned int)."""
@@ -282,6 +301,7 @@ _SETTINGS = {
     "guidance":      ("_guidance", "k5_dit_set_guidance",      (None,)),
     "skip_guidance": ("_skip",     "k5_dit_set_skip_guidance", (None,)),
     "stochastic":    ("_stochastic", "k5_dit_set_stochastic",  (None,)),
+    "enhance":       ("_enhance",  "k5_dit_set_enhance",       (None,)),
 }
 
 
@@ -339,6 +359,7 @@ class DiffusionTransformer3D(nn.Module):
         self._regions = None         # the prompts, masks and base weight of set_regions: likewise
         self._skip = None            # the set of set_skip_guidance (blocks, scale, mode, steps | None): likewise
         self._stochastic = None      # the plan of set_stochastic (dt_down, scale, noise_coef, seed, first_stream): likewise
+        self._enhance = None         # (weight, steps | None) of set_enhance: likewise
         self._guidance = None        # the plan of set_guidance (weights list | None, zero_star, zero_init_steps, rescale): likewise
         self._borrowed = {}          # setting name -> what the live handle borrows from the stored value (structs, device copies, ctypes arrays)
 
@@ -657,7 +678,7 @@ class DiffusionTransformer3D(nn.Module):
 
     @contextlib.contextmanager
     def setting_for_call(self, name, args):
-        """Context: setting `name` ("watch", "nag", "regions", "guidance", "skip_guidance", "stochastic") as `set_<name>(*args)` makes it, for one call; what was
+        """Context: setting `name` ("watch", "nag", "regions", "guidance", "skip_guidance", "stochastic", "enhance") as `set_<name>(*args)` makes it, for one call; what was
         stored before is installed again afterwards (the stored object itself, not a copy) or the setting is cleared, also on an exception.
         args None: nothing is touched."""
         if args is None:
@@ -843,6 +864,45 @@ class DiffusionTransformer3D(nn.Module):
         `reset` zeroes the count afterwards."""
         on, n = self._state("k5_dit_stochastic_state", (C.c_int, C.c_longlong), int(bool(reset)))
         return bool(on), n
+
+    # ---------------------------------------------------------------- Enhance-A-Video: the cross-frame attention score scales each visual block
+    def set_enhance(self, weight, steps=None):
+        """Enhance-A-Video (k5_dit_set_enhance; Luo et al. 2025): in every visual block the mean off-diagonal mass of the frame-by-frame
+        attention of each spatial position, times (frames + `weight`) and clamped at 1 from below, multiplies the self-attention output.
+        Every forward — conditional and unconditional, `forward*` and `sample*` — computes its own scores.  `steps`: one 0 / 1 per step of
+        the calls to come (`generation_utils.enhance_plan` builds it; None = every step).  `weight` 0 is a valid weight.  One frame is
+        accepted and inert.  `sample` and `forward` refuse, before anything runs: a `steps` list of another length than the call's steps, a
+        rank of a sequence-parallel group, more than 64 latent frames per forward.
+        No checkpoint was at hand when this was built: the rule is the published one, visual quality is not claimed."""
+        return self._put("enhance", check_enhance_args(weight, steps))
+
+    def _marshal_enhance(self, enhance):
+        weight, steps = enhance
+        e = E.Enhance()
+        e.weight = float(weight)
+        sarr = None
+        if steps is not None:
+            sarr = (C.c_ubyte * len(steps))(*steps)           # copied by the call
+            e.steps, e.num_steps = C.cast(sarr, C.POINTER(C.c_ubyte)), len(steps)
+        return (C.byref(e),), sarr
+
+    def clear_enhance(self):
+        """Remove it: a forward enqueues exactly what it did before `set_enhance`."""
+        return self._clear("enhance")
+
+    def enhance_state(self, reset=False):
+        """(on, launches, scores): whether it is on, how many score launches the engine has enqueued — one per visual block and forward that
+        applied it — and the last such forward's per-block scores as a list of floats (k5_dit_enhance_state; it waits for that forward).  A
+        score of 1.0 means the clamp held.  `reset` zeroes the count afterwards."""
+        if self._handle is None:
+            return False, 0, []
+        on, n, nb = C.c_int(0), C.c_longlong(0), C.c_int(0)
+        cap = self.num_visual_blocks
+        buf = (C.c_float * max(cap, 1))()
+        with torch.cuda.device(self._handle_device):
+            E.check(E.lib().k5_dit_enhance_state(self._handle, C.byref(on), C.byref(n), buf, cap, C.byref(nb), int(bool(reset))),
+                    "k5_dit_enhance_state")
+        return bool(on.value), n.value, [float(v) for v in buf[:min(nb.value, cap)]]
 
     @torch.no_grad()
     def forward_skip(self, x, text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos,

@@ -96,7 +96,7 @@ class Kandinsky5T2VPipeline:
                  nag_scale: float = None, nag_tau: float = 2.5, nag_alpha: float = 0.25, regions=None, region_base_weight: float = 0.0,
                  guidance_schedule=None, guidance_interval=None, cfg_zero_star: bool = False, cfg_zero_init: int = 0, cfg_rescale: float = 0.0,
                  slg_blocks=None, slg_scale: float = 0.0, slg_interval=None, slg_mode: str = "block", eta: float = 0.0, s_noise: float = 1.0,
-                 sde_interval=None, sde_seed: int = None):
+                 sde_interval=None, sde_seed: int = None, enhance_weight: float = None, enhance_interval=None):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -141,8 +141,22 @@ class Kandinsky5T2VPipeline:
         sigma lies in `sde_interval` (None = all) the Euler step stops short and the latent is re-noised to the next sigma with noise
         generated inside the update kernel from (`sde_seed`, step, element) (`sde_seed` None = `seed`); see `generate`.  eta 0 (default) is
         off, every rank passes the same values.  Not together with `context_seconds`, MagCache or previews.  No checkpoint was at hand when
-        this was written: visual quality is not claimed."""
+        this was written: visual quality is not claimed.
+        `enhance_weight`, `enhance_interval` (optional, extension): Enhance-A-Video, `pipe(text, enhance_weight=4.0)` — on the steps whose
+        sigma lies in `enhance_interval` (None = all) every visual block scales its self-attention output by the cross-frame attention
+        score of its own queries and keys; see `generate`.  None (default) is off, 0.0 is a valid weight.  Not on a sequence-parallel
+        group, not with more than 64 latent frames per forward.  No checkpoint was at hand when this was written: visual quality is not
+        claimed."""
         ctx = {}
+        enhance_kw = {}
+        if enhance_weight is not None or enhance_interval is not None:
+            from .generation_utils import _enhance_for_run, enhance_plan
+            enhance_plan([1.0, 0.0], enhance_interval)
+            lat = 1 if time_length == 0 else time_length * 24 // 4 + 1
+            _enhance_for_run(self.dit, [1.0, 0.0], 0, enhance_weight, None, lat if context_seconds is None else min(lat, int(context_seconds * 24 // 4 + 1)))
+            if enhance_weight is None:
+                raise ValueError("enhance_interval needs enhance_weight")
+            enhance_kw = dict(enhance_weight=float(enhance_weight), enhance_interval=enhance_interval)
         sto_kw = {}
         if eta or sde_interval is not None or float(s_noise) != 1.0:
             from .generation_utils import _stochastic_for_run, stochastic_plan
@@ -225,6 +239,7 @@ class Kandinsky5T2VPipeline:
                                  device=self.device_map["dit"], vae_device=self.device_map["vae"],
                                  text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload,
                                  image=image, video=video, strength=strength, mask=mask, callback=callback,
-                                 preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw, **guide_kw, **skip_kw, **sto_kw)
+                                 preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw, **guide_kw, **skip_kw, **sto_kw,
+                                 **enhance_kw)
         torch.cuda.empty_cache()
         return self._save(images, time_length, save_path) if self.local_dit_rank == 0 else None

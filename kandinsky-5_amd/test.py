@@ -105,7 +105,29 @@ def build_parser():
     p.add_argument("--sde_interval", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("LO", "HI"),
                    help="with --eta: only on the steps whose sigma lies in [LO, HI] (default every step)")
     p.add_argument("--sde_seed", type=int, default=argparse.SUPPRESS, metavar="N", help="with --eta: seed of the step noise (default: the run's seed)")
+    p.add_argument("--enhance_weight", type=float, default=argparse.SUPPRESS, metavar="W",
+                   help="Enhance-A-Video: every visual block scales its self-attention output by max(1, mean cross-frame attention * (frames + W)); "
+                        "W >= 0, 0 is a valid weight (commonly 2 to 5 — not tuned on these checkpoints)")
+    p.add_argument("--enhance_interval", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("LO", "HI"),
+                   help="with --enhance_weight: only on the steps whose sigma lies in [LO, HI] (default every step)")
     return p
+
+
+def enhance_keywords(args):
+    """--enhance_weight / --enhance_interval -> the pipeline's keywords"""
+    if not hasattr(args, "enhance_weight"):
+        if hasattr(args, "enhance_interval"):
+            raise ValueError("--enhance_interval needs --enhance_weight")
+        return {}
+    kw = {"enhance_weight": args.enhance_weight}
+    if not kw["enhance_weight"] >= 0.0 or kw["enhance_weight"] == float("inf"):
+        raise ValueError(f"--enhance_weight must be a finite number >= 0 (got {kw['enhance_weight']})")
+    if hasattr(args, "enhance_interval"):
+        lo, hi = args.enhance_interval
+        if not lo <= hi:
+            raise ValueError(f"--enhance_interval needs LO <= HI (got {lo}, {hi})")
+        kw["enhance_interval"] = (lo, hi)
+    return kw
 
 
 def stochastic_keywords(args):
@@ -284,6 +306,7 @@ def main(argv=None):
     guide_kw = guidance_keywords(args)
     skip_kw = skip_keywords(args)
     sto_kw = stochastic_keywords(args)
+    enhance_kw = enhance_keywords(args)
     from kandinsky import get_T2V_pipeline
     pipe = get_T2V_pipeline(device_map={"dit": "cuda:0", "vae": "cuda:0", "text_embedder": "cuda:0"}, conf_path=args.config,
                             offload=args.offload, magcache=args.magcache and not args.calibrate_magcache,
@@ -323,6 +346,7 @@ def main(argv=None):
     edit_kw.update(guide_kw)
     edit_kw.update(skip_kw)
     edit_kw.update(sto_kw)
+    edit_kw.update(enhance_kw)
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
