@@ -557,7 +557,7 @@ struct k5_dit {
   } guide;
 
   // Skip-layer guidance (k5_dit_set_skip_guidance): a third velocity from the conditional forward with some visual blocks skipped.
-  // forward_impl forks at the first skipped block (Fork below); sample_impl decides per step.  on: a set is held; live(): it also has a scale.
+  // ForwardRun forks at the first skipped block (visual_blocks / skip_branch); sample_impl decides per step.  on: a set is held; live(): it also has a scale.
   struct Skip {
     bool on = false;
     std::vector<char> skipped;                     // [num_visual_blocks] 0 / 1
@@ -581,8 +581,8 @@ struct k5_dit {
   } sto;
 
   // Enhance-A-Video (k5_dit_set_enhance): per visual block the cross-frame attention score of the normalised q | k, and the
-  // attention output times that score in front of the out projection.  sample_impl sets `gate` per step; forward_impl decides `live` for the
-  // forward (and the column table under NABLA), run_block names the score's slot, run_self_attention enqueues.
+  // attention output times that score in front of the out projection.  sample_impl sets `gate` per step; ForwardRun decides `live` for the
+  // forward (and the column table under NABLA, token_order), its block() names the score's slot, run_self_attention enqueues.
   struct Enhance {
     bool on = false;
     float weight = 0.f;
@@ -597,6 +597,8 @@ struct k5_dit {
     DevBuf scores, part, frame_rows;               // fp32 [num_visual_blocks] | double [S Hh] | int32 [S][T]
     int rows_shape[3] = {0, 0, 0};                 // the (T, H/2, W/2) frame_rows was built for
     bool at(int i) const { return on && (steps.empty() || steps[i] != 0); }
+    // a forward of `frames` frames applies it: it is set, the sampler's step (if any) has it on and there is more than one frame
+    bool applies(int frames, int blocks) const { return on && gate != 0 && frames >= 2 && blocks > 0; }
   } enh;
 
   // MagCache (reference kandinsky/magcache_utils.py:16-101): skip the visual blocks on some calls and re-apply the
@@ -612,6 +614,18 @@ struct k5_dit {
     DevBuf residual[2]; size_t res_elems[2] = {0, 0};
     DevBuf pm_one;                                 // fp32 [+1 x D | -1 x D]
     long long n_ran = 0, n_skipped = 0;
+    int slot() const { return cnt & 1; }           // the cond / uncond slot of the call to come
+    void reset_acc() { for (int j = 0; j < 2; ++j) { acc_ratio[j] = 1.0; acc_err[j] = 0; acc_steps[j] = 0; } }
+    // does the call to come skip its visual blocks (magcache_utils.py:59-76)?  float64 like the reference's numpy scalars
+    bool decide() {
+      const int j = slot();
+      if (cnt < (int)((double)table.size() * retention)) return false;
+      acc_ratio[j] *= table[cnt]; acc_steps[j] += 1; acc_err[j] += std::fabs(1.0 - acc_ratio[j]);
+      if (acc_err[j] < thresh && acc_steps[j] <= K) return true;
+      acc_err[j] = 0; acc_steps[j] = 0; acc_ratio[j] = 1.0;
+      return false;
+    }
+    void advance() { cnt += stride; if (cnt >= (int)table.size()) { cnt = first; reset_acc(); } }   // the end of a call (:91-100)
   } mag;
 
   // MagCache calibration (k5_dit_set_magcache_calibrate): every call runs its blocks and leaves the statistics of its residual against the
@@ -624,6 +638,8 @@ struct k5_dit {
     size_t res_elems[2] = {0, 0};
     DevBuf table, part;                            // [2 * num_steps][4] | per-workgroup partials of the pass
     hipStream_t last_stream = nullptr;
+    int slot() const { return cnt & 1; }
+    int cur() const { return prev[slot()] ^ 1; }   // the slot's buffer the call to come fills
   } cal;
 
   // LoRA adapters merged into the packed weights (k5_dit_add_lora): the packed bits of every touched matrix as they were before the first
@@ -1655,6 +1671,16 @@ int to_bf16(k5_dit* d, hipStream_t s, const void* src, int dtype, size_t n, DevB
 // ---------------------------------------------------------------------------------------------
 struct SpCand { int mode, slices, passes; const char* name; };
 
+// Token shards of a sequence-parallel forward: whole 64-token blocks, ceil(blocks / P) per rank in whole slices (the sliced K / V^T exchange,
+// "sp_slices"); the last rank takes what is left (3660 blocks over 8 ranks: 7 x 458 + 454).  n_pad = slot size in the gather buffers, n = rows
+// `rank` really owns from token tok0 on; idle: the slot size leaves a rank without rows.  The forward's layout and the autotune's candidates
+struct Shard { int n, n_pad, tok0; bool idle; };
+Shard shard_layout(int N, int P, int slices, int rank) {
+  const int S = slices > 1 ? slices : 1;
+  const int n_pad = ((N / 64 + P * S - 1) / (P * S)) * S * 64, tok0 = rank * n_pad;
+  return {N - tok0 < n_pad ? N - tok0 : n_pad, n_pad, tok0, (long long)(P - 1) * n_pad >= N};
+}
+
 // pure host logic, exported for a CPU test (k5_sp_pick_schedule): candidate c costs max over ranks of times[r * ncand + c] (a collective
 // schedule is as slow as its slowest rank); the cheapest valid one wins, ties to the lowest index (= the more conservative schedule);
 // a non-finite or non-positive time disqualifies the candidate on every rank alike (all ranks see the same gathered table)
@@ -1670,6 +1696,14 @@ int sp_pick(const float* times, int ncand, int world, const int* valid, float* c
     if (ok && (best < 0 || t < best_t)) { best = c; best_t = t; }
   }
   return best;
+}
+
+// the workspaces of a sharded forward whose slots hold n_pad rows: the gather buffers take every rank's slot
+int ensure_sp_workspaces(k5_dit* d, int n_pad, int L) {
+  const size_t P = d->sp_world, slot = (size_t)n_pad * d->D * 2;
+  K5CHK(ensure_workspaces(d, (int)P * n_pad, L));
+  K5CHK(d->ws_q.ensure(slot)); K5CHK(d->ws_kfull.ensure(P * slot));
+  return d->ws_vtfull.ensure(P * slot);
 }
 
 int sp_autotune_run(k5_dit* d, hipStream_t s, int N, int L, const NablaArgs* nabla) {
@@ -1712,12 +1746,10 @@ int sp_autotune_run(k5_dit* d, hipStream_t s, int N, int L, const NablaArgs* nab
   const AttnW& a = d->vblocks[0].self_attn;
   for (int c = 0; c < nc; ++c) {
     d->sp_mode = cands[c].mode; d->sp_slices = cands[c].slices; d->sp_nabla_passes = cands[c].passes;
-    const int S = d->sp_slices > 1 ? d->sp_slices : 1;
-    const int n_pad = ((N / 64 + P * S - 1) / (P * S)) * S * 64, tok0 = d->sp_rank * n_pad;
-    const int n = N - tok0 < n_pad ? N - tok0 : n_pad;
-    if ((long long)(P - 1) * n_pad >= N || n <= 0) continue;       // this slot size leaves a rank without rows: not a candidate (time stays -1 everywhere)
-    K5CHK(ensure_workspaces(d, P * n_pad, L));
-    K5CHK(d->ws_q.ensure((size_t)n_pad * D * 2)); K5CHK(d->ws_kfull.ensure((size_t)P * n_pad * D * 2)); K5CHK(d->ws_vtfull.ensure((size_t)P * n_pad * D * 2));
+    const Shard sh = shard_layout(N, P, d->sp_slices, d->sp_rank);
+    if (sh.idle) continue;       // this slot size leaves a rank without rows: not a candidate (time stays -1 everywhere)
+    const int n = sh.n, n_pad = sh.n_pad, tok0 = sh.tok0;
+    K5CHK(ensure_sp_workspaces(d, n_pad, L));
     // finite, harmless operands: activations 0.1 (bf16 0x3dcd), rotary tables and gates zero (the out projection then adds nothing)
     HIPCHK(hipMemsetD16Async((hipDeviceptr_t)d->ws_h.p, 0x3dcd, (size_t)n_pad * D, s));
     HIPCHK(hipMemsetD16Async((hipDeviceptr_t)d->ws_vis.p, 0x3dcd, (size_t)n_pad * D, s));
@@ -1872,144 +1904,171 @@ static const char* magcache_mode(const k5_dit* d) {
   return d->mag.on ? "MagCache is set" : d->cal.on ? "MagCache calibration is" : nullptr;
 }
 
-int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, float time, const float* x,
-                 int x_channels, void* out_velocity, hipStream_t s, const float* tvec = nullptr, const int* step = nullptr,
-                 int text_slot = -1, const float* vcond = nullptr, void* out_skip = nullptr) {
+// NABLA's fractal token order (utils.py:31-41,54-78): 8 x 8 spatial tiles contiguous.  Row i of that order holds token (t, y, x)
+struct Tok { int t, y, x; };
+Tok fractal_token(int i, int Hp, int Wp) {
+  const int Hb = Hp / 8, Wb = Wp / 8, b = i >> 6, r = i & 63;
+  return {b / (Hb * Wb), (b / Wb) % Hb * 8 + (r >> 3), b % Wb * 8 + (r & 7)};
+}
+// A table over the rows of that order, cached per shape: put(v, i, the token of row i) fills it.  The upload is synchronous: the eager first step
+// of a shape reaches it, a captured step finds the table
+template <class Put> int token_table(DevBuf& buf, int (&shape)[3], int Tp, int Hp, int Wp, Put put) {
+  if (shape[0] == Tp && shape[1] == Hp && shape[2] == Wp) return K5_OK;
+  const int N = Tp * Hp * Wp;
+  std::vector<int32_t> v((size_t)N);
+  for (int i = 0; i < N; ++i) put(v.data(), i, fractal_token(i, Hp, Wp));
+  K5CHK(buf.ensure((size_t)N * 4));
+  HIPCHK(hipMemcpy(buf.p, v.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+  shape[0] = Tp; shape[1] = Hp; shape[2] = Wp;
+  return K5_OK;
+}
+
+// One forward as its caller asks for it: k5_dit_forward, k5_dit_forward_skip (k5_dit_forward_many through the first) and SampleRun::forward fill it
+struct ForwardCall {
+  const k5_forward_args* a; const k5_text_cond& cond; float time;
+  const float* x; int x_channels;
+  void* out; hipStream_t s;
+  const float* tvec = nullptr; const int* step = nullptr;   // a captured step reads its time through the device-side step tables and counter
+  int text_slot = -1;                                        // the text cache slot of a k5_sample* call (0 cond, 1 uncond); -1: a forward of its own
+  const float* vcond = nullptr;                              // visual conditioning beside an x of in_visual_dim channels
+  void* out_skip = nullptr;                                  // the forking forward: where the skip branch's velocity goes
+};
+
+struct ForwardShape {   // patched frames / rows / columns, visual tokens, text rows, model width, input channels of the patch embedding
+  int Tp, Hp, Wp, N, L, D, Cin;
+  ForwardShape(const k5_dit* d, const ForwardCall& f)
+      : Tp(f.a->T), Hp(f.a->H / 2), Wp(f.a->W / 2), N(Tp * Hp * Wp), L(f.cond.text_len), D(d->D),
+        Cin(d->cfg.visual_cond ? 2 * d->cfg.in_visual_dim + 1 : d->cfg.in_visual_dim) {}
+};
+
+// Everything forward_impl refuses on its arguments and the handle's settings, before anything is enqueued or allocated and before any per-forward
+// state is touched: no HIP call and no write to the handle here.  (One refusal depends on the run, not on the settings: ForwardRun::shard.)
+static int forward_refusals(const k5_dit* d, const ForwardCall& f) {
   const k5_dit_config& c = d->cfg;
+  const k5_forward_args* a = f.a;
   if (!d->finalized) { k5_set_error("k5_dit_forward before k5_dit_finalize"); return K5_ERR_STATE; }
-  if (a->attention_type == 1) {   // NABLA workgroup size of this forward (see nabla_group_rows)
-    d->nabla_grp_now = d->nabla_group_rows ? d->nabla_group_rows : 4;
-    if (d->nabla_group_rows == 0 && d->h_nabla_kept && d->nabla_hint_possible > 0) {
-      const unsigned long long kept = *(volatile unsigned long long*)d->h_nabla_kept;   // whatever has landed: no synchronisation
-      if (kept > 0 && (double)kept < 0.5 * (double)d->nabla_hint_possible) d->nabla_grp_now = 2;
-    }
-    d->nabla_hint_pending = true;
-  }
   if (a->attention_type != 0 && a->attention_type != 1) { k5_set_error("attention_type must be 0 (flash) or 1 (nabla)"); return K5_ERR_ARG; }
   if (c.patch_size[0] != 1 || c.patch_size[1] != 2 || c.patch_size[2] != 2) return K5_ERR_UNSUPPORTED;
-  const int Tp = a->T, Hp = a->H / 2, Wp = a->W / 2;
-  const int N = Tp * Hp * Wp, L = cond.text_len, D = d->D;
-  const int Cin = c.visual_cond ? 2 * c.in_visual_dim + 1 : c.in_visual_dim;
-  if (N <= 0 || L <= 0 || (a->H & 1) || (a->W & 1)) { k5_set_error("bad shapes"); return K5_ERR_ARG; }
-  if (x_channels != Cin && x_channels != c.in_visual_dim) { k5_set_error("x_channels must be %d or %d", Cin, c.in_visual_dim); return K5_ERR_ARG; }
-  if (vcond && (!c.visual_cond || x_channels != c.in_visual_dim)) { k5_set_error("visual_cond needs a visual_cond model and x of in_visual_dim channels"); return K5_ERR_ARG; }
+  const ForwardShape sh(d, f);
+  if (sh.N <= 0 || sh.L <= 0 || (a->H & 1) || (a->W & 1)) { k5_set_error("bad shapes"); return K5_ERR_ARG; }
+  if (f.x_channels != sh.Cin && f.x_channels != c.in_visual_dim) { k5_set_error("x_channels must be %d or %d", sh.Cin, c.in_visual_dim); return K5_ERR_ARG; }
+  if (f.vcond && (!c.visual_cond || f.x_channels != c.in_visual_dim)) { k5_set_error("visual_cond needs a visual_cond model and x of in_visual_dim channels"); return K5_ERR_ARG; }
   const int P = d->sp_world;
   const bool sp = d->comm.active();  // a communicator (even of size 1) selects the sharded code path
-  auto& sk = d->skip;
-  if (out_skip) {   // the forking forward (k5_dit_forward_skip, a skip step of k5_sample*): refused before anything is enqueued
-    if (!sk.on) { k5_set_error("k5_dit_forward_skip: no skip set on the handle (k5_dit_set_skip_guidance)"); return K5_ERR_STATE; }
+  if (f.out_skip) {   // the forking forward (k5_dit_forward_skip, a skip step of k5_sample*)
+    if (!d->skip.on) { k5_set_error("k5_dit_forward_skip: no skip set on the handle (k5_dit_set_skip_guidance)"); return K5_ERR_STATE; }
     if (const char* mode = magcache_mode(d)) {
       k5_set_error("k5_dit_forward_skip: %s on the handle: the ratio table is indexed by the calls of a plain run", mode);
       return K5_ERR_STATE;
     }
   }
-  if (d->cal.on) {   // refusals of the calibration mode, before anything is enqueued
+  if (const k5_dit::MagCalib& cl = d->cal; cl.on) {
     if (sp || d->pair.active()) { k5_set_error("MagCache calibration is a one-GPU job: the handle is in a %s", sp ? "sequence-parallel group" : "CFG pair"); return K5_ERR_STATE; }
-    if (d->cal.cnt >= 2 && d->cal.res_elems[d->cal.cnt & 1] != (size_t)N * D) {
-      k5_set_error("MagCache calibration: this forward has %d x %d residual elements, the previous call of its slot had %zu", N, D, d->cal.res_elems[d->cal.cnt & 1]);
+    if (cl.cnt >= 2 && cl.res_elems[cl.slot()] != (size_t)sh.N * sh.D) {
+      k5_set_error("MagCache calibration: this forward has %d x %d residual elements, the previous call of its slot had %zu", sh.N, sh.D, cl.res_elems[cl.slot()]);
       return K5_ERR_ARG;
     }
   }
-  if (sp && P > 1 && !d->emulated && d->sp_autotune && !d->sp_tuned && !d->vblocks.empty() && N % 64 == 0) {
-    NablaArgs tna{};
-    const bool tn = a->attention_type == 1 && !(Hp % 8) && !(Wp % 8);
-    if (tn) tna = NablaArgs{Tp, Hp / 8, Wp / 8, a->nabla_wT, a->nabla_wH, a->nabla_wW, a->nabla_P};
-    if (a->attention_type == 0 || tn) K5CHK(sp_autotune_run(d, s, N, L, tn ? &tna : nullptr));
+  if (sp) {   // with the slices the handle has now: a tuning run that follows only picks slot sizes that leave no rank without work
+    if (sh.N % 64) { k5_set_error("sequence parallelism needs whole 64-token blocks (token count %d)", sh.N); return K5_ERR_UNSUPPORTED; }
+    if (shard_layout(sh.N, P, d->sp_slices, d->sp_rank).idle) { k5_set_error("sequence parallel x%d: %d token blocks leave a rank without work", P, sh.N / 64); return K5_ERR_UNSUPPORTED; }
   }
-  // token shards: whole 64-token blocks, ceil(blocks / P) per rank; the last rank takes what is left (3660 blocks over 8
-  // ranks: 7 x 458 + 454).  n_pad = slot size in the gather buffers, n = rows this rank really owns.
-  int n = N, n_pad = N, tok0 = 0;
-  if (sp) {
-    if (N % 64) { k5_set_error("sequence parallelism needs whole 64-token blocks (token count %d)", N); return K5_ERR_UNSUPPORTED; }
-    const int S = d->sp_slices > 1 ? d->sp_slices : 1;   // slots are whole slices (sliced K / V^T exchange, "sp_slices")
-    n_pad = ((N / 64 + P * S - 1) / (P * S)) * S * 64;
-    tok0 = d->sp_rank * n_pad;
-    n = N - tok0 < n_pad ? N - tok0 : n_pad;
-    if ((long long)(P - 1) * n_pad >= N) { k5_set_error("sequence parallel x%d: %d token blocks leave a rank without work", P, N / 64); return K5_ERR_UNSUPPORTED; }
-  }
-  // normalized attention guidance: the conditional branch only (slot 1 is the unconditional forward of k5_sample*)
-  const k5_text_cond* ncond = d->nag.on && text_slot != 1 ? d->nag.neg : nullptr;
-  // regional prompts: the same branch; a forward of another shape than the masks' is refused before anything is enqueued
-  auto& rg = d->regions;
+  const k5_dit::Regions& rg = d->regions;
   if (rg.on && (a->T != rg.T || a->H != rg.H || a->W != rg.W)) {
     k5_set_error("regional prompts: the masks are (%d, %d, %d), this forward is (%d, %d, %d)", rg.T, rg.H, rg.W, a->T, a->H, a->W);
     return K5_ERR_ARG;
   }
-  const int Rg = rg.on && text_slot != 1 ? rg.R : 0;
-  // Enhance-A-Video: this forward applies it when it is set, the sampler's step (if any) has it on and there is more than one frame
-  auto& en = d->enh;
-  en.live = en.on && en.gate != 0 && Tp >= 2 && c.num_visual_blocks > 0;
-  if (en.live && sp) {
-    en.live = false;
-    k5_set_error("Enhance-A-Video is set (k5_dit_set_enhance) and the handle is in a sequence-parallel group: the frames of a column live on different ranks");
-    return K5_ERR_STATE;
-  }
-  if (en.live && Tp > 64) {
-    en.live = false;
-    k5_set_error("Enhance-A-Video is set (k5_dit_set_enhance): %d frames are more than a wave's four 32 x 32 accumulators hold (64)", Tp);
-    return K5_ERR_UNSUPPORTED;
-  }
-  int Lmax = ncond && ncond->text_len > L ? ncond->text_len : L;   // every stream borrows the text blocks' scratch: size it by the longest
-  for (int r = 0; r < Rg; ++r) Lmax = rg.conds[r].text_len > Lmax ? rg.conds[r].text_len : Lmax;
-  K5CHK(ensure_workspaces(d, sp ? P * n_pad : N, Lmax));
-  if (sp) {
-    K5CHK(d->ws_q.ensure((size_t)n_pad * D * 2)); K5CHK(d->ws_kfull.ensure((size_t)P * n_pad * D * 2));
-    K5CHK(d->ws_vtfull.ensure((size_t)P * n_pad * D * 2));
-  }
-  // NABLA: tokens are processed in fractal order (8x8 spatial tiles contiguous), utils.py:31-41,54-78
-  const bool nabla = a->attention_type == 1;
-  d->last_nabla = nabla;
-  NablaArgs na{};
-  const int32_t* perm = nullptr;
-  if (nabla) {
-    if ((Hp % 8) || (Wp % 8)) { k5_set_error("nabla attention needs latent H, W divisible by 16 (got %d x %d)", a->H, a->W); return K5_ERR_ARG; }
-    na = NablaArgs{Tp, Hp / 8, Wp / 8, a->nabla_wT, a->nabla_wH, a->nabla_wW, a->nabla_P};
-    if (d->perm_shape[0] != Tp || d->perm_shape[1] != Hp || d->perm_shape[2] != Wp) {
-      std::vector<int32_t> pv((size_t)N);
-      const int Hb = Hp / 8, Wb = Wp / 8;
-      for (int i = 0; i < N; ++i) {
-        const int b = i >> 6, r = i & 63, t = b / (Hb * Wb), hb = (b / Wb) % Hb, wb = b % Wb;
-        pv[i] = (t * Hp + hb * 8 + (r >> 3)) * Wp + wb * 8 + (r & 7);
-      }
-      K5CHK(d->ws_perm.ensure((size_t)N * 4));
-      HIPCHK(hipMemcpy(d->ws_perm.p, pv.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-      d->perm_shape[0] = Tp; d->perm_shape[1] = Hp; d->perm_shape[2] = Wp;
+  if (d->enh.applies(sh.Tp, c.num_visual_blocks)) {
+    if (sp) {
+      k5_set_error("Enhance-A-Video is set (k5_dit_set_enhance) and the handle is in a sequence-parallel group: the frames of a column live on different ranks");
+      return K5_ERR_STATE;
     }
-    perm = d->ws_perm.as<int32_t>();
-  }
-  if (en.live) {   // the score's workspaces, and under NABLA the token row of every (position, frame), cached per shape like the permutation
-    const int S = Hp * Wp;
-    K5CHK(en.scores.ensure((size_t)c.num_visual_blocks * 4));
-    K5CHK(en.part.ensure((size_t)k5_enhance_parts(d->Hh, S) * sizeof(double)));
-    en.T = Tp; en.S = S; en.rows = nullptr;
-    if (nabla) {
-      if (en.rows_shape[0] != Tp || en.rows_shape[1] != Hp || en.rows_shape[2] != Wp) {
-        std::vector<int32_t> fr((size_t)N);
-        const int Hb = Hp / 8, Wb = Wp / 8;
-        for (int i = 0; i < N; ++i) {   // row i of the fractal order holds token (t, y, x): see the permutation above
-          const int b = i >> 6, r = i & 63, t = b / (Hb * Wb), hb = (b / Wb) % Hb, wb = b % Wb;
-          const int p = (hb * 8 + (r >> 3)) * Wp + wb * 8 + (r & 7);
-          fr[(size_t)p * Tp + t] = i;
-        }
-        K5CHK(en.frame_rows.ensure((size_t)N * 4));
-        HIPCHK(hipMemcpy(en.frame_rows.p, fr.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-        en.rows_shape[0] = Tp; en.rows_shape[1] = Hp; en.rows_shape[2] = Wp;
-      }
-      en.rows = en.frame_rows.as<int32_t>();
+    if (sh.Tp > 64) {
+      k5_set_error("Enhance-A-Video is set (k5_dit_set_enhance): %d frames are more than a wave's four 32 x 32 accumulators hold (64)", sh.Tp);
+      return K5_ERR_UNSUPPORTED;
     }
-    en.last_stream = s;
   }
-  K5CHK(prepare_rope(d, s, a, Tp, Hp, Wp, perm));
-  const float *tcos = nullptr, *tsin = nullptr;
-  K5CHK(prepare_text_rope(d, s, cond, &tcos, &tsin));
+  if (a->attention_type == 1 && ((sh.Hp % 8) || (sh.Wp % 8))) { k5_set_error("nabla attention needs latent H, W divisible by 16 (got %d x %d)", a->H, a->W); return K5_ERR_ARG; }
+  return K5_OK;
+}
 
-  const float* mod = d->ws_mod.as<float>();
-  k5_dit::TextStream& base = d->streams[0];
+// What one forward_impl call works on: filled top to bottom by shard() and token_order() before the first launch, then read by the phases in the
+// order forward_impl names them.
+struct ForwardRun : ForwardShape {
+  k5_dit* const d; const ForwardCall& f; const k5_forward_args* const a; const hipStream_t s;
+  const bool sp, nabla;                     // sp: a communicator (even of size 1) selects the sharded code path
+  // normalized attention guidance and regional prompts: the conditional branch only (slot 1 is the unconditional forward of k5_sample*)
+  const k5_text_cond* const ncond; const int Rg;
+  int n, n_pad, tok0 = 0, sched = 0;        // the shard (shard_layout) and its self-attention schedule (sp_schedule)
+  NablaArgs na{}; const int32_t* perm = nullptr;   // NABLA: its arguments, and the permutation of the fractal order its tokens are processed in
+  const float *mod = nullptr, *tcos = nullptr, *tsin = nullptr;   // every Modulation layer's output (one vector per forward); the prompt's RoPE tables
+  // the text streams of this forward's cross-attentions, in launch order, and where each one's attention output goes: the forward's own prompt,
+  // then the negative one of k5_dit_set_nag, then the regions' of k5_dit_set_regions; nothing but the first on a step MagCache skips
+  struct { const k5_text_cond* cond; int stream; void* o; } act[1 + 1 + 8];   // stream: its index in k5_dit::streams
+  CrossStreams cx; bool cx_all = false;     // cx_all: the streams hold the keys / V^T of all visual blocks ("cross_kv_batched")
+  bool mag_skip = false;                    // MagCache skips this call's visual blocks
+  int fork_at = -1;                         // skip-layer guidance: the block whose input the skip branch starts from
+  size_t vis_elems() const { return (size_t)n * D; }
+
+  ForwardRun(k5_dit* d_, const ForwardCall& f_)
+      : ForwardShape(d_, f_), d(d_), f(f_), a(f_.a), s(f_.s), sp(d_->comm.active()), nabla(f_.a->attention_type == 1),
+        ncond(d_->nag.on && f_.text_slot != 1 ? d_->nag.neg : nullptr), Rg(d_->regions.on && f_.text_slot != 1 ? d_->regions.R : 0), n(N), n_pad(N) {}
+
+  // ---- the shard, what the forward decides before its first launch, and the workspaces ----
+  int shard() {
+    if (nabla) {   // NABLA workgroup size of this forward (see nabla_group_rows)
+      d->nabla_grp_now = d->nabla_group_rows ? d->nabla_group_rows : 4;
+      if (d->nabla_group_rows == 0 && d->h_nabla_kept && d->nabla_hint_possible > 0) {
+        const unsigned long long kept = *(volatile unsigned long long*)d->h_nabla_kept;   // whatever has landed: no synchronisation
+        if (kept > 0 && (double)kept < 0.5 * (double)d->nabla_hint_possible) d->nabla_grp_now = 2;
+      }
+      d->nabla_hint_pending = true;
+      na = NablaArgs{Tp, Hp / 8, Wp / 8, a->nabla_wT, a->nabla_wH, a->nabla_wW, a->nabla_P};
+    }
+    const int P = d->sp_world;
+    if (sp && P > 1 && !d->emulated && d->sp_autotune && !d->sp_tuned && !d->vblocks.empty()) K5CHK(sp_autotune_run(d, s, N, L, nabla ? &na : nullptr));
+    if (sp) { const Shard sh = shard_layout(N, P, d->sp_slices, d->sp_rank); n = sh.n; n_pad = sh.n_pad; tok0 = sh.tok0; }
+    auto& mg = d->mag;   // the one refusal that depends on the run: made here, with nothing enqueued (what decide() did to the accumulators stays)
+    if (mg.on && (mag_skip = mg.decide()) && mg.res_elems[mg.slot()] != vis_elems()) {
+      k5_set_error("magcache: skip decided but no cached residual of this shape for the slot");
+      return K5_ERR_ARG;
+    }
+    d->enh.live = d->enh.applies(Tp, d->cfg.num_visual_blocks);
+    int Lmax = ncond && ncond->text_len > L ? ncond->text_len : L;   // every stream borrows the text blocks' scratch: size it by the longest
+    for (int r = 0; r < Rg; ++r) Lmax = d->regions.conds[r].text_len > Lmax ? d->regions.conds[r].text_len : Lmax;
+    K5CHK(sp ? ensure_sp_workspaces(d, n_pad, Lmax) : ensure_workspaces(d, N, Lmax));
+    mod = d->ws_mod.as<float>();
+    return K5_OK;
+  }
+
+  // ---- token order: NABLA's permutation, the Enhance-A-Video score's workspaces (under NABLA the token row of every (position, frame)), RoPE ----
+  int token_order() {
+    auto& en = d->enh;
+    d->last_nabla = nabla;
+    if (nabla) {
+      K5CHK(token_table(d->ws_perm, d->perm_shape, Tp, Hp, Wp, [this](int32_t* v, int i, Tok k) { v[i] = (k.t * Hp + k.y) * Wp + k.x; }));
+      perm = d->ws_perm.as<int32_t>();
+    }
+    if (en.live) {
+      const int S = Hp * Wp;
+      K5CHK(en.scores.ensure((size_t)d->cfg.num_visual_blocks * 4));
+      K5CHK(en.part.ensure((size_t)k5_enhance_parts(d->Hh, S) * sizeof(double)));
+      en.T = Tp; en.S = S; en.rows = nullptr;
+      if (nabla) {
+        K5CHK(token_table(en.frame_rows, en.rows_shape, Tp, Hp, Wp, [this](int32_t* v, int i, Tok k) { v[(size_t)(k.y * Wp + k.x) * Tp + k.t] = i; }));
+        en.rows = en.frame_rows.as<int32_t>();
+      }
+      en.last_stream = s;
+    }
+    K5CHK(prepare_rope(d, s, a, Tp, Hp, Wp, perm));
+    return prepare_text_rope(d, s, f.cond, &tcos, &tsin);
+  }
+
   // ---- before_text_transformer_blocks (dit.py:129-137) ----
-  {
+  int prologue() {
     Scope sc(d, s, "prologue");
-    K5CHK(text_embeddings(d, s, cond, base, d->stream_cache(0, text_slot), true));
-    K5CHK(k5_launch_time_features(time, d->ws_tfeat.as<float>(), D, s, tvec, step));
+    K5CHK(text_embeddings(d, s, f.cond, d->streams[0], d->stream_cache(0, f.text_slot), true));
+    K5CHK(k5_launch_time_features(f.time, d->ws_tfeat.as<float>(), D, s, f.tvec, f.step));
     K5CHK(k5_launch_gemv_f32(d->ws_tfeat.as<float>(), d->time_w1.as<float>(), d->time_b1.as<float>(), d->ws_th1.as<float>(),
                              d->TD, D, 0, nullptr, s));
     K5CHK(k5_launch_gemv_f32(d->ws_th1.as<float>(), d->time_w2.as<float>(), d->time_b2.as<float>(), d->ws_temb.as<float>(),
@@ -2017,92 +2076,85 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     // every Modulation layer of the network in one GEMV (they all consume the same time_embed)
     K5CHK(k5_launch_gemv_f32(d->ws_temb.as<float>(), d->mod_w.as<float>(), d->mod_b.as<float>(), d->ws_mod.as<float>(),
                              (int)d->mod_rows, d->TD, 1, nullptr, s));
-    if (vcond) K5CHK(k5_launch_patchify_cond(x, vcond, d->ws_xp.p, a->T, a->H, a->W, x_channels, Cin, d->KvisPad, perm, s));
-    else K5CHK(k5_launch_patchify(x, d->ws_xp.p, a->T, a->H, a->W, x_channels, Cin, d->KvisPad, perm, s));
-    K5CHK(linear(LinearArgs(d->vis_lin, Act{d->ws_xp.as<bf16_t>() + (size_t)tok0 * d->KvisPad, nullptr, n, d->KvisPad}, d->ws_vis.p, D, s)));
+    if (f.vcond) K5CHK(k5_launch_patchify_cond(f.x, f.vcond, d->ws_xp.p, a->T, a->H, a->W, f.x_channels, Cin, d->KvisPad, perm, s));
+    else K5CHK(k5_launch_patchify(f.x, d->ws_xp.p, a->T, a->H, a->W, f.x_channels, Cin, d->KvisPad, perm, s));
+    return linear(LinearArgs(d->vis_lin, Act{d->ws_xp.as<bf16_t>() + (size_t)tok0 * d->KvisPad, nullptr, n, d->KvisPad}, d->ws_vis.p, D, s));
   }
-  K5CHK(text_blocks_run(d, s, base, tcos, tsin, mod));
-  // ---- MagCache decision (magcache_utils.py:59-76), float64 like the reference's numpy scalars ----
-  auto& mg = d->mag;
-  bool mag_skip = false;
-  const int slot = mg.cnt & 1;
-  const size_t vis_elems = (size_t)n * D;
-  if (mg.on) {
-    if (mg.cnt >= (int)((double)mg.table.size() * mg.retention)) {
-      mg.acc_ratio[slot] *= mg.table[mg.cnt];
-      mg.acc_steps[slot] += 1;
-      mg.acc_err[slot] += std::fabs(1.0 - mg.acc_ratio[slot]);
-      if (mg.acc_err[slot] < mg.thresh && mg.acc_steps[slot] <= mg.K) mag_skip = true;
-      else { mg.acc_err[slot] = 0; mg.acc_steps[slot] = 0; mg.acc_ratio[slot] = 1.0; }
-    }
-    if (mag_skip) {
-      if (mg.res_elems[slot] != vis_elems) { k5_set_error("magcache: skip decided but no cached residual of this shape for the slot"); return K5_ERR_ARG; }
+
+  // ---- MagCache and its calibration where the visual stream enters the blocks: a skipped call adds the slot's cached residual, a running one
+  // keeps ori_visual_embed ----
+  int residual_begin() {
+    auto& mg = d->mag;
+    if (mg.on && mag_skip) {
       Scope sc(d, s, "elementwise");   // visual_embed + residual (bf16 add), :78-79
-      K5CHK(k5_launch_gate_sum(d->ws_vis.p, mg.residual[slot].p, mg.pm_one.as<float>(), d->ws_vis.p, n, D, s));
+      K5CHK(k5_launch_gate_sum(d->ws_vis.p, mg.residual[mg.slot()].p, mg.pm_one.as<float>(), d->ws_vis.p, n, D, s));
       mg.n_skipped++;
-    } else {
-      K5CHK(mg.residual[slot].ensure(vis_elems * 2));
-      HIPCHK(hipMemcpyAsync(mg.residual[slot].p, d->ws_vis.p, vis_elems * 2, hipMemcpyDeviceToDevice, s));  // ori_visual_embed
+    } else if (mg.on) {
+      K5CHK(mg.residual[mg.slot()].ensure(vis_elems() * 2));
+      HIPCHK(hipMemcpyAsync(mg.residual[mg.slot()].p, d->ws_vis.p, vis_elems() * 2, hipMemcpyDeviceToDevice, s));  // ori_visual_embed
       mg.n_ran++;
     }
-  }
-  auto& cl = d->cal;
-  const int cslot = cl.cnt & 1, ccur = cl.prev[cslot] ^ 1;   // the slot's buffer this call fills
-  if (cl.on) {
-    K5CHK(cl.res[cslot][ccur].ensure(vis_elems * 2));
-    K5CHK(cl.part.ensure((size_t)k5_magcache_stats_blocks(n) * 4 * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(cl.res[cslot][ccur].p, d->ws_vis.p, vis_elems * 2, hipMemcpyDeviceToDevice, s));  // ori_visual_embed
-  }
-  // ---- visual blocks (dit.py:176-178, 61-79) ----
-  const bool cx_all = !mag_skip && d->cross_kv_batched && c.num_visual_blocks > 1 && d->cx_k.w.p;
-  if (!mag_skip) K5CHK(text_cross_kv(d, s, base, cx_all));
-  // ---- the text streams of this forward's cross-attentions, in launch order, and where each one's attention output goes: the forward's own
-  // prompt, then the negative one of k5_dit_set_nag, then the regions' of k5_dit_set_regions; nothing but the first on a step MagCache skips ----
-  struct { const k5_text_cond* cond; int stream; void* o; } act[1 + 1 + 8] = {{&cond, 0, d->ws_o.p}};   // stream: its index in k5_dit::streams
-  CrossStreams cx;
-  cx.n = 1; cx.kv_ready = cx_all;
-  if (!mag_skip && c.num_visual_blocks > 0) {
-    if (ncond) {
-      K5CHK(d->nag.o.ensure((size_t)n * D * 2));
-      act[cx.n++] = {ncond, 1, d->nag.o.p};
-      cx.nag = true;
+    auto& cl = d->cal;
+    if (cl.on) {
+      DevBuf& cur = cl.res[cl.slot()][cl.cur()];
+      K5CHK(cur.ensure(vis_elems() * 2)); K5CHK(cl.part.ensure((size_t)k5_magcache_stats_blocks(n) * 4 * sizeof(double)));
+      HIPCHK(hipMemcpyAsync(cur.p, d->ws_vis.p, vis_elems() * 2, hipMemcpyDeviceToDevice, s));  // ori_visual_embed
     }
-    if (Rg) K5CHK(rg.o.ensure((size_t)Rg * n * D * 2));
-    for (int r = 0; r < Rg; ++r) act[cx.n++] = {&rg.conds[r], 2 + r, rg.o.as<bf16_t>() + (size_t)r * n * D};
-    cx.R = Rg; cx.region_o_stride = (long long)n * D;
+    return K5_OK;
   }
-  for (int k = 1; k < cx.n; ++k)
-    K5CHK(text_stream_run(d, s, *act[k].cond, d->streams[act[k].stream], d->stream_cache(act[k].stream, text_slot), mod, cx_all));
-  // the regions' token weights in this forward's token order (computed once per region set and order; a sequence-parallel rank reads its rows
-  // from tok0 on)
-  if (cx.R) {
-    if (rg.w_order != (nabla ? 1 : 0)) {
-      Scope sc(d, s, "elementwise");
-      K5CHK(rg.w.ensure((size_t)N * (Rg + 1) * 4));
-      K5CHK(k5_launch_region_weights(rg.masks, Rg, rg.T, rg.H, rg.W, c.patch_size[0], c.patch_size[1], c.patch_size[2], rg.base_weight, perm,
-                                     rg.w.as<float>(), s));
-      rg.w_order = nabla ? 1 : 0;
+
+  // ---- the forward's streams: the base prompt's cross-attention keys / V^T, then every other active prompt through the text side ----
+  int text_streams() {
+    auto& rg = d->regions;
+    const int blocks = d->cfg.num_visual_blocks;
+    cx_all = !mag_skip && d->cross_kv_batched && blocks > 1 && d->cx_k.w.p;
+    if (!mag_skip) K5CHK(text_cross_kv(d, s, d->streams[0], cx_all));
+    act[0] = {&f.cond, 0, d->ws_o.p};
+    cx.n = 1; cx.kv_ready = cx_all;
+    if (!mag_skip && blocks > 0) {
+      if (ncond) {
+        K5CHK(d->nag.o.ensure(vis_elems() * 2));
+        act[cx.n++] = {ncond, 1, d->nag.o.p};
+        cx.nag = true;
+      }
+      if (Rg) K5CHK(rg.o.ensure((size_t)Rg * vis_elems() * 2));
+      for (int r = 0; r < Rg; ++r) act[cx.n++] = {&rg.conds[r], 2 + r, rg.o.as<bf16_t>() + (size_t)r * vis_elems()};
+      cx.R = Rg; cx.region_o_stride = (long long)vis_elems();
     }
-    cx.region_w = rg.w.as<float>() + (size_t)tok0 * (Rg + 1);
+    for (int k = 1; k < cx.n; ++k)
+      K5CHK(text_stream_run(d, s, *act[k].cond, d->streams[act[k].stream], d->stream_cache(act[k].stream, f.text_slot), mod, cx_all));
+    // the regions' token weights in this forward's token order (computed once per region set and order; a sequence-parallel rank reads its rows
+    // from tok0 on)
+    if (cx.R) {
+      if (rg.w_order != (nabla ? 1 : 0)) {
+        Scope sc(d, s, "elementwise");
+        const int* ps = d->cfg.patch_size;
+        K5CHK(rg.w.ensure((size_t)N * (Rg + 1) * 4));
+        K5CHK(k5_launch_region_weights(rg.masks, Rg, rg.T, rg.H, rg.W, ps[0], ps[1], ps[2], rg.base_weight, perm, rg.w.as<float>(), s));
+        rg.w_order = nabla ? 1 : 0;
+      }
+      cx.region_w = rg.w.as<float>() + (size_t)tok0 * (Rg + 1);
+    }
+    sched = sp ? sp_schedule(d, nabla) : 0;
+    if (sp) d->sp_mode_used = sched;
+    return K5_OK;
   }
-  const int sched = sp ? sp_schedule(d, nabla) : 0;
-  if (sp) d->sp_mode_used = sched;
+
   // one visual block on ws_vis.  pref_slot: the row of the softmax-form memory (0 cond, 1 uncond, 2 the skip branch); drop_sa: skip-layer
   // guidance mode 1, the block without its self-attention residual (its first LayerNorm goes with it)
-  auto run_block = [&](int i, int pref_slot, bool drop_sa) -> int {
+  int block(int i, int pref_slot, bool drop_sa) {
     const BlockW& b = d->vblocks[i];
     const float* m = mod + b.mod_off;
     const float* vcos = d->ws_vcos.as<float>() + (size_t)tok0 * 32;
     const float* vsin = d->ws_vsin.as<float>() + (size_t)tok0 * 32;
-    const bool ulysses = sched == 1, two_level = sched == 2;
-    en.block = i;   // the slot of this block's Enhance-A-Video score
+    d->enh.block = i;   // the slot of this block's Enhance-A-Video score
     // fp8 modes: the LayerNorm writes the e4m3 rows the projections read (no bf16 h, no quantisation pass) — "fp8_fuse_ln" = 0 keeps the two passes
     const bool h8_sa = d->fp8_fuse_ln && sched == 0 && (sp ? sa_sp_fp8_in(d, b.self_attn, n, n_pad, nabla) : sa_fp8_in(d, b.self_attn, n));
     if (!drop_sa) {
       K5CHK(ln_mod(d, s, d->ws_vis.p, m, d->ws_h.p, n, h8_sa));
       if (d->profiling) ++d->prof_self_blocks;   // bench.py: FLOPs of the roofline kernel = per-block FLOPs x the blocks that RAN
-      if (ulysses || two_level) {
-        K5CHK(run_self_attention_heads(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, two_level, pref_slot));
+      if (sched) {   // 1 Ulysses, 2 two-level
+        K5CHK(run_self_attention_heads(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, sched == 2, pref_slot));
       } else if (sp) {
         K5CHK(run_self_attention_sp(d, s, b.self_attn, d->ws_h.p, n, n_pad, N, d->ws_o.p, vcos, vsin, d->ws_vis.p, m + 2 * D, nabla ? &na : nullptr, pref_slot, h8_sa));
       } else {
@@ -2115,65 +2167,91 @@ int forward_impl(k5_dit* d, const k5_forward_args* a, const k5_text_cond& cond, 
     K5CHK(run_cross_attention(d, s, b.cross_attn, d->ws_h.p, n, d->ws_qk.p, cx, d->ws_vis.p, m + 5 * D));
     const bool h8_ff = d->fp8_fuse_ln && ff_fp8_in(d, b, n);
     K5CHK(ln_mod(d, s, d->ws_vis.p, m + 6 * D, d->ws_h.p, n, h8_ff));
-    K5CHK(run_ff(d, s, b, d->ws_h.p, n, d->ws_ff.p, d->ws_vis.p, m + 8 * D, h8_ff));
+    return run_ff(d, s, b, d->ws_h.p, n, d->ws_ff.p, d->ws_vis.p, m + 8 * D, h8_ff);
+  }
+
+  // ---- visual blocks (dit.py:176-178, 61-79).  The fork of skip-layer guidance: the visual stream as it enters block `fork_at` (the first skipped
+  // one; 0 with "skip_share_prefix" = 0) is copied aside, skip_branch starts from it ----
+  int visual_blocks() {
+    auto& sk = d->skip;
+    if (f.out_skip) {
+      fork_at = sk.share_prefix ? sk.k0 : 0;
+      K5CHK(sk.vis.ensure(vis_elems() * 2));
+    }
+    const int blocks = mag_skip ? 0 : d->cfg.num_visual_blocks;
+    for (int i = 0; i < blocks; ++i) {
+      if (i == fork_at) HIPCHK(hipMemcpyAsync(sk.vis.p, d->ws_vis.p, vis_elems() * 2, hipMemcpyDeviceToDevice, s));
+      K5CHK(block(i, f.text_slot > 0 ? 1 : 0, false));
+    }
+    if (d->enh.live && !mag_skip) d->enh.last_blocks = blocks;
     return K5_OK;
-  };
-  // the fork of skip-layer guidance: the visual stream as it enters block `fork_at` (the first skipped one; 0 with "skip_share_prefix" = 0) is
-  // copied aside, the skip branch starts from it below
-  const int fork_at = out_skip ? (sk.share_prefix ? sk.k0 : 0) : -1;
-  if (out_skip) K5CHK(sk.vis.ensure(vis_elems * 2));
-  for (int i = 0; i < (mag_skip ? 0 : c.num_visual_blocks); ++i) {
-    if (i == fork_at) HIPCHK(hipMemcpyAsync(sk.vis.p, d->ws_vis.p, vis_elems * 2, hipMemcpyDeviceToDevice, s));
-    K5CHK(run_block(i, text_slot > 0 ? 1 : 0, false));
   }
-  if (en.live && !mag_skip) en.last_blocks = c.num_visual_blocks;
-  if (mg.on) {
-    if (!mag_skip) {  // residual = visual_embed - ori_visual_embed (bf16), :84
-      Scope sc(d, s, "elementwise");
-      K5CHK(k5_launch_gate_sum(d->ws_vis.p, mg.residual[slot].p, mg.pm_one.as<float>() + D, mg.residual[slot].p, n, D, s));
-      mg.res_elems[slot] = vis_elems;
+
+  // ---- MagCache and its calibration where the visual stream leaves the blocks ----
+  int residual_end() {
+    auto& mg = d->mag;
+    if (mg.on) {
+      if (!mag_skip) {  // residual = visual_embed - ori_visual_embed (bf16), :84
+        Scope sc(d, s, "elementwise");
+        K5CHK(k5_launch_gate_sum(d->ws_vis.p, mg.residual[mg.slot()].p, mg.pm_one.as<float>() + D, mg.residual[mg.slot()].p, n, D, s));
+        mg.res_elems[mg.slot()] = vis_elems();
+      }
+      mg.advance();
     }
-    mg.cnt += mg.stride;   // :91-100
-    if (mg.cnt >= (int)mg.table.size()) {
-      mg.cnt = mg.first;
-      for (int j = 0; j < 2; ++j) { mg.acc_ratio[j] = 1.0; mg.acc_err[j] = 0; mg.acc_steps[j] = 0; }
+    auto& cl = d->cal;
+    if (cl.on) {   // the residual MagCache would cache, and its statistics against the slot's previous one (none on the slot's first call of a run)
+      const int slot = cl.slot(), cur = cl.cur();
+      {
+        Scope sc(d, s, "elementwise");
+        K5CHK(k5_launch_magcache_stats(d->ws_vis.p, cl.res[slot][cur].p, cl.cnt < 2 ? nullptr : cl.res[slot][cur ^ 1].p, cl.res[slot][cur].p,
+                                       cl.table.as<double>() + (size_t)cl.cnt * 4, cl.part.as<double>(), 1, n, D, s));
+      }
+      cl.prev[slot] = cur; cl.res_elems[slot] = vis_elems(); cl.last_stream = s;
+      cl.cnt += cl.no_cfg ? 2 : 1;
+      if (cl.cnt >= 2 * cl.num_steps) { cl.cnt = 0; cl.runs++; }
     }
+    return K5_OK;
   }
-  if (cl.on) {   // the residual MagCache would cache, and its statistics against the slot's previous one (none on the slot's first call of a run)
-    {
-      Scope sc(d, s, "elementwise");
-      K5CHK(k5_launch_magcache_stats(d->ws_vis.p, cl.res[cslot][ccur].p, cl.cnt < 2 ? nullptr : cl.res[cslot][ccur ^ 1].p, cl.res[cslot][ccur].p,
-                                     cl.table.as<double>() + (size_t)cl.cnt * 4, cl.part.as<double>(), 1, n, D, s));
-    }
-    cl.prev[cslot] = ccur; cl.res_elems[cslot] = vis_elems; cl.last_stream = s;
-    cl.cnt += cl.no_cfg ? 2 : 1;
-    if (cl.cnt >= 2 * cl.num_steps) { cl.cnt = 0; cl.runs++; }
-  }
+
   // ---- after_blocks / OutLayer (dit.py:149-153, nn.py:374-400) ----
-  auto out_layer = [&](void* out) -> int {
+  int out_layer(void* out) {
     Scope sc(d, s, "epilogue");
     const float* m = mod + d->out_mod_off;  // [shift | scale]
     K5CHK(k5_launch_ln_modulate(d->ws_vis.p, m + D, m, d->ws_h.p, n, D, D, D, s));
     K5CHK(linear(LinearArgs(d->out_lin, Act{d->ws_h.p, nullptr, n, D}, d->ws_y.as<bf16_t>() + (size_t)tok0 * d->Fout, d->Fout, s)));
     // every rank needs the whole velocity: the (replicated) latent is advanced identically on all ranks
     if (sp) K5CHK(d->comm.all_gather_inplace(d->ws_y.p, (size_t)n_pad * d->Fout, 2, s));
-    K5CHK(k5_launch_unpatchify(d->ws_y.p, out, Tp, Hp, Wp, c.out_visual_dim, d->Fout, perm, s));
-    return K5_OK;
-  };
-  K5CHK(out_layer(out_velocity));
-  // ---- the skip branch: the same latent, prompt and time, so the text streams, the modulation vector and the stacked cross-attention K/V above
-  // are its own; it restores the visual stream of the fork and runs the blocks from there under the skip rule, on row 2 of the form memory ----
-  if (out_skip) {
-    HIPCHK(hipMemcpyAsync(d->ws_vis.p, sk.vis.p, vis_elems * 2, hipMemcpyDeviceToDevice, s));
-    for (int i = fork_at; i < c.num_visual_blocks; ++i) {
+    return k5_launch_unpatchify(d->ws_y.p, out, Tp, Hp, Wp, d->cfg.out_visual_dim, d->Fout, perm, s);
+  }
+
+  // ---- the skip branch: the same latent, prompt and time, so the text streams, the modulation vector and the stacked cross-attention K/V are
+  // its own; it restores the visual stream of the fork and runs the blocks from there under the skip rule, on row 2 of the form memory ----
+  int skip_branch() {
+    auto& sk = d->skip;
+    HIPCHK(hipMemcpyAsync(d->ws_vis.p, sk.vis.p, vis_elems() * 2, hipMemcpyDeviceToDevice, s));
+    for (int i = fork_at; i < d->cfg.num_visual_blocks; ++i) {
       if (sk.skipped[i] && sk.mode == 0) continue;   // the identity: nothing is launched
-      K5CHK(run_block(i, 2, sk.skipped[i] != 0));
+      K5CHK(block(i, 2, sk.skipped[i] != 0));
       ++sk.blocks_run;
     }
     sk.blocks_shared += fork_at;
-    K5CHK(out_layer(out_skip));
+    return out_layer(f.out_skip);
   }
-  return K5_OK;
+};
+
+int forward_impl(k5_dit* d, const ForwardCall& f) {
+  K5CHK(forward_refusals(d, f));
+  ForwardRun r(d, f);
+  K5CHK(r.shard());
+  K5CHK(r.token_order());
+  K5CHK(r.prologue());
+  K5CHK(text_blocks_run(d, r.s, d->streams[0], r.tcos, r.tsin, r.mod));
+  K5CHK(r.residual_begin());
+  K5CHK(r.text_streams());
+  K5CHK(r.visual_blocks());
+  K5CHK(r.residual_end());
+  K5CHK(r.out_layer(f.out));
+  return f.out_skip ? r.skip_branch() : K5_OK;
 }
 
 }  // namespace
@@ -2373,7 +2451,7 @@ extern "C" int k5_dit_set_magcache(k5_dit* d, const double* ratio_table, int tab
   if (table_len > 0 && d->cal.on) { k5_set_error("k5_dit_set_magcache: the handle is calibrating (k5_dit_set_magcache_calibrate)"); return K5_ERR_STATE; }
   auto& mg = d->mag;
   mg.cnt = 0; mg.n_ran = mg.n_skipped = 0;
-  for (int j = 0; j < 2; ++j) { mg.acc_ratio[j] = 1.0; mg.acc_err[j] = 0; mg.acc_steps[j] = 0; mg.res_elems[j] = 0; }
+  mg.reset_acc(); mg.res_elems[0] = mg.res_elems[1] = 0;
   if (table_len <= 0) { mg.on = false; mg.table.clear(); return K5_OK; }
   if (!ratio_table || (table_len & 1) || K < 0) { k5_set_error("k5_dit_set_magcache: table of 2*num_steps ratios expected"); return K5_ERR_ARG; }
   mg.table.assign(ratio_table, ratio_table + table_len);
@@ -2443,8 +2521,7 @@ extern "C" int k5_dit_magcache_calibration(k5_dit* d, double* out, int cap_rows,
 extern "C" int k5_dit_forward(k5_dit* d, const k5_forward_args* a, void* out_velocity, void* stream) {
   g_err[0] = 0;
   if (!d || !a || !out_velocity || !a->x) return K5_ERR_ARG;
-  const int st = forward_impl(d, a, a->cond, a->time, a->x, a->x_channels, out_velocity, (hipStream_t)stream);
-  return st;
+  return forward_impl(d, ForwardCall{a, a->cond, a->time, a->x, a->x_channels, out_velocity, (hipStream_t)stream});
 }
 
 // "sequence-parallel group" or "CFG pair": the rank group the handle is in (nullptr: none), for the refusals of what is single-rank only
@@ -2453,7 +2530,7 @@ static const char* rank_group(const k5_dit* d) {
 }
 
 // Everything sample_impl refuses, before anything is enqueued or allocated and before any per-call state is touched: no HIP call and no
-// write to the handle here.  (A watched call's shape check comes later, where it always was: Watch::begin.)
+// write to the handle here (the forward's side of the same contract: forward_refusals).  (A watched call's shape check comes later, where it always was: Watch::begin.)
 static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit,
                            const k5_sample_windows_args* win, const char* who) {
   if (!d || !a || !a->latent || !a->sigmas || a->num_steps <= 0) return K5_ERR_ARG;
@@ -2659,8 +2736,10 @@ struct SampleRun {
   // `vel`.  `tables`: the forward reads its time through the device-side step tables when the step is captured; windows pass none.
   // `skip_vel`: the forward forks and leaves the skip branch's velocity there.
   int forward(int i, const k5_text_cond& cond, int slot, const float* x, void* vel, const float* vc, bool tables = true, void* skip_vel = nullptr) {
-    return forward_impl(d, &a->fwd, cond, t1000[i], x, d->cfg.in_visual_dim, vel, s, tables ? tvec : nullptr, tables ? step_ctr : nullptr, slot, vc,
-                        skip_vel);
+    ForwardCall f{&a->fwd, cond, t1000[i], x, d->cfg.in_visual_dim, vel, s};
+    if (tables) { f.tvec = tvec; f.step = step_ctr; }
+    f.text_slot = slot; f.vcond = vc; f.out_skip = skip_vel;
+    return forward_impl(d, f);
   }
 
   int step(int i) {   // enqueue step i: the forwards, then CFG + Euler
@@ -3279,7 +3358,9 @@ extern "C" int k5_dit_enhance_state(k5_dit* d, int* on, long long* launches, flo
 extern "C" int k5_dit_forward_skip(k5_dit* d, const k5_forward_args* a, void* out_velocity, void* out_velocity_skip, void* stream) {
   g_err[0] = 0;
   if (!d || !a || !out_velocity || !out_velocity_skip || !a->x) return K5_ERR_ARG;
-  return forward_impl(d, a, a->cond, a->time, a->x, a->x_channels, out_velocity, (hipStream_t)stream, nullptr, nullptr, -1, nullptr, out_velocity_skip);
+  ForwardCall f{a, a->cond, a->time, a->x, a->x_channels, out_velocity, (hipStream_t)stream};
+  f.out_skip = out_velocity_skip;
+  return forward_impl(d, f);
 }
 
 extern "C" int k5_dit_nag_state(k5_dit* d, int* on, long long* combines, int reset) {
@@ -3431,7 +3512,7 @@ int lora_drop_derived(k5_dit* d) {
   K5CHK(reset_attn_pref(d, nullptr));
   auto& mg = d->mag;
   mg.cnt = mg.first;
-  for (int j = 0; j < 2; ++j) { mg.acc_ratio[j] = 1.0; mg.acc_err[j] = 0; mg.acc_steps[j] = 0; mg.res_elems[j] = 0; }
+  mg.reset_acc(); mg.res_elems[0] = mg.res_elems[1] = 0;
   auto& cl = d->cal;
   if (cl.on) {
     cl.cnt = 0; cl.runs = 0;
@@ -3745,7 +3826,7 @@ extern "C" int k5_dit_get_option(k5_dit* d, const char* name, int* value) {
   else if (!strcmp(name, "sp_tuned")) *value = d->sp_tuned ? 1 : 0;
   else if (!strcmp(name, "fp8_effective")) {   // the classes of k5_dit_set_fp8 that RUN in e4m3 on this handle's path — the sharded schedules keep the out
     int m = d->fp8_mask;                       // projection in bf16 (bit 4), Ulysses also the q | k | V^T projections (bit 2); a bench must label its line with THIS mask
-    if (d->comm.active()) { m &= ~4; if (sp_schedule(d, d->last_nabla) != 0) m &= ~2; }   // the dispatch's own predicate (forward_impl: sp_schedule), with the attention type of the LAST forward
+    if (d->comm.active()) { m &= ~4; if (sp_schedule(d, d->last_nabla) != 0) m &= ~2; }   // the dispatch's own predicate (ForwardRun::text_streams: sp_schedule), with the attention type of the LAST forward
     *value = m;
   }
   else if (!strcmp(name, "rccl_ranks")) {   // the size the RCCL communicator reports (ncclCommCount): 0 = no communicator, -1 = a loopback group / no such symbol

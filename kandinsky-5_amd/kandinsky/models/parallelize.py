@@ -11,7 +11,7 @@ host-side shard bookkeeping shared with the tests.
 
 
 def token_shard(num_tokens: int, world: int, rank: int, slices: int = 1):
-    """(start, count) of the token rows owned by `rank` — the engine's layout (csrc/engine.hip forward_impl): whole 64-token
+    """(start, count) of the token rows owned by `rank` — the engine's layout (csrc/engine.hip shard_layout, used by forward_impl): whole 64-token
     blocks, ceil(blocks / world) per rank, the LAST rank takes what is left (3660 blocks over 8 ranks = 7 x 458 + 454), so the
     slot size in the gather buffers is the same on every rank and only the tail of the last slot is unused.  With the sliced
     K / V^T exchange (engine option "sp_slices" = slices > 1) a slot is a whole number of slices: a multiple of 64 * slices."""

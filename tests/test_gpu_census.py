@@ -1,5 +1,5 @@
 """What the in-engine sampler enqueues, by the engine's own profile: the launches of every kernel family after one `generate` of 4 steps on
-the tiny golden model, in nine modes, against the counts recorded in tests/golden/sampler_census.json (tools/sampler_census.py wrote them).
+the tiny golden model, in every mode of the tool, against the counts recorded in tests/golden/sampler_census.json (tools/sampler_census.py wrote them).
 Bit-identity does not catch a launch enqueued twice or a per-call reset that moved; these counts do.  Profiling turns graph replay off, so
 this is the eager loop; the captured step is held by bits in test_gpu_watch.py, test_gpu_edit.py and test_gpu_nag.py."""
 import importlib.util

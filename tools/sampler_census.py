@@ -1,10 +1,14 @@
 """What the sampler enqueues, counted by the engine's own profile: the launches of every kernel family after one `generate` of 4 steps on the
-tiny model of tests/golden/dit_tiny.safetensors at the golden shape (3, 8, 12, 16), in nine modes of the in-engine loop.  Bit-identity of the
+tiny model of tests/golden/dit_tiny.safetensors at the golden shape (3, 8, 12, 16), in the modes of the in-engine loop listed in MODES: nine
+of the sampler's own, then nine that reach the parts of the engine's forward the first nine never do (NABLA's token order alone and with
+Enhance-A-Video, which needs both token-order tables, at (3, 16, 16, 16), the smallest shape NABLA takes; the forking forward of skip-layer
+guidance in both modes; Enhance-A-Video dense; MagCache skipping and running; MagCache calibration; visual conditioning).  Bit-identity of the
 latent does not catch a launch that was enqueued twice or a per-call reset that moved; these counts do.  Profiling turns graph replay off, so
-this is the eager loop.  Public Python API only: the same script runs on any commit that has the nine modes.
+this is the eager loop.  Public Python API only: the same script runs on any commit that has the modes.
 
     python tools/sampler_census.py [--write]      (--write: tests/golden/sampler_census.json, what tests/test_gpu_census.py asserts)
 """
+import contextlib
 import json
 import os
 import sys
@@ -21,9 +25,23 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 CENSUS = os.path.join(GOLDEN, "sampler_census.json")
 FAMILIES = ("elementwise", "gemm", "attn_self", "attn_cross", "nabla_map", "prologue", "epilogue", "comm", "attn_text")
 MODES = ("plain_w1", "plain_w5", "edit_mask_w5", "windows_t6_w5", "watch_preview_x0_w5", "nag_A_w1", "regions_B_w5", "nag_regions_w1",
-         "regions_B_w5_per_block_kv")
+         "regions_B_w5_per_block_kv", "nabla_w5", "nabla_enhance_A_w5", "skip_block_w5", "skip_attention_interval_w5", "enhance_A_w5",
+         "magcache_hand_w2", "magcache_calibrate_w2", "visual_cond_w5")
 STEPS, HW = 4, (8, 12, 16)
+NABLA_HW = (16, 16, 16)   # the smallest latent whose H and W are divisible by 16: one 8 x 8 token tile per frame
 FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+
+
+def meta(name):
+    return json.load(open(os.path.join(GOLDEN, name)))
+
+
+def mode_conf(mode):
+    """the `conf` of a mode's `generate`: NABLA attention with the `nabla_attention` block of dit_tiny_meta.json, dense otherwise"""
+    if not mode.startswith("nabla_"):
+        return FLASH
+    return NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(**meta("dit_tiny_meta.json")["nabla_attention"])),
+              metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
 
 
 def tiny_model(device="cuda:0"):
@@ -68,7 +86,50 @@ def mode_keywords(mode, g):
         return g["gen.noise"], 1.0, {**nag, **regions}
     if mode in ("regions_B_w5", "regions_B_w5_per_block_kv"):   # guidance 5: the unconditional forwards, which must not grow, are counted too
         return g["gen.noise"], 5.0, regions
+    enhance = dict(enhance_weight=meta("dit_tiny_enhance_meta.json")["sets"]["A"]["weight"])
+    if mode in ("nabla_w5", "nabla_enhance_A_w5"):
+        return torch.randn(3, *NABLA_HW, generator=rnd), 5.0, enhance if mode == "nabla_enhance_A_w5" else {}
+    if mode == "enhance_A_w5":
+        return g["gen.noise"], 5.0, enhance
+    if mode in ("skip_block_w5", "skip_attention_interval_w5"):   # the tiny model has two visual blocks: the second is skipped, the first is the shared prefix
+        case = meta("dit_tiny_skip_meta.json")["cases"]["block_mid" if mode == "skip_block_w5" else "attention_interval"]
+        kw = dict(slg_blocks=[1], slg_scale=case["g"], slg_mode=case["mode"])
+        if "interval" in case:   # of the 4 steps' sigmas 1, .9375, .833, .625 three lie inside: steps that fork and one that does not
+            kw["slg_interval"] = tuple(case["interval"])
+        return g["gen.noise"], case["w"], kw
+    if mode == "magcache_hand_w2":
+        return g["gen.noise"], [c for c in meta("magcache_meta.json")["cases"] if c["tag"] == "hand_10"][0]["guidance_weight"], {}
+    if mode == "magcache_calibrate_w2":
+        return g["gen.noise"], [c for c in meta("magcache_calib_tiny.json")["cases"] if c["tag"] == "cfg"][0]["guidance_weight"], {}
+    if mode == "visual_cond_w5":
+        return g["gen.noise"], 5.0, dict(visual_cond=torch.randn(3, *HW, generator=rnd).cuda(),
+                                         visual_cond_mask=(torch.rand(3, *HW[:2], 1, generator=rnd) > 0.5).float().cuda())
     raise KeyError(mode)
+
+
+@contextlib.contextmanager
+def mode_handle(dit, mode):
+    """what a mode sets on the model around its `generate` and takes back after it"""
+    from kandinsky import magcache_utils as M
+    if mode == "magcache_hand_w2":
+        # the hand-made table of magcache_meta.json, re-sampled to the 4 steps: [1, 1, .97, .96, 1, .99, .99, .98].  The reference's retention of
+        # 0.2 would let call 1 of 8 decide before its slot has a residual, so the first half of the run is retained: calls 0..3 run, 4..7 skip
+        M.set_magcache_params(dit, [c for c in meta("magcache_meta.json")["cases"] if c["tag"] == "hand_10"][0]["ratios"], STEPS, False)
+        dit.retention_ratio = 0.5
+        M._apply(dit)
+        try:
+            yield
+            assert M.magcache_state(dit)[1:] == (4, 4), M.magcache_state(dit)
+        finally:
+            M.disable_magcache(dit)
+    elif mode == "magcache_calibrate_w2":
+        M.start_magcache_calibration(dit, STEPS, False)
+        try:
+            yield
+        finally:
+            M.stop_magcache_calibration(dit)
+    else:
+        yield
 
 
 def census(dit, g, mode):
@@ -77,16 +138,17 @@ def census(dit, g, mode):
     noise, w, kw = mode_keywords(mode, g)
     te = {"text_embeds": g["fwd.text"].cuda(), "pooled_embed": g["fwd.pooled"].cuda()}
     ne = {"text_embeds": g["gen.null_text"].cuda(), "pooled_embed": g["gen.null_pooled"].cuda()}
-    pos = [torch.arange(3), torch.arange(HW[0] // 2), torch.arange(HW[1] // 2)]
+    pos = [torch.arange(3), torch.arange(noise.shape[1] // 2), torch.arange(noise.shape[2] // 2)]
     dit.engine(torch.device("cuda", 0))
     dit.set_profiling(True)
     per_block_kv = mode.endswith("_per_block_kv")   # every visual block projects its own cross-attention keys / V^T
     try:
         if per_block_kv:
             dit.set_option("cross_kv_batched", 0)
-        dit.reset_profile()
-        generate(dit, "cuda:0", tuple(noise.shape), STEPS, te, ne, pos, torch.arange(7), torch.arange(4), w, 5.0, FLASH, noise=noise, **kw)
-        torch.cuda.synchronize()
+        with mode_handle(dit, mode):
+            dit.reset_profile()
+            generate(dit, "cuda:0", tuple(noise.shape), STEPS, te, ne, pos, torch.arange(7), torch.arange(4), w, 5.0, mode_conf(mode), noise=noise, **kw)
+            torch.cuda.synchronize()
         return {f: dit.get_profile(f)[1] for f in FAMILIES}
     finally:
         if per_block_kv:
