@@ -897,8 +897,8 @@ int k5_conv3d_bf16(const void* X, const void* W, const float* bias, void* out, i
  * and padding 0: out [To*Ho*Wo][ldc], To = (Ts-1)/st_t + 1, Ho = (Hs-1)/st_s + 1, Wo = (Ws-1)/st_s + 1. */
 int k5_conv3d_strided_bf16(const void* X, const void* W, const float* bias, void* out, int Ts, int Hs, int Ws, int Cin, int Cout,
                            int st_t, int st_s, int ldc, void* stream);
-/* nn.GroupNorm(G, C, eps) (+SiLU) on channels-last bf16 rows [M][C] (vae.py:246-263,672-673): fp32 statistics,
- * bf16 out.  workspace: device scratch of k5_groupnorm_workspace_size(M, G) bytes. */
+/* nn.GroupNorm(G, C, eps) (+SiLU) on channels-last bf16 rows [M][C] (vae.py:246-263,672-673): one-pass statistics (sums of
+ * x and x^2: fp32 over 4 rows, double beyond), fp32 normalisation, bf16 out.  workspace: device scratch of k5_groupnorm_workspace_size(M, G) bytes. */
 int64_t k5_groupnorm_workspace_size(int M, int G);
 int k5_groupnorm_bf16(const void* x, const float* gamma, const float* beta, void* out, int M, int C, int G, float eps,
                       int silu, void* workspace, void* stream);

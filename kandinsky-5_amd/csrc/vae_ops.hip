@@ -1,6 +1,6 @@
 // vae_ops.hip — HBM-bound kernels of the HunyuanVideo VAE decoder on channels-last bf16 activations [M][C].
 //   GroupNorm(32, eps 1e-6) (+SiLU)   vae.py:246-263, 351-355 (attention group_norm), 672-673
-//       two-level statistics: per-block fp32 partial sums -> double-precision combine -> mean / rstd per group,
+//       two-level statistics: per-block partial sums (fp32 within a loop trip, double beyond) -> combine -> mean / rstd per group,
 //       then one fused normalise*gamma+beta(+SiLU) pass writing bf16 (the fp32 GroupNorm output of autocast is
 //       only ever consumed by a bf16 conv / linear).
 //   frame-causal softmax              prepare_causal_attention_mask vae.py:110-122 + diffusers Attention softmax
@@ -13,56 +13,60 @@ namespace {
 
 constexpr int GN_ROWS = 512;  // rows per statistics block
 
-// partial[blk][g] = (sum, sumsq) over GN_ROWS rows x (C/G) channels.  Deterministic: per-thread partials go to LDS
+constexpr int GN_LOADS = 4;   // 16-B loads in flight per thread of the statistics pass = rows of one loop trip
+
+// partial[blk][g] = (sum, sumsq) over GN_ROWS rows x (C/G) channels, in double.  Deterministic: per-thread partials go to LDS
 // and each group is summed by one thread in a fixed order (no float atomics -> bit-reproducible decodes).
-__global__ __launch_bounds__(256) void gn_partial_kernel(const bf16_t* __restrict__ x, float* __restrict__ partial, int M,
+// The statistics are ONE pass over x and x^2, so the variance is what is left of sums (mean / sigma)^2 times as large, and bf16
+// inputs lie on a coarse grid: a long fp32 accumulation of their squares does not merely lose bits, it stalls — at mean 32, sigma 1
+// every other addend of a running sum past 2^20 ends in exactly half an ulp, a tie that rounds to the same (even) side each time, and
+// the variance came out 1 % low at C = 2048 (rstd 5e-3 high; 1e-3 at C = 512).  So only the GN_LOADS rows x 4 channels of one loop
+// trip are added in fp32 (exact for such data, 2^-24 of that short sum otherwise); trips, threads and blocks are added in double.
+__global__ __launch_bounds__(256) void gn_partial_kernel(const bf16_t* __restrict__ x, double* __restrict__ partial, int M,
                                                          int C, int ldx, int G) {
-  __shared__ float ps[256][4];  // per thread: (sum, sumsq) for its first group, (sum, sumsq) for its second group
+  __shared__ double ps[256][4];  // per thread: (sum, sumsq) for its first group, (sum, sumsq) for its second group
   const int tid = threadIdx.x;
   const int nch = C >> 3, cg = C / G;       // 16-B chunks per row; channels per group
   const int r0 = blockIdx.x * GN_ROWS, r1 = min(r0 + GN_ROWS, M);
   // thread -> fixed chunk column (tid % nch), strides over rows: its 8 channels lie in <= 2 groups
   const int rows_par = 256 / nch > 0 ? 256 / nch : 1;
   const int ch = tid % nch, rsub = tid / nch;
-  float s[2] = {0.f, 0.f}, q[2] = {0.f, 0.f};
+  // a chunk's 8 channels lie in ONE group (cg >= 8) or are the two 4-channel groups of cg == 4: sum the halves separately
+  double slo = 0.0, shi = 0.0, qlo = 0.0, qhi = 0.0;
   if (rsub < rows_par) {
-    // a chunk's 8 channels lie in ONE group (cg >= 8) or are the two 4-channel groups of cg == 4: sum the halves separately
-    float slo = 0.f, shi = 0.f, qlo = 0.f, qhi = 0.f;
-    for (int rb = r0 + rsub; rb < r1; rb += 4 * rows_par) {   // four independent loads in flight; summation order unchanged
-      u32x4 raw[4];
+    for (int rb = r0 + rsub; rb < r1; rb += GN_LOADS * rows_par) {
+      u32x4 raw[GN_LOADS];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
+      for (int u = 0; u < GN_LOADS; ++u) {
         const int r = rb + u * rows_par;
         raw[u] = r < r1 ? *reinterpret_cast<const u32x4*>(x + (size_t)r * ldx + 8 * ch) : u32x4{0u, 0u, 0u, 0u};
       }
+      float tslo = 0.f, tshi = 0.f, tqlo = 0.f, tqhi = 0.f;   // this trip's values
 #pragma unroll
-      for (int u = 0; u < 4; ++u)
+      for (int u = 0; u < GN_LOADS; ++u)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float v = (j & 1) ? __uint_as_float(raw[u][j >> 1] & 0xffff0000u) : __uint_as_float(raw[u][j >> 1] << 16);
-          if (j < 4) { slo += v; qlo += v * v; } else { shi += v; qhi += v * v; }
+          if (j < 4) { tslo += v; tqlo += v * v; } else { tshi += v; tqhi += v * v; }
         }
+      slo += (double)tslo; shi += (double)tshi; qlo += (double)tqlo; qhi += (double)tqhi;
     }
-    if (cg == 4) { s[0] = slo; q[0] = qlo; s[1] = shi; q[1] = qhi; }
-    else { s[0] = slo + shi; q[0] = qlo + qhi; }
   }
-  ps[tid][0] = s[0]; ps[tid][1] = q[0]; ps[tid][2] = s[1]; ps[tid][3] = q[1];
+  if (cg == 4) { ps[tid][0] = slo; ps[tid][1] = qlo; ps[tid][2] = shi; ps[tid][3] = qhi; }
+  else { ps[tid][0] = slo + shi; ps[tid][1] = qlo + qhi; }
   __syncthreads();
-  if (tid < G) {
-    float ss = 0.f, qq = 0.f;
-    const int used = min(256, rows_par * nch);
-    for (int t = 0; t < used; ++t) {
-      const int tg0 = (8 * (t % nch)) / cg;
-      if (tg0 == tid) { ss += ps[t][0]; qq += ps[t][1]; }
-      else if (cg < 8 && tg0 + 1 == tid) { ss += ps[t][2]; qq += ps[t][3]; }
-    }
+  if (tid < G) {   // group tid's threads in increasing thread number: chunk columns tid cg / 8 .. + cg / 8 (cg == 4: half tid & 1 of chunk tid / 2) of every row slot
+    double ss = 0.0, qq = 0.0;
+    const int per = cg >= 8 ? cg >> 3 : 1, c0 = cg >= 8 ? tid * per : tid >> 1, half = cg >= 8 ? 0 : 2 * (tid & 1);
+    for (int rs = 0; rs < rows_par; ++rs)
+      for (int i = 0; i < per; ++i) { ss += ps[rs * nch + c0 + i][half]; qq += ps[rs * nch + c0 + i][half + 1]; }
     partial[((size_t)blockIdx.x * G + tid) * 2] = ss;
     partial[((size_t)blockIdx.x * G + tid) * 2 + 1] = qq;
   }
 }
 
 // one 256-thread block per group: strided double-precision sums over the per-block partials, LDS tree
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ partial, float* __restrict__ stats, int nblk,
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const double* __restrict__ partial, float* __restrict__ stats, int nblk,
                                                           int G, double count, float eps) {
   __shared__ double rs[256], rq[256];
   const int g = blockIdx.x, tid = threadIdx.x;
@@ -318,7 +322,7 @@ inline int done() { return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
 }  // namespace
 
 size_t k5_groupnorm_workspace_bytes(int M, int G) {
-  const size_t own = ((size_t)((M + GN_ROWS - 1) / GN_ROWS) * G * 2 + 2 * G) * sizeof(float);   // partials + (mean, rstd) of the two-pass form
+  const size_t own = (size_t)((M + GN_ROWS - 1) / GN_ROWS) * G * 2 * sizeof(double) + 2 * G * sizeof(float);   // partials + (mean, rstd) of the two-pass form
   const size_t quads = 2 * 64 * sizeof(float) + (size_t)64 * GNQ_SPLIT * 2 * sizeof(double);      // (mean, rstd) + first-level partials of the fused form
   return own > quads ? own : quads;
 }
@@ -354,8 +358,8 @@ int k5_launch_groupnorm_bf16(const void* x, const float* gamma, const float* bet
   if (!gn_shape_ok(M, C, G, ldx, ldo)) return K5_ERR_UNSUPPORTED;
   const int cg = C / G;
   const int nblk = (M + GN_ROWS - 1) / GN_ROWS;
-  float* partial = (float*)workspace;
-  float* stats = partial + (size_t)nblk * G * 2;
+  double* partial = (double*)workspace;
+  float* stats = (float*)(partial + (size_t)nblk * G * 2);
   hipLaunchKernelGGL(gn_partial_kernel, dim3(nblk), dim3(256), 0, s, (const bf16_t*)x, partial, M, C, ldx, G);
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(G), dim3(256), 0, s, partial, stats, nblk, G, (double)M * cg, eps);
   return gn_apply(x, stats, gamma, beta, out, M, C, G, silu, ldx, ldo, s);
