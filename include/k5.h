@@ -743,6 +743,59 @@ typedef struct k5_enhance { float weight; const unsigned char* steps; int num_st
 int k5_dit_set_enhance(k5_dit* dit, const k5_enhance* enhance /* NULL clears */);
 int k5_dit_enhance_state(k5_dit* dit, int* on, long long* launches, float* scores /* host [cap], nullable */, int cap, int* nblocks, int reset);
 
+/* The forecast cache (added under ABI 11, as the exports above were): skip the visual blocks on a fixed plan of steps and extrapolate their
+ * residual instead.  This is TaylorSeer (Liu et al. 2025) in its "lite" form: one residual across all visual blocks, not one per block.  The
+ * plan depends on the step index alone, so nothing is decided from data: no ratio table, no host round trip, every rank decides the same.
+ *
+ * THE RULE.  Per handle and per branch slot (0 conditional, 1 unconditional) the state is F0 bf16 [n][D], D1 and D2 fp32 [n][D] (allocated
+ * only up to the order in use), j = the step of the slot's last full call, have = the slot's full calls so far in this run, and g, gp = the
+ * steps between its last two full calls and between the two before; one bf16 [n][D] buffer `ori` per handle; n = the rows this rank holds.
+ *   Full call at step i: the blocks run as always; ori = the visual stream as it enters them, vis = as it leaves them.  One pass
+ *   (k5_forecast_update_bf16) computes r = bf16(vis - ori) — the bits of k5_gate_sum_bf16 with a gate of -1, MagCache's residual — and, with
+ *   g = fp32(i - j): if have >= 1 (and order >= 1) d1 = (float(r) - float(F0)) / g; if have >= 2 (and order >= 2) d2 = (d1 - D1) / g; then
+ *   F0 = r, D1 = d1, D2 = d2, gp = g, j = i, have += 1.  vis is not written: a full call's output is the plain forward's, bit for bit.
+ *   Forecast call at step i: k = i - j, m = min(order, have - 1).  The call enqueues what a call MagCache skips enqueues, and one pass
+ *   (k5_forecast_apply_bf16) stands in place of the residual add: p = float(F0); if m >= 1 p = p + c1 D1; if m >= 2 p = p + c2 D2;
+ *   vis = bf16(float(vis) + p), with c1 = fp32(k) and c2 = fp32(k (k + g) g / (g + gp)) passed by value.  That is Newton's backward form on
+ *   the stored differences (D1 is the slope half a gap behind j, D2 the second divided difference times (g + gp) / g), so order 2 reproduces a
+ *   residual that is a quadratic in the step exactly, and order 1 a linear one; with equal gaps c2 = k (k + g) / 2.  The Taylor coefficient
+ *   k k / 2 on the same differences would miss a quadratic a + b i + c i^2 by c k g.
+ *   Every difference, quotient, product and sum is one fp32 operation rounded on its own; nothing is contracted into an FMA.  With m = 0 the
+ *   forecast is k5_gate_sum_bf16 with a gate of +1 bit for bit (MagCache's order-0 re-application).
+ * The plan is full[num_steps] of 0 / 1 with full[0] = 1 (kandinsky.generation_utils.forecast_plan builds it).
+ *
+ * The two passes, standalone: vis bf16 [rows][ld] (D columns used; ld >= D, ld % 8 == 0), ori / F0 bf16 and D1 / D2 fp32 [rows][D], D % 8 == 0,
+ * every pointer 16-byte aligned.  update reads and writes its state in place and may alias nothing else; D1 / D2 beyond min(order, have)
+ * (apply: min(order, have - 1)) are neither read nor written and may be NULL; apply reads g and gp with two terms only.  K5_ERR_ARG + message,
+ * before any launch: a NULL or misaligned pointer, rows < 1, D % 8, a bad ld, g < 1 (apply: g or gp < 1 with two terms), k < 1, order outside
+ * 0..2, have < 0 (apply: < 1). */
+int k5_forecast_update_bf16(const void* vis, int ld, const void* ori, void* F0, float* D1, float* D2, int rows, int D, int g, int order, int have,
+                            void* stream);
+int k5_forecast_apply_bf16(void* vis, int ld, const void* F0, const float* D1, const float* D2, int rows, int D, int k, int g, int gp, int order,
+                           int have, void* stream);
+/* The cache on the handle.  k5_dit_set_forecast copies the plan (full is HOST memory) and clears the history; NULL clears and frees the
+ * buffers.  K5_ERR_ARG: num_steps < 1, a NULL full, full[0] == 0, order outside 0..2; K5_ERR_STATE: MagCache or its calibration is set
+ * (k5_dit_set_magcache / k5_dit_set_magcache_calibrate refuse likewise while a plan is set).
+ * k5_sample, k5_sample_cond, k5_sample_edit and k5_sample_many drive it themselves: step i is a full or a forecast call, as full[i] says,
+ * for both of its forwards (slot 0 the conditional, slot 1 the unconditional), and the history is cleared at the start of every call and
+ * sample.  On a forecast call everything inside the blocks is skipped with them (NAG, regional prompts, Enhance-A-Video, NABLA maps, fp8,
+ * LoRA), as under MagCache.  Works with stochastic sampling, editing, visual_cond, a watch, and sequence-parallel groups of either transport
+ * and every sp_mode (the state is the rank's own rows).  A plan without a 0 is off: the forwards are plain ones that keep no history, only
+ * counted as full calls, and the captured step is used; any other plan has steps of two kinds and runs eagerly.
+ * Refused by k5_sample* before anything is enqueued, with a message: K5_ERR_ARG when num_steps differs from the call's; K5_ERR_STATE with
+ * skip-layer guidance (its third branch has no slot), with a guidance plan that has guided and unguided steps or zero-init (the unconditional
+ * slot would have gaps), at k5_sample_windows with more than one window, and on a handle in a CFG pair.
+ * k5_dit_forecast_at is the cursor for callers outside k5_sample*: the next k5_dit_forward is the call (step, slot) of the plan, and that one
+ * forward consumes the cursor.  A k5_dit_forward without a cursor is a plain forward and touches no state.  A full call whose step <= j, or
+ * whose n x D differs from the slot's, starts the slot's history over.  K5_ERR_STATE without a plan; K5_ERR_ARG for a step outside
+ * 0..num_steps-1 or a slot outside {0, 1}.  The forward itself refuses with K5_ERR_STATE, before anything is enqueued: a forecast call whose
+ * slot has have == 0, whose residual has another n x D, or whose step is not after j; a handle in a CFG pair.
+ * k5_dit_forecast_state: whether a plan is set, the full and forecast calls so far, and the bytes of F0 / D1 / D2 / ori now allocated. */
+typedef struct k5_forecast { int order; const unsigned char* full; int num_steps; } k5_forecast;   /* full HOST [num_steps], copied */
+int k5_dit_set_forecast(k5_dit* dit, const k5_forecast* forecast /* NULL clears */);
+int k5_dit_forecast_at(k5_dit* dit, int step, int slot);
+int k5_dit_forecast_state(k5_dit* dit, int* on, long long* full_calls, long long* forecast_calls, long long* state_bytes, int reset);
+
 /* Stochastic sampling on the handle (added under ABI 11, as the exports above were; the rule is written at k5_euler_step_args): while a plan is
  * set, step i of k5_sample / k5_sample_cond / k5_sample_edit takes dt_down[i] as its dt and applies k5_stochastic_euler's kernel with scale[i],
  * noise_coef[i] and stream id first_stream + i; the time the forwards see is unchanged.  The noise is generated inside the update kernel: no

@@ -642,6 +642,27 @@ struct k5_dit {
     int cur() const { return prev[slot()] ^ 1; }   // the slot's buffer the call to come fills
   } cal;
 
+  // The forecast cache (k5_dit_set_forecast; the rule is written at k5_forecast_update_bf16 in include/k5.h): on the plan's forecast steps
+  // the visual blocks are skipped and their residual is extrapolated from the slot's finite differences.  Decisions depend on the step only.
+  struct Forecast {
+    bool on = false, mixed = false;                // mixed: the plan has a 0 (a plan of ones is off: k5_sample* runs plain forwards)
+    int order = 1;
+    std::vector<unsigned char> full;               // [num_steps], full[0] = 1
+    DevBuf F0[2], D1[2], D2[2], ori;               // per slot bf16 | fp32 | fp32 [n][D]; ori bf16 [n][D], one per handle
+    int j[2] = {-1, -1}, have[2] = {0, 0};         // per slot: the step of its last full call, its full calls so far in this run
+    int gap[2] = {1, 1}, gap_prev[2] = {1, 1};     // per slot: the steps between its last two full calls, and between the two before
+    size_t elems[2] = {0, 0};                      // n x D of the slot's state
+    int at_step = -1, at_slot = 0;                 // k5_dit_forecast_at's cursor (-1: none)
+    long long full_calls = 0, forecast_calls = 0;
+    hipStream_t last_stream = nullptr;
+    void clear_history() { for (int k = 0; k < 2; ++k) { j[k] = -1; have[k] = 0; gap[k] = gap_prev[k] = 1; } at_step = -1; }
+    long long state_bytes() const {
+      size_t b = ori.bytes;
+      for (int k = 0; k < 2; ++k) b += F0[k].bytes + D1[k].bytes + D2[k].bytes;
+      return (long long)b;
+    }
+  } fc;
+
   // LoRA adapters merged into the packed weights (k5_dit_add_lora): the packed bits of every touched matrix as they were before the first
   // merge, keyed by the matrix's address (a region of a fused / stacked buffer counts as its own matrix); k5_dit_clear_lora copies them back
   struct LoraBackup { DevBuf copy; size_t bytes = 0; Linear* lin = nullptr; };   // lin: the layer the matrix belongs to (its e4m3 copy follows the bf16 bits); null: an fp32 matrix
@@ -1932,6 +1953,7 @@ struct ForwardCall {
   int text_slot = -1;                                        // the text cache slot of a k5_sample* call (0 cond, 1 uncond); -1: a forward of its own
   const float* vcond = nullptr;                              // visual conditioning beside an x of in_visual_dim channels
   void* out_skip = nullptr;                                  // the forking forward: where the skip branch's velocity goes
+  int fc_step = -1, fc_slot = 0;                             // the forecast cache's cursor: this forward is call (step, slot) of the plan; -1: a plain forward
 };
 
 struct ForwardShape {   // patched frames / rows / columns, visual tokens, text rows, model width, input channels of the patch embedding
@@ -1961,6 +1983,10 @@ static int forward_refusals(const k5_dit* d, const ForwardCall& f) {
       k5_set_error("k5_dit_forward_skip: %s on the handle: the ratio table is indexed by the calls of a plain run", mode);
       return K5_ERR_STATE;
     }
+  }
+  if (f.fc_step >= 0) {   // a call of the forecast plan (what depends on the shard: ForwardRun::shard)
+    if (f.out_skip) { k5_set_error("k5_dit_forward_skip: a forecast plan is set (k5_dit_set_forecast): the skip branch has no slot"); return K5_ERR_STATE; }
+    if (d->pair.active()) { k5_set_error("a forecast plan is set (k5_dit_set_forecast) and the handle is in a CFG pair: not built"); return K5_ERR_STATE; }
   }
   if (const k5_dit::MagCalib& cl = d->cal; cl.on) {
     if (sp || d->pair.active()) { k5_set_error("MagCache calibration is a one-GPU job: the handle is in a %s", sp ? "sequence-parallel group" : "CFG pair"); return K5_ERR_STATE; }
@@ -2007,6 +2033,8 @@ struct ForwardRun : ForwardShape {
   struct { const k5_text_cond* cond; int stream; void* o; } act[1 + 1 + 8];   // stream: its index in k5_dit::streams
   CrossStreams cx; bool cx_all = false;     // cx_all: the streams hold the keys / V^T of all visual blocks ("cross_kv_batched")
   bool mag_skip = false;                    // MagCache skips this call's visual blocks
+  int fc_kind = 0;                          // the forecast cache: 0 a plain forward, 1 a full call, 2 a forecast call (the blocks are skipped)
+  bool no_blocks() const { return mag_skip || fc_kind == 2; }
   int fork_at = -1;                         // skip-layer guidance: the block whose input the skip branch starts from
   size_t vis_elems() const { return (size_t)n * D; }
 
@@ -2032,6 +2060,16 @@ struct ForwardRun : ForwardShape {
     if (mg.on && (mag_skip = mg.decide()) && mg.res_elems[mg.slot()] != vis_elems()) {
       k5_set_error("magcache: skip decided but no cached residual of this shape for the slot");
       return K5_ERR_ARG;
+    }
+    auto& fc = d->fc;   // likewise: a forecast call needs the slot's history at this shard's shape
+    if (fc.on && f.fc_step >= 0) {
+      const int k = f.fc_slot;
+      fc_kind = fc.full[f.fc_step] ? 1 : 2;
+      if (fc_kind == 2 && (fc.have[k] == 0 || fc.elems[k] != vis_elems() || f.fc_step <= fc.j[k])) {
+        k5_set_error("forecast: step %d of slot %d is a forecast call but the slot has %s", f.fc_step, k,
+                     fc.have[k] == 0 ? "no full call yet" : fc.elems[k] != vis_elems() ? "a residual of another shape" : "no full call before this step");
+        return K5_ERR_STATE;
+      }
     }
     d->enh.live = d->enh.applies(Tp, d->cfg.num_visual_blocks);
     int Lmax = ncond && ncond->text_len > L ? ncond->text_len : L;   // every stream borrows the text blocks' scratch: size it by the longest
@@ -2094,6 +2132,20 @@ struct ForwardRun : ForwardShape {
       HIPCHK(hipMemcpyAsync(mg.residual[mg.slot()].p, d->ws_vis.p, vis_elems() * 2, hipMemcpyDeviceToDevice, s));  // ori_visual_embed
       mg.n_ran++;
     }
+    auto& fc = d->fc;
+    if (fc_kind == 2) {   // the extrapolated residual in place of the blocks
+      Scope sc(d, s, "elementwise");
+      const int k = f.fc_slot;
+      K5CHK(k5_launch_forecast_apply(d->ws_vis.p, D, fc.F0[k].p, fc.D1[k].as<float>(), fc.D2[k].as<float>(), n, D, f.fc_step - fc.j[k], fc.gap[k],
+                                     fc.gap_prev[k], fc.order, fc.have[k], s));
+      fc.forecast_calls++; fc.last_stream = s;
+    } else if (fc_kind == 1) {
+      const int k = f.fc_slot;
+      K5CHK(fc.ori.ensure(vis_elems() * 2)); K5CHK(fc.F0[k].ensure(vis_elems() * 2));
+      if (fc.order >= 1) K5CHK(fc.D1[k].ensure(vis_elems() * 4));
+      if (fc.order >= 2) K5CHK(fc.D2[k].ensure(vis_elems() * 4));
+      HIPCHK(hipMemcpyAsync(fc.ori.p, d->ws_vis.p, vis_elems() * 2, hipMemcpyDeviceToDevice, s));  // the stream as it enters the blocks
+    }
     auto& cl = d->cal;
     if (cl.on) {
       DevBuf& cur = cl.res[cl.slot()][cl.cur()];
@@ -2107,11 +2159,11 @@ struct ForwardRun : ForwardShape {
   int text_streams() {
     auto& rg = d->regions;
     const int blocks = d->cfg.num_visual_blocks;
-    cx_all = !mag_skip && d->cross_kv_batched && blocks > 1 && d->cx_k.w.p;
-    if (!mag_skip) K5CHK(text_cross_kv(d, s, d->streams[0], cx_all));
+    cx_all = !no_blocks() && d->cross_kv_batched && blocks > 1 && d->cx_k.w.p;
+    if (!no_blocks()) K5CHK(text_cross_kv(d, s, d->streams[0], cx_all));
     act[0] = {&f.cond, 0, d->ws_o.p};
     cx.n = 1; cx.kv_ready = cx_all;
-    if (!mag_skip && blocks > 0) {
+    if (!no_blocks() && blocks > 0) {
       if (ncond) {
         K5CHK(d->nag.o.ensure(vis_elems() * 2));
         act[cx.n++] = {ncond, 1, d->nag.o.p};
@@ -2178,12 +2230,12 @@ struct ForwardRun : ForwardShape {
       fork_at = sk.share_prefix ? sk.k0 : 0;
       K5CHK(sk.vis.ensure(vis_elems() * 2));
     }
-    const int blocks = mag_skip ? 0 : d->cfg.num_visual_blocks;
+    const int blocks = no_blocks() ? 0 : d->cfg.num_visual_blocks;
     for (int i = 0; i < blocks; ++i) {
       if (i == fork_at) HIPCHK(hipMemcpyAsync(sk.vis.p, d->ws_vis.p, vis_elems() * 2, hipMemcpyDeviceToDevice, s));
       K5CHK(block(i, f.text_slot > 0 ? 1 : 0, false));
     }
-    if (d->enh.live && !mag_skip) d->enh.last_blocks = blocks;
+    if (d->enh.live && !no_blocks()) d->enh.last_blocks = blocks;
     return K5_OK;
   }
 
@@ -2197,6 +2249,18 @@ struct ForwardRun : ForwardShape {
         mg.res_elems[mg.slot()] = vis_elems();
       }
       mg.advance();
+    }
+    auto& fc = d->fc;
+    if (fc_kind == 1) {   // the residual and its finite differences against the slot's history; a step at or before j, or another shape, starts over
+      Scope sc(d, s, "elementwise");
+      const int k = f.fc_slot;
+      if (f.fc_step <= fc.j[k] || fc.elems[k] != vis_elems()) fc.have[k] = 0;
+      const int g = fc.have[k] ? f.fc_step - fc.j[k] : 1;
+      K5CHK(k5_launch_forecast_update(d->ws_vis.p, D, fc.ori.p, fc.F0[k].p, fc.D1[k].as<float>(), fc.D2[k].as<float>(), n, D, g, fc.order, fc.have[k], s));
+      fc.gap_prev[k] = fc.gap[k]; fc.gap[k] = g;
+      fc.j[k] = f.fc_step; fc.elems[k] = vis_elems(); fc.last_stream = s;
+      if (fc.have[k] < 3) fc.have[k]++;   // the rule reads have only up to 3 (m = min(order, have - 1))
+      fc.full_calls++;
     }
     auto& cl = d->cal;
     if (cl.on) {   // the residual MagCache would cache, and its statistics against the slot's previous one (none on the slot's first call of a run)
@@ -2449,6 +2513,7 @@ extern "C" int k5_dit_set_magcache(k5_dit* d, const double* ratio_table, int tab
                                    double retention_ratio) {
   if (!d || !d->finalized) { k5_set_error("k5_dit_set_magcache: handle not finalized"); return K5_ERR_STATE; }
   if (table_len > 0 && d->cal.on) { k5_set_error("k5_dit_set_magcache: the handle is calibrating (k5_dit_set_magcache_calibrate)"); return K5_ERR_STATE; }
+  if (table_len > 0 && d->fc.on) { k5_set_error("k5_dit_set_magcache: a forecast plan is set on the handle (k5_dit_set_forecast)"); return K5_ERR_STATE; }
   auto& mg = d->mag;
   mg.cnt = 0; mg.n_ran = mg.n_skipped = 0;
   mg.reset_acc(); mg.res_elems[0] = mg.res_elems[1] = 0;
@@ -2487,6 +2552,7 @@ extern "C" int k5_dit_set_magcache_calibrate(k5_dit* d, int num_steps, int no_cf
   auto& cl = d->cal;
   if (num_steps > 0) {
     if (d->mag.on) { k5_set_error("k5_dit_set_magcache_calibrate: MagCache is set on the handle"); return K5_ERR_STATE; }
+    if (d->fc.on) { k5_set_error("k5_dit_set_magcache_calibrate: a forecast plan is set on the handle (k5_dit_set_forecast)"); return K5_ERR_STATE; }
     if (d->comm.active()) { k5_set_error("k5_dit_set_magcache_calibrate: the handle is in a sequence-parallel group (calibration is a one-GPU job)"); return K5_ERR_STATE; }
     if (d->pair.active()) { k5_set_error("k5_dit_set_magcache_calibrate: the handle is in a CFG pair (calibration is a one-GPU job)"); return K5_ERR_STATE; }
   }
@@ -2518,10 +2584,54 @@ extern "C" int k5_dit_magcache_calibration(k5_dit* d, double* out, int cap_rows,
   return K5_OK;
 }
 
+extern "C" int k5_dit_set_forecast(k5_dit* d, const k5_forecast* p) {
+  g_err[0] = 0;
+  if (!d || !d->finalized) { k5_set_error("k5_dit_set_forecast: handle not finalized"); return K5_ERR_STATE; }
+  auto& fc = d->fc;
+  if (p) {   // every refusal before the handle is touched
+    if (p->num_steps < 1 || !p->full) { k5_set_error("k5_dit_set_forecast: full with num_steps = %d", p->num_steps); return K5_ERR_ARG; }
+    if (p->order < 0 || p->order > 2) { k5_set_error("k5_dit_set_forecast: order must be 0, 1 or 2 (got %d)", p->order); return K5_ERR_ARG; }
+    if (!p->full[0]) { k5_set_error("k5_dit_set_forecast: full[0] must be 1: the first step has nothing to extrapolate from"); return K5_ERR_ARG; }
+    if (const char* mode = magcache_mode(d)) { k5_set_error("k5_dit_set_forecast: %s on the handle", mode); return K5_ERR_STATE; }
+  }
+  if (fc.last_stream) HIPCHK(hipStreamSynchronize(fc.last_stream));   // the buffers freed below may still be read
+  fc.last_stream = nullptr;
+  for (int k = 0; k < 2; ++k) { fc.F0[k].release(); fc.D1[k].release(); fc.D2[k].release(); fc.elems[k] = 0; }
+  fc.ori.release();
+  fc.clear_history();   // (the call counts stay: k5_dit_forecast_state resets them)
+  fc.on = fc.mixed = false; fc.full.clear();
+  if (!p) return K5_OK;
+  fc.full.resize((size_t)p->num_steps);
+  for (int i = 0; i < p->num_steps; ++i) { fc.full[i] = p->full[i] ? 1 : 0; fc.mixed = fc.mixed || !p->full[i]; }
+  fc.order = p->order; fc.on = true;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_forecast_at(k5_dit* d, int step, int slot) {
+  g_err[0] = 0;
+  if (!d || !d->fc.on) { k5_set_error("k5_dit_forecast_at: no forecast plan on the handle (k5_dit_set_forecast)"); return K5_ERR_STATE; }
+  if (step < 0 || step >= (int)d->fc.full.size()) { k5_set_error("k5_dit_forecast_at: step %d is outside 0..%d", step, (int)d->fc.full.size() - 1); return K5_ERR_ARG; }
+  if (slot != 0 && slot != 1) { k5_set_error("k5_dit_forecast_at: slot must be 0 (conditional) or 1 (unconditional), got %d", slot); return K5_ERR_ARG; }
+  d->fc.at_step = step; d->fc.at_slot = slot;
+  return K5_OK;
+}
+
+extern "C" int k5_dit_forecast_state(k5_dit* d, int* on, long long* full_calls, long long* forecast_calls, long long* state_bytes, int reset) {
+  if (!d) { k5_set_error("k5_dit_forecast_state: null handle"); return K5_ERR_ARG; }
+  if (on) *on = d->fc.on ? 1 : 0;
+  if (full_calls) *full_calls = d->fc.full_calls;
+  if (forecast_calls) *forecast_calls = d->fc.forecast_calls;
+  if (state_bytes) *state_bytes = d->fc.state_bytes();
+  if (reset) d->fc.full_calls = d->fc.forecast_calls = 0;
+  return K5_OK;
+}
+
 extern "C" int k5_dit_forward(k5_dit* d, const k5_forward_args* a, void* out_velocity, void* stream) {
   g_err[0] = 0;
   if (!d || !a || !out_velocity || !a->x) return K5_ERR_ARG;
-  return forward_impl(d, ForwardCall{a, a->cond, a->time, a->x, a->x_channels, out_velocity, (hipStream_t)stream});
+  ForwardCall f{a, a->cond, a->time, a->x, a->x_channels, out_velocity, (hipStream_t)stream};
+  if (d->fc.on && d->fc.at_step >= 0) { f.fc_step = d->fc.at_step; f.fc_slot = d->fc.at_slot; d->fc.at_step = -1; }   // one forward consumes the cursor
+  return forward_impl(d, f);
 }
 
 // "sequence-parallel group" or "CFG pair": the rank group the handle is in (nullptr: none), for the refusals of what is single-rank only
@@ -2618,6 +2728,34 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
     }
     if (win) {
       k5_set_error("%s: skip-layer guidance is set (k5_dit_set_skip_guidance): a windowed step has one velocity pair per window, the skip branch is not built for it", who);
+      return K5_ERR_STATE;
+    }
+  }
+  const k5_dit::Forecast& fc = d->fc;
+  if (fc.on) {
+    if ((int)fc.full.size() != a->num_steps) {
+      k5_set_error("%s: the forecast plan has %d steps, this call %d", who, (int)fc.full.size(), a->num_steps);
+      return K5_ERR_ARG;
+    }
+    if (sg.live()) {
+      k5_set_error("%s: a forecast plan is set (k5_dit_set_forecast) and skip-layer guidance (k5_dit_set_skip_guidance): the skip branch has no slot", who);
+      return K5_ERR_STATE;
+    }
+    if (gd.on) {
+      int guided = 0, unguided = 0;
+      for (int i = 0; i < a->num_steps; ++i) (fabsf((gd.weights.empty() ? a->guidance_weight : gd.weights[i]) - 1.0f) > 1e-6f ? guided : unguided) += 1;
+      if ((guided && unguided) || gd.zero_init > 0) {
+        k5_set_error("%s: a forecast plan is set (k5_dit_set_forecast) and the guidance plan has %s: the unconditional slot would have gaps", who,
+                     gd.zero_init > 0 ? "zero-init steps" : "guided and unguided steps");
+        return K5_ERR_STATE;
+      }
+    }
+    if (win) {
+      k5_set_error("%s: a forecast plan is set (k5_dit_set_forecast): a windowed step makes nwin calls per slot, the cache holds one residual per slot", who);
+      return K5_ERR_STATE;
+    }
+    if (d->pair.active()) {
+      k5_set_error("%s: a forecast plan is set (k5_dit_set_forecast) and the handle is in a CFG pair: not built", who);
       return K5_ERR_STATE;
     }
   }
@@ -2739,6 +2877,9 @@ struct SampleRun {
     ForwardCall f{&a->fwd, cond, t1000[i], x, d->cfg.in_visual_dim, vel, s};
     if (tables) { f.tvec = tvec; f.step = step_ctr; }
     f.text_slot = slot; f.vcond = vc; f.out_skip = skip_vel;
+    // the forecast cache: step i's forwards are the plan's calls (i, slot); a plan of ones is off — plain forwards, counted as full calls
+    if (d->fc.on && d->fc.mixed) { f.fc_step = i; f.fc_slot = slot; }
+    else if (d->fc.on) d->fc.full_calls++;
     return forward_impl(d, f);
   }
 
@@ -2812,9 +2953,9 @@ struct SampleRun {
 // The handle's launch counters that a step advances from host code.  A replay of the captured step enqueues the same launches without that
 // host code, so sample_impl takes the difference over the capture and adds it per further replay.  A new counter is one more entry of `of` (and of K).
 struct ReplayCounts {
-  static constexpr int K = 5;
+  static constexpr int K = 6;
   long long per_step[K] = {};
-  static void of(k5_dit* d, long long* (&c)[K]) { c[0] = &d->nag.combines; c[1] = &d->regions.combines; c[2] = &d->skip.blocks_shared; c[3] = &d->skip.blocks_run; c[4] = &d->enh.launches; }
+  static void of(k5_dit* d, long long* (&c)[K]) { c[0] = &d->nag.combines; c[1] = &d->regions.combines; c[2] = &d->skip.blocks_shared; c[3] = &d->skip.blocks_run; c[4] = &d->enh.launches; c[5] = &d->fc.full_calls; }
   void snapshot(k5_dit* d) { long long* c[K]; of(d, c); for (int i = 0; i < K; ++i) per_step[i] = *c[i]; }
   void difference(k5_dit* d) { long long* c[K]; of(d, c); for (int i = 0; i < K; ++i) per_step[i] = *c[i] - per_step[i]; }
   void add(k5_dit* d) const { long long* c[K]; of(d, c); for (int i = 0; i < K; ++i) *c[i] += per_step[i]; }
@@ -2946,6 +3087,9 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   for (int i = first; i < N; ++i) nenh += d->enh.at(i) && a->fwd.T >= 2 ? 1 : 0;
   uniform = uniform && (nenh == 0 || nenh == N - first);
   struct EnhanceGuard { k5_dit* d; ~EnhanceGuard() { d->enh.gate = -1; } } enhance_guard{d};
+  // the forecast cache: every call and every sample starts without history; a plan with forecast steps has steps of two kinds
+  d->fc.clear_history();
+  uniform = uniform && !(d->fc.on && d->fc.mixed);
   r.pair = r.cfg_on && d->pair.active();
   if (r.pair) K5CHK(d->ws_vel_pair.ensure(2 * r.n * 2));
   else {   // one slot per window

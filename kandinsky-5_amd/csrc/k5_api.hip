@@ -560,6 +560,29 @@ int k5_scale_by_dev_bf16(void* x, int rows, int D, int ld, const float* score_de
   return ret(st, "k5_scale_by_dev_bf16");
 }
 
+int k5_forecast_update_bf16(const void* vis, int ld, const void* ori, void* F0, float* D1, float* D2, int rows, int D, int g, int order, int have,
+                            void* stream) {
+  const int st = k5_launch_forecast_update(vis, ld, ori, F0, D1, D2, rows, D, g, order, have, (hipStream_t)stream);
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_forecast_update_bf16: need 16-byte aligned non-null vis, ori, F0 (and D1 / D2 up to min(order, have)), rows > 0, D %% 8 == 0, "
+                 "ld >= D, ld %% 8 == 0, g >= 1, order in 0..2, have >= 0 (rows %d, D %d, ld %d, g %d, order %d, have %d)", rows, D, ld, g, order, have);
+    return st;
+  }
+  return ret(st, "k5_forecast_update_bf16");
+}
+
+int k5_forecast_apply_bf16(void* vis, int ld, const void* F0, const float* D1, const float* D2, int rows, int D, int k, int g, int gp, int order,
+                           int have, void* stream) {
+  const int st = k5_launch_forecast_apply(vis, ld, F0, D1, D2, rows, D, k, g, gp, order, have, (hipStream_t)stream);
+  if (st == K5_ERR_ARG) {
+    k5_set_error("k5_forecast_apply_bf16: need 16-byte aligned non-null vis, F0 (and D1 / D2 up to min(order, have - 1)), rows > 0, D %% 8 == 0, "
+                 "ld >= D, ld %% 8 == 0, k >= 1, g and gp >= 1 at two terms, order in 0..2, have >= 1 (rows %d, D %d, ld %d, k %d, g %d, gp %d, order %d, "
+                 "have %d)", rows, D, ld, k, g, gp, order, have);
+    return st;
+  }
+  return ret(st, "k5_forecast_apply_bf16");
+}
+
 int k5_region_combine_bf16(const void* z0, const void* zr, long long zr_stride, int R, const float* w, int ldw, void* out, int rows, int D,
                            int ld, void* stream) {
   const int st = k5_launch_region_combine(z0, zr, zr_stride, R, w, ldw, out, rows, D, ld, (hipStream_t)stream);

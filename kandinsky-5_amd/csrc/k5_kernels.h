@@ -243,6 +243,17 @@ int k5_launch_enhance_scores(const void* Q, const void* K, int ldq, int ldk, int
 // x [rows][ld] bf16 (D columns used) *= *score_dev in place: bf16(float(x) * s), 16 bytes per lane, grid-stride; a workgroup that reads s == 1
 // touches nothing.  Refusals as k5_launch_nag_combine's (without its D limit).
 int k5_launch_scale_by_dev(void* x, int rows, int D, int ld, const float* score_dev, hipStream_t stream);
+// The forecast cache's two passes (forecast.hip; the rule is written at k5_forecast_update_bf16 in include/k5.h).  vis bf16 [rows][ld] (D columns
+// used), ori / F0 bf16 and D1 / D2 fp32 [rows][D]; 16 bytes per lane, grid-stride, no atomics.
+// update: F0 = bf16(vis - ori) and, with level = min(order, have), level >= 1: D1 = (F0' - F0) / g, level >= 2: D2 = (D1' - D1) / g, in place;
+// vis and ori are only read and alias nothing.  apply: vis = bf16(vis + F0 + k D1 + c2 D2) with m = min(order, have - 1) terms and
+// c2 = k (k + g) g / (g + gp), g and gp the slot's last two gaps between full calls (read at m = 2 only).
+// K5_ERR_ARG before any launch: a NULL or not 16-byte aligned pointer among those the level / m reads or writes (the others may be NULL),
+// rows < 1, D % 8, ld < D, ld % 8, order outside 0..2, g < 1 (apply: g or gp < 1 at m = 2), k < 1, have < 0 (update) or < 1 (apply).
+int k5_launch_forecast_update(const void* vis, int ld, const void* ori, void* F0, float* D1, float* D2, int rows, int D, int g, int order, int have,
+                              hipStream_t stream);
+int k5_launch_forecast_apply(void* vis, int ld, const void* F0, const float* D1, const float* D2, int rows, int D, int k, int g, int gp, int order,
+                             int have, hipStream_t stream);
 // fp32 -> bf16 cast, bf16 -> fp32
 int k5_launch_cast_f32_bf16(const float* x, void* out, int64_t n, hipStream_t stream);
 // weight packing: src [rows][cols] (K5_F32 / K5_BF16 / K5_F16, device) -> dst [rows][ld] bf16 (RNE) or fp32, pad columns zeroed

@@ -124,6 +124,11 @@ class Enhance(C.Structure):
     _fields_ = [("weight", C.c_float), ("steps", C.POINTER(C.c_ubyte)), ("num_steps", C.c_int)]
 
 
+class Forecast(C.Structure):
+    """k5_forecast: the plan of k5_dit_set_forecast (full is HOST memory, copied by the call)."""
+    _fields_ = [("order", C.c_int), ("full", C.POINTER(C.c_ubyte)), ("num_steps", C.c_int)]
+
+
 class Stochastic(C.Structure):
     """k5_stochastic: the plan of k5_dit_set_stochastic (the three tables are HOST memory, copied by the call)."""
     _fields_ = [("num_steps", C.c_int), ("dt_down", C.POINTER(C.c_float)), ("scale", C.POINTER(C.c_float)),
@@ -258,6 +263,11 @@ SYMBOLS = {
     "k5_scale_by_dev_bf16": (_I, [_P, _I, _I, _I, _P, _P]),
     "k5_dit_set_enhance": (_I, [_P, C.POINTER(Enhance)]),
     "k5_dit_enhance_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), C.POINTER(C.c_float), _I, C.POINTER(_I), _I]),
+    "k5_forecast_update_bf16": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "k5_forecast_apply_bf16": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "k5_dit_set_forecast": (_I, [_P, C.POINTER(Forecast)]),
+    "k5_dit_forecast_at": (_I, [_P, _I, _I]),
+    "k5_dit_forecast_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _I]),
     "k5_region_combine_bf16": (_I, [_P, _P, C.c_longlong, _I, _P, _I, _P, _I, _I, _I, _P]),
     "k5_region_weights_f32": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "k5_dit_set_regions": (_I, [_P, C.POINTER(TextCond), _I, _P, _I, _I, _I, _F]),

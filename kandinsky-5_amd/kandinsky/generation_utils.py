@@ -180,6 +180,78 @@ def _skip_for_run(model, sigmas, first, slg_blocks, slg_scale, slg_interval, slg
     return blocks, scale, mode, mask
 
 
+def forecast_plan(num_steps, interval, warmup=None, tail=1, order=1):
+    """The forecast cache's plan: full[num_steps] of 0 / 1, 1 = the step runs its visual blocks, 0 = their residual is extrapolated
+    (`DiffusionTransformer3D.set_forecast`).  full[i] = 1 if i < warmup, or i >= num_steps - tail, or (i - warmup) % interval == 0.
+    `warmup` None = max(order + 1, int(0.2 * num_steps)), MagCache's retention share and enough full steps for the differences of `order`.
+    warmup >= 1, tail >= 0, interval >= 1.  interval == 1, or a plan without a 0, means off.  Host only, like `guidance_plan`."""
+    num_steps, interval, tail, order = int(num_steps), int(interval), int(tail), int(order)
+    if num_steps < 1:
+        raise ValueError(f"forecast_plan: num_steps must be >= 1 (got {num_steps})")
+    if interval < 1:
+        raise ValueError(f"forecast_interval must be >= 1 (got {interval})")
+    if not 0 <= order <= 2:
+        raise ValueError(f"forecast_order must be 0, 1 or 2 (got {order})")
+    warmup = max(order + 1, int(0.2 * num_steps)) if warmup is None else int(warmup)
+    if warmup < 1:
+        raise ValueError(f"forecast_warmup must be >= 1 (got {warmup}): the first step has nothing to extrapolate from")
+    if tail < 0:
+        raise ValueError(f"forecast_tail must be >= 0 (got {tail})")
+    return [1 if i < warmup or i >= num_steps - tail or (i - warmup) % interval == 0 else 0 for i in range(num_steps)]
+
+
+def _forecast_for_run(model, steps_run, forecast_interval, forecast_order, forecast_warmup, forecast_tail, guide, skip, windowed):
+    """`generate`'s forecast keywords -> None when they are off (no interval, interval 1, or a plan without a 0: nothing changes), otherwise
+    (order, full) over the `steps_run` steps the run executes (an edit run: those after its cut) with the ValueErrors of what the engine
+    refuses.  `guide`, `skip`: the run's checked guidance plan and skip set; `windowed`: more than one context window."""
+    if forecast_interval is None:
+        return None
+    order = forecast_order
+    if isinstance(order, bool) or not isinstance(order, int) or not 0 <= order <= 2:
+        raise ValueError(f"forecast_order must be 0, 1 or 2 (got {order!r})")
+    full = forecast_plan(steps_run, forecast_interval, forecast_warmup, forecast_tail, order)
+    if all(full):
+        return None
+    if _has_magcache(model):
+        raise ValueError("forecast_interval with MagCache (or its calibration) on the model: one cache at a time")
+    if skip is not None:
+        raise ValueError("forecast_interval together with slg_blocks is not supported: the skip branch has no slot in the cache")
+    if guide is not None and (guide[2] > 0 or (guide[0] is not None and len({_is_guided(w) for w in guide[0]}) > 1)):
+        raise ValueError("forecast_interval together with a guidance plan that has guided and unguided steps (guidance_schedule / "
+                         "guidance_interval) or cfg_zero_init is not supported: the unconditional slot would have gaps")
+    if windowed:
+        raise ValueError("forecast_interval together with context windows (context_frames) is not supported: a windowed step makes a call "
+                         "per window, the cache holds one residual per branch")
+    if _is_cfg_pair(model):
+        raise ValueError("forecast_interval on a CFG pair is not supported")
+    if not (hasattr(model, "set_forecast") and hasattr(model, "forecast_at")):
+        raise ValueError("forecast_interval needs a model with set_forecast and forecast_at (the engine-backed DiffusionTransformer3D has "
+                         "them): the cache lives inside its forward, a wrapped callable without them cannot take it")
+    return order, full
+
+
+@contextlib.contextmanager
+def _forecast_for_call(model, forecast):
+    """The plan on the model for exactly one run; what was there before comes back, also on an exception.  forecast None: nothing is touched.
+    The engine-backed model does it itself (`setting_for_call`); a wrapper that hands `set_forecast`, `clear_forecast` and `_forecast` on to
+    one is served through those."""
+    if forecast is None:
+        yield
+    elif hasattr(model, "setting_for_call"):
+        with model.setting_for_call("forecast", forecast):
+            yield
+    else:
+        before = getattr(model, "_forecast", None)
+        try:
+            model.set_forecast(*forecast)
+            yield
+        finally:
+            if before is not None:
+                model.set_forecast(*before)
+            else:
+                model.clear_forecast()
+
+
 def enhance_plan(sigmas, interval=None):
     """The per-step mask of Enhance-A-Video over `sigmas` (num_steps + 1 values): a list of num_steps 0 / 1, 1 on the steps with
     lo <= sigmas[i] <= hi of `interval` = (lo, hi); None = every step.  Host only, like `skip_plan`."""
@@ -511,7 +583,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
              region_text_embeds=None, region_text_rope_pos=None, region_masks=None, region_base_weight=0.0,
              guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0, cfg_rescale=0.0,
              slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0, sde_interval=None, sde_seed=None,
-             enhance_weight=None, enhance_interval=None):
+             enhance_weight=None, enhance_interval=None, forecast_interval=None, forecast_order=1, forecast_warmup=None, forecast_tail=1):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -595,7 +667,15 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     inert.  The engine-backed model runs it inside its loop (set for this call and removed afterwards), a model that hands `set_enhance` on
     step by step from the per-step loop: the same bits.  ValueError, before anything runs: a bad weight or interval; a rank of a
     sequence-parallel group; more than 64 latent frames per forward; a model without `set_enhance`.  No checkpoint was at hand, visual
-    quality is not claimed."""
+    quality is not claimed.
+    `forecast_interval`, `forecast_order`, `forecast_warmup`, `forecast_tail` (optional, extension): the forecast cache (TaylorSeer "lite",
+    Liu et al. 2025).  After `forecast_warmup` full steps only every `forecast_interval`-th step (and the last `forecast_tail`) runs the visual
+    blocks; the others add the blocks' residual extrapolated from the finite differences of the full steps, up to `forecast_order` (0, 1, 2),
+    per CFG branch (`forecast_plan`, `DiffusionTransformer3D.set_forecast`).  The plan depends on the step index alone: no ratio table, and
+    it works with `strength` < 1 (the plan covers the steps that run), `eta`, NAG, regions and sequence-parallel groups.  None or 1 (default)
+    is off and nothing changes.  ValueError, before anything runs: MagCache on the model, `slg_blocks`, a guidance plan with steps of
+    different kinds or `cfg_zero_init`, more than one context window, a CFG pair, a model without `set_forecast` / `forecast_at`.  No
+    checkpoint was at hand, visual quality is not claimed."""
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
         raise ValueError(f"shape[0] = {shape[0]} frames do not divide into batch={batch} samples")
@@ -631,9 +711,10 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         sto = _stochastic_for_run(model, sigmas, first, eta, s_noise, sde_interval, seed if sde_seed is None else sde_seed, windowed, preview_every)
     if wants_enhance:
         enhance = _enhance_for_run(model, sigmas, first, enhance_weight, enhance_interval, plan[0] if windowed else shape[0] // batch)
+    forecast = _forecast_for_run(model, steps_run, forecast_interval, forecast_order, forecast_warmup, forecast_tail, guide, skip, windowed)
     if region_text_embeds is not None and windowed:
         raise ValueError("region_text_embeds together with context windows is not supported: the masks cover the clip, a window sees a slice")
-    with _skip_for_call(model, skip), _enhance_for_call(model, enhance), _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
+    with _skip_for_call(model, skip), _forecast_for_call(model, forecast), _enhance_for_call(model, enhance), _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
             _regions_for_call(model, region_text_embeds, region_text_rope_pos, region_masks, region_base_weight):
         # one hook for the whole call (it owns the bar): the samples of a batch share it
         watch = _StepWatch(model, callback, preview_every, preview_factors, preview_x0, progress, batch * steps_run, shape[-1])
@@ -648,19 +729,20 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
                    null_text_rope_pos, guidance_weight, scheduler_scale, conf, watch)
             what = (context, visual_cond, visual_cond_mask, init_latent, strength, keep_mask)
             if batch > 1:
-                return _generate_batch(*run, batch, *what, guide=guide, skip=skip, sto=sto, enhance=enhance)
-            return _generate_one(*run, plan, *what, guide=guide, skip=skip, sto=sto, enhance=enhance)
+                return _generate_batch(*run, batch, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast)
+            return _generate_one(*run, plan, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast)
         finally:
             watch.close()
 
 
 def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                   guidance_weight, scheduler_scale, conf, watch, plan, context, visual_cond, visual_cond_mask, init_latent, strength,
-                  keep_mask, guide=None, skip=None, sto=None, enhance=None):
+                  keep_mask, guide=None, skip=None, sto=None, enhance=None, forecast=None):
     """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch`, the checked `plan` of
     `_context_plan`, the checked guidance plan `guide` of `_guidance_for_run`, the checked skip set `skip` of `_skip_for_run` (installed on
     the model by `generate`), the checked stochastic plan `sto` of `_stochastic_for_run` and the checked Enhance-A-Video set `enhance` of
-    `_enhance_for_run` (`generate` puts back what the model held); returns the latent."""
+    `_enhance_for_run` (`generate` puts back what the model held) and the checked forecast plan `forecast` of `_forecast_for_run` (installed
+    on the model by `generate`); returns the latent."""
     context_text = context[2]
     if plan is not None:
         F, starts, weights = plan
@@ -710,14 +792,16 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
 
     # The per-step loop.  Each step takes (v_cond, v_uncond, v_skip) from one of three sources (a windowed run: its per-window buffers), makes
     # the one update call and calls the hook.
-    def forward(x, te, tp, t1000):
+    def forward(x, te, tp, t1000, slot=0):
+        if forecast is not None:   # this forward is call (step, slot) of the plan, as the engine's loop makes it
+            model.forecast_at(step_now, slot)
         return model(x, te["text_embeds"], te["pooled_embed"], t1000, visual_rope_pos, tp, scale_factor=conf.metrics.scale_factor,
                      sparse_params=sparse_params)
 
     def plain_velocities(t1000, guided):   # cond, then uncond
         x = _model_input(model, img, cond_in)
         v = forward(x, text_embeds, text_rope_pos, t1000)
-        u = forward(x, null_text_embeds, null_text_rope_pos, t1000) if guided else None
+        u = forward(x, null_text_embeds, null_text_rope_pos, t1000, 1) if guided else None
         return v.contiguous(), None if u is None else u.contiguous(), None
 
     def skip_velocities(t1000, guided):   # cond + skip in one forking forward, then uncond: the engine's order
@@ -753,6 +837,9 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         ubuf = torch.empty_like(vbuf) if cfg_on else None
 
     n = len(timesteps) - 1
+    step_now = 0
+    if forecast is not None and hasattr(model, "set_forecast"):
+        model.set_forecast(*forecast)   # every run starts without history, as every k5_sample* call does
     km = None if edit is None else edit[2]
     keep = {} if km is None else dict(source=edit[0], noise=edit[1], keep_mask=km)
     if edit is not None:
@@ -764,6 +851,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         w_at = guidance_weight if g_weights is None else g_weights[i]
         kind = "zero" if i < g_zero_init else "guided" if (cfg_on if guide is None else _is_guided(w_at)) else "unguided"
         skip_at = kind != "zero" and skip is not None and bool(skip[3][i])
+        step_now = i
         wants_preview = watch.active and watch.preview_at(i, n)
         _enhance_at(model, enhance, i)
         t1000 = torch.tensor([timestep]) * 1000
@@ -799,7 +887,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
 
 def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                     guidance_weight, scheduler_scale, conf, watch, batch, context, visual_cond, visual_cond_mask, init_latent, strength,
-                    keep_mask, guide=None, skip=None, sto=None, enhance=None):
+                    keep_mask, guide=None, skip=None, sto=None, enhance=None, forecast=None):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
     T = img.shape[0] // batch
     tes, nes = split_per_sample(text_embeds, batch, "text_embeds"), split_per_sample(null_text_embeds, batch, "null_text_embeds")
@@ -832,6 +920,7 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         watch.sample = b
         img[rows] = _generate_one(model, device, img[rows].clone(), num_steps, tes[b], nes[b], visual_rope_pos, tps[b], nps[b], guidance_weight,
                                   scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide, skip=skip, enhance=enhance,
+                                  forecast=forecast,
                                   sto=None if sto is None else (*sto[:3], (sto[3] + b) & (2 ** 64 - 1), sto[4]))   # a seed per sample
     return img
 
@@ -876,7 +965,8 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                     nag_scale=None, nag_tau=2.5, nag_alpha=0.25, region_text_embeds=None, region_text_rope_pos=None, region_masks=None,
                     region_base_weight=0.0, guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0,
                     cfg_rescale=0.0, slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0,
-                    sde_interval=None, sde_seed=None, enhance_weight=None, enhance_interval=None):
+                    sde_interval=None, sde_seed=None, enhance_weight=None, enhance_interval=None, forecast_interval=None, forecast_order=1,
+                    forecast_warmup=None, forecast_tail=1):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -901,8 +991,15 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     `slg_blocks`, `slg_scale`, `slg_interval`, `slg_mode` (optional, extension): skip-layer guidance, passed to `generate` (see there).  Off by
     default.
     `eta`, `s_noise`, `sde_interval`, `sde_seed` (optional, extension): stochastic sampling, passed to `generate` (see there).  Off by default.
-    `enhance_weight`, `enhance_interval` (optional, extension): Enhance-A-Video, passed to `generate` (see there).  None (default) is off."""
+    `enhance_weight`, `enhance_interval` (optional, extension): Enhance-A-Video, passed to `generate` (see there).  None (default) is off.
+    `forecast_interval`, `forecast_order`, `forecast_warmup`, `forecast_tail` (optional, extension): the forecast cache, passed to `generate`
+    (see there).  None or 1 (default) is off."""
     batch, frames, height, width, channels = shape
+    forecast_kw = {}
+    if forecast_interval is not None:   # before any model runs: the numbers (what depends on the run is checked by `generate`)
+        forecast_plan(num_steps, forecast_interval, forecast_warmup, forecast_tail, forecast_order)
+        forecast_kw = dict(forecast_interval=forecast_interval, forecast_order=forecast_order, forecast_warmup=forecast_warmup,
+                           forecast_tail=forecast_tail)
     enhance_kw = {}
     if enhance_weight is not None or enhance_interval is not None:   # before any model runs: the numbers and what the handle's state refuses
         fwd_frames = frames if context_frames is None else min(int(frames), int(context_frames))
@@ -1029,7 +1126,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                           text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
                           progress=progress, batch=batch, callback=callback, preview_every=preview_every,
                           preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw, **guide_kw, **skip_kw, **sto_kw,
-                          **enhance_kw)
+                          **enhance_kw, **forecast_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

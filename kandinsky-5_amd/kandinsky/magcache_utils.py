@@ -69,7 +69,11 @@ def set_magcache_params(dit, mag_ratios, num_steps, no_cfg):
     dit.retention_ratio = 0.2
     dit.mag_ratios = ratio_table(mag_ratios, num_steps)
     dit.no_cfg = no_cfg
-    _apply(dit)
+    try:
+        _apply(dit)
+    except Exception:   # refused by the engine (a forecast plan is set, the handle is calibrating): the model carries no table
+        dit.mag_ratios = None
+        raise
 
 
 def disable_magcache(dit):

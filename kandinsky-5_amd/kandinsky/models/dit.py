@@ -189,6 +189,18 @@ def check_enhance_args(weight, steps):
     return weight, steps
 
 
+def check_forecast_args(order, full):
+    """The ValueErrors of `set_forecast`; returns (order as an int, full as a list of 0 / 1)."""
+    if isinstance(order, bool) or not isinstance(order, int) or not 0 <= order <= 2:
+        raise ValueError(f"forecast: order must be 0, 1 or 2 (got {order!r})")
+    full = [1 if bool(v) else 0 for v in full]
+    if not full:
+        raise ValueError("forecast: full must hold one 0 / 1 per step")
+    if not full[0]:
+        raise ValueError("forecast: full[0] must be 1: the first step has nothing to extrapolate from")
+    return order, full
+
+
 def check_stochastic_args(dt_down, scale, noise_coef, seed, first_stream=0):
     """The ValueErrors of `set_stochastic`; returns (dt_down, scale, noise_coef as lists of floats, seed as a 64-bit and first_stream as a
     32-bit unsigned int)."""
@@ -302,6 +314,7 @@ _SETTINGS = {
     "skip_guidance": ("_skip",     "k5_dit_set_skip_guidance", (None,)),
     "stochastic":    ("_stochastic", "k5_dit_set_stochastic",  (None,)),
     "enhance":       ("_enhance",  "k5_dit_set_enhance",       (None,)),
+    "forecast":      ("_forecast", "k5_dit_set_forecast",      (None,)),
 }
 
 
@@ -360,6 +373,7 @@ class DiffusionTransformer3D(nn.Module):
         self._skip = None            # the set of set_skip_guidance (blocks, scale, mode, steps | None): likewise
         self._stochastic = None      # the plan of set_stochastic (dt_down, scale, noise_coef, seed, first_stream): likewise
         self._enhance = None         # (weight, steps | None) of set_enhance: likewise
+        self._forecast = None        # (order, full) of set_forecast: likewise
         self._guidance = None        # the plan of set_guidance (weights list | None, zero_star, zero_init_steps, rescale): likewise
         self._borrowed = {}          # setting name -> what the live handle borrows from the stored value (structs, device copies, ctypes arrays)
 
@@ -531,6 +545,9 @@ class DiffusionTransformer3D(nn.Module):
         """Reference signature dit.py:155-165.  x (T,H,W,C_in) ; returns velocity (T,H,W,out_visual_dim) bf16."""
         a, out, keep = self._forward_prologue("forward", x, (), text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos, scale_factor,
                                               sparse_params)
+        cursor, self._forecast_cursor = getattr(self, "_forecast_cursor", None), None
+        if cursor is not None:       # a `forecast_at` from before the engine was built
+            self.forecast_at(*cursor)
         return self._call("k5_dit_forward", out, C.byref(a), out.data_ptr())
 
     def _forward_prologue(self, who, x, lead, text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos, scale_factor, sparse_params):
@@ -678,7 +695,7 @@ class DiffusionTransformer3D(nn.Module):
 
     @contextlib.contextmanager
     def setting_for_call(self, name, args):
-        """Context: setting `name` ("watch", "nag", "regions", "guidance", "skip_guidance", "stochastic", "enhance") as `set_<name>(*args)` makes it, for one call; what was
+        """Context: setting `name` ("watch", "nag", "regions", "guidance", "skip_guidance", "stochastic", "enhance", "forecast") as `set_<name>(*args)` makes it, for one call; what was
         stored before is installed again afterwards (the stored object itself, not a copy) or the setting is cleared, also on an exception.
         args None: nothing is touched."""
         if args is None:
@@ -903,6 +920,46 @@ class DiffusionTransformer3D(nn.Module):
             E.check(E.lib().k5_dit_enhance_state(self._handle, C.byref(on), C.byref(n), buf, cap, C.byref(nb), int(bool(reset))),
                     "k5_dit_enhance_state")
         return bool(on.value), n.value, [float(v) for v in buf[:min(nb.value, cap)]]
+
+    # ---------------------------------------------------------------- the forecast cache: skip the visual blocks on a fixed plan of steps
+    def set_forecast(self, order, full):
+        """The forecast cache (k5_dit_set_forecast; TaylorSeer "lite", Liu et al. 2025).  `full`: one 0 / 1 per step of the calls to come
+        (`generation_utils.forecast_plan` builds it), full[0] = 1.  A step with 1 runs its forwards as always and keeps finite differences of
+        the residual across the visual blocks, per branch (conditional / unconditional), up to `order` (0, 1 or 2); a step with 0 skips the
+        blocks and adds the residual extrapolated to that step.  `sample` / `sample_many` drive it themselves; `forecast_at` is the cursor for
+        forwards made one at a time.  A plan without a 0 is off.  Refused, before anything runs: MagCache or its calibration on the model
+        (either order); by `sample`: a plan of another length than its steps, skip-layer guidance, a guidance plan with steps of different
+        kinds or zero-init, `windows`, a CFG pair.  Memory per branch: n x D x (2 + 4 order) bytes, plus n x D x 2 once.
+        No checkpoint was at hand when this was built: the rule is the published one, visual quality is not claimed."""
+        return self._put("forecast", check_forecast_args(order, full))
+
+    def _marshal_forecast(self, plan):
+        order, full = plan
+        p = E.Forecast()
+        arr = (C.c_ubyte * len(full))(*full)                  # copied by the call
+        p.order, p.full, p.num_steps = order, C.cast(arr, C.POINTER(C.c_ubyte)), len(full)
+        return (C.byref(p),), arr
+
+    def clear_forecast(self):
+        """Remove the plan and free its buffers: a forward enqueues exactly what it did before `set_forecast`."""
+        return self._clear("forecast")
+
+    def forecast_at(self, step, slot=0):
+        """The next `forward` is call (`step`, `slot`) of the plan (k5_dit_forecast_at; slot 0 conditional, 1 unconditional); that one forward
+        consumes the cursor.  A forward without it is a plain forward and touches no state."""
+        if self._forecast is None:
+            raise ValueError("forecast_at: no forecast plan (set_forecast)")
+        if self._handle is None:     # no engine yet: `forward` builds it and then sets the cursor
+            self._forecast_cursor = (int(step), int(slot))
+        else:
+            E.check(E.lib().k5_dit_forecast_at(self._handle, int(step), int(slot)), "k5_dit_forecast_at")
+        return self
+
+    def forecast_state(self, reset=False):
+        """(on, full_calls, forecast_calls, state_bytes): whether a plan is set, how many forwards ran their blocks / extrapolated under one,
+        and the bytes the history holds now (k5_dit_forecast_state).  `reset` zeroes the counts afterwards."""
+        on, *counts = self._state("k5_dit_forecast_state", (C.c_int,) + (C.c_longlong,) * 3, int(bool(reset)))
+        return (bool(on), *counts)
 
     @torch.no_grad()
     def forward_skip(self, x, text_embed, pooled_text_embed, time, visual_rope_pos, text_rope_pos,

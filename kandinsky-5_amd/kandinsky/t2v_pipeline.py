@@ -96,7 +96,8 @@ class Kandinsky5T2VPipeline:
                  nag_scale: float = None, nag_tau: float = 2.5, nag_alpha: float = 0.25, regions=None, region_base_weight: float = 0.0,
                  guidance_schedule=None, guidance_interval=None, cfg_zero_star: bool = False, cfg_zero_init: int = 0, cfg_rescale: float = 0.0,
                  slg_blocks=None, slg_scale: float = 0.0, slg_interval=None, slg_mode: str = "block", eta: float = 0.0, s_noise: float = 1.0,
-                 sde_interval=None, sde_seed: int = None, enhance_weight: float = None, enhance_interval=None):
+                 sde_interval=None, sde_seed: int = None, enhance_weight: float = None, enhance_interval=None,
+                 forecast_interval: int = None, forecast_order: int = 1, forecast_warmup: int = None, forecast_tail: int = 1):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -148,6 +149,10 @@ class Kandinsky5T2VPipeline:
         group, not with more than 64 latent frames per forward.  No checkpoint was at hand when this was written: visual quality is not
         claimed."""
         ctx = {}
+        forecast_kw = {}
+        if forecast_interval is not None:   # `generate` documents it; None or 1 is off
+            forecast_kw = dict(forecast_interval=forecast_interval, forecast_order=forecast_order, forecast_warmup=forecast_warmup,
+                               forecast_tail=forecast_tail)
         enhance_kw = {}
         if enhance_weight is not None or enhance_interval is not None:
             from .generation_utils import _enhance_for_run, enhance_plan
@@ -240,6 +245,6 @@ class Kandinsky5T2VPipeline:
                                  text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload,
                                  image=image, video=video, strength=strength, mask=mask, callback=callback,
                                  preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw, **guide_kw, **skip_kw, **sto_kw,
-                                 **enhance_kw)
+                                 **enhance_kw, **forecast_kw)
         torch.cuda.empty_cache()
         return self._save(images, time_length, save_path) if self.local_dit_rank == 0 else None

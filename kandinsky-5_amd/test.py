@@ -110,7 +110,30 @@ def build_parser():
                         "W >= 0, 0 is a valid weight (commonly 2 to 5 — not tuned on these checkpoints)")
     p.add_argument("--enhance_interval", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("LO", "HI"),
                    help="with --enhance_weight: only on the steps whose sigma lies in [LO, HI] (default every step)")
+    p.add_argument("--forecast_interval", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="forecast cache: after the warm-up only every N-th step runs the visual blocks, the others extrapolate their residual "
+                        "(1 is off)")
+    p.add_argument("--forecast_order", type=int, choices=(0, 1, 2), default=argparse.SUPPRESS, metavar="M",
+                   help="with --forecast_interval: order of the extrapolation, 0, 1 or 2 (default 1)")
+    p.add_argument("--forecast_warmup", type=int, default=argparse.SUPPRESS, metavar="W",
+                   help="with --forecast_interval: full steps at the start (default max(order + 1, a fifth of the steps))")
+    p.add_argument("--forecast_tail", type=int, default=argparse.SUPPRESS, metavar="L",
+                   help="with --forecast_interval: full steps at the end (default 1)")
     return p
+
+
+def forecast_keywords(args):
+    """--forecast_interval / --forecast_order / --forecast_warmup / --forecast_tail -> the pipeline's keywords"""
+    rest = [k for k in ("forecast_order", "forecast_warmup", "forecast_tail") if hasattr(args, k)]
+    if not hasattr(args, "forecast_interval"):
+        if rest:
+            raise ValueError(f"--{rest[0]} needs --forecast_interval")
+        return {}
+    if args.forecast_interval < 1:
+        raise ValueError(f"--forecast_interval must be >= 1 (got {args.forecast_interval})")
+    if getattr(args, "forecast_warmup", 1) < 1 or getattr(args, "forecast_tail", 0) < 0:
+        raise ValueError("--forecast_warmup must be >= 1 and --forecast_tail >= 0")
+    return {"forecast_interval": args.forecast_interval, **{k: getattr(args, k) for k in rest}}
 
 
 def enhance_keywords(args):
@@ -307,6 +330,7 @@ def main(argv=None):
     skip_kw = skip_keywords(args)
     sto_kw = stochastic_keywords(args)
     enhance_kw = enhance_keywords(args)
+    forecast_kw = forecast_keywords(args)
     from kandinsky import get_T2V_pipeline
     pipe = get_T2V_pipeline(device_map={"dit": "cuda:0", "vae": "cuda:0", "text_embedder": "cuda:0"}, conf_path=args.config,
                             offload=args.offload, magcache=args.magcache and not args.calibrate_magcache,
@@ -347,6 +371,7 @@ def main(argv=None):
     edit_kw.update(skip_kw)
     edit_kw.update(sto_kw)
     edit_kw.update(enhance_kw)
+    edit_kw.update(forecast_kw)
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
