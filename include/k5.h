@@ -371,6 +371,51 @@ typedef struct k5_euler_step_args {
   uint32_t stream_id;
 } k5_euler_step_args;
 int k5_euler_step(const k5_euler_step_args* args, void* stream);
+/* FlowEdit (added under ABI 11, as the exports above were; Kulikov et al. 2024, "FlowEdit: Inversion-Free Text-Based Editing Using Pre-Trained
+ * Flow Models", Algorithm 1 with n_avg = 1).  x_src is the clean source latent, z_fe starts as x_src.  With N steps,
+ * first = edit_first_step(N, strength) and R = refine, steps first <= i < N - R are FlowEdit steps and steps N - R <= i < N plain steps.
+ * A FlowEdit step i: s = sigmas[i], dt = sigmas[i + 1] - sigmas[i], z = k5_noise_normal_f32(seed, stream_id = i).  Per element, every operation
+ * rounded on its own (nothing contracted):
+ *   zs   = rn(rn((1 - s) x_src) + rn(s z))                                       (k5_edit_renoise's bits with z as the noise)
+ *   zt   = rn(zs + rn(z_fe - x_src))                                             (this order: z_fe == x_src gives zt == zs exactly)
+ *   v_s  = w_src != 1 ? bf16(u_s + bf16(w_src bf16(c_s - u_s))) : c_s            (the CFG combine as k5_euler_step forms it)
+ *   v_t  = likewise from c_t, u_t, w_tar
+ *   d    = bf16(rn(v_t - v_s)),  e = bf16(rn(dt d))
+ *   z_fe = m == 1 ? z_fe : m == 0 ? rn(z_fe + e) : rn(z_fe + rn(rn(1 - m) e))    (m = keep_mask[cell], 0 without a mask)
+ * c_s, u_s: the forwards on zs with the source and the negative prompt at time 1000 s; c_t, u_t: those on zt with the target and the negative
+ * prompt; on the stream in this order, a forward whose weight is 1 is not run.  Refine: the first plain step forms zt at sigmas[N - R] with
+ * stream id N - R as above, steps N - R .. N - 1 are k5_euler_step steps on that latent with the target prompt and w_tar, and that latent is
+ * the result; with R = 0 the result is z_fe.
+ * k5_flowedit_step is one pass over the latent that finishes step i (the last five lines, when the velocities are given: c_src and c_tar
+ * both or neither) and prepares step i + 1 (the first two, when `prepare` != 0: sigma_next is that step's s, stream_id its stream, zs / zt
+ * receive its inputs and are formed from the z_fe just written).  Without velocities the launch only prepares: the first launch of a run.
+ * Every pointer is device memory, 4-byte aligned; z_fe, zs and zt must not overlap each other or an input.  znoise (fp32 [cells * C], NULL =
+ * the generator's normals) replaces z.  A u_* at weight 1 and, in a launch that only prepares, the velocities and the mask are not read.
+ * K5_ERR_ARG with a message that names the condition, nothing launched: a NULL args, z_fe or x_src; cells or C < 1; c_src without c_tar or the
+ * reverse; neither velocities nor prepare; w_src != 1 without u_src, w_tar != 1 without u_tar; prepare without zs and zt; a pointer that is
+ * not 4-byte aligned. */
+typedef struct k5_flowedit_step_args {
+  float* z_fe;             /* fp32 [cells * C], updated in place when the velocities are given */
+  const float* x_src;      /* fp32 [cells * C] */
+  const void* c_src;       /* bf16 [cells * C] each; NULL (both c_*) = prepare only */
+  const void* u_src;       /* needed where w_src != 1 */
+  const void* c_tar;
+  const void* u_tar;       /* needed where w_tar != 1 */
+  float w_src;
+  float w_tar;
+  float dt;
+  const float* keep_mask;  /* fp32 [cells], NULL = no mask */
+  int prepare;             /* != 0: form zs / zt of the next step */
+  float sigma_next;        /* the next step's s */
+  float* zs;               /* fp32 [cells * C] each, written when prepare != 0 */
+  float* zt;
+  const float* znoise;     /* NULL = the generator's normals */
+  uint64_t seed;
+  uint32_t stream_id;      /* of the next step */
+  int64_t cells;
+  int C;
+} k5_flowedit_step_args;
+int k5_flowedit_step(const k5_flowedit_step_args* args, void* stream);
 /* k5_cfg_euler over temporal context windows (added under ABI 11, as the exports above were): a clip of T frames whose velocities come from
  * nwin <= 64 windows of F frames.  img fp32 [T][frame_elems]; v_cond / v_uncond (NULL = no guidance) bf16 [nwin][F][frame_elems]; starts_dev
  * DEVICE int32 [nwin], window i covers frames starts[i] .. starts[i] + F - 1; weights_dev DEVICE fp32 [nwin][F], the share of window i's local
@@ -556,6 +601,34 @@ typedef struct k5_edit_args {
   const float* keep_mask;   /* device; NULL = no mask */
 } k5_edit_args;
 int k5_sample_edit(k5_dit* dit, const k5_sample_args* args, const float* visual_cond /* nullable */, const k5_edit_args* edit, void* stream);
+
+/* FlowEdit: prompt-driven editing of a clip (added under ABI 11; the rule is written at k5_flowedit_step_args).  `source` is the clean source
+ * latent (device fp32 (T,H,W,in_visual_dim)), source_cond the prompt that describes it and source_weight its guidance weight; sample.fwd.cond,
+ * sample.guidance_weight and sample.null_cond are the target side, the negative prompt is shared by both.  sample.latent is OUTPUT ONLY.  A
+ * strength below 1 is a shorter schedule, as for k5_sample_edit: the caller hands sigmas[first:] and num_steps - first, and first_stream = first,
+ * so that step i draws from stream first_stream + i — the noise of the full schedule.  The last `refine` steps are plain steps on the target
+ * side.  keep_mask (device fp32 (T,H,W,1), 1 = keep the source, or NULL): kept cells hold `source` bit for bit.  A side whose weight is 1
+ * (within 1e-6, as k5_sample decides) runs no unconditional forward: a step is two to four forwards — source cond, source uncond, target cond,
+ * target uncond — and one k5_flowedit_step pass.  The text prologue of every distinct prompt is computed once per call.  Always eager, also with
+ * k5_dit_set_graph on; never returns to the host between steps.  A watch without previews, Enhance-A-Video, visual_cond, NABLA, fp8 and LoRA
+ * work as for a plain step.  Refused before anything is enqueued, with a message: K5_ERR_STATE on a handle in a sequence-parallel group or a
+ * CFG pair, with MagCache or its calibration, a forecast plan that has forecast steps, skip-layer guidance, a guidance plan, a stochastic plan,
+ * NAG or regions set, or a watch with previews; K5_ERR_ARG for a NULL source or source prompt, refine outside 0..num_steps, refine > 0 with a
+ * keep_mask, a pointer that is not 4-byte aligned, or source / keep_mask / visual_cond overlapping latent.
+ * k5_dit_flowedit_state: since the last reset, the FlowEdit steps and the forwards that k5_sample_flowedit calls enqueued and the text
+ * prologues they computed (any out pointer may be NULL; reset != 0 zeroes the three after reading). */
+typedef struct k5_flowedit_args {
+  const float* source;
+  k5_text_cond source_cond;
+  float source_weight;
+  const float* keep_mask;   /* device; NULL = no mask */
+  int refine;
+  uint64_t seed;
+  uint32_t first_stream;
+} k5_flowedit_args;
+int k5_sample_flowedit(k5_dit* dit, const k5_sample_args* sample, const k5_flowedit_args* flowedit, const float* visual_cond /* nullable */,
+                       void* stream);
+int k5_dit_flowedit_state(k5_dit* dit, long long* steps, long long* forwards, long long* prologues, int reset);
 
 /* Long clips: temporal context windows (added under ABI 11; extends the loop of generation_utils.py:102-128, which runs one forward over the whole
  * clip).  A clip of total_T latent frames, longer than the model's trained length, is sampled as nwin overlapping windows of sample.fwd.T frames:

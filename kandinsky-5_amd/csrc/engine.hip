@@ -504,8 +504,18 @@ struct k5_dit {
   // prompt only, so k5_sample computes them once per call and branch (slot 0 = cond, 1 = uncond) and every later step copies
   // 0.9 MB instead of re-running two GEMMs + two LayerNorms.  k5_dit_forward (one call per step, caller-owned buffers that
   // may change between calls) does not cache.
-  struct TextCache { DevBuf text, pool; bool valid = false; int L = 0; } text_cache[3 + 8];   // [2]: the negative prompt of k5_dit_set_nag (text only); [3 + r]: region r of k5_dit_set_regions (likewise)
+  struct TextCache { DevBuf text, pool; bool valid = false; int L = 0; } text_cache[3 + 8 + 2];   // [2]: the negative prompt of k5_dit_set_nag (text only); [3 + r]: region r of k5_dit_set_regions (likewise); [11], [12]: FlowEdit's source side (kFlowEditSlot)
+  static constexpr int kFlowEditSlot = 3 + 8;      // the source prompt; the negative prompt is one prompt for both sides and keeps slot 1, so slot 12 stays empty
   void drop_text_cache() { for (auto& t : text_cache) t.valid = false; }
+
+  // FlowEdit (k5_sample_flowedit): the call's workspaces — zs / zt, the two forwards' inputs of a step, and the source side's two
+  // velocities (the target side's are ws_vel_c / ws_vel_u) — and what k5_dit_flowedit_state reports.  `active` brackets a call: the text
+  // prologues computed meanwhile are counted.
+  struct FlowEdit {
+    DevBuf zs, zt, vel_c, vel_u;
+    long long steps = 0, forwards = 0, prologues = 0;
+    bool active = false;
+  } fe;
 
   // What one prompt leaves behind in a forward: every prompt — the forward's own, the negative one of k5_dit_set_nag, a region's of
   // k5_dit_set_regions — goes through the text blocks into a stream of its own (text_stream_run) and from there into every visual block's
@@ -1867,6 +1877,7 @@ int text_embeddings(k5_dit* d, hipStream_t s, const k5_text_cond& c, k5_dit::Tex
     if (pooled) HIPCHK(hipMemcpyAsync(d->ws_pool_f32.p, tc->pool.p, (size_t)d->TD * 4, hipMemcpyDeviceToDevice, s));
     return K5_OK;
   }
+  if (d->fe.active) d->fe.prologues += 1;
   const void* text_bf; const void* pool_bf;
   K5CHK(to_bf16(d, s, c.text_embed, c.text_dtype, (size_t)L * cfg.in_text_dim, d->ws_text_in, &text_bf));
   if (pooled) K5CHK(to_bf16(d, s, c.pooled_embed, c.text_dtype, (size_t)cfg.in_text_dim2, d->ws_pool_in, &pool_bf));
@@ -1951,6 +1962,7 @@ struct ForwardCall {
   void* out; hipStream_t s;
   const float* tvec = nullptr; const int* step = nullptr;   // a captured step reads its time through the device-side step tables and counter
   int text_slot = -1;                                        // the text cache slot of a k5_sample* call (0 cond, 1 uncond); -1: a forward of its own
+  int cache_slot = -1;                                       // FlowEdit's source prompt: the text_cache entry of the forward's own prompt where it is not text_slot
   const float* vcond = nullptr;                              // visual conditioning beside an x of in_visual_dim channels
   void* out_skip = nullptr;                                  // the forking forward: where the skip branch's velocity goes
   int fc_step = -1, fc_slot = 0;                             // the forecast cache's cursor: this forward is call (step, slot) of the plan; -1: a plain forward
@@ -2105,7 +2117,7 @@ struct ForwardRun : ForwardShape {
   // ---- before_text_transformer_blocks (dit.py:129-137) ----
   int prologue() {
     Scope sc(d, s, "prologue");
-    K5CHK(text_embeddings(d, s, f.cond, d->streams[0], d->stream_cache(0, f.text_slot), true));
+    K5CHK(text_embeddings(d, s, f.cond, d->streams[0], f.cache_slot >= 0 ? &d->text_cache[f.cache_slot] : d->stream_cache(0, f.text_slot), true));
     K5CHK(k5_launch_time_features(f.time, d->ws_tfeat.as<float>(), D, s, f.tvec, f.step));
     K5CHK(k5_launch_gemv_f32(d->ws_tfeat.as<float>(), d->time_w1.as<float>(), d->time_b1.as<float>(), d->ws_th1.as<float>(),
                              d->TD, D, 0, nullptr, s));
@@ -2360,6 +2372,7 @@ extern "C" void k5_dit_destroy(k5_dit* d) {
   if (d->h_leave_sig) { (void)hipHostFree(d->h_leave_sig); d->h_leave_sig = nullptr; }
   for (auto& t : d->text_cache) { t.text.release(); t.pool.release(); }
   for (auto& st : d->streams) st.release();
+  for (DevBuf* b : {&d->fe.zs, &d->fe.zt, &d->fe.vel_c, &d->fe.vel_u}) b->release();
   d->nag.o.release(); d->regions.o.release(); d->regions.w.release(); d->skip.vis.release(); d->skip.vel.release();
   for (auto& kv : d->staged) kv.second.dev.release();   // a handle destroyed before finalize still holds its staged matrices
   d->mag.residual[0].release(); d->mag.residual[1].release(); d->mag.pm_one.release();
@@ -2642,7 +2655,7 @@ static const char* rank_group(const k5_dit* d) {
 // Everything sample_impl refuses, before anything is enqueued or allocated and before any per-call state is touched: no HIP call and no
 // write to the handle here (the forward's side of the same contract: forward_refusals).  (A watched call's shape check comes later, where it always was: Watch::begin.)
 static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit,
-                           const k5_sample_windows_args* win, const char* who) {
+                           const k5_sample_windows_args* win, const char* who, const k5_flowedit_args* fe = nullptr) {
   if (!d || !a || !a->latent || !a->sigmas || a->num_steps <= 0) return K5_ERR_ARG;
   const k5_dit_config& c = d->cfg;
   const char* const mag = magcache_mode(d);
@@ -2663,6 +2676,42 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
       if (p0 & 3) { k5_set_error("%s: edit %s is not 4-byte aligned", who, t.name); return K5_ERR_ARG; }
       if (p0 < l1 && l0 < p1) { k5_set_error("%s: edit %s overlaps latent (latent is output only)", who, t.name); return K5_ERR_ARG; }
     }
+  }
+  if (fe) {   // FlowEdit: every forward and update of a step is this mode's own, so what changes either is refused, not half honoured
+    if (!fe->source || !fe->source_cond.text_embed) { k5_set_error("%s: FlowEdit needs a source latent and a source prompt", who); return K5_ERR_ARG; }
+    if (n <= 0) { k5_set_error("%s: bad shapes", who); return K5_ERR_ARG; }
+    if (fe->refine < 0 || fe->refine > a->num_steps) {
+      k5_set_error("%s: refine must be in 0..num_steps (got %d of %d)", who, fe->refine, a->num_steps);
+      return K5_ERR_ARG;
+    }
+    if (fe->refine > 0 && fe->keep_mask) {
+      k5_set_error("%s: refine = %d with a keep_mask: the keep rule of a plain step needs an eps this mode does not have", who, fe->refine);
+      return K5_ERR_ARG;
+    }
+    const uintptr_t l0 = reinterpret_cast<uintptr_t>(a->latent), l1 = l0 + (uintptr_t)n * 4;
+    const struct { const float* p; int64_t elems; const char* name; } in[3] = {
+        {fe->source, n, "source"}, {fe->keep_mask, n / c.out_visual_dim, "keep_mask"}, {vcond, n / c.out_visual_dim * (c.in_visual_dim + 1), "visual_cond"}};
+    if (l0 & 3) { k5_set_error("%s: latent is not 4-byte aligned", who); return K5_ERR_ARG; }
+    for (const auto& t : in) {
+      if (!t.p) continue;
+      const uintptr_t p0 = reinterpret_cast<uintptr_t>(t.p), p1 = p0 + (uintptr_t)t.elems * 4;
+      if (p0 & 3) { k5_set_error("%s: FlowEdit %s is not 4-byte aligned", who, t.name); return K5_ERR_ARG; }
+      if (p0 < l1 && l0 < p1) { k5_set_error("%s: FlowEdit %s overlaps latent (latent is output only)", who, t.name); return K5_ERR_ARG; }
+    }
+    if (rank_group(d)) {
+      k5_set_error("%s: the handle is in a %s: the forwards of a FlowEdit step are not split over ranks", who, rank_group(d));
+      return K5_ERR_STATE;
+    }
+    if (mag) { k5_set_error("%s: %s on the handle: the ratio table is indexed by the calls of a plain run", who, mag); return K5_ERR_STATE; }
+    const char* why = d->fc.on && d->fc.mixed ? "a forecast plan with forecast steps is set (k5_dit_set_forecast): the cache holds two slots, a step has four forwards"
+                      : d->skip.live() ? "skip-layer guidance is set (k5_dit_set_skip_guidance): the update has no skip term"
+                      : d->guide.on ? "a guidance plan is set (k5_dit_set_guidance): one plan, two guided sides"
+                      : d->sto.on ? "a stochastic plan is set (k5_dit_set_stochastic): FlowEdit draws its own noise"
+                      : d->nag.on ? "normalized attention guidance is set (k5_dit_set_nag): two conditional forwards, whose is it?"
+                      : d->regions.on ? "regional prompts are set (k5_dit_set_regions): two conditional forwards, whose are they?"
+                      : d->watch.on && d->watch.every > 0 ? "the watch has previews: z_fe is not on the model's path, x0 = x - sigma v does not hold; install the watch with preview_every = 0"
+                      : nullptr;
+    if (why) { k5_set_error("%s: %s", who, why); return K5_ERR_STATE; }
   }
   const k5_dit::Watch& wt = d->watch;
   if (wt.on && rank_group(d)) {
@@ -2837,6 +2886,10 @@ namespace {
 // What one sample_impl call works on: filled top to bottom by sample_impl before the first step, read by step(i) and by the watch.
 struct SampleRun {
   k5_dit* d; const k5_sample_args* a; const float* vcond; const k5_edit_args* edit; const k5_sample_windows_args* win;
+  const k5_flowedit_args* fe = nullptr;     // k5_sample_flowedit: steps below fe_steps are FlowEdit steps, the rest plain steps on the target side
+  int fe_steps = 0;
+  bool fe_src_cfg = false;                  //   the source side runs its unconditional forward
+  int fe_src_slot = 0;                      //   the text cache slot of the source prompt (0: it is the target prompt)
   hipStream_t s = nullptr;
   int64_t n = 0, cells = 0;                 // elements and cells of the latent one forward sees (with win: a window's)
   bool cfg_on = false, pair = false;        // pair: CFG-parallel, one branch here, the other on the paired handle
@@ -2873,14 +2926,56 @@ struct SampleRun {
   // One forward of step i: the text condition through text cache slot `slot`, on the latent slice `x` with its conditioning slice `vc`, into
   // `vel`.  `tables`: the forward reads its time through the device-side step tables when the step is captured; windows pass none.
   // `skip_vel`: the forward forks and leaves the skip branch's velocity there.
-  int forward(int i, const k5_text_cond& cond, int slot, const float* x, void* vel, const float* vc, bool tables = true, void* skip_vel = nullptr) {
+  int forward(int i, const k5_text_cond& cond, int slot, const float* x, void* vel, const float* vc, bool tables = true, void* skip_vel = nullptr,
+              int cache_slot = -1) {
     ForwardCall f{&a->fwd, cond, t1000[i], x, d->cfg.in_visual_dim, vel, s};
     if (tables) { f.tvec = tvec; f.step = step_ctr; }
-    f.text_slot = slot; f.vcond = vc; f.out_skip = skip_vel;
+    f.text_slot = slot; f.vcond = vc; f.out_skip = skip_vel; f.cache_slot = cache_slot;
+    if (fe) d->fe.forwards += 1;
     // the forecast cache: step i's forwards are the plan's calls (i, slot); a plan of ones is off — plain forwards, counted as full calls
     if (d->fc.on && d->fc.mixed) { f.fc_step = i; f.fc_slot = slot; }
     else if (d->fc.on) d->fc.full_calls++;
     return forward_impl(d, f);
+  }
+
+  // The launch that finishes FlowEdit step i (i < 0: none, the call's first launch) and prepares step i + 1 when there is one to prepare: a
+  // further FlowEdit step, or the first plain step, whose latent is zt
+  int flowedit_pass(int i) {
+    Scope sc(d, s, "elementwise");
+    const int nx = i + 1;
+    k5_flowedit_step_args e{};
+    e.z_fe = a->latent; e.x_src = fe->source; e.w_src = 1.0f; e.w_tar = 1.0f;
+    if (i >= 0) {
+      e.c_src = d->fe.vel_c.p; e.c_tar = vel_c; e.dt = dt[i]; e.keep_mask = fe->keep_mask;
+      if (fe_src_cfg) { e.u_src = d->fe.vel_u.p; e.w_src = fe->source_weight; }
+      if (cfg_on) { e.u_tar = vel_u; e.w_tar = a->guidance_weight; }
+    }
+    e.prepare = nx < a->num_steps;   // past the last step nothing reads them
+    if (e.prepare) {
+      e.sigma_next = a->sigmas[nx]; e.zs = d->fe.zs.as<float>(); e.zt = d->fe.zt.as<float>();
+      e.seed = fe->seed; e.stream_id = fe->first_stream + (uint32_t)nx;
+    }
+    e.cells = cells; e.C = d->cfg.out_visual_dim;
+    if (i < 0 && !e.prepare) return K5_OK;
+    return k5_launch_flowedit_step(e, s);
+  }
+
+  // FlowEdit step i: source cond, source uncond on zs, target cond, target uncond on zt (a side of weight 1 runs no unconditional forward), then
+  // the pass.  After the last FlowEdit step of a call with refine steps the latent becomes zt.
+  int flowedit_step(int i) {
+    const float* zs = d->fe.zs.as<float>(); const float* zt = d->fe.zt.as<float>();
+    K5CHK(forward(i, fe->source_cond, 0, zs, d->fe.vel_c.p, vcond, false, nullptr, fe_src_slot));
+    if (fe_src_cfg) K5CHK(forward(i, a->null_cond, 1, zs, d->fe.vel_u.p, vcond, false));
+    K5CHK(forward(i, a->fwd.cond, 0, zt, vel_c, vcond, false));
+    if (cfg_on) K5CHK(forward(i, a->null_cond, 1, zt, vel_u, vcond, false));
+    K5CHK(flowedit_pass(i));
+    d->fe.steps += 1;
+    if (i + 1 == fe_steps && fe_steps < a->num_steps) return flowedit_to_plain();
+    return K5_OK;
+  }
+  int flowedit_to_plain() {   // the plain steps that close the run start from zt
+    HIPCHK(hipMemcpyAsync(a->latent, d->fe.zt.p, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    return K5_OK;
   }
 
   int step(int i) {   // enqueue step i: the forwards, then CFG + Euler
@@ -2909,6 +3004,7 @@ struct SampleRun {
       return K5_OK;
     }
     if (kind(i) == ZERO) return K5_OK;   // velocity 0: no forward, no update
+    if (fe && i < fe_steps) return flowedit_step(i);
     const bool skip = skip_at(i);
     if (pair) {
       // my branch only; then the pair's velocities change hands on the side stream (fork / join by events: capturable) and both
@@ -3039,12 +3135,13 @@ int k5_dit::Watch::end(const SampleRun& r) {   // the last step's callback; a st
 // The sampler loop behind k5_sample / k5_sample_cond (edit == nullptr: their launches, their bits), k5_sample_edit and k5_sample_windows
 // (win != nullptr: a->fwd is the window, a->latent / vcond the whole clip of win->total_T frames; never together with edit).
 static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream, const char* who,
-                       const k5_sample_windows_args* win = nullptr) {
+                       const k5_sample_windows_args* win = nullptr, const k5_flowedit_args* fe = nullptr) {
   g_err[0] = 0;
-  K5CHK(sample_refusals(d, a, vcond, edit, win, who));
+  K5CHK(sample_refusals(d, a, vcond, edit, win, who, fe));
   const k5_dit_config& c = d->cfg;
   k5_dit::Watch& wt = d->watch;
   SampleRun r{d, a, vcond, edit, win};
+  r.fe = fe;
   r.s = (hipStream_t)stream;
   r.cells = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W;
   r.n = r.cells * c.out_visual_dim;
@@ -3108,7 +3205,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   // holds one forward pair).  The IPC transport IS replayable: its epochs live on the device and the peers' buffers were mapped by the eager
   // first step (ipc_comm.h)
   const bool graph = d->use_graph && !d->mag.on && !d->cal.on && !d->profiling && a->num_steps > 2 && !d->nabla_tap && !d->comm.loop && !d->pair.loop &&
-                     !win && uniform;
+                     !win && !fe && uniform;   // FlowEdit: steps of two kinds, and the pass reads its scalars by value
   if (d->sto.on) r.sto = &d->sto;
   const size_t sto_at = (gd.on ? 4 : 3) * (size_t)N;   // with a stochastic plan two more tables: scale and noise_coef
   r.host_tab.resize(sto_at + (r.sto ? 2 : 0) * (size_t)N);
@@ -3149,6 +3246,21 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     HIPCHK(hipMemcpyAsync(static_cast<char*>(d->ws_win.p) + sb, win->weights, wb, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));   // the caller's tables are host memory
     r.win_starts = d->ws_win.as<int32_t>(); r.win_weights = reinterpret_cast<const float*>(static_cast<char*>(d->ws_win.p) + sb);
+  }
+  struct FlowEditGuard { k5_dit* d; ~FlowEditGuard() { d->fe.active = false; } } flowedit_guard{d};
+  if (fe) {   // z_fe = x_src lives in the latent; the first launch forms zs / zt of step 0 (with no FlowEdit step: the first plain step's latent)
+    const k5_text_cond& sc = fe->source_cond; const k5_text_cond& tc = a->fwd.cond;
+    r.fe_steps = N - fe->refine;
+    r.fe_src_cfg = fabsf(fe->source_weight - 1.0f) > 1e-6f;
+    r.fe_src_slot = sc.text_embed == tc.text_embed && sc.pooled_embed == tc.pooled_embed && sc.text_len == tc.text_len ? 0 : k5_dit::kFlowEditSlot;
+    K5CHK(d->fe.zs.ensure((size_t)r.n * 4));
+    K5CHK(d->fe.zt.ensure((size_t)r.n * 4));
+    K5CHK(d->fe.vel_c.ensure((size_t)r.n * 2));
+    if (r.fe_src_cfg) K5CHK(d->fe.vel_u.ensure((size_t)r.n * 2));
+    d->fe.active = true;
+    HIPCHK(hipMemcpyAsync(a->latent, fe->source, (size_t)r.n * 4, hipMemcpyDeviceToDevice, s));
+    K5CHK(r.flowedit_pass(-1));
+    if (r.fe_steps == 0) K5CHK(r.flowedit_to_plain());
   }
   d->drop_text_cache();                                      // the prompt tensors are constant for THIS call only
   K5CHK(reset_attn_pref(d, s));                              // ... and so is what the softmax-form memory of the layers is worth
@@ -3215,6 +3327,20 @@ extern "C" int k5_sample(k5_dit* d, const k5_sample_args* a, void* stream) { ret
 
 extern "C" int k5_sample_edit(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream) {
   return sample_impl(d, a, vcond, edit, stream, edit ? "k5_sample_edit" : "k5_sample_cond");
+}
+
+extern "C" int k5_sample_flowedit(k5_dit* d, const k5_sample_args* a, const k5_flowedit_args* fe, const float* vcond, void* stream) {
+  if (!fe) { g_err[0] = 0; k5_set_error("k5_sample_flowedit: null FlowEdit arguments"); return K5_ERR_ARG; }
+  return sample_impl(d, a, vcond, nullptr, stream, "k5_sample_flowedit", nullptr, fe);
+}
+
+extern "C" int k5_dit_flowedit_state(k5_dit* d, long long* steps, long long* forwards, long long* prologues, int reset) {
+  if (!d) { k5_set_error("k5_dit_flowedit_state: null handle"); return K5_ERR_ARG; }
+  if (steps) *steps = d->fe.steps;
+  if (forwards) *forwards = d->fe.forwards;
+  if (prologues) *prologues = d->fe.prologues;
+  if (reset) d->fe.steps = d->fe.forwards = d->fe.prologues = 0;
+  return K5_OK;
 }
 
 extern "C" int k5_sample_windows(k5_dit* d, const k5_sample_windows_args* w, const float* vcond, void* stream) {

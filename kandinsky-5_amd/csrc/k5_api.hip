@@ -496,6 +496,16 @@ int k5_euler_step(const k5_euler_step_args* args, void* stream) {
   return ret(st, "k5_euler_step");
 }
 
+int k5_flowedit_step(const k5_flowedit_step_args* args, void* stream) {
+  if (!args) { k5_set_error("k5_flowedit_step: args is NULL"); return K5_ERR_ARG; }
+  if (const char* why = k5_flowedit_step_refusal(*args)) {
+    k5_set_error("k5_flowedit_step: %s (cells %lld, C %d, w_src %g, w_tar %g)", why, (long long)args->cells, args->C, (double)args->w_src,
+                 (double)args->w_tar);
+    return K5_ERR_ARG;
+  }
+  return ret(k5_launch_flowedit_step(*args, (hipStream_t)stream), "k5_flowedit_step");
+}
+
 int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts_dev,
                          const float* weights_dev, int nwin, int F, int T, int64_t frame_elems, void* stream) {
   if (!img || !v_cond || !starts_dev || !weights_dev || nwin < 1 || nwin > 64 || F < 1 || T < 1 || frame_elems < 1) {

@@ -187,6 +187,10 @@ struct K5EulerStepArgs : k5_euler_step_args {
   K5EulerStepArgs(const k5_euler_step_args& pub, hipStream_t s) : k5_euler_step_args(pub), stream(s) {}
 };
 int k5_launch_euler_step(const K5EulerStepArgs& a);
+// FlowEdit's pass of one step (finish step i, prepare step i + 1) on cells * C elements; the rule is written once, at k5_flowedit_step_args in
+// include/k5.h.  k5_flowedit_step_refusal names what the launcher refuses (nullptr: nothing); K5_ERR_ARG, nothing launched.
+const char* k5_flowedit_step_refusal(const k5_flowedit_step_args& a);
+int k5_launch_flowedit_step(const k5_flowedit_step_args& a, hipStream_t stream);
 // Philox4x32-10 raw words: out [nblk][4] of blocks blk0 .. blk0 + nblk - 1 (mod 2^64) under key = seed and counter words 2 / 3 = c2 / c3
 int k5_launch_philox_words(uint32_t* out, uint64_t blk0, int64_t nblk, uint64_t seed, uint32_t c2, uint32_t c3, hipStream_t stream);
 // out[g] = normal g & 3 of Philox block g >> 2 (counter (blk lo, blk hi, stream_id, 0), key = seed; Box-Muller in fp32), any n >= 1

@@ -807,6 +807,105 @@ __global__ __launch_bounds__(256) void euler_step_kernel(float* __restrict__ img
   }
 }
 
+// e added to z under the keep mask: m == 1 -> z, m == 0 -> z + e, otherwise z + (1 - m) * e, the difference, the product and the sum rounded
+// to fp32 each on its own (the pragma: see renoise_at)
+__device__ __forceinline__ float flowedit_add(float z, float e, float m) {
+#pragma clang fp contract(off)
+  if (m == 1.0f) return z;
+  if (m == 0.0f) return z + e;
+  const float k = 1.0f - m;
+  const float ke = k * e;
+  return z + ke;
+}
+// zt = zs + (z_fe - x_src): the difference first, so that z_fe == x_src gives zs bit for bit
+__device__ __forceinline__ float flowedit_target(float zs, float zfe, float x0) {
+#pragma clang fp contract(off)
+  const float d = zfe - x0;
+  return zs + d;
+}
+
+// FlowEdit (k5_flowedit_step, the rule is written at k5_flowedit_step_args): one pass finishes step i and prepares step i + 1.  UPDATE: z_fe +=
+// bf16(dt * bf16(v_t - v_s)) under the keep mask, v_s / v_t the CFG velocities of the source and target side (cfg_velocity; an `us` / `ut` of
+// NULL is weight 1: the conditional velocity itself).  PREPARE: zs = renoise_at(1 - sigma, sigma, x_src, z) and zt = zs + (z_fe - x_src) for the
+// next step, z from `znoise` or philox_normal4.  A thread owns the four elements of one Philox block, as euler_step_kernel<ST> does: 16 B of each
+// fp32 stream and 8 B of each bf16 stream per access where n % 4 == 0 and the bases allow it (a wave then covers 1 KiB / 512 B of consecutive
+// addresses per instruction), otherwise element by element with the same bits.  The update runs before the generator, so the four velocity
+// streams are dead and z_fe is stored before the Philox rounds need registers.  As compiled by build.py (resources.json): <true, true> 55 VGPRs,
+// 106 SGPRs with 9 of them spilled to lanes, 7 waves per SIMD — the ten pointers and the wide scalars, not the vector registers, cost the eighth
+// wave; <true, false> 38 VGPRs and <false, true> 48, both at 8 waves.  z_fe is read and written by the same thread only.
+template <bool UPDATE, bool PREPARE>
+__global__ __launch_bounds__(256) void flowedit_step_kernel(float* __restrict__ zfe, const float* __restrict__ x0, const bf16_t* __restrict__ cs,
+                                                            const bf16_t* __restrict__ us, const bf16_t* __restrict__ ct,
+                                                            const bf16_t* __restrict__ ut, float w_src, float w_tar, float dt,
+                                                            const float* __restrict__ mask, int C, float sigma, float* __restrict__ zs_out,
+                                                            float* __restrict__ zt_out, const float* __restrict__ znoise, uint64_t seed,
+                                                            uint32_t stream_id, int64_t n) {
+  const float a = 1.0f - sigma;
+  const bf16_t* usp = us ? us : cs;   // weight 1: u is unused, the same address again costs no traffic (see euler_step_kernel)
+  const bf16_t* utp = ut ? ut : ct;
+  const int64_t items = (n + 3) >> 2;
+  const auto at = [](const void* q, uintptr_t m) { return (reinterpret_cast<uintptr_t>(q) & (m - 1)) == 0; };
+  const bool vec = (n & 3) == 0 && at(zfe, 16) && at(x0, 16) && at(cs, 8) && at(us, 8) && at(ct, 8) && at(ut, 8) && at(zs_out, 16) &&
+                   at(zt_out, 16) && at(znoise, 16);
+  for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (int64_t)gridDim.x * 256) {
+    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 fv = {0.0f, 0.0f, 0.0f, 0.0f}, xv = fv, zv = fv, sv = fv, tv = fv;
+    u32x2 csv = {0u, 0u}, usv = csv, ctv = csv, utv = csv;
+    if (vec) {   // every load ahead of the arithmetic
+      fv = *reinterpret_cast<const f32x4*>(zfe + it * 4);
+      if (UPDATE) {
+        csv = *reinterpret_cast<const u32x2*>(cs + it * 4);
+        usv = *reinterpret_cast<const u32x2*>(usp + it * 4);
+        ctv = *reinterpret_cast<const u32x2*>(ct + it * 4);
+        utv = *reinterpret_cast<const u32x2*>(utp + it * 4);
+      }
+      if (PREPARE) xv = *reinterpret_cast<const f32x4*>(x0 + it * 4);
+      if (PREPARE && znoise) zv = *reinterpret_cast<const f32x4*>(znoise + it * 4);
+    }
+    // the update first: its four velocity streams are done with, and z_fe is on its way out, before the generator's arithmetic needs registers
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t g = it * 4 + k;
+      if (g >= n) break;
+      if (!vec) fv[k] = zfe[g];
+      if (UPDATE) {
+        float c1, u1, c2, u2;
+        if (vec) {
+          c1 = bf16_at(csv, k); u1 = bf16_at(usv, k); c2 = bf16_at(ctv, k); u2 = bf16_at(utv, k);
+        } else {
+          const bf16_t b1 = cs[g], b2 = usp[g], b3 = ct[g], b4 = utp[g];
+          c1 = bf2f(b1); u1 = bf2f(b2); c2 = bf2f(b3); u2 = bf2f(b4);
+        }
+        const float m = mask ? mask[g / C] : 0.0f;
+        const float v_s = us ? cfg_velocity(w_src, c1, u1) : c1;
+        const float v_t = ut ? cfg_velocity(w_tar, c2, u2) : c2;
+        const float d = bf_round(__fsub_rn(v_t, v_s));
+        const float e = bf_round(__fmul_rn(dt, d));
+        fv[k] = flowedit_add(fv[k], e, m);
+        if (!vec) zfe[g] = fv[k];
+      }
+    }
+    if (UPDATE && vec) *reinterpret_cast<f32x4*>(zfe + it * 4) = fv;
+    if (PREPARE) {
+      if (!znoise) philox_normal4((uint64_t)it, seed, stream_id, z);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int64_t g = it * 4 + k;
+        if (g >= n) break;
+        const float x = vec ? xv[k] : x0[g];
+        const float zz = znoise ? (vec ? zv[k] : znoise[g]) : z[k];
+        const float s1 = renoise_at(a, sigma, x, zz);
+        const float t1 = flowedit_target(s1, fv[k], x);
+        if (vec) { sv[k] = s1; tv[k] = t1; } else { zs_out[g] = s1; zt_out[g] = t1; }
+      }
+      if (vec) {
+        *reinterpret_cast<f32x4*>(zs_out + it * 4) = sv;
+        *reinterpret_cast<f32x4*>(zt_out + it * 4) = tv;
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void edit_renoise_kernel(float* __restrict__ out, const float* __restrict__ x0,
                                                            const float* __restrict__ eps, float sigma, int64_t n) {
   const float a = 1.0f - sigma;
@@ -1206,6 +1305,36 @@ int k5_launch_euler_step(const K5EulerStepArgs& a) {
                      (const bf16_t*)a.v_uncond, a.w, a.ab, a.dt, a.source, a.noise, a.keep_mask, a.sigma_next, a.C, (bf16_t*)a.v_out, a.dtvec,
                      a.signext, a.step, n, (const bf16_t*)a.v_skip, a.skip_scale, a.scale, a.noise_coef, a.znoise, a.seed, a.stream_id,
                      a.scalevec, a.coefvec);
+  return done();
+}
+
+const char* k5_flowedit_step_refusal(const k5_flowedit_step_args& a) {
+  const auto off4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
+  if (!a.z_fe) return "z_fe is NULL";
+  if (!a.x_src) return "x_src is NULL";
+  if (a.cells < 1 || a.C < 1) return "cells and C must be >= 1";
+  if ((a.c_src != nullptr) != (a.c_tar != nullptr)) return "c_src and c_tar go together";
+  if (!a.c_src && !a.prepare) return "neither velocities nor a next sigma: nothing to do";
+  if (a.c_src && a.w_src != 1.0f && !a.u_src) return "w_src != 1 needs u_src";
+  if (a.c_src && a.w_tar != 1.0f && !a.u_tar) return "w_tar != 1 needs u_tar";
+  if (a.prepare && (!a.zs || !a.zt)) return "a next sigma needs zs and zt";
+  if (off4(a.z_fe) || off4(a.x_src) || off4(a.c_src) || off4(a.u_src) || off4(a.c_tar) || off4(a.u_tar) || off4(a.keep_mask) || off4(a.zs) ||
+      off4(a.zt) || off4(a.znoise))
+    return "a pointer is not 4-byte aligned";
+  return nullptr;
+}
+
+int k5_launch_flowedit_step(const k5_flowedit_step_args& a, hipStream_t s) {
+  if (k5_flowedit_step_refusal(a)) return K5_ERR_ARG;
+  const int64_t n = a.cells * a.C;
+  const bool update = a.c_src != nullptr;
+  const auto kernel = update ? (a.prepare ? flowedit_step_kernel<true, true> : flowedit_step_kernel<true, false>)
+                             : flowedit_step_kernel<false, true>;
+  // a weight of 1 is the conditional velocity itself: its u is not handed on and so is never read
+  hipLaunchKernelGGL(kernel, dim3(grid_for((n + 3) / 4, 256, 2048)), dim3(256), 0, s, a.z_fe, a.x_src, (const bf16_t*)a.c_src,
+                     (const bf16_t*)(a.w_src != 1.0f ? a.u_src : nullptr), (const bf16_t*)a.c_tar,
+                     (const bf16_t*)(a.w_tar != 1.0f ? a.u_tar : nullptr), a.w_src, a.w_tar, a.dt, update ? a.keep_mask : nullptr, a.C,
+                     a.sigma_next, a.zs, a.zt, a.prepare ? a.znoise : nullptr, a.seed, a.stream_id, n);
   return done();
 }
 

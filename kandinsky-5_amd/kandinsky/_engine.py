@@ -145,6 +145,20 @@ class EulerStep(C.Structure):
                 ("stream_id", C.c_uint32)]
 
 
+class FlowEditStep(C.Structure):
+    """k5_flowedit_step_args: FlowEdit's pass of one step, field for field (every pointer is device memory)."""
+    _fields_ = [("z_fe", C.c_void_p), ("x_src", C.c_void_p), ("c_src", C.c_void_p), ("u_src", C.c_void_p), ("c_tar", C.c_void_p),
+                ("u_tar", C.c_void_p), ("w_src", C.c_float), ("w_tar", C.c_float), ("dt", C.c_float), ("keep_mask", C.c_void_p),
+                ("prepare", C.c_int), ("sigma_next", C.c_float), ("zs", C.c_void_p), ("zt", C.c_void_p), ("znoise", C.c_void_p),
+                ("seed", C.c_uint64), ("stream_id", C.c_uint32), ("cells", C.c_int64), ("C", C.c_int)]
+
+
+class FlowEditArgs(C.Structure):
+    """k5_flowedit_args: the source side of k5_sample_flowedit."""
+    _fields_ = [("source", C.c_void_p), ("source_cond", TextCond), ("source_weight", C.c_float), ("keep_mask", C.c_void_p),
+                ("refine", C.c_int), ("seed", C.c_uint64), ("first_stream", C.c_uint32)]
+
+
 class VaeConfig(C.Structure):
     _fields_ = [("latent_channels", C.c_int), ("out_channels", C.c_int), ("block_out_channels", C.c_int * 4),
                 ("layers_per_block", C.c_int), ("norm_num_groups", C.c_int)]
@@ -243,6 +257,9 @@ SYMBOLS = {
     "k5_noise_normal_f32": (_I, [_P, _I64, C.c_uint64, C.c_uint32, _P]),
     "k5_stochastic_euler": (_I, [_P, _P, _P, _P, _F, _P, _F, _F, _P, _P, _P, _F, _I64, _I, _P, _F, _F, _P, C.c_uint64, C.c_uint32, _P]),
     "k5_euler_step": (_I, [C.POINTER(EulerStep), _P]),
+    "k5_flowedit_step": (_I, [C.POINTER(FlowEditStep), _P]),
+    "k5_sample_flowedit": (_I, [_P, C.POINTER(SampleArgs), C.POINTER(FlowEditArgs), _P, _P]),
+    "k5_dit_flowedit_state": (_I, [_P, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), _I]),
     "k5_dit_set_stochastic": (_I, [_P, C.POINTER(Stochastic)]),
     "k5_dit_stochastic_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), _I]),
     "k5_cfg_euler_windows": (_I, [_P, _P, _P, _F, _F, _P, _P, _I, _I, _I, _I64, _P]),
@@ -568,6 +585,35 @@ def euler_step_(img, v_cond, v_uncond=None, *, w=1.0, dt, ab=None, v_skip=None, 
     with torch.cuda.device(img.device):
         check(lib().k5_euler_step(C.byref(a), stream_ptr(img.device)), "k5_euler_step")
     return img
+
+
+def flowedit_step_(z_fe, x_src, c_src=None, u_src=None, c_tar=None, u_tar=None, *, w_src=1.0, w_tar=1.0, dt=0.0, keep_mask=None, sigma_next=None,
+                   zs=None, zt=None, seed=0, stream_id=0, z=None):
+    """FlowEdit's pass of one step (k5_flowedit_step; the rule is written at k5_flowedit_step_args in include/k5.h).  With the velocities (bf16,
+    c_src and c_tar both; u_src / u_tar where the side's weight is not 1): z_fe += bf16(dt bf16(v_tar - v_src)) in place, under keep_mask (fp32,
+    one value per cell).  With sigma_next (the next step's sigma): zs = (1 - sigma_next) x_src + sigma_next z and zt = zs + (z_fe - x_src) are
+    written for the next step, z the fp32 tensor `z` or the generator's normals of (seed, stream_id).  Without velocities the call only
+    prepares.  Returns z_fe."""
+    for t in (z_fe, x_src, zs, zt, z):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != z_fe.numel()):
+            raise ValueError("flowedit_step_: z_fe, x_src, zs, zt and z must be contiguous fp32 tensors of one size")
+    for v in (c_src, u_src, c_tar, u_tar):
+        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != z_fe.numel()):
+            raise ValueError("flowedit_step_: the velocities must be contiguous bf16 tensors of z_fe's size")
+    C_ = z_fe.shape[-1]
+    cells = z_fe.numel() // C_
+    if keep_mask is not None and (keep_mask.dtype != torch.float32 or not keep_mask.is_contiguous() or keep_mask.numel() != cells):
+        raise ValueError("flowedit_step_: keep_mask must be a contiguous fp32 tensor with one value per cell")
+    if any(t is not None and t.device != z_fe.device for t in (x_src, c_src, u_src, c_tar, u_tar, keep_mask, zs, zt, z)):
+        raise ValueError("flowedit_step_: z_fe and every other tensor must be on one device")
+    _need_cuda(z_fe)
+    a = FlowEditStep(z_fe=ptr(z_fe), x_src=ptr(x_src), c_src=ptr(c_src), u_src=ptr(u_src), c_tar=ptr(c_tar), u_tar=ptr(u_tar), w_src=float(w_src),
+                     w_tar=float(w_tar), dt=float(dt), keep_mask=ptr(keep_mask), prepare=int(sigma_next is not None),
+                     sigma_next=float(sigma_next or 0.0), zs=ptr(zs), zt=ptr(zt), znoise=ptr(z), seed=int(seed) & (2 ** 64 - 1),
+                     stream_id=int(stream_id) & 0xffffffff, cells=cells, C=C_)
+    with torch.cuda.device(z_fe.device):
+        check(lib().k5_flowedit_step(C.byref(a), stream_ptr(z_fe.device)), "k5_flowedit_step")
+    return z_fe
 
 
 def cfg_euler_(img, v_cond, v_uncond, w, dt):

@@ -479,6 +479,47 @@ def _is_multi_rank_engine(model):
     return type(model) is DiffusionTransformer3D and (model._sp is not None or model._cfg_pair is not None)
 
 
+def flowedit_plan(num_steps, strength, refine=0):
+    """The kind of every step of a FlowEdit run (Kulikov et al. 2024; the rule is written at k5_flowedit_step_args in include/k5.h): "skipped"
+    for i < first = edit_first_step(num_steps, strength), "flowedit" for first <= i < num_steps - refine, "plain" for the last `refine`
+    steps.  ValueError for a refine outside 0 .. num_steps - first."""
+    first = edit_first_step(num_steps, strength)
+    if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= num_steps - first:
+        raise ValueError(f"flowedit_refine must be an integer in 0..{num_steps - first} (the steps that run), got {refine!r}")
+    return ["skipped"] * first + ["flowedit"] * (num_steps - first - refine) + ["plain"] * refine
+
+
+def _flowedit_for_run(model, num_steps, strength, init_latent, keep_mask, guidance_weight, seed, source_text_embeds, source_text_rope_pos,
+                      source_guidance_weight, flowedit_refine, flowedit_seed, refused):
+    """The ValueErrors of `generate`'s FlowEdit keywords; returns None without a source prompt, otherwise (source_text_embeds,
+    source_text_rope_pos, source weight, refine, seed).  `refused`: (name, whether it was asked for) of what does not go with FlowEdit."""
+    if source_text_embeds is None:
+        if source_text_rope_pos is not None or source_guidance_weight is not None or flowedit_refine or flowedit_seed is not None:
+            raise ValueError("source_text_rope_pos / source_guidance_weight / flowedit_refine / flowedit_seed need source_text_embeds (the prompt "
+                             "that describes the source clip)")
+        return None
+    if init_latent is None:
+        raise ValueError("source_text_embeds (FlowEdit) needs init_latent (the clip to edit)")
+    if source_text_rope_pos is None:
+        raise ValueError("source_text_embeds needs source_text_rope_pos")
+    refine = flowedit_plan(num_steps, strength, flowedit_refine).count("plain")
+    if refine > 0 and keep_mask is not None:
+        raise ValueError("flowedit_refine > 0 together with keep_mask is not supported: the keep rule of a plain step needs an eps this mode "
+                         "does not have")
+    w_src = float(guidance_weight if source_guidance_weight is None else source_guidance_weight)
+    if not math.isfinite(w_src):
+        raise ValueError(f"source_guidance_weight must be a finite number, got {source_guidance_weight}")
+    for name, asked in refused:
+        if asked:
+            raise ValueError(f"{name} together with source_text_embeds (FlowEdit) is not supported: a FlowEdit step runs the source and the "
+                             "target side's forwards and its own update")
+    if _has_magcache(model):
+        raise ValueError("source_text_embeds (FlowEdit) with MagCache: the ratio table is indexed by the call of a plain run")
+    if _is_multi_rank_engine(model) or _is_cfg_pair(model):
+        raise ValueError("source_text_embeds (FlowEdit) needs a single-rank model (no sequence-parallel group, no CFG pair)")
+    return source_text_embeds, source_text_rope_pos, w_src, refine, int(seed if flowedit_seed is None else flowedit_seed)
+
+
 class _StepWatch:
     """`generate`'s progress bar and callback as one per-step hook, shared by the fused path (installed as the engine's watch) and the
     per-step Python paths (called from the loop), so a callback sees the same sequence whichever ran."""
@@ -583,7 +624,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
              region_text_embeds=None, region_text_rope_pos=None, region_masks=None, region_base_weight=0.0,
              guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0, cfg_rescale=0.0,
              slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0, sde_interval=None, sde_seed=None,
-             enhance_weight=None, enhance_interval=None, forecast_interval=None, forecast_order=1, forecast_warmup=None, forecast_tail=1):
+             enhance_weight=None, enhance_interval=None, forecast_interval=None, forecast_order=1, forecast_warmup=None, forecast_tail=1,
+             source_text_embeds=None, source_text_rope_pos=None, source_guidance_weight=None, flowedit_refine=0, flowedit_seed=None):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
@@ -675,6 +717,21 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     it works with `strength` < 1 (the plan covers the steps that run), `eta`, NAG, regions and sequence-parallel groups.  None or 1 (default)
     is off and nothing changes.  ValueError, before anything runs: MagCache on the model, `slg_blocks`, a guidance plan with steps of
     different kinds or `cfg_zero_init`, more than one context window, a CFG pair, a model without `set_forecast` / `forecast_at`.  No
+    checkpoint was at hand, visual quality is not claimed.
+    `source_text_embeds`, `source_text_rope_pos`, `source_guidance_weight`, `flowedit_refine`, `flowedit_seed` (optional, extension): FlowEdit
+    (Kulikov et al. 2024), prompt-driven editing of `init_latent`: "the same clip, but the cat is a dog".  `source_text_embeds` (a dict like
+    `text_embeds`) describes the source clip and selects the mode; without it `init_latent` is the SDEdit path above, exactly as before.
+    Steps first = edit_first_step(num_steps, strength) .. num_steps - flowedit_refine - 1 integrate the difference between the target and the
+    source prompt's guided velocities along a noisy path tied to the source, with fresh noise at every step from the update kernel's
+    counter-based generator (`flowedit_seed` None = `seed`; step i draws stream i, so a cut schedule draws the noise of the full one); the
+    last `flowedit_refine` steps are plain steps on the target prompt.  Nothing is inverted, and the result stays on the source wherever the
+    two prompts agree.  `source_guidance_weight` None = `guidance_weight`; `null_text_embeds` is the negative prompt of both sides; a side
+    of weight 1 runs no unconditional forward.  `keep_mask` cells of 1 hold the source bit for bit.  `noise` is not read.  The
+    engine-backed model runs the one call (k5_sample_flowedit), any other callable the same forwards in the same order from the per-step
+    loop through `E.flowedit_step_`: the same bits.  With batch > 1 the samples run one at a time, sample b with seed flowedit_seed + b.
+    ValueError, before anything runs: without init_latent or source_text_rope_pos; flowedit_refine outside 0 .. the steps that run, or > 0
+    with keep_mask; together with context windows, MagCache, a multi-rank model, forecast steps, slg_blocks, a guidance plan, eta > 0, NAG,
+    regions or preview_every > 0.  SD3's published values (33 of 50 steps, source guidance 3.5, target 13.5) are examples: no Kandinsky
     checkpoint was at hand, visual quality is not claimed."""
     batch = int(batch)
     if batch < 1 or shape[0] % batch:
@@ -712,6 +769,12 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     if wants_enhance:
         enhance = _enhance_for_run(model, sigmas, first, enhance_weight, enhance_interval, plan[0] if windowed else shape[0] // batch)
     forecast = _forecast_for_run(model, steps_run, forecast_interval, forecast_order, forecast_warmup, forecast_tail, guide, skip, windowed)
+    flow = _flowedit_for_run(model, num_steps, strength, init_latent, keep_mask, guidance_weight, seed, source_text_embeds, source_text_rope_pos,
+                             source_guidance_weight, flowedit_refine, flowedit_seed,
+                             (("forecast_interval", forecast is not None), ("slg_blocks", skip is not None),
+                              ("guidance_schedule / guidance_interval / cfg_zero_star / cfg_zero_init / cfg_rescale", guide is not None),
+                              ("eta > 0", sto is not None), ("nag_scale", nag_scale is not None),
+                              ("region_text_embeds", region_text_embeds is not None), ("preview_every > 0", int(preview_every or 0) > 0)))
     if region_text_embeds is not None and windowed:
         raise ValueError("region_text_embeds together with context windows is not supported: the masks cover the clip, a window sees a slice")
     with _skip_for_call(model, skip), _forecast_for_call(model, forecast), _enhance_for_call(model, enhance), _nag_for_call(model, nag_text_embeds, nag_text_rope_pos, nag_scale, nag_tau, nag_alpha), \
@@ -729,20 +792,20 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
                    null_text_rope_pos, guidance_weight, scheduler_scale, conf, watch)
             what = (context, visual_cond, visual_cond_mask, init_latent, strength, keep_mask)
             if batch > 1:
-                return _generate_batch(*run, batch, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast)
-            return _generate_one(*run, plan, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast)
+                return _generate_batch(*run, batch, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast, flow=flow)
+            return _generate_one(*run, plan, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast, flow=flow)
         finally:
             watch.close()
 
 
 def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                   guidance_weight, scheduler_scale, conf, watch, plan, context, visual_cond, visual_cond_mask, init_latent, strength,
-                  keep_mask, guide=None, skip=None, sto=None, enhance=None, forecast=None):
+                  keep_mask, guide=None, skip=None, sto=None, enhance=None, forecast=None, flow=None):
     """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch`, the checked `plan` of
     `_context_plan`, the checked guidance plan `guide` of `_guidance_for_run`, the checked skip set `skip` of `_skip_for_run` (installed on
     the model by `generate`), the checked stochastic plan `sto` of `_stochastic_for_run` and the checked Enhance-A-Video set `enhance` of
     `_enhance_for_run` (`generate` puts back what the model held) and the checked forecast plan `forecast` of `_forecast_for_run` (installed
-    on the model by `generate`); returns the latent."""
+    on the model by `generate`) and the checked FlowEdit side `flow` of `_flowedit_for_run`; returns the latent."""
     context_text = context[2]
     if plan is not None:
         F, starts, weights = plan
@@ -756,14 +819,15 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     if init_latent is not None:   # img (the draw) is eps from here on; the latent is a buffer of its own that the engine fills
         src = init_latent.to(device=img.device, dtype=torch.float32).contiguous()
         km = None if keep_mask is None else keep_mask.to(device=img.device, dtype=torch.float32).contiguous()
-        edit = (src, img, km)
-        img = torch.empty_like(img)
+        edit = (src, img, km) if flow is None else None
+        img = torch.empty_like(img) if flow is None else src.clone()   # FlowEdit: the latent is z_fe, which starts as the source
+    fe_km = km if flow is not None else None
     cond_in = _conditioning(model, img, visual_cond, visual_cond_mask)
 
     sparse_params = get_sparse_params(conf, {"visual": img if plan is None else img[:plan[0]]}, device)
     timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()  # one sync, before the loop
-    if edit is not None:
-        timesteps = timesteps[edit_first_step(num_steps, strength):]   # strength is a truncation of the schedule, nothing more
+    first = edit_first_step(num_steps, strength) if init_latent is not None else 0
+    timesteps = timesteps[first:]   # strength is a truncation of the schedule, nothing more
 
     if isinstance(model, torch.nn.Module):      # per-step paths below: a new sampling run starts with no softmax-form memory (k5_sample resets its own)
         for m in model.modules():
@@ -787,6 +851,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
                          null_text_rope_pos, guidance_weight, scale_factor=conf.metrics.scale_factor,
                          sparse_params=sparse_params,
                          visual_cond=None if cond_in is None else torch.cat(cond_in, dim=-1).contiguous(), edit=edit,
+                         flowedit=None if flow is None else (src, flow[0], flow[1], flow[2], fe_km, flow[3], flow[4], first),
                          windows=None if plan is None else (plan[1], plan[2]), window_text=None if plan is None else context_text)
         return img
 
@@ -844,6 +909,20 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     keep = {} if km is None else dict(source=edit[0], noise=edit[1], keep_mask=km)
     if edit is not None:
         E.renoise(edit[0], edit[1], float(timesteps[0]), out=img)
+    fe_steps = 0
+    if flow is not None:
+        # FlowEdit as the engine's loop runs it: img is z_fe; one pass finishes step i and forms zs / zt, the forwards' inputs of step i + 1
+        # (of the first plain step: its latent), with that step's sigma and noise stream
+        src_te, src_pos, w_src, refine, fe_seed = flow
+        src_guided, fe_steps = _is_guided(w_src), n - refine
+        zs, zt = torch.empty_like(img), torch.empty_like(img)
+
+        def prepare(nx):
+            return dict(sigma_next=float(timesteps[nx]), zs=zs, zt=zt, seed=fe_seed, stream_id=first + nx) if nx < n else {}
+
+        E.flowedit_step_(img, src, **prepare(0))
+        if fe_steps == 0:
+            img.copy_(zt)
     for i, (timestep, timestep_diff, sigma_next) in enumerate(zip(timesteps[:-1].tolist(), torch.diff(timesteps).tolist(),
                                                                   timesteps[1:].tolist())):
         # the step's weight, kind and fork, as the engine's loop (SampleRun in engine.hip) decides them: zero (no forward, no update), unguided
@@ -857,6 +936,16 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         t1000 = torch.tensor([timestep]) * 1000
         if kind == "zero":
             v, u = (torch.zeros(img.shape, dtype=torch.bfloat16, device=img.device) if wants_preview else None), None   # velocity 0: x0 = x
+        elif i < fe_steps:             # source cond, source uncond on zs; target cond, target uncond on zt; then the pass
+            xs, xt = _model_input(model, zs, cond_in), _model_input(model, zt, cond_in)
+            cs = forward(xs, src_te, src_pos, t1000).contiguous()
+            us = forward(xs, null_text_embeds, null_text_rope_pos, t1000, 1).contiguous() if src_guided else None
+            v = forward(xt, text_embeds, text_rope_pos, t1000).contiguous()
+            u = forward(xt, null_text_embeds, null_text_rope_pos, t1000, 1).contiguous() if cfg_on else None
+            E.flowedit_step_(img, src, cs, us, v, u, w_src=w_src if src_guided else 1.0, w_tar=guidance_weight if cfg_on else 1.0,
+                             dt=timestep_diff, keep_mask=fe_km, **prepare(i + 1))
+            if i + 1 == fe_steps and fe_steps < n:
+                img.copy_(zt)          # the plain steps that close the run start from zt
         elif plan is not None:         # every window's pair, then the one blend + Euler pass over the clip: a kernel of its own
             v, u = window_velocities(t1000, kind == "guided")
             E.cfg_euler_windows_(img, v, u, guidance_weight, timestep_diff, st_dev, wt_dev)
@@ -887,7 +976,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
 
 def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                     guidance_weight, scheduler_scale, conf, watch, batch, context, visual_cond, visual_cond_mask, init_latent, strength,
-                    keep_mask, guide=None, skip=None, sto=None, enhance=None, forecast=None):
+                    keep_mask, guide=None, skip=None, sto=None, enhance=None, forecast=None, flow=None):
     """`generate` for batch > 1 on the drawn noise `img` (batch*T, H, W, C), updated in place sample by sample"""
     T = img.shape[0] // batch
     tes, nes = split_per_sample(text_embeds, batch, "text_embeds"), split_per_sample(null_text_embeds, batch, "null_text_embeds")
@@ -920,7 +1009,7 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         watch.sample = b
         img[rows] = _generate_one(model, device, img[rows].clone(), num_steps, tes[b], nes[b], visual_rope_pos, tps[b], nps[b], guidance_weight,
                                   scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide, skip=skip, enhance=enhance,
-                                  forecast=forecast,
+                                  forecast=forecast, flow=None if flow is None else (*flow[:4], (flow[4] + b) & (2 ** 64 - 1)),
                                   sto=None if sto is None else (*sto[:3], (sto[3] + b) & (2 ** 64 - 1), sto[4]))   # a seed per sample
     return img
 
@@ -966,7 +1055,8 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                     region_base_weight=0.0, guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0,
                     cfg_rescale=0.0, slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0,
                     sde_interval=None, sde_seed=None, enhance_weight=None, enhance_interval=None, forecast_interval=None, forecast_order=1,
-                    forecast_warmup=None, forecast_tail=1):
+                    forecast_warmup=None, forecast_tail=1, source_caption=None, source_guidance_weight=None, flowedit_refine=0,
+                    flowedit_seed=None):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -993,8 +1083,23 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     `eta`, `s_noise`, `sde_interval`, `sde_seed` (optional, extension): stochastic sampling, passed to `generate` (see there).  Off by default.
     `enhance_weight`, `enhance_interval` (optional, extension): Enhance-A-Video, passed to `generate` (see there).  None (default) is off.
     `forecast_interval`, `forecast_order`, `forecast_warmup`, `forecast_tail` (optional, extension): the forecast cache, passed to `generate`
-    (see there).  None or 1 (default) is off."""
+    (see there).  None or 1 (default) is off.
+    `source_caption`, `source_guidance_weight`, `flowedit_refine`, `flowedit_seed` (optional, extension): FlowEdit (see `generate`): with
+    `video`, `source_caption` describes the source clip, `caption` the result; `strength` and `mask` keep their meaning.  None (default)
+    is off: `video` alone is the SDEdit path."""
     batch, frames, height, width, channels = shape
+    flow_kw = {}
+    if source_caption is None:
+        if source_guidance_weight is not None or flowedit_refine or flowedit_seed is not None:
+            raise ValueError("source_guidance_weight / flowedit_refine / flowedit_seed need source_caption (the prompt that describes the clip)")
+    else:   # before any model runs: the numbers (what depends on the run is checked by `generate`)
+        if video is None:
+            raise ValueError("source_caption (FlowEdit) needs a source video")
+        if not isinstance(source_caption, str):
+            raise ValueError("source_caption must be one prompt: every sample of the batch edits the same clip")
+        if flowedit_plan(num_steps, strength, flowedit_refine).count("plain") and mask is not None:
+            raise ValueError("flowedit_refine > 0 together with mask is not supported (see `generate`)")
+        flow_kw = dict(source_guidance_weight=source_guidance_weight, flowedit_refine=flowedit_refine, flowedit_seed=flowedit_seed)
     forecast_kw = {}
     if forecast_interval is not None:   # before any model runs: the numbers (what depends on the run is checked by `generate`)
         forecast_plan(num_steps, forecast_interval, forecast_warmup, forecast_tail, forecast_order)
@@ -1109,6 +1214,9 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         by_prompt = dict(zip(distinct, encoded))
         cond = [by_prompt[p][0] for p in captions]
         text_pos = [torch.arange(by_prompt[p][1]) for p in captions]
+    if source_caption is not None:
+        (src_cond, n_src), = _encode_prompts(text_embedder, [source_caption], kind, device)
+        flow_kw.update(source_text_embeds=src_cond, source_text_rope_pos=torch.arange(n_src))
     if offload:
         text_embedder = text_embedder.to("cpu")
 
@@ -1126,7 +1234,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                           text_pos, torch.arange(n_uncond), guidance_weight, scheduler_scale, conf, seed=seed,
                           progress=progress, batch=batch, callback=callback, preview_every=preview_every,
                           preview_factors=preview_factors, **cond_kw, **ctx_kw, **nag_kw, **region_kw, **guide_kw, **skip_kw, **sto_kw,
-                          **enhance_kw, **forecast_kw)
+                          **enhance_kw, **forecast_kw, **flow_kw)
     if offload:
         dit.to("cpu", non_blocking=True)
         torch.cuda.empty_cache()

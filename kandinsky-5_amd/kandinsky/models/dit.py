@@ -575,7 +575,7 @@ class DiffusionTransformer3D(nn.Module):
     @torch.no_grad()
     def sample(self, latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                null_text_rope_pos, guidance_weight, scale_factor=(1.0, 1.0, 1.0), sparse_params=None, visual_cond=None, edit=None,
-               windows=None, window_text=None):
+               windows=None, window_text=None, flowedit=None):
         """Whole Euler/CFG loop on device (generation_utils.py:80-129) in one C call.  `latent` fp32
         (T,H,W,in_visual_dim) is updated in place; `sigmas` = the sigma schedule (num_steps+1 floats, host).
         `visual_cond` (optional, a model with visual_cond only): contiguous fp32 (T,H,W,in_visual_dim+1) on the latent's device, the
@@ -587,7 +587,16 @@ class DiffusionTransformer3D(nn.Module):
         length runs as overlapping temporal windows of F frames whose velocities are cross-faded at every step (k5_sample_windows).
         `visual_rope_pos[0]` and `sparse_params` are then the WINDOW's (F positions), `latent` and `visual_cond` the whole clip's.
         `window_text` (optional, with `windows`): a prompt per window, a list of nwin `(text_embeds, text_rope_pos)` pairs that replaces
-        `text_embeds` / `text_rope_pos`.  Not with `edit`; a single-rank model without MagCache only, and a watch without previews."""
+        `text_embeds` / `text_rope_pos`.  Not with `edit`; a single-rank model without MagCache only, and a watch without previews.
+        `flowedit` (optional): `(source, source_text_embeds, source_text_rope_pos, source_weight, keep_mask | None, refine, seed, first_stream)`:
+        FlowEdit (k5_sample_flowedit; the rule is written at k5_flowedit_step_args in include/k5.h).  `source` is the clean source latent,
+        the source prompt describes it; `text_embeds` / `guidance_weight` are the target side and the negative prompt serves both.  `sigmas`
+        is the cut schedule sigmas[first:] and `first_stream` = first.  `latent` is output only.  Not with `edit` or `windows`."""
+        if flowedit is not None:
+            if edit is not None or windows is not None:
+                raise ValueError("flowedit together with edit or windows is not supported")
+            return self._sample_flowedit(latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
+                                         guidance_weight, scale_factor, sparse_params, visual_cond, flowedit)
         if windows is None and window_text is not None:
             raise ValueError("window_text needs windows")
         if windows is not None:
@@ -629,6 +638,31 @@ class DiffusionTransformer3D(nn.Module):
         keep.append(arr)
         s.latent, s.num_steps, s.sigmas, s.guidance_weight = latent.data_ptr(), len(sig) - 1, arr, float(guidance_weight)
         return keep, edit
+
+    def _sample_flowedit(self, latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos, guidance_weight,
+                         scale_factor, sparse_params, visual_cond, flowedit):
+        """`sample(flowedit=...)`: the k5_sample_flowedit call."""
+        if not isinstance(flowedit, (tuple, list)) or len(flowedit) != 8:
+            raise ValueError("flowedit must be (source, source_text_embeds, source_text_rope_pos, source_weight, keep_mask or None, refine, seed, "
+                             "first_stream)")
+        source, src_text, src_pos, src_w, keep_mask, refine, seed, first_stream = flowedit
+        source, _, keep_mask = self._check_edit((source, source, keep_mask), latent)   # the shape, dtype and device rules of an edit's tensors
+        s = E.SampleArgs()
+        keep, _ = self._fill_sample_args(s, latent, None, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
+                                         null_text_rope_pos, guidance_weight, scale_factor, sparse_params, visual_cond)
+        dev = latent.device
+        if _is_guided(src_w) and not _is_guided(guidance_weight):    # the negative prompt serves the source side alone
+            s.null_cond = self._text_cond(null_text_embeds["text_embeds"].to(dev), null_text_embeds["pooled_embed"].to(dev), null_text_rope_pos, keep)
+        fa = E.FlowEditArgs(source=source.data_ptr(), source_weight=float(src_w), keep_mask=E.ptr(keep_mask), refine=int(refine),
+                            seed=int(seed) & (2 ** 64 - 1), first_stream=int(first_stream) & 0xffffffff)
+        # the same tensors as the target prompt give the same pointers: the engine then computes that prompt's prologue once
+        fa.source_cond = self._text_cond(src_text["text_embeds"].to(dev), src_text["pooled_embed"].to(dev), src_pos, keep)
+        return self._run_sampler("k5_sample_flowedit", latent, C.byref(s), C.byref(fa), E.ptr(visual_cond))
+
+    def flowedit_state(self, reset=False):
+        """(steps, forwards, prologues): the FlowEdit steps and forwards the engine has enqueued in `sample(flowedit=...)` calls and the text
+        prologues it computed for them, since the last reset (k5_dit_flowedit_state)."""
+        return tuple(self._state("k5_dit_flowedit_state", (C.c_longlong, C.c_longlong, C.c_longlong), int(bool(reset))))
 
     def _run_sampler(self, name, latent, *args):
         """The k5_sample* call `name` on the latent's device and stream, between the watch's begin and end."""

@@ -97,7 +97,8 @@ class Kandinsky5T2VPipeline:
                  guidance_schedule=None, guidance_interval=None, cfg_zero_star: bool = False, cfg_zero_init: int = 0, cfg_rescale: float = 0.0,
                  slg_blocks=None, slg_scale: float = 0.0, slg_interval=None, slg_mode: str = "block", eta: float = 0.0, s_noise: float = 1.0,
                  sde_interval=None, sde_seed: int = None, enhance_weight: float = None, enhance_interval=None,
-                 forecast_interval: int = None, forecast_order: int = 1, forecast_warmup: int = None, forecast_tail: int = 1):
+                 forecast_interval: int = None, forecast_order: int = 1, forecast_warmup: int = None, forecast_tail: int = 1,
+                 source_caption: str = None, source_guidance_weight: float = None, flowedit_refine: int = 0, flowedit_seed: int = None):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -147,8 +148,20 @@ class Kandinsky5T2VPipeline:
         sigma lies in `enhance_interval` (None = all) every visual block scales its self-attention output by the cross-frame attention
         score of its own queries and keys; see `generate`.  None (default) is off, 0.0 is a valid weight.  Not on a sequence-parallel
         group, not with more than 64 latent frames per forward.  No checkpoint was at hand when this was written: visual quality is not
-        claimed."""
+        claimed.
+        `source_caption`, `source_guidance_weight`, `flowedit_refine`, `flowedit_seed` (optional, extension): FlowEdit,
+        `pipe("a dog on a sofa", video=clip, source_caption="a cat on a sofa", strength=0.7)` — "the same clip, but the cat is a dog": the
+        difference between the two prompts' velocities is integrated along a noisy path tied to the clip, nothing is inverted and the clip
+        stays where the prompts agree; see `generate`.  `source_caption` is not expanded.  None (default) is off and `video` is the SDEdit
+        path.  Single-rank, without MagCache, previews or the other sampler extensions.  SD3's published values (33 of 50 steps, source
+        guidance 3.5, target 13.5) are examples: no Kandinsky checkpoint was at hand when this was written, visual quality is not claimed."""
         ctx = {}
+        flow_kw = {}
+        if source_caption is not None:
+            flow_kw = dict(source_caption=source_caption, source_guidance_weight=source_guidance_weight, flowedit_refine=flowedit_refine,
+                           flowedit_seed=flowedit_seed)
+        elif source_guidance_weight is not None or flowedit_refine or flowedit_seed is not None:
+            raise ValueError("source_guidance_weight / flowedit_refine / flowedit_seed need source_caption (the prompt that describes the clip)")
         forecast_kw = {}
         if forecast_interval is not None:   # `generate` documents it; None or 1 is off
             forecast_kw = dict(forecast_interval=forecast_interval, forecast_order=forecast_order, forecast_warmup=forecast_warmup,
@@ -245,6 +258,6 @@ class Kandinsky5T2VPipeline:
                                  text_embedder_device=self.device_map["text_embedder"], progress=progress, offload=self.offload,
                                  image=image, video=video, strength=strength, mask=mask, callback=callback,
                                  preview_every=preview_every, preview_factors=preview_factors, **ctx, **region_kw, **guide_kw, **skip_kw, **sto_kw,
-                                 **enhance_kw, **forecast_kw)
+                                 **enhance_kw, **forecast_kw, **flow_kw)
         torch.cuda.empty_cache()
         return self._save(images, time_length, save_path) if self.local_dit_rank == 0 else None

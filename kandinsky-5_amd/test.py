@@ -4,6 +4,7 @@ README launch lines keep working against this package:
     python test.py --prompt "a cat in a blue hat" --config ./configs/config_5s_sft.yaml
     python test.py --prompt "the cat turns its head" --image cat.png     # image-to-video: the clip starts from cat.png
     python test.py --prompt "the same street at night" --video clip.mp4 --strength 0.6 --mask keep.png   # video-to-video, masked
+    python test.py --prompt "a dog on a sofa" --video clip.mp4 --source_prompt "a cat on a sofa" --strength 0.7   # FlowEdit
     python test.py --config ./configs/config_5s_distil.yaml --calibrate_magcache ratios.json   # measure a MagCache table, then:
     python test.py --config ./configs/config_5s_distil.yaml --magcache --magcache_ratios ratios.json
     python test.py --prompt "a cat in a blue hat" --lora style.safetensors --lora_scale 0.8   # LoRA adapter(s) merged into the DiT
@@ -105,6 +106,15 @@ def build_parser():
     p.add_argument("--sde_interval", type=float, nargs=2, default=argparse.SUPPRESS, metavar=("LO", "HI"),
                    help="with --eta: only on the steps whose sigma lies in [LO, HI] (default every step)")
     p.add_argument("--sde_seed", type=int, default=argparse.SUPPRESS, metavar="N", help="with --eta: seed of the step noise (default: the run's seed)")
+    p.add_argument("--source_prompt", type=str, default=argparse.SUPPRESS, metavar="TEXT",
+                   help="with --video: FlowEdit — TEXT describes the source clip, --prompt the result; the clip stays where the two agree "
+                        "(without it --video is the SDEdit path)")
+    p.add_argument("--source_guidance", type=float, default=argparse.SUPPRESS, metavar="W",
+                   help="with --source_prompt: guidance weight of the source side (default: --guidance_weight)")
+    p.add_argument("--flowedit_refine", type=int, default=argparse.SUPPRESS, metavar="R",
+                   help="with --source_prompt: the last R steps are plain steps on --prompt (default 0)")
+    p.add_argument("--flowedit_seed", type=int, default=argparse.SUPPRESS, metavar="N",
+                   help="with --source_prompt: seed of the per-step noise (default: the run's seed)")
     p.add_argument("--enhance_weight", type=float, default=argparse.SUPPRESS, metavar="W",
                    help="Enhance-A-Video: every visual block scales its self-attention output by max(1, mean cross-frame attention * (frames + W)); "
                         "W >= 0, 0 is a valid weight (commonly 2 to 5 — not tuned on these checkpoints)")
@@ -150,6 +160,34 @@ def enhance_keywords(args):
         if not lo <= hi:
             raise ValueError(f"--enhance_interval needs LO <= HI (got {lo}, {hi})")
         kw["enhance_interval"] = (lo, hi)
+    return kw
+
+
+def flowedit_keywords(args):
+    """--source_prompt / --source_guidance / --flowedit_refine / --flowedit_seed -> the pipeline's keywords"""
+    if not hasattr(args, "source_prompt"):
+        if hasattr(args, "source_guidance") or hasattr(args, "flowedit_refine") or hasattr(args, "flowedit_seed"):
+            raise ValueError("--source_guidance, --flowedit_refine and --flowedit_seed need --source_prompt")
+        return {}
+    if not hasattr(args, "video"):
+        raise ValueError("--source_prompt needs --video (the clip it describes)")
+    kw = {"source_caption": args.source_prompt}
+    if hasattr(args, "source_guidance"):
+        kw["source_guidance_weight"] = args.source_guidance
+    if hasattr(args, "flowedit_refine"):
+        if args.flowedit_refine < 0:
+            raise ValueError(f"--flowedit_refine must be >= 0 (got {args.flowedit_refine})")
+        if args.flowedit_refine > 0 and hasattr(args, "mask"):
+            raise ValueError("--flowedit_refine together with --mask is not supported")
+        kw["flowedit_refine"] = args.flowedit_refine
+    if hasattr(args, "flowedit_seed"):
+        kw["flowedit_seed"] = args.flowedit_seed
+    for flag in ("context_seconds", "eta", "slg_blocks", "nag_scale", "regions", "region", "preview", "forecast_interval", "guidance_interval",
+                 "cfg_zero_star", "cfg_zero_init", "cfg_rescale"):
+        if getattr(args, flag, None):
+            raise ValueError(f"--source_prompt together with --{flag} is not supported")
+    if getattr(args, "magcache", False) or getattr(args, "calibrate_magcache", None):
+        raise ValueError("--source_prompt together with --magcache is not supported: the ratio table is indexed by the call of a plain run")
     return kw
 
 
@@ -331,6 +369,7 @@ def main(argv=None):
     sto_kw = stochastic_keywords(args)
     enhance_kw = enhance_keywords(args)
     forecast_kw = forecast_keywords(args)
+    flow_kw = flowedit_keywords(args)
     from kandinsky import get_T2V_pipeline
     pipe = get_T2V_pipeline(device_map={"dit": "cuda:0", "vae": "cuda:0", "text_embedder": "cuda:0"}, conf_path=args.config,
                             offload=args.offload, magcache=args.magcache and not args.calibrate_magcache,
@@ -372,6 +411,7 @@ def main(argv=None):
     edit_kw.update(sto_kw)
     edit_kw.update(enhance_kw)
     edit_kw.update(forecast_kw)
+    edit_kw.update(flow_kw)
     t0 = time.perf_counter()
     pipe(args.prompt, time_length=args.video_duration, width=args.width, height=args.height, num_steps=args.sample_steps,
          guidance_weight=args.guidance_weight, scheduler_scale=args.scheduler_scale, expand_prompts=args.expand_prompt,
