@@ -268,6 +268,14 @@ int k5_patchify_bf16(const float* x, void* out, int T, int H, int W, int x_chann
  * (T,H,W,Cin_total-x_channels), 0 < x_channels < Cin_total; bit-identical output. */
 int k5_patchify_cond_bf16(const float* x, const float* vcond, void* out, int T, int H, int W, int x_channels, int Cin_total,
                           int Kpad, const int32_t* tok_perm, void* stream);
+/* k5_patchify_bf16 / k5_patchify_cond_bf16 of a strided view (added under ABI 11, as the exports further down were): the (T,H,W) box of a
+ * larger tensor, x with frame stride x_frame_stride and row stride x_row_stride (in elements; the cells of a row are x_channels apart), vcond
+ * (NULL = k5_patchify_bf16's zero channels) likewise with cells Cin_total - x_channels apart.  With compact strides it equals the two entries
+ * above bit for bit; on a view it equals them on a contiguous copy of the view.  Nothing outside the box is read.  K5_ERR_ARG, nothing
+ * launched: a NULL x or out, an extent < 1, odd H or W, a row stride below W cells or a frame stride below H rows. */
+int k5_patchify_view_bf16(const float* x, int64_t x_frame_stride, int64_t x_row_stride, const float* vcond, int64_t vc_frame_stride,
+                          int64_t vc_row_stride, void* out, int T, int H, int W, int x_channels, int Cin_total, int Kpad,
+                          const int32_t* tok_perm, void* stream);
 /* OutLayer un-patchify nn.py:384-399: [Ntok][4C] (c,ph,pw) -> (T,2Hp,2Wp,C) bf16. */
 int k5_unpatchify_bf16(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx,
                        const int32_t* tok_perm, void* stream);
@@ -426,6 +434,31 @@ int k5_flowedit_step(const k5_flowedit_step_args* args, void* stream);
  * synchronises the stream). */
 int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts_dev,
                          const float* weights_dev, int nwin, int F, int T, int64_t frame_elems, void* stream);
+/* k5_cfg_euler over a 3-D plan of context windows (spatial tiles; added under ABI 11, as the exports above were).  img fp32 (T,H,W,C); the
+ * plan is the product of three 1-D plans (kandinsky.generation_utils.tile_windows): nt x ny x nx windows of (Ft,Fh,Fw) cells, window
+ * k = (it * ny + iy) * nx + ix with its corner at (starts_t[it], starts_y[iy], starts_x[ix]); v_cond / v_uncond (NULL = no guidance) bf16
+ * [nwin][Ft][Fh][Fw][C], nwin = nt * ny * nx <= 64.  The six tables are DEVICE memory.  The rule, with every rounding point:
+ *   1. cell (t,y,x) walks the windows that cover it in ascending k;
+ *   2. window k's share is s_k = rn(rn(wt[it][t - t0] * wy[iy][y - y0]) * wx[ix][x - x0]);
+ *   3. v_k is formed as k5_cfg_euler forms it (the same three bf16 roundings);
+ *   4. acc = rn(s_0 * v_0), then acc = rn(acc + rn(s_k * v_k));
+ *   5. nothing is contracted;
+ *   6. img = rn(img + bf16(rn(dt * acc))).
+ * ny = nx = 1 with weights 1.0 is k5_cfg_euler_windows bit for bit, one window of weight 1 is k5_cfg_euler bit for bit.  One pass over img;
+ * only velocity slots inside a window's box are read, whatever the tables hold.  K5_ERR_ARG + message, nothing launched: a NULL pointer, nwin
+ * outside 1..64, an extent or window size < 1, starts of an axis that do not ascend, a window reaching outside the clip, or a cell no window
+ * covers (the nt + ny + nx starts are read back once, which synchronises the stream). */
+typedef struct k5_tile_plan {
+  int nt, ny, nx, Ft, Fh, Fw;
+  const int32_t* starts_t;   /* DEVICE [nt] */
+  const int32_t* starts_y;   /* DEVICE [ny] */
+  const int32_t* starts_x;   /* DEVICE [nx] */
+  const float* wt;           /* DEVICE [nt][Ft] */
+  const float* wy;           /* DEVICE [ny][Fh] */
+  const float* wx;           /* DEVICE [nx][Fw] */
+} k5_tile_plan;
+int k5_cfg_euler_tiles(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const k5_tile_plan* plan, int T, int H, int W,
+                       int C, void* stream);
 /* Sampler preview (added under ABI 11, as the exports above were): the denoised estimate of a flow-matching step and a cheap RGB view of it, one
  * pass.  After the update of a step the latent x (fp32, cells * C) sits at sigma_next and v_cond / v_uncond (bf16, v_uncond NULL = no guidance)
  * still hold that step's velocities: v is combined exactly as in k5_cfg_euler, x0 = rn(x - rn(sigma_next * v)) in fp32 (sigma_next == 0 gives
@@ -654,6 +687,40 @@ typedef struct k5_sample_windows_args {
   const k5_text_cond* null_conds;    /* HOST [nwin] or NULL */
 } k5_sample_windows_args;
 int k5_sample_windows(k5_dit* dit, const k5_sample_windows_args* args, const float* visual_cond /* nullable */, void* stream);
+
+/* Large frames: spatial context windows (tiles; added under ABI 11).  k5_sample_windows in three axes: a clip of (total_T, total_H, total_W)
+ * latent cells, larger than the model's trained size, is sampled as nt x ny x nx overlapping windows of (sample.fwd.T, fwd.H, fwd.W) cells.
+ * A spatial window is not contiguous: each forward patchifies a strided view of the latent (k5_patchify_view_bf16) and writes the compact slot
+ * k = (it * ny + iy) * nx + ix of the velocity buffers; at every step the windows run in order k, conditional before unconditional, with the
+ * window's RoPE positions sample.fwd.pos_t / pos_h / pos_w, and one k5_cfg_euler_tiles pass cross-fades their velocities into the update of
+ * the whole latent.  The result is bit-identical to the same forwards issued one by one through k5_dit_forward on contiguous copies of the
+ * views, on a fresh softmax-form memory, followed by k5_cfg_euler_tiles per step.
+ *   sample: as k5_sample, except that fwd.T / H / W (and pos_*, the NABLA geometry, Enhance-A-Video's T) are the WINDOW's and latent is device
+ *           fp32 (total_T,total_H,total_W,in_visual_dim).
+ *   starts_* HOST, ascending per axis, every window inside the clip, every cell covered, spatial starts even (patch-aligned);
+ *   wt / wy / wx HOST [nt][fwd.T], [ny][fwd.H], [nx][fwd.W].
+ *   conds / null_conds: HOST [nt * ny * nx] prompts, one per window, or NULL.
+ *   visual_cond: device fp32 (total_T,total_H,total_W,in_visual_dim+1) or NULL; each window sees its slice through the view.
+ * A clip no larger than the window in every axis is k5_sample_cond on the whole clip; ny = nx = 1 with total_H = fwd.H and total_W = fwd.W is
+ * k5_sample_windows (its launches, its bits).  Always eager, also with k5_dit_set_graph on.  A watch without previews works (progress, cancel;
+ * info reports the whole clip's extents).  NAG and Enhance-A-Video work.  Refused before anything is enqueued, by the same checks and error
+ * codes as k5_sample_windows: rank groups, CFG pairs, MagCache or its calibration, a watch with previews, a forecast plan with forecast
+ * steps, guidance plans, skip-layer guidance, a stochastic plan, regions; K5_ERR_ARG for a plan that does not hold (nwin outside 1..64, an
+ * axis whose starts do not ascend or leave the clip, an uncovered cell, odd spatial starts or extents, NULL tables). */
+typedef struct k5_sample_tiles_args {
+  k5_sample_args sample;
+  int total_T, total_H, total_W;
+  int nt, ny, nx;
+  const int32_t* starts_t;           /* HOST [nt] */
+  const int32_t* starts_y;           /* HOST [ny] */
+  const int32_t* starts_x;           /* HOST [nx] */
+  const float* wt;                   /* HOST [nt][sample.fwd.T] */
+  const float* wy;                   /* HOST [ny][sample.fwd.H] */
+  const float* wx;                   /* HOST [nx][sample.fwd.W] */
+  const k5_text_cond* conds;         /* HOST [nt * ny * nx] or NULL */
+  const k5_text_cond* null_conds;    /* HOST [nt * ny * nx] or NULL */
+} k5_sample_tiles_args;
+int k5_sample_tiles(k5_dit* dit, const k5_sample_tiles_args* args, const float* visual_cond /* nullable */, void* stream);
 
 /* Several samples in one call (generate_sample's shape = (bs, frames, h, w, c), reference generation_utils.py:150): a CONVENIENCE entry point,
  * not a batched kernel path.  The B samples of one (T, H, W) run ONE AFTER ANOTHER on the stream, each as k5_sample_cond on its own slice of

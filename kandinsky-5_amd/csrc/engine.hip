@@ -1966,6 +1966,7 @@ struct ForwardCall {
   const float* vcond = nullptr;                              // visual conditioning beside an x of in_visual_dim channels
   void* out_skip = nullptr;                                  // the forking forward: where the skip branch's velocity goes
   int fc_step = -1, fc_slot = 0;                             // the forecast cache's cursor: this forward is call (step, slot) of the plan; -1: a plain forward
+  int64_t x_frame = 0, x_row = 0, vc_frame = 0, vc_row = 0;  // a spatial window: x (and vcond) is a strided view, in elements; x_row == 0: compact
 };
 
 struct ForwardShape {   // patched frames / rows / columns, visual tokens, text rows, model width, input channels of the patch embedding
@@ -2126,7 +2127,9 @@ struct ForwardRun : ForwardShape {
     // every Modulation layer of the network in one GEMV (they all consume the same time_embed)
     K5CHK(k5_launch_gemv_f32(d->ws_temb.as<float>(), d->mod_w.as<float>(), d->mod_b.as<float>(), d->ws_mod.as<float>(),
                              (int)d->mod_rows, d->TD, 1, nullptr, s));
-    if (f.vcond) K5CHK(k5_launch_patchify_cond(f.x, f.vcond, d->ws_xp.p, a->T, a->H, a->W, f.x_channels, Cin, d->KvisPad, perm, s));
+    if (f.x_row) K5CHK(k5_launch_patchify_view(f.x, f.x_frame, f.x_row, f.vcond, f.vc_frame, f.vc_row, d->ws_xp.p, a->T, a->H, a->W, f.x_channels, Cin,
+                                               d->KvisPad, perm, s));
+    else if (f.vcond) K5CHK(k5_launch_patchify_cond(f.x, f.vcond, d->ws_xp.p, a->T, a->H, a->W, f.x_channels, Cin, d->KvisPad, perm, s));
     else K5CHK(k5_launch_patchify(f.x, d->ws_xp.p, a->T, a->H, a->W, f.x_channels, Cin, d->KvisPad, perm, s));
     return linear(LinearArgs(d->vis_lin, Act{d->ws_xp.as<bf16_t>() + (size_t)tok0 * d->KvisPad, nullptr, n, d->KvisPad}, d->ws_vis.p, D, s));
   }
@@ -2655,7 +2658,8 @@ static const char* rank_group(const k5_dit* d) {
 // Everything sample_impl refuses, before anything is enqueued or allocated and before any per-call state is touched: no HIP call and no
 // write to the handle here (the forward's side of the same contract: forward_refusals).  (A watched call's shape check comes later, where it always was: Watch::begin.)
 static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit,
-                           const k5_sample_windows_args* win, const char* who, const k5_flowedit_args* fe = nullptr) {
+                           const k5_sample_windows_args* win, const char* who, const k5_flowedit_args* fe = nullptr,
+                           const k5_sample_tiles_args* tile = nullptr) {
   if (!d || !a || !a->latent || !a->sigmas || a->num_steps <= 0) return K5_ERR_ARG;
   const k5_dit_config& c = d->cfg;
   const char* const mag = magcache_mode(d);
@@ -2858,6 +2862,28 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
       return K5_ERR_STATE;
     }
     const int F = a->fwd.T;
+    if (tile) {   // a 3-D plan: each axis on its own, by the rule of the temporal one; spatial windows start on a patch
+      if (tile->nt < 1 || tile->ny < 1 || tile->nx < 1 || tile->nt > 64 || tile->ny > 64 || tile->nx > 64 || tile->nt * tile->ny * tile->nx > 64 ||
+          !tile->wt || !tile->wy || !tile->wx || n <= 0) {
+        k5_set_error("%s: nwin must be 1..64 (got %d x %d x %d) with starts, weights and a window shape", who, tile->nt, tile->ny, tile->nx);
+        return K5_ERR_ARG;
+      }
+      if (reinterpret_cast<uintptr_t>(a->latent) & 3) { k5_set_error("%s: latent is not 4-byte aligned", who); return K5_ERR_ARG; }
+      if ((tile->total_H & 1) || (tile->total_W & 1) || (a->fwd.H & 1) || (a->fwd.W & 1)) {
+        k5_set_error("%s: the clip's and the window's rows and columns must be even (clip %d x %d, window %d x %d)", who, tile->total_H, tile->total_W,
+                     a->fwd.H, a->fwd.W);
+        return K5_ERR_ARG;
+      }
+      const struct { const char* name; int n; const int32_t* st; int F, total; bool even; } ax[3] = {
+          {"frame", tile->nt, tile->starts_t, F, tile->total_T, false}, {"row", tile->ny, tile->starts_y, a->fwd.H, tile->total_H, true},
+          {"column", tile->nx, tile->starts_x, a->fwd.W, tile->total_W, true}};
+      for (const auto& x : ax) {
+        if (const char* why = k5_tile_axis_refusal(x.name, x.n, x.st, x.F, x.total)) { k5_set_error("%s: %s", who, why); return K5_ERR_ARG; }
+        for (int i = 0; x.even && i < x.n; ++i)
+          if (x.st[i] & 1) { k5_set_error("%s: %s window %d starts at %d: spatial windows start on a patch (an even cell)", who, x.name, i, x.st[i]); return K5_ERR_ARG; }
+      }
+      return K5_OK;
+    }
     if (win->nwin < 1 || win->nwin > 64 || !win->starts || !win->weights || F < 1 || n <= 0) {
       k5_set_error("%s: nwin must be 1..64 (got %d) with starts, weights and a window shape", who, win->nwin);
       return K5_ERR_ARG;
@@ -2886,6 +2912,9 @@ namespace {
 // What one sample_impl call works on: filled top to bottom by sample_impl before the first step, read by step(i) and by the watch.
 struct SampleRun {
   k5_dit* d; const k5_sample_args* a; const float* vcond; const k5_edit_args* edit; const k5_sample_windows_args* win;
+  const k5_sample_tiles_args* tile = nullptr;   // k5_sample_tiles: win holds the window count and the prompts, this the 3-D plan
+  k5_tile_plan tile_dev{};                  //   ... and its tables on the device
+  int64_t x_frame = 0, x_row = 0, vc_frame = 0, vc_row = 0;   //   ... and the strides of a window's view of the latent and of vcond
   const k5_flowedit_args* fe = nullptr;     // k5_sample_flowedit: steps below fe_steps are FlowEdit steps, the rest plain steps on the target side
   int fe_steps = 0;
   bool fe_src_cfg = false;                  //   the source side runs its unconditional forward
@@ -2931,6 +2960,7 @@ struct SampleRun {
     ForwardCall f{&a->fwd, cond, t1000[i], x, d->cfg.in_visual_dim, vel, s};
     if (tables) { f.tvec = tvec; f.step = step_ctr; }
     f.text_slot = slot; f.vcond = vc; f.out_skip = skip_vel; f.cache_slot = cache_slot;
+    f.x_frame = x_frame; f.x_row = x_row; f.vc_frame = vc_frame; f.vc_row = vc_row;
     if (fe) d->fe.forwards += 1;
     // the forecast cache: step i's forwards are the plan's calls (i, slot); a plan of ones is off — plain forwards, counted as full calls
     if (d->fc.on && d->fc.mixed) { f.fc_step = i; f.fc_slot = slot; }
@@ -2978,6 +3008,11 @@ struct SampleRun {
     return K5_OK;
   }
 
+  int64_t tile_corner(int k) const {   // the cell of the whole clip at which window k = (it * ny + iy) * nx + ix of a 3-D plan begins
+    const int ix = k % tile->nx, iy = (k / tile->nx) % tile->ny, it = k / (tile->nx * tile->ny);
+    return ((int64_t)tile->starts_t[it] * tile->total_H + tile->starts_y[iy]) * tile->total_W + tile->starts_x[ix];
+  }
+
   int step(int i) {   // enqueue step i: the forwards, then CFG + Euler
     const k5_dit_config& c = d->cfg;
     d->enh.gate = d->enh.at(i) ? 1 : 0;   // Enhance-A-Video: this step's forwards apply it or enqueue what they always did
@@ -2989,8 +3024,11 @@ struct SampleRun {
       for (int k = 0; k < win->nwin; ++k) {
         const k5_text_cond& ck = win->conds ? win->conds[k] : a->fwd.cond;
         const k5_text_cond& uk = win->null_conds ? win->null_conds[k] : a->null_cond;
-        const float* xk = a->latent + (int64_t)win->starts[k] * frame;
-        const float* vk = vcond ? vcond + (int64_t)win->starts[k] * vframe : nullptr;
+        // where window k begins: whole frames for a temporal plan, the corner cell of its box for a 3-D one (the view strides do the rest)
+        const int64_t xoff = tile ? tile_corner(k) * c.out_visual_dim : (int64_t)win->starts[k] * frame;
+        const int64_t voff = tile ? tile_corner(k) * (c.in_visual_dim + 1) : (int64_t)win->starts[k] * vframe;
+        const float* xk = a->latent + xoff;
+        const float* vk = vcond ? vcond + voff : nullptr;
         if (slot_prompt[0] != ck.text_embed) { d->text_cache[0].valid = false; slot_prompt[0] = ck.text_embed; }
         K5CHK(forward(i, ck, 0, xk, static_cast<bf16_t*>(vel_c) + k * n, vk, false));
         if (cfg_on) {
@@ -2999,6 +3037,9 @@ struct SampleRun {
         }
       }
       Scope sc(d, s, "elementwise");
+      if (tile)
+        return k5_launch_cfg_euler_tiles(a->latent, vel_c, vu, a->guidance_weight, dt[i], tile_dev, tile->total_T, tile->total_H, tile->total_W,
+                                         c.out_visual_dim, s);
       K5CHK(k5_launch_cfg_euler_windows(a->latent, vel_c, vu, a->guidance_weight, dt[i], win_starts, win_weights, win->nwin, a->fwd.T,
                                         win->total_T, frame, s));
       return K5_OK;
@@ -3120,7 +3161,8 @@ int k5_dit::Watch::deliver(const SampleRun& r, int i) {
   info.sigma_next = r.sigma_next[i];
   info.rgb = pv ? h_rgb[slot] : nullptr;
   info.x0 = pv && want_x0 ? x0[slot].as<float>() : nullptr;
-  info.T = r.win ? r.win->total_T : r.a->fwd.T; info.H = r.a->fwd.H; info.W = r.a->fwd.W; info.C = r.d->cfg.in_visual_dim;
+  info.T = r.win ? r.win->total_T : r.a->fwd.T; info.H = r.tile ? r.tile->total_H : r.a->fwd.H; info.W = r.tile ? r.tile->total_W : r.a->fwd.W;
+  info.C = r.d->cfg.in_visual_dim;
   if (fn(user, &info) != 0) stopped = 1;
   return K5_OK;
 }
@@ -3135,13 +3177,14 @@ int k5_dit::Watch::end(const SampleRun& r) {   // the last step's callback; a st
 // The sampler loop behind k5_sample / k5_sample_cond (edit == nullptr: their launches, their bits), k5_sample_edit and k5_sample_windows
 // (win != nullptr: a->fwd is the window, a->latent / vcond the whole clip of win->total_T frames; never together with edit).
 static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream, const char* who,
-                       const k5_sample_windows_args* win = nullptr, const k5_flowedit_args* fe = nullptr) {
+                       const k5_sample_windows_args* win = nullptr, const k5_flowedit_args* fe = nullptr,
+                       const k5_sample_tiles_args* tile = nullptr) {
   g_err[0] = 0;
-  K5CHK(sample_refusals(d, a, vcond, edit, win, who, fe));
+  K5CHK(sample_refusals(d, a, vcond, edit, win, who, fe, tile));
   const k5_dit_config& c = d->cfg;
   k5_dit::Watch& wt = d->watch;
   SampleRun r{d, a, vcond, edit, win};
-  r.fe = fe;
+  r.fe = fe; r.tile = tile;
   r.s = (hipStream_t)stream;
   r.cells = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W;
   r.n = r.cells * c.out_visual_dim;
@@ -3239,7 +3282,29 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     Scope sc(d, s, "elementwise");
     K5CHK(k5_launch_edit_renoise(a->latent, edit->source, edit->noise, a->sigmas[0], r.n, s));
   }
-  if (win) {   // the plan, uploaded once per call: [nwin] int32 starts, then [nwin][F] fp32 weights
+  if (tile) {   // the 3-D plan, uploaded once per call: the three int32 start vectors, then the three fp32 weight tables
+    const int cnt[3] = {tile->nt, tile->ny, tile->nx}, ext[3] = {a->fwd.T, a->fwd.H, a->fwd.W};
+    const int32_t* st[3] = {tile->starts_t, tile->starts_y, tile->starts_x};
+    const float* wg[3] = {tile->wt, tile->wy, tile->wx};
+    std::vector<int32_t> host((size_t)cnt[0] + cnt[1] + cnt[2]);
+    size_t at = 0, off[6];
+    for (int i = 0; i < 3; ++i) { off[i] = at; memcpy(host.data() + at, st[i], (size_t)cnt[i] * 4); at += cnt[i]; }
+    for (int i = 0; i < 3; ++i) {
+      off[3 + i] = at;
+      host.resize(at + (size_t)cnt[i] * ext[i]);
+      memcpy(host.data() + at, wg[i], (size_t)cnt[i] * ext[i] * 4);
+      at += (size_t)cnt[i] * ext[i];
+    }
+    K5CHK(d->ws_win.ensure(host.size() * 4));
+    HIPCHK(hipMemcpyAsync(d->ws_win.p, host.data(), host.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));   // `host` lives in this block only
+    const int32_t* base = d->ws_win.as<int32_t>();
+    r.tile_dev = k5_tile_plan{tile->nt, tile->ny, tile->nx, a->fwd.T, a->fwd.H, a->fwd.W, base + off[0], base + off[1], base + off[2],
+                              reinterpret_cast<const float*>(base + off[3]), reinterpret_cast<const float*>(base + off[4]),
+                              reinterpret_cast<const float*>(base + off[5])};
+    r.x_row = (int64_t)tile->total_W * c.out_visual_dim; r.x_frame = r.x_row * tile->total_H;
+    r.vc_row = (int64_t)tile->total_W * (c.in_visual_dim + 1); r.vc_frame = r.vc_row * tile->total_H;
+  } else if (win) {   // the plan, uploaded once per call: [nwin] int32 starts, then [nwin][F] fp32 weights
     const size_t sb = (size_t)win->nwin * 4, wb = (size_t)win->nwin * a->fwd.T * 4;
     K5CHK(d->ws_win.ensure(sb + wb));
     HIPCHK(hipMemcpyAsync(d->ws_win.p, win->starts, sb, hipMemcpyHostToDevice, s));
@@ -3355,6 +3420,32 @@ extern "C" int k5_sample_windows(k5_dit* d, const k5_sample_windows_args* w, con
     return sample_impl(d, &one, vcond, nullptr, stream, "k5_sample_windows");
   }
   return sample_impl(d, &w->sample, vcond, nullptr, stream, "k5_sample_windows", w);
+}
+
+extern "C" int k5_sample_tiles(k5_dit* d, const k5_sample_tiles_args* t, const float* vcond, void* stream) {
+  g_err[0] = 0;
+  if (!d || !t) { k5_set_error("k5_sample_tiles: null handle or arguments"); return K5_ERR_ARG; }
+  if (t->total_T < 1 || t->total_H < 1 || t->total_W < 1) {
+    k5_set_error("k5_sample_tiles: the clip must be >= 1 in every axis (got %d, %d, %d)", t->total_T, t->total_H, t->total_W);
+    return K5_ERR_ARG;
+  }
+  const k5_forward_args& f = t->sample.fwd;
+  if (t->total_T <= f.T && t->total_H <= f.H && t->total_W <= f.W) {   // one window: the plain run on the whole clip (the first entries of pos_* are its positions)
+    k5_sample_args one = t->sample;
+    one.fwd.T = t->total_T; one.fwd.H = t->total_H; one.fwd.W = t->total_W;
+    if (t->conds) one.fwd.cond = t->conds[0];
+    if (t->null_conds) one.null_cond = t->null_conds[0];
+    return sample_impl(d, &one, vcond, nullptr, stream, "k5_sample_tiles");
+  }
+  // what sample_impl reads of a windowed run whatever its plan: the window count, the clip's frames, the prompts
+  const auto count = [](int n) { return n >= 1 && n <= 64; };   // nwin = 0 where a count is out of range: the plan check names it
+  const int nwin = count(t->nt) && count(t->ny) && count(t->nx) ? t->nt * t->ny * t->nx : 0;
+  k5_sample_windows_args w{t->sample, t->total_T, nwin, t->starts_t, t->wt, t->conds, t->null_conds};
+  if (t->ny == 1 && t->nx == 1 && t->total_H == f.H && t->total_W == f.W) {   // a temporal plan: k5_sample_windows' launches
+    w.nwin = t->nt;
+    return sample_impl(d, &w.sample, vcond, nullptr, stream, "k5_sample_tiles", &w);
+  }
+  return sample_impl(d, &w.sample, vcond, nullptr, stream, "k5_sample_tiles", &w, nullptr, t);
 }
 
 // What k5_sample_many / k5_dit_forward_many refuse before anything is enqueued: handle states whose per-call bookkeeping is not per sample (rank

@@ -363,6 +363,14 @@ int k5_patchify_cond_bf16(const float* x, const float* vcond, void* out, int T, 
              "k5_patchify_cond_bf16");
 }
 
+int k5_patchify_view_bf16(const float* x, int64_t x_frame_stride, int64_t x_row_stride, const float* vcond, int64_t vc_frame_stride,
+                          int64_t vc_row_stride, void* out, int T, int H, int W, int x_channels, int Cin_total, int Kpad,
+                          const int32_t* tok_perm, void* stream) {
+  return ret(k5_launch_patchify_view(x, x_frame_stride, x_row_stride, vcond, vc_frame_stride, vc_row_stride, out, T, H, W, x_channels,
+                                     Cin_total, Kpad, tok_perm, (hipStream_t)stream),
+             "k5_patchify_view_bf16");
+}
+
 int k5_unpatchify_bf16(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx, const int32_t* tok_perm,
                        void* stream) {
   return ret(k5_launch_unpatchify(x, out, T, Hp, Wp, C, ldx, tok_perm, (hipStream_t)stream), "k5_unpatchify_bf16");
@@ -524,6 +532,36 @@ int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, f
     }
   return ret(k5_launch_cfg_euler_windows(img, v_cond, v_uncond, w, dt, starts_dev, weights_dev, nwin, F, T, frame_elems, s),
              "k5_cfg_euler_windows");
+}
+
+int k5_cfg_euler_tiles(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const k5_tile_plan* p, int T, int H, int W, int C,
+                       void* stream) {
+  if (!img || !v_cond || !p || !p->starts_t || !p->starts_y || !p->starts_x || !p->wt || !p->wy || !p->wx) {
+    k5_set_error("k5_cfg_euler_tiles: null pointer (img, v_cond, the plan or one of its six tables)");
+    return K5_ERR_ARG;
+  }
+  if (T < 1 || H < 1 || W < 1 || C < 1 || p->Ft < 1 || p->Fh < 1 || p->Fw < 1) {
+    k5_set_error("k5_cfg_euler_tiles: the clip (%d, %d, %d, %d) and the window (%d, %d, %d) must be >= 1", T, H, W, C, p->Ft, p->Fh, p->Fw);
+    return K5_ERR_ARG;
+  }
+  if (p->nt < 1 || p->ny < 1 || p->nx < 1 || p->nt > 64 || p->ny > 64 || p->nx > 64 || p->nt * p->ny * p->nx > 64) {
+    k5_set_error("k5_cfg_euler_tiles: nwin must be 1..64 (got %d x %d x %d)", p->nt, p->ny, p->nx);
+    return K5_ERR_ARG;
+  }
+  // the plan is checked on the host: the three start vectors come back once (this entry is the per-step paths' and the tests'; k5_sample_tiles holds its plan on the host)
+  int32_t st[3][64];
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpyAsync(st[0], p->starts_t, (size_t)p->nt * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(st[1], p->starts_y, (size_t)p->ny * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(st[2], p->starts_x, (size_t)p->nx * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return ret(K5_ERR_HIP, "k5_cfg_euler_tiles");
+  const struct { const char* name; int n, F, total; } ax[3] = {{"frame", p->nt, p->Ft, T}, {"row", p->ny, p->Fh, H}, {"column", p->nx, p->Fw, W}};
+  for (int i = 0; i < 3; ++i)
+    if (const char* why = k5_tile_axis_refusal(ax[i].name, ax[i].n, st[i], ax[i].F, ax[i].total)) {
+      k5_set_error("k5_cfg_euler_tiles: %s", why);
+      return K5_ERR_ARG;
+    }
+  return ret(k5_launch_cfg_euler_tiles(img, v_cond, v_uncond, w, dt, *p, T, H, W, C, s), "k5_cfg_euler_tiles");
 }
 
 int k5_x0_preview(const float* x, const void* v_cond, const void* v_uncond, float w, float sigma_next, const float* source,

@@ -170,6 +170,11 @@ int k5_launch_patchify(const float* x, void* out, int T, int H, int W, int C, in
 // latent and mask); the same bits as k5_launch_patchify on the concatenated tensor
 int k5_launch_patchify_cond(const float* x, const float* vcond, void* out, int T, int H, int W, int C, int Cin_total, int Kpad,
                             const int32_t* tok_perm, hipStream_t stream);
+// patchify of a (T,H,W) box inside a larger tensor: x with its own frame and row strides (elements; cells of a row C apart), vcond (nullable:
+// the conditioning channels are then zero) with its own.  Compact strides give k5_launch_patchify / k5_launch_patchify_cond bit for bit; only
+// cells of the box are read.  K5_ERR_ARG, nothing launched: what they refuse, and a row stride < W cells or a frame stride < H rows.
+int k5_launch_patchify_view(const float* x, int64_t x_frame, int64_t x_row, const float* vcond, int64_t vc_frame, int64_t vc_row, void* out,
+                            int T, int H, int W, int C, int Cin_total, int Kpad, const int32_t* tok_perm, hipStream_t stream);
 // un-patchify (K17 tail): [Ntok][C*4] bf16 (feature order c,ph,pw) -> (T,H,W,C) bf16, token perm optional
 int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx,
                          const int32_t* tok_perm, hipStream_t stream);
@@ -212,6 +217,15 @@ int k5_launch_guidance_coeffs(const void* v_cond, const void* v_uncond, int64_t 
 // 16-byte latent accesses when frame_elems % 4 == 0 and img is 16-byte, the velocities 8-byte aligned.  A frame without a window stays as it is.
 int k5_launch_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts,
                                 const float* weights, int nwin, int F, int T, int64_t frame_elems, hipStream_t stream);
+// One axis of a tile plan on the HOST: n windows of F at starts[] over 0 .. total - 1.  nullptr when the starts ascend, every window lies inside
+// and every coordinate is covered; otherwise what is wrong, in words (a thread-local buffer).
+const char* k5_tile_axis_refusal(const char* axis, int n, const int32_t* starts, int F, int total);
+// K18 over a 3-D plan of context windows (tiles): img fp32 (T,H,W,C); v_cond / v_uncond (null = no guidance) bf16 [nwin][Ft][Fh][Fw][C]; the
+// plan's tables on the device.  The rule is written once, at k5_cfg_euler_tiles in include/k5.h.  A lane owns four channels of a cell when
+// C % 4 == 0 and img is 16-byte, the velocities 8-byte aligned; otherwise one.  A cell without a window stays as it is; only slots inside a
+// window's box are read.  K5_ERR_ARG, nothing launched: a null pointer, a count or extent < 1, nt * ny * nx > 64, T * H or W * C beyond an int.
+int k5_launch_cfg_euler_tiles(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const k5_tile_plan& plan, int T, int H,
+                              int W, int C, hipStream_t stream);
 // sampler preview: with v combined as in K18, x0 = x - sigma_next * v (fp32, uncontracted; keep_blend(x0, source, m) under a keep mask) on cells * C
 // elements, optionally stored as fp32 (x0_out), and rgb[cell][j] = sat_u8(rint((b[j] + sum_k W[k][j] x0[k]) * 127.5 + 127.5)), NaN -> 0, with
 // W [C][3] / b [3] (null = zeros) fp32 on the device.  rgb and rgb_w come together or not at all; one of rgb / x0_out is needed.  C % 4 == 0 and

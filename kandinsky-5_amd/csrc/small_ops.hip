@@ -590,6 +590,30 @@ __global__ __launch_bounds__(256) void patchify_cond_kernel(const float* __restr
   }
 }
 
+__global__ __launch_bounds__(256) void patchify_view_kernel(const float* __restrict__ x, int64_t xf, int64_t xr,
+                                                            const float* __restrict__ vc, int64_t vf, int64_t vr,
+                                                            bf16_t* __restrict__ out, int T, int H, int W, int Cx, int Cin, int Kpad,
+                                                            const int32_t* __restrict__ tok_perm) {
+  // patchify_kernel / patchify_cond_kernel on a (T,H,W) box inside a larger tensor: x has frame stride xf and row stride xr (elements; a row's
+  // cells are Cx apart), vc (nullable; then the channels [Cx, Cin) are zero) has vf, vr and cells Cin - Cx apart.  Reads only cells of the box.
+  const int Hp = H / 2, Wp = W / 2, Cv = Cin - Cx;
+  const int64_t total = (int64_t)T * Hp * Wp * Kpad;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
+    const int f = (int)(g % Kpad);
+    const int64_t row = g / Kpad;
+    float v = 0.f;
+    if (f < 4 * Cin) {
+      const int64_t tok = tok_perm ? tok_perm[row] : row;
+      const int wp = (int)(tok % Wp), hp = (int)((tok / Wp) % Hp), t = (int)(tok / ((int64_t)Wp * Hp));
+      const int c = f % Cin, pp = f / Cin, ph = pp >> 1, pw = pp & 1;
+      const int r = 2 * hp + ph, col = 2 * wp + pw;
+      if (c < Cx) v = x[(int64_t)t * xf + (int64_t)r * xr + (int64_t)col * Cx + c];
+      else if (vc) v = vc[(int64_t)t * vf + (int64_t)r * vr + (int64_t)col * Cv + (c - Cx)];
+    }
+    out[g] = f2bf(v);
+  }
+}
+
 __global__ __launch_bounds__(256) void unpatchify_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ out, int T,
                                                          int Hp, int Wp, int C, int ldx, const int32_t* __restrict__ tok_perm) {
   // x [Ntok][C*4] feature (c, ph, pw) -> out (T, 2Hp, 2Wp, C)
@@ -1055,6 +1079,91 @@ __global__ __launch_bounds__(256) void cfg_euler_windows_kernel(float* __restric
   }
 }
 
+// Spatial context windows (tiles): the share of window (it, iy, ix) at a cell is the product of its three per-axis weights, left to right, each
+// product rounded to fp32 on its own (the pragma: see renoise_at)
+__device__ __forceinline__ float tile_share(float wt, float wy, float wx) {
+#pragma clang fp contract(off)
+  const float ty = wt * wy;
+  return ty * wx;
+}
+
+// The windows of one axis that cover coordinate p: starts ascend, window i spans starts[i] .. starts[i] + F - 1, so the covering windows are
+// the contiguous range [lo, hi).  n <= 64; with a workgroup-uniform p (a row's frame and row index) the loop is scalar loads and compares.
+__device__ __forceinline__ void covering(const int32_t* __restrict__ starts, int n, int F, int p, int& lo, int& hi) {
+  lo = n; hi = 0;
+  for (int i = 0; i < n; ++i) {
+    const int j = p - starts[i];
+    if (j >= 0 && j < F) { lo = i < lo ? i : lo; hi = i + 1; }
+  }
+}
+
+// cfg_euler_windows_kernel over a 3-D plan: img fp32 (T,H,W,C), vc / vu bf16 [nwin][Ft][Fh][Fw][C], window k = (it * ny + iy) * nx + ix at
+// (st[it], sy[iy], sx[ix]).  A workgroup takes whole rows (t, y) of the latent, grid-stride: the frame and row ranges of covering windows,
+// their weights and local indices are the workgroup's (scalar), no lane divides a 64-bit index.  Inside a row a lane owns VEC consecutive
+// channels of one cell (VEC divides C), walks the windows that cover the cell in ascending k — a product of three contiguous index ranges —
+// forms v_k with cfg_velocity, blends with window_term under the share tile_share(wt, wy, wx) and applies img += bf16(dt * acc).  Only slots
+// inside a window's box are read, whatever the tables hold; a cell no window covers is left as it is.
+template <int VEC>
+__global__ __launch_bounds__(256) void cfg_euler_tiles_kernel(float* __restrict__ img, const bf16_t* __restrict__ vc,
+                                                              const bf16_t* __restrict__ vu, float w, float dt, k5_tile_plan p, int T, int H,
+                                                              int W, int C) {
+  const int per_cell = C / VEC, units = W * per_cell, rows = T * H;   // a row's lane-sized pieces; the launcher keeps both products in an int
+  for (int row = blockIdx.x; row < rows; row += gridDim.x) {
+    const int t = row / H, y = row - t * H;
+    int t_lo, t_hi, y_lo, y_hi;
+    covering(p.starts_t, p.nt, p.Ft, t, t_lo, t_hi);
+    covering(p.starts_y, p.ny, p.Fh, y, y_lo, y_hi);
+    for (int u = threadIdx.x; u < units; u += 256) {
+      const int x = u / per_cell, c = (u - x * per_cell) * VEC;
+      int x_lo, x_hi;
+      covering(p.starts_x, p.nx, p.Fw, x, x_lo, x_hi);
+      float acc[VEC];
+      bool first = true;
+      for (int it = t_lo; it < t_hi; ++it) {
+        const int jt = t - p.starts_t[it];
+        const float wt = p.wt[it * p.Ft + jt];
+        for (int iy = y_lo; iy < y_hi; ++iy) {
+          const int jy = y - p.starts_y[iy];
+          const float wy = p.wy[iy * p.Fh + jy];
+          const int64_t slot_row = (((int64_t)it * p.ny + iy) * p.nx * p.Ft + jt) * p.Fh + jy;   // of window (it, iy, 0); one window further: Ft * Fh rows
+          for (int ix = x_lo; ix < x_hi; ++ix) {
+            const int jx = x - p.starts_x[ix];
+            const float share = tile_share(wt, wy, p.wx[ix * p.Fw + jx]);
+            const int64_t off = ((slot_row + (int64_t)ix * p.Ft * p.Fh) * p.Fw + jx) * C + c;
+            float v[VEC];
+            if constexpr (VEC == 4) {
+              const u32x2 cr = *reinterpret_cast<const u32x2*>(vc + off);
+              u32x2 ur = {0u, 0u};
+              if (vu) ur = *reinterpret_cast<const u32x2*>(vu + off);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                v[e] = bf16_at(cr, e);
+                if (vu) v[e] = cfg_velocity(w, v[e], bf16_at(ur, e));
+              }
+            } else {
+              v[0] = bf2f(vc[off]);
+              if (vu) v[0] = cfg_velocity(w, v[0], bf2f(vu[off]));
+            }
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[e] = window_term(first ? 0.0f : acc[e], share, v[e], first);
+            first = false;
+          }
+        }
+      }
+      if (first) continue;
+      float* q = img + ((int64_t)row * W + x) * C + c;
+      if constexpr (VEC == 4) {
+        f32x4 r = *reinterpret_cast<const f32x4*>(q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) r[e] = __fadd_rn(r[e], bf_round(__fmul_rn(dt, acc[e])));
+        *reinterpret_cast<f32x4*>(q) = r;
+      } else {
+        q[0] = __fadd_rn(q[0], bf_round(__fmul_rn(dt, acc[0])));
+      }
+    }
+  }
+}
+
 __global__ void step_inc_kernel(int* step) { *step += 1; }
 
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, int64_t n) {
@@ -1278,6 +1387,19 @@ int k5_launch_patchify_cond(const float* x, const float* vcond, void* out, int T
   return done();
 }
 
+int k5_launch_patchify_view(const float* x, int64_t x_frame, int64_t x_row, const float* vcond, int64_t vc_frame, int64_t vc_row, void* out,
+                            int T, int H, int W, int C, int Cin_total, int Kpad, const int32_t* tok_perm, hipStream_t s) {
+  if (!x || !out || T <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || Kpad < 4 * Cin_total || C <= 0 || C > Cin_total) return K5_ERR_ARG;
+  if (vcond && C >= Cin_total) return K5_ERR_ARG;
+  // a stride spans the extent below it: a row holds W cells, a frame H rows
+  if (x_row < (int64_t)W * C || x_frame < (int64_t)H * x_row) return K5_ERR_ARG;
+  if (vcond && (vc_row < (int64_t)W * (Cin_total - C) || vc_frame < (int64_t)H * vc_row)) return K5_ERR_ARG;
+  const int64_t total = (int64_t)T * (H / 2) * (W / 2) * Kpad;
+  hipLaunchKernelGGL(patchify_view_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, x_frame, x_row, vcond, vc_frame, vc_row, (bf16_t*)out, T,
+                     H, W, C, Cin_total, Kpad, tok_perm);
+  return done();
+}
+
 int k5_launch_unpatchify(const void* x, void* out, int T, int Hp, int Wp, int C, int ldx, const int32_t* tok_perm,
                          hipStream_t s) {
   if (!x || !out || T <= 0 || Hp <= 0 || Wp <= 0 || C <= 0 || ldx < 4 * (int64_t)C) return K5_ERR_ARG;   // every extent on its own, not their product
@@ -1389,6 +1511,43 @@ int k5_launch_cfg_euler_windows(float* img, const void* vc, const void* vu, floa
   else
     hipLaunchKernelGGL(cfg_euler_windows_kernel<1>, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, w, dt, starts,
                        weights, nwin, F, T, frame_elems);
+  return done();
+}
+
+const char* k5_tile_axis_refusal(const char* axis, int n, const int32_t* starts, int F, int total) {
+  static thread_local char msg[160];
+  if (n < 1 || F < 1 || total < 1 || !starts) { snprintf(msg, sizeof msg, "%s: %d windows of %d in %d, or no starts", axis, n, F, total); return msg; }
+  for (int i = 0; i < n; ++i) {
+    const int st = starts[i];
+    if (st < 0 || (int64_t)st + F > total) {
+      snprintf(msg, sizeof msg, "%s window %d (%d .. %lld) reaches outside 0 .. %d", axis, i, st, (long long)st + F - 1, total - 1);
+      return msg;
+    }
+    if (i > 0 && st <= starts[i - 1]) { snprintf(msg, sizeof msg, "%s starts must ascend (starts[%d] = %d after %d)", axis, i, st, starts[i - 1]); return msg; }
+    const int covered_to = i == 0 ? 0 : starts[i - 1] + F;   // the first coordinate the windows before i leave uncovered
+    if (st > covered_to) { snprintf(msg, sizeof msg, "no %s window covers %d", axis, covered_to); return msg; }
+  }
+  if (starts[n - 1] + F < total) { snprintf(msg, sizeof msg, "no %s window covers %d", axis, starts[n - 1] + F); return msg; }
+  return nullptr;
+}
+
+int k5_launch_cfg_euler_tiles(float* img, const void* vc, const void* vu, float w, float dt, const k5_tile_plan& p, int T, int H, int W, int C,
+                              hipStream_t s) {
+  if (!img || !vc || !p.starts_t || !p.starts_y || !p.starts_x || !p.wt || !p.wy || !p.wx) return K5_ERR_ARG;
+  if (p.nt < 1 || p.ny < 1 || p.nx < 1 || p.Ft < 1 || p.Fh < 1 || p.Fw < 1 || T < 1 || H < 1 || W < 1 || C < 1) return K5_ERR_ARG;
+  if ((int64_t)p.nt * p.ny * p.nx > 64) return K5_ERR_ARG;
+  if ((int64_t)T * H > 0x7fffffff || (int64_t)W * C > 0x7fffffff) return K5_ERR_ARG;   // the kernel counts rows, and a row's elements, in an int
+  const auto misaligned = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) != 0; };
+  if (misaligned(img, 4) || misaligned(vc, 2) || misaligned(vu, 2) || misaligned(p.starts_t, 4) || misaligned(p.starts_y, 4) ||
+      misaligned(p.starts_x, 4) || misaligned(p.wt, 4) || misaligned(p.wy, 4) || misaligned(p.wx, 4))
+    return K5_ERR_ARG;
+  // a lane owns four channels of one cell: 16-byte latent accesses, 8-byte velocity accesses, when C is whole groups of four and the bases allow it
+  const bool vec = (C & 3) == 0 && !misaligned(img, 16) && !misaligned(vc, 8) && !misaligned(vu, 8);
+  const int64_t n = (int64_t)T * H * 256;   // a workgroup per row of cells
+  if (vec)
+    hipLaunchKernelGGL(cfg_euler_tiles_kernel<4>, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, w, dt, p, T, H, W, C);
+  else
+    hipLaunchKernelGGL(cfg_euler_tiles_kernel<1>, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, w, dt, p, T, H, W, C);
   return done();
 }
 

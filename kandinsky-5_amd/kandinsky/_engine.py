@@ -59,6 +59,20 @@ class SampleWindowsArgs(C.Structure):   # k5_sample_windows_args
                 ("weights", C.POINTER(C.c_float)), ("conds", C.POINTER(TextCond)), ("null_conds", C.POINTER(TextCond))]
 
 
+class TilePlan(C.Structure):   # k5_tile_plan: the tables are device memory
+    _fields_ = [("nt", C.c_int), ("ny", C.c_int), ("nx", C.c_int), ("Ft", C.c_int), ("Fh", C.c_int), ("Fw", C.c_int),
+                ("starts_t", C.c_void_p), ("starts_y", C.c_void_p), ("starts_x", C.c_void_p),
+                ("wt", C.c_void_p), ("wy", C.c_void_p), ("wx", C.c_void_p)]
+
+
+class SampleTilesArgs(C.Structure):   # k5_sample_tiles_args: the tables are host memory
+    _fields_ = [("sample", SampleArgs), ("total_T", C.c_int), ("total_H", C.c_int), ("total_W", C.c_int),
+                ("nt", C.c_int), ("ny", C.c_int), ("nx", C.c_int),
+                ("starts_t", C.POINTER(C.c_int32)), ("starts_y", C.POINTER(C.c_int32)), ("starts_x", C.POINTER(C.c_int32)),
+                ("wt", C.POINTER(C.c_float)), ("wy", C.POINTER(C.c_float)), ("wx", C.POINTER(C.c_float)),
+                ("conds", C.POINTER(TextCond)), ("null_conds", C.POINTER(TextCond))]
+
+
 class EditArgs(C.Structure):
     _fields_ = [("source", C.c_void_p), ("noise", C.c_void_p), ("keep_mask", C.c_void_p)]
 
@@ -264,6 +278,9 @@ SYMBOLS = {
     "k5_dit_stochastic_state": (_I, [_P, C.POINTER(_I), C.POINTER(C.c_longlong), _I]),
     "k5_cfg_euler_windows": (_I, [_P, _P, _P, _F, _F, _P, _P, _I, _I, _I, _I64, _P]),
     "k5_sample_windows": (_I, [_P, C.POINTER(SampleWindowsArgs), _P, _P]),
+    "k5_cfg_euler_tiles": (_I, [_P, _P, _P, _F, _F, C.POINTER(TilePlan), _I, _I, _I, _I, _P]),
+    "k5_patchify_view_bf16": (_I, [_P, _I64, _I64, _P, _I64, _I64, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "k5_sample_tiles": (_I, [_P, C.POINTER(SampleTilesArgs), _P, _P]),
     "k5_x0_preview": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I64, _I, _P]),
     "k5_dit_set_watch": (_I, [_P, C.POINTER(Watch)]),
     "k5_dit_watch_state": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
@@ -650,6 +667,71 @@ def cfg_euler_windows_(img, v_cond, v_uncond, w, dt, starts, weights):
     check(lib().k5_cfg_euler_windows(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), ptr(starts), ptr(weights), int(nwin), int(F),
                                      int(T), int(frame), stream_ptr(img.device)), "k5_cfg_euler_windows")
     return img
+
+
+class TileTables:
+    """The plan of `generation_utils.tile_windows` as the device tables of `cfg_euler_tiles_`: `.plan` is the k5_tile_plan, `.window` =
+    (Ft, Fh, Fw), `.nwin`; the six tensors stay alive with the object."""
+
+    def __init__(self, starts, weights, device):
+        if len(starts) != 3 or len(weights) != 3:
+            raise ValueError("tile_tables: starts and weights hold one entry per axis (t, y, x)")
+        self.starts = [torch.tensor([int(v) for v in s], dtype=torch.int32, device=device) for s in starts]
+        self.weights = [torch.as_tensor(w, dtype=torch.float32).to(device).contiguous() for w in weights]
+        for s, w in zip(self.starts, self.weights):
+            if w.dim() != 2 or w.shape[0] != s.numel() or s.numel() < 1:
+                raise ValueError("tile_tables: the weights of an axis hold one row of F values per window of that axis")
+        self.counts = tuple(int(s.numel()) for s in self.starts)
+        self.window = tuple(int(w.shape[1]) for w in self.weights)
+        self.nwin = self.counts[0] * self.counts[1] * self.counts[2]
+        self.device = self.starts[0].device
+        self.plan = TilePlan(*self.counts, *self.window, *(ptr(s) for s in self.starts), *(ptr(w) for w in self.weights))
+
+
+def tile_tables(plan, device):
+    """`generation_utils.tile_windows`' plan (anything with `.starts` and `.weights`, one entry per axis t, y, x) on `device`: a TileTables."""
+    return TileTables(plan.starts, plan.weights, device)
+
+
+def cfg_euler_tiles_(img, v_cond, v_uncond, w, dt, tables):
+    """cfg_euler_ over a 3-D plan of context windows (k5_cfg_euler_tiles; the rule is written there in include/k5.h): img fp32 (T, H, W, C),
+    v_cond / v_uncond (None = no guidance) bf16 (nwin, Ft, Fh, Fw, C), `tables` a TileTables on img's device."""
+    _need_cuda(img, v_cond, v_uncond)
+    if img.dtype != torch.float32 or not img.is_contiguous() or img.dim() != 4:
+        raise ValueError("cfg_euler_tiles_: img must be a contiguous fp32 tensor (T, H, W, C)")
+    if not isinstance(tables, TileTables) or tables.device != img.device:
+        raise ValueError("cfg_euler_tiles_: tables must be the TileTables of `tile_tables` on img's device")
+    T, H, W, C_ = img.shape
+    n = tables.nwin * tables.window[0] * tables.window[1] * tables.window[2] * C_
+    for v in (v_cond, v_uncond):
+        if v is not None and (v.dtype != torch.bfloat16 or not v.is_contiguous() or v.numel() != n or v.device != img.device):
+            raise ValueError("cfg_euler_tiles_: the velocities must be contiguous bf16 tensors (nwin, Ft, Fh, Fw, C) on img's device")
+    with torch.cuda.device(img.device):
+        check(lib().k5_cfg_euler_tiles(ptr(img), ptr(v_cond), ptr(v_uncond), float(w), float(dt), C.byref(tables.plan), int(T), int(H), int(W),
+                                       int(C_), stream_ptr(img.device)), "k5_cfg_euler_tiles")
+    return img
+
+
+def patchify_view_(x, vcond, Cin_total, Kpad, tok_perm=None, out=None):
+    """Patchify of a strided view (k5_patchify_view_bf16): x fp32 (T, H, W, Cx), a box sliced out of a larger contiguous tensor (its channel
+    stride 1 and its column stride Cx), vcond (optional) likewise; channels up to Cin_total read as zero without one.  Returns bf16
+    [T * H/2 * W/2][Kpad], rows in `tok_perm` order (int32, optional)."""
+    _need_cuda(x, vcond, tok_perm, out)
+    for name, t in (("x", x), ("vcond", vcond)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
+            raise ValueError(f"patchify_view_: {name} must be an fp32 (T, H, W, C) view whose cells are contiguous and C apart along a row")
+    T, H, W, Cx = x.shape
+    if vcond is not None and (tuple(vcond.shape[:3]) != (T, H, W) or vcond.device != x.device):
+        raise ValueError("patchify_view_: vcond must cover the cells of x, on its device")
+    if out is None:
+        out = torch.empty((T * (H // 2) * (W // 2), int(Kpad)), dtype=torch.bfloat16, device=x.device)
+    vs = (0, 0) if vcond is None else (vcond.stride(0), vcond.stride(1))
+    with torch.cuda.device(x.device):
+        check(lib().k5_patchify_view_bf16(ptr(x), x.stride(0), x.stride(1), ptr(vcond), vs[0], vs[1], ptr(out), int(T), int(H), int(W), int(Cx),
+                                          int(Cin_total), int(Kpad), ptr(tok_perm), stream_ptr(x.device)), "k5_patchify_view_bf16")
+    return out
 
 
 def renoise(source, noise, sigma, out=None):

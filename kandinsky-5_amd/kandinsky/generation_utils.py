@@ -421,6 +421,53 @@ def context_windows(T, frames, overlap):
     return starts, weights
 
 
+class TileWindows:
+    """The plan of `tile_windows`: `clip` = (T, H, W) and `window` = (Ft, Fh, Fw) in latent cells (a window never exceeds the clip), `starts` =
+    (st, sy, sx) lists of cell starts, `weights` = (wt [nt][Ft], wy [ny][Fh], wx [nx][Fw]) float32 tensors, `counts` = (nt, ny, nx), `nwin`.
+    Window k = (it * ny + iy) * nx + ix: t-major, then rows, then columns."""
+
+    def __init__(self, clip, window, overlap, starts, weights):
+        self.clip, self.window, self.overlap, self.starts, self.weights = tuple(clip), tuple(window), tuple(overlap), tuple(starts), tuple(weights)
+        self.counts = tuple(len(s) for s in self.starts)
+        self.nwin = self.counts[0] * self.counts[1] * self.counts[2]
+
+    def corner(self, k):
+        """(t0, y0, x0): the cell at which window k begins."""
+        nt, ny, nx = self.counts
+        return self.starts[0][k // (ny * nx)], self.starts[1][(k // nx) % ny], self.starts[2][k % nx]
+
+    def box(self, k):
+        """The three slices of window k in the clip."""
+        return tuple(slice(s, s + f) for s, f in zip(self.corner(k), self.window))
+
+    def __repr__(self):
+        return f"TileWindows(clip={self.clip}, window={self.window}, overlap={self.overlap}, counts={self.counts})"
+
+
+def tile_windows(clip, window, overlap):
+    """The plan of a large clip sampled as overlapping windows in three axes: the product of three `context_windows` plans.  `clip` = (T, H, W),
+    `window` = (Ft, Fh, Fw), `overlap` = (ot, oh, ow), all in latent cells.  The temporal axis is planned in frames.  The two spatial axes are
+    planned in PATCHES of 2 cells — extents, windows and overlaps must be even — so `context_windows(H / 2, Fh / 2, oh / 2)` gives patch starts and
+    per-patch weights: a cell start is twice the patch start and both cells of a patch carry its weight.  An axis whose window is at least the
+    extent has one window of weight 1.  Each axis is normalised on its own, so the shares rn(rn(wt wy) wx) of a cell sum to 1 up to fp32
+    rounding.  ValueError for odd spatial sizes and for nwin = nt ny nx > 64.  Returns a TileWindows."""
+    (T, H, W), (Ft, Fh, Fw), (ot, oh, ow) = (tuple(int(v) for v in a) for a in (clip, window, overlap))
+    for name, v in (("H", H), ("W", W), ("window height", Fh), ("window width", Fw), ("overlap (rows)", oh), ("overlap (columns)", ow)):
+        if v & 1:
+            raise ValueError(f"tile_windows: {name} = {v} is odd: the spatial axes are planned in patches of 2 cells")
+    Ft, Fh, Fw = min(Ft, T), min(Fh, H), min(Fw, W)
+    st, wt = context_windows(T, Ft, ot if T > Ft else 0)
+    axes = []
+    for n, F, o in ((H, Fh, oh), (W, Fw, ow)):
+        ps, pw = context_windows(n // 2, F // 2, o // 2 if n > F else 0)
+        axes.append(([2 * s for s in ps], pw.repeat_interleave(2, dim=1).contiguous()))
+    plan = TileWindows((T, H, W), (Ft, Fh, Fw), (ot, oh, ow), (list(st), axes[0][0], axes[1][0]), (wt, axes[0][1], axes[1][1]))
+    if plan.nwin > 64:
+        raise ValueError(f"tile_windows: clip {plan.clip} as windows of {plan.window} with overlap {plan.overlap} needs nwin = "
+                         f"{plan.counts[0]} x {plan.counts[1]} x {plan.counts[2]} = {plan.nwin} windows, at most 64 are supported")
+    return plan
+
+
 def _context_plan(model, T, context_frames, context_overlap, context_text, init_latent, preview_every):
     """`generate`'s context keywords -> (F, starts, weights) or None for a plain run, with the ValueErrors of the combinations that are refused."""
     if context_frames is None:
@@ -444,6 +491,49 @@ def _context_plan(model, T, context_frames, context_overlap, context_text, init_
     if _is_multi_rank_engine(model) or getattr(model, "_cfg_parallel", None) is not None:
         raise ValueError("context_frames needs a single-rank model (no sequence-parallel group, no CFG pair)")
     return F, starts, weights
+
+
+def _even_down(v):
+    return int(v) // 2 * 2
+
+
+def _plan_for(model, clip, context, init_latent, preview_every):
+    """`generate`'s context keywords `context` = (frames, overlap, text, height, width, overlap_hw) for a sample of `clip` = (T, H, W) latent
+    cells -> `(plan, tiles)`: the temporal plan of `_context_plan` or None, and the TileWindows of a run with more than one window in a
+    spatial axis or None; never both.  Without the spatial keywords this is `_context_plan`; a spatial plan whose rows and columns are one
+    window each is the temporal plan of its first axis.  The refusals are `_context_plan`'s, raised before the model is touched."""
+    frames, overlap, text, height, width, overlap_hw = context
+    T, H, W = (int(v) for v in clip)
+    if height is None and width is None:
+        if overlap_hw is not None:
+            raise ValueError("context_overlap_hw needs context_height / context_width")
+        return _context_plan(model, T, frames, overlap, text, init_latent, preview_every), None
+    if overlap is not None and frames is None:
+        raise ValueError("context_overlap needs context_frames")
+    Ft = T if frames is None else min(int(frames), T)
+    Fh, Fw = (n if v is None else min(int(v), n) for v, n in ((height, H), (width, W)))
+    if overlap_hw is None:   # a quarter of the window, rounded down to even
+        oh, ow = _even_down(Fh // 4), _even_down(Fw // 4)
+    else:
+        oh, ow = (int(v) for v in ((overlap_hw, overlap_hw) if isinstance(overlap_hw, int) else overlap_hw))
+    ot = Ft // 4 if overlap is None else int(overlap)
+    tiles = tile_windows((T, H, W), (Ft, Fh, Fw), (ot, oh, ow))
+    if text is not None and len(text) != tiles.nwin:
+        raise ValueError(f"context_text holds {len(text)} prompts, the plan {tiles!r} has nwin = {tiles.nwin} windows")
+    if tiles.counts[1] == 1 and tiles.counts[2] == 1:   # rows and columns are whole: the temporal plan, on the temporal path
+        if tiles.nwin == 1:
+            return (None if text is None else (T, tiles.starts[0], tiles.weights[0])), None
+        return _context_plan(model, T, Ft, ot, text, init_latent, preview_every), None
+    what = "context_height / context_width"
+    if init_latent is not None:
+        raise ValueError(f"init_latent (editing) together with {what} is not supported")
+    if int(preview_every) > 0:
+        raise ValueError(f"preview_every > 0 together with {what} is not supported: the preview reads one velocity pair per cell")
+    if _has_magcache(model):
+        raise ValueError(f"{what} with MagCache: the ratio table is indexed by the call of a plain run")
+    if _is_multi_rank_engine(model) or getattr(model, "_cfg_parallel", None) is not None:
+        raise ValueError(f"{what} needs a single-rank model (no sequence-parallel group, no CFG pair)")
+    return None, tiles
 
 
 def _has_magcache(model):
@@ -625,8 +715,17 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
              guidance_schedule=None, guidance_interval=None, cfg_zero_star=False, cfg_zero_init=0, cfg_rescale=0.0,
              slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0, sde_interval=None, sde_seed=None,
              enhance_weight=None, enhance_interval=None, forecast_interval=None, forecast_order=1, forecast_warmup=None, forecast_tail=1,
-             source_text_embeds=None, source_text_rope_pos=None, source_guidance_weight=None, flowedit_refine=0, flowedit_seed=None):
+             source_text_embeds=None, source_text_rope_pos=None, source_guidance_weight=None, flowedit_refine=0, flowedit_seed=None,
+             context_height=None, context_width=None, context_overlap_hw=None):
     """reference generation_utils.py:80-129.  `noise` (optional, extension) overrides the seeded draw.
+    `context_height`, `context_width`, `context_overlap_hw` (optional, extension): a frame larger than the model's trained size, next to
+    `context_frames` / `context_overlap` and in the same unit, latent cells.  The sample runs at every step on the overlapping windows of
+    `tile_windows((T, H, W), (context_frames, context_height, context_width), overlaps)` — `context_overlap_hw` an int or a (rows, columns)
+    pair, default a quarter of the window rounded down to even — each window with the first entries of `visual_rope_pos` as its positions,
+    and one k5_cfg_euler_tiles pass cross-fades the windows' velocities into the update.  `context_text` is then one prompt per window of
+    the 3-D plan (t-major, rows, columns).  The engine-backed model runs the whole loop in one call (k5_sample_tiles), any other callable
+    runs each forward on a contiguous copy of its window and gives the same bits.  Refused in the combinations `context_frames` refuses;
+    a plan whose rows and columns are one window each is the `context_frames` run, bit for bit.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
     `batch` (extension): `shape` = (batch*T, H, W, C) holds `batch` samples of T frames, sample b = frames [bT, (b+1)T) of the
@@ -737,8 +836,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     if batch < 1 or shape[0] % batch:
         raise ValueError(f"shape[0] = {shape[0]} frames do not divide into batch={batch} samples")
     _check_edit_args(model, shape, init_latent, strength, keep_mask)
-    context = (context_frames, context_overlap, context_text)
-    plan = _context_plan(model, shape[0] // batch, *context, init_latent, preview_every)
+    context = (context_frames, context_overlap, context_text, context_height, context_width, context_overlap_hw)
+    plan, tiles = _plan_for(model, (shape[0] // batch, shape[1], shape[2]), context, init_latent, preview_every)
     many = any(isinstance(v, (list, tuple)) for v in (text_embeds, null_text_embeds))
     if batch == 1 and many:
         text_embeds, null_text_embeds, text_rope_pos, null_text_rope_pos = (
@@ -748,7 +847,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     steps_run = num_steps - first
     guide_kw = (guidance_schedule, guidance_interval, cfg_zero_star, cfg_zero_init, cfg_rescale)
     guide = skip = None
-    windowed = plan is not None and len(plan[1]) > 1
+    windowed = tiles is not None or (plan is not None and len(plan[1]) > 1)
     wants_guide = any(v is not None for v in guide_kw[:2]) or any(guide_kw[2:])
     wants_skip = slg_blocks is not None or slg_scale or slg_interval is not None
     sto = None
@@ -767,7 +866,8 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     if wants_sto:
         sto = _stochastic_for_run(model, sigmas, first, eta, s_noise, sde_interval, seed if sde_seed is None else sde_seed, windowed, preview_every)
     if wants_enhance:
-        enhance = _enhance_for_run(model, sigmas, first, enhance_weight, enhance_interval, plan[0] if windowed else shape[0] // batch)
+        enhance = _enhance_for_run(model, sigmas, first, enhance_weight, enhance_interval,
+                                   tiles.window[0] if tiles is not None else plan[0] if windowed else shape[0] // batch)
     forecast = _forecast_for_run(model, steps_run, forecast_interval, forecast_order, forecast_warmup, forecast_tail, guide, skip, windowed)
     flow = _flowedit_for_run(model, num_steps, strength, init_latent, keep_mask, guidance_weight, seed, source_text_embeds, source_text_rope_pos,
                              source_guidance_weight, flowedit_refine, flowedit_seed,
@@ -793,20 +893,25 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
             what = (context, visual_cond, visual_cond_mask, init_latent, strength, keep_mask)
             if batch > 1:
                 return _generate_batch(*run, batch, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast, flow=flow)
-            return _generate_one(*run, plan, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast, flow=flow)
+            return _generate_one(*run, plan, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast, flow=flow, tiles=tiles)
         finally:
             watch.close()
 
 
 def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                   guidance_weight, scheduler_scale, conf, watch, plan, context, visual_cond, visual_cond_mask, init_latent, strength,
-                  keep_mask, guide=None, skip=None, sto=None, enhance=None, forecast=None, flow=None):
+                  keep_mask, guide=None, skip=None, sto=None, enhance=None, forecast=None, flow=None, tiles=None):
     """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch`, the checked `plan` of
     `_context_plan`, the checked guidance plan `guide` of `_guidance_for_run`, the checked skip set `skip` of `_skip_for_run` (installed on
     the model by `generate`), the checked stochastic plan `sto` of `_stochastic_for_run` and the checked Enhance-A-Video set `enhance` of
     `_enhance_for_run` (`generate` puts back what the model held) and the checked forecast plan `forecast` of `_forecast_for_run` (installed
-    on the model by `generate`) and the checked FlowEdit side `flow` of `_flowedit_for_run`; returns the latent."""
+    on the model by `generate`) and the checked FlowEdit side `flow` of `_flowedit_for_run`; `tiles`: the TileWindows of `_plan_for` (then `plan` is None); returns the latent."""
     context_text = context[2]
+    if tiles is not None:   # the window's positions are the first entries of the clip's, in every axis
+        F = tiles.window[0]
+        if context_text is not None:
+            text_embeds, text_rope_pos = context_text[0]
+        visual_rope_pos = [torch.as_tensor(p)[:n] for p, n in zip(visual_rope_pos, (F, tiles.window[1] // 2, tiles.window[2] // 2))]
     if plan is not None:
         F, starts, weights = plan
         if context_text is not None:   # the first window's prompt stands where the one prompt of a plain run does
@@ -824,7 +929,8 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     fe_km = km if flow is not None else None
     cond_in = _conditioning(model, img, visual_cond, visual_cond_mask)
 
-    sparse_params = get_sparse_params(conf, {"visual": img if plan is None else img[:plan[0]]}, device)
+    one_window = img[:tiles.window[0], :tiles.window[1], :tiles.window[2]] if tiles is not None else img if plan is None else img[:plan[0]]
+    sparse_params = get_sparse_params(conf, {"visual": one_window}, device)
     timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()  # one sync, before the loop
     first = edit_first_step(num_steps, strength) if init_latent is not None else 0
     timesteps = timesteps[first:]   # strength is a truncation of the schedule, nothing more
@@ -852,7 +958,8 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
                          sparse_params=sparse_params,
                          visual_cond=None if cond_in is None else torch.cat(cond_in, dim=-1).contiguous(), edit=edit,
                          flowedit=None if flow is None else (src, flow[0], flow[1], flow[2], fe_km, flow[3], flow[4], first),
-                         windows=None if plan is None else (plan[1], plan[2]), window_text=None if plan is None else context_text)
+                         windows=None if plan is None else (plan[1], plan[2]), tiles=tiles,
+                         window_text=None if plan is None and tiles is None else context_text)
         return img
 
     # The per-step loop.  Each step takes (v_cond, v_uncond, v_skip) from one of three sources (a windowed run: its per-window buffers), makes
@@ -892,6 +999,15 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
                 ubuf[k] = forward(x, null_text_embeds, null_text_rope_pos, t1000)
         return vbuf, ubuf
 
+    def tile_velocities(t1000, guided):
+        # the forwards of k5_sample_tiles in its order: window by window, cond then uncond, each on a contiguous copy of its box of the latent
+        for k in range(tiles.nwin):
+            x = _model_input(model, img, cond_in, tiles.box(k)).contiguous()
+            vbuf[k] = forward(x, *((text_embeds, text_rope_pos) if context_text is None else context_text[k]), t1000)
+            if cfg_on:
+                ubuf[k] = forward(x, null_text_embeds, null_text_rope_pos, t1000)
+        return vbuf, ubuf
+
     if exchange:
         from .models.parallelize import exchange_velocity
         mine = (text_embeds, text_rope_pos) if cfg_parallel[0] == 0 else (null_text_embeds, null_text_rope_pos)
@@ -899,6 +1015,10 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     elif plan is not None:
         st_dev, wt_dev = E.window_tables(starts, weights, img.device)
         vbuf = torch.empty((len(starts), F) + tuple(img.shape[1:]), dtype=torch.bfloat16, device=img.device)
+        ubuf = torch.empty_like(vbuf) if cfg_on else None
+    elif tiles is not None:
+        tile_dev = E.tile_tables(tiles, img.device)
+        vbuf = torch.empty((tiles.nwin,) + tiles.window + (img.shape[-1],), dtype=torch.bfloat16, device=img.device)
         ubuf = torch.empty_like(vbuf) if cfg_on else None
 
     n = len(timesteps) - 1
@@ -949,6 +1069,9 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         elif plan is not None:         # every window's pair, then the one blend + Euler pass over the clip: a kernel of its own
             v, u = window_velocities(t1000, kind == "guided")
             E.cfg_euler_windows_(img, v, u, guidance_weight, timestep_diff, st_dev, wt_dev)
+        elif tiles is not None:        # the same over the 3-D plan
+            v, u = tile_velocities(t1000, kind == "guided")
+            E.cfg_euler_tiles_(img, v, u, guidance_weight, timestep_diff, tile_dev)
         else:
             v, u, sv = (skip_velocities if skip_at else pair_velocities if exchange else plain_velocities)(t1000, kind == "guided")
             # the plan's coefficients are reduced on the device and read there; the skip term comes after them
@@ -986,7 +1109,7 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         if v is not None and v.shape[0] != img.shape[0]:
             raise ValueError(f"{n} must have {img.shape[0]} frames (batch={batch} x {T}), got {v.shape[0]}")
 
-    if sto is None and init_latent is None and context[0] is None and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) \
+    if sto is None and init_latent is None and all(v is None for v in (context[0], context[3], context[4])) and type(model) is DiffusionTransformer3D and model.visual_cond in (True, False) \
             and model.many_ready() and getattr(model, "_cfg_parallel", None) is None:
         cond = _conditioning(model, img, visual_cond, visual_cond_mask)
         if cond is not None:
@@ -1005,11 +1128,11 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         rows = slice(b * T, (b + 1) * T)
         vc, vm, src, km = (None if v is None else v[rows] for v in (visual_cond, visual_cond_mask, init_latent, keep_mask))
         _check_edit_args(model, img[rows].shape, src, strength, km)
-        plan = _context_plan(model, T, *context, src, watch.every)
+        plan, tiles = _plan_for(model, (T, img.shape[1], img.shape[2]), context, src, watch.every)
         watch.sample = b
         img[rows] = _generate_one(model, device, img[rows].clone(), num_steps, tes[b], nes[b], visual_rope_pos, tps[b], nps[b], guidance_weight,
                                   scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide, skip=skip, enhance=enhance,
-                                  forecast=forecast, flow=None if flow is None else (*flow[:4], (flow[4] + b) & (2 ** 64 - 1)),
+                                  tiles=tiles, forecast=forecast, flow=None if flow is None else (*flow[:4], (flow[4] + b) & (2 ** 64 - 1)),
                                   sto=None if sto is None else (*sto[:3], (sto[3] + b) & (2 ** 64 - 1), sto[4]))   # a seed per sample
     return img
 
@@ -1056,7 +1179,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                     cfg_rescale=0.0, slg_blocks=None, slg_scale=0.0, slg_interval=None, slg_mode="block", eta=0.0, s_noise=1.0,
                     sde_interval=None, sde_seed=None, enhance_weight=None, enhance_interval=None, forecast_interval=None, forecast_order=1,
                     forecast_warmup=None, forecast_tail=1, source_caption=None, source_guidance_weight=None, flowedit_refine=0,
-                    flowedit_seed=None):
+                    flowedit_seed=None, context_height=None, context_width=None, context_overlap_hw=None):
     """reference generation_utils.py:132-228 (same signature): text encode -> generate -> VAE decode -> uint8.
     With `offload` each of the three models visits the GPU only for its own stage.  `image` (optional, extension: PIL image or
     tensor, see conditioning.preprocess_image): image-to-video, the picture's VAE latent conditions latent frame 0 of every
@@ -1086,7 +1209,10 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     (see there).  None or 1 (default) is off.
     `source_caption`, `source_guidance_weight`, `flowedit_refine`, `flowedit_seed` (optional, extension): FlowEdit (see `generate`): with
     `video`, `source_caption` describes the source clip, `caption` the result; `strength` and `mask` keep their meaning.  None (default)
-    is off: `video` alone is the SDEdit path."""
+    is off: `video` alone is the SDEdit path.
+    `context_height`, `context_width`, `context_overlap_hw` (optional, extension): a frame larger than the model's trained size, sampled as
+    overlapping spatial windows of that many latent cells (see `generate` and `tile_windows`); `image` conditions the whole frame and each
+    window sees its slice.  With bs = 1 `caption` may then be a list of nwin prompts, one per window of the 3-D plan."""
     batch, frames, height, width, channels = shape
     flow_kw = {}
     if source_caption is None:
@@ -1119,6 +1245,9 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     if wants_sto or wants_skip:   # what both pre-checks refuse together with more than one context window
         windowed = context_frames is not None and len(context_windows(
             frames, context_frames, int(context_frames) // 4 if context_overlap is None else int(context_overlap))[0]) > 1
+        if context_height is not None or context_width is not None:
+            windowed = windowed or _plan_for(dit, (frames, height, width), (context_frames, context_overlap, None, context_height, context_width,
+                                                                            context_overlap_hw), video, preview_every)[1] is not None
     if wants_sto:   # before any model runs: the numbers and what the handle's state refuses
         _stochastic_for_run(dit, [1.0, 0.5, 0.0], 0, eta, s_noise, None, seed if sde_seed is None else sde_seed, windowed, preview_every)
         stochastic_plan([1.0, 0.0], eta, s_noise, sde_interval)   # (what depends on the schedule is checked by `generate`)
@@ -1136,7 +1265,19 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         if guidance_interval is not None:
             guidance_plan([1.0, 0.0], guidance_weight, None, guidance_interval)
     ctx_kw, window_captions = {}, None
-    if context_frames is not None:
+    if context_height is not None or context_width is not None:   # before any model runs: the plan and what it is refused with
+        context = (context_frames, context_overlap, None, context_height, context_width, context_overlap_hw)
+        plan_t, tiles = _plan_for(dit, (frames, height, width), context, video, preview_every)
+        nwin = tiles.nwin if tiles is not None else 1 if plan_t is None else len(plan_t[1])
+        ctx_kw = {k: v for k, v in zip(("context_frames", "context_overlap", "", "context_height", "context_width", "context_overlap_hw"), context)
+                  if k and v is not None}
+        if batch == 1 and isinstance(caption, (list, tuple)):
+            if len(caption) != nwin:
+                raise ValueError(f"{len(caption)} prompts for a plan of nwin = {nwin} windows ({tiles!r}): pass one prompt, or one per window")
+            window_captions, caption = list(caption), caption[0]
+    elif context_overlap_hw is not None:
+        raise ValueError("context_overlap_hw needs context_height / context_width")
+    elif context_frames is not None:
         overlap = int(context_frames) // 4 if context_overlap is None else int(context_overlap)
         nwin = len(context_windows(frames, context_frames, overlap)[0])
         ctx_kw = dict(context_frames=int(context_frames), context_overlap=overlap)
@@ -1157,7 +1298,7 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
                               region_base_weight)
         else:
             check_region_args(region_text_embeds, region_text_rope_pos, region_masks, region_base_weight)
-        if context_frames is not None:
+        if context_frames is not None or ctx_kw:
             raise ValueError("regions together with context_frames is not supported: the masks cover the clip, a window sees a slice")
         if tuple(region_masks.shape[1:]) != (frames, height, width):
             raise ValueError(f"regions: the masks are {tuple(region_masks.shape[1:])}, one sample's latent is {(frames, height, width)}")

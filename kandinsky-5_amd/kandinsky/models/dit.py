@@ -575,7 +575,7 @@ class DiffusionTransformer3D(nn.Module):
     @torch.no_grad()
     def sample(self, latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
                null_text_rope_pos, guidance_weight, scale_factor=(1.0, 1.0, 1.0), sparse_params=None, visual_cond=None, edit=None,
-               windows=None, window_text=None, flowedit=None):
+               windows=None, window_text=None, flowedit=None, tiles=None):
         """Whole Euler/CFG loop on device (generation_utils.py:80-129) in one C call.  `latent` fp32
         (T,H,W,in_visual_dim) is updated in place; `sigmas` = the sigma schedule (num_steps+1 floats, host).
         `visual_cond` (optional, a model with visual_cond only): contiguous fp32 (T,H,W,in_visual_dim+1) on the latent's device, the
@@ -591,14 +591,23 @@ class DiffusionTransformer3D(nn.Module):
         `flowedit` (optional): `(source, source_text_embeds, source_text_rope_pos, source_weight, keep_mask | None, refine, seed, first_stream)`:
         FlowEdit (k5_sample_flowedit; the rule is written at k5_flowedit_step_args in include/k5.h).  `source` is the clean source latent,
         the source prompt describes it; `text_embeds` / `guidance_weight` are the target side and the negative prompt serves both.  `sigmas`
-        is the cut schedule sigmas[first:] and `first_stream` = first.  `latent` is output only.  Not with `edit` or `windows`."""
+        is the cut schedule sigmas[first:] and `first_stream` = first.  `latent` is output only.  Not with `edit` or `windows`.
+        `tiles` (optional): the plan of `generation_utils.tile_windows` (anything with its `clip`, `window`, `starts`, `weights`): a frame
+        larger than the model's trained size runs as overlapping windows in three axes (k5_sample_tiles).  `visual_rope_pos` and
+        `sparse_params` are then the WINDOW's in every axis, `latent` and `visual_cond` the whole clip's; `window_text` is a prompt per window
+        of the 3-D plan.  Not with `edit`, `windows` or `flowedit`; refused where `windows` is."""
         if flowedit is not None:
-            if edit is not None or windows is not None:
-                raise ValueError("flowedit together with edit or windows is not supported")
+            if edit is not None or windows is not None or tiles is not None:
+                raise ValueError("flowedit together with edit, windows or tiles is not supported")
             return self._sample_flowedit(latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
                                          guidance_weight, scale_factor, sparse_params, visual_cond, flowedit)
+        if tiles is not None:
+            if edit is not None or windows is not None:
+                raise ValueError("tiles together with edit or windows is not supported")
+            return self._sample_tiles(latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
+                                      guidance_weight, scale_factor, sparse_params, visual_cond, tiles, window_text)
         if windows is None and window_text is not None:
-            raise ValueError("window_text needs windows")
+            raise ValueError("window_text needs windows or tiles")
         if windows is not None:
             if edit is not None:
                 raise ValueError("edit together with windows is not supported")
@@ -615,13 +624,15 @@ class DiffusionTransformer3D(nn.Module):
         return self._run_sampler("k5_sample_cond", latent, C.byref(s), visual_cond.data_ptr())
 
     def _fill_sample_args(self, s, latent, frames, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
-                          guidance_weight, scale_factor, sparse_params, visual_cond, edit=None):
+                          guidance_weight, scale_factor, sparse_params, visual_cond, edit=None, window_hw=None):
         """Check what a k5_sample* call borrows and fill its SampleArgs `s`, for a forward that sees `frames` frames: the latent's T in a plain
-        run (`frames` None), F in a window.  Returns (what must stay alive as long as `s` is used, the checked `edit` triple or None)."""
+        run (`frames` None), F in a window; `window_hw`: the rows and columns it sees where they are not the latent's (a tile).  Returns (what must stay alive as long as `s` is used, the checked `edit` triple or None)."""
         if not latent.is_cuda or latent.dtype != torch.float32 or not latent.is_contiguous():
             raise RuntimeError("latent must be a contiguous fp32 CUDA tensor")
         T, H, W, _ = latent.shape
         frames = T if frames is None else frames
+        if window_hw is not None:
+            H, W = window_hw
         self._last_tokens = frames * (H // self.patch_size[1]) * (W // self.patch_size[2])   # rows of a residual (magcache_calibration)
         self._check_visual_cond(visual_cond, latent)
         edit = self._check_edit(edit, latent)
@@ -698,6 +709,38 @@ class DiffusionTransformer3D(nn.Module):
         wt = (C.c_float * (nwin * F))(*[v for row in weights for v in row])
         a.total_T, a.nwin, a.starts, a.weights = latent.shape[0], nwin, st, wt
         return self._run_sampler("k5_sample_windows", latent, C.byref(a), E.ptr(visual_cond))
+
+    def _sample_tiles(self, latent, sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
+                      guidance_weight, scale_factor, sparse_params, visual_cond, tiles, window_text):
+        """`sample(tiles=...)`: the k5_sample_tiles call."""
+        starts = [[int(v) for v in s] for s in tiles.starts]
+        weights = [torch.as_tensor(w, dtype=torch.float32) for w in tiles.weights]
+        window = tuple(int(v) for v in tiles.window)
+        if len(starts) != 3 or len(weights) != 3 or any(len(s) < 1 or tuple(w.shape) != (len(s), f) for s, w, f in zip(starts, weights, window)):
+            raise ValueError("tiles must hold, per axis (t, y, x), starts [n] and weights [n][F] with F the window's extent")
+        if tuple(latent.shape[:3]) != tuple(int(v) for v in tiles.clip):
+            raise ValueError(f"tiles were planned for a clip of {tuple(tiles.clip)}, the latent is {tuple(latent.shape[:3])}")
+        nwin = len(starts[0]) * len(starts[1]) * len(starts[2])
+        if window_text is not None and len(window_text) != nwin:
+            raise ValueError(f"window_text holds {len(window_text)} prompts, the plan has nwin = {nwin} windows")
+        if window_text is not None:
+            text_embeds, text_rope_pos = window_text[0]
+        a = E.SampleTilesArgs()
+        keep, _ = self._fill_sample_args(a.sample, latent, window[0], sigmas, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos,
+                                         null_text_rope_pos, guidance_weight, scale_factor, sparse_params, visual_cond, window_hw=window[1:])
+        if window_text is not None:
+            dev = latent.device
+            conds = (E.TextCond * nwin)()
+            for i, (te, tp) in enumerate(window_text):
+                conds[i] = self._text_cond(te["text_embeds"].to(dev), te["pooled_embed"].to(dev), tp, keep)
+            a.conds = conds
+        a.total_T, a.total_H, a.total_W = (int(v) for v in latent.shape[:3])
+        a.nt, a.ny, a.nx = (len(s) for s in starts)
+        st = [E.i32_array(s) for s in starts]
+        wt = [(C.c_float * w.numel())(*w.reshape(-1).tolist()) for w in weights]
+        a.starts_t, a.starts_y, a.starts_x = st
+        a.wt, a.wy, a.wx = wt
+        return self._run_sampler("k5_sample_tiles", latent, C.byref(a), E.ptr(visual_cond))
 
     # ---------------------------------------------------------------- settings on the handle (_SETTINGS): put, clear, state, for one call
     def _put(self, name, value):

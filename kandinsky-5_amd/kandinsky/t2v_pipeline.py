@@ -66,6 +66,35 @@ class Kandinsky5T2VPipeline:
         if (height, width) not in allowed:
             raise ValueError(f"Wrong height, width pair. Available (height, width) are: {allowed}")
 
+    def _check_tiles(self, height, width, tile_height, tile_width, tile_overlap):
+        """The tile keywords (pixels) -> `generate`'s spatial context keywords (latent cells), or None without them.  The tile must be one of
+        the allowed sizes, the frame multiples of 16 that are at least the tile and, when sqrt(height * width) > 900, keys of the VAE's spatial
+        tiling table (the decode tiles there); ValueError naming the allowed values otherwise."""
+        if tile_height is None and tile_width is None:
+            if tile_overlap is not None:
+                raise ValueError("tile_overlap needs tile_height and tile_width")
+            return None
+        if self.resolution != 512:
+            raise NotImplementedError("Only 512 resolution is available for now")
+        allowed = self.RESOLUTIONS[self.resolution]
+        if (tile_height, tile_width) not in allowed:
+            raise ValueError(f"Wrong tile_height, tile_width pair. Available (tile_height, tile_width) are: {allowed}")
+        if height % 16 or width % 16 or height < tile_height or width < tile_width:
+            raise ValueError(f"With tiles, height and width must be multiples of 16 that are at least the tile ({tile_height}, {tile_width}), "
+                             f"got ({height}, {width})")
+        if (height * width) ** 0.5 > 900:
+            from .models.vae import OPT_SPATIAL_TILING
+            keys = sorted(OPT_SPATIAL_TILING)
+            if height not in keys or width not in keys:
+                raise ValueError(f"With tiles and sqrt(height * width) > 900, height and width must be keys of the VAE's spatial tiling table: "
+                                 f"{keys}, got ({height}, {width})")
+        out = dict(context_height=tile_height // 8, context_width=tile_width // 8)
+        if tile_overlap is not None:
+            if tile_overlap < 0 or tile_overlap % 16 or tile_overlap >= min(tile_height, tile_width):
+                raise ValueError(f"tile_overlap must be a multiple of 16 in [0, {min(tile_height, tile_width)}), got {tile_overlap}")
+            out["context_overlap_hw"] = tile_overlap // 8
+        return out
+
     def _beautified(self, prompt):
         if self.offload:
             self.text_embedder = self.text_embedder.to(self.device_map["text_embedder"])
@@ -98,7 +127,8 @@ class Kandinsky5T2VPipeline:
                  slg_blocks=None, slg_scale: float = 0.0, slg_interval=None, slg_mode: str = "block", eta: float = 0.0, s_noise: float = 1.0,
                  sde_interval=None, sde_seed: int = None, enhance_weight: float = None, enhance_interval=None,
                  forecast_interval: int = None, forecast_order: int = 1, forecast_warmup: int = None, forecast_tail: int = 1,
-                 source_caption: str = None, source_guidance_weight: float = None, flowedit_refine: int = 0, flowedit_seed: int = None):
+                 source_caption: str = None, source_guidance_weight: float = None, flowedit_refine: int = 0, flowedit_seed: int = None,
+                 tile_height: int = None, tile_width: int = None, tile_overlap: int = None):
         """reference t2v_pipeline.py:90-189 (same arguments, defaults, errors and return values: uint8 tensor (1,3,F,H,W) on
         rank 0 / list of PIL images for time_length = 0, None on the other ranks).  `image` (optional, extension): image-to-video,
         the clip starts from this picture (PIL image or tensor, resized to cover (height, width) and centre-cropped); every rank
@@ -154,8 +184,19 @@ class Kandinsky5T2VPipeline:
         difference between the two prompts' velocities is integrated along a noisy path tied to the clip, nothing is inverted and the clip
         stays where the prompts agree; see `generate`.  `source_caption` is not expanded.  None (default) is off and `video` is the SDEdit
         path.  Single-rank, without MagCache, previews or the other sampler extensions.  SD3's published values (33 of 50 steps, source
-        guidance 3.5, target 13.5) are examples: no Kandinsky checkpoint was at hand when this was written, visual quality is not claimed."""
+        guidance 3.5, target 13.5) are examples: no Kandinsky checkpoint was at hand when this was written, visual quality is not claimed.
+        `tile_height`, `tile_width`, `tile_overlap` (optional, extension; pixels): a frame larger than the checkpoint's trained size,
+        `pipe(text, height=1024, width=1024, tile_height=512, tile_width=768, tile_overlap=128)` — the model runs on overlapping spatial
+        windows of the trained size (one of the allowed (height, width) pairs) whose velocities are cross-faded at every step; see
+        `generate`.  height and width are then multiples of 16 that are at least the tile and, beyond sqrt(height * width) = 900, keys of the
+        VAE's spatial tiling table.  `tile_overlap` None = a quarter of the tile.  Works with `image` and with `context_seconds`; single-rank,
+        without `video`, previews or MagCache.  No checkpoint was at hand when this was written: visual quality is not claimed."""
         ctx = {}
+        tiled = self._check_tiles(height, width, tile_height, tile_width, tile_overlap)
+        if tiled is not None:
+            ctx.update(tiled)
+        windowed = context_seconds is not None or tiled is not None   # what the windows refuse, the tiles refuse
+        windows_kw = "context_seconds" if context_seconds is not None else "tile_height / tile_width"
         flow_kw = {}
         if source_caption is not None:
             flow_kw = dict(source_caption=source_caption, source_guidance_weight=source_guidance_weight, flowedit_refine=flowedit_refine,
@@ -179,30 +220,29 @@ class Kandinsky5T2VPipeline:
         if eta or sde_interval is not None or float(s_noise) != 1.0:
             from .generation_utils import _stochastic_for_run, stochastic_plan
             stochastic_plan([1.0, 0.0], eta, s_noise, sde_interval)
-            _stochastic_for_run(self.dit, [1.0, 0.5, 0.0], 0, eta, s_noise, None, 0 if sde_seed is None else sde_seed, context_seconds is not None,
-                                preview_every)
+            _stochastic_for_run(self.dit, [1.0, 0.5, 0.0], 0, eta, s_noise, None, 0 if sde_seed is None else sde_seed, windowed, preview_every)
             sto_kw = dict(eta=eta, s_noise=s_noise, sde_interval=sde_interval, sde_seed=sde_seed)
         skip_kw = {}
         if slg_blocks is not None or slg_scale or slg_interval is not None:
             from .generation_utils import _skip_for_run, skip_plan
             skip_plan([1.0, 0.0], slg_interval)
-            _skip_for_run(self.dit, [1.0, 0.0], 0, slg_blocks, slg_scale, None, slg_mode, context_seconds is not None)
+            _skip_for_run(self.dit, [1.0, 0.0], 0, slg_blocks, slg_scale, None, slg_mode, windowed)
             skip_kw = dict(slg_blocks=slg_blocks, slg_scale=slg_scale, slg_interval=slg_interval, slg_mode=slg_mode)
         guide_kw = {k: v for k, v in dict(guidance_schedule=guidance_schedule, guidance_interval=guidance_interval, cfg_zero_star=cfg_zero_star,
                                           cfg_zero_init=cfg_zero_init, cfg_rescale=cfg_rescale).items() if v}
         if guide_kw:
             from .models.dit import check_guidance_args
-            if context_seconds is not None:
+            if windowed:
                 raise ValueError("guidance_schedule / guidance_interval / cfg_zero_star / cfg_zero_init / cfg_rescale together with "
-                                 "context_seconds are not supported: one statistic per window is not the published rule")
+                                 f"{windows_kw} are not supported: one statistic per window is not the published rule")
             check_guidance_args(None if guidance_schedule is None or callable(guidance_schedule) else guidance_schedule, cfg_zero_star,
                                 cfg_zero_init, cfg_rescale)
         region_kw = {}
         if regions is not None:
             from .conditioning import region_masks_to_latent
             from .models.dit import check_region_args
-            if context_seconds is not None:
-                raise ValueError("regions together with context_seconds is not supported: the masks cover the clip, a window sees a slice")
+            if windowed:
+                raise ValueError(f"regions together with {windows_kw} is not supported: the masks cover the clip, a window sees a slice")
             pairs = list(regions)
             if not 1 <= len(pairs) <= 8 or not all(isinstance(p, (list, tuple)) and len(p) == 2 and isinstance(p[0], str) for p in pairs):
                 raise ValueError("regions must be a list of 1 to 8 (prompt, mask) pairs")
@@ -239,7 +279,8 @@ class Kandinsky5T2VPipeline:
         weight = self.guidance_weight if guidance_weight is None else guidance_weight
         if seed is None:
             seed = self._agree_on(lambda: int(torch.randint(2 ** 63 - 1, (1,)).item()))
-        self._check_size(height, width)
+        if tiled is None:
+            self._check_size(height, width)
         frames = 1 if time_length == 0 else time_length * 24 // 4 + 1
         if isinstance(text, (list, tuple)):
             if len(text) == 0:

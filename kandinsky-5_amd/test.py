@@ -28,14 +28,27 @@ NEGATIVE = ("Static, 2D cartoon, cartoon, 2d animation, paintings, images, worst
             "walking backwards")
 
 
+class _Parser(argparse.ArgumentParser):
+    """--width / --height take the trained sizes only, as they always did; the choice is lifted for a command line that has --tile, whose frame
+    the pipeline checks (multiples of 16 that are at least the tile)."""
+    size_actions = ()
+
+    def parse_known_args(self, args=None, namespace=None):
+        argv = sys.argv[1:] if args is None else list(args)
+        tiled = any(a == "--tile" or a.startswith("--tile=") for a in argv)
+        for action in self.size_actions:
+            action.choices = None if tiled else [768, 512]
+        return super().parse_known_args(args, namespace)
+
+
 def build_parser():
-    p = argparse.ArgumentParser(description="Generate a video with Kandinsky 5 (MI355X engine)")
+    p = _Parser(description="Generate a video with Kandinsky 5 (MI355X engine)")
     p.add_argument("--local-rank", type=int, help="set by the launcher (one process per GPU)")
     p.add_argument("--config", type=str, default="./configs/config_5s_sft.yaml", help="YAML config (reference schema); a missing default name is created")
     p.add_argument("--prompt", type=str, default="a cat in a blue hat", help="text prompt")
     p.add_argument("--negative_prompt", type=str, default=NEGATIVE, help="negative prompt of the unconditional branch")
-    p.add_argument("--width", type=int, default=768, choices=[768, 512], help="frame width in pixels")
-    p.add_argument("--height", type=int, default=512, choices=[768, 512], help="frame height in pixels")
+    p.size_actions = (p.add_argument("--width", type=int, default=768, choices=[768, 512], help="frame width in pixels; with --tile a larger multiple of 16"),
+                      p.add_argument("--height", type=int, default=512, choices=[768, 512], help="frame height in pixels; with --tile a larger multiple of 16"))
     p.add_argument("--video_duration", type=int, default=5, help="clip length in seconds (0 = a single image)")
     p.add_argument("--expand_prompt", type=int, default=1, help="1 = rewrite the prompt with the Qwen2.5-VL chat model first")
     p.add_argument("--sample_steps", type=int, default=None, help="number of Euler steps (default: the config's)")
@@ -72,6 +85,11 @@ def build_parser():
                         "(e.g. --video_duration 20 --context_seconds 10)")
     p.add_argument("--context_overlap_seconds", type=float, default=argparse.SUPPRESS, metavar="S",
                    help="with --context_seconds: how far neighbouring windows overlap (default a quarter of the window)")
+    p.add_argument("--tile", type=int, nargs=2, default=argparse.SUPPRESS, metavar=("HEIGHT", "WIDTH"),
+                   help="a frame larger than the checkpoint's trained size: sample --height x --width as overlapping spatial windows of HEIGHT x "
+                        "WIDTH pixels, one of the trained sizes (e.g. --height 1024 --width 1024 --tile 512 768)")
+    p.add_argument("--tile_overlap", type=int, default=argparse.SUPPRESS, metavar="PX",
+                   help="with --tile: how far neighbouring windows overlap, a multiple of 16 pixels (default a quarter of the window)")
     p.add_argument("--nag_scale", type=float, default=argparse.SUPPRESS, metavar="S",
                    help="normalized attention guidance: --negative_prompt steers inside the cross-attention of the one forward (what makes it "
                         "count without classifier-free guidance); S >= 1, commonly 5 — a starting point, not tuned on these checkpoints")
@@ -316,6 +334,18 @@ def context_keywords(args):
     return kw
 
 
+def tile_keywords(args):
+    """--tile / --tile_overlap -> the pipeline's keywords"""
+    if not hasattr(args, "tile"):
+        if hasattr(args, "tile_overlap"):
+            raise ValueError("--tile_overlap needs --tile HEIGHT WIDTH")
+        return {}
+    kw = {"tile_height": args.tile[0], "tile_width": args.tile[1]}
+    if hasattr(args, "tile_overlap"):
+        kw["tile_overlap"] = args.tile_overlap
+    return kw
+
+
 def preview_keywords(args):
     """--preview / --preview_every / --preview_factors -> the pipeline's keywords"""
     if not hasattr(args, "preview"):
@@ -354,6 +384,10 @@ def load_edit_inputs(args):
 
 
 def validate_args(args):
+    if hasattr(args, "tile"):   # the frame is the pipeline's to check: multiples of 16 that are at least the tile
+        if (args.tile[1], args.tile[0]) not in SUPPORTED_SIZES:
+            raise NotImplementedError(f"Provided size of tile is not supported: {(args.tile[1], args.tile[0])}")
+        return
     if (args.width, args.height) not in SUPPORTED_SIZES:
         raise NotImplementedError(f"Provided size of video is not supported: {(args.width, args.height)}")
 
@@ -404,6 +438,7 @@ def main(argv=None):
         return
     edit_kw.update(preview_keywords(args))
     edit_kw.update(context_keywords(args))
+    edit_kw.update(tile_keywords(args))
     edit_kw.update(nag_kw)
     edit_kw.update(region_kw)
     edit_kw.update(guide_kw)
