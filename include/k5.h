@@ -1165,6 +1165,12 @@ int k5_frames_to_uint8(const void* x_bf16, void* out_u8, int64_t n, void* stream
  * only after k5_dit_set_fp8(dit, 1). */
 int k5_gemm_fp8(const void* A8, const void* W8, const float* w_scale, void* C, int M, int N, int K, int lda, int ldw, int ldc,
                 int epi, const void* resid, int ldr, const float* gate, void* stream);
+/* (added under ABI 11) k5_gemm_fp8 with the launcher's two remaining arguments, as the engine's q | k | V^T projections use them: `bias` (nullable)
+ * is fp32 per output column n and is added to acc * w_scale in one fma; scale_m != 0 is the operand-swapped form (weights as the A8 rows, tokens
+ * as N) where w_scale and bias are indexed by the output ROW m — K5_EPI_BIAS only, K5_ERR_ARG otherwise.  bias == NULL and scale_m == 0 is
+ * k5_gemm_fp8, bit for bit. */
+int k5_gemm_fp8_ex(const void* A8, const void* W8, const float* w_scale, void* C, int M, int N, int K, int lda, int ldw, int ldc,
+                   int epi, const void* resid, int ldr, const float* gate, void* stream, const float* bias, int scale_m);
 int k5_quant_rows_fp8(const void* x_bf16, void* out_fp8, float* scale, int rows, int K, int ldx, int ldo, void* stream);
 
 /* Run linear layers of the visual blocks in W8A8 e4m3 (weights quantised per output channel on first enable, activations with the

@@ -76,6 +76,12 @@ int k5_gemm_fp8(const void* A8, const void* W8, const float* w_scale, void* C, i
   return ret(k5_launch_gemm_fp8(A8, W8, w_scale, C, M, N, K, lda, ldw, ldc, epi, resid, ldr, gate, (hipStream_t)stream), "k5_gemm_fp8");
 }
 
+int k5_gemm_fp8_ex(const void* A8, const void* W8, const float* w_scale, void* C, int M, int N, int K, int lda, int ldw, int ldc, int epi,
+                   const void* resid, int ldr, const float* gate, void* stream, const float* bias, int scale_m) {
+  return ret(k5_launch_gemm_fp8(A8, W8, w_scale, C, M, N, K, lda, ldw, ldc, epi, resid, ldr, gate, (hipStream_t)stream, bias, scale_m),
+             "k5_gemm_fp8_ex");
+}
+
 int k5_quant_rows_fp8(const void* x, void* out, float* scale, int rows, int K, int ldx, int ldo, void* stream) {
   return ret(k5_launch_quant_rows_fp8(x, out, scale, rows, K, ldx, ldo, (hipStream_t)stream), "k5_quant_rows_fp8");
 }
