@@ -45,7 +45,12 @@ const char* k5_last_error(void);
  * Replaces autocast nn.Linear: kandinsky/models/nn.py:180-191 (get_qkv), :204-206 (out_l),
  * :352-361 (FeedForward incl. nn.GELU), :71 (TextEmbeddings), :96 (VisualEmbeddings), :382 (OutLayer);
  * K5_EPI_GATE additionally fuses apply_gate_sum nn.py:30-33: C = bf16(resid + gate[n]*bf16(acc+bias)).
- * K5_EPI_BIAS_M adds bias[m] (used to emit V^T = W_v . X^T directly). bias/gate are fp32. */
+ * K5_EPI_BIAS_M adds bias[m] (used to emit V^T = W_v . X^T directly). bias/gate are fp32.
+ * Operand footprint: when K is a multiple of 128 and >= 256, M >= 512, N >= 128, N and ldc multiples of 8 (the four-wave kernel and its quadrant tail
+ * may take the call), up to 143 rows PAST the last row of A (M not a multiple of the 256- / 192- / 128-row tile) and of W (N not a multiple of 256) are
+ * read: 143 * lda resp. 143 * ldw elements beyond row M - 1 resp. N - 1.  Their values are never used (they feed outputs that are not stored), but they
+ * must be MAPPED memory: keep the operand inside an allocation with that slack.  Every other shape reads rows 0 .. M - 1 / N - 1 only.
+ * The padding columns K .. lda - 1 / ldw - 1 and C's columns N .. ldc - 1 and rows >= M are never read or written. */
 int k5_gemm_bf16(const void* A, const void* W, const float* bias, void* C, int M, int N, int K, int lda,
                  int ldw, int ldc, int epilogue, const void* resid, int ldr, const float* gate, void* stream);
 /* The same GEMM on a NAMED kernel (tests and A/B tools; k5_gemm_bf16 picks by shape and cost): kernel 0 = as k5_gemm_bf16, 2 = 128 x 128 tiles,
@@ -58,7 +63,8 @@ int k5_gemm_bf16_variant(const void* A, const void* W, const float* bias, void* 
 /* S_f32[M][N] = alpha * A[M][K] . W[N][K]^T — the fp32 attention scores of the VAE mid block (diffusers Attention called from
  * HunyuanVideoMidBlock3D, kandinsky/models/vae.py:341-362, with prepare_causal_attention_mask vae.py:110-122).  causal_hw > 0:
  * row i is only ever read at columns < (i / causal_hw + 1) * causal_hw (its own and earlier frames); output tiles wholly beyond
- * that limit are not computed and left unwritten.  C is fp32 [M][ldc]. */
+ * that limit are not computed and left unwritten.  C is fp32 [M][ldc].  Operand footprint as k5_gemm_bf16: with K a multiple of 128 and >= 256, M >= 512,
+ * N >= 256, N and ldc multiples of 4 and at least 256 kept 256 x 256 tiles, up to 143 rows past the last row of A and of W are read and must be mapped. */
 int k5_gemm_bf16_f32out(const void* A, const void* W, float* C, int M, int N, int K, int lda, int ldw, int ldc,
                         float alpha, int causal_hw, void* stream);
 

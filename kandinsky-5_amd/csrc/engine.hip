@@ -65,10 +65,11 @@ struct DevBuf {   // owning device buffer (move-only): freed with whatever holds
   DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes), owned(o.owned) { o.p = nullptr; o.bytes = 0; o.owned = true; }
   DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { release(); p = o.p; bytes = o.bytes; owned = o.owned; o.p = nullptr; o.bytes = 0; o.owned = true; } return *this; }
   ~DevBuf() { release(); }
-  int ensure(size_t n) {
+  // slack: bytes allocated beyond n (GEMM operands: K5_GEMM_GUARD_ROWS rows, k5_kernels.h); never counted in `bytes`
+  int ensure(size_t n, size_t slack = 0) {
     if (n <= bytes) return K5_OK;
     release();
-    HIPCHK(hipMalloc(&p, n));
+    HIPCHK(hipMalloc(&p, n + slack));
     bytes = n;
     return K5_OK;
   }
@@ -126,7 +127,7 @@ struct Linear {
   int quantise(bool create) {
     if (!w8.p) {
       if (!create) return K5_OK;
-      K5CHK(w8.ensure((size_t)N * K)); K5CHK(sc.ensure((size_t)N * 4));
+      K5CHK(w8.ensure((size_t)N * K, (size_t)K5_GEMM_GUARD_ROWS * K)); K5CHK(sc.ensure((size_t)N * 4));
     }
     return k5_launch_quant_rows_fp8(w.p, w8.p, sc.as<float>(), N, K, ld, K, nullptr);
   }
@@ -765,7 +766,8 @@ int pack_rows(DevBuf& dst, bool bf16, const HostTensor* t, size_t rows, size_t c
   if (!t || !t->dev.p || t->count() != rows * cols) { k5_set_error("internal: matrix not staged on the device"); return K5_ERR_STATE; }
   if (total_rows == 0) total_rows = rows;
   const size_t es = bf16 ? 2 : 4;
-  K5CHK(dst.ensure(total_rows * ld * es));
+  // packed bf16 weights are GEMM operands (the A side in the V^T form, where 1792 rows are ragged for the 192-row tile): guard rows behind them
+  K5CHK(dst.ensure(total_rows * ld * es, bf16 ? (size_t)K5_GEMM_GUARD_ROWS * ld * es : 0));
   return k5_launch_pack_matrix(t->dev.p, t->dtype, (char*)dst.p + row0 * ld * es, bf16 ? 1 : 0, (int64_t)rows, (int)cols, (int)ld, nullptr);
 }
 int pack_f32(DevBuf& dst, const HostTensor* t, size_t rows, size_t cols, size_t row0 = 0, size_t total_rows = 0) {
@@ -955,7 +957,7 @@ int e4m3_rows(k5_dit* d, hipStream_t s, const void* x, int rows, bool want, bool
   act = Act{x, nullptr, rows, D};
   if (ready && !want) { k5_set_error("internal: e4m3 activations handed to a bf16 projection"); return K5_ERR_ARG; }
   if (!want) return K5_OK;
-  K5CHK(d->ws_h8.ensure((size_t)rows * D));
+  K5CHK(d->ws_h8.ensure((size_t)rows * D, (size_t)K5_GEMM_GUARD_ROWS * D));
   if (!ready) {
     Scope sc(d, s, "elementwise");
     K5CHK(k5_launch_quant_rows_fp8(x, d->ws_h8.p, nullptr, rows, D, D, D, s));
@@ -1593,7 +1595,7 @@ int run_ff(k5_dit* d, hipStream_t s, const BlockW& b, const void* h, int rows, v
   // opt-in lossy path (ff_fp8_in): h -> e4m3 (static scale; by the LayerNorm itself when h8_ready), FF1 on the fp8 MFMA with the GELU epilogue
   // writing e4m3 into ws_ff8, FF2 reading that, likewise with the gated-residual epilogue (gemm_fp8.hip)
   const bool f8 = ff_fp8_in(d, b, rows);
-  if (f8) K5CHK(d->ws_ff8.ensure((size_t)rows * FF));
+  if (f8) K5CHK(d->ws_ff8.ensure((size_t)rows * FF, (size_t)K5_GEMM_GUARD_ROWS * FF));
   Act x;
   K5CHK(e4m3_rows(d, s, h, rows, f8, h8_ready, x));
   LinearArgs g1(b.w1, x, f8 ? d->ws_ff8.p : ff, FF, s), g2(b.w2, Act{ff, f8 ? d->ws_ff8.p : nullptr, rows, FF}, resid, D, s);
@@ -1617,7 +1619,7 @@ int reset_attn_pref(k5_dit* d, hipStream_t s, bool sync = false) {
 int ln_mod(k5_dit* d, hipStream_t s, const void* x, const float* mod3, void* out, int rows, bool to_e4m3 = false) {
   // mod3 = [shift | scale | gate] (dit.py:36,40,64,69,74).  to_e4m3: every consumer of this h is an fp8 GEMM — the rows go to ws_h8 as e4m3
   // (the bf16 rounding, then the e4m3 one: what the separate quantisation pass made of the bf16 h), and no bf16 h is written at all
-  if (to_e4m3) K5CHK(d->ws_h8.ensure((size_t)rows * d->D));
+  if (to_e4m3) K5CHK(d->ws_h8.ensure((size_t)rows * d->D, (size_t)K5_GEMM_GUARD_ROWS * d->D));
   Scope sc(d, s, "elementwise");
   return k5_launch_ln_modulate(x, mod3 + d->D, mod3, to_e4m3 ? nullptr : out, rows, d->D, d->D, d->D, s, to_e4m3 ? d->ws_h8.p : nullptr);
 }
@@ -1629,15 +1631,16 @@ int ln_mod(k5_dit* d, hipStream_t s, const void* x, const float* mod3, void* out
 int ensure_workspaces(k5_dit* d, int N, int L) {
   const size_t D = d->D, FF = d->FF;
   const size_t Lr = rup(L, 8), Nr = rup(N, 8);
-  K5CHK(d->ws_text_in.ensure((size_t)L * d->cfg.in_text_dim * 2));
-  K5CHK(d->ws_th.ensure(L * D * 2)); K5CHK(d->ws_tqk.ensure(L * 2 * D * 2));
-  K5CHK(d->ws_tvt.ensure(D * Lr * 2)); K5CHK(d->ws_to.ensure(L * D * 2)); K5CHK(d->ws_tff.ensure(L * FF * 2));
+  const size_t gs = (size_t)K5_GEMM_GUARD_ROWS * 2;   // the rows a GEMM may read past an activation operand, in bytes per bf16 element of a row
+  K5CHK(d->ws_text_in.ensure((size_t)L * d->cfg.in_text_dim * 2, gs * d->cfg.in_text_dim));
+  K5CHK(d->ws_th.ensure(L * D * 2, gs * D)); K5CHK(d->ws_tqk.ensure(L * 2 * D * 2, gs * 2 * D));
+  K5CHK(d->ws_tvt.ensure(D * Lr * 2, gs * Lr)); K5CHK(d->ws_to.ensure(L * D * 2, gs * D)); K5CHK(d->ws_tff.ensure(L * FF * 2, gs * FF));
   K5CHK(d->ws_pool_in.ensure((size_t)rup(d->cfg.in_text_dim2, 8) * 2)); K5CHK(d->ws_pool_lin.ensure(d->TD * 2));
   K5CHK(d->ws_pool_f32.ensure(d->TD * 4)); K5CHK(d->ws_time.ensure(16)); K5CHK(d->ws_tfeat.ensure(D * 4));
   K5CHK(d->ws_th1.ensure(d->TD * 4)); K5CHK(d->ws_temb.ensure(d->TD * 4)); K5CHK(d->ws_mod.ensure(d->mod_rows * 4));
-  K5CHK(d->ws_xp.ensure((size_t)N * d->KvisPad * 2)); K5CHK(d->ws_vis.ensure(N * D * 2)); K5CHK(d->ws_h.ensure(N * D * 2));
-  K5CHK(d->ws_qk.ensure((size_t)N * 2 * D * 2)); K5CHK(d->ws_vt.ensure(D * Nr * 2)); K5CHK(d->ws_o.ensure(N * D * 2));
-  K5CHK(d->ws_ff.ensure((size_t)N * FF * 2));
+  K5CHK(d->ws_xp.ensure((size_t)N * d->KvisPad * 2, gs * d->KvisPad)); K5CHK(d->ws_vis.ensure(N * D * 2, gs * D)); K5CHK(d->ws_h.ensure(N * D * 2, gs * D));
+  K5CHK(d->ws_qk.ensure((size_t)N * 2 * D * 2, gs * 2 * D)); K5CHK(d->ws_vt.ensure(D * Nr * 2, gs * Nr)); K5CHK(d->ws_o.ensure(N * D * 2, gs * D));
+  K5CHK(d->ws_ff.ensure((size_t)N * FF * 2, gs * FF));
   K5CHK(d->ws_y.ensure((size_t)N * d->Fout * 2));
   K5CHK(d->ws_vcos.ensure((size_t)N * 32 * 4)); K5CHK(d->ws_vsin.ensure((size_t)N * 32 * 4));
   return K5_OK;

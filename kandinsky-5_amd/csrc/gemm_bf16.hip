@@ -1172,7 +1172,8 @@ int k5_launch_gemm_bf16(const void* A, const void* W, const float* bias, void* C
   // which therefore keeps the range below 256 tiles); below that from W4_MIN_TILES tiles of the height w4_pick_mt chooses.
   const bool w4_ok = (K % (2 * BK)) == 0 && K >= 4 * BK && M >= 512 && N >= 128 && !(N & 7)   // (N = 128: the VAE's 256 -> 128 shortcut at full resolution, 6.7 M rows — half of the
                                                                                                     // 256-wide weight tile multiplies zeros the buffer range check supplies, and it is still twice the 128 x 128 kernel's rate)
-                     && !(ldc & 7) && (epi != K5_EPI_GATE || !(ldr & 3));
+                     && !(ldc & 7) && (epi != K5_EPI_GATE || !(ldr & 3))
+                     && 255ll * 2 * lda + 2ll * K < (1ll << 31) && 255ll * 2 * ldw + 2ll * K < (1ll << 31);   // its 32-bit lane offsets and the signed buffer range are per tile
   static const int num_cu = k5_num_cu();   // one device per process (one process per GPU); initialised once, thread-safe
   if (num_cu <= 0) return K5_ERR_HIP;
   const int mt_pick = w4_ok ? w4_pick_mt(M, N, num_cu, force_mt) : 8;
@@ -1186,7 +1187,10 @@ int k5_launch_gemm_bf16(const void* A, const void* W, const float* bias, void* C
       default: return K5_ERR_ARG;
     }
   }
-  if ((K % BK) == 0 && K >= 2 * BK && M >= 512 && N >= 256 && (force_kernel == 8 || (force_kernel == 0 && tiles256 >= K8_MIN_TILES))) {
+  // the 8-wave kernel keeps each lane's operand row as a 32-bit byte offset from the operand base: both operands' last byte must lie below 4 GiB
+  // (a few rows at a huge stride do not: they go on to the 128 x 128 kernel, which forms 64-bit addresses)
+  const bool k8_fits = 2ll * (M - 1) * lda + 2ll * K < (1ll << 32) && 2ll * (N - 1) * ldw + 2ll * K < (1ll << 32);
+  if (k8_fits && (K % BK) == 0 && K >= 2 * BK && M >= 512 && N >= 256 && (force_kernel == 8 || (force_kernel == 0 && tiles256 >= K8_MIN_TILES))) {
     switch (epi) {
       case K5_EPI_BIAS: return launch_k8<K5_EPI_BIAS>(p, stream);
       case K5_EPI_BIAS_M: return launch_k8<K5_EPI_BIAS_M>(p, stream);
@@ -1233,7 +1237,8 @@ int k5_launch_gemm_bf16_f32out(const void* A, const void* W, float* C, int M, in
     const int last = std::min((i + 1) * K8_BM, M) - 1;
     kept += causal_hw > 0 ? std::min(tn, (int)((std::min((long long)N, ((long long)last / causal_hw + 1) * causal_hw) + K8_BN - 1) / K8_BN)) : tn;
   }
-  if ((K % (2 * BK)) == 0 && K >= 4 * BK && M >= 512 && N >= 256 && !(N & 3) && !(ldc & 3) && kept >= 256 && kept < (1ll << 30)) {
+  if ((K % (2 * BK)) == 0 && K >= 4 * BK && M >= 512 && N >= 256 && !(N & 3) && !(ldc & 3) && kept >= 256 && kept < (1ll << 30) &&
+      255ll * 2 * lda + 2ll * K < (1ll << 31) && 255ll * 2 * ldw + 2ll * K < (1ll << 31)) {
     static const hipError_t attr_rc = hipFuncSetAttribute((const void*)gemm_bf16_w4_kernel<K5_EPI_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS);   // set once, thread-safe (function-local static: loopback ranks launch from P host threads)
     if (attr_rc != hipSuccess) return K5_ERR_HIP;
     static const int num_cu = k5_num_cu();   // one device per process (one process per GPU); initialised once, thread-safe

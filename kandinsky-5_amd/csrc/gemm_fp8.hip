@@ -25,6 +25,8 @@
 #include "k5_common.h"
 #include "k5_kernels.h"
 
+void k5_set_error(const char* fmt, ...);   // engine.hip: the text behind k5_last_error
+
 namespace {
 
 typedef int v8i __attribute__((ext_vector_type(8)));
@@ -521,8 +523,16 @@ int launch_f8(Gemm8P p, hipStream_t stream) {
   // the four-wave kernel from one full round of tiles up (K in whole pairs of K-tiles; 16-B stores need N % 16 == 0 and aligned rows)
   static const int force = getenv("K5_GEMM_FP8_V") ? atoi(getenv("K5_GEMM_FP8_V")) : 0;   // A/B: 8 = the 8-wave kernel, 4 = this one
   const bool w4_ok = (p.K % (2 * F8_BK)) == 0 && p.K >= 4 * F8_BK && p.M >= 512 && p.N >= 256 && !(p.N & 15) && !(p.ldc & 15) &&
-                     (EPI != K5_EPI_GATE || !(p.ldr & 3));
-  if (w4_ok && (force == 4 || (force == 0 && p.lid_limit >= num_cu))) return launch_f8_w4<EPI>(p, stream, num_cu);
+                     (EPI != K5_EPI_GATE || !(p.ldr & 3)) &&
+                     255ll * p.lda + p.K < (1ll << 31) && 255ll * p.ldw + p.K < (1ll << 31);   // its per-tile 32-bit lane + row offsets and the signed buffer range (bytes)
+  // the 8-wave kernel keeps each lane's operand row as a 32-bit byte offset from the operand base (gemm_bf16.hip has the same guard): operands
+  // whose last byte lies at or past 4 GiB go to the four-wave kernel, which rebases per tile, or are refused — there is no third kernel here
+  const bool k8_fits = (long long)(p.M - 1) * p.lda + p.K < (1ll << 32) && (long long)(p.N - 1) * p.ldw + p.K < (1ll << 32);
+  if (w4_ok && (force == 4 || !k8_fits || (force == 0 && p.lid_limit >= num_cu))) return launch_f8_w4<EPI>(p, stream, num_cu);
+  if (!k8_fits) {
+    k5_set_error("k5_gemm_fp8: an operand's last row starts at or beyond 4 GiB from its base (M %d lda %d, N %d ldw %d) and the shape is not one the four-wave kernel takes", p.M, p.lda, p.N, p.ldw);
+    return K5_ERR_ARG;
+  }
   hipLaunchKernelGGL(gemm_fp8_k8_kernel<EPI>, dim3(min(p.lid_limit, num_cu)), dim3(512), F8_LDS, stream, p);
   return hipGetLastError() == hipSuccess ? K5_OK : K5_ERR_HIP;
 }

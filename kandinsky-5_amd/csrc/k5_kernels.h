@@ -5,6 +5,10 @@
 
 #include "k5.h"  // status codes, epilogue ids (public C ABI)
 
+// Operand footprint of the GEMMs (bf16 and e4m3): the four-wave kernels and the q4 tail fetch a ragged tile's operand rows with buffer loads whose
+// per-instruction row offset is not range-checked, so up to 143 rows past an operand's last row are READ (never used: they land in accumulator
+// rows that are not stored).  They must be mapped memory: whoever allocates an activation or weight buffer that a GEMM reads adds this many rows.
+constexpr int K5_GEMM_GUARD_ROWS = 144;
 int k5_launch_gemm_bf16(const void* A, const void* W, const float* bias, void* C, int M, int N, int K,
                         int lda, int ldw, int ldc, int epi, const void* resid, int ldr,
                         const float* gate, hipStream_t stream,

@@ -41,11 +41,13 @@ struct Buf {   // owning device buffer: freed with the handle (k5_vae_destroy)
   Buf(Buf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
   Buf& operator=(Buf&& o) noexcept { if (this != &o) { release(); p = o.p; bytes = o.bytes; o.p = nullptr; o.bytes = 0; } return *this; }
   ~Buf() { release(); }
-  int ensure(size_t n) {
+  // slack: bytes allocated beyond n and never counted in `bytes` — what a GEMM may read past an operand (gemm_guard below); every buffer that a GEMM
+  // reads passes it where it is allocated
+  int ensure(size_t n, size_t slack = 0) {
     if (n <= bytes) return K5_OK;
     if (p) (void)hipFree(p);
     p = nullptr; bytes = 0;
-    HIPCHK(hipMalloc(&p, n));
+    HIPCHK(hipMalloc(&p, n + slack));
     bytes = n;
     return K5_OK;
   }
@@ -117,8 +119,12 @@ struct k5_vae {
 
 namespace {
 
+// the widest activation row of the schedule, in channels
+size_t widest_rows(const k5_vae_config& c) { size_t m = 64; for (int i = 0; i < 4; ++i) m = std::max(m, (size_t)c.block_out_channels[i]); return m; }
 int upload_f32(Buf& b, const float* src, size_t n) { K5CHK(b.ensure(n * 4)); HIPCHK(hipMemcpy(b.p, src, n * 4, hipMemcpyHostToDevice)); return K5_OK; }
-int upload_bf16(Buf& b, const std::vector<uint16_t>& v) { K5CHK(b.ensure(v.size() * 2)); HIPCHK(hipMemcpy(b.p, v.data(), v.size() * 2, hipMemcpyHostToDevice)); return K5_OK; }
+// bytes of the K5_GEMM_GUARD_ROWS rows (k5_kernels.h) a GEMM may read past a bf16 operand whose rows are row_elems long
+size_t gemm_guard(size_t row_elems) { return (size_t)K5_GEMM_GUARD_ROWS * row_elems * 2; }
+int upload_bf16(Buf& b, const std::vector<uint16_t>& v, size_t slack = 0) { K5CHK(b.ensure(v.size() * 2, slack)); HIPCHK(hipMemcpy(b.p, v.data(), v.size() * 2, hipMemcpyHostToDevice)); return K5_OK; }
 int upload_bias(Buf& b, const float* src, size_t n) {  // autocast casts the bias to bf16
   std::vector<float> t(n);
   for (size_t i = 0; i < n; ++i) t[i] = bf16_roundf(src[i]);
@@ -139,7 +145,7 @@ int pack_conv(k5_vae* v, const std::string& name, Conv& c) {
     for (int i = 0; i < c.cin; ++i)
       for (int t = 0; t < taps; ++t)
         p[((size_t)o * taps + t) * c.cin_pad + i] = bf16_rne(w->d[((size_t)o * c.cin + i) * taps + t]);
-  K5CHK(upload_bf16(c.w, p));
+  K5CHK(upload_bf16(c.w, p, c.k == 1 ? gemm_guard(c.cin_pad) : 0));   // 1x1x1: the weight operand of a GEMM
   K5CHK(upload_bias(c.b, b->d.data(), c.cout));
   return K5_OK;
 }
@@ -170,11 +176,11 @@ int pack_mid_attn(k5_vae* v, const std::string& ap, MidAttn& a) {
   K5CHK(pack_gn(v, ap + "group_norm", a.gn));
   std::vector<uint16_t> w; std::vector<float> b;
   K5CHK(pack_linear(v, ap + "to_q", w, b)); K5CHK(pack_linear(v, ap + "to_k", w, b));
-  K5CHK(upload_bf16(a.wqk, w)); K5CHK(upload_f32(a.bqk, b.data(), b.size()));
+  K5CHK(upload_bf16(a.wqk, w, gemm_guard(a.gn.c))); K5CHK(upload_f32(a.bqk, b.data(), b.size()));
   w.clear(); b.clear(); K5CHK(pack_linear(v, ap + "to_v", w, b));
-  K5CHK(upload_bf16(a.wv, w)); K5CHK(upload_f32(a.bv, b.data(), b.size()));
+  K5CHK(upload_bf16(a.wv, w, gemm_guard(a.gn.c))); K5CHK(upload_f32(a.bv, b.data(), b.size()));
   w.clear(); b.clear(); K5CHK(pack_linear(v, ap + "to_out.0", w, b));
-  K5CHK(upload_bf16(a.wo, w)); K5CHK(upload_f32(a.bo, b.data(), b.size()));
+  K5CHK(upload_bf16(a.wo, w, gemm_guard(a.gn.c))); K5CHK(upload_f32(a.bo, b.data(), b.size()));
   std::vector<float> one(a.gn.c, 1.0f);
   return upload_f32(a.ones, one.data(), one.size());
 }
@@ -269,8 +275,8 @@ int mid_attention(k5_vae* v, hipStream_t s, const MidAttn& a, void* h, int T, in
   static const bool flash_ok = !(getenv("K5_VAE_FLASH") && atoi(getenv("K5_VAE_FLASH")) == 0);   // A/B switch for benchmarking
   const bool flash = flash_ok && a.gn.c == 512;   // one kernel, no score matrix (vae_attn.hip); other widths: GEMM - softmax - GEMM
   const int C = a.gn.c, S = T * H * W, Sp = (int)rup(S, flash ? 32 : 8);
-  K5CHK(v->qk.ensure((size_t)S * 2 * C * 2)); K5CHK(v->vt.ensure((size_t)C * Sp * 2)); K5CHK(v->o.ensure((size_t)S * C * 2));
-  if (!flash) { K5CHK(v->scores.ensure((size_t)S * Sp * 4)); K5CHK(v->P.ensure((size_t)S * Sp * 2)); }
+  K5CHK(v->qk.ensure((size_t)S * 2 * C * 2, gemm_guard(2 * C))); K5CHK(v->vt.ensure((size_t)C * Sp * 2, gemm_guard(Sp))); K5CHK(v->o.ensure((size_t)S * C * 2, gemm_guard(C)));
+  if (!flash) { K5CHK(v->scores.ensure((size_t)S * Sp * 4)); K5CHK(v->P.ensure((size_t)S * Sp * 2, gemm_guard(Sp))); }
   ++v->path[flash ? 6 : 7];
   K5CHK(gn(v, s, a.gn, h, v->bt1.p, S, false));
   K5CHK(k5_launch_gemm_bf16(v->bt1.p, a.wqk.p, a.bqk.as<float>(), v->qk.p, S, 2 * C, C, C, C, 2 * C, K5_EPI_BIAS, nullptr, 0, nullptr, s));
@@ -421,8 +427,8 @@ extern "C" int k5_vae_decode_tile_strided(k5_vae* v, const float* z, int64_t z_c
     }
   }
   const int M0 = T * H * W;
-  K5CHK(v->zin.ensure((size_t)M0 * Cz * 2)); K5CHK(v->x0.ensure((size_t)M0 * 64 * 2));
-  for (Buf* b : {&v->bx, &v->balt, &v->bt1, &v->bt2, &v->bres}) K5CHK(b->ensure(maxel * 2));
+  K5CHK(v->zin.ensure((size_t)M0 * Cz * 2, gemm_guard(Cz))); K5CHK(v->x0.ensure((size_t)M0 * 64 * 2));
+  for (Buf* b : {&v->bx, &v->balt, &v->bt1, &v->bt2, &v->bres}) K5CHK(b->ensure(maxel * 2, gemm_guard(widest_rows(v->cfg))));   // operands of the 1x1x1 and attention GEMMs
   // post_quant_conv (1x1x1) into a 64-channel zero-padded buffer, then conv_in
   K5CHK(k5_launch_nchw_to_mc(z, v->zin.p, Cz, M0, Cz, s, z_channel_stride));
   HIPCHK(hipMemsetAsync(v->x0.p, 0, (size_t)M0 * 64 * 2, s));
@@ -474,7 +480,7 @@ extern "C" int k5_vae_encode_tile(k5_vae* v, const float* x, int T, int H, int W
   }
   const int M0 = T * H * W;
   K5CHK(v->xin.ensure((size_t)M0 * 64 * 2));
-  for (Buf* b : {&v->bx, &v->balt, &v->bt1, &v->bt2, &v->bres}) K5CHK(b->ensure(maxel * 2));
+  for (Buf* b : {&v->bx, &v->balt, &v->bt1, &v->bt2, &v->bres}) K5CHK(b->ensure(maxel * 2, gemm_guard(widest_rows(v->cfg))));   // operands of the 1x1x1 and attention GEMMs
   K5CHK(k5_launch_nchw_to_mc(x, v->xin.p, Cin, M0, 64, s));     // channels 3..63 zero: conv_in's weight is packed to 64 input channels
   K5CHK(conv(v, s, v->e_conv_in, v->xin.p, v->bx.p, T, H, W, 1, 1, nullptr));
   void* cur = v->bx.p;
