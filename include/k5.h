@@ -188,7 +188,8 @@ int k5_attention_bf16_balanced(const void* Q, const void* K, const void* Vt, voi
  * fast_sta_nabla :108-133) + flex_attention(q,k,v,block_mask) (nn.py:257-280), tokens in fractal order
  * (utils.py:31-41): N = T*Hb*Wb*64.  k5_nabla_select_bf16 fills `workspace` (k5_nabla_workspace_size bytes) with the
  * block map of every (head, 64-query block); k5_attention_nabla_bf16 consumes it; k5_nabla_mask_u8 expands the map to
- * uint8 [H][N/64][N/64] (tests / diagnostics) and k5_nabla_counts copies the kept-block count per row. */
+ * uint8 [H][N/64][N/64] (tests / diagnostics); k5_dit_nabla_block_counts reports an engine's kept-block totals.
+ * P >= 1 keeps every block, as the reference's `cvals >= 1 - thr` does. */
 int64_t k5_nabla_workspace_size(int H, int num_blocks);
 int k5_nabla_select_bf16(const void* q, const void* k, int ldq, int ldk, int H, int N, int T, int Hb, int Wb, int wT,
                          int wH, int wW, float P, void* workspace, void* stream);

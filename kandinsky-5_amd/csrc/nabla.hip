@@ -8,7 +8,9 @@
 //                          prefix whose cumulative sum stays below 1-P (`cvals >= 1 - thr`), OR the sliding-tile
 //                          window |dt|<=wT/2, |dh|<=wH/2, |dw|<=wW/2.  No sort: the cut value is found by bisection on
 //                          the fp32 bit pattern (monotone for non-negative floats); entries EQUAL to the cut value are
-//                          ranked by index like a stable ascending sort.  Output: one bit per (query block, kv block).
+//                          ranked by index like a stable ascending sort.  P >= 1 (cut at 0): `cvals >= 0` holds for every entry, so
+//                          every real block j < nb is kept — also one whose probability underflowed to 0, which is neither above
+//                          the smallest positive value nor tied with it.  Output: one bit per (query block, kv block).
 //   3. nabla_union_kernel  the attention workgroup covers 4 query blocks: OR their rows, compact the kv-block ids and
 //                          attach a 4-bit membership mask (which of the 4 query blocks wants that kv block).
 // The sparse attention kernel itself is attn_fwd.hip (SPARSE variant).
@@ -230,7 +232,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
       if (c + 1 < p.nw || j < p.nb) {                  // only the last word can hold padding
         const unsigned vb = __float_as_uint(pv[c]);
         tie = vb == vbits;
-        keep = vb > vbits;
+        keep = vb > vbits || !(p.target > 0.f);      // P >= 1: the reference keeps every block, underflowed ones included
         const int tj = hw_blocks == 1 ? j : (int)__umulhi((unsigned)j, p.magic_hw), rj = j - tj * hw_blocks;
         const int hj = p.Wb == 1 ? rj : (int)__umulhi((unsigned)rj, p.magic_w), wj = rj - hj * p.Wb;
         keep = keep || (abs(ti - tj) <= p.wT / 2 && abs(hi_ - hj) <= p.wH / 2 && abs(wi - wj) <= p.wW / 2);

@@ -79,7 +79,7 @@ def _may_differ(q, k, P, tol, mode="bf16"):
 @pytest.mark.parametrize("grid,window,P,H", [((6, 2, 2), (3, 1, 1), 0.7, 2), ((10, 3, 4), (5, 3, 3), 0.9, 3),
                                              ((4, 2, 3), (11, 3, 3), 0.5, 1), ((3, 1, 1), (1, 1, 1), 0.9, 2),
                                              # one case per register-resident instantiation of the select kernel (values per lane x rows
-                                             # per wave): 600 blocks <16,4>, 1464 (the 10 s clip) <24,4>, 1600 <32,4>, 2100 <64,2>
+                                             # per wave): 600 blocks <16,4>, 1464 (the 10 s clip) <24,4>, 1600 <32,4>, 2100 = NV 48 (33 words; NV 64 starts at 3073 blocks)
                                              ((25, 4, 6), (5, 3, 3), 0.9, 2), ((61, 4, 6), (11, 3, 3), 0.9, 2),
                                              ((25, 8, 8), (11, 3, 3), 0.9, 1), ((35, 6, 10), (5, 3, 3), 0.8, 1),
                                              # BASELINE config 5's own row length: (61, 96, 160) latent = 61 x 6 x 10 = 3660 blocks (<64,2>)
