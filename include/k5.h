@@ -436,9 +436,10 @@ int k5_flowedit_step(const k5_flowedit_step_args* args, void* stream);
  * DEVICE int32 [nwin], window i covers frames starts[i] .. starts[i] + F - 1; weights_dev DEVICE fp32 [nwin][F], the share of window i's local
  * frame j (kandinsky.generation_utils.context_windows builds both).  Every element of frame t walks the windows that cover t in window order:
  * v_i as k5_cfg_euler forms it (the same three bf16 roundings), acc = rn(wt_0 * v_0), then acc = rn(acc + rn(wt_i * v_i)), nothing contracted;
- * img = rn(img + bf16(rn(dt * acc))).  One window of weight 1 is k5_cfg_euler bit for bit.  One pass over img.  K5_ERR_ARG + message, nothing
- * launched: a NULL pointer, nwin outside 1..64, F < 1, or a window reaching outside 0..T-1 (the nwin starts are read back once, which
- * synchronises the stream). */
+ * img = rn(img + bf16(rn(dt * acc))).  One window of weight 1 is k5_cfg_euler bit for bit.  One pass over img.  This entry IS k5_cfg_euler_tiles
+ * below, on the clip (T, 1, 1, frame_elems) with one row window and one column window of weight 1.0, whose share rn(rn(wt * 1) * 1) is wt itself.
+ * K5_ERR_ARG + message, nothing launched: a NULL pointer, nwin outside 1..64, F < 1, frame_elems outside 1 .. 2^31 - 1, starts that do not
+ * ascend, a window reaching outside 0..T-1, or a frame no window covers (the nwin starts are read back once, which synchronises the stream). */
 int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts_dev,
                          const float* weights_dev, int nwin, int F, int T, int64_t frame_elems, void* stream);
 /* k5_cfg_euler over a 3-D plan of context windows (spatial tiles; added under ABI 11, as the exports above were).  img fp32 (T,H,W,C); the
@@ -451,7 +452,7 @@ int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, f
  *   4. acc = rn(s_0 * v_0), then acc = rn(acc + rn(s_k * v_k));
  *   5. nothing is contracted;
  *   6. img = rn(img + bf16(rn(dt * acc))).
- * ny = nx = 1 with weights 1.0 is k5_cfg_euler_windows bit for bit, one window of weight 1 is k5_cfg_euler bit for bit.  One pass over img;
+ * ny = nx = 1 with weights 1.0 is a temporal plan (k5_cfg_euler_windows), one window of weight 1 is k5_cfg_euler bit for bit.  One pass over img;
  * only velocity slots inside a window's box are read, whatever the tables hold.  K5_ERR_ARG + message, nothing launched: a NULL pointer, nwin
  * outside 1..64, an extent or window size < 1, starts of an axis that do not ascend, a window reaching outside the clip, or a cell no window
  * covers (the nt + ny + nx starts are read back once, which synchronises the stream). */
@@ -680,11 +681,14 @@ int k5_dit_flowedit_state(k5_dit* dit, long long* steps, long long* forwards, lo
  *   starts HOST [nwin], ascending, 0 <= starts[i], starts[i] + fwd.T <= total_T, every frame covered; weights HOST [nwin][fwd.T].
  *   conds / null_conds: HOST [nwin] prompts, one per window, or NULL = sample.fwd.cond / sample.null_cond for every window.
  *   visual_cond (k5_sample_cond): device fp32 (total_T,H,W,in_visual_dim+1) or NULL.
+ * This entry IS k5_sample_tiles below with one row window and one column window of weight 1.0 that span the clip (ny = nx = 1, total_H = fwd.H,
+ * total_W = fwd.W): such windows are whole frames, so the forwards read their contiguous slices as they always did.
  * total_T <= fwd.T (one window) is k5_sample_cond on total_T frames.  Always eager, also with k5_dit_set_graph on.  A watch without previews
  * works (progress, cancel; info->T = total_T).  Refused before anything is enqueued, with a message: K5_ERR_STATE on a handle in a
  * sequence-parallel group or a CFG pair (any transport), with MagCache or its calibration set (the table is indexed by the call of a plain run),
  * with a watch that has previews (the preview reads one velocity pair per cell); K5_ERR_ARG for nwin outside 1..64, starts that do not ascend or
- * leave 0..total_T, a frame without a window, NULL starts / weights. */
+ * leave 0..total_T, a frame without a window, NULL starts / weights, odd fwd.H or fwd.W (the check of every window plan: an odd latent is
+ * refused before anything is enqueued, not inside the first forward). */
 typedef struct k5_sample_windows_args {
   k5_sample_args sample;
   int total_T, nwin;
@@ -709,7 +713,7 @@ int k5_sample_windows(k5_dit* dit, const k5_sample_windows_args* args, const flo
  *   conds / null_conds: HOST [nt * ny * nx] prompts, one per window, or NULL.
  *   visual_cond: device fp32 (total_T,total_H,total_W,in_visual_dim+1) or NULL; each window sees its slice through the view.
  * A clip no larger than the window in every axis is k5_sample_cond on the whole clip; ny = nx = 1 with total_H = fwd.H and total_W = fwd.W is
- * k5_sample_windows (its launches, its bits).  Always eager, also with k5_dit_set_graph on.  A watch without previews works (progress, cancel;
+ * a temporal plan, what k5_sample_windows passes.  Always eager, also with k5_dit_set_graph on.  A watch without previews works (progress, cancel;
  * info reports the whole clip's extents).  NAG and Enhance-A-Video work.  Refused before anything is enqueued, by the same checks and error
  * codes as k5_sample_windows: rank groups, CFG pairs, MagCache or its calibration, a watch with previews, a forecast plan with forecast
  * steps, guidance plans, skip-layer guidance, a stochastic plan, regions; K5_ERR_ARG for a plan that does not hold (nwin outside 1..64, an

@@ -375,7 +375,7 @@ struct k5_dit {
   DevBuf ws_xp, ws_vis, ws_h, ws_qk, ws_vt, ws_o, ws_ff, ws_y;
   DevBuf ws_vcos, ws_vsin, ws_pos;
   DevBuf ws_vel_c, ws_vel_u;
-  DevBuf ws_win;                                   // k5_sample_windows: the call's plan, [nwin] int32 starts then [nwin][F] fp32 weights
+  DevBuf ws_win;                                   // a windowed run: the call's plan, the three int32 start vectors then the three fp32 weight tables
   // sequence parallelism (token shards): this rank owns rows [sp_rank*n_loc, (sp_rank+1)*n_loc) of the N visual
   // tokens; K and V^T of every block are all-gathered in place into ws_kfull [N][D] / ws_vtfull [P][D][n_loc]
   Comm comm;
@@ -2658,11 +2658,28 @@ static const char* rank_group(const k5_dit* d) {
   return d->comm.active() ? "sequence-parallel group" : d->pair.active() ? "CFG pair" : nullptr;
 }
 
+// The latent of an editing mode (`mode`: "edit" / "FlowEdit") is output only: it is 4-byte aligned, and so is every borrowed input, none of
+// which overlaps it
+struct Borrowed { const float* p; int64_t elems; const char* name; };
+static int borrowed_refusal(const char* who, const char* mode, const float* latent, int64_t n, std::initializer_list<Borrowed> in) {
+  const uintptr_t l0 = reinterpret_cast<uintptr_t>(latent), l1 = l0 + (uintptr_t)n * 4;
+  if (l0 & 3) { k5_set_error("%s: latent is not 4-byte aligned", who); return K5_ERR_ARG; }
+  for (const auto& t : in) {
+    if (!t.p) continue;
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(t.p), p1 = p0 + (uintptr_t)t.elems * 4;
+    if (p0 & 3) { k5_set_error("%s: %s %s is not 4-byte aligned", who, mode, t.name); return K5_ERR_ARG; }
+    if (p0 < l1 && l0 < p1) { k5_set_error("%s: %s %s overlaps latent (latent is output only)", who, mode, t.name); return K5_ERR_ARG; }
+  }
+  return K5_OK;
+}
+
 // Everything sample_impl refuses, before anything is enqueued or allocated and before any per-call state is touched: no HIP call and no
 // write to the handle here (the forward's side of the same contract: forward_refusals).  (A watched call's shape check comes later, where it always was: Watch::begin.)
+// `tile`: the window plan of k5_sample_tiles / k5_sample_windows (nullptr: a plain run).  A temporal plan is a 3-D plan with one row window and
+// one column window, so it meets the 3-D checks: among them "rows and columns must be even", which refuses a temporal plan on an odd latent
+// here, before anything is enqueued, and not inside its first forward.
 static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit,
-                           const k5_sample_windows_args* win, const char* who, const k5_flowedit_args* fe = nullptr,
-                           const k5_sample_tiles_args* tile = nullptr) {
+                           const k5_sample_tiles_args* tile, const char* who, const k5_flowedit_args* fe = nullptr) {
   if (!d || !a || !a->latent || !a->sigmas || a->num_steps <= 0) return K5_ERR_ARG;
   const k5_dit_config& c = d->cfg;
   const char* const mag = magcache_mode(d);
@@ -2673,16 +2690,8 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
   if (edit) {   // the latent is output only and must not be one of the borrowed inputs
     if (!edit->source || !edit->noise) { k5_set_error("%s: edit needs source and noise", who); return K5_ERR_ARG; }
     if (n <= 0) { k5_set_error("%s: bad shapes", who); return K5_ERR_ARG; }
-    const uintptr_t l0 = reinterpret_cast<uintptr_t>(a->latent), l1 = l0 + (uintptr_t)n * 4;
-    const struct { const float* p; int64_t elems; const char* name; } in[3] = {
-        {edit->source, n, "source"}, {edit->noise, n, "noise"}, {edit->keep_mask, n / c.out_visual_dim, "keep_mask"}};
-    if (l0 & 3) { k5_set_error("%s: latent is not 4-byte aligned", who); return K5_ERR_ARG; }
-    for (const auto& t : in) {
-      if (!t.p) continue;
-      const uintptr_t p0 = reinterpret_cast<uintptr_t>(t.p), p1 = p0 + (uintptr_t)t.elems * 4;
-      if (p0 & 3) { k5_set_error("%s: edit %s is not 4-byte aligned", who, t.name); return K5_ERR_ARG; }
-      if (p0 < l1 && l0 < p1) { k5_set_error("%s: edit %s overlaps latent (latent is output only)", who, t.name); return K5_ERR_ARG; }
-    }
+    K5CHK(borrowed_refusal(who, "edit", a->latent, n, {{edit->source, n, "source"}, {edit->noise, n, "noise"},
+                                                       {edit->keep_mask, n / c.out_visual_dim, "keep_mask"}}));
   }
   if (fe) {   // FlowEdit: every forward and update of a step is this mode's own, so what changes either is refused, not half honoured
     if (!fe->source || !fe->source_cond.text_embed) { k5_set_error("%s: FlowEdit needs a source latent and a source prompt", who); return K5_ERR_ARG; }
@@ -2695,16 +2704,8 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
       k5_set_error("%s: refine = %d with a keep_mask: the keep rule of a plain step needs an eps this mode does not have", who, fe->refine);
       return K5_ERR_ARG;
     }
-    const uintptr_t l0 = reinterpret_cast<uintptr_t>(a->latent), l1 = l0 + (uintptr_t)n * 4;
-    const struct { const float* p; int64_t elems; const char* name; } in[3] = {
-        {fe->source, n, "source"}, {fe->keep_mask, n / c.out_visual_dim, "keep_mask"}, {vcond, n / c.out_visual_dim * (c.in_visual_dim + 1), "visual_cond"}};
-    if (l0 & 3) { k5_set_error("%s: latent is not 4-byte aligned", who); return K5_ERR_ARG; }
-    for (const auto& t : in) {
-      if (!t.p) continue;
-      const uintptr_t p0 = reinterpret_cast<uintptr_t>(t.p), p1 = p0 + (uintptr_t)t.elems * 4;
-      if (p0 & 3) { k5_set_error("%s: FlowEdit %s is not 4-byte aligned", who, t.name); return K5_ERR_ARG; }
-      if (p0 < l1 && l0 < p1) { k5_set_error("%s: FlowEdit %s overlaps latent (latent is output only)", who, t.name); return K5_ERR_ARG; }
-    }
+    K5CHK(borrowed_refusal(who, "FlowEdit", a->latent, n, {{fe->source, n, "source"}, {fe->keep_mask, n / c.out_visual_dim, "keep_mask"},
+                                                           {vcond, n / c.out_visual_dim * (c.in_visual_dim + 1), "visual_cond"}}));
     if (rank_group(d)) {
       k5_set_error("%s: the handle is in a %s: the forwards of a FlowEdit step are not split over ranks", who, rank_group(d));
       return K5_ERR_STATE;
@@ -2727,7 +2728,7 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
     return K5_ERR_STATE;
   }
   const k5_dit::Regions& rg = d->regions;
-  if (rg.on && win) {
+  if (rg.on && tile) {
     k5_set_error("%s: regional prompts are set (k5_dit_set_regions): the masks cover the clip, a context window sees a slice of it", who);
     return K5_ERR_STATE;
   }
@@ -2736,17 +2737,17 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
     return K5_ERR_ARG;
   }
   const k5_dit::Guidance& gd = d->guide;
+  int guided = 0, unguided = 0;   // the steps of the guidance plan, by kind
   if (gd.on) {
     const int N = a->num_steps;
     if (!gd.weights.empty() && (int)gd.weights.size() != N) {
       k5_set_error("%s: the guidance plan has %d weights, this call %d steps", who, (int)gd.weights.size(), N);
       return K5_ERR_ARG;
     }
-    int guided = 0, unguided = 0;
     for (int i = 0; i < N; ++i) (fabsf((gd.weights.empty() ? a->guidance_weight : gd.weights[i]) - 1.0f) > 1e-6f ? guided : unguided) += 1;
     const bool mixed = guided && unguided, zinit = gd.zero_init > 0;
     const char* what = zinit ? "zero-init steps" : "guided and unguided steps";
-    if (win) {
+    if (tile) {
       k5_set_error("%s: a guidance plan is set (k5_dit_set_guidance): one statistic per window is not the published rule", who);
       return K5_ERR_STATE;
     }
@@ -2782,7 +2783,7 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
                    who, mag);
       return K5_ERR_STATE;
     }
-    if (win) {
+    if (tile) {
       k5_set_error("%s: skip-layer guidance is set (k5_dit_set_skip_guidance): a windowed step has one velocity pair per window, the skip branch is not built for it", who);
       return K5_ERR_STATE;
     }
@@ -2797,16 +2798,12 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
       k5_set_error("%s: a forecast plan is set (k5_dit_set_forecast) and skip-layer guidance (k5_dit_set_skip_guidance): the skip branch has no slot", who);
       return K5_ERR_STATE;
     }
-    if (gd.on) {
-      int guided = 0, unguided = 0;
-      for (int i = 0; i < a->num_steps; ++i) (fabsf((gd.weights.empty() ? a->guidance_weight : gd.weights[i]) - 1.0f) > 1e-6f ? guided : unguided) += 1;
-      if ((guided && unguided) || gd.zero_init > 0) {
-        k5_set_error("%s: a forecast plan is set (k5_dit_set_forecast) and the guidance plan has %s: the unconditional slot would have gaps", who,
-                     gd.zero_init > 0 ? "zero-init steps" : "guided and unguided steps");
-        return K5_ERR_STATE;
-      }
+    if (gd.on && ((guided && unguided) || gd.zero_init > 0)) {
+      k5_set_error("%s: a forecast plan is set (k5_dit_set_forecast) and the guidance plan has %s: the unconditional slot would have gaps", who,
+                   gd.zero_init > 0 ? "zero-init steps" : "guided and unguided steps");
+      return K5_ERR_STATE;
     }
-    if (win) {
+    if (tile) {
       k5_set_error("%s: a forecast plan is set (k5_dit_set_forecast): a windowed step makes nwin calls per slot, the cache holds one residual per slot", who);
       return K5_ERR_STATE;
     }
@@ -2838,7 +2835,7 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
       k5_set_error("%s: the stochastic plan has %d steps, this call %d", who, (int)so.dt_down.size(), a->num_steps);
       return K5_ERR_ARG;
     }
-    if (win) {
+    if (tile) {
       k5_set_error("%s: a stochastic plan is set (k5_dit_set_stochastic): the windowed update blends one velocity pair per window and has no noise term", who);
       return K5_ERR_STATE;
     }
@@ -2852,7 +2849,7 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
       return K5_ERR_STATE;
     }
   }
-  if (win) {
+  if (tile) {
     if (edit) { k5_set_error("%s: editing with context windows is not supported", who); return K5_ERR_UNSUPPORTED; }
     if (rank_group(d)) { k5_set_error("%s: the handle is in a %s (context windows are single-rank only)", who, rank_group(d)); return K5_ERR_STATE; }
     if (mag) {
@@ -2864,47 +2861,25 @@ static int sample_refusals(const k5_dit* d, const k5_sample_args* a, const float
                    "install the watch with preview_every = 0", who, wt.every);
       return K5_ERR_STATE;
     }
-    const int F = a->fwd.T;
-    if (tile) {   // a 3-D plan: each axis on its own, by the rule of the temporal one; spatial windows start on a patch
-      if (tile->nt < 1 || tile->ny < 1 || tile->nx < 1 || tile->nt > 64 || tile->ny > 64 || tile->nx > 64 || tile->nt * tile->ny * tile->nx > 64 ||
-          !tile->wt || !tile->wy || !tile->wx || n <= 0) {
-        k5_set_error("%s: nwin must be 1..64 (got %d x %d x %d) with starts, weights and a window shape", who, tile->nt, tile->ny, tile->nx);
-        return K5_ERR_ARG;
-      }
-      if (reinterpret_cast<uintptr_t>(a->latent) & 3) { k5_set_error("%s: latent is not 4-byte aligned", who); return K5_ERR_ARG; }
-      if ((tile->total_H & 1) || (tile->total_W & 1) || (a->fwd.H & 1) || (a->fwd.W & 1)) {
-        k5_set_error("%s: the clip's and the window's rows and columns must be even (clip %d x %d, window %d x %d)", who, tile->total_H, tile->total_W,
-                     a->fwd.H, a->fwd.W);
-        return K5_ERR_ARG;
-      }
-      const struct { const char* name; int n; const int32_t* st; int F, total; bool even; } ax[3] = {
-          {"frame", tile->nt, tile->starts_t, F, tile->total_T, false}, {"row", tile->ny, tile->starts_y, a->fwd.H, tile->total_H, true},
-          {"column", tile->nx, tile->starts_x, a->fwd.W, tile->total_W, true}};
-      for (const auto& x : ax) {
-        if (const char* why = k5_tile_axis_refusal(x.name, x.n, x.st, x.F, x.total)) { k5_set_error("%s: %s", who, why); return K5_ERR_ARG; }
-        for (int i = 0; x.even && i < x.n; ++i)
-          if (x.st[i] & 1) { k5_set_error("%s: %s window %d starts at %d: spatial windows start on a patch (an even cell)", who, x.name, i, x.st[i]); return K5_ERR_ARG; }
-      }
-      return K5_OK;
-    }
-    if (win->nwin < 1 || win->nwin > 64 || !win->starts || !win->weights || F < 1 || n <= 0) {
-      k5_set_error("%s: nwin must be 1..64 (got %d) with starts, weights and a window shape", who, win->nwin);
+    // the plan: each axis on its own, by one rule (k5_tile_axis_refusal); spatial windows start on a patch
+    if (tile->nt < 1 || tile->ny < 1 || tile->nx < 1 || tile->nt > 64 || tile->ny > 64 || tile->nx > 64 || tile->nt * tile->ny * tile->nx > 64 ||
+        !tile->wt || !tile->wy || !tile->wx || n <= 0) {
+      k5_set_error("%s: nwin must be 1..64 (got %d x %d x %d) with starts, weights and a window shape", who, tile->nt, tile->ny, tile->nx);
       return K5_ERR_ARG;
     }
     if (reinterpret_cast<uintptr_t>(a->latent) & 3) { k5_set_error("%s: latent is not 4-byte aligned", who); return K5_ERR_ARG; }
-    for (int i = 0; i < win->nwin; ++i) {
-      const int st = win->starts[i];
-      if (st < 0 || (int64_t)st + F > win->total_T) {
-        k5_set_error("%s: window %d (frames %d .. %lld) reaches outside the %d frames", who, i, st, (long long)st + F - 1, win->total_T);
-        return K5_ERR_ARG;
-      }
-      if (i > 0 && st <= win->starts[i - 1]) { k5_set_error("%s: starts must ascend (starts[%d] = %d after %d)", who, i, st, win->starts[i - 1]); return K5_ERR_ARG; }
-      const int covered_to = i == 0 ? 0 : win->starts[i - 1] + F;   // first frame the windows before i leave uncovered
-      if (st > covered_to) { k5_set_error("%s: no window covers frame %d", who, covered_to); return K5_ERR_ARG; }
-    }
-    if (win->starts[win->nwin - 1] + F < win->total_T) {
-      k5_set_error("%s: no window covers frame %d", who, win->starts[win->nwin - 1] + F);
+    if ((tile->total_H & 1) || (tile->total_W & 1) || (a->fwd.H & 1) || (a->fwd.W & 1)) {
+      k5_set_error("%s: the clip's and the window's rows and columns must be even (clip %d x %d, window %d x %d)", who, tile->total_H, tile->total_W,
+                   a->fwd.H, a->fwd.W);
       return K5_ERR_ARG;
+    }
+    const struct { const char* name; int n; const int32_t* st; int F, total; bool even; } ax[3] = {
+        {"frame", tile->nt, tile->starts_t, a->fwd.T, tile->total_T, false}, {"row", tile->ny, tile->starts_y, a->fwd.H, tile->total_H, true},
+        {"column", tile->nx, tile->starts_x, a->fwd.W, tile->total_W, true}};
+    for (const auto& x : ax) {
+      if (const char* why = k5_tile_axis_refusal(x.name, x.n, x.st, x.F, x.total)) { k5_set_error("%s: %s", who, why); return K5_ERR_ARG; }
+      for (int i = 0; x.even && i < x.n; ++i)
+        if (x.st[i] & 1) { k5_set_error("%s: %s window %d starts at %d: spatial windows start on a patch (an even cell)", who, x.name, i, x.st[i]); return K5_ERR_ARG; }
     }
   }
   return K5_OK;
@@ -2914,16 +2889,17 @@ namespace {
 
 // What one sample_impl call works on: filled top to bottom by sample_impl before the first step, read by step(i) and by the watch.
 struct SampleRun {
-  k5_dit* d; const k5_sample_args* a; const float* vcond; const k5_edit_args* edit; const k5_sample_windows_args* win;
-  const k5_sample_tiles_args* tile = nullptr;   // k5_sample_tiles: win holds the window count and the prompts, this the 3-D plan
-  k5_tile_plan tile_dev{};                  //   ... and its tables on the device
-  int64_t x_frame = 0, x_row = 0, vc_frame = 0, vc_row = 0;   //   ... and the strides of a window's view of the latent and of vcond
+  k5_dit* d; const k5_sample_args* a; const float* vcond; const k5_edit_args* edit;
+  const k5_sample_tiles_args* tile;         // the window plan (nullptr: a plain run): a->fwd is the window, a->latent / vcond the whole clip
+  int nwin = 1;                             //   ... its nt * ny * nx windows
+  k5_tile_plan tile_dev{};                  //   ... its tables on the device
+  int64_t x_frame = 0, x_row = 0, vc_frame = 0, vc_row = 0;   //   ... and the strides of a window's view of the latent and of vcond (0: the window spans the rows and columns)
   const k5_flowedit_args* fe = nullptr;     // k5_sample_flowedit: steps below fe_steps are FlowEdit steps, the rest plain steps on the target side
   int fe_steps = 0;
   bool fe_src_cfg = false;                  //   the source side runs its unconditional forward
   int fe_src_slot = 0;                      //   the text cache slot of the source prompt (0: it is the target prompt)
   hipStream_t s = nullptr;
-  int64_t n = 0, cells = 0;                 // elements and cells of the latent one forward sees (with win: a window's)
+  int64_t n = 0, cells = 0;                 // elements and cells of the latent one forward sees (with a plan: a window's)
   bool cfg_on = false, pair = false;        // pair: CFG-parallel, one branch here, the other on the paired handle
   void* vel_c = nullptr; void* vel_u = nullptr;
   void* vel_s = nullptr;                    // skip-layer guidance: the skip branch's velocity (sized when the call has a skip step)
@@ -2933,7 +2909,6 @@ struct SampleRun {
   const float* sigma_next = nullptr;        //   where the kept region is re-noised to after step i (k5_sample_edit)
   const float* tvec = nullptr; const float* dtvec = nullptr; const float* signext = nullptr;   // graph mode: the same tables on the device ...
   int* step_ctr = nullptr;                                                                      // ... and the device-side step counter
-  const int32_t* win_starts = nullptr; const float* win_weights = nullptr;   // the window plan on the device
   const void* slot_prompt[2] = {nullptr, nullptr};   // windows with prompts of their own: whose prologue each text cache slot holds
   // the guidance plan (k5_dit_set_guidance; nullptr: none, every step is of the call's one kind and enqueues what it always did)
   const k5_dit::Guidance* plan = nullptr;
@@ -2951,9 +2926,9 @@ struct SampleRun {
     return fabsf(w_at(i) - 1.0f) > 1e-6f ? GUIDED : UNGUIDED;   // generation_utils.py:63
   }
   // a skip step (k5_dit_set_skip_guidance): the conditional forward forks and the update reads three velocities
-  bool skip_at(int i) const { return !win && d->skip.at(i) && kind(i) != ZERO; }
+  bool skip_at(int i) const { return !tile && d->skip.at(i) && kind(i) != ZERO; }
   // what the watch's preview of step i combines: a guided step with coefficients and a skip step left their v in vel_c, a zero step has velocity 0 there
-  const void* preview_vu(int i) const { return win ? (cfg_on ? vel_u : nullptr) : kind(i) == GUIDED && !stats && !skip_at(i) ? vel_u : nullptr; }
+  const void* preview_vu(int i) const { return tile ? (cfg_on ? vel_u : nullptr) : kind(i) == GUIDED && !stats && !skip_at(i) ? vel_u : nullptr; }
 
   // One forward of step i: the text condition through text cache slot `slot`, on the latent slice `x` with its conditioning slice `vc`, into
   // `vel`.  `tables`: the forward reads its time through the device-side step tables when the step is captured; windows pass none.
@@ -3011,7 +2986,7 @@ struct SampleRun {
     return K5_OK;
   }
 
-  int64_t tile_corner(int k) const {   // the cell of the whole clip at which window k = (it * ny + iy) * nx + ix of a 3-D plan begins
+  int64_t tile_corner(int k) const {   // the cell of the whole clip at which window k = (it * ny + iy) * nx + ix of the plan begins
     const int ix = k % tile->nx, iy = (k / tile->nx) % tile->ny, it = k / (tile->nx * tile->ny);
     return ((int64_t)tile->starts_t[it] * tile->total_H + tile->starts_y[iy]) * tile->total_W + tile->starts_x[ix];
   }
@@ -3019,19 +2994,15 @@ struct SampleRun {
   int step(int i) {   // enqueue step i: the forwards, then CFG + Euler
     const k5_dit_config& c = d->cfg;
     d->enh.gate = d->enh.at(i) ? 1 : 0;   // Enhance-A-Video: this step's forwards apply it or enqueue what they always did
-    void* const vu = (win ? cfg_on : kind(i) == GUIDED) ? vel_u : nullptr;
-    if (win) {
-      // every window on its own slice of the latent (T is outermost: a temporal window is contiguous), cond then uncond, into slot k of the
-      // velocity buffers; then one pass over the whole clip blends the windows and applies the step
-      const int64_t frame = n / a->fwd.T, vframe = frame / c.out_visual_dim * (c.in_visual_dim + 1);
-      for (int k = 0; k < win->nwin; ++k) {
-        const k5_text_cond& ck = win->conds ? win->conds[k] : a->fwd.cond;
-        const k5_text_cond& uk = win->null_conds ? win->null_conds[k] : a->null_cond;
-        // where window k begins: whole frames for a temporal plan, the corner cell of its box for a 3-D one (the view strides do the rest)
-        const int64_t xoff = tile ? tile_corner(k) * c.out_visual_dim : (int64_t)win->starts[k] * frame;
-        const int64_t voff = tile ? tile_corner(k) * (c.in_visual_dim + 1) : (int64_t)win->starts[k] * vframe;
-        const float* xk = a->latent + xoff;
-        const float* vk = vcond ? vcond + voff : nullptr;
+    void* const vu = (tile ? cfg_on : kind(i) == GUIDED) ? vel_u : nullptr;
+    if (tile) {
+      // every window on its own box of the latent, from its corner cell (the view strides do the rest; a window of whole frames is contiguous),
+      // cond then uncond, into slot k of the velocity buffers; then one pass over the whole clip blends the windows and applies the step
+      for (int k = 0; k < nwin; ++k) {
+        const k5_text_cond& ck = tile->conds ? tile->conds[k] : a->fwd.cond;
+        const k5_text_cond& uk = tile->null_conds ? tile->null_conds[k] : a->null_cond;
+        const float* xk = a->latent + tile_corner(k) * c.out_visual_dim;
+        const float* vk = vcond ? vcond + tile_corner(k) * (c.in_visual_dim + 1) : nullptr;
         if (slot_prompt[0] != ck.text_embed) { d->text_cache[0].valid = false; slot_prompt[0] = ck.text_embed; }
         K5CHK(forward(i, ck, 0, xk, static_cast<bf16_t*>(vel_c) + k * n, vk, false));
         if (cfg_on) {
@@ -3040,12 +3011,8 @@ struct SampleRun {
         }
       }
       Scope sc(d, s, "elementwise");
-      if (tile)
-        return k5_launch_cfg_euler_tiles(a->latent, vel_c, vu, a->guidance_weight, dt[i], tile_dev, tile->total_T, tile->total_H, tile->total_W,
-                                         c.out_visual_dim, s);
-      K5CHK(k5_launch_cfg_euler_windows(a->latent, vel_c, vu, a->guidance_weight, dt[i], win_starts, win_weights, win->nwin, a->fwd.T,
-                                        win->total_T, frame, s));
-      return K5_OK;
+      return k5_launch_cfg_euler_tiles(a->latent, vel_c, vu, a->guidance_weight, dt[i], tile_dev, tile->total_T, tile->total_H, tile->total_W,
+                                       c.out_visual_dim, s);
     }
     if (kind(i) == ZERO) return K5_OK;   // velocity 0: no forward, no update
     if (fe && i < fe_steps) return flowedit_step(i);
@@ -3143,7 +3110,7 @@ int k5_dit::Watch::step(const SampleRun& r, int i) {   // after step i is enqueu
     Scope sc(r.d, r.s, "elementwise");
     const int C = r.d->cfg.in_visual_dim;
     const float* w = wb.as<float>();
-    if (!r.win && r.kind(i) == SampleRun::ZERO) HIPCHK(hipMemsetAsync(r.vel_c, 0, (size_t)r.n * 2, r.s));   // a zero-init step: x0 = x
+    if (!r.tile && r.kind(i) == SampleRun::ZERO) HIPCHK(hipMemsetAsync(r.vel_c, 0, (size_t)r.n * 2, r.s));   // a zero-init step: x0 = x
     K5CHK(k5_launch_x0_preview(r.a->latent, r.vel_c, r.preview_vu(i), r.w_at(i), r.sigma_next[i],
                                r.edit ? r.edit->source : nullptr, r.edit ? r.edit->keep_mask : nullptr, w, w + 3 * C,
                                want_x0 ? x0[slot].as<float>() : nullptr, rgb[slot].as<uint8_t>(), r.cells, C, r.s));
@@ -3164,7 +3131,7 @@ int k5_dit::Watch::deliver(const SampleRun& r, int i) {
   info.sigma_next = r.sigma_next[i];
   info.rgb = pv ? h_rgb[slot] : nullptr;
   info.x0 = pv && want_x0 ? x0[slot].as<float>() : nullptr;
-  info.T = r.win ? r.win->total_T : r.a->fwd.T; info.H = r.tile ? r.tile->total_H : r.a->fwd.H; info.W = r.tile ? r.tile->total_W : r.a->fwd.W;
+  info.T = r.tile ? r.tile->total_T : r.a->fwd.T; info.H = r.tile ? r.tile->total_H : r.a->fwd.H; info.W = r.tile ? r.tile->total_W : r.a->fwd.W;
   info.C = r.d->cfg.in_visual_dim;
   if (fn(user, &info) != 0) stopped = 1;
   return K5_OK;
@@ -3177,17 +3144,17 @@ int k5_dit::Watch::end(const SampleRun& r) {   // the last step's callback; a st
   return K5_OK;
 }
 
-// The sampler loop behind k5_sample / k5_sample_cond (edit == nullptr: their launches, their bits), k5_sample_edit and k5_sample_windows
-// (win != nullptr: a->fwd is the window, a->latent / vcond the whole clip of win->total_T frames; never together with edit).
+// The sampler loop behind k5_sample / k5_sample_cond (edit == nullptr: their launches, their bits), k5_sample_edit, k5_sample_flowedit and
+// the windowed entries (tile != nullptr: a->fwd is the window, a->latent / vcond the whole clip of the plan; never together with edit or fe).
 static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, const k5_edit_args* edit, void* stream, const char* who,
-                       const k5_sample_windows_args* win = nullptr, const k5_flowedit_args* fe = nullptr,
-                       const k5_sample_tiles_args* tile = nullptr) {
+                       const k5_sample_tiles_args* tile = nullptr, const k5_flowedit_args* fe = nullptr) {
   g_err[0] = 0;
-  K5CHK(sample_refusals(d, a, vcond, edit, win, who, fe, tile));
+  K5CHK(sample_refusals(d, a, vcond, edit, tile, who, fe));
   const k5_dit_config& c = d->cfg;
   k5_dit::Watch& wt = d->watch;
-  SampleRun r{d, a, vcond, edit, win};
-  r.fe = fe; r.tile = tile;
+  SampleRun r{d, a, vcond, edit, tile};
+  r.fe = fe;
+  if (tile) r.nwin = tile->nt * tile->ny * tile->nx;
   r.s = (hipStream_t)stream;
   r.cells = (int64_t)a->fwd.T * a->fwd.H * a->fwd.W;
   r.n = r.cells * c.out_visual_dim;
@@ -3236,8 +3203,8 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   r.pair = r.cfg_on && d->pair.active();
   if (r.pair) K5CHK(d->ws_vel_pair.ensure(2 * r.n * 2));
   else {   // one slot per window
-    K5CHK(d->ws_vel_c.ensure((win ? win->nwin : 1) * r.n * 2));
-    if (r.cfg_on) K5CHK(d->ws_vel_u.ensure((win ? win->nwin : 1) * r.n * 2));
+    K5CHK(d->ws_vel_c.ensure(r.nwin * r.n * 2));
+    if (r.cfg_on) K5CHK(d->ws_vel_u.ensure(r.nwin * r.n * 2));
   }
   r.vel_c = r.pair ? d->ws_vel_pair.p : d->ws_vel_c.p;
   r.vel_u = r.pair ? (void*)(d->ws_vel_pair.as<bf16_t>() + r.n) : d->ws_vel_u.p;
@@ -3251,7 +3218,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
   // holds one forward pair).  The IPC transport IS replayable: its epochs live on the device and the peers' buffers were mapped by the eager
   // first step (ipc_comm.h)
   const bool graph = d->use_graph && !d->mag.on && !d->cal.on && !d->profiling && a->num_steps > 2 && !d->nabla_tap && !d->comm.loop && !d->pair.loop &&
-                     !win && !fe && uniform;   // FlowEdit: steps of two kinds, and the pass reads its scalars by value
+                     !tile && !fe && uniform;   // FlowEdit: steps of two kinds, and the pass reads its scalars by value
   if (d->sto.on) r.sto = &d->sto;
   const size_t sto_at = (gd.on ? 4 : 3) * (size_t)N;   // with a stochastic plan two more tables: scale and noise_coef
   r.host_tab.resize(sto_at + (r.sto ? 2 : 0) * (size_t)N);
@@ -3285,7 +3252,7 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     Scope sc(d, s, "elementwise");
     K5CHK(k5_launch_edit_renoise(a->latent, edit->source, edit->noise, a->sigmas[0], r.n, s));
   }
-  if (tile) {   // the 3-D plan, uploaded once per call: the three int32 start vectors, then the three fp32 weight tables
+  if (tile) {   // the plan, uploaded once per call: the three int32 start vectors, then the three fp32 weight tables
     const int cnt[3] = {tile->nt, tile->ny, tile->nx}, ext[3] = {a->fwd.T, a->fwd.H, a->fwd.W};
     const int32_t* st[3] = {tile->starts_t, tile->starts_y, tile->starts_x};
     const float* wg[3] = {tile->wt, tile->wy, tile->wx};
@@ -3305,15 +3272,12 @@ static int sample_impl(k5_dit* d, const k5_sample_args* a, const float* vcond, c
     r.tile_dev = k5_tile_plan{tile->nt, tile->ny, tile->nx, a->fwd.T, a->fwd.H, a->fwd.W, base + off[0], base + off[1], base + off[2],
                               reinterpret_cast<const float*>(base + off[3]), reinterpret_cast<const float*>(base + off[4]),
                               reinterpret_cast<const float*>(base + off[5])};
-    r.x_row = (int64_t)tile->total_W * c.out_visual_dim; r.x_frame = r.x_row * tile->total_H;
-    r.vc_row = (int64_t)tile->total_W * (c.in_visual_dim + 1); r.vc_frame = r.vc_row * tile->total_H;
-  } else if (win) {   // the plan, uploaded once per call: [nwin] int32 starts, then [nwin][F] fp32 weights
-    const size_t sb = (size_t)win->nwin * 4, wb = (size_t)win->nwin * a->fwd.T * 4;
-    K5CHK(d->ws_win.ensure(sb + wb));
-    HIPCHK(hipMemcpyAsync(d->ws_win.p, win->starts, sb, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(static_cast<char*>(d->ws_win.p) + sb, win->weights, wb, hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));   // the caller's tables are host memory
-    r.win_starts = d->ws_win.as<int32_t>(); r.win_weights = reinterpret_cast<const float*>(static_cast<char*>(d->ws_win.p) + sb);
+    // the one place the plan's shape is looked at: a window that spans the clip's rows and columns is whole frames, contiguous, and its
+    // forwards take the compact patchify kernels; any other window is a strided view
+    if (a->fwd.H != tile->total_H || a->fwd.W != tile->total_W) {
+      r.x_row = (int64_t)tile->total_W * c.out_visual_dim; r.x_frame = r.x_row * tile->total_H;
+      r.vc_row = (int64_t)tile->total_W * (c.in_visual_dim + 1); r.vc_frame = r.vc_row * tile->total_H;
+    }
   }
   struct FlowEditGuard { k5_dit* d; ~FlowEditGuard() { d->fe.active = false; } } flowedit_guard{d};
   if (fe) {   // z_fe = x_src lives in the latent; the first launch forms zs / zt of step 0 (with no FlowEdit step: the first plain step's latent)
@@ -3411,44 +3375,41 @@ extern "C" int k5_dit_flowedit_state(k5_dit* d, long long* steps, long long* for
   return K5_OK;
 }
 
+// The windowed run behind k5_sample_tiles and k5_sample_windows (`who`).  A clip no larger than the window in every axis is the plain run on the
+// whole clip (the first entries of pos_* are its positions).
+static int sample_windowed(k5_dit* d, const k5_sample_tiles_args* t, const float* vcond, void* stream, const char* who) {
+  g_err[0] = 0;
+  if (t->total_T < 1 || t->total_H < 1 || t->total_W < 1) {
+    k5_set_error("%s: the clip must be >= 1 in every axis (got %d, %d, %d)", who, t->total_T, t->total_H, t->total_W);
+    return K5_ERR_ARG;
+  }
+  const k5_forward_args& f = t->sample.fwd;
+  if (t->total_T <= f.T && t->total_H <= f.H && t->total_W <= f.W) {
+    k5_sample_args one = t->sample;
+    one.fwd.T = t->total_T; one.fwd.H = t->total_H; one.fwd.W = t->total_W;
+    if (t->conds) one.fwd.cond = t->conds[0];
+    if (t->null_conds) one.null_cond = t->null_conds[0];
+    return sample_impl(d, &one, vcond, nullptr, stream, who);
+  }
+  return sample_impl(d, &t->sample, vcond, nullptr, stream, who, t);
+}
+
+// A temporal plan is the 3-D plan with one row window and one column window of weight 1 that span the clip
 extern "C" int k5_sample_windows(k5_dit* d, const k5_sample_windows_args* w, const float* vcond, void* stream) {
   g_err[0] = 0;
   if (!d || !w) { k5_set_error("k5_sample_windows: null handle or arguments"); return K5_ERR_ARG; }
-  if (w->total_T < 1) { k5_set_error("k5_sample_windows: total_T must be >= 1 (got %d)", w->total_T); return K5_ERR_ARG; }
-  if (w->total_T <= w->sample.fwd.T) {   // one window: the plain run on total_T frames (pos_t's first total_T entries are its positions)
-    k5_sample_args one = w->sample;
-    one.fwd.T = w->total_T;
-    if (w->conds) one.fwd.cond = w->conds[0];
-    if (w->null_conds) one.null_cond = w->null_conds[0];
-    return sample_impl(d, &one, vcond, nullptr, stream, "k5_sample_windows");
-  }
-  return sample_impl(d, &w->sample, vcond, nullptr, stream, "k5_sample_windows", w);
+  const k5_forward_args& f = w->sample.fwd;
+  static const int32_t zero = 0;
+  const std::vector<float> ones((size_t)std::max(1, std::max(f.H, f.W)), 1.0f);
+  const k5_sample_tiles_args t{w->sample, w->total_T, f.H, f.W, w->nwin, 1, 1, w->starts, &zero, &zero, w->weights, ones.data(), ones.data(),
+                               w->conds, w->null_conds};
+  return sample_windowed(d, &t, vcond, stream, "k5_sample_windows");
 }
 
 extern "C" int k5_sample_tiles(k5_dit* d, const k5_sample_tiles_args* t, const float* vcond, void* stream) {
   g_err[0] = 0;
   if (!d || !t) { k5_set_error("k5_sample_tiles: null handle or arguments"); return K5_ERR_ARG; }
-  if (t->total_T < 1 || t->total_H < 1 || t->total_W < 1) {
-    k5_set_error("k5_sample_tiles: the clip must be >= 1 in every axis (got %d, %d, %d)", t->total_T, t->total_H, t->total_W);
-    return K5_ERR_ARG;
-  }
-  const k5_forward_args& f = t->sample.fwd;
-  if (t->total_T <= f.T && t->total_H <= f.H && t->total_W <= f.W) {   // one window: the plain run on the whole clip (the first entries of pos_* are its positions)
-    k5_sample_args one = t->sample;
-    one.fwd.T = t->total_T; one.fwd.H = t->total_H; one.fwd.W = t->total_W;
-    if (t->conds) one.fwd.cond = t->conds[0];
-    if (t->null_conds) one.null_cond = t->null_conds[0];
-    return sample_impl(d, &one, vcond, nullptr, stream, "k5_sample_tiles");
-  }
-  // what sample_impl reads of a windowed run whatever its plan: the window count, the clip's frames, the prompts
-  const auto count = [](int n) { return n >= 1 && n <= 64; };   // nwin = 0 where a count is out of range: the plan check names it
-  const int nwin = count(t->nt) && count(t->ny) && count(t->nx) ? t->nt * t->ny * t->nx : 0;
-  k5_sample_windows_args w{t->sample, t->total_T, nwin, t->starts_t, t->wt, t->conds, t->null_conds};
-  if (t->ny == 1 && t->nx == 1 && t->total_H == f.H && t->total_W == f.W) {   // a temporal plan: k5_sample_windows' launches
-    w.nwin = t->nt;
-    return sample_impl(d, &w.sample, vcond, nullptr, stream, "k5_sample_tiles", &w);
-  }
-  return sample_impl(d, &w.sample, vcond, nullptr, stream, "k5_sample_tiles", &w, nullptr, t);
+  return sample_windowed(d, t, vcond, stream, "k5_sample_tiles");
 }
 
 // What k5_sample_many / k5_dit_forward_many refuse before anything is enqueued: handle states whose per-call bookkeeping is not per sample (rank

@@ -520,24 +520,32 @@ int k5_flowedit_step(const k5_flowedit_step_args* args, void* stream) {
   return ret(k5_launch_flowedit_step(*args, (hipStream_t)stream), "k5_flowedit_step");
 }
 
+// the row and column axes of a temporal plan: one window at 0 of weight 1.0 (never written)
+__device__ int32_t k5_whole_axis_start = 0;
+__device__ float k5_whole_axis_weight = 1.0f;
+
+// A temporal plan is the 3-D plan over (T, 1, 1, frame_elems) with one row window and one column window of weight 1.0
 int k5_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts_dev,
                          const float* weights_dev, int nwin, int F, int T, int64_t frame_elems, void* stream) {
-  if (!img || !v_cond || !starts_dev || !weights_dev || nwin < 1 || nwin > 64 || F < 1 || T < 1 || frame_elems < 1) {
-    k5_set_error("k5_cfg_euler_windows: null pointer, or nwin (1..64) / F / T / frame_elems out of range");
+  if (!img || !v_cond || !starts_dev || !weights_dev || nwin < 1 || nwin > 64 || F < 1 || T < 1 || frame_elems < 1 || frame_elems > 0x7fffffff) {
+    k5_set_error("k5_cfg_euler_windows: null pointer, or nwin (1..64) / F / T / frame_elems (below 2^31) out of range");
     return K5_ERR_ARG;
   }
-  // the plan is checked on the host: nwin ints come back once (this entry is the per-step paths' and the tests'; k5_sample_windows holds its plan on the host)
+  // the plan is checked on the host: nwin ints come back once (this entry is the tests' and the tools'; the sampler holds its plan on the host)
   int32_t st[64];
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemcpyAsync(st, starts_dev, (size_t)nwin * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+  const int32_t* zero = nullptr;
+  const float* one = nullptr;
+  if (hipMemcpyAsync(st, starts_dev, (size_t)nwin * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess ||
+      hipGetSymbolAddress((void**)&zero, HIP_SYMBOL(k5_whole_axis_start)) != hipSuccess ||
+      hipGetSymbolAddress((void**)&one, HIP_SYMBOL(k5_whole_axis_weight)) != hipSuccess)
     return ret(K5_ERR_HIP, "k5_cfg_euler_windows");
-  for (int i = 0; i < nwin; ++i)
-    if (st[i] < 0 || (int64_t)st[i] + F > T) {
-      k5_set_error("k5_cfg_euler_windows: window %d (frames %d .. %lld) reaches outside the %d frames", i, st[i], (long long)st[i] + F - 1, T);
-      return K5_ERR_ARG;
-    }
-  return ret(k5_launch_cfg_euler_windows(img, v_cond, v_uncond, w, dt, starts_dev, weights_dev, nwin, F, T, frame_elems, s),
-             "k5_cfg_euler_windows");
+  if (const char* why = k5_tile_axis_refusal("frame", nwin, st, F, T)) {
+    k5_set_error("k5_cfg_euler_windows: %s", why);
+    return K5_ERR_ARG;
+  }
+  const k5_tile_plan p{nwin, 1, 1, F, 1, 1, starts_dev, zero, zero, weights_dev, one, one};
+  return ret(k5_launch_cfg_euler_tiles(img, v_cond, v_uncond, w, dt, p, T, 1, 1, (int)frame_elems, s), "k5_cfg_euler_windows");
 }
 
 int k5_cfg_euler_tiles(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const k5_tile_plan* p, int T, int H, int W, int C,

@@ -214,18 +214,12 @@ int k5_launch_edit_renoise(float* out, const float* source, const float* noise, 
 int k5_guidance_blocks(int64_t n);
 int k5_launch_guidance_coeffs(const void* v_cond, const void* v_uncond, int64_t n, float w, int zero_star, float rescale, double* part,
                               double* sums, float* ab, hipStream_t stream, const float* wvec = nullptr, const int* step = nullptr);
-// K18 over temporal context windows: img fp32 [T][frame_elems]; v_cond / v_uncond (null = no guidance) bf16 [nwin][F][frame_elems], window i
-// covering frames starts[i] .. starts[i] + F - 1 (device int32 [nwin]) with the share weights[i][j] (device fp32 [nwin][F]) of its local frame j.
-// Per element the windows that cover its frame are walked in order: v_i as K18 forms it, acc = wt_0 * v_0, then acc = acc + wt_i * v_i
-// (every product and sum rounded to fp32 on its own), img += float(bf16(dt * acc)): one window of weight 1 is K18 bit for bit.  One pass;
-// 16-byte latent accesses when frame_elems % 4 == 0 and img is 16-byte, the velocities 8-byte aligned.  A frame without a window stays as it is.
-int k5_launch_cfg_euler_windows(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const int32_t* starts,
-                                const float* weights, int nwin, int F, int T, int64_t frame_elems, hipStream_t stream);
 // One axis of a tile plan on the HOST: n windows of F at starts[] over 0 .. total - 1.  nullptr when the starts ascend, every window lies inside
 // and every coordinate is covered; otherwise what is wrong, in words (a thread-local buffer).
 const char* k5_tile_axis_refusal(const char* axis, int n, const int32_t* starts, int F, int total);
 // K18 over a 3-D plan of context windows (tiles): img fp32 (T,H,W,C); v_cond / v_uncond (null = no guidance) bf16 [nwin][Ft][Fh][Fw][C]; the
-// plan's tables on the device.  The rule is written once, at k5_cfg_euler_tiles in include/k5.h.  A lane owns four channels of a cell when
+// plan's tables on the device.  The rule is written once, at k5_cfg_euler_tiles in include/k5.h.  The only windowed update: a temporal plan
+// is the plan with one row window and one column window of weight 1.0 (k5_cfg_euler_windows).  A lane owns four channels of a cell when
 // C % 4 == 0 and img is 16-byte, the velocities 8-byte aligned; otherwise one.  A cell without a window stays as it is; only slots inside a
 // window's box are read.  K5_ERR_ARG, nothing launched: a null pointer, a count or extent < 1, nt * ny * nx > 64, T * H or W * C beyond an int.
 int k5_launch_cfg_euler_tiles(float* img, const void* v_cond, const void* v_uncond, float w, float dt, const k5_tile_plan& plan, int T, int H,

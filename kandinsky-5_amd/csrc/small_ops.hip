@@ -1016,7 +1016,7 @@ __global__ __launch_bounds__(320) void guidance_finish_kernel(const double* __re
   }
 }
 
-// Temporal context windows: one term of the cross-fade, acc = wt_0 * v_0 for the first window that covers the frame and acc + wt_i * v_i for
+// Context windows: one term of the cross-fade, acc = wt_0 * v_0 for the first window that covers the cell and acc + wt_i * v_i for
 // every later one.  The product and the sum round to fp32 each on its own (the pragma: see renoise_at), so the torch expression with separate
 // ops is the oracle bit for bit, and one window of weight 1 leaves v itself.
 __device__ __forceinline__ float window_term(float acc, float wt, float v, bool first) {
@@ -1024,59 +1024,6 @@ __device__ __forceinline__ float window_term(float acc, float wt, float v, bool 
   const float p = wt * v;
   if (first) return p;
   return acc + p;
-}
-
-// euler_step_kernel's CFG update over a clip of T frames whose velocities come from nwin windows of F frames: vc / vu [nwin][F][frame_elems] bf16, window i
-// covers frames starts[i] .. starts[i] + F - 1 and weights[i][j] is the share of its local frame j.  One pass over img: a lane owns VEC
-// consecutive elements of one frame (frame = g / (frame_elems / VEC), VEC divides frame_elems, so no lane straddles two frames), walks the
-// windows in order, forms each window's guided velocity with cfg_velocity, blends (window_term) and
-// applies img += bf16(dt * acc).  Only slots (i, t - starts[i]) with 0 <= t - starts[i] < F are read, so whatever the tables hold no read
-// leaves the [nwin][F] velocity buffers; a frame no window covers is left as it is.
-template <int VEC>
-__global__ __launch_bounds__(256) void cfg_euler_windows_kernel(float* __restrict__ img, const bf16_t* __restrict__ vc,
-                                                                const bf16_t* __restrict__ vu, float w, float dt,
-                                                                const int32_t* __restrict__ starts, const float* __restrict__ weights,
-                                                                int nwin, int F, int T, int64_t frame_elems) {
-  const int64_t per_frame = frame_elems / VEC, total = (int64_t)T * per_frame;
-  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += (int64_t)gridDim.x * 256) {
-    const int t = (int)(g / per_frame);
-    const int64_t e = (g - (int64_t)t * per_frame) * VEC;   // first element inside the frame
-    float acc[VEC];
-    bool first = true;
-    for (int i = 0; i < nwin; ++i) {
-      const int j = t - starts[i];
-      if (j < 0 || j >= F) continue;
-      const float wt = weights[(int64_t)i * F + j];
-      const int64_t off = ((int64_t)i * F + j) * frame_elems + e;
-      float v[VEC];
-      if constexpr (VEC == 4) {
-        const u32x2 cr = *reinterpret_cast<const u32x2*>(vc + off);
-        u32x2 ur = {0u, 0u};
-        if (vu) ur = *reinterpret_cast<const u32x2*>(vu + off);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          v[k] = bf16_at(cr, k);
-          if (vu) v[k] = cfg_velocity(w, v[k], bf16_at(ur, k));
-        }
-      } else {
-        v[0] = bf2f(vc[off]);
-        if (vu) v[0] = cfg_velocity(w, v[0], bf2f(vu[off]));
-      }
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) acc[k] = window_term(first ? 0.0f : acc[k], wt, v[k], first);
-      first = false;
-    }
-    if (first) continue;
-    float* p = img + (int64_t)t * frame_elems + e;
-    if constexpr (VEC == 4) {
-      f32x4 x = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) x[k] = __fadd_rn(x[k], bf_round(__fmul_rn(dt, acc[k])));
-      *reinterpret_cast<f32x4*>(p) = x;
-    } else {
-      p[0] = __fadd_rn(p[0], bf_round(__fmul_rn(dt, acc[0])));
-    }
-  }
 }
 
 // Spatial context windows (tiles): the share of window (it, iy, ix) at a cell is the product of its three per-axis weights, left to right, each
@@ -1097,7 +1044,8 @@ __device__ __forceinline__ void covering(const int32_t* __restrict__ starts, int
   }
 }
 
-// cfg_euler_windows_kernel over a 3-D plan: img fp32 (T,H,W,C), vc / vu bf16 [nwin][Ft][Fh][Fw][C], window k = (it * ny + iy) * nx + ix at
+// euler_step_kernel's CFG update over a clip whose velocities come from the windows of a 3-D plan (a temporal plan: ny = nx = 1 with weights
+// 1.0, where tile_share leaves wt itself): img fp32 (T,H,W,C), vc / vu bf16 [nwin][Ft][Fh][Fw][C], window k = (it * ny + iy) * nx + ix at
 // (st[it], sy[iy], sx[ix]).  A workgroup takes whole rows (t, y) of the latent, grid-stride: the frame and row ranges of covering windows,
 // their weights and local indices are the workgroup's (scalar), no lane divides a 64-bit index.  Inside a row a lane owns VEC consecutive
 // channels of one cell (VEC divides C), walks the windows that cover the cell in ascending k — a product of three contiguous index ranges —
@@ -1494,23 +1442,6 @@ int k5_launch_guidance_coeffs(const void* vc, const void* vu, int64_t n, float w
   hipLaunchKernelGGL(guidance_stats_kernel, dim3(grid), dim3(256), 0, s, (const bf16_t*)vc, (const bf16_t*)vu, part, n / 8);
   hipLaunchKernelGGL(guidance_finish_kernel, dim3(1), dim3(320), 0, s, (const double*)part, grid, (double)n, w, zero_star, rescale, wvec, step,
                      sums, ab);
-  return done();
-}
-
-int k5_launch_cfg_euler_windows(float* img, const void* vc, const void* vu, float w, float dt, const int32_t* starts, const float* weights,
-                                int nwin, int F, int T, int64_t frame_elems, hipStream_t s) {
-  if (!img || !vc || !starts || !weights || nwin < 1 || F < 1 || T < 1 || frame_elems < 1) return K5_ERR_ARG;
-  const auto misaligned = [](const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
-  if (misaligned(img, 4) || misaligned(vc, 2) || misaligned(vu, 2) || misaligned(starts, 4) || misaligned(weights, 4)) return K5_ERR_ARG;
-  // 16-byte accesses to the latent (8-byte ones to the bf16 velocities) when a frame is whole groups of four and the bases allow it
-  const bool vec = (frame_elems & 3) == 0 && !misaligned(img, 16) && !misaligned(vc, 8) && !misaligned(vu, 8);
-  const int64_t n = (int64_t)T * (vec ? frame_elems / 4 : frame_elems);
-  if (vec)
-    hipLaunchKernelGGL(cfg_euler_windows_kernel<4>, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, w, dt, starts,
-                       weights, nwin, F, T, frame_elems);
-  else
-    hipLaunchKernelGGL(cfg_euler_windows_kernel<1>, dim3(grid_for(n)), dim3(256), 0, s, img, (const bf16_t*)vc, (const bf16_t*)vu, w, dt, starts,
-                       weights, nwin, F, T, frame_elems);
   return done();
 }
 

@@ -468,63 +468,43 @@ def tile_windows(clip, window, overlap):
     return plan
 
 
-def _context_plan(model, T, context_frames, context_overlap, context_text, init_latent, preview_every):
-    """`generate`'s context keywords -> (F, starts, weights) or None for a plain run, with the ValueErrors of the combinations that are refused."""
-    if context_frames is None:
-        if context_overlap is not None or context_text is not None:
-            raise ValueError("context_overlap / context_text need context_frames")
-        return None
-    F = int(context_frames)
-    overlap = F // 4 if context_overlap is None else int(context_overlap)
-    starts, weights = context_windows(T, F, overlap)
-    nwin = len(starts)
-    if context_text is not None and len(context_text) != nwin:
-        raise ValueError(f"context_text holds {len(context_text)} prompts, the plan of T={T}, frames={F}, overlap={overlap} has nwin = {nwin} windows")
-    if nwin == 1:
-        return None if context_text is None else (T, starts, weights)
-    if init_latent is not None:
-        raise ValueError("init_latent (editing) together with context_frames is not supported")
-    if int(preview_every) > 0:
-        raise ValueError("preview_every > 0 together with context_frames is not supported: the preview reads one velocity pair per cell")
-    if _has_magcache(model):
-        raise ValueError("context_frames with MagCache: the ratio table is indexed by the call of a plain run")
-    if _is_multi_rank_engine(model) or getattr(model, "_cfg_parallel", None) is not None:
-        raise ValueError("context_frames needs a single-rank model (no sequence-parallel group, no CFG pair)")
-    return F, starts, weights
-
-
 def _even_down(v):
     return int(v) // 2 * 2
 
 
 def _plan_for(model, clip, context, init_latent, preview_every):
     """`generate`'s context keywords `context` = (frames, overlap, text, height, width, overlap_hw) for a sample of `clip` = (T, H, W) latent
-    cells -> `(plan, tiles)`: the temporal plan of `_context_plan` or None, and the TileWindows of a run with more than one window in a
-    spatial axis or None; never both.  Without the spatial keywords this is `_context_plan`; a spatial plan whose rows and columns are one
-    window each is the temporal plan of its first axis.  The refusals are `_context_plan`'s, raised before the model is touched."""
+    cells -> the TileWindows of the run, or None for a plain run: no keyword, or one window and no `context_text`.  `context_frames` alone
+    is the 3-D plan with one row window and one column window of weight 1 over `context_windows(T, frames, overlap)`.  The ValueErrors of the
+    combinations that are refused name the keywords the caller gave and are raised before the model is touched."""
     frames, overlap, text, height, width, overlap_hw = context
     T, H, W = (int(v) for v in clip)
     if height is None and width is None:
         if overlap_hw is not None:
             raise ValueError("context_overlap_hw needs context_height / context_width")
-        return _context_plan(model, T, frames, overlap, text, init_latent, preview_every), None
-    if overlap is not None and frames is None:
-        raise ValueError("context_overlap needs context_frames")
-    Ft = T if frames is None else min(int(frames), T)
-    Fh, Fw = (n if v is None else min(int(v), n) for v, n in ((height, H), (width, W)))
-    if overlap_hw is None:   # a quarter of the window, rounded down to even
-        oh, ow = _even_down(Fh // 4), _even_down(Fw // 4)
+        if frames is None:
+            if overlap is not None or text is not None:
+                raise ValueError("context_overlap / context_text need context_frames")
+            return None
+        what, F = "context_frames", int(frames)
+        ot = F // 4 if overlap is None else int(overlap)
+        starts, weights = context_windows(T, F, ot)
+        tiles = TileWindows((T, H, W), (min(F, T), H, W), (ot, 0, 0), (starts, [0], [0]), (weights, torch.ones(1, H), torch.ones(1, W)))
     else:
-        oh, ow = (int(v) for v in ((overlap_hw, overlap_hw) if isinstance(overlap_hw, int) else overlap_hw))
-    ot = Ft // 4 if overlap is None else int(overlap)
-    tiles = tile_windows((T, H, W), (Ft, Fh, Fw), (ot, oh, ow))
+        what = "context_height / context_width"
+        if overlap is not None and frames is None:
+            raise ValueError("context_overlap needs context_frames")
+        Ft = T if frames is None else min(int(frames), T)
+        Fh, Fw = (n if v is None else min(int(v), n) for v, n in ((height, H), (width, W)))
+        if overlap_hw is None:   # a quarter of the window, rounded down to even
+            oh, ow = _even_down(Fh // 4), _even_down(Fw // 4)
+        else:
+            oh, ow = (int(v) for v in ((overlap_hw, overlap_hw) if isinstance(overlap_hw, int) else overlap_hw))
+        tiles = tile_windows((T, H, W), (Ft, Fh, Fw), (Ft // 4 if overlap is None else int(overlap), oh, ow))
     if text is not None and len(text) != tiles.nwin:
         raise ValueError(f"context_text holds {len(text)} prompts, the plan {tiles!r} has nwin = {tiles.nwin} windows")
-    if tiles.counts[1] == 1 and tiles.counts[2] == 1:   # rows and columns are whole: the temporal plan, on the temporal path
-        if tiles.nwin == 1:
-            return (None if text is None else (T, tiles.starts[0], tiles.weights[0])), None
-        return _context_plan(model, T, Ft, ot, text, init_latent, preview_every), None
-    what = "context_height / context_width"
+    if tiles.nwin == 1:   # the plain run; with context_text the plan stays, for its one prompt
+        return None if text is None else tiles
     if init_latent is not None:
         raise ValueError(f"init_latent (editing) together with {what} is not supported")
     if int(preview_every) > 0:
@@ -533,7 +513,7 @@ def _plan_for(model, clip, context, init_latent, preview_every):
         raise ValueError(f"{what} with MagCache: the ratio table is indexed by the call of a plain run")
     if _is_multi_rank_engine(model) or getattr(model, "_cfg_parallel", None) is not None:
         raise ValueError(f"{what} needs a single-rank model (no sequence-parallel group, no CFG pair)")
-    return None, tiles
+    return tiles
 
 
 def _has_magcache(model):
@@ -725,7 +705,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     and one k5_cfg_euler_tiles pass cross-fades the windows' velocities into the update.  `context_text` is then one prompt per window of
     the 3-D plan (t-major, rows, columns).  The engine-backed model runs the whole loop in one call (k5_sample_tiles), any other callable
     runs each forward on a contiguous copy of its window and gives the same bits.  Refused in the combinations `context_frames` refuses;
-    a plan whose rows and columns are one window each is the `context_frames` run, bit for bit.
+    `context_frames` alone is this plan with one row window and one column window of weight 1, on the same path.
     `visual_cond` (T,H,W,in_visual_dim) and `visual_cond_mask` (T,H,W,1) (optional, extension; `conditioning.py` builds them) fill
     the conditioning channels of a visual_cond model that the reference's loop leaves zero; either alone means zeros for the other.
     `batch` (extension): `shape` = (batch*T, H, W, C) holds `batch` samples of T frames, sample b = frames [bT, (b+1)T) of the
@@ -748,10 +728,10 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     Python loop with the same kernel, so the sequence and the preview bits are the same.  ValueError on a multi-rank engine model.
     `context_frames`, `context_overlap`, `context_text` (optional, extension): a clip longer than the model's trained length.  With
     `context_frames` = F below the sample's T frames the model runs at every step on the overlapping windows of `context_windows(T, F,
-    context_overlap)` (overlap default F // 4) and the windows' velocities are cross-faded into one update (k5_cfg_euler_windows);
+    context_overlap)` (overlap default F // 4) and the windows' velocities are cross-faded into one update (k5_cfg_euler_tiles);
     `visual_rope_pos[0]` (its first F entries when it holds the clip's) and the NABLA parameters are the window's.  `context_text`: a
     list of nwin `(text_embeds, text_rope_pos)` pairs, a prompt per window in order, instead of `text_embeds` / `text_rope_pos`.  F >= T
-    is the plain run, bit for bit.  The engine-backed model runs the whole loop in one call (k5_sample_windows), any other callable the
+    is the plain run, bit for bit.  The engine-backed model runs the whole loop in one call (k5_sample_tiles), any other callable the
     same forwards in the same order from Python.  ValueError with init_latent, preview_every > 0, MagCache or a multi-rank model.
     `nag_scale`, `nag_tau`, `nag_alpha`, `nag_text_embeds`, `nag_text_rope_pos` (optional, extension): normalized attention guidance, a
     negative prompt inside the cross-attention of the conditional forward (`DiffusionTransformer3D.set_nag`) — the way to a negative
@@ -837,7 +817,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         raise ValueError(f"shape[0] = {shape[0]} frames do not divide into batch={batch} samples")
     _check_edit_args(model, shape, init_latent, strength, keep_mask)
     context = (context_frames, context_overlap, context_text, context_height, context_width, context_overlap_hw)
-    plan, tiles = _plan_for(model, (shape[0] // batch, shape[1], shape[2]), context, init_latent, preview_every)
+    tiles = _plan_for(model, (shape[0] // batch, shape[1], shape[2]), context, init_latent, preview_every)
     many = any(isinstance(v, (list, tuple)) for v in (text_embeds, null_text_embeds))
     if batch == 1 and many:
         text_embeds, null_text_embeds, text_rope_pos, null_text_rope_pos = (
@@ -847,7 +827,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
     steps_run = num_steps - first
     guide_kw = (guidance_schedule, guidance_interval, cfg_zero_star, cfg_zero_init, cfg_rescale)
     guide = skip = None
-    windowed = tiles is not None or (plan is not None and len(plan[1]) > 1)
+    windowed = tiles is not None and tiles.nwin > 1
     wants_guide = any(v is not None for v in guide_kw[:2]) or any(guide_kw[2:])
     wants_skip = slg_blocks is not None or slg_scale or slg_interval is not None
     sto = None
@@ -867,7 +847,7 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
         sto = _stochastic_for_run(model, sigmas, first, eta, s_noise, sde_interval, seed if sde_seed is None else sde_seed, windowed, preview_every)
     if wants_enhance:
         enhance = _enhance_for_run(model, sigmas, first, enhance_weight, enhance_interval,
-                                   tiles.window[0] if tiles is not None else plan[0] if windowed else shape[0] // batch)
+                                   shape[0] // batch if tiles is None else tiles.window[0])
     forecast = _forecast_for_run(model, steps_run, forecast_interval, forecast_order, forecast_warmup, forecast_tail, guide, skip, windowed)
     flow = _flowedit_for_run(model, num_steps, strength, init_latent, keep_mask, guidance_weight, seed, source_text_embeds, source_text_rope_pos,
                              source_guidance_weight, flowedit_refine, flowedit_seed,
@@ -893,33 +873,27 @@ def generate(model, device, shape, num_steps, text_embeds, null_text_embeds, vis
             what = (context, visual_cond, visual_cond_mask, init_latent, strength, keep_mask)
             if batch > 1:
                 return _generate_batch(*run, batch, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast, flow=flow)
-            return _generate_one(*run, plan, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast, flow=flow, tiles=tiles)
+            return _generate_one(*run, *what, guide=guide, skip=skip, sto=sto, enhance=enhance, forecast=forecast, flow=flow, tiles=tiles)
         finally:
             watch.close()
 
 
 def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, visual_rope_pos, text_rope_pos, null_text_rope_pos,
-                  guidance_weight, scheduler_scale, conf, watch, plan, context, visual_cond, visual_cond_mask, init_latent, strength,
+                  guidance_weight, scheduler_scale, conf, watch, context, visual_cond, visual_cond_mask, init_latent, strength,
                   keep_mask, guide=None, skip=None, sto=None, enhance=None, forecast=None, flow=None, tiles=None):
-    """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch`, the checked `plan` of
-    `_context_plan`, the checked guidance plan `guide` of `_guidance_for_run`, the checked skip set `skip` of `_skip_for_run` (installed on
+    """`generate` for one sample on its drawn noise `img` (contiguous fp32 on the device), with the hook `watch`, the checked window plan
+    `tiles` of `_plan_for`, the checked guidance plan `guide` of `_guidance_for_run`, the checked skip set `skip` of `_skip_for_run` (installed on
     the model by `generate`), the checked stochastic plan `sto` of `_stochastic_for_run` and the checked Enhance-A-Video set `enhance` of
     `_enhance_for_run` (`generate` puts back what the model held) and the checked forecast plan `forecast` of `_forecast_for_run` (installed
-    on the model by `generate`) and the checked FlowEdit side `flow` of `_flowedit_for_run`; `tiles`: the TileWindows of `_plan_for` (then `plan` is None); returns the latent."""
+    on the model by `generate`) and the checked FlowEdit side `flow` of `_flowedit_for_run`; returns the latent."""
     context_text = context[2]
-    if tiles is not None:   # the window's positions are the first entries of the clip's, in every axis
-        F = tiles.window[0]
-        if context_text is not None:
-            text_embeds, text_rope_pos = context_text[0]
-        visual_rope_pos = [torch.as_tensor(p)[:n] for p, n in zip(visual_rope_pos, (F, tiles.window[1] // 2, tiles.window[2] // 2))]
-    if plan is not None:
-        F, starts, weights = plan
+    if tiles is not None:
         if context_text is not None:   # the first window's prompt stands where the one prompt of a plain run does
             text_embeds, text_rope_pos = context_text[0]
-        if len(starts) == 1:
-            plan = None
-        else:
-            visual_rope_pos = [torch.as_tensor(visual_rope_pos[0])[:F], visual_rope_pos[1], visual_rope_pos[2]]
+        if tiles.nwin == 1:
+            tiles = None
+        else:   # the window's positions are the first entries of the clip's, in every axis
+            visual_rope_pos = [torch.as_tensor(p)[:n] for p, n in zip(visual_rope_pos, (tiles.window[0], tiles.window[1] // 2, tiles.window[2] // 2))]
     edit = None
     if init_latent is not None:   # img (the draw) is eps from here on; the latent is a buffer of its own that the engine fills
         src = init_latent.to(device=img.device, dtype=torch.float32).contiguous()
@@ -929,7 +903,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
     fe_km = km if flow is not None else None
     cond_in = _conditioning(model, img, visual_cond, visual_cond_mask)
 
-    one_window = img[:tiles.window[0], :tiles.window[1], :tiles.window[2]] if tiles is not None else img if plan is None else img[:plan[0]]
+    one_window = img if tiles is None else img[:tiles.window[0], :tiles.window[1], :tiles.window[2]]
     sparse_params = get_sparse_params(conf, {"visual": one_window}, device)
     timesteps = sigma_schedule(num_steps, scheduler_scale, device=device).cpu()  # one sync, before the loop
     first = edit_first_step(num_steps, strength) if init_latent is not None else 0
@@ -958,8 +932,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
                          sparse_params=sparse_params,
                          visual_cond=None if cond_in is None else torch.cat(cond_in, dim=-1).contiguous(), edit=edit,
                          flowedit=None if flow is None else (src, flow[0], flow[1], flow[2], fe_km, flow[3], flow[4], first),
-                         windows=None if plan is None else (plan[1], plan[2]), tiles=tiles,
-                         window_text=None if plan is None and tiles is None else context_text)
+                         tiles=tiles, window_text=None if tiles is None else context_text)
         return img
 
     # The per-step loop.  Each step takes (v_cond, v_uncond, v_skip) from one of three sources (a windowed run: its per-window buffers), makes
@@ -990,17 +963,8 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
             both = torch.empty((2,) + tuple(v.shape), dtype=v.dtype, device=v.device)
         return (*exchange_velocity(v, cfg_parallel[1], out=both), None)
 
-    def window_velocities(t1000, guided):
-        # the forwards of k5_sample_windows in its order: window by window, cond then uncond, each on its own slice of the latent
-        for k, st in enumerate(starts):
-            x = _model_input(model, img, cond_in, slice(st, st + F))
-            vbuf[k] = forward(x, *((text_embeds, text_rope_pos) if context_text is None else context_text[k]), t1000)
-            if cfg_on:
-                ubuf[k] = forward(x, null_text_embeds, null_text_rope_pos, t1000)
-        return vbuf, ubuf
-
     def tile_velocities(t1000, guided):
-        # the forwards of k5_sample_tiles in its order: window by window, cond then uncond, each on a contiguous copy of its box of the latent
+        # the forwards of k5_sample_tiles / k5_sample_windows in their order: window by window, cond then uncond, each on a contiguous copy of its box of the latent
         for k in range(tiles.nwin):
             x = _model_input(model, img, cond_in, tiles.box(k)).contiguous()
             vbuf[k] = forward(x, *((text_embeds, text_rope_pos) if context_text is None else context_text[k]), t1000)
@@ -1012,10 +976,6 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
         from .models.parallelize import exchange_velocity
         mine = (text_embeds, text_rope_pos) if cfg_parallel[0] == 0 else (null_text_embeds, null_text_rope_pos)
         both = None
-    elif plan is not None:
-        st_dev, wt_dev = E.window_tables(starts, weights, img.device)
-        vbuf = torch.empty((len(starts), F) + tuple(img.shape[1:]), dtype=torch.bfloat16, device=img.device)
-        ubuf = torch.empty_like(vbuf) if cfg_on else None
     elif tiles is not None:
         tile_dev = E.tile_tables(tiles, img.device)
         vbuf = torch.empty((tiles.nwin,) + tiles.window + (img.shape[-1],), dtype=torch.bfloat16, device=img.device)
@@ -1066,10 +1026,7 @@ def _generate_one(model, device, img, num_steps, text_embeds, null_text_embeds, 
                              dt=timestep_diff, keep_mask=fe_km, **prepare(i + 1))
             if i + 1 == fe_steps and fe_steps < n:
                 img.copy_(zt)          # the plain steps that close the run start from zt
-        elif plan is not None:         # every window's pair, then the one blend + Euler pass over the clip: a kernel of its own
-            v, u = window_velocities(t1000, kind == "guided")
-            E.cfg_euler_windows_(img, v, u, guidance_weight, timestep_diff, st_dev, wt_dev)
-        elif tiles is not None:        # the same over the 3-D plan
+        elif tiles is not None:        # every window's pair, then the one blend + Euler pass over the clip: a kernel of its own
             v, u = tile_velocities(t1000, kind == "guided")
             E.cfg_euler_tiles_(img, v, u, guidance_weight, timestep_diff, tile_dev)
         else:
@@ -1128,10 +1085,10 @@ def _generate_batch(model, device, img, num_steps, text_embeds, null_text_embeds
         rows = slice(b * T, (b + 1) * T)
         vc, vm, src, km = (None if v is None else v[rows] for v in (visual_cond, visual_cond_mask, init_latent, keep_mask))
         _check_edit_args(model, img[rows].shape, src, strength, km)
-        plan, tiles = _plan_for(model, (T, img.shape[1], img.shape[2]), context, src, watch.every)
+        tiles = _plan_for(model, (T, img.shape[1], img.shape[2]), context, src, watch.every)
         watch.sample = b
         img[rows] = _generate_one(model, device, img[rows].clone(), num_steps, tes[b], nes[b], visual_rope_pos, tps[b], nps[b], guidance_weight,
-                                  scheduler_scale, conf, watch, plan, context, vc, vm, src, strength, km, guide=guide, skip=skip, enhance=enhance,
+                                  scheduler_scale, conf, watch, context, vc, vm, src, strength, km, guide=guide, skip=skip, enhance=enhance,
                                   tiles=tiles, forecast=forecast, flow=None if flow is None else (*flow[:4], (flow[4] + b) & (2 ** 64 - 1)),
                                   sto=None if sto is None else (*sto[:3], (sto[3] + b) & (2 ** 64 - 1), sto[4]))   # a seed per sample
     return img
@@ -1242,12 +1199,10 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
     sto_kw = {}
     wants_sto = eta or sde_interval is not None or float(s_noise) != 1.0
     wants_skip = slg_blocks is not None or slg_scale or slg_interval is not None
-    if wants_sto or wants_skip:   # what both pre-checks refuse together with more than one context window
-        windowed = context_frames is not None and len(context_windows(
-            frames, context_frames, int(context_frames) // 4 if context_overlap is None else int(context_overlap))[0]) > 1
-        if context_height is not None or context_width is not None:
-            windowed = windowed or _plan_for(dit, (frames, height, width), (context_frames, context_overlap, None, context_height, context_width,
-                                                                            context_overlap_hw), video, preview_every)[1] is not None
+    # before any model runs: the window plan and what it is refused with; more than one context window is what both pre-checks below refuse
+    context = (context_frames, context_overlap, None, context_height, context_width, context_overlap_hw)
+    tiles = _plan_for(dit, (frames, height, width), context, video, preview_every)
+    windowed = tiles is not None
     if wants_sto:   # before any model runs: the numbers and what the handle's state refuses
         _stochastic_for_run(dit, [1.0, 0.5, 0.0], 0, eta, s_noise, None, seed if sde_seed is None else sde_seed, windowed, preview_every)
         stochastic_plan([1.0, 0.0], eta, s_noise, sde_interval)   # (what depends on the schedule is checked by `generate`)
@@ -1265,29 +1220,14 @@ def generate_sample(shape, caption, dit, vae, conf, text_embedder, num_steps=25,
         if guidance_interval is not None:
             guidance_plan([1.0, 0.0], guidance_weight, None, guidance_interval)
     ctx_kw, window_captions = {}, None
-    if context_height is not None or context_width is not None:   # before any model runs: the plan and what it is refused with
-        context = (context_frames, context_overlap, None, context_height, context_width, context_overlap_hw)
-        plan_t, tiles = _plan_for(dit, (frames, height, width), context, video, preview_every)
-        nwin = tiles.nwin if tiles is not None else 1 if plan_t is None else len(plan_t[1])
+    if any(v is not None for v in context):
+        nwin = 1 if tiles is None else tiles.nwin
         ctx_kw = {k: v for k, v in zip(("context_frames", "context_overlap", "", "context_height", "context_width", "context_overlap_hw"), context)
                   if k and v is not None}
         if batch == 1 and isinstance(caption, (list, tuple)):
             if len(caption) != nwin:
                 raise ValueError(f"{len(caption)} prompts for a plan of nwin = {nwin} windows ({tiles!r}): pass one prompt, or one per window")
             window_captions, caption = list(caption), caption[0]
-    elif context_overlap_hw is not None:
-        raise ValueError("context_overlap_hw needs context_height / context_width")
-    elif context_frames is not None:
-        overlap = int(context_frames) // 4 if context_overlap is None else int(context_overlap)
-        nwin = len(context_windows(frames, context_frames, overlap)[0])
-        ctx_kw = dict(context_frames=int(context_frames), context_overlap=overlap)
-        if batch == 1 and isinstance(caption, (list, tuple)):
-            if len(caption) != nwin:
-                raise ValueError(f"{len(caption)} prompts for a plan of nwin = {nwin} windows ({frames} frames as windows of "
-                                 f"{int(context_frames)} with overlap {overlap}): pass one prompt, or one per window")
-            window_captions, caption = list(caption), caption[0]
-    elif context_overlap is not None:
-        raise ValueError("context_overlap needs context_frames")
     region_kw, region_prompts = {}, []
     if region_text_embeds is not None:   # before any model runs
         if isinstance(region_text_embeds, (list, tuple)) and region_text_embeds and all(isinstance(p, str) for p in region_text_embeds):

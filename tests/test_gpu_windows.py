@@ -172,6 +172,40 @@ def test_one_window_of_weight_one_is_k5_cfg_euler(w, n):
     assert torch.equal(win, plain)
 
 
+@pytest.mark.parametrize("w", [1.0, 5.0])
+def test_cfg_euler_windows_on_a_misaligned_base_takes_the_scalar_path(w):
+    """img one float into a larger buffer: 4-byte but not 16-byte aligned, so a frame of whole groups of four (5 * 7 * 16) still runs a lane
+    per element.  The same torch oracle, the same guards as test_cfg_euler_windows_bit_exact."""
+    from kandinsky import _engine as E
+    from kandinsky.generation_utils import context_windows
+    T, F, o = 7, 3, 2
+    starts, weights = context_windows(T, F, o)
+    nwin, n = len(starts), 5 * 7 * 16
+    g = torch.Generator().manual_seed(n + T + int(w) + 1)
+    img = torch.randn(T, n, generator=g).cuda()
+    pad = 64
+    bufs = [torch.full((nwin * F * n + 2 * pad,), float("nan"), dtype=BF, device="cuda") for _ in range(2)]   # NaN around the velocities
+    c = bufs[0][pad:pad + nwin * F * n].view(nwin, F, n)
+    c.copy_(torch.randn(nwin, F, n, generator=g).to(BF))
+    u = None
+    if w != 1.0:
+        u = bufs[1][pad:pad + nwin * F * n].view(nwin, F, n)
+        u.copy_(torch.randn(nwin, F, n, generator=g).to(BF))
+    dt = f32(-0.0625 * 1.3)
+    st_dev, wt_dev = E.window_tables(starts, weights, "cuda")
+    want = windows_ref(img, c, u, w, dt, starts, wt_dev)
+    buf = torch.full((1 + T * n + 64,), 7.0, device="cuda")                 # a guard float in front of the latent and a guard region after it
+    lat = buf[1:1 + T * n]
+    lat.copy_(img.view(-1))
+    assert buf.data_ptr() % 16 == 0 and lat.data_ptr() % 16 == 4 and n % 4 == 0
+    E.check(E.lib().k5_cfg_euler_windows(lat.data_ptr(), c.data_ptr(), E.ptr(u), w, dt, st_dev.data_ptr(), wt_dev.data_ptr(), nwin, F, T, n,
+                                         E.stream_ptr()), "k5_cfg_euler_windows")
+    torch.cuda.synchronize()
+    assert torch.isfinite(buf).all()                                        # none of the NaN around the velocities was read
+    assert torch.equal(lat.view(T, n), want)
+    assert buf[0] == 7.0 and (buf[1 + T * n:] == 7.0).all()
+
+
 def test_kernel_entry_refusals():
     from kandinsky import _engine as E
     L = E.lib()
@@ -336,9 +370,9 @@ def test_refusals_touch_nothing(tiny_dit, cfg, tiny_sd, golden, win_golden):
         assert torch.equal(lat, before) and torch.equal(lat7, before7)
 
     # plans: a frame without a window, starts that do not ascend, a window past the end, too many windows
-    refused(tiny_dit, "no window covers frame 3", windows=([0, 4], weights[:2]), x=lat7)     # 7 frames, windows of 3 at 0 and 4: frame 3 is bare
-    refused(tiny_dit, "no window covers frame 5", windows=([0, 2], weights[:2]))
-    refused(tiny_dit, "no window covers frame 0", windows=([1, 3], weights[:2]))
+    refused(tiny_dit, "no frame window covers 3", windows=([0, 4], weights[:2]), x=lat7)     # 7 frames, windows of 3 at 0 and 4: frame 3 is bare
+    refused(tiny_dit, "no frame window covers 5", windows=([0, 2], weights[:2]))
+    refused(tiny_dit, "no frame window covers 0", windows=([1, 3], weights[:2]))
     refused(tiny_dit, "must ascend", windows=([0, 3, 1], weights))
     refused(tiny_dit, "must ascend", windows=([0, 0, 3], weights))
     refused(tiny_dit, "reaches outside", windows=([0, 1, 4], weights))
@@ -378,6 +412,21 @@ def test_refusals_touch_nothing(tiny_dit, cfg, tiny_sd, golden, win_golden):
     assert E.lib().k5_sample_windows(tiny_dit.engine(lat.device), None, None, E.stream_ptr()) == 1
 
 
+def test_an_odd_latent_is_refused_before_anything_is_enqueued(tiny_dit, golden):
+    """rows and columns must be even: a temporal plan meets the check of every window plan, with the latent untouched"""
+    from kandinsky.generation_utils import context_windows, sigma_schedule
+    te, ne = prompts(golden)
+    starts, weights = context_windows(6, 3, 1)
+    lat = torch.randn(6, 7, 12, 16, generator=torch.Generator().manual_seed(77)).cuda().contiguous()
+    before = lat.clone()
+    pos = [torch.arange(3), torch.arange(7 // 2), torch.arange(6)]
+    with pytest.raises(RuntimeError, match="must be even"):
+        tiny_dit.sample(lat, sigma_schedule(4, 5.0).tolist(), te, ne, pos, torch.arange(7), torch.arange(4), 5.0, scale_factor=(1.0, 2.0, 2.0),
+                        windows=(starts, weights))
+    torch.cuda.synchronize()
+    assert torch.equal(lat, before)
+
+
 # ------------------------------------------------------------------------------------------ pipeline end to end
 def _tiny_pipeline():
     from test_pipeline import StubTextEmbedder, make_conf
@@ -411,7 +460,7 @@ def test_pipeline_with_context_windows_end_to_end():
     samp = dit.sample
 
     def spy_sample(*a, **k):
-        seen["windows"], seen["window_text"], seen["pos_t"] = k.get("windows"), k.get("window_text"), len(a[4][0])
+        seen["tiles"], seen["window_text"], seen["pos_t"] = k.get("tiles"), k.get("window_text"), len(a[4][0])
         return samp(*a, **k)
 
     dit.sample = spy_sample
@@ -419,7 +468,7 @@ def test_pipeline_with_context_windows_end_to_end():
     # 1 s = 7 latent frames as windows of 0.5 s = 4 frames overlapping by 0.25 s = 1 frame: starts 0 and 3
     out = pipe("a cat in a blue hat", context_seconds=0.5, context_overlap_seconds=0.25, **kw)
     assert out.dtype == torch.uint8 and tuple(out.shape) == (1, 3, 25, 512, 512)
-    assert seen["windows"][0] == [0, 3] and seen["pos_t"] == 4 and seen["window_text"] is None
+    assert seen["tiles"].starts[0] == [0, 3] and seen["tiles"].counts == (2, 1, 1) and seen["pos_t"] == 4 and seen["window_text"] is None
     two = pipe(["a cat in a blue hat", "a dog"], context_seconds=0.5, context_overlap_seconds=0.25, **kw)
     assert tuple(two.shape) == (1, 3, 25, 512, 512) and len(seen["window_text"]) == 2
     assert not torch.equal(two, out)

@@ -16,6 +16,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "kandinsky-5_amd")
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from tile_kernels_reference import cpu_cfg_euler_tiles, cpu_tile_tables  # noqa: E402
 
 CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
 WINDOW = (3, 8, 12)
@@ -138,22 +139,6 @@ class FakeDit:
         return (0.5 * x + text_embed.mean() + pooled.mean() * float(t.reshape(-1)[0]) / 1000).to(torch.bfloat16)
 
 
-def cpu_tile_tables(plan, device):
-    return plan
-
-
-def cpu_cfg_euler_tiles(img, vc, vu, w, dt, plan):
-    wt, wy, wx = plan.weights
-    nt, ny, nx = plan.counts
-    acc = torch.zeros_like(img)
-    for k in range(plan.nwin):
-        it, iy, ix = k // (ny * nx), (k // nx) % ny, k % nx
-        v = vc[k] if vu is None else vu[k] + w * (vc[k] - vu[k])
-        acc[plan.box(k)] += ((wt[it][:, None, None] * wy[iy][None, :, None]) * wx[ix][None, None, :])[..., None] * v.float()
-    img.add_((dt * acc).to(torch.bfloat16).float())
-    return img
-
-
 def prompt(n, seed):
     g = torch.Generator().manual_seed(seed)
     return {"text_embeds": torch.randn(n, 8, generator=g), "pooled_embed": torch.randn(1, 4, generator=g)}
@@ -215,12 +200,39 @@ def test_per_window_prompts_and_batches(cpu_kernels):
 
 def test_the_default_overlap_is_a_quarter_of_the_window_rounded_down_to_even(cpu_kernels):
     G = cpu_kernels
-    _, tiles = G._plan_for(NS(visual_cond=False), (3, 16, 40), (None, None, None, 8, 12, None), None, 0)
+    tiles = G._plan_for(NS(visual_cond=False), (3, 16, 40), (None, None, None, 8, 12, None), None, 0)
     assert tiles.overlap == (0, 2, 2) and tiles.window == (3, 8, 12)       # 8 // 4 = 2; 12 // 4 = 3 -> 2
-    _, tiles = G._plan_for(NS(visual_cond=False), (3, 16, 40), (None, None, None, 8, 12, 4), None, 0)
+    tiles = G._plan_for(NS(visual_cond=False), (3, 16, 40), (None, None, None, 8, 12, 4), None, 0)
     assert tiles.overlap == (0, 4, 4)
-    _, tiles = G._plan_for(NS(visual_cond=False), (3, 16, 40), (None, None, None, 8, 12, (2, 6)), None, 0)
+    tiles = G._plan_for(NS(visual_cond=False), (3, 16, 40), (None, None, None, 8, 12, (2, 6)), None, 0)
     assert tiles.overlap == (0, 2, 6)
+
+
+def test_context_frames_alone_is_the_3d_plan_with_one_row_and_one_column_window():
+    from kandinsky import generation_utils as G
+    model = NS(visual_cond=False)
+    for T, F, o in ((7, 3, 2), (6, 3, 1), (5, 3, None)):
+        st, wt = G.context_windows(T, F, F // 4 if o is None else o)
+        p = G._plan_for(model, (T, 8, 12), (F, o, None, None, None, None), None, 0)
+        assert isinstance(p, G.TileWindows) and p.counts == (len(st), 1, 1) and p.nwin == len(st)
+        assert p.clip == (T, 8, 12) and p.window == (F, 8, 12)
+        assert p.starts[0] == st and torch.equal(p.weights[0], wt) and list(p.starts[1]) == [0] and list(p.starts[2]) == [0]
+        assert p.weights[1].dtype == torch.float32 and tuple(p.weights[1].shape) == (1, 8) and tuple(p.weights[2].shape) == (1, 12)
+        assert (p.weights[1] == 1.0).all() and (p.weights[2] == 1.0).all()
+    assert G._plan_for(model, (3, 8, 12), (3, None, None, None, None, None), None, 0) is None          # one window: the plain run
+    one = G._plan_for(model, (3, 8, 12), (5, 1, [None], None, None, None), None, 0)                      # ... kept for its one prompt
+    assert one.nwin == 1 and one.window == (3, 8, 12)
+    ctx = (3, 1, None, None, None, None)
+    for refused in (lambda: G._plan_for(model, (6, 8, 12), ctx, torch.zeros(1), 0),
+                    lambda: G._plan_for(model, (6, 8, 12), ctx, None, 2),
+                    lambda: G._plan_for(NS(visual_cond=False, mag_ratios=[1.0] * 8), (6, 8, 12), ctx, None, 0),
+                    lambda: G._plan_for(NS(visual_cond=False, _cfg_parallel=(0, None)), (6, 8, 12), ctx, None, 0)):
+        with pytest.raises(ValueError, match="context_frames") as e:
+            refused()
+        assert "context_height" not in str(e.value)
+    with pytest.raises(ValueError, match="context_height / context_width") as e:                       # the keywords the caller gave
+        G._plan_for(model, (6, 8, 24), (3, 1, None, None, 12, None), torch.zeros(1), 0)
+    assert "context_frames" not in str(e.value)
 
 
 # ------------------------------------------------------------------------------------------ refusals

@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "kandinsky-5_amd")
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import euler_step_reference as ER  # noqa: E402
+from tile_kernels_reference import cpu_cfg_euler_tiles, cpu_tile_tables  # noqa: E402
 
 CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
 
@@ -141,20 +142,6 @@ class FakeDit:
         return (0.5 * x + text_embed.mean() + pooled.mean() * float(t.reshape(-1)[0]) / 1000).to(torch.bfloat16)
 
 
-def cpu_window_tables(starts, weights, device):
-    return torch.tensor(list(starts), dtype=torch.int32), torch.as_tensor(weights, dtype=torch.float32).clone()
-
-
-def cpu_cfg_euler_windows(img, vc, vu, w, dt, starts, weights):
-    F = weights.shape[1]
-    acc = torch.zeros_like(img)
-    for k, st in enumerate(starts.tolist()):
-        v = vc[k] if vu is None else vu[k] + w * (vc[k] - vu[k])
-        acc[st:st + F] += weights[k][:, None, None, None] * v.float()
-    img.add_((dt * acc).to(torch.bfloat16).float())
-    return img
-
-
 def prompt(n, seed):
     g = torch.Generator().manual_seed(seed)
     return {"text_embeds": torch.randn(n, 8, generator=g), "pooled_embed": torch.randn(1, 4, generator=g)}
@@ -164,8 +151,8 @@ def prompt(n, seed):
 def cpu_kernels(monkeypatch):
     from kandinsky import generation_utils as G
     monkeypatch.setattr(G.E, "euler_step_", ER.euler_step_)
-    monkeypatch.setattr(G.E, "cfg_euler_windows_", cpu_cfg_euler_windows)
-    monkeypatch.setattr(G.E, "window_tables", cpu_window_tables)
+    monkeypatch.setattr(G.E, "cfg_euler_tiles_", cpu_cfg_euler_tiles)
+    monkeypatch.setattr(G.E, "tile_tables", cpu_tile_tables)
     return G
 
 
