@@ -11,16 +11,9 @@ import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
+from kit import PKG, ROOT, built_lib  # noqa: E402
+
 LIB = os.path.join(PKG, "lib", "libk5.so")
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
 
 
 def declared_symbols():

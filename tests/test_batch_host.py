@@ -2,25 +2,17 @@
 its own on a duck-typed model, the argument errors fire before any work, the pipeline hands a prompt list through as one batch,
 and libk5.so exports (and refuses, without a GPU) the two many-sample entry points."""
 import ctypes as C
-import os
-import sys
+import functools
 from types import SimpleNamespace as NS
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import euler_step_reference as ER  # noqa: E402
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+import kit  # noqa: E402
+from kit import built_lib, flash_conf  # noqa: E402
 
-
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
+CONF = flash_conf()
 
 
 class FakeDit:
@@ -35,9 +27,7 @@ class FakeDit:
         return (0.5 * x + text_embed.mean() + pooled.mean() * float(t.reshape(-1)[0]) / 1000).to(torch.bfloat16)
 
 
-def prompt(n, seed):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 8, generator=g), "pooled_embed": torch.randn(1, 4, generator=g)}
+prompt = functools.partial(kit.host_prompt, dims=(8, 4))
 
 
 @pytest.mark.parametrize("w", [1.0, 5.0])

@@ -2,38 +2,21 @@
 (`set_enhance`, `generate`, `generate_sample`, the CLI) with every refusal before a model runs, and the new entries of the C ABI, which
 refuse bad arguments without a device."""
 import ctypes as C
+import functools
 import os
-import sys
-from types import SimpleNamespace as NS
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+import kit  # noqa: E402
+from kit import K5_ERR_ARG, K5_ERR_UNSUPPORTED, PKG, POS, built_lib, cfg, flash_conf  # noqa: E402
+
+CONF = flash_conf()
 SHAPE = (3, 8, 12, 16)
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-K5_ERR_ARG, K5_ERR_UNSUPPORTED = 1, 6
 
 import enhance_reference as R  # noqa: E402
 from kandinsky.generation_utils import edit_first_step, enhance_plan, sigma_schedule  # noqa: E402
 from kandinsky.models.dit import check_enhance_args  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
-
-
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
 
 
 def tiny(cfg):
@@ -41,15 +24,10 @@ def tiny(cfg):
     return DiffusionTransformer3D(**cfg)
 
 
-def prompt(n, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 96, generator=g), "pooled_embed": torch.randn(1, 48, generator=g)}
+prompt = functools.partial(kit.host_prompt, dims=(96, 48))
 
 
-def call_generate(model, w=5.0, steps=4, shape=SHAPE, pos=POS, **kw):
-    from kandinsky.generation_utils import generate
-    return generate(model, "cpu", shape, steps, prompt(7), prompt(4, 1), pos, torch.arange(7), torch.arange(4), w, 5.0, CONF,
-                    noise=torch.zeros(shape), **kw)
+call_generate = functools.partial(kit.call_generate, w=5.0, steps=4, shape=SHAPE, pos=POS, conf=CONF, prompt=prompt)
 
 
 # ------------------------------------------------------------------------------------------ the rule

@@ -3,49 +3,28 @@
 library agree, and every refusal of k5_flowedit_step / k5_sample_flowedit's NULL arguments is made before anything is launched, so without
 a GPU.  No GPU."""
 import ctypes as C
+import functools
 import os
-import re
-import sys
 from types import SimpleNamespace as NS
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+import kit  # noqa: E402
+from kit import PKG, POS, assert_abi_entries, built_lib, flash_conf, host_tiny  # noqa: E402
+
+CONF = flash_conf()
 SHAPE = (3, 8, 12, 16)
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
 
 import flowedit_reference as FR  # noqa: E402
 import stochastic_reference as SR  # noqa: E402
 from kandinsky.generation_utils import edit_first_step, flowedit_plan, sigma_schedule  # noqa: E402
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
+prompt = functools.partial(kit.host_prompt, dims=(96, 48))
 
 
-def tiny(golden_meta):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return DiffusionTransformer3D(**c)
-
-
-def prompt(n, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 96, generator=g), "pooled_embed": torch.randn(1, 48, generator=g)}
-
-
-def call_generate(model, w=5.0, steps=4, **kw):
-    from kandinsky.generation_utils import generate
-    return generate(model, "cpu", SHAPE, steps, prompt(7), prompt(4, 1), POS, torch.arange(7), torch.arange(4), w, 5.0, CONF,
-                    noise=torch.zeros(SHAPE), **kw)
+call_generate = functools.partial(kit.call_generate, w=5.0, steps=4, shape=SHAPE, pos=POS, conf=CONF, prompt=prompt)
 
 
 # ------------------------------------------------------------------------------------------ the step classification
@@ -66,20 +45,11 @@ def test_step_classification_refuses_a_refine_outside_the_steps_that_run():
 
 
 # ------------------------------------------------------------------------------------------ generate's refusals
-class Wrapped(torch.nn.Module):
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond, self.num_visual_blocks = m, m.visual_cond, m.num_visual_blocks
-
-    def forward(self, *a, **k):
-        pytest.fail("refused calls must not run the model")
-
-    def forward_skip(self, *a, **k):
-        pytest.fail("refused calls must not run the model")
+Wrapped = functools.partial(kit.Wrapped, blocks=True, hand_on=("forward_skip",), refuse=True)
 
 
 def test_generate_refusals(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     m.sample = lambda *a, **k: pytest.fail("refused calls must not sample")
     src, mask = torch.zeros(SHAPE), torch.zeros(*SHAPE[:-1], 1)
     fe = dict(init_latent=src, source_text_embeds=prompt(5, 2), source_text_rope_pos=torch.arange(5))
@@ -123,7 +93,7 @@ def test_generate_sample_pipeline_and_cli_keywords(golden_meta, monkeypatch):
     import importlib.util
     from kandinsky import generation_utils as G
     from kandinsky import t2v_pipeline as P
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     shape = (1, 3, 8, 12, 16)
     for kw, word in ((dict(source_caption="a cat"), "needs a source video"), (dict(source_guidance_weight=3.5), "need source_caption"),
                      (dict(flowedit_refine=1), "need source_caption"), (dict(flowedit_seed=1), "need source_caption"),
@@ -235,18 +205,7 @@ NEW = ("k5_flowedit_step", "k5_sample_flowedit", "k5_dit_flowedit_state")
 
 def test_header_binding_and_library_agree_on_the_new_entries(built_lib):
     from kandinsky import _engine as E
-    hdr = open(os.path.join(ROOT, "include", "k5.h")).read()
-    assert int(re.search(r"#define K5_ABI_VERSION (\d+)", hdr).group(1)) == 11 == E.ABI_VERSION
-    lib = C.CDLL(built_lib)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in NEW:
-        decl = re.search(r"\b%s\s*\((.*?)\);" % name, code, flags=re.S)
-        assert decl, name
-        assert name in E.SYMBOLS and hasattr(lib, name)
-        assert len(decl.group(1).split(",")) == len(E.SYMBOLS[name][1]), name
-    for struct, cls in (("k5_flowedit_step_args", E.FlowEditStep), ("k5_flowedit_args", E.FlowEditArgs)):
-        fields = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), code, flags=re.S).group(1)
-        assert [f.strip().split()[-1].lstrip("*") for f in fields.split(";") if f.strip()] == [n for n, _ in cls._fields_], struct
+    assert_abi_entries(built_lib, NEW, [("k5_flowedit_step_args", E.FlowEditStep), ("k5_flowedit_args", E.FlowEditArgs)])
 
 
 def test_entries_refuse_bad_arguments_without_a_gpu(built_lib, golden_meta):
@@ -272,7 +231,7 @@ def test_entries_refuse_bad_arguments_without_a_gpu(built_lib, golden_meta):
         assert L.k5_flowedit_step(C.byref(good(**kw)), None) == 1, kw
         assert "k5_flowedit_step" in E.last_error() and word in E.last_error(), (kw, E.last_error())
     assert L.k5_dit_flowedit_state(None, None, None, None, 0) == 1 and "null handle" in E.last_error()
-    h = tiny(golden_meta)._create_handle()           # a handle is host memory until weights arrive
+    h = host_tiny(golden_meta)._create_handle()           # a handle is host memory until weights arrive
     try:
         s, f, t = C.c_longlong(7), C.c_longlong(7), C.c_longlong(7)
         assert L.k5_dit_flowedit_state(h, C.byref(s), C.byref(f), C.byref(t), 1) == 0 and (s.value, f.value, t.value) == (0, 0, 0)

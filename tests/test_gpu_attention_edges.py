@@ -23,23 +23,10 @@ pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
 from oracle import parity as P  # noqa: E402
+from kit import BF, E, bfr  # noqa: E402
 
-BF = torch.bfloat16
 C = O.SOFTMAX_C
 PROBE_TOL = 2.0 ** -8
-
-
-@pytest.fixture(scope="module")
-def E():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    from kandinsky import _engine as E
-    E.lib()
-    return E
-
-
-def bfr(x):
-    return x.to(BF).float()
 
 
 def rms8(x):

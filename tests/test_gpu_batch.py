@@ -3,7 +3,6 @@
 The invariant of the whole feature, asserted bit for bit everywhere: every sample of a many-sample call equals the same sample (same noise,
 prompt, negative prompt, conditioning) run alone through k5_sample / k5_sample_cond on the same handle with the same options."""
 import ctypes as C
-import os
 from types import SimpleNamespace as NS
 
 import pytest
@@ -12,29 +11,20 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
+from kit import make_dit, need_gpu, tiny_config  # noqa: E402
 
 NABLA = {"P": 0.8, "wT": 3, "wH": 3, "wW": 3}
 
 
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-
-
 @pytest.fixture(scope="module")
 def tiny_cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
+    return tiny_config(golden_meta)
 
 
 @pytest.fixture(scope="module")
 def tiny_dit(tiny_cfg, tiny_sd):
     need_gpu()
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**tiny_cfg)
-    d.load_state_dict(tiny_sd, assign=True)
-    return d.to("cuda:0")
+    return make_dit(tiny_cfg, tiny_sd)
 
 
 def wide_dit(qk_gain=1.0, seed=4):

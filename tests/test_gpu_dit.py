@@ -12,31 +12,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
+from kit import POS, cfg, make_dit, need_gpu, rel  # noqa: E402
 
 
 @pytest.fixture(scope="module")
 def tiny_dit(cfg, tiny_sd):
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    from kandinsky.models.dit import DiffusionTransformer3D
-    dit = DiffusionTransformer3D(**cfg)
-    dit.load_state_dict(tiny_sd, assign=True)
-    return dit.to("cuda:0")
-
-
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
+    need_gpu()
+    return make_dit(cfg, tiny_sd)
 
 
 def test_forward_tiny_vs_oracle_and_golden(tiny_dit, tiny_sd, cfg, golden):

@@ -5,12 +5,12 @@ Tolerances are those of tests/test_gpu_dit.py and tests/test_gpu_visual_cond.py:
 bf16-island oracle and 3e-2 of the reference's fp32 golden (tools/gen_golden_edit.py).  Everything that claims "the same computation"
 is asserted bit for bit, and so is the kept region: cells of keep mask 1 end as the source."""
 import ctypes as C
+import functools
 import json
 import os
 import socket
 import subprocess
 import sys
-from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
@@ -19,22 +19,11 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
+import kit  # noqa: E402
+from kit import BF, GOLDEN, POS, ROOT, _sp_case, cfg, edit_mask, f32, flash_conf, make_dit, prompts, rel, source_latent, tiny_dit, Wrapped  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
-BF = torch.bfloat16
+FLASH = flash_conf()
 SHAPE = (3, 8, 12, 16)
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def bfr(x):
-    return x.to(BF).float()
 
 
 @pytest.fixture(scope="module")
@@ -45,51 +34,7 @@ def edit_golden():
     return g, json.load(open(os.path.join(GOLDEN, "dit_tiny_edit_meta.json")))
 
 
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
-
-
-def make_dit(cfg, sd, **over):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**dict(cfg, **over))
-    d.load_state_dict(sd, assign=True)
-    return d.to("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def tiny_dit(cfg, tiny_sd):
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return make_dit(cfg, tiny_sd)
-
-
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
-
-
-def edit_mask(shape=SHAPE):
-    """frame 0 and the left half of the other frames kept, then a band of 0.25, the rest free"""
-    T, H, W, _ = shape
-    m = torch.zeros(T, H, W, 1)
-    m[0] = 1.0
-    m[1:, :, :W // 2] = 1.0
-    m[1:, :, W // 2:W // 2 + 2] = 0.25
-    return m
-
-
-def source_latent(shape=SHAPE, seed=77):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def run_generate(model, golden, w, steps=4, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)
-    return generate(model, "cuda:0", SHAPE, steps, te, ne, POS, torch.arange(7), torch.arange(4), w, 5.0, FLASH, noise=golden["gen.noise"], **kw)
+run_generate = functools.partial(kit.run_generate, steps=4, shape=SHAPE, pos=POS)
 
 
 def kept_exact(out, source, mask):
@@ -97,18 +42,7 @@ def kept_exact(out, source, mask):
     return torch.equal(out.cpu()[keep], source[keep])
 
 
-class Wrapped(torch.nn.Module):   # any non-DiffusionTransformer3D callable takes the per-step path of generate
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond = m, m.visual_cond
-
-    def forward(self, *a, **k):
-        return self.m(*a, **k)
-
-
 # ------------------------------------------------------------------------------------------ kernels
-def f32(x):
-    return float(np.float32(x))
 
 
 def renoise_ref(x0, eps, sigma):
@@ -262,13 +196,6 @@ def test_graph_captured_edit_step_is_bit_identical(cfg, tiny_sd, golden, w, sp):
     assert torch.isfinite(outs[0]).all()
     assert torch.equal(outs[0], outs[1])
     assert kept_exact(outs[1], src, mask)
-
-
-def _sp_case():
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from edit_rank_worker import case
-    shape, noise, te, ne, src, mask = case()
-    return shape, noise, {k: v.cuda() for k, v in te.items()}, {k: v.cuda() for k, v in ne.items()}, src, mask
 
 
 @pytest.mark.timeout(600)

@@ -5,20 +5,18 @@ scaling, the in-place scale against torch, and the engine through every way it r
 Kernel bound: relative error <= 1e-5 on the mean and on the score, the bound the project holds its fp32 transcendental chain to
 (k5_noise_normal_f32).  The products of bf16 values are exact in the MFMA's fp32 accumulator; what is left is 64 fp32 additions per logit, one
 v_exp_f32 per probability and up to 64 fp32 additions per row sum, each a few 2^-24 relative, averaged over T S Hh rows."""
+import functools
 import json
 import os
-import sys
-from types import SimpleNamespace as NS
 
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-BF = torch.bfloat16
+import kit  # noqa: E402
+from kit import BF, GOLDEN, K5_ERR_ARG, K5_ERR_STATE, K5_ERR_UNSUPPORTED, POS, cfg, flash_conf, need_gpu, prompts, rel  # noqa: E402
+
 BOUND = 1e-5
 WEIGHT = 4.0
 
@@ -207,17 +205,10 @@ def test_scale_refusals_launch_nothing():
 
 
 # ------------------------------------------------------------------------------------------ the engine
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+FLASH = flash_conf()
 SHAPE = (3, 8, 12, 16)                     # 72 tokens: T = 3, S = 24; not a multiple of 64, so the keys in memory are plain
 STEPS = 4
 INTERVAL = (0.7, 0.95)                     # of the sigmas 1, .938, .833, .625 (4 steps, scale 5) steps 1 and 2 lie inside
-K5_ERR_ARG, K5_ERR_STATE, K5_ERR_UNSUPPORTED = 1, 4, 6
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
 
 
 @pytest.fixture(scope="module")
@@ -227,40 +218,16 @@ def enh_golden():
             json.load(open(os.path.join(GOLDEN, "dit_tiny_enhance_meta.json"))))
 
 
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
-
-
-def make_dit(cfg, sd):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**cfg)
-    d.load_state_dict(sd, assign=True)
-    d = d.to("cuda:0")
-    d.engine("cuda:0")
-    return d
+make_dit = functools.partial(kit.make_dit, engine=True)
 
 
 @pytest.fixture(scope="module")
 def tiny_dit(cfg, tiny_sd):
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
+    need_gpu()
     return make_dit(cfg, tiny_sd)
 
 
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
-
-
-def run_generate(model, golden, w, steps=STEPS, shape=SHAPE, noise=None, pos=POS, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)
-    noise = golden["gen.noise"] if noise is None else noise
-    return generate(model, "cuda:0", shape, steps, te, ne, pos, torch.arange(7), torch.arange(4), w, 5.0, FLASH, noise=noise, **kw)
+run_generate = functools.partial(kit.run_generate, steps=STEPS, shape=SHAPE, pos=POS)
 
 
 def forward(model, golden, **kw):
@@ -278,23 +245,7 @@ def inputs_at(shape, seed=21):
     return (x.cuda(), text.cuda(), pooled.cuda(), t, pos, torch.arange(7))
 
 
-class Wrapped(torch.nn.Module):   # any non-DiffusionTransformer3D callable takes the per-step path of generate; this one hands the setting on
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond, self.num_visual_blocks = m, m.visual_cond, m.num_visual_blocks
-
-    def forward(self, *a, **k):
-        return self.m(*a, **k)
-
-    def set_enhance(self, *a, **k):
-        self.m.set_enhance(*a, **k)
-
-    def clear_enhance(self):
-        self.m.clear_enhance()
-
-    @property
-    def _enhance(self):
-        return self.m._enhance
+Wrapped = functools.partial(kit.Wrapped, blocks=True, hand_on=("set_enhance", "clear_enhance", "_enhance"))   # hands the setting on
 
 
 @pytest.fixture(scope="module")

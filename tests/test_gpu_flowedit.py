@@ -8,24 +8,20 @@ draws.  Everything that claims "the same computation" is asserted bit for bit.  
 |(out - src) - (gold - src)| / |gold - src|: the source dominates the full latent and would hide an error.  The engine is held to 1.5 x the
 distance of the bf16 oracle loop from the golden that the generator recorded (the forecast cache's margin: the engine's rounding points are
 the oracle's, its reduction orders are not)."""
+import functools
 import json
 import os
-import sys
-from types import SimpleNamespace as NS
 
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import flowedit_reference as FR  # noqa: E402
+import kit  # noqa: E402
+from kit import BF, GOLDEN, K5_ERR_ARG, K5_ERR_STATE, POS, cfg, flash_conf, make_dit, need_gpu, rel, tiny_dit  # noqa: E402
 
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
-BF = torch.bfloat16
+FLASH = flash_conf()
 SHAPE = (3, 8, 12, 16)
 STEPS = 6
 STRENGTH = 0.7            # first = 2: four of the six steps run
@@ -34,16 +30,6 @@ CASES = {"g1_1": (1.0, 1.0), "g2_5": (2.0, 5.0), "g1_5": (1.0, 5.0)}      # (sou
 FORWARDS = {"g1_1": 2, "g2_5": 4, "g1_5": 3}
 PROMPTS = {"g1_1": 2, "g2_5": 3, "g1_5": 3}                               # distinct prompts of a call
 GRID_TRIP = 2048 * 256 * 4                                                 # elements of one trip of the launcher's capped grid
-
-
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
 
 
 # ------------------------------------------------------------------------------------------ the kernel
@@ -236,46 +222,18 @@ def test_every_refusal_launches_nothing():
 
 
 # ------------------------------------------------------------------------------------------ the engine
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
 
 
-def make_dit(cfg, sd):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**cfg)
-    d.load_state_dict(sd, assign=True)
-    return d.to("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def tiny_dit(cfg, tiny_sd):
-    need_gpu()
-    return make_dit(cfg, tiny_sd)
-
-
-class Wrapped(torch.nn.Module):   # any non-DiffusionTransformer3D callable takes the per-step path of generate
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond, self.num_visual_blocks = m, m.visual_cond, m.num_visual_blocks
-
-    def forward(self, *a, **k):
-        return self.m(*a, **k)
+Wrapped = functools.partial(kit.Wrapped, blocks=True)
 
 
 def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    se = {k: v.cuda() for k, v in FR.source_prompt(golden).items()}
-    return te, ne, se
+    """the kit's two prompts and the source clip's"""
+    return (*kit.prompts(golden), {k: v.cuda() for k, v in FR.source_prompt(golden).items()})
 
 
-def run_generate(model, golden, w=5.0, steps=STEPS, te=None, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)[0] if te is None else te, prompts(golden)[1]
-    return generate(model, "cuda:0", SHAPE, steps, te, ne, POS, torch.arange(7), torch.arange(4), w, 5.0, FLASH, noise=golden["gen.noise"], **kw)
+def run_generate(model, golden, w=5.0, steps=STEPS, **kw):
+    return kit.run_generate(model, golden, w, steps=steps, shape=SHAPE, pos=POS, **kw)
 
 
 def run_flowedit(model, golden, name="g2_5", source=None, **kw):
@@ -412,9 +370,6 @@ def test_other_calls_on_the_handle_keep_their_bits(tiny_dit, golden, fused_runs)
         assert torch.equal(a, b)
     assert torch.equal(run_flowedit(tiny_dit, golden, "g2_5"), fused_runs["g2_5"][0])
     assert all(getattr(tiny_dit, a) is None for a in ("_watch", "_nag", "_regions", "_guidance", "_skip", "_stochastic", "_enhance", "_forecast"))
-
-
-K5_ERR_ARG, K5_ERR_STATE = 1, 4
 
 
 def test_c_level_refusals_leave_the_latent_untouched(tiny_dit, cfg, tiny_sd, golden):

@@ -6,9 +6,9 @@ the per-step loop's bits everywhere); parity with the bf16 oracle and the refere
 The model is the tiny config with four visual blocks on synthetic weights (tests/skip_reference.py), latent (3, 8, 12, 16), 8 or 9 steps:
 plan (9, interval 3, warmup 2, tail 1) has forecasts with k = 1 and 2 and an update with g = 3, plan (8, 2, 3, 1) alternates."""
 import ctypes as C
+import functools
 import json
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -18,15 +18,12 @@ pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import forecast_reference as FR  # noqa: E402
 import skip_reference as S  # noqa: E402
-from test_gpu_skip import (BIG, FLASH, K5_ERR_ARG, K5_ERR_STATE, POS, SHAPE, Recorder, edit_mask, make_dit, prompts, rel, run_generate,  # noqa: E402
-                           source_latent)
+import kit  # noqa: E402
+from kit import BF, GOLDEN, K5_ERR_ARG, K5_ERR_STATE, POS, edit_mask, make_dit, prompts, rel, source_latent  # noqa: E402
+from test_gpu_skip import BIG, FLASH, SHAPE, Recorder, run_generate  # noqa: E402
 
-BF = torch.bfloat16
 PLANS = {9: dict(forecast_interval=3, forecast_warmup=2, forecast_tail=1), 8: dict(forecast_interval=2, forecast_warmup=3, forecast_tail=1)}
 FULL = {9: [1, 1, 1, 0, 0, 1, 0, 0, 1], 8: [1, 1, 1, 1, 0, 1, 0, 1]}
 
@@ -366,26 +363,8 @@ def test_order_0_under_magcaches_mask_is_magcache(cfg, sd4, golden, no_cfg):
     d._destroy_engine(force=True)
 
 
-class Wrapped(torch.nn.Module):   # any non-DiffusionTransformer3D callable takes the per-step path of generate; this one hands the plan on
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond, self.num_visual_blocks = m, m.visual_cond, m.num_visual_blocks
-
-    def forward(self, *a, **k):
-        return self.m(*a, **k)
-
-    def set_forecast(self, *a):
-        self.m.set_forecast(*a)
-
-    def clear_forecast(self):
-        self.m.clear_forecast()
-
-    def forecast_at(self, *a):
-        self.m.forecast_at(*a)
-
-    @property
-    def _forecast(self):
-        return self.m._forecast
+Wrapped = functools.partial(kit.Wrapped, blocks=True,          # this one hands the plan on
+                            hand_on=("set_forecast", "clear_forecast", "forecast_at", "_forecast"))
 
 
 @pytest.mark.parametrize("case", [(9, 5.0, 2), (9, 1.0, 1), (8, 5.0, 1), (8, 1.0, 2)])

@@ -15,12 +15,11 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
+from kit import GOLDEN, K5_ERR_ARG, K5_ERR_STATE, K5_ERR_UNSUPPORTED  # noqa: E402
+
 FAMILIES = ("elementwise", "gemm", "attn_self", "attn_cross", "nabla_map", "prologue", "epilogue", "comm", "attn_text")
 SF = (1.0, 2.0, 2.0)
 SHAPE, OTHER = (3, 8, 12), (2, 8, 12)       # the golden forward's latent (72 tokens) and another one (48 tokens)
-K5_ERR_ARG, K5_ERR_STATE, K5_ERR_UNSUPPORTED = 1, 4, 6
 
 
 @pytest.fixture(scope="module")

@@ -8,7 +8,6 @@ and 3e-2 of the reference's fp32 golden (tools/gen_golden_guidance.py).  Everyth
 import ctypes as C
 import json
 import os
-import sys
 from types import SimpleNamespace as NS
 
 import numpy as np
@@ -19,13 +18,12 @@ pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import guidance_reference as R  # noqa: E402
+import kit  # noqa: E402
+from kit import (GOLDEN, K5_ERR_ARG, K5_ERR_STATE, K5_ERR_UNSUPPORTED, POS, _sp_case, cfg,  # noqa: E402
+                 edit_mask, f32, flash_conf, make_dit, prompts, rel, source_latent, tiny_dit, Wrapped)
 
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+FLASH = flash_conf()
 BF = torch.bfloat16
 SHAPE = (3, 8, 12, 16)
 STEPS = 6
@@ -36,71 +34,10 @@ PLANS = {"schedule": dict(guidance_schedule=SCHEDULE),
          "zero_star_init": dict(cfg_zero_star=True, cfg_zero_init=1),
          "rescale": dict(cfg_rescale=0.7),
          "all": dict(guidance_schedule=SCHEDULE, guidance_interval=INTERVAL, cfg_zero_star=True, cfg_zero_init=1, cfg_rescale=0.7)}
-K5_ERR_ARG, K5_ERR_STATE, K5_ERR_UNSUPPORTED = 1, 4, 6
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def f32(x):
-    return float(np.float32(x))
-
-
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
-
-
-def make_dit(cfg, sd, **over):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**dict(cfg, **over))
-    d.load_state_dict(sd, assign=True)
-    return d.to("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def tiny_dit(cfg, tiny_sd):
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return make_dit(cfg, tiny_sd)
-
-
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
 
 
 def run_generate(model, golden, w=5.0, steps=STEPS, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)
-    return generate(model, "cuda:0", SHAPE, steps, te, ne, POS, torch.arange(7), torch.arange(4), w, 5.0, FLASH, noise=golden["gen.noise"], **kw)
-
-
-def edit_mask(shape=SHAPE):
-    T, H, W, _ = shape
-    m = torch.zeros(T, H, W, 1)
-    m[0] = 1.0
-    m[1:, :, :W // 2] = 1.0
-    m[1:, :, W // 2:W // 2 + 2] = 0.25
-    return m
-
-
-def source_latent(shape=SHAPE, seed=77):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-class Wrapped(torch.nn.Module):   # any non-DiffusionTransformer3D callable takes the per-step path of generate
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond = m, m.visual_cond
-
-    def forward(self, *a, **k):
-        return self.m(*a, **k)
+    return kit.run_generate(model, golden, w, steps=steps, shape=SHAPE, pos=POS, **kw)
 
 
 # ------------------------------------------------------------------------------------------ kernels: the statistics
@@ -424,17 +361,13 @@ def test_parity_with_the_oracle_and_the_reference_golden(tiny_dit, tiny_sd, cfg,
 
 
 # ------------------------------------------------------------------------------------------ ranks
-def _sp_case():
-    from edit_rank_worker import case
-    shape, noise, te, ne, src, mask = case()
-    return shape, noise, {k: v.cuda() for k, v in te.items()}, {k: v.cuda() for k, v in ne.items()}
 
 
 @pytest.mark.timeout(600)
 def test_loopback_ranks_with_a_mixed_plan(tiny_sd, cfg):
     from test_gpu_loopback import run_ranks
     from kandinsky.generation_utils import generate
-    shape, noise, te, ne = _sp_case()
+    shape, noise, te, ne = _sp_case()[:4]
     pos = [torch.arange(8)] * 3
     plan = dict(guidance_interval=(0.6, 0.95), cfg_zero_star=True, cfg_rescale=0.7)     # 4 steps of scale 5: sigmas 1, .938, .833, .625
 
@@ -454,7 +387,7 @@ def test_loopback_ranks_with_a_mixed_plan(tiny_sd, cfg):
 def test_cfg_pair_in_the_engine_with_a_uniform_plan(tiny_sd, cfg):
     from test_gpu_loopback import run_cfg_ranks
     from kandinsky.generation_utils import generate
-    shape, noise, te, ne = _sp_case()
+    shape, noise, te, ne = _sp_case()[:4]
     pos = [torch.arange(8)] * 3
     plan = dict(guidance_schedule=[5.0, 4.0, 3.0, 2.0], cfg_zero_star=True, cfg_rescale=0.7)
 

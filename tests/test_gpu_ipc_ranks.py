@@ -22,14 +22,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
+from kit import ROOT, rel  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.join(ROOT, "tests", "golden")
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
 
 
 def launch(P, case, out, extra=(), timeout=840, expect_failure=False, ipc_timeout="120"):

@@ -11,26 +11,12 @@ pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
 from oracle import parity as P  # noqa: E402
-
-BF = torch.bfloat16
-
-
-@pytest.fixture(scope="module")
-def E():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X (torch.cuda.is_available() is False)")
-    from kandinsky import _engine as E
-    E.lib()
-    return E
+from kit import BF, E, bfr  # noqa: E402
 
 
 def rnd(*shape, seed=0, scale=1.0):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(*shape, generator=g) * scale
-
-
-def bfr(x):
-    return x.to(BF).float()
 
 
 def assert_bf16_close(got, ref, ulps=2, atol=1e-3, what=""):

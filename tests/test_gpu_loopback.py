@@ -16,11 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
+from kit import rel  # noqa: E402
 
 
 def run_ranks(P, make_dit, call, slices=1, options=None):

@@ -11,6 +11,7 @@ Engine (k5_dit_add_lora / k5_dit_clear_lora / k5_dit_lora_state): handle X gets 
 (tools/gen_golden_lora.py), handle Y is loaded with a checkpoint whose matrices were merged beforehand by k5_lora_merge on torch tensors in
 the packed dtype.  X and Y must agree bit for bit wherever the engine is deterministic, and differ from the un-adapted handle."""
 import ctypes as C
+import functools
 import os
 import threading
 
@@ -20,25 +21,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
+import kit  # noqa: E402
+from kit import E, GOLDEN, POS, rel  # noqa: E402
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
+make_dit = functools.partial(kit.make_dit, engine=True)
+
 NPOS = [torch.arange(6), torch.arange(16), torch.arange(16)]
 SF = (1.0, 2.0, 2.0)
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-@pytest.fixture(scope="module")
-def E():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    from kandinsky import _engine
-    _engine.lib()
-    return _engine
 
 
 # ------------------------------------------------------------------------------------------ 1. kernel against float64
@@ -164,15 +153,6 @@ def merged_on_gpu(E, sd, adapters):
             out[key] = W.float().cpu()
     torch.cuda.synchronize()
     return out
-
-
-def make_dit(cfg, sd):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**cfg)
-    d.load_state_dict(sd, assign=True)
-    d = d.to("cuda:0")
-    d.engine("cuda:0")
-    return d
 
 
 def sigmas(steps, scale=5.0):

@@ -6,7 +6,6 @@ Yardstick of the ratio comparisons (DESIGN.md §2 form): dist(a, b) = |a - b|_2 
     engine vs bf16 oracle          <= 1.5 x dist(bf16 oracle, fp32 reference)   — a second bf16 realisation of the same function
     engine vs the fp32 reference   <= 3   x dist(bf16 oracle, fp32 reference)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -16,13 +15,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
 from test_magcache_calib_host import POS, case_inputs, load_fixture, oracle_calibration  # noqa: E402
-
-K5_ERR_ARG, K5_ERR_ALIGN, K5_ERR_STATE = 1, 2, 4   # include/k5.h
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
+from kit import K5_ERR_ALIGN, K5_ERR_ARG, K5_ERR_STATE, cfg, rel  # noqa: E402
 
 
 def dist(a, b):
@@ -104,11 +97,6 @@ def test_stats_kernel_odd_width_and_arguments():
 
 
 # ------------------------------------------------------------------------------------------ engine, tiny model
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
 
 
 def fresh_dit(cfg, tiny_sd):

@@ -13,26 +13,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
 from oracle import parity  # noqa: E402
-
-BF = torch.bfloat16
-
-
-@pytest.fixture(scope="module")
-def E():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    from kandinsky import _engine as E
-    E.lib()
-    return E
-
-
-def bfr(x):
-    return x.to(BF).float()
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
+from kit import BF, E, bfr, rel  # noqa: E402
 
 
 def _cdf_at_entries(q, k, mode="bf16"):

@@ -16,13 +16,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
+from kit import rel  # noqa: E402
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
 
 
 def _case(tag):

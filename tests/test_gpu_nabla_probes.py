@@ -25,19 +25,8 @@ pytestmark = pytest.mark.gpu
 
 import nabla_probe_reference as R  # noqa: E402
 from oracle import parity  # noqa: E402
-from test_gpu_attention_edges import PROBE_TOL, bfr, dev, rms8  # noqa: E402
-
-BF = torch.bfloat16
-K5_ERR_ARG, K5_ERR_UNSUPPORTED = 1, 6
-
-
-@pytest.fixture(scope="module")
-def E():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    from kandinsky import _engine as E
-    E.lib()
-    return E
+from test_gpu_attention_edges import PROBE_TOL, dev, rms8  # noqa: E402
+from kit import BF, E, K5_ERR_ARG, K5_ERR_UNSUPPORTED, bfr  # noqa: E402
 
 
 def wide(x):

@@ -5,31 +5,23 @@ the plain run where the rule is an identity, and against itself where two paths 
 Kernel bound, per element: |out - ref| <= 2^-8 |ref| + 2^-12 (|z+| + |f g|) — bf16's half ulp, plus the fp32 chain with worst-case row sums
 (D 2^-24 ~ 1.1e-4 at D = 1792, the figure DESIGN.md uses for the row LayerNorm).  Engine parity: relative L2 <= min(3e-2, delta / 4), 3e-2 being
 the project's bound against fp32 goldens and delta the golden's own distance from the plain run, so a build that ignores NAG fails."""
+import functools
 import json
 import os
-import sys
-from types import SimpleNamespace as NS
 
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
-BF = torch.bfloat16
+import kit  # noqa: E402
+from kit import BF, GOLDEN, POS, cfg, flash_conf, make_dit, prompts, rank_case, rel, tiny_dit  # noqa: E402
+
+FLASH = flash_conf()
 SHAPE = (3, 8, 12, 16)
 PARAMS = (5.0, 2.5, 0.25)
 
 from nag_reference import nag_inputs, nag_reference  # noqa: E402
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
 
 
 # ------------------------------------------------------------------------------------------ the kernel
@@ -138,44 +130,13 @@ def nag_golden():
     return dict(load_file(os.path.join(GOLDEN, "dit_tiny_nag.safetensors"))), json.load(open(os.path.join(GOLDEN, "dit_tiny_nag_meta.json")))
 
 
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
-
-
-def make_dit(cfg, sd):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**cfg)
-    d.load_state_dict(sd, assign=True)
-    return d.to("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def tiny_dit(cfg, tiny_sd):
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return make_dit(cfg, tiny_sd)
-
-
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
-
-
 def nag_kw(golden, params=PARAMS, positive=False):
     te, ne = prompts(golden)
     s, tau, alpha = params
     return dict(nag_text_embeds=te if positive else ne, nag_text_rope_pos=torch.arange(7 if positive else 4), nag_scale=s, nag_tau=tau, nag_alpha=alpha)
 
 
-def run_generate(model, golden, w, steps=4, shape=SHAPE, noise=None, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)
-    noise = golden["gen.noise"] if noise is None else noise
-    return generate(model, "cuda:0", shape, steps, te, ne, POS, torch.arange(7), torch.arange(4), w, 5.0, FLASH, noise=noise, **kw)
+run_generate = functools.partial(kit.run_generate, steps=4, shape=SHAPE, pos=POS)
 
 
 def forward(model, golden, x=None, neg=False, time=None):
@@ -402,13 +363,6 @@ def test_magcache_skips_the_guidance_with_the_blocks(cfg, tiny_sd, golden):
 
 
 # ------------------------------------------------------------------------------------------ ranks
-def rank_case():
-    g = torch.Generator().manual_seed(5)
-    shape = (8, 16, 16, 16)
-    noise = torch.randn(*shape, generator=g)
-    te = {"text_embeds": torch.randn(9, 96, generator=g).cuda(), "pooled_embed": torch.randn(1, 48, generator=g).cuda()}
-    ne = {"text_embeds": torch.randn(4, 96, generator=g).cuda(), "pooled_embed": torch.randn(1, 48, generator=g).cuda()}
-    return shape, noise, te, ne
 
 
 @pytest.mark.timeout(600)

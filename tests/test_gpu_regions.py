@@ -9,9 +9,9 @@ at most R + 8 <= 16 roundings occur (4 cells and their division, R + 1 additions
 relative L2 <= min(3e-2, delta / 4), 3e-2 being the project's bound against fp32 goldens and delta the golden's own distance from the plain
 run, so a build that ignores the regions fails; the run with the two masks swapped must be farther away than delta / 4, so a build with the
 wrong token order fails."""
+import functools
 import json
 import os
-import sys
 from types import SimpleNamespace as NS
 
 import pytest
@@ -19,20 +19,13 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
-BF = torch.bfloat16
+import kit  # noqa: E402
+from kit import BF, GOLDEN, POS, cfg, flash_conf, make_dit, prompts, rank_case, rel, tiny_dit  # noqa: E402
+
+FLASH = flash_conf()
 SHAPE = (3, 8, 12, 16)
 
 from regions_reference import combine_inputs, combine_reference, mask_cases, nabla_perm, token_weights_reference  # noqa: E402
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
 
 
 def bits(t):
@@ -188,33 +181,6 @@ def reg_golden():
             json.load(open(os.path.join(GOLDEN, "dit_tiny_regions_meta.json"))))
 
 
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
-
-
-def make_dit(cfg, sd):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**cfg)
-    d.load_state_dict(sd, assign=True)
-    return d.to("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def tiny_dit(cfg, tiny_sd):
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return make_dit(cfg, tiny_sd)
-
-
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
-
-
 def region_kw(g, masks, bw=0.0, swap=False, only=None):
     """generate()'s keywords for the fixture's two region prompts on `masks` (2, T, H, W)"""
     texts = [{"text_embeds": g["regions.text0"].cuda()}, {"text_embeds": g["regions.text1"].cuda()}]
@@ -230,12 +196,7 @@ def set_regions(model, kw):
     return model.set_regions(kw["region_text_embeds"], kw["region_text_rope_pos"], kw["region_masks"], kw["region_base_weight"])
 
 
-def run_generate(model, golden, w, steps=4, shape=SHAPE, noise=None, te=None, text_pos=None, **kw):
-    from kandinsky.generation_utils import generate
-    base, ne = prompts(golden)
-    noise = golden["gen.noise"] if noise is None else noise
-    return generate(model, "cuda:0", shape, steps, base if te is None else te, ne, POS, torch.arange(7) if text_pos is None else text_pos,
-                    torch.arange(4), w, 5.0, FLASH, noise=noise, **kw)
+run_generate = functools.partial(kit.run_generate, steps=4, shape=SHAPE, pos=POS)
 
 
 def forward(model, golden, x=None, neg=False, time=None, te=None, n=None):
@@ -509,13 +470,6 @@ def test_with_nag_and_zero_masks_the_run_is_the_nag_run(tiny_dit, golden, reg_go
 
 
 # ------------------------------------------------------------------------------------------ ranks
-def rank_case():
-    g = torch.Generator().manual_seed(5)
-    shape = (8, 16, 16, 16)
-    noise = torch.randn(*shape, generator=g)
-    te = {"text_embeds": torch.randn(9, 96, generator=g).cuda(), "pooled_embed": torch.randn(1, 48, generator=g).cuda()}
-    ne = {"text_embeds": torch.randn(4, 96, generator=g).cuda(), "pooled_embed": torch.randn(1, 48, generator=g).cuda()}
-    return shape, noise, te, ne
 
 
 def rank_regions():

@@ -2,37 +2,20 @@
 reach: that all of them together survive a rebuild of the engine bit for bit, and that an install the library refuses leaves the previous
 setting installed and the memory the engine borrows for it alive."""
 import gc
-import os
-import sys
 
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-K5_ERR_ARG = 1
+from kit import K5_ERR_ARG, POS, make_dit, need_gpu, prompts, tiny_config  # noqa: E402
 
 
 @pytest.fixture
 def dit(golden_meta, tiny_sd):
     """a tiny model of its own per test: both tests leave the handle in a state of their making"""
-    from kandinsky.models.dit import DiffusionTransformer3D
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    d = DiffusionTransformer3D(**c)
-    d.load_state_dict(tiny_sd, assign=True)
-    return d.to("cuda:0")
-
-
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
+    need_gpu()
+    return make_dit(tiny_config(golden_meta), tiny_sd)
 
 
 def other_prompt(n, seed):

@@ -8,9 +8,9 @@ at once.  Tolerances are the project's (tests/test_gpu_dit.py, tests/test_gpu_gu
 1e-2 of the bf16-island oracle and 3e-2 of the reference's fp32 golden (tools/gen_golden_skip.py), the NABLA forward included.  Everything
 that claims "the same computation" is asserted bit for bit."""
 import ctypes as C
+import functools
 import json
 import os
-import sys
 from types import SimpleNamespace as NS
 
 import numpy as np
@@ -21,14 +21,11 @@ pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import skip_reference as S  # noqa: E402
+import kit  # noqa: E402
+from kit import BF, GOLDEN, K5_ERR_ARG, K5_ERR_STATE, POS, edit_mask, f32, flash_conf, make_dit, prompts, rel, source_latent  # noqa: E402
 
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
-BF = torch.bfloat16
+FLASH = flash_conf()
 SHAPE = (3, 8, 12, 16)
 STEPS = 6
 INTERVAL = (0.6, 0.97)      # of the sigmas 1, .962, .909, .833, .714, .5 (6 steps, scale 5) steps 1..4 lie inside: a mixed run
@@ -36,16 +33,6 @@ CASES = {"block_mid": (5.0, dict(slg_blocks=[1], slg_scale=3.0)),
          "block_first_nocfg": (1.0, dict(slg_blocks=[0], slg_scale=3.0)),
          "attention_interval": (5.0, dict(slg_blocks=[1, 2], slg_scale=3.0, slg_mode="attention", slg_interval=INTERVAL)),
          "with_zero_star_rescale": (5.0, dict(slg_blocks=[2], slg_scale=3.0, cfg_zero_star=True, cfg_rescale=0.7))}
-K5_ERR_ARG, K5_ERR_STATE = 1, 4
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def f32(x):
-    return float(np.float32(x))
 
 
 @pytest.fixture(scope="module")
@@ -58,13 +45,6 @@ def sd4(cfg):
     return S.tiny4_weights(cfg)
 
 
-def make_dit(cfg, sd, **over):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**dict(cfg, **over))
-    d.load_state_dict(sd, assign=True)
-    return d.to("cuda:0")
-
-
 @pytest.fixture(scope="module")
 def dit(cfg, sd4):
     if not torch.cuda.is_available():
@@ -74,51 +54,12 @@ def dit(cfg, sd4):
     return d
 
 
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
-
-
 def run_generate(model, golden, w=5.0, steps=STEPS, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)
-    return generate(model, "cuda:0", SHAPE, steps, te, ne, POS, torch.arange(7), torch.arange(4), w, 5.0, FLASH, noise=golden["gen.noise"], **kw)
+    return kit.run_generate(model, golden, w, steps=steps, shape=SHAPE, pos=POS, **kw)
 
 
-def edit_mask(shape=SHAPE):
-    T, H, W, _ = shape
-    m = torch.zeros(T, H, W, 1)
-    m[0] = 1.0
-    m[1:, :, :W // 2] = 1.0
-    m[1:, :, W // 2:W // 2 + 2] = 0.25
-    return m
-
-
-def source_latent(shape=SHAPE, seed=77):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-class Wrapped(torch.nn.Module):   # any non-DiffusionTransformer3D callable takes the per-step path of generate; this one can fork
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond, self.num_visual_blocks = m, m.visual_cond, m.num_visual_blocks
-
-    def forward(self, *a, **k):
-        return self.m(*a, **k)
-
-    def forward_skip(self, *a, **k):
-        return self.m.forward_skip(*a, **k)
-
-    def set_skip_guidance(self, *a, **k):
-        self.m.set_skip_guidance(*a, **k)
-
-    def clear_skip_guidance(self):
-        self.m.clear_skip_guidance()
-
-    @property
-    def _skip(self):
-        return self.m._skip
+Wrapped = functools.partial(kit.Wrapped, blocks=True,          # this one can fork
+                            hand_on=("forward_skip", "set_skip_guidance", "clear_skip_guidance", "_skip"))
 
 
 # ------------------------------------------------------------------------------------------ kernel: the three-velocity update

@@ -8,8 +8,6 @@ proves on the CPU that each case reaches the path it claims and tells the true i
 Every output buffer has guard rows before and after (and guard columns where there is a row stride), filled with a NaN bit pattern
 that must come back untouched."""
 import itertools
-import os
-import sys
 
 from types import SimpleNamespace as NS
 
@@ -18,12 +16,12 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kit import BF, E  # noqa: E402
+
 import small_ops_reference as R  # noqa: E402
 
 from oracle import k5_oracle as O  # noqa: E402
 
-BF = torch.bfloat16
 OK, ERR_ARG, ERR_ALIGN, ERR_UNSUPPORTED = 0, 1, 2, 6
 
 # ------------------------------------------------------------------------------------------ case tables (shared with the host file)
@@ -53,15 +51,6 @@ UNPATCH_TRIP_CASES = UNPATCH_CASES[-1:]
 
 def ids(v):
     return str(v).replace(" ", "")
-
-
-@pytest.fixture(scope="module")
-def E():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X (torch.cuda.is_available() is False)")
-    from kandinsky import _engine as E
-    E.lib()
-    return E
 
 
 _cache = {}

@@ -11,26 +11,13 @@ pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
 from oracle import parity as P  # noqa: E402
+from kit import BF, E, bfr  # noqa: E402
 
-BF = torch.bfloat16
 C = torch.tensor(O.SOFTMAX_C, dtype=torch.float32)
-
-
-@pytest.fixture(scope="module")
-def E():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    from kandinsky import _engine as E
-    E.lib()
-    return E
 
 
 def rnd(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
-
-
-def bfr(x):
-    return x.to(BF).float()
 
 
 def close(got, ref, ulps=4, atol=1e-2, what=""):

@@ -14,7 +14,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
-from test_gpu_loopback import rel, run_cfg_ranks, run_ranks, tiny_cfg  # noqa: E402
+from kit import rel  # noqa: E402
+from test_gpu_loopback import run_cfg_ranks, run_ranks, tiny_cfg  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HERE = os.path.join(ROOT, "tests", "golden")

@@ -12,10 +12,9 @@ float64 side has no fp32 counterpart (sincospif takes 2 u1 exactly) but the radi
 sin / cos and the final product, 5.8 * a few * 6e-8 ~ 2e-6, and near u0 -> 1 the log's absolute error of ~1 ulp(1e-7) under the square root
 adds the same order: about 4e-6 in all, capped at 1e-5.  Measured on the MI355X: 6.4e-7 at n = 2^20 (the test prints it)."""
 import ctypes as C
+import functools
 import json
 import os
-import sys
-from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
@@ -25,13 +24,12 @@ pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import stochastic_reference as SR  # noqa: E402
+import kit  # noqa: E402
+from kit import (GOLDEN, K5_ERR_ARG, K5_ERR_STATE, POS, _sp_case, cfg, edit_mask,  # noqa: E402
+                 f32, flash_conf, make_dit, need_gpu, prompts, rel, source_latent, tiny_dit)
 
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+FLASH = flash_conf()
 BF = torch.bfloat16
 SHAPE = (3, 8, 12, 16)
 STEPS = 6
@@ -41,16 +39,6 @@ CASES = {"eta1_cfg": (5.0, dict(eta=1.0)),
          "eta_half_interval_nocfg": (1.0, dict(eta=0.5, sde_interval=INTERVAL)),
          "eta1_zero_star_skip": (5.0, dict(eta=1.0, cfg_zero_star=True, slg_blocks=[1], slg_scale=2.0))}
 NOISY = {"eta1_cfg": 5, "eta_half_interval_nocfg": 4, "eta1_zero_star_skip": 5}
-K5_ERR_ARG, K5_ERR_STATE = 1, 4
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def f32(x):
-    return float(np.float32(x))
 
 
 def u32(t):
@@ -59,9 +47,6 @@ def u32(t):
 
 
 # ------------------------------------------------------------------------------------------ raw words
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
 
 
 @pytest.mark.parametrize("blk0, seed, c2, c3, want", [
@@ -289,71 +274,14 @@ def test_stochastic_euler_refusals_launch_nothing():
 
 
 # ------------------------------------------------------------------------------------------ the tiny model
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
-
-
-def make_dit(cfg, sd, **over):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**dict(cfg, **over))
-    d.load_state_dict(sd, assign=True)
-    return d.to("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def tiny_dit(cfg, tiny_sd):
-    need_gpu()
-    return make_dit(cfg, tiny_sd)
-
-
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
 
 
 def run_generate(model, golden, w=5.0, steps=STEPS, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)
-    return generate(model, "cuda:0", SHAPE, steps, te, ne, POS, torch.arange(7), torch.arange(4), w, 5.0, FLASH, noise=golden["gen.noise"], **kw)
+    return kit.run_generate(model, golden, w, steps=steps, shape=SHAPE, pos=POS, **kw)
 
 
-def edit_mask(shape=SHAPE):
-    T, H, W, _ = shape
-    m = torch.zeros(T, H, W, 1)
-    m[0] = 1.0
-    m[1:, :, :W // 2] = 1.0
-    m[1:, :, W // 2:W // 2 + 2] = 0.25
-    return m
-
-
-def source_latent(shape=SHAPE, seed=77):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-class Wrapped(torch.nn.Module):   # any non-DiffusionTransformer3D callable takes the per-step path of generate; this one can fork
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond, self.num_visual_blocks = m, m.visual_cond, m.num_visual_blocks
-
-    def forward(self, *a, **k):
-        return self.m(*a, **k)
-
-    def forward_skip(self, *a, **k):
-        return self.m.forward_skip(*a, **k)
-
-    def set_skip_guidance(self, *a, **k):
-        self.m.set_skip_guidance(*a, **k)
-
-    def clear_skip_guidance(self):
-        self.m.clear_skip_guidance()
-
-    @property
-    def _skip(self):
-        return self.m._skip
+Wrapped = functools.partial(kit.Wrapped, blocks=True,          # this one can fork
+                            hand_on=("forward_skip", "set_skip_guidance", "clear_skip_guidance", "_skip"))
 
 
 @pytest.fixture(scope="module")
@@ -504,10 +432,6 @@ def test_parity_with_the_oracle_and_the_reference_golden(tiny_sd, cfg, golden, s
 
 
 # ------------------------------------------------------------------------------------------ ranks
-def _sp_case():
-    from edit_rank_worker import case
-    shape, noise, te, ne, src, mask = case()
-    return shape, noise, {k: v.cuda() for k, v in te.items()}, {k: v.cuda() for k, v in ne.items()}
 
 
 @pytest.mark.timeout(600)
@@ -515,7 +439,7 @@ def test_loopback_ranks(tiny_sd, cfg):
     from test_gpu_loopback import run_ranks
     from kandinsky.generation_utils import generate
     need_gpu()
-    shape, noise, te, ne = _sp_case()
+    shape, noise, te, ne = _sp_case()[:4]
     pos = [torch.arange(8)] * 3
 
     def call(d, r):
@@ -535,7 +459,7 @@ def test_cfg_pair_in_the_engine(tiny_sd, cfg):
     from test_gpu_loopback import run_cfg_ranks
     from kandinsky.generation_utils import generate
     need_gpu()
-    shape, noise, te, ne = _sp_case()
+    shape, noise, te, ne = _sp_case()[:4]
     pos = [torch.arange(8)] * 3
 
     def call(d, i):

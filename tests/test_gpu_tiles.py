@@ -15,10 +15,11 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
-from test_gpu_windows import BF, FLASH, GOLDEN, Wrapped, _tiny_pipeline, f32, make_dit, other_prompt, prompts, rel  # noqa: E402
+import kit  # noqa: E402
+from kit import BF, GOLDEN, POS, Wrapped, cfg, f32, make_dit, prompts, rel, tiny_dit  # noqa: E402
+from test_gpu_windows import _tiny_pipeline, other_prompt  # noqa: E402
 
 WINDOW = (3, 8, 12)
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
 CASES = ("s14", "s22", "t2s2")
 
 
@@ -28,24 +29,8 @@ def tile_golden():
     return dict(load_file(os.path.join(GOLDEN, "dit_tiny_tiles.safetensors"))), json.load(open(os.path.join(GOLDEN, "dit_tiny_tiles_meta.json")))
 
 
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
-
-
-@pytest.fixture(scope="module")
-def tiny_dit(cfg, tiny_sd):
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return make_dit(cfg, tiny_sd)
-
-
 def run_generate(model, golden, noise, w, steps=4, pos=None, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)
-    return generate(model, "cuda:0", tuple(noise.shape), steps, te, ne, pos or POS, torch.arange(7), torch.arange(4), w, 5.0, FLASH, noise=noise, **kw)
+    return kit.run_generate(model, golden, w, steps=steps, shape=tuple(noise.shape), pos=pos or POS, noise=noise, **kw)
 
 
 def tile_kw(meta, tag):

@@ -11,13 +11,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import vae_oracle as V  # noqa: E402
+from kit import ABI_VERSION_PIN, bfr, rel  # noqa: E402
 
 CFG = dict(latent_channels=16, out_channels=3, block_out_channels=(64, 64, 128, 128), layers_per_block=2, norm_num_groups=16)
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
 
 
 @pytest.fixture(scope="module")
@@ -37,10 +33,6 @@ def vae():
             sd[k] = torch.randn(p.shape, generator=g) * (1.5 / (p[0].numel() ** 0.5))
     m.load_state_dict(sd, assign=True)
     return m.to("cuda:0"), sd
-
-
-def bfr(x):
-    return x.bfloat16().float()
 
 
 def test_conv3d_kernel_with_upsample_and_residual(vae):
@@ -466,7 +458,7 @@ def test_blend_place_launcher_contract():
     one frame into a longer buffer); calls that would read past what a or b hold are refused with K5_ERR_ARG before any launch."""
     from kandinsky import _engine as E
     L = E.lib()
-    assert L.k5_abi_version() == 11                     # the ABI that gave the launcher b's length
+    assert L.k5_abi_version() == ABI_VERSION_PIN        # the ABI that gave the launcher b's length
     g = torch.Generator().manual_seed(12)
     outer, la, lb, h, w, extent, keep = 3, 9, 12, 5, 8, 4, 7
     inner = h * w

@@ -8,17 +8,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import vae_oracle as V  # noqa: E402
+from kit import bfr, rel  # noqa: E402
 
 CFG = dict(latent_channels=16, out_channels=3, block_out_channels=(64, 64, 128, 128), layers_per_block=2, norm_num_groups=16)
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def bfr(x):
-    return x.bfloat16().float()
 
 
 @pytest.fixture(scope="module")

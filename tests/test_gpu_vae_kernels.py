@@ -13,18 +13,16 @@ Every output has NaN-pattern guard rows before and after (and guard columns wher
 untouched; every call is run twice and must give the same bits.  tests/test_vae_kernels_host.py imports the case tables below and
 proves on the CPU that each case reaches the path it claims."""
 import math
-import os
-import sys
 
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kit import BF, E  # noqa: E402
+
 import vae_kernels_reference as R  # noqa: E402
 
-BF = torch.bfloat16
 OK, ERR_ARG, ERR_ALIGN, ERR_UNSUPPORTED = 0, 1, 2, 6
 
 # ------------------------------------------------------------------------------------------ case tables (shared with the host file)
@@ -81,15 +79,6 @@ GN_REFUSALS = [((4, 520, 65), ERR_ARG), ((4, 128, 24), ERR_ARG), ((4, 36, 9), ER
 
 def ids(v):
     return str(v).replace(" ", "")
-
-
-@pytest.fixture(scope="module")
-def E():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X (torch.cuda.is_available() is False)")
-    from kandinsky import _engine as E
-    E.lib()
-    return E
 
 
 _cache = {}

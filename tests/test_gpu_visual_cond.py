@@ -17,16 +17,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
+import kit  # noqa: E402
+from kit import GOLDEN, POS, ROOT, cfg, flash_conf, make_dit, prompts, rel, tiny_dit, Wrapped  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
+FLASH = flash_conf()
 
 
 @pytest.fixture(scope="module")
@@ -50,51 +44,12 @@ def vc_meta():
     return json.load(open(os.path.join(GOLDEN, "dit_tiny_visual_cond_meta.json")))
 
 
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
-
-
-def make_dit(cfg, sd, **over):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**dict(cfg, **over))
-    d.load_state_dict(sd, assign=True)
-    return d.to("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def tiny_dit(cfg, tiny_sd):
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return make_dit(cfg, tiny_sd)
-
-
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
-
-
 def cond17(vc_golden, prefix="cond"):
     return torch.cat([vc_golden[f"{prefix}.visual_cond"], vc_golden[f"{prefix}.mask"]], -1).cuda().contiguous()
 
 
 def run_generate(model, golden, vc_golden, w, steps=4, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)
-    return generate(model, "cuda:0", (3, 8, 12, 16), steps, te, ne, POS, torch.arange(7), torch.arange(4), w, 5.0, FLASH,
-                    noise=golden["gen.noise"], **kw)
-
-
-class Wrapped(torch.nn.Module):   # any non-DiffusionTransformer3D callable takes the per-step path of generate
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond = m, m.visual_cond
-
-    def forward(self, *a, **k):
-        return self.m(*a, **k)
+    return kit.run_generate(model, golden, w, steps=steps, shape=(3, 8, 12, 16), pos=POS, **kw)
 
 
 def conditioned_oracle(sd, cfg, noise, steps, w, s, te, ne, pos, vc, mask, mode, attention=None):

@@ -11,6 +11,7 @@ Kernel bounds (written down before the kernel ran):
   RGB  never more than one code from the float64 value, and equal wherever float64 +- the dot-product bound
        (C + 2) 2^-24 127.5 (|b_j| + sum_k |W_kj| |x0_k|) rounds to one code."""
 import ctypes as C
+import functools
 import json
 import os
 from types import SimpleNamespace as NS
@@ -21,17 +22,13 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+import kit  # noqa: E402
+from kit import (GOLDEN, K5_ERR_ARG, K5_ERR_STATE, K5_ERR_UNSUPPORTED, POS, cfg,  # noqa: E402
+                 edit_mask, f32, flash_conf, make_dit, need_gpu, prompts, source_latent, Wrapped)
+
+FLASH = flash_conf()
 BF = torch.bfloat16
 SHAPE = (3, 8, 12, 16)
-K5_ERR_ARG, K5_ERR_STATE, K5_ERR_UNSUPPORTED = 1, 4, 6
-
-
-def f32(x):
-    return float(np.float32(x))
 
 
 def factors(Cc=16, seed=5, scale=1.0):
@@ -184,63 +181,15 @@ def test_x0_preview_refuses_other_channel_counts(Cc):
 
 
 # ------------------------------------------------------------------------------------------ engine
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
-
-
-def make_dit(cfg, sd, **over):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**dict(cfg, **over))
-    d.load_state_dict(sd, assign=True)
-    return d.to("cuda:0")
 
 
 @pytest.fixture(scope="module")
 def tiny_dit(cfg, tiny_sd):
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    d = make_dit(cfg, tiny_sd)
-    d.engine("cuda:0")
-    return d
+    need_gpu()
+    return make_dit(cfg, tiny_sd, engine=True)
 
 
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
-
-
-def edit_mask(shape=SHAPE):
-    """frame 0 and the left half of the other frames kept, then a band of 0.25, the rest free (as tests/test_gpu_edit.py)"""
-    T, H, W, _ = shape
-    m = torch.zeros(T, H, W, 1)
-    m[0] = 1.0
-    m[1:, :, :W // 2] = 1.0
-    m[1:, :, W // 2:W // 2 + 2] = 0.25
-    return m
-
-
-def source_latent(shape=SHAPE, seed=77):
-    return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def run_generate(model, golden, w, steps=4, shape=SHAPE, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)
-    kw.setdefault("noise", golden["gen.noise"])
-    return generate(model, "cuda:0", shape, steps, te, ne, POS, torch.arange(7), torch.arange(4), w, 5.0, FLASH, **kw)
-
-
-class Wrapped(torch.nn.Module):   # any non-DiffusionTransformer3D callable takes the per-step path of generate
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond = m, m.visual_cond
-
-    def forward(self, *a, **k):
-        return self.m(*a, **k)
+run_generate = functools.partial(kit.run_generate, steps=4, shape=SHAPE, pos=POS)
 
 
 class Recorder:

@@ -6,7 +6,6 @@ Tolerances are those of tests/test_gpu_edit.py (tests/test_gpu_dit.py, tests/tes
 Everything that claims "the same computation" is asserted bit for bit."""
 import json
 import os
-from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
@@ -15,22 +14,11 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import k5_oracle as O  # noqa: E402
+import kit  # noqa: E402
+from kit import BF, GOLDEN, cfg, f32, make_dit, prompts, rel, tiny_dit, Wrapped  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-FLASH = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
-BF = torch.bfloat16
 HW = (8, 12, 16)
 PLANS = {"t5": (5, 3, 1), "t6": (6, 3, 1), "t7": (7, 3, 2)}     # single / double coverage; ragged overlaps of 2 and 1; three-fold
-
-
-def rel(a, b):
-    a, b = a.float().cpu(), b.float().cpu()
-    return ((a - b).norm() / b.norm()).item()
-
-
-def f32(x):
-    return float(np.float32(x))
 
 
 def pos_for(F):
@@ -41,33 +29,6 @@ def pos_for(F):
 def win_golden():
     from safetensors.torch import load_file
     return dict(load_file(os.path.join(GOLDEN, "dit_tiny_windows.safetensors"))), json.load(open(os.path.join(GOLDEN, "dit_tiny_windows_meta.json")))
-
-
-@pytest.fixture(scope="module")
-def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return c
-
-
-def make_dit(cfg, sd, **over):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    d = DiffusionTransformer3D(**dict(cfg, **over))
-    d.load_state_dict(sd, assign=True)
-    return d.to("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def tiny_dit(cfg, tiny_sd):
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a real MI355X")
-    return make_dit(cfg, tiny_sd)
-
-
-def prompts(golden):
-    te = {"text_embeds": golden["fwd.text"].cuda(), "pooled_embed": golden["fwd.pooled"].cuda()}
-    ne = {"text_embeds": golden["gen.null_text"].cuda(), "pooled_embed": golden["gen.null_pooled"].cuda()}
-    return te, ne
 
 
 def other_prompt(golden, L=5):
@@ -85,24 +46,12 @@ def noise_of(tag, win_golden):
 
 
 def run_generate(model, golden, noise, w, steps=4, pos=None, **kw):
-    from kandinsky.generation_utils import generate
-    te, ne = prompts(golden)
-    return generate(model, "cuda:0", tuple(noise.shape), steps, te, ne, pos or pos_for(3), torch.arange(7), torch.arange(4), w, 5.0, FLASH,
-                    noise=noise, **kw)
+    return kit.run_generate(model, golden, w, steps=steps, shape=tuple(noise.shape), pos=pos or pos_for(3), noise=noise, **kw)
 
 
 def run_windows(model, golden, win_golden, tag, w, **kw):
     T, F, o = PLANS[tag]
     return run_generate(model, golden, noise_of(tag, win_golden), w, context_frames=F, context_overlap=o, **kw)
-
-
-class Wrapped(torch.nn.Module):   # any non-DiffusionTransformer3D callable takes the per-step path of generate
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond = m, m.visual_cond
-
-    def forward(self, *a, **k):
-        return self.m(*a, **k)
 
 
 # ------------------------------------------------------------------------------------------ kernel

@@ -3,51 +3,29 @@ coefficient rule from five sums against the published tensor forms, the bf16 ora
 needs no GPU (set_guidance, generate, the pipeline, the CLI, the library entries), that the defaults change nothing, and header / binding /
 library agreement on the new entries."""
 import ctypes as C
+import functools
 import json
 import os
-import re
-import sys
 from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+import kit  # noqa: E402
+from kit import GOLDEN, PKG, POS, assert_abi_entries, built_lib, flash_conf, host_tiny  # noqa: E402
+
+CONF = flash_conf()
 SHAPE = (3, 8, 12, 16)
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
 
 import guidance_reference as R  # noqa: E402
 from kandinsky.generation_utils import edit_first_step, guidance_plan, sigma_schedule  # noqa: E402
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
+prompt = functools.partial(kit.host_prompt, dims=(96, 48))
 
 
-def tiny(golden_meta):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return DiffusionTransformer3D(**c)
-
-
-def prompt(n, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 96, generator=g), "pooled_embed": torch.randn(1, 48, generator=g)}
-
-
-def call_generate(model, w=5.0, steps=4, **kw):
-    from kandinsky.generation_utils import generate
-    return generate(model, "cpu", SHAPE, steps, prompt(7), prompt(4, 1), POS, torch.arange(7), torch.arange(4), w, 5.0, CONF,
-                    noise=torch.zeros(SHAPE), **kw)
+call_generate = functools.partial(kit.call_generate, w=5.0, steps=4, shape=SHAPE, pos=POS, conf=CONF, prompt=prompt)
 
 
 # ------------------------------------------------------------------------------------------ guidance_plan
@@ -83,7 +61,7 @@ def test_plan_interval_edges():
 
 def test_plan_is_cut_with_the_schedule_under_strength(golden_meta):
     """strength < 1 runs the tail of the schedule: the plan is the full run's, cut at the same step"""
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen = []
     m.sample = lambda img, sigmas, *a, **k: seen.append((list(sigmas), m._guidance))
     sched = [5.0, 4.0, 3.0, 2.0, 1.5, 1.0, 2.5, 3.5]
@@ -178,14 +156,14 @@ BAD = [dict(weights=[]), dict(weights=[5.0, float("nan")]), dict(weights="abc"),
 
 @pytest.mark.parametrize("bad", BAD)
 def test_set_guidance_refuses_bad_numbers(golden_meta, bad):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     with pytest.raises(ValueError, match="guidance"):
         m.set_guidance(**bad)
     assert m._guidance is None and m.guidance_state() == (False, 0, 0, 0)
 
 
 def test_set_guidance_is_remembered_until_the_engine_exists(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     assert m.set_guidance([5, 4, 1], zero_star=1, zero_init_steps=1, rescale=0.5) is m
     assert m._guidance == ([5.0, 4.0, 1.0], True, 1, 0.5)
     assert m.set_guidance()._guidance == (None, False, 0, 0.0)
@@ -193,7 +171,7 @@ def test_set_guidance_is_remembered_until_the_engine_exists(golden_meta):
 
 
 def test_generate_with_the_defaults_passes_nothing_to_the_model(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen = []
     m.sample = lambda img, *a, **k: seen.append(m._guidance)
     m.set_guidance = m.clear_guidance = lambda *a, **k: pytest.fail("the defaults must not touch the model")
@@ -203,7 +181,7 @@ def test_generate_with_the_defaults_passes_nothing_to_the_model(golden_meta):
 
 
 def test_generate_sets_the_plan_for_the_call_and_clears_it_also_on_an_exception(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen = []
 
     def sample(img, *a, **k):
@@ -225,17 +203,11 @@ def test_generate_sets_the_plan_for_the_call_and_clears_it_also_on_an_exception(
     assert seen[3][0] == guidance_plan(sigma_schedule(4, 5.0).tolist(), 5.0, None, (0.0, 0.9)) and seen[3][1:] == (False, 0, 0.0)
 
 
-class Wrapped(torch.nn.Module):
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond = m, m.visual_cond
-
-    def forward(self, *a, **k):
-        pytest.fail("refused calls must not run the model")
+Wrapped = functools.partial(kit.Wrapped, refuse=True)
 
 
 def test_generate_refusals(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     m.sample = lambda *a, **k: pytest.fail("refused calls must not sample")
     for model in (m, Wrapped(m)):
         for kw, word in ((dict(guidance_schedule=[5.0] * 3), "4 steps"), (dict(cfg_rescale=1.5), "rescale"), (dict(cfg_zero_init=-1), "zero_init"),
@@ -267,7 +239,7 @@ def test_generate_refusals(golden_meta):
 def test_generate_sample_and_pipeline_keywords(golden_meta, monkeypatch):
     from kandinsky import generation_utils as G
     from kandinsky import t2v_pipeline as P
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     for kw in (dict(cfg_rescale=2.0), dict(cfg_zero_init=-2), dict(guidance_schedule=[1.0, float("inf")]), dict(guidance_interval=(1.0, 0.0))):
         with pytest.raises(ValueError, match="guidance"):
             G.generate_sample((1, 3, 8, 12, 16), "a", m, None, CONF, None, **kw)
@@ -342,24 +314,13 @@ NEW = ("k5_guidance_stats_blocks", "k5_guidance_coeffs_bf16", "k5_guided_euler",
 
 def test_header_binding_and_library_agree_on_the_new_entries(built_lib):
     from kandinsky import _engine as E
-    hdr = open(os.path.join(ROOT, "include", "k5.h")).read()
-    assert int(re.search(r"#define K5_ABI_VERSION (\d+)", hdr).group(1)) == 11 == E.ABI_VERSION
-    lib = C.CDLL(built_lib)
-    assert lib.k5_abi_version() == 11
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in NEW:
-        decl = re.search(r"\b%s\s*\((.*?)\);" % name, code, flags=re.S)
-        assert decl, name
-        assert name in E.SYMBOLS and hasattr(lib, name)
-        assert len(decl.group(1).split(",")) == len(E.SYMBOLS[name][1]), name
-    fields = re.search(r"typedef struct k5_guidance \{(.*?)\} k5_guidance;", code, flags=re.S).group(1)
-    assert [f.strip().split()[-1].lstrip("*") for f in fields.replace(";", ",").split(",") if f.strip()] == [n for n, _ in E.Guidance._fields_]
+    assert_abi_entries(built_lib, NEW, [("k5_guidance", E.Guidance)])
 
 
 def test_entries_refuse_bad_arguments_without_a_gpu(built_lib, golden_meta):
     from kandinsky import _engine as E
     L = E.lib()
-    h = tiny(golden_meta)._create_handle()           # a handle is host memory until weights arrive
+    h = host_tiny(golden_meta)._create_handle()           # a handle is host memory until weights arrive
     try:
         w = (C.c_float * 3)(5.0, 4.0, 1.0)
         wp = C.cast(w, C.POINTER(C.c_float))

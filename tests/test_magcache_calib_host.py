@@ -12,9 +12,7 @@ import pytest
 import torch
 
 from oracle import k5_oracle as O
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
+from kit import GOLDEN, POS, tiny_config  # noqa: E402
 
 
 class RecordingCache(list):
@@ -98,9 +96,7 @@ def case_inputs(golden, case):
 
 @pytest.fixture(scope="module")
 def ocfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return O.DitConfig(**c)
+    return O.DitConfig(**tiny_config(golden_meta))
 
 
 @pytest.fixture(scope="module")

@@ -2,47 +2,26 @@
 the CLI, the library entries), that `nag_scale=None` changes nothing, that `generate` removes the guidance it set also when the run raises,
 header / binding / library agreement on the new entries, and the identities of the float64 definition the GPU tests compare against."""
 import ctypes as C
+import functools
 import os
-import re
-import sys
 from types import SimpleNamespace as NS
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+import kit  # noqa: E402
+from kit import PKG, POS, assert_abi_entries, built_lib, flash_conf, host_tiny  # noqa: E402
+
+CONF = flash_conf()
 SHAPE = (3, 8, 12, 16)
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
 
 from nag_reference import nag_inputs, nag_reference  # noqa: E402
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
+prompt = functools.partial(kit.host_prompt, dims=(96, 48))
 
 
-def tiny(golden_meta):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return DiffusionTransformer3D(**c)
-
-
-def prompt(n, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 96, generator=g), "pooled_embed": torch.randn(1, 48, generator=g)}
-
-
-def call_generate(model, **kw):
-    from kandinsky.generation_utils import generate
-    return generate(model, "cpu", SHAPE, 4, prompt(7), prompt(4, 1), POS, torch.arange(7), torch.arange(4), 1.0, 5.0, CONF,
-                    noise=torch.zeros(SHAPE), **kw)
+call_generate = functools.partial(kit.call_generate, w=1.0, steps=4, shape=SHAPE, pos=POS, conf=CONF, prompt=prompt)
 
 
 # ------------------------------------------------------------------------------------------ the float64 definition
@@ -78,14 +57,14 @@ BAD = [dict(scale=0.5), dict(tau=0.9), dict(alpha=-0.1), dict(alpha=1.5), dict(s
 
 @pytest.mark.parametrize("bad", BAD)
 def test_set_nag_refuses_bad_numbers(golden_meta, bad):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     with pytest.raises(ValueError, match="nag"):
         m.set_nag(prompt(4), torch.arange(4), **bad)
     assert m._nag is None
 
 
 def test_set_nag_refuses_bad_prompts(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     for te, pos in ((None, torch.arange(4)), ({"pooled_embed": torch.zeros(1, 48)}, torch.arange(4)), (prompt(4), torch.arange(3)),
                     (prompt(4), None), ({"text_embeds": torch.zeros(0, 96)}, []), ({"text_embeds": torch.zeros(4, 80)}, torch.arange(4)),
                     ({"text_embeds": torch.zeros(96)}, [0])):
@@ -95,7 +74,7 @@ def test_set_nag_refuses_bad_prompts(golden_meta):
 
 
 def test_set_nag_is_remembered_until_the_engine_exists(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     ne = prompt(4)
     assert m.set_nag(ne, torch.arange(4)) is m
     assert m._nag["args"] == (5.0, 2.5, 0.25) and m._nag["text"] is ne["text_embeds"]       # the model keeps the tensors alive
@@ -104,7 +83,7 @@ def test_set_nag_is_remembered_until_the_engine_exists(golden_meta):
 
 
 def test_generate_without_nag_scale_passes_nothing_to_the_model(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen = []
     m.sample = lambda img, *a, **k: seen.append(m._nag)
     m.set_nag = m.clear_nag = lambda *a, **k: pytest.fail("nag_scale=None must not touch the model")
@@ -114,7 +93,7 @@ def test_generate_without_nag_scale_passes_nothing_to_the_model(golden_meta):
 
 
 def test_generate_sets_nag_for_the_call_and_clears_it_also_on_an_exception(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     ne = prompt(4, 3)
     seen = []
 
@@ -139,7 +118,7 @@ def test_generate_sets_nag_for_the_call_and_clears_it_also_on_an_exception(golde
 
 
 def test_generate_refusals(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     m.sample = lambda *a, **k: pytest.fail("refused calls must not sample")
     ne = prompt(4)
     for kw in (dict(nag_scale=0.5), dict(nag_scale=5.0, nag_tau=0.5), dict(nag_scale=5.0, nag_alpha=2.0)):
@@ -152,19 +131,13 @@ def test_generate_refusals(golden_meta):
     assert m._nag is None
 
 
-class Wrapped(torch.nn.Module):
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond = m, m.visual_cond
-
-    def forward(self, *a, **k):
-        pytest.fail("refused calls must not run the model")
+Wrapped = functools.partial(kit.Wrapped, refuse=True)
 
 
 def test_a_model_without_the_engine_raises(golden_meta):
     kw = dict(nag_text_embeds=prompt(4), nag_text_rope_pos=torch.arange(4), nag_scale=5.0)
     with pytest.raises(ValueError, match="engine"):
-        call_generate(Wrapped(tiny(golden_meta)), **kw)
+        call_generate(Wrapped(host_tiny(golden_meta)), **kw)
     with pytest.raises(ValueError, match="engine"):
         call_generate(NS(visual_cond=True), **kw)
     from kandinsky.generation_utils import generate_sample
@@ -174,7 +147,7 @@ def test_a_model_without_the_engine_raises(golden_meta):
 
 def test_generate_sample_refusals_and_the_negative_caption(golden_meta, monkeypatch):
     from kandinsky import generation_utils as G
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     for kw in (dict(nag_scale=0.0), dict(nag_scale=5.0, nag_tau=0.0), dict(nag_scale=5.0, nag_alpha=-1.0)):
         with pytest.raises(ValueError, match="nag"):
             G.generate_sample((1, 3, 8, 12, 16), "a", m, None, CONF, None, **kw)
@@ -249,23 +222,13 @@ NEW = ("k5_nag_combine_bf16", "k5_dit_set_nag", "k5_dit_nag_state")
 
 
 def test_header_binding_and_library_agree_on_the_new_entries(built_lib):
-    from kandinsky import _engine as E
-    hdr = open(os.path.join(ROOT, "include", "k5.h")).read()
-    assert int(re.search(r"#define K5_ABI_VERSION (\d+)", hdr).group(1)) == 11 == E.ABI_VERSION
-    lib = C.CDLL(built_lib)
-    assert lib.k5_abi_version() == 11
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in NEW:
-        decl = re.search(r"\b%s\s*\((.*?)\);" % name, code, flags=re.S)
-        assert decl, name
-        assert name in E.SYMBOLS and hasattr(lib, name)
-        assert len(decl.group(1).split(",")) == len(E.SYMBOLS[name][1]), name
+    assert_abi_entries(built_lib, NEW)
 
 
 def test_entries_refuse_bad_arguments_without_a_gpu(built_lib, golden_meta):
     from kandinsky import _engine as E
     L = E.lib()
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     h = m._create_handle()           # a handle is host memory until weights arrive
     try:
         pos = (C.c_int32 * 4)(0, 1, 2, 3)

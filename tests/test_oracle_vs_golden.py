@@ -9,16 +9,14 @@ import pytest
 import torch
 
 from oracle import k5_oracle as O
+from kit import tiny_config
 
 TOL = dict(atol=2e-5, rtol=2e-5)
 
 
 @pytest.fixture(scope="module")
 def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"] = tuple(c["patch_size"])
-    c["axes_dims"] = tuple(c["axes_dims"])
-    return O.DitConfig(**c)
+    return O.DitConfig(**tiny_config(golden_meta))
 
 
 def close(a, b, **kw):

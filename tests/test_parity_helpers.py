@@ -16,8 +16,8 @@ import torch
 
 from oracle import k5_oracle as O
 from oracle import parity as P
+from kit import bfr  # noqa: E402
 
-BF = torch.bfloat16
 HERE = os.path.dirname(os.path.abspath(__file__))
 SHAPES = [(72, 72), (300, 77), (513, 7), (1000, 1000), (64, 640), (10, 4096)]
 DEFECT_KEYS = [77, 1000, 4096]
@@ -25,10 +25,6 @@ DEFECT_KEYS = [77, 1000, 4096]
 
 def rnd(*shape, seed=0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed))
-
-
-def bfr(x):
-    return x.to(BF).float()
 
 
 def kernel_model(q, k, v, *, keep=None, twice=0, scale=0.125, pad_keys=0):

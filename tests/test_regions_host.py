@@ -2,47 +2,26 @@
 against a loop, that `generate` sets the regions for exactly one call (and not at all by default), the CLI flags, header / binding / library
 agreement on the new entries, and every refusal of the library entries that needs no GPU."""
 import ctypes as C
+import functools
 import os
-import re
-import sys
 from types import SimpleNamespace as NS
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+import kit  # noqa: E402
+from kit import PKG, POS, assert_abi_entries, built_lib, flash_conf, host_tiny  # noqa: E402
+
+CONF = flash_conf()
 SHAPE = (3, 8, 12, 16)
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
 
 from regions_reference import combine_inputs, combine_reference, mask_cases, nabla_perm, token_weights_reference  # noqa: E402
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
+prompt = functools.partial(kit.host_prompt, dims=(96, 48))
 
 
-def tiny(golden_meta):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return DiffusionTransformer3D(**c)
-
-
-def prompt(n, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 96, generator=g), "pooled_embed": torch.randn(1, 48, generator=g)}
-
-
-def call_generate(model, **kw):
-    from kandinsky.generation_utils import generate
-    return generate(model, "cpu", SHAPE, 4, prompt(7), prompt(4, 1), POS, torch.arange(7), torch.arange(4), 1.0, 5.0, CONF,
-                    noise=torch.zeros(SHAPE), **kw)
+call_generate = functools.partial(kit.call_generate, w=1.0, steps=4, shape=SHAPE, pos=POS, conf=CONF, prompt=prompt)
 
 
 def region_kw(R=2, bw=0.25):
@@ -130,7 +109,7 @@ def test_region_masks_to_latent_against_a_loop():
 
 # ------------------------------------------------------------------------------------------ set_regions / generate
 def test_set_regions_refusals(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     ok = region_kw()
     te, pos, masks = ok["region_text_embeds"], ok["region_text_rope_pos"], ok["region_masks"]
     for args in ((te, pos, masks, -0.1), (te, pos, masks, 1.5), (te, pos, masks, float("nan")), (te, pos, masks, "x"),
@@ -144,7 +123,7 @@ def test_set_regions_refusals(golden_meta):
 
 
 def test_set_regions_is_remembered_until_the_engine_exists(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     kw = region_kw()
     assert m.set_regions(kw["region_text_embeds"], kw["region_text_rope_pos"], kw["region_masks"]) is m
     assert m._regions["base_weight"] == 0.0 and m._regions["text"][1] is kw["region_text_embeds"][1]["text_embeds"]   # the model keeps the tensors
@@ -153,7 +132,7 @@ def test_set_regions_is_remembered_until_the_engine_exists(golden_meta):
 
 
 def test_generate_by_default_passes_nothing_to_the_model(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen = []
     m.sample = lambda img, *a, **k: seen.append(m._regions)
     m.set_regions = m.clear_regions = lambda *a, **k: pytest.fail("without region_text_embeds the model must not be touched")
@@ -163,7 +142,7 @@ def test_generate_by_default_passes_nothing_to_the_model(golden_meta):
 
 
 def test_generate_sets_the_regions_for_the_call_and_clears_them_also_on_an_exception(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen = []
 
     def sample(img, *a, **k):
@@ -193,7 +172,7 @@ def test_generate_sets_the_regions_for_the_call_and_clears_them_also_on_an_excep
 
 
 def test_generate_refusals(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     m.sample = lambda *a, **k: pytest.fail("refused calls must not sample")
     kw = region_kw()
     for bad in (dict(region_base_weight=2.0), dict(region_masks=None), dict(region_text_rope_pos=None), dict(region_masks=kw["region_masks"][:1])):
@@ -220,7 +199,7 @@ def test_generate_refusals(golden_meta):
 
 def test_generate_sample_encodes_region_prompts_with_the_caption(golden_meta, monkeypatch):
     from kandinsky import generation_utils as G
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen, calls = {}, []
 
     class Embedder:
@@ -309,23 +288,13 @@ NEW = ("k5_region_combine_bf16", "k5_region_weights_f32", "k5_dit_set_regions", 
 
 
 def test_header_binding_and_library_agree_on_the_new_entries(built_lib):
-    from kandinsky import _engine as E
-    hdr = open(os.path.join(ROOT, "include", "k5.h")).read()
-    assert int(re.search(r"#define K5_ABI_VERSION (\d+)", hdr).group(1)) == 11 == E.ABI_VERSION
-    lib = C.CDLL(built_lib)
-    assert lib.k5_abi_version() == 11
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in NEW:
-        decl = re.search(r"\b%s\s*\((.*?)\);" % name, code, flags=re.S)
-        assert decl, name
-        assert name in E.SYMBOLS and hasattr(lib, name)
-        assert len(decl.group(1).split(",")) == len(E.SYMBOLS[name][1]), name
+    assert_abi_entries(built_lib, NEW)
 
 
 def test_entries_refuse_bad_arguments_without_a_gpu(built_lib, golden_meta):
     from kandinsky import _engine as E
     L = E.lib()
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     h = m._create_handle()           # a handle is host memory until weights arrive
     try:
         pos = (C.c_int32 * 4)(0, 1, 2, 3)

@@ -1,18 +1,19 @@
 """CPU-only checks of `generate`'s per-step loop on a duck-typed model: the CFG-parallel exchange (one forward per step on this side, the
 pair's velocities through `exchange_velocity`) against the plain two-forward run, and what a batch off the many-sample path hands to the
 callback, the progress bar and the per-sample checks."""
-import os
+import functools
 import sys
 import types
-from types import SimpleNamespace as NS
 
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kit  # noqa: E402
+from kit import flash_conf  # noqa: E402
+
 import euler_step_reference as ER  # noqa: E402
 
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+CONF = flash_conf()
 SHAPE, STEPS = (3, 4, 6, 16), 3
 
 
@@ -30,9 +31,7 @@ class FakeDit:
         return (0.5 * x + text_embed.mean() + pooled.mean() * float(t.reshape(-1)[0]) / 1000).to(torch.bfloat16)
 
 
-def prompt(n, seed):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 8, generator=g), "pooled_embed": torch.randn(1, 4, generator=g)}
+prompt = functools.partial(kit.host_prompt, dims=(8, 4))
 
 
 @pytest.fixture()

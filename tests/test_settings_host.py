@@ -4,19 +4,16 @@ status, the handle is a stand-in.  set / clear / state, the re-install after a r
 `setting_for_call`, and what a refused install leaves behind."""
 import contextlib
 import ctypes as C
-import os
-import sys
-from types import SimpleNamespace as NS
+import functools
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+import kit  # noqa: E402
+from kit import K5_ERR_ARG, POS, flash_conf, host_tiny  # noqa: E402
+
+CONF = flash_conf()
 SHAPE = (3, 8, 12, 16)
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
-K5_ERR_ARG = 1
 SETTERS = ["k5_dit_set_watch", "k5_dit_set_nag", "k5_dit_set_regions", "k5_dit_set_guidance", "k5_dit_set_skip_guidance"]   # the re-install order
 ATTRS = ["_watch", "_nag", "_regions", "_guidance", "_skip"]
 
@@ -51,16 +48,13 @@ class Recorder:
 @pytest.fixture
 def rig(monkeypatch, golden_meta):
     from kandinsky import _engine as E
-    from kandinsky.models.dit import DiffusionTransformer3D
     rec = Recorder()
     monkeypatch.setattr(E, "lib", lambda: rec)
     monkeypatch.setattr(torch.cuda, "device", contextlib.nullcontext)   # torch.cuda.device(...) raises without a GPU
     made = []
 
     def make(handle=True):
-        c = dict(golden_meta["tiny_config"])
-        c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-        m = DiffusionTransformer3D(**c)
+        m = host_tiny(golden_meta)
         if handle:
             m._handle, m._handle_device = C.c_void_p(0x5e77), torch.device("cpu")
         made.append(m)
@@ -71,9 +65,7 @@ def rig(monkeypatch, golden_meta):
         m._handle = None
 
 
-def prompt(n, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 96, generator=g), "pooled_embed": torch.randn(1, 48, generator=g)}
+prompt = functools.partial(kit.host_prompt, dims=(96, 48))
 
 
 def half_mask(R=1):
@@ -93,10 +85,7 @@ def set_all(m, seed=0):
     return cb
 
 
-def call_generate(model, steps=3, **kw):
-    from kandinsky.generation_utils import generate
-    return generate(model, "cpu", SHAPE, steps, prompt(7), prompt(4, 1), POS, torch.arange(7), torch.arange(4), 5.0, 5.0, CONF,
-                    noise=torch.zeros(SHAPE), **kw)
+call_generate = functools.partial(kit.call_generate, w=5.0, steps=3, shape=SHAPE, pos=POS, conf=CONF, prompt=prompt)
 
 
 def per_call_keywords(seed=10):

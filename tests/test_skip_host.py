@@ -2,34 +2,24 @@
 reference's golden, the host surface (`set_skip_guidance`, `generate`, `generate_sample`, the pipeline, the CLI) with every refusal before a
 model runs, and the new entries of the C ABI: header, binding and library agree, and they refuse bad arguments without a device."""
 import ctypes as C
+import functools
 import json
 import os
-import re
-import sys
 from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+import kit  # noqa: E402
+from kit import GOLDEN, PKG, POS, assert_abi_entries, built_lib, flash_conf  # noqa: E402
+
+CONF = flash_conf()
 SHAPE = (3, 8, 12, 16)
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
 
 import skip_reference as S  # noqa: E402
 from kandinsky.generation_utils import edit_first_step, sigma_schedule, skip_plan  # noqa: E402
 from oracle import k5_oracle as O  # noqa: E402
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
 
 
 @pytest.fixture(scope="module")
@@ -42,15 +32,10 @@ def tiny4(cfg4):
     return DiffusionTransformer3D(**cfg4)
 
 
-def prompt(n, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 96, generator=g), "pooled_embed": torch.randn(1, 48, generator=g)}
+prompt = functools.partial(kit.host_prompt, dims=(96, 48))
 
 
-def call_generate(model, w=5.0, steps=4, **kw):
-    from kandinsky.generation_utils import generate
-    return generate(model, "cpu", SHAPE, steps, prompt(7), prompt(4, 1), POS, torch.arange(7), torch.arange(4), w, 5.0, CONF,
-                    noise=torch.zeros(SHAPE), **kw)
+call_generate = functools.partial(kit.call_generate, w=5.0, steps=4, shape=SHAPE, pos=POS, conf=CONF, prompt=prompt)
 
 
 # ------------------------------------------------------------------------------------------ skip_plan
@@ -230,13 +215,7 @@ def test_generate_sets_the_skip_set_for_the_call_and_clears_it_also_on_an_except
     assert seen[2] == ([3], 2.0, "block", [1, 1, 1, 1]) and m._skip == ([0], 1.5, "block", None)
 
 
-class Wrapped(torch.nn.Module):
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond, self.num_visual_blocks = m, m.visual_cond, m.num_visual_blocks
-
-    def forward(self, *a, **k):
-        pytest.fail("refused calls must not run the model")
+Wrapped = functools.partial(kit.Wrapped, blocks=True, refuse=True)
 
 
 def test_generate_refusals(cfg4):
@@ -348,17 +327,7 @@ NEW = ("k5_skip_euler", "k5_dit_set_skip_guidance", "k5_dit_skip_state", "k5_dit
 
 def test_header_binding_and_library_agree_on_the_new_entries(built_lib):
     from kandinsky import _engine as E
-    hdr = open(os.path.join(ROOT, "include", "k5.h")).read()
-    assert int(re.search(r"#define K5_ABI_VERSION (\d+)", hdr).group(1)) == 11 == E.ABI_VERSION
-    lib = C.CDLL(built_lib)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in NEW:
-        decl = re.search(r"\b%s\s*\((.*?)\);" % name, code, flags=re.S)
-        assert decl, name
-        assert name in E.SYMBOLS and hasattr(lib, name)
-        assert len(decl.group(1).split(",")) == len(E.SYMBOLS[name][1]), name
-    fields = re.search(r"typedef struct k5_skip_guidance \{(.*?)\} k5_skip_guidance;", code, flags=re.S).group(1)
-    assert [f.strip().split()[-1].lstrip("*") for f in fields.replace(";", ",").split(",") if f.strip()] == [n for n, _ in E.SkipGuidance._fields_]
+    assert_abi_entries(built_lib, NEW, [("k5_skip_guidance", E.SkipGuidance)])
 
 
 def test_entries_refuse_bad_arguments_without_a_gpu(built_lib, cfg4):

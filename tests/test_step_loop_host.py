@@ -11,40 +11,26 @@ skip_reference and stochastic_reference bit for bit.
 The wrapper and the entry: `E.euler_step_` raises before any library call, `k5_euler_step` refuses before any launch, and the header's struct
 and the binding's agree field for field."""
 import ctypes as C
-import os
-import re
-import sys
-from types import SimpleNamespace as NS
+import functools
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import euler_step_reference as ER  # noqa: E402
 import guidance_reference as R  # noqa: E402
 import skip_reference as S  # noqa: E402
 import stochastic_reference as SR  # noqa: E402
 from kandinsky import generation_utils as G  # noqa: E402
+import kit  # noqa: E402
+from kit import BF, assert_abi_entries, built_lib, flash_conf  # noqa: E402
 
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+CONF = flash_conf()
 SHAPE, STEPS, SCALE = (3, 4, 6, 16), 6, 5.0
 POS = [torch.arange(3), torch.arange(2), torch.arange(3)]
-BF = torch.bfloat16
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
-
-
-def prompt(n, seed):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 8, generator=g), "pooled_embed": torch.randn(1, 4, generator=g)}
+prompt = functools.partial(kit.host_prompt, dims=(8, 4))
 
 
 TE, NE = prompt(4, 1), prompt(2, 2)
@@ -203,13 +189,7 @@ def test_the_step_loop_on_the_stand_in_is_the_reference_bf16_loop(stand_ins, cas
 # ------------------------------------------------------------------------------------------ header, binding, entry and wrapper
 def test_header_and_binding_agree_on_the_step_struct(built_lib):
     from kandinsky import _engine as E
-    hdr = open(os.path.join(ROOT, "include", "k5.h")).read()
-    assert int(re.search(r"#define K5_ABI_VERSION (\d+)", hdr).group(1)) == 11 == E.ABI_VERSION
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    decl = re.search(r"\bk5_euler_step\s*\((.*?)\);", code, flags=re.S)
-    assert decl and len(decl.group(1).split(",")) == len(E.SYMBOLS["k5_euler_step"][1]) and hasattr(C.CDLL(built_lib), "k5_euler_step")
-    fields = re.search(r"typedef struct k5_euler_step_args \{(.*?)\} k5_euler_step_args;", code, flags=re.S).group(1)
-    assert [f.strip().split()[-1].lstrip("*") for f in fields.replace(";", ",").split(",") if f.strip()] == [n for n, _ in E.EulerStep._fields_]
+    assert_abi_entries(built_lib, ("k5_euler_step",), [("k5_euler_step_args", E.EulerStep)])
 
 
 def test_the_entry_refuses_bad_arguments_without_a_gpu(built_lib):

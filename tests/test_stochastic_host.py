@@ -3,51 +3,29 @@ against its float64 restatement, the host surface (`set_stochastic`, `generate`,
 ValueError before a model runs, the settings round trip on a model without an engine, and the new entries of the C ABI: header, binding and
 library agree, and they refuse bad arguments without a device."""
 import ctypes as C
+import functools
 import json
 import os
-import re
-import sys
 from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+import kit  # noqa: E402
+from kit import GOLDEN, PKG, POS, assert_abi_entries, built_lib, flash_conf, host_tiny  # noqa: E402
+
+CONF = flash_conf()
 SHAPE = (3, 8, 12, 16)
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
 
 import stochastic_reference as SR  # noqa: E402
 from kandinsky.generation_utils import edit_first_step, sigma_schedule, stochastic_plan  # noqa: E402
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
+prompt = functools.partial(kit.host_prompt, dims=(96, 48))
 
 
-def tiny(golden_meta):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return DiffusionTransformer3D(**c)
-
-
-def prompt(n, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 96, generator=g), "pooled_embed": torch.randn(1, 48, generator=g)}
-
-
-def call_generate(model, w=5.0, steps=4, **kw):
-    from kandinsky.generation_utils import generate
-    return generate(model, "cpu", SHAPE, steps, prompt(7), prompt(4, 1), POS, torch.arange(7), torch.arange(4), w, 5.0, CONF,
-                    noise=torch.zeros(SHAPE), **kw)
+call_generate = functools.partial(kit.call_generate, w=5.0, steps=4, shape=SHAPE, pos=POS, conf=CONF, prompt=prompt)
 
 
 # ------------------------------------------------------------------------------------------ the generator's restatement
@@ -139,7 +117,7 @@ def test_plan_refuses_bad_numbers():
 
 
 def test_plan_is_cut_with_the_schedule_under_strength(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen = []
     m.sample = lambda img, *a, **k: seen.append(m._stochastic)
     assert edit_first_step(6, 0.5) == 3
@@ -177,7 +155,7 @@ def test_loops_without_noise_are_the_plain_loops():
 # ------------------------------------------------------------------------------------------ the host surface
 def test_set_stochastic_checks_and_round_trip_without_an_engine(golden_meta):
     from kandinsky.models.dit import _SETTINGS, check_stochastic_args
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     assert "stochastic" in _SETTINGS and _SETTINGS["stochastic"][:2] == ("_stochastic", "k5_dit_set_stochastic")
     assert m.stochastic_state() == (False, 0)
     m.set_stochastic([-0.1, -0.2], [0.5, 1], [0.25, 0], seed=2 ** 64 + 5, first_stream=3)
@@ -209,7 +187,7 @@ def test_set_stochastic_checks_and_round_trip_without_an_engine(golden_meta):
 
 
 def test_generate_with_the_defaults_passes_nothing_to_the_model(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen = []
     m.sample = lambda img, *a, **k: seen.append(m._stochastic)
     m.set_stochastic = m.clear_stochastic = lambda *a, **k: pytest.fail("the defaults must not touch the model")
@@ -222,7 +200,7 @@ def test_generate_with_the_defaults_passes_nothing_to_the_model(golden_meta):
 
 
 def test_generate_sets_the_plan_for_the_call_and_clears_it_also_on_an_exception(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen = []
 
     def sample(img, *a, **k):
@@ -244,7 +222,7 @@ def test_generate_sets_the_plan_for_the_call_and_clears_it_also_on_an_exception(
 
 def test_a_batch_runs_one_sample_at_a_time_with_a_seed_each(golden_meta):
     from kandinsky.generation_utils import generate
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     seen = []
     m.sample = lambda img, *a, **k: seen.append(m._stochastic[3])
     m.sample_many = lambda *a, **k: pytest.fail("one plan holds one seed: the batch must not go through sample_many")
@@ -254,17 +232,11 @@ def test_a_batch_runs_one_sample_at_a_time_with_a_seed_each(golden_meta):
     assert seen == [2 ** 64 - 1, 0, 1]
 
 
-class Wrapped(torch.nn.Module):
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond, self.num_visual_blocks = m, m.visual_cond, m.num_visual_blocks
-
-    def forward(self, *a, **k):
-        pytest.fail("refused calls must not run the model")
+Wrapped = functools.partial(kit.Wrapped, blocks=True, refuse=True)
 
 
 def test_generate_refusals(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     m.sample = lambda *a, **k: pytest.fail("refused calls must not sample")
     W, b = torch.zeros(16, 3), torch.zeros(3)
     for model in (m, Wrapped(m)):
@@ -290,7 +262,7 @@ def test_generate_refusals(golden_meta):
 def test_generate_sample_and_pipeline_keywords(golden_meta, monkeypatch):
     from kandinsky import generation_utils as G
     from kandinsky import t2v_pipeline as P
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     for kw, word in ((dict(eta=2.0), "eta"), (dict(eta=1.0, s_noise=-3.0), "s_noise"), (dict(eta=1.0, sde_interval=(1.0, 0.0)), "sde_interval"),
                      (dict(eta=1.0, context_frames=2, context_overlap=1), "context windows"), (dict(eta=1.0, preview_every=2), "preview")):
         with pytest.raises(ValueError, match=word):
@@ -364,18 +336,7 @@ NEW = ("k5_philox_words", "k5_noise_normal_f32", "k5_stochastic_euler", "k5_dit_
 
 def test_header_binding_and_library_agree_on_the_new_entries(built_lib):
     from kandinsky import _engine as E
-    hdr = open(os.path.join(ROOT, "include", "k5.h")).read()
-    assert int(re.search(r"#define K5_ABI_VERSION (\d+)", hdr).group(1)) == 11 == E.ABI_VERSION
-    lib = C.CDLL(built_lib)
-    assert lib.k5_abi_version() == 11
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in NEW:
-        decl = re.search(r"\b%s\s*\((.*?)\);" % name, code, flags=re.S)
-        assert decl, name
-        assert name in E.SYMBOLS and hasattr(lib, name)
-        assert len(decl.group(1).split(",")) == len(E.SYMBOLS[name][1]), name
-    fields = re.search(r"typedef struct k5_stochastic \{(.*?)\} k5_stochastic;", code, flags=re.S).group(1)
-    assert [f.strip().split()[-1].lstrip("*") for f in fields.replace(";", ",").split(",") if f.strip()] == [n for n, _ in E.Stochastic._fields_]
+    assert_abi_entries(built_lib, NEW, [("k5_stochastic", E.Stochastic)])
 
 
 def test_entries_refuse_bad_arguments_without_a_gpu(built_lib, golden_meta):
@@ -385,7 +346,7 @@ def test_entries_refuse_bad_arguments_without_a_gpu(built_lib, golden_meta):
     good = lambda: E.Stochastic(2, fl(-0.5, -0.5), fl(0.5, 1.0), fl(0.7, 0.0), 9, 0)   # noqa: E731
     assert L.k5_dit_set_stochastic(None, C.byref(good())) == 1 and "null handle" in E.last_error()      # a NULL handle, without a GPU
     assert L.k5_dit_stochastic_state(None, None, None, 0) == 1 and "null handle" in E.last_error()
-    h = tiny(golden_meta)._create_handle()           # a handle is host memory until weights arrive
+    h = host_tiny(golden_meta)._create_handle()           # a handle is host memory until weights arrive
     try:
         bad = [(E.Stochastic(0, fl(0.0), fl(1.0), fl(0.0), 1, 0), "num_steps"), (E.Stochastic(2, None, fl(1.0, 1.0), fl(0.0, 0.0), 1, 0), "num_steps"),
                (E.Stochastic(2, fl(-0.5, -0.5), None, fl(0.0, 0.0), 1, 0), "num_steps"), (E.Stochastic(2, fl(-0.5, -0.5), fl(1.0, 1.0), None, 1, 0), "num_steps"),

@@ -2,34 +2,25 @@
 which boxes, in which order), every refusal that needs no GPU, the pipeline's size check and the CLI's keywords, and header / binding / library
 agreement on the new entry points."""
 import ctypes as C
+import functools
 import os
-import re
 import shutil
 import subprocess
-import sys
 from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from tile_kernels_reference import cpu_cfg_euler_tiles, cpu_tile_tables  # noqa: E402
+import kit  # noqa: E402
+from kit import PKG, POS, ROOT, assert_abi_entries, built_lib, flash_conf, host_tiny  # noqa: E402
 
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
+CONF = flash_conf()
 WINDOW = (3, 8, 12)
 ISSUE_CASES = {"s22": ((3, 12, 20), (0, 4, 4), (1, 2, 2), ([0], [0, 4], [0, 8])),
                "s14": ((3, 8, 24), (0, 0, 8), (1, 1, 4), ([0], [0], [0, 4, 8, 12])),
                "t2s2": ((5, 8, 20), (1, 0, 4), (2, 1, 2), ([0, 2], [0], [0, 8]))}
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
 
 
 def shares(plan):
@@ -139,9 +130,7 @@ class FakeDit:
         return (0.5 * x + text_embed.mean() + pooled.mean() * float(t.reshape(-1)[0]) / 1000).to(torch.bfloat16)
 
 
-def prompt(n, seed):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 8, generator=g), "pooled_embed": torch.randn(1, 4, generator=g)}
+prompt = functools.partial(kit.host_prompt, dims=(8, 4))
 
 
 @pytest.fixture()
@@ -237,27 +226,10 @@ def test_context_frames_alone_is_the_3d_plan_with_one_row_and_one_column_window(
 
 # ------------------------------------------------------------------------------------------ refusals
 SHAPE = (3, 12, 20, 16)
-POS = [torch.arange(3), torch.arange(4), torch.arange(6)]
 TILED = dict(context_height=8, context_width=12)
 
 
-def tiny(golden_meta):
-    from kandinsky.models.dit import DiffusionTransformer3D
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return DiffusionTransformer3D(**c)
-
-
-class Wrapped(torch.nn.Module):
-    def __init__(self, m):
-        super().__init__()
-        self.m, self.visual_cond, self.num_visual_blocks = m, m.visual_cond, m.num_visual_blocks
-
-    def forward(self, *a, **k):
-        pytest.fail("refused calls must not run the model")
-
-    def forward_skip(self, *a, **k):
-        pytest.fail("refused calls must not run the model")
+Wrapped = functools.partial(kit.Wrapped, blocks=True, hand_on=("forward_skip",), refuse=True)
 
 
 def big_prompt(n, seed=0):
@@ -265,14 +237,11 @@ def big_prompt(n, seed=0):
     return {"text_embeds": torch.randn(n, 96, generator=g), "pooled_embed": torch.randn(1, 48, generator=g)}
 
 
-def call_generate(model, **kw):
-    from kandinsky.generation_utils import generate
-    return generate(model, "cpu", SHAPE, 4, big_prompt(7), big_prompt(4, 1), POS, torch.arange(7), torch.arange(4), 5.0, 5.0, CONF,
-                    noise=torch.zeros(SHAPE), **kw)
+call_generate = functools.partial(kit.call_generate, w=5.0, steps=4, shape=SHAPE, pos=POS, conf=CONF, prompt=big_prompt)
 
 
 def test_generate_refuses_every_refused_combination_before_the_model_is_touched(golden_meta):
-    m = tiny(golden_meta)
+    m = host_tiny(golden_meta)
     m.sample = lambda *a, **k: pytest.fail("refused calls must not sample")
     src = torch.zeros(SHAPE)
     W, b = torch.zeros(16, 3), torch.zeros(3)
@@ -410,18 +379,8 @@ def test_cli_flags_reach_the_pipeline_keywords():
 # ------------------------------------------------------------------------------------------ ABI
 def test_header_binding_and_library_agree_on_the_new_entries(built_lib):
     from kandinsky import _engine as E
-    hdr = open(os.path.join(ROOT, "include", "k5.h")).read()
-    assert int(re.search(r"#define K5_ABI_VERSION (\d+)", hdr).group(1)) == 11 == E.ABI_VERSION
-    lib = C.CDLL(built_lib)
-    assert lib.k5_abi_version() == 11
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    for name in ("k5_cfg_euler_tiles", "k5_patchify_view_bf16", "k5_sample_tiles"):
-        assert re.search(r"\b%s\s*\(" % name, code), name
-        assert name in E.SYMBOLS and hasattr(lib, name)
-    for struct, binding in (("k5_tile_plan", E.TilePlan), ("k5_sample_tiles_args", E.SampleTilesArgs)):   # the header's fields in the header's order
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), code, flags=re.S).group(1)
-        fields = [re.search(r"(\w+)\s*$", decl.strip()).group(1) for decl in body.replace(",", ";").split(";") if decl.strip()]
-        assert fields == [f[0] for f in binding._fields_], struct
+    assert_abi_entries(built_lib, ("k5_cfg_euler_tiles", "k5_patchify_view_bf16", "k5_sample_tiles"),
+                       [("k5_tile_plan", E.TilePlan), ("k5_sample_tiles_args", E.SampleTilesArgs)])
 
 
 def test_struct_sizes_match_a_compiled_c_program(tmp_path):

@@ -5,24 +5,13 @@ import ctypes
 import json
 import os
 import re
-import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 from oracle import k5_oracle as O
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
+from kit import GOLDEN, ROOT, built_lib, rel, tiny_config  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -49,13 +38,7 @@ def vc_meta():
 
 @pytest.fixture(scope="module")
 def cfg(golden_meta):
-    c = dict(golden_meta["tiny_config"])
-    c["patch_size"], c["axes_dims"] = tuple(c["patch_size"]), tuple(c["axes_dims"])
-    return O.DitConfig(**c)
-
-
-def rel(a, b):
-    return ((a.float() - b.float()).norm() / b.float().norm()).item()
+    return O.DitConfig(**tiny_config(golden_meta))
 
 
 def conditioned_oracle(sd, cfg, noise, steps, w, s, te, ne, pos, vc, mask, mode, attention=None):

@@ -2,29 +2,20 @@
 `generate` on a duck-typed model (which forwards run, on which slices, in which order), every refusal that needs no GPU, the pipeline's and
 the CLI's keywords, and header / binding / library agreement on the new entry points."""
 import ctypes as C
+import functools
 import os
-import re
-import sys
 from types import SimpleNamespace as NS
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "kandinsky-5_amd")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 import euler_step_reference as ER  # noqa: E402
 from tile_kernels_reference import cpu_cfg_euler_tiles, cpu_tile_tables  # noqa: E402
+import kit  # noqa: E402
+from kit import PKG, assert_abi_entries, built_lib, flash_conf  # noqa: E402
 
-CONF = NS(model=NS(dit_params=NS(patch_size=(1, 2, 2)), attention=NS(type="flash")), metrics=NS(scale_factor=(1.0, 2.0, 2.0)))
-
-
-@pytest.fixture(scope="module")
-def built_lib():
-    sys.path.insert(0, PKG)
-    import build as k5build
-    return k5build.build(verbose=False)
+CONF = flash_conf()
 
 
 # ------------------------------------------------------------------------------------------ plan
@@ -142,9 +133,7 @@ class FakeDit:
         return (0.5 * x + text_embed.mean() + pooled.mean() * float(t.reshape(-1)[0]) / 1000).to(torch.bfloat16)
 
 
-def prompt(n, seed):
-    g = torch.Generator().manual_seed(seed)
-    return {"text_embeds": torch.randn(n, 8, generator=g), "pooled_embed": torch.randn(1, 4, generator=g)}
+prompt = functools.partial(kit.host_prompt, dims=(8, 4))
 
 
 @pytest.fixture()
@@ -310,18 +299,7 @@ def test_cli_flags_reach_the_pipeline_keywords():
 # ------------------------------------------------------------------------------------------ ABI
 def test_header_binding_and_library_agree_on_the_new_entries(built_lib):
     from kandinsky import _engine as E
-    hdr = open(os.path.join(ROOT, "include", "k5.h")).read()
-    assert int(re.search(r"#define K5_ABI_VERSION (\d+)", hdr).group(1)) == 11 == E.ABI_VERSION
-    lib = C.CDLL(built_lib)
-    assert lib.k5_abi_version() == 11
-    for name in ("k5_cfg_euler_windows", "k5_sample_windows"):
-        assert re.search(r"\b%s\s*\(" % name, re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)), name
-        assert name in E.SYMBOLS and hasattr(lib, name)
-    # the struct of the binding has the header's fields in the header's order
-    body = re.search(r"typedef struct k5_sample_windows_args \{(.*?)\} k5_sample_windows_args;", hdr, flags=re.S).group(1)
-    fields = [re.search(r"(\w+)\s*$", decl.strip()).group(1) for decl in re.sub(r"/\*.*?\*/", "", body, flags=re.S).replace(",", ";").split(";")
-              if decl.strip()]
-    assert fields == [f[0] for f in E.SampleWindowsArgs._fields_]
+    assert_abi_entries(built_lib, ("k5_cfg_euler_windows", "k5_sample_windows"), [("k5_sample_windows_args", E.SampleWindowsArgs)])
     assert C.sizeof(E.SampleWindowsArgs) == C.sizeof(E.SampleArgs) + 8 + 4 * C.sizeof(C.c_void_p)
 
 
